@@ -1,25 +1,33 @@
 #!/usr/bin/env python3
 """bench.py -- QPS of the distance + top-k hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1 without a launcher: this script starts N child ranks itself, before anything touches the GPU;
    under `python -m torch.distributed.run --nproc-per-node N ...` it is one of the ranks.)
 
 A *step* is one pass of the hot path over one batch of 32 synthetic queries that are already
 resident in HBM: exact brute force, k = 5, against the synthetic SIFT-1M base (1 000 000 x 128 fp32,
 generator of SURVEY.md 8d, seeds 20251205 / 20251206).  `value` = queries / second of the whole job.
-The timed region of exactly K steps is repeated `--repeats` times (barrier + synchronize on both
-sides, max over ranks each time); `value` / `ms_per_step` are the median region.
+The timed region is exactly K steps (barrier + synchronize on both sides, max over ranks) after W
+warm-up steps, continued until half a second has passed (clocks ramp); `ms_per_step` = region / K.
+`--repeats R` times R regions of K steps and reports the median one (0 = as many as fit a quarter of
+a second).
 
 N = 1  : config "SIFT-1M brute-force batch=32 on 1xMI355X" (BASELINE.json configs[2]).
 N > 1  : the same base row-sharded over the ranks (strong scaling); every rank scans its shard for
          the same queries, the per-shard top-(k+1) lists are exchanged with ONE RCCL all-gather per
          group of `--coll-every` steps and merged on the device (the only collective the path has).
-Extras on the same JSON line: "ivf" (nlist=1024 nprobe=32, configs[3]/[4]), "ivf_nprobe8", "bf_int8", "q8_runner",
+
+A plain run does only that: set up, warm up, time the K steps, write the outputs if asked and print
+the result line.  --dump-outputs DIR writes what the last timed step returned to its caller -- the
+[32 x (k+1)] ids and distances of its batch and the batch's tie flags -- as DIR/bf_ids.npy (float64),
+DIR/bf_dists.npy (float32) and DIR/bf_flags.npy (float64); the inputs depend on the arguments only.
+
+--full adds everything else, each leg timed in its own steady state after the headline.  Extras on
+the same JSON line: "ivf" (nlist=1024 nprobe=32, configs[3]/[4]), "ivf_nprobe8", "bf_int8", "q8_runner",
 "host_api" (vs_bf_search / vs_ivf_search on host buffers: upload, download and reference tie order
 inside the timed region -- SURVEY 8(d)'s QPS definition), "siftsmall_b1", "sift1m_b1" (configs[1]).
-
-The line also carries `roofline` (dominant kernel vs the HBM roof, timed with HIP events on the
+The line then also carries `roofline` (dominant kernel vs the HBM roof, timed with HIP events on the
 stream it runs on) and `cpu_baseline` (the oracle's restatement of cpu_baseline.cpp on this box's
 host cores, bounded sample, rank 0 at N = 1 only).
 """
@@ -87,10 +95,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=40)
-    ap.add_argument("--repeats", type=int, default=0,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region of K steps is repeated R times and the median is reported; 0 = as many as fit "
                          "a quarter of a second (at least 5, at most 200): a short region (K = 20 is under 2 ms) is at the mercy of "
-                         "clock ramps and launch jitter, many of them back to back are not")
+                         "clock ramps and launch jitter, many of them back to back are not.  Default: one region for the "
+                         "headline (exactly K timed steps), 0 for the timed legs of --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: int8 / q8 / IVF / host-API / B = 1 legs, the scan "
+                         "kernel's roofline and the CPU baseline (the --no-* options below thin this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned (ids, distances, tie flags) as DIR/*.npy")
     ap.add_argument("--coll-every", type=int, default=32,
                     help="batches per multi-batch call (and per all-gather + merge when N > 1)")
     ap.add_argument("--rows", type=int, default=N_BASE, help="base rows (default SIFT-1M)")
@@ -137,7 +151,10 @@ def main():
 
     n_rows = args.rows
     steps, warmup, S = max(1, args.steps), max(1, args.warmup), max(1, min(32, args.coll_every))
-    R = args.repeats  # 0 = chosen from the first region's length (the same on every rank: the time is the max over ranks)
+    # regions of the headline / of the --full legs; 0 = chosen from the first region's length (the same on every rank:
+    # the time is the max over ranks)
+    R = 1 if args.repeats is None else args.repeats
+    R_x = 0 if args.repeats is None else args.repeats
     K1 = K + 1
 
     # ---------------------------------------------------------------- data (synthetic, deterministic)
@@ -236,11 +253,28 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(step_fn, nsteps, nwarm, repeats=None):
-        """W warm-up steps, then R regions of exactly `nsteps` steps, each bracketed by barrier + synchronize, max over
-        ranks per region; returns the list of region times."""
+    warm_extra = [0]  # warm-up steps the last timed() call ran beyond nwarm
+
+    def timed(step_fn, nsteps, nwarm, repeats=None, warm_s=0.0):
+        """W warm-up steps (with warm_s > 0 followed by more, in calls of S steps, until warm_s seconds have passed: the
+        first few ms after a short warm-up run below full clocks), then R regions of exactly `nsteps` steps, each
+        bracketed by barrier + synchronize, max over ranks per region; returns the list of region times."""
+        t = time.perf_counter()
         for i in range(nwarm):
             step_fn(i, nwarm)
+        warm_extra[0] = 0
+        while warm_s > 0:
+            barrier()
+            done = time.perf_counter() - t >= warm_s
+            if dist is not None:  # every rank runs the same number of steps (the sharded calls are collective)
+                f = torch.tensor([1 if done else 0], dtype=torch.int32, device=dev)
+                dist.all_reduce(f, op=dist.ReduceOp.MIN)
+                done = bool(f.item())
+            if done:
+                break
+            for i in range(S):
+                step_fn(i, S)
+            warm_extra[0] += S
         out = []
         want = repeats if repeats is not None else R
         while True:
@@ -261,17 +295,25 @@ def main():
                 return out
 
     # ---------------------------------------------------------------- brute force fp32 (the headline)
-    bf.prof_enable(not args.no_prof)
-    regions = timed(bf_step, steps, warmup)
+    bf.prof_enable(args.full and not args.no_prof)
+    regions = timed(bf_step, steps, warmup, warm_s=0.5)
     kern_ms, kern_n = bf.prof_read(0)
     bf.prof_enable(False)
+    if args.dump_outputs and rank == 0:
+        # the last step's batch is the last of its group's batches in the multi-batch call's [gs * B x (k+1)] outputs
+        s_last = (steps - 1) % S
+        rows_last = slice(s_last * BATCH, (s_last + 1) * BATCH)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "bf_ids.npy"), out_i[rows_last].cpu().numpy().astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "bf_dists.npy"), out_d[rows_last].cpu().numpy().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "bf_flags.npy"), flags[rows_last].cpu().numpy().astype(np.float64))
     elapsed = median(regions)
     qps = steps * BATCH / elapsed
     ms_per_step = elapsed / steps * 1e3
-    # the prof window covers every launch of the warm-up and of the R regions = warmup + R * steps batches (the last
+    # the prof window covers every launch of the warm-up and of the R regions = warmup + extra + R * steps batches (the last
     # launch of a run may hold fewer than S batches): time per batch, scaled to a launch of S batches
     R_used = len(regions)
-    n_batches_prof = warmup + R_used * steps
+    n_batches_prof = warmup + warm_extra[0] + R_used * steps
     kern_per_batch_s = (kern_ms * 1e-3) / n_batches_prof if kern_n else 0.0
     kern_avg_s = kern_per_batch_s * S
     rows_local = r1 - r0
@@ -295,8 +337,9 @@ def main():
         except Exception:
             traffic = None
     log(f"brute force: {qps:.0f} QPS, {ms_per_step * 1e3:.1f} us/step (median of {R_used} regions, min "
-        f"{min(regions) / steps * 1e6:.1f} max {max(regions) / steps * 1e6:.1f}), scan kernel {kern_per_batch_s * 1e6:.1f} us/batch "
-        f"({mfma_tflops:.1f} TFLOP/s fp32 MFMA, {achieved:.0f} GB/s of SURVEY 8(d) bytes, {2 if pair else 1} batch(es) per pass)")
+        f"{min(regions) / steps * 1e6:.1f} max {max(regions) / steps * 1e6:.1f})" +
+        (f", scan kernel {kern_per_batch_s * 1e6:.1f} us/batch ({mfma_tflops:.1f} TFLOP/s fp32 MFMA, {achieved:.0f} GB/s of "
+         f"SURVEY 8(d) bytes, {2 if pair else 1} batch(es) per pass)" if args.full else ""))
 
     # exactness guard on what was just timed: ascending, finite, ids in range
     torch.cuda.synchronize()
@@ -306,7 +349,7 @@ def main():
 
     # ---------------------------------------------------------------- int8 extra
     int8_info = None
-    if not args.no_int8:
+    if args.full and not args.no_int8:
         try:
             bf.set_precision(2)
         except pkg.VSearchError:
@@ -316,7 +359,7 @@ def main():
             # says for the headline (20 batches are 5 passes of 4: the 8 waves of a workgroup cannot share them evenly)
             steps8 = max(steps, S) if world == 1 else steps
             bf.prof_enable(not args.no_prof)
-            reg8 = timed(bf_step, steps8, warmup)
+            reg8 = timed(bf_step, steps8, warmup, repeats=R_x)
             k8_ms, k8_n = bf.prof_read(0)
             bf.prof_enable(False)
             torch.cuda.synchronize()
@@ -352,7 +395,7 @@ def main():
 
     # ---------------------------------------------------------------- host-buffer API (SURVEY 8(d)'s QPS definition)
     host_info = None
-    if world == 1 and not args.no_extras and not args.only_b1:
+    if args.full and world == 1 and not args.no_extras and not args.only_b1:
         nq_h = n_queries
         tm = pkg.Timing()
         bf.search(queries[:nq_h], K)  # pinned staging + tie scratch allocated here, not in the timed calls
@@ -370,7 +413,7 @@ def main():
 
     # ---------------------------------------------------------------- B = 1 legs (BASELINE.json configs[1])
     b1_info = {}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         o1_d = torch.zeros((32, K1), dtype=torch.float32, device=dev)
         o1_i = torch.zeros((32, K1), dtype=torch.int32, device=dev)
         f1 = torch.zeros((32,), dtype=torch.int32, device=dev)
@@ -432,7 +475,7 @@ def main():
 
     # ---------------------------------------------------------------- UFIXED_POINT_8 score path (second half)
     q8_info = None
-    if world == 1 and not args.no_extras and not args.only_b1:
+    if args.full and world == 1 and not args.no_extras and not args.only_b1:
         try:
             in_s = float(queries.max()) / 255.0
             w_s = float(shard.max()) / 255.0
@@ -501,7 +544,7 @@ def main():
     # ---------------------------------------------------------------- IVF extras
     ivf_info = None
     ivf8_info = None
-    if not args.no_ivf:
+    if args.full and not args.no_ivf:
         # (an extra: whatever goes wrong in it must not cost the headline line below)
         try:
             t0 = time.time()
@@ -559,7 +602,7 @@ def main():
                 # 640 queries at a time gets about half the rate)
                 isteps = max(steps, SI)
                 index.prof_enable(True)
-                ireg = timed(ivf_step, isteps, max(warmup, SI))
+                ireg = timed(ivf_step, isteps, max(warmup, SI), repeats=R_x)
                 okern_ms, okern_n = index.prof_read(1)
                 index.prof_enable(False)
                 iel = median(ireg)
@@ -772,7 +815,7 @@ def main():
                     all_gather(all_i.view(torch.float32), rep_i.view(-1).view(torch.float32))
                     all_gather(all_d, rep_d.view(-1))
 
-                rreg = timed(rep_step, steps, warmup)
+                rreg = timed(rep_step, steps, warmup, repeats=R_x)
                 ivf_info["replicas"] = {"metric": "ivf_qps, every rank holds the whole index and serves steps / N batches (results all-gathered)",
                                         "value": round(steps * BATCH / median(rreg), 1), "nprobe": NPROBE, "n_gpus": world}
                 log(f"IVF nprobe={NPROBE}, replicas: {ivf_info['replicas']['value']:.0f} QPS on {world} GPUs")
@@ -806,7 +849,7 @@ def main():
 
     # ---------------------------------------------------------------- CPU baseline (rank 0, N = 1)
     cpu_info = None
-    if world == 1 and rank == 0 and not args.no_cpu:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu:
         import oracle
         oracle.search_bf(shard, queries[:2], K)  # thread pool + page-in warm-up
         # bounded sample: chunks of 128 queries until ~15 s of CPU work (or 2048 queries) are done
@@ -868,7 +911,7 @@ def main():
                           "kernel_us_per_batch": round(kern_per_batch_s * 1e6, 2),
                           "algorithmic_bytes_per_launch": algo_bytes,
                           "batches_per_launch": S, "batches_per_pass": 1,
-                          "mfma_tflops": round(mfma_tflops, 2)}),
+                          "mfma_tflops": round(mfma_tflops, 2)}) if args.full else None,
             "cpu_baseline": cpu_info,
             "ivf": ivf_info,
             "ivf_nprobe8": ivf8_info,

@@ -120,11 +120,9 @@ def _worker(rank, world, port, mode, out_dir):
 
 
 @pytest.mark.parametrize("mode", ["rows", "lists", "sliced"])
-def test_two_rank_gloo_shards_merge_to_unsharded(mode, tmp_path):
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as ge
+def test_two_rank_gloo_shards_merge_to_unsharded(mode, tmp_path, pkg):
+    # (the pkg fixture builds the library if it is missing: the spawned ranks load it)
     import oracle
-    pkg = ge.load_package()
     world = 2
     mp.spawn(_worker, args=(world, _free_port(), mode, str(tmp_path)), nprocs=world, join=True)
     z = np.load(tmp_path / f"{mode}.npz")
@@ -157,10 +155,7 @@ def test_two_rank_gloo_shards_merge_to_unsharded(mode, tmp_path):
             assert sorted(z["i"][q].tolist()) == sorted(ids[q].tolist())
 
 
-def test_shard_bookkeeping(pkg=None):
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
+def test_shard_bookkeeping(pkg):
     for world in (1, 2, 3, 8):
         b = pkg.row_shard_bounds(1_000_000, world)
         assert b[0] == 0 and b[-1] == 1_000_000 and np.all(np.diff(b) > 0) and np.all(b[1:-1] % 16 == 0)
