@@ -22,6 +22,7 @@
 #include "../../include/vsearch.h"
 #include "vs_host.h"
 #include "vs_kernels.h"
+#include "vs_res.h"
 
 using vs::set_error;
 
@@ -58,7 +59,7 @@ constexpr int kTieDense = 4096;   // rows whose distances the tie resolver takes
 constexpr int kTieCap = 8192;     // candidate slots per flagged query (more: full-row fallback)
 
 struct ProfSlot {
-    std::vector<hipEvent_t> ev;  // pairs
+    std::vector<vs::Event> ev;  // pairs
     int used = 0;
 };
 
@@ -80,79 +81,81 @@ struct vs_index {
     int batch = vs::kMaxBatch;
     int num_cus = 256;
 
-    float* d_vecs = nullptr;   // [n_rows][128]
-    float* d_norm = nullptr;   // [n_rows + 64]
+    vs::DevBuf<float> d_vecs;   // [n_rows][128]
+    vs::DevBuf<float> d_norm;   // [n_rows + 64]
     // int8 data path: only when every base value is an integer in [0, 255]
-    int8_t* d_vecs_u8 = nullptr;   // [n_rows][128] bytes (x - 128)
-    int32_t* d_rterm = nullptr;    // [n_rows + 64] ||b||^2 - 256 * sum(b - 128)
+    vs::DevBuf<int8_t> d_vecs_u8;   // [n_rows][128] bytes (x - 128)
+    vs::DevBuf<int32_t> d_rterm;    // [n_rows + 64] ||b||^2 - 256 * sum(b - 128)
     // the seed's sample tiles, compact and in MFMA fragment order (SeedParams::sample_*; brute-force indexes)
-    float* d_seed_f32 = nullptr;
-    float* d_seed_bnorm = nullptr;
-    int8_t* d_seed_u8 = nullptr;
-    int32_t* d_seed_rterm = nullptr;
+    vs::DevBuf<float> d_seed_f32;
+    vs::DevBuf<float> d_seed_bnorm;
+    vs::DevBuf<int8_t> d_seed_u8;
+    vs::DevBuf<int32_t> d_seed_rterm;
     // wide IVF scan: the byte rows once more, every list padded to a multiple of 32 rows ("padded rows") and stored as
     // 16-row MFMA tiles of 2 KB, [half of the row][16-byte chunk][row][16 bytes] -- a wave's A-operand load is then 1 KB
     // of consecutive bytes (from the row-major copy the same load touches 16 B in each of 64 places)
-    int8_t* d_vecs_t8 = nullptr;   // [n_padded + 64 rows]
-    int32_t* d_nrh_t = nullptr;    // [n_padded + 64] -(rterm >> 1) by padded row: the MFMA C operand
-    int32_t* d_rterm_t = nullptr;  // [n_padded + 64]
-    int32_t* d_r2o_t = nullptr;    // [n_padded + 64] padded row -> original id (-1: padding)
-    int32_t* d_tdelta = nullptr;   // [nlist] padded row - row, per list
-    int32_t* d_chunk_trow0 = nullptr;  // [n_chunks] first padded row of a chunk
-    int32_t* d_invalid = nullptr;  // [kMaxMulti] batches the int8 scan had to skip
+    vs::DevBuf<int8_t> d_vecs_t8;   // [n_padded + 64 rows]
+    vs::DevBuf<int32_t> d_nrh_t;    // [n_padded + 64] -(rterm >> 1) by padded row: the MFMA C operand
+    vs::DevBuf<int32_t> d_rterm_t;  // [n_padded + 64]
+    vs::DevBuf<int32_t> d_r2o_t;    // [n_padded + 64] padded row -> original id (-1: padding)
+    vs::DevBuf<int32_t> d_tdelta;   // [nlist] padded row - row, per list
+    vs::DevBuf<int32_t> d_chunk_trow0;  // [n_chunks] first padded row of a chunk
+    vs::DevBuf<int32_t> d_invalid;  // [kMaxMulti] batches the int8 scan had to skip
     int precision = 0;             // 0 = auto (int8 when possible), 1 = fp32, 2 = int8
 
     // IVF
     int nlist = 0;
     int rank = 0, world = 1;
-    float* d_centroids = nullptr;  // [nlist][128]
-    float* d_cnorm = nullptr;      // [nlist + 16]
-    int32_t* d_offsets = nullptr;  // [nlist + 1] offsets into the LOCAL d_vecs (non-owned lists are empty)
-    int32_t* d_r2o = nullptr;      // [n_rows] local position -> original id
+    vs::DevBuf<float> d_centroids;  // [nlist][128]
+    vs::DevBuf<float> d_cnorm;      // [nlist + 16]
+    vs::DevBuf<int32_t> d_offsets;  // [nlist + 1] offsets into the LOCAL d_vecs (non-owned lists are empty)
+    vs::DevBuf<int32_t> d_r2o;      // [n_rows] local position -> original id
     std::vector<int32_t> h_offsets_global;  // as loaded (for save / stats)
     double avg_cluster_size = 0;
 
     // scratch
-    float* d_q = nullptr;        // staging for host queries [32][128]
+    vs::DevBuf<float> d_q;        // staging for host queries [32][128]
     // Pipeline lanes: consecutive batches of a multi-batch call run on different internal streams
     // so that the start-up / tail of one scan overlaps the streaming phase of its neighbours
     // (inside one launch all workgroups go through those phases in lock-step and HBM idles).
     struct Lane {
-        hipStream_t s = nullptr;
-        hipEvent_t done_ev = nullptr;
-        float* slots = nullptr;     // [kMaxMulti][32][kSlotStride] threshold-exchange slots, reset per launch
-        int* done = nullptr;        // [kMaxMulti] arrival counters, reset per launch
-        float* part_d = nullptr;    // [kMaxMulti][32][kSlotStride][16]
-        int32_t* part_i = nullptr;
-        float* seed_qnorm = nullptr; // [kMaxMulti][32]   scratch of launch_seed
-        float* qfrag = nullptr;      // [kMaxMulti][2][8][64][4] queries in MFMA B-fragment order (fp32 streaming scan)
-        int8_t* q8frag = nullptr;    // [kMaxMulti][2][2][64][16] byte queries in B-fragment order (wide int8 scan)
-        float* seed_wmin = nullptr;  // [kMaxMulti][kSeedWaves][32]
-        float* tau0 = nullptr;       // [kMaxMulti][32]   bounds of the current multi-batch launch
-        // wide int8 scan (several batches per pass over the rows): prepared queries + per-query candidate lists
-        int8_t* q8 = nullptr;        // [kMaxMulti][32][128]
-        int32_t* qterm = nullptr;    // [kMaxMulti][32]
-        int32_t* wcnt = nullptr;     // [16] (word 0: overflow) + [kMaxMulti][32][kWideSub]
-        float* wcand_d = nullptr;    // [kMaxMulti][32][kWideCap]
-        int32_t* wcand_i = nullptr;
-        int4* wbuf = nullptr;        // [256 * 8][kWideWaveCap] wave-private candidate buffers of the scan
+        vs::Stream s;
+        vs::Event done_ev;
+        vs::DevBuf<float> slots;     // [kMaxMulti][32][kSlotStride] threshold-exchange slots, reset per launch
+        vs::DevBuf<int> done;        // [kMaxMulti] arrival counters, reset per launch
+        vs::DevBuf<float> part_d;    // [kMaxMulti][32][kSlotStride][16]
+        vs::DevBuf<int32_t> part_i;
+        vs::DevBuf<float> seed_qnorm; // [kMaxMulti][32]   scratch of launch_seed
+        vs::DevBuf<float> qfrag;      // [kMaxMulti][2][8][64][4] queries in MFMA B-fragment order (fp32 streaming scan)
+        vs::DevBuf<int8_t> q8frag;    // [kMaxMulti][2][2][64][16] byte queries in B-fragment order (wide int8 scan)
+        vs::DevBuf<float> seed_wmin;  // [kMaxMulti][kSeedWaves][32]
+        vs::DevBuf<float> tau0;       // [kMaxMulti][32]   bounds of the current multi-batch launch
+        // wide int8 scan (several batches per pass over the rows): prepared queries + per-query candidate lists (ensure_wide)
+        struct Wide8 {
+            vs::DevBuf<int8_t> q8;        // [kMaxMulti][32][128]
+            vs::DevBuf<int32_t> qterm;    // [kMaxMulti][32]
+            vs::DevBuf<int32_t> wcnt;     // [16] (word 0: overflow) + [kMaxMulti][32][kWideSub]
+            vs::DevBuf<float> wcand_d;    // [kMaxMulti][32][kWideCap]
+            vs::DevBuf<int32_t> wcand_i;
+            vs::DevBuf<int4> wbuf;        // [256 * 8][kWideWaveCap] wave-private candidate buffers of the scan
+            bool ready = false;           // every buffer above allocated
+        } wide8;
     };
     Lane lane[kMaxLanes];
     int n_lanes = 1;
-    hipEvent_t fork = nullptr;
-    float* d_out_d = nullptr;    // [32][64]
-    int32_t* d_out_i = nullptr;
-    int32_t* d_flags = nullptr;  // [32]
-    float* d_scores = nullptr;   // IVF query-major fallback: coarse scores [32][nlist_pad]; tie fallback rows
-    int64_t scores_cap = 0;      // floats
-    int32_t* d_probes = nullptr; // [32][kMaxNprobe]
-    float* d_ipart_d = nullptr;  // [32][kMaxNprobe][16]
-    int32_t* d_ipart_i = nullptr;
-    unsigned long long* d_cand = nullptr;
+    vs::Event fork;
+    vs::DevBuf<float> d_out_d;    // [32][64]
+    vs::DevBuf<int32_t> d_out_i;
+    vs::DevBuf<int32_t> d_flags;  // [32]
+    vs::DevBuf<float> d_scores;   // IVF query-major fallback: coarse scores [32][nlist_pad]; tie fallback rows
+    vs::DevBuf<int32_t> d_probes; // [32][kMaxNprobe]
+    vs::DevBuf<float> d_ipart_d;  // [32][kMaxNprobe][16]
+    vs::DevBuf<int32_t> d_ipart_i;
+    vs::DevBuf<unsigned long long> d_cand;
     // list-major IVF scan (grouped path)
-    int32_t* d_chunk_list = nullptr;   // [n_chunks] (list, 1024-row chunk) work items over the resident lists
-    int32_t* d_chunk_row0 = nullptr;
-    int32_t* d_chunk_rows = nullptr;
+    vs::DevBuf<int32_t> d_chunk_list;   // [n_chunks] (list, 1024-row chunk) work items over the resident lists
+    vs::DevBuf<int32_t> d_chunk_row0;
+    vs::DevBuf<int32_t> d_chunk_rows;
     int ivf_gb = 32;                   // batches per launch group (multiple of 32) the wide pipeline's scratch is sized for
     int ivf_nsb = 1;                   // ... in at most this many super-batches (sharded: one per rank)
     int ivf_lanes = 2;                 // streams the launch groups of one device call are dealt to
@@ -160,45 +163,44 @@ struct vs_index {
     // sharded index: the first kIvfTauRows rows of EVERY list (resident or not), replicated on every rank: a query's bound
     // then comes from its two nearest lists wherever they live -- the bounds of the unsharded index (a bound from the
     // nearest RESIDENT lists of an eighth of the lists let ten times the candidates through)
-    float* d_head_vecs = nullptr;      // [head rows + 64][128], lists packed
-    float* d_head_norm = nullptr;      // [head rows + 64]
-    int32_t* d_head_off = nullptr;     // [nlist + 1]
-    int8_t* d_head_t8 = nullptr;       // byte-valued heads: 16-row tiles, every list padded to a multiple of 16 rows
-    int32_t* d_head_rterm_t = nullptr;
-    int32_t* d_head_tdelta = nullptr;  // [nlist] padded row - row
-    int32_t* d_sh = nullptr;           // sharded brute force, host-buffer calls: the gathered scratch of the owner (see ShBuf)
-    size_t sh_words = 0;
-    float* d_sh_row = nullptr;         // ... and full distance rows (tie fallback)
-    size_t sh_row_words = 0;
-    int32_t* vsh_blk = nullptr;        // virtual ranks (vs_ivf_search_dev_vshards): the gathered blocks / top-k lists, owned by shard 0
-    int32_t* vsh_loc = nullptr;
-    size_t vsh_loc_words = 0;
+    vs::DevBuf<float> d_head_vecs;      // [head rows + 64][128], lists packed
+    vs::DevBuf<float> d_head_norm;      // [head rows + 64]
+    vs::DevBuf<int32_t> d_head_off;     // [nlist + 1]
+    vs::DevBuf<int8_t> d_head_t8;       // byte-valued heads: 16-row tiles, every list padded to a multiple of 16 rows
+    vs::DevBuf<int32_t> d_head_rterm_t;
+    vs::DevBuf<int32_t> d_head_tdelta;  // [nlist] padded row - row
+    vs::DevBuf<int32_t> d_sh;           // sharded brute force, host-buffer calls: the gathered scratch of the owner (see ShBuf)
+    vs::DevBuf<float> d_sh_row;         // ... and full distance rows (tie fallback)
+    vs::DevBuf<int32_t> vsh_blk;        // virtual ranks (vs_ivf_search_dev_vshards): the gathered blocks / top-k lists, owned by shard 0
+    vs::DevBuf<int32_t> vsh_loc;
     // wide IVF pipeline (a launch group of up to 32 batches shares one list-major pass): slot tables, zeroed counters,
     // plans, bounds, prepared queries, candidate sink
     struct IvfWide {
-        int32_t* lq = nullptr;      // [ivf_nsb][nlist][kIvfWideQ]
-        int32_t* zero = nullptr;    // one zeroed block per launch group (see wide_zero)
+        vs::DevBuf<int32_t> lq;      // [ivf_nsb][nlist][kIvfWideQ]
+        vs::DevBuf<int32_t> zero;    // one zeroed block per launch group (see wide_zero)
         size_t zero_words = 0;
-        int32_t* units = nullptr;   // [n_sb_max][units_cap][4]
+        vs::DevBuf<int32_t> units;   // [n_sb_max][units_cap][4]
         int units_cap = 0;
-        float* tau = nullptr;       // [1024]
-        int32_t* tq = nullptr;      // [nlist][group queries] bound tables (ivf_bounds_list_body)
-        float* tk = nullptr;        // [group queries][kBoundSegs][16]
-        int32_t* nseg = nullptr;    // [group queries]
-        float* qnorm = nullptr;     // [1024]
-        int8_t* q8 = nullptr;       // [1024][128]
-        int32_t* qterm = nullptr;   // [1024]
-        int4* wbuf = nullptr;       // [waves][kIvfWideWaveCap]
+        vs::DevBuf<float> tau;       // [1024]
+        vs::DevBuf<int32_t> tq;      // [nlist][group queries] bound tables (ivf_bounds_list_body)
+        vs::DevBuf<float> tk;        // [group queries][kBoundSegs][16]
+        vs::DevBuf<int32_t> nseg;    // [group queries]
+        vs::DevBuf<float> qnorm;     // [1024]
+        vs::DevBuf<int8_t> q8;       // [1024][128]
+        vs::DevBuf<int32_t> qterm;   // [1024]
+        vs::DevBuf<int4> wbuf;       // [waves][kIvfWideWaveCap]
         int n_waves = 0;
-        float* cand_d = nullptr;    // [1024][16][kIvfWideSubCap]
-        int32_t* rank_list = nullptr;   // groups of more than 2048 queries: [0] count, [1..] the queries the wave-per-query ranking left over
-        int32_t* cand_i = nullptr;
+        vs::DevBuf<float> cand_d;    // [1024][16][kIvfWideSubCap]
+        vs::DevBuf<int32_t> rank_list;   // groups of more than 2048 queries: [0] count, [1..] the queries the wave-per-query ranking left over
+        vs::DevBuf<int32_t> cand_i;
         bool dirty = false;         // the zeroed block may hold a failed call's counts: memset before the next group
-        char* slab = nullptr;       // per batch: probes [32][kMaxNprobe] | coarse scores [32][nlist padded]
+        vs::DevBuf<char> slab;       // per batch: probes [32][kMaxNprobe] | coarse scores [32][nlist padded]
         long long slab_stride = 0, off_scores = 0;
+        bool ready = false;         // every buffer above allocated (ensure_ivf_wide)
     } wide[kWideLanesMax];          // scratch sets: consecutive launch groups of one call run on different streams
-    hipStream_t wide_stream[kWideLanesMax] = {};
-    hipEvent_t wide_fork = nullptr, wide_join[kWideLanesMax] = {};
+    vs::Stream wide_stream[kWideLanesMax];
+    vs::Event wide_fork, wide_join[kWideLanesMax];
+    bool wide_streams_ready = false;
     int64_t n_units_max = 0;
     int n_chunks = 0;
     int32_t max_list = 0;              // longest resident list
@@ -208,42 +210,50 @@ struct vs_index {
     // host-buffer API (vs_bf_search / vs_ivf_search): two slots of pinned staging + device I/O buffers, so that chunk
     // c + 1's query upload and chunk c - 1's result download run beside chunk c's kernels (copy streams + events)
     struct PipeSlot {
-        float* pin_q = nullptr;    // [kMaxMulti * 32][128]
-        char* pin_out = nullptr;   // dists | ids | flags of one chunk
+        vs::PinBuf<float> pin_q;   // [kMaxMulti * 32][128]
+        vs::PinBuf<char> pin_out;  // dists | ids | flags of one chunk
+        // device I/O: views of the index's d_q / d_out_* / d_flags (slot 0) or of the own_* buffers (slot 1)
         float* d_q = nullptr;
         float* d_out_d = nullptr;  // [kMaxMulti * 32][64]
         int32_t* d_out_i = nullptr;
         int32_t* d_flags = nullptr;
-        hipEvent_t ev_h2d = nullptr, ev_comp = nullptr, ev_d2h = nullptr;
+        vs::DevBuf<float> own_q, own_out_d;
+        vs::DevBuf<int32_t> own_out_i, own_flags;
+        vs::Event ev_h2d, ev_comp, ev_d2h;
         int64_t q0 = -1, n = 0;    // the chunk in flight in this slot (q0 < 0: free)
     } pipe[2];
-    hipStream_t s_h2d = nullptr, s_d2h = nullptr;
+    vs::Stream s_h2d, s_d2h;
+    bool pipe_ready = false;       // both slots and the copy streams set up (ensure_pipe)
     // vs_ivf_search through the wide pipeline: larger chunks (up to kIvfHostGroups launch groups each, dealt to the two
     // lanes), ONE upload and ONE download per chunk -- every hipMemcpyAsync costs the host tens of microseconds
     struct IvfHostSlot {
-        float* pin_q = nullptr;   // [kIvfHostChunk][128]
-        float* pin_out = nullptr; // dists [n][k] | ids [n][k] of one chunk
-        float* d_q = nullptr;
-        float* d_out = nullptr;   // same layout on the device
-        hipEvent_t ev_h2d = nullptr, ev_comp[2] = {nullptr, nullptr}, ev_d2h = nullptr;
+        vs::PinBuf<float> pin_q;   // [kIvfHostChunk][128]
+        vs::PinBuf<float> pin_out; // dists [n][k] | ids [n][k] of one chunk
+        vs::DevBuf<float> d_q;
+        vs::DevBuf<float> d_out;   // same layout on the device
+        vs::Event ev_h2d, ev_comp[2], ev_d2h;
         int64_t q0 = -1, n = 0;
+        bool ready = false;        // every buffer and event above created (ensure_ivf_host)
     } ihs[2];
     // tie resolver (flagged queries of vs_bf_search): distances to the first kTieDense rows, bound, filtered candidates
-    float* d_tie_dense = nullptr;  // [32][kTieDense]
-    char* pin_tie = nullptr;       // pinned staging of the tie resolver: dense [32][kTieDense] f32 | cnt [32] | rows [32][kTieCap] | dists [32][kTieCap]
-    float* d_tie_tau = nullptr;    // [32]
-    int32_t* d_tie_cnt = nullptr;  // [32]
-    int32_t* d_tie_row = nullptr;  // [32][kTieCap]
-    float* d_tie_d = nullptr;      // [32][kTieCap]
+    struct Tie {
+        vs::DevBuf<float> dense;  // [32][kTieDense]
+        vs::PinBuf<char> pin;     // pinned staging: dense [32][kTieDense] f32 | cnt [32] | rows [32][kTieCap] | dists [32][kTieCap]
+        vs::DevBuf<float> tau;    // [32]
+        vs::DevBuf<int32_t> cnt;  // [32]
+        vs::DevBuf<int32_t> row;  // [32][kTieCap]
+        vs::DevBuf<float> d;      // [32][kTieCap]
+        bool ready = false;       // every buffer above allocated
+    } tie;
 
     // SearchTiming split of vs_ivf_search (IVFIndex.h:31-36): HIP events between the stages of every launch group
-    std::vector<hipEvent_t> stage_ev;  // quadruples: start, after coarse + pick, after grouping, after scan + select
+    std::vector<vs::Event> stage_ev;  // quadruples: start, after coarse + pick, after grouping, after scan + select
     int stage_used = 0;
     bool stage_on = false;
     double stage_ms[3] = {0, 0, 0};
 
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_busy = nullptr;  // a call on another stream than the previous call's waits for that stream through this event
+    vs::Stream stream;
+    vs::Event ev_busy;  // a call on another stream than the previous call's waits for that stream through this event
     hipStream_t last_stream = nullptr;
     bool have_last = false;
     bool prof = false;
@@ -255,87 +265,6 @@ namespace {
 int set_device(const vs_index* h) {
     HIPCHK(hipSetDevice(h->device));
     return VS_OK;
-}
-
-template <typename T>
-int dev_alloc(T** p, size_t n) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T)));
-    return VS_OK;
-}
-
-void free_all(vs_index* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    for (auto& L : h->lane) {
-        if (L.slots) (void)hipFree(L.slots);
-        if (L.done) (void)hipFree(L.done);
-        if (L.part_d) (void)hipFree(L.part_d);
-        if (L.part_i) (void)hipFree(L.part_i);
-        if (L.seed_qnorm) (void)hipFree(L.seed_qnorm);
-        if (L.qfrag) (void)hipFree(L.qfrag);
-        if (L.q8frag) (void)hipFree(L.q8frag);
-        if (L.seed_wmin) (void)hipFree(L.seed_wmin);
-        if (L.tau0) (void)hipFree(L.tau0);
-        void* wide[] = {L.q8, L.qterm, L.wcnt, L.wcand_d, L.wcand_i, L.wbuf};
-        for (void* w : wide)
-            if (w) (void)hipFree(w);
-        if (L.done_ev) (void)hipEventDestroy(L.done_ev);
-        if (L.s) (void)hipStreamDestroy(L.s);
-    }
-    if (h->fork) (void)hipEventDestroy(h->fork);
-    void* ptrs[] = {h->d_vecs, h->d_norm, h->d_vecs_u8, h->d_rterm, h->d_seed_f32, h->d_seed_bnorm, h->d_seed_u8, h->d_seed_rterm, h->d_vecs_t8, h->d_nrh_t, h->d_rterm_t, h->d_r2o_t, h->d_tdelta, h->d_chunk_trow0, h->d_invalid, h->d_centroids, h->d_cnorm, h->d_offsets, h->d_r2o, h->d_q,
-                    h->d_out_d, h->d_out_i,
-                    h->d_flags, h->d_scores, h->d_probes, h->d_ipart_d, h->d_ipart_i, h->d_cand,
-                    h->d_chunk_list, h->d_chunk_row0, h->d_chunk_rows, h->vsh_blk, h->vsh_loc,
-                    h->d_head_vecs, h->d_head_norm, h->d_head_off, h->d_head_t8, h->d_head_rterm_t, h->d_head_tdelta, h->d_sh, h->d_sh_row};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    {
-        for (auto& W : h->wide) {
-            void* wd[] = {W.lq, W.zero, W.units, W.tau, W.qnorm, W.q8, W.qterm, W.wbuf, W.cand_d, W.cand_i, W.slab, W.rank_list};
-            for (void* w : wd)
-                if (w) (void)hipFree(w);
-        }
-        for (int i = 0; i < kWideLanesMax; ++i) {
-            if (h->wide_stream[i]) (void)hipStreamDestroy(h->wide_stream[i]);
-            if (h->wide_join[i]) (void)hipEventDestroy(h->wide_join[i]);
-        }
-        if (h->wide_fork) (void)hipEventDestroy(h->wide_fork);
-    }
-    for (auto& S : h->ihs) {
-        if (S.pin_q) (void)hipHostFree(S.pin_q);
-        if (S.pin_out) (void)hipHostFree(S.pin_out);
-        if (S.d_q) (void)hipFree(S.d_q);
-        if (S.d_out) (void)hipFree(S.d_out);
-        hipEvent_t evs[] = {S.ev_h2d, S.ev_comp[0], S.ev_comp[1], S.ev_d2h};
-        for (hipEvent_t e : evs)
-            if (e) (void)hipEventDestroy(e);
-    }
-    for (auto& ps : h->prof_slot)
-        for (auto e : ps.ev) (void)hipEventDestroy(e);
-    for (auto e : h->stage_ev) (void)hipEventDestroy(e);
-    for (int i = 0; i < 2; ++i) {
-        vs_index::PipeSlot& S = h->pipe[i];
-        if (S.pin_q) (void)hipHostFree(S.pin_q);
-        if (S.pin_out) (void)hipHostFree(S.pin_out);
-        if (i > 0) {  // slot 0 aliases d_q / d_out_* / d_flags, freed above
-            void* dp[] = {S.d_q, S.d_out_d, S.d_out_i, S.d_flags};
-            for (void* q : dp)
-                if (q) (void)hipFree(q);
-        }
-        hipEvent_t evs[] = {S.ev_h2d, S.ev_comp, S.ev_d2h};
-        for (hipEvent_t e : evs)
-            if (e) (void)hipEventDestroy(e);
-    }
-    if (h->pin_tie) (void)hipHostFree(h->pin_tie);
-    void* tie[] = {h->d_tie_dense, h->d_tie_tau, h->d_tie_cnt, h->d_tie_row, h->d_tie_d};
-    for (void* q : tie)
-        if (q) (void)hipFree(q);
-    if (h->s_h2d) (void)hipStreamDestroy(h->s_h2d);
-    if (h->s_d2h) (void)hipStreamDestroy(h->s_d2h);
-    if (h->ev_busy) (void)hipEventDestroy(h->ev_busy);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
 }
 
 int check_device(int device) {
@@ -368,11 +297,10 @@ void scan_geometry(int64_t rows, int num_cus, int& grid, int& tiles_per_wg, int 
 // scratch of the query-major IVF fallback (one batch at a time)
 int alloc_ivf_scratch(vs_index* h) {
     int rc;
-    h->scores_cap = (int64_t)32 * ((h->nlist + 63) & ~63);
-    if ((rc = dev_alloc(&h->d_scores, (size_t)h->scores_cap))) return rc;
-    if ((rc = dev_alloc(&h->d_probes, 32 * kMaxNprobe))) return rc;
-    if ((rc = dev_alloc(&h->d_ipart_d, (size_t)32 * kMaxNprobe * kKcapMax))) return rc;
-    if ((rc = dev_alloc(&h->d_ipart_i, (size_t)32 * kMaxNprobe * kKcapMax))) return rc;
+    if ((rc = h->d_scores.alloc((size_t)32 * ((h->nlist + 63) & ~63)))) return rc;
+    if ((rc = h->d_probes.alloc(32 * kMaxNprobe))) return rc;
+    if ((rc = h->d_ipart_d.alloc((size_t)32 * kMaxNprobe * kKcapMax))) return rc;
+    if ((rc = h->d_ipart_i.alloc((size_t)32 * kMaxNprobe * kKcapMax))) return rc;
     return VS_OK;
 }
 
@@ -385,7 +313,7 @@ int alloc_scratch(vs_index* h) {
     int tp;
     scan_geometry(std::max<int64_t>(h->n_rows, 1), h->num_cus, h->max_grid, tp);
     h->max_grid = std::max(h->max_grid, h->num_cus);
-    if ((rc = dev_alloc(&h->d_q, (size_t)kMaxMulti * 32 * vs::kDim))) return rc;
+    if ((rc = h->d_q.alloc((size_t)kMaxMulti * 32 * vs::kDim))) return rc;
     {
         const char* e = getenv("VSEARCH_LANES");
         h->n_lanes = e ? std::max(1, std::min(kMaxLanes, atoi(e))) : 1;
@@ -393,40 +321,38 @@ int alloc_scratch(vs_index* h) {
         const size_t part = (size_t)kMaxMulti * 32 * vs::kSlotStride * kKcapMax;
         for (int i = 0; i < h->n_lanes; ++i) {
             vs_index::Lane& L = h->lane[i];
-            if ((rc = dev_alloc(&L.slots, nslot))) return rc;
-            if ((rc = dev_alloc(&L.seed_qnorm, (size_t)kMaxMulti * 32))) return rc;
-            if ((rc = dev_alloc(&L.qfrag, (size_t)kMaxMulti * 4096))) return rc;
-            if ((rc = dev_alloc(&L.q8frag, (size_t)kMaxMulti * 4096))) return rc;
-            if ((rc = dev_alloc(&L.seed_wmin, (size_t)kMaxMulti * vs::kSeedWaves * 32))) return rc;
-            if ((rc = dev_alloc(&L.tau0, (size_t)kMaxMulti * 32))) return rc;
-            if ((rc = dev_alloc(&L.done, kMaxMulti))) return rc;
+            if ((rc = L.slots.alloc(nslot))) return rc;
+            if ((rc = L.seed_qnorm.alloc((size_t)kMaxMulti * 32))) return rc;
+            if ((rc = L.qfrag.alloc((size_t)kMaxMulti * 4096))) return rc;
+            if ((rc = L.q8frag.alloc((size_t)kMaxMulti * 4096))) return rc;
+            if ((rc = L.seed_wmin.alloc((size_t)kMaxMulti * vs::kSeedWaves * 32))) return rc;
+            if ((rc = L.tau0.alloc((size_t)kMaxMulti * 32))) return rc;
+            if ((rc = L.done.alloc(kMaxMulti))) return rc;
             HIPCHK(hipMemset(L.done, 0, kMaxMulti * sizeof(int)));  // arrival counter of the single-call scan: 0 between launches
             if (h->kind == 0) {
-                if ((rc = dev_alloc(&L.part_d, part))) return rc;
-                if ((rc = dev_alloc(&L.part_i, part))) return rc;
+                if ((rc = L.part_d.alloc(part))) return rc;
+                if ((rc = L.part_i.alloc(part))) return rc;
             }
-            HIPCHK(hipStreamCreateWithFlags(&L.s, hipStreamNonBlocking));
-            HIPCHK(hipEventCreateWithFlags(&L.done_ev, hipEventDisableTiming));
+            if ((rc = L.s.create()) || (rc = L.done_ev.create())) return rc;
         }
-        HIPCHK(hipEventCreateWithFlags(&h->fork, hipEventDisableTiming));
+        if ((rc = h->fork.create())) return rc;
     }
-    if ((rc = dev_alloc(&h->d_out_d, (size_t)kMaxMulti * 32 * 64))) return rc;
-    if ((rc = dev_alloc(&h->d_out_i, (size_t)kMaxMulti * 32 * 64))) return rc;
-    if ((rc = dev_alloc(&h->d_flags, (size_t)kMaxMulti * 32))) return rc;
+    if ((rc = h->d_out_d.alloc((size_t)kMaxMulti * 32 * 64))) return rc;
+    if ((rc = h->d_out_i.alloc((size_t)kMaxMulti * 32 * 64))) return rc;
+    if ((rc = h->d_flags.alloc((size_t)kMaxMulti * 32))) return rc;
     if (h->kind == 1) {
-        if ((rc = dev_alloc(&h->d_cand, 1))) return rc;
+        if ((rc = h->d_cand.alloc(1))) return rc;
         if ((rc = alloc_ivf_scratch(h))) return rc;
     }
-    HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    return VS_OK;
+    return h->stream.create();
 }
 
 // upload `rows x dim` floats in chunks through the default pageable path and compute norms
 int upload_vectors(vs_index* h, const float* host, int64_t rows) {
     int rc;
-    if ((rc = dev_alloc(&h->d_vecs, ((size_t)std::max<int64_t>(rows, 1) + vs::kScanPadRows) * vs::kDim))) return rc;
+    if ((rc = h->d_vecs.alloc(((size_t)std::max<int64_t>(rows, 1) + vs::kScanPadRows) * vs::kDim))) return rc;
     HIPCHK(hipMemset(h->d_vecs + (size_t)std::max<int64_t>(rows, 1) * vs::kDim, 0, (size_t)vs::kScanPadRows * vs::kDim * sizeof(float)));
-    if ((rc = dev_alloc(&h->d_norm, (size_t)rows + 64))) return rc;
+    if ((rc = h->d_norm.alloc((size_t)rows + 64))) return rc;
     HIPCHK(hipMemset(h->d_norm, 0, ((size_t)rows + 64) * sizeof(float)));
     if (rows > 0) {
         HIPCHK(hipMemcpy(h->d_vecs, host, (size_t)rows * vs::kDim * sizeof(float), hipMemcpyHostToDevice));
@@ -454,9 +380,9 @@ int build_u8_copy(vs_index* h, const float* host, int64_t rows, std::vector<int8
         rterm[(size_t)i] = n2 - 256 * sb;
     }
     int rc;
-    if ((rc = dev_alloc(&h->d_vecs_u8, bytes.size()))) return rc;
-    if ((rc = dev_alloc(&h->d_rterm, rterm.size()))) return rc;
-    if ((rc = dev_alloc(&h->d_invalid, (size_t)kMaxMulti))) return rc;
+    if ((rc = h->d_vecs_u8.alloc(bytes.size()))) return rc;
+    if ((rc = h->d_rterm.alloc(rterm.size()))) return rc;
+    if ((rc = h->d_invalid.alloc((size_t)kMaxMulti))) return rc;
     HIPCHK(hipMemcpy(h->d_vecs_u8, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->d_rterm, rterm.data(), rterm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     if (bytes_out) bytes_out->swap(bytes);
@@ -469,9 +395,9 @@ void prof_begin(vs_index* h, int which, hipStream_t s) {
     ProfSlot& ps = h->prof_slot[which];
     if (ps.used + 2 > kMaxEvents) return;
     while ((int)ps.ev.size() < ps.used + 2) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        ps.ev.push_back(e);
+        vs::Event e;
+        if (e.create(true)) return;
+        ps.ev.push_back(std::move(e));
     }
     (void)hipEventRecord(ps.ev[ps.used], s);
 }
@@ -491,12 +417,12 @@ void stage_mark(vs_index* h, int i, hipStream_t s) {
         return;
     }
     while ((int)h->stage_ev.size() < h->stage_used + 4) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) {
+        vs::Event e;
+        if (e.create(true)) {
             h->stage_on = false;
             return;
         }
-        h->stage_ev.push_back(e);
+        h->stage_ev.push_back(std::move(e));
     }
     (void)hipEventRecord(h->stage_ev[h->stage_used + i], s);
     if (i == 3) h->stage_used += 4;
@@ -545,22 +471,17 @@ int g_stream = [] {
 }();
 
 int ensure_wide(vs_index::Lane& L) {
-    if (L.wbuf) return VS_OK;  // (the buffer allocated LAST: a call that ran out of memory half way is repeated in full)
-    void* partial[] = {L.q8, L.qterm, L.wcnt, L.wcand_d, L.wcand_i};
-    for (void* q : partial)
-        if (q) (void)hipFree(q);
-    L.q8 = nullptr;
-    L.qterm = nullptr;
-    L.wcnt = nullptr;
-    L.wcand_d = nullptr;
-    L.wcand_i = nullptr;
+    if (L.wide8.ready) return VS_OK;
+    vs_index::Lane::Wide8 w;
     int rc;
-    if ((rc = dev_alloc(&L.q8, (size_t)kMaxMulti * 32 * vs::kDim))) return rc;
-    if ((rc = dev_alloc(&L.qterm, (size_t)kMaxMulti * 32))) return rc;
-    if ((rc = dev_alloc(&L.wcnt, (size_t)kMaxMulti * 32 * kWideSub + 64))) return rc;  // overflow word | skipped batches | list counters
-    if ((rc = dev_alloc(&L.wcand_d, (size_t)kMaxMulti * 32 * kWideSub * kWideCap))) return rc;
-    if ((rc = dev_alloc(&L.wcand_i, (size_t)kMaxMulti * 32 * kWideSub * kWideCap))) return rc;
-    if ((rc = dev_alloc(&L.wbuf, (size_t)vs::kSlotStride * vs::kScanWaves * kWideWaveCap))) return rc;
+    if ((rc = w.q8.alloc((size_t)kMaxMulti * 32 * vs::kDim))) return rc;
+    if ((rc = w.qterm.alloc((size_t)kMaxMulti * 32))) return rc;
+    if ((rc = w.wcnt.alloc((size_t)kMaxMulti * 32 * kWideSub + 64))) return rc;  // overflow word | skipped batches | list counters
+    if ((rc = w.wcand_d.alloc((size_t)kMaxMulti * 32 * kWideSub * kWideCap))) return rc;
+    if ((rc = w.wcand_i.alloc((size_t)kMaxMulti * 32 * kWideSub * kWideCap))) return rc;
+    if ((rc = w.wbuf.alloc((size_t)vs::kSlotStride * vs::kScanWaves * kWideWaveCap))) return rc;
+    w.ready = true;
+    L.wide8 = std::move(w);
     return VS_OK;
 }
 
@@ -643,12 +564,12 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
         if (rc) return rc;
     }
     // one zeroed block per launch: [0] overflow word | [16, 48) batches the int8 path has to skip | [64, ...) list counters
-    int32_t* const overflow = L.wcnt;
-    int32_t* const invalid = L.wcnt ? L.wcnt + 16 : nullptr;
+    int32_t* const overflow = L.wide8.wcnt;
+    int32_t* const invalid = L.wide8.wcnt ? L.wide8.wcnt + 16 : nullptr;
     // (cleared by the seed's query-preparation launch where there is one and nobody else writes the batches' verdict words)
     const size_t zero_words = 64 + (stream ? (size_t)nb * 32 * kWideSub : 0);
     const bool zero_in_seed = seeded && (!use_u8 || i8_seed);
-    if (L.wcnt && !zero_in_seed) HIPCHK(hipMemsetAsync(L.wcnt, 0, zero_words * sizeof(int32_t), s));
+    if (L.wide8.wcnt && !zero_in_seed) HIPCHK(hipMemsetAsync(L.wide8.wcnt, 0, zero_words * sizeof(int32_t), s));
     if (seeded) {
         vs::SeedParams sp{};
         sp.base = h->d_vecs;
@@ -672,21 +593,21 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
         sp.wmin = L.seed_wmin;
         sp.tau0 = L.tau0;
         if (zero_in_seed) {
-            sp.zero = L.wcnt;
+            sp.zero = L.wide8.wcnt;
             sp.zero_words = (int)zero_words;
         }
         sp.qfrag = L.qfrag;
         if (i8_seed) {  // queries as bytes + constant terms + the "not byte valued" verdict: int8 seed and wide int8 scan
-            sp.q8 = L.q8;
+            sp.q8 = L.wide8.q8;
             sp.q8frag = L.q8frag;
-            sp.qterm = L.qterm;
+            sp.qterm = L.wide8.qterm;
             sp.invalid = invalid;
         }
         HIPCHK(vs::launch_seed(sp, s));
         p.tau0 = L.tau0;
     } else if (exchange) {
         // 0x7f800000 = +inf
-        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(L.slots), 0x7f800000, (size_t)nb * 32 * vs::kSlotStride, s));
+        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(L.slots.get()), 0x7f800000, (size_t)nb * 32 * vs::kSlotStride, s));
         p.slots_cur = L.slots;
     }
     vs::MergeParams m{};
@@ -700,12 +621,12 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     m.invalid = use_u8 ? invalid : nullptr;
     if (stream) {
         vs::CandSink sink{};
-        sink.wbuf = L.wbuf;
+        sink.wbuf = L.wide8.wbuf;
         sink.wcap = kWideWaveCap;
         sink.overflow = overflow;
-        sink.cnt = L.wcnt + 64;
-        sink.cand_d = L.wcand_d;
-        sink.cand_i = L.wcand_i;
+        sink.cnt = L.wide8.wcnt + 64;
+        sink.cand_d = L.wide8.wcand_d;
+        sink.cand_i = L.wide8.wcand_i;
         sink.cap = kWideCap;
         sink.nsub = kWideSub;
         prof_begin(h, 0, s);
@@ -714,9 +635,9 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
             wp.base_u8 = h->d_vecs_u8;
             wp.rterm = h->d_rterm;
             wp.n_rows = h->n_rows;
-            wp.q8 = L.q8;
+            wp.q8 = L.wide8.q8;
             wp.q8frag = L.q8frag;
-            wp.qterm = L.qterm;
+            wp.qterm = L.wide8.qterm;
             wp.tau0 = L.tau0;
             wp.invalid = invalid;
             wp.n_batches = nb;
@@ -752,11 +673,11 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
         }
         // every query's candidate list (unsorted, a few hundred entries) -> k1 best by (dist, id), tie flags
         vs::MergeParams mf = m;
-        mf.part_d = L.wcand_d;
-        mf.part_i = L.wcand_i;
+        mf.part_d = L.wide8.wcand_d;
+        mf.part_i = L.wide8.wcand_i;
         mf.G = kWideSub;
         mf.kin = kWideCap;
-        mf.flat_len = L.wcnt + 64;
+        mf.flat_len = L.wide8.wcnt + 64;
         mf.run_if = overflow;
         mf.run_mode = 2;
         HIPCHK(vs::launch_merge_layout(mf, kWideCap, (int64_t)kWideSub * kWideCap, s));
@@ -891,36 +812,38 @@ int ivf_fallback_batch_dev(vs_index* h, const float* q_dev, int B, int k, int np
 
 // Scratch of one lane of the wide pipeline, sized for launch groups of h->ivf_gb batches in up to h->ivf_nsb super-batches.
 int ensure_ivf_wide(vs_index* h, int lane) {
-    vs_index::IvfWide& W = h->wide[lane];
-    if (W.slab) return VS_OK;
+    if (h->wide[lane].ready) return VS_OK;
+    vs_index::IvfWide W;
     int rc;
     const size_t nq = (size_t)h->ivf_gb * 32;
     const int n_sb_max = h->ivf_nsb;
     W.n_waves = 0;
     for (int n = 1; n <= n_sb_max; ++n) W.n_waves = std::max(W.n_waves, vs::ivf_wide_waves(h->num_cus, n));
     W.zero_words = (size_t)n_sb_max * vs::ivf_wide_plan_words(h->nlist) + nq + 16 + h->ivf_gb + nq * kWideSub;
-    if ((rc = dev_alloc(&W.lq, (size_t)n_sb_max * h->nlist * vs::kIvfWideQ))) return rc;
-    if ((rc = dev_alloc(&W.zero, W.zero_words))) return rc;
+    if ((rc = W.lq.alloc((size_t)n_sb_max * h->nlist * vs::kIvfWideQ))) return rc;
+    if ((rc = W.zero.alloc(W.zero_words))) return rc;
     HIPCHK(hipMemset(W.zero, 0, W.zero_words * sizeof(int32_t)));
     W.units_cap = (int)std::min<int64_t>(2 * h->n_units_max + 4096, 0x7fffffff / 16);
-    if ((rc = dev_alloc(&W.units, (size_t)n_sb_max * W.units_cap * 4))) return rc;
-    if ((rc = dev_alloc(&W.tau, nq))) return rc;
-    if ((rc = dev_alloc(&W.tq, (size_t)h->nlist * nq))) return rc;
-    if ((rc = dev_alloc(&W.tk, nq * vs::kBoundSegs * 16))) return rc;
-    if ((rc = dev_alloc(&W.nseg, nq))) return rc;
-    if ((rc = dev_alloc(&W.qnorm, nq))) return rc;
-    if ((rc = dev_alloc(&W.q8, nq * vs::kDim))) return rc;
-    if ((rc = dev_alloc(&W.qterm, nq))) return rc;
-    if ((rc = dev_alloc(&W.wbuf, (size_t)W.n_waves * kIvfWideWaveCap))) return rc;
-    if ((rc = dev_alloc(&W.cand_d, nq * kWideSub * kIvfWideSubCap))) return rc;
-    if ((rc = dev_alloc(&W.cand_i, nq * kWideSub * kIvfWideSubCap))) return rc;
+    if ((rc = W.units.alloc((size_t)n_sb_max * W.units_cap * 4))) return rc;
+    if ((rc = W.tau.alloc(nq))) return rc;
+    if ((rc = W.tq.alloc((size_t)h->nlist * nq))) return rc;
+    if ((rc = W.tk.alloc(nq * vs::kBoundSegs * 16))) return rc;
+    if ((rc = W.nseg.alloc(nq))) return rc;
+    if ((rc = W.qnorm.alloc(nq))) return rc;
+    if ((rc = W.q8.alloc(nq * vs::kDim))) return rc;
+    if ((rc = W.qterm.alloc(nq))) return rc;
+    if ((rc = W.wbuf.alloc((size_t)W.n_waves * kIvfWideWaveCap))) return rc;
+    if ((rc = W.cand_d.alloc(nq * kWideSub * kIvfWideSubCap))) return rc;
+    if ((rc = W.cand_i.alloc(nq * kWideSub * kIvfWideSubCap))) return rc;
     if (nq > 2048) {
-        if ((rc = dev_alloc(&W.rank_list, nq + 1))) return rc;
+        if ((rc = W.rank_list.alloc(nq + 1))) return rc;
         HIPCHK(hipMemset(W.rank_list, 0, sizeof(int32_t)));
     }
     W.off_scores = (32ll * kMaxNprobe * 4 + 255) & ~255ll;
     W.slab_stride = (W.off_scores + 32ll * ((h->nlist + 63) & ~63) * 4 + 255) & ~255ll;
-    if ((rc = dev_alloc(&W.slab, (size_t)W.slab_stride * h->ivf_gb))) return rc;
+    if ((rc = W.slab.alloc((size_t)W.slab_stride * h->ivf_gb))) return rc;
+    W.ready = true;
+    h->wide[lane] = std::move(W);
     return VS_OK;
 }
 
@@ -979,7 +902,7 @@ vs::IvfWideParams wide_params(vs_index* h, vs_index::IvfWide& W, const float* q_
     wp.q8 = W.q8;
     wp.qterm = W.qterm;
     wp.invalid = z.invalid;
-    wp.probes = reinterpret_cast<int32_t*>(W.slab);
+    wp.probes = reinterpret_cast<int32_t*>(W.slab.get());
     wp.probes_batch_bytes = W.slab_stride;
     wp.lq = W.lq;
     wp.zero = z.plan;
@@ -1084,7 +1007,7 @@ int ivf_group_wide_dev(vs_index* h, int lane, const float* q_dev, int nb, int B,
     stage_mark(h, 0, s);
     HIPCHK(vs::launch_ivf_coarse_pick(q_dev, B, h->d_centroids, h->d_cnorm, h->nlist, nprobe, h->metric,
                                       reinterpret_cast<float*>(W.slab + W.off_scores), (h->nlist + 63) & ~63,
-                                      reinterpret_cast<int32_t*>(W.slab), grp, s, nb));
+                                      reinterpret_cast<int32_t*>(W.slab.get()), grp, s, nb));
     stage_mark(h, 1, s);
     HIPCHK(vs::launch_ivf_wide_bounds_plan(wp, s));
     stage_mark(h, 2, s);  // "gather" (IVFIndex.cpp's second stage) = bounds + plan here; the fine search is the scan + ranking
@@ -1174,7 +1097,7 @@ int ivf_shard_back(vs_index* h, int lane, const float* q_dev, int nb, int sbb, i
     const WideZero z = wide_zero(h, W);
     const vs::IvfGroup grp = wide_group(h, W, sbb, B);
     const vs::IvfWideParams wp = wide_params(h, W, q_dev, nb, sbb, B, k, nprobe, out_d, out_i);
-    HIPCHK(vs::launch_ivf_fill(gathered, ivf_block_words(sbb, nprobe), B, nprobe, h->nlist, h->d_offsets, reinterpret_cast<int32_t*>(W.slab),
+    HIPCHK(vs::launch_ivf_fill(gathered, ivf_block_words(sbb, nprobe), B, nprobe, h->nlist, h->d_offsets, reinterpret_cast<int32_t*>(W.slab.get()),
                                W.tau, z.slow, grp, s, nb));
     HIPCHK(vs::launch_ivf_wide_bounds_plan(wp, s, 2));  // plan only
     int rc = wide_scan_rank(h, W, wp, s);
@@ -1184,12 +1107,19 @@ int ivf_shard_back(vs_index* h, int lane, const float* q_dev, int nb, int sbb, i
 }
 
 int ensure_wide_streams(vs_index* h) {
-    if (h->wide_fork) return VS_OK;
+    if (h->wide_streams_ready) return VS_OK;
+    vs::Stream st[kWideLanesMax];
+    vs::Event join[kWideLanesMax], fork;
+    int rc;
+    for (int i = 0; i < kWideLanesMax; ++i)
+        if ((rc = st[i].create()) || (rc = join[i].create())) return rc;
+    if ((rc = fork.create())) return rc;
     for (int i = 0; i < kWideLanesMax; ++i) {
-        HIPCHK(hipStreamCreateWithFlags(&h->wide_stream[i], hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&h->wide_join[i], hipEventDisableTiming));
+        h->wide_stream[i] = std::move(st[i]);
+        h->wide_join[i] = std::move(join[i]);
     }
-    HIPCHK(hipEventCreateWithFlags(&h->wide_fork, hipEventDisableTiming));
+    h->wide_fork = std::move(fork);
+    h->wide_streams_ready = true;
     return VS_OK;
 }
 
@@ -1197,17 +1127,16 @@ int ensure_ivf_host(vs_index* h) {
     int rc;
     h->ivf_host_cap = std::max<int64_t>(kIvfHostChunk, (int64_t)h->ivf_gb * 32);
     const size_t cap = (size_t)h->ivf_host_cap;
-    for (auto& S : h->ihs)
-        if (!S.pin_q) {
-            HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&S.pin_q), cap * vs::kDim * sizeof(float), hipHostMallocDefault));
-            HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&S.pin_out), cap * 64 * 2 * sizeof(float), hipHostMallocDefault));
-            if ((rc = dev_alloc(&S.d_q, cap * vs::kDim))) return rc;
-            if ((rc = dev_alloc(&S.d_out, cap * 64 * 2))) return rc;
-            HIPCHK(hipEventCreateWithFlags(&S.ev_h2d, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&S.ev_comp[0], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&S.ev_comp[1], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&S.ev_d2h, hipEventDisableTiming));
-        }
+    for (auto& slot : h->ihs) {
+        if (slot.ready) continue;
+        vs_index::IvfHostSlot S;
+        if ((rc = S.pin_q.alloc(cap * vs::kDim)) || (rc = S.pin_out.alloc(cap * 64 * 2)) || (rc = S.d_q.alloc(cap * vs::kDim)) ||
+            (rc = S.d_out.alloc(cap * 64 * 2)) || (rc = S.ev_h2d.create()) || (rc = S.ev_comp[0].create()) || (rc = S.ev_comp[1].create()) ||
+            (rc = S.ev_d2h.create()))
+            return rc;
+        S.ready = true;
+        slot = std::move(S);
+    }
     return VS_OK;
 }
 
@@ -1264,7 +1193,8 @@ int order_begin(vs_index* h, hipStream_t s) {
     // Calls that stay on one stream are ordered by the stream itself: no event traffic (two runtime calls and two
     // barrier packets per search call are what a single-query call's latency is made of).  A call on ANOTHER stream than
     // the previous one waits for everything enqueued on that one so far.
-    if (!h->ev_busy) HIPCHK(hipEventCreateWithFlags(&h->ev_busy, hipEventDisableTiming));
+    int rc;
+    if (!h->ev_busy && (rc = h->ev_busy.create())) return rc;
     if (h->have_last && h->last_stream != s) {
         HIPCHK(hipEventRecord(h->ev_busy, h->last_stream));
         HIPCHK(hipStreamWaitEvent(s, h->ev_busy, 0));
@@ -1275,31 +1205,42 @@ int order_begin(vs_index* h, hipStream_t s) {
 }
 int order_end(vs_index*, hipStream_t) { return VS_OK; }
 
+// A call that failed half way leaves chunks marked in flight in the host-buffer slots: wait for the streams their work
+// went to, then free the slots (nothing of that call may land in, or be retired into, THIS call's buffers).
+template <class Slot>
+void settle_slots(Slot (&slots)[2], std::initializer_list<hipStream_t> streams) {
+    if (slots[0].q0 < 0 && slots[1].q0 < 0) return;
+    for (hipStream_t s : streams) (void)hipStreamSynchronize(s);
+    slots[0].q0 = slots[1].q0 = -1;
+}
+
 int ensure_pipe(vs_index* h) {
-    if (h->pipe[0].pin_q) return VS_OK;
+    if (h->pipe_ready) return VS_OK;
     const size_t nqc = (size_t)kMaxMulti * 32;
+    vs_index::PipeSlot P[2];
+    vs::Stream h2d, d2h;
+    int rc;
     for (int i = 0; i < 2; ++i) {
-        vs_index::PipeSlot& S = h->pipe[i];
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&S.pin_q), nqc * vs::kDim * sizeof(float), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&S.pin_out), nqc * (64 * 2 + 1) * sizeof(float), hipHostMallocDefault));
-        if (i == 0) {
-            S.d_q = h->d_q;
-            S.d_out_d = h->d_out_d;
-            S.d_out_i = h->d_out_i;
-            S.d_flags = h->d_flags;
-        } else {
-            int rc;
-            if ((rc = dev_alloc(&S.d_q, nqc * vs::kDim))) return rc;
-            if ((rc = dev_alloc(&S.d_out_d, nqc * 64))) return rc;
-            if ((rc = dev_alloc(&S.d_out_i, nqc * 64))) return rc;
-            if ((rc = dev_alloc(&S.d_flags, nqc))) return rc;
-        }
-        HIPCHK(hipEventCreateWithFlags(&S.ev_h2d, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&S.ev_comp, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&S.ev_d2h, hipEventDisableTiming));
+        vs_index::PipeSlot& S = P[i];
+        if ((rc = S.pin_q.alloc(nqc * vs::kDim)) || (rc = S.pin_out.alloc(nqc * (64 * 2 + 1) * sizeof(float)))) return rc;
+        if (i == 1 && ((rc = S.own_q.alloc(nqc * vs::kDim)) || (rc = S.own_out_d.alloc(nqc * 64)) || (rc = S.own_out_i.alloc(nqc * 64)) ||
+                       (rc = S.own_flags.alloc(nqc))))
+            return rc;
+        if ((rc = S.ev_h2d.create()) || (rc = S.ev_comp.create()) || (rc = S.ev_d2h.create())) return rc;
     }
-    HIPCHK(hipStreamCreateWithFlags(&h->s_h2d, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&h->s_d2h, hipStreamNonBlocking));
+    if ((rc = h2d.create()) || (rc = d2h.create())) return rc;
+    P[0].d_q = h->d_q;
+    P[0].d_out_d = h->d_out_d;
+    P[0].d_out_i = h->d_out_i;
+    P[0].d_flags = h->d_flags;
+    P[1].d_q = P[1].own_q;
+    P[1].d_out_d = P[1].own_out_d;
+    P[1].d_out_i = P[1].own_out_i;
+    P[1].d_flags = P[1].own_flags;
+    for (int i = 0; i < 2; ++i) h->pipe[i] = std::move(P[i]);
+    h->s_h2d = std::move(h2d);
+    h->s_d2h = std::move(d2h);
+    h->pipe_ready = true;
     return VS_OK;
 }
 
@@ -1307,15 +1248,9 @@ int ensure_pipe(vs_index* h) {
 int resolve_dense_full(vs_index* h, const float* q_dev, int B, const std::vector<int>& which, const int64_t* qidx, int k,
                        int32_t* ids, float* dists) {
     const int64_t ld = (h->n_rows + 15) & ~int64_t(15);
-    if (h->scores_cap < (int64_t)B * ld) {
-        if (h->d_scores) (void)hipFree(h->d_scores);
-        h->d_scores = nullptr;
-        h->scores_cap = 0;
-        int rc = dev_alloc(&h->d_scores, (size_t)32 * ld);
-        if (rc) return rc;
-        h->scores_cap = (int64_t)32 * ld;
-    }
-    int rc = scores_dev(h, h->d_vecs, h->d_norm, h->n_rows, q_dev, B, h->d_scores, ld, h->stream);
+    int rc;
+    if (h->d_scores.size() < (size_t)B * ld && (rc = h->d_scores.alloc((size_t)32 * ld))) return rc;
+    rc = scores_dev(h, h->d_vecs, h->d_norm, h->n_rows, q_dev, B, h->d_scores, ld, h->stream);
     if (rc) return rc;
     std::vector<float> row((size_t)ld);
     for (int b : which) {
@@ -1337,18 +1272,18 @@ int resolve_ties(vs_index* h, const float* queries_host, const std::vector<int64
     int rc;
     const int64_t L0 = std::min<int64_t>(h->n_rows, kTieDense);
     const int64_t L0p = (L0 + 15) & ~int64_t(15);
-    if (!h->d_tie_dense) {
-        if ((rc = dev_alloc(&h->d_tie_dense, (size_t)32 * kTieDense))) return rc;
-        if ((rc = dev_alloc(&h->d_tie_tau, 32))) return rc;
-        if ((rc = dev_alloc(&h->d_tie_cnt, 32))) return rc;
-        if ((rc = dev_alloc(&h->d_tie_row, (size_t)32 * kTieCap))) return rc;
-        if ((rc = dev_alloc(&h->d_tie_d, (size_t)32 * kTieCap))) return rc;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->pin_tie), (size_t)32 * kTieDense * 4 + 128 + (size_t)2 * 32 * kTieCap * 4, hipHostMallocDefault));
+    if (!h->tie.ready) {
+        vs_index::Tie t;
+        if ((rc = t.dense.alloc((size_t)32 * kTieDense)) || (rc = t.tau.alloc(32)) || (rc = t.cnt.alloc(32)) || (rc = t.row.alloc((size_t)32 * kTieCap)) ||
+            (rc = t.d.alloc((size_t)32 * kTieCap)) || (rc = t.pin.alloc((size_t)32 * kTieDense * 4 + 128 + (size_t)2 * 32 * kTieCap * 4)))
+            return rc;
+        t.ready = true;
+        h->tie = std::move(t);
     }
     const int group = 32;
     // downloads land in pinned memory (pageable destinations are staged by the runtime: several times slower)
-    float* const dense = reinterpret_cast<float*>(h->pin_tie);
-    int32_t* const cnt = reinterpret_cast<int32_t*>(h->pin_tie + (size_t)32 * kTieDense * 4);
+    float* const dense = reinterpret_cast<float*>(h->tie.pin.get());
+    int32_t* const cnt = reinterpret_cast<int32_t*>(h->tie.pin + (size_t)32 * kTieDense * 4);
     int32_t* const cr = cnt + 32;
     float* const cd = reinterpret_cast<float*>(cr + (size_t)32 * kTieCap);
     std::vector<float> qbuf((size_t)group * vs::kDim);
@@ -1357,19 +1292,19 @@ int resolve_ties(vs_index* h, const float* queries_host, const std::vector<int64
         for (int b = 0; b < B; ++b)
             std::memcpy(&qbuf[(size_t)b * vs::kDim], queries_host + flagged[f0 + b] * vs::kDim, vs::kDim * sizeof(float));
         HIPCHK(hipMemcpyAsync(h->d_q, qbuf.data(), (size_t)B * vs::kDim * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        if ((rc = scores_dev(h, h->d_vecs, h->d_norm, L0, h->d_q, B, h->d_tie_dense, L0p, h->stream))) return rc;
+        if ((rc = scores_dev(h, h->d_vecs, h->d_norm, L0, h->d_q, B, h->tie.dense, L0p, h->stream))) return rc;
         const bool sparse = h->n_rows > L0;
         if (sparse) {
             // bound = next_up(k-th smallest of the dense rows): merge kernel over G = L0 one-entry lists
-            HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->d_tie_tau), 0xff800000u, 32, h->stream));  // -inf: padding queries emit nothing
-            HIPCHK(hipMemsetAsync(h->d_tie_cnt, 0, 32 * sizeof(int32_t), h->stream));
+            HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->tie.tau.get()), 0xff800000u, 32, h->stream));  // -inf: padding queries emit nothing
+            HIPCHK(hipMemsetAsync(h->tie.cnt, 0, 32 * sizeof(int32_t), h->stream));
             vs::MergeParams m{};
-            m.part_d = h->d_tie_dense;
+            m.part_d = h->tie.dense;
             m.G = (int)L0;
             m.kin = 1;
             m.nq = B;
             m.kout = k;
-            m.tau_out = h->d_tie_tau;
+            m.tau_out = h->tie.tau;
             HIPCHK(vs::launch_merge_layout(m, 1, L0p, h->stream));
             vs::ScanParams p{};
             p.base = h->d_vecs;
@@ -1379,20 +1314,20 @@ int resolve_ties(vs_index* h, const float* queries_host, const std::vector<int64
             p.metric = h->metric;
             p.nq_valid = B;
             p.k1 = k + 1;
-            p.tau0 = h->d_tie_tau;
+            p.tau0 = h->tie.tau;
             p.row_begin = L0;  // multiple of 16 (kTieDense)
             p.row_end = h->n_rows;
-            p.f_cnt = h->d_tie_cnt;
-            p.f_row = h->d_tie_row;
-            p.f_d = h->d_tie_d;
+            p.f_cnt = h->tie.cnt;
+            p.f_row = h->tie.row;
+            p.f_d = h->tie.d;
             p.f_cap = kTieCap;
             int grid, tp;
             scan_geometry(h->n_rows - L0, h->num_cus, grid, tp);
             p.tiles_per_wg = tp;
             HIPCHK(vs::launch_scan(p, grid, 8, 2, vs::kModeFilter, h->stream));
-            HIPCHK(hipMemcpyAsync(cnt, h->d_tie_cnt, 32 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(cnt, h->tie.cnt, 32 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         }
-        HIPCHK(hipMemcpyAsync(dense, h->d_tie_dense, (size_t)B * L0p * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(dense, h->tie.dense, (size_t)B * L0p * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         int mx = 0;
         std::vector<int> overflow;
@@ -1402,9 +1337,9 @@ int resolve_ties(vs_index* h, const float* queries_host, const std::vector<int64
                 else mx = std::max(mx, cnt[b]);
             }
             if (mx > 0) {
-                HIPCHK(hipMemcpy2DAsync(cr, (size_t)mx * 4, h->d_tie_row, (size_t)kTieCap * 4, (size_t)mx * 4, B,
+                HIPCHK(hipMemcpy2DAsync(cr, (size_t)mx * 4, h->tie.row, (size_t)kTieCap * 4, (size_t)mx * 4, B,
                                         hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(hipMemcpy2DAsync(cd, (size_t)mx * 4, h->d_tie_d, (size_t)kTieCap * 4, (size_t)mx * 4, B,
+                HIPCHK(hipMemcpy2DAsync(cd, (size_t)mx * 4, h->tie.d, (size_t)kTieCap * 4, (size_t)mx * 4, B,
                                         hipMemcpyDeviceToHost, h->stream));
                 HIPCHK(hipStreamSynchronize(h->stream));
             }
@@ -1478,7 +1413,12 @@ int vs_device_count(void) {
 int64_t vs_index_rows(const vs_index* h) { return h ? h->n_total : 0; }
 int vs_index_dim(const vs_index* h) { return h ? h->dim : 0; }
 int vs_index_nlist(const vs_index* h) { return h ? h->nlist : 0; }
-void vs_destroy(vs_index* h) { free_all(h); }
+void vs_destroy(vs_index* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    (void)hipDeviceSynchronize();  // (the handles release without waiting for queued work)
+    delete h;
+}
 
 int vs_set_batch(vs_index* h, int batch) {
     if (!h || batch < 1 || batch > vs::kMaxBatch) {
@@ -1569,18 +1509,18 @@ static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int m
     h->n_rows = h->n_total = n_rows;
     h->id_offset = id_offset;
     if ((rc = upload_vectors(h, base_host, n_rows)) || (rc = alloc_scratch(h))) {
-        free_all(h);
+        vs_destroy(h);
         return rc;
     }
     if (metric == VS_METRIC_L2 && (rc = build_u8_copy(h, base_host, n_rows))) {
-        free_all(h);
+        vs_destroy(h);
         return rc;
     }
     if ((n_rows + vs::kTileRows - 1) / vs::kTileRows >= 2 * vs::kSeedWaves) {  // shards on which launches are seeded (bf_launch)
         auto sample = [&]() -> int {
             int r2;
-            if ((r2 = dev_alloc(&h->d_seed_f32, (size_t)vs::kSeedWaves * 2048)) || (r2 = dev_alloc(&h->d_seed_bnorm, (size_t)vs::kSeedWaves * 16))) return r2;
-            if (h->d_vecs_u8 && ((r2 = dev_alloc(&h->d_seed_u8, (size_t)vs::kSeedWaves * 2048)) || (r2 = dev_alloc(&h->d_seed_rterm, (size_t)vs::kSeedWaves * 16))))
+            if ((r2 = h->d_seed_f32.alloc((size_t)vs::kSeedWaves * 2048)) || (r2 = h->d_seed_bnorm.alloc((size_t)vs::kSeedWaves * 16))) return r2;
+            if (h->d_vecs_u8 && ((r2 = h->d_seed_u8.alloc((size_t)vs::kSeedWaves * 2048)) || (r2 = h->d_seed_rterm.alloc((size_t)vs::kSeedWaves * 16))))
                 return r2;
             HIPCHK(vs::launch_seed_sample(h->d_vecs, h->d_norm, h->d_vecs_u8, h->d_rterm, n_rows, h->d_seed_f32, h->d_seed_bnorm,
                                           h->d_seed_u8, h->d_seed_rterm, nullptr));
@@ -1588,7 +1528,7 @@ static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int m
             return VS_OK;
         };
         if ((rc = sample())) {
-            free_all(h);
+            vs_destroy(h);
             return rc;
         }
     }
@@ -1680,13 +1620,7 @@ int vs_bf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int3
             return VS_ERR_UNSUPPORTED;
         }
         if ((rc = ensure_pipe(h)) || (rc = order_begin(h, h->stream))) return rc;
-        // (a call that failed half way leaves chunks marked in flight: nothing of it may be retired into THIS call's buffers)
-        if (h->pipe[0].q0 >= 0 || h->pipe[1].q0 >= 0) {
-            (void)hipStreamSynchronize(h->stream);
-            (void)hipStreamSynchronize(h->s_h2d);
-            (void)hipStreamSynchronize(h->s_d2h);
-            h->pipe[0].q0 = h->pipe[1].q0 = -1;
-        }
+        settle_slots(h->pipe, {h->stream, h->s_h2d, h->s_d2h});
         // Queries go through in chunks of kMaxMulti batches: one persistent scan launch + one merge launch per chunk
         // (the harness loop of main.cpp:201-251 collapsed into a call; a ragged tail batch gets its own launch).  Two
         // chunks are in flight: uploads and downloads run on copy streams beside the other chunk's kernels.
@@ -1705,8 +1639,8 @@ int vs_bf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int3
             return r2;
         };
         auto download = [&](vs_index::PipeSlot& S, hipStream_t st) -> int {
-            float* hd = reinterpret_cast<float*>(S.pin_out);
-            int32_t* hi = reinterpret_cast<int32_t*>(S.pin_out) + (size_t)chunk * k1;
+            float* hd = reinterpret_cast<float*>(S.pin_out.get());
+            int32_t* hi = reinterpret_cast<int32_t*>(S.pin_out.get()) + (size_t)chunk * k1;
             int32_t* hf = hi + (size_t)chunk * k1;
             HIPCHK(hipMemcpyAsync(hd, S.d_out_d, (size_t)S.n * k1 * sizeof(float), hipMemcpyDeviceToHost, st));
             HIPCHK(hipMemcpyAsync(hi, S.d_out_i, (size_t)S.n * k1 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1734,8 +1668,8 @@ int vs_bf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int3
             if (S.q0 < 0) return VS_OK;
             const double t0 = now_ms();
             HIPCHK(hipEventSynchronize(S.ev_d2h));
-            const float* hd = reinterpret_cast<const float*>(S.pin_out);
-            const int32_t* hi = reinterpret_cast<const int32_t*>(S.pin_out) + (size_t)chunk * k1;
+            const float* hd = reinterpret_cast<const float*>(S.pin_out.get());
+            const int32_t* hi = reinterpret_cast<const int32_t*>(S.pin_out.get()) + (size_t)chunk * k1;
             const int32_t* hf = hi + (size_t)chunk * k1;
             bool rerun = false;
             for (int64_t b = 0; b < S.n; ++b) rerun = rerun || hf[(size_t)b] == 2;
@@ -1839,8 +1773,8 @@ static int build_tau_heads(vs_index* h, const float* vectors, const int32_t* off
         if (hoff[c + 1] > hoff[c])
             std::memcpy(&hv[(size_t)hoff[c] * vs::kDim], vectors + (size_t)offsets[c] * vs::kDim, (size_t)(hoff[c + 1] - hoff[c]) * vs::kDim * sizeof(float));
     int rc;
-    if ((rc = dev_alloc(&h->d_head_vecs, hv.size())) || (rc = dev_alloc(&h->d_head_norm, nh + 64)) || (rc = dev_alloc(&h->d_head_off, hoff.size())) ||
-        (rc = dev_alloc(&h->d_head_tdelta, tdelta.size())))
+    if ((rc = h->d_head_vecs.alloc(hv.size())) || (rc = h->d_head_norm.alloc(nh + 64)) || (rc = h->d_head_off.alloc(hoff.size())) ||
+        (rc = h->d_head_tdelta.alloc(tdelta.size())))
         return rc;
     HIPCHK(hipMemcpy(h->d_head_vecs, hv.data(), hv.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(h->d_head_norm, 0, (nh + 64) * sizeof(float)));
@@ -1867,7 +1801,7 @@ static int build_tau_heads(vs_index* h, const float* vectors, const int32_t* off
             }
             rterm_t[R] = n2 - 256 * sb;
         }
-    if ((rc = dev_alloc(&h->d_head_t8, tb.size())) || (rc = dev_alloc(&h->d_head_rterm_t, nt))) return rc;
+    if ((rc = h->d_head_t8.alloc(tb.size())) || (rc = h->d_head_rterm_t.alloc(nt))) return rc;
     HIPCHK(hipMemcpy(h->d_head_t8, tb.data(), tb.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->d_head_rterm_t, rterm_t.data(), nt * 4, hipMemcpyHostToDevice));
     return VS_OK;
@@ -1939,7 +1873,7 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
                 loc_r2o[(size_t)loc_off[c] + (r - offsets[c])] = r2o ? r2o[r] : r;
 
     auto fail = [&](int code) {
-        free_all(h);
+        vs_destroy(h);
         return code;
     };
     if ((rc = upload_vectors(h, up, n_local))) return fail(rc);
@@ -1947,11 +1881,11 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
     std::vector<int8_t> host_bytes;
     std::vector<int32_t> host_rterm;
     if (h->metric == VS_METRIC_L2 && n_local > 0 && (rc = build_u8_copy(h, up, n_local, &host_bytes, &host_rterm))) return fail(rc);
-    if ((rc = dev_alloc(&h->d_centroids, ((size_t)nlist + vs::kScanPadRows) * dim))) return fail(rc);
+    if ((rc = h->d_centroids.alloc(((size_t)nlist + vs::kScanPadRows) * dim))) return fail(rc);
     if (hipMemset(h->d_centroids + (size_t)nlist * dim, 0, (size_t)vs::kScanPadRows * dim * sizeof(float)) != hipSuccess) return fail(VS_ERR_DEVICE);
-    if ((rc = dev_alloc(&h->d_cnorm, (size_t)nlist + 64))) return fail(rc);
-    if ((rc = dev_alloc(&h->d_offsets, (size_t)nlist + 1))) return fail(rc);
-    if ((rc = dev_alloc(&h->d_r2o, (size_t)std::max<int64_t>(n_local, 1)))) return fail(rc);
+    if ((rc = h->d_cnorm.alloc((size_t)nlist + 64))) return fail(rc);
+    if ((rc = h->d_offsets.alloc((size_t)nlist + 1))) return fail(rc);
+    if ((rc = h->d_r2o.alloc((size_t)std::max<int64_t>(n_local, 1)))) return fail(rc);
     hipError_t e;
     if ((e = hipMemset(h->d_cnorm, 0, ((size_t)nlist + 64) * sizeof(float))) != hipSuccess ||
         (e = hipMemcpy(h->d_centroids, centroids, (size_t)nlist * dim * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess ||
@@ -2005,8 +1939,8 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
                     r2o_t[R] = loc_r2o[row];
                 }
             for (size_t i = 0; i < cl.size(); ++i) ctr0.push_back(cr0[i] + tdelta[cl[i]]);
-            if ((rc = dev_alloc(&h->d_vecs_t8, tb.size())) || (rc = dev_alloc(&h->d_nrh_t, n_t)) || (rc = dev_alloc(&h->d_rterm_t, n_t)) ||
-                (rc = dev_alloc(&h->d_r2o_t, n_t)) || (rc = dev_alloc(&h->d_tdelta, tdelta.size())) || (rc = dev_alloc(&h->d_chunk_trow0, ctr0.size())))
+            if ((rc = h->d_vecs_t8.alloc(tb.size())) || (rc = h->d_nrh_t.alloc(n_t)) || (rc = h->d_rterm_t.alloc(n_t)) ||
+                (rc = h->d_r2o_t.alloc(n_t)) || (rc = h->d_tdelta.alloc(tdelta.size())) || (rc = h->d_chunk_trow0.alloc(ctr0.size())))
                 return fail(rc);
             if ((e = hipMemcpy(h->d_vecs_t8, tb.data(), tb.size(), hipMemcpyHostToDevice)) != hipSuccess ||
                 (e = hipMemcpy(h->d_nrh_t, nrh_t.data(), n_t * 4, hipMemcpyHostToDevice)) != hipSuccess ||
@@ -2019,9 +1953,9 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
             }
         }
         if (h->n_chunks > 0) {
-            if ((rc = dev_alloc(&h->d_chunk_list, cl.size()))) return fail(rc);
-            if ((rc = dev_alloc(&h->d_chunk_row0, cl.size()))) return fail(rc);
-            if ((rc = dev_alloc(&h->d_chunk_rows, cl.size()))) return fail(rc);
+            if ((rc = h->d_chunk_list.alloc(cl.size()))) return fail(rc);
+            if ((rc = h->d_chunk_row0.alloc(cl.size()))) return fail(rc);
+            if ((rc = h->d_chunk_rows.alloc(cl.size()))) return fail(rc);
             h->n_units_max = 0;
             for (int32_t r : crn) h->n_units_max += (r + 31) >> 5;
             if ((e = hipMemcpy(h->d_chunk_list, cl.data(), cl.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
@@ -2076,37 +2010,20 @@ static int ivf_build_impl(const float* base_host, int64_t n_rows, int dim, int n
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     const int num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    float *d_x = nullptr, *d_norm = nullptr, *d_cents = nullptr, *d_best_d = nullptr;
-    int32_t *d_best_i = nullptr, *d_counts = nullptr;
-    unsigned long long* d_acc = nullptr;
-    double* d_shift = nullptr;
-    auto cleanup = [&]() {
-        void* ptrs[] = {d_x, d_norm, d_cents, d_best_d, d_best_i, d_counts, d_acc, d_shift};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-    };
-#define BUILD_CHK(expr)                                                                \
-    do {                                                                               \
-        hipError_t _e = (expr);                                                        \
-        if (_e != hipSuccess) {                                                        \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));              \
-            cleanup();                                                                 \
-            return VS_ERR_DEVICE;                                                      \
-        }                                                                              \
-    } while (0)
+    vs::DevBuf<float> d_x, d_norm, d_cents, d_best_d;
+    vs::DevBuf<int32_t> d_best_i, d_counts;
+    vs::DevBuf<unsigned long long> d_acc;
+    vs::DevBuf<double> d_shift;
     const int nlist_pad = (nlist + 31) & ~31;
-    BUILD_CHK(hipMalloc(&d_x, ((size_t)n_rows + vs::kScanPadRows) * dim * sizeof(float)));
-    BUILD_CHK(hipMemset(d_x + (size_t)n_rows * dim, 0, (size_t)vs::kScanPadRows * dim * sizeof(float)));
-    BUILD_CHK(hipMalloc(&d_norm, ((size_t)n_rows + 64) * sizeof(float)));
-    BUILD_CHK(hipMalloc(&d_cents, (size_t)nlist_pad * dim * sizeof(float)));
-    BUILD_CHK(hipMalloc(&d_best_d, (size_t)n_rows * sizeof(float)));
-    BUILD_CHK(hipMalloc(&d_best_i, (size_t)n_rows * sizeof(int32_t)));
-    BUILD_CHK(hipMalloc(&d_counts, (size_t)nlist * sizeof(int32_t)));
-    BUILD_CHK(hipMalloc(&d_acc, (size_t)nlist * dim * sizeof(unsigned long long)));
-    BUILD_CHK(hipMalloc(&d_shift, (size_t)nlist * sizeof(double)));
-    BUILD_CHK(hipMemcpy(d_x, base_host, (size_t)n_rows * dim * sizeof(float), hipMemcpyHostToDevice));
-    BUILD_CHK(hipMemset(d_norm, 0, ((size_t)n_rows + 64) * sizeof(float)));
-    BUILD_CHK(vs::launch_row_sqnorm(d_x, n_rows, dim, d_norm, nullptr));
+    if ((rc = d_x.alloc(((size_t)n_rows + vs::kScanPadRows) * dim))) return rc;
+    HIPCHK(hipMemset(d_x + (size_t)n_rows * dim, 0, (size_t)vs::kScanPadRows * dim * sizeof(float)));
+    if ((rc = d_norm.alloc((size_t)n_rows + 64)) || (rc = d_cents.alloc((size_t)nlist_pad * dim)) || (rc = d_best_d.alloc((size_t)n_rows)) ||
+        (rc = d_best_i.alloc((size_t)n_rows)) || (rc = d_counts.alloc((size_t)nlist)) || (rc = d_acc.alloc((size_t)nlist * dim)) ||
+        (rc = d_shift.alloc((size_t)nlist)))
+        return rc;
+    HIPCHK(hipMemcpy(d_x, base_host, (size_t)n_rows * dim * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_norm, 0, ((size_t)n_rows + 64) * sizeof(float)));
+    HIPCHK(vs::launch_row_sqnorm(d_x, n_rows, dim, d_norm, nullptr));
     // initial centroids: k-means++ (D^2 sampling), sklearn's default for the reference's KMeans(random_state=42, n_init=1),
     // create_ivf_model_reordered.py:97-103.  sklearn's RNG stream and its greedy multi-trial variant are not
     // reproduced (VSEARCH_KMEANS_INIT=random: nlist distinct random rows instead).
@@ -2120,7 +2037,7 @@ static int ivf_build_impl(const float* base_host, int64_t n_rows, int dim, int n
         };
         const char* init_env = getenv("VSEARCH_KMEANS_INIT");
         const bool random_init = init_env && std::string(init_env) == "random";
-        BUILD_CHK(hipMemset(d_cents, 0, (size_t)nlist_pad * dim * sizeof(float)));
+        HIPCHK(hipMemset(d_cents, 0, (size_t)nlist_pad * dim * sizeof(float)));
         if (random_init) {
             std::vector<float> init((size_t)nlist_pad * dim, 0.f);
             std::vector<bool> used((size_t)n_rows, false);
@@ -2130,22 +2047,21 @@ static int ivf_build_impl(const float* base_host, int64_t n_rows, int dim, int n
                 used[(size_t)r] = true;
                 std::memcpy(&init[(size_t)c * dim], base_host + r * dim, (size_t)dim * sizeof(float));
             }
-            BUILD_CHK(hipMemcpy(d_cents, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_cents, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice));
         } else {
             const int n_blocks = (int)((n_rows + vs::kKppBlockRows - 1) / vs::kKppBlockRows);
-            double* d_bsum = nullptr;
-            BUILD_CHK(hipMalloc(&d_bsum, (size_t)n_blocks * sizeof(double)));
+            vs::DevBuf<double> d_bsum;
+            if ((rc = d_bsum.alloc((size_t)n_blocks))) return rc;
             const int64_t first = (int64_t)(next() % (uint64_t)n_rows);
             hipError_t e = hipMemcpy(d_cents, d_x + first * dim, (size_t)dim * sizeof(float), hipMemcpyDeviceToDevice);
             // d_best_d doubles as the running min squared distance (+inf to start with)
-            if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_best_d), 0x7f800000, (size_t)n_rows, nullptr);
+            if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_best_d.get()), 0x7f800000, (size_t)n_rows, nullptr);
             for (int c = 1; c < nlist && e == hipSuccess; ++c) {
                 const double u = (double)(next() >> 11) * (1.0 / 9007199254740992.0);  // [0, 1)
                 e = vs::launch_kpp_step(d_x, d_norm, n_rows, d_cents, c, d_best_d, d_bsum, n_blocks, u, nullptr);
             }
             if (e == hipSuccess) e = hipDeviceSynchronize();
-            (void)hipFree(d_bsum);
-            BUILD_CHK(e);
+            HIPCHK(e);
         }
     }
     // sklearn's stopping rule: sum of squared centre shifts <= tol * mean per-feature variance
@@ -2168,7 +2084,7 @@ static int ivf_build_impl(const float* base_host, int64_t n_rows, int dim, int n
     int grid, tp;
     scan_geometry(n_rows, num_cus, grid, tp);
     auto assign_pass = [&]() -> hipError_t {
-        hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_best_d), 0x7f800000, (size_t)n_rows, nullptr);
+        hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_best_d.get()), 0x7f800000, (size_t)n_rows, nullptr);
         if (e != hipSuccess) return e;
         e = hipMemsetAsync(d_best_i, 0xff, (size_t)n_rows * sizeof(int32_t), nullptr);
         if (e != hipSuccess) return e;
@@ -2203,9 +2119,9 @@ static int ivf_build_impl(const float* base_host, int64_t n_rows, int dim, int n
     int it = 0;
     std::vector<double> shift((size_t)nlist);
     for (; it < max_iter; ++it) {
-        BUILD_CHK(assign_pass());
-        BUILD_CHK(vs::launch_kmeans_update(d_x, d_best_i, n_rows, nlist, d_cents, d_acc, d_counts, d_shift, nullptr));
-        BUILD_CHK(hipMemcpy(shift.data(), d_shift, (size_t)nlist * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(assign_pass());
+        HIPCHK(vs::launch_kmeans_update(d_x, d_best_i, n_rows, nlist, d_cents, d_acc, d_counts, d_shift, nullptr));
+        HIPCHK(hipMemcpy(shift.data(), d_shift, (size_t)nlist * sizeof(double), hipMemcpyDeviceToHost));
         double total = 0;
         for (double v : shift) total += v;
         if (total <= tol_abs) {
@@ -2213,11 +2129,9 @@ static int ivf_build_impl(const float* base_host, int64_t n_rows, int dim, int n
             break;
         }
     }
-    BUILD_CHK(assign_pass());  // labels consistent with the final centroids
-    BUILD_CHK(hipMemcpy(assign_out, d_best_i, (size_t)n_rows * sizeof(int32_t), hipMemcpyDeviceToHost));
-    BUILD_CHK(hipMemcpy(centroids_out, d_cents, (size_t)nlist * dim * sizeof(float), hipMemcpyDeviceToHost));
-#undef BUILD_CHK
-    cleanup();
+    HIPCHK(assign_pass());  // labels consistent with the final centroids
+    HIPCHK(hipMemcpy(assign_out, d_best_i, (size_t)n_rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(centroids_out, d_cents, (size_t)nlist * dim * sizeof(float), hipMemcpyDeviceToHost));
     if (iters_done) *iters_done = it;
     return VS_OK;
 }
@@ -2417,6 +2331,7 @@ int vs_ivf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int
         const double t_start = now_ms();
         vs_timing tm{};
         if ((rc = ensure_pipe(h)) || (rc = ensure_wide_streams(h)) || (rc = ensure_ivf_host(h)) || (rc = order_begin(h, h->stream))) return rc;
+        settle_slots(h->ihs, {h->wide_stream[0], h->wide_stream[1], h->s_h2d, h->s_d2h});
         h->stage_on = true;
         h->stage_used = 0;
         HIPCHK(hipMemsetAsync(h->d_cand, 0, sizeof(unsigned long long), h->stream));
@@ -2490,7 +2405,6 @@ int vs_ivf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int
             S.q0 = -1;
             return VS_OK;
         };
-        for (auto& S : h->ihs) S.q0 = -1;  // (a call that failed half way may have left a chunk marked in flight)
         int c = 0;
         for (int64_t q0 = 0; q0 < nq; q0 += wchunk, ++c) {
             vs_index::IvfHostSlot& S = h->ihs[c & 1];
@@ -2655,38 +2569,31 @@ int rccl_ready() {
 struct vs_comm {
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1, device = 0;
-    hipStream_t s_coll = nullptr;
-    hipEvent_t ev_scan[2] = {}, ev_coll[2] = {};
+    vs::Stream s_coll;
+    vs::Event ev_scan[2], ev_coll[2];
     bool coll_used[2] = {false, false};
-    int32_t* d_loc[2] = {};   // this rank's lists of one launch group: [dists n*kin][ids n*kin] as 32-bit words
-    int32_t* d_gath[2] = {};  // [world] x the same
-    size_t cap_words = 0;     // per-rank capacity of d_loc
+    vs::DevBuf<int32_t> d_loc[2];   // this rank's lists of one launch group: [dists n*kin][ids n*kin] as 32-bit words
+    vs::DevBuf<int32_t> d_gath[2];  // [world] x the same
     // cluster-sharded IVF: the slices' blocks (probes | tau | slow) of one launch group, exchanged between its two halves
-    int32_t* d_blk[2] = {};   // this rank's block
-    int32_t* d_blkg[2] = {};  // [world] blocks
-    size_t blk_cap = 0;       // words per block
-    hipEvent_t ev_front[2] = {}, ev_probe[2] = {};
+    vs::DevBuf<int32_t> d_blk[2];   // this rank's block
+    vs::DevBuf<int32_t> d_blkg[2];  // [world] blocks
+    vs::Event ev_front[2], ev_probe[2];
 };
 
 namespace {
 
-int comm_reserve(vs_comm* c, size_t words) {
-    if (c->cap_words >= words) return VS_OK;
-    HIPCHK(hipDeviceSynchronize());
-    for (int i = 0; i < 2; ++i) {
-        if (c->d_loc[i]) (void)hipFree(c->d_loc[i]);
-        if (c->d_gath[i]) (void)hipFree(c->d_gath[i]);
-        c->d_loc[i] = c->d_gath[i] = nullptr;
-    }
-    c->cap_words = 0;
-    for (int i = 0; i < 2; ++i) {
-        int rc;
-        if ((rc = dev_alloc(&c->d_loc[i], words))) return rc;
-        if ((rc = dev_alloc(&c->d_gath[i], words * (size_t)c->world))) return rc;
-    }
-    c->cap_words = words;
-    return VS_OK;
+// two pairs of grow-only buffers of a communicator: `words` each in own[], `words` per rank in gath[] (the device is
+// synchronised before any of them is replaced)
+int reserve_pairs(vs::DevBuf<int32_t> (&own)[2], vs::DevBuf<int32_t> (&gath)[2], size_t words, int world) {
+    bool grow = false;
+    for (int i = 0; i < 2; ++i) grow |= own[i].size() < words || gath[i].size() < words * (size_t)world;
+    if (grow) HIPCHK(hipDeviceSynchronize());
+    int rc = VS_OK;
+    for (int i = 0; i < 2 && !rc; ++i)
+        if (!(rc = own[i].reserve(words))) rc = gath[i].reserve(words * (size_t)world);
+    return rc;
 }
+
 
 // groups of <= kMaxMulti batches: local top-kin of group g on `user` -> event -> (collective stream) all-gather + merge
 // into the caller's outputs; the local search of group g + 1 is enqueued on `user` right away and runs meanwhile.
@@ -2698,7 +2605,7 @@ int sharded_groups(vs_index* h, vs_comm* c, int n_batches, int B, int kin, int k
         set_error("index and communicator live on different devices");
         return VS_ERR_INVALID;
     }
-    int rc = comm_reserve(c, (size_t)(2 * kin + 1) * kMaxMulti * 32);
+    int rc = reserve_pairs(c->d_loc, c->d_gath, (size_t)(2 * kin + 1) * kMaxMulti * 32, c->world);
     if (rc) return rc;
     int g = 0;
     for (int b0 = 0; b0 < n_batches; b0 += kMaxMulti, ++g) {
@@ -2707,7 +2614,7 @@ int sharded_groups(vs_index* h, vs_comm* c, int n_batches, int B, int kin, int k
         const size_t n = (size_t)nb * B;         // queries of the group
         const size_t words = 2 * n * kin + (flags_dev ? n : 0);  // per rank: dists | ids | (brute force) the shard's own flags
         if (c->coll_used[buf]) HIPCHK(hipStreamWaitEvent(user, c->ev_coll[buf], 0));  // group g - 2 is done with the buffers
-        float* loc_d = reinterpret_cast<float*>(c->d_loc[buf]);
+        float* loc_d = reinterpret_cast<float*>(c->d_loc[buf].get());
         int32_t* loc_i = c->d_loc[buf] + n * kin;
         if ((rc = local(b0, nb, loc_d, loc_i, c->d_loc[buf] + 2 * n * kin, user))) return rc;
         HIPCHK(hipEventRecord(c->ev_scan[buf], user));
@@ -2785,17 +2692,12 @@ int vs_comm_create(const void* unique_id, int rank, int world, int device, vs_co
         delete c;
         return VS_ERR_DEVICE;
     }
-    hipError_t e = hipStreamCreateWithFlags(&c->s_coll, hipStreamNonBlocking);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipEventCreateWithFlags(&c->ev_scan[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_coll[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_front[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_probe[i], hipEventDisableTiming);
-    }
-    if (e != hipSuccess) {
-        set_error(std::string("vs_comm_create: ") + hipGetErrorString(e));
+    rc = c->s_coll.create();
+    for (int i = 0; i < 2 && !rc; ++i)
+        if (!(rc = c->ev_scan[i].create()) && !(rc = c->ev_coll[i].create()) && !(rc = c->ev_front[i].create())) rc = c->ev_probe[i].create();
+    if (rc) {
         vs_comm_destroy(c);
-        return VS_ERR_DEVICE;
+        return rc;
     }
     *out = c;
     return VS_OK;
@@ -2809,17 +2711,6 @@ void vs_comm_destroy(vs_comm* c) {
     (void)hipSetDevice(c->device);
     if (c->s_coll) (void)hipStreamSynchronize(c->s_coll);
     if (c->comm && rccl().lib) (void)rccl().CommDestroy(c->comm);
-    for (int i = 0; i < 2; ++i) {
-        if (c->d_loc[i]) (void)hipFree(c->d_loc[i]);
-        if (c->d_gath[i]) (void)hipFree(c->d_gath[i]);
-        if (c->ev_scan[i]) (void)hipEventDestroy(c->ev_scan[i]);
-        if (c->ev_coll[i]) (void)hipEventDestroy(c->ev_coll[i]);
-        if (c->d_blk[i]) (void)hipFree(c->d_blk[i]);
-        if (c->d_blkg[i]) (void)hipFree(c->d_blkg[i]);
-        if (c->ev_front[i]) (void)hipEventDestroy(c->ev_front[i]);
-        if (c->ev_probe[i]) (void)hipEventDestroy(c->ev_probe[i]);
-    }
-    if (c->s_coll) (void)hipStreamDestroy(c->s_coll);
     delete c;
 }
 
@@ -2888,21 +2779,8 @@ int vs_ivf_search_dev_sharded(vs_index* h, vs_comm* c, const float* queries_dev,
     // rank -- so that an exchange is in flight while the neighbouring group computes.  Group g uses lane g & 1.
     const int world = c->world, gb = h->ivf_gb;
     const size_t blk_words_max = (size_t)ivf_block_words(vs::kIvfWideBatches, kMaxNprobe);
-    if (c->blk_cap < blk_words_max) {
-        HIPCHK(hipDeviceSynchronize());
-        for (int i = 0; i < 2; ++i) {
-            if (c->d_blk[i]) (void)hipFree(c->d_blk[i]);
-            if (c->d_blkg[i]) (void)hipFree(c->d_blkg[i]);
-            c->d_blk[i] = c->d_blkg[i] = nullptr;
-        }
-        c->blk_cap = 0;
-        for (int i = 0; i < 2; ++i) {
-            if ((rc = dev_alloc(&c->d_blk[i], blk_words_max))) return rc;
-            if ((rc = dev_alloc(&c->d_blkg[i], blk_words_max * (size_t)world))) return rc;
-        }
-        c->blk_cap = blk_words_max;
-    }
-    if ((rc = comm_reserve(c, (size_t)2 * gb * 32 * k))) return rc;
+    if ((rc = reserve_pairs(c->d_blk, c->d_blkg, blk_words_max, world))) return rc;
+    if ((rc = reserve_pairs(c->d_loc, c->d_gath, (size_t)2 * gb * 32 * k, c->world))) return rc;
     struct Grp {
         int b0, nb, sbb;
     };
@@ -2919,7 +2797,7 @@ int vs_ivf_search_dev_sharded(vs_index* h, vs_comm* c, const float* queries_dev,
         const Grp G = group_of(g);
         const int lane = g & 1;
         const size_t n = (size_t)G.nb * B, words = 2 * n * k;
-        float* loc_d = reinterpret_cast<float*>(c->d_loc[lane]);
+        float* loc_d = reinterpret_cast<float*>(c->d_loc[lane].get());
         int32_t* loc_i = c->d_loc[lane] + n * k;
         HIPCHK(hipStreamWaitEvent(user, c->ev_probe[lane], 0));
         if (c->coll_used[lane]) HIPCHK(hipStreamWaitEvent(user, c->ev_coll[lane], 0));  // group g - 2's merge has read d_gath
@@ -2929,7 +2807,7 @@ int vs_ivf_search_dev_sharded(vs_index* h, vs_comm* c, const float* queries_dev,
         HIPCHK(hipStreamWaitEvent(c->s_coll, c->ev_scan[lane], 0));
         NCCLCHK(rccl().AllGather(c->d_loc[lane], c->d_gath[lane], words, ncclInt32, c->comm, c->s_coll));
         vs::MergeParams m{};
-        m.part_d = reinterpret_cast<const float*>(c->d_gath[lane]);
+        m.part_d = reinterpret_cast<const float*>(c->d_gath[lane].get());
         m.part_i = c->d_gath[lane] + n * k;
         m.G = world;
         m.kin = k;
@@ -2994,18 +2872,13 @@ int vs_ivf_search_dev_vshards(vs_index* const* shards, int G, const float* queri
         const int gb = h0->ivf_gb;
         const size_t blk_max = (size_t)ivf_block_words(vs::kIvfWideBatches, kMaxNprobe);
         const size_t loc_max = (size_t)2 * gb * 32 * k;
-        if (!h0->vsh_blk || h0->vsh_loc_words < loc_max * G) {
-            HIPCHK(hipStreamSynchronize(s));
-            if (h0->vsh_blk) (void)hipFree(h0->vsh_blk);
-            if (h0->vsh_loc) (void)hipFree(h0->vsh_loc);
-            h0->vsh_blk = h0->vsh_loc = nullptr;
-            if ((rc = dev_alloc(&h0->vsh_blk, blk_max * G)) || (rc = dev_alloc(&h0->vsh_loc, loc_max * G))) return rc;
-            h0->vsh_loc_words = loc_max * G;
-        }
-        std::vector<hipEvent_t> ev;
+        if (h0->vsh_blk.size() < blk_max * G || h0->vsh_loc.size() < loc_max * G) HIPCHK(hipStreamSynchronize(s));
+        if ((rc = h0->vsh_blk.reserve(blk_max * G)) || (rc = h0->vsh_loc.reserve(loc_max * G))) return rc;
+        std::vector<vs::Event> ev;
         if (rank_ms) {
             ev.resize((size_t)4 * G);
-            for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+            for (auto& e : ev)
+                if ((rc = e.create(true))) return rc;
             for (int r = 0; r < G; ++r) rank_ms[r] = 0;
         }
         for (int b0 = 0; b0 < n_batches && !rc; b0 += gb) {
@@ -3029,7 +2902,7 @@ int vs_ivf_search_dev_vshards(vs_index* const* shards, int G, const float* queri
             }
             if (rc) break;
             vs::MergeParams m{};
-            m.part_d = reinterpret_cast<const float*>(h0->vsh_loc);
+            m.part_d = reinterpret_cast<const float*>(h0->vsh_loc.get());
             m.part_i = h0->vsh_loc + n * k;
             m.G = G;
             m.kin = k;
@@ -3048,7 +2921,6 @@ int vs_ivf_search_dev_vshards(vs_index* const* shards, int G, const float* queri
                 }
             }
         }
-        for (auto& e : ev) (void)hipEventDestroy(e);
         return rc;
     });
 }
@@ -3087,15 +2959,8 @@ struct ShBuf {
 int sh_reserve(vs_index* o, int G, int k1, ShBuf& B) {
     const size_t main_words = (size_t)(2 * k1 + 1) * kMaxMulti * 32;
     const size_t total = (size_t)G * (main_words + 32 + (size_t)32 * kTieDense + kShPackWords + 2);
-    if (o->sh_words < total) {
-        HIPCHK(hipDeviceSynchronize());
-        if (o->d_sh) (void)hipFree(o->d_sh);
-        o->d_sh = nullptr;
-        o->sh_words = 0;
-        int rc = dev_alloc(&o->d_sh, total);
-        if (rc) return rc;
-        o->sh_words = total;
-    }
+    if (o->d_sh.size() < total) HIPCHK(hipDeviceSynchronize());
+    if (int rc = o->d_sh.reserve(total)) return rc;
     B.main_words = main_words;
     B.main = o->d_sh;
     B.tau = B.main + (size_t)G * main_words;
@@ -3231,20 +3096,14 @@ int resolve_ties_shards(const BfShards& S, const ShBuf& Bf, const std::vector<in
                 ldm = std::max<int64_t>(ldm, ((int64_t)meta[2 * g] + 15) & ~int64_t(15));
                 total += meta[2 * g];
             }
-            if (o->sh_row_words < (size_t)G * ldm) {
-                HIPCHK(hipStreamSynchronize(st));
-                if (o->d_sh_row) (void)hipFree(o->d_sh_row);
-                o->d_sh_row = nullptr;
-                o->sh_row_words = 0;
-                if ((rc = dev_alloc(&o->d_sh_row, (size_t)G * ldm))) return rc;
-                o->sh_row_words = (size_t)G * ldm;
-            }
+            if (o->d_sh_row.size() < (size_t)G * ldm) HIPCHK(hipStreamSynchronize(st));
+            if ((rc = o->d_sh_row.reserve((size_t)G * ldm))) return rc;
             for (size_t i = 0; i < S.hs.size(); ++i) {
                 vs_index* h = S.hs[i];
                 const int g = S.first + (int)i;
                 if ((rc = scores_dev(h, h->d_vecs, h->d_norm, h->n_rows, o->d_q + (size_t)b * vs::kDim, 1, o->d_sh_row + (size_t)g * ldm, ldm, st))) return rc;
             }
-            if ((rc = S.exchange(reinterpret_cast<int32_t*>(o->d_sh_row), (size_t)ldm))) return rc;
+            if ((rc = S.exchange(reinterpret_cast<int32_t*>(o->d_sh_row.get()), (size_t)ldm))) return rc;
             std::vector<float> row((size_t)total);
             int64_t at = 0;
             for (int g = 0; g < G; ++g) {

@@ -30,12 +30,14 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/vsearch.h"
 #include "vs_host.h"
+#include "vs_res.h"
 
 using vs::set_error;
 
@@ -384,30 +386,20 @@ struct vs_q8 {
     vs_q8_encodings enc{};
     float inv_in = 0, mult = 0;
     int num_cus = 256;
-    int8_t* d_wq = nullptr;      // [n_pad][128]
-    int32_t* d_wterm = nullptr;  // [n_pad]
-    int8_t* d_q8 = nullptr;      // [kGroup][32][128] quantised queries of up to kGroup batches
-    int32_t* d_cq = nullptr;     // [kGroup][32]
-    float* d_q = nullptr;        // [32][128] staging of host queries
-    uint8_t* d_scores = nullptr; // [32][n_pad]  the runner's output buffer (QnnRunner.cpp:322-323)
-    u64* d_cand = nullptr;       // [32][n_chunks][kCand]
-    int32_t* d_ids = nullptr;    // [32][16]
-    uint8_t* d_top = nullptr;    // [32][16]
+    vs::DevBuf<int8_t> d_wq;       // [n_pad][128]
+    vs::DevBuf<int32_t> d_wterm;   // [n_pad]
+    vs::DevBuf<int8_t> d_q8;       // [kGroup][32][128] quantised queries of up to kGroup batches
+    vs::DevBuf<int32_t> d_cq;      // [kGroup][32]
+    vs::DevBuf<float> d_q;         // [32][128] staging of host queries
+    vs::DevBuf<uint8_t> d_scores;  // [32][n_pad]  the runner's output buffer (QnnRunner.cpp:322-323)
+    vs::DevBuf<u64> d_cand;        // [32][n_chunks][kCand]
+    vs::DevBuf<int32_t> d_ids;     // [32][16]
+    vs::DevBuf<uint8_t> d_top;     // [32][16]
     int n_chunks = 0;
-    hipStream_t stream = nullptr;
+    vs::Stream stream;
 };
 
 namespace {
-
-void q8_free(vs_q8* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    void* p[] = {h->d_wq, h->d_wterm, h->d_q8, h->d_cq, h->d_q, h->d_scores, h->d_cand, h->d_ids, h->d_top};
-    for (void* x : p)
-        if (x) (void)hipFree(x);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
 
 // the reference's quantiser on the host (database side, once): QnnRunner.cpp:50-54, then the weight offset
 inline uint8_t quant_host(float x, float inv_scale, int w_off) {
@@ -471,7 +463,7 @@ int q8_create_impl(const float* base_host, int64_t n_rows, int dim, const vs_q8_
         return VS_ERR_INVALID;
     }
     HIPCHK(hipSetDevice(device));
-    vs_q8* h = new (std::nothrow) vs_q8();
+    std::unique_ptr<vs_q8> h(new (std::nothrow) vs_q8());  // (released, with what it holds, on every early return)
     if (!h) {
         set_error("out of host memory");
         return VS_ERR_NOMEM;
@@ -484,22 +476,20 @@ int q8_create_impl(const float* base_host, int64_t n_rows, int dim, const vs_q8_
     h->inv_in = 1.0f / enc.input_scale;                                 // QnnRunner.cpp:619
     h->mult = (enc.input_scale * enc.weight_scale) / enc.output_scale;  // accumulator unit -> output unit
     h->n_chunks = (int)((n_rows + kChunkRows - 1) / kChunkRows);
-    auto fail = [&](int rc) {
-        q8_free(h);
-        return rc;
-    };
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) h->num_cus = prop.multiProcessorCount;
     // database -> uint8 (stored minus 128) + 128 * row sums, in slabs of 1 M rows
-    if (hipMalloc((void**)&h->d_wq, (size_t)h->n_pad * kDim) != hipSuccess || hipMalloc((void**)&h->d_wterm, (size_t)h->n_pad * 4) != hipSuccess ||
-        hipMalloc((void**)&h->d_q8, (size_t)kGroup * kBatch * kDim) != hipSuccess || hipMalloc((void**)&h->d_cq, (size_t)kGroup * kBatch * 4) != hipSuccess ||
-        hipMalloc((void**)&h->d_q, kBatch * kDim * 4) != hipSuccess || hipMalloc((void**)&h->d_scores, (size_t)kBatch * h->n_pad) != hipSuccess ||
-        hipMalloc((void**)&h->d_cand, (size_t)kBatch * h->n_chunks * kCand * 8) != hipSuccess ||
-        hipMalloc((void**)&h->d_ids, kBatch * kCand * 4) != hipSuccess || hipMalloc((void**)&h->d_top, kBatch * kCand) != hipSuccess ||
-        hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        set_error("vs_q8_create: device allocation failed");
-        return fail(VS_ERR_DEVICE);
-    }
+    int rc;
+    if ((rc = h->d_wq.alloc((size_t)h->n_pad * kDim))) return rc;
+    if ((rc = h->d_wterm.alloc((size_t)h->n_pad))) return rc;
+    if ((rc = h->d_q8.alloc((size_t)kGroup * kBatch * kDim))) return rc;
+    if ((rc = h->d_cq.alloc((size_t)kGroup * kBatch))) return rc;
+    if ((rc = h->d_q.alloc((size_t)kBatch * kDim))) return rc;
+    if ((rc = h->d_scores.alloc((size_t)kBatch * h->n_pad))) return rc;
+    if ((rc = h->d_cand.alloc((size_t)kBatch * h->n_chunks * kCand))) return rc;
+    if ((rc = h->d_ids.alloc((size_t)kBatch * kCand))) return rc;
+    if ((rc = h->d_top.alloc((size_t)kBatch * kCand))) return rc;
+    if ((rc = h->stream.create())) return rc;
     const float inv_w = 1.0f / enc.weight_scale;
     const int64_t slab = 1 << 20;
     std::vector<int8_t> bytes((size_t)std::min(slab, h->n_pad) * kDim);
@@ -518,10 +508,10 @@ int q8_create_impl(const float* base_host, int64_t n_rows, int dim, const vs_q8_
         if (hipMemcpy(h->d_wq + (size_t)r0 * kDim, bytes.data(), (size_t)rows * kDim, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(h->d_wterm + r0, term.data(), (size_t)rows * 4, hipMemcpyHostToDevice) != hipSuccess) {
             set_error("vs_q8_create: upload failed");
-            return fail(VS_ERR_DEVICE);
+            return VS_ERR_DEVICE;
         }
     }
-    *out = h;
+    *out = h.release();
     return VS_OK;
 }
 
@@ -571,7 +561,12 @@ int vs_q8_create(const float* base_host, int64_t n_rows, int dim, const vs_q8_en
     return guarded([&]() -> int { return q8_create_impl(base_host, n_rows, dim, enc, device, id_offset, out); });
 }
 
-void vs_q8_destroy(vs_q8* h) { q8_free(h); }
+void vs_q8_destroy(vs_q8* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    (void)hipDeviceSynchronize();  // (the handles release without waiting for queued work)
+    delete h;
+}
 
 int64_t vs_q8_num_docs(const vs_q8* h) { return h ? h->n_rows : 0; }
 int vs_q8_dim(const vs_q8* h) { return h ? kDim : 0; }
