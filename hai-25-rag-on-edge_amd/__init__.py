@@ -174,6 +174,7 @@ def lib():
         "vs_index_rows": (i64, [vp]),
         "vs_index_dim": (i32, [vp]),
         "vs_index_nlist": (i32, [vp]),
+        "vs_f32_filter_bound": (C.c_float, [C.c_double] * 6),
         "vs_destroy": (None, [vp]),
     }
     for name, (res, args) in sig.items():

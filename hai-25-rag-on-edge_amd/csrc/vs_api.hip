@@ -44,7 +44,8 @@ constexpr int kMaxLanes = 4;
 constexpr int kMaxMulti = 32;  // batches per persistent scan launch
 constexpr int kOneMaxBatches = 4;  // calls of fewer batches take one single-call scan launch per batch (fp32 rows)
 constexpr int kOneMaxQueries = 16;  // ... when a batch holds at most this many queries
-constexpr int kPairMinTiles = 96;   // tiles per workgroup and pass from which the fp32 streaming scan pairs batches
+constexpr int kPairMinTiles = 96;
+constexpr int kFilterNb4MinTiles = 0;  // tiles per workgroup and pass from which the bf16 prefilter takes four batches per pass (else two)   // tiles per workgroup and pass from which the fp32 streaming scan pairs batches
 constexpr int kIvfGroupDefault = 256; // batches per launch group of an unsharded IVF index (VSEARCH_IVF_GROUP): 46 us per 1024 queries against 79 with groups of 32
 constexpr int kIvfGroupMax = 256;     // ... at most (8 super-batches of 32): also the group of an index sharded 8 ways
 constexpr int kIvfShardMaxWorld = 16; // ranks the cluster-sharded pipeline is compiled for (one super-batch per rank)
@@ -83,6 +84,10 @@ struct vs_index {
 
     vs::DevBuf<float> d_vecs;   // [n_rows][128]
     vs::DevBuf<float> d_norm;   // [n_rows + 64]
+    // the bf16 prefilter of the fp32 streaming scan (scan_f32f_kernel): shard constants, and whether every row is well
+    // scaled (otherwise the index keeps scan_f32s_kernel)
+    vs::FilterStats fstats{};
+    bool filter_ok = false;
     // int8 data path: only when every base value is an integer in [0, 255]
     vs::DevBuf<int8_t> d_vecs_u8;   // [n_rows][128] bytes (x - 128)
     vs::DevBuf<int32_t> d_rterm;    // [n_rows + 64] ||b||^2 - 256 * sum(b - 128)
@@ -128,6 +133,8 @@ struct vs_index {
         vs::DevBuf<float> seed_qnorm; // [kMaxMulti][32]   scratch of launch_seed
         vs::DevBuf<float> qfrag;      // [kMaxMulti][2][8][64][4] queries in MFMA B-fragment order (fp32 streaming scan)
         vs::DevBuf<int8_t> q8frag;    // [kMaxMulti][2][2][64][16] byte queries in B-fragment order (wide int8 scan)
+        vs::DevBuf<uint16_t> qbf;     // [kMaxMulti][2][4][64][8] bf16 queries in B-fragment order (bf16 prefilter)
+        vs::DevBuf<float> qbound;     // [kMaxMulti][32] the prefilter's error bound per query
         vs::DevBuf<float> seed_wmin;  // [kMaxMulti][kSeedWaves][32]
         vs::DevBuf<float> tau0;       // [kMaxMulti][32]   bounds of the current multi-batch launch
         // wide int8 scan (several batches per pass over the rows): prepared queries + per-query candidate lists (ensure_wide)
@@ -325,6 +332,8 @@ int alloc_scratch(vs_index* h) {
             if ((rc = L.seed_qnorm.alloc((size_t)kMaxMulti * 32))) return rc;
             if ((rc = L.qfrag.alloc((size_t)kMaxMulti * 4096))) return rc;
             if ((rc = L.q8frag.alloc((size_t)kMaxMulti * 4096))) return rc;
+            if ((rc = L.qbf.alloc((size_t)kMaxMulti * 4096))) return rc;
+            if ((rc = L.qbound.alloc((size_t)kMaxMulti * 32))) return rc;
             if ((rc = L.seed_wmin.alloc((size_t)kMaxMulti * vs::kSeedWaves * 32))) return rc;
             if ((rc = L.tau0.alloc((size_t)kMaxMulti * 32))) return rc;
             if ((rc = L.done.alloc(kMaxMulti))) return rc;
@@ -357,6 +366,20 @@ int upload_vectors(vs_index* h, const float* host, int64_t rows) {
     if (rows > 0) {
         HIPCHK(hipMemcpy(h->d_vecs, host, (size_t)rows * vs::kDim * sizeof(float), hipMemcpyHostToDevice));
         HIPCHK(vs::launch_row_sqnorm(h->d_vecs, rows, vs::kDim, h->d_norm, nullptr));
+        if (h->kind == 0) {  // brute force: the bf16 prefilter's shard constants
+            vs::DevBuf<unsigned long long> st;
+            if ((rc = st.alloc(4))) return rc;
+            HIPCHK(hipMemset(st, 0, 4 * sizeof(unsigned long long)));
+            HIPCHK(vs::launch_row_filter_stats(h->d_vecs, rows, st, nullptr));
+            unsigned long long v[4];
+            HIPCHK(hipMemcpy(v, st, sizeof(v), hipMemcpyDeviceToHost));
+            double m[3];
+            for (int i = 0; i < 3; ++i) memcpy(&m[i], &v[i], sizeof(double));
+            h->fstats.bmax = sqrt(m[0]);
+            h->fstats.emax = sqrt(m[1]);
+            h->fstats.bpmax = sqrt(m[2]);
+            h->filter_ok = v[3] == 0 && std::isfinite(m[0]) && std::isfinite(m[2]);
+        }
         HIPCHK(hipDeviceSynchronize());
     }
     return VS_OK;
@@ -463,6 +486,14 @@ int g_f32_pair = [] {
     return e ? atoi(e) : 1;
 }();
 
+// tuning knob (VSEARCH_F32_FILTER=0): seeded streaming launches on fp32 rows run scan_f32s_kernel (every dot product on fp32
+// MFMA) instead of the bf16 prefilter with the exact fp32 recheck (scan_f32f_kernel; default 1, on shards whose rows are well
+// scaled).  VSEARCH_F32_PAIR applies to scan_f32s_kernel only.
+int g_f32_filter = [] {
+    const char* e = getenv("VSEARCH_F32_FILTER");
+    return e ? atoi(e) : 1;
+}();
+
 // tuning knob (VSEARCH_STREAM=0): seeded launches use the per-batch scan kernels (lane lists + workgroup merge) instead of
 // the streaming scans
 int g_stream = [] {
@@ -530,6 +561,7 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     // ticket per workgroup and write survivors to candidate lists -- no barrier, no workgroup merge, no per-batch prologue.
     const bool i8_seed = h->d_vecs_u8 && h->metric == VS_METRIC_L2 && g_seed_i8;
     const bool stream = seeded && g_stream && (use_u8 ? (g_i8_wide > 0 && i8_seed) : true);
+    const bool f32_filter = stream && !use_u8 && g_f32_filter && h->filter_ok;
     if (!seeded && !use_u8 && nb < kOneMaxBatches && B <= kOneMaxQueries) {
         // a short call on the fp32 rows: one launch per batch (lane lists, workgroup ranking, the last workgroup merges).
         // Batches of more than 16 queries stay with the per-batch scan below: with two column blocks per tile the
@@ -597,6 +629,11 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
             sp.zero_words = (int)zero_words;
         }
         sp.qfrag = L.qfrag;
+        if (f32_filter) {
+            sp.qbf = L.qbf;
+            sp.qbound = L.qbound;
+            sp.fstats = h->fstats;
+        }
         if (i8_seed) {  // queries as bytes + constant terms + the "not byte valued" verdict: int8 seed and wide int8 scan
             sp.q8 = L.wide8.q8;
             sp.q8frag = L.q8frag;
@@ -668,6 +705,11 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
             // two batches per pass pay where a workgroup has many tiles per pass (1 M rows: 244, + 14 %); on a small shard
             // (125 K rows: 30 tiles) the per-pass operand fetch and drain weigh more than the halved traffic saves (- 15 %)
             sp.batches_per_pass = (nb >= 2 && (g_f32_pair > 1 || (g_f32_pair == 1 && tiles_total / sgrid >= kPairMinTiles))) ? 2 : 1;
+            if (f32_filter) {
+                sp.qbf = L.qbf;
+                sp.qbound = L.qbound;
+                sp.batches_per_pass = tiles_total / sgrid >= kFilterNb4MinTiles ? 4 : 2;
+            }
             HIPCHK(vs::launch_scan_f32_stream(sp, sgrid, s));
             prof_end(h, 0, s);
         }
@@ -1412,6 +1454,9 @@ int vs_device_count(void) {
 
 int64_t vs_index_rows(const vs_index* h) { return h ? h->n_total : 0; }
 int vs_index_dim(const vs_index* h) { return h ? h->dim : 0; }
+float vs_f32_filter_bound(double eq, double nq, double nqp, double bmax, double emax, double bpmax) {
+    return vs::filter_bound(eq, nq, nqp, vs::FilterStats{bmax, emax, bpmax});
+}
 int vs_index_nlist(const vs_index* h) { return h ? h->nlist : 0; }
 void vs_destroy(vs_index* h) {
     if (!h) return;

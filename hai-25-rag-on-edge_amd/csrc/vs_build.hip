@@ -41,6 +41,54 @@ hipError_t launch_row_sqnorm(const float* v, int64_t rows, int dim, float* out, 
     return hipGetLastError();
 }
 
+// Shard constants of the bf16 prefilter (FilterStats): 8 threads per row as above, in double (exact squares of the
+// rounding residuals, which in float could fall below the normal range), maxima by integer atomics on the bits of
+// non-negative doubles (their order is the integers' order).
+__device__ __forceinline__ bool filter_scaled(float x) {
+    const float a = fabsf(x);
+    return a == 0.f || (a >= (float)kFiltLo && a <= (float)kFiltHi);  // (false for inf and NaN)
+}
+__global__ __launch_bounds__(256) void row_filter_stats_kernel(const float* __restrict__ v, int64_t rows,
+                                                               unsigned long long* __restrict__ out) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t row = gid >> 3;
+    const int j = (int)(gid & 7);
+    const bool ok = row < rows;
+    const float* src = v + (ok ? row : 0) * kDim;
+    double n2 = 0.0, e2 = 0.0, p2 = 0.0;
+    bool bad = false;
+    for (int i = 0; i < kDim; i += 8) {
+        const float x = src[i + j];
+        const float xp = (float)(__bf16)x;
+        bad = bad || !filter_scaled(x);
+        const double d = (double)x - (double)xp;
+        n2 = fma((double)x, (double)x, n2);
+        e2 = fma(d, d, e2);
+        p2 = fma((double)xp, (double)xp, p2);
+    }
+#pragma unroll
+    for (int u = 1; u < 8; u <<= 1) {
+        n2 += __shfl_xor(n2, u);
+        e2 += __shfl_xor(e2, u);
+        p2 += __shfl_xor(p2, u);
+    }
+    const bool any_bad = __any(ok && bad);
+    if (ok && j == 0) {
+        atomicMax(out + 0, (unsigned long long)__double_as_longlong(n2));
+        atomicMax(out + 1, (unsigned long long)__double_as_longlong(e2));
+        atomicMax(out + 2, (unsigned long long)__double_as_longlong(p2));
+    }
+    if (any_bad && (threadIdx.x & 63) == 0) atomicMax(out + 3, 1ull);
+}
+
+hipError_t launch_row_filter_stats(const float* v, int64_t rows, unsigned long long* out, hipStream_t s) {
+    if (rows <= 0) return hipSuccess;
+    const int64_t threads = rows * 8;
+    const int grid = (int)((threads + 255) / 256);
+    hipLaunchKernelGGL(row_filter_stats_kernel, dim3(grid), dim3(256), 0, s, v, rows, out);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // k-means update (index builder, create_ivf_model_reordered.py:96-105): cluster sums are accumulated
 // in 44.20 fixed point with 64-bit integer atomics, so the result does not depend on the order in

@@ -56,6 +56,32 @@ struct ScanParams {
 // Brute-force / coarse scan.  kcap in {8, 16}; nqh = 1 (<=16 queries) or 2.
 hipError_t launch_scan(const ScanParams& p, int grid, int kcap, int nqh, int mode, hipStream_t s);
 
+// bf16 prefilter of the fp32 streaming scan (scan_f32f_kernel).  With S = q.b exact, S_fl the fp32 chain of
+// scan_f32s_kernel and S' the v_mfma_f32_16x16x32_bf16 sum of q' = bf16(q), b' = bf16(b):
+//   |S_fl - S'| <= |S_fl - S| + |S - q'.b'| + |q'.b' - S'|
+//               <= g32 ||q|| ||b||  +  (e_q ||b|| + ||q'|| e_b)  +  g16 ||q'|| ||b'||
+// with e_x = ||x - x'||.  S - q'.b' = (q - q').b + q'.(b - b') and Cauchy-Schwarz give the middle term.  g32 = 128 u / (1 -
+// 128 u), u = 2^-24, is the classic bound of a 128-step fmaf chain (each step rounds once).  bf16 x bf16 products are exact in
+// fp32; how the bf16 MFMA accumulates them is not documented, so g16 assumes the worst that is plausible: a unit roundoff
+// of 2^-22 (truncation allowed, twice over) per each of the 128 additions.  Shard constants replace ||b||, e_b, ||b'||
+// by their maxima.  Holds on well-scaled data only: every value finite and every non-zero magnitude in [2^-60, 2^60],
+// so that no product leaves the normal range and flushing subnormals cannot matter (a 2^-100 absolute term covers
+// partial sums that cancel into the subnormal range).  The result is rounded up to float.
+constexpr double kFiltG32 = 128.0 / 16777216.0 / (1.0 - 128.0 / 16777216.0);
+constexpr double kFiltG16 = 128.0 / 4194304.0 / (1.0 - 128.0 / 4194304.0);
+constexpr double kFiltLo = 8.673617379884035e-19;  // 2^-60
+constexpr double kFiltHi = 1152921504606846976.0;  // 2^60
+struct FilterStats {     // per shard, from launch_row_filter_stats (index creation)
+    double bmax;         // max ||b||
+    double emax;         // max ||b - bf16(b)||
+    double bpmax;        // max ||bf16(b)||
+};
+__host__ __device__ inline float filter_bound(double eq, double nq, double nqp, const FilterStats& f) {
+    const double nb = f.bmax > f.bpmax ? f.bmax : f.bpmax, nqm = nq > nqp ? nq : nqp;
+    const double e = eq * f.bmax + nqp * f.emax + (kFiltG32 + kFiltG16) * nqm * nb + 7.888609052210118e-31;  // + 2^-100
+    return (float)(e * (1.0 + 1.0 / 1048576.0));  // (the 2^-20 covers the rounding of the norms and of this cast)
+}
+
 // Bounds for a multi-batch scan, computed up front on a sample of the rows: kSeedWaves 16-row tiles spread evenly
 // over the shard, scored against every batch; tau0[batch][q] = next_up of the k1-th smallest of 64 group minima
 // (groups of 32 tiles) -- an upper bound of the k1-th best distance, because k1 distinct rows are at least that
@@ -96,6 +122,13 @@ struct SeedParams {
     // piece (as fragments straight from the row-major queries it is 64 pieces 512 bytes apart per instruction, and eight
     // waves entering a pass kept a CU's address unit busy for 8 us)
     float* qfrag;            // [n_batches][2][8][64][4]
+    // optional, with qfrag: the queries rounded to bf16 (RNE) in the B-fragment order of the bf16 prefilter
+    // (scan_f32f_kernel): qbf[batch][h][s][lane][j] = Q'[16 h + (lane & 15)][32 s + 16 (j >> 2) + 4 (lane >> 4) + (j & 3)],
+    // and per query the bound E of the prefilter (filter_bound with the shard constants below; +inf for a query outside
+    // the well-scaled range, 0 for padding)
+    uint16_t* qbf;           // [n_batches][2][4][64][8]
+    float* qbound;           // [n_batches][32]
+    FilterStats fstats;
     int8_t* q8frag;          // [n_batches][2][2][64][16] the byte queries likewise: (h, half, lane) -> bytes [64 half + 16 (lane >> 4) ..] of query 16 h + (lane & 15)
 };
 hipError_t launch_seed(const SeedParams& p, hipStream_t s);
@@ -164,7 +197,10 @@ struct StreamParams {
     int n_batches, nq_valid, metric;
     int32_t id_offset;
     CandSink sink;
-    int batches_per_pass;    // 1 (HBM bound) or 2 (two batches share a pass over the rows: MFMA bound)
+    int batches_per_pass;    // 1 (HBM bound) or 2 (two batches share a pass over the rows: MFMA bound); 4 with qbf
+    // the bf16 prefilter (scan_f32f_kernel) instead, when set: SeedParams::qbf / qbound
+    const uint16_t* qbf;
+    const float* qbound;
 };
 hipError_t launch_scan_f32_stream(const StreamParams& p, int grid, hipStream_t s);
 
@@ -232,6 +268,9 @@ constexpr int kKppBlockRows = 1024;
 
 // ||v||^2 per row in the reference's AVX2 summation order (cpu_baseline.cpp:95-114).
 hipError_t launch_row_sqnorm(const float* v, int64_t rows, int dim, float* out, hipStream_t s);
+// shard constants of the bf16 prefilter: out[0..2] = max of ||b||^2, ||b - bf16(b)||^2, ||bf16(b)||^2 as double bits,
+// out[3] = 1 when a row is not well scaled (FilterStats); out must be zeroed before
+hipError_t launch_row_filter_stats(const float* v, int64_t rows, unsigned long long* out, hipStream_t s);
 
 // ---- IVF ----
 // Per query: the nprobe nearest centroids (ascending (dist, id)) out of a [B][ld] score matrix.

@@ -4,6 +4,8 @@
 //                          v_mfma_f32_16x16x4_f32 with the L2 epilogue (cpu_baseline.cpp:229-242), NB batches per pass
 //                          over the rows, candidates under seeded bounds to per-wave buffers; scan_i8w_kernel: the same
 //                          on exact u8 rows (v_mfma_i32_16x16x64_i8), four batches per pass.
+//   scan_f32f_kernel<NB> : the same fp32 scan with the bulk test on v_mfma_f32_16x16x32_bf16 under a rigorous error bound,
+//                          four batches per pass, survivors recomputed with scan_f32s_kernel's exact fp32 chain (default).
 //   scan_kernel          : per-batch scan with the top-k (cpu_baseline.cpp:127-153) fused in (short calls, fallback);
 //                          kModeStore = the B x N score matrix of QnnRunner::executeBatchRaw, kModeAssign = k-means
 //                          assignment for the index builder, kModeFilter = tie-resolver candidates.
@@ -990,6 +992,14 @@ __global__ __launch_bounds__(kScanThreads, NQH <= 8 ? 2 : 1) void scan_i8w_kerne
     sink_bin_wave(p.sink, (int)blockIdx.x * kScanWaves + wave, wbase, lane);  // no separate binning launch
 }
 
+// L2 bound of the streaming fp32 scan's hot test fma(-2, dot, bn) < thr: d = RN(RN(qn + bn) - 2 dot) < tau implies
+// RN(bn - 2 dot) < tau - qn + slack: the three roundings together move the comparison by less than 2^-24 * 8 (qn + |tau|)
+// (a row under the bound has bn < 2 (qn + tau)); the slack is 16 times that.  (One function: the exact recheck of the bf16
+// prefilter must form the same bits.)
+__device__ __forceinline__ float stream_l2_thr(float tau, float qn) {
+    return (tau - qn) + 9.5367431640625e-7f * (qn + fabsf(tau));
+}
+
 // ------------------------------------------------------------------------------------------------
 // Streaming fp32 scan (see StreamParams): scan_kernel's fp32 data path and arithmetic, the wide int8 scan's organisation.
 // ------------------------------------------------------------------------------------------------
@@ -1118,10 +1128,8 @@ __global__ __launch_bounds__(kScanThreads, NB == 1 ? 2 : 1) void scan_f32s_kerne
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // operands are here (and so are both staged tiles)
 #pragma unroll
             for (int h = 0; h < NH; ++h) {
-                // bound of the hot test.  L2: d = RN(RN(qn + bn) - 2 dot) < tau implies RN(bn - 2 dot) < tau - qn + slack:
-                // the three roundings together move the comparison by less than 2^-24 * 8 (qn + |tau|) (a row under the
-                // bound has bn < 2 (qn + tau)); the slack is 16 times that.  IP: -dot < tau <=> dot > -tau, exactly.
-                const float l2thr = (tau[h] - qn[h]) + 9.5367431640625e-7f * (qn[h] + fabsf(tau[h]));
+                // bound of the hot test (stream_l2_thr).  IP: -dot < tau <=> dot > -tau, exactly.
+                const float l2thr = stream_l2_thr(tau[h], qn[h]);
                 thr[h] = p.metric ? (live[h] ? -tau[h] : __builtin_inff()) : (live[h] ? l2thr : -__builtin_inff());
             }
         }
@@ -1209,10 +1217,284 @@ __global__ __launch_bounds__(kScanThreads, NB == 1 ? 2 : 1) void scan_f32s_kerne
     sink_bin_wave(p.sink, (int)blockIdx.x * kScanWaves + wave, wbase, lane);  // no separate binning launch
 }
 
+// ------------------------------------------------------------------------------------------------
+// bf16 prefilter of the streaming fp32 scan: scan_f32s_kernel's organisation (persistent workgroups of 8
+// waves, a private LDS-DMA ring per wave, whole passes per wave, no barrier, survivors to the wave's buffer, binning at
+// the end), but the bulk test runs on v_mfma_f32_16x16x32_bf16 -- 4 MFMAs per 16-row tile and column block instead of 32
+// fp32 ones -- against a bound widened by the rigorous error bound of bf16 against the fp32 chain (filter_bound,
+// vs_kernels.h), and whatever passes is recomputed with scan_f32s_kernel's exact fmaf chain when the wave bins its buffer
+// (RecheckF32).  The candidate lists then hold exactly the entries of scan_f32s_kernel, with the same bits.
+//
+// The A side keeps the LDS image and fa[] addressing: k-step s of the bf16 MFMA pairs chunks a[2 s] and a[2 s + 1], so
+// lane (r, g) supplies row r, k = 32 s + 4 g + i (elements 0..3) and 32 s + 16 + 4 g + i (4..7); the query fragments of
+// launch_seed (SeedParams::qbf) use the same order.  NB = 4 batches (8 column blocks) per pass: the bf16 B operands are
+// 128 registers, at two waves per SIMD.
+// ------------------------------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// the exact recheck: scan_f32s_kernel's dot of (row, query), its distance and both of its tests, or a dropped entry
+struct RecheckF32 {
+    const float* base;
+    const float* bnorm;
+    const float* q;
+    int64_t q_batch_stride;
+    const float* qnorm;
+    const float* tau0;
+    int metric;
+    int32_t id_offset;
+    __device__ __forceinline__ int4 operator()(const int4& c) const {
+        const int qg = c.x;
+        const int64_t row = (int64_t)c.z - id_offset;
+        const float* b = base + row * kDim;
+        const float* qq = q + (int64_t)(qg / kMaxBatch) * q_batch_stride + (int64_t)(qg % kMaxBatch) * kDim;
+        // the MFMA chain of scan_f32s_kernel: step (c, i) of v_mfma_f32_16x16x4_f32 adds the four products of k = 16 c +
+        // 4 g + i, g = 0..3 in order, each rounded like an fmaf
+        float dot = 0.f;
+#pragma unroll
+        for (int cc = 0; cc < 8; ++cc) {
+            f32x4 bv[4], qv[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                bv[g] = *reinterpret_cast<const f32x4*>(b + 16 * cc + 4 * g);
+                qv[g] = *reinterpret_cast<const f32x4*>(qq + 16 * cc + 4 * g);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) dot = fmaf(bv[g][i], qv[g][i], dot);
+        }
+        const float qn = qnorm[qg], tau = tau0[qg], bn = bnorm[row];
+        bool keep;
+        float d;
+        if (!metric) {
+            d = fmaf(-2.0f, dot, qn + bn);
+            keep = fmaf(-2.0f, dot, bn) < stream_l2_thr(tau, qn) && d < tau;
+        } else {
+            d = -dot;
+            keep = dot > -tau && d < tau;
+        }
+        return keep ? make_int4(qg, __builtin_bit_cast(int, d), c.z, 0) : make_int4(-1, 0, 0, 0);
+    }
+};
+
+template <int NB>
+__global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const StreamParams p) {
+    constexpr int NH = 2 * NB;  // 16-query column blocks per pass
+    constexpr int TR = kTileRows;
+    constexpr int kTileVmem = 9;  // vector-memory instructions of issue_tile: 8 row pieces + 1 norm piece
+    static_assert(TR * kDim * 4 == 8 * 1024 && kDepth == 2, "issue_tile: 8 pieces of 1 KB; one tile in flight behind the one used");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = lane & 15, g = lane >> 4;
+    const int tiles_total = (int)((p.n_rows + TR - 1) / TR);
+    const int G = (int)gridDim.x;
+    const int T = (tiles_total - (int)blockIdx.x + G - 1) / G;  // tiles of this workgroup per pass (grid <= tiles_total)
+    const int n_pass = (p.n_batches + NB - 1) / NB;
+    // whole passes per wave, then equal contiguous ranges of the remaining passes' tiles (see scan_f32s_kernel)
+    const int n_whole = n_pass & ~(kScanWaves - 1), n_rest = n_pass - n_whole;
+    char* ring = smem + wave * (kDepth * kSlotBytes);
+    unsigned voff[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int row_in = 2 * j + (lane >> 5);
+        voff[j] = (unsigned)(row_in * 512 + 16 * ((lane & 31) ^ row_in));
+    }
+    const unsigned voff_n = (unsigned)lane * 4u;
+    const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)ring);
+    auto issue_tile = [&](int tile, int slot) __attribute__((always_inline)) {  // kTileVmem instructions
+        const int64_t row0 = (int64_t)tile * TR;
+        const unsigned dst = ring_lds + (unsigned)(slot * kSlotBytes);
+        const char* tb = reinterpret_cast<const char*>(p.base) + row0 * (kDim * 4);
+        static_assert(VS_ROW_CPOL == 2, "the row pieces are issued with the nt policy");
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            asm volatile("s_add_u32 m0, %0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt" ::"s"(dst), "v"(voff[j]), "s"(tb), "n"(j * 1024) : "memory", "scc");
+        const char* nb = reinterpret_cast<const char*>(p.bnorm + row0);
+        asm volatile("s_add_u32 m0, %0, 8192\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" ::"s"(dst), "v"(voff_n), "s"(nb) : "memory", "scc");
+    };
+    unsigned fa[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) fa[c] = (unsigned)(wave * (kDepth * kSlotBytes) + r * 512 + (((4 * c + g) ^ r) << 4));
+    const unsigned fa_n = (unsigned)(wave * (kDepth * kSlotBytes) + 8192 + 16 * g);
+    int it_u = wave - kScanWaves, it_n = 0, it_end = 0, it_pass = 0;
+    int rem_pos = (int)((long long)wave * n_rest * T / kScanWaves), rem_end = (int)((long long)(wave + 1) * n_rest * T / kScanWaves);
+    auto next_tile = [&](int& pass_out) __attribute__((always_inline)) -> int {
+        while (it_n >= it_end) {
+            if (it_u + kScanWaves < n_whole) {
+                it_u += kScanWaves;
+                it_pass = it_u, it_n = 0, it_end = T;
+            } else if (rem_pos < rem_end) {
+                const int pr = rem_pos / T;
+                it_pass = n_whole + pr;
+                it_n = rem_pos - pr * T;
+                it_end = min(T, it_n + (rem_end - rem_pos));
+                rem_pos += it_end - it_n;
+            } else {
+                pass_out = n_pass;
+                return (int)blockIdx.x;  // past the end: the DMA still goes out (queue accounting), to a tile nobody uses
+            }
+        }
+        pass_out = it_pass;
+        return (int)blockIdx.x + (it_n++) * G;
+    };
+
+    // per-pass state: the NH column blocks as bf16 B operands (qb[h][s], SeedParams::qbf) and the widened bounds.  The
+    // loads are inline asm so that the compiler puts no wait of its own in front of the operands' first use (it would
+    // be vmcnt(0) in every tile step); each loaded register is tied to the explicit wait below.
+    u32x4 qb[NH][4];
+    float thr[NH];
+    auto load_pass = [&](int pass) __attribute__((always_inline)) {
+        float qn[NH], tau[NH], eb[NH];
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            const int batch = min(pass * NB + h / 2, p.n_batches - 1);
+            const int qrow = 16 * (h & 1) + r;
+            const int qglob = batch * kMaxBatch + (qrow < p.nq_valid ? qrow : 0);
+            const uint16_t* src = p.qbf + (((int64_t)batch * 2 + (h & 1)) * 4 * 64 + lane) * 8;  // 1 KB per instruction
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const uint16_t* ps = src + s * 64 * 8;
+                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qb[h][s]) : "v"(ps) : "memory");
+            }
+            const float* pn = p.qnorm + qglob;
+            const float* pt = p.tau0 + qglob;
+            const float* pe = p.qbound + qglob;
+            asm volatile("global_load_dword %0, %1, off" : "=v"(qn[h]) : "v"(pn) : "memory");
+            asm volatile("global_load_dword %0, %1, off" : "=v"(tau[h]) : "v"(pt) : "memory");
+            asm volatile("global_load_dword %0, %1, off" : "=v"(eb[h]) : "v"(pe) : "memory");
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // operands are here (and so are both staged tiles)
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            asm volatile("" : "+v"(qb[h][0]), "+v"(qb[h][1]), "+v"(qb[h][2]), "+v"(qb[h][3]), "+v"(qn[h]), "+v"(tau[h]), "+v"(eb[h]) :: "memory");
+            const bool live = 16 * (h & 1) + r < p.nq_valid && pass * NB + h / 2 < p.n_batches;
+            // |S_fl - S'| <= E.  L2: the exact hot test RN(bn - 2 S_fl) < thr means bn - 2 S_fl < thr, so bn - 2 S' < thr + 2E
+            // <= t (a float: RN, then one step up) and RN(bn - 2 S') <= t < next_up(t) =: thr'.  IP: S_fl > thr gives
+            // S' > thr - E >= thr' := next_down(RN(thr - E)).  E = +inf (a query outside the well-scaled range) admits every row.
+            const float inf = __builtin_inff();
+            if (!p.metric) {
+                const float t = nextafterf(stream_l2_thr(tau[h], qn[h]) + 2.0f * eb[h], inf);
+                thr[h] = live ? nextafterf(t, inf) : -inf;
+            } else {
+                thr[h] = live ? nextafterf(-tau[h] - eb[h], -inf) : inf;
+            }
+        }
+    };
+
+    int4* wbuf = p.sink.wbuf + ((int64_t)blockIdx.x * kScanWaves + wave) * p.sink.wcap;
+    int wbase = 0;  // wave-uniform fill of the private candidate buffer
+    int pass_cur, pass_nxt;
+    int tile_cur = next_tile(pass_cur);
+    int tile_nxt = next_tile(pass_nxt);
+    issue_tile(tile_cur, 0);
+    issue_tile(tile_nxt, 1);
+    int have_pass = -1;
+
+    auto step = [&](const int sl) __attribute__((always_inline)) {
+        if (pass_cur != have_pass) {  // wave-uniform: this wave enters the next pass
+            load_pass(pass_cur);
+            have_pass = pass_cur;
+        }
+        int pass_new;
+        const int tile_new = next_tile(pass_new);
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kTileVmem * (kDepth - 1)) : "memory");  // the older staged tile has landed
+        const char* src = smem + sl * kSlotBytes;
+        f32x4 a[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) a[c] = *reinterpret_cast<const f32x4*>(src + fa[c]);
+        const f32x4 bn = *reinterpret_cast<const f32x4*>(src + fa_n);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        issue_tile(tile_new, sl);  // the slot is refilled as soon as its fragments sit in registers
+        bf16x8 ab[4];  // k-step s = chunks 2 s, 2 s + 1, rounded to nearest even (v_cvt_pk_bf16_f32)
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                ab[s][i] = (__bf16)a[2 * s][i];
+                ab[s][4 + i] = (__bf16)a[2 * s + 1][i];
+            }
+        f32x4 acc[NH];
+#pragma unroll
+        for (int h = 0; h < NH; ++h) acc[h] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int h = 0; h < NH; ++h)
+                acc[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[s], __builtin_bit_cast(bf16x8, qb[h][s]), acc[h], 0, 0, 0);
+        // one fma and one compare per value, as in scan_f32s_kernel (a dead column block has thr = -inf / +inf)
+        unsigned long long hit[NH][4], hits = 0;
+        if (!p.metric) {
+#pragma unroll
+            for (int h = 0; h < NH; ++h)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    hit[h][j] = __ballot(fmaf(-2.0f, acc[h][j], bn[j]) < thr[h]);
+                    hits |= hit[h][j];
+                }
+        } else {
+#pragma unroll
+            for (int h = 0; h < NH; ++h)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    hit[h][j] = __ballot(acc[h][j] > thr[h]);
+                    hits |= hit[h][j];
+                }
+        }
+        if (hits) {  // rare: a few hundred rows per query per million
+            const int row_t = tile_cur * TR + 4 * g;
+#pragma unroll
+            for (int h = 0; h < NH; ++h)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (!hit[h][j]) continue;  // wave-uniform
+                    const int row = row_t + j;
+                    const bool pass = ((hit[h][j] >> lane) & 1) && row < (int)p.n_rows;
+                    const unsigned long long mask = __ballot(pass);
+                    if (mask) {
+                        const int pos = wbase + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+                        // (query, value, id): the value is the bf16 sum, replaced by the exact distance in RecheckF32
+                        const int qglob = (pass_cur * NB + h / 2) * kMaxBatch + 16 * (h & 1) + r;
+                        if (pass && pos < p.sink.wcap)
+                            wbuf[pos] = make_int4(qglob, __builtin_bit_cast(int, acc[h][j]), row + p.id_offset, 0);
+                        wbase += __popcll(mask);
+                    }
+                }
+        }
+        tile_cur = tile_nxt;
+        pass_cur = pass_nxt;
+        tile_nxt = tile_new;
+        pass_nxt = pass_new;
+    };
+    while (pass_cur < n_pass) {
+        step(0);
+        if (pass_cur >= n_pass) break;
+        step(1);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // retire the tail prefetches before the wave ends
+    const RecheckF32 fix{p.base, p.bnorm, p.q, p.q_batch_stride, p.qnorm, p.tau0, p.metric, p.id_offset};
+    sink_bin_wave<RecheckF32, true>(p.sink, (int)blockIdx.x * kScanWaves + wave, wbase, lane, fix);
+}
+
 hipError_t launch_scan_f32_stream(const StreamParams& p, int grid, hipStream_t s) {
     static bool attr_set[64][2] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (p.qbf) {  // the bf16 prefilter: 2 or 4 batches per pass
+        static bool fattr_set[64][2] = {};
+        const int w = p.batches_per_pass == 4 ? 1 : 0;
+        if (p.batches_per_pass != 2 && p.batches_per_pass != 4) return hipErrorInvalidValue;
+        const void* fn = w ? reinterpret_cast<const void*>(scan_f32f_kernel<4>) : reinterpret_cast<const void*>(scan_f32f_kernel<2>);
+        if (!fattr_set[dev][w]) {
+            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kWideLds);
+            if (e != hipSuccess) return e;
+            fattr_set[dev][w] = true;
+        }
+        if (w) hipLaunchKernelGGL(scan_f32f_kernel<4>, dim3(grid), dim3(kScanThreads), kWideLds, s, p);
+        else hipLaunchKernelGGL(scan_f32f_kernel<2>, dim3(grid), dim3(kScanThreads), kWideLds, s, p);
+        return hipGetLastError();
+    }
     const int v = p.batches_per_pass == 2 ? 1 : 0;
     const void* fn = v ? reinterpret_cast<const void*>(scan_f32s_kernel<2>) : reinterpret_cast<const void*>(scan_f32s_kernel<1>);
     if (!attr_set[dev][v]) {

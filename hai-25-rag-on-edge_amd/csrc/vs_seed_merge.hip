@@ -37,6 +37,14 @@ __global__ __launch_bounds__(256) void seed_qnorm_kernel(const SeedParams p) {
             f32x4 v = *reinterpret_cast<const f32x4*>(qb + min(qrow, p.nq_valid - 1) * kDim + 16 * c + 4 * (fl >> 4));
             if (qrow >= p.nq_valid) v = (f32x4){0.f, 0.f, 0.f, 0.f};
             *reinterpret_cast<f32x4*>(p.qfrag + ((int64_t)batch * 1024 + idx) * 4) = v;
+            if (p.qbf) {  // the same four values rounded to bf16: elements 4 (c & 1) .. of k-step c >> 1 (see SeedParams)
+                ushort4 w;
+                w.x = __builtin_bit_cast(uint16_t, (__bf16)v[0]);
+                w.y = __builtin_bit_cast(uint16_t, (__bf16)v[1]);
+                w.z = __builtin_bit_cast(uint16_t, (__bf16)v[2]);
+                w.w = __builtin_bit_cast(uint16_t, (__bf16)v[3]);
+                *reinterpret_cast<ushort4*>(p.qbf + ((((int64_t)batch * 2 + hh) * 4 + (c >> 1)) * 64 + fl) * 8 + 4 * (c & 1)) = w;
+            }
         }
         return;
     }
@@ -61,11 +69,22 @@ __global__ __launch_bounds__(256) void seed_qnorm_kernel(const SeedParams p) {
     float acc = 0.f;
     int part = 0;        // sum(q - 128) over this thread's 16 elements
     bool q_ok = true;    // ... all of them integers in [0, 255]
+    double n2 = 0.0, e2 = 0.0, p2 = 0.0;  // ||q||^2, ||q - q'||^2, ||q'||^2 for the bf16 prefilter's bound
+    bool scaled = true;
     if (row < p.nq_valid) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const float x = qb[row * kDim + 8 * i + j];
             acc = fmaf(x, x, acc);
+            if (p.qbound) {
+                const float xp = (float)(__bf16)x;
+                const float ax = fabsf(x);
+                scaled = scaled && (ax == 0.f || (ax >= (float)kFiltLo && ax <= (float)kFiltHi));
+                const double d = (double)x - (double)xp;
+                n2 = fma((double)x, (double)x, n2);
+                e2 = fma(d, d, e2);
+                p2 = fma((double)xp, (double)xp, p2);
+            }
             if (p.q8) {
                 const int xi = (int)x;
                 q_ok = q_ok && ((float)xi == x) && xi >= 0 && xi <= 255;
@@ -82,6 +101,19 @@ __global__ __launch_bounds__(256) void seed_qnorm_kernel(const SeedParams p) {
 #pragma unroll
     for (int u = 1; u < 8; ++u) sum = sum + __shfl(acc, b8 + u);
     if (j == 0) p.qnorm[batch * kMaxBatch + row] = sum;
+    if (p.qbound) {  // (8-lane groups: every lane takes part in the shuffles)
+        int ok_q = scaled ? 1 : 0;
+#pragma unroll
+        for (int u = 1; u < 8; u <<= 1) {
+            n2 += __shfl_xor(n2, u);
+            e2 += __shfl_xor(e2, u);
+            p2 += __shfl_xor(p2, u);
+            ok_q &= __shfl_xor(ok_q, u);
+        }
+        if (j == 0)
+            p.qbound[batch * kMaxBatch + row] = row >= p.nq_valid ? 0.f
+                                                : ok_q ? filter_bound(sqrt(e2), sqrt(n2), sqrt(p2), p.fstats) : __builtin_inff();
+    }
     if (p.q8) {
         part += __shfl_xor(part, 1);
         part += __shfl_xor(part, 2);

@@ -11,7 +11,8 @@ namespace vs {
 struct SinkEntryAsIs {
     __device__ __forceinline__ int4 operator()(const int4& c) const { return c; }
 };
-template <typename Fix = SinkEntryAsIs>
+// Drop = true: an entry that `fix` returns with a negative query is not binned (the bf16 prefilter's exact recheck).
+template <typename Fix = SinkEntryAsIs, bool Drop = false>
 __device__ __forceinline__ void sink_bin_wave(const CandSink& p, int wb, int n, int lane, const Fix fix = Fix(), int diag = 0) {
     if (n > p.wcap) {
         if (lane == 0) p.overflow[0] = 1;  // entries were dropped: the fallback kernels behind take over
@@ -33,6 +34,9 @@ __device__ __forceinline__ void sink_bin_wave(const CandSink& p, int wb, int n, 
         const unsigned long long lo = __hip_atomic_load(s64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned long long hi = __hip_atomic_load(s64 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int4 c = fix(make_int4((int)lo, (int)(lo >> 32), (int)hi, (int)(hi >> 32)));  // (query, distance bits, id, -)
+        if constexpr (Drop) {
+            if (c.x < 0) continue;
+        }
         const int64_t lst = (int64_t)c.x * p.nsub + sub;
 #ifdef VS_STAMPS
         if (diag & 32) {

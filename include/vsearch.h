@@ -368,6 +368,10 @@ VS_API int vs_prof_read_launches(vs_index* h, int which, double* ms_out, int64_t
 VS_API int64_t vs_index_rows(const vs_index* h);
 VS_API int vs_index_dim(const vs_index* h);
 VS_API int vs_index_nlist(const vs_index* h);     /* 0 for brute force */
+/* The error bound E of the bf16 prefilter of the fp32 brute-force scan: |fp32 dot - bf16 MFMA dot| <= E for a
+ * query with ||q|| = nq, ||bf16(q)|| = nqp, ||q - bf16(q)|| = eq against a shard with max ||b|| = bmax, max ||b - bf16(b)||
+ * = emax, max ||bf16(b)|| = bpmax, as the library computes it (rounded up to float).  Pure host arithmetic. */
+VS_API float vs_f32_filter_bound(double eq, double nq, double nqp, double bmax, double emax, double bpmax);
 VS_API void vs_destroy(vs_index* h);
 
 #ifdef __cplusplus
