@@ -45,7 +45,6 @@ constexpr int kMaxMulti = 32;  // batches per persistent scan launch
 constexpr int kOneMaxBatches = 4;  // calls of fewer batches take one single-call scan launch per batch (fp32 rows)
 constexpr int kOneMaxQueries = 16;  // ... when a batch holds at most this many queries
 constexpr int kPairMinTiles = 96;
-constexpr int kFilterNb4MinTiles = 0;  // tiles per workgroup and pass from which the bf16 prefilter takes four batches per pass (else two)   // tiles per workgroup and pass from which the fp32 streaming scan pairs batches
 constexpr int kIvfGroupDefault = 256; // batches per launch group of an unsharded IVF index (VSEARCH_IVF_GROUP): 46 us per 1024 queries against 79 with groups of 32
 constexpr int kIvfGroupMax = 256;     // ... at most (8 super-batches of 32): also the group of an index sharded 8 ways
 constexpr int kIvfShardMaxWorld = 16; // ranks the cluster-sharded pipeline is compiled for (one super-batch per rank)
@@ -705,10 +704,9 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
             // two batches per pass pay where a workgroup has many tiles per pass (1 M rows: 244, + 14 %); on a small shard
             // (125 K rows: 30 tiles) the per-pass operand fetch and drain weigh more than the halved traffic saves (- 15 %)
             sp.batches_per_pass = (nb >= 2 && (g_f32_pair > 1 || (g_f32_pair == 1 && tiles_total / sgrid >= kPairMinTiles))) ? 2 : 1;
-            if (f32_filter) {
+            if (f32_filter) {  // one sweep over the rows serves all nb batches (batches_per_pass does not apply)
                 sp.qbf = L.qbf;
                 sp.qbound = L.qbound;
-                sp.batches_per_pass = tiles_total / sgrid >= kFilterNb4MinTiles ? 4 : 2;
             }
             HIPCHK(vs::launch_scan_f32_stream(sp, sgrid, s));
             prof_end(h, 0, s);

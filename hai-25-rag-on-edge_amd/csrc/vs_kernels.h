@@ -197,8 +197,9 @@ struct StreamParams {
     int n_batches, nq_valid, metric;
     int32_t id_offset;
     CandSink sink;
-    int batches_per_pass;    // 1 (HBM bound) or 2 (two batches share a pass over the rows: MFMA bound); 4 with qbf
-    // the bf16 prefilter (scan_f32f_kernel) instead, when set: SeedParams::qbf / qbound
+    int batches_per_pass;    // scan_f32s_kernel: 1 (HBM bound) or 2 (two batches share a pass over the rows: MFMA bound)
+    // the bf16 prefilter (scan_f32f_kernel: one sweep over the rows for all n_batches <= 32) instead, when set:
+    // SeedParams::qbf / qbound
     const uint16_t* qbf;
     const float* qbound;
 };

@@ -4,8 +4,9 @@
 //                          v_mfma_f32_16x16x4_f32 with the L2 epilogue (cpu_baseline.cpp:229-242), NB batches per pass
 //                          over the rows, candidates under seeded bounds to per-wave buffers; scan_i8w_kernel: the same
 //                          on exact u8 rows (v_mfma_i32_16x16x64_i8), four batches per pass.
-//   scan_f32f_kernel<NB> : the same fp32 scan with the bulk test on v_mfma_f32_16x16x32_bf16 under a rigorous error bound,
-//                          four batches per pass, survivors recomputed with scan_f32s_kernel's exact fp32 chain (default).
+//   scan_f32f_kernel<CBW, D> : the same fp32 scan with the bulk test on v_mfma_f32_16x16x32_bf16 under a rigorous error
+//                          bound, one sweep over the rows for all batches of a launch through a ring shared by the
+//                          workgroup, survivors recomputed with scan_f32s_kernel's exact fp32 chain (default).
 //   scan_kernel          : per-batch scan with the top-k (cpu_baseline.cpp:127-153) fused in (short calls, fallback);
 //                          kModeStore = the B x N score matrix of QnnRunner::executeBatchRaw, kModeAssign = k-means
 //                          assignment for the index builder, kModeFilter = tie-resolver candidates.
@@ -1218,17 +1219,22 @@ __global__ __launch_bounds__(kScanThreads, NB == 1 ? 2 : 1) void scan_f32s_kerne
 }
 
 // ------------------------------------------------------------------------------------------------
-// bf16 prefilter of the streaming fp32 scan: scan_f32s_kernel's organisation (persistent workgroups of 8
-// waves, a private LDS-DMA ring per wave, whole passes per wave, no barrier, survivors to the wave's buffer, binning at
-// the end), but the bulk test runs on v_mfma_f32_16x16x32_bf16 -- 4 MFMAs per 16-row tile and column block instead of 32
-// fp32 ones -- against a bound widened by the rigorous error bound of bf16 against the fp32 chain (filter_bound,
-// vs_kernels.h), and whatever passes is recomputed with scan_f32s_kernel's exact fmaf chain when the wave bins its buffer
-// (RecheckF32).  The candidate lists then hold exactly the entries of scan_f32s_kernel, with the same bits.
+// bf16 prefilter of the streaming fp32 scan: the bulk test runs on v_mfma_f32_16x16x32_bf16 -- 4 MFMAs per
+// 16-row tile and column block instead of 32 fp32 ones -- against a bound widened by the rigorous error bound of bf16
+// against the fp32 chain (filter_bound, vs_kernels.h), survivors go to the wave's candidate buffer, and whatever passes
+// is recomputed with scan_f32s_kernel's exact fmaf chain when the wave bins its buffer (RecheckF32).  The candidate
+// lists then hold exactly the entries of scan_f32s_kernel, with the same bits.
 //
-// The A side keeps the LDS image and fa[] addressing: k-step s of the bf16 MFMA pairs chunks a[2 s] and a[2 s + 1], so
-// lane (r, g) supplies row r, k = 32 s + 4 g + i (elements 0..3) and 32 s + 16 + 4 g + i (4..7); the query fragments of
-// launch_seed (SeedParams::qbf) use the same order.  NB = 4 batches (8 column blocks) per pass: the bf16 B operands are
-// 128 registers, at two waves per SIMD.
+// Organisation: ONE sweep of the workgroup's tiles (blockIdx.x + n G) serves every batch of the launch.  The launch's
+// 2 n_batches 16-query column blocks are dealt to the 8 waves (wave w: column blocks w + 8 h, h < CBW), whose bf16 B
+// operands stay in registers for the whole launch, and the 8 waves share one ring of D tile slots in LDS: every tile is
+// staged once per workgroup (wave w moves its w-th 1 KB piece), not once per wave.  One raw barrier per tile publishes
+// the slot (the handshake is described at the tile loop below).
+//
+// The A side keeps scan_f32s_kernel's slot image and fa[] addressing: k-step s of the bf16 MFMA pairs chunks a[2 s] and
+// a[2 s + 1], so lane (r, g) supplies row r, k = 32 s + 4 g + i (elements 0..3) and 32 s + 16 + 4 g + i (4..7); the
+// query fragments of launch_seed (SeedParams::qbf) use the same order.  At CBW = 8 (17..32 batches) the bf16 B operands
+// are 128 registers, at two waves per SIMD.
 // ------------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -1278,135 +1284,147 @@ struct RecheckF32 {
     }
 };
 
-template <int NB>
+// Ring depth (tile slots) of scan_f32f_kernel, and the cache policy of its row pieces (2 = nt: a launch reads every row
+// once, and the 512 MB of a SIFT-1M shard never fit a cache from one launch to the next).
+#ifndef VS_F32F_DEPTH
+#define VS_F32F_DEPTH 8
+#endif
+#ifndef VS_F32F_CPOL
+#define VS_F32F_CPOL 2
+#endif
+#if VS_F32F_CPOL == 2
+#define VS_F32F_CPOL_ASM " nt"
+#elif VS_F32F_CPOL == 0
+#define VS_F32F_CPOL_ASM ""
+#else
+#error "VS_F32F_CPOL: 0 (default policy) or 2 (nt)"
+#endif
+constexpr int kFilterDepth = VS_F32F_DEPTH;
+
+// CBW = column blocks per wave (1, 2, 4 or 8: up to 4, 8, 16 or 32 batches), D = tile slots of the shared ring.
+template <int CBW, int D>
 __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const StreamParams p) {
-    constexpr int NH = 2 * NB;  // 16-query column blocks per pass
     constexpr int TR = kTileRows;
-    constexpr int kTileVmem = 9;  // vector-memory instructions of issue_tile: 8 row pieces + 1 norm piece
-    static_assert(TR * kDim * 4 == 8 * 1024 && kDepth == 2, "issue_tile: 8 pieces of 1 KB; one tile in flight behind the one used");
+    constexpr int kTileVmem = 2;  // vector-memory instructions per wave and tile: its row piece + the norm piece
+    static_assert(TR * kDim * 4 == kScanWaves * 1024, "a tile is one 1 KB row piece per wave");
+    static_assert(D >= 3 && D * kSlotBytes <= kWideLds, "the ring: one slot being read, one being filled, >= 1 in flight");
+    static_assert((D - 2) * kTileVmem <= 63, "vmcnt is a 6-bit count");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, g = lane >> 4;
     const int tiles_total = (int)((p.n_rows + TR - 1) / TR);
     const int G = (int)gridDim.x;
-    const int T = (tiles_total - (int)blockIdx.x + G - 1) / G;  // tiles of this workgroup per pass (grid <= tiles_total)
-    const int n_pass = (p.n_batches + NB - 1) / NB;
-    // whole passes per wave, then equal contiguous ranges of the remaining passes' tiles (see scan_f32s_kernel)
-    const int n_whole = n_pass & ~(kScanWaves - 1), n_rest = n_pass - n_whole;
-    char* ring = smem + wave * (kDepth * kSlotBytes);
-    unsigned voff[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int row_in = 2 * j + (lane >> 5);
-        voff[j] = (unsigned)(row_in * 512 + 16 * ((lane & 31) ^ row_in));
-    }
-    const unsigned voff_n = (unsigned)lane * 4u;
-    const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)ring);
-    auto issue_tile = [&](int tile, int slot) __attribute__((always_inline)) {  // kTileVmem instructions
-        const int64_t row0 = (int64_t)tile * TR;
-        const unsigned dst = ring_lds + (unsigned)(slot * kSlotBytes);
+    const int T = (tiles_total - (int)blockIdx.x + G - 1) / G;  // tiles of this workgroup (grid <= tiles_total: T >= 1)
+    const int n_cb = 2 * p.n_batches;                           // column blocks of the launch (<= 8 CBW)
+
+    // LDS-DMA written as instructions (see scan_f32s_kernel): "scalar tile base + this lane's 32-bit offset".  Wave w
+    // moves rows 2 w, 2 w + 1 of a tile: lane l lands at row 2 w + (l >> 5), stored chunk l & 31 <- source chunk
+    // (l & 31) ^ row.  Every wave also moves the tile's 16 norms (lane l <- norm of row l & 15, one 64-byte line), so
+    // that all waves issue the same kTileVmem instructions per tile and one constant vmcnt serves them all; the eight
+    // copies write the same bytes, and fa_n reads the first 16 of them.  M0 is written in the statement that reads it,
+    // and restored there: the compiler neither knows nor preserves it around an asm statement.
+    const int row_in = 2 * wave + (lane >> 5);
+    const unsigned voff = (unsigned)(row_in * 512 + 16 * ((lane & 31) ^ row_in));
+    const unsigned voff_n = (unsigned)r * 4u;
+    const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
+    auto issue_tile = [&](int n, int slot) __attribute__((always_inline)) {  // tile n of the workgroup, kTileVmem instructions
+        // past the end (the last D - 1 prefetches): the workgroup's last tile once more, into a slot nobody reads -- in
+        // bounds, and the count of the queue stays what the waits assume
+        const int64_t row0 = ((int64_t)blockIdx.x + (int64_t)min(n, T - 1) * G) * TR;
         const char* tb = reinterpret_cast<const char*>(p.base) + row0 * (kDim * 4);
-        static_assert(VS_ROW_CPOL == 2, "the row pieces are issued with the nt policy");
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            asm volatile("s_add_u32 m0, %0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt" ::"s"(dst), "v"(voff[j]), "s"(tb), "n"(j * 1024) : "memory", "scc");
         const char* nb = reinterpret_cast<const char*>(p.bnorm + row0);
-        asm volatile("s_add_u32 m0, %0, 8192\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" ::"s"(dst), "v"(voff_n), "s"(nb) : "memory", "scc");
+        const unsigned dst = ring_lds + (unsigned)(slot * kSlotBytes) + (unsigned)wave * 1024u;
+        const unsigned dst_n = ring_lds + (unsigned)(slot * kSlotBytes + 8192);
+        unsigned keep;
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" VS_F32F_CPOL_ASM "\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(voff), "s"(tb), "s"(dst) : "memory");
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(voff_n), "s"(nb), "s"(dst_n) : "memory");
     };
     unsigned fa[8];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) fa[c] = (unsigned)(wave * (kDepth * kSlotBytes) + r * 512 + (((4 * c + g) ^ r) << 4));
-    const unsigned fa_n = (unsigned)(wave * (kDepth * kSlotBytes) + 8192 + 16 * g);
-    int it_u = wave - kScanWaves, it_n = 0, it_end = 0, it_pass = 0;
-    int rem_pos = (int)((long long)wave * n_rest * T / kScanWaves), rem_end = (int)((long long)(wave + 1) * n_rest * T / kScanWaves);
-    auto next_tile = [&](int& pass_out) __attribute__((always_inline)) -> int {
-        while (it_n >= it_end) {
-            if (it_u + kScanWaves < n_whole) {
-                it_u += kScanWaves;
-                it_pass = it_u, it_n = 0, it_end = T;
-            } else if (rem_pos < rem_end) {
-                const int pr = rem_pos / T;
-                it_pass = n_whole + pr;
-                it_n = rem_pos - pr * T;
-                it_end = min(T, it_n + (rem_end - rem_pos));
-                rem_pos += it_end - it_n;
-            } else {
-                pass_out = n_pass;
-                return (int)blockIdx.x;  // past the end: the DMA still goes out (queue accounting), to a tile nobody uses
-            }
-        }
-        pass_out = it_pass;
-        return (int)blockIdx.x + (it_n++) * G;
-    };
+    for (int c = 0; c < 8; ++c) fa[c] = (unsigned)(r * 512 + (((4 * c + g) ^ r) << 4));
+    const unsigned fa_n = (unsigned)(8192 + 16 * g);
 
-    // per-pass state: the NH column blocks as bf16 B operands (qb[h][s], SeedParams::qbf) and the widened bounds.  The
-    // loads are inline asm so that the compiler puts no wait of its own in front of the operands' first use (it would
-    // be vmcnt(0) in every tile step); each loaded register is tied to the explicit wait below.
-    u32x4 qb[NH][4];
-    float thr[NH];
-    auto load_pass = [&](int pass) __attribute__((always_inline)) {
-        float qn[NH], tau[NH], eb[NH];
+    // The wave's column blocks as bf16 B operands (qb[h][s], SeedParams::qbf), loaded once for the launch, and their
+    // widened bounds.  The loads are inline asm so that the compiler puts no wait of its own in front of the operands'
+    // first use (it would be vmcnt(0), a drain of the ring); each loaded register is tied to the explicit wait of the
+    // prologue below.  A column block past the launch's (cb >= n_cb) loads the last one and gets thr = -inf / +inf.
+    u32x4 qb[CBW][4];
+    float thr[CBW];
+    float qn[CBW], tau[CBW], eb[CBW];
 #pragma unroll
-        for (int h = 0; h < NH; ++h) {
-            const int batch = min(pass * NB + h / 2, p.n_batches - 1);
-            const int qrow = 16 * (h & 1) + r;
-            const int qglob = batch * kMaxBatch + (qrow < p.nq_valid ? qrow : 0);
-            const uint16_t* src = p.qbf + (((int64_t)batch * 2 + (h & 1)) * 4 * 64 + lane) * 8;  // 1 KB per instruction
+    for (int h = 0; h < CBW; ++h) {
+        const int cb = min(wave + kScanWaves * h, n_cb - 1);  // = 2 batch + half
+        const int qrow = 16 * (cb & 1) + r;
+        const int qglob = (cb >> 1) * kMaxBatch + (qrow < p.nq_valid ? qrow : 0);
+        const uint16_t* src = p.qbf + ((int64_t)cb * 4 * 64 + lane) * 8;  // 1 KB per instruction
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const uint16_t* ps = src + s * 64 * 8;
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qb[h][s]) : "v"(ps) : "memory");
-            }
-            const float* pn = p.qnorm + qglob;
-            const float* pt = p.tau0 + qglob;
-            const float* pe = p.qbound + qglob;
-            asm volatile("global_load_dword %0, %1, off" : "=v"(qn[h]) : "v"(pn) : "memory");
-            asm volatile("global_load_dword %0, %1, off" : "=v"(tau[h]) : "v"(pt) : "memory");
-            asm volatile("global_load_dword %0, %1, off" : "=v"(eb[h]) : "v"(pe) : "memory");
+        for (int s = 0; s < 4; ++s) {
+            const uint16_t* ps = src + s * 64 * 8;
+            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qb[h][s]) : "v"(ps) : "memory");
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // operands are here (and so are both staged tiles)
+        const float* pn = p.qnorm + qglob;
+        const float* pt = p.tau0 + qglob;
+        const float* pe = p.qbound + qglob;
+        asm volatile("global_load_dword %0, %1, off" : "=v"(qn[h]) : "v"(pn) : "memory");
+        asm volatile("global_load_dword %0, %1, off" : "=v"(tau[h]) : "v"(pt) : "memory");
+        asm volatile("global_load_dword %0, %1, off" : "=v"(eb[h]) : "v"(pe) : "memory");
+    }
+    // prologue: tiles 0 .. D - 2 into slots 0 .. D - 2
 #pragma unroll
-        for (int h = 0; h < NH; ++h) {
-            asm volatile("" : "+v"(qb[h][0]), "+v"(qb[h][1]), "+v"(qb[h][2]), "+v"(qb[h][3]), "+v"(qn[h]), "+v"(tau[h]), "+v"(eb[h]) :: "memory");
-            const bool live = 16 * (h & 1) + r < p.nq_valid && pass * NB + h / 2 < p.n_batches;
-            // |S_fl - S'| <= E.  L2: the exact hot test RN(bn - 2 S_fl) < thr means bn - 2 S_fl < thr, so bn - 2 S' < thr + 2E
-            // <= t (a float: RN, then one step up) and RN(bn - 2 S') <= t < next_up(t) =: thr'.  IP: S_fl > thr gives
-            // S' > thr - E >= thr' := next_down(RN(thr - E)).  E = +inf (a query outside the well-scaled range) admits every row.
-            const float inf = __builtin_inff();
-            if (!p.metric) {
-                const float t = nextafterf(stream_l2_thr(tau[h], qn[h]) + 2.0f * eb[h], inf);
-                thr[h] = live ? nextafterf(t, inf) : -inf;
-            } else {
-                thr[h] = live ? nextafterf(-tau[h] - eb[h], -inf) : inf;
-            }
+    for (int s = 0; s < D - 1; ++s) issue_tile(s, s);
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 2) * kTileVmem) : "memory");  // the operands (older than every DMA) are here
+#pragma unroll
+    for (int h = 0; h < CBW; ++h) {
+        asm volatile("" : "+v"(qb[h][0]), "+v"(qb[h][1]), "+v"(qb[h][2]), "+v"(qb[h][3]), "+v"(qn[h]), "+v"(tau[h]), "+v"(eb[h]) :: "memory");
+        const int cb = wave + kScanWaves * h;
+        const bool live = cb < n_cb && 16 * (cb & 1) + r < p.nq_valid;
+        // |S_fl - S'| <= E.  L2: the exact hot test RN(bn - 2 S_fl) < thr means bn - 2 S_fl < thr, so bn - 2 S' < thr + 2E
+        // <= t (a float: RN, then one step up) and RN(bn - 2 S') <= t < next_up(t) =: thr'.  IP: S_fl > thr gives
+        // S' > thr - E >= thr' := next_down(RN(thr - E)).  E = +inf (a query outside the well-scaled range) admits every row.
+        const float inf = __builtin_inff();
+        if (!p.metric) {
+            const float t = nextafterf(stream_l2_thr(tau[h], qn[h]) + 2.0f * eb[h], inf);
+            thr[h] = live ? nextafterf(t, inf) : -inf;
+        } else {
+            thr[h] = live ? nextafterf(-tau[h] - eb[h], -inf) : inf;
         }
-    };
+    }
 
     int4* wbuf = p.sink.wbuf + ((int64_t)blockIdx.x * kScanWaves + wave) * p.sink.wcap;
     int wbase = 0;  // wave-uniform fill of the private candidate buffer
-    int pass_cur, pass_nxt;
-    int tile_cur = next_tile(pass_cur);
-    int tile_nxt = next_tile(pass_nxt);
-    issue_tile(tile_cur, 0);
-    issue_tile(tile_nxt, 1);
-    int have_pass = -1;
 
-    auto step = [&](const int sl) __attribute__((always_inline)) {
-        if (pass_cur != have_pass) {  // wave-uniform: this wave enters the next pass
-            load_pass(pass_cur);
-            have_pass = pass_cur;
-        }
-        int pass_new;
-        const int tile_new = next_tile(pass_new);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kTileVmem * (kDepth - 1)) : "memory");  // the older staged tile has landed
+    // Step t (tile t in slot t % D, its fragments already in registers; tiles t + 1 .. t + D - 2 in flight on entry):
+    //   1. s_waitcnt vmcnt((D - 3) kTileVmem): this wave's pieces of tile t + 1 have landed; those of t + 2 .. t + D - 2
+    //      stay in flight.  Candidate stores to wbuf count on vmcnt as well, but every one of them is younger than the
+    //      DMAs of the tile it follows: they can only make this wait retire more, never less, than tile t + 1.
+    //   2. raw s_barrier: every wave has passed step 1, so all 8 pieces and the norms of tile t + 1 are in LDS; and
+    //      every wave has finished step t - 1, whose fragment reads (of tile t) it waited for before its conversions,
+    //      so slot (t - 1) % D is free.  (__syncthreads() would add vmcnt(0) -- a drain of the ring -- through its fence.)
+    //   3. issue tile t + D - 1 into slot (t + D - 1) % D = (t - 1) % D;
+    //   4. convert tile t to bf16, read tile t + 1's fragments (their latency hides behind the MFMAs), then the MFMAs
+    //      and the test of tile t.
+    // The waves leave the barrier together, so a wave must not wait for LDS between it and its MFMAs: the fragments
+    // of a tile are read one step ahead, and the test of a column block runs beside the MFMAs of the next one.
+    // The slot index is a constant in the unrolled body, so the slot offset folds into the ds_read offsets.
+    f32x4 a[8], bn;
+    auto read_frags = [&](const int sl) __attribute__((always_inline)) {
         const char* src = smem + sl * kSlotBytes;
-        f32x4 a[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) a[c] = *reinterpret_cast<const f32x4*>(src + fa[c]);
-        const f32x4 bn = *reinterpret_cast<const f32x4*>(src + fa_n);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        issue_tile(tile_new, sl);  // the slot is refilled as soon as its fragments sit in registers
+        bn = *reinterpret_cast<const f32x4*>(src + fa_n);
+    };
+    // tile 0 landed with the operands (the wait above): publish it, read it
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    read_frags(0);
+    auto step = [&](const int t, const int sl) __attribute__((always_inline)) {
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 3) * kTileVmem) : "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        issue_tile(t + D - 1, (sl + D - 1) % D);
         bf16x8 ab[4];  // k-step s = chunks 2 s, 2 s + 1, rounded to nearest even (v_cvt_pk_bf16_f32)
 #pragma unroll
         for (int s = 0; s < 4; ++s)
@@ -1415,85 +1433,100 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
                 ab[s][i] = (__bf16)a[2 * s][i];
                 ab[s][4 + i] = (__bf16)a[2 * s + 1][i];
             }
-        f32x4 acc[NH];
+        const f32x4 bt = bn;
+        read_frags((sl + 1) % D);  // tile t + 1 (past the end: the re-read last tile, unused)
+        auto mfma_cb = [&](const int h) __attribute__((always_inline)) -> f32x4 {
+            f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int h = 0; h < NH; ++h) acc[h] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int h = 0; h < NH; ++h)
-                acc[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[s], __builtin_bit_cast(bf16x8, qb[h][s]), acc[h], 0, 0, 0);
-        // one fma and one compare per value, as in scan_f32s_kernel (a dead column block has thr = -inf / +inf)
-        unsigned long long hit[NH][4], hits = 0;
-        if (!p.metric) {
-#pragma unroll
-            for (int h = 0; h < NH; ++h)
+            for (int s = 0; s < 4; ++s)
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[s], __builtin_bit_cast(bf16x8, qb[h][s]), acc, 0, 0, 0);
+            return acc;
+        };
+        // one fma and one compare per value, as in scan_f32s_kernel (a dead column block has thr = -inf / +inf); the
+        // verdicts as wave masks in scalar registers
+        auto test_cb = [&](const int h, const f32x4 acc) __attribute__((always_inline)) {
+            unsigned long long hit[4], hits = 0;
+            if (!p.metric) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    hit[h][j] = __ballot(fmaf(-2.0f, acc[h][j], bn[j]) < thr[h]);
-                    hits |= hit[h][j];
+                    hit[j] = __ballot(fmaf(-2.0f, acc[j], bt[j]) < thr[h]);
+                    hits |= hit[j];
                 }
-        } else {
-#pragma unroll
-            for (int h = 0; h < NH; ++h)
+            } else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    hit[h][j] = __ballot(acc[h][j] > thr[h]);
-                    hits |= hit[h][j];
+                    hit[j] = __ballot(acc[j] > thr[h]);  // -acc < tau, widened
+                    hits |= hit[j];
                 }
-        }
-        if (hits) {  // rare: a few hundred rows per query per million
-            const int row_t = tile_cur * TR + 4 * g;
-#pragma unroll
-            for (int h = 0; h < NH; ++h)
+            }
+            if (__builtin_expect(hits != 0, 0)) {  // rare: a few hundred rows per query per million
+                const int row_t = ((int)blockIdx.x + t * G) * TR + 4 * g;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if (!hit[h][j]) continue;  // wave-uniform
+                    if (!hit[j]) continue;  // wave-uniform
                     const int row = row_t + j;
-                    const bool pass = ((hit[h][j] >> lane) & 1) && row < (int)p.n_rows;
+                    const bool pass = ((hit[j] >> lane) & 1) && row < (int)p.n_rows;
                     const unsigned long long mask = __ballot(pass);
                     if (mask) {
                         const int pos = wbase + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-                        // (query, value, id): the value is the bf16 sum, replaced by the exact distance in RecheckF32
-                        const int qglob = (pass_cur * NB + h / 2) * kMaxBatch + 16 * (h & 1) + r;
+                        // (query, value, id): the value is the bf16 sum, replaced by the exact distance in RecheckF32;
+                        // query = batch * 32 + 16 half + r = 16 cb + r
+                        const int qglob = 16 * (wave + kScanWaves * h) + r;
                         if (pass && pos < p.sink.wcap)
-                            wbuf[pos] = make_int4(qglob, __builtin_bit_cast(int, acc[h][j]), row + p.id_offset, 0);
+                            wbuf[pos] = make_int4(qglob, __builtin_bit_cast(int, acc[j]), row + p.id_offset, 0);
                         wbase += __popcll(mask);
                     }
                 }
+            }
+        };
+        // column block h + 1's MFMAs go out before column block h's test, which then runs beside them: two
+        // accumulators live at a time
+        f32x4 acc = mfma_cb(0);
+#pragma unroll
+        for (int h = 1; h < CBW; ++h) {
+            const f32x4 nxt = mfma_cb(h);
+            test_cb(h - 1, acc);
+            acc = nxt;
         }
-        tile_cur = tile_nxt;
-        pass_cur = pass_nxt;
-        tile_nxt = tile_new;
-        pass_nxt = pass_new;
+        test_cb(CBW - 1, acc);
     };
-    while (pass_cur < n_pass) {
-        step(0);
-        if (pass_cur >= n_pass) break;
-        step(1);
+    for (int t0 = 0; t0 < T; t0 += D) {  // T is workgroup-uniform: every wave passes the same barriers
+#pragma unroll
+        for (int sl = 0; sl < D; ++sl) {
+            if (t0 + sl >= T) break;
+            step(t0 + sl, sl);
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // retire the tail prefetches before the wave ends
     const RecheckF32 fix{p.base, p.bnorm, p.q, p.q_batch_stride, p.qnorm, p.tau0, p.metric, p.id_offset};
     sink_bin_wave<RecheckF32, true>(p.sink, (int)blockIdx.x * kScanWaves + wave, wbase, lane, fix);
 }
 
+template <int CBW>
+static hipError_t launch_scan_f32f(const StreamParams& p, int grid, hipStream_t s) {
+    constexpr int kLds = kFilterDepth * kSlotBytes;
+    auto kfn = scan_f32f_kernel<CBW, kFilterDepth>;
+    static bool attr_set[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (!attr_set[dev]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+        if (e != hipSuccess) return e;
+        attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(kScanThreads), kLds, s, p);
+    return hipGetLastError();
+}
+
 hipError_t launch_scan_f32_stream(const StreamParams& p, int grid, hipStream_t s) {
     static bool attr_set[64][2] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (p.qbf) {  // the bf16 prefilter: 2 or 4 batches per pass
-        static bool fattr_set[64][2] = {};
-        const int w = p.batches_per_pass == 4 ? 1 : 0;
-        if (p.batches_per_pass != 2 && p.batches_per_pass != 4) return hipErrorInvalidValue;
-        const void* fn = w ? reinterpret_cast<const void*>(scan_f32f_kernel<4>) : reinterpret_cast<const void*>(scan_f32f_kernel<2>);
-        if (!fattr_set[dev][w]) {
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kWideLds);
-            if (e != hipSuccess) return e;
-            fattr_set[dev][w] = true;
-        }
-        if (w) hipLaunchKernelGGL(scan_f32f_kernel<4>, dim3(grid), dim3(kScanThreads), kWideLds, s, p);
-        else hipLaunchKernelGGL(scan_f32f_kernel<2>, dim3(grid), dim3(kScanThreads), kWideLds, s, p);
-        return hipGetLastError();
+    if (p.qbf) {  // the bf16 prefilter: column blocks per wave for the launch's 2 n_batches column blocks
+        const int cbw = (2 * p.n_batches + kScanWaves - 1) / kScanWaves;
+        if (p.n_batches < 1 || cbw > 8) return hipErrorInvalidValue;
+        return cbw == 1 ? launch_scan_f32f<1>(p, grid, s) : cbw == 2 ? launch_scan_f32f<2>(p, grid, s)
+             : cbw <= 4 ? launch_scan_f32f<4>(p, grid, s) : launch_scan_f32f<8>(p, grid, s);
     }
     const int v = p.batches_per_pass == 2 ? 1 : 0;
     const void* fn = v ? reinterpret_cast<const void*>(scan_f32s_kernel<2>) : reinterpret_cast<const void*>(scan_f32s_kernel<1>);
