@@ -131,6 +131,8 @@ def lib():
         "vs_bf_search_dev": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
         "vs_bf_search_dev_multi": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "vs_bf_scores_dev": (i32, [vp, vp, i32, vp, i64, vp]),
+        "vs_bf_search_topk": (i32, [vp, vp, i64, i32, vp, vp, C.POINTER(Timing)]),
+        "vs_bf_search_topk_dev_multi": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "vs_ivf_load": (i32, [C.c_char_p, i32, i32, i32, C.POINTER(vp)]),
         "vs_ivf_create": (i32, [vp, i64, i32, vp, i32, vp, vp, i32, i32, i32, C.POINTER(vp)]),
         "vs_ivf_build": (i32, [vp, i64, i32, i32, i32, C.c_double, C.c_uint64, i32, vp, vp, C.POINTER(i32)]),
@@ -365,6 +367,22 @@ class BruteForceIndex(_Index):
                          flags_ptr: int, stream: int):
         """n_batches consecutive batches of B queries, pipelined over internal streams (vs_bf_search_dev_multi)."""
         _check(lib().vs_bf_search_dev_multi(self._h, q_ptr, n_batches, B, k, ids_ptr, dists_ptr, flags_ptr, stream))
+
+    def search_topk(self, queries, k: int, timing: Timing | None = None):
+        """``search`` for 1 <= k <= 128 (vs_bf_search_topk): for k <= 15 the same result; for k >= 16 ties leave in
+        select_topk's slot order, stably sorted."""
+        q = _f32c(queries).reshape(-1, self.d)
+        nq = q.shape[0]
+        ids = np.empty((nq, k), dtype=np.int32)
+        dists = np.empty((nq, k), dtype=np.float32)
+        tm = timing if timing is not None else Timing()
+        _check(lib().vs_bf_search_topk(self._h, _p(q), nq, k, _p(ids), _p(dists), C.byref(tm)))
+        return ids, dists
+
+    def search_topk_dev_multi(self, q_ptr: int, n_batches: int, B: int, k: int, ids_ptr: int, dists_ptr: int,
+                              flags_ptr: int, stream: int):
+        """``search_dev_multi`` for 1 <= k <= 128 (vs_bf_search_topk_dev_multi): outputs are [n_batches*B, k+1]."""
+        _check(lib().vs_bf_search_topk_dev_multi(self._h, q_ptr, n_batches, B, k, ids_ptr, dists_ptr, flags_ptr, stream))
 
     @staticmethod
     def search_vshards(shards, queries: np.ndarray, k: int, timing: "Timing | None" = None):

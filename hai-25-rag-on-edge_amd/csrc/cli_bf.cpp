@@ -9,6 +9,9 @@
 //   ... --q8[=in_scale,w_scale,w_offset,out_scale]: the qidk form through the runner's UFIXED_POINT_8 path (QnnRunner.cpp:
 //                                                13-55, 608-645; main.cpp:30-57): uint8 scores, results.txt holds
 //                                                (id, score8 * output_scale) with 4 decimals (main.cpp:244-246)
+//   vsearch_bf --groundtruth <base.fvecs> <query.fvecs> <out.ivecs> [k=100]
+//                                              : exact k-NN ground truth (TEXMEX .ivecs: one row of k ids per query, the
+//                                                ids of vs_bf_search_topk, 1 <= k <= 128), for vsearch_ivf's recall; one GPU
 //   ... --gpus N                               : any form on N GPUs, one process per GPU (forked before HIP starts): the base
 //                                                is row-sharded, per-shard top-(k+1) lists meet in one RCCL all-gather per
 //                                                32 batches (vs_bf_search_sharded); rank 0 writes the files
@@ -163,13 +166,13 @@ bool run_benchmark(const std::string& dataset_name, const std::string& base_file
             vs_timing wt{};
             if (wn > 0) {
                 if (g_ranks.world > 1) index.searchSharded(g_ranks.comm, wq, wn, k, wr, &wt);
-                else index.search(wq, wn, k, wr, &wt);
+                else index.search_topk(wq, wn, k, wr, &wt);
             }
         }
         vsearch::check(vs_prof_enable(index.handle(), 1));
         auto t0 = high_resolution_clock::now();
         if (g_ranks.world > 1) index.searchSharded(g_ranks.comm, Q_data, Q_rows, k, results, &r.tm);
-        else index.search(Q_data, Q_rows, k, results, &r.tm);
+        else index.search_topk(Q_data, Q_rows, k, results, &r.tm);  // (k <= 15: exactly index.search)
         auto t1 = high_resolution_clock::now();
         r.total_s = duration_cast<duration<double>>(t1 - t0).count();
         {   // per-batch device times: launch l served min(32, remaining) batches
@@ -288,6 +291,50 @@ bool run_q8(const std::string& docs_file, const std::string& query_file, int k, 
     }
 }
 
+// --groundtruth: the ids of vs_bf_search_topk as TEXMEX ground truth (main_ivf.cpp:35-50 reads it back)
+bool run_groundtruth(const std::string& base_file, const std::string& query_file, const std::string& out_file, int k) {
+    std::vector<float> Q_data, B_data;
+    int Q_rows = 0, Q_dim = 0, B_rows = 0, B_dim = 0;
+    if (!vsearch::read_fvecs(base_file, B_data, B_rows, B_dim) || !vsearch::read_fvecs(query_file, Q_data, Q_rows, Q_dim)) {
+        std::cerr << "Error: " << vs_last_error() << std::endl;
+        return false;
+    }
+    if (Q_dim != B_dim) {
+        std::cerr << "Error: Query and Base dimensions must be equal." << std::endl;
+        return false;
+    }
+    try {
+        vsearch::ExactSearch index(B_data, B_rows, B_dim, 0);
+        std::vector<int32_t> ids((size_t)Q_rows * k);
+        std::vector<float> dists((size_t)Q_rows * k);
+        vs_timing tm{};
+        vsearch::check(vs_bf_search_topk(index.handle(), Q_data.data(), Q_rows, k, ids.data(), dists.data(), &tm));
+        if (vs_ivecs_write(out_file.c_str(), ids.data(), Q_rows, k) != VS_OK) {
+            std::cerr << "Error: " << vs_last_error() << std::endl;
+            return false;
+        }
+        std::cout << "Ground truth: " << Q_rows << " queries x " << k << " ids over " << B_rows << " rows -> " << out_file << std::endl;
+        std::cout << "  total_ms " << tm.total_ms << " (search " << tm.fine_search_ms << ", tie resolution " << tm.tie_resolve_ms
+                  << " for " << tm.tie_queries << " queries)" << std::endl;
+        return true;
+    } catch (const std::exception& e) {
+        std::cerr << "Error: " << e.what() << std::endl;
+        return false;
+    }
+}
+
+const char* kUsage =
+    "usage: vsearch_bf                                   (k = 5 on siftsmall/ and sift/)\n"
+    "       vsearch_bf <base.fvecs> <query.fvecs> <k> <out> [batch]\n"
+    "       vsearch_bf <context_binary> <queries.fvecs> <results_dir> <backend.so> <documents.fvecs> <top_k> [batch] [--q8[=...]]\n"
+    "       vsearch_bf --groundtruth <base.fvecs> <query.fvecs> <out.ivecs> [k=100]\n"
+    "       (any form but --groundtruth: [--gpus N]; 1 <= k <= 128, on one GPU for k > 15)\n";
+
+bool file_exists(const char* path) {
+    struct stat st;
+    return path && *path && stat(path, &st) == 0 && S_ISREG(st.st_mode);
+}
+
 std::string metrics_name(const std::string& out) {
     const std::string tag = "_results.txt";
     if (out.size() >= tag.size() && out.compare(out.size() - tag.size(), tag.size(), tag) == 0)
@@ -317,8 +364,48 @@ int main(int argc, char* argv[]) {
         --argc;
         break;
     }
+    // argument checks that need no GPU come first: nothing below them has touched HIP yet
+    bool groundtruth = false;
+    for (int i = 1; i < argc; ++i) {
+        if (std::string(argv[i]) != "--groundtruth") continue;
+        groundtruth = true;
+        for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+        --argc;
+        break;
+    }
+    int world = 1;
     try {
-        g_ranks = vsearch::fork_ranks(vsearch::take_gpus_flag(argc, argv));  // before anything touches HIP
+        world = vsearch::take_gpus_flag(argc, argv);
+    } catch (const std::exception& e) {
+        std::cerr << "FATAL ERROR: " << e.what() << "\n" << kUsage;
+        return 1;
+    }
+    if (groundtruth) {
+        int k = 100;
+        if (argc < 4 || argc > 5 || (argc == 5 && !vsearch::arg_int(argv[4], k)) || k < 1 || k > 128 || q8) {
+            std::cerr << "FATAL ERROR: --groundtruth needs <base.fvecs> <query.fvecs> <out.ivecs> [k in 1..128]\n" << kUsage;
+            return 1;
+        }
+        if (!file_exists(argv[1]) || !file_exists(argv[2]) || !*argv[3]) {
+            std::cerr << "FATAL ERROR: --groundtruth: missing input file or empty output path\n" << kUsage;
+            return 1;
+        }
+        if (world > 1) {
+            std::cerr << "FATAL ERROR: --groundtruth runs on one GPU (the sharded search keeps k <= 15)\n" << kUsage;
+            return 1;
+        }
+        return run_groundtruth(argv[1], argv[2], argv[3], k) ? 0 : 1;
+    }
+    if (!q8 && argc >= 5 && argc <= 8) {  // the positional and qidk forms: k in 1..128, and k > 15 on one GPU only
+        int k = 0;
+        const bool ok = vsearch::arg_int(argv[argc == 7 || argc == 8 ? 6 : 3], k);
+        if (ok && (k < 1 || k > 128 || (k > 15 && world > 1))) {
+            std::cerr << "FATAL ERROR: k must be in 1..128 (k > 15: one GPU)\n" << kUsage;
+            return 1;
+        }
+    }
+    try {
+        g_ranks = vsearch::fork_ranks(world);  // before anything touches HIP
         vsearch::connect_ranks(g_ranks);
     } catch (const std::exception& e) {
         std::cerr << "FATAL ERROR: " << e.what() << std::endl;

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <limits>
 #include <numeric>
@@ -57,6 +58,8 @@ constexpr int kIvfWideWaveCap = 512;  // entries per wave buffer of the wide IVF
 constexpr int kIvfWideSubCap = 256;   // entries per candidate sub-list (16 per query: 4096 candidates)
 constexpr int kTieDense = 4096;   // rows whose distances the tie resolver takes densely
 constexpr int kTieCap = 8192;     // candidate slots per flagged query (more: full-row fallback)
+constexpr int kTopwFilterCap = 8192;  // filter candidates per query of the wide-k launcher (more: the dense fallback)
+constexpr int64_t kTopwChunkBytes = (int64_t)256 << 20;  // score scratch of the wide-k dense fallback ([32][chunk] floats)
 
 struct ProfSlot {
     std::vector<vs::Event> ev;  // pairs
@@ -250,7 +253,31 @@ struct vs_index {
         vs::DevBuf<int32_t> row;  // [32][kTieCap]
         vs::DevBuf<float> d;      // [32][kTieCap]
         bool ready = false;       // every buffer above allocated
+        int64_t dense_cap = kTieDense;  // rows per query `dense` and `pin` hold (k >= 16 takes a longer prefix)
     } tie;
+    // wide-k brute force (k + 1 > 16, topw_launch), allocated on the first such call: distances to the prefix rows, the
+    // prefix's k1 best and bound, the filter's candidates, the dense fallback's chunk scores and per-chunk lists, and the
+    // host call's staging
+    struct TopW {
+        int64_t l0p = 0;              // prefix rows (padded) the buffers hold: topw_prefix(n_rows, kTopkWideMax)
+        int64_t chunk = 0;            // rows per chunk of the dense fallback
+        int n_chunks = 0;
+        vs::DevBuf<float> pre;        // [32][l0p]
+        vs::DevBuf<float> tau;        // [32]
+        vs::DevBuf<float> pre_d;      // [32][kTopkWideMax]
+        vs::DevBuf<int32_t> pre_i;
+        vs::DevBuf<int32_t> fz;       // filter counts [32] | overflow word (cleared by the prefix selection)
+        vs::DevBuf<int32_t> f_row;    // [32][kTopwFilterCap]
+        vs::DevBuf<float> f_d;
+        vs::DevBuf<float> full;       // [32][chunk]
+        vs::DevBuf<float> ch_d;       // [32][n_chunks][kTopkWideMax]
+        vs::DevBuf<int32_t> ch_i;
+        vs::PinBuf<float> pin_q;      // [kMaxMulti * 32][128]
+        vs::PinBuf<char> pin_out;     // dists | ids | flags of one chunk of queries
+        vs::DevBuf<float> d_q, out_d;
+        vs::DevBuf<int32_t> out_i, flags;
+        bool ready = false;           // every buffer above allocated (ensure_topw)
+    } topw;
 
     // SearchTiming split of vs_ivf_search (IVFIndex.h:31-36): HIP events between the stages of every launch group
     std::vector<vs::Event> stage_ev;  // quadruples: start, after coarse + pick, after grouping, after scan + select
@@ -767,8 +794,9 @@ int bf_multi_dev(vs_index* h, const float* q_dev, int nb, int B, int k1, float* 
 }
 
 int scores_dev(vs_index* h, const float* vecs, const float* norms, int64_t rows, const float* q_dev, int B,
-               float* scores, int64_t ld, hipStream_t s) {
+               float* scores, int64_t ld, hipStream_t s, const int32_t* run_if = nullptr) {
     vs::ScanParams p{};
+    p.run_if = run_if;
     p.base = vecs;
     p.bnorm = norms;
     p.q = q_dev;
@@ -783,6 +811,175 @@ int scores_dev(vs_index* h, const float* vecs, const float* norms, int64_t rows,
     p.store = scores;
     p.store_ld = ld;
     HIPCHK(vs::launch_scan(p, grid, 8, B <= 16 ? 1 : 2, vs::kModeStore, s));
+    return VS_OK;
+}
+
+// ---- wide k (k1 = k + 1 in 17..129).  Per batch: the distances to a prefix of the rows (scores_dev), its k1 best and
+// bound tau = next_up(k1-th best) (topk_wide_kernel, dense form), one filtered pass over the other rows that keeps every
+// distance under tau (kModeFilter, about n_rows * k1 / prefix rows per query), and the k1 best of the prefix's list and the
+// candidates (topk_wide_kernel, list form).  Exact: a row after the prefix at or above tau has k1 prefix rows before it.
+// A candidate list that overflows (masses of equal rows) raises the batch's overflow word, and the dense fallback enqueued
+// behind it (scores of row chunks, a selection per chunk, a selection over the chunk lists) rewrites the outputs.
+int64_t topw_prefix(int64_t n_rows, int k1) {
+    // about n_rows / 512 candidates per query at most 2048 (larger bases take a longer prefix), a multiple of 4096 rows
+    int64_t l = std::max<int64_t>(512 * (int64_t)k1, n_rows * k1 / 2048);
+    l = (l + 4095) & ~int64_t(4095);
+    return std::min(l, n_rows);
+}
+
+int ensure_topw(vs_index* h) {
+    if (h->topw.ready) return VS_OK;
+    vs_index::TopW w;
+    const size_t nqc = (size_t)kMaxMulti * 32;
+    w.l0p = (topw_prefix(h->n_rows, vs::kTopkWideMax) + 15) & ~int64_t(15);
+    w.chunk = std::min<int64_t>((h->n_rows + 15) & ~int64_t(15), kTopwChunkBytes / (32 * sizeof(float)));
+    w.n_chunks = (int)((h->n_rows + w.chunk - 1) / w.chunk);
+    const size_t kw = vs::kTopkWideMax;
+    int rc;
+    if ((rc = w.pre.alloc((size_t)32 * w.l0p)) || (rc = w.tau.alloc(32)) || (rc = w.pre_d.alloc(32 * kw)) || (rc = w.pre_i.alloc(32 * kw)) ||
+        (rc = w.fz.alloc(64)) || (rc = w.f_row.alloc((size_t)32 * kTopwFilterCap)) || (rc = w.f_d.alloc((size_t)32 * kTopwFilterCap)) ||
+        (rc = w.full.alloc((size_t)32 * w.chunk)) || (rc = w.ch_d.alloc((size_t)32 * w.n_chunks * kw)) ||
+        (rc = w.ch_i.alloc((size_t)32 * w.n_chunks * kw)) || (rc = w.pin_q.alloc(nqc * vs::kDim)) ||
+        (rc = w.pin_out.alloc(nqc * (2 * kw + 1) * sizeof(float))) || (rc = w.d_q.alloc(nqc * vs::kDim)) ||
+        (rc = w.out_d.alloc(nqc * kw)) || (rc = w.out_i.alloc(nqc * kw)) || (rc = w.flags.alloc(nqc)))
+        return rc;
+    HIPCHK(hipMemset(w.fz, 0, 64 * sizeof(int32_t)));
+    w.ready = true;
+    h->topw = std::move(w);
+    return VS_OK;
+}
+
+// diagnostic knob (VSEARCH_TOPW_STATS=1): topw_launch waits for every batch and counts the batches whose candidate lists
+// overflowed and the candidates per query; vs_bf_search_topk prints the counts to stderr
+int g_topw_stats = [] {
+    const char* e = getenv("VSEARCH_TOPW_STATS");
+    return e ? atoi(e) : 0;
+}();
+struct TopwStats {
+    int64_t batches = 0, overflowed = 0, queries = 0, cand_sum = 0, cand_max = 0;
+} g_topw_st;
+
+// nb batches of B queries -> [nb][B][k1] by (dist, id) + flags (1 = two equal distances among the k1), on stream s
+int topw_launch(vs_index* h, const float* q_dev, int nb, int B, int k1, float* out_d, int32_t* out_i, int32_t* flags,
+                hipStream_t s) {
+    vs_index::TopW& W = h->topw;
+    const int64_t n = h->n_rows;
+    const int64_t l0 = topw_prefix(n, k1), l0p = (l0 + 15) & ~int64_t(15);
+    int32_t* const overflow = W.fz + 32;
+    int rc;
+    prof_begin(h, 0, s);
+    for (int b = 0; b < nb; ++b) {
+        const float* qb = q_dev + (size_t)b * B * vs::kDim;
+        float* const od = out_d + (size_t)b * B * k1;
+        int32_t* const oi = out_i + (size_t)b * B * k1;
+        int32_t* const fl = flags ? flags + (size_t)b * B : nullptr;
+        if ((rc = scores_dev(h, h->d_vecs, h->d_norm, l0, qb, B, W.pre, l0p, s))) return rc;
+        vs::TopkWideParams t{};
+        t.dense = W.pre;
+        t.dense_ld = l0p;
+        t.n_dense = l0;
+        t.dense_id0 = (int32_t)h->id_offset;
+        t.nq = B;
+        t.k1 = k1;
+        if (l0 == n) {  // the prefix is the whole shard
+            t.out_d = od;
+            t.out_i = oi;
+            t.out_ld = k1;
+            t.flags = fl;
+            HIPCHK(vs::launch_topk_wide(t, B, s));
+            continue;
+        }
+        t.out_d = W.pre_d;
+        t.out_i = W.pre_i;
+        t.out_ld = vs::kTopkWideMax;
+        t.tau_out = W.tau;
+        t.zero = W.fz;
+        t.zero_words = 33;
+        HIPCHK(vs::launch_topk_wide(t, 32, s));
+        vs::ScanParams p{};
+        p.base = h->d_vecs;
+        p.bnorm = h->d_norm;
+        p.q = qb;
+        p.n_batches = 1;
+        p.metric = h->metric;
+        p.nq_valid = B;
+        p.k1 = k1;
+        p.tau0 = W.tau;
+        p.row_begin = l0;  // a multiple of 4096
+        p.row_end = n;
+        p.f_cnt = W.fz;
+        p.f_row = W.f_row;
+        p.f_d = W.f_d;
+        p.f_cap = kTopwFilterCap;
+        int grid, tp;
+        scan_geometry(n - l0, h->num_cus, grid, tp);
+        p.tiles_per_wg = tp;
+        HIPCHK(vs::launch_scan(p, grid, 8, 2, vs::kModeFilter, s));
+        vs::TopkWideParams f{};
+        f.list[0] = {W.pre_d, W.pre_i, vs::kTopkWideMax, nullptr, k1, 0};
+        f.list[1] = {W.f_d, W.f_row, kTopwFilterCap, W.fz, kTopwFilterCap, (int32_t)h->id_offset};
+        f.n_list = 2;
+        f.nq = B;
+        f.k1 = k1;
+        f.out_d = od;
+        f.out_i = oi;
+        f.out_ld = k1;
+        f.flags = fl;
+        f.overflow = overflow;
+        HIPCHK(vs::launch_topk_wide(f, B, s));
+        if (g_topw_stats) {
+            int32_t c[33];
+            HIPCHK(hipMemcpyAsync(c, W.fz, sizeof(c), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            ++g_topw_st.batches;
+            g_topw_st.overflowed += c[32] != 0;
+            for (int i = 0; i < B; ++i) {
+                ++g_topw_st.queries;
+                g_topw_st.cand_sum += c[i];
+                g_topw_st.cand_max = std::max<int64_t>(g_topw_st.cand_max, c[i]);
+            }
+        }
+        // dense fallback, idle unless a candidate list overflowed
+        const int nc = W.n_chunks;
+        for (int c = 0; c < nc; ++c) {
+            const int64_t r0 = (int64_t)c * W.chunk, rows = std::min(W.chunk, n - r0);
+            if ((rc = scores_dev(h, h->d_vecs + (size_t)r0 * vs::kDim, h->d_norm + r0, rows, qb, B, W.full, W.chunk, s, overflow)))
+                return rc;
+            vs::TopkWideParams d{};
+            d.dense = W.full;
+            d.dense_ld = W.chunk;
+            d.n_dense = rows;
+            d.dense_id0 = (int32_t)(h->id_offset + r0);
+            d.nq = B;
+            d.k1 = k1;
+            d.run_if = overflow;
+            if (nc == 1) {
+                d.out_d = od;
+                d.out_i = oi;
+                d.out_ld = k1;
+                d.flags = fl;
+            } else {
+                d.out_d = W.ch_d + (size_t)c * k1;
+                d.out_i = W.ch_i + (size_t)c * k1;
+                d.out_ld = (int64_t)nc * k1;
+            }
+            HIPCHK(vs::launch_topk_wide(d, B, s));
+        }
+        if (nc > 1) {
+            vs::TopkWideParams m{};
+            m.list[0] = {W.ch_d, W.ch_i, (int64_t)nc * k1, nullptr, nc * k1, 0};
+            m.n_list = 1;
+            m.nq = B;
+            m.k1 = k1;
+            m.out_d = od;
+            m.out_i = oi;
+            m.out_ld = k1;
+            m.flags = fl;
+            m.run_if = overflow;
+            HIPCHK(vs::launch_topk_wide(m, B, s));
+        }
+    }
+    prof_end(h, 0, s);
     return VS_OK;
 }
 
@@ -1310,12 +1507,16 @@ int resolve_dense_full(vs_index* h, const float* q_dev, int B, const std::vector
 // "dense rows, then candidates in row order".  Exact whenever the distances are (integer-valued SIFT: always).
 int resolve_ties(vs_index* h, const float* queries_host, const std::vector<int64_t>& flagged, int k, int32_t* ids, float* dists) {
     int rc;
-    const int64_t L0 = std::min<int64_t>(h->n_rows, kTieDense);
+    // k >= 16: a prefix that grows with k (512 k rows, a multiple of 4096), so that about n_rows / 512 rows pass the bound
+    // whatever k is (the k <= 15 prefix of kTieDense rows would let n_rows * k / 4096 through, past kTieCap at 1 M rows)
+    const int64_t dense_rows = k <= 15 ? kTieDense : ((int64_t)512 * k + 4095) & ~int64_t(4095);
+    const int64_t L0 = std::min<int64_t>(h->n_rows, dense_rows);
     const int64_t L0p = (L0 + 15) & ~int64_t(15);
-    if (!h->tie.ready) {
+    if (!h->tie.ready || h->tie.dense_cap < dense_rows) {
         vs_index::Tie t;
-        if ((rc = t.dense.alloc((size_t)32 * kTieDense)) || (rc = t.tau.alloc(32)) || (rc = t.cnt.alloc(32)) || (rc = t.row.alloc((size_t)32 * kTieCap)) ||
-            (rc = t.d.alloc((size_t)32 * kTieCap)) || (rc = t.pin.alloc((size_t)32 * kTieDense * 4 + 128 + (size_t)2 * 32 * kTieCap * 4)))
+        t.dense_cap = std::max<int64_t>(dense_rows, h->tie.ready ? h->tie.dense_cap : kTieDense);
+        if ((rc = t.dense.alloc((size_t)32 * t.dense_cap)) || (rc = t.tau.alloc(32)) || (rc = t.cnt.alloc(32)) || (rc = t.row.alloc((size_t)32 * kTieCap)) ||
+            (rc = t.d.alloc((size_t)32 * kTieCap)) || (rc = t.pin.alloc((size_t)32 * t.dense_cap * 4 + 128 + (size_t)2 * 32 * kTieCap * 4)))
             return rc;
         t.ready = true;
         h->tie = std::move(t);
@@ -1323,7 +1524,7 @@ int resolve_ties(vs_index* h, const float* queries_host, const std::vector<int64
     const int group = 32;
     // downloads land in pinned memory (pageable destinations are staged by the runtime: several times slower)
     float* const dense = reinterpret_cast<float*>(h->tie.pin.get());
-    int32_t* const cnt = reinterpret_cast<int32_t*>(h->tie.pin + (size_t)32 * kTieDense * 4);
+    int32_t* const cnt = reinterpret_cast<int32_t*>(h->tie.pin + (size_t)32 * h->tie.dense_cap * 4);
     int32_t* const cr = cnt + 32;
     float* const cd = reinterpret_cast<float*>(cr + (size_t)32 * kTieCap);
     std::vector<float> qbuf((size_t)group * vs::kDim);
@@ -1338,14 +1539,28 @@ int resolve_ties(vs_index* h, const float* queries_host, const std::vector<int64
             // bound = next_up(k-th smallest of the dense rows): merge kernel over G = L0 one-entry lists
             HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->tie.tau.get()), 0xff800000u, 32, h->stream));  // -inf: padding queries emit nothing
             HIPCHK(hipMemsetAsync(h->tie.cnt, 0, 32 * sizeof(int32_t), h->stream));
-            vs::MergeParams m{};
-            m.part_d = h->tie.dense;
-            m.G = (int)L0;
-            m.kin = 1;
-            m.nq = B;
-            m.kout = k;
-            m.tau_out = h->tie.tau;
-            HIPCHK(vs::launch_merge_layout(m, 1, L0p, h->stream));
+            if (k <= 15) {
+                vs::MergeParams m{};
+                m.part_d = h->tie.dense;
+                m.G = (int)L0;
+                m.kin = 1;
+                m.nq = B;
+                m.kout = k;
+                m.tau_out = h->tie.tau;
+                HIPCHK(vs::launch_merge_layout(m, 1, L0p, h->stream));
+            } else {  // (vs_bf_search_topk: the wide-k scratch exists)
+                vs::TopkWideParams t{};
+                t.dense = h->tie.dense;
+                t.dense_ld = L0p;
+                t.n_dense = L0;
+                t.nq = B;
+                t.k1 = k;
+                t.out_d = h->topw.pre_d;
+                t.out_i = h->topw.pre_i;
+                t.out_ld = vs::kTopkWideMax;
+                t.tau_out = h->tie.tau;
+                HIPCHK(vs::launch_topk_wide(t, 32, h->stream));
+            }
             vs::ScanParams p{};
             p.base = h->d_vecs;
             p.bnorm = h->d_norm;
@@ -1355,7 +1570,7 @@ int resolve_ties(vs_index* h, const float* queries_host, const std::vector<int64
             p.nq_valid = B;
             p.k1 = k + 1;
             p.tau0 = h->tie.tau;
-            p.row_begin = L0;  // multiple of 16 (kTieDense)
+            p.row_begin = L0;  // multiple of 16 (kTieDense, 4096)
             p.row_end = h->n_rows;
             p.f_cnt = h->tie.cnt;
             p.f_row = h->tie.row;
@@ -1758,6 +1973,108 @@ int vs_bf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int3
         if (timing) *timing = tm;
         return order_end(h, h->stream);
     });
+}
+
+int vs_bf_search_topk(vs_index* h, const float* queries_host, int64_t nq, int k, int32_t* ids, float* dists, vs_timing* timing) {
+    if (!h || h->kind != 0 || !queries_host || !ids || !dists || nq < 0 || k < 1) {
+        set_error("vs_bf_search_topk: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    if (k > vs::kTopkWideMax - 1) {
+        set_error("vs_bf_search_topk: k > 128");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (k + 1 <= kKcapMax) return vs_bf_search(h, queries_host, nq, k, ids, dists, timing);
+    return guarded([&]() -> int {
+        int rc = set_device(h);
+        if (rc) return rc;
+        const double t_start = now_ms();
+        vs_timing tm{};
+        const int k1 = k + 1;
+        if (g_topw_stats) g_topw_st = TopwStats{};
+        if ((rc = ensure_topw(h)) || (rc = order_begin(h, h->stream))) return rc;
+        settle_slots(h->pipe, {h->stream, h->s_h2d, h->s_d2h});
+        vs_index::TopW& W = h->topw;
+        const int64_t chunk = (int64_t)kMaxMulti * h->batch;
+        float* const hd = reinterpret_cast<float*>(W.pin_out.get());
+        int32_t* const hi = reinterpret_cast<int32_t*>(hd + (size_t)chunk * k1);
+        int32_t* const hf = hi + (size_t)chunk * k1;
+        std::vector<int64_t> flagged;
+        const float inf = std::numeric_limits<float>::infinity();
+        // chunks of kMaxMulti batches, one after the other: upload, the wide-k launches (full batches, then a ragged tail
+        // batch), download
+        for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+            const int64_t n = std::min<int64_t>(chunk, nq - q0);
+            const double t0 = now_ms();
+            std::memcpy(W.pin_q, queries_host + q0 * vs::kDim, (size_t)n * vs::kDim * sizeof(float));
+            HIPCHK(hipMemcpyAsync(W.d_q, W.pin_q, (size_t)n * vs::kDim * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            tm.h2d_ms += now_ms() - t0;
+            const int full = (int)(n / h->batch), rem = (int)(n % h->batch);
+            if (full && (rc = topw_launch(h, W.d_q, full, h->batch, k1, W.out_d, W.out_i, W.flags, h->stream))) return rc;
+            if (rem) {
+                const size_t o = (size_t)full * h->batch;
+                if ((rc = topw_launch(h, W.d_q + o * vs::kDim, 1, rem, k1, W.out_d + o * k1, W.out_i + o * k1, W.flags + o, h->stream)))
+                    return rc;
+            }
+            const double t1 = now_ms();
+            HIPCHK(hipMemcpyAsync(hd, W.out_d, (size_t)n * k1 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(hi, W.out_i, (size_t)n * k1 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(hf, W.flags, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            tm.d2h_ms += now_ms() - t1;
+            for (int64_t b = 0; b < n; ++b) {
+                for (int t = 0; t < k; ++t) {
+                    const int32_t id = hi[(size_t)b * k1 + t];
+                    ids[(q0 + b) * k + t] = id;
+                    float d = id >= 0 ? hd[(size_t)b * k1 + t] : inf;
+                    if (h->metric == VS_METRIC_IP && id >= 0) d = -d;
+                    dists[(q0 + b) * k + t] = d;
+                }
+                if (hf[(size_t)b]) flagged.push_back(q0 + b);
+            }
+        }
+        tm.fine_search_ms = now_ms() - t_start;
+        // equal distances among the k + 1 best: select_topk's slots over the rows that can change them (resolve_ties)
+        if (!flagged.empty() && h->metric == VS_METRIC_L2) {
+            const double t0 = now_ms();
+            if ((rc = resolve_ties(h, queries_host, flagged, k, ids, dists))) return rc;
+            tm.tie_resolve_ms = now_ms() - t0;
+            tm.tie_queries = (int64_t)flagged.size();
+        }
+        tm.total_ms = now_ms() - t_start;
+        if (timing) *timing = tm;
+        if (g_topw_stats)
+            fprintf(stderr, "topw_stats k=%d batches=%lld overflowed=%lld queries=%lld cand_mean=%.1f cand_max=%lld flagged=%lld\n", k,
+                    (long long)g_topw_st.batches, (long long)g_topw_st.overflowed, (long long)g_topw_st.queries,
+                    g_topw_st.queries ? (double)g_topw_st.cand_sum / g_topw_st.queries : 0.0, (long long)g_topw_st.cand_max,
+                    (long long)flagged.size());
+        return order_end(h, h->stream);
+    });
+}
+
+int vs_bf_search_topk_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k, int32_t* ids_dev,
+                                float* dists_dev, int32_t* flags_dev, void* stream) {
+    if (!h || h->kind != 0 || !queries_dev || !ids_dev || !dists_dev || n_batches < 1 || B < 1 || B > vs::kMaxBatch || k < 1) {
+        set_error("vs_bf_search_topk_dev_multi: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    if (k > vs::kTopkWideMax - 1) {
+        set_error("vs_bf_search_topk_dev_multi: k > 128");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (k + 1 <= kKcapMax) return vs_bf_search_dev_multi(h, queries_dev, n_batches, B, k, ids_dev, dists_dev, flags_dev, stream);
+    int rc = set_device(h);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if ((rc = ensure_topw(h)) || (rc = order_begin(h, st))) return rc;
+    const int k1 = k + 1;
+    for (int b0 = 0; b0 < n_batches; b0 += kMaxMulti) {
+        const int n = std::min(kMaxMulti, n_batches - b0);
+        if ((rc = topw_launch(h, queries_dev + (size_t)b0 * B * vs::kDim, n, B, k1, dists_dev + (size_t)b0 * B * k1,
+                              ids_dev + (size_t)b0 * B * k1, flags_dev ? flags_dev + (size_t)b0 * B : nullptr, st)))
+            return rc;
+    }
+    return order_end(h, st);
 }
 
 // --------------------------------------------------------------------------------------------- IVF

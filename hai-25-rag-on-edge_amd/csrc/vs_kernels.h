@@ -256,6 +256,41 @@ hipError_t launch_merge(const MergeParams& p, hipStream_t s);  // scan-partial l
 // general layout: entry (g, q, j) at g*stride_g + q*stride_q + j
 hipError_t launch_merge_layout(const MergeParams& p, int64_t stride_g, int64_t stride_q, hipStream_t s);
 
+// Wide top-k (vs_topk_wide.hip): per query, the k1 <= kTopkWideMax smallest 64-bit keys (order-preserving bits of the
+// distance) << 32 | id out of a dense score block and / or up to two candidate lists -- i.e. the k1 best by (dist, id).
+// Radix select over the keys with LDS histograms (8-bit digits, most significant first) until the entries at or below the
+// selected prefix fit in LDS, then one compaction and a bitonic sort of those.  Non-finite distances are treated like
+// merge_compact_kernel does: +inf and NaN never enter an output (slots past the finite entries are (+inf, -1)).
+constexpr int kTopkWideMax = 129;   // k1 = k + 1 for k <= 128
+struct TopkList {
+    const float* d;          // entry e of query q at d[q * stride_q + e]
+    const int32_t* i;        // ids (negative: padding, skipped)
+    int64_t stride_q;
+    const int32_t* cnt;      // optional [nq]: entries of query q (more than cap: the launch's overflow word is raised)
+    int cap;                 // entries per query (cnt == nullptr: all of them)
+    int32_t id_add;          // added to every id read from i
+};
+struct TopkWideParams {
+    const float* dense;      // optional form (b): [nq][dense_ld] scores, column c has id dense_id0 + c
+    int64_t dense_ld;        // a multiple of 4
+    int64_t n_dense;         // columns per query
+    int32_t dense_id0;
+    TopkList list[2];        // form (a): list[0..n_list) (unsorted)
+    int n_list;
+    int nq;                  // queries with outputs; blocks [nq, gridDim.x) only write tau_out = -inf
+    int k1;
+    float* out_d;            // [nq][out_ld] ascending (dist, id), padded with (+inf, -1)
+    int32_t* out_i;
+    int64_t out_ld;
+    int32_t* flags;          // optional [nq]: 1 = two equal finite distances among the k1 outputs
+    float* tau_out;          // optional [gridDim.x]: next_up(k1-th best), +inf when there are fewer, -inf for blocks >= nq
+    int32_t* zero;           // optional: zero_words words cleared by block 0 (before anything reads them: not an input)
+    int zero_words;
+    int32_t* overflow;       // optional [1]: set to 1 when a list count exceeds its cap
+    const int32_t* run_if;   // optional [1]: the launch does nothing unless *run_if != 0
+};
+hipError_t launch_topk_wide(const TopkWideParams& p, int grid, hipStream_t s);
+
 // One Lloyd update: deterministic fixed-point cluster sums -> new centroids; shift[c] = ||new - old||^2.
 hipError_t launch_kmeans_update(const float* x, const int32_t* assign, int64_t rows, int nlist, float* cents,
                                 unsigned long long* acc, int32_t* counts, double* shift, hipStream_t s);

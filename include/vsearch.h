@@ -155,6 +155,17 @@ VS_API int vs_bf_search_dev(vs_index* h, const float* queries_dev, int B, int k,
 VS_API int vs_bf_search_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k,
                                   int32_t* ids_dev, float* dists_dev, int32_t* flags_dev, void* stream);
 
+/* Wide k: 1 <= k <= 128.  For k <= 15 the result is exactly vs_bf_search's (same code path).  For k >= 16: the k best by
+ * select_topk's slot semantics; order among equal distances = slot order, stably sorted.  k > 128 returns
+ * VS_ERR_UNSUPPORTED.  The k >= 16 path scans the fp32 rows whatever vs_set_precision says (the distances are the same). */
+VS_API int vs_bf_search_topk(vs_index* h, const float* queries_host, int64_t nq, int k,
+                             int32_t* ids, float* dists, vs_timing* timing);
+/* Device form of vs_bf_search_dev_multi for 1 <= k <= 128: outputs [n_batches*B x (k+1)] by (dist, id) ascending,
+ * flags[n_batches*B] as vs_bf_search_dev_multi (1 = equal distances among the k+1, 2 = int8 batch skipped; for k >= 16
+ * the fp32 rows are scanned and 2 does not occur). */
+VS_API int vs_bf_search_topk_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k,
+                                       int32_t* ids_dev, float* dists_dev, int32_t* flags_dev, void* stream);
+
 /* QnnRunner::executeBatchRaw proper (QnnRunner.cpp:683-724): the raw
  * [B x ld] score matrix, scores_dev[b*ld + j] = dist(query b, row j), ld >= n_rows. */
 VS_API int vs_bf_scores_dev(vs_index* h, const float* queries_dev, int B,

@@ -97,6 +97,17 @@ public:
             for (int t = 0; t < k; ++t)
                 if (ids[(size_t)i * k + t] >= 0) results[(size_t)i].push_back({dists[(size_t)i * k + t], ids[(size_t)i * k + t]});
     }
+    // the same for 1 <= k <= 128 (vs_bf_search_topk): for k >= 16 ties leave in select_topk's slot order, stably sorted
+    void search_topk(const std::vector<float>& queries, int nq, int k, std::vector<std::vector<Result>>& results,
+                     vs_timing* timing = nullptr) {
+        std::vector<int32_t> ids((size_t)nq * k);
+        std::vector<float> dists((size_t)nq * k);
+        check(vs_bf_search_topk(h_, queries.data(), nq, k, ids.data(), dists.data(), timing));
+        results.assign((size_t)nq, {});
+        for (int i = 0; i < nq; ++i)
+            for (int t = 0; t < k; ++t)
+                if (ids[(size_t)i * k + t] >= 0) results[(size_t)i].push_back({dists[(size_t)i * k + t], ids[(size_t)i * k + t]});
+    }
     // collective over `comm` (every rank: same queries, own shard); ties come out in (dist, id) order
     void searchSharded(vs_comm* comm, const std::vector<float>& queries, int nq, int k, std::vector<std::vector<Result>>& results,
                        vs_timing* timing = nullptr) {
