@@ -153,10 +153,10 @@ struct vs_index {
     Lane lane[kMaxLanes];
     int n_lanes = 1;
     vs::Event fork;
-    vs::DevBuf<float> d_out_d;    // [32][64]
+    vs::DevBuf<float> d_out_d;    // [kMaxMulti * 32][kTopkWideMax]
     vs::DevBuf<int32_t> d_out_i;
-    vs::DevBuf<int32_t> d_flags;  // [32]
-    vs::DevBuf<float> d_scores;   // IVF query-major fallback: coarse scores [32][nlist_pad]; tie fallback rows
+    vs::DevBuf<int32_t> d_flags;  // [kMaxMulti * 32]
+    vs::DevBuf<float> d_scores;   // IVF query-major fallback: coarse scores [32][nlist_pad]
     vs::DevBuf<int32_t> d_probes; // [32][kMaxNprobe]
     vs::DevBuf<float> d_ipart_d;  // [32][kMaxNprobe][16]
     vs::DevBuf<int32_t> d_ipart_i;
@@ -178,8 +178,8 @@ struct vs_index {
     vs::DevBuf<int8_t> d_head_t8;       // byte-valued heads: 16-row tiles, every list padded to a multiple of 16 rows
     vs::DevBuf<int32_t> d_head_rterm_t;
     vs::DevBuf<int32_t> d_head_tdelta;  // [nlist] padded row - row
-    vs::DevBuf<int32_t> d_sh;           // sharded brute force, host-buffer calls: the gathered scratch of the owner (see ShBuf)
-    vs::DevBuf<float> d_sh_row;         // ... and full distance rows (tie fallback)
+    vs::DevBuf<int32_t> d_sh;           // host-buffer brute force (bf_search_shards): the owner's gathered scratch (see ShBuf)
+    vs::PinBuf<char> pin_sh;            // ... and the tie resolver's pinned downloads
     vs::DevBuf<int32_t> vsh_blk;        // virtual ranks (vs_ivf_search_dev_vshards): the gathered blocks / top-k lists, owned by shard 0
     vs::DevBuf<int32_t> vsh_loc;
     // wide IVF pipeline (a launch group of up to 32 batches shares one list-major pass): slot tables, zeroed counters,
@@ -216,14 +216,14 @@ struct vs_index {
     int max_grid = 0;
     unsigned one_calls = 0;            // single-call scans issued so far (they alternate the direction of their pass)
 
-    // host-buffer API (vs_bf_search / vs_ivf_search): two slots of pinned staging + device I/O buffers, so that chunk
+    // host-buffer API (bf_search_shards / vs_ivf_search): two slots of pinned staging + device I/O buffers, so that chunk
     // c + 1's query upload and chunk c - 1's result download run beside chunk c's kernels (copy streams + events)
     struct PipeSlot {
         vs::PinBuf<float> pin_q;   // [kMaxMulti * 32][128]
-        vs::PinBuf<char> pin_out;  // dists | ids | flags of one chunk
+        vs::PinBuf<char> pin_out;  // dists | ids | flags of one chunk (k1 <= kTopkWideMax)
         // device I/O: views of the index's d_q / d_out_* / d_flags (slot 0) or of the own_* buffers (slot 1)
         float* d_q = nullptr;
-        float* d_out_d = nullptr;  // [kMaxMulti * 32][64]
+        float* d_out_d = nullptr;  // [kMaxMulti * 32][kTopkWideMax]
         int32_t* d_out_i = nullptr;
         int32_t* d_flags = nullptr;
         vs::DevBuf<float> own_q, own_out_d;
@@ -244,20 +244,8 @@ struct vs_index {
         int64_t q0 = -1, n = 0;
         bool ready = false;        // every buffer and event above created (ensure_ivf_host)
     } ihs[2];
-    // tie resolver (flagged queries of vs_bf_search): distances to the first kTieDense rows, bound, filtered candidates
-    struct Tie {
-        vs::DevBuf<float> dense;  // [32][kTieDense]
-        vs::PinBuf<char> pin;     // pinned staging: dense [32][kTieDense] f32 | cnt [32] | rows [32][kTieCap] | dists [32][kTieCap]
-        vs::DevBuf<float> tau;    // [32]
-        vs::DevBuf<int32_t> cnt;  // [32]
-        vs::DevBuf<int32_t> row;  // [32][kTieCap]
-        vs::DevBuf<float> d;      // [32][kTieCap]
-        bool ready = false;       // every buffer above allocated
-        int64_t dense_cap = kTieDense;  // rows per query `dense` and `pin` hold (k >= 16 takes a longer prefix)
-    } tie;
     // wide-k brute force (k + 1 > 16, topw_launch), allocated on the first such call: distances to the prefix rows, the
-    // prefix's k1 best and bound, the filter's candidates, the dense fallback's chunk scores and per-chunk lists, and the
-    // host call's staging
+    // prefix's k1 best and bound, the filter's candidates, the dense fallback's chunk scores and per-chunk lists
     struct TopW {
         int64_t l0p = 0;              // prefix rows (padded) the buffers hold: topw_prefix(n_rows, kTopkWideMax)
         int64_t chunk = 0;            // rows per chunk of the dense fallback
@@ -272,10 +260,6 @@ struct vs_index {
         vs::DevBuf<float> full;       // [32][chunk]
         vs::DevBuf<float> ch_d;       // [32][n_chunks][kTopkWideMax]
         vs::DevBuf<int32_t> ch_i;
-        vs::PinBuf<float> pin_q;      // [kMaxMulti * 32][128]
-        vs::PinBuf<char> pin_out;     // dists | ids | flags of one chunk of queries
-        vs::DevBuf<float> d_q, out_d;
-        vs::DevBuf<int32_t> out_i, flags;
         bool ready = false;           // every buffer above allocated (ensure_topw)
     } topw;
 
@@ -372,8 +356,8 @@ int alloc_scratch(vs_index* h) {
         }
         if ((rc = h->fork.create())) return rc;
     }
-    if ((rc = h->d_out_d.alloc((size_t)kMaxMulti * 32 * 64))) return rc;
-    if ((rc = h->d_out_i.alloc((size_t)kMaxMulti * 32 * 64))) return rc;
+    if ((rc = h->d_out_d.alloc((size_t)kMaxMulti * 32 * vs::kTopkWideMax))) return rc;
+    if ((rc = h->d_out_i.alloc((size_t)kMaxMulti * 32 * vs::kTopkWideMax))) return rc;
     if ((rc = h->d_flags.alloc((size_t)kMaxMulti * 32))) return rc;
     if (h->kind == 1) {
         if ((rc = h->d_cand.alloc(1))) return rc;
@@ -830,7 +814,6 @@ int64_t topw_prefix(int64_t n_rows, int k1) {
 int ensure_topw(vs_index* h) {
     if (h->topw.ready) return VS_OK;
     vs_index::TopW w;
-    const size_t nqc = (size_t)kMaxMulti * 32;
     w.l0p = (topw_prefix(h->n_rows, vs::kTopkWideMax) + 15) & ~int64_t(15);
     w.chunk = std::min<int64_t>((h->n_rows + 15) & ~int64_t(15), kTopwChunkBytes / (32 * sizeof(float)));
     w.n_chunks = (int)((h->n_rows + w.chunk - 1) / w.chunk);
@@ -839,9 +822,7 @@ int ensure_topw(vs_index* h) {
     if ((rc = w.pre.alloc((size_t)32 * w.l0p)) || (rc = w.tau.alloc(32)) || (rc = w.pre_d.alloc(32 * kw)) || (rc = w.pre_i.alloc(32 * kw)) ||
         (rc = w.fz.alloc(64)) || (rc = w.f_row.alloc((size_t)32 * kTopwFilterCap)) || (rc = w.f_d.alloc((size_t)32 * kTopwFilterCap)) ||
         (rc = w.full.alloc((size_t)32 * w.chunk)) || (rc = w.ch_d.alloc((size_t)32 * w.n_chunks * kw)) ||
-        (rc = w.ch_i.alloc((size_t)32 * w.n_chunks * kw)) || (rc = w.pin_q.alloc(nqc * vs::kDim)) ||
-        (rc = w.pin_out.alloc(nqc * (2 * kw + 1) * sizeof(float))) || (rc = w.d_q.alloc(nqc * vs::kDim)) ||
-        (rc = w.out_d.alloc(nqc * kw)) || (rc = w.out_i.alloc(nqc * kw)) || (rc = w.flags.alloc(nqc)))
+        (rc = w.ch_i.alloc((size_t)32 * w.n_chunks * kw)))
         return rc;
     HIPCHK(hipMemset(w.fz, 0, 64 * sizeof(int32_t)));
     w.ready = true;
@@ -1459,8 +1440,9 @@ int ensure_pipe(vs_index* h) {
     int rc;
     for (int i = 0; i < 2; ++i) {
         vs_index::PipeSlot& S = P[i];
-        if ((rc = S.pin_q.alloc(nqc * vs::kDim)) || (rc = S.pin_out.alloc(nqc * (64 * 2 + 1) * sizeof(float)))) return rc;
-        if (i == 1 && ((rc = S.own_q.alloc(nqc * vs::kDim)) || (rc = S.own_out_d.alloc(nqc * 64)) || (rc = S.own_out_i.alloc(nqc * 64)) ||
+        if ((rc = S.pin_q.alloc(nqc * vs::kDim)) || (rc = S.pin_out.alloc(nqc * (2 * vs::kTopkWideMax + 1) * sizeof(float)))) return rc;
+        if (i == 1 && ((rc = S.own_q.alloc(nqc * vs::kDim)) || (rc = S.own_out_d.alloc(nqc * vs::kTopkWideMax)) ||
+                       (rc = S.own_out_i.alloc(nqc * vs::kTopkWideMax)) ||
                        (rc = S.own_flags.alloc(nqc))))
             return rc;
         if ((rc = S.ev_h2d.create()) || (rc = S.ev_comp.create()) || (rc = S.ev_d2h.create())) return rc;
@@ -1478,177 +1460,6 @@ int ensure_pipe(vs_index* h) {
     h->s_h2d = std::move(h2d);
     h->s_d2h = std::move(d2h);
     h->pipe_ready = true;
-    return VS_OK;
-}
-
-// Full-row fallback of the tie resolver: the whole distance row of one query (already in h->d_q at row `b`) -> host replay.
-int resolve_dense_full(vs_index* h, const float* q_dev, int B, const std::vector<int>& which, const int64_t* qidx, int k,
-                       int32_t* ids, float* dists) {
-    const int64_t ld = (h->n_rows + 15) & ~int64_t(15);
-    int rc;
-    if (h->d_scores.size() < (size_t)B * ld && (rc = h->d_scores.alloc((size_t)32 * ld))) return rc;
-    rc = scores_dev(h, h->d_vecs, h->d_norm, h->n_rows, q_dev, B, h->d_scores, ld, h->stream);
-    if (rc) return rc;
-    std::vector<float> row((size_t)ld);
-    for (int b : which) {
-        HIPCHK(hipMemcpyAsync(row.data(), h->d_scores + (size_t)b * ld, (size_t)h->n_rows * sizeof(float), hipMemcpyDeviceToHost,
-                              h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        vs::select_topk_slots_dense(row.data(), h->n_rows, k, (int32_t)h->id_offset, ids + qidx[b] * k, dists + qidx[b] * k);
-    }
-    return VS_OK;
-}
-
-// Exact select_topk (cpu_baseline.cpp:127-153) for queries whose k+1 best distances contain a tie.  The slot replay
-// only depends on rows that change the k-slot buffer, i.e. rows whose distance is below the buffer maximum when they
-// arrive -- and that maximum never rises.  So: the first kTieDense rows are taken densely (their distance rows), the
-// k-th smallest of them bounds the buffer maximum for every later row, and ONE filtered pass over the rest of the base
-// emits the few rows under that bound (about N * k / kTieDense of them).  The host replays the slots over
-// "dense rows, then candidates in row order".  Exact whenever the distances are (integer-valued SIFT: always).
-int resolve_ties(vs_index* h, const float* queries_host, const std::vector<int64_t>& flagged, int k, int32_t* ids, float* dists) {
-    int rc;
-    // k >= 16: a prefix that grows with k (512 k rows, a multiple of 4096), so that about n_rows / 512 rows pass the bound
-    // whatever k is (the k <= 15 prefix of kTieDense rows would let n_rows * k / 4096 through, past kTieCap at 1 M rows)
-    const int64_t dense_rows = k <= 15 ? kTieDense : ((int64_t)512 * k + 4095) & ~int64_t(4095);
-    const int64_t L0 = std::min<int64_t>(h->n_rows, dense_rows);
-    const int64_t L0p = (L0 + 15) & ~int64_t(15);
-    if (!h->tie.ready || h->tie.dense_cap < dense_rows) {
-        vs_index::Tie t;
-        t.dense_cap = std::max<int64_t>(dense_rows, h->tie.ready ? h->tie.dense_cap : kTieDense);
-        if ((rc = t.dense.alloc((size_t)32 * t.dense_cap)) || (rc = t.tau.alloc(32)) || (rc = t.cnt.alloc(32)) || (rc = t.row.alloc((size_t)32 * kTieCap)) ||
-            (rc = t.d.alloc((size_t)32 * kTieCap)) || (rc = t.pin.alloc((size_t)32 * t.dense_cap * 4 + 128 + (size_t)2 * 32 * kTieCap * 4)))
-            return rc;
-        t.ready = true;
-        h->tie = std::move(t);
-    }
-    const int group = 32;
-    // downloads land in pinned memory (pageable destinations are staged by the runtime: several times slower)
-    float* const dense = reinterpret_cast<float*>(h->tie.pin.get());
-    int32_t* const cnt = reinterpret_cast<int32_t*>(h->tie.pin + (size_t)32 * h->tie.dense_cap * 4);
-    int32_t* const cr = cnt + 32;
-    float* const cd = reinterpret_cast<float*>(cr + (size_t)32 * kTieCap);
-    std::vector<float> qbuf((size_t)group * vs::kDim);
-    for (size_t f0 = 0; f0 < flagged.size(); f0 += group) {
-        const int B = (int)std::min<size_t>(group, flagged.size() - f0);
-        for (int b = 0; b < B; ++b)
-            std::memcpy(&qbuf[(size_t)b * vs::kDim], queries_host + flagged[f0 + b] * vs::kDim, vs::kDim * sizeof(float));
-        HIPCHK(hipMemcpyAsync(h->d_q, qbuf.data(), (size_t)B * vs::kDim * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        if ((rc = scores_dev(h, h->d_vecs, h->d_norm, L0, h->d_q, B, h->tie.dense, L0p, h->stream))) return rc;
-        const bool sparse = h->n_rows > L0;
-        if (sparse) {
-            // bound = next_up(k-th smallest of the dense rows): merge kernel over G = L0 one-entry lists
-            HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->tie.tau.get()), 0xff800000u, 32, h->stream));  // -inf: padding queries emit nothing
-            HIPCHK(hipMemsetAsync(h->tie.cnt, 0, 32 * sizeof(int32_t), h->stream));
-            if (k <= 15) {
-                vs::MergeParams m{};
-                m.part_d = h->tie.dense;
-                m.G = (int)L0;
-                m.kin = 1;
-                m.nq = B;
-                m.kout = k;
-                m.tau_out = h->tie.tau;
-                HIPCHK(vs::launch_merge_layout(m, 1, L0p, h->stream));
-            } else {  // (vs_bf_search_topk: the wide-k scratch exists)
-                vs::TopkWideParams t{};
-                t.dense = h->tie.dense;
-                t.dense_ld = L0p;
-                t.n_dense = L0;
-                t.nq = B;
-                t.k1 = k;
-                t.out_d = h->topw.pre_d;
-                t.out_i = h->topw.pre_i;
-                t.out_ld = vs::kTopkWideMax;
-                t.tau_out = h->tie.tau;
-                HIPCHK(vs::launch_topk_wide(t, 32, h->stream));
-            }
-            vs::ScanParams p{};
-            p.base = h->d_vecs;
-            p.bnorm = h->d_norm;
-            p.q = h->d_q;
-            p.n_batches = 1;
-            p.metric = h->metric;
-            p.nq_valid = B;
-            p.k1 = k + 1;
-            p.tau0 = h->tie.tau;
-            p.row_begin = L0;  // multiple of 16 (kTieDense, 4096)
-            p.row_end = h->n_rows;
-            p.f_cnt = h->tie.cnt;
-            p.f_row = h->tie.row;
-            p.f_d = h->tie.d;
-            p.f_cap = kTieCap;
-            int grid, tp;
-            scan_geometry(h->n_rows - L0, h->num_cus, grid, tp);
-            p.tiles_per_wg = tp;
-            HIPCHK(vs::launch_scan(p, grid, 8, 2, vs::kModeFilter, h->stream));
-            HIPCHK(hipMemcpyAsync(cnt, h->tie.cnt, 32 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        }
-        HIPCHK(hipMemcpyAsync(dense, h->tie.dense, (size_t)B * L0p * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        int mx = 0;
-        std::vector<int> overflow;
-        if (sparse) {
-            for (int b = 0; b < B; ++b) {
-                if (cnt[b] > kTieCap) overflow.push_back(b);
-                else mx = std::max(mx, cnt[b]);
-            }
-            if (mx > 0) {
-                HIPCHK(hipMemcpy2DAsync(cr, (size_t)mx * 4, h->tie.row, (size_t)kTieCap * 4, (size_t)mx * 4, B,
-                                        hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(hipMemcpy2DAsync(cd, (size_t)mx * 4, h->tie.d, (size_t)kTieCap * 4, (size_t)mx * 4, B,
-                                        hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(hipStreamSynchronize(h->stream));
-            }
-        }
-        // the flagged queries are independent: their replays run on a few host threads (a replay walks ~5000 entries)
-        auto replay = [&](int b_begin, int b_end) {
-            std::vector<int32_t> srow, order;
-            std::vector<float> sdist;
-            for (int b = b_begin; b < b_end; ++b) {
-                const int m = sparse ? cnt[b] : 0;
-                if (m > kTieCap) continue;  // full-row fallback below
-                srow.resize((size_t)L0 + m);
-                sdist.resize((size_t)L0 + m);
-                for (int64_t j = 0; j < L0; ++j) {
-                    srow[(size_t)j] = (int32_t)(j + h->id_offset);
-                    sdist[(size_t)j] = dense[(size_t)b * L0p + j];
-                }
-                order.resize((size_t)m);
-                std::iota(order.begin(), order.end(), 0);
-                const int32_t* rr = m ? &cr[(size_t)b * mx] : nullptr;
-                const float* dd = m ? &cd[(size_t)b * mx] : nullptr;
-                std::sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return rr[x] < rr[y]; });
-                for (int j = 0; j < m; ++j) {
-                    srow[(size_t)L0 + j] = rr[order[(size_t)j]] + (int32_t)h->id_offset;
-                    sdist[(size_t)L0 + j] = dd[order[(size_t)j]];
-                }
-                const int64_t qi = flagged[f0 + b];
-                vs::select_topk_slots_sparse(srow.data(), sdist.data(), (int64_t)srow.size(), k, ids + qi * k, dists + qi * k);
-            }
-        };
-        const int n_thr = std::min(4, B / 4);
-        if (n_thr <= 1) {
-            replay(0, B);
-        } else {
-            std::vector<std::thread> pool;
-            std::atomic<bool> failed{false};
-            for (int t = 0; t < n_thr; ++t)
-                pool.emplace_back([&, t]() {
-                    try {
-                        replay(B * t / n_thr, B * (t + 1) / n_thr);
-                    } catch (...) {
-                        failed = true;
-                    }
-                });
-            for (auto& th : pool) th.join();
-            if (failed) {
-                set_error("out of host memory");
-                return VS_ERR_NOMEM;
-            }
-        }
-        if (!overflow.empty()) {  // massive ties / duplicates: more rows under the bound than the candidate buffer holds
-            if ((rc = resolve_dense_full(h, h->d_q, B, overflow, &flagged[f0], k, ids, dists))) return rc;
-        }
-    }
     return VS_OK;
 }
 
@@ -1859,197 +1670,6 @@ int vs_bf_scores_dev(vs_index* h, const float* queries_dev, int B, float* scores
     if ((rc = order_begin(h, st))) return rc;
     rc = scores_dev(h, h->d_vecs, h->d_norm, h->n_rows, queries_dev, B, scores_dev_, ld, st);
     return rc ? rc : order_end(h, st);
-}
-
-int vs_bf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int32_t* ids, float* dists,
-                 vs_timing* timing) {
-    if (!h || h->kind != 0 || !queries_host || !ids || !dists || nq < 0 || k < 1) {
-        set_error("vs_bf_search: bad arguments");
-        return VS_ERR_INVALID;
-    }
-    return guarded([&]() -> int {
-        int rc = set_device(h);
-        if (rc) return rc;
-        const double t_start = now_ms();
-        vs_timing tm{};
-        const int k1 = k + 1;
-        if (!pick_kcap(k1)) {
-            set_error("k too large for the compiled scan kernels (k <= 15)");
-            return VS_ERR_UNSUPPORTED;
-        }
-        if ((rc = ensure_pipe(h)) || (rc = order_begin(h, h->stream))) return rc;
-        settle_slots(h->pipe, {h->stream, h->s_h2d, h->s_d2h});
-        // Queries go through in chunks of kMaxMulti batches: one persistent scan launch + one merge launch per chunk
-        // (the harness loop of main.cpp:201-251 collapsed into a call; a ragged tail batch gets its own launch).  Two
-        // chunks are in flight: uploads and downloads run on copy streams beside the other chunk's kernels.
-        const int64_t chunk = (int64_t)kMaxMulti * h->batch;
-        std::vector<int64_t> flagged;
-        const float inf = std::numeric_limits<float>::infinity();
-        auto launch_chunk = [&](vs_index::PipeSlot& S, bool force_f32) -> int {
-            const int full = (int)(S.n / h->batch), rem = (int)(S.n % h->batch);
-            int r2 = VS_OK;
-            if (full) r2 = bf_launch(h, h->lane[0], S.d_q, full, h->batch, k1, S.d_out_d, S.d_out_i, S.d_flags, h->stream, force_f32);
-            if (!r2 && rem) {
-                const size_t o = (size_t)full * h->batch;
-                r2 = bf_launch(h, h->lane[0], S.d_q + o * vs::kDim, 1, rem, k1, S.d_out_d + o * k1, S.d_out_i + o * k1, S.d_flags + o,
-                               h->stream, force_f32);
-            }
-            return r2;
-        };
-        auto download = [&](vs_index::PipeSlot& S, hipStream_t st) -> int {
-            float* hd = reinterpret_cast<float*>(S.pin_out.get());
-            int32_t* hi = reinterpret_cast<int32_t*>(S.pin_out.get()) + (size_t)chunk * k1;
-            int32_t* hf = hi + (size_t)chunk * k1;
-            HIPCHK(hipMemcpyAsync(hd, S.d_out_d, (size_t)S.n * k1 * sizeof(float), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(hi, S.d_out_i, (size_t)S.n * k1 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(hf, S.d_flags, (size_t)S.n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            return VS_OK;
-        };
-        auto enqueue = [&](vs_index::PipeSlot& S, int64_t q0, int64_t n) -> int {
-            const double t0 = now_ms();
-            S.q0 = q0;
-            S.n = n;
-            std::memcpy(S.pin_q, queries_host + q0 * vs::kDim, (size_t)n * vs::kDim * sizeof(float));
-            HIPCHK(hipMemcpyAsync(S.d_q, S.pin_q, (size_t)n * vs::kDim * sizeof(float), hipMemcpyHostToDevice, h->s_h2d));
-            HIPCHK(hipEventRecord(S.ev_h2d, h->s_h2d));
-            tm.h2d_ms += now_ms() - t0;
-            HIPCHK(hipStreamWaitEvent(h->stream, S.ev_h2d, 0));
-            int r2 = launch_chunk(S, false);
-            if (r2) return r2;
-            HIPCHK(hipEventRecord(S.ev_comp, h->stream));
-            HIPCHK(hipStreamWaitEvent(h->s_d2h, S.ev_comp, 0));
-            if ((r2 = download(S, h->s_d2h))) return r2;
-            HIPCHK(hipEventRecord(S.ev_d2h, h->s_d2h));
-            return VS_OK;
-        };
-        auto retire = [&](vs_index::PipeSlot& S) -> int {
-            if (S.q0 < 0) return VS_OK;
-            const double t0 = now_ms();
-            HIPCHK(hipEventSynchronize(S.ev_d2h));
-            const float* hd = reinterpret_cast<const float*>(S.pin_out.get());
-            const int32_t* hi = reinterpret_cast<const int32_t*>(S.pin_out.get()) + (size_t)chunk * k1;
-            const int32_t* hf = hi + (size_t)chunk * k1;
-            bool rerun = false;
-            for (int64_t b = 0; b < S.n; ++b) rerun = rerun || hf[(size_t)b] == 2;
-            if (rerun) {
-                // a query of this chunk is not an integer in [0, 255]: the int8 scan skipped its batch -> fp32 path
-                int r2 = launch_chunk(S, true);
-                if (r2) return r2;
-                if ((r2 = download(S, h->stream))) return r2;
-                HIPCHK(hipStreamSynchronize(h->stream));
-            }
-            tm.d2h_ms += now_ms() - t0;
-            for (int64_t b = 0; b < S.n; ++b) {
-                for (int t = 0; t < k; ++t) {
-                    const int32_t id = hi[(size_t)b * k1 + t];
-                    ids[(S.q0 + b) * k + t] = id;
-                    float d = id >= 0 ? hd[(size_t)b * k1 + t] : inf;
-                    if (h->metric == VS_METRIC_IP && id >= 0) d = -d;
-                    dists[(S.q0 + b) * k + t] = d;
-                }
-                if (hf[(size_t)b]) flagged.push_back(S.q0 + b);
-            }
-            S.q0 = -1;
-            return VS_OK;
-        };
-        int c = 0;
-        for (int64_t q0 = 0; q0 < nq; q0 += chunk, ++c) {
-            vs_index::PipeSlot& S = h->pipe[c & 1];
-            if ((rc = retire(S))) return rc;
-            if ((rc = enqueue(S, q0, std::min<int64_t>(chunk, nq - q0)))) return rc;
-        }
-        if ((rc = retire(h->pipe[c & 1]))) return rc;        // the older chunk first
-        if ((rc = retire(h->pipe[(c + 1) & 1]))) return rc;
-        tm.fine_search_ms = now_ms() - t_start;
-        // Ties inside the k+1 best: the reference's order is history dependent (cpu_baseline.cpp:127-153) -> replay
-        // select_topk over the rows that can change its buffer (resolve_ties).
-        if (!flagged.empty() && h->metric == VS_METRIC_L2) {
-            const double t0 = now_ms();
-            if ((rc = resolve_ties(h, queries_host, flagged, k, ids, dists))) return rc;
-            tm.tie_resolve_ms = now_ms() - t0;
-            tm.tie_queries = (int64_t)flagged.size();
-        }
-        tm.total_ms = now_ms() - t_start;
-        if (timing) *timing = tm;
-        return order_end(h, h->stream);
-    });
-}
-
-int vs_bf_search_topk(vs_index* h, const float* queries_host, int64_t nq, int k, int32_t* ids, float* dists, vs_timing* timing) {
-    if (!h || h->kind != 0 || !queries_host || !ids || !dists || nq < 0 || k < 1) {
-        set_error("vs_bf_search_topk: bad arguments");
-        return VS_ERR_INVALID;
-    }
-    if (k > vs::kTopkWideMax - 1) {
-        set_error("vs_bf_search_topk: k > 128");
-        return VS_ERR_UNSUPPORTED;
-    }
-    if (k + 1 <= kKcapMax) return vs_bf_search(h, queries_host, nq, k, ids, dists, timing);
-    return guarded([&]() -> int {
-        int rc = set_device(h);
-        if (rc) return rc;
-        const double t_start = now_ms();
-        vs_timing tm{};
-        const int k1 = k + 1;
-        if (g_topw_stats) g_topw_st = TopwStats{};
-        if ((rc = ensure_topw(h)) || (rc = order_begin(h, h->stream))) return rc;
-        settle_slots(h->pipe, {h->stream, h->s_h2d, h->s_d2h});
-        vs_index::TopW& W = h->topw;
-        const int64_t chunk = (int64_t)kMaxMulti * h->batch;
-        float* const hd = reinterpret_cast<float*>(W.pin_out.get());
-        int32_t* const hi = reinterpret_cast<int32_t*>(hd + (size_t)chunk * k1);
-        int32_t* const hf = hi + (size_t)chunk * k1;
-        std::vector<int64_t> flagged;
-        const float inf = std::numeric_limits<float>::infinity();
-        // chunks of kMaxMulti batches, one after the other: upload, the wide-k launches (full batches, then a ragged tail
-        // batch), download
-        for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
-            const int64_t n = std::min<int64_t>(chunk, nq - q0);
-            const double t0 = now_ms();
-            std::memcpy(W.pin_q, queries_host + q0 * vs::kDim, (size_t)n * vs::kDim * sizeof(float));
-            HIPCHK(hipMemcpyAsync(W.d_q, W.pin_q, (size_t)n * vs::kDim * sizeof(float), hipMemcpyHostToDevice, h->stream));
-            tm.h2d_ms += now_ms() - t0;
-            const int full = (int)(n / h->batch), rem = (int)(n % h->batch);
-            if (full && (rc = topw_launch(h, W.d_q, full, h->batch, k1, W.out_d, W.out_i, W.flags, h->stream))) return rc;
-            if (rem) {
-                const size_t o = (size_t)full * h->batch;
-                if ((rc = topw_launch(h, W.d_q + o * vs::kDim, 1, rem, k1, W.out_d + o * k1, W.out_i + o * k1, W.flags + o, h->stream)))
-                    return rc;
-            }
-            const double t1 = now_ms();
-            HIPCHK(hipMemcpyAsync(hd, W.out_d, (size_t)n * k1 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipMemcpyAsync(hi, W.out_i, (size_t)n * k1 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipMemcpyAsync(hf, W.flags, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            tm.d2h_ms += now_ms() - t1;
-            for (int64_t b = 0; b < n; ++b) {
-                for (int t = 0; t < k; ++t) {
-                    const int32_t id = hi[(size_t)b * k1 + t];
-                    ids[(q0 + b) * k + t] = id;
-                    float d = id >= 0 ? hd[(size_t)b * k1 + t] : inf;
-                    if (h->metric == VS_METRIC_IP && id >= 0) d = -d;
-                    dists[(q0 + b) * k + t] = d;
-                }
-                if (hf[(size_t)b]) flagged.push_back(q0 + b);
-            }
-        }
-        tm.fine_search_ms = now_ms() - t_start;
-        // equal distances among the k + 1 best: select_topk's slots over the rows that can change them (resolve_ties)
-        if (!flagged.empty() && h->metric == VS_METRIC_L2) {
-            const double t0 = now_ms();
-            if ((rc = resolve_ties(h, queries_host, flagged, k, ids, dists))) return rc;
-            tm.tie_resolve_ms = now_ms() - t0;
-            tm.tie_queries = (int64_t)flagged.size();
-        }
-        tm.total_ms = now_ms() - t_start;
-        if (timing) *timing = tm;
-        if (g_topw_stats)
-            fprintf(stderr, "topw_stats k=%d batches=%lld overflowed=%lld queries=%lld cand_mean=%.1f cand_max=%lld flagged=%lld\n", k,
-                    (long long)g_topw_st.batches, (long long)g_topw_st.overflowed, (long long)g_topw_st.queries,
-                    g_topw_st.queries ? (double)g_topw_st.cand_sum / g_topw_st.queries : 0.0, (long long)g_topw_st.cand_max,
-                    (long long)flagged.size());
-        return order_end(h, h->stream);
-    });
 }
 
 int vs_bf_search_topk_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k, int32_t* ids_dev,
@@ -3291,15 +2911,17 @@ int vs_ivf_search_dev_vshards(vs_index* const* shards, int G, const float* queri
 
 namespace {
 
-// ---- brute force over row shards, host buffers in, the reference's answer out (cpu_baseline.cpp:127-153 tie order included).
+// ---- brute force on host buffers, the reference's answer out (cpu_baseline.cpp:127-153 tie order included), over row shards.
 // The shards this process drives are either ONE shard of a collective job (comm: the other ranks run the same code, the
 // exchanges are RCCL all-gathers) or ALL G shards on one device (virtual ranks: an exchange is a no-op, every shard has
 // written its part of the gathered buffer in place).  Everything else -- per-shard device steps, merge, host replay -- is
 // the same code.  Shards are contiguous row ranges in rank order (vs_bf_create(rows of the shard, id_offset = first row)).
+// vs_bf_search / vs_bf_search_topk are one index (G = 1, no communicator) without the merge.
 struct BfShards {
     std::vector<vs_index*> hs;  // the shards driven here; hs[i] is global shard first + i
     int G = 1, first = 0;
     vs_comm* c = nullptr;
+    bool merge = true;          // the shards' lists go through the exchange and the merge (every sharded call, G = 1 included)
     vs_index* owner() const { return hs[0]; }
     hipStream_t s() const { return hs[0]->stream; }
     int exchange(int32_t* buf, size_t words) const {  // buf = [G][words], this process's parts in place
@@ -3311,66 +2933,101 @@ struct BfShards {
 
 constexpr size_t kShPackWords = 32 + (size_t)2 * 32 * kTieCap;  // filter output of one shard: cnt [32] | rows [32][kTieCap] | dists [32][kTieCap]
 
-// gathered scratch of the owner: main [G][main] | tau [G][32] | dense [G][32 * kTieDense] | pack [G][kShPackWords] | meta [G][2]
+// gathered scratch of the owner, [G] parts per region: meta [G][2] (rows, id_offset) | lists [G][lists_words] (sharded calls:
+// each shard's dists | ids | flags of one launch step) | the tie resolver's tau [G][32] | dense [G][32 * L0p] |
+// pack [G][kShPackWords] | row [G][ldm] (one query's full distance row).  The search reserves meta and lists, the resolver
+// meta and its own regions (L0p > 0); nothing in the buffer outlives either.
 struct ShBuf {
-    int32_t *main, *tau, *dense, *pack, *meta;
-    size_t main_words;
+    int32_t *meta, *lists, *tau, *dense, *pack, *row;
 };
-int sh_reserve(vs_index* o, int G, int k1, ShBuf& B) {
-    const size_t main_words = (size_t)(2 * k1 + 1) * kMaxMulti * 32;
-    const size_t total = (size_t)G * (main_words + 32 + (size_t)32 * kTieDense + kShPackWords + 2);
+int sh_reserve(vs_index* o, int G, size_t lists_words, int64_t L0p, int64_t ldm, ShBuf& B) {
+    const size_t tie = L0p ? 32 + (size_t)32 * L0p + kShPackWords + (size_t)ldm : 0;
+    const size_t total = (size_t)G * (2 + lists_words + tie);
     if (o->d_sh.size() < total) HIPCHK(hipDeviceSynchronize());
     if (int rc = o->d_sh.reserve(total)) return rc;
-    B.main_words = main_words;
-    B.main = o->d_sh;
-    B.tau = B.main + (size_t)G * main_words;
+    B.meta = o->d_sh;
+    B.lists = B.meta + (size_t)G * 2;
+    B.tau = B.lists + (size_t)G * lists_words;
     B.dense = B.tau + (size_t)G * 32;
-    B.pack = B.dense + (size_t)G * 32 * kTieDense;
-    B.meta = B.pack + (size_t)G * kShPackWords;
+    B.pack = B.dense + (size_t)G * 32 * L0p;
+    B.row = B.pack + (size_t)G * kShPackWords;
     return VS_OK;
 }
 
-// exact select_topk for the flagged queries of a sharded search (see resolve_ties for the single-shard form and why a
-// row-ordered superset of the rows that change the slot buffer suffices): the dense prefix is shard 0's first rows, its
-// k-th smallest distance bounds the buffer maximum for every later row of every shard, each shard filters its rows under
-// that bound, and the host replays "dense rows, then the shards' candidates in row order".
-int resolve_ties_shards(const BfShards& S, const ShBuf& Bf, const std::vector<int32_t>& meta /*[G][2] rows, id_offset*/,
-                        const float* queries_host, const std::vector<int64_t>& flagged, int k, int32_t* ids, float* dists) {
+// Exact select_topk (cpu_baseline.cpp:127-153) for the queries whose k+1 best distances contain a tie.  The slot replay
+// only depends on rows that change the k-slot buffer, i.e. rows whose distance is below the buffer maximum when they
+// arrive -- and that maximum never rises.  So: the first L0 rows of shard 0 are taken densely (their distance rows), the
+// k-th smallest of them bounds the buffer maximum for every later row of every shard, each shard emits its rows under that
+// bound in ONE filtered pass (about N * k / L0 of them), and the host replays "dense rows, then the shards' candidates in row
+// order".  Exact whenever the distances are (integer-valued SIFT: always).
+int resolve_ties_shards(const BfShards& S, const std::vector<int32_t>& meta /*[G][2] rows, id_offset*/, const float* queries_host,
+                        const std::vector<int64_t>& flagged, int k, int32_t* ids, float* dists) {
     vs_index* o = S.owner();
     hipStream_t st = S.s();
     const int G = S.G;
-    const int64_t L0 = std::min<int64_t>(meta[0], kTieDense);
-    const int64_t L0p = (L0 + 15) & ~int64_t(15);
     for (int g = 1; g < G; ++g)
         if ((int64_t)meta[2 * g + 1] != (int64_t)meta[2 * (g - 1) + 1] + meta[2 * (g - 1)]) {
             set_error("sharded tie order needs shards that are contiguous row ranges in rank order");
             return VS_ERR_UNSUPPORTED;
         }
-    std::vector<float> qbuf((size_t)32 * vs::kDim), dense((size_t)32 * L0p);
-    std::vector<int32_t> cnt((size_t)G * 32), rows;
-    std::vector<float> cds;
+    // k >= 16 (one index: the sharded calls take k <= 15): a prefix that grows with k (512 k rows, a multiple of 4096), so
+    // that about n_rows / 512 rows pass the bound whatever k is (the k <= 15 prefix of kTieDense rows would let
+    // n_rows * k / 4096 through, past kTieCap at 1 M rows)
+    const int64_t L0 = std::min<int64_t>(meta[0], k <= 15 ? kTieDense : ((int64_t)512 * k + 4095) & ~int64_t(4095));
+    const int64_t L0p = (L0 + 15) & ~int64_t(15);
+    int64_t ldm = 0, total = 0;
+    for (int g = 0; g < G; ++g) {
+        ldm = std::max<int64_t>(ldm, ((int64_t)meta[2 * g] + 15) & ~int64_t(15));
+        total += meta[2 * g];
+    }
+    ShBuf Bf{};
     int rc;
+    if ((rc = sh_reserve(o, G, 0, L0p, ldm, Bf))) return rc;
+    // downloads land in pinned memory (pageable destinations are staged by the runtime: several times slower):
+    // dense [32][L0p] f32 | cnt [G][32] | rows [G][32][mx] | dists [G][32][mx], mx <= kTieCap
+    if ((rc = o->pin_sh.reserve(((size_t)32 * L0p + (size_t)G * 32 * (1 + 2 * (size_t)kTieCap)) * sizeof(float)))) return rc;
+    float* const dense = reinterpret_cast<float*>(o->pin_sh.get());
+    int32_t* const cnt = reinterpret_cast<int32_t*>(dense + (size_t)32 * L0p);
+    int32_t* const cr = cnt + (size_t)G * 32;
+    float* const cd = reinterpret_cast<float*>(cr + (size_t)G * 32 * kTieCap);
+    float* const tau0 = reinterpret_cast<float*>(Bf.tau);      // shard 0's part: the bound every shard filters with
+    float* const dense0 = reinterpret_cast<float*>(Bf.dense);  // shard 0's part: [B][L0p]
+    std::vector<float> qbuf((size_t)32 * vs::kDim), row;
     for (size_t f0 = 0; f0 < flagged.size(); f0 += 32) {
         const int B = (int)std::min<size_t>(32, flagged.size() - f0);
         for (int b = 0; b < B; ++b)
             std::memcpy(&qbuf[(size_t)b * vs::kDim], queries_host + flagged[f0 + b] * vs::kDim, vs::kDim * sizeof(float));
         HIPCHK(hipMemcpyAsync(o->d_q, qbuf.data(), (size_t)B * vs::kDim * sizeof(float), hipMemcpyHostToDevice, st));
-        float* tau0 = reinterpret_cast<float*>(Bf.tau);        // shard 0's part: the bound every shard filters with
-        float* dense0 = reinterpret_cast<float*>(Bf.dense);    // shard 0's part: [B][L0p]
         if (S.first == 0) {
             vs_index* h0 = S.hs[0];
             if ((rc = scores_dev(h0, h0->d_vecs, h0->d_norm, L0, o->d_q, B, dense0, L0p, st))) return rc;
-            HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(tau0), 0xff800000u, 32, st));  // -inf: padding queries emit nothing
-            vs::MergeParams m{};
-            m.part_d = dense0;
-            m.G = (int)L0;
-            m.kin = 1;
-            m.nq = B;
-            m.kout = k;
-            m.tau_out = tau0;
-            HIPCHK(vs::launch_merge_layout(m, 1, L0p, st));
+            if (total > L0) {  // rows follow the prefix: bound = next_up(k-th smallest of the dense rows)
+                HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(tau0), 0xff800000u, 32, st));  // -inf: padding queries emit nothing
+                if (k <= 15) {  // merge kernel over G = L0 one-entry lists
+                    vs::MergeParams m{};
+                    m.part_d = dense0;
+                    m.G = (int)L0;
+                    m.kin = 1;
+                    m.nq = B;
+                    m.kout = k;
+                    m.tau_out = tau0;
+                    HIPCHK(vs::launch_merge_layout(m, 1, L0p, st));
+                } else {  // (vs_bf_search_topk: the wide-k scratch exists)
+                    vs::TopkWideParams t{};
+                    t.dense = dense0;
+                    t.dense_ld = L0p;
+                    t.n_dense = L0;
+                    t.nq = B;
+                    t.k1 = k;
+                    t.out_d = h0->topw.pre_d;
+                    t.out_i = h0->topw.pre_i;
+                    t.out_ld = vs::kTopkWideMax;
+                    t.tau_out = tau0;
+                    HIPCHK(vs::launch_topk_wide(t, 32, st));
+                }
+            }
         }
-        if ((rc = S.exchange(Bf.tau, 32)) || (rc = S.exchange(Bf.dense, (size_t)32 * kTieDense))) return rc;
+        if ((rc = S.exchange(Bf.tau, 32)) || (rc = S.exchange(Bf.dense, (size_t)32 * L0p))) return rc;
         for (size_t i = 0; i < S.hs.size(); ++i) {
             vs_index* h = S.hs[i];
             const int g = S.first + (int)i;
@@ -3387,7 +3044,7 @@ int resolve_ties_shards(const BfShards& S, const ShBuf& Bf, const std::vector<in
             p.nq_valid = B;
             p.k1 = k + 1;
             p.tau0 = tau0;
-            p.row_begin = rb;  // a multiple of 16 (kTieDense) where rows follow
+            p.row_begin = rb;  // a multiple of 16 (kTieDense, 4096) where rows follow
             p.row_end = h->n_rows;
             p.f_cnt = pk;
             p.f_row = pk + 32;
@@ -3399,11 +3056,11 @@ int resolve_ties_shards(const BfShards& S, const ShBuf& Bf, const std::vector<in
             HIPCHK(vs::launch_scan(p, grid, 8, 2, vs::kModeFilter, st));
         }
         if ((rc = S.exchange(Bf.pack, kShPackWords))) return rc;
-        HIPCHK(hipMemcpyAsync(dense.data(), dense0, (size_t)B * L0p * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpy2DAsync(cnt.data(), 32 * 4, Bf.pack, kShPackWords * 4, 32 * 4, G, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(dense, dense0, (size_t)B * L0p * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpy2DAsync(cnt, 32 * 4, Bf.pack, kShPackWords * 4, 32 * 4, G, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         int mx = 0;
-        std::vector<int> overflow;
+        std::vector<int> overflow;  // more than kTieCap candidates on a shard: the full-row fallback below
         for (int b = 0; b < B; ++b) {
             bool ov = false;
             for (int g = 0; g < G; ++g) {
@@ -3413,61 +3070,81 @@ int resolve_ties_shards(const BfShards& S, const ShBuf& Bf, const std::vector<in
             }
             if (ov) overflow.push_back(b);
         }
-        rows.assign((size_t)G * 32 * std::max(mx, 1), 0);
-        cds.assign((size_t)G * 32 * std::max(mx, 1), 0.f);
         if (mx > 0) {
             for (int g = 0; g < G; ++g) {
                 const int32_t* pk = Bf.pack + (size_t)g * kShPackWords;
-                HIPCHK(hipMemcpy2DAsync(&rows[(size_t)g * 32 * mx], (size_t)mx * 4, pk + 32, (size_t)kTieCap * 4, (size_t)mx * 4, B, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipMemcpy2DAsync(&cds[(size_t)g * 32 * mx], (size_t)mx * 4, pk + 32 + (size_t)32 * kTieCap, (size_t)kTieCap * 4, (size_t)mx * 4, B,
+                HIPCHK(hipMemcpy2DAsync(cr + (size_t)g * 32 * mx, (size_t)mx * 4, pk + 32, (size_t)kTieCap * 4, (size_t)mx * 4, B,
                                         hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpy2DAsync(cd + (size_t)g * 32 * mx, (size_t)mx * 4, pk + 32 + (size_t)32 * kTieCap, (size_t)kTieCap * 4,
+                                        (size_t)mx * 4, B, hipMemcpyDeviceToHost, st));
             }
             HIPCHK(hipStreamSynchronize(st));
         }
-        std::vector<int32_t> srow, order;
-        std::vector<float> sdist;
-        for (int b = 0; b < B; ++b) {
-            if (std::find(overflow.begin(), overflow.end(), b) != overflow.end()) continue;
-            srow.clear();
-            sdist.clear();
-            for (int64_t j = 0; j < L0; ++j) {
-                srow.push_back((int32_t)(j + meta[1]));
-                sdist.push_back(dense[(size_t)b * L0p + j]);
-            }
-            for (int g = 0; g < G; ++g) {
-                const int m = cnt[(size_t)g * 32 + b];
-                const int32_t* rr = &rows[((size_t)g * 32 + b) * mx];
-                const float* dd = &cds[((size_t)g * 32 + b) * mx];
-                order.resize((size_t)m);
-                std::iota(order.begin(), order.end(), 0);
-                std::sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return rr[x] < rr[y]; });
-                for (int j = 0; j < m; ++j) {
-                    srow.push_back(rr[order[(size_t)j]] + meta[2 * g + 1]);
-                    sdist.push_back(dd[order[(size_t)j]]);
+        // the flagged queries are independent: their replays run on a few host threads (a replay walks ~5000 entries)
+        auto replay = [&](int b_begin, int b_end) {
+            std::vector<int32_t> srow, order;
+            std::vector<float> sdist;
+            for (int b = b_begin; b < b_end; ++b) {
+                if (std::find(overflow.begin(), overflow.end(), b) != overflow.end()) continue;
+                int64_t n = L0;
+                for (int g = 0; g < G; ++g) n += cnt[(size_t)g * 32 + b];
+                srow.resize((size_t)n);
+                sdist.resize((size_t)n);
+                for (int64_t j = 0; j < L0; ++j) {
+                    srow[(size_t)j] = (int32_t)(j + meta[1]);
+                    sdist[(size_t)j] = dense[(size_t)b * L0p + j];
                 }
+                int64_t at = L0;
+                for (int g = 0; g < G; ++g) {
+                    const int m = cnt[(size_t)g * 32 + b];
+                    const int32_t* rr = cr + ((size_t)g * 32 + b) * mx;
+                    const float* dd = cd + ((size_t)g * 32 + b) * mx;
+                    order.resize((size_t)m);
+                    std::iota(order.begin(), order.end(), 0);
+                    std::sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return rr[x] < rr[y]; });
+                    for (int j = 0; j < m; ++j, ++at) {
+                        srow[(size_t)at] = rr[order[(size_t)j]] + meta[2 * g + 1];
+                        sdist[(size_t)at] = dd[order[(size_t)j]];
+                    }
+                }
+                const int64_t qi = flagged[f0 + b];
+                vs::select_topk_slots_sparse(srow.data(), sdist.data(), n, k, ids + qi * k, dists + qi * k);
             }
-            const int64_t qi = flagged[f0 + b];
-            vs::select_topk_slots_sparse(srow.data(), sdist.data(), (int64_t)srow.size(), k, ids + qi * k, dists + qi * k);
+        };
+        const int n_thr = std::min(4, B / 4);
+        if (n_thr <= 1) {
+            replay(0, B);
+        } else {
+            std::vector<std::thread> pool;
+            std::atomic<bool> failed{false};
+            for (int t = 0; t < n_thr; ++t)
+                pool.emplace_back([&, t]() {
+                    try {
+                        replay(B * t / n_thr, B * (t + 1) / n_thr);
+                    } catch (...) {
+                        failed = true;
+                    }
+                });
+            for (auto& th : pool) th.join();
+            if (failed) {
+                set_error("out of host memory");
+                return VS_ERR_NOMEM;
+            }
         }
         // masses of rows under the bound (duplicates): the query's full distance row, shard after shard, replayed densely
         for (int b : overflow) {
-            int64_t ldm = 0, total = 0;
-            for (int g = 0; g < G; ++g) {
-                ldm = std::max<int64_t>(ldm, ((int64_t)meta[2 * g] + 15) & ~int64_t(15));
-                total += meta[2 * g];
-            }
-            if (o->d_sh_row.size() < (size_t)G * ldm) HIPCHK(hipStreamSynchronize(st));
-            if ((rc = o->d_sh_row.reserve((size_t)G * ldm))) return rc;
             for (size_t i = 0; i < S.hs.size(); ++i) {
                 vs_index* h = S.hs[i];
                 const int g = S.first + (int)i;
-                if ((rc = scores_dev(h, h->d_vecs, h->d_norm, h->n_rows, o->d_q + (size_t)b * vs::kDim, 1, o->d_sh_row + (size_t)g * ldm, ldm, st))) return rc;
+                if ((rc = scores_dev(h, h->d_vecs, h->d_norm, h->n_rows, o->d_q + (size_t)b * vs::kDim, 1,
+                                     reinterpret_cast<float*>(Bf.row + (size_t)g * ldm), ldm, st)))
+                    return rc;
             }
-            if ((rc = S.exchange(reinterpret_cast<int32_t*>(o->d_sh_row.get()), (size_t)ldm))) return rc;
-            std::vector<float> row((size_t)total);
+            if ((rc = S.exchange(Bf.row, (size_t)ldm))) return rc;
+            row.resize((size_t)total);
             int64_t at = 0;
             for (int g = 0; g < G; ++g) {
-                HIPCHK(hipMemcpyAsync(row.data() + at, o->d_sh_row + (size_t)g * ldm, (size_t)meta[2 * g] * sizeof(float), hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(row.data() + at, Bf.row + (size_t)g * ldm, (size_t)meta[2 * g] * sizeof(float), hipMemcpyDeviceToHost, st));
                 at += meta[2 * g];
             }
             HIPCHK(hipStreamSynchronize(st));
@@ -3485,93 +3162,148 @@ int bf_search_shards(const BfShards& S, const float* queries_host, int64_t nq, i
     const double t_start = now_ms();
     vs_timing tm{};
     const int k1 = k + 1;
-    if (!pick_kcap(k1)) {
+    if (S.merge && !pick_kcap(k1)) {
         set_error("k too large for the compiled scan kernels (k <= 15)");
         return VS_ERR_UNSUPPORTED;
     }
     int rc;
+    if ((rc = ensure_pipe(o))) return rc;
+    settle_slots(o->pipe, {st, o->s_h2d, o->s_d2h});
     ShBuf Bf{};
-    if ((rc = sh_reserve(o, G, k1, Bf))) return rc;
+    if ((rc = sh_reserve(o, G, S.merge ? (size_t)(2 * k1 + 1) * kMaxMulti * 32 : 0, 0, 0, Bf))) return rc;
+    if (k1 > kKcapMax && (rc = ensure_topw(o))) return rc;
     // every process needs every shard's (rows, id_offset)
     std::vector<int32_t> meta((size_t)2 * G, 0);
     for (size_t i = 0; i < S.hs.size(); ++i) {
-        const int32_t mine[2] = {(int32_t)S.hs[i]->n_rows, (int32_t)S.hs[i]->id_offset};
-        HIPCHK(hipMemcpyAsync(Bf.meta + 2 * (S.first + i), mine, sizeof(mine), hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));  // (`mine` is a stack buffer)
+        meta[2 * (S.first + i)] = (int32_t)S.hs[i]->n_rows;
+        meta[2 * (S.first + i) + 1] = (int32_t)S.hs[i]->id_offset;
     }
-    if ((rc = S.exchange(Bf.meta, 2))) return rc;
-    HIPCHK(hipMemcpyAsync(meta.data(), Bf.meta, meta.size() * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (S.c && S.c->world > 1) {
+        HIPCHK(hipMemcpyAsync(Bf.meta + 2 * S.first, &meta[2 * S.first], 2 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if ((rc = S.exchange(Bf.meta, 2))) return rc;
+        HIPCHK(hipMemcpyAsync(meta.data(), Bf.meta, meta.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    // the launch step: nb batches of B queries at q -> [nb * B][k1] lists by (dist, id) + flags, on st
+    auto step = [&](const float* q, int nb, int B, float* out_d, int32_t* out_i, int32_t* flags, bool force_f32) -> int {
+        if (k1 > kKcapMax) return topw_launch(o, q, nb, B, k1, out_d, out_i, flags, st);
+        if (!S.merge) return bf_launch(o, o->lane[0], q, nb, B, k1, out_d, out_i, flags, st, force_f32);
+        // the lists of every shard driven here, the exchange, the merge
+        const size_t np = (size_t)nb * B, words = 2 * np * k1 + np;
+        for (size_t i = 0; i < S.hs.size(); ++i) {
+            int32_t* loc = Bf.lists + (S.first + i) * words;
+            int r2 = bf_launch(S.hs[i], S.hs[i]->lane[0], q, nb, B, k1, reinterpret_cast<float*>(loc), loc + np * k1, loc + 2 * np * k1,
+                               st, force_f32);
+            if (r2) return r2;
+        }
+        if (int r2 = S.exchange(Bf.lists, words)) return r2;
+        vs::MergeParams m{};
+        m.part_d = reinterpret_cast<const float*>(Bf.lists);
+        m.part_i = Bf.lists + np * k1;
+        m.G = G;
+        m.kin = k1;
+        m.nq = (int)np;
+        m.kout = k1;
+        m.out_d = out_d;
+        m.out_i = out_i;
+        m.flags = flags;
+        m.flag_empty = 1;
+        m.shard_flags = Bf.lists + 2 * np * k1;
+        m.shard_flags_stride = (int64_t)words;
+        HIPCHK(vs::launch_merge_layout(m, (int64_t)words, k1, st));
+        return VS_OK;
+    };
+    // Queries go through in chunks of kMaxMulti batches: the full batches in one launch step, a ragged tail batch in another
+    // (the harness loop of main.cpp:201-251 collapsed into a call).  Two chunks are in flight: uploads and downloads run on
+    // copy streams beside the other chunk's kernels.
     const int batch = o->batch;
     const int64_t chunk = (int64_t)kMaxMulti * batch;
-    std::vector<float> hd((size_t)chunk * k1);
-    std::vector<int32_t> hi((size_t)chunk * k1), hf((size_t)chunk);
-    std::vector<int64_t> flagged;
     const float inf = std::numeric_limits<float>::infinity();
-    for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
-        const int64_t n = std::min<int64_t>(chunk, nq - q0);
-        const int full = (int)(n / batch), rem = (int)(n % batch);
-        HIPCHK(hipMemcpyAsync(o->d_q, queries_host + q0 * vs::kDim, (size_t)n * vs::kDim * sizeof(float), hipMemcpyHostToDevice, st));
-        // one part of the chunk (its full batches, or the ragged tail batch): local lists of every shard driven here, the
-        // exchange, the merge into the owner's output buffers
-        auto part = [&](size_t o0, int nb, int B, bool force_f32) -> int {
-            const size_t np = (size_t)nb * B, words = 2 * np * k1 + np;
-            for (size_t i = 0; i < S.hs.size(); ++i) {
-                int32_t* loc = Bf.main + (size_t)(S.first + i) * words;
-                int r2 = bf_launch(S.hs[i], S.hs[i]->lane[0], o->d_q + o0 * vs::kDim, nb, B, k1, reinterpret_cast<float*>(loc),
-                                   loc + np * k1, loc + 2 * np * k1, st, force_f32);
-                if (r2) return r2;
-            }
-            int r2 = S.exchange(Bf.main, words);
-            if (r2) return r2;
-            vs::MergeParams m{};
-            m.part_d = reinterpret_cast<const float*>(Bf.main);
-            m.part_i = Bf.main + np * k1;
-            m.G = G;
-            m.kin = k1;
-            m.nq = (int)np;
-            m.kout = k1;
-            m.out_d = o->d_out_d + o0 * k1;
-            m.out_i = o->d_out_i + o0 * k1;
-            m.flags = o->d_flags + o0;
-            m.flag_empty = 1;
-            m.shard_flags = Bf.main + 2 * np * k1;
-            m.shard_flags_stride = (int64_t)words;
-            HIPCHK(vs::launch_merge_layout(m, (int64_t)words, k1, st));
-            return VS_OK;
-        };
-        auto pass = [&](bool force_f32) -> int {
-            int r2 = VS_OK;
-            if (full) r2 = part(0, full, batch, force_f32);
-            if (!r2 && rem) r2 = part((size_t)full * batch, 1, rem, force_f32);
-            if (r2) return r2;
-            HIPCHK(hipMemcpyAsync(hd.data(), o->d_out_d, (size_t)n * k1 * sizeof(float), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(hi.data(), o->d_out_i, (size_t)n * k1 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(hf.data(), o->d_flags, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            return VS_OK;
-        };
-        if ((rc = pass(false))) return rc;
+    std::vector<int64_t> flagged;
+    auto launch_chunk = [&](vs_index::PipeSlot& P, bool force_f32) -> int {
+        const int full = (int)(P.n / batch), rem = (int)(P.n % batch);
+        int r2 = VS_OK;
+        if (full) r2 = step(P.d_q, full, batch, P.d_out_d, P.d_out_i, P.d_flags, force_f32);
+        if (!r2 && rem) {
+            const size_t o0 = (size_t)full * batch;
+            r2 = step(P.d_q + o0 * vs::kDim, 1, rem, P.d_out_d + o0 * k1, P.d_out_i + o0 * k1, P.d_flags + o0, force_f32);
+        }
+        return r2;
+    };
+    auto download = [&](vs_index::PipeSlot& P, hipStream_t s) -> int {
+        float* hd = reinterpret_cast<float*>(P.pin_out.get());
+        int32_t* hi = reinterpret_cast<int32_t*>(P.pin_out.get()) + (size_t)chunk * k1;
+        int32_t* hf = hi + (size_t)chunk * k1;
+        HIPCHK(hipMemcpyAsync(hd, P.d_out_d, (size_t)P.n * k1 * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(hi, P.d_out_i, (size_t)P.n * k1 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(hf, P.d_flags, (size_t)P.n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        return VS_OK;
+    };
+    auto enqueue = [&](vs_index::PipeSlot& P, int64_t q0, int64_t n) -> int {
+        const double t0 = now_ms();
+        P.q0 = q0;
+        P.n = n;
+        std::memcpy(P.pin_q, queries_host + q0 * vs::kDim, (size_t)n * vs::kDim * sizeof(float));
+        HIPCHK(hipMemcpyAsync(P.d_q, P.pin_q, (size_t)n * vs::kDim * sizeof(float), hipMemcpyHostToDevice, o->s_h2d));
+        HIPCHK(hipEventRecord(P.ev_h2d, o->s_h2d));
+        tm.h2d_ms += now_ms() - t0;
+        HIPCHK(hipStreamWaitEvent(st, P.ev_h2d, 0));
+        int r2 = launch_chunk(P, false);
+        if (r2) return r2;
+        HIPCHK(hipEventRecord(P.ev_comp, st));
+        HIPCHK(hipStreamWaitEvent(o->s_d2h, P.ev_comp, 0));
+        if ((r2 = download(P, o->s_d2h))) return r2;
+        HIPCHK(hipEventRecord(P.ev_d2h, o->s_d2h));
+        return VS_OK;
+    };
+    auto retire = [&](vs_index::PipeSlot& P) -> int {
+        if (P.q0 < 0) return VS_OK;
+        const double t0 = now_ms();
+        HIPCHK(hipEventSynchronize(P.ev_d2h));
+        const float* hd = reinterpret_cast<const float*>(P.pin_out.get());
+        const int32_t* hi = reinterpret_cast<const int32_t*>(P.pin_out.get()) + (size_t)chunk * k1;
+        const int32_t* hf = hi + (size_t)chunk * k1;
         bool rerun = false;
-        for (int64_t b = 0; b < n; ++b) rerun = rerun || hf[(size_t)b] == 2;
-        // a shard's int8 scan skipped a batch (a query that is not an integer in [0, 255]): the merged flag says so on every
-        // rank alike, and every rank reruns the chunk on its fp32 rows
-        if (rerun && (rc = pass(true))) return rc;
-        for (int64_t b = 0; b < n; ++b) {
+        for (int64_t b = 0; b < P.n; ++b) rerun = rerun || hf[(size_t)b] == 2;
+        // Flag 2: an int8 scan skipped a batch of this chunk (a query that is not an integer in [0, 255]) -> the chunk again
+        // on the fp32 rows.  Sharded calls issue every collective in the same order on every rank: the chunks' exchanges,
+        // a rerun's (decided here from the merged flags, which every rank holds alike; enqueued behind the next chunk), then
+        // the tie resolver's.
+        if (rerun) {
+            int r2 = launch_chunk(P, true);
+            if (r2) return r2;
+            if ((r2 = download(P, st))) return r2;
+            HIPCHK(hipStreamSynchronize(st));
+        }
+        tm.d2h_ms += now_ms() - t0;
+        // k of the k1 entries (+inf: no row; inner product: the score q.v); flag 1: equal distances among the k1
+        for (int64_t b = 0; b < P.n; ++b) {
             for (int t = 0; t < k; ++t) {
                 const int32_t id = hi[(size_t)b * k1 + t];
-                ids[(q0 + b) * k + t] = id;
+                ids[(P.q0 + b) * k + t] = id;
                 float d = id >= 0 ? hd[(size_t)b * k1 + t] : inf;
                 if (o->metric == VS_METRIC_IP && id >= 0) d = -d;
-                dists[(q0 + b) * k + t] = d;
+                dists[(P.q0 + b) * k + t] = d;
             }
-            if (hf[(size_t)b] == 1) flagged.push_back(q0 + b);
+            if (hf[(size_t)b] == 1) flagged.push_back(P.q0 + b);
         }
+        P.q0 = -1;
+        return VS_OK;
+    };
+    int c = 0;
+    for (int64_t q0 = 0; q0 < nq; q0 += chunk, ++c) {
+        vs_index::PipeSlot& P = o->pipe[c & 1];
+        if ((rc = retire(P))) return rc;
+        if ((rc = enqueue(P, q0, std::min<int64_t>(chunk, nq - q0)))) return rc;
     }
+    if ((rc = retire(o->pipe[c & 1]))) return rc;  // the older chunk first
+    if ((rc = retire(o->pipe[(c + 1) & 1]))) return rc;
     tm.fine_search_ms = now_ms() - t_start;
+    // ties inside the k+1 best: the reference's order is history dependent -> replay select_topk over the rows that can
+    // change its buffer
     if (!flagged.empty() && o->metric == VS_METRIC_L2) {
         const double t0 = now_ms();
-        if ((rc = resolve_ties_shards(S, Bf, meta, queries_host, flagged, k, ids, dists))) return rc;
+        if ((rc = resolve_ties_shards(S, meta, queries_host, flagged, k, ids, dists))) return rc;
         tm.tie_resolve_ms = now_ms() - t0;
         tm.tie_queries = (int64_t)flagged.size();
     }
@@ -3583,6 +3315,57 @@ int bf_search_shards(const BfShards& S, const float* queries_host, int64_t nq, i
 }  // namespace
 
 extern "C" {
+
+int vs_bf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int32_t* ids, float* dists,
+                 vs_timing* timing) {
+    if (!h || h->kind != 0 || !queries_host || !ids || !dists || nq < 0 || k < 1) {
+        set_error("vs_bf_search: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    return guarded([&]() -> int {
+        int rc = set_device(h);
+        if (rc) return rc;
+        if (!pick_kcap(k + 1)) {
+            set_error("k too large for the compiled scan kernels (k <= 15)");
+            return VS_ERR_UNSUPPORTED;
+        }
+        if ((rc = order_begin(h, h->stream))) return rc;
+        BfShards S;
+        S.hs = {h};
+        S.merge = false;
+        return bf_search_shards(S, queries_host, nq, k, ids, dists, timing);
+    });
+}
+
+int vs_bf_search_topk(vs_index* h, const float* queries_host, int64_t nq, int k, int32_t* ids, float* dists, vs_timing* timing) {
+    if (!h || h->kind != 0 || !queries_host || !ids || !dists || nq < 0 || k < 1) {
+        set_error("vs_bf_search_topk: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    if (k > vs::kTopkWideMax - 1) {
+        set_error("vs_bf_search_topk: k > 128");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (k + 1 <= kKcapMax) return vs_bf_search(h, queries_host, nq, k, ids, dists, timing);
+    return guarded([&]() -> int {
+        int rc = set_device(h);
+        if (rc) return rc;
+        if (g_topw_stats) g_topw_st = TopwStats{};
+        if ((rc = order_begin(h, h->stream))) return rc;
+        BfShards S;
+        S.hs = {h};
+        S.merge = false;
+        vs_timing tm{};
+        if ((rc = bf_search_shards(S, queries_host, nq, k, ids, dists, &tm))) return rc;
+        if (timing) *timing = tm;
+        if (g_topw_stats)
+            fprintf(stderr, "topw_stats k=%d batches=%lld overflowed=%lld queries=%lld cand_mean=%.1f cand_max=%lld flagged=%lld\n", k,
+                    (long long)g_topw_st.batches, (long long)g_topw_st.overflowed, (long long)g_topw_st.queries,
+                    g_topw_st.queries ? (double)g_topw_st.cand_sum / g_topw_st.queries : 0.0, (long long)g_topw_st.cand_max,
+                    (long long)tm.tie_queries);
+        return VS_OK;
+    });
+}
 
 // Host-buffer forms of the sharded searches (what the CLIs call with --gpus N): every rank passes the same queries and
 // receives the same result -- for brute force the reference's own (select_topk's tie order, fp32 rerun of batches the

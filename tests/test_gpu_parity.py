@@ -596,13 +596,19 @@ def test_sharded_shard_that_skips_a_batch_is_rerun_not_dropped(gpu_pkg):
     q = rng.integers(0, 200, size=(40, 128)).astype(np.float32)
     q[3, 10] += 0.25                                                        # non-integer query in the first batch
     q[0] = a[17]                                                            # whose neighbours are in the byte shard
-    od = ((q.astype(np.float64)[:, None, :] - base.astype(np.float64)[None]) ** 2).sum(-1)
-    want = np.argsort(od, axis=1, kind="stable")[:, :5]
+    # the same batch in the second chunk of 1 024 queries (2 100 queries: a third, ragged chunk is enqueued before its rerun)
+    q2 = rng.integers(0, 200, size=(2100, 128)).astype(np.float32)
+    q2[1600:1640] = q
     shards = [gpu_pkg.BruteForceIndex(a, id_offset=0), gpu_pkg.BruteForceIndex(b, id_offset=4000)]
     try:
-        ids, d = gpu_pkg.BruteForceIndex.search_vshards(shards, q, 5)
-        assert np.array_equal(ids, want.astype(np.int32))
-        assert np.allclose(d, np.take_along_axis(od, want, 1), rtol=1e-6)
+        for qq in (q, q2):
+            # float64 distances, exact here: every product and sum is a multiple of 1/16 far below 2^53
+            q64, b64 = qq.astype(np.float64), base.astype(np.float64)
+            od = (q64 ** 2).sum(1)[:, None] + (b64 ** 2).sum(1)[None] - 2.0 * (q64 @ b64.T)
+            want = np.argsort(od, axis=1, kind="stable")[:, :5]
+            ids, d = gpu_pkg.BruteForceIndex.search_vshards(shards, qq, 5)
+            assert np.array_equal(ids, want.astype(np.int32))
+            assert np.allclose(d, np.take_along_axis(od, want, 1), rtol=1e-6)
     finally:
         for sh in shards:
             sh.close()

@@ -108,6 +108,13 @@ def test_ties_and_duplicates_k100(gpu_pkg):
     ramp = np.zeros((4000, 128), dtype=np.float32)
     ramp[:, 0] = np.arange(4000, 0, -1) % 251
     _check_exact(gpu_pkg, ramp, np.zeros((3, 128), dtype=np.float32), 100)
+    # more than one chunk of 1 024 queries and a ragged tail, on a base past the k = 100 dense prefix (53 248 rows): the
+    # queries that equal a planted duplicate are flagged in every chunk
+    big = rng.integers(0, 219, size=(60000, 128)).astype(np.float32)
+    big[56000:56300] = big[:300]
+    qb = rng.integers(0, 219, size=(2100, 128)).astype(np.float32)
+    qb[::7] = big[rng.integers(0, 300, size=300)]
+    _check_exact(gpu_pkg, big, qb, 100)
 
 
 def test_mass_duplicates_overflow_to_dense_path(gpu_pkg):
