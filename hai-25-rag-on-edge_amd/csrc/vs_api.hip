@@ -180,8 +180,8 @@ struct vs_index {
     vs::DevBuf<int32_t> d_head_tdelta;  // [nlist] padded row - row
     vs::DevBuf<int32_t> d_sh;           // host-buffer brute force (bf_search_shards): the owner's gathered scratch (see ShBuf)
     vs::PinBuf<char> pin_sh;            // ... and the tie resolver's pinned downloads
-    vs::DevBuf<int32_t> vsh_blk;        // virtual ranks (vs_ivf_search_dev_vshards): the gathered blocks / top-k lists, owned by shard 0
-    vs::DevBuf<int32_t> vsh_loc;
+    vs::DevBuf<int32_t> sl_blk[2];      // sliced IVF pipeline (ivf_sliced_groups): the owner's gathered blocks / top-k lists, per lane
+    vs::DevBuf<int32_t> sl_lists[2];
     // wide IVF pipeline (a launch group of up to 32 batches shares one list-major pass): slot tables, zeroed counters,
     // plans, bounds, prepared queries, candidate sink
     struct IvfWide {
@@ -2290,134 +2290,6 @@ int vs_ivf_search_dev_multi(vs_index* h, const float* queries_dev, int n_batches
     return rc ? rc : order_end(h, user);
 }
 
-int vs_ivf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int nprobe, int32_t* ids, float* dists,
-                  int64_t* total_candidates, vs_timing* timing) {
-    if (!h || h->kind != 1 || !queries_host || !ids || !dists || nq < 0 || k < 1 || nprobe < 1) {
-        set_error("vs_ivf_search: bad arguments");
-        return VS_ERR_INVALID;
-    }
-    nprobe = std::min(nprobe, h->nlist);
-    if (nprobe > kMaxNprobe) {
-        set_error("nprobe > 256 not supported");
-        return VS_ERR_UNSUPPORTED;
-    }
-    if (k > 64) {
-        set_error("k > 64 not supported by the host-buffer API");
-        return VS_ERR_UNSUPPORTED;
-    }
-    return guarded([&]() -> int {
-        int rc = set_device(h);
-        if (rc) return rc;
-        const double t_start = now_ms();
-        vs_timing tm{};
-        if ((rc = ensure_pipe(h)) || (rc = ensure_wide_streams(h)) || (rc = ensure_ivf_host(h)) || (rc = order_begin(h, h->stream))) return rc;
-        settle_slots(h->ihs, {h->wide_stream[0], h->wide_stream[1], h->s_h2d, h->s_d2h});
-        h->stage_on = true;
-        h->stage_used = 0;
-        HIPCHK(hipMemsetAsync(h->d_cand, 0, sizeof(unsigned long long), h->stream));
-        const float inf = std::numeric_limits<float>::infinity();
-        // Queries go through in chunks (the harness loop of main_ivf.cpp:150-214 collapsed into a call): a chunk is ONE
-        // upload, its launch groups dealt to the two lanes' streams, ONE download -- the host, not the device, is the limit
-        // of this call (a hipMemcpyAsync costs about as much host time as a launch group's five launches).  Two chunks in
-        // flight; at least two chunks per call where there is enough work, so that the second upload runs beside the
-        // first chunk's kernels.  A ragged tail batch gets a launch group of its own.
-        const bool wide = ivf_wide_ok(h, k);
-        HIPCHK(hipEventRecord(h->wide_fork, h->stream));  // (behind the memset above)
-        for (int i = 0; i < 2; ++i) HIPCHK(hipStreamWaitEvent(h->wide_stream[i], h->wide_fork, 0));
-        const int64_t group_q = (int64_t)h->ivf_gb * h->batch;
-        const int64_t unit_q = (int64_t)vs::kIvfWideBatches * h->batch;  // a super-batch of queries: chunks are cut at these
-        const int64_t cap_q = h->ivf_host_cap / unit_q * unit_q;
-        const int64_t wchunk = std::min<int64_t>(cap_q, std::max<int64_t>(unit_q, (nq / 2 + unit_q - 1) / unit_q * unit_q));
-        int next_lane = 0;
-        auto enqueue = [&](vs_index::IvfHostSlot& S, int64_t q0, int64_t n) -> int {
-            const double t0 = now_ms();
-            S.q0 = q0;
-            S.n = n;
-            std::memcpy(S.pin_q, queries_host + q0 * vs::kDim, (size_t)n * vs::kDim * sizeof(float));
-            HIPCHK(hipMemcpyAsync(S.d_q, S.pin_q, (size_t)n * vs::kDim * sizeof(float), hipMemcpyHostToDevice, h->s_h2d));
-            HIPCHK(hipEventRecord(S.ev_h2d, h->s_h2d));
-            tm.h2d_ms += now_ms() - t0;
-            float* od = S.d_out;
-            int32_t* oi = reinterpret_cast<int32_t*>(S.d_out + (size_t)n * k);
-            bool used[2] = {false, false};
-            for (int64_t g0 = 0; g0 < n; g0 += group_q) {
-                const int64_t gn = std::min<int64_t>(group_q, n - g0);
-                const int full = (int)(gn / h->batch), rem = (int)(gn % h->batch);
-                const int lane = wide ? next_lane : 0;
-                next_lane ^= 1;
-                const hipStream_t cs = h->wide_stream[lane];
-                if (!used[lane]) HIPCHK(hipStreamWaitEvent(cs, S.ev_h2d, 0));
-                used[lane] = true;
-                int r2 = VS_OK;
-                auto run = [&](size_t o, int nb, int B) -> int {
-                    if (wide) return ivf_group_wide_dev(h, lane, S.d_q + o * vs::kDim, nb, B, k, nprobe, od + o * k, oi + o * k, cs);
-                    int r3 = VS_OK;
-                    for (int b = 0; b < nb && !r3; ++b)
-                        r3 = ivf_fallback_batch_dev(h, S.d_q + (o + (size_t)b * B) * vs::kDim, B, k, nprobe, od + (o + (size_t)b * B) * k,
-                                                    oi + (o + (size_t)b * B) * k, cs);
-                    return r3;
-                };
-                if (full) r2 = run((size_t)g0, full, h->batch);
-                if (!r2 && rem) r2 = run((size_t)g0 + (size_t)full * h->batch, 1, rem);  // the call's ragged tail
-                if (r2) return r2;
-            }
-            for (int lane = 0; lane < 2; ++lane)
-                if (used[lane]) {
-                    HIPCHK(hipEventRecord(S.ev_comp[lane], h->wide_stream[lane]));
-                    HIPCHK(hipStreamWaitEvent(h->s_d2h, S.ev_comp[lane], 0));
-                }
-            HIPCHK(hipMemcpyAsync(S.pin_out, S.d_out, (size_t)n * k * 2 * sizeof(float), hipMemcpyDeviceToHost, h->s_d2h));
-            HIPCHK(hipEventRecord(S.ev_d2h, h->s_d2h));
-            return VS_OK;
-        };
-        auto retire = [&](vs_index::IvfHostSlot& S) -> int {
-            if (S.q0 < 0) return VS_OK;
-            const double t0 = now_ms();
-            HIPCHK(hipEventSynchronize(S.ev_d2h));
-            tm.d2h_ms += now_ms() - t0;
-            const float* hd = S.pin_out;
-            const int32_t* hi = reinterpret_cast<const int32_t*>(S.pin_out + (size_t)S.n * k);
-            for (int64_t i = 0; i < S.n * k; ++i) {
-                const int32_t id = hi[i];
-                ids[S.q0 * k + i] = id;
-                dists[S.q0 * k + i] = id >= 0 ? (h->metric == VS_METRIC_IP ? -hd[i] : hd[i]) : inf;  // (IP: the score q.v, as IVFIndex returns it)
-            }
-            S.q0 = -1;
-            return VS_OK;
-        };
-        int c = 0;
-        for (int64_t q0 = 0; q0 < nq; q0 += wchunk, ++c) {
-            vs_index::IvfHostSlot& S = h->ihs[c & 1];
-            if ((rc = retire(S))) return rc;
-            if ((rc = enqueue(S, q0, std::min<int64_t>(wchunk, nq - q0)))) return rc;
-        }
-        if ((rc = retire(h->ihs[c & 1]))) return rc;
-        if ((rc = retire(h->ihs[(c + 1) & 1]))) return rc;
-        for (int i = 0; i < 2; ++i) {  // the index's stream continues behind the lanes
-            HIPCHK(hipEventRecord(h->wide_join[i], h->wide_stream[i]));
-            HIPCHK(hipStreamWaitEvent(h->stream, h->wide_join[i], 0));
-        }
-        unsigned long long cand = 0;
-        HIPCHK(hipMemcpyAsync(&cand, h->d_cand, sizeof(cand), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (total_candidates) *total_candidates = (int64_t)cand;
-        tm.total_ms = now_ms() - t_start;
-        // SearchTiming split (IVFIndex.h:31-36): device time of the three stages from the events between their launches,
-        // summed over the call's launch groups (uploads and downloads overlap them)
-        for (int i = 0; i + 3 < h->stage_used; i += 4) {
-            float ms[3] = {0, 0, 0};
-            for (int j = 0; j < 3; ++j) (void)hipEventElapsedTime(&ms[j], h->stage_ev[i + j], h->stage_ev[i + j + 1]);
-            tm.centroid_search_ms += ms[0];
-            tm.gather_ms += ms[1];
-            tm.fine_search_ms += ms[2];
-        }
-        h->stage_on = false;
-        h->stage_used = 0;
-        if (timing) *timing = tm;
-        return order_end(h, h->stream);
-    });
-}
-
 #ifdef VS_STAMPS
 // diagnostic builds only (make EXTRA=-DVS_STAMPS; not part of the ABI): state of the wide IVF pipeline after the last launch group
 __attribute__((visibility("default"))) int vs_debug_ivf_wide_stats(vs_index* h, int64_t* out /*[8]*/) {
@@ -2554,10 +2426,7 @@ struct vs_comm {
     bool coll_used[2] = {false, false};
     vs::DevBuf<int32_t> d_loc[2];   // this rank's lists of one launch group: [dists n*kin][ids n*kin] as 32-bit words
     vs::DevBuf<int32_t> d_gath[2];  // [world] x the same
-    // cluster-sharded IVF: the slices' blocks (probes | tau | slow) of one launch group, exchanged between its two halves
-    vs::DevBuf<int32_t> d_blk[2];   // this rank's block
-    vs::DevBuf<int32_t> d_blkg[2];  // [world] blocks
-    vs::Event ev_front[2], ev_probe[2];
+    vs::Event ev_front[2], ev_probe[2];  // cluster-sharded IVF: a lane's blocks are written / exchanged (ivf_sliced_groups)
 };
 
 namespace {
@@ -2626,6 +2495,133 @@ int sharded_groups(vs_index* h, vs_comm* c, int n_batches, int B, int kin, int k
     // the caller's stream continues after the last two groups' merges
     for (int buf = 0; buf < 2; ++buf)
         if (c->coll_used[buf]) HIPCHK(hipStreamWaitEvent(user, c->ev_coll[buf], 0));
+    return VS_OK;
+}
+
+// ---- The shards one process drives: either ONE shard of a collective job (c: the other ranks run the same code, the
+// exchanges are RCCL all-gathers) or ALL G shards on one device (virtual ranks: an exchange is a no-op, every shard has
+// written its part of the gathered buffer in place).  Everything else -- per-shard device steps, merge, host steps -- is
+// the same code.  Brute force: shards are contiguous row ranges in rank order (vs_bf_create(rows of the shard, id_offset =
+// first row)), and vs_bf_search / vs_bf_search_topk are one index (G = 1, no communicator) without the merge.  IVF: shard r
+// is the index created with (rank r, world G).
+struct Shards {
+    std::vector<vs_index*> hs;  // the shards driven here; hs[i] is global shard first + i
+    int G = 1, first = 0;
+    vs_comm* c = nullptr;
+    bool merge = true;          // brute force: the shards' lists go through the exchange and the merge (every sharded call, G = 1 included)
+    vs_index* owner() const { return hs[0]; }
+    hipStream_t s() const { return hs[0]->stream; }
+    int exchange(int32_t* buf, size_t words, hipStream_t st) const {  // buf = [G][words], this process's parts in place
+        if (!c || c->world == 1) return VS_OK;
+        NCCLCHK(rccl().AllGather(buf + (size_t)c->rank * words, buf, words, ncclInt32, c->comm, st));
+        return VS_OK;
+    }
+};
+
+// ---- sliced pipeline of the shards driven here, per launch group of the owner's ivf_gb batches: every shard's front half
+// (its own slice) into its part of the gathered blocks [G][block words], the exchange of the blocks, every shard's back half
+// (all slices, its own lists) into its part of the gathered lists [G][2 * n * k], the exchange of the lists, one merge into
+// the caller's outputs.  With a communicator the groups are software pipelined over two lanes: the caller's stream runs
+// F(g), then B(g - 1); the collective stream the exchange of g's blocks, then g - 1's lists and their merge -- the same
+// order on every rank -- so that an exchange is in flight while the neighbouring group computes.  Group g uses lane g & 1.
+// Virtual ranks run F(g), then B(g), on lane 0 and the caller's stream alone; rank_ms[r] (optional) then adds the device
+// time of shard r's two halves.
+int ivf_sliced_groups(const Shards& S, const float* q_dev, int n_batches, int B, int k, int nprobe, int32_t* ids, float* dists,
+                      double* rank_ms, hipStream_t st) {
+    vs_index* o = S.owner();
+    vs_comm* c = S.c;
+    const int G = S.G, gb = o->ivf_gb, lanes = c ? 2 : 1;
+    const hipStream_t sc = c ? static_cast<hipStream_t>(c->s_coll) : st;  // exchanges and merge
+    // the owner's gathered buffers of each lane: grown only after a synchronise (an earlier call's groups may still use them)
+    const size_t blk_words = (size_t)G * ivf_block_words(vs::kIvfWideBatches, kMaxNprobe), list_words = (size_t)G * 2 * gb * 32 * k;
+    bool grow = false;
+    for (int l = 0; l < lanes; ++l) grow |= o->sl_blk[l].size() < blk_words || o->sl_lists[l].size() < list_words;
+    if (grow) HIPCHK(hipDeviceSynchronize());
+    int rc;
+    for (int l = 0; l < lanes; ++l)
+        if ((rc = o->sl_blk[l].reserve(blk_words)) || (rc = o->sl_lists[l].reserve(list_words))) return rc;
+    std::vector<vs::Event> ev;  // rank_ms: start and end of each shard's front and back half
+    if (rank_ms) {
+        ev.resize((size_t)4 * S.hs.size());
+        for (auto& e : ev)
+            if ((rc = e.create(true))) return rc;
+        for (size_t i = 0; i < S.hs.size(); ++i) rank_ms[S.first + i] = 0;
+    }
+    auto front = [&](int g) -> int {
+        const int lane = g % lanes, b0 = g * gb, nb = std::min(gb, n_batches - b0);
+        const float* q = q_dev + (size_t)b0 * B * vs::kDim;
+        int sbb = (nb + G - 1) / G, sb0, nbs;
+        for (size_t i = 0; i < S.hs.size(); ++i) {
+            ivf_slice(nb, G, S.first + (int)i, sbb, sb0, nbs);
+            // (the lane's scratch and blocks: group g - 2's back half is behind on this stream, and it waited for that group's exchange)
+            int32_t* blk = o->sl_blk[lane] + (size_t)(S.first + i) * ivf_block_words(sbb, nprobe);
+            if (rank_ms) HIPCHK(hipEventRecord(ev[4 * i], st));
+            if (int r2 = ivf_shard_front(S.hs[i], lane, q, nb, sbb, sb0, nbs, B, k, nprobe, blk, st)) return r2;
+            if (rank_ms) HIPCHK(hipEventRecord(ev[4 * i + 1], st));
+        }
+        if (c) {
+            HIPCHK(hipEventRecord(c->ev_front[lane], st));
+            HIPCHK(hipStreamWaitEvent(sc, c->ev_front[lane], 0));
+        }
+        if (int r2 = S.exchange(o->sl_blk[lane], (size_t)ivf_block_words(sbb, nprobe), sc)) return r2;
+        if (c) HIPCHK(hipEventRecord(c->ev_probe[lane], sc));
+        return VS_OK;
+    };
+    auto back = [&](int g) -> int {
+        const int lane = g % lanes, b0 = g * gb, nb = std::min(gb, n_batches - b0), sbb = (nb + G - 1) / G;  // (= ivf_slice's)
+        const float* q = q_dev + (size_t)b0 * B * vs::kDim;
+        const size_t n = (size_t)nb * B, words = 2 * n * k;
+        int32_t* lists = o->sl_lists[lane];
+        if (c) {
+            HIPCHK(hipStreamWaitEvent(st, c->ev_probe[lane], 0));
+            if (c->coll_used[lane]) HIPCHK(hipStreamWaitEvent(st, c->ev_coll[lane], 0));  // group g - 2's merge has read the lists
+        }
+        for (size_t i = 0; i < S.hs.size(); ++i) {
+            int32_t* loc = lists + (S.first + i) * words;
+            if (rank_ms) HIPCHK(hipEventRecord(ev[4 * i + 2], st));
+            if (int r2 = ivf_shard_back(S.hs[i], lane, q, nb, sbb, B, k, nprobe, o->sl_blk[lane], reinterpret_cast<float*>(loc), loc + n * k, st))
+                return r2;
+            if (rank_ms) HIPCHK(hipEventRecord(ev[4 * i + 3], st));
+        }
+        if (c) {
+            HIPCHK(hipEventRecord(c->ev_scan[lane], st));
+            HIPCHK(hipStreamWaitEvent(sc, c->ev_scan[lane], 0));
+        }
+        if (int r2 = S.exchange(lists, words, sc)) return r2;
+        vs::MergeParams m{};
+        m.part_d = reinterpret_cast<const float*>(lists);
+        m.part_i = lists + n * k;
+        m.G = G;
+        m.kin = k;
+        m.nq = (int)n;
+        m.kout = k;
+        m.out_d = dists + (size_t)b0 * B * k;
+        m.out_i = ids + (size_t)b0 * B * k;
+        HIPCHK(vs::launch_merge_layout(m, (int64_t)words, k, sc));
+        if (c) {
+            HIPCHK(hipEventRecord(c->ev_coll[lane], sc));
+            c->coll_used[lane] = true;
+        }
+        if (rank_ms) {
+            HIPCHK(hipStreamSynchronize(st));
+            for (size_t i = 0; i < S.hs.size(); ++i) {
+                float a = 0, b = 0;
+                HIPCHK(hipEventElapsedTime(&a, ev[4 * i], ev[4 * i + 1]));
+                HIPCHK(hipEventElapsedTime(&b, ev[4 * i + 2], ev[4 * i + 3]));
+                rank_ms[S.first + i] += a + b;
+            }
+        }
+        return VS_OK;
+    };
+    const int n_groups = (n_batches + gb - 1) / gb, lag = c ? 1 : 0;
+    for (int g = 0; g < n_groups + lag; ++g) {
+        if (g < n_groups && (rc = front(g))) return rc;
+        if (g >= lag && (rc = back(g - lag))) return rc;
+    }
+    // the caller's stream continues after the last two groups' merges
+    if (c)
+        for (int lane = 0; lane < 2; ++lane)
+            if (c->coll_used[lane]) HIPCHK(hipStreamWaitEvent(st, c->ev_coll[lane], 0));
     return VS_OK;
 }
 
@@ -2753,71 +2749,13 @@ int vs_ivf_search_dev_sharded(vs_index* h, vs_comm* c, const float* queries_dev,
                             });
         return rc ? rc : order_end(h, user);
     }
-    // ---- sliced pipeline: group g's front half (own slice), the exchange of the slices' blocks, its back half (all
-    // slices, own lists), the all-gather of top-k lists and their merge.  Software pipelined over the launch groups:
-    // the compute stream runs F(g), then B(g - 1); the collective stream P(g), then T(g - 1) -- the same order on every
-    // rank -- so that an exchange is in flight while the neighbouring group computes.  Group g uses lane g & 1.
-    const int world = c->world, gb = h->ivf_gb;
-    const size_t blk_words_max = (size_t)ivf_block_words(vs::kIvfWideBatches, kMaxNprobe);
-    if ((rc = reserve_pairs(c->d_blk, c->d_blkg, blk_words_max, world))) return rc;
-    if ((rc = reserve_pairs(c->d_loc, c->d_gath, (size_t)2 * gb * 32 * k, c->world))) return rc;
-    struct Grp {
-        int b0, nb, sbb;
-    };
-    auto group_of = [&](int g) {
-        Grp G;
-        G.b0 = g * gb;
-        G.nb = std::min(gb, n_batches - G.b0);
-        int b0_, nbs_;
-        ivf_slice(G.nb, world, 0, G.sbb, b0_, nbs_);  // batches per slice (<= 32)
-        return G;
-    };
-    const int n_groups = (n_batches + gb - 1) / gb;
-    auto back_and_gather = [&](int g) -> int {
-        const Grp G = group_of(g);
-        const int lane = g & 1;
-        const size_t n = (size_t)G.nb * B, words = 2 * n * k;
-        float* loc_d = reinterpret_cast<float*>(c->d_loc[lane].get());
-        int32_t* loc_i = c->d_loc[lane] + n * k;
-        HIPCHK(hipStreamWaitEvent(user, c->ev_probe[lane], 0));
-        if (c->coll_used[lane]) HIPCHK(hipStreamWaitEvent(user, c->ev_coll[lane], 0));  // group g - 2's merge has read d_gath
-        int r2 = ivf_shard_back(h, lane, queries_dev + (size_t)G.b0 * B * vs::kDim, G.nb, G.sbb, B, k, nprobe, c->d_blkg[lane], loc_d, loc_i, user);
-        if (r2) return r2;
-        HIPCHK(hipEventRecord(c->ev_scan[lane], user));
-        HIPCHK(hipStreamWaitEvent(c->s_coll, c->ev_scan[lane], 0));
-        NCCLCHK(rccl().AllGather(c->d_loc[lane], c->d_gath[lane], words, ncclInt32, c->comm, c->s_coll));
-        vs::MergeParams m{};
-        m.part_d = reinterpret_cast<const float*>(c->d_gath[lane].get());
-        m.part_i = c->d_gath[lane] + n * k;
-        m.G = world;
-        m.kin = k;
-        m.nq = (int)n;
-        m.kout = k;
-        m.out_d = dists_dev + (size_t)G.b0 * B * k;
-        m.out_i = ids_dev + (size_t)G.b0 * B * k;
-        HIPCHK(vs::launch_merge_layout(m, (int64_t)words, k, c->s_coll));
-        HIPCHK(hipEventRecord(c->ev_coll[lane], c->s_coll));
-        c->coll_used[lane] = true;
-        return VS_OK;
-    };
-    for (int g = 0; g < n_groups; ++g) {
-        const Grp G = group_of(g);
-        const int lane = g & 1;
-        int sbb_, sb0, nbs;
-        ivf_slice(G.nb, world, c->rank, sbb_, sb0, nbs);
-        // (lane's scratch and block buffers: group g - 2's back half is behind on this stream, its exchange was waited for there)
-        if ((rc = ivf_shard_front(h, lane, queries_dev + (size_t)G.b0 * B * vs::kDim, G.nb, G.sbb, sb0, nbs, B, k, nprobe, c->d_blk[lane], user)))
-            return rc;
-        HIPCHK(hipEventRecord(c->ev_front[lane], user));
-        HIPCHK(hipStreamWaitEvent(c->s_coll, c->ev_front[lane], 0));
-        NCCLCHK(rccl().AllGather(c->d_blk[lane], c->d_blkg[lane], (size_t)ivf_block_words(G.sbb, nprobe), ncclInt32, c->comm, c->s_coll));
-        HIPCHK(hipEventRecord(c->ev_probe[lane], c->s_coll));
-        if (g >= 1 && (rc = back_and_gather(g - 1))) return rc;
-    }
-    if ((rc = back_and_gather(n_groups - 1))) return rc;
-    for (int lane = 0; lane < 2; ++lane)
-        if (c->coll_used[lane]) HIPCHK(hipStreamWaitEvent(user, c->ev_coll[lane], 0));
-    return order_end(h, user);
+    Shards S;
+    S.hs = {h};
+    S.G = c->world;
+    S.first = c->rank;
+    S.c = c;
+    rc = ivf_sliced_groups(S, queries_dev, n_batches, B, k, nprobe, ids_dev, dists_dev, nullptr, user);
+    return rc ? rc : order_end(h, user);
 }
 
 // Virtual ranks: the cluster-sharded pipeline of vs_ivf_search_dev_sharded for G shards that live on ONE device, driven by
@@ -2849,87 +2787,19 @@ int vs_ivf_search_dev_vshards(vs_index* const* shards, int G, const float* queri
         hipStream_t s = static_cast<hipStream_t>(stream);
         for (int r = 0; r < G; ++r)
             if ((rc = order_begin(shards[r], s))) return rc;
-        const int gb = h0->ivf_gb;
-        const size_t blk_max = (size_t)ivf_block_words(vs::kIvfWideBatches, kMaxNprobe);
-        const size_t loc_max = (size_t)2 * gb * 32 * k;
-        if (h0->vsh_blk.size() < blk_max * G || h0->vsh_loc.size() < loc_max * G) HIPCHK(hipStreamSynchronize(s));
-        if ((rc = h0->vsh_blk.reserve(blk_max * G)) || (rc = h0->vsh_loc.reserve(loc_max * G))) return rc;
-        std::vector<vs::Event> ev;
-        if (rank_ms) {
-            ev.resize((size_t)4 * G);
-            for (auto& e : ev)
-                if ((rc = e.create(true))) return rc;
-            for (int r = 0; r < G; ++r) rank_ms[r] = 0;
-        }
-        for (int b0 = 0; b0 < n_batches && !rc; b0 += gb) {
-            const int nb = std::min(gb, n_batches - b0), sbb = (nb + G - 1) / G;  // (= ivf_slice's)
-            const float* q = queries_dev + (size_t)b0 * B * vs::kDim;
-            const size_t n = (size_t)nb * B, words = 2 * n * k;
-            const long long bw = ivf_block_words(sbb, nprobe);
-            for (int r = 0; r < G && !rc; ++r) {
-                int sbb_, sb0, nbs;
-                ivf_slice(nb, G, r, sbb_, sb0, nbs);
-                if (rank_ms) HIPCHK(hipEventRecord(ev[4 * r], s));
-                rc = ivf_shard_front(shards[r], 0, q, nb, sbb, sb0, nbs, B, k, nprobe, h0->vsh_blk + (size_t)r * bw, s);
-                if (rank_ms) HIPCHK(hipEventRecord(ev[4 * r + 1], s));
-            }
-            for (int r = 0; r < G && !rc; ++r) {
-                float* loc_d = reinterpret_cast<float*>(h0->vsh_loc + (size_t)r * words);
-                int32_t* loc_i = h0->vsh_loc + (size_t)r * words + n * k;
-                if (rank_ms) HIPCHK(hipEventRecord(ev[4 * r + 2], s));
-                rc = ivf_shard_back(shards[r], 0, q, nb, sbb, B, k, nprobe, h0->vsh_blk, loc_d, loc_i, s);
-                if (rank_ms) HIPCHK(hipEventRecord(ev[4 * r + 3], s));
-            }
-            if (rc) break;
-            vs::MergeParams m{};
-            m.part_d = reinterpret_cast<const float*>(h0->vsh_loc.get());
-            m.part_i = h0->vsh_loc + n * k;
-            m.G = G;
-            m.kin = k;
-            m.nq = (int)n;
-            m.kout = k;
-            m.out_d = dists_dev + (size_t)b0 * B * k;
-            m.out_i = ids_dev + (size_t)b0 * B * k;
-            HIPCHK(vs::launch_merge_layout(m, (int64_t)words, k, s));
-            if (rank_ms) {
-                HIPCHK(hipStreamSynchronize(s));
-                for (int r = 0; r < G; ++r) {
-                    float a = 0, b = 0;
-                    HIPCHK(hipEventElapsedTime(&a, ev[4 * r], ev[4 * r + 1]));
-                    HIPCHK(hipEventElapsedTime(&b, ev[4 * r + 2], ev[4 * r + 3]));
-                    rank_ms[r] += a + b;
-                }
-            }
-        }
-        return rc;
+        Shards S;
+        S.hs.assign(shards, shards + G);
+        S.G = G;
+        return ivf_sliced_groups(S, queries_dev, n_batches, B, k, nprobe, ids_dev, dists_dev, rank_ms, s);
     });
 }
 
-// Host-buffer forms of the sharded searches (what the CLIs call with --gpus N): every rank passes the same queries and
-// receives the same merged result.  Chunks of kMaxMulti batches: upload, vs_*_search_dev_sharded, download.
 }  // extern "C"
 
 namespace {
 
-// ---- brute force on host buffers, the reference's answer out (cpu_baseline.cpp:127-153 tie order included), over row shards.
-// The shards this process drives are either ONE shard of a collective job (comm: the other ranks run the same code, the
-// exchanges are RCCL all-gathers) or ALL G shards on one device (virtual ranks: an exchange is a no-op, every shard has
-// written its part of the gathered buffer in place).  Everything else -- per-shard device steps, merge, host replay -- is
-// the same code.  Shards are contiguous row ranges in rank order (vs_bf_create(rows of the shard, id_offset = first row)).
-// vs_bf_search / vs_bf_search_topk are one index (G = 1, no communicator) without the merge.
-struct BfShards {
-    std::vector<vs_index*> hs;  // the shards driven here; hs[i] is global shard first + i
-    int G = 1, first = 0;
-    vs_comm* c = nullptr;
-    bool merge = true;          // the shards' lists go through the exchange and the merge (every sharded call, G = 1 included)
-    vs_index* owner() const { return hs[0]; }
-    hipStream_t s() const { return hs[0]->stream; }
-    int exchange(int32_t* buf, size_t words) const {  // buf = [G][words], this process's parts in place
-        if (!c || c->world == 1) return VS_OK;
-        NCCLCHK(rccl().AllGather(buf + (size_t)c->rank * words, buf, words, ncclInt32, c->comm, s()));
-        return VS_OK;
-    }
-};
+// ---- brute force on host buffers, the reference's answer out (cpu_baseline.cpp:127-153 tie order included), over the row
+// shards of a Shards.
 
 constexpr size_t kShPackWords = 32 + (size_t)2 * 32 * kTieCap;  // filter output of one shard: cnt [32] | rows [32][kTieCap] | dists [32][kTieCap]
 
@@ -2960,7 +2830,7 @@ int sh_reserve(vs_index* o, int G, size_t lists_words, int64_t L0p, int64_t ldm,
 // k-th smallest of them bounds the buffer maximum for every later row of every shard, each shard emits its rows under that
 // bound in ONE filtered pass (about N * k / L0 of them), and the host replays "dense rows, then the shards' candidates in row
 // order".  Exact whenever the distances are (integer-valued SIFT: always).
-int resolve_ties_shards(const BfShards& S, const std::vector<int32_t>& meta /*[G][2] rows, id_offset*/, const float* queries_host,
+int resolve_ties_shards(const Shards& S, const std::vector<int32_t>& meta /*[G][2] rows, id_offset*/, const float* queries_host,
                         const std::vector<int64_t>& flagged, int k, int32_t* ids, float* dists) {
     vs_index* o = S.owner();
     hipStream_t st = S.s();
@@ -3027,7 +2897,7 @@ int resolve_ties_shards(const BfShards& S, const std::vector<int32_t>& meta /*[G
                 }
             }
         }
-        if ((rc = S.exchange(Bf.tau, 32)) || (rc = S.exchange(Bf.dense, (size_t)32 * L0p))) return rc;
+        if ((rc = S.exchange(Bf.tau, 32, st)) || (rc = S.exchange(Bf.dense, (size_t)32 * L0p, st))) return rc;
         for (size_t i = 0; i < S.hs.size(); ++i) {
             vs_index* h = S.hs[i];
             const int g = S.first + (int)i;
@@ -3055,7 +2925,7 @@ int resolve_ties_shards(const BfShards& S, const std::vector<int32_t>& meta /*[G
             p.tiles_per_wg = tp;
             HIPCHK(vs::launch_scan(p, grid, 8, 2, vs::kModeFilter, st));
         }
-        if ((rc = S.exchange(Bf.pack, kShPackWords))) return rc;
+        if ((rc = S.exchange(Bf.pack, kShPackWords, st))) return rc;
         HIPCHK(hipMemcpyAsync(dense, dense0, (size_t)B * L0p * sizeof(float), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpy2DAsync(cnt, 32 * 4, Bf.pack, kShPackWords * 4, 32 * 4, G, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -3140,7 +3010,7 @@ int resolve_ties_shards(const BfShards& S, const std::vector<int32_t>& meta /*[G
                                      reinterpret_cast<float*>(Bf.row + (size_t)g * ldm), ldm, st)))
                     return rc;
             }
-            if ((rc = S.exchange(Bf.row, (size_t)ldm))) return rc;
+            if ((rc = S.exchange(Bf.row, (size_t)ldm, st))) return rc;
             row.resize((size_t)total);
             int64_t at = 0;
             for (int g = 0; g < G; ++g) {
@@ -3155,7 +3025,7 @@ int resolve_ties_shards(const BfShards& S, const std::vector<int32_t>& meta /*[G
     return VS_OK;
 }
 
-int bf_search_shards(const BfShards& S, const float* queries_host, int64_t nq, int k, int32_t* ids, float* dists, vs_timing* timing) {
+int bf_search_shards(const Shards& S, const float* queries_host, int64_t nq, int k, int32_t* ids, float* dists, vs_timing* timing) {
     vs_index* o = S.owner();
     hipStream_t st = S.s();
     const int G = S.G;
@@ -3180,7 +3050,7 @@ int bf_search_shards(const BfShards& S, const float* queries_host, int64_t nq, i
     }
     if (S.c && S.c->world > 1) {
         HIPCHK(hipMemcpyAsync(Bf.meta + 2 * S.first, &meta[2 * S.first], 2 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if ((rc = S.exchange(Bf.meta, 2))) return rc;
+        if ((rc = S.exchange(Bf.meta, 2, st))) return rc;
         HIPCHK(hipMemcpyAsync(meta.data(), Bf.meta, meta.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
@@ -3196,7 +3066,7 @@ int bf_search_shards(const BfShards& S, const float* queries_host, int64_t nq, i
                                st, force_f32);
             if (r2) return r2;
         }
-        if (int r2 = S.exchange(Bf.lists, words)) return r2;
+        if (int r2 = S.exchange(Bf.lists, words, st)) return r2;
         vs::MergeParams m{};
         m.part_d = reinterpret_cast<const float*>(Bf.lists);
         m.part_i = Bf.lists + np * k1;
@@ -3312,6 +3182,126 @@ int bf_search_shards(const BfShards& S, const float* queries_host, int64_t nq, i
     return VS_OK;
 }
 
+// ---- IVF on host buffers (vs_ivf_search; vs_ivf_search_sharded: c = the communicator).  Queries go through in chunks (the
+// harness loop of main_ivf.cpp:150-214 collapsed into a call): a chunk is ONE upload, its launch step, ONE download -- the
+// host, not the device, is the limit of this call (a hipMemcpyAsync costs about as much host time as a launch group's five
+// launches).  Two chunks in flight; at least two chunks per call where there is enough work, so that the second upload runs
+// beside the first chunk's kernels.  The launch step deals the chunk's launch groups to the two lanes' streams, a ragged
+// tail batch in a group of its own; sharded, it is the device-sharded search on the index's stream, for the chunk's full
+// batches and then for its ragged tail.  The chunks depend on nq, batch, ivf_gb and ivf_host_cap only: every rank issues
+// the same collectives in the same order.
+int ivf_search_host(vs_index* h, vs_comm* c, const float* queries_host, int64_t nq, int k, int nprobe, int32_t* ids, float* dists,
+                    int64_t* total_candidates, vs_timing* timing) {
+    int rc = set_device(h);
+    if (rc) return rc;
+    const double t_start = now_ms();
+    vs_timing tm{};
+    if ((rc = ensure_pipe(h)) || (rc = ensure_wide_streams(h)) || (rc = ensure_ivf_host(h)) || (rc = order_begin(h, h->stream))) return rc;
+    settle_slots(h->ihs, {h->stream, h->wide_stream[0], h->wide_stream[1], h->s_h2d, h->s_d2h, c ? c->s_coll : h->stream});
+    h->stage_on = !c;  // (the sharded call has no stage split)
+    h->stage_used = 0;
+    HIPCHK(hipMemsetAsync(h->d_cand, 0, sizeof(unsigned long long), h->stream));
+    const float inf = std::numeric_limits<float>::infinity();
+    const bool wide = ivf_wide_ok(h, k);
+    HIPCHK(hipEventRecord(h->wide_fork, h->stream));  // (behind the memset above)
+    for (int i = 0; i < 2; ++i) HIPCHK(hipStreamWaitEvent(h->wide_stream[i], h->wide_fork, 0));
+    const int64_t unit_q = (int64_t)vs::kIvfWideBatches * h->batch;  // a super-batch of queries: chunks are cut at these
+    const int64_t cap_q = h->ivf_host_cap / unit_q * unit_q;
+    const int64_t wchunk = std::min<int64_t>(cap_q, std::max<int64_t>(unit_q, (nq / 2 + unit_q - 1) / unit_q * unit_q));
+    const int64_t group_q = c ? wchunk : (int64_t)h->ivf_gb * h->batch;  // queries per launch step
+    auto lane_stream = [&](int lane) -> hipStream_t { return c ? static_cast<hipStream_t>(h->stream) : static_cast<hipStream_t>(h->wide_stream[lane]); };
+    int next_lane = 0;
+    auto enqueue = [&](vs_index::IvfHostSlot& S, int64_t q0, int64_t n) -> int {
+        const double t0 = now_ms();
+        S.q0 = q0;
+        S.n = n;
+        std::memcpy(S.pin_q, queries_host + q0 * vs::kDim, (size_t)n * vs::kDim * sizeof(float));
+        HIPCHK(hipMemcpyAsync(S.d_q, S.pin_q, (size_t)n * vs::kDim * sizeof(float), hipMemcpyHostToDevice, h->s_h2d));
+        HIPCHK(hipEventRecord(S.ev_h2d, h->s_h2d));
+        tm.h2d_ms += now_ms() - t0;
+        float* od = S.d_out;
+        int32_t* oi = reinterpret_cast<int32_t*>(S.d_out + (size_t)n * k);
+        bool used[2] = {false, false};
+        for (int64_t g0 = 0; g0 < n; g0 += group_q) {
+            const int64_t gn = std::min<int64_t>(group_q, n - g0);
+            const int full = (int)(gn / h->batch), rem = (int)(gn % h->batch);
+            const int lane = wide && !c ? next_lane : 0;
+            next_lane ^= 1;
+            const hipStream_t cs = lane_stream(lane);
+            if (!used[lane]) HIPCHK(hipStreamWaitEvent(cs, S.ev_h2d, 0));
+            used[lane] = true;
+            int r2 = VS_OK;
+            auto run = [&](size_t o, int nb, int B) -> int {
+                const float* q = S.d_q + o * vs::kDim;
+                if (c) return vs_ivf_search_dev_sharded(h, c, q, nb, B, k, nprobe, oi + o * k, od + o * k, cs);
+                if (wide) return ivf_group_wide_dev(h, lane, q, nb, B, k, nprobe, od + o * k, oi + o * k, cs);
+                int r3 = VS_OK;
+                for (int b = 0; b < nb && !r3; ++b)
+                    r3 = ivf_fallback_batch_dev(h, q + (size_t)b * B * vs::kDim, B, k, nprobe, od + (o + (size_t)b * B) * k,
+                                                oi + (o + (size_t)b * B) * k, cs);
+                return r3;
+            };
+            if (full) r2 = run((size_t)g0, full, h->batch);
+            if (!r2 && rem) r2 = run((size_t)g0 + (size_t)full * h->batch, 1, rem);  // the call's ragged tail
+            if (r2) return r2;
+        }
+        for (int lane = 0; lane < 2; ++lane)
+            if (used[lane]) {
+                HIPCHK(hipEventRecord(S.ev_comp[lane], lane_stream(lane)));
+                HIPCHK(hipStreamWaitEvent(h->s_d2h, S.ev_comp[lane], 0));
+            }
+        HIPCHK(hipMemcpyAsync(S.pin_out, S.d_out, (size_t)n * k * 2 * sizeof(float), hipMemcpyDeviceToHost, h->s_d2h));
+        HIPCHK(hipEventRecord(S.ev_d2h, h->s_d2h));
+        return VS_OK;
+    };
+    auto retire = [&](vs_index::IvfHostSlot& S) -> int {
+        if (S.q0 < 0) return VS_OK;
+        const double t0 = now_ms();
+        HIPCHK(hipEventSynchronize(S.ev_d2h));
+        tm.d2h_ms += now_ms() - t0;
+        const float* hd = S.pin_out;
+        const int32_t* hi = reinterpret_cast<const int32_t*>(S.pin_out + (size_t)S.n * k);
+        for (int64_t i = 0; i < S.n * k; ++i) {
+            const int32_t id = hi[i];
+            ids[S.q0 * k + i] = id;
+            dists[S.q0 * k + i] = id >= 0 ? (h->metric == VS_METRIC_IP ? -hd[i] : hd[i]) : inf;  // (IP: the score q.v, as IVFIndex returns it)
+        }
+        S.q0 = -1;
+        return VS_OK;
+    };
+    int ci = 0;
+    for (int64_t q0 = 0; q0 < nq; q0 += wchunk, ++ci) {
+        vs_index::IvfHostSlot& S = h->ihs[ci & 1];
+        if ((rc = retire(S))) return rc;
+        if ((rc = enqueue(S, q0, std::min<int64_t>(wchunk, nq - q0)))) return rc;
+    }
+    if ((rc = retire(h->ihs[ci & 1]))) return rc;
+    if ((rc = retire(h->ihs[(ci + 1) & 1]))) return rc;
+    for (int i = 0; i < 2; ++i) {  // the index's stream continues behind the lanes
+        HIPCHK(hipEventRecord(h->wide_join[i], h->wide_stream[i]));
+        HIPCHK(hipStreamWaitEvent(h->stream, h->wide_join[i], 0));
+    }
+    unsigned long long cand = 0;  // (sharded: the rows THIS rank scanned, IVFIndex::searchBatch's return value per shard)
+    HIPCHK(hipMemcpyAsync(&cand, h->d_cand, sizeof(cand), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (total_candidates) *total_candidates = (int64_t)cand;
+    tm.total_ms = now_ms() - t_start;
+    // SearchTiming split (IVFIndex.h:31-36): device time of the three stages from the events between their launches,
+    // summed over the call's launch groups (uploads and downloads overlap them)
+    for (int i = 0; i + 3 < h->stage_used; i += 4) {
+        float ms[3] = {0, 0, 0};
+        for (int j = 0; j < 3; ++j) (void)hipEventElapsedTime(&ms[j], h->stage_ev[i + j], h->stage_ev[i + j + 1]);
+        tm.centroid_search_ms += ms[0];
+        tm.gather_ms += ms[1];
+        tm.fine_search_ms += ms[2];
+    }
+    if (c) tm.fine_search_ms = tm.total_ms;
+    h->stage_on = false;
+    h->stage_used = 0;
+    if (timing) *timing = tm;
+    return order_end(h, h->stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -3330,7 +3320,7 @@ int vs_bf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int3
             return VS_ERR_UNSUPPORTED;
         }
         if ((rc = order_begin(h, h->stream))) return rc;
-        BfShards S;
+        Shards S;
         S.hs = {h};
         S.merge = false;
         return bf_search_shards(S, queries_host, nq, k, ids, dists, timing);
@@ -3352,7 +3342,7 @@ int vs_bf_search_topk(vs_index* h, const float* queries_host, int64_t nq, int k,
         if (rc) return rc;
         if (g_topw_stats) g_topw_st = TopwStats{};
         if ((rc = order_begin(h, h->stream))) return rc;
-        BfShards S;
+        Shards S;
         S.hs = {h};
         S.merge = false;
         vs_timing tm{};
@@ -3384,7 +3374,7 @@ int vs_bf_search_sharded(vs_index* h, vs_comm* c, const float* queries_host, int
         int rc = set_device(h);
         if (rc) return rc;
         if ((rc = order_begin(h, h->stream))) return rc;
-        BfShards S;
+        Shards S;
         S.hs = {h};
         S.G = c->world;
         S.first = c->rank;
@@ -3411,7 +3401,7 @@ int vs_bf_search_vshards(vs_index* const* shards, int G, const float* queries_ho
     return guarded([&]() -> int {
         int rc = set_device(shards[0]);
         if (rc) return rc;
-        BfShards S;
+        Shards S;
         S.hs.assign(shards, shards + G);
         S.G = G;
         for (int g = 0; g < G; ++g)
@@ -3420,50 +3410,31 @@ int vs_bf_search_vshards(vs_index* const* shards, int G, const float* queries_ho
     });
 }
 
+int vs_ivf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int nprobe, int32_t* ids, float* dists,
+                  int64_t* total_candidates, vs_timing* timing) {
+    if (!h || h->kind != 1 || !queries_host || !ids || !dists || nq < 0 || k < 1 || nprobe < 1) {
+        set_error("vs_ivf_search: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    nprobe = std::min(nprobe, h->nlist);
+    if (nprobe > kMaxNprobe) {
+        set_error("nprobe > 256 not supported");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (k > 64) {
+        set_error("k > 64 not supported by the host-buffer API");
+        return VS_ERR_UNSUPPORTED;
+    }
+    return guarded([&] { return ivf_search_host(h, nullptr, queries_host, nq, k, nprobe, ids, dists, total_candidates, timing); });
+}
+
 int vs_ivf_search_sharded(vs_index* h, vs_comm* c, const float* queries_host, int64_t nq, int k, int nprobe, int32_t* ids,
                           float* dists, int64_t* total_candidates, vs_timing* timing) {
     if (!h || !c || h->kind != 1 || !queries_host || !ids || !dists || nq < 0 || k < 1 || k > 16 || nprobe < 1) {
         set_error("vs_ivf_search_sharded: bad arguments");
         return VS_ERR_INVALID;
     }
-    return guarded([&]() -> int {
-        int rc = set_device(h);
-        if (rc) return rc;
-        const double t_start = now_ms();
-        vs_timing tm{};
-        HIPCHK(hipMemsetAsync(h->d_cand, 0, sizeof(unsigned long long), h->stream));
-        const int64_t chunk = (int64_t)kMaxMulti * h->batch;
-        std::vector<float> hd((size_t)chunk * k);
-        std::vector<int32_t> hi((size_t)chunk * k);
-        const float inf = std::numeric_limits<float>::infinity();
-        for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
-            const int64_t n = std::min<int64_t>(chunk, nq - q0);
-            const int full = (int)(n / h->batch), rem = (int)(n % h->batch);
-            HIPCHK(hipMemcpyAsync(h->d_q, queries_host + q0 * vs::kDim, (size_t)n * vs::kDim * sizeof(float), hipMemcpyHostToDevice, h->stream));
-            if (full && (rc = vs_ivf_search_dev_sharded(h, c, h->d_q, full, h->batch, k, nprobe, h->d_out_i, h->d_out_d, h->stream))) return rc;
-            if (rem) {
-                const size_t o = (size_t)full * h->batch;
-                if ((rc = vs_ivf_search_dev_sharded(h, c, h->d_q + o * vs::kDim, 1, rem, k, nprobe, h->d_out_i + o * k, h->d_out_d + o * k,
-                                                    h->stream)))
-                    return rc;
-            }
-            HIPCHK(hipMemcpyAsync(hd.data(), h->d_out_d, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipMemcpyAsync(hi.data(), h->d_out_i, (size_t)n * k * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            for (int64_t b = 0; b < n; ++b)
-                for (int t = 0; t < k; ++t) {
-                    const int32_t id = hi[(size_t)b * k + t];
-                    ids[(q0 + b) * k + t] = id;
-                    dists[(q0 + b) * k + t] = id >= 0 ? hd[(size_t)b * k + t] : inf;
-                }
-        }
-        unsigned long long cand = 0;  // rows THIS rank scanned (IVFIndex::searchBatch's return value, per shard)
-        HIPCHK(hipMemcpy(&cand, h->d_cand, sizeof(cand), hipMemcpyDeviceToHost));
-        if (total_candidates) *total_candidates = (int64_t)cand;
-        tm.total_ms = tm.fine_search_ms = now_ms() - t_start;
-        if (timing) *timing = tm;
-        return VS_OK;
-    });
+    return guarded([&] { return ivf_search_host(h, c, queries_host, nq, k, nprobe, ids, dists, total_candidates, timing); });
 }
 
 }  // extern "C"

@@ -336,8 +336,9 @@ VS_API int vs_ivf_search_dev_sharded(vs_index* h, vs_comm* c, const float* queri
  * group g + 1.  Indexes with nlist > 4096 or fewer lists than ranks run the whole pipeline per rank (one all-gather).
  *
  * Virtual ranks: the same pipeline for G shards (vs_ivf_create / vs_ivf_load with rank r, world G) on ONE device, driven
- * by the calling thread, the collectives replaced by writing into the gathered layout.  For tests and for measuring
- * a rank's cost per launch group on one GPU: rank_ms[r] (optional, G doubles) = device time of rank r's two halves. */
+ * by the calling thread, the collectives no-ops (every shard writes its part of the gathered layout).  For tests and
+ * for measuring a rank's cost per launch group on one GPU: rank_ms[r] (optional, G doubles) = device time of rank r's
+ * two halves. */
 /* Host-side arithmetic of the sliced pipeline (no device needed).  vs_ivf_shard_group: batches per launch group of an index
  * created with `world`.  vs_ivf_shard_slice: a group of n_batches batches is cut into `world` slices of *slice_batches
  * batches (the last ones may be short or empty); rank's own slice is [*first_batch, *first_batch + *own_batches).
@@ -356,7 +357,8 @@ VS_API int vs_ivf_search_dev_vshards(vs_index* const* shards, int G, const float
  * smallest distance bounds select_topk's buffer maximum for every later row, every shard filters its rows under that
  * bound, the candidates are exchanged (all-gathers of fixed-size buffers) and every rank replays the slots over "dense
  * rows, then candidates in row order".  Shards must be contiguous row ranges in rank order.
- * IVF: *total_candidates = rows scanned by THIS rank's shard.
+ * IVF: vs_ivf_search's chunk pipeline (the same chunks, timing fields and inner-product sign) with the device-sharded
+ * search as its launch step; *total_candidates = rows scanned by THIS rank's shard.
  * vs_bf_search_vshards: the brute-force call for G shards on ONE device, driven by the calling thread (no collective):
  * tests of the sharded tie order without a multi-GPU node. */
 VS_API int vs_bf_search_sharded(vs_index* h, vs_comm* c, const float* queries_host, int64_t nq, int k, int32_t* ids,

@@ -496,6 +496,11 @@ def test_library_collective_world_1_ivf(gpu_pkg):
         ids, d, total = ivf.searchBatch(q[:200], 200, k, nprobe)
         sid, sd, stotal = ivf.searchBatch_sharded(comm, q[:200], k, nprobe)
         assert np.array_equal(sd, d) and stotal == total
+        # inner product: both host calls return the score q.v (the device ranks by -q.v); all queries = two chunks
+        ivf.set_metric(1)
+        ids, d, total = ivf.searchBatch(q, len(q), k, nprobe)
+        sid, sd, stotal = ivf.searchBatch_sharded(comm, q, k, nprobe)
+        assert np.array_equal(sd, d) and stotal == total
 
 
 def test_native_index_builder_end_to_end(gpu_pkg, tmp_path):
