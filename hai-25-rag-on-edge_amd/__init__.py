@@ -172,6 +172,7 @@ def lib():
         "vs_q8_search": (i32, [vp, vp, i64, i32, vp, vp]),
         "vs_prof_enable": (i32, [vp, i32]),
         "vs_prof_read": (i32, [vp, i32, C.POINTER(C.c_double), C.POINTER(i64)]),
+        "vs_ivf_widek_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_prof_read_launches": (i32, [vp, i32, vp, i64, C.POINTER(i64)]),
         "vs_index_rows": (i64, [vp]),
         "vs_index_dim": (i32, [vp]),
@@ -560,6 +561,13 @@ class IVFIndex(_Index):
                            dists_ptr: int, stream: int):
         """Collective: this rank's lists + ONE RCCL all-gather of top-k lists per launch group + device merge."""
         _check(lib().vs_ivf_search_dev_sharded(self._h, comm._c, q_ptr, n_batches, B, k, nprobe, ids_ptr, dists_ptr, stream))
+
+    def widek_stats(self, reset: bool = False):
+        """Wide-k (17 <= k <= 128) diagnostics, collected when VSEARCH_IVF_WIDEK_STATS=1 was set at the index's first
+        such call: (candidates ranked, most candidates of one query, queries ranked exactly, overflowed launch groups)."""
+        out = (C.c_int64 * 4)()
+        _check(lib().vs_ivf_widek_stats(self._h, out, 1 if reset else 0))
+        return tuple(int(v) for v in out)
 
     def set_metric(self, metric: int):
         """0 = squared L2 (the north-star's), 1 = inner product (the reference's own ranking, IVFIndex.cpp:449-496)."""

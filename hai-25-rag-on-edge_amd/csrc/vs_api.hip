@@ -56,6 +56,9 @@ constexpr int kWideSub = 16;      // sub-lists per query of the streaming scans'
 constexpr int kWideCap = 128;     // entries per sub-list (2048 per query; more: the per-batch scan behind takes over)
 constexpr int kIvfWideWaveCap = 512;  // entries per wave buffer of the wide IVF scan (expected fill: a few dozen per group)
 constexpr int kIvfWideSubCap = 256;   // entries per candidate sub-list (16 per query: 4096 candidates)
+// wide k (17 <= k <= 128): candidates per query grow about in proportion to k (DESIGN.md 4.6b has the measured fill)
+constexpr int kIvfWideKWaveCap = 32768;  // entries per wave buffer (more in one wave: the group is ranked exactly)
+constexpr int kIvfWideKSubCap = 1024;   // entries per candidate sub-list (more: the query is ranked exactly)
 constexpr int kTieDense = 4096;   // rows whose distances the tie resolver takes densely
 constexpr int kTieCap = 8192;     // candidate slots per flagged query (more: full-row fallback)
 constexpr int kTopwFilterCap = 8192;  // filter candidates per query of the wide-k launcher (more: the dense fallback)
@@ -207,6 +210,18 @@ struct vs_index {
         long long slab_stride = 0, off_scores = 0;
         bool ready = false;         // every buffer above allocated (ensure_ivf_wide)
     } wide[kWideLanesMax];          // scratch sets: consecutive launch groups of one call run on different streams
+    // wide k (17 <= k <= 128), per lane beside `wide`, allocated on the first such call: the segments' distances, their k
+    // smallest, a larger candidate sink
+    struct IvfWideK {
+        vs::DevBuf<float> tk;        // [group queries][kBoundSegs][kIvfTauRows] (+inf between groups)
+        vs::DevBuf<float> kth_d;     // [group queries][128]
+        vs::DevBuf<int32_t> kth_i;
+        vs::DevBuf<int4> wbuf;       // [waves][kIvfWideKWaveCap]
+        vs::DevBuf<float> cand_d;    // [group queries][16][kIvfWideKSubCap]
+        vs::DevBuf<int32_t> cand_i;
+        bool ready = false;          // every buffer above allocated (ensure_ivf_widek)
+    } widek[kWideLanesMax];
+    vs::DevBuf<unsigned long long> widek_stats;  // [4] (VSEARCH_IVF_WIDEK_STATS=1 only): see vs_ivf_widek_stats
     vs::Stream wide_stream[kWideLanesMax];
     vs::Event wide_fork, wide_join[kWideLanesMax];
     bool wide_streams_ready = false;
@@ -242,6 +257,7 @@ struct vs_index {
         vs::DevBuf<float> d_out;   // same layout on the device
         vs::Event ev_h2d, ev_comp[2], ev_d2h;
         int64_t q0 = -1, n = 0;
+        int out_k = 0;             // results per query the output buffers hold
         bool ready = false;        // every buffer and event above created (ensure_ivf_host)
     } ihs[2];
     // wide-k brute force (k + 1 > 16, topw_launch), allocated on the first such call: distances to the prefix rows, the
@@ -980,7 +996,9 @@ int ivf_group_batches() {
 
 // Is the wide list-major pipeline available for this index?  (nlist <= 4096, rows resident, k <= 16; otherwise the
 // query-major fallback: coarse scores on the MFMA scan kernel, pick_probes, one workgroup per (query, probe).)
-bool ivf_wide_ok(const vs_index* h, int k) { return h->nlist <= vs::kIvfFastNlist && h->n_chunks > 0 && pick_kcap(k) != 0; }
+bool ivf_wide_ok(const vs_index* h, int k) {
+    return h->nlist <= vs::kIvfFastNlist && h->n_chunks > 0 && k >= 1 && k <= vs::kIvfWideKMax;
+}
 
 // Query-major fallback for one batch (nlist > 4096, or a shard without resident rows).
 int ivf_fallback_batch_dev(vs_index* h, const float* q_dev, int B, int k, int nprobe, float* out_d, int32_t* out_i, hipStream_t s) {
@@ -1062,6 +1080,29 @@ int ensure_ivf_wide(vs_index* h, int lane) {
     if ((rc = W.slab.alloc((size_t)W.slab_stride * h->ivf_gb))) return rc;
     W.ready = true;
     h->wide[lane] = std::move(W);
+    return VS_OK;
+}
+
+// Wide-k scratch of one lane (beside ensure_ivf_wide's): built in a local set, so that a failure part way frees what it
+// allocated, and moved in when complete.
+int ensure_ivf_widek(vs_index* h, int lane) {
+    if (h->widek[lane].ready) return VS_OK;
+    vs_index::IvfWideK K;
+    const size_t nq = (size_t)h->ivf_gb * 32;
+    const size_t tk_words = nq * vs::kBoundSegs * vs::kIvfTauRows;
+    int rc;
+    if ((rc = K.tk.alloc(tk_words)) || (rc = K.kth_d.alloc(nq * vs::kIvfWideKMax)) || (rc = K.kth_i.alloc(nq * vs::kIvfWideKMax)) ||
+        (rc = K.wbuf.alloc((size_t)h->wide[lane].n_waves * kIvfWideKWaveCap)) || (rc = K.cand_d.alloc(nq * kWideSub * kIvfWideKSubCap)) ||
+        (rc = K.cand_i.alloc(nq * kWideSub * kIvfWideKSubCap)))
+        return rc;
+    HIPCHK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(K.tk.get()), 0x7f800000, tk_words));  // +inf
+    static const bool stats = getenv("VSEARCH_IVF_WIDEK_STATS") && atoi(getenv("VSEARCH_IVF_WIDEK_STATS"));  // (diagnostic knob)
+    if (stats && !h->widek_stats) {
+        if ((rc = h->widek_stats.alloc(4))) return rc;
+        HIPCHK(hipMemset(h->widek_stats, 0, 4 * sizeof(unsigned long long)));
+    }
+    K.ready = true;
+    h->widek[lane] = std::move(K);
     return VS_OK;
 }
 
@@ -1210,7 +1251,48 @@ int wide_scan_rank(vs_index* h, vs_index::IvfWide& W, const vs::IvfWideParams& w
 // also prepares the byte queries) + pick (also fills the lists' slot tables), bounds and plan in one launch, ONE list-major
 // pass per super-batch of 32 batches with candidates to the sink (binned by the scan's own waves), and the ranking launch
 // (merge, or the exact slow path for queries without a bound / for everybody if a candidate buffer overflowed).
+// The same for 17 <= k <= 128: coarse + pick as above; bounds + plan with the segments' distances stored, their k-th
+// (topk_wide_kernel) as the bound; the scan reading those bounds into the wide-k sink; the wide-k ranking.
+int ivf_group_widek_dev(vs_index* h, int lane, const float* q_dev, int nb, int B, int k, int nprobe, float* out_d, int32_t* out_i,
+                        hipStream_t s) {
+    int rc;
+    if ((rc = ensure_ivf_wide(h, lane)) || (rc = ensure_ivf_widek(h, lane))) return rc;
+    vs_index::IvfWide& W = h->wide[lane];
+    vs_index::IvfWideK& K = h->widek[lane];
+    if (W.dirty) {  // (a failed call may also have left segment distances behind)
+        HIPCHK(hipMemsetAsync(W.zero, 0, W.zero_words * sizeof(int32_t), s));
+        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(K.tk.get()), 0x7f800000, (size_t)h->ivf_gb * 32 * vs::kBoundSegs * vs::kIvfTauRows, s));
+    }
+    W.dirty = true;
+    const int sbb = vs::kIvfWideBatches;
+    const vs::IvfGroup grp = wide_group(h, W, sbb, B);
+    vs::IvfWideParams wp = wide_params(h, W, q_dev, nb, sbb, B, k, nprobe, out_d, out_i);
+    wp.tau_inline = 0;  // (the scan reads tau / slow)
+    wp.tk = K.tk;
+    wp.sink.wbuf = K.wbuf;
+    wp.sink.wcap = kIvfWideKWaveCap;
+    wp.sink.cand_d = K.cand_d;
+    wp.sink.cand_i = K.cand_i;
+    wp.sink.cap = kIvfWideKSubCap;
+    stage_mark(h, 0, s);
+    HIPCHK(vs::launch_ivf_coarse_pick(q_dev, B, h->d_centroids, h->d_cnorm, h->nlist, nprobe, h->metric,
+                                      reinterpret_cast<float*>(W.slab + W.off_scores), (h->nlist + 63) & ~63,
+                                      reinterpret_cast<int32_t*>(W.slab.get()), grp, s, nb));
+    stage_mark(h, 1, s);
+    HIPCHK(vs::launch_ivf_widek_bounds_plan(wp, K.kth_d, K.kth_i, s));
+    stage_mark(h, 2, s);
+    prof_begin(h, 1, s);
+    HIPCHK(vs::launch_ivf_wide_scan(wp, h->num_cus, s));
+    prof_end(h, 1, s);
+    const int32_t* id_map = (wp.vecs_t8 && h->d_r2o_t) ? h->d_r2o_t : h->d_r2o;  // (as wide_scan_rank: padded rows on the byte path)
+    HIPCHK(vs::launch_ivf_widek_rank(wp, id_map, h->widek_stats.get(), s));
+    W.dirty = false;
+    stage_mark(h, 3, s);
+    return VS_OK;
+}
+
 int ivf_group_wide_dev(vs_index* h, int lane, const float* q_dev, int nb, int B, int k, int nprobe, float* out_d, int32_t* out_i, hipStream_t s) {
+    if (k > 16) return ivf_group_widek_dev(h, lane, q_dev, nb, B, k, nprobe, out_d, out_i, s);
     int rc = ensure_ivf_wide(h, lane);
     if (rc) return rc;
     vs_index::IvfWide& W = h->wide[lane];
@@ -1341,15 +1423,19 @@ int ensure_wide_streams(vs_index* h) {
     return VS_OK;
 }
 
-int ensure_ivf_host(vs_index* h) {
+// k: the call's (the output buffers hold 64 results per query, 128 from the first call with k > 64 on)
+int ensure_ivf_host(vs_index* h, int k = 0) {
     int rc;
     h->ivf_host_cap = std::max<int64_t>(kIvfHostChunk, (int64_t)h->ivf_gb * 32);
     const size_t cap = (size_t)h->ivf_host_cap;
     for (auto& slot : h->ihs) {
-        if (slot.ready) continue;
+        if (slot.ready && k <= slot.out_k) continue;
+        if (slot.ready) HIPCHK(hipDeviceSynchronize());  // (growing: a failed call's copies may still use the old buffers)
         vs_index::IvfHostSlot S;
-        if ((rc = S.pin_q.alloc(cap * vs::kDim)) || (rc = S.pin_out.alloc(cap * 64 * 2)) || (rc = S.d_q.alloc(cap * vs::kDim)) ||
-            (rc = S.d_out.alloc(cap * 64 * 2)) || (rc = S.ev_h2d.create()) || (rc = S.ev_comp[0].create()) || (rc = S.ev_comp[1].create()) ||
+        S.out_k = std::max(k > 64 ? vs::kIvfWideKMax : 64, slot.ready ? slot.out_k : 0);
+        const size_t out = cap * S.out_k * 2;
+        if ((rc = S.pin_q.alloc(cap * vs::kDim)) || (rc = S.pin_out.alloc(out)) || (rc = S.d_q.alloc(cap * vs::kDim)) ||
+            (rc = S.d_out.alloc(out)) || (rc = S.ev_h2d.create()) || (rc = S.ev_comp[0].create()) || (rc = S.ev_comp[1].create()) ||
             (rc = S.ev_d2h.create()))
             return rc;
         S.ready = true;
@@ -1363,6 +1449,11 @@ int ensure_ivf_host(vs_index* h) {
 // kernels fill the device beside the current group's scan and ranking)
 int ivf_multi_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int nprobe, float* out_d, int32_t* out_i, hipStream_t user) {
     int rc = VS_OK;
+    if (k > vs::kIvfWideKMax || (k > 16 && !ivf_wide_ok(h, k))) {
+        set_error(k > vs::kIvfWideKMax ? "k > 128 not supported"
+                                       : "k > 16 needs the list-major IVF pipeline (nlist <= 4096, rows resident)");
+        return VS_ERR_UNSUPPORTED;
+    }
     if (!ivf_wide_ok(h, k)) {
         for (int b = 0; b < nb && !rc; ++b)
             rc = ivf_fallback_batch_dev(h, q_dev + (size_t)b * B * vs::kDim, B, k, nprobe, out_d + (size_t)b * B * k, out_i + (size_t)b * B * k, user);
@@ -1502,6 +1593,25 @@ int vs_prof_enable(vs_index* h, int on) {
     if (!h) return VS_ERR_INVALID;
     h->prof = on != 0;
     for (auto& ps : h->prof_slot) ps.used = 0;
+    return VS_OK;
+}
+
+int vs_ivf_widek_stats(vs_index* h, int64_t* out, int reset) {
+    if (!h || h->kind != 1 || !out) {
+        set_error("vs_ivf_widek_stats: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    if (!h->widek_stats) {
+        set_error("vs_ivf_widek_stats: no wide-k call since VSEARCH_IVF_WIDEK_STATS=1 was set");
+        return VS_ERR_UNSUPPORTED;
+    }
+    int rc = set_device(h);
+    if (rc) return rc;
+    unsigned long long v[4];
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(v, h->widek_stats, sizeof(v), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; ++i) out[i] = (int64_t)v[i];
+    if (reset) HIPCHK(hipMemset(h->widek_stats, 0, sizeof(v)));
     return VS_OK;
 }
 
@@ -3196,7 +3306,7 @@ int ivf_search_host(vs_index* h, vs_comm* c, const float* queries_host, int64_t 
     if (rc) return rc;
     const double t_start = now_ms();
     vs_timing tm{};
-    if ((rc = ensure_pipe(h)) || (rc = ensure_wide_streams(h)) || (rc = ensure_ivf_host(h)) || (rc = order_begin(h, h->stream))) return rc;
+    if ((rc = ensure_pipe(h)) || (rc = ensure_wide_streams(h)) || (rc = ensure_ivf_host(h, k)) || (rc = order_begin(h, h->stream))) return rc;
     settle_slots(h->ihs, {h->stream, h->wide_stream[0], h->wide_stream[1], h->s_h2d, h->s_d2h, c ? c->s_coll : h->stream});
     h->stage_on = !c;  // (the sharded call has no stage split)
     h->stage_used = 0;
@@ -3421,8 +3531,8 @@ int vs_ivf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int
         set_error("nprobe > 256 not supported");
         return VS_ERR_UNSUPPORTED;
     }
-    if (k > 64) {
-        set_error("k > 64 not supported by the host-buffer API");
+    if (k > vs::kIvfWideKMax) {
+        set_error("k > 128 not supported");
         return VS_ERR_UNSUPPORTED;
     }
     return guarded([&] { return ivf_search_host(h, nullptr, queries_host, nq, k, nprobe, ids, dists, total_candidates, timing); });
@@ -3430,9 +3540,13 @@ int vs_ivf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int
 
 int vs_ivf_search_sharded(vs_index* h, vs_comm* c, const float* queries_host, int64_t nq, int k, int nprobe, int32_t* ids,
                           float* dists, int64_t* total_candidates, vs_timing* timing) {
-    if (!h || !c || h->kind != 1 || !queries_host || !ids || !dists || nq < 0 || k < 1 || k > 16 || nprobe < 1) {
+    if (!h || !c || h->kind != 1 || !queries_host || !ids || !dists || nq < 0 || k < 1 || nprobe < 1) {
         set_error("vs_ivf_search_sharded: bad arguments");
         return VS_ERR_INVALID;
+    }
+    if (k > 16) {
+        set_error("k > 16 not supported by the sharded IVF calls");
+        return VS_ERR_UNSUPPORTED;
     }
     return guarded([&] { return ivf_search_host(h, c, queries_host, nq, k, nprobe, ids, dists, total_candidates, timing); });
 }

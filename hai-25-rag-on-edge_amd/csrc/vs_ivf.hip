@@ -4,6 +4,7 @@
 #include "vs_dev.h"
 #include "vs_sink.h"
 #include "vs_merge.h"
+#include "vs_wide_select.h"
 #include <type_traits>
 #include <algorithm>
 
@@ -668,6 +669,9 @@ hipError_t launch_ivf_fill(const int32_t* gathered, long long blk_words, int B, 
 #endif
 constexpr int kBoundParts = VS_BOUND_PARTS;
 constexpr int kBoundLds = kIvfTauRows * kDim + kIvfTauRows * 4 + 4 * 16 * 16 * 4;  // rows | row terms | the waves' lists
+// WIDE (k >= 17): no selection here -- the distances of every (query, segment) entry go to tk as [query][kBoundSegs][kIvfTauRows]
+// (+inf past the list's end), and the bound is selected from them afterwards (see launch_ivf_widek_bounds).
+template <bool WIDE>
 __device__ __forceinline__ void ivf_bounds_list_body(const IvfWideParams& p, const int c, const int part, char* const lds, const int pad_sb) {
     typedef int i32x4 __attribute__((ext_vector_type(4)));
     typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
@@ -790,7 +794,8 @@ __device__ __forceinline__ void ivf_bounds_list_body(const IvfWideParams& p, con
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const float d = p.metric ? -acc[j] : fmaf(-2.0f, acc[j], qn + bn[j]);
-                        v[4 * i + j] = 16 * t + 4 * g + j < rows ? ((f32_ordered(d) & ~0xffu) | (unsigned)(16 * t + 4 * g + j)) : kNone;
+                        if constexpr (WIDE) v[4 * i + j] = __builtin_bit_cast(unsigned, 16 * t + 4 * g + j < rows ? d : VS_INF);  // (the exact distance)
+                        else v[4 * i + j] = 16 * t + 4 * g + j < rows ? ((f32_ordered(d) & ~0xffu) | (unsigned)(16 * t + 4 * g + j)) : kNone;
                     }
                 } else {
 #pragma unroll
@@ -799,6 +804,19 @@ __device__ __forceinline__ void ivf_bounds_list_body(const IvfWideParams& p, con
             }
         }
         BL_STAMP(2);
+        if constexpr (WIDE) {
+            // lane (column r, group g) holds rows 16 t + 4 g .. + 3 of tile t = wave + 4 i: one 16-byte store per tile
+            if (has) {
+                float* out = p.tk + ((int64_t)qg * kBoundSegs + seg) * kIvfTauRows + 4 * g;
+#pragma unroll
+                for (int i = 0; i < NT; ++i) {
+                    f32x4 x;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) x[j] = i8 ? (v[4 * i + j] == kNone ? VS_INF : (float)(v[4 * i + j] >> 8)) : __builtin_bit_cast(float, v[4 * i + j]);
+                    *reinterpret_cast<f32x4*>(out + 16 * (wave + 4 * i)) = x;
+                }
+            }
+        } else {
         // the wave's k smallest per column, ascending
         for (int round = 0; round < p.k; ++round) {
             unsigned m = v[0];
@@ -826,6 +844,7 @@ __device__ __forceinline__ void ivf_bounds_list_body(const IvfWideParams& p, con
             }
         }
         __syncthreads();
+        }
         e = e_nx;
         e_nx = e_nx2;
         b0 = nb0;
@@ -1061,11 +1080,12 @@ __device__ __forceinline__ void ivf_plan_body(const IvfWideParams& p, const int 
 // Bounds and plan in ONE launch (both need the pick kernel's output only: side by side instead of one after the other).  The
 // first n_plan * n_sb workgroups plan, the rest take (list, part) pairs of the bounds.  Four workgroups per CU: the bounds'
 // workgroups are one short chain of cache misses each, all of a launch group's lists should be in flight together.
+template <bool WIDE>
 __global__ __launch_bounds__(256, 4) void ivf_bounds_plan_kernel(const IvfWideParams p, const int n_plan, const int n_sb, const bool pad_here) {
     __shared__ __attribute__((aligned(16))) char lds[kBoundLds > kPlanLds ? kBoundLds : kPlanLds];
     const int wg = blockIdx.x;
     if (wg < n_plan * n_sb) ivf_plan_body(p, wg / n_plan, wg % n_plan, n_plan, lds, pad_here);
-    else ivf_bounds_list_body(p, (wg - n_plan * n_sb) % p.nlist, (wg - n_plan * n_sb) / p.nlist, lds, pad_here ? 0 : n_sb);
+    else ivf_bounds_list_body<WIDE>(p, (wg - n_plan * n_sb) % p.nlist, (wg - n_plan * n_sb) / p.nlist, lds, pad_here ? 0 : n_sb);
 }
 
 // The list-major scan of one super-batch (blockIdx.y).  A workgroup stages the super-batch's queries once (as bytes: 128
@@ -1724,13 +1744,14 @@ hipError_t launch_ivf_wide_bounds_plan(const IvfWideParams& p, hipStream_t s, in
     if (n_plan * n_sb + n_tau == 0) return hipSuccess;
     if ((what & 1) && (!p.tq || p.n_batches * kMaxBatch > 0x10000 || p.n_batches * kMaxBatch > p.tq_cap)) return hipErrorInvalidValue;
     // (who pads the slot tables: the bounds' workgroups if the tables are complete when they run, i.e. with the plan beside them)
-    hipLaunchKernelGGL(ivf_bounds_plan_kernel, dim3(n_plan * n_sb + n_tau), dim3(256), 0, s, p, n_plan, n_sb, n_tau == 0 || n_plan == 0 || n_sb > 16);
+    hipLaunchKernelGGL(ivf_bounds_plan_kernel<false>, dim3(n_plan * n_sb + n_tau), dim3(256), 0, s, p, n_plan, n_sb, n_tau == 0 || n_plan == 0 || n_sb > 16);
     if ((what & 1) && !p.tau_inline) hipLaunchKernelGGL(ivf_tau_combine_kernel, dim3((p.n_batches * kMaxBatch + 255) / 256), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
 hipError_t launch_ivf_wide_scan(const IvfWideParams& p, int num_cus, hipStream_t s) {
-    if (p.nlist > kIvfFastNlist || p.nprobe > kIvfMaxProbe || p.k > 16 || p.sb_batches < 1 || p.sb_batches > kIvfWideBatches) return hipErrorInvalidValue;
+    // (a wide-k group's scan reads its bounds from `tau` / `slow`: the inline bound merges lists of 16)
+    if (p.nlist > kIvfFastNlist || p.nprobe > kIvfMaxProbe || p.k > (p.tau_inline ? 16 : kIvfWideKMax) || p.sb_batches < 1 || p.sb_batches > kIvfWideBatches) return hipErrorInvalidValue;
     const int n_sb = (p.n_batches + p.sb_batches - 1) / p.sb_batches;
     static bool attr_set[64] = {};
     int dev = 0;
@@ -1947,6 +1968,171 @@ hipError_t launch_ivf_wide_rank(const MergeParams& m, int64_t stride_g, int64_t 
         hipLaunchKernelGGL(ivf_wide_rank_list_kernel, dim3(256), dim3(256), 0, s, m, L, p, glist);
     }
     else hipLaunchKernelGGL(ivf_wide_rank_kernel, dim3(m.nq), dim3(256), 0, s, m, L, p);
+    return hipGetLastError();
+}
+
+// ---- wide k (17 <= k <= kIvfWideKMax).  Same coarse / pick / plan / scan as above; the bound and the ranking differ:
+//  - bound: ivf_bounds_plan_kernel<true> stores the distances of a query's two segments (<= 2 x kIvfTauRows) to tk, the
+//    dense topk_wide_kernel selects their k smallest, and ivf_widek_tau_kernel turns the k-th into the query's bound
+//    (ivf_tau_of's slack) or marks the query slow;
+//  - ranking: ivf_widek_rank_kernel, the k smallest (dist, row) keys over the query's candidate sub-lists, or over every
+//    row of its probed lists for a slow query / an overflowed group.
+
+// the bound of every query of the group from the k-th smallest of its segments' distances (kth: [queries][k])
+__global__ __launch_bounds__(256) void ivf_widek_tau_kernel(const IvfWideParams p, const float* const kth) {
+    const int qg = blockIdx.x * 256 + threadIdx.x;
+    const int batch = qg >> 5, qi = qg & 31;
+    if (batch >= p.n_batches || qi >= p.B) return;
+    const float x = kth[(int64_t)qg * p.k + p.k - 1];
+    const bool i8 = p.vecs_u8 && p.metric == 0 && p.invalid[batch] == 0;
+    const float tb = i8 ? next_up(x) : x + 1e-4f * fabsf(x) + 1e-30f;  // (as ivf_tau_of)
+    const float t = x < VS_INF ? tb : VS_INF;  // +inf: fewer than k rows in the query's segments
+    p.tau[qg] = t;
+    if (!(t < VS_INF)) p.slow[qg] = 1;
+}
+
+hipError_t launch_ivf_widek_bounds_plan(const IvfWideParams& p, float* kth_d, int32_t* kth_i, hipStream_t s) {
+    if (p.nlist > kIvfFastNlist || p.nprobe > kIvfMaxProbe || p.k <= 16 || p.k > kIvfWideKMax || p.tau_inline || !p.tq || !kth_d || !kth_i ||
+        p.sb_batches < 1 || p.sb_batches > kIvfWideBatches || p.n_batches * kMaxBatch > 0x10000 || p.n_batches * kMaxBatch > p.tq_cap)
+        return hipErrorInvalidValue;
+    const int n_sb = (p.n_batches + p.sb_batches - 1) / p.sb_batches;
+    static const int plan_wgs = getenv("VSEARCH_PLAN_WGS") ? atoi(getenv("VSEARCH_PLAN_WGS")) : 16;  // (as launch_ivf_wide_bounds_plan)
+    const int n_plan = std::max(plan_wgs, 16 / n_sb);
+    const int n_tau = p.nlist * kBoundParts;
+    hipLaunchKernelGGL(ivf_bounds_plan_kernel<true>, dim3(n_plan * n_sb + n_tau), dim3(256), 0, s, p, n_plan, n_sb, n_sb > 16);
+    TopkWideParams t{};
+    t.dense = p.tk;
+    t.dense_ld = kBoundSegs * kIvfTauRows;
+    t.n_dense = kBoundSegs * kIvfTauRows;
+    t.nq = p.n_batches * kMaxBatch;
+    t.k1 = p.k;
+    t.out_d = kth_d;
+    t.out_i = kth_i;
+    t.out_ld = p.k;
+    hipError_t e = launch_topk_wide(t, t.nq, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ivf_widek_tau_kernel, dim3((p.n_batches * kMaxBatch + 255) / 256), dim3(256), 0, s, p, kth_d);
+    return hipGetLastError();
+}
+
+constexpr int kRankKThreads = 256;
+constexpr int kRankKCap = 2048;  // keys the final sort holds (16 KB of LDS)
+// One workgroup per output query.  The group's last kernel: it leaves the counters zeroed as ivf_wide_rank_kernel does,
+// and its query's segment distances (tk) at +inf for the next wide-k group.  stats (optional): candidates in all, the most
+// of one query, queries ranked exactly, groups whose candidate buffers overflowed.
+__global__ __launch_bounds__(kRankKThreads) void ivf_widek_rank_kernel(const IvfWideParams p, const int32_t* const id_map,
+                                                                       unsigned long long* const stats) {
+    __shared__ WideSelLds<kRankKCap> sel;
+    __shared__ int s_len[16];
+    __shared__ int s_upper;
+    const int q = blockIdx.x;  // output query = batch * B + qi
+    const int batch = q / p.B, qi = q % p.B;
+    const int qg = batch * kMaxBatch + qi;
+    const int tid = threadIdx.x;
+    const CandSink& sk = p.sink;
+    const bool ovf = sk.overflow[0] != 0;
+    const bool exact = ovf || p.slow[qg] != 0;  // (workgroup-uniform)
+    if (tid == 0) s_upper = 0;
+    __syncthreads();
+    int M;
+    if (!exact) {
+        if (tid < sk.nsub) {
+            const int n = min(sk.cnt[(int64_t)tid * sk.cnt_sub_stride + qg], sk.cap);  // (a sub-list that overflowed marks the query slow)
+            s_len[tid] = n;
+            atomicAdd(&s_upper, n);
+        }
+        __syncthreads();
+        M = wide_select<kRankKThreads>(sel, s_upper, p.k, [&](auto&& f) {
+            for (int sub = 0; sub < sk.nsub; ++sub) {
+                const int64_t base = ((int64_t)qg * sk.nsub + sub) * sk.cap;
+                for (int e = tid; e < s_len[sub]; e += kRankKThreads) {
+                    uint64_t key;
+                    if (tw_key(sk.cand_d[base + e], sk.cand_i[base + e], key)) f(key);
+                }
+            }
+        });
+    } else {
+        // every row of the probed lists, with the arithmetic of ivf_wide_slow_body; rows as the scan has them (padded rows
+        // on the byte path)
+        const int32_t* pr = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(p.probes) + (long long)batch * p.probes_batch_bytes) + qi * p.nprobe;
+        const float* qv = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.q) + (long long)batch * p.q_batch_bytes) + qi * kDim;
+        const bool i8 = p.vecs_u8 && p.metric == 0 && p.invalid[batch] == 0;
+        const float qn = p.qnorm[qg];
+        const int qt = p.qterm[qg];
+        for (int pp = tid; pp < p.nprobe; pp += kRankKThreads) {
+            const int c = pr[pp];
+            if (c >= 0) atomicAdd(&s_upper, p.offsets[c + 1] - p.offsets[c]);
+        }
+        __syncthreads();
+        M = wide_select<kRankKThreads>(sel, s_upper, p.k, [&](auto&& f) {
+            for (int pp = 0; pp < p.nprobe; ++pp) {
+                const int c = pr[pp];
+                if (c < 0) continue;
+                const int s0 = p.offsets[c], s1 = p.offsets[c + 1];
+                const int td = p.tdelta ? p.tdelta[c] : 0;
+                for (int row = s0 + tid; row < s1; row += kRankKThreads) {
+                    float d;
+                    if (i8) {
+                        typedef int i32x4 __attribute__((ext_vector_type(4)));
+                        const i32x4* b = reinterpret_cast<const i32x4*>(p.vecs_u8 + (int64_t)row * kDim);
+                        const i32x4* qq = reinterpret_cast<const i32x4*>(p.q8 + (int64_t)qg * kDim);
+                        int dot = 0;
+#pragma unroll
+                        for (int t = 0; t < kDim / 16; ++t) {
+                            const i32x4 bv = b[t], qv4 = qq[t];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) dot = __builtin_amdgcn_sdot4(bv[e], qv4[e], dot, false);
+                        }
+                        d = (float)(qt + p.rterm[row] - 2 * dot);
+                    } else {
+                        const float* b = p.vecs + (int64_t)row * kDim;
+                        float dot = 0.f;
+                        for (int t = 0; t < kDim; ++t) dot = fmaf(b[t], qv[t], dot);
+                        d = p.metric ? -dot : fmaf(-2.0f, dot, qn + p.vnorm[row]);
+                    }
+                    uint64_t key;
+                    if (tw_key(d, row + td, key)) f(key);
+                }
+            }
+        });
+    }
+    const int n_out = min(M, p.k);
+    for (int t = tid; t < p.k; t += kRankKThreads) {
+        float d = VS_INF;
+        int32_t id = -1;
+        if (t < n_out) {
+            d = tw_dist(sel.keys[t]);
+            const int32_t r = (int32_t)(uint32_t)sel.keys[t];
+            id = id_map ? id_map[r] : r;
+        }
+        p.out_d[(int64_t)q * p.k + t] = d;
+        p.out_i[(int64_t)q * p.k + t] = id;
+    }
+    if (stats && tid == 0) {
+        atomicAdd(stats + 0, (unsigned long long)(exact ? 0 : s_upper));
+        atomicMax(stats + 1, (unsigned long long)(exact ? 0 : s_upper));
+        if (exact) atomicAdd(stats + 2, 1ull);
+        if (ovf && q == 0) atomicAdd(stats + 3, 1ull);
+    }
+    // the group's counters are left zeroed for the next group (see ivf_wide_rank_kernel), the query's segment distances at +inf
+    if (tid < sk.nsub) sk.cnt[(int64_t)tid * sk.cnt_sub_stride + qg] = 0;
+    if (tid == 0) p.slow[qg] = 0;
+    for (int i = tid; i < kBoundSegs * kIvfTauRows / 4; i += kRankKThreads)
+        reinterpret_cast<f32x4*>(p.tk + (int64_t)qg * kBoundSegs * kIvfTauRows)[i] = (f32x4){VS_INF, VS_INF, VS_INF, VS_INF};
+    const int sb = batch / p.sb_batches;
+    const int nql = (min(p.n_batches, (sb + 1) * p.sb_batches) - sb * p.sb_batches) * p.B;  // workgroups of this super-batch
+    const int ql = (batch - sb * p.sb_batches) * p.B + qi;
+    for (int c = ql + tid * nql; c < p.nlist; c += kRankKThreads * nql) {
+        p.zero[sb * ivf_wide_plan_words(p.nlist) + (int64_t)c * kIvfWideCntStride] = 0;
+        if (sb == 0) p.zero[(int64_t)c * kIvfWideCntStride + 1] = 0;  // (the list's bound-table counter lives in super-batch 0's line)
+    }
+    if (ql == 0 && tid == 0) p.zero[sb * ivf_wide_plan_words(p.nlist) + (int64_t)p.nlist * kIvfWideCntStride] = 0;  // the record count
+}
+
+hipError_t launch_ivf_widek_rank(const IvfWideParams& p, const int32_t* id_map, unsigned long long* stats, hipStream_t s) {
+    if (p.k <= 16 || p.k > kIvfWideKMax || p.sink.nsub < 1 || p.sink.nsub > 16 || !p.sink.xcd_subs || p.n_batches * p.B < 1)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ivf_widek_rank_kernel, dim3(p.n_batches * p.B), dim3(kRankKThreads), 0, s, p, id_map, stats);
     return hipGetLastError();
 }
 

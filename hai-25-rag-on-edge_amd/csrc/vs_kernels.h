@@ -436,6 +436,14 @@ int ivf_wide_waves(int num_cus, int n_sb);   // its waves = candidate buffers
 // few that need a workgroup to a second launch (the list's count, word 0, is cleared by the next group's coarse / prep kernel)
 hipError_t launch_ivf_wide_rank(const MergeParams& m, int64_t stride_g, int64_t stride_q, const IvfWideParams& p, hipStream_t s,
                                 int32_t* glist = nullptr);
+// wide k (17 <= k <= kIvfWideKMax, p.tau_inline = 0): the pipeline above with another bound and another ranking.
+// Bounds + plan: the bounds launch stores every (query, segment) distance to p.tk ([queries][kBoundSegs][kIvfTauRows], left
+// at +inf by the ranking), topk_wide_kernel selects the k smallest per query into kth_d / kth_i ([queries][k]), and the
+// k-th becomes p.tau (or p.slow).  The ranking: the k smallest (dist, row) per query over its candidate sub-lists, or over
+// every row of its probed lists for a slow query or an overflowed group; ids through id_map; the counters left zeroed.
+constexpr int kIvfWideKMax = 128;
+hipError_t launch_ivf_widek_bounds_plan(const IvfWideParams& p, float* kth_d, int32_t* kth_i, hipStream_t s);
+hipError_t launch_ivf_widek_rank(const IvfWideParams& p, const int32_t* id_map, unsigned long long* stats, hipStream_t s);
 
 struct IvfScanParams {
     const float* vecs;        // [n_rows][128] cluster-reordered (vectors_reordered.npy)

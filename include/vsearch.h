@@ -270,12 +270,14 @@ VS_API int vs_ivf_save(vs_index* h, const char* index_dir);
 /* IVFIndex::searchBatch (IVFIndex.h:45-48, IVFIndex.cpp:640-859): ids/dists
  * [nq x k] (L2: ascending distance; ids are original row numbers), returns the
  * total number of candidates scanned through *total_candidates (the
- * function's return value in the reference) and the SearchTiming fields. */
+ * function's return value in the reference) and the SearchTiming fields.
+ * k: 1..128.  17 <= k <= 128 needs the list-major pipeline (nlist <= 4096, rows resident): VS_ERR_UNSUPPORTED
+ * otherwise, and for k > 128.  Slots past the candidates of the probed lists are (-1, +inf) for every k. */
 VS_API int vs_ivf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int nprobe,
                          int32_t* ids, float* dists, int64_t* total_candidates, vs_timing* timing);
 
 /* Device-level, asynchronous: one batch, outputs [B x k] on the device.
- * For a sharded index the outputs are this shard's local top-k (global ids). */
+ * For a sharded index the outputs are this shard's local top-k (global ids).  k: as vs_ivf_search. */
 VS_API int vs_ivf_search_dev(vs_index* h, const float* queries_dev, int B, int k, int nprobe,
                              int32_t* ids_dev, float* dists_dev, void* stream);
 
@@ -283,7 +285,9 @@ VS_API int vs_ivf_search_dev(vs_index* h, const float* queries_dev, int B, int k
  * batches [n_batches][B][dim] -> [n_batches][B][k].  Every kernel of the pipeline is launched once for a
  * launch group of up to 32 batches (1024 queries share ONE list-major pass over the probed lists), and the
  * groups of a call are dealt to two internal streams that fork from and join `stream`: pass as many batches
- * per call as there are (128 batches per call: 13.6 M QPS at nlist 1024 / nprobe 32; 32 per call: 10.9 M). */
+ * per call as there are (128 batches per call: 13.6 M QPS at nlist 1024 / nprobe 32; 32 per call: 10.9 M).
+ * k: as vs_ivf_search (17 <= k <= 128 takes a pipeline of its own: bound from the k-th of the segments' distances,
+ * wide-k ranking; the k <= 16 path is not affected). */
 VS_API int vs_ivf_search_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k, int nprobe,
                                    int32_t* ids_dev, float* dists_dev, void* stream);
 
@@ -338,7 +342,9 @@ VS_API int vs_ivf_search_dev_sharded(vs_index* h, vs_comm* c, const float* queri
  * Virtual ranks: the same pipeline for G shards (vs_ivf_create / vs_ivf_load with rank r, world G) on ONE device, driven
  * by the calling thread, the collectives no-ops (every shard writes its part of the gathered layout).  For tests and
  * for measuring a rank's cost per launch group on one GPU: rank_ms[r] (optional, G doubles) = device time of rank r's
- * two halves. */
+ * two halves.
+ * k: 1..16 on all three sharded IVF calls (vs_ivf_search_dev_sharded, vs_ivf_search_dev_vshards, vs_ivf_search_sharded):
+ * VS_ERR_UNSUPPORTED for k >= 17 (their exchange and merge are laid out for top-16). */
 /* Host-side arithmetic of the sliced pipeline (no device needed).  vs_ivf_shard_group: batches per launch group of an index
  * created with `world`.  vs_ivf_shard_slice: a group of n_batches batches is cut into `world` slices of *slice_batches
  * batches (the last ones may be short or empty); rank's own slice is [*first_batch, *first_batch + *own_batches).
@@ -373,6 +379,12 @@ VS_API int vs_bf_search_vshards(vs_index* const* shards, int G, const float* que
  * (bench.py's roofline leg).  which: 0 = brute-force scan, 1 = IVF list scan. */
 VS_API int vs_prof_enable(vs_index* h, int on);
 VS_API int vs_prof_read(vs_index* h, int which, double* total_ms, int64_t* launches);
+/* Diagnostics of the wide-k IVF pipeline (17 <= k <= 128), collected only when the environment variable
+ * VSEARCH_IVF_WIDEK_STATS=1 was set at the index's first wide-k call: out[0] = candidates ranked (queries ranked from
+ * their candidate lists), out[1] = the most candidates of one such query, out[2] = queries ranked exactly over every row
+ * of their probed lists (no bound, or a candidate list overflowed), out[3] = launch groups whose candidate buffers
+ * overflowed (all their queries ranked exactly).  Synchronises the device; reset != 0 clears the counters. */
+VS_API int vs_ivf_widek_stats(vs_index* h, int64_t* out /* [4] */, int reset);
 /* per-launch durations (ms) of the same window, oldest first; *launches = how many there were (may exceed cap).
  * One brute-force launch serves up to 32 batches: the CLIs turn these into the per-batch statistics of
  * main.cpp:262-330 (avg / stddev / min / max / P50 / P95 / P99 "graph execute time"). */

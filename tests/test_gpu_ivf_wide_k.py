@@ -1,0 +1,321 @@
+"""IVF search for 17 <= k <= 128 (the wide-k pipeline) against the oracle's IVFIndex::searchBatch and exact search.
+The k <= 16 path is the reference for the first 16 columns; the oracle orders results by (distance, reordered row)."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import oracle
+
+pytestmark = pytest.mark.gpu
+
+_INDEX_CACHE = {}
+
+
+def _make_index(pkg, n=20000, nlist=64, seed=3):
+    key = (n, nlist, seed)
+    if key not in _INDEX_CACHE:
+        _INDEX_CACHE[key] = _build_index(pkg, pkg.synth_sift(n, seed=seed), nlist, seed)
+    return _INDEX_CACHE[key]
+
+
+def _build_index(pkg, base, nlist, seed):
+    rng = np.random.default_rng(seed)
+    cents = base[rng.choice(len(base), nlist, replace=False)].copy()
+    for _ in range(2):  # a few Lloyd steps on the host (index building is not the path under test)
+        d = (base ** 2).sum(1)[:, None] - 2 * base @ cents.T + (cents ** 2).sum(1)[None]
+        a = d.argmin(1)
+        for c in range(nlist):
+            if (a == c).any():
+                cents[c] = base[a == c].mean(0)
+    cents = cents.astype(np.float32)
+    d = (base ** 2).sum(1)[:, None] - 2 * base @ cents.T + (cents ** 2).sum(1)[None]
+    a = d.argmin(1)
+    vr, off, r2o = pkg.ivf_layout_from_assignment(base, a, nlist)
+    return base, cents, vr, off, r2o
+
+
+def _open(pkg, idx, **kw):
+    base, cents, vr, off, r2o = idx
+    return pkg.IVFIndex(vectors_reordered=vr, centroids=cents, cluster_offsets=off, reorder_to_original=r2o, **kw)
+
+
+def _dev_multi(ivf, q, k, nprobe, B=32):
+    """search_dev_multi over len(q) // B full batches"""
+    import torch
+    dev = torch.device("cuda:0")
+    nb = len(q) // B
+    qd = torch.from_numpy(np.ascontiguousarray(q[:nb * B])).to(dev)
+    oi = torch.full((nb * B, k), -7, dtype=torch.int32, device=dev)
+    od = torch.zeros((nb * B, k), dtype=torch.float32, device=dev)
+    ivf.search_dev_multi(qd.data_ptr(), nb, B, k, nprobe, oi.data_ptr(), od.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return oi.cpu().numpy(), od.cpu().numpy()
+
+
+def _dev_one(ivf, q, k, nprobe):
+    import torch
+    dev = torch.device("cuda:0")
+    qd = torch.from_numpy(np.ascontiguousarray(q)).to(dev)
+    oi = torch.full((len(q), k), -7, dtype=torch.int32, device=dev)
+    od = torch.zeros((len(q), k), dtype=torch.float32, device=dev)
+    ivf.search_dev(qd.data_ptr(), len(q), k, nprobe, oi.data_ptr(), od.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return oi.cpu().numpy(), od.cpu().numpy()
+
+
+def _unambiguous(q, cents, nprobe):
+    """queries whose float64 coarse distances at ranks nprobe and nprobe + 1 differ by more than 1e-4 relative"""
+    q64, c64 = q.astype(np.float64), cents.astype(np.float64)
+    d = (q64 ** 2).sum(1)[:, None] - 2 * q64 @ c64.T + (c64 ** 2).sum(1)[None]
+    if nprobe >= d.shape[1]:
+        return np.ones(len(q), dtype=bool)
+    s = np.sort(d, axis=1)
+    a, b = s[:, nprobe - 1], s[:, nprobe]
+    return (b - a) > 1e-4 * np.maximum(np.abs(a), 1e-30)
+
+
+def _check_oracle(ids, d, idx, q, k, nprobe, metric=0, sign=1.0):
+    base, cents, vr, off, r2o = idx
+    oi, od, _ = oracle.ivf_search(vr, off, r2o, cents, q, k, nprobe, metric=metric)
+    d = sign * d
+    same_d = np.array([np.array_equal(d[i], od[i]) for i in range(len(q))])
+    assert same_d.mean() >= 0.97, same_d.mean()
+    clear = _unambiguous(q, cents, nprobe)
+    bad = np.where(clear & ~np.array([np.array_equal(d[i], od[i]) and np.array_equal(ids[i], oi[i]) for i in range(len(q))]))[0]
+    assert len(bad) == 0, f"{len(bad)} unambiguous queries differ, first {bad[:5]}"
+
+
+def _check_props(ids, d, base, q):
+    ex = oracle.exact_int_dists(q, base)
+    valid = ids >= 0
+    got = np.take_along_axis(ex, np.where(valid, ids, 0).astype(np.int64), 1).astype(np.float32)
+    assert np.array_equal(got[valid], d[valid])
+    assert np.isinf(d[~valid]).all()
+    assert (np.diff(np.where(np.isinf(d), np.float32(3e38), d), axis=1) >= 0).all()
+    for i in range(len(q)):
+        v = ids[i][ids[i] >= 0]
+        assert len(np.unique(v)) == len(v)
+        assert valid[i].sum() == 0 or valid[i][:valid[i].sum()].all()  # padding only at the end
+
+
+@pytest.mark.parametrize("shape", [(20000, 64), (60000, 1024)])
+@pytest.mark.parametrize("precision", [0, 1])
+@pytest.mark.parametrize("nprobe", [8, 32])
+def test_prefix_identity(gpu_pkg, shape, precision, nprobe):
+    idx = _make_index(gpu_pkg, *shape)
+    q = gpu_pkg.synth_sift(96, seed=41)
+    with _open(gpu_pkg, idx) as ivf:
+        ivf.set_precision(precision)
+        i16, d16, t16 = ivf.searchBatch(q, len(q), 16, nprobe)
+        for k in (17, 32, 64, 100, 128):
+            ik, dk, tk = ivf.searchBatch(q, len(q), k, nprobe)
+            assert ik.shape == (len(q), k)
+            assert np.array_equal(ik[:, :16], i16) and np.array_equal(dk[:, :16], d16), k
+            assert tk == t16
+
+
+@pytest.mark.parametrize("nprobe", [8, 32])
+def test_matches_oracle_k100(gpu_pkg, nprobe):
+    idx = _make_index(gpu_pkg)
+    q = gpu_pkg.synth_sift(128, seed=43)
+    with _open(gpu_pkg, idx) as ivf:
+        ids, d, _ = ivf.searchBatch(q, len(q), 100, nprobe)
+        di, dd = _dev_multi(ivf, q, 100, nprobe)
+    _check_oracle(ids, d, idx, q, 100, nprobe)
+    assert np.array_equal(di, ids) and np.array_equal(dd, d)
+
+
+def test_result_properties_and_padding(gpu_pkg):
+    idx = _make_index(gpu_pkg)
+    base = idx[0]
+    q = gpu_pkg.synth_sift(64, seed=44)
+    with _open(gpu_pkg, idx) as ivf:
+        ids, d, _ = ivf.searchBatch(q, len(q), 128, 8)
+    _check_props(ids, d, base, q)
+    # lists of a few dozen rows: nprobe 1 at k = 128 leaves (-1, +inf) padding
+    small = _make_index(gpu_pkg, n=3000, nlist=100, seed=45)
+    with _open(gpu_pkg, small) as ivf:
+        ids, d, total = ivf.searchBatch(q, len(q), 128, 1)
+    _check_props(ids, d, small[0], q)
+    assert (ids == -1).any(axis=1).mean() > 0.8 and total < len(q) * 128
+    _check_oracle(ids, d, small, q, 128, 1)
+
+
+def test_full_probe_equals_exact(gpu_pkg):
+    idx = _make_index(gpu_pkg, n=12000, nlist=32, seed=46)
+    base = idx[0]
+    q = gpu_pkg.synth_sift(64, seed=47)
+    oi, od = oracle.search_bf(base, q, 100)
+    with _open(gpu_pkg, idx) as ivf:
+        ids, d, total = ivf.searchBatch(q, len(q), 100, 32)
+    assert total == len(q) * len(base)
+    assert np.array_equal(d, od)
+    ex = oracle.exact_int_dists(q, base)
+    top = np.sort(ex, axis=1)[:, :101]
+    notie = (top[:, 1:] != top[:, :-1]).all(1)
+    assert notie.mean() > 0.5 and np.array_equal(ids[notie], oi[notie])
+
+
+def test_slow_and_overflow_paths(gpu_pkg):
+    # tiny lists: the two nearest lists hold fewer than k rows -> every query is ranked exactly
+    tiny = _make_index(gpu_pkg, n=4000, nlist=256, seed=48)
+    q = gpu_pkg.synth_sift(64, seed=49)
+    with _open(gpu_pkg, tiny) as ivf:
+        ids, d, _ = ivf.searchBatch(q, len(q), 100, 16)
+    _check_oracle(ids, d, tiny, q, 100, 16)
+    _check_props(ids, d, tiny[0], q)
+    # a mass of duplicate rows under every query's bound: candidate lists and wave buffers overflow
+    base = gpu_pkg.synth_sift(20000, seed=50)
+    base[5000:17000] = base[5000]
+    dup = _build_index(gpu_pkg, base, 16, 51)
+    qd = np.repeat(base[5000:5001], 96, axis=0) + np.arange(96, dtype=np.float32)[:, None] % 3
+    with _open(gpu_pkg, dup) as ivf:
+        for k in (64, 128):
+            ids, d, _ = ivf.searchBatch(qd, len(qd), k, 4)
+            _check_oracle(ids, d, dup, qd, k, 4)
+            _check_props(ids, d, base, qd)
+        # the next call on the same index is unaffected
+        q2 = gpu_pkg.synth_sift(64, seed=52)
+        ids, d, _ = ivf.searchBatch(q2, len(q2), 100, 4)
+    _check_oracle(ids, d, dup, q2, 100, 4)
+
+
+def test_state_between_calls(gpu_pkg):
+    idx = _make_index(gpu_pkg, n=60000, nlist=1024)
+    q = gpu_pkg.synth_sift(320, seed=53)
+    seq = (100, 5, 128, 5, 100)
+    with _open(gpu_pkg, idx) as ivf:
+        got = [ivf.searchBatch(q, len(q), k, 32)[:2] for k in seq]
+    for k, (gi, gd) in zip(seq, got):
+        with _open(gpu_pkg, idx) as fresh:
+            fi, fd, _ = fresh.searchBatch(q, len(q), k, 32)
+        assert np.array_equal(gi, fi) and np.array_equal(gd, fd), k
+    # 300 batches: a full launch group of 256 batches and a partial one
+    qq = gpu_pkg.synth_sift(300 * 8, seed=54)
+    with _open(gpu_pkg, idx) as ivf:
+        mi, md = _dev_multi(ivf, qq, 64, 32, B=8)
+        for b in (0, 1, 255, 256, 299):
+            bi, bd = _dev_one(ivf, qq[b * 8:(b + 1) * 8], 64, 32)
+            assert np.array_equal(bi, mi[b * 8:(b + 1) * 8]) and np.array_equal(bd, md[b * 8:(b + 1) * 8]), b
+    _check_props(mi[:256], md[:256], idx[0], qq[:256])
+
+
+def test_precision_and_metric(gpu_pkg):
+    idx = _make_index(gpu_pkg)
+    q = gpu_pkg.synth_sift(128, seed=55)
+    with _open(gpu_pkg, idx) as ivf:
+        i0, d0, t0 = ivf.searchBatch(q, len(q), 100, 16)
+        ivf.set_precision(1)
+        i1, d1, t1 = ivf.searchBatch(q, len(q), 100, 16)
+    assert np.array_equal(i0, i1) and np.array_equal(d0, d1) and t0 == t1
+    with _open(gpu_pkg, idx) as ivf:
+        ivf.set_metric(1)
+        ids, d, _ = ivf.searchBatch(q, len(q), 64, 8)
+        di, dd = _dev_multi(ivf, q, 64, 8)
+    assert np.array_equal(di, ids) and np.array_equal(dd, -d)  # host call: q.v, device calls: -q.v
+    _check_oracle(ids, d, idx, q, 64, 8, metric=1, sign=-1.0)
+
+
+def test_host_call_chunks(gpu_pkg):
+    idx = _make_index(gpu_pkg, n=60000, nlist=1024)
+    q = gpu_pkg.synth_sift(5000, seed=56)
+    with _open(gpu_pkg, idx) as ivf:
+        ids, d, total = ivf.searchBatch(q, len(q), 128, 32)
+        _, _, total5 = ivf.searchBatch(q, len(q), 5, 32)
+        mi, md = _dev_multi(ivf, q, 128, 32)
+        ti, td = _dev_one(ivf, q[len(mi):], 128, 32)
+    assert total == total5
+    assert np.array_equal(ids, np.concatenate([mi, ti])) and np.array_equal(d, np.concatenate([md, td]))
+
+
+def test_sift1m_shape(gpu_pkg, tmp_path):
+    base = gpu_pkg.synth_sift(1000000, seed=57)
+    ivf, _ = gpu_pkg.IVFIndex.build(base, 1024, max_iter=4, seed=42)
+    idir = str(tmp_path / "index")
+    with ivf:
+        ivf.save(idir)
+    cents = np.load(os.path.join(idir, "centroids.npy"))
+    vr = np.load(os.path.join(idir, "vectors_reordered.npy"))
+    off = np.load(os.path.join(idir, "cluster_offsets.npy"))
+    r2o = np.load(os.path.join(idir, "reorder_to_original.npy"))
+    idx = (base, cents, vr, off, r2o)
+    q = gpu_pkg.synth_sift(512, seed=58)
+    with _open(gpu_pkg, idx) as ivf:
+        for precision in (0, 1):
+            ivf.set_precision(precision)
+            for nprobe in (8, 32):
+                ids, d, _ = ivf.searchBatch(q, len(q), 100, nprobe)
+                _check_oracle(ids, d, idx, q, 100, nprobe)
+
+
+def _exe(pkg, name):
+    exe = os.path.join(os.path.dirname(pkg.LIB_PATH), name)
+    assert os.path.exists(exe), f"{name} not built (make -C hai-25-rag-on-edge_amd/csrc all)"
+    return exe
+
+
+def test_cli_recall_at_100(gpu_pkg, tmp_path):
+    base = gpu_pkg.synth_sift(20000, seed=59)
+    q = gpu_pkg.synth_sift(50, seed=60)
+    bf, qf, gt = str(tmp_path / "base.fvecs"), str(tmp_path / "q.fvecs"), str(tmp_path / "gt.ivecs")
+    gpu_pkg.write_fvecs(bf, base)
+    gpu_pkg.write_fvecs(qf, q)
+    r = subprocess.run([_exe(gpu_pkg, "vsearch_bf"), "--groundtruth", bf, qf, gt], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = gpu_pkg.read_ivecs(gt)
+    assert got.shape == (50, 100)
+    ivf, _ = gpu_pkg.IVFIndex.build(base, 32, max_iter=5, seed=42)
+    idir = str(tmp_path / "index")
+    with ivf:
+        ivf.save(idir)
+    res = str(tmp_path / "ivf_out")
+    r = subprocess.run([_exe(gpu_pkg, "vsearch_ivf"), idir, qf, res, "none.so", "100", "32", gt], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    m = re.search(r"Recall@100: ([0-9.eE+-]+)%", r.stdout)
+    assert m, r.stdout
+    pid, _ = oracle.parse_results_txt(os.path.join(res, "results.txt"))
+    pid = np.array(pid)
+    assert pid.shape == (50, 100)
+    want = np.mean([len(set(pid[i].tolist()) & set(got[i].tolist())) / 100.0 for i in range(len(q))])
+    assert abs(float(m.group(1)) - 100.0 * want) < 1e-3
+    assert want > 0.5
+
+
+def test_limits(gpu_pkg):
+    idx = _make_index(gpu_pkg)
+    q = gpu_pkg.synth_sift(8, seed=61)
+    with _open(gpu_pkg, idx) as ivf:
+        for k, status in ((129, -5), (0, -1)):
+            with pytest.raises(gpu_pkg.VSearchError) as e:
+                ivf.searchBatch(q, len(q), k, 8)
+            assert e.value.status == status
+        with pytest.raises(gpu_pkg.VSearchError) as e:
+            _dev_one(ivf, q, 129, 8)
+        assert e.value.status == -5
+    # virtual ranks: k >= 17 is not supported
+    import torch
+    base, cents, vr, off, r2o = idx
+    shards = [_open(gpu_pkg, idx, rank=r, world=2) for r in range(2)]
+    try:
+        qd = torch.from_numpy(q).cuda()
+        oi = torch.zeros((8, 17), dtype=torch.int32, device="cuda")
+        od = torch.zeros((8, 17), dtype=torch.float32, device="cuda")
+        with pytest.raises(gpu_pkg.VSearchError) as e:
+            gpu_pkg.IVFIndex.search_dev_vshards(shards, qd.data_ptr(), 1, 8, 17, 8, oi.data_ptr(), od.data_ptr(),
+                                                torch.cuda.current_stream().cuda_stream)
+        assert e.value.status == -5
+    finally:
+        for s in shards:
+            s.close()
+    # nlist > 4096: the query-major path stops at k = 16
+    b = gpu_pkg.synth_sift(4200, seed=62)
+    vr2, off2, r2o2 = gpu_pkg.ivf_layout_from_assignment(b, np.arange(4200), 4200)
+    with gpu_pkg.IVFIndex(vectors_reordered=vr2, centroids=b.copy(), cluster_offsets=off2, reorder_to_original=r2o2) as ivf:
+        ivf.searchBatch(q, len(q), 16, 4)
+        with pytest.raises(gpu_pkg.VSearchError) as e:
+            ivf.searchBatch(q, len(q), 17, 4)
+        assert e.value.status == -5
