@@ -124,6 +124,7 @@ def lib():
         "vs_synth_mixture": (i32, [vp, i64, i64, i32, C.c_uint64, i32, C.c_double, C.c_double]),
         "vs_select_topk_slots": (i32, [vp, vp, i64, i32, vp, vp]),
         "vs_bf_create": (i32, [vp, i64, i32, i32, i32, i64, C.POINTER(vp)]),
+        "vs_bf_create_nd": (i32, [vp, i64, i32, i32, i32, i64, C.POINTER(vp)]),
         "vs_set_batch": (i32, [vp, i32]),
         "vs_set_precision": (i32, [vp, i32]),
         "vs_ivf_set_metric": (i32, [vp, i32]),
@@ -331,7 +332,10 @@ class _Index:
 class BruteForceIndex(_Index):
     """Exact L2 (or IP) search over a resident base: the GPU side of run_benchmark
     (cpu_baseline.cpp:177-254).  ``search`` returns exactly what the reference writes
-    to results.txt: ids and squared-L2 distances, ascending, reference tie order."""
+    to results.txt: ids and squared-L2 distances, ascending, reference tie order.
+
+    Any vector length 1 <= d <= 2048: 128-d bases take vs_bf_create (every specialised path), the others
+    vs_bf_create_nd (fp32 rows, the general-dimension scan; no sharded calls, no int8 precision)."""
 
     def __init__(self, base, metric: int = METRIC_L2, device: int = 0, id_offset: int = 0):
         super().__init__()
@@ -339,7 +343,9 @@ class BruteForceIndex(_Index):
         if base.ndim != 2:
             raise ValueError("base must be [N, d]")
         self.n, self.d = base.shape
-        _check(lib().vs_bf_create(_p(base), self.n, self.d, metric, device, id_offset, C.byref(self._h)))
+        create = lib().vs_bf_create if self.d == 128 else lib().vs_bf_create_nd
+        _check(create(_p(base), self.n, self.d, metric, device, id_offset, C.byref(self._h)))
+        self.d = self.getDim()  # (buffers of every call below are sized by the index's own dimension)
 
     def search(self, queries, k: int, timing: Timing | None = None):
         q = _f32c(queries).reshape(-1, self.d)

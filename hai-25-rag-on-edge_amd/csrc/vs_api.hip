@@ -80,6 +80,12 @@ struct vs_index {
     int kind = 0;  // 0 = brute force, 1 = IVF
     int device = 0;
     int dim = 0;
+    // general index (vs_bf_create_nd with dim != 128, or VSEARCH_ND_FORCE): rows of dim_p = nd_dim_p(dim) floats, zero padded,
+    // scanned by scan_nd_kernel; no int8 copy, no seed sample, no bf16 filter statistics.  Otherwise dim_p == dim == 128.
+    bool general = false;
+    int dim_p = 0;
+    vs::DevBuf<float> d_nd_qfrag;  // [kMaxMulti][dim_p / 16][2][64][4] scratch of launch_scan_nd
+    vs::DevBuf<float> d_nd_qnorm;  // [kMaxMulti][32]
     int metric = VS_METRIC_L2;
     int64_t n_rows = 0;   // rows resident on this GPU
     int64_t n_total = 0;  // rows of the whole (unsharded) index
@@ -87,7 +93,7 @@ struct vs_index {
     int batch = vs::kMaxBatch;
     int num_cus = 256;
 
-    vs::DevBuf<float> d_vecs;   // [n_rows][128]
+    vs::DevBuf<float> d_vecs;   // [n_rows + 64][128] (general index: [n_rows + 64][dim_p])
     vs::DevBuf<float> d_norm;   // [n_rows + 64]
     // the bf16 prefilter of the fp32 streaming scan (scan_f32f_kernel): shard constants, and whether every row is well
     // scaled (otherwise the index keeps scan_f32s_kernel)
@@ -124,7 +130,7 @@ struct vs_index {
     double avg_cluster_size = 0;
 
     // scratch
-    vs::DevBuf<float> d_q;        // staging for host queries [32][128]
+    vs::DevBuf<float> d_q;        // staging for host queries [kMaxMulti * 32][dim]
     // Pipeline lanes: consecutive batches of a multi-batch call run on different internal streams
     // so that the start-up / tail of one scan overlaps the streaming phase of its neighbours
     // (inside one launch all workgroups go through those phases in lock-step and HBM idles).
@@ -234,7 +240,7 @@ struct vs_index {
     // host-buffer API (bf_search_shards / vs_ivf_search): two slots of pinned staging + device I/O buffers, so that chunk
     // c + 1's query upload and chunk c - 1's result download run beside chunk c's kernels (copy streams + events)
     struct PipeSlot {
-        vs::PinBuf<float> pin_q;   // [kMaxMulti * 32][128]
+        vs::PinBuf<float> pin_q;   // [kMaxMulti * 32][dim]
         vs::PinBuf<char> pin_out;  // dists | ids | flags of one chunk (k1 <= kTopkWideMax)
         // device I/O: views of the index's d_q / d_out_* / d_flags (slot 0) or of the own_* buffers (slot 1)
         float* d_q = nullptr;
@@ -346,7 +352,9 @@ int alloc_scratch(vs_index* h) {
     int tp;
     scan_geometry(std::max<int64_t>(h->n_rows, 1), h->num_cus, h->max_grid, tp);
     h->max_grid = std::max(h->max_grid, h->num_cus);
-    if ((rc = h->d_q.alloc((size_t)kMaxMulti * 32 * vs::kDim))) return rc;
+    if ((rc = h->d_q.alloc((size_t)kMaxMulti * 32 * h->dim))) return rc;
+    if (h->general && ((rc = h->d_nd_qfrag.alloc((size_t)kMaxMulti * 32 * h->dim_p)) || (rc = h->d_nd_qnorm.alloc((size_t)kMaxMulti * 32))))
+        return rc;
     {
         const char* e = getenv("VSEARCH_LANES");
         h->n_lanes = e ? std::max(1, std::min(kMaxLanes, atoi(e))) : 1;
@@ -385,6 +393,18 @@ int alloc_scratch(vs_index* h) {
 // upload `rows x dim` floats in chunks through the default pageable path and compute norms
 int upload_vectors(vs_index* h, const float* host, int64_t rows) {
     int rc;
+    if (h->general) {  // [rows + 64][dim_p], zero filled: the padding of a row and the spare rows add exact zeros
+        const size_t ld = (size_t)h->dim_p, total = ((size_t)std::max<int64_t>(rows, 1) + vs::kScanPadRows) * ld;
+        if ((rc = h->d_vecs.alloc(total))) return rc;
+        HIPCHK(hipMemset(h->d_vecs, 0, total * sizeof(float)));
+        if ((rc = h->d_norm.alloc((size_t)rows + 64))) return rc;
+        HIPCHK(hipMemset(h->d_norm, 0, ((size_t)rows + 64) * sizeof(float)));
+        HIPCHK(hipMemcpy2D(h->d_vecs, ld * sizeof(float), host, (size_t)h->dim * sizeof(float), (size_t)h->dim * sizeof(float), (size_t)rows,
+                           hipMemcpyHostToDevice));
+        HIPCHK(vs::launch_row_sqnorm_ld(h->d_vecs, rows, h->dim, (int64_t)ld, h->d_norm, nullptr));
+        HIPCHK(hipDeviceSynchronize());
+        return VS_OK;
+    }
     if ((rc = h->d_vecs.alloc(((size_t)std::max<int64_t>(rows, 1) + vs::kScanPadRows) * vs::kDim))) return rc;
     HIPCHK(hipMemset(h->d_vecs + (size_t)std::max<int64_t>(rows, 1) * vs::kDim, 0, (size_t)vs::kScanPadRows * vs::kDim * sizeof(float)));
     if ((rc = h->d_norm.alloc((size_t)rows + 64))) return rc;
@@ -527,6 +547,37 @@ int g_stream = [] {
     return e ? atoi(e) : 1;
 }();
 
+// comparison toggle (VSEARCH_ND_FORCE=1): vs_bf_create builds a general index at dim 128 as well, so that scan_nd_kernel
+// can be set against the specialised 128-d paths on the same data (default 0: nothing changes)
+int g_nd_force = [] {
+    const char* e = getenv("VSEARCH_ND_FORCE");
+    return e ? atoi(e) : 0;
+}();
+
+// floats between consecutive device rows of a brute-force index
+inline int64_t row_ld(const vs_index* h) { return h->general ? h->dim_p : vs::kDim; }
+
+// the per-batch scan of an index: scan_kernel on 128-d rows, scan_nd_kernel on a general index
+hipError_t scan_any(vs_index* h, const vs::ScanParams& p, int grid, int kcap, int nqh, int mode, hipStream_t s) {
+    if (!h->general) return vs::launch_scan(p, grid, kcap, nqh, mode, s);
+    vs::ScanNdParams np{};
+    np.s = p;
+    np.dim = h->dim;
+    np.dim_p = h->dim_p;
+    np.qfrag = h->d_nd_qfrag;
+    np.qnorm = h->d_nd_qnorm;
+    return vs::launch_scan_nd(np, grid, kcap, nqh, mode, s);
+}
+
+// calls that are compiled for 128-d rows only
+int refuse_general(const vs_index* h, const char* what) {
+    if (!h || !h->general) return VS_OK;
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: not available on a general-dimension index (dim = %d); only dim == 128 is compiled in", what, h->dim);
+    set_error(msg);
+    return VS_ERR_UNSUPPORTED;
+}
+
 int ensure_wide(vs_index::Lane& L) {
     if (L.wide8.ready) return VS_OK;
     vs_index::Lane::Wide8 w;
@@ -559,7 +610,7 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     p.bnorm = h->d_norm;
     p.q = q_dev;
     p.n_batches = nb;
-    p.q_batch_stride = (int64_t)B * vs::kDim;
+    p.q_batch_stride = (int64_t)B * h->dim;
     p.metric = h->metric;
     p.id_offset = (int32_t)h->id_offset;
     p.nq_valid = B;
@@ -577,7 +628,8 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     // half the capacity (5.6 M rows at k = 5) would overflow on nearly every launch and run the fallback scan as well:
     // it takes the per-batch scan directly.
     const bool cap_ok = (double)h->n_rows * k1 <= 0.5 * 32768.0 * kWideSub * kWideCap;
-    const bool seeded = nb >= g_seed_min_batches && tiles_total >= 2 * vs::kSeedWaves && g_xchg_first_it >= 0 && cap_ok;
+    // (a general index has no seed sample and no streaming scan: per-batch scan_nd_kernel + merge, with the threshold exchange)
+    const bool seeded = !h->general && nb >= g_seed_min_batches && tiles_total >= 2 * vs::kSeedWaves && g_xchg_first_it >= 0 && cap_ok;
     int grid, tp;
     scan_geometry(h->n_rows, h->num_cus, grid, tp, seeded ? 0 : (u8_path ? 16 : 6) * vs::kScanWaves);
     const bool exchange = !seeded && grid >= 16 && tp >= (u8_path ? 16 : 6) * vs::kScanWaves && g_xchg_first_it >= 0;
@@ -588,7 +640,7 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     const bool i8_seed = h->d_vecs_u8 && h->metric == VS_METRIC_L2 && g_seed_i8;
     const bool stream = seeded && g_stream && (use_u8 ? (g_i8_wide > 0 && i8_seed) : true);
     const bool f32_filter = stream && !use_u8 && g_f32_filter && h->filter_ok;
-    if (!seeded && !use_u8 && nb < kOneMaxBatches && B <= kOneMaxQueries) {
+    if (!h->general && !seeded && !use_u8 && nb < kOneMaxBatches && B <= kOneMaxQueries) {
         // a short call on the fp32 rows: one launch per batch (lane lists, workgroup ranking, the last workgroup merges).
         // Batches of more than 16 queries stay with the per-batch scan below: with two column blocks per tile the
         // single-call kernel's lane lists cost more than that kernel's threshold exchange (measured at 1 M rows, B = 32:
@@ -765,7 +817,7 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
         p.invalid = invalid;
     }
     if (!stream) prof_begin(h, 0, s);
-    HIPCHK(vs::launch_scan(p, grid, kcap, nqh, vs::kModeTopK, s));
+    HIPCHK(scan_any(h, p, grid, kcap, nqh, vs::kModeTopK, s));
     if (!stream) prof_end(h, 0, s);
     // one merge launch ranks every (batch, query): lists are [batch*32 + q][workgroup][kcap]
     m.part_d = L.part_d;
@@ -786,7 +838,7 @@ int bf_multi_dev(vs_index* h, const float* q_dev, int nb, int B, int k1, float* 
                  hipStream_t user) {
     for (int b0 = 0; b0 < nb; b0 += kMaxMulti) {
         const int n = std::min(kMaxMulti, nb - b0);
-        int rc = bf_launch(h, h->lane[0], q_dev + (size_t)b0 * B * vs::kDim, n, B, k1, out_d + (size_t)b0 * B * k1,
+        int rc = bf_launch(h, h->lane[0], q_dev + (size_t)b0 * B * h->dim, n, B, k1, out_d + (size_t)b0 * B * k1,
                            out_i + (size_t)b0 * B * k1, flags ? flags + (size_t)b0 * B : nullptr, user);
         if (rc) return rc;
     }
@@ -810,7 +862,7 @@ int scores_dev(vs_index* h, const float* vecs, const float* norms, int64_t rows,
     p.tiles_per_wg = tp;
     p.store = scores;
     p.store_ld = ld;
-    HIPCHK(vs::launch_scan(p, grid, 8, B <= 16 ? 1 : 2, vs::kModeStore, s));
+    HIPCHK(scan_any(h, p, grid, 8, B <= 16 ? 1 : 2, vs::kModeStore, s));
     return VS_OK;
 }
 
@@ -866,7 +918,7 @@ int topw_launch(vs_index* h, const float* q_dev, int nb, int B, int k1, float* o
     int rc;
     prof_begin(h, 0, s);
     for (int b = 0; b < nb; ++b) {
-        const float* qb = q_dev + (size_t)b * B * vs::kDim;
+        const float* qb = q_dev + (size_t)b * B * h->dim;
         float* const od = out_d + (size_t)b * B * k1;
         int32_t* const oi = out_i + (size_t)b * B * k1;
         int32_t* const fl = flags ? flags + (size_t)b * B : nullptr;
@@ -911,7 +963,7 @@ int topw_launch(vs_index* h, const float* q_dev, int nb, int B, int k1, float* o
         int grid, tp;
         scan_geometry(n - l0, h->num_cus, grid, tp);
         p.tiles_per_wg = tp;
-        HIPCHK(vs::launch_scan(p, grid, 8, 2, vs::kModeFilter, s));
+        HIPCHK(scan_any(h, p, grid, 8, 2, vs::kModeFilter, s));
         vs::TopkWideParams f{};
         f.list[0] = {W.pre_d, W.pre_i, vs::kTopkWideMax, nullptr, k1, 0};
         f.list[1] = {W.f_d, W.f_row, kTopwFilterCap, W.fz, kTopwFilterCap, (int32_t)h->id_offset};
@@ -940,7 +992,7 @@ int topw_launch(vs_index* h, const float* q_dev, int nb, int B, int k1, float* o
         const int nc = W.n_chunks;
         for (int c = 0; c < nc; ++c) {
             const int64_t r0 = (int64_t)c * W.chunk, rows = std::min(W.chunk, n - r0);
-            if ((rc = scores_dev(h, h->d_vecs + (size_t)r0 * vs::kDim, h->d_norm + r0, rows, qb, B, W.full, W.chunk, s, overflow)))
+            if ((rc = scores_dev(h, h->d_vecs + (size_t)r0 * row_ld(h), h->d_norm + r0, rows, qb, B, W.full, W.chunk, s, overflow)))
                 return rc;
             vs::TopkWideParams d{};
             d.dense = W.full;
@@ -1531,8 +1583,8 @@ int ensure_pipe(vs_index* h) {
     int rc;
     for (int i = 0; i < 2; ++i) {
         vs_index::PipeSlot& S = P[i];
-        if ((rc = S.pin_q.alloc(nqc * vs::kDim)) || (rc = S.pin_out.alloc(nqc * (2 * vs::kTopkWideMax + 1) * sizeof(float)))) return rc;
-        if (i == 1 && ((rc = S.own_q.alloc(nqc * vs::kDim)) || (rc = S.own_out_d.alloc(nqc * vs::kTopkWideMax)) ||
+        if ((rc = S.pin_q.alloc(nqc * h->dim)) || (rc = S.pin_out.alloc(nqc * (2 * vs::kTopkWideMax + 1) * sizeof(float)))) return rc;
+        if (i == 1 && ((rc = S.own_q.alloc(nqc * h->dim)) || (rc = S.own_out_d.alloc(nqc * vs::kTopkWideMax)) ||
                        (rc = S.own_out_i.alloc(nqc * vs::kTopkWideMax)) ||
                        (rc = S.own_flags.alloc(nqc))))
             return rc;
@@ -1597,6 +1649,7 @@ int vs_prof_enable(vs_index* h, int on) {
 }
 
 int vs_ivf_widek_stats(vs_index* h, int64_t* out, int reset) {
+    if (refuse_general(h, "vs_ivf_widek_stats")) return VS_ERR_UNSUPPORTED;
     if (!h || h->kind != 1 || !out) {
         set_error("vs_ivf_widek_stats: bad arguments");
         return VS_ERR_INVALID;
@@ -1650,18 +1703,30 @@ int vs_prof_read_launches(vs_index* h, int which, double* ms_out, int64_t cap, i
 }
 
 // ------------------------------------------------------------------------------------- brute force
-static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset, vs_index** out);
+static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset, vs_index** out,
+                          bool any_dim);
 int vs_bf_create(const float* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset,
                  vs_index** out) {
-    return guarded([&]() -> int { return bf_create_impl(base_host, n_rows, dim, metric, device, id_offset, out); });
+    return guarded([&]() -> int { return bf_create_impl(base_host, n_rows, dim, metric, device, id_offset, out, false); });
+}
+int vs_bf_create_nd(const float* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset, vs_index** out) {
+    return guarded([&]() -> int { return bf_create_impl(base_host, n_rows, dim, metric, device, id_offset, out, true); });
 }
 static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset,
-                          vs_index** out) {
+                          vs_index** out, bool any_dim) {
     if (!out || !base_host || n_rows <= 0) {
-        set_error("vs_bf_create: bad arguments");
+        set_error(any_dim ? "vs_bf_create_nd: bad arguments" : "vs_bf_create: bad arguments");
         return VS_ERR_INVALID;
     }
-    if (dim != vs::kDim) {
+    if (any_dim && dim < 1) {
+        set_error("vs_bf_create_nd: dim must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (any_dim && dim > vs::kNdMaxDim) {
+        set_error("vs_bf_create_nd: dim > 2048 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (!any_dim && dim != vs::kDim) {
         set_error("only dim == 128 is compiled in");
         return VS_ERR_UNSUPPORTED;
     }
@@ -1684,12 +1749,18 @@ static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int m
     h->kind = 0;
     h->device = device;
     h->dim = dim;
+    h->general = dim != vs::kDim || g_nd_force != 0;
+    h->dim_p = h->general ? vs::nd_dim_p(dim) : dim;
     h->metric = metric;
     h->n_rows = h->n_total = n_rows;
     h->id_offset = id_offset;
     if ((rc = upload_vectors(h, base_host, n_rows)) || (rc = alloc_scratch(h))) {
         vs_destroy(h);
         return rc;
+    }
+    if (h->general) {  // fp32 rows only: no int8 copy, no seed sample
+        *out = h;
+        return VS_OK;
     }
     if (metric == VS_METRIC_L2 && (rc = build_u8_copy(h, base_host, n_rows))) {
         vs_destroy(h);
@@ -1716,6 +1787,7 @@ static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int m
 }
 
 int vs_ivf_set_metric(vs_index* h, int metric) {
+    if (refuse_general(h, "vs_ivf_set_metric")) return VS_ERR_UNSUPPORTED;
     if (!h || h->kind != 1 || (metric != VS_METRIC_L2 && metric != VS_METRIC_IP)) {
         set_error("vs_ivf_set_metric: an IVF index and VS_METRIC_L2 or VS_METRIC_IP");
         return VS_ERR_INVALID;
@@ -1729,6 +1801,7 @@ int vs_set_precision(vs_index* h, int precision) {
         set_error("vs_set_precision: 0 = auto, 1 = fp32, 2 = int8");
         return VS_ERR_INVALID;
     }
+    if (precision == 2 && h->general) return refuse_general(h, "vs_set_precision(2)");
     if (precision == 2 && !h->d_vecs_u8) {
         set_error("int8 path unavailable: the base is not integer valued in [0, 255] (or the index is not brute-force L2)");
         return VS_ERR_UNSUPPORTED;
@@ -1800,7 +1873,7 @@ int vs_bf_search_topk_dev_multi(vs_index* h, const float* queries_dev, int n_bat
     const int k1 = k + 1;
     for (int b0 = 0; b0 < n_batches; b0 += kMaxMulti) {
         const int n = std::min(kMaxMulti, n_batches - b0);
-        if ((rc = topw_launch(h, queries_dev + (size_t)b0 * B * vs::kDim, n, B, k1, dists_dev + (size_t)b0 * B * k1,
+        if ((rc = topw_launch(h, queries_dev + (size_t)b0 * B * h->dim, n, B, k1, dists_dev + (size_t)b0 * B * k1,
                               ids_dev + (size_t)b0 * B * k1, flags_dev ? flags_dev + (size_t)b0 * B : nullptr, st)))
             return rc;
     }
@@ -2320,6 +2393,7 @@ int vs_ivf_load(const char* index_dir, int device, int rank, int world, vs_index
 }
 
 int vs_ivf_save(vs_index* h, const char* index_dir) {
+    if (refuse_general(h, "vs_ivf_save")) return VS_ERR_UNSUPPORTED;
     if (!h || h->kind != 1 || !index_dir) {
         set_error("vs_ivf_save: bad arguments");
         return VS_ERR_INVALID;
@@ -2363,6 +2437,7 @@ int vs_ivf_save(vs_index* h, const char* index_dir) {
 
 int vs_ivf_search_dev(vs_index* h, const float* queries_dev, int B, int k, int nprobe, int32_t* ids_dev,
                       float* dists_dev, void* stream) {
+    if (refuse_general(h, "vs_ivf_search_dev")) return VS_ERR_UNSUPPORTED;
     if (!h || h->kind != 1 || !queries_dev || !ids_dev || !dists_dev || B < 1 || B > vs::kMaxBatch || k < 1 || nprobe < 1) {
         set_error("vs_ivf_search_dev: bad arguments");
         return VS_ERR_INVALID;
@@ -2382,6 +2457,7 @@ int vs_ivf_search_dev(vs_index* h, const float* queries_dev, int B, int k, int n
 
 int vs_ivf_search_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k, int nprobe, int32_t* ids_dev,
                             float* dists_dev, void* stream) {
+    if (refuse_general(h, "vs_ivf_search_dev_multi")) return VS_ERR_UNSUPPORTED;
     if (!h || h->kind != 1 || !queries_dev || !ids_dev || !dists_dev || n_batches < 1 || B < 1 || B > vs::kMaxBatch || k < 1 ||
         nprobe < 1) {
         set_error("vs_ivf_search_dev_multi: bad arguments");
@@ -2806,6 +2882,7 @@ int vs_bf_search_dev_sharded(vs_index* h, vs_comm* c, const float* queries_dev, 
         set_error("vs_bf_search_dev_sharded: bad arguments");
         return VS_ERR_INVALID;
     }
+    if (refuse_general(h, "vs_bf_search_dev_sharded")) return VS_ERR_UNSUPPORTED;
     int rc = set_device(h);
     if (rc) return rc;
     const int k1 = k + 1;
@@ -2825,6 +2902,7 @@ int vs_bf_search_dev_sharded(vs_index* h, vs_comm* c, const float* queries_dev, 
 
 int vs_ivf_search_dev_sharded(vs_index* h, vs_comm* c, const float* queries_dev, int n_batches, int B, int k, int nprobe,
                               int32_t* ids_dev, float* dists_dev, void* stream) {
+    if (refuse_general(h, "vs_ivf_search_dev_sharded")) return VS_ERR_UNSUPPORTED;
     if (!h || !c || h->kind != 1 || !queries_dev || !ids_dev || !dists_dev || n_batches < 1 || B < 1 || B > vs::kMaxBatch || k < 1 ||
         nprobe < 1) {
         set_error("vs_ivf_search_dev_sharded: bad arguments");
@@ -2879,6 +2957,8 @@ int vs_ivf_search_dev_vshards(vs_index* const* shards, int G, const float* queri
         set_error("vs_ivf_search_dev_vshards: bad arguments");
         return VS_ERR_INVALID;
     }
+    for (int r = 0; r < G; ++r)
+        if (shards[r] && refuse_general(shards[r], "vs_ivf_search_dev_vshards")) return VS_ERR_UNSUPPORTED;
     for (int r = 0; r < G; ++r)
         if (!shards[r] || shards[r]->kind != 1 || shards[r]->world != G || shards[r]->rank != r || shards[r]->device != shards[0]->device ||
             shards[r]->nlist != shards[0]->nlist || !ivf_wide_ok(shards[r], k)) {
@@ -2972,12 +3052,13 @@ int resolve_ties_shards(const Shards& S, const std::vector<int32_t>& meta /*[G][
     float* const cd = reinterpret_cast<float*>(cr + (size_t)G * 32 * kTieCap);
     float* const tau0 = reinterpret_cast<float*>(Bf.tau);      // shard 0's part: the bound every shard filters with
     float* const dense0 = reinterpret_cast<float*>(Bf.dense);  // shard 0's part: [B][L0p]
-    std::vector<float> qbuf((size_t)32 * vs::kDim), row;
+    const size_t qd = (size_t)o->dim;  // floats per query in the caller's buffer and in d_q
+    std::vector<float> qbuf((size_t)32 * qd), row;
     for (size_t f0 = 0; f0 < flagged.size(); f0 += 32) {
         const int B = (int)std::min<size_t>(32, flagged.size() - f0);
         for (int b = 0; b < B; ++b)
-            std::memcpy(&qbuf[(size_t)b * vs::kDim], queries_host + flagged[f0 + b] * vs::kDim, vs::kDim * sizeof(float));
-        HIPCHK(hipMemcpyAsync(o->d_q, qbuf.data(), (size_t)B * vs::kDim * sizeof(float), hipMemcpyHostToDevice, st));
+            std::memcpy(&qbuf[(size_t)b * qd], queries_host + flagged[f0 + b] * qd, qd * sizeof(float));
+        HIPCHK(hipMemcpyAsync(o->d_q, qbuf.data(), (size_t)B * qd * sizeof(float), hipMemcpyHostToDevice, st));
         if (S.first == 0) {
             vs_index* h0 = S.hs[0];
             if ((rc = scores_dev(h0, h0->d_vecs, h0->d_norm, L0, o->d_q, B, dense0, L0p, st))) return rc;
@@ -3033,7 +3114,7 @@ int resolve_ties_shards(const Shards& S, const std::vector<int32_t>& meta /*[G][
             int grid, tp;
             scan_geometry(h->n_rows - rb, h->num_cus, grid, tp);
             p.tiles_per_wg = tp;
-            HIPCHK(vs::launch_scan(p, grid, 8, 2, vs::kModeFilter, st));
+            HIPCHK(scan_any(h, p, grid, 8, 2, vs::kModeFilter, st));
         }
         if ((rc = S.exchange(Bf.pack, kShPackWords, st))) return rc;
         HIPCHK(hipMemcpyAsync(dense, dense0, (size_t)B * L0p * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -3116,7 +3197,7 @@ int resolve_ties_shards(const Shards& S, const std::vector<int32_t>& meta /*[G][
             for (size_t i = 0; i < S.hs.size(); ++i) {
                 vs_index* h = S.hs[i];
                 const int g = S.first + (int)i;
-                if ((rc = scores_dev(h, h->d_vecs, h->d_norm, h->n_rows, o->d_q + (size_t)b * vs::kDim, 1,
+                if ((rc = scores_dev(h, h->d_vecs, h->d_norm, h->n_rows, o->d_q + (size_t)b * qd, 1,
                                      reinterpret_cast<float*>(Bf.row + (size_t)g * ldm), ldm, st)))
                     return rc;
             }
@@ -3206,7 +3287,7 @@ int bf_search_shards(const Shards& S, const float* queries_host, int64_t nq, int
         if (full) r2 = step(P.d_q, full, batch, P.d_out_d, P.d_out_i, P.d_flags, force_f32);
         if (!r2 && rem) {
             const size_t o0 = (size_t)full * batch;
-            r2 = step(P.d_q + o0 * vs::kDim, 1, rem, P.d_out_d + o0 * k1, P.d_out_i + o0 * k1, P.d_flags + o0, force_f32);
+            r2 = step(P.d_q + o0 * (size_t)o->dim, 1, rem, P.d_out_d + o0 * k1, P.d_out_i + o0 * k1, P.d_flags + o0, force_f32);
         }
         return r2;
     };
@@ -3223,8 +3304,8 @@ int bf_search_shards(const Shards& S, const float* queries_host, int64_t nq, int
         const double t0 = now_ms();
         P.q0 = q0;
         P.n = n;
-        std::memcpy(P.pin_q, queries_host + q0 * vs::kDim, (size_t)n * vs::kDim * sizeof(float));
-        HIPCHK(hipMemcpyAsync(P.d_q, P.pin_q, (size_t)n * vs::kDim * sizeof(float), hipMemcpyHostToDevice, o->s_h2d));
+        std::memcpy(P.pin_q, queries_host + q0 * o->dim, (size_t)n * o->dim * sizeof(float));
+        HIPCHK(hipMemcpyAsync(P.d_q, P.pin_q, (size_t)n * o->dim * sizeof(float), hipMemcpyHostToDevice, o->s_h2d));
         HIPCHK(hipEventRecord(P.ev_h2d, o->s_h2d));
         tm.h2d_ms += now_ms() - t0;
         HIPCHK(hipStreamWaitEvent(st, P.ev_h2d, 0));
@@ -3476,6 +3557,7 @@ int vs_bf_search_sharded(vs_index* h, vs_comm* c, const float* queries_host, int
         set_error("vs_bf_search_sharded: bad arguments");
         return VS_ERR_INVALID;
     }
+    if (refuse_general(h, "vs_bf_search_sharded")) return VS_ERR_UNSUPPORTED;
     if (h->device != c->device) {
         set_error("index and communicator live on different devices");
         return VS_ERR_INVALID;
@@ -3503,6 +3585,8 @@ int vs_bf_search_vshards(vs_index* const* shards, int G, const float* queries_ho
         return VS_ERR_INVALID;
     }
     for (int g = 0; g < G; ++g)
+        if (shards[g] && refuse_general(shards[g], "vs_bf_search_vshards")) return VS_ERR_UNSUPPORTED;
+    for (int g = 0; g < G; ++g)
         if (!shards[g] || shards[g]->kind != 0 || shards[g]->device != shards[0]->device || shards[g]->metric != shards[0]->metric ||
             shards[g]->batch != shards[0]->batch) {
             set_error("vs_bf_search_vshards: shards must be brute-force indexes on one device with one metric and batch size");
@@ -3522,6 +3606,7 @@ int vs_bf_search_vshards(vs_index* const* shards, int G, const float* queries_ho
 
 int vs_ivf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int nprobe, int32_t* ids, float* dists,
                   int64_t* total_candidates, vs_timing* timing) {
+    if (refuse_general(h, "vs_ivf_search")) return VS_ERR_UNSUPPORTED;
     if (!h || h->kind != 1 || !queries_host || !ids || !dists || nq < 0 || k < 1 || nprobe < 1) {
         set_error("vs_ivf_search: bad arguments");
         return VS_ERR_INVALID;
@@ -3540,6 +3625,7 @@ int vs_ivf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int
 
 int vs_ivf_search_sharded(vs_index* h, vs_comm* c, const float* queries_host, int64_t nq, int k, int nprobe, int32_t* ids,
                           float* dists, int64_t* total_candidates, vs_timing* timing) {
+    if (refuse_general(h, "vs_ivf_search_sharded")) return VS_ERR_UNSUPPORTED;
     if (!h || !c || h->kind != 1 || !queries_host || !ids || !dists || nq < 0 || k < 1 || nprobe < 1) {
         set_error("vs_ivf_search_sharded: bad arguments");
         return VS_ERR_INVALID;

@@ -12,12 +12,12 @@ namespace vs {
 // right, then the scalar tail (cpu_baseline.cpp:95-114).  8 threads per row.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void row_sqnorm_kernel(const float* __restrict__ v, int64_t rows, int dim,
-                                                         float* __restrict__ out) {
+                                                         int64_t ld, float* __restrict__ out) {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t row = gid >> 3;
     const int j = (int)(gid & 7);
     const bool ok = row < rows;
-    const float* src = v + (ok ? row : 0) * dim;
+    const float* src = v + (ok ? row : 0) * ld;
     float acc = 0.f;
     const int d8 = dim & ~7;
     for (int i = 0; i < d8; i += 8) {
@@ -34,10 +34,14 @@ __global__ __launch_bounds__(256) void row_sqnorm_kernel(const float* __restrict
 }
 
 hipError_t launch_row_sqnorm(const float* v, int64_t rows, int dim, float* out, hipStream_t s) {
+    return launch_row_sqnorm_ld(v, rows, dim, dim, out, s);
+}
+
+hipError_t launch_row_sqnorm_ld(const float* v, int64_t rows, int dim, int64_t ld, float* out, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
     const int64_t threads = rows * 8;
     const int grid = (int)((threads + 255) / 256);
-    hipLaunchKernelGGL(row_sqnorm_kernel, dim3(grid), dim3(256), 0, s, v, rows, dim, out);
+    hipLaunchKernelGGL(row_sqnorm_kernel, dim3(grid), dim3(256), 0, s, v, rows, dim, ld, out);
     return hipGetLastError();
 }
 

@@ -56,6 +56,20 @@ struct ScanParams {
 // Brute-force / coarse scan.  kcap in {8, 16}; nqh = 1 (<=16 queries) or 2.
 hipError_t launch_scan(const ScanParams& p, int grid, int kcap, int nqh, int mode, hipStream_t s);
 
+// General-dimension scan (vs_scan_nd.hip): ScanParams as above for kModeTopK / kModeStore / kModeFilter, with
+// rows of dim_p = nd_dim_p(dim) floats ([n_rows + kScanPadRows][dim_p], zero padded) and queries of dim floats
+// ([n_batches][nq_valid][dim], unpadded; q_batch_stride in floats).  A preparation launch writes the queries in MFMA
+// B-fragment order and their squared norms into the caller's scratch; the fp32 fields of ScanParams are the only ones read.
+constexpr int kNdMaxDim = 2048;
+constexpr int nd_dim_p(int dim) { return (dim + 15) & ~15; }  // whole 64-byte segments
+struct ScanNdParams {
+    ScanParams s;
+    int dim, dim_p;
+    float* qfrag;            // scratch [n_batches][dim_p / 16][2][64][4]: fragment (c, h, lane) = Q[16 h + (lane & 15)][16 c + 4 (lane >> 4) ..]
+    float* qnorm;            // scratch [n_batches][32]
+};
+hipError_t launch_scan_nd(const ScanNdParams& p, int grid, int kcap, int nqh, int mode, hipStream_t s);
+
 // bf16 prefilter of the fp32 streaming scan (scan_f32f_kernel).  With S = q.b exact, S_fl the fp32 chain of
 // scan_f32s_kernel and S' the v_mfma_f32_16x16x32_bf16 sum of q' = bf16(q), b' = bf16(b):
 //   |S_fl - S'| <= |S_fl - S| + |S - q'.b'| + |q'.b' - S'|
@@ -304,6 +318,7 @@ constexpr int kKppBlockRows = 1024;
 
 // ||v||^2 per row in the reference's AVX2 summation order (cpu_baseline.cpp:95-114).
 hipError_t launch_row_sqnorm(const float* v, int64_t rows, int dim, float* out, hipStream_t s);
+hipError_t launch_row_sqnorm_ld(const float* v, int64_t rows, int dim, int64_t ld, float* out, hipStream_t s);  // rows ld floats apart
 // shard constants of the bf16 prefilter: out[0..2] = max of ||b||^2, ||b - bf16(b)||^2, ||bf16(b)||^2 as double bits,
 // out[3] = 1 when a row is not well scaled (FilterStats); out must be zeroed before
 hipError_t launch_row_filter_stats(const float* v, int64_t rows, unsigned long long* out, hipStream_t s);

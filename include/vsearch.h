@@ -111,6 +111,20 @@ VS_API int vs_select_topk_slots(const int32_t* rows, const float* dists, int64_t
 VS_API int vs_bf_create(const float* base_host, int64_t n_rows, int dim, int metric,
                         int device, int64_t id_offset, vs_index** out);
 
+/* The same for any vector length, as cpu_baseline.cpp reads whatever dimension the .fvecs
+ * header states: 1 <= dim <= 2048 (dim < 1: VS_ERR_INVALID, dim > 2048: VS_ERR_UNSUPPORTED).
+ * dim == 128 gives exactly vs_bf_create's index.  Any other dim gives a "general" index: fp32
+ * rows padded to a multiple of 16 floats, scanned by the general-dimension kernel.  It is
+ * accepted by vs_bf_search, vs_bf_search_topk, vs_bf_search_dev, vs_bf_search_dev_multi,
+ * vs_bf_search_topk_dev_multi, vs_bf_scores_dev, vs_set_batch, vs_index_rows, vs_index_dim,
+ * vs_prof_* and vs_destroy, with the same signatures and output layouts (queries are
+ * [nq][dim], unpadded).  vs_set_precision: 0 and 1 both mean the fp32 rows, 2 returns
+ * VS_ERR_UNSUPPORTED (a byte copy of the rows for other dimensions is a follow-up).  The
+ * sharded calls (vs_bf_search_dev_sharded, vs_bf_search_sharded, vs_bf_search_vshards) and
+ * every vs_ivf_* call return VS_ERR_UNSUPPORTED on a general index; IVF and q8 stay at 128. */
+VS_API int vs_bf_create_nd(const float* base_host, int64_t n_rows, int dim, int metric,
+                           int device, int64_t id_offset, vs_index** out);
+
 /* Fixed model batch, like QnnRunner::getBatchSize (QnnRunner.h:37); 1..32, default 32.
  * Larger query sets are processed in batches of this size, the last one
  * zero-padded (main.cpp:206-211). */

@@ -69,14 +69,16 @@ struct Result {  // cpu_baseline.cpp:13-19
     bool operator<(const Result& other) const { return dist < other.dist; }
 };
 
+// Any vector length 1 <= dim <= 2048: 128-d bases take vs_bf_create, the others vs_bf_create_nd (a general index:
+// one GPU, fp32 rows; the sharded calls refuse it with the library's message).
 class ExactSearch {
 public:
     ExactSearch(const std::vector<float>& base, int rows, int dim, int device = 0, int metric = VS_METRIC_L2) {
-        check(vs_bf_create(base.data(), rows, dim, metric, device, 0, &h_));
+        check((dim == 128 ? vs_bf_create : vs_bf_create_nd)(base.data(), rows, dim, metric, device, 0, &h_));
     }
     // one rank's row shard of a larger base: ids are shard rows + id_offset (multi-GPU, vs_bf_search_sharded)
     ExactSearch(const float* shard, int64_t rows, int dim, int64_t id_offset, int device, int metric = VS_METRIC_L2) {
-        check(vs_bf_create(shard, rows, dim, metric, device, id_offset, &h_));
+        check((dim == 128 ? vs_bf_create : vs_bf_create_nd)(shard, rows, dim, metric, device, id_offset, &h_));
     }
     ~ExactSearch() { vs_destroy(h_); }
     ExactSearch(const ExactSearch&) = delete;

@@ -1,0 +1,112 @@
+"""General-dimension brute force at N = 1 M rows: device time per batch of the per-batch scan (64 batches of 32 queries per
+call, k = 5, fp32 rows) and the delivered row bytes 4 N dim_p per second as a fraction of the HBM peak, per dimension; and
+(--host) host-to-host QPS of search / search_topk with tie replay at one dimension.  One JSON line per measurement; every
+repeat is listed, not only the best.
+
+    python scripts/nd_bench.py [--dims 96,128,256,384,768,960,1024,2048] [--rows 1000000] [--reps 5]
+    python scripts/nd_bench.py --host --dims 960 --k 5,100 --nq 1000
+
+Each dimension runs in a process of its own.  128 is measured twice, alternating: the specialised per-batch scan_kernel
+(VSEARCH_STREAM=0: streaming scans off) and the general kernel on the same data (VSEARCH_ND_FORCE=1).
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+HBM_PEAK_GBS = 8000.0  # as bench.py
+
+
+def _data(rows, dim, seed):
+    rng = np.random.default_rng(seed)
+    out = np.empty((rows, dim), dtype=np.float32)
+    step = max(1, (1 << 26) // dim)
+    for r0 in range(0, rows, step):
+        out[r0:r0 + step] = rng.integers(0, 64, size=(min(step, rows - r0), dim), dtype=np.uint8)
+    return out
+
+
+def one(a, dim):
+    import torch
+    import __graft_entry__ as ge
+
+    pkg = ge.load_package()
+    base = _data(a.rows, dim, 1)
+    tag = os.environ.get("ND_BENCH_TAG", "general")
+    with pkg.BruteForceIndex(base) as idx:
+        idx.set_precision(1)
+        if a.host:
+            q = _data(a.nq, dim, 2)
+            for k in [int(x) for x in a.k.split(",")]:
+                idx.search_topk(q[:64], k)
+                qps = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    idx.search_topk(q, k)
+                    qps.append(a.nq / (time.perf_counter() - t0))
+                print(json.dumps({"what": "host_qps", "dim": dim, "rows": a.rows, "nq": a.nq, "k": k, "qps": [round(x, 1) for x in qps]}), flush=True)
+            return
+        dev = torch.device("cuda:0")
+        nb, B, k = 64, 32, 5
+        qd = torch.from_numpy(_data(nb * B, dim, 2)).to(dev)
+        oi = torch.empty((nb * B, k + 1), dtype=torch.int32, device=dev)
+        od = torch.empty((nb * B, k + 1), dtype=torch.float32, device=dev)
+        fl = torch.empty((nb * B,), dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream().cuda_stream
+        call = lambda: idx.search_dev_multi(qd.data_ptr(), nb, B, k, oi.data_ptr(), od.data_ptr(), fl.data_ptr(), st)
+        for _ in range(2):
+            call()
+        torch.cuda.synchronize()
+        us = []
+        for _ in range(a.reps):
+            idx.prof_enable(True)
+            call()
+            torch.cuda.synchronize()
+            ms, _n = idx.prof_read(0)
+            idx.prof_enable(False)
+            us.append(ms * 1e3 / nb)
+        dim_p = dim if tag == "scan_kernel" else (dim + 15) // 16 * 16
+        frac = [4.0 * a.rows * dim_p / (u * 1e-6) / 1e9 / HBM_PEAK_GBS for u in us]
+        print(json.dumps({"what": "scan_us_per_batch", "kernel": tag, "dim": dim, "dim_p": dim_p, "rows": a.rows,
+                          "us_per_batch": [round(u, 2) for u in us], "hbm_frac": [round(f, 4) for f in frac],
+                          "tflops": round(2.0 * B * a.rows * dim / (min(us) * 1e-6) / 1e12, 2)}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dims", default="96,128,256,384,768,960,1024,2048")
+    ap.add_argument("--rows", type=int, default=1_000_000)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--host", action="store_true")
+    ap.add_argument("--k", default="5,100")
+    ap.add_argument("--nq", type=int, default=1000)
+    ap.add_argument("--one", type=int, default=0, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.one:
+        one(a, a.one)
+        return
+    base_cmd = [sys.executable, os.path.abspath(__file__), "--rows", str(a.rows), "--reps", str(a.reps), "--k", a.k, "--nq", str(a.nq)]
+    if a.host:
+        base_cmd.append("--host")
+    for dim in [int(x) for x in a.dims.split(",")]:
+        runs = [({}, "general")]
+        if dim == 128 and not a.host:  # alternate the yardstick and the forced general kernel
+            y, g = ({"VSEARCH_STREAM": "0"}, "scan_kernel"), ({"VSEARCH_ND_FORCE": "1"}, "general")
+            runs = [y, g, y, g]
+        for env, tag in runs:
+            e = dict(os.environ)
+            e.update(env)
+            e["ND_BENCH_TAG"] = tag
+            r = subprocess.run(base_cmd + ["--one", str(dim)], env=e, timeout=900)
+            if r.returncode != 0:  # a failed or faulted step ends the run: nothing more is started on the GPU
+                sys.exit(r.returncode if r.returncode > 0 else 1)
+
+
+if __name__ == "__main__":
+    main()
