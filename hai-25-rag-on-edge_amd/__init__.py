@@ -654,6 +654,17 @@ def ivf_build(base, n_clusters: int, max_iter: int = 100, tol: float = 1e-4, see
     return vr, off, r2o, cents, int(it.value)
 
 
+def ivf_kmeans(base, nlist: int, max_iter: int, tol: float, seed: int, device: int = 0):
+    """vs_ivf_build as it is: no nlist clamp, no layout.  Returns (centroids [nlist x dim], assign [n_rows], n_iter)."""
+    base = _f32c(base)
+    n, d = base.shape
+    cents = np.empty((nlist, d), dtype=np.float32)
+    assign = np.empty(n, dtype=np.int32)
+    it = C.c_int(0)
+    _check(lib().vs_ivf_build(_p(base), n, d, nlist, max_iter, tol, seed, device, _p(cents), _p(assign), C.byref(it)))
+    return cents, assign, int(it.value)
+
+
 def clamp_nlist(n_vectors: int, n_clusters: int) -> int:
     """nlist clamp of create_ivf_model_reordered.py:92-94 (vs_ivf_clamp_nlist)."""
     return int(lib().vs_ivf_clamp_nlist(n_vectors, n_clusters))

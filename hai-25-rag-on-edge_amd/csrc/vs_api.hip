@@ -2167,6 +2167,42 @@ static int ivf_build_impl(const float* base_host, int64_t n_rows, int dim, int n
         set_error("only dim == 128 is compiled in");
         return VS_ERR_UNSUPPORTED;
     }
+    // One host pass before any device work: every value finite, max |x| inside the range of the fixed-point cluster
+    // sums (kmeans_accum_kernel: 64-bit sums of rint(x * 2^20) wrap once a sum leaves +-2^63), and the per-feature
+    // variance of sklearn's stopping rule: sum of squared centre shifts <= tol * mean per-feature variance.
+    double tol_abs = 0.0;
+    {
+        std::vector<double> sum(dim, 0.0), sq(dim, 0.0);
+        double amax = 0.0;
+        bool finite = true;
+        for (int64_t i = 0; i < n_rows; ++i)
+            for (int t = 0; t < dim; ++t) {
+                const double v = base_host[i * dim + t];
+                const double a = std::fabs(v);
+                if (!(a <= 3.4028234663852886e38)) finite = false;  // inf or NaN
+                else if (a > amax) amax = a;
+                sum[t] += v;
+                sq[t] += v * v;
+            }
+        if (!finite) {
+            set_error("vs_ivf_build: the base holds a NaN or an infinity");
+            return VS_ERR_INVALID;
+        }
+        // |sum of n quantised values| <= n * (max|x| * 2^20 + 1/2) must stay below 2^63
+        if ((double)n_rows * (amax + 0x1p-21) >= 0x1p43) {
+            set_error("vs_ivf_build: n_rows * max|x| = " + std::to_string((double)n_rows * amax) +
+                      " is outside the fixed-point range of the k-means update (must be < 2^43)");
+            return VS_ERR_INVALID;
+        }
+        if (tol > 0) {
+            double mv = 0;
+            for (int t = 0; t < dim; ++t) {
+                const double m = sum[t] / n_rows;
+                mv += sq[t] / n_rows - m * m;
+            }
+            tol_abs = tol * mv / dim;
+        }
+    }
     int rc = check_device(device);
     if (rc) return rc;
     HIPCHK(hipSetDevice(device));
@@ -2226,23 +2262,6 @@ static int ivf_build_impl(const float* base_host, int64_t n_rows, int dim, int n
             if (e == hipSuccess) e = hipDeviceSynchronize();
             HIPCHK(e);
         }
-    }
-    // sklearn's stopping rule: sum of squared centre shifts <= tol * mean per-feature variance
-    double tol_abs = 0.0;
-    if (tol > 0) {
-        std::vector<double> sum(dim, 0.0), sq(dim, 0.0);
-        for (int64_t i = 0; i < n_rows; ++i)
-            for (int t = 0; t < dim; ++t) {
-                const double v = base_host[i * dim + t];
-                sum[t] += v;
-                sq[t] += v * v;
-            }
-        double mv = 0;
-        for (int t = 0; t < dim; ++t) {
-            const double m = sum[t] / n_rows;
-            mv += sq[t] / n_rows - m * m;
-        }
-        tol_abs = tol * mv / dim;
     }
     int grid, tp;
     scan_geometry(n_rows, num_cus, grid, tp);

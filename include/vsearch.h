@@ -261,7 +261,35 @@ VS_API int vs_ivf_create(const float* vectors_reordered, int64_t n_rows, int dim
  * on the GPU, sklearn's default init; its RNG stream and greedy multi-trial variant are not reproduced, so the
  * centres are statistically, not bitwise, sklearn's; VSEARCH_KMEANS_INIT=random = nlist distinct random rows).
  * Outputs: centroids_out [nlist x dim], assign_out [n_rows] (cluster of every row); vs_ivf_layout turns the
- * assignment into the reordered layout of :108-128, vs_ivf_build_index does all of it. */
+ * assignment into the reordered layout of :108-128, vs_ivf_build_index does all of it.
+ *
+ * What a build computes, exactly (tests/test_gpu_ivf_build.py replays it on the CPU):
+ *   - seeding stream: splitmix64 with state s0 = seed * 0x9E3779B97F4A7C15 + 0x1234567 (mod 2^64); next() is
+ *     s += 0x9E3779B97F4A7C15; z = s; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *     return z ^ z >> 31.
+ *   - k-means++: centre 0 is row next() % n_rows.  Every further centre c draws one u = (next() >> 11) * 2^-53 and is the
+ *     first row (in row order) at which the running sum of D^2 (squared distance to the nearest earlier centre, summed in
+ *     double) exceeds u * total; when every D^2 is zero it is the last row.  A row with D^2 = 0 is never drawn while
+ *     another row has D^2 > 0.  (D^2 is summed per block of 1024 rows; on data whose sums round, the running sum inside
+ *     the chosen block may stay under the target, and the centre is then that block's last row with D^2 > 0.  With
+ *     exact sums, e.g. integer-valued rows with distances below 2^24, this cannot happen.)
+ *   - VSEARCH_KMEANS_INIT=random (read at every call): centre c is row next() % n_rows, drawn again while that row
+ *     number was already taken.
+ *   - assignment: the nearest centroid under fp32 ||x||^2 + ||c||^2 - 2 x.c; equal distances go to the lower centroid id.
+ *   - update: with A = the cluster's sum of rint(x * 2^20), accumulated exactly in 64-bit integers (order independent),
+ *     centroid = (float)((double)A / 2^20 / count): the conversion of A (exact while |A| < 2^53, e.g. integer-valued
+ *     rows, whose A has 20 zero low bits), one double division and one cast to float.  For rows on the 2^-20 grid with
+ *     |A| < 2^53 that is float(double(sum) / count); in general each component is within 2^-21 + 2^-24 |mean| of the
+ *     mean.  A cluster without rows keeps its centroid.
+ *   - max_iter = 0 returns the seeds and the assignment to them, *iters_done = 0.
+ *   - *iters_done = the number of updates performed: update t (t = 1, 2, ...) moves the centroids by s_t = the sum of
+ *     squared shifts; the build stops after the first update with s_t <= tol * mean per-feature variance (population
+ *     variance of every column, averaged over the columns) and reports that t, or max_iter when none qualifies.  With
+ *     tol = 0 it stops after the first update that moves nothing.  assign_out is the assignment to the returned
+ *     centroids.
+ *   - limits, checked on the host before any device work (VS_ERR_INVALID, nothing written to the outputs): every value
+ *     finite, and n_rows * (max|x| + 2^-21) < 2^43, the range in which the 64-bit fixed-point sums cannot wrap.
+ *   - nlist > n_rows or max_iter < 0: VS_ERR_INVALID; dim != 128: VS_ERR_UNSUPPORTED. */
 VS_API int vs_ivf_build(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol,
                         uint64_t seed, int device, float* centroids_out, int32_t* assign_out, int* iters_done);
 

@@ -171,6 +171,41 @@ def test_argument_validation(pkg):
     assert np.array_equal(vr, v[r2o])
 
 
+def test_ivf_build_argument_validation(pkg):
+    """vs_ivf_build refuses bad arguments and data outside the range of its fixed-point update on the host, before it
+    looks for a device: the same statuses with and without a GPU, outputs untouched."""
+    L = pkg.lib()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+
+    def call(base, nlist, max_iter=3, tol=0.0, dim=None):
+        cents = np.full((max(nlist, 1), 128), -7.25, dtype=np.float32)
+        assign = np.full(len(base), -77, dtype=np.int32)
+        it = C.c_int(-55)
+        rc = L.vs_ivf_build(p(base), len(base), base.shape[1] if dim is None else dim, nlist, max_iter, tol, 1, 0,
+                            p(cents), p(assign), C.byref(it))
+        assert np.all(cents == -7.25) and np.all(assign == -77) and it.value == -55
+        return rc, L.vs_last_error().decode()
+
+    good = pkg.synth_sift(64, seed=1)
+    assert call(good, 8, max_iter=-1)[0] == -1
+    assert call(good, 65)[0] == -1                                  # nlist > n_rows
+    assert call(good, 0)[0] == -1
+    assert call(np.zeros((64, 64), dtype=np.float32), 8)[0] == -5   # dim != 128
+    for bad_value in (np.nan, np.inf, -np.inf):
+        for tol in (0.0, 1e-4):
+            base = good.copy()
+            base[63, 127] = bad_value
+            rc, msg = call(base, 8, tol=tol)
+            assert rc == -1 and msg
+    big = good.copy()
+    big[5, 9] = -2.0 ** 37                                          # 64 * 2^37 = 2^43
+    rc, msg = call(big, 8)
+    assert rc == -1 and "2^43" in msg
+    big[5, 9] = -(2.0 ** 37 - 2.0 ** 14)                            # the fp32 number below: inside the limit
+    if pkg.device_count() == 0:
+        assert call(big, 8)[0] == -3 and call(good, 8)[0] == -3     # every host check passed: only the device is missing
+
+
 def test_q8_argument_validation(pkg):
     L = pkg.lib()
     h = C.c_void_p(None)
