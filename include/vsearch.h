@@ -146,7 +146,10 @@ VS_API int vs_ivf_set_metric(vs_index* h, int metric);
 /* Host-buffer search with the reference's exact semantics: ids/dists are
  * [nq x k], ascending distance, ties ordered exactly as select_topk leaves
  * them (flagged queries are re-resolved, see DESIGN.md "Ties").  k clamps to
- * n_rows; unused slots are id -1 / dist +inf. */
+ * n_rows; unused slots are id -1 / dist +inf.
+ * VS_METRIC_IP: dists holds the scores q.v, descending (the *_dev calls below return
+ * -q.v, ascending); equal scores are returned in ascending id, with no tie replay
+ * (timing->tie_queries stays 0). */
 VS_API int vs_bf_search(vs_index* h, const float* queries_host, int64_t nq, int k,
                         int32_t* ids, float* dists, vs_timing* timing);
 
@@ -171,7 +174,9 @@ VS_API int vs_bf_search_dev_multi(vs_index* h, const float* queries_dev, int n_b
 
 /* Wide k: 1 <= k <= 128.  For k <= 15 the result is exactly vs_bf_search's (same code path).  For k >= 16: the k best by
  * select_topk's slot semantics; order among equal distances = slot order, stably sorted.  k > 128 returns
- * VS_ERR_UNSUPPORTED.  The k >= 16 path scans the fp32 rows whatever vs_set_precision says (the distances are the same). */
+ * VS_ERR_UNSUPPORTED.  The k >= 16 path scans the fp32 rows whatever vs_set_precision says (the distances are the same).
+ * VS_METRIC_IP, for every k: the scores q.v, descending (vs_bf_search_topk_dev_multi returns -q.v, ascending); equal scores
+ * in ascending id, with no tie replay. */
 VS_API int vs_bf_search_topk(vs_index* h, const float* queries_host, int64_t nq, int k,
                              int32_t* ids, float* dists, vs_timing* timing);
 /* Device form of vs_bf_search_dev_multi for 1 <= k <= 128: outputs [n_batches*B x (k+1)] by (dist, id) ascending,
