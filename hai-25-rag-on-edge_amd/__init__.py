@@ -119,12 +119,16 @@ def lib():
         "vs_ivecs_read": (i32, [C.c_char_p, vp, i64, C.POINTER(i64), C.POINTER(i32)]),
         "vs_fvecs_write": (i32, [C.c_char_p, vp, i64, i32]),
         "vs_ivecs_write": (i32, [C.c_char_p, vp, i64, i32]),
+        "vs_bvecs_shape": (i32, [C.c_char_p, C.POINTER(i64), C.POINTER(i32)]),
+        "vs_bvecs_read": (i32, [C.c_char_p, vp, i64, C.POINTER(i64), C.POINTER(i32)]),
+        "vs_bvecs_write": (i32, [C.c_char_p, vp, i64, i32]),
         "vs_results_write": (i32, [C.c_char_p, vp, vp, i64, i32, i32]),
         "vs_synth_sift": (i32, [vp, i64, i64, i32, C.c_uint64]),
         "vs_synth_mixture": (i32, [vp, i64, i64, i32, C.c_uint64, i32, C.c_double, C.c_double]),
         "vs_select_topk_slots": (i32, [vp, vp, i64, i32, vp, vp]),
         "vs_bf_create": (i32, [vp, i64, i32, i32, i32, i64, C.POINTER(vp)]),
         "vs_bf_create_nd": (i32, [vp, i64, i32, i32, i32, i64, C.POINTER(vp)]),
+        "vs_bf_create_nd_u8": (i32, [vp, i64, i32, i32, i64, C.POINTER(vp)]),
         "vs_set_batch": (i32, [vp, i32]),
         "vs_set_precision": (i32, [vp, i32]),
         "vs_ivf_set_metric": (i32, [vp, i32]),
@@ -235,6 +239,22 @@ def read_ivecs(path: str) -> np.ndarray:
     return out
 
 
+def read_bvecs(path: str) -> np.ndarray:
+    """TEXMEX .bvecs ([int32 d][d x uint8] records) as a uint8 array."""
+    L = lib()
+    rows, dim = C.c_int64(0), C.c_int(0)
+    _check(L.vs_bvecs_shape(path.encode(), C.byref(rows), C.byref(dim)))
+    out = np.empty((rows.value, max(dim.value, 0)), dtype=np.uint8)
+    if out.size:
+        _check(L.vs_bvecs_read(path.encode(), _p(out), out.size, C.byref(rows), C.byref(dim)))
+    return out
+
+
+def write_bvecs(path: str, x) -> None:
+    x = np.ascontiguousarray(x, dtype=np.uint8)
+    _check(lib().vs_bvecs_write(path.encode(), _p(x), x.shape[0], x.shape[1]))
+
+
 def write_fvecs(path: str, x) -> None:
     x = _f32c(x)
     _check(lib().vs_fvecs_write(path.encode(), _p(x), x.shape[0], x.shape[1]))
@@ -335,7 +355,9 @@ class BruteForceIndex(_Index):
     to results.txt: ids and squared-L2 distances, ascending, reference tie order.
 
     Any vector length 1 <= d <= 2048: 128-d bases take vs_bf_create (every specialised path), the others
-    vs_bf_create_nd (fp32 rows, the general-dimension scan; no sharded calls, no int8 precision)."""
+    vs_bf_create_nd (fp32 rows, the general-dimension scan; no sharded calls, no int8 precision).  ``from_u8`` takes
+    uint8 rows instead (vs_bf_create_nd_u8): squared L2, and at dimensions other than 128 a byte copy of the rows beside
+    the fp32 ones, scanned with int8 MFMA for k <= 15 (set_precision 0 / 2; 1 = fp32 rows)."""
 
     def __init__(self, base, metric: int = METRIC_L2, device: int = 0, id_offset: int = 0):
         super().__init__()
@@ -346,6 +368,22 @@ class BruteForceIndex(_Index):
         create = lib().vs_bf_create if self.d == 128 else lib().vs_bf_create_nd
         _check(create(_p(base), self.n, self.d, metric, device, id_offset, C.byref(self._h)))
         self.d = self.getDim()  # (buffers of every call below are sized by the index's own dimension)
+
+    @classmethod
+    def from_u8(cls, base_u8, device: int = 0, id_offset: int = 0):
+        """An index over uint8 rows [N, d] (vs_bf_create_nd_u8)."""
+        base = np.asarray(base_u8)
+        if base.dtype != np.uint8:
+            raise ValueError("base_u8 must have dtype uint8")
+        if base.ndim != 2:
+            raise ValueError("base must be [N, d]")
+        base = np.ascontiguousarray(base)
+        self = cls.__new__(cls)
+        _Index.__init__(self)
+        self.n, self.d = base.shape
+        _check(lib().vs_bf_create_nd_u8(_p(base), self.n, self.d, device, id_offset, C.byref(self._h)))
+        self.d = self.getDim()
+        return self
 
     def search(self, queries, k: int, timing: Timing | None = None):
         q = _f32c(queries).reshape(-1, self.d)

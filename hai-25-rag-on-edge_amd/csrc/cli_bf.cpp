@@ -12,6 +12,8 @@
 //   vsearch_bf --groundtruth <base.fvecs> <query.fvecs> <out.ivecs> [k=100]
 //                                              : exact k-NN ground truth (TEXMEX .ivecs: one row of k ids per query, the
 //                                                ids of vs_bf_search_topk, 1 <= k <= 128), for vsearch_ivf's recall; one GPU
+//   a <base> or <query> file whose name ends in .bvecs is read as TEXMEX byte vectors: a byte base becomes an index over
+//   uint8 rows (vs_bf_create_nd_u8), byte queries are converted to float; the output files are the same
 //   ... --gpus N                               : any form on N GPUs, one process per GPU (forked before HIP starts): the base
 //                                                is row-sharded, per-shard top-(k+1) lists meet in one RCCL all-gather per
 //                                                32 batches (vs_bf_search_sharded); rank 0 writes the files
@@ -29,6 +31,7 @@
 #include <fstream>
 #include <iomanip>
 #include <iostream>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -116,6 +119,25 @@ void write_metrics(const std::string& path, const RunStats& r) {
 
 vsearch::RankSet g_ranks;
 
+bool is_bvecs(const std::string& f) { return f.size() >= 6 && f.compare(f.size() - 6, 6, ".bvecs") == 0; }
+
+// a vector file of either format: .bvecs rows land in `bytes` when the caller wants them as they are (a base), else as floats
+bool read_vectors(const std::string& f, std::vector<float>& data, std::vector<uint8_t>* bytes, int& rows, int& dim) {
+    if (!is_bvecs(f)) return vsearch::read_fvecs(f, data, rows, dim);
+    std::vector<uint8_t> b;
+    if (!vsearch::read_bvecs(f, b, rows, dim)) return false;
+    if (bytes) bytes->swap(b);
+    else data.assign(b.begin(), b.end());
+    return true;
+}
+
+// the index over rows [r0, r1) of a base read by read_vectors
+std::unique_ptr<vsearch::ExactSearch> make_index(const std::vector<float>& f, const std::vector<uint8_t>& bytes, bool byte_base,
+                                                 int64_t r0, int64_t r1, int dim, int device) {
+    if (byte_base) return std::make_unique<vsearch::ExactSearch>(bytes.data() + (size_t)r0 * dim, r1 - r0, dim, r0, device);
+    return std::make_unique<vsearch::ExactSearch>(f.data() + (size_t)r0 * dim, r1 - r0, dim, r0, device);
+}
+
 bool run_benchmark(const std::string& dataset_name, const std::string& base_file, const std::string& query_file, int k,
                    const std::string& output_file, const std::string& metrics_file, int batch) {
     using namespace std::chrono;
@@ -124,15 +146,16 @@ bool run_benchmark(const std::string& dataset_name, const std::string& base_file
     std::cout << "========================================\n" << std::endl;
 
     std::vector<float> Q_data, B_data;
+    std::vector<uint8_t> B_bytes;
     int Q_rows = 0, Q_dim = 0, B_rows = 0, B_dim = 0;
     std::cout << "Loading base file: " << base_file << std::endl;
-    if (!vsearch::read_fvecs(base_file, B_data, B_rows, B_dim)) {
+    if (!read_vectors(base_file, B_data, &B_bytes, B_rows, B_dim)) {
         std::cerr << "Error: " << vs_last_error() << std::endl;
         std::cerr << "Failed to load base file!" << std::endl;
         return false;
     }
     std::cout << "Loading query file: " << query_file << std::endl;
-    if (!vsearch::read_fvecs(query_file, Q_data, Q_rows, Q_dim)) {
+    if (!read_vectors(query_file, Q_data, nullptr, Q_rows, Q_dim)) {
         std::cerr << "Error: " << vs_last_error() << std::endl;
         std::cerr << "Failed to load query file!" << std::endl;
         return false;
@@ -147,7 +170,8 @@ bool run_benchmark(const std::string& dataset_name, const std::string& base_file
         const int64_t r0 = vsearch::shard_bound(B_rows, g_ranks.world, g_ranks.rank);
         const int64_t r1 = vsearch::shard_bound(B_rows, g_ranks.world, g_ranks.rank + 1);
         if (r1 <= r0) throw std::runtime_error("more GPUs than 16-row tiles in the base");
-        vsearch::ExactSearch index(B_data.data() + (size_t)r0 * B_dim, r1 - r0, B_dim, r0, g_ranks.rank);
+        const auto index_p = make_index(B_data, B_bytes, is_bvecs(base_file), r0, r1, B_dim, g_ranks.rank);
+        vsearch::ExactSearch& index = *index_p;
         // the device scans at most 32 queries per pass: a model batch of 64 (run_all.sh's grid) is two passes
         const int dev_batch = std::min(std::max(batch, 1), 32);
         index.setBatchSize(dev_batch);
@@ -294,8 +318,9 @@ bool run_q8(const std::string& docs_file, const std::string& query_file, int k, 
 // --groundtruth: the ids of vs_bf_search_topk as TEXMEX ground truth (main_ivf.cpp:35-50 reads it back)
 bool run_groundtruth(const std::string& base_file, const std::string& query_file, const std::string& out_file, int k) {
     std::vector<float> Q_data, B_data;
+    std::vector<uint8_t> B_bytes;
     int Q_rows = 0, Q_dim = 0, B_rows = 0, B_dim = 0;
-    if (!vsearch::read_fvecs(base_file, B_data, B_rows, B_dim) || !vsearch::read_fvecs(query_file, Q_data, Q_rows, Q_dim)) {
+    if (!read_vectors(base_file, B_data, &B_bytes, B_rows, B_dim) || !read_vectors(query_file, Q_data, nullptr, Q_rows, Q_dim)) {
         std::cerr << "Error: " << vs_last_error() << std::endl;
         return false;
     }
@@ -304,7 +329,8 @@ bool run_groundtruth(const std::string& base_file, const std::string& query_file
         return false;
     }
     try {
-        vsearch::ExactSearch index(B_data, B_rows, B_dim, 0);
+        const auto index_p = make_index(B_data, B_bytes, is_bvecs(base_file), 0, B_rows, B_dim, 0);
+        vsearch::ExactSearch& index = *index_p;
         std::vector<int32_t> ids((size_t)Q_rows * k);
         std::vector<float> dists((size_t)Q_rows * k);
         vs_timing tm{};

@@ -86,6 +86,15 @@ struct vs_index {
     int dim_p = 0;
     vs::DevBuf<float> d_nd_qfrag;  // [kMaxMulti][dim_p / 16][2][64][4] scratch of launch_scan_nd
     vs::DevBuf<float> d_nd_qnorm;  // [kMaxMulti][32]
+    // general index made from uint8 rows (vs_bf_create_nd_u8): the rows once more as int8 (x - 128), scanned by
+    // scan_nd_i8_kernel for k <= 15.  Absent when max ||b||^2 >= 2^24: no batch could ever run on it.
+    bool nd_from_u8 = false;
+    int dim_b = 0;                   // dim rounded up to 64 bytes
+    int32_t nd_bmax = 0;             // max ||b||^2 over the base (< 2^24)
+    vs::DevBuf<int8_t> d_nd_u8;      // [n_rows + 64][dim_b], zero padded
+    vs::DevBuf<int32_t> d_nd_rterm;  // [n_rows + 64] sum (b - 128)^2
+    vs::DevBuf<int8_t> d_nd_q8frag;  // [kMaxMulti][dim_b / 64][2][64][16] scratch of launch_scan_nd_i8
+    vs::DevBuf<int32_t> d_nd_qterm;  // [kMaxMulti][32]
     int metric = VS_METRIC_L2;
     int64_t n_rows = 0;   // rows resident on this GPU
     int64_t n_total = 0;  // rows of the whole (unsharded) index
@@ -459,6 +468,38 @@ int build_u8_copy(vs_index* h, const float* host, int64_t rows, std::vector<int8
     return VS_OK;
 }
 
+// byte copy of a general index made from uint8 rows: int8 (x - 128) rows padded to dim_b bytes, rterm = sum (b - 128)^2
+// over the real dim (dist = qterm + rterm - 2 q'.b', see vs_scan_nd_i8.hip), and max ||b||^2 for the exactness rule
+int build_nd_u8_copy(vs_index* h, const uint8_t* rows_u8, int64_t rows) {
+    const size_t ld = (size_t)h->dim_b;
+    std::vector<int8_t> bytes(((size_t)rows + vs::kScanPadRows) * ld, 0);  // spare rows: block loads are not clamped
+    std::vector<int32_t> rterm((size_t)rows + 64, 0);
+    int64_t bmax = 0;
+    for (int64_t i = 0; i < rows; ++i) {
+        const uint8_t* src = rows_u8 + (size_t)i * h->dim;
+        int8_t* dst = bytes.data() + (size_t)i * ld;
+        int64_t n2 = 0;
+        int32_t t = 0;
+        for (int c = 0; c < h->dim; ++c) {
+            const int x = src[c], sb = x - 128;
+            dst[c] = (int8_t)sb;
+            n2 += x * x;
+            t += sb * sb;
+        }
+        rterm[(size_t)i] = t;
+        bmax = std::max(bmax, n2);
+    }
+    if (bmax >= (int64_t)1 << 24) return VS_OK;  // ||q||^2 + ||b||^2 <= 2^24 fails for every batch: fp32 rows only
+    h->nd_bmax = (int32_t)bmax;
+    int rc;
+    if ((rc = h->d_nd_u8.alloc(bytes.size())) || (rc = h->d_nd_rterm.alloc(rterm.size())) || (rc = h->d_invalid.alloc((size_t)kMaxMulti)) ||
+        (rc = h->d_nd_q8frag.alloc((size_t)kMaxMulti * 32 * ld)) || (rc = h->d_nd_qterm.alloc((size_t)kMaxMulti * 32)))
+        return rc;
+    HIPCHK(hipMemcpy(h->d_nd_u8, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_nd_rterm, rterm.data(), rterm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    return VS_OK;
+}
+
 void prof_begin(vs_index* h, int which, hipStream_t s) {
     if (!h->prof) return;
     ProfSlot& ps = h->prof_slot[which];
@@ -557,9 +598,25 @@ int g_nd_force = [] {
 // floats between consecutive device rows of a brute-force index
 inline int64_t row_ld(const vs_index* h) { return h->general ? h->dim_p : vs::kDim; }
 
-// the per-batch scan of an index: scan_kernel on 128-d rows, scan_nd_kernel on a general index
+// whether a top-k launch on this index takes the byte scan of a general index (scan_nd_i8_kernel)
+inline bool nd_u8_path(const vs_index* h, bool force_f32) {
+    return h->general && h->d_nd_u8 && h->precision != 1 && h->metric == VS_METRIC_L2 && !force_f32;
+}
+
+// the per-batch scan of an index: scan_kernel on 128-d rows, scan_nd_kernel on a general index -- or, for a top-k launch
+// whose caller set the byte fields of p (bf_launch, under nd_u8_path), scan_nd_i8_kernel on its byte copy
 hipError_t scan_any(vs_index* h, const vs::ScanParams& p, int grid, int kcap, int nqh, int mode, hipStream_t s) {
     if (!h->general) return vs::launch_scan(p, grid, kcap, nqh, mode, s);
+    if (p.base_u8 && mode == vs::kModeTopK) {
+        vs::ScanNdI8Params bp{};
+        bp.s = p;
+        bp.dim = h->dim;
+        bp.dim_b = h->dim_b;
+        bp.bmax = h->nd_bmax;
+        bp.q8frag = h->d_nd_q8frag;
+        bp.qterm = h->d_nd_qterm;
+        return vs::launch_scan_nd_i8(bp, grid, kcap, nqh, s);
+    }
     vs::ScanNdParams np{};
     np.s = p;
     np.dim = h->dim;
@@ -815,6 +872,12 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
         p.base_u8 = h->d_vecs_u8;
         p.rterm = h->d_rterm;
         p.invalid = invalid;
+    }
+    if (nd_u8_path(h, force_f32)) {  // the verdict words are written (0 or 1) by the byte scan's preparation launch
+        p.base_u8 = h->d_nd_u8;
+        p.rterm = h->d_nd_rterm;
+        p.invalid = h->d_invalid;
+        m.invalid = h->d_invalid;
     }
     if (!stream) prof_begin(h, 0, s);
     HIPCHK(scan_any(h, p, grid, kcap, nqh, vs::kModeTopK, s));
@@ -1704,7 +1767,7 @@ int vs_prof_read_launches(vs_index* h, int which, double* ms_out, int64_t cap, i
 
 // ------------------------------------------------------------------------------------- brute force
 static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset, vs_index** out,
-                          bool any_dim);
+                          bool any_dim, const uint8_t* rows_u8 = nullptr);
 int vs_bf_create(const float* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset,
                  vs_index** out) {
     return guarded([&]() -> int { return bf_create_impl(base_host, n_rows, dim, metric, device, id_offset, out, false); });
@@ -1712,8 +1775,28 @@ int vs_bf_create(const float* base_host, int64_t n_rows, int dim, int metric, in
 int vs_bf_create_nd(const float* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset, vs_index** out) {
     return guarded([&]() -> int { return bf_create_impl(base_host, n_rows, dim, metric, device, id_offset, out, true); });
 }
+// uint8 rows: the checks of vs_bf_create_nd, then the rows as floats through the same path, plus the byte copy
+int vs_bf_create_nd_u8(const uint8_t* base_host, int64_t n_rows, int dim, int device, int64_t id_offset, vs_index** out) {
+    return guarded([&]() -> int {
+        if (!out || !base_host || n_rows <= 0) {
+            set_error("vs_bf_create_nd_u8: bad arguments");
+            return VS_ERR_INVALID;
+        }
+        if (dim < 1) {
+            set_error("vs_bf_create_nd_u8: dim must be at least 1");
+            return VS_ERR_INVALID;
+        }
+        if (dim > vs::kNdMaxDim) {
+            set_error("vs_bf_create_nd_u8: dim > 2048 is not compiled in");
+            return VS_ERR_UNSUPPORTED;
+        }
+        std::vector<float> f((size_t)n_rows * dim);
+        for (size_t i = 0; i < f.size(); ++i) f[i] = (float)base_host[i];
+        return bf_create_impl(f.data(), n_rows, dim, VS_METRIC_L2, device, id_offset, out, true, base_host);
+    });
+}
 static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset,
-                          vs_index** out, bool any_dim) {
+                          vs_index** out, bool any_dim, const uint8_t* rows_u8) {
     if (!out || !base_host || n_rows <= 0) {
         set_error(any_dim ? "vs_bf_create_nd: bad arguments" : "vs_bf_create: bad arguments");
         return VS_ERR_INVALID;
@@ -1758,7 +1841,15 @@ static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int m
         vs_destroy(h);
         return rc;
     }
-    if (h->general) {  // fp32 rows only: no int8 copy, no seed sample
+    if (h->general) {  // no seed sample; fp32 rows only, unless the rows came as uint8 (vs_bf_create_nd_u8)
+        if (rows_u8) {
+            h->nd_from_u8 = true;
+            h->dim_b = vs::nd_dim_b(dim);
+            if ((rc = build_nd_u8_copy(h, rows_u8, n_rows))) {
+                vs_destroy(h);
+                return rc;
+            }
+        }
         *out = h;
         return VS_OK;
     }
@@ -1801,8 +1892,12 @@ int vs_set_precision(vs_index* h, int precision) {
         set_error("vs_set_precision: 0 = auto, 1 = fp32, 2 = int8");
         return VS_ERR_INVALID;
     }
-    if (precision == 2 && h->general) return refuse_general(h, "vs_set_precision(2)");
-    if (precision == 2 && !h->d_vecs_u8) {
+    if (precision == 2 && h->general && !h->nd_from_u8) return refuse_general(h, "vs_set_precision(2)");
+    if (precision == 2 && h->general && !h->d_nd_u8) {
+        set_error("vs_set_precision(2): max ||b||^2 >= 2^24 on this index: no batch could run on the byte rows");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (precision == 2 && !h->general && !h->d_vecs_u8) {
         set_error("int8 path unavailable: the base is not integer valued in [0, 255] (or the index is not brute-force L2)");
         return VS_ERR_UNSUPPORTED;
     }

@@ -20,9 +20,9 @@ void set_error(const std::string& msg) { g_err = msg; }
 const char* get_error() { return g_err.c_str(); }
 
 // ------------------------------------------------------------------------------------------ xvecs
-// cpu_baseline.cpp:31-58: records of [int32 d][d x 4 bytes]; d constant; a partial trailing
-// record is "truncated".  Returns VS_OK / VS_ERR_IO.
-static int xvecs_scan(const char* path, void* dst, int64_t cap_elems, int64_t* rows_out, int* dim_out) {
+// cpu_baseline.cpp:31-58: records of [int32 d][d x esz bytes] (esz = 4: .fvecs / .ivecs, 1: .bvecs); d constant; a
+// partial trailing record is "truncated".  Returns VS_OK / VS_ERR_IO.
+static int xvecs_scan(const char* path, void* dst, int64_t cap_elems, int64_t* rows_out, int* dim_out, int esz = 4) {
     FILE* f = std::fopen(path, "rb");
     if (!f) {
         set_error(std::string("Cannot open file ") + path);
@@ -41,7 +41,7 @@ static int xvecs_scan(const char* path, void* dst, int64_t cap_elems, int64_t* r
             rc = VS_ERR_IO;
         } else {
             dim = d0;
-            const int64_t rec = 4 + 4 * (int64_t)dim;
+            const int64_t rec = 4 + esz * (int64_t)dim;
             rows = fsize / rec;
             if (fsize % rec != 0) {
                 set_error(std::string("File seems truncated: ") + path);  // cpu_baseline.cpp:53-56
@@ -71,7 +71,7 @@ static int xvecs_scan(const char* path, void* dst, int64_t cap_elems, int64_t* r
                                 rc = VS_ERR_IO;
                                 break;
                             }
-                            std::memcpy(out + (done + i) * 4 * (int64_t)dim, buf.data() + i * rec + 4, 4 * (size_t)dim);
+                            std::memcpy(out + (done + i) * esz * (int64_t)dim, buf.data() + i * rec + 4, (size_t)esz * (size_t)dim);
                         }
                         done += n;
                     }
@@ -88,7 +88,7 @@ static int xvecs_scan(const char* path, void* dst, int64_t cap_elems, int64_t* r
     return rc;
 }
 
-static int xvecs_write(const char* path, const void* src, int64_t rows, int dim) {
+static int xvecs_write(const char* path, const void* src, int64_t rows, int dim, int esz = 4) {
     FILE* f = std::fopen(path, "wb");
     if (!f) {
         set_error(std::string("Cannot open output file ") + path);
@@ -96,10 +96,10 @@ static int xvecs_write(const char* path, const void* src, int64_t rows, int dim)
     }
     const char* in = static_cast<const char*>(src);
     const int32_t d = dim;
-    std::vector<char> rec(4 + 4 * (size_t)dim);
+    std::vector<char> rec(4 + (size_t)esz * (size_t)dim);
     for (int64_t i = 0; i < rows; ++i) {
         std::memcpy(rec.data(), &d, 4);
-        std::memcpy(rec.data() + 4, in + i * 4 * (int64_t)dim, 4 * (size_t)dim);
+        std::memcpy(rec.data() + 4, in + i * esz * (int64_t)dim, (size_t)esz * (size_t)dim);
         if (std::fwrite(rec.data(), rec.size(), 1, f) != 1) {
             std::fclose(f);
             set_error(std::string("write failed: ") + path);
@@ -462,6 +462,11 @@ int vs_ivecs_read(const char* path, int32_t* dst, int64_t cap, int64_t* rows, in
     if (!dst) { vs::set_error("dst is NULL"); return VS_ERR_INVALID; }
     return vs::xvecs_scan(path, dst, cap, rows, dim);
 }
+int vs_bvecs_shape(const char* path, int64_t* rows, int* dim) { return vs::xvecs_scan(path, nullptr, 0, rows, dim, 1); }
+int vs_bvecs_read(const char* path, uint8_t* dst, int64_t cap, int64_t* rows, int* dim) {
+    return vs::xvecs_scan(path, dst ? static_cast<void*>(dst) : nullptr, cap, rows, dim, 1);
+}
+int vs_bvecs_write(const char* path, const uint8_t* src, int64_t rows, int dim) { return vs::xvecs_write(path, src, rows, dim, 1); }
 int vs_fvecs_write(const char* path, const float* src, int64_t rows, int dim) { return vs::xvecs_write(path, src, rows, dim); }
 int vs_ivecs_write(const char* path, const int32_t* src, int64_t rows, int dim) { return vs::xvecs_write(path, src, rows, dim); }
 

@@ -70,6 +70,21 @@ struct ScanNdParams {
 };
 hipError_t launch_scan_nd(const ScanNdParams& p, int grid, int kcap, int nqh, int mode, hipStream_t s);
 
+// Byte scan of a general index made from uint8 rows (vs_scan_nd_i8.hip): launch_scan_nd's kModeTopK contract
+// on s.base_u8 = [n_rows + kScanPadRows][dim_b] bytes (x - 128), dim_b = nd_dim_b(dim), zero padded, with
+// s.rterm[n_rows + 64] = sum (b - 128)^2 per row.  The preparation launch writes the byte queries in MFMA B-fragment
+// order, qterm = sum (q - 128)^2 per query and s.invalid[batch] (0 or 1): 1 unless every query value of the batch is an
+// integer in [0, 255] and max ||q||^2 + bmax <= 2^24; the scan skips such a batch.  L2 only.
+constexpr int nd_dim_b(int dim) { return (dim + 63) & ~63; }  // whole 64-byte MFMA steps
+struct ScanNdI8Params {
+    ScanParams s;
+    int dim, dim_b;
+    int32_t bmax;            // max over the base of ||b||^2, < 2^24
+    int8_t* q8frag;          // scratch [n_batches][dim_b / 64][2][64][16]: fragment (s, h, lane) = bytes Q'[16 h + (lane & 15)][64 s + 16 (lane >> 4) ..]
+    int32_t* qterm;          // scratch [n_batches][32]
+};
+hipError_t launch_scan_nd_i8(const ScanNdI8Params& p, int grid, int kcap, int nqh, hipStream_t s);
+
 // bf16 prefilter of the fp32 streaming scan (scan_f32f_kernel).  With S = q.b exact, S_fl the fp32 chain of
 // scan_f32s_kernel and S' the v_mfma_f32_16x16x32_bf16 sum of q' = bf16(q), b' = bf16(b):
 //   |S_fl - S'| <= |S_fl - S| + |S - q'.b'| + |q'.b' - S'|

@@ -1,0 +1,442 @@
+// vs_scan_nd_i8.hip -- the byte scan of a general-dimension index made from uint8 rows (vs_bf_create_nd_u8; gfx950).
+//
+//   scan_nd_i8_kernel<NQH, KCAP> : scan_nd_kernel's kModeTopK contract (vs_scan_nd.hip: partial lists
+//                          [batch*32+q][workgroup][kcap], threshold exchange through slots_cur, tau0, run_if, id_offset) on
+//                          rows stored as int8 (x - 128), with v_mfma_i32_16x16x64_i8 (base rows = A operand).  A quarter
+//                          of scan_nd_kernel's row bytes, the same distances.
+//   nd_prep_i8_kernel    : per batch, the queries as bytes (x - 128) zero-padded to dim_b and to 32 queries in MFMA
+//                          B-fragment order, the per-query term, and the verdict whether the batch may run on bytes.
+//
+// Rows are [n_rows + kScanPadRows][dim_b] with dim_b = dim rounded up to 64 bytes; padding bytes and spare rows are
+// zero, so they add nothing to any dot product.
+//
+// Terms.  With q' = q - 128, b' = b - 128 (both in [-128, 127]) and zero padding,
+//     ||q - b||^2 = sum (q' - b')^2 = qterm + rterm - 2 q'.b',   qterm = sum q'^2, rterm = sum b'^2 over the real dim.
+// Both terms are <= 2048 * 128^2 = 2^25, |q'.b'| <= 2^25 and the distance is <= 2048 * 255^2 < 2^27: every int32
+// intermediate fits in any order of evaluation.
+//
+// Exactness rule.  The fp32 path's distance fma(-2, dot, qn + bn) is the exact integer when all values are
+// integers and ||q||^2 + ||b||^2 <= 2^24 (both norms, every partial sum of q.b <= (||q||^2 + ||b||^2) / 2 and the epilogue
+// are then exactly representable, in any summation order).  A batch runs here only when every query value is an integer in
+// [0, 255] and max over the batch of ||q||^2 + max over the base of ||b||^2 <= 2^24; the int32 distance is then that
+// same integer (< 2^24, so the conversion to float is exact).  Any other batch gets invalid[batch] = 1 and is skipped:
+// the merge reports flags = 2 and the host calls rerun it on the fp32 rows.
+//
+// Organisation: scan_nd_kernel's.  Nothing in a wave grows with dim: a wave owns a block of kNd8Tiles 16-row tiles and
+// keeps their kNd8Tiles x NQH int32 accumulators resident while it walks the rows in steps of 128 bytes (one line per
+// row, two 16x16x64 MFMAs per tile and query block), with a 64-byte tail step when dim_b / 64 is odd.  Rows and
+// fragments are loaded one step ahead with ordinary global loads whose waits the compiler places.  The threshold exchange
+// and the workgroup merge are scan_nd_kernel's, repeated here so that vs_scan_nd.hip and its measured figures stay as
+// they are.
+#include "vs_kernels.h"
+#include "vs_dev.h"
+#include <type_traits>
+
+namespace vs {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kNd8Tiles = 4;                          // 16-row tiles per wave block
+constexpr int kNd8BlockRows = kNd8Tiles * kTileRows;  // 64 <= kScanPadRows: a block never reads past the spare rows
+static_assert(kNd8BlockRows <= kScanPadRows, "row blocks are loaded unclamped");
+constexpr int kNd8MergeSmall = 64;                    // entries per query of the workgroup merge's fast path
+constexpr int kNd8PassQ = 4;                          // queries per pass of its fallback
+constexpr int kNd8NormLimit = 1 << 24;                // ||q||^2 + ||b||^2 at most this: the fp32 path is exact
+
+// x as an integer in [0, 255], or false (NaN and infinities included)
+__device__ __forceinline__ bool byte_value(float x, int& xi) {
+    xi = 128;
+    if (!(x >= 0.f && x <= 255.f)) return false;
+    const int v = (int)x;
+    if ((float)v != x) return false;
+    xi = v;
+    return true;
+}
+
+// grid = n_batches, 256 threads
+__global__ __launch_bounds__(256) void nd_prep_i8_kernel(const float* __restrict__ q, int64_t q_batch_stride, int nq_valid, int dim,
+                                                         int dim_b, int bmax, int8_t* __restrict__ q8frag,
+                                                         int32_t* __restrict__ qterm, int32_t* __restrict__ invalid,
+                                                         const int32_t* run_if) {
+    if (run_if && !run_if[0]) return;
+    const int batch = blockIdx.x;
+    const float* qb = q + (int64_t)batch * q_batch_stride;
+    const int S = dim_b / 64;
+    i32x4* out = reinterpret_cast<i32x4*>(q8frag) + (int64_t)batch * S * 128;
+    bool bad = false;
+    // fragment (s, h, lane) = bytes Q'[16 h + (lane & 15)][64 s + 16 (lane >> 4) ..], zeros past dim and past nq_valid
+    for (int e = threadIdx.x; e < S * 128; e += 256) {
+        const int lane = e & 63, h = (e >> 6) & 1, s = e >> 7;
+        const int qi = 16 * h + (lane & 15), k0 = 64 * s + 16 * (lane >> 4);
+        i32x4 v = {0, 0, 0, 0};
+        if (qi < nq_valid) {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                unsigned word = 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int k = k0 + 4 * w + i;
+                    if (k < dim) {
+                        int xi;
+                        bad |= !byte_value(qb[(int64_t)qi * dim + k], xi);
+                        word |= ((unsigned)((xi - 128) & 0xff)) << (8 * i);
+                    }
+                }
+                v[w] = (int)word;
+            }
+        }
+        out[e] = v;
+    }
+    // per query (8 lanes each): qterm = sum (q - 128)^2 and ||q||^2, in integers; absent queries are zero and never
+    // invalidate a batch
+    const int row = threadIdx.x >> 3, j = threadIdx.x & 7;
+    const bool live = row < nq_valid;
+    const float* src = qb + (int64_t)(live ? row : 0) * dim;
+    int t = 0, n2 = 0;
+    if (live) {
+        for (int i = j; i < dim; i += 8) {
+            int xi;
+            if (byte_value(src[i], xi)) {
+                t += (xi - 128) * (xi - 128);
+                n2 += xi * xi;
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 1; m < 8; m <<= 1) {
+        t += __shfl_xor(t, m);
+        n2 += __shfl_xor(n2, m);
+    }
+    if (j == 0) qterm[batch * kMaxBatch + row] = t;
+    if (live && n2 > kNd8NormLimit - bmax) bad = true;  // (n2 <= 2048 * 255^2, 0 <= bmax < 2^24: no overflow)
+    const int any = __syncthreads_or(bad ? 1 : 0);
+    if (threadIdx.x == 0) invalid[batch] = any ? 1 : 0;  // written as 0 or 1: nobody has to clear it before
+}
+
+template <int NQH, int KCAP>
+__global__ __launch_bounds__(kScanThreads, 1) void scan_nd_i8_kernel(const ScanNdI8Params pn) {
+    const ScanParams& p = pn.s;
+    constexpr int T = kNd8Tiles;
+    constexpr int NQ = NQH * 16;
+    constexpr int CAP = 32 * KCAP;  // 32 lane lists per query
+    // the fragments of a step are loaded one step ahead like its rows, except in the largest instantiation (two query
+    // blocks, 16-entry lists), which has no registers left for the second set: there they are loaded in their own step
+    constexpr bool BAHEAD = NQH * KCAP < 32;
+    __shared__ float lds_wmin[kScanWaves * 32];
+    __shared__ float lds_tau[32];
+    __shared__ int lds_cnt[32];
+    __shared__ float mrg_d[kMaxBatch * kNd8MergeSmall];  // fast path [32][kNd8MergeSmall]; fallback [kNd8PassQ][CAP]
+    __shared__ int mrg_i[kMaxBatch * kNd8MergeSmall];
+    static_assert(kNd8PassQ * CAP <= kMaxBatch * kNd8MergeSmall, "the fallback pass fits the merge buffer");
+    if (p.run_if && !p.run_if[0]) return;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, g = lane >> 4;
+    const int dim_b = pn.dim_b;
+    const unsigned voff = (unsigned)(r * dim_b + 16 * g);  // this lane's 16 bytes inside a 16-row tile's 64-byte step
+    const int S = dim_b / 64;          // 64-byte steps per row
+    const int n_pairs = S >> 1;        // full 128-byte lines
+    const int64_t n_rows = p.row_end - p.row_begin;
+    const int64_t last_row = p.row_end - 1;
+    const int blocks_total = (int)((n_rows + kNd8BlockRows - 1) / kNd8BlockRows);
+    // blocks are dealt round-robin: block (n * G + workgroup) * 8 + wave -- workgroups in lock-step read consecutive rows
+    const int wb0 = blockIdx.x * kScanWaves + wave;
+    const int wb_step = gridDim.x * kScanWaves;
+
+#pragma clang loop unroll(disable)
+    for (int batch = 0; batch < p.n_batches; ++batch) {
+        if (p.invalid[batch]) continue;  // (workgroup-uniform) not a byte batch: flags = 2, the caller reruns it in fp32
+        const i32x4* qf_b = reinterpret_cast<const i32x4*>(pn.q8frag) + (int64_t)batch * S * 128;
+        float* slots = p.slots_cur ? p.slots_cur + (int64_t)batch * 32 * kSlotStride : nullptr;
+        int qt[NQH];
+        float tau[NQH], tq[NQH], wmin[NQH];
+#pragma unroll
+        for (int h = 0; h < NQH; ++h) {
+            qt[h] = pn.qterm[batch * kMaxBatch + h * 16 + r];
+            tau[h] = tq[h] = VS_INF;
+            wmin[h] = VS_INF;
+        }
+        if (p.tau0) {
+#pragma unroll
+            for (int h = 0; h < NQH; ++h) tau[h] = tq[h] = p.tau0[batch * kMaxBatch + h * 16 + r];
+        }
+        float ld[NQH][KCAP];
+        int li[NQH][KCAP];
+#pragma unroll
+        for (int h = 0; h < NQH; ++h)
+#pragma unroll
+            for (int j = 0; j < KCAP; ++j) {
+                ld[h][j] = VS_INF;
+                li[h][j] = -1;
+            }
+
+        // one block of T tiles: distances into the lane lists
+        auto do_block = [&](int wb) __attribute__((always_inline)) {
+            const int64_t row0 = p.row_begin + (int64_t)wb * kNd8BlockRows;
+            // "uniform base + 32-bit lane offset" addressing: one address register serves every load of the block
+            const char* sb = reinterpret_cast<const char*>(p.base_u8) + row0 * (int64_t)dim_b;
+            const unsigned tile_bytes = 16u * (unsigned)dim_b;  // 16 rows
+            i32x4 acc[T][NQH];
+#pragma unroll
+            for (int t = 0; t < T; ++t)
+#pragma unroll
+                for (int h = 0; h < NQH; ++h) acc[t][h] = (i32x4){0, 0, 0, 0};
+            i32x4 a[T][2], b[NQH][2];
+            auto load_a = [&](int s, i32x4 (&av)[T][2]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    av[t][0] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(sb + (t * tile_bytes + 128u * s) + voff));
+                    av[t][1] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(sb + (t * tile_bytes + 128u * s + 64u) + voff));
+                }
+            };
+            auto load_b = [&](int s, i32x4 (&bv)[NQH][2]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int h = 0; h < NQH; ++h) {
+                    bv[h][0] = qf_b[((2 * s) * 2 + h) * 64 + lane];
+                    bv[h][1] = qf_b[((2 * s + 1) * 2 + h) * 64 + lane];
+                }
+            };
+            auto mfma_half = [&](const i32x4 (&av)[T][2], const i32x4 (&bv)[NQH][2], int u) __attribute__((always_inline)) {
+#pragma unroll
+                for (int t = 0; t < T; ++t)
+#pragma unroll
+                    for (int h = 0; h < NQH; ++h)
+                        acc[t][h] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av[t][u], bv[h][u], acc[t][h], 0, 0, 0);
+            };
+            if (n_pairs > 0) {
+                load_a(0, a);
+                if (BAHEAD) load_b(0, b);
+            }
+            for (int s = 0; s < n_pairs; ++s) {
+                i32x4 an[T][2], bn2[NQH][2];
+                const bool more = s + 1 < n_pairs;
+                if (!BAHEAD) load_b(s, b);  // (issued before the rows of the next step: its wait leaves those in flight)
+                if (more) {
+                    load_a(s + 1, an);
+                    if (BAHEAD) load_b(s + 1, bn2);
+                }
+                mfma_half(a, b, 0);
+                mfma_half(a, b, 1);
+                if (more) {
+#pragma unroll
+                    for (int t = 0; t < T; ++t) {
+                        a[t][0] = an[t][0];
+                        a[t][1] = an[t][1];
+                    }
+                    if (BAHEAD) {
+#pragma unroll
+                        for (int h = 0; h < NQH; ++h) {
+                            b[h][0] = bn2[h][0];
+                            b[h][1] = bn2[h][1];
+                        }
+                    }
+                }
+            }
+            if (S & 1) {  // the last 64 bytes of a row whose dim_b is an odd number of steps
+#pragma unroll
+                for (int t = 0; t < T; ++t) a[t][0] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(sb + (t * tile_bytes + 128u * n_pairs) + voff));
+#pragma unroll
+                for (int h = 0; h < NQH; ++h) b[h][0] = qf_b[((2 * n_pairs) * 2 + h) * 64 + lane];
+                mfma_half(a, b, 0);
+            }
+            const bool ragged = row0 + kNd8BlockRows - 1 > last_row;  // wave-uniform
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const int64_t rbase = row0 + 16 * t + 4 * g;
+                int rt[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) rt[j] = p.rterm[rbase + j];  // (the terms have 64 spare entries)
+#pragma unroll
+                for (int h = 0; h < NQH; ++h) {
+                    float d[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        // the integer the fp32 path computes exactly: ||q||^2 + ||b||^2 - 2 q.b
+                        d[j] = (float)(qt[h] + rt[j] - 2 * acc[t][h][j]);
+                        if (ragged && rbase + j > last_row) d[j] = VS_INF;
+                    }
+                    const float dmin = fminf(fminf(d[0], d[1]), fminf(d[2], d[3]));
+                    wmin[h] = fminf(wmin[h], dmin);
+                    if (dmin < tau[h]) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (d[j] < tau[h]) {
+                                list_insert<KCAP>(ld[h], li[h], d[j], (int)(rbase + j) + p.id_offset);
+                                tau[h] = fminf(tau[h], ld[h][KCAP - 1]);
+                            }
+                    }
+                }
+            }
+        };
+
+        bool xchg = slots != nullptr;  // (workgroup-uniform)
+        for (int wb = wb0; wb < blocks_total || xchg; wb += wb_step) {
+        if (wb < blocks_total) do_block(wb);
+        if (xchg) {
+            xchg = false;
+            // ---- threshold exchange (scan_nd_kernel's): the first block goes into the lane lists unbounded; every
+            // workgroup then publishes, per query, the smallest distance it has seen, reads what the others published
+            // and takes the k1-th smallest of 16 group minima as an upper bound of the final k1-th best distance.  The
+            // spin is bounded and an unpublished slot reads +inf, which only loosens the bound: the result does not
+            // depend on timing or residency.
+#pragma unroll
+            for (int h = 0; h < NQH; ++h) {
+                float m = wmin[h];
+                m = fminf(m, __shfl_xor(m, 16));
+                m = fminf(m, __shfl_xor(m, 32));
+                if (g == 0) lds_wmin[wave * 32 + h * 16 + r] = m;
+            }
+            __syncthreads();
+            if (tid < NQ) {
+                float m = lds_wmin[tid];
+#pragma unroll
+                for (int w = 1; w < kScanWaves; ++w) m = fminf(m, lds_wmin[w * 32 + tid]);
+                __hip_atomic_store(slots + tid * kSlotStride + blockIdx.x, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            // DPP row g of wave w reduces query 4 w + g: lane r folds workgroups 16 r .. 16 r + 15
+            const int qx = 4 * wave + g;
+            const float* s0 = slots + qx * kSlotStride + 16 * r;
+            const int need = (int)gridDim.x / 2;
+            float m = VS_INF;
+            for (int spin = 0;; ++spin) {
+                int cf = 0;
+                m = VS_INF;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float v = __hip_atomic_load(s0 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    cf += v < VS_INF;
+                    m = fminf(m, v);
+                }
+                cf += dpp_mov_i<0xB1>(cf);
+                cf += dpp_mov_i<0x4E>(cf);
+                cf += dpp_mov_i<0x141>(cf);
+                cf += dpp_mov_i<0x140>(cf);  // row sum: workgroups that have published this row's query
+                if (__all(qx >= NQ || cf >= need) || spin >= 2048) break;
+                __builtin_amdgcn_s_sleep(24);
+            }
+            float kth = VS_INF;
+            for (int round = 0; round < p.k1; ++round) {
+                float x = m;
+                x = fminf(x, dpp_mov_f<0xB1>(x));
+                x = fminf(x, dpp_mov_f<0x4E>(x));
+                x = fminf(x, dpp_mov_f<0x141>(x));
+                x = fminf(x, dpp_mov_f<0x140>(x));  // row minimum in every lane of the row
+                kth = x;
+                const unsigned rowmask = (unsigned)((__ballot(m == x) >> (16 * g)) & 0xFFFFull);
+                if (rowmask != 0u && r == __builtin_ctz(rowmask)) m = VS_INF;  // drop exactly one instance
+            }
+            if (r == 0) lds_tau[qx] = kth < VS_INF ? next_up(kth) : VS_INF;
+            __syncthreads();
+#pragma unroll
+            for (int h = 0; h < NQH; ++h) {
+                tq[h] = lds_tau[h * 16 + r];
+                tau[h] = fminf(tau[h], tq[h]);
+            }
+        }
+        }
+
+        // ---- workgroup merge (scan_nd_kernel's): the entries that can still matter (d < bound) are compacted into LDS
+        // and ranked; the sorted per-workgroup lists go to merge_compact_kernel.
+        auto rank = [&](int qq, const float* cand_d, const int* cand_i, auto epl_tag) {
+            constexpr int EPL = decltype(epl_tag)::value;
+            const int M = min(lds_cnt[qq], EPL * 64);
+            float cd[EPL];
+            int ci[EPL];
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) {
+                const int idx = e * 64 + lane;
+                cd[e] = idx < M ? cand_d[idx] : VS_INF;
+                ci[e] = idx < M ? cand_i[idx] : 0x7fffffff;
+            }
+            // partial lists are query-major: [batch][query][workgroup][KCAP] (one merge launch ranks all batches)
+            float* od = p.part_d + (((int64_t)batch * kMaxBatch + qq) * kSlotStride + blockIdx.x) * KCAP;
+            int32_t* oi = p.part_i + (((int64_t)batch * kMaxBatch + qq) * kSlotStride + blockIdx.x) * KCAP;
+            const int rounds = min(min(p.k1, KCAP), M);
+            for (int round = 0; round < rounds; ++round) {
+                float md = cd[0];
+                int mi = ci[0];
+#pragma unroll
+                for (int e = 1; e < EPL; ++e)
+                    if (lex_lt(cd[e], ci[e], md, mi)) {
+                        md = cd[e];
+                        mi = ci[e];
+                    }
+                float bd;
+                int bi;
+                wave_lexmin(md, mi, bd, bi);
+                if (lane == 0) {
+                    od[round] = bd;
+                    oi[round] = bi;
+                }
+#pragma unroll
+                for (int e = 0; e < EPL; ++e)
+                    if (ci[e] == bi && cd[e] == bd) {
+                        cd[e] = VS_INF;
+                        ci[e] = 0x7fffffff;
+                    }
+            }
+            if (lane < KCAP && lane >= rounds) {
+                od[lane] = VS_INF;
+                oi[lane] = -1;
+            }
+        };
+        auto compact = [&](int q_lo, int q_n, int cap) {
+#pragma unroll
+            for (int h = 0; h < NQH; ++h) {
+                const int qidx = h * 16 + r;
+                if (qidx < q_lo || qidx >= q_lo + q_n) continue;
+#pragma unroll
+                for (int j = 0; j < KCAP; ++j)
+                    if (li[h][j] >= 0 && ld[h][j] < tq[h]) {
+                        const int pos = atomicAdd(&lds_cnt[qidx], 1);
+                        if (pos < cap) {
+                            mrg_d[(qidx - q_lo) * cap + pos] = ld[h][j];
+                            mrg_i[(qidx - q_lo) * cap + pos] = li[h][j];
+                        }
+                    }
+            }
+        };
+        if (tid < 32) lds_cnt[tid] = 0;
+        __syncthreads();
+        compact(0, NQ, kNd8MergeSmall);
+        const bool too_many = __syncthreads_or(lds_cnt[tid & 31] > kNd8MergeSmall);
+        if (!too_many) {
+            for (int qq = wave; qq < NQ; qq += kScanWaves)
+                rank(qq, mrg_d + qq * kNd8MergeSmall, mrg_i + qq * kNd8MergeSmall, std::integral_constant<int, 1>{});
+        } else {
+            for (int q_lo = 0; q_lo < NQ; q_lo += kNd8PassQ) {
+                __syncthreads();
+                if (tid < 32) lds_cnt[tid] = 0;
+                __syncthreads();
+                compact(q_lo, kNd8PassQ, CAP);
+                __syncthreads();
+                if (wave < kNd8PassQ) rank(q_lo + wave, mrg_d + wave * CAP, mrg_i + wave * CAP, std::integral_constant<int, CAP / 64>{});
+            }
+        }
+        __syncthreads();  // LDS is reused by the next batch
+    }
+}
+
+template <int NQH, int KCAP>
+static hipError_t launch_scan_nd_i8_t(const ScanNdI8Params& p, int grid, hipStream_t s) {
+    hipLaunchKernelGGL((scan_nd_i8_kernel<NQH, KCAP>), dim3(grid), dim3(kScanThreads), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_scan_nd_i8(const ScanNdI8Params& p, int grid, int kcap, int nqh, hipStream_t s) {
+    if (p.dim < 1 || p.dim > kNdMaxDim || p.dim_b != nd_dim_b(p.dim) || !p.q8frag || !p.qterm || !p.s.base_u8 || !p.s.rterm ||
+        !p.s.invalid || p.bmax < 0 || p.bmax >= kNd8NormLimit || p.s.metric != 0 || grid < 1 || grid > kSlotStride ||
+        (p.s.row_begin & 15) || p.s.n_batches < 1 || p.s.nq_valid < 1 || p.s.nq_valid > kMaxBatch)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nd_prep_i8_kernel, dim3(p.s.n_batches), dim3(256), 0, s, p.s.q, p.s.q_batch_stride, p.s.nq_valid, p.dim, p.dim_b,
+                       p.bmax, p.q8frag, p.qterm, p.s.invalid, p.s.run_if);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (kcap == 8) return nqh == 1 ? launch_scan_nd_i8_t<1, 8>(p, grid, s) : launch_scan_nd_i8_t<2, 8>(p, grid, s);
+    if (kcap == 16) return nqh == 1 ? launch_scan_nd_i8_t<1, 16>(p, grid, s) : launch_scan_nd_i8_t<2, 16>(p, grid, s);
+    return hipErrorInvalidValue;
+}
+
+}  // namespace vs

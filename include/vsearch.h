@@ -79,6 +79,12 @@ VS_API int vs_fvecs_read(const char* path, float* dst, int64_t cap_elems, int64_
 VS_API int vs_ivecs_read(const char* path, int32_t* dst, int64_t cap_elems, int64_t* rows, int* dim);
 VS_API int vs_fvecs_write(const char* path, const float* src, int64_t rows, int dim);
 VS_API int vs_ivecs_write(const char* path, const int32_t* src, int64_t rows, int dim);
+/* .bvecs (TEXMEX byte vectors): repeated [int32 d][d x uint8], little endian; the same rules
+ * and errors as the .fvecs functions (cannot open, truncated, inconsistent d: VS_ERR_IO;
+ * cap_elems < rows*dim: VS_ERR_INVALID). */
+VS_API int vs_bvecs_shape(const char* path, int64_t* rows, int* dim);
+VS_API int vs_bvecs_read(const char* path, uint8_t* dst, int64_t cap_elems, int64_t* rows, int* dim);
+VS_API int vs_bvecs_write(const char* path, const uint8_t* src, int64_t rows, int dim);
 
 /* results.txt: "Query <i>: (<id>, <dist>) ...\n".
  * style 0 = cpu_baseline.cpp:155-175 (default ostream float formatting),
@@ -119,11 +125,38 @@ VS_API int vs_bf_create(const float* base_host, int64_t n_rows, int dim, int met
  * vs_bf_search_topk_dev_multi, vs_bf_scores_dev, vs_set_batch, vs_index_rows, vs_index_dim,
  * vs_prof_* and vs_destroy, with the same signatures and output layouts (queries are
  * [nq][dim], unpadded).  vs_set_precision: 0 and 1 both mean the fp32 rows, 2 returns
- * VS_ERR_UNSUPPORTED (a byte copy of the rows for other dimensions is a follow-up).  The
+ * VS_ERR_UNSUPPORTED (an index with a byte copy of the rows at other dimensions comes from
+ * vs_bf_create_nd_u8 below, not from this creator).  The
  * sharded calls (vs_bf_search_dev_sharded, vs_bf_search_sharded, vs_bf_search_vshards) and
  * every vs_ivf_* call return VS_ERR_UNSUPPORTED on a general index; IVF and q8 stay at 128. */
 VS_API int vs_bf_create_nd(const float* base_host, int64_t n_rows, int dim, int metric,
                            int device, int64_t id_offset, vs_index** out);
+
+/* Byte-valued rows at any vector length: base_host is uint8 [n_rows][dim], 1 <= dim <= 2048
+ * (dim < 1: VS_ERR_INVALID, dim > 2048: VS_ERR_UNSUPPORTED), squared L2 only.  dim == 128 gives
+ * the index vs_bf_create gives for the same rows converted to float: same results, same
+ * launches.  Any other dim gives a general index exactly as vs_bf_create_nd builds it (fp32
+ * rows padded to 16 floats, norms) PLUS the rows once more as int8 (x - 128), padded to 64
+ * bytes, with an int32 term per row, scanned with int8 MFMA for k <= 15 at a quarter of the
+ * row traffic.  The fp32 rows stay -- they serve k >= 16, vs_bf_scores_dev, the tie replay and
+ * reruns -- so the index takes 1.25 x the device memory of a vs_bf_create_nd index (more below
+ * 64-d, where the byte rows are padded to 64).
+ *
+ * Exactness rule.  The byte scan returns the fp32 scan's distances to the bit when every fp32
+ * quantity of the epilogue is an exactly representable integer: with integer values and
+ * ||q||^2 + ||b||^2 <= 2^24 both norms, every partial sum of q.b (each <= (||q||^2 + ||b||^2) / 2)
+ * and fma(-2, dot, qn + bn) are exact in any summation order.  A batch therefore runs on the
+ * byte rows only when (1) every query value of the batch is an integer in [0, 255] and (2) max
+ * over the batch of ||q||^2 + max over the base of ||b||^2 <= 2^24; both are checked on the
+ * device, in integers.  Any other batch is skipped: the *_dev calls report flags == 2 for its
+ * queries, vs_bf_search / vs_bf_search_topk rerun it on the fp32 rows themselves.  Nothing ever
+ * returns a distance that differs from the fp32 path's.
+ *
+ * vs_set_precision on such an index: 0 (default) and 2 use the byte scan for k <= 15, 1 forces
+ * the fp32 rows; 2 returns VS_ERR_UNSUPPORTED when max ||b||^2 >= 2^24 (the byte rows are then
+ * not kept: no batch could run on them).  Calls accepted and refused: as vs_bf_create_nd. */
+VS_API int vs_bf_create_nd_u8(const uint8_t* base_host, int64_t n_rows, int dim,
+                              int device, int64_t id_offset, vs_index** out);
 
 /* Fixed model batch, like QnnRunner::getBatchSize (QnnRunner.h:37); 1..32, default 32.
  * Larger query sets are processed in batches of this size, the last one

@@ -37,6 +37,18 @@ inline bool read_fvecs(const std::string& filename, std::vector<float>& data, in
     return true;
 }
 
+// TEXMEX .bvecs ([int32 d][d x uint8] records): read_fvecs' contract for byte vectors
+inline bool read_bvecs(const std::string& filename, std::vector<uint8_t>& data, int& rows, int& dim) {
+    int64_t r = 0;
+    int d = 0;
+    if (vs_bvecs_shape(filename.c_str(), &r, &d) != VS_OK) return false;
+    data.resize((size_t)r * (size_t)d);
+    if (r > 0 && vs_bvecs_read(filename.c_str(), data.data(), (int64_t)data.size(), &r, &d) != VS_OK) return false;
+    rows = (int)r;
+    dim = d;
+    return true;
+}
+
 // main_ivf.cpp:35-50 (throws like the reference)
 inline void load_ivecs(const std::string& filename, std::vector<std::vector<int>>& vectors, int& dim) {
     int64_t r = 0;
@@ -70,9 +82,13 @@ struct Result {  // cpu_baseline.cpp:13-19
 };
 
 // Any vector length 1 <= dim <= 2048: 128-d bases take vs_bf_create, the others vs_bf_create_nd (a general index:
-// one GPU, fp32 rows; the sharded calls refuse it with the library's message).
+// one GPU, fp32 rows; the sharded calls refuse it with the library's message).  uint8 rows take vs_bf_create_nd_u8:
+// squared L2, and at dimensions other than 128 a byte copy beside the fp32 rows, scanned with int8 MFMA for k <= 15.
 class ExactSearch {
 public:
+    ExactSearch(const uint8_t* rows_u8, int64_t rows, int dim, int64_t id_offset = 0, int device = 0) {
+        check(vs_bf_create_nd_u8(rows_u8, rows, dim, device, id_offset, &h_));
+    }
     ExactSearch(const std::vector<float>& base, int rows, int dim, int device = 0, int metric = VS_METRIC_L2) {
         check((dim == 128 ? vs_bf_create : vs_bf_create_nd)(base.data(), rows, dim, metric, device, 0, &h_));
     }

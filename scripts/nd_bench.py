@@ -5,6 +5,11 @@ repeat is listed, not only the best.
 
     python scripts/nd_bench.py [--dims 96,128,256,384,768,960,1024,2048] [--rows 1000000] [--reps 5]
     python scripts/nd_bench.py --host --dims 960 --k 5,100 --nq 1000
+    python scripts/nd_bench.py --u8 [--dims 96,256,960,2048]
+
+--u8 is the byte leg: the same shapes on an index made from uint8 rows (BruteForceIndex.from_u8), precision 1 (fp32 rows,
+scan_nd_kernel) and precision 2 (byte rows, scan_nd_i8_kernel) alternating on the same index in the same process; the byte
+scan's delivered bytes are N dim_b, dim_b = dim rounded up to 64.
 
 Each dimension runs in a process of its own.  128 is measured twice, alternating: the specialised per-batch scan_kernel
 (VSEARCH_STREAM=0: streaming scans off) and the general kernel on the same data (VSEARCH_ND_FORCE=1).
@@ -23,9 +28,9 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # as bench.py
 
 
-def _data(rows, dim, seed):
+def _data(rows, dim, seed, dtype=np.float32):
     rng = np.random.default_rng(seed)
-    out = np.empty((rows, dim), dtype=np.float32)
+    out = np.empty((rows, dim), dtype=dtype)
     step = max(1, (1 << 26) // dim)
     for r0 in range(0, rows, step):
         out[r0:r0 + step] = rng.integers(0, 64, size=(min(step, rows - r0), dim), dtype=np.uint8)
@@ -37,8 +42,10 @@ def one(a, dim):
     import __graft_entry__ as ge
 
     pkg = ge.load_package()
-    base = _data(a.rows, dim, 1)
     tag = os.environ.get("ND_BENCH_TAG", "general")
+    if a.u8:
+        return one_u8(a, dim, pkg, torch)
+    base = _data(a.rows, dim, 1)
     with pkg.BruteForceIndex(base) as idx:
         idx.set_precision(1)
         if a.host:
@@ -78,12 +85,55 @@ def one(a, dim):
                           "tflops": round(2.0 * B * a.rows * dim / (min(us) * 1e-6) / 1e12, 2)}), flush=True)
 
 
+def one_u8(a, dim, pkg, torch):
+    base = _data(a.rows, dim, 1, np.uint8)
+    with pkg.BruteForceIndex.from_u8(base) as idx:
+        del base
+        dev = torch.device("cuda:0")
+        nb, B, k = 64, 32, 5
+        qd = torch.from_numpy(_data(nb * B, dim, 2)).to(dev)
+        oi = torch.empty((nb * B, k + 1), dtype=torch.int32, device=dev)
+        od = torch.empty((nb * B, k + 1), dtype=torch.float32, device=dev)
+        fl = torch.empty((nb * B,), dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream().cuda_stream
+        call = lambda: idx.search_dev_multi(qd.data_ptr(), nb, B, k, oi.data_ptr(), od.data_ptr(), fl.data_ptr(), st)
+        us = {1: [], 2: []}
+        dists = {}
+        for prec in (1, 2):  # warm-up of both kernels; the byte scan must have run every batch and agree with fp32
+            idx.set_precision(prec)
+            for _ in range(2):
+                call()
+            torch.cuda.synchronize()
+            assert not bool((fl == 2).any()), "a batch was refused by the byte scan"
+            dists[prec] = od.clone()
+        assert torch.equal(dists[1], dists[2]), "byte and fp32 distances differ"
+        for _ in range(a.reps):
+            for prec in (1, 2):
+                idx.set_precision(prec)
+                idx.prof_enable(True)
+                call()
+                torch.cuda.synchronize()
+                ms, _n = idx.prof_read(0)
+                idx.prof_enable(False)
+                us[prec].append(ms * 1e3 / nb)
+        dim_p, dim_b = (dim + 15) // 16 * 16, (dim + 63) // 64 * 64
+        for prec, kernel, row_bytes in ((1, "fp32", 4.0 * dim_p), (2, "i8", 1.0 * dim_b)):
+            frac = [a.rows * row_bytes / (u * 1e-6) / 1e9 / HBM_PEAK_GBS for u in us[prec]]
+            print(json.dumps({"what": "scan_us_per_batch", "index": "from_u8", "kernel": kernel, "precision": prec, "dim": dim,
+                              "row_bytes": int(row_bytes), "rows": a.rows, "us_per_batch": [round(u, 2) for u in us[prec]],
+                              "hbm_frac": [round(f, 4) for f in frac]}), flush=True)
+        med = {p: sorted(us[p])[len(us[p]) // 2] for p in us}
+        print(json.dumps({"what": "i8_vs_fp32", "dim": dim, "rows": a.rows, "median_us_fp32": round(med[1], 2),
+                          "median_us_i8": round(med[2], 2), "speedup": round(med[1] / med[2], 3)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dims", default="96,128,256,384,768,960,1024,2048")
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host", action="store_true")
+    ap.add_argument("--u8", action="store_true", help="byte leg: from_u8 index, precision 2 against 1")
     ap.add_argument("--k", default="5,100")
     ap.add_argument("--nq", type=int, default=1000)
     ap.add_argument("--one", type=int, default=0, help=argparse.SUPPRESS)
@@ -94,9 +144,11 @@ def main():
     base_cmd = [sys.executable, os.path.abspath(__file__), "--rows", str(a.rows), "--reps", str(a.reps), "--k", a.k, "--nq", str(a.nq)]
     if a.host:
         base_cmd.append("--host")
+    if a.u8:
+        base_cmd.append("--u8")
     for dim in [int(x) for x in a.dims.split(",")]:
         runs = [({}, "general")]
-        if dim == 128 and not a.host:  # alternate the yardstick and the forced general kernel
+        if dim == 128 and not a.host and not a.u8:  # alternate the yardstick and the forced general kernel
             y, g = ({"VSEARCH_STREAM": "0"}, "scan_kernel"), ({"VSEARCH_ND_FORCE": "1"}, "general")
             runs = [y, g, y, g]
         for env, tag in runs:

@@ -1,0 +1,342 @@
+"""Byte-valued brute force at any vector length (vs_bf_create_nd_u8, scan_nd_i8_kernel) against the CPU oracle.
+
+Data: nd_u8_data.u8_data (integer values under hi(dim), planted duplicates and the int8 extremes, every squared norm under
+2^23, so oracle.search_bf is exact).  The expected value is always the oracle's, never the code under test; where a test
+compares two precisions of one index it says so."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import oracle
+from nd_u8_data import sqnorm_max, u8_data
+
+pytestmark = pytest.mark.gpu
+
+DIMS = [1, 3, 63, 64, 65, 100, 129, 192, 320, 960, 1024, 2048]
+
+
+def _f32(a):
+    return a.astype(np.float32)
+
+
+def _ids_by_id_order(base, q, oi, od, rows):
+    """The ids a device call owes for the queries `rows`, none of which has two equal distances among its od: in every
+    column the smallest id among the rows at that oracle distance (oracle.l2_row), since every scan orders equal distances
+    by id.  The device calls return k + 1 entries and the last one may be tied with a row beyond them; the reference's
+    slot replacement keeps whichever of the two its slot order left there, not always the smaller id, so the last column
+    of oi is not the expectation.  The columns before it are unique rows and must be the oracle's own."""
+    bf, qf = _f32(base), _f32(q)
+    bn = oracle.compute_norms(bf)
+    want = np.array(oi, copy=True)
+    for i in rows:
+        row = oracle.l2_row(qf[i], bf, bn)
+        for j in range(od.shape[1]):
+            hit = np.flatnonzero(row == od[i, j])
+            assert hit.size > 0
+            want[i, j] = hit[0]
+        assert np.array_equal(want[i, :-1], oi[i, :-1])
+    return want
+
+
+def _check_exact(pkg, base, q, ks, precisions=(2, 1), batch=None, want_ties=True):
+    want = {k: oracle.search_bf(_f32(base), _f32(q), k) for k in ks}
+    with pkg.BruteForceIndex.from_u8(base) as idx:
+        assert idx.getDim() == base.shape[1] and idx.getNumDocs() == base.shape[0]
+        if batch:
+            idx.set_batch(batch)
+        for prec in precisions:
+            idx.set_precision(prec)
+            for k in ks:
+                oi, od = want[k]
+                tm = pkg.Timing()
+                ids, d = idx.search(_f32(q), k, tm)
+                tag = f"(N={base.shape[0]}, dim={base.shape[1]}, nq={len(q)}, k={k}, batch={batch}, precision={prec})"
+                assert np.array_equal(d, od), "dists differ " + tag
+                assert np.array_equal(ids, oi), "ids differ " + tag
+                if want_ties:
+                    assert tm.tie_queries > 0, "the tie resolver did not run " + tag
+
+
+@pytest.mark.parametrize("dim", DIMS)
+def test_exact_at_every_dimension(gpu_pkg, dim):
+    """Odd and even counts of 64-byte steps, unpadded and padded tails; precision 2 (bytes) and 1 (fp32 rows) of one index."""
+    rng = np.random.default_rng(1000 + dim)
+    base, q = u8_data(rng, 20000, 70, dim)
+    _check_exact(gpu_pkg, base, q, (1, 5, 15))
+
+
+@pytest.mark.parametrize("dim", [100, 960])
+@pytest.mark.parametrize("n", [1, 5, 17, 63, 65, 4099])
+def test_ragged_bases(gpu_pkg, dim, n):
+    rng = np.random.default_rng(2000 + dim + n)
+    base, q = u8_data(rng, n, 33, dim)
+    if n >= 2:
+        base[n - 1] = base[0]
+        q[0] = base[0]
+    _check_exact(gpu_pkg, base, q, (min(5, n),), want_ties=n >= 2)
+
+
+@pytest.mark.parametrize("batch", [1, 7, 16, 17, 32])
+def test_batch_sizes_at_dim_320(gpu_pkg, batch):
+    """One and two query blocks per tile; k = 5 and 15 take the 8- and the 16-entry lane lists."""
+    rng = np.random.default_rng(3000 + batch)
+    base, q = u8_data(rng, 20000, 70, 320)
+    _check_exact(gpu_pkg, base, q, (5, 15), precisions=(2,), batch=batch)
+
+
+# ---- device calls at dim 768: 9 batches of 32, k = 5 (shared by the two tests below; nothing modifies it)
+_DEV = {}
+
+
+def _dev_case():
+    if not _DEV:
+        rng = np.random.default_rng(5000)
+        dim, nb, B, k = 768, 9, 32, 5
+        base, q = u8_data(rng, 20000, nb * B, dim)
+        oi, od = oracle.search_bf(_f32(base), _f32(q), k + 1)
+        untied = np.flatnonzero(~(od[:, 1:] == od[:, :-1]).any(1))
+        wi = _ids_by_id_order(base, q, oi, od, untied)
+        _DEV.update(dim=dim, nb=nb, B=B, k=k, base=base, q=_f32(q), oi=oi, od=od, wi=wi)
+    return _DEV
+
+
+def _dev_multi(idx, q, nb, B, k):
+    import torch
+    dev = torch.device("cuda:0")
+    s = torch.cuda.current_stream().cuda_stream
+    qd = torch.from_numpy(np.ascontiguousarray(q)).to(dev)
+    ids = torch.full((nb * B, k + 1), -7, dtype=torch.int32, device=dev)
+    d = torch.zeros((nb * B, k + 1), dtype=torch.float32, device=dev)
+    fl = torch.full((nb * B,), -7, dtype=torch.int32, device=dev)
+    idx.search_dev_multi(qd.data_ptr(), nb, B, k, ids.data_ptr(), d.data_ptr(), fl.data_ptr(), s)
+    torch.cuda.synchronize()
+    return ids.cpu().numpy(), d.cpu().numpy(), fl.cpu().numpy()
+
+
+def test_device_calls_at_dim_768(gpu_pkg):
+    import torch
+    c = _dev_case()
+    nb, B, k, od, wi = c["nb"], c["B"], c["k"], c["od"], c["wi"]
+    ties = (od[:, 1:] == od[:, :-1]).any(1)
+    with gpu_pkg.BruteForceIndex.from_u8(c["base"]) as idx:
+        idx.set_precision(2)
+        ids, d, flags = _dev_multi(idx, c["q"], nb, B, k)
+        assert np.array_equal(d, od)
+        assert not (flags == 2).any()
+        assert np.array_equal(flags != 0, ties)
+        assert (flags == 0).sum() > 0 and (flags != 0).sum() > 0
+        assert np.array_equal(ids[flags == 0], wi[flags == 0])
+        # one short batch through vs_bf_search_dev
+        dev = torch.device("cuda:0")
+        s = torch.cuda.current_stream().cuda_stream
+        qd = torch.from_numpy(c["q"][:5].copy()).to(dev)
+        i5 = torch.full((5, k + 1), -7, dtype=torch.int32, device=dev)
+        d5 = torch.zeros((5, k + 1), dtype=torch.float32, device=dev)
+        f5 = torch.full((5,), -7, dtype=torch.int32, device=dev)
+        idx.search_dev(qd.data_ptr(), 5, k, i5.data_ptr(), d5.data_ptr(), f5.data_ptr(), s)
+        torch.cuda.synchronize()
+        f5 = f5.cpu().numpy()
+        assert np.array_equal(d5.cpu().numpy(), od[:5])
+        assert np.array_equal(f5 != 0, ties[:5]) and not (f5 == 2).any()
+        assert np.array_equal(i5.cpu().numpy()[f5 == 0], wi[:5][f5 == 0])
+
+
+def test_non_byte_queries_are_refused_per_batch(gpu_pkg):
+    """Batch 3 gets a query value of 7.5 and batch 6 a value of 256: exactly those two batches report flags == 2 (only the
+    byte scan ever does), the others are as before, and the host call reruns them on the fp32 rows."""
+    c = _dev_case()
+    nb, B, k, od, wi = c["nb"], c["B"], c["k"], c["od"], c["wi"]
+    ties = (od[:, 1:] == od[:, :-1]).any(1)
+    q = c["q"].copy()
+    q[3 * B + 4, 10] = 7.5
+    q[6 * B + 0, 3] = 256.0
+    skipped = np.zeros(nb * B, dtype=bool)
+    skipped[3 * B:4 * B] = True
+    skipped[6 * B:7 * B] = True
+    with gpu_pkg.BruteForceIndex.from_u8(c["base"]) as idx:
+        idx.set_precision(2)
+        ids, d, flags = _dev_multi(idx, q, nb, B, k)
+        assert np.array_equal(flags == 2, skipped)
+        keep = ~skipped
+        assert np.array_equal(d[keep], od[keep])
+        assert np.array_equal((flags != 0)[keep], ties[keep])
+        assert np.array_equal(ids[keep & (flags == 0)], wi[keep & (flags == 0)])
+        got = idx.search(q, k)
+        idx.set_precision(1)
+        ids1, d1, flags1 = _dev_multi(idx, q, nb, B, k)
+        assert not (flags1 == 2).any()
+        want = idx.search(q, k)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+    # (the untouched queries of the host call against the oracle)
+    untouched = np.ones(nb * B, dtype=bool)
+    untouched[[3 * B + 4, 6 * B]] = False
+    oi5, od5 = oracle.search_bf(_f32(c["base"]), c["q"], k)
+    assert np.array_equal(got[0][untouched], oi5[untouched]) and np.array_equal(got[1][untouched], od5[untouched])
+
+
+def _with_sqnorm(target, dim):
+    """A byte vector whose squared norm is exactly `target` (greedy: the largest square that fits, coordinate by coordinate)."""
+    v = np.zeros(dim, dtype=np.uint8)
+    left = target
+    for i in range(dim):
+        x = min(255, math.isqrt(left))
+        v[i] = x
+        left -= x * x
+    assert left == 0 and sqnorm_max(v[None]) == target
+    return v
+
+
+def test_norm_rule_at_dim_2048(gpu_pkg):
+    """||q||^2 + max ||b||^2 <= 2^24 decides per batch, to the unit: a query exactly on the bound is scanned on bytes (and
+    its distances equal the oracle's: the fp32 reference is exact up to there), one unit above it is refused."""
+    rng = np.random.default_rng(5500)
+    dim, n, B, k = 2048, 5000, 32, 5
+    base = rng.integers(0, 41, size=(n, dim)).astype(np.uint8)
+    bmax = sqnorm_max(base)
+    assert bmax < 2048 * 1600 + 1
+    q = rng.integers(0, 41, size=(3 * B, dim)).astype(np.uint8)
+    q[7] = _with_sqnorm(2 ** 24 - bmax, dim)          # batch 0: on the bound
+    q[B + 5] = 255                                      # batch 1: far above it
+    q[2 * B + 9] = _with_sqnorm(2 ** 24 - bmax + 1, dim)  # batch 2: one above it
+    with gpu_pkg.BruteForceIndex.from_u8(base) as idx:
+        idx.set_precision(2)
+        ids, d, flags = _dev_multi(idx, _f32(q), 3, B, k)
+        assert not (flags[:B] == 2).any()
+        assert (flags[B:] == 2).all()
+        oi, od = oracle.search_bf(_f32(base), _f32(q[:B]), k + 1)
+        assert np.array_equal(d[:B], od)
+        assert np.array_equal(flags[:B] != 0, (od[:, 1:] == od[:, :-1]).any(1))
+        wi = _ids_by_id_order(base, q[:B], oi, od, np.flatnonzero(flags[:B] == 0))
+        assert np.array_equal(ids[:B][flags[:B] == 0], wi[flags[:B] == 0])
+        got = idx.search(_f32(q), k)
+        idx.set_precision(1)
+        want = idx.search(_f32(q), k)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+
+
+def test_base_norm_too_large_for_the_byte_scan(gpu_pkg):
+    """One all-255 row at dim 2048 (||b||^2 = 2048 * 255^2 >= 2^24): the index is created, precision 2 is refused, and
+    precision 0 gives what precision 1 gives."""
+    rng = np.random.default_rng(5600)
+    dim, n = 2048, 3000
+    base = rng.integers(0, 41, size=(n, dim)).astype(np.uint8)
+    base[1234] = 255
+    q = _f32(rng.integers(0, 41, size=(40, dim)).astype(np.uint8))
+    with gpu_pkg.BruteForceIndex.from_u8(base) as idx:
+        assert gpu_pkg.lib().vs_set_precision(idx._h, 2) == -5
+        assert "2^24" in gpu_pkg.lib().vs_last_error().decode()
+        idx.set_precision(0)
+        got = idx.search(q, 5)
+        idx.set_precision(1)
+        want = idx.search(q, 5)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+
+
+def test_dim_128_is_vs_bf_create_and_the_refusals(gpu_pkg):
+    L = gpu_pkg.lib()
+    b128 = gpu_pkg.synth_sift(40000, seed=21)
+    q128 = gpu_pkg.synth_sift(100, seed=22)
+    b128_u8 = b128.astype(np.uint8)
+    assert np.array_equal(_f32(b128_u8), b128)
+    res = []
+    for u8 in (False, True):
+        hh = C.c_void_p(None)
+        if u8:
+            assert L.vs_bf_create_nd_u8(b128_u8.ctypes.data_as(C.c_void_p), 40000, 128, 0, 0, C.byref(hh)) == 0
+        else:
+            assert L.vs_bf_create(b128.ctypes.data_as(C.c_void_p), 40000, 128, 0, 0, 0, C.byref(hh)) == 0
+        ids = np.zeros((100, 5), dtype=np.int32)
+        d = np.zeros((100, 5), dtype=np.float32)
+        assert L.vs_prof_enable(hh, 1) == 0
+        assert L.vs_set_precision(hh, 2) == 0
+        assert L.vs_set_precision(hh, 0) == 0
+        assert L.vs_bf_search(hh, q128.ctypes.data_as(C.c_void_p), 100, 5, ids.ctypes.data_as(C.c_void_p),
+                              d.ctypes.data_as(C.c_void_p), None) == 0
+        ms, n = C.c_double(0), C.c_int64(0)
+        assert L.vs_prof_read(hh, 0, C.byref(ms), C.byref(n)) == 0
+        assert L.vs_index_dim(hh) == 128
+        res.append((ids, d, n.value))
+        L.vs_destroy(hh)
+    assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1]) and res[0][2] == res[1][2] > 0
+    oi, od = oracle.search_bf(b128, q128, 5)
+    assert np.array_equal(res[1][0], oi) and np.array_equal(res[1][1], od)
+    # argument checks as vs_bf_create_nd
+    h = C.c_void_p(None)
+    bp = b128_u8.ctypes.data_as(C.c_void_p)
+    assert L.vs_bf_create_nd_u8(bp, 2000, 0, 0, 0, C.byref(h)) == -1
+    assert L.vs_bf_create_nd_u8(bp, 200, 2049, 0, 0, C.byref(h)) == -5
+    # what a general index refuses stays refused
+    rng = np.random.default_rng(9000)
+    base, _ = u8_data(rng, 2000, 4, 300)
+    with gpu_pkg.BruteForceIndex.from_u8(base) as idx:
+        q = _f32(base[:3])
+        with pytest.raises(gpu_pkg.VSearchError) as e:
+            gpu_pkg.BruteForceIndex.search_vshards([idx], q, 5)
+        assert e.value.status == -5 and "300" in str(e.value)
+        ids = np.zeros((3, 5), dtype=np.int32)
+        d = np.zeros((3, 5), dtype=np.float32)
+        assert L.vs_ivf_search(idx._h, q.ctypes.data_as(C.c_void_p), 3, 5, 4, ids.ctypes.data_as(C.c_void_p),
+                               d.ctypes.data_as(C.c_void_p), None, None) == -5
+        oi, od = oracle.search_bf(_f32(base), q, 5)
+        gi, gd = idx.search(q, 5)
+        assert np.array_equal(gi, oi) and np.array_equal(gd, od)
+
+
+def test_wide_k_and_scores_use_the_fp32_rows(gpu_pkg):
+    import torch
+    rng = np.random.default_rng(4050)
+    base, q = u8_data(rng, 30000, 40, 96)
+    oi, od = oracle.search_bf(_f32(base), _f32(q), 50)
+    dev = torch.device("cuda:0")
+    s = torch.cuda.current_stream().cuda_stream
+    B, ld = 20, 30016
+    qd = torch.from_numpy(_f32(q[:B])).to(dev)
+    sc = []
+    with gpu_pkg.BruteForceIndex.from_u8(base) as idx:
+        tm = gpu_pkg.Timing()
+        ids, d = idx.search_topk(_f32(q), 50, tm)
+        assert np.array_equal(d, od) and np.array_equal(ids, oi)
+        assert tm.tie_queries > 0
+        out = torch.full((B, ld), -1.0, dtype=torch.float32, device=dev)
+        idx.scores_dev(qd.data_ptr(), B, out.data_ptr(), ld, s)
+        torch.cuda.synchronize()
+        sc.append(out.cpu().numpy())
+    with gpu_pkg.BruteForceIndex(_f32(base)) as idx:
+        out = torch.full((B, ld), -1.0, dtype=torch.float32, device=dev)
+        idx.scores_dev(qd.data_ptr(), B, out.data_ptr(), ld, s)
+        torch.cuda.synchronize()
+        sc.append(out.cpu().numpy())
+    assert np.array_equal(sc[0], sc[1])
+    assert np.array_equal(sc[0][:, :30000], np.stack([oracle.l2_row(_f32(q[i]), _f32(base)) for i in range(B)]))
+
+
+def test_cli_reads_bvecs(gpu_pkg, tmp_path):
+    rng = np.random.default_rng(9500)
+    base, q = u8_data(rng, 5000, 50, 300)
+    exe = os.path.join(os.path.dirname(gpu_pkg.LIB_PATH), "vsearch_bf")
+    assert os.path.exists(exe), "vsearch_bf not built (make -C hai-25-rag-on-edge_amd/csrc all)"
+    env = dict(os.environ)
+    env["LD_LIBRARY_PATH"] = gpu_pkg.hip_runtime_dir() + os.pathsep + env.get("LD_LIBRARY_PATH", "")
+    out = {}
+    for ext in ("fvecs", "bvecs"):
+        d = tmp_path / ext
+        d.mkdir()
+        if ext == "fvecs":
+            gpu_pkg.write_fvecs(str(d / "base.fvecs"), _f32(base))
+            gpu_pkg.write_fvecs(str(d / "query.fvecs"), _f32(q))
+        else:
+            gpu_pkg.write_bvecs(str(d / "base.bvecs"), base)
+            gpu_pkg.write_bvecs(str(d / "query.bvecs"), q)
+        r = subprocess.run([exe, f"base.{ext}", f"query.{ext}", "5", "results.txt"], cwd=d, env=env, capture_output=True,
+                           text=True, timeout=300)
+        assert r.returncode == 0, r.stderr
+        assert "Dimension: 300" in r.stdout
+        out[ext] = open(d / "results.txt", "rb").read()
+    assert out["bvecs"] == out["fvecs"]
+    oi, od = oracle.search_bf(_f32(base), _f32(q), 5)
+    oracle.write_results(str(tmp_path / "oracle_results.txt"), oi, od)
+    assert out["bvecs"] == open(tmp_path / "oracle_results.txt", "rb").read()
