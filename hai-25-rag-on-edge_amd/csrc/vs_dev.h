@@ -96,12 +96,29 @@ __device__ __forceinline__ float wave_kth_smallest(float a0, float a1, float a2,
     return res;
 }
 
-// kout rounds of wave-wide (dist, id) argmin over M <= 64*EPL candidates parked in LDS (cd/ci);
-// lane-local candidates live in registers, the reduction is DPP only.  Writes kout (dist, id)
-// pairs (padded with +inf / -1) and, if flag != nullptr, whether two emitted distances are equal.
-template <int EPL>
-__device__ __forceinline__ void wave_rank_emit(const float* cd, const int* ci, int M, int kout, float* out_d,
-                                               int32_t* out_i, int32_t* flag, const int32_t* id_map, int lane) {
+// k-th smallest (1-based) of the 16 values a DPP row holds, one per lane (r = lane & 15, g = lane >> 4), in every lane
+// of the row; +inf if fewer are finite
+__device__ __forceinline__ float row_kth_smallest(float m, int k, int r, int g) {
+    float kth = VS_INF;
+    for (int round = 0; round < k; ++round) {
+        float x = m;
+        x = fminf(x, dpp_mov_f<0xB1>(x));
+        x = fminf(x, dpp_mov_f<0x4E>(x));
+        x = fminf(x, dpp_mov_f<0x141>(x));
+        x = fminf(x, dpp_mov_f<0x140>(x));  // row minimum in every lane of the row
+        kth = x;
+        const unsigned rowmask = (unsigned)((__ballot(m == x) >> (16 * g)) & 0xFFFFull);
+        if (rowmask != 0u && r == __builtin_ctz(rowmask)) m = VS_INF;  // drop exactly one instance
+    }
+    return kth;
+}
+
+// The selection loop: `rounds` rounds of wave-wide (dist, id) argmin over M <= 64*EPL candidates parked in LDS (cd/ci).
+// Lane-local candidates live in registers, the reduction is DPP only (no LDS traffic, no barriers).  Every lane calls
+// emit(round, bd, bi) with the round's winner, which is then knocked out; once the candidates are used up the winner
+// is (+inf, 0x7fffffff).
+template <int EPL, typename Emit>
+__device__ __forceinline__ void wave_select_rounds(const float* cd, const int* ci, int M, int rounds, int lane, Emit emit) {
     float d[EPL];
     int id[EPL];
 #pragma unroll
@@ -110,9 +127,7 @@ __device__ __forceinline__ void wave_rank_emit(const float* cd, const int* ci, i
         d[e] = idx < M ? cd[idx] : VS_INF;
         id[e] = idx < M ? ci[idx] : 0x7fffffff;
     }
-    float prev = VS_INF;
-    int tie = 0;
-    for (int round = 0; round < kout; ++round) {
+    for (int round = 0; round < rounds; ++round) {
         float md = d[0];
         int mi = id[0];
 #pragma unroll
@@ -124,13 +139,7 @@ __device__ __forceinline__ void wave_rank_emit(const float* cd, const int* ci, i
         float bd;
         int bi;
         wave_lexmin(md, mi, bd, bi);
-        const bool none = bi == 0x7fffffff;
-        if (!none && round > 0 && bd == prev) tie = 1;
-        prev = none ? VS_INF : bd;
-        if (lane == 0) {
-            if (out_d) out_d[round] = none ? VS_INF : bd;
-            if (out_i) out_i[round] = none ? -1 : (id_map ? id_map[bi] : bi);
-        }
+        emit(round, bd, bi);
 #pragma unroll
         for (int e = 0; e < EPL; ++e)
             if (id[e] == bi && d[e] == bd) {
@@ -138,7 +147,6 @@ __device__ __forceinline__ void wave_rank_emit(const float* cd, const int* ci, i
                 id[e] = 0x7fffffff;
             }
     }
-    if (flag && lane == 0) *flag = tie;
 }
 
 // Rank by counting: lane e < M holds pair e; returns the number of pairs before it in (dist, id) order (ids are unique).

@@ -18,14 +18,6 @@ constexpr int kCompactCap = 4096;
 template <int EPL>
 __device__ __forceinline__ void wave_rank_and_emit(const MergeParams& p, int q, const float* cd, const int* ci, int M,
                                                    float* outd, int lane) {
-    float d[EPL];
-    int id[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int idx = e * 64 + lane;
-        d[e] = idx < M ? cd[idx] : VS_INF;
-        id[e] = idx < M ? ci[idx] : 0x7fffffff;
-    }
     // lane (round % 64) keeps the round's winner; the wave writes 64 rounds at a time (the id map is read once per output
     // there, all lanes at once: read inside the rounds it costs a cache round trip per round)
     float keep_d = VS_INF;
@@ -37,18 +29,7 @@ __device__ __forceinline__ void wave_rank_and_emit(const MergeParams& p, int q, 
             if (p.out_i) p.out_i[(int64_t)q * p.kout + round] = (keep_i >= 0 && p.id_map) ? p.id_map[keep_i] : keep_i;
         }
     };
-    for (int round = 0; round < p.kout; ++round) {
-        float md = d[0];
-        int mi = id[0];
-#pragma unroll
-        for (int e = 1; e < EPL; ++e)
-            if (lex_lt(d[e], id[e], md, mi)) {
-                md = d[e];
-                mi = id[e];
-            }
-        float bd;
-        int bi;
-        wave_lexmin(md, mi, bd, bi);
+    wave_select_rounds<EPL>(cd, ci, M, p.kout, lane, [&](int round, float bd, int bi) {
         const bool none = bi == 0x7fffffff;
         if (lane == 0 && round < kMergeTrack) outd[round] = none ? VS_INF : bd;
         if (lane == (round & 63)) {
@@ -56,13 +37,7 @@ __device__ __forceinline__ void wave_rank_and_emit(const MergeParams& p, int q, 
             keep_i = none ? -1 : bi;
         }
         if ((round & 63) == 63) flush(round - 63, 64);
-#pragma unroll
-        for (int e = 0; e < EPL; ++e)
-            if (id[e] == bi && d[e] == bd) {
-                d[e] = VS_INF;
-                id[e] = 0x7fffffff;
-            }
-    }
+    });
     if (p.kout & 63) flush(p.kout & ~63, p.kout & 63);
 }
 
@@ -174,32 +149,12 @@ __device__ __forceinline__ void merge_compact_body(const MergeParams& p, const M
     bool filtered = false;
     if (M > 256 && p.kout <= 64) {  // workgroup-uniform
         if (wave == 0) {
-            float d[4];
-            int id[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                d[e] = cd[e * 64 + lane];
-                id[e] = ci[e * 64 + lane];
-            }
             float bd = VS_INF;
             int bi = 0x7fffffff;
-            for (int round = 0; round < p.kout; ++round) {
-                float md = d[0];
-                int mi = id[0];
-#pragma unroll
-                for (int e = 1; e < 4; ++e)
-                    if (lex_lt(d[e], id[e], md, mi)) {
-                        md = d[e];
-                        mi = id[e];
-                    }
-                wave_lexmin(md, mi, bd, bi);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (id[e] == bi && d[e] == bd) {
-                        d[e] = VS_INF;
-                        id[e] = 0x7fffffff;
-                    }
-            }
+            wave_select_rounds<4>(cd, ci, 256, p.kout, lane, [&](int, float wd, int wi) {  // (M > 256: all 256 are candidates)
+                bd = wd;
+                bi = wi;
+            });
             if (lane == 0) {
                 s_thr_d = bd;
                 s_thr_i = bi;

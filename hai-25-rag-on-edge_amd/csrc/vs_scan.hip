@@ -633,17 +633,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
             // groups this large it is within a few per cent of the k1-th smallest of all 256.
             float m = fminf(fminf(fminf(v0[0], v0[1]), fminf(v0[2], v0[3])), fminf(fminf(v1[0], v1[1]), fminf(v1[2], v1[3])));
             m = fminf(m, fminf(fminf(fminf(v2[0], v2[1]), fminf(v2[2], v2[3])), fminf(fminf(v3[0], v3[1]), fminf(v3[2], v3[3]))));
-            float kth = VS_INF;
-            for (int round = 0; round < p.k1; ++round) {
-                float x = m;
-                x = fminf(x, dpp_mov_f<0xB1>(x));
-                x = fminf(x, dpp_mov_f<0x4E>(x));
-                x = fminf(x, dpp_mov_f<0x141>(x));
-                x = fminf(x, dpp_mov_f<0x140>(x));  // row minimum in every lane of the row
-                kth = x;
-                const unsigned rowmask = (unsigned)((__ballot(m == x) >> (16 * g)) & 0xFFFFull);
-                if (rowmask != 0u && r == __builtin_ctz(rowmask)) m = VS_INF;  // drop exactly one instance
-            }
+            const float kth = row_kth_smallest(m, p.k1, r, g);
             if (r == 0) lds_tau[4 * wave + g] = kth < VS_INF ? next_up(kth) : VS_INF;
         }
         lds_barrier();
@@ -728,41 +718,16 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
         constexpr int EPL = decltype(epl_tag)::value;
         for (int qq = wave; qq < NQ; qq += kScanWaves) {
             const int M = lds_cnt[qq];
-            float cd[EPL];
-            int ci[EPL];
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) {
-                const int idx = e * 64 + lane;
-                cd[e] = idx < M ? cand_d[qq * cap + idx] : VS_INF;
-                ci[e] = idx < M ? cand_i[qq * cap + idx] : 0x7fffffff;
-            }
             // partial lists are query-major: [batch][query][workgroup][KCAP] (one merge launch ranks all batches)
             float* od = p.part_d + (((int64_t)batch * kMaxBatch + qq) * kSlotStride + blockIdx.x) * KCAP;
             int32_t* oi = p.part_i + (((int64_t)batch * kMaxBatch + qq) * kSlotStride + blockIdx.x) * KCAP;
             const int rounds = min(min(p.k1, KCAP), M);
-            for (int round = 0; round < rounds; ++round) {
-                float md = cd[0];
-                int mi = ci[0];
-#pragma unroll
-                for (int e = 1; e < EPL; ++e)
-                    if (lex_lt(cd[e], ci[e], md, mi)) {
-                        md = cd[e];
-                        mi = ci[e];
-                    }
-                float bd;
-                int bi;
-                wave_lexmin(md, mi, bd, bi);
+            wave_select_rounds<EPL>(cand_d + qq * cap, cand_i + qq * cap, M, rounds, lane, [&](int round, float bd, int bi) {
                 if (lane == 0) {
                     od[round] = bd;
                     oi[round] = bi;
                 }
-#pragma unroll
-                for (int e = 0; e < EPL; ++e)
-                    if (ci[e] == bi && cd[e] == bd) {
-                        cd[e] = VS_INF;
-                        ci[e] = 0x7fffffff;
-                    }
-            }
+            });
             if (lane < KCAP && lane >= rounds) {
                 od[lane] = VS_INF;
                 oi[lane] = -1;

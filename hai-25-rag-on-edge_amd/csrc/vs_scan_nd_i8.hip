@@ -25,12 +25,11 @@
 // Organisation: scan_nd_kernel's.  Nothing in a wave grows with dim: a wave owns a block of kNd8Tiles 16-row tiles and
 // keeps their kNd8Tiles x NQH int32 accumulators resident while it walks the rows in steps of 128 bytes (one line per
 // row, two 16x16x64 MFMAs per tile and query block), with a 64-byte tail step when dim_b / 64 is odd.  Rows and
-// fragments are loaded one step ahead with ordinary global loads whose waits the compiler places.  The threshold exchange
-// and the workgroup merge are scan_nd_kernel's, repeated here so that vs_scan_nd.hip and its measured figures stay as
-// they are.
+// fragments are loaded one step ahead with ordinary global loads whose waits the compiler places.  The top-k step, the
+// threshold exchange and the workgroup merge are the ones scan_nd_kernel uses (vs_scan_tail.h).
 #include "vs_kernels.h"
 #include "vs_dev.h"
-#include <type_traits>
+#include "vs_scan_tail.h"
 
 namespace vs {
 
@@ -39,8 +38,6 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr int kNd8Tiles = 4;                          // 16-row tiles per wave block
 constexpr int kNd8BlockRows = kNd8Tiles * kTileRows;  // 64 <= kScanPadRows: a block never reads past the spare rows
 static_assert(kNd8BlockRows <= kScanPadRows, "row blocks are loaded unclamped");
-constexpr int kNd8MergeSmall = 64;                    // entries per query of the workgroup merge's fast path
-constexpr int kNd8PassQ = 4;                          // queries per pass of its fallback
 constexpr int kNd8NormLimit = 1 << 24;                // ||q||^2 + ||b||^2 at most this: the fp32 path is exact
 
 // x as an integer in [0, 255], or false (NaN and infinities included)
@@ -117,17 +114,10 @@ template <int NQH, int KCAP>
 __global__ __launch_bounds__(kScanThreads, 1) void scan_nd_i8_kernel(const ScanNdI8Params pn) {
     const ScanParams& p = pn.s;
     constexpr int T = kNd8Tiles;
-    constexpr int NQ = NQH * 16;
-    constexpr int CAP = 32 * KCAP;  // 32 lane lists per query
     // the fragments of a step are loaded one step ahead like its rows, except in the largest instantiation (two query
     // blocks, 16-entry lists), which has no registers left for the second set: there they are loaded in their own step
     constexpr bool BAHEAD = NQH * KCAP < 32;
-    __shared__ float lds_wmin[kScanWaves * 32];
-    __shared__ float lds_tau[32];
-    __shared__ int lds_cnt[32];
-    __shared__ float mrg_d[kMaxBatch * kNd8MergeSmall];  // fast path [32][kNd8MergeSmall]; fallback [kNd8PassQ][CAP]
-    __shared__ int mrg_i[kMaxBatch * kNd8MergeSmall];
-    static_assert(kNd8PassQ * CAP <= kMaxBatch * kNd8MergeSmall, "the fallback pass fits the merge buffer");
+    __shared__ NdTailLds tail;
     if (p.run_if && !p.run_if[0]) return;
 
     const int tid = threadIdx.x;
@@ -257,16 +247,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_nd_i8_kernel(const ScanN
                         d[j] = (float)(qt[h] + rt[j] - 2 * acc[t][h][j]);
                         if (ragged && rbase + j > last_row) d[j] = VS_INF;
                     }
-                    const float dmin = fminf(fminf(d[0], d[1]), fminf(d[2], d[3]));
-                    wmin[h] = fminf(wmin[h], dmin);
-                    if (dmin < tau[h]) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            if (d[j] < tau[h]) {
-                                list_insert<KCAP>(ld[h], li[h], d[j], (int)(rbase + j) + p.id_offset);
-                                tau[h] = fminf(tau[h], ld[h][KCAP - 1]);
-                            }
-                    }
+                    nd_topk_step<KCAP>(d, rbase, p.id_offset, wmin[h], tau[h], ld[h], li[h]);
                 }
             }
         };
@@ -276,146 +257,10 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_nd_i8_kernel(const ScanN
         if (wb < blocks_total) do_block(wb);
         if (xchg) {
             xchg = false;
-            // ---- threshold exchange (scan_nd_kernel's): the first block goes into the lane lists unbounded; every
-            // workgroup then publishes, per query, the smallest distance it has seen, reads what the others published
-            // and takes the k1-th smallest of 16 group minima as an upper bound of the final k1-th best distance.  The
-            // spin is bounded and an unpublished slot reads +inf, which only loosens the bound: the result does not
-            // depend on timing or residency.
-#pragma unroll
-            for (int h = 0; h < NQH; ++h) {
-                float m = wmin[h];
-                m = fminf(m, __shfl_xor(m, 16));
-                m = fminf(m, __shfl_xor(m, 32));
-                if (g == 0) lds_wmin[wave * 32 + h * 16 + r] = m;
-            }
-            __syncthreads();
-            if (tid < NQ) {
-                float m = lds_wmin[tid];
-#pragma unroll
-                for (int w = 1; w < kScanWaves; ++w) m = fminf(m, lds_wmin[w * 32 + tid]);
-                __hip_atomic_store(slots + tid * kSlotStride + blockIdx.x, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            // DPP row g of wave w reduces query 4 w + g: lane r folds workgroups 16 r .. 16 r + 15
-            const int qx = 4 * wave + g;
-            const float* s0 = slots + qx * kSlotStride + 16 * r;
-            const int need = (int)gridDim.x / 2;
-            float m = VS_INF;
-            for (int spin = 0;; ++spin) {
-                int cf = 0;
-                m = VS_INF;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float v = __hip_atomic_load(s0 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    cf += v < VS_INF;
-                    m = fminf(m, v);
-                }
-                cf += dpp_mov_i<0xB1>(cf);
-                cf += dpp_mov_i<0x4E>(cf);
-                cf += dpp_mov_i<0x141>(cf);
-                cf += dpp_mov_i<0x140>(cf);  // row sum: workgroups that have published this row's query
-                if (__all(qx >= NQ || cf >= need) || spin >= 2048) break;
-                __builtin_amdgcn_s_sleep(24);
-            }
-            float kth = VS_INF;
-            for (int round = 0; round < p.k1; ++round) {
-                float x = m;
-                x = fminf(x, dpp_mov_f<0xB1>(x));
-                x = fminf(x, dpp_mov_f<0x4E>(x));
-                x = fminf(x, dpp_mov_f<0x141>(x));
-                x = fminf(x, dpp_mov_f<0x140>(x));  // row minimum in every lane of the row
-                kth = x;
-                const unsigned rowmask = (unsigned)((__ballot(m == x) >> (16 * g)) & 0xFFFFull);
-                if (rowmask != 0u && r == __builtin_ctz(rowmask)) m = VS_INF;  // drop exactly one instance
-            }
-            if (r == 0) lds_tau[qx] = kth < VS_INF ? next_up(kth) : VS_INF;
-            __syncthreads();
-#pragma unroll
-            for (int h = 0; h < NQH; ++h) {
-                tq[h] = lds_tau[h * 16 + r];
-                tau[h] = fminf(tau[h], tq[h]);
-            }
+            xchg_bound<NQH>(tail, slots, p.k1, tid, wave, wmin, tq, tau);  // (after the first block: vs_scan_tail.h)
         }
         }
-
-        // ---- workgroup merge (scan_nd_kernel's): the entries that can still matter (d < bound) are compacted into LDS
-        // and ranked; the sorted per-workgroup lists go to merge_compact_kernel.
-        auto rank = [&](int qq, const float* cand_d, const int* cand_i, auto epl_tag) {
-            constexpr int EPL = decltype(epl_tag)::value;
-            const int M = min(lds_cnt[qq], EPL * 64);
-            float cd[EPL];
-            int ci[EPL];
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) {
-                const int idx = e * 64 + lane;
-                cd[e] = idx < M ? cand_d[idx] : VS_INF;
-                ci[e] = idx < M ? cand_i[idx] : 0x7fffffff;
-            }
-            // partial lists are query-major: [batch][query][workgroup][KCAP] (one merge launch ranks all batches)
-            float* od = p.part_d + (((int64_t)batch * kMaxBatch + qq) * kSlotStride + blockIdx.x) * KCAP;
-            int32_t* oi = p.part_i + (((int64_t)batch * kMaxBatch + qq) * kSlotStride + blockIdx.x) * KCAP;
-            const int rounds = min(min(p.k1, KCAP), M);
-            for (int round = 0; round < rounds; ++round) {
-                float md = cd[0];
-                int mi = ci[0];
-#pragma unroll
-                for (int e = 1; e < EPL; ++e)
-                    if (lex_lt(cd[e], ci[e], md, mi)) {
-                        md = cd[e];
-                        mi = ci[e];
-                    }
-                float bd;
-                int bi;
-                wave_lexmin(md, mi, bd, bi);
-                if (lane == 0) {
-                    od[round] = bd;
-                    oi[round] = bi;
-                }
-#pragma unroll
-                for (int e = 0; e < EPL; ++e)
-                    if (ci[e] == bi && cd[e] == bd) {
-                        cd[e] = VS_INF;
-                        ci[e] = 0x7fffffff;
-                    }
-            }
-            if (lane < KCAP && lane >= rounds) {
-                od[lane] = VS_INF;
-                oi[lane] = -1;
-            }
-        };
-        auto compact = [&](int q_lo, int q_n, int cap) {
-#pragma unroll
-            for (int h = 0; h < NQH; ++h) {
-                const int qidx = h * 16 + r;
-                if (qidx < q_lo || qidx >= q_lo + q_n) continue;
-#pragma unroll
-                for (int j = 0; j < KCAP; ++j)
-                    if (li[h][j] >= 0 && ld[h][j] < tq[h]) {
-                        const int pos = atomicAdd(&lds_cnt[qidx], 1);
-                        if (pos < cap) {
-                            mrg_d[(qidx - q_lo) * cap + pos] = ld[h][j];
-                            mrg_i[(qidx - q_lo) * cap + pos] = li[h][j];
-                        }
-                    }
-            }
-        };
-        if (tid < 32) lds_cnt[tid] = 0;
-        __syncthreads();
-        compact(0, NQ, kNd8MergeSmall);
-        const bool too_many = __syncthreads_or(lds_cnt[tid & 31] > kNd8MergeSmall);
-        if (!too_many) {
-            for (int qq = wave; qq < NQ; qq += kScanWaves)
-                rank(qq, mrg_d + qq * kNd8MergeSmall, mrg_i + qq * kNd8MergeSmall, std::integral_constant<int, 1>{});
-        } else {
-            for (int q_lo = 0; q_lo < NQ; q_lo += kNd8PassQ) {
-                __syncthreads();
-                if (tid < 32) lds_cnt[tid] = 0;
-                __syncthreads();
-                compact(q_lo, kNd8PassQ, CAP);
-                __syncthreads();
-                if (wave < kNd8PassQ) rank(q_lo + wave, mrg_d + wave * CAP, mrg_i + wave * CAP, std::integral_constant<int, CAP / 64>{});
-            }
-        }
-        __syncthreads();  // LDS is reused by the next batch
+        wg_merge_lists<NQH, KCAP>(tail, p, batch, tid, wave, ld, li, tq);  // (ends with a barrier)
     }
 }
 

@@ -42,8 +42,8 @@ def _ids_by_id_order(base, q, oi, od, rows):
     return want
 
 
-def _check_exact(pkg, base, q, ks, precisions=(2, 1), batch=None, want_ties=True):
-    want = {k: oracle.search_bf(_f32(base), _f32(q), k) for k in ks}
+def _check_exact(pkg, base, q, ks, precisions=(2, 1), batch=None, want_ties=True, want=None):
+    want = want or {k: oracle.search_bf(_f32(base), _f32(q), k) for k in ks}
     with pkg.BruteForceIndex.from_u8(base) as idx:
         assert idx.getDim() == base.shape[1] and idx.getNumDocs() == base.shape[0]
         if batch:
@@ -86,6 +86,25 @@ def test_batch_sizes_at_dim_320(gpu_pkg, batch):
     rng = np.random.default_rng(3000 + batch)
     base, q = u8_data(rng, 20000, 70, 320)
     _check_exact(gpu_pkg, base, q, (5, 15), precisions=(2,), batch=batch)
+
+
+def test_threshold_exchange_of_both_precisions(gpu_pkg):
+    """The in-kernel threshold exchange of scan_nd_i8_kernel and of scan_nd_kernel on one index, against the oracle.
+
+    The exchange cannot be seen from outside; the row count turns it on.  bf_launch enables it when grid >= 16 and a
+    workgroup has at least 16 * kScanWaves = 128 16-row tiles on the byte path (6 * kScanWaves = 48 on the fp32 rows).
+    270001 rows are 16876 tiles; on 256 CUs scan_geometry gives the byte path 16876 / 128 = 131 workgroups of 129 tiles
+    and the fp32 rows 256 workgroups of 66 tiles, so both precisions exchange (the 20 000- and 30 000-row bases above
+    never do).  dim_b = 192 is three 64-byte steps: the paired loop and the tail step both run, and the last 64-row
+    block is ragged.  Batches of 32 with k = 5 and 15 are NQH = 2 with the 8- and 16-entry lists, a batch of 16 is
+    NQH = 1: all four instantiations of the byte kernel and the fp32 kernel's top-k ones."""
+    base, q = u8_data(np.random.default_rng(11000), 270001, 70, 192)
+    ks = (5, 15)
+    bf, qf = _f32(base), _f32(q)
+    want = {k: oracle.search_bf(bf, qf, k) for k in ks}
+    del bf
+    _check_exact(gpu_pkg, base, q, ks, precisions=(2, 1), want=want)
+    _check_exact(gpu_pkg, base, q, ks, precisions=(2,), batch=16, want=want)
 
 
 # ---- device calls at dim 768: 9 batches of 32, k = 5 (shared by the two tests below; nothing modifies it)
