@@ -527,7 +527,10 @@ class Q8Runner:
 
 
 class IVFIndex(_Index):
-    """class IVFIndex (IVFIndex.h:14-97) on the GPU, reordered (contiguous list) layout, L2."""
+    """class IVFIndex (IVFIndex.h:14-97) on the GPU, reordered (contiguous list) layout, L2.
+
+    Any vector length 1 <= d <= 2048: 128-d arrays or directories give the specialised index, any other dimension a
+    general IVF index (fp32 rows, squared L2, k <= 16, one GPU; vsearch.h at vs_ivf_create)."""
 
     def __init__(self, index_dir: str | None = None, device: int = 0, rank: int = 0, world: int = 1, *,
                  vectors_reordered=None, centroids=None, cluster_offsets=None, reorder_to_original=None):
@@ -598,7 +601,7 @@ class IVFIndex(_Index):
 
     def search_dev_multi(self, q_ptr: int, n_batches: int, B: int, k: int, nprobe: int, ids_ptr: int, dists_ptr: int,
                          stream: int):
-        """n_batches independent batches [n_batches][B][128] -> [n_batches][B][k]; asynchronous on `stream`."""
+        """n_batches independent batches [n_batches][B][dim] -> [n_batches][B][k]; asynchronous on `stream`."""
         _check(lib().vs_ivf_search_dev_multi(self._h, q_ptr, n_batches, B, k, nprobe, ids_ptr, dists_ptr, stream))
 
     def search_dev_sharded(self, comm: "Comm", q_ptr: int, n_batches: int, B: int, k: int, nprobe: int, ids_ptr: int,

@@ -82,6 +82,9 @@ struct vs_index {
     int dim = 0;
     // general index (vs_bf_create_nd with dim != 128, or VSEARCH_ND_FORCE): rows of dim_p = nd_dim_p(dim) floats, zero padded,
     // scanned by scan_nd_kernel; no int8 copy, no seed sample, no bf16 filter statistics.  Otherwise dim_p == dim == 128.
+    // General IVF index (kind 1; vs_ivf_create / vs_ivf_load with dim != 128, or VSEARCH_IVF_ND_FORCE): rows and centroids
+    // laid out the same way, searched by the list-major general scan (ivf_group_nd_dev); no int8 copy, no tiled copy, no
+    // head rows, no chunk table.
     bool general = false;
     int dim_p = 0;
     vs::DevBuf<float> d_nd_qfrag;  // [kMaxMulti][dim_p / 16][2][64][4] scratch of launch_scan_nd
@@ -237,6 +240,19 @@ struct vs_index {
         bool ready = false;          // every buffer above allocated (ensure_ivf_widek)
     } widek[kWideLanesMax];
     vs::DevBuf<unsigned long long> widek_stats;  // [4] (VSEARCH_IVF_WIDEK_STATS=1 only): see vs_ivf_widek_stats
+    // general IVF index: scratch of one launch group of up to kIvfNdGroupQ queries (vs::IvfNdParams; ensure_ivf_nd)
+    struct IvfNd {
+        int np_max = 0;              // probes per query the buffers hold: min(kMaxNprobe, nlist)
+        vs::DevBuf<int32_t> probes;  // [kIvfNdGroupQ][np_max]
+        vs::DevBuf<float> qrows;     // [kIvfNdGroupQ][dim_p]
+        vs::DevBuf<float> qnorm;     // [kIvfNdGroupQ]
+        vs::DevBuf<int32_t> plan;    // list_cnt [2][nlist] | list_start [nlist + 1] | n_items [1]
+        vs::DevBuf<int32_t> slots;   // [kIvfNdGroupQ * np_max]
+        vs::DevBuf<int32_t> items;   // [ivf_nd_items_cap(nlist, np_max)][2]
+        vs::DevBuf<float> part_d;    // [kIvfNdGroupQ][np_max][kKcapMax]
+        vs::DevBuf<int32_t> part_i;
+        bool ready = false;          // every buffer above allocated
+    } ivfnd;
     vs::Stream wide_stream[kWideLanesMax];
     vs::Event wide_fork, wide_join[kWideLanesMax];
     bool wide_streams_ready = false;
@@ -266,7 +282,7 @@ struct vs_index {
     // vs_ivf_search through the wide pipeline: larger chunks (up to kIvfHostGroups launch groups each, dealt to the two
     // lanes), ONE upload and ONE download per chunk -- every hipMemcpyAsync costs the host tens of microseconds
     struct IvfHostSlot {
-        vs::PinBuf<float> pin_q;   // [kIvfHostChunk][128]
+        vs::PinBuf<float> pin_q;   // [ivf_host_cap][dim]
         vs::PinBuf<float> pin_out; // dists [n][k] | ids [n][k] of one chunk
         vs::DevBuf<float> d_q;
         vs::DevBuf<float> d_out;   // same layout on the device
@@ -631,6 +647,18 @@ int refuse_general(const vs_index* h, const char* what) {
     if (!h || !h->general) return VS_OK;
     char msg[160];
     snprintf(msg, sizeof(msg), "%s: not available on a general-dimension index (dim = %d); only dim == 128 is compiled in", what, h->dim);
+    set_error(msg);
+    return VS_ERR_UNSUPPORTED;
+}
+
+// vs_ivf_* calls on an index made by vs_bf_create_nd*
+int refuse_general_bf(const vs_index* h, const char* what) { return h && h->kind == 0 ? refuse_general(h, what) : VS_OK; }
+// what a general IVF index leaves out
+int refuse_general_ivf(const vs_index* h, const char* what) {
+    if (!h || !h->general || h->kind != 1) return VS_OK;
+    char msg[200];
+    snprintf(msg, sizeof(msg), "%s: not available on a general-dimension IVF index (dim = %d): fp32 rows, squared L2, k <= 16, one GPU", what,
+             h->dim);
     set_error(msg);
     return VS_ERR_UNSUPPORTED;
 }
@@ -1161,6 +1189,87 @@ int ivf_fallback_batch_dev(vs_index* h, const float* q_dev, int B, int k, int np
     return VS_OK;
 }
 
+// Scratch of the general IVF index's launch groups.  Built aside and moved in whole: a failure part-way frees what it
+// allocated and leaves the index as it was.
+int ensure_ivf_nd(vs_index* h) {
+    if (h->ivfnd.ready) return VS_OK;
+    vs_index::IvfNd W;
+    int rc;
+    W.np_max = std::min(kMaxNprobe, h->nlist);
+    const size_t gq = vs::kIvfNdGroupQ, pairs = gq * W.np_max;
+    if ((rc = W.probes.alloc(pairs)) || (rc = W.qrows.alloc(gq * h->dim_p)) || (rc = W.qnorm.alloc(gq)) ||
+        (rc = W.plan.alloc((size_t)3 * h->nlist + 2)) || (rc = W.slots.alloc(pairs)) ||
+        (rc = W.items.alloc((size_t)2 * vs::ivf_nd_items_cap(h->nlist, W.np_max))) || (rc = W.part_d.alloc(pairs * kKcapMax)) ||
+        (rc = W.part_i.alloc(pairs * kKcapMax)))
+        return rc;
+    W.ready = true;
+    h->ivfnd = std::move(W);
+    return VS_OK;
+}
+
+// One launch group of a general IVF index: nb <= 32 batches of B queries ([nb][B][dim], back to back), everything on s.
+// Coarse scores per batch are the brute-force general scan's on the centroid table (equal scores: the lower list id,
+// launch_pick_probes); then the plan, the list-major scan and the ranking of the group's partial lists.
+int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int nprobe, float* out_d, int32_t* out_i, hipStream_t s) {
+    const int kcap = pick_kcap(k);
+    if (!kcap) return refuse_general_ivf(h, "k > 16");
+    int rc = ensure_ivf_nd(h);
+    if (rc) return rc;
+    vs_index::IvfNd& W = h->ivfnd;
+    if (nb < 1 || nb * B > vs::kIvfNdGroupQ || nprobe > W.np_max) {
+        set_error("ivf_group_nd_dev: launch group out of range");
+        return VS_ERR_INVALID;
+    }
+    const int64_t ld = (h->nlist + 63) & ~63;
+    stage_mark(h, 0, s);
+    for (int b = 0; b < nb; ++b) {
+        if ((rc = scores_dev(h, h->d_centroids, h->d_cnorm, h->nlist, q_dev + (size_t)b * B * h->dim, B, h->d_scores, ld, s))) return rc;
+        HIPCHK(vs::launch_pick_probes(h->d_scores, ld, B, h->nlist, nprobe, W.probes + (size_t)b * B * nprobe, s));
+    }
+    stage_mark(h, 1, s);
+    vs::IvfNdParams ip{};
+    ip.vecs = h->d_vecs;
+    ip.vnorm = h->d_norm;
+    ip.offsets = h->d_offsets;
+    ip.nlist = h->nlist;
+    ip.dim = h->dim;
+    ip.dim_p = h->dim_p;
+    ip.q = q_dev;
+    ip.group_q = nb * B;
+    ip.nprobe = nprobe;
+    ip.k = k;
+    ip.kcap = kcap;
+    ip.probes = W.probes;
+    ip.qrows = W.qrows;
+    ip.qnorm = W.qnorm;
+    ip.list_cnt = W.plan;
+    ip.list_start = W.plan + (size_t)2 * h->nlist;
+    ip.n_items = W.plan + (size_t)3 * h->nlist + 1;
+    ip.slots = W.slots;
+    ip.items = W.items;
+    ip.part_d = W.part_d;
+    ip.part_i = W.part_i;
+    ip.cand_count = h->d_cand;
+    HIPCHK(vs::launch_ivf_nd_plan(ip, s));
+    stage_mark(h, 2, s);
+    prof_begin(h, 1, s);
+    HIPCHK(vs::launch_ivf_nd_scan(ip, h->num_cus, s));
+    prof_end(h, 1, s);
+    vs::MergeParams m{};
+    m.part_d = W.part_d;
+    m.part_i = W.part_i;
+    m.G = nprobe;
+    m.kin = kcap;
+    m.nq = nb * B;
+    m.kout = k;
+    m.out_d = out_d;
+    m.out_i = out_i;
+    m.id_map = h->d_r2o;
+    HIPCHK(vs::launch_merge_layout(m, kcap, (int64_t)nprobe * kcap, s));
+    stage_mark(h, 3, s);
+    return VS_OK;
+}
+
 // Scratch of one lane of the wide pipeline, sized for launch groups of h->ivf_gb batches in up to h->ivf_nsb super-batches.
 int ensure_ivf_wide(vs_index* h, int lane) {
     if (h->wide[lane].ready) return VS_OK;
@@ -1549,7 +1658,7 @@ int ensure_ivf_host(vs_index* h, int k = 0) {
         vs_index::IvfHostSlot S;
         S.out_k = std::max(k > 64 ? vs::kIvfWideKMax : 64, slot.ready ? slot.out_k : 0);
         const size_t out = cap * S.out_k * 2;
-        if ((rc = S.pin_q.alloc(cap * vs::kDim)) || (rc = S.pin_out.alloc(out)) || (rc = S.d_q.alloc(cap * vs::kDim)) ||
+        if ((rc = S.pin_q.alloc(cap * h->dim)) || (rc = S.pin_out.alloc(out)) || (rc = S.d_q.alloc(cap * h->dim)) ||
             (rc = S.d_out.alloc(out)) || (rc = S.ev_h2d.create()) || (rc = S.ev_comp[0].create()) || (rc = S.ev_comp[1].create()) ||
             (rc = S.ev_d2h.create()))
             return rc;
@@ -1569,9 +1678,15 @@ int ivf_multi_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int npr
                                        : "k > 16 needs the list-major IVF pipeline (nlist <= 4096, rows resident)");
         return VS_ERR_UNSUPPORTED;
     }
+    if (h->general) {  // launch groups of up to 32 batches, all on the caller's stream
+        for (int b0 = 0; b0 < nb && !rc; b0 += vs::kIvfWideBatches)
+            rc = ivf_group_nd_dev(h, q_dev + (size_t)b0 * B * h->dim, std::min(vs::kIvfWideBatches, nb - b0), B, k, nprobe,
+                                  out_d + (size_t)b0 * B * k, out_i + (size_t)b0 * B * k, user);
+        return rc;
+    }
     if (!ivf_wide_ok(h, k)) {
         for (int b = 0; b < nb && !rc; ++b)
-            rc = ivf_fallback_batch_dev(h, q_dev + (size_t)b * B * vs::kDim, B, k, nprobe, out_d + (size_t)b * B * k, out_i + (size_t)b * B * k, user);
+            rc = ivf_fallback_batch_dev(h, q_dev + (size_t)b * B * h->dim, B, k, nprobe, out_d + (size_t)b * B * k, out_i + (size_t)b * B * k, user);
         return rc;
     }
     const int gb = h->ivf_gb;
@@ -1579,7 +1694,7 @@ int ivf_multi_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int npr
     const int lanes = std::min({h->ivf_lanes, kWideLanesMax, groups});
     if (lanes <= 1) {
         for (int b0 = 0; b0 < nb && !rc; b0 += gb)
-            rc = ivf_group_wide_dev(h, 0, q_dev + (size_t)b0 * B * vs::kDim, std::min(gb, nb - b0), B, k, nprobe, out_d + (size_t)b0 * B * k,
+            rc = ivf_group_wide_dev(h, 0, q_dev + (size_t)b0 * B * h->dim, std::min(gb, nb - b0), B, k, nprobe, out_d + (size_t)b0 * B * k,
                                     out_i + (size_t)b0 * B * k, user);
         return rc;
     }
@@ -1588,7 +1703,7 @@ int ivf_multi_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int npr
     for (int i = 0; i < lanes; ++i) HIPCHK(hipStreamWaitEvent(h->wide_stream[i], h->wide_fork, 0));
     int g = 0;
     for (int b0 = 0; b0 < nb && !rc; b0 += gb, ++g)
-        rc = ivf_group_wide_dev(h, g % lanes, q_dev + (size_t)b0 * B * vs::kDim, std::min(gb, nb - b0), B, k, nprobe, out_d + (size_t)b0 * B * k,
+        rc = ivf_group_wide_dev(h, g % lanes, q_dev + (size_t)b0 * B * h->dim, std::min(gb, nb - b0), B, k, nprobe, out_d + (size_t)b0 * B * k,
                                 out_i + (size_t)b0 * B * k, h->wide_stream[g % lanes]);
     for (int i = 0; i < lanes; ++i) {  // (also after an error: the user's stream must not run ahead of what was enqueued)
         HIPCHK(hipEventRecord(h->wide_join[i], h->wide_stream[i]));
@@ -1712,7 +1827,7 @@ int vs_prof_enable(vs_index* h, int on) {
 }
 
 int vs_ivf_widek_stats(vs_index* h, int64_t* out, int reset) {
-    if (refuse_general(h, "vs_ivf_widek_stats")) return VS_ERR_UNSUPPORTED;
+    if (refuse_general_bf(h, "vs_ivf_widek_stats") || refuse_general_ivf(h, "vs_ivf_widek_stats")) return VS_ERR_UNSUPPORTED;
     if (!h || h->kind != 1 || !out) {
         set_error("vs_ivf_widek_stats: bad arguments");
         return VS_ERR_INVALID;
@@ -1878,11 +1993,12 @@ static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int m
 }
 
 int vs_ivf_set_metric(vs_index* h, int metric) {
-    if (refuse_general(h, "vs_ivf_set_metric")) return VS_ERR_UNSUPPORTED;
+    if (refuse_general_bf(h, "vs_ivf_set_metric")) return VS_ERR_UNSUPPORTED;
     if (!h || h->kind != 1 || (metric != VS_METRIC_L2 && metric != VS_METRIC_IP)) {
         set_error("vs_ivf_set_metric: an IVF index and VS_METRIC_L2 or VS_METRIC_IP");
         return VS_ERR_INVALID;
     }
+    if (metric == VS_METRIC_IP && refuse_general_ivf(h, "vs_ivf_set_metric(VS_METRIC_IP)")) return VS_ERR_UNSUPPORTED;
     h->metric = metric;  // (inner product: centroid scores, bounds, list scan and ranking on -q.v over the fp32 rows)
     return VS_OK;
 }
@@ -2072,8 +2188,18 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
         set_error("vs_ivf_create: bad arguments");
         return VS_ERR_INVALID;
     }
-    if (dim != vs::kDim) {
-        set_error("only dim == 128 is compiled in");
+    if (dim < 1) {
+        set_error("vs_ivf_create: dim must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (dim > vs::kNdMaxDim) {
+        set_error("vs_ivf_create: dim > 2048 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (dim != vs::kDim && world > 1) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "vs_ivf_create: a general-dimension IVF index (dim = %d) cannot be sharded; only dim == 128 can", dim);
+        set_error(msg);
         return VS_ERR_UNSUPPORTED;
     }
     if (offsets[0] != 0 || offsets[nlist] != n_rows) {
@@ -2096,6 +2222,11 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
     h->kind = 1;
     h->device = device;
     h->dim = dim;
+    // comparison toggle (VSEARCH_IVF_ND_FORCE=1, read here): an unsharded 128-d index is built as a general IVF index as
+    // well, so that the list-major general scan can be set against the specialised pipeline on the same data
+    const char* nd_force = getenv("VSEARCH_IVF_ND_FORCE");
+    h->general = dim != vs::kDim || (world == 1 && nd_force && atoi(nd_force) != 0);
+    h->dim_p = h->general ? vs::nd_dim_p(dim) : dim;
     h->metric = VS_METRIC_L2;
     h->n_total = n_rows;
     h->nlist = nlist;
@@ -2138,21 +2269,37 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
     // exact int8 copy of the (reordered, local) rows when they are byte valued: the list scan then moves 4x fewer bytes
     std::vector<int8_t> host_bytes;
     std::vector<int32_t> host_rterm;
-    if (h->metric == VS_METRIC_L2 && n_local > 0 && (rc = build_u8_copy(h, up, n_local, &host_bytes, &host_rterm))) return fail(rc);
-    if ((rc = h->d_centroids.alloc(((size_t)nlist + vs::kScanPadRows) * dim))) return fail(rc);
-    if (hipMemset(h->d_centroids + (size_t)nlist * dim, 0, (size_t)vs::kScanPadRows * dim * sizeof(float)) != hipSuccess) return fail(VS_ERR_DEVICE);
+    if (!h->general && h->metric == VS_METRIC_L2 && n_local > 0 && (rc = build_u8_copy(h, up, n_local, &host_bytes, &host_rterm)))
+        return fail(rc);
+    // centroids [nlist + 64][dim_p]: zero padded like the rows on a general index (the coarse scores are a brute-force scan
+    // of this table)
+    const size_t cld = (size_t)h->dim_p, cents_total = ((size_t)nlist + vs::kScanPadRows) * cld;
+    if ((rc = h->d_centroids.alloc(cents_total))) return fail(rc);
+    if (hipMemset(h->d_centroids, 0, cents_total * sizeof(float)) != hipSuccess) return fail(VS_ERR_DEVICE);
     if ((rc = h->d_cnorm.alloc((size_t)nlist + 64))) return fail(rc);
     if ((rc = h->d_offsets.alloc((size_t)nlist + 1))) return fail(rc);
     if ((rc = h->d_r2o.alloc((size_t)std::max<int64_t>(n_local, 1)))) return fail(rc);
     hipError_t e;
     if ((e = hipMemset(h->d_cnorm, 0, ((size_t)nlist + 64) * sizeof(float))) != hipSuccess ||
-        (e = hipMemcpy(h->d_centroids, centroids, (size_t)nlist * dim * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy2D(h->d_centroids, cld * sizeof(float), centroids, (size_t)dim * sizeof(float), (size_t)dim * sizeof(float), (size_t)nlist,
+                         hipMemcpyHostToDevice)) != hipSuccess ||
         (e = hipMemcpy(h->d_offsets, loc_off.data(), ((size_t)nlist + 1) * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess ||
         (e = hipMemcpy(h->d_r2o, loc_r2o.data(), (size_t)std::max<int64_t>(n_local, 1) * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = vs::launch_row_sqnorm(h->d_centroids, nlist, dim, h->d_cnorm, nullptr)) != hipSuccess ||
+        (e = vs::launch_row_sqnorm_ld(h->d_centroids, nlist, dim, (int64_t)cld, h->d_cnorm, nullptr)) != hipSuccess ||
         (e = hipDeviceSynchronize()) != hipSuccess) {
         set_error(std::string("ivf upload: ") + hipGetErrorString(e));
         return fail(VS_ERR_DEVICE);
+    }
+    if (h->general) {
+        // no chunk table, no tiled copy, no heads: launch groups of 32 batches on the caller's stream (ivf_group_nd_dev),
+        // their scratch and the host staging now rather than inside the first search
+        h->ivf_gb = vs::kIvfWideBatches;
+        h->ivf_lanes = 1;
+        h->ivf_nsb = 1;
+        for (int c = 0; c < nlist; ++c) h->max_list = std::max(h->max_list, loc_off[c + 1] - loc_off[c]);
+        if ((rc = alloc_scratch(h)) || (rc = ensure_ivf_nd(h)) || (rc = ensure_wide_streams(h)) || (rc = ensure_ivf_host(h))) return fail(rc);
+        *out = h;
+        return VS_OK;
     }
     {
         // (list, 1024-row chunk) work items of the list-major scan, resident lists only
@@ -2507,7 +2654,7 @@ int vs_ivf_load(const char* index_dir, int device, int rank, int world, vs_index
 }
 
 int vs_ivf_save(vs_index* h, const char* index_dir) {
-    if (refuse_general(h, "vs_ivf_save")) return VS_ERR_UNSUPPORTED;
+    if (refuse_general_bf(h, "vs_ivf_save")) return VS_ERR_UNSUPPORTED;
     if (!h || h->kind != 1 || !index_dir) {
         set_error("vs_ivf_save: bad arguments");
         return VS_ERR_INVALID;
@@ -2521,8 +2668,10 @@ int vs_ivf_save(vs_index* h, const char* index_dir) {
     const std::string dir(index_dir);
     std::vector<float> vecs((size_t)h->n_rows * h->dim), cents((size_t)h->nlist * h->dim);
     std::vector<int32_t> r2o((size_t)h->n_rows);
-    HIPCHK(hipMemcpy(vecs.data(), h->d_vecs, vecs.size() * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cents.data(), h->d_centroids, cents.size() * sizeof(float), hipMemcpyDeviceToHost));
+    // unpadded [n_rows][dim] arrays (a general index keeps rows of dim_p floats on the device)
+    const size_t row_b = (size_t)h->dim * sizeof(float), ld_b = (size_t)h->dim_p * sizeof(float);
+    HIPCHK(hipMemcpy2D(vecs.data(), row_b, h->d_vecs, ld_b, row_b, (size_t)h->n_rows, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(cents.data(), row_b, h->d_centroids, ld_b, row_b, (size_t)h->nlist, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(r2o.data(), h->d_r2o, r2o.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     std::vector<int32_t> sizes(h->nlist);
     int32_t mn = std::numeric_limits<int32_t>::max(), mx = 0;
@@ -2551,11 +2700,12 @@ int vs_ivf_save(vs_index* h, const char* index_dir) {
 
 int vs_ivf_search_dev(vs_index* h, const float* queries_dev, int B, int k, int nprobe, int32_t* ids_dev,
                       float* dists_dev, void* stream) {
-    if (refuse_general(h, "vs_ivf_search_dev")) return VS_ERR_UNSUPPORTED;
+    if (refuse_general_bf(h, "vs_ivf_search_dev")) return VS_ERR_UNSUPPORTED;
     if (!h || h->kind != 1 || !queries_dev || !ids_dev || !dists_dev || B < 1 || B > vs::kMaxBatch || k < 1 || nprobe < 1) {
         set_error("vs_ivf_search_dev: bad arguments");
         return VS_ERR_INVALID;
     }
+    if (k > 16 && refuse_general_ivf(h, "vs_ivf_search_dev with k > 16")) return VS_ERR_UNSUPPORTED;
     nprobe = std::min(nprobe, h->nlist);  // IVFIndex.cpp:647
     if (nprobe > kMaxNprobe) {
         set_error("nprobe > 256 not supported");
@@ -2571,12 +2721,13 @@ int vs_ivf_search_dev(vs_index* h, const float* queries_dev, int B, int k, int n
 
 int vs_ivf_search_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k, int nprobe, int32_t* ids_dev,
                             float* dists_dev, void* stream) {
-    if (refuse_general(h, "vs_ivf_search_dev_multi")) return VS_ERR_UNSUPPORTED;
+    if (refuse_general_bf(h, "vs_ivf_search_dev_multi")) return VS_ERR_UNSUPPORTED;
     if (!h || h->kind != 1 || !queries_dev || !ids_dev || !dists_dev || n_batches < 1 || B < 1 || B > vs::kMaxBatch || k < 1 ||
         nprobe < 1) {
         set_error("vs_ivf_search_dev_multi: bad arguments");
         return VS_ERR_INVALID;
     }
+    if (k > 16 && refuse_general_ivf(h, "vs_ivf_search_dev_multi with k > 16")) return VS_ERR_UNSUPPORTED;
     nprobe = std::min(nprobe, h->nlist);  // IVFIndex.cpp:647
     if (nprobe > kMaxNprobe) {
         set_error("nprobe > 256 not supported");
@@ -3016,7 +3167,7 @@ int vs_bf_search_dev_sharded(vs_index* h, vs_comm* c, const float* queries_dev, 
 
 int vs_ivf_search_dev_sharded(vs_index* h, vs_comm* c, const float* queries_dev, int n_batches, int B, int k, int nprobe,
                               int32_t* ids_dev, float* dists_dev, void* stream) {
-    if (refuse_general(h, "vs_ivf_search_dev_sharded")) return VS_ERR_UNSUPPORTED;
+    if (refuse_general_bf(h, "vs_ivf_search_dev_sharded") || refuse_general_ivf(h, "vs_ivf_search_dev_sharded")) return VS_ERR_UNSUPPORTED;
     if (!h || !c || h->kind != 1 || !queries_dev || !ids_dev || !dists_dev || n_batches < 1 || B < 1 || B > vs::kMaxBatch || k < 1 ||
         nprobe < 1) {
         set_error("vs_ivf_search_dev_sharded: bad arguments");
@@ -3072,7 +3223,8 @@ int vs_ivf_search_dev_vshards(vs_index* const* shards, int G, const float* queri
         return VS_ERR_INVALID;
     }
     for (int r = 0; r < G; ++r)
-        if (shards[r] && refuse_general(shards[r], "vs_ivf_search_dev_vshards")) return VS_ERR_UNSUPPORTED;
+        if (shards[r] && (refuse_general_bf(shards[r], "vs_ivf_search_dev_vshards") || refuse_general_ivf(shards[r], "vs_ivf_search_dev_vshards")))
+            return VS_ERR_UNSUPPORTED;
     for (int r = 0; r < G; ++r)
         if (!shards[r] || shards[r]->kind != 1 || shards[r]->world != G || shards[r]->rank != r || shards[r]->device != shards[0]->device ||
             shards[r]->nlist != shards[0]->nlist || !ivf_wide_ok(shards[r], k)) {
@@ -3507,7 +3659,7 @@ int ivf_search_host(vs_index* h, vs_comm* c, const float* queries_host, int64_t 
     h->stage_used = 0;
     HIPCHK(hipMemsetAsync(h->d_cand, 0, sizeof(unsigned long long), h->stream));
     const float inf = std::numeric_limits<float>::infinity();
-    const bool wide = ivf_wide_ok(h, k);
+    const bool wide = !h->general && ivf_wide_ok(h, k);
     HIPCHK(hipEventRecord(h->wide_fork, h->stream));  // (behind the memset above)
     for (int i = 0; i < 2; ++i) HIPCHK(hipStreamWaitEvent(h->wide_stream[i], h->wide_fork, 0));
     const int64_t unit_q = (int64_t)vs::kIvfWideBatches * h->batch;  // a super-batch of queries: chunks are cut at these
@@ -3520,8 +3672,8 @@ int ivf_search_host(vs_index* h, vs_comm* c, const float* queries_host, int64_t 
         const double t0 = now_ms();
         S.q0 = q0;
         S.n = n;
-        std::memcpy(S.pin_q, queries_host + q0 * vs::kDim, (size_t)n * vs::kDim * sizeof(float));
-        HIPCHK(hipMemcpyAsync(S.d_q, S.pin_q, (size_t)n * vs::kDim * sizeof(float), hipMemcpyHostToDevice, h->s_h2d));
+        std::memcpy(S.pin_q, queries_host + q0 * h->dim, (size_t)n * h->dim * sizeof(float));
+        HIPCHK(hipMemcpyAsync(S.d_q, S.pin_q, (size_t)n * h->dim * sizeof(float), hipMemcpyHostToDevice, h->s_h2d));
         HIPCHK(hipEventRecord(S.ev_h2d, h->s_h2d));
         tm.h2d_ms += now_ms() - t0;
         float* od = S.d_out;
@@ -3537,12 +3689,13 @@ int ivf_search_host(vs_index* h, vs_comm* c, const float* queries_host, int64_t 
             used[lane] = true;
             int r2 = VS_OK;
             auto run = [&](size_t o, int nb, int B) -> int {
-                const float* q = S.d_q + o * vs::kDim;
+                const float* q = S.d_q + o * h->dim;
                 if (c) return vs_ivf_search_dev_sharded(h, c, q, nb, B, k, nprobe, oi + o * k, od + o * k, cs);
                 if (wide) return ivf_group_wide_dev(h, lane, q, nb, B, k, nprobe, od + o * k, oi + o * k, cs);
+                if (h->general) return ivf_group_nd_dev(h, q, nb, B, k, nprobe, od + o * k, oi + o * k, cs);
                 int r3 = VS_OK;
                 for (int b = 0; b < nb && !r3; ++b)
-                    r3 = ivf_fallback_batch_dev(h, q + (size_t)b * B * vs::kDim, B, k, nprobe, od + (o + (size_t)b * B) * k,
+                    r3 = ivf_fallback_batch_dev(h, q + (size_t)b * B * h->dim, B, k, nprobe, od + (o + (size_t)b * B) * k,
                                                 oi + (o + (size_t)b * B) * k, cs);
                 return r3;
             };
@@ -3720,11 +3873,12 @@ int vs_bf_search_vshards(vs_index* const* shards, int G, const float* queries_ho
 
 int vs_ivf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int nprobe, int32_t* ids, float* dists,
                   int64_t* total_candidates, vs_timing* timing) {
-    if (refuse_general(h, "vs_ivf_search")) return VS_ERR_UNSUPPORTED;
+    if (refuse_general_bf(h, "vs_ivf_search")) return VS_ERR_UNSUPPORTED;
     if (!h || h->kind != 1 || !queries_host || !ids || !dists || nq < 0 || k < 1 || nprobe < 1) {
         set_error("vs_ivf_search: bad arguments");
         return VS_ERR_INVALID;
     }
+    if (k > 16 && refuse_general_ivf(h, "vs_ivf_search with k > 16")) return VS_ERR_UNSUPPORTED;
     nprobe = std::min(nprobe, h->nlist);
     if (nprobe > kMaxNprobe) {
         set_error("nprobe > 256 not supported");
@@ -3739,7 +3893,7 @@ int vs_ivf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int
 
 int vs_ivf_search_sharded(vs_index* h, vs_comm* c, const float* queries_host, int64_t nq, int k, int nprobe, int32_t* ids,
                           float* dists, int64_t* total_candidates, vs_timing* timing) {
-    if (refuse_general(h, "vs_ivf_search_sharded")) return VS_ERR_UNSUPPORTED;
+    if (refuse_general_bf(h, "vs_ivf_search_sharded") || refuse_general_ivf(h, "vs_ivf_search_sharded")) return VS_ERR_UNSUPPORTED;
     if (!h || !c || h->kind != 1 || !queries_host || !ids || !dists || nq < 0 || k < 1 || nprobe < 1) {
         set_error("vs_ivf_search_sharded: bad arguments");
         return VS_ERR_INVALID;

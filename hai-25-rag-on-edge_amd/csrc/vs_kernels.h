@@ -490,4 +490,38 @@ struct IvfScanParams {
 };
 hipError_t launch_ivf_scan(const IvfScanParams& p, hipStream_t s);
 
+// ---- list-major IVF scan of a general index (vs_ivf_nd.hip): a launch group of group_q <= kIvfNdGroupQ
+// queries (batches back to back, [group_q][dim]) whose probes are known.  launch_ivf_nd_plan prepares the queries
+// (zero-padded rows + squared norms in nd_prep_kernel's order), inverts probes[group_q][nprobe] into per-list runs of
+// slots (query << 8 | probe rank) and cuts the runs of the non-empty lists into items of up to 16 slots;
+// launch_ivf_nd_scan scores every item's list against its slots' queries (scan_nd_kernel's accumulation chain: a distance
+// is the number the brute-force general scan returns for that row and query) and writes the item's sorted top-kcap by
+// (distance, row) per slot to part[(query * nprobe + rank) * kcap] -- the layout ivf_fallback_batch_dev ranks.
+constexpr int kIvfNdGroupQ = 1024;     // 32 batches of 32 queries
+constexpr int kIvfNdSlotBlock = 16;    // slots per item: one MFMA column block
+constexpr long long ivf_nd_items_cap(int nlist, int nprobe) {  // every probed list ends in one ragged item at most
+    return (long long)kIvfNdGroupQ * nprobe / kIvfNdSlotBlock + ((long long)kIvfNdGroupQ * nprobe < nlist ? (long long)kIvfNdGroupQ * nprobe : nlist);
+}
+struct IvfNdParams {
+    const float* vecs;        // [n_rows + kScanPadRows][dim_p] cluster-reordered, zero padded
+    const float* vnorm;       // [n_rows + 64]
+    const int32_t* offsets;   // [nlist + 1]
+    int nlist, dim, dim_p;
+    const float* q;           // [group_q][dim] raw queries
+    int group_q, nprobe, k, kcap;
+    const int32_t* probes;    // [group_q][nprobe] (-1: none)
+    float* qrows;             // scratch [kIvfNdGroupQ][dim_p]
+    float* qnorm;             // scratch [kIvfNdGroupQ]
+    int32_t* list_cnt;        // scratch [2][nlist]: pairs per list, fill cursors (cleared by the plan's first launch)
+    int32_t* list_start;      // scratch [nlist + 1] first slot of every list's run
+    int32_t* slots;           // scratch [group_q * nprobe]
+    int32_t* items;           // scratch [ivf_nd_items_cap][2] (list, first slot)
+    int32_t* n_items;         // scratch [1]
+    float* part_d;            // [group_q][nprobe][kcap] (pairs without an item: (+inf, -1))
+    int32_t* part_i;          // reordered row positions
+    unsigned long long* cand_count;  // += rows of every probed list, per (query, probe) pair
+};
+hipError_t launch_ivf_nd_plan(const IvfNdParams& p, hipStream_t s);
+hipError_t launch_ivf_nd_scan(const IvfNdParams& p, int grid, hipStream_t s);
+
 }  // namespace vs

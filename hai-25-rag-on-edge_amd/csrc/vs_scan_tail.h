@@ -1,6 +1,7 @@
 // vs_scan_tail.h -- what scan_nd_kernel (vs_scan_nd.hip) and scan_nd_i8_kernel (vs_scan_nd_i8.hip) do with their
 // distances in kModeTopK, whatever the rows are made of: the top-k step on a group of four distances, the in-kernel
-// threshold exchange and the workgroup merge into the partial lists of merge_compact_kernel.  Device functions only;
+// threshold exchange and the workgroup merge into the partial lists of merge_compact_kernel; ivf_scan_nd_kernel
+// (vs_ivf_nd.hip) takes the top-k step and the merge, with its own output lists.  Device functions only;
 // the kernel declares one NdTailLds and hands it to them.  tid, lane = tid & 63, wave = tid >> 6 (uniform),
 // r = lane & 15 and g = lane >> 4 are the kernels' own: lane (r, g) holds queries h * 16 + r, h < NQH.
 #pragma once
@@ -93,13 +94,15 @@ __device__ __forceinline__ void xchg_bound(NdTailLds& L, float* slots, int k1, i
     }
 }
 
-// Workgroup merge: the entries of the lane lists that can still matter (d < tq) are compacted into LDS and ranked; the
-// sorted per-workgroup lists go to merge_compact_kernel.  With a bound in force a query keeps a handful of entries per
-// workgroup (fast path, one wave per query); lists full of unfiltered entries (small shards) go through in passes of
-// kNdPassQ queries.  Every thread of the workgroup calls it; it ends with a barrier, so the LDS is free again.
-template <int NQH, int KCAP>
-__device__ __forceinline__ void wg_merge_lists(NdTailLds& L, const ScanParams& p, int batch, int tid, int wave,
-                                               const float (&ld)[NQH][KCAP], const int (&li)[NQH][KCAP], const float (&tq)[NQH]) {
+// Workgroup merge: the entries of the lane lists that can still matter (d < tq) are compacted into LDS and ranked into
+// one sorted list of KCAP entries per query (the first min(k1, KCAP) by (dist, id), then (+inf, -1)).  With a bound in
+// force a query keeps a handful of entries per workgroup (fast path, one wave per query); lists full of unfiltered
+// entries (small shards, list scans without a bound) go through in passes of kNdPassQ queries.  where(qq, od, oi) names
+// query qq's output list, or returns false for a query without one; it is called by whole waves with qq uniform.  Every
+// thread of the workgroup calls the merge; it ends with a barrier, so the LDS is free again.
+template <int NQH, int KCAP, class Where>
+__device__ __forceinline__ void wg_merge_lists_to(NdTailLds& L, int k1, int tid, int wave, const float (&ld)[NQH][KCAP],
+                                                  const int (&li)[NQH][KCAP], const float (&tq)[NQH], Where where) {
     constexpr int NQ = NQH * 16;
     constexpr int CAP = 32 * KCAP;  // 32 lane lists per query
     static_assert(kNdPassQ * CAP <= kMaxBatch * kNdMergeSmall, "the fallback pass fits the merge buffer");
@@ -107,10 +110,10 @@ __device__ __forceinline__ void wg_merge_lists(NdTailLds& L, const ScanParams& p
     auto rank = [&](int qq, const float* cand_d, const int* cand_i, auto epl_tag) {
         constexpr int EPL = decltype(epl_tag)::value;
         const int M = min(L.cnt[qq], EPL * 64);
-        // partial lists are query-major: [batch][query][workgroup][KCAP] (one merge launch ranks all batches)
-        float* od = p.part_d + (((int64_t)batch * kMaxBatch + qq) * kSlotStride + blockIdx.x) * KCAP;
-        int32_t* oi = p.part_i + (((int64_t)batch * kMaxBatch + qq) * kSlotStride + blockIdx.x) * KCAP;
-        const int rounds = min(min(p.k1, KCAP), M);
+        float* od;
+        int32_t* oi;
+        if (!where(qq, od, oi)) return;
+        const int rounds = min(min(k1, KCAP), M);
         wave_select_rounds<EPL>(cand_d, cand_i, M, rounds, lane, [&](int round, float bd, int bi) {
             if (lane == 0) {
                 od[round] = bd;
@@ -156,6 +159,18 @@ __device__ __forceinline__ void wg_merge_lists(NdTailLds& L, const ScanParams& p
         }
     }
     __syncthreads();  // LDS is reused by the next batch
+}
+
+// The merge of the per-batch brute-force scans: the sorted per-workgroup lists go to merge_compact_kernel.
+template <int NQH, int KCAP>
+__device__ __forceinline__ void wg_merge_lists(NdTailLds& L, const ScanParams& p, int batch, int tid, int wave,
+                                               const float (&ld)[NQH][KCAP], const int (&li)[NQH][KCAP], const float (&tq)[NQH]) {
+    // partial lists are query-major: [batch][query][workgroup][KCAP] (one merge launch ranks all batches)
+    wg_merge_lists_to<NQH, KCAP>(L, p.k1, tid, wave, ld, li, tq, [&](int qq, float*& od, int32_t*& oi) {
+        od = p.part_d + (((int64_t)batch * kMaxBatch + qq) * kSlotStride + blockIdx.x) * KCAP;
+        oi = p.part_i + (((int64_t)batch * kMaxBatch + qq) * kSlotStride + blockIdx.x) * KCAP;
+        return true;
+    });
 }
 
 }  // namespace vs

@@ -128,7 +128,8 @@ VS_API int vs_bf_create(const float* base_host, int64_t n_rows, int dim, int met
  * VS_ERR_UNSUPPORTED (an index with a byte copy of the rows at other dimensions comes from
  * vs_bf_create_nd_u8 below, not from this creator).  The
  * sharded calls (vs_bf_search_dev_sharded, vs_bf_search_sharded, vs_bf_search_vshards) and
- * every vs_ivf_* call return VS_ERR_UNSUPPORTED on a general index; IVF and q8 stay at 128. */
+ * every vs_ivf_* call return VS_ERR_UNSUPPORTED on a general index made by this creator (an IVF
+ * index at other dimensions comes from vs_ivf_create / vs_ivf_load); q8 stays at 128. */
 VS_API int vs_bf_create_nd(const float* base_host, int64_t n_rows, int dim, int metric,
                            int device, int64_t id_offset, vs_index** out);
 
@@ -286,7 +287,33 @@ VS_API int vs_q8_search(vs_q8* h, const float* queries_host, int64_t nq, int k, 
  * (cluster-sharded search); 0/1 = everything. */
 VS_API int vs_ivf_load(const char* index_dir, int device, int rank, int world, vs_index** out);
 
-/* Same, from arrays in host memory (layout of create_ivf_model_reordered.py:141-169). */
+/* Same, from arrays in host memory (layout of create_ivf_model_reordered.py:141-169).
+ *
+ * Both creators take the dimension the arrays / ivf_config.json state (IVFIndex.cpp:181-204):
+ * 1 <= dim <= 2048.  dim == 128 builds the specialised index described elsewhere in this header.
+ * Any other dim builds a GENERAL IVF INDEX: the reordered rows and the centroids as fp32 rows
+ * padded to a multiple of 16 floats with their norms, offsets and reorder_to_original -- no byte
+ * copy, no sharding.  VSEARCH_IVF_ND_FORCE=1 (read at creation) builds the general index at
+ * dim 128 as well (unsharded only): the comparison toggle, as VSEARCH_ND_FORCE is for brute force.
+ *
+ * Checks, in this order (the first four need no device): null pointers, n_rows / nlist <= 0 or a
+ * bad (rank, world) -> VS_ERR_INVALID; dim < 1 -> VS_ERR_INVALID; dim > 2048 ->
+ * VS_ERR_UNSUPPORTED; dim != 128 with world > 1 -> VS_ERR_UNSUPPORTED; offsets that do not cover
+ * the rows or are not monotone -> VS_ERR_INVALID; then the device.
+ *
+ * A general IVF index is searched list-major on its fp32 rows under squared L2.
+ * A centroid score is the number the brute-force general scan returns for the centroid as a row;
+ * equal scores go to the lower list id.  A distance is bit-identical to what vs_bf_create_nd's
+ * index returns for that row and query; equal distances rank by position in vectors_reordered.
+ *   accepted: vs_ivf_search, vs_ivf_search_dev, vs_ivf_search_dev_multi for 1 <= k <= 16 (same
+ *     signatures and output layouts; queries are [nq][dim], unpadded; every launch group of up to
+ *     32 batches stays on the caller's stream), vs_ivf_save, vs_index_rows, vs_index_dim,
+ *     vs_index_nlist, vs_prof_*, vs_set_batch, vs_destroy, vs_set_precision 0 or 1 (both mean the
+ *     fp32 rows), vs_ivf_set_metric(VS_METRIC_L2);
+ *   VS_ERR_UNSUPPORTED, with the dimension in the message: 17 <= k <= 128, vs_set_precision 2,
+ *     vs_ivf_set_metric(VS_METRIC_IP), vs_ivf_widek_stats, every sharded and virtual-shard call.
+ * vs_ivf_build and vs_ivf_build_index stay 128-d only: arrays for other dimensions come from the
+ * caller or from a directory. */
 VS_API int vs_ivf_create(const float* vectors_reordered, int64_t n_rows, int dim,
                          const float* centroids, int nlist, const int32_t* cluster_offsets,
                          const int32_t* reorder_to_original, int device, int rank, int world,
@@ -344,7 +371,8 @@ VS_API int vs_ivf_layout(const int32_t* assign, int64_t n_rows, int nlist, int32
 VS_API int vs_ivf_build_index(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol,
                               uint64_t seed, int device, vs_index** out, int* iters_done);
 
-/* Writes the index held by h in the reference's directory format. */
+/* Writes the index held by h in the reference's directory format: unpadded [n_rows][dim] and [nlist][dim] arrays at
+ * any dimension; vs_ivf_load of that directory gives the same index. */
 VS_API int vs_ivf_save(vs_index* h, const char* index_dir);
 
 /* IVFIndex::searchBatch (IVFIndex.h:45-48, IVFIndex.cpp:640-859): ids/dists
@@ -352,7 +380,8 @@ VS_API int vs_ivf_save(vs_index* h, const char* index_dir);
  * total number of candidates scanned through *total_candidates (the
  * function's return value in the reference) and the SearchTiming fields.
  * k: 1..128.  17 <= k <= 128 needs the list-major pipeline (nlist <= 4096, rows resident): VS_ERR_UNSUPPORTED
- * otherwise, and for k > 128.  Slots past the candidates of the probed lists are (-1, +inf) for every k. */
+ * otherwise, and for k > 128.  Slots past the candidates of the probed lists are (-1, +inf) for every k.
+ * A general IVF index (dim != 128, see vs_ivf_create) takes 1 <= k <= 16. */
 VS_API int vs_ivf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int nprobe,
                          int32_t* ids, float* dists, int64_t* total_candidates, vs_timing* timing);
 

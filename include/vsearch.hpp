@@ -207,6 +207,8 @@ public:
 
     // backendPath is kept for signature compatibility (the reference passes libQnnHtp.so); the
     // backend here is always the HIP library this header links against.
+    // The directory states the dimension (1 <= dim <= 2048, getDim()): 128-d indexes take the specialised pipeline,
+    // any other a general IVF index (fp32 rows, squared L2, k <= 16, one GPU; vsearch.h at vs_ivf_create).
     explicit IVFIndex(const std::string& indexDir, const std::string& backendPath = "libvsearch_hip.so",
                       int device = 0, int rank = 0, int world = 1) {
         (void)backendPath;

@@ -1,0 +1,296 @@
+"""IVF search at any vector length 1 <= dim <= 2048 (a general IVF index: vs_ivf_create / vs_ivf_load with dim != 128,
+ivf_scan_nd_kernel) against the CPU oracle.
+
+Data: integers in [0, hi) with 2 dim (hi - 1)^2 < 2^24 (`_hi` of tests/test_gpu_nd.py), rows assigned to the nearest of
+nlist sampled rows in int64, and centroids = rint(mean): integer valued, so every coarse score and every distance is exact
+in fp32 in any summation order.  The assertions are therefore equalities for every query: oracle.ivf_search breaks ties by
+(distance, reordered position) and equal coarse scores by the lower list id, and so must the pipeline.  The lists are cut
+on purpose: one empty, one of 1 row, lists of 63, 64 and 65 rows, one of 1200 rows (every wave of the scan takes more than
+one 64-row block), and the last list ends at row N (its last block reads the spare rows)."""
+import ctypes as C
+import functools
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import oracle
+
+pytestmark = pytest.mark.gpu
+
+DIMS = [1, 3, 20, 100, 130, 384, 960, 2048]
+N, NLIST, NQ = 6000, 24, 96  # (tests that want the issue's 70 queries -- batches of 32, 32 and 6 -- take the first 70)
+# list -> rows; the others share what is left
+SHAPED = {0: 1200, 3: 0, 5: 1, 7: 63, 8: 64, 9: 65}
+EMPTY = 3
+
+
+def _hi(dim):
+    hi = min(int(math.isqrt((2 ** 23 - 1) // dim)) + 1, 256)
+    assert 2 * dim * (hi - 1) ** 2 < 2 ** 24
+    return hi
+
+
+def _nearest(rows, cents):
+    """argmin of the squared L2 distance in int64 (exact), ties to the lower centre"""
+    r, c = rows.astype(np.int64), cents.astype(np.int64)
+    d = (r * r).sum(1)[:, None] - 2 * (r @ c.T) + (c * c).sum(1)[None, :]
+    return d.argmin(1)
+
+
+@functools.lru_cache(maxsize=2)
+def _int_index(dim):
+    """(vectors_reordered, centroids, offsets, reorder_to_original, queries), read-only and shared between tests"""
+    rng = np.random.default_rng(5000 + dim)
+    hi = _hi(dim)
+    base = rng.integers(0, hi, size=(N, dim)).astype(np.float32)
+    src = rng.integers(100, N - 100, size=40)
+    base[:20] = base[src[:20]]  # 40 duplicated rows, at both ends of the base
+    base[N - 20:] = base[src[20:]]
+    q = rng.integers(0, hi, size=(NQ, dim)).astype(np.float32)
+    q[:4] = base[src[:4]]  # queries that ARE duplicated rows
+    assign = _nearest(base, base[rng.choice(N, NLIST, replace=False)])
+    order = np.argsort(assign, kind="stable")  # clusters stay together; the cuts below shape the lists
+    rest = N - sum(SHAPED.values())
+    free = [c for c in range(NLIST) if c not in SHAPED]
+    sizes = np.zeros(NLIST, dtype=np.int64)
+    for c, n in SHAPED.items():
+        sizes[c] = n
+    for j, c in enumerate(free):
+        sizes[c] = rest // len(free) + (1 if j < rest % len(free) else 0)
+    off = np.zeros(NLIST + 1, dtype=np.int32)
+    off[1:] = np.cumsum(sizes)
+    assert off[-1] == N and sizes[NLIST - 1] > 0
+    vr = np.ascontiguousarray(base[order])
+    r2o = order.astype(np.int32)
+    cents = np.zeros((NLIST, dim), dtype=np.float32)
+    for c in range(NLIST):
+        if sizes[c]:
+            cents[c] = np.rint(vr[off[c]:off[c + 1]].astype(np.float64).mean(0))
+    # the empty list's centroid: a point no other centroid sits on, and a query on it -- its nearest list is the empty one
+    while True:
+        v = rng.integers(0, hi, size=dim).astype(np.float32)
+        if not any(np.array_equal(v, cents[c]) for c in range(NLIST) if c != EMPTY):
+            break
+    cents[EMPTY] = v
+    q[4] = v
+    for a in (vr, cents, off, r2o, q):
+        a.setflags(write=False)
+    return vr, cents, off, r2o, q
+
+
+def _open(pkg, vr, cents, off, r2o, **kw):
+    return pkg.IVFIndex(vectors_reordered=vr, centroids=cents, cluster_offsets=off, reorder_to_original=r2o, **kw)
+
+
+def _check(ivf, data, q, k, nprobe, tag=""):
+    vr, cents, off, r2o, _ = data
+    oi, od, ototal = oracle.ivf_search(vr, off, r2o, cents, q, k, nprobe)
+    ids, d, total = ivf.searchBatch(q, len(q), k, nprobe)
+    tag = f"(dim={vr.shape[1]}, nq={len(q)}, k={k}, nprobe={nprobe}{tag})"
+    assert np.array_equal(d, od), "dists differ " + tag
+    assert np.array_equal(ids, oi), "ids differ " + tag
+    assert total == ototal, "total_candidates differs " + tag
+    return ids, d
+
+
+@pytest.mark.parametrize("dim", DIMS)
+def test_every_dimension(gpu_pkg, dim):
+    data = _int_index(dim)
+    vr, cents, off, r2o, q = data
+    q = q[:70]
+    with _open(gpu_pkg, vr, cents, off, r2o) as ivf:
+        assert ivf.getDim() == dim and ivf.getNumVectors() == N and ivf.getNumClusters() == NLIST
+        for k, nprobe in ((1, 1), (5, 4), (16, NLIST)):
+            ids, d = _check(ivf, data, q, k, nprobe)
+            if nprobe == 1:  # query 4 sits on the empty list's centroid: fewer candidates than k
+                assert ids[4, 0] == -1 and d[4, 0] == np.inf
+            if nprobe == NLIST:
+                assert ids.min() >= 0
+        # lists shorter than k: queries that probe only the 1-row list / only the empty one
+        qq = np.stack([vr[off[5]], cents[EMPTY]])
+        oi, od, _ = oracle.ivf_search(vr, off, r2o, cents, qq, 5, 1)
+        ids, d, _ = ivf.searchBatch(qq, 2, 5, 1)
+        assert np.array_equal(ids, oi) and np.array_equal(d, od)
+        assert np.all(ids[1] == -1) and np.all(d[1] == np.inf)
+
+
+@pytest.mark.parametrize("nq", [1, 15, 16, 17, 33])
+def test_query_block_edges(gpu_pkg, nq):
+    """nprobe = nlist: every list's run holds nq slots -- one ragged item, one full item, a full and a ragged one, ..."""
+    data = _int_index(100)
+    vr, cents, off, r2o, q = data
+    with _open(gpu_pkg, vr, cents, off, r2o) as ivf:
+        _check(ivf, data, q[:nq], 5, NLIST)
+
+
+@pytest.mark.parametrize("batch", [1, 7, 32])
+def test_batch_sizes(gpu_pkg, batch):
+    data = _int_index(100)
+    vr, cents, off, r2o, q = data
+    with _open(gpu_pkg, vr, cents, off, r2o) as ivf:
+        ivf.set_batch(batch)
+        _check(ivf, data, q[:70], 5, NLIST, tag=f", batch={batch}")
+        _check(ivf, data, q[:70], 5, 4, tag=f", batch={batch}")
+
+
+def test_device_calls(gpu_pkg):
+    """search_dev (B = 5) and search_dev_multi (3 x 32) on a non-default torch stream give the host call's arrays."""
+    import torch
+    dev = torch.device("cuda:0")
+    data = _int_index(100)
+    vr, cents, off, r2o, q = data
+    dim, k, nprobe = 100, 5, 4
+    with _open(gpu_pkg, vr, cents, off, r2o) as ivf:
+        want_i, want_d, _ = ivf.searchBatch(q, NQ, k, nprobe)
+        oi, od, _ = oracle.ivf_search(vr, off, r2o, cents, q, k, nprobe)
+        assert np.array_equal(want_i, oi) and np.array_equal(want_d, od)
+        st = torch.cuda.Stream()
+        with torch.cuda.stream(st):
+            qd = torch.from_numpy(np.array(q)).to(dev)
+            gi = torch.full((NQ, k), -7, dtype=torch.int32, device=dev)
+            gd = torch.zeros((NQ, k), dtype=torch.float32, device=dev)
+            ivf.search_dev_multi(qd.data_ptr(), 3, 32, k, nprobe, gi.data_ptr(), gd.data_ptr(), st.cuda_stream)
+            si = torch.full((5, k), -7, dtype=torch.int32, device=dev)
+            sd = torch.zeros((5, k), dtype=torch.float32, device=dev)
+            ivf.search_dev(qd.data_ptr() + 40 * dim * 4, 5, k, nprobe, si.data_ptr(), sd.data_ptr(), st.cuda_stream)
+        st.synchronize()
+        assert np.array_equal(gi.cpu().numpy(), want_i) and np.array_equal(gd.cpu().numpy(), want_d)
+        assert np.array_equal(si.cpu().numpy(), want_i[40:45]) and np.array_equal(sd.cpu().numpy(), want_d[40:45])
+
+
+@pytest.mark.parametrize("dim", [96, 768])
+def test_distances_are_the_brute_force_scans_bits(gpu_pkg, dim):
+    """N(0, 1) rows (no ties), nprobe = nlist: the accumulation chain of a distance is scan_nd_kernel's, so distances are
+    bit-equal to the brute-force general index (vs_bf_create_nd, fp32 rows) on the same rows, and ids are equal."""
+    rng = np.random.default_rng(6000 + dim)
+    n, nlist, k = 4000, 16, 5
+    base = rng.normal(0, 1, size=(n, dim)).astype(np.float32)
+    q = rng.normal(0, 1, size=(70, dim)).astype(np.float32)
+    cen0 = base[rng.choice(n, nlist, replace=False)].astype(np.float64)
+    b64 = base.astype(np.float64)
+    assign = ((b64 * b64).sum(1)[:, None] - 2 * b64 @ cen0.T + (cen0 * cen0).sum(1)[None, :]).argmin(1)
+    vr, off, r2o = gpu_pkg.ivf_layout_from_assignment(base, assign, nlist)
+    cents = np.stack([vr[off[c]:off[c + 1]].mean(0) if off[c + 1] > off[c] else cen0[c] for c in range(nlist)]).astype(np.float32)
+    with gpu_pkg.BruteForceIndex(base) as bf:
+        bf.set_precision(1)
+        bi, bd = bf.search(q, k)
+    with _open(gpu_pkg, vr, cents, off, r2o) as ivf:
+        ids, d, total = ivf.searchBatch(q, len(q), k, nlist)
+        ids2, d2, _ = ivf.searchBatch(q, len(q), k, nlist)
+    assert total == len(q) * n
+    assert np.array_equal(d.view(np.int32), bd.view(np.int32))
+    assert np.array_equal(ids, bi)
+    assert np.array_equal(d2.view(np.int32), d.view(np.int32)) and np.array_equal(ids2, ids)
+
+
+_TOGGLE_SCRIPT = r"""
+import sys, numpy as np
+sys.path.insert(0, sys.argv[1])
+import __graft_entry__ as ge
+pkg = ge.load_package()
+base = pkg.synth_sift(20000, seed=31)
+q = pkg.synth_sift(70, seed=32)
+cents = base[:: len(base) // 64][:64].copy()
+b, c = base.astype(np.int64), cents.astype(np.int64)
+assign = ((b * b).sum(1)[:, None] - 2 * (b @ c.T) + (c * c).sum(1)[None, :]).argmin(1)
+vr, off, r2o = pkg.ivf_layout_from_assignment(base, assign, 64)
+with pkg.IVFIndex(vectors_reordered=vr, centroids=cents, cluster_offsets=off, reorder_to_original=r2o) as ivf:
+    general = pkg.lib().vs_set_precision(ivf._h, 2) == -5 and b"dim = 128" in pkg.lib().vs_last_error()
+    ivf.set_precision(1)
+    i8, d8, t8 = ivf.searchBatch(q, len(q), 5, 8)
+    i64, d64, t64 = ivf.searchBatch(q, len(q), 10, 64)
+np.savez(sys.argv[2], i8=i8, d8=d8, t8=t8, i64=i64, d64=d64, t64=t64, general=general)
+print("TOGGLE_OK")
+"""
+
+
+def test_toggle_equals_the_128d_pipeline(gpu_pkg, tmp_path):
+    """VSEARCH_IVF_ND_FORCE=1 (read when an index is created) builds the general index at dim 128: on synth_sift rows with
+    sampled-row centroids (everything exact) it returns the ids and distances of the specialised pipeline on fp32 rows."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = {}
+    for tag, force in (("default", None), ("forced", "1")):
+        e = dict(os.environ)
+        e.pop("VSEARCH_IVF_ND_FORCE", None)
+        if force:
+            e["VSEARCH_IVF_ND_FORCE"] = force
+        path = str(tmp_path / f"{tag}.npz")
+        r = subprocess.run([sys.executable, "-c", _TOGGLE_SCRIPT, root, path], env=e, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0 and "TOGGLE_OK" in r.stdout, (tag, r.stdout[-400:], r.stderr[-1200:])
+        out[tag] = np.load(path)
+    assert not out["default"]["general"] and out["forced"]["general"]
+    for key in ("i8", "d8", "t8", "i64", "d64", "t64"):
+        assert np.array_equal(out["default"][key], out["forced"][key]), key
+
+
+def test_save_load_round_trip_at_dim_300(gpu_pkg, tmp_path):
+    rng = np.random.default_rng(7300)
+    n, dim, nlist = 3000, 300, 12
+    hi = _hi(dim)
+    base = rng.integers(0, hi, size=(n, dim)).astype(np.float32)
+    q = rng.integers(0, hi, size=(40, dim)).astype(np.float32)
+    assign = _nearest(base, base[rng.choice(n, nlist, replace=False)])
+    vr, off, r2o = gpu_pkg.ivf_layout_from_assignment(base, assign, nlist)
+    cents = np.stack([np.rint(vr[off[c]:off[c + 1]].astype(np.float64).mean(0)) for c in range(nlist)]).astype(np.float32)
+    oi, od, ot = oracle.ivf_search(vr, off, r2o, cents, q, 5, 3)
+    d = tmp_path / "idx"
+    with _open(gpu_pkg, vr, cents, off, r2o) as ivf:
+        ivf.save(str(d))
+        a = ivf.searchBatch(q, len(q), 5, 3)
+    assert np.load(d / "vectors_reordered.npy").shape == (n, dim)
+    assert np.load(d / "centroids.npy").shape == (nlist, dim)
+    assert np.array_equal(np.load(d / "vectors_reordered.npy"), vr) and np.array_equal(np.load(d / "centroids.npy"), cents)
+    assert np.array_equal(np.load(d / "cluster_offsets.npy"), off) and np.array_equal(np.load(d / "reorder_to_original.npy"), r2o)
+    with gpu_pkg.IVFIndex(str(d)) as ivf2:
+        assert ivf2.getDim() == dim and ivf2.getNumVectors() == n and ivf2.getNumClusters() == nlist
+        b = ivf2.searchBatch(q, len(q), 5, 3)
+    for x, y, z in zip(a, b, (oi, od, ot)):
+        assert np.array_equal(x, y) and np.array_equal(x, z)
+
+
+def test_refusals(gpu_pkg):
+    import torch
+    L = gpu_pkg.lib()
+    data = _int_index(100)
+    vr, cents, off, r2o, q = data
+    q = np.array(q[:8])
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+
+    def refused(call, *a):
+        with pytest.raises(gpu_pkg.VSearchError) as e:
+            call(*a)
+        assert e.value.status == -5 and "100" in str(e.value), str(e.value)
+
+    with _open(gpu_pkg, vr, cents, off, r2o) as ivf:
+        refused(ivf.searchBatch, q, len(q), 17, 4)
+        refused(ivf.set_precision, 2)
+        refused(ivf.set_metric, gpu_pkg.METRIC_IP)
+        refused(ivf.widek_stats)
+        ivf.set_precision(0)
+        ivf.set_precision(1)
+        ivf.set_metric(gpu_pkg.METRIC_L2)
+        dev = torch.device("cuda:0")
+        qd = torch.from_numpy(q).to(dev)
+        gi = torch.zeros((8, 17), dtype=torch.int32, device=dev)
+        gd = torch.zeros((8, 17), dtype=torch.float32, device=dev)
+        s = torch.cuda.current_stream().cuda_stream
+        refused(ivf.search_dev, qd.data_ptr(), 8, 17, 4, gi.data_ptr(), gd.data_ptr(), s)
+        refused(ivf.search_dev_multi, qd.data_ptr(), 1, 8, 17, 4, gi.data_ptr(), gd.data_ptr(), s)
+        refused(gpu_pkg.IVFIndex.search_dev_vshards, [ivf, ivf], qd.data_ptr(), 1, 8, 5, 4, gi.data_ptr(), gd.data_ptr(), s)
+        ids = np.zeros((8, 5), dtype=np.int32)
+        d = np.zeros((8, 5), dtype=np.float32)
+        assert L.vs_ivf_search(ivf._h, p(q), 8, 0, 4, p(ids), p(d), None, None) == -1  # k = 0
+        _check(ivf, data, q, 5, 4)  # still usable after the refusals
+    h = C.c_void_p(None)
+    vrc, cc = np.ascontiguousarray(vr), np.ascontiguousarray(cents)
+    assert L.vs_ivf_create(p(vrc), N, 100, p(cc), NLIST, p(np.ascontiguousarray(off)), None, 0, 0, 2, C.byref(h)) == -5  # world = 2
+    assert b"100" in L.vs_last_error()
+    # a brute-force general index keeps refusing the IVF calls
+    with gpu_pkg.BruteForceIndex(vrc[:500]) as bf:
+        ids = np.zeros((8, 5), dtype=np.int32)
+        d = np.zeros((8, 5), dtype=np.float32)
+        assert L.vs_ivf_search(bf._h, p(q), 8, 5, 4, p(ids), p(d), None, None) == -5
