@@ -92,12 +92,14 @@ hipError_t launch_pick_probes(const float* scores, int64_t ld, int B, int nlist,
 }
 
 // ------------------------------------------------------------------------------------------------
-// IVF coarse stage + probe selection in one launch (IVFIndex.cpp:654-666 centroid scores, :697-723
-// top-nprobe): one 256-thread workgroup per query.  Distances to all centroids with the same
-// 8-lanes-per-row dot product as the list scan (centroids are L2 resident), then selection without
-// sorting rounds: the nprobe-th smallest of the 256 per-thread minima bounds the answer, the few
-// scores under that bound are compacted and ranked by counting (every candidate counts how many
-// others precede it in (dist, id) order and writes itself to that slot).  Deterministic.
+// IVF coarse stage and probe selection (IVFIndex.cpp:654-666 centroid scores, :697-723 top-nprobe), two launches:
+// ivf_coarse_mfma_kernel scores a launch group's queries against all centroids, ivf_pick_kernel selects per query.
+// Arithmetic contract of a score, pinned bit for bit by the tests against the oracle's "chain" order on non-integer
+// centroids: q.c as one fmaf chain over the elements 16 c + 4 g + i (c = 0..7 ascending, i = 0..3, g = 0..3 -- g = lane >> 4
+// is the MFMA's k index, a v_mfma_f32_16x16x4_f32 adds its four products in k order, one rounding each), the norms in
+// the reference's 8-lane order, then fmaf(-2, q.c, ||q||^2 + ||c||^2).  The list-major scans, the bound kernel and the
+// slow paths use the same chain; the brute-force scan kernel in store mode (the coarse stage above 4096 lists) too.
+// Selection: ascending (score, list id), deterministic.
 // ------------------------------------------------------------------------------------------------
 
 // multi-batch launches: advance a per-batch pointer to batch blockIdx.y's copy (see IvfMulti)
@@ -473,7 +475,10 @@ __global__ __launch_bounds__(256) void ivf_pick_kernel(const float* __restrict__
 // alternating groups of 8 rows.  8 lanes share a row: every wave-instruction reads 8 rows x 128
 // contiguous bytes (whole cache lines), four instructions cover the 512-byte rows, nothing is
 // staged through LDS because no byte is used twice.  The 8 partial sums are folded with DPP
-// (quad_perm xor 1, xor 2, row_half_mirror).  The running top-k of a wave is one sorted list with
+// (quad_perm xor 1, xor 2, row_half_mirror).  Summation order of a dot product (the oracle's
+// "fold8", pinned by the tests on non-integer queries): lane s of a row's 8 walks the elements
+// 32 m + 4 s + i (m ascending, i = 0..3) as one fmaf chain, the fold gives
+// ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)) -- not the MFMA kernels' chain.  The running top-k of a wave is one sorted list with
 // entry j living in lane j; inserting is a ballot + popcount + row_shr:1 shift.
 // ------------------------------------------------------------------------------------------------
 template <int KCAP>
@@ -1631,6 +1636,21 @@ __global__ __launch_bounds__(kIvfWideF32Threads) void ivf_scan_wide_f32_kernel(c
     sink_bin_wave(p.sink, wb, wbase, lane);
 }
 
+// One thread's fp32 dot product of a row and a query in the order of the MFMA scans: element 16 c + 4 g + i for c ascending,
+// i = 0..3, g = 0..3 (g is the MFMA's k index), each step one fused multiply-add -- the chain a v_mfma_f32_16x16x4_f32
+// sequence works through.  A query that the slow paths rank gets the bits the list scan gives it: on rows or queries that are
+// not integers the result does not depend on which of the two scored it (plain ascending order differed in the last bits).
+__device__ __forceinline__ float dot_mfma_order(const float* __restrict__ b, const float* __restrict__ q) {
+    float dot = 0.f;
+    for (int c = 0; c < kDim / 16; ++c) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) dot = fmaf(b[16 * c + 4 * g + i], q[16 * c + 4 * g + i], dot);
+    }
+    return dot;
+}
+
 // Exact slow path, one workgroup per query that has no usable bound (or every query when a candidate buffer overflowed:
 // masses of duplicate rows): all rows of the query's probed lists, thread-private sorted lists, ranking through LDS.
 // (sd, sp: 256 * 16 words of LDS each, from the kernel)
@@ -1674,8 +1694,7 @@ __device__ __forceinline__ void ivf_wide_slow_body(const IvfWideParams& p, const
                 d = (float)(qt + p.rterm[row] - 2 * dot);
             } else {
                 const float* b = p.vecs + (int64_t)row * kDim;
-                float dot = 0.f;
-                for (int t = 0; t < kDim; ++t) dot = fmaf(b[t], qv[t], dot);
+                const float dot = dot_mfma_order(b, qv);
                 d = p.metric ? -dot : fmaf(-2.0f, dot, qn + p.vnorm[row]);
             }
             if (lex_lt(d, row, ld[KM - 1], lp[KM - 1])) list_insert<KM>(ld, lp, d, row);
@@ -2086,8 +2105,7 @@ __global__ __launch_bounds__(kRankKThreads) void ivf_widek_rank_kernel(const Ivf
                         d = (float)(qt + p.rterm[row] - 2 * dot);
                     } else {
                         const float* b = p.vecs + (int64_t)row * kDim;
-                        float dot = 0.f;
-                        for (int t = 0; t < kDim; ++t) dot = fmaf(b[t], qv[t], dot);
+                        const float dot = dot_mfma_order(b, qv);
                         d = p.metric ? -dot : fmaf(-2.0f, dot, qn + p.vnorm[row]);
                     }
                     uint64_t key;

@@ -63,6 +63,17 @@ def lib():
         L.vo_ivf_search_metric.restype = C.c_int64
         L.vo_ivf_search_metric.argtypes = [_f32p, _f32p, C.c_int64, C.c_int, _f32p, C.c_int, _i32p, C.c_void_p,
                                            _f32p, C.c_int64, C.c_int, C.c_int, C.c_int, _i32p, _f32p, C.c_void_p]
+        L.vo_dot_ordered.restype = C.c_float
+        L.vo_dot_ordered.argtypes = [_f32p, _f32p, C.c_int, C.c_int]
+        L.vo_l2_row_order.restype = None
+        L.vo_l2_row_order.argtypes = [_f32p, C.c_float, _f32p, _f32p, C.c_int64, C.c_int, C.c_int, _f32p]
+        L.vo_search_bf_order.restype = C.c_int
+        L.vo_search_bf_order.argtypes = [_f32p, C.c_int64, C.c_int, _f32p, C.c_int64, C.c_int, C.c_int, _i32p, _f32p,
+                                         C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.vo_ivf_search_order.restype = C.c_int64
+        L.vo_ivf_search_order.argtypes = [_f32p, _f32p, C.c_int64, C.c_int, _f32p, C.c_int, _i32p, C.c_void_p,
+                                          _f32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _f32p,
+                                          C.c_void_p, C.c_void_p]
         L.vo_recall.restype = C.c_double
         L.vo_recall.argtypes = [_i32p, C.c_int, _i32p, C.c_int, C.c_int]
         L.vo_num_threads.restype = C.c_int
@@ -80,6 +91,18 @@ def lib():
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+# Summation orders of a dot product (vs_oracle.c, vo_dot_order).  "lanes8": the stand-in for the reference's sgemm.
+# "chain": the product's fp32 MFMA kernels, element 16c + 4g + i for c ascending, i = 0..3, g = 0..3.  "fold8": the
+# list scan of the query-major IVF path (ivf_scan_kernel).  On integer data below 2^24 all three give the same bits.
+DOT_ORDERS = {"lanes8": 0, "chain": 1, "fold8": 2}
+
+
+def dot(a: np.ndarray, b: np.ndarray, dot_order: str = "lanes8") -> np.float32:
+    a, b = _f32(a).reshape(-1), _f32(b).reshape(-1)
+    assert a.shape == b.shape
+    return np.float32(lib().vo_dot_ordered(a, b, a.shape[0], DOT_ORDERS[dot_order]))
 
 
 def read_fvecs(path: str) -> np.ndarray:
@@ -103,15 +126,22 @@ def compute_norms(x: np.ndarray) -> np.ndarray:
     return out
 
 
-def l2_row(q: np.ndarray, base: np.ndarray, bn: np.ndarray | None = None) -> np.ndarray:
+def l2_row(q: np.ndarray, base: np.ndarray, bn: np.ndarray | None = None, dot_order: str = "lanes8") -> np.ndarray:
     q = _f32(q).reshape(1, -1)
     base = _f32(base)
     if bn is None:
         bn = compute_norms(base)
     qn = compute_norms(q)[0]
     out = np.empty(base.shape[0], dtype=np.float32)
-    lib().vo_l2_row(q[0], float(qn), base, _f32(bn), base.shape[0], base.shape[1], out)
+    lib().vo_l2_row_order(q[0], float(qn), base, _f32(bn), base.shape[0], base.shape[1], DOT_ORDERS[dot_order], out)
     return out
+
+
+def l2_matrix(queries: np.ndarray, base: np.ndarray, dot_order: str = "lanes8") -> np.ndarray:
+    """[nq, N] squared L2 distances, one l2_row per query (the base norms are worked out once)."""
+    queries, base = _f32(queries), _f32(base)
+    bn = compute_norms(base)
+    return np.stack([l2_row(q, base, bn, dot_order) for q in queries])
 
 
 def select_topk(dist: np.ndarray, k: int):
@@ -131,14 +161,15 @@ def select_topk_sparse(rows: np.ndarray, dist: np.ndarray, k: int):
     return idx, dd
 
 
-def search_bf(base: np.ndarray, queries: np.ndarray, k: int, timing: dict | None = None):
+def search_bf(base: np.ndarray, queries: np.ndarray, k: int, timing: dict | None = None, dot_order: str = "lanes8"):
     """cpu_baseline.cpp run_benchmark loop: returns (ids[nq,k], dists[nq,k])."""
     base, queries = _f32(base), _f32(queries)
     nq = queries.shape[0]
     idx = np.empty((nq, k), dtype=np.int32)
     dd = np.empty((nq, k), dtype=np.float32)
     td, tk = C.c_double(0), C.c_double(0)
-    rc = lib().vo_search_bf(base, base.shape[0], base.shape[1], queries, nq, k, idx, dd, C.byref(td), C.byref(tk))
+    rc = lib().vo_search_bf_order(base, base.shape[0], base.shape[1], queries, nq, k, DOT_ORDERS[dot_order], idx, dd,
+                                  C.byref(td), C.byref(tk))
     if rc != 0:
         raise MemoryError("vo_search_bf")
     if timing is not None:
@@ -153,9 +184,12 @@ def write_results(path: str, idx: np.ndarray, dist: np.ndarray) -> None:
         raise IOError(path)
 
 
-def ivf_search(vectors_reordered, offsets, reorder_to_original, centroids, queries, k, nprobe, return_probes=False, metric=0):
+def ivf_search(vectors_reordered, offsets, reorder_to_original, centroids, queries, k, nprobe, return_probes=False, metric=0,
+               dot_order="lanes8", scan_order=None, return_coarse=False):
     """IVFIndex::searchBatch (reordered mode) restated with L2 (metric 0) or the reference's own inner product (metric 1:
-    dists = -q.v, smallest first).  Returns ids, dists, total_candidates[, probes]."""
+    dists = -q.v, smallest first).  dot_order names the summation order of the coarse scores and of the list scan
+    (DOT_ORDERS); scan_order, if given, that of the list scan alone.  Returns ids, dists, total_candidates[, probes
+    [, coarse scores of the probes]]."""
     v = _f32(vectors_reordered)
     cen = _f32(centroids)
     q = _f32(queries)
@@ -171,9 +205,14 @@ def ivf_search(vectors_reordered, offsets, reorder_to_original, centroids, queri
     if reorder_to_original is not None:
         r2o = np.ascontiguousarray(reorder_to_original, dtype=np.int32)
         r2o_p = r2o.ctypes.data_as(C.c_void_p)
-    probes = np.empty((nq, npb), dtype=np.int32) if return_probes else None
-    total = lib().vo_ivf_search_metric(v, vn, v.shape[0], v.shape[1], cen, nlist, off, r2o_p, q, nq, k, nprobe, int(metric), idx, dd,
-                                       probes.ctypes.data_as(C.c_void_p) if probes is not None else None)
+    probes = np.empty((nq, npb), dtype=np.int32) if return_probes or return_coarse else None
+    coarse = np.empty((nq, npb), dtype=np.float32) if return_coarse else None
+    total = lib().vo_ivf_search_order(v, vn, v.shape[0], v.shape[1], cen, nlist, off, r2o_p, q, nq, k, nprobe, int(metric),
+                                      DOT_ORDERS[dot_order], DOT_ORDERS[scan_order or dot_order], idx, dd,
+                                      probes.ctypes.data_as(C.c_void_p) if probes is not None else None,
+                                      coarse.ctypes.data_as(C.c_void_p) if coarse is not None else None)
+    if return_coarse:
+        return idx, dd, int(total), probes, coarse
     if return_probes:
         return idx, dd, int(total), probes
     return idx, dd, int(total)

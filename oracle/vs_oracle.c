@@ -83,7 +83,7 @@ static float vo_norm_one(const float* v, int dim) {
     float sum = r[0] + r[1];
     sum = sum + r[2]; sum = sum + r[3]; sum = sum + r[4];
     sum = sum + r[5]; sum = sum + r[6]; sum = sum + r[7];
-    for (; i < dim; ++i) sum += v[i] * v[i];
+    for (; i < dim; ++i) sum = fmaf(v[i], v[i], sum);  /* (gcc -O3 -mfma contracts :110 to this; explicit, as in the kernels) */
     return sum;
 }
 
@@ -107,17 +107,62 @@ static inline float vo_dot(const float* a, const float* b, int dim) {
     return sum;
 }
 
+/* The product's fp32 MFMA dot product, restated.  A v_mfma_f32_16x16x4_f32 adds its four products to the
+ * accumulator one after the other, k = 0..3, each as one fused multiply-add (one rounding).  Every fp32 MFMA
+ * kernel of the product hands the MFMA of step (c, i) the elements 16c + 4g + i of the two vectors as k index g
+ * (lane >> 4), with c ascending over the 16-float segments and i = 0..3 inside a segment, so a dot product is
+ * the fmaf chain below.  Segments are zero padded: elements past dim add exact zeros and are skipped.
+ * Pinned on the device by the score-matrix test of tests/test_gpu_nd.py, not by the reference. */
+static inline float vo_dot_chain(const float* a, const float* b, int dim) {
+    float acc = 0.0f;
+    for (int c = 0; 16 * c < dim; ++c)
+        for (int i = 0; i < 4; ++i)
+            for (int g = 0; g < 4; ++g) {
+                const int x = 16 * c + 4 * g + i;
+                if (x < dim) acc = fmaf(a[x], b[x], acc);
+            }
+    return acc;
+}
+
+/* The list scan of the query-major IVF path (ivf_scan_kernel, nlist > 4096): 8 lanes share a row, lane s walks
+ * the elements 32m + 4s + i (m ascending, i = 0..3) as one fmaf chain, and the 8 partial sums are folded
+ * ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)). */
+static inline float vo_dot_fold8(const float* a, const float* b, int dim) {
+    float p[8];
+    for (int s = 0; s < 8; ++s) {
+        float acc = 0.0f;
+        for (int m = 0; 32 * m < dim; ++m)
+            for (int i = 0; i < 4; ++i) {
+                const int x = 32 * m + 4 * s + i;
+                if (x < dim) acc = fmaf(a[x], b[x], acc);
+            }
+        p[s] = acc;
+    }
+    return ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+}
+
+/* dot orders of the *_order entry points */
+enum { VO_LANES8 = 0, VO_CHAIN = 1, VO_FOLD8 = 2 };
+static inline float vo_dot_order(const float* a, const float* b, int dim, int order) {
+    return order == VO_CHAIN ? vo_dot_chain(a, b, dim) : order == VO_FOLD8 ? vo_dot_fold8(a, b, dim) : vo_dot(a, b, dim);
+}
+VO_API float vo_dot_ordered(const float* a, const float* b, int dim, int order) { return vo_dot_order(a, b, dim, order); }
+
 /* One query against the whole base: sgemm stand-in + the epilogue
  * dist[j] = qn + bn[j] - 2*dot[j]  (cpu_baseline.cpp:239-242).  gcc -O3 -mfma
  * contracts the reference expression to fnmadd(2, dot, qn+bn); written
  * explicitly so the oracle does not depend on -ffp-contract. */
-VO_API void vo_l2_row(const float* q, float qn, const float* base, const float* bn,
-                      int64_t N, int dim, float* dist) {
+VO_API void vo_l2_row_order(const float* q, float qn, const float* base, const float* bn,
+                            int64_t N, int dim, int order, float* dist) {
 #pragma omp parallel for schedule(static)
     for (int64_t j = 0; j < N; ++j) {
-        float dot = vo_dot(q, base + j * dim, dim);
+        float dot = vo_dot_order(q, base + j * dim, dim, order);
         dist[j] = fmaf(-2.0f, dot, qn + bn[j]);
     }
+}
+VO_API void vo_l2_row(const float* q, float qn, const float* base, const float* bn,
+                      int64_t N, int dim, float* dist) {
+    vo_l2_row_order(q, qn, base, bn, N, dim, VO_LANES8, dist);
 }
 
 /* ------------------------------------------------------------- select_topk */
@@ -204,8 +249,8 @@ static double vo_now(void) {
 #endif
 }
 
-VO_API int vo_search_bf(const float* base, int64_t N, int dim, const float* queries, int64_t nq,
-                        int k, int* out_idx, float* out_dist, double* t_dist_s, double* t_topk_s) {
+VO_API int vo_search_bf_order(const float* base, int64_t N, int dim, const float* queries, int64_t nq,
+                              int k, int order, int* out_idx, float* out_dist, double* t_dist_s, double* t_topk_s) {
     float* bn = (float*)malloc(sizeof(float) * (size_t)N);
     float* qn = (float*)malloc(sizeof(float) * (size_t)(nq > 0 ? nq : 1));
     float* dist = (float*)malloc(sizeof(float) * (size_t)N);
@@ -215,7 +260,7 @@ VO_API int vo_search_bf(const float* base, int64_t N, int dim, const float* quer
     double td = 0, tk = 0;
     for (int64_t i = 0; i < nq; ++i) {
         double t0 = vo_now();
-        vo_l2_row(queries + i * dim, qn[i], base, bn, N, dim, dist);
+        vo_l2_row_order(queries + i * dim, qn[i], base, bn, N, dim, order, dist);
         double t1 = vo_now();
         vo_select_topk(dist, N, k, out_idx + i * k, out_dist + i * k);
         double t2 = vo_now();
@@ -225,6 +270,10 @@ VO_API int vo_search_bf(const float* base, int64_t N, int dim, const float* quer
     if (t_topk_s) *t_topk_s = tk;
     free(bn); free(qn); free(dist);
     return 0;
+}
+VO_API int vo_search_bf(const float* base, int64_t N, int dim, const float* queries, int64_t nq,
+                        int k, int* out_idx, float* out_dist, double* t_dist_s, double* t_topk_s) {
+    return vo_search_bf_order(base, N, dim, queries, nq, k, VO_LANES8, out_idx, out_dist, t_dist_s, t_topk_s);
 }
 
 /* ------------------------------------------------------------ write_results */
@@ -286,11 +335,15 @@ VO_API int64_t vo_ivf_search(const float* vectors_reordered, const float* vec_no
                                 nprobe, 0, out_idx, out_dist, out_probes);
 }
 
-VO_API int64_t vo_ivf_search_metric(const float* vectors_reordered, const float* vec_norms, int64_t N, int dim,
-                                    const float* centroids, int nlist, const int32_t* offsets,
-                                    const int32_t* reorder_to_original,
-                                    const float* queries, int64_t nq, int k, int nprobe, int metric,
-                                    int* out_idx, float* out_dist, int32_t* out_probes /* nq*nprobe or NULL */) {
+/* The same search with the dot products of the coarse stage and of the list scan in a named order (vo_dot_order):
+ * the product's kernels are pinned to these bit for bit on non-integer data. */
+VO_API int64_t vo_ivf_search_order(const float* vectors_reordered, const float* vec_norms, int64_t N, int dim,
+                                   const float* centroids, int nlist, const int32_t* offsets,
+                                   const int32_t* reorder_to_original,
+                                   const float* queries, int64_t nq, int k, int nprobe, int metric,
+                                   int coarse_order, int scan_order,
+                                   int* out_idx, float* out_dist, int32_t* out_probes /* nq*nprobe or NULL */,
+                                   float* out_coarse /* nq*nprobe scores of the probes, or NULL */) {
     if (nprobe > nlist) nprobe = nlist;
     float* cn = (float*)malloc(sizeof(float) * (size_t)nlist);
     vo_compute_norms(centroids, nlist, dim, cn);
@@ -301,7 +354,7 @@ VO_API int64_t vo_ivf_search_metric(const float* vectors_reordered, const float*
         float qn = vo_norm_one(q, dim);
         vo_pair* cs = (vo_pair*)malloc(sizeof(vo_pair) * (size_t)nlist);
         for (int c = 0; c < nlist; ++c) {
-            const float cdot = vo_dot(q, centroids + (int64_t)c * dim, dim);
+            const float cdot = vo_dot_order(q, centroids + (int64_t)c * dim, dim, coarse_order);
             cs[c].d = metric ? -cdot : fmaf(-2.0f, cdot, qn + cn[c]);
             cs[c].id = c;
         }
@@ -314,8 +367,9 @@ VO_API int64_t vo_ivf_search_metric(const float* vectors_reordered, const float*
         for (int p = 0; p < nprobe; ++p) {
             int c = cs[p].id;
             if (out_probes) out_probes[b * nprobe + p] = c;
+            if (out_coarse) out_coarse[b * nprobe + p] = cs[p].d;
             for (int32_t r = offsets[c]; r < offsets[c + 1]; ++r) {
-                float dot = vo_dot(q, vectors_reordered + (int64_t)r * dim, dim);
+                float dot = vo_dot_order(q, vectors_reordered + (int64_t)r * dim, dim, scan_order);
                 all[m].d = metric ? -dot : fmaf(-2.0f, dot, qn + vec_norms[r]);
                 all[m].id = r;
                 ++m;
@@ -333,6 +387,15 @@ VO_API int64_t vo_ivf_search_metric(const float* vectors_reordered, const float*
     free(cn);
     (void)N;
     return total;
+}
+
+VO_API int64_t vo_ivf_search_metric(const float* vectors_reordered, const float* vec_norms, int64_t N, int dim,
+                                    const float* centroids, int nlist, const int32_t* offsets,
+                                    const int32_t* reorder_to_original,
+                                    const float* queries, int64_t nq, int k, int nprobe, int metric,
+                                    int* out_idx, float* out_dist, int32_t* out_probes /* nq*nprobe or NULL */) {
+    return vo_ivf_search_order(vectors_reordered, vec_norms, N, dim, centroids, nlist, offsets, reorder_to_original, queries, nq, k,
+                               nprobe, metric, VO_LANES8, VO_LANES8, out_idx, out_dist, out_probes, NULL);
 }
 
 /* main_ivf.cpp:52-59 compute_recall: |pred[:k] n gt[:k]| / k (set overlap). */

@@ -17,6 +17,7 @@ import sys
 import numpy as np
 import pytest
 
+import near_ties
 import oracle
 
 pytestmark = pytest.mark.gpu
@@ -185,6 +186,119 @@ def test_distances_are_the_brute_force_scans_bits(gpu_pkg, dim):
     assert np.array_equal(d.view(np.int32), bd.view(np.int32))
     assert np.array_equal(ids, bi)
     assert np.array_equal(d2.view(np.int32), d.view(np.int32)) and np.array_equal(ids2, ids)
+    # and both are the CPU reference's bits: the oracle in the kernels' summation order
+    oi, od, ototal = oracle.ivf_search(vr, off, r2o, cents, q, k, nlist, dot_order="chain")
+    assert np.array_equal(d.view(np.int32), od.view(np.int32)) and np.array_equal(ids, oi) and total == ototal
+
+
+@functools.lru_cache(maxsize=3)
+def _gauss_index(dim):
+    """N(0, 1) rows in NLIST lists (nearest of NLIST sampled rows, float64), centroids = the lists' means in fp32: nothing
+    is an integer, every coarse score and distance is rounded.  70 ordinary queries and 300 forced coarse near-ties at
+    nprobe = 1 (tests/near_ties.py) with the mask of those whose probe set depends on the summation order.
+
+    The forced queries' seeds are the midpoints of the twelve closest pairs of centroids, plus N(0, 0.01^2) noise.  A score
+    is fl(fl(|q|^2 + |c|^2) - 2 q.c): the summation order changes q.c by a few units in ITS last place, which survives the
+    final rounding only where 2 q.c is not much smaller than the score |q - c|^2 -- a query close to both centroids.  With
+    N(0, 1) seeds 5 to 13 % of all scores differ between the two orders at all and the probe set of 2 to 4 % of the forced
+    queries does; from these seeds 13 % (20-d) to 40 % (960-d).  At nprobe = 4 the two centroids at the boundary are
+    farther from the query than three others and the share stays under 10 % for any seed tried (4 to 10 %), so the
+    (5, 4) and (16, 24) cases run the same queries without a claim about near-ties."""
+    rng = np.random.default_rng(9000 + dim)
+    base = rng.normal(0, 1, size=(N, dim)).astype(np.float32)
+    q = rng.normal(0, 1, size=(70, dim)).astype(np.float32)
+    b64 = base.astype(np.float64)
+    cen0 = b64[rng.choice(N, NLIST, replace=False)]
+    assign = ((b64 * b64).sum(1)[:, None] - 2 * b64 @ cen0.T + (cen0 * cen0).sum(1)[None, :]).argmin(1)
+    order = np.argsort(assign, kind="stable")
+    off = np.zeros(NLIST + 1, dtype=np.int32)
+    off[1:] = np.cumsum(np.bincount(assign, minlength=NLIST))
+    vr = np.ascontiguousarray(base[order])
+    r2o = order.astype(np.int32)
+    cents = np.stack([vr[off[c]:off[c + 1]].astype(np.float64).mean(0) for c in range(NLIST)]).astype(np.float32)
+    c64 = cents.astype(np.float64)
+    gap = ((c64[:, None] - c64[None]) ** 2).sum(2)
+    gap[np.tril_indices(NLIST)] = np.inf
+    pairs = np.dstack(np.unravel_index(np.argsort(gap, axis=None)[:12], gap.shape))[0]
+    pick = pairs[rng.integers(0, len(pairs), 300)]
+    seeds = 0.5 * (c64[pick[:, 0]] + c64[pick[:, 1]]) + 0.01 * rng.normal(0, 1, size=(300, dim))
+    fq, mask = near_ties.boundary_queries(cents, seeds, 1, rng)
+    for a in (vr, cents, off, r2o, q, fq, mask):
+        a.setflags(write=False)
+    return vr, cents, off, r2o, q, fq, mask
+
+
+@pytest.mark.parametrize("dim", [20, 100, 960])
+def test_non_integer_data_equals_the_chain_oracle(gpu_pkg, dim):
+    """A CPU reference for the general pipeline on data that is not integer valued: coarse scores (scan_nd_kernel's store
+    mode on the centroid table), probe selection and list scan (ivf_scan_nd_kernel) against the oracle in the kernels'
+    summation order.  ids, distance bits and total_candidates are equal for EVERY query, the forced near-ties included."""
+    vr, cents, off, r2o, q, fq, mask = _gauss_index(dim)
+    near_ties.require_teeth(mask, f"general index dim {dim} nlist {NLIST} nprobe 1")
+    qq = np.concatenate([q, fq])
+    with _open(gpu_pkg, vr, cents, off, r2o) as ivf:
+        for k, nprobe in ((1, 1), (5, 4), (16, NLIST)):
+            oi, od, ototal = oracle.ivf_search(vr, off, r2o, cents, qq, k, nprobe, dot_order="chain")
+            ids, d, total = ivf.searchBatch(qq, len(qq), k, nprobe)
+            bad = np.nonzero([not (np.array_equal(d[i].view(np.int32), od[i].view(np.int32)) and np.array_equal(ids[i], oi[i]))
+                              for i in range(len(qq))])[0]
+            if len(bad):
+                print(f"dim {dim} k {k} nprobe {nprobe}: {len(bad)} of {len(qq)} queries differ, first {bad[:5]}")
+                print(near_ties.describe(cents, qq, int(bad[0]), nprobe))
+            assert len(bad) == 0, (dim, k, nprobe, bad[:10])
+            assert total == ototal, (dim, k, nprobe, total, ototal)
+
+
+def _int_lists(dim, n, sizes, seed):
+    """integer rows as in _int_index, cut into lists of the given sizes (clusters stay together), centroids = rint(mean)"""
+    rng = np.random.default_rng(seed)
+    hi = _hi(dim)
+    nlist = len(sizes)
+    base = rng.integers(0, hi, size=(n, dim)).astype(np.float32)
+    assign = _nearest(base, base[rng.choice(n, 64, replace=False)])
+    order = np.argsort(assign, kind="stable")
+    off = np.zeros(nlist + 1, dtype=np.int32)
+    off[1:] = np.cumsum(sizes)
+    assert off[-1] == n
+    vr = np.ascontiguousarray(base[order])
+    cents = np.stack([np.rint(vr[off[c]:off[c + 1]].astype(np.float64).mean(0)) for c in range(nlist)]).astype(np.float32)
+    return vr, cents, off, order.astype(np.int32), hi, rng
+
+
+def test_plan_with_two_lists_per_prefix_thread_and_two_launch_groups(gpu_pkg):
+    """nlist = 1500: every thread of ivf_nd_prefix owns two lists; 1100 queries in one host call: a launch group of 1024
+    queries (kIvfNdGroupQ) and one of 76.  Integer data: equality with the oracle for every query."""
+    dim, n, nlist, nq, k, nprobe = 100, 6000, 1500, 1100, 5, 4
+    vr, cents, off, r2o, hi, rng = _int_lists(dim, n, np.full(nlist, n // nlist), 5600)
+    q = rng.integers(0, hi, size=(nq, dim)).astype(np.float32)
+    q[:50] = vr[rng.choice(n, 50, replace=False)]
+    oi, od, ototal = oracle.ivf_search(vr, off, r2o, cents, q, k, nprobe, dot_order="chain")
+    with _open(gpu_pkg, vr, cents, off, r2o) as ivf:
+        assert ivf.getNumClusters() == nlist
+        ids, d, total = ivf.searchBatch(q, nq, k, nprobe)
+    assert np.array_equal(d, od) and np.array_equal(ids, oi) and total == ototal
+    assert np.array_equal(d[:50, 0], np.zeros(50, dtype=np.float32))  # (a query that is a row finds it: the probes are right)
+
+
+def test_plan_with_a_hot_list_nprobe_256_and_a_wrapping_item_loop(gpu_pkg):
+    """nlist = 300, list 0 holds a third of the rows and is among every query's probes; k = 8 (the KCAP 8 scan), nprobe = 256
+    (probe rank 255 in the slot's low byte), 1024 + 7 queries: in the first launch group list 0 is probed by all 1024
+    queries (64 items on one list) and the 16 000 items wrap the scan's fixed grid many times.  Integer data: equality
+    with the oracle for every query."""
+    dim, n, nlist, nq, k, nprobe = 100, 6000, 300, 1024 + 7, 8, 256
+    sizes = np.full(nlist, 0)
+    sizes[0] = 2000
+    rest = n - 2000
+    sizes[1:] = rest // (nlist - 1)
+    sizes[1:1 + rest % (nlist - 1)] += 1
+    vr, cents, off, r2o, hi, rng = _int_lists(dim, n, sizes, 5700)
+    q = rng.integers(0, hi, size=(nq, dim)).astype(np.float32)
+    oi, od, ototal, probes = oracle.ivf_search(vr, off, r2o, cents, q, k, nprobe, return_probes=True, dot_order="chain")
+    assert (probes == 0).any(1).all()  # list 0 is probed by every query
+    assert probes.shape == (nq, 256)
+    with _open(gpu_pkg, vr, cents, off, r2o) as ivf:
+        ids, d, total = ivf.searchBatch(q, nq, k, nprobe)
+    assert np.array_equal(d, od) and np.array_equal(ids, oi) and total == ototal
 
 
 _TOGGLE_SCRIPT = r"""

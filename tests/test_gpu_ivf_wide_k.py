@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import near_ties
 import oracle
 
 pytestmark = pytest.mark.gpu
@@ -66,26 +67,21 @@ def _dev_one(ivf, q, k, nprobe):
     return oi.cpu().numpy(), od.cpu().numpy()
 
 
-def _unambiguous(q, cents, nprobe):
-    """queries whose float64 coarse distances at ranks nprobe and nprobe + 1 differ by more than 1e-4 relative"""
-    q64, c64 = q.astype(np.float64), cents.astype(np.float64)
-    d = (q64 ** 2).sum(1)[:, None] - 2 * q64 @ c64.T + (c64 ** 2).sum(1)[None]
-    if nprobe >= d.shape[1]:
-        return np.ones(len(q), dtype=bool)
-    s = np.sort(d, axis=1)
-    a, b = s[:, nprobe - 1], s[:, nprobe]
-    return (b - a) > 1e-4 * np.maximum(np.abs(a), 1e-30)
-
-
 def _check_oracle(ids, d, idx, q, k, nprobe, metric=0, sign=1.0):
+    """ids and distances equal the oracle's for EVERY query.  The oracle sums its dot products in the kernels' order
+    (dot_order="chain"), so the probes on the non-integer centroids are the device's probes bit for bit."""
     base, cents, vr, off, r2o = idx
-    oi, od, _ = oracle.ivf_search(vr, off, r2o, cents, q, k, nprobe, metric=metric)
-    d = sign * d
-    same_d = np.array([np.array_equal(d[i], od[i]) for i in range(len(q))])
-    assert same_d.mean() >= 0.97, same_d.mean()
-    clear = _unambiguous(q, cents, nprobe)
-    bad = np.where(clear & ~np.array([np.array_equal(d[i], od[i]) and np.array_equal(ids[i], oi[i]) for i in range(len(q))]))[0]
-    assert len(bad) == 0, f"{len(bad)} unambiguous queries differ, first {bad[:5]}"
+    oi, od, _ = oracle.ivf_search(vr, off, r2o, cents, q, k, nprobe, metric=metric, dot_order="chain")
+    d = (sign * d).astype(np.float32)
+    same = np.array([np.array_equal(d[i].view(np.int32), od[i].view(np.int32)) and np.array_equal(ids[i], oi[i]) for i in range(len(q))])
+    bad = np.nonzero(~same)[0]
+    if len(bad):
+        i = int(bad[0])
+        print(f"{len(bad)} of {len(q)} queries differ from the chain oracle (k={k}, nprobe={nprobe}, metric={metric}); first: {i}")
+        print(near_ties.describe(cents, q, i, min(nprobe, len(cents)), metric))
+        col = np.nonzero((d[i].view(np.int32) != od[i].view(np.int32)) | (ids[i] != oi[i]))[0][:1]
+        print(f"first differing column {col}: device {ids[i][col]} {d[i][col]}, oracle {oi[i][col]} {od[i][col]}")
+    assert len(bad) == 0, f"{len(bad)} queries differ, first {bad[:5]}"
 
 
 def _check_props(ids, d, base, q):
@@ -126,6 +122,14 @@ def test_matches_oracle_k100(gpu_pkg, nprobe):
         di, dd = _dev_multi(ivf, q, 100, nprobe)
     _check_oracle(ids, d, idx, q, 100, nprobe)
     assert np.array_equal(di, ids) and np.array_equal(dd, d)
+    # forced coarse near-ties (tests/near_ties.py): not byte valued, their batches rank on the fp32 rows
+    fq, mask = near_ties.boundary_queries(idx[1], gpu_pkg.synth_sift(256, seed=143), nprobe, np.random.default_rng(143))
+    near_ties.require_teeth(mask, f"wide k = 100, nlist 64, nprobe {nprobe}")
+    with _open(gpu_pkg, idx) as ivf:
+        fi, fd, _ = ivf.searchBatch(fq, len(fq), 100, nprobe)
+        mi, md = _dev_multi(ivf, fq, 100, nprobe)
+    _check_oracle(fi, fd, idx, fq, 100, nprobe)
+    assert np.array_equal(mi, fi) and np.array_equal(md.view(np.int32), fd.view(np.int32))
 
 
 def test_result_properties_and_padding(gpu_pkg):

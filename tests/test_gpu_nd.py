@@ -160,6 +160,42 @@ def test_scores_dev_at_dim_100(gpu_pkg):
     assert np.all(got[:, n:] == -1.0)  # padding columns untouched
 
 
+@pytest.mark.parametrize("dim", [1, 3, 20, 100, 128, 130, 384, 2048])
+def test_score_matrix_is_the_chain_oracles_bits(gpu_pkg, dim):
+    """The direct evidence for the arithmetic contract of every fp32 MFMA kernel: on N(0, 1) rows the score matrix equals,
+    bit for bit, the oracle's "chain" order -- q.b as one fmaf chain over the elements 16 c + 4 g + i (c ascending, i =
+    0..3, g = 0..3 the MFMA's k index), norms in the 8-lane order, fmaf(-2, q.b, |q|^2 + |b|^2) -- and does not equal the
+    "lanes8" order.  300 rows = four full 64-row blocks and a ragged one; 100-d is 7 segments (the single-segment tail),
+    128-d the specialised index (scan_kernel's store mode, also the coarse stage of an IVF index above 4096 lists)."""
+    import torch
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(8000 + dim)
+    n, B, ld = 300, 20, 320
+    base = rng.normal(0, 1, size=(n, dim)).astype(np.float32)
+    q = rng.normal(0, 1, size=(B, dim)).astype(np.float32)
+    want = oracle.l2_matrix(q, base, "chain")
+    other = oracle.l2_matrix(q, base, "lanes8")
+    if dim >= 20:  # (one or three products: every order is the same chain)
+        assert not np.array_equal(want.view(np.int32), other.view(np.int32))
+    sc = torch.full((B, ld), -1.0, dtype=torch.float32, device=dev)
+    qd = torch.from_numpy(q).to(dev)
+    with gpu_pkg.BruteForceIndex(base) as idx:
+        assert idx.getDim() == dim
+        idx.scores_dev(qd.data_ptr(), B, sc.data_ptr(), ld, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+    got = sc.cpu().numpy()[:, :n].copy()
+    bad = np.argwhere(got.view(np.int32) != want.view(np.int32))
+    print(f"dim {dim}: {len(bad)} of {got.size} scores differ from the chain order, "
+          f"{int((got.view(np.int32) != other.view(np.int32)).sum())} from lanes8")
+    if len(bad):
+        i, j = bad[0]
+        print(f"first: query {i} row {j}: device {float(got[i, j])!r} ({got.view(np.int32)[i, j]:#x}) "
+              f"chain {float(want[i, j])!r} ({want.view(np.int32)[i, j]:#x}) lanes8 {float(other[i, j])!r}")
+    assert np.array_equal(got.view(np.int32), want.view(np.int32))
+    if dim >= 20:
+        assert not np.array_equal(got.view(np.int32), other.view(np.int32))
+
+
 def test_search_topk_dev_multi_k100(gpu_pkg):
     import torch
     dev = torch.device("cuda:0")
@@ -237,6 +273,9 @@ def test_non_integer_data_within_derived_tolerance(gpu_pkg, dim):
             gaps_ok[i, t] = min(lo, hi) > 4 * tol
     assert gaps_ok.mean() > 0.9
     assert np.array_equal(ids[gaps_ok], oi[gaps_ok])
+    # and bit for bit what the chain order gives (the kernel's own order; no two of a query's distances are equal here)
+    ci, cd = oracle.search_bf(base, q, 5, dot_order="chain")
+    assert np.array_equal(d.view(np.int32), cd.view(np.int32)) and np.array_equal(ids, ci)
 
 
 _FORCE_SCRIPT = r"""

@@ -146,3 +146,132 @@ def test_q8_quantiser_known_answers_and_numpy_recomputation():
         assert ids[b].tolist() == order.tolist() and top[b].tolist() == got[b][order].tolist()
     ids, top = oracle.q8_topk(got[:, :4], 6)  # fewer rows than k (IVFIndex.cpp:457 clamps likewise): (-1, 0) tail
     assert np.all(ids[:, 4:] == -1) and np.all(top[:, 4:] == 0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dot orders: "chain" (the product's fp32 MFMA kernels) and "fold8" (the query-major IVF list scan) beside "lanes8"
+# ---------------------------------------------------------------------------------------------------------------------
+def _chain_index_order(dim):
+    return [16 * c + 4 * g + i for c in range((dim + 15) // 16) for i in range(4) for g in range(4) if 16 * c + 4 * g + i < dim]
+
+
+def _fma_chain(a, b, order):
+    """acc = fmaf(a[x], b[x], acc) over `order`, one rounding per step: the product of two fp32 numbers is exact in
+    float64, and the float64 sum of that product and an fp32 accumulator rounded to fp32 is the fused result unless the
+    float64 sum itself had to round -- which the callers' inputs (few significant bits) rule out."""
+    acc = np.float32(0)
+    for x in order:
+        s = np.float64(a[x]) * np.float64(b[x]) + np.float64(acc)
+        acc = np.float32(s)
+    return acc
+
+
+@pytest.mark.parametrize("dim", [1, 3, 20, 100, 128, 130, 300])
+def test_dot_orders_are_exact_on_integer_data(dim):
+    rng = np.random.default_rng(dim)
+    base = rng.integers(0, 219, size=(200, dim)).astype(np.float32)
+    q = rng.integers(0, 219, size=(5, dim)).astype(np.float32)
+    ex = oracle.exact_int_dists(q, base).astype(np.float32)
+    for order in ("lanes8", "chain", "fold8"):
+        assert np.array_equal(oracle.l2_matrix(q, base, order), ex), order
+        ids, d = oracle.search_bf(base, q, 5, dot_order=order)
+        ids0, d0 = oracle.search_bf(base, q, 5)
+        assert np.array_equal(ids, ids0) and np.array_equal(d, d0), order
+
+
+@pytest.mark.parametrize("dim", [1, 7, 20, 100, 128, 960, 2048])
+def test_dot_orders_within_gamma_of_float64(dim):
+    """Any fp32 summation of dim products, fused or not, stays within gamma_dim * sum |a b| of the true value
+    (gamma_n = n u / (1 - n u), u = 2^-24: Higham, Accuracy and Stability of Numerical Algorithms, section 3.1)."""
+    rng = np.random.default_rng(100 + dim)
+    a = rng.standard_normal((50, dim)).astype(np.float32)
+    b = rng.standard_normal((50, dim)).astype(np.float32)
+    u = 2.0 ** -24
+    gamma = dim * u / (1 - dim * u)
+    for order in ("lanes8", "chain", "fold8"):
+        for i in range(len(a)):
+            got = float(oracle.dot(a[i], b[i], order))
+            true = float(a[i].astype(np.float64) @ b[i].astype(np.float64))
+            bound = gamma * float(np.abs(a[i].astype(np.float64) * b[i].astype(np.float64)).sum())
+            assert abs(got - true) <= bound, (order, dim, i, got, true, bound)
+
+
+def test_chain_order_by_hand_on_20_elements():
+    """b = 1; a holds one 2^24 (element 0), one -2^24 and ones.  A 1 added to +-2^24 is lost (ties to even), a 1 added to
+    anything smaller survives: the result counts the ones that an order visits outside the stretch between the two big
+    elements.  Visiting orders of the 20 elements: chain = 0 4 8 12 | 1 5 9 13 | 2 6 10 14 | 3 7 11 15 | 16 17 18 19,
+    ascending = 0 1 2 ... 19 (the ones at 1 .. 8 are lost, 10 survive), lanes8 = lane j sums j and j + 8 (r0 = 2^24: one
+    lost, r1 = 1 - 2^24 exact, the others 2), the lanes are added pairwise (1 + 4 + 8 = 13), then the tail 16 .. 19: 17."""
+    a = np.ones(20, dtype=np.float32)
+    b = np.ones(20, dtype=np.float32)
+    a[0] = 2.0 ** 24
+    a[9] = -2.0 ** 24     # chain position 6: the ones at 4, 8, 12, 1, 5 are lost, the 13 after it survive
+    chain = _fma_chain(a, b, _chain_index_order(20))
+    asc = _fma_chain(a, b, range(20))
+    # lanes8 by hand: lanes r[j] = a[j] + a[j + 8] (exact, fmaf), ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), tail
+    r = [np.float32(np.float64(a[j]) + np.float64(a[j + 8])) for j in range(8)]
+    f = lambda x, y: np.float32(np.float64(x) + np.float64(y))
+    l8 = f(f(f(r[0], r[1]), f(r[2], r[3])), f(f(r[4], r[5]), f(r[6], r[7])))
+    for x in range(16, 20):
+        l8 = f(l8, a[x])
+    assert (float(chain), float(asc), float(l8)) == (13.0, 10.0, 17.0)
+    assert oracle.dot(a, b, "chain") == chain
+    assert oracle.dot(a, b, "lanes8") == l8
+    # the same numbers through math.fma where the interpreter has it (3.13+): double rounding cannot occur here
+    import math
+    if hasattr(math, "fma"):
+        acc = 0.0
+        for x in _chain_index_order(20):
+            acc = float(np.float32(math.fma(float(a[x]), float(b[x]), acc)))
+        assert acc == 13.0
+    # fold8: lane s walks 4s .. 4s + 3 (only m = 0 exists below 32): p0 = 2^24 (three ones lost), p1 = 4, p2 = 1 - 2^24 + 1 + 1
+    # = -2^24 + 3 (exact: the spacing below 2^24 is 1), p3 = p4 = 4, p5 = p6 = p7 = 0: ((2^24 + 4) + (-2^24 + 7)) + (4 + 0) = 15
+    assert float(oracle.dot(a, b, "fold8")) == 15.0
+
+
+def test_chain_order_on_random_fp32_equals_the_python_chain():
+    """random 11-bit mantissas: every product has <= 22 bits and the float64 accumulation step of _fma_chain is exact"""
+    rng = np.random.default_rng(7)
+    for dim in (1, 3, 20, 100, 130):
+        a = (rng.integers(-1023, 1024, dim) * 2.0 ** rng.integers(-6, 6, dim)).astype(np.float32)
+        b = (rng.integers(-1023, 1024, dim) * 2.0 ** rng.integers(-6, 6, dim)).astype(np.float32)
+        assert oracle.dot(a, b, "chain") == _fma_chain(a, b, _chain_index_order(dim)), dim
+    differs = 0
+    for _ in range(50):
+        a = rng.standard_normal(100).astype(np.float32)
+        b = rng.standard_normal(100).astype(np.float32)
+        differs += oracle.dot(a, b, "chain") != oracle.dot(a, b, "lanes8")
+    assert differs >= 10   # the two orders are different functions on ordinary data
+
+
+def test_norm_tail_is_a_fused_multiply_add():
+    """dims that are no multiple of 8: the tail of the squared norm is fmaf(v, v, sum), as in the kernels' prep code,
+    whatever -ffp-contract says.  Lanes: 64^2 + 64^2 = 8192 (spacing 2^-10 there).  Tail v = 1 + 2^-12, v^2 = 1 + 2^-11 +
+    2^-24: fused, 8193 + 2^-11 + 2^-24 lies above the half-way point and rounds up to 8193 + 2^-10; with the product
+    rounded first (to 1 + 2^-11, ties to even) the sum is the exact half-way point and rounds to the even 8193."""
+    v = np.zeros((1, 9), dtype=np.float32)
+    v[0, 0] = v[0, 1] = 64.0
+    v[0, 8] = np.float32(1 + 2.0 ** -12)
+    assert oracle.compute_norms(v)[0] == np.float32(8193 + 2.0 ** -10)
+    assert np.float32(np.float32(v[0, 8] * v[0, 8]) + np.float32(8192)) == np.float32(8193)  # the unfused tail differs
+
+
+def test_ivf_oracle_orders_agree_on_integer_centroids_and_name_the_scan_order():
+    rng = np.random.default_rng(3)
+    base = rng.integers(0, 219, size=(3000, 128)).astype(np.float32)
+    q = rng.integers(0, 219, size=(20, 128)).astype(np.float32)
+    nlist = 24
+    cents = base[rng.choice(len(base), nlist, replace=False)].copy()
+    d = (base ** 2).sum(1)[:, None] - 2 * base @ cents.T + (cents ** 2).sum(1)[None]
+    assign = d.argmin(1)
+    order = np.argsort(assign, kind="stable").astype(np.int32)
+    off = np.zeros(nlist + 1, dtype=np.int32)
+    off[1:] = np.cumsum(np.bincount(assign, minlength=nlist))
+    want = oracle.ivf_search(base[order], off, order, cents, q, 5, 4, return_probes=True)
+    for kw in ({"dot_order": "chain"}, {"dot_order": "chain", "scan_order": "fold8"}, {"dot_order": "lanes8"}):
+        got = oracle.ivf_search(base[order], off, order, cents, q, 5, 4, return_probes=True, **kw)
+        assert all(np.array_equal(np.asarray(x), np.asarray(y)) for x, y in zip(got, want)), kw
+    got = oracle.ivf_search(base[order], off, order, cents, q, 5, 4, dot_order="chain", return_coarse=True)
+    assert got[4].shape == (20, 4) and (np.diff(got[4], axis=1) >= 0).all()
+    ex = oracle.exact_int_dists(q, cents).astype(np.float32)
+    assert np.array_equal(np.take_along_axis(ex, got[3].astype(np.int64), 1), got[4])
