@@ -183,6 +183,7 @@ def lib():
         "vs_index_dim": (i32, [vp]),
         "vs_index_nlist": (i32, [vp]),
         "vs_f32_filter_bound": (C.c_float, [C.c_double] * 6),
+        "vs_bf_filter_image_read": (i32, [vp, i64, i64, vp]),
         "vs_destroy": (None, [vp]),
     }
     for name, (res, args) in sig.items():
@@ -384,6 +385,12 @@ class BruteForceIndex(_Index):
         _check(lib().vs_bf_create_nd_u8(_p(base), self.n, self.d, device, id_offset, C.byref(self._h)))
         self.d = self.getDim()
         return self
+
+    def filter_image(self, row0: int, n: int) -> np.ndarray:
+        """Rows [row0, row0 + n) of the prefilter's bf16 row image as uint16 [n, 128] (vs_bf_filter_image_read)."""
+        out = np.empty((n, 128), dtype=np.uint16)
+        _check(lib().vs_bf_filter_image_read(self._h, row0, n, _p(out)))
+        return out
 
     def search(self, queries, k: int, timing: Timing | None = None):
         q = _f32c(queries).reshape(-1, self.d)

@@ -107,10 +107,12 @@ struct vs_index {
 
     vs::DevBuf<float> d_vecs;   // [n_rows + 64][128] (general index: [n_rows + 64][dim_p])
     vs::DevBuf<float> d_norm;   // [n_rows + 64]
-    // the bf16 prefilter of the fp32 streaming scan (scan_f32f_kernel): shard constants, and whether every row is well
-    // scaled (otherwise the index keeps scan_f32s_kernel)
+    // the bf16 prefilter of the fp32 streaming scan (scan_f32f_kernel): shard constants, whether every row is well
+    // scaled (otherwise the index keeps scan_f32s_kernel), and the rows once more as bf16 in A-fragment order, which is
+    // what that kernel sweeps (launch_row_filter_image; present exactly when filter_ok: +256 bytes per row)
     vs::FilterStats fstats{};
     bool filter_ok = false;
+    vs::DevBuf<uint16_t> d_img;  // [n_rows + 64][128], spare rows zero
     // int8 data path: only when every base value is an integer in [0, 255]
     vs::DevBuf<int8_t> d_vecs_u8;   // [n_rows][128] bytes (x - 128)
     vs::DevBuf<int32_t> d_rterm;    // [n_rows + 64] ||b||^2 - 256 * sum(b - 128)
@@ -415,6 +417,8 @@ int alloc_scratch(vs_index* h) {
     return h->stream.create();
 }
 
+bool f32_filter_enabled();  // VSEARCH_F32_FILTER != 0 (below)
+
 // upload `rows x dim` floats in chunks through the default pageable path and compute norms
 int upload_vectors(vs_index* h, const float* host, int64_t rows) {
     int rc;
@@ -437,11 +441,20 @@ int upload_vectors(vs_index* h, const float* host, int64_t rows) {
     if (rows > 0) {
         HIPCHK(hipMemcpy(h->d_vecs, host, (size_t)rows * vs::kDim * sizeof(float), hipMemcpyHostToDevice));
         HIPCHK(vs::launch_row_sqnorm(h->d_vecs, rows, vs::kDim, h->d_norm, nullptr));
-        if (h->kind == 0) {  // brute force: the bf16 prefilter's shard constants
+        if (h->kind == 0) {  // brute force: the bf16 prefilter's shard constants and row image, in one pass
             vs::DevBuf<unsigned long long> st;
             if ((rc = st.alloc(4))) return rc;
             HIPCHK(hipMemset(st, 0, 4 * sizeof(unsigned long long)));
-            HIPCHK(vs::launch_row_filter_stats(h->d_vecs, rows, st, nullptr));
+            // the image is an accelerator, not a requirement: without the memory for it the index keeps scan_f32s_kernel
+            // (and only a shard that the seeded streaming launches take can use it: bf_launch's tiles_total test)
+            const bool want_img = f32_filter_enabled() && (rows + vs::kTileRows - 1) / vs::kTileRows >= 2 * vs::kSeedWaves;
+            bool have_img = want_img && h->d_img.alloc(((size_t)rows + vs::kScanPadRows) * vs::kDim) == VS_OK;
+            if (want_img && !have_img) {
+                (void)hipGetLastError();
+                vs::set_error("");
+            }
+            if (have_img) HIPCHK(hipMemset(h->d_img + (size_t)rows * vs::kDim, 0, (size_t)vs::kScanPadRows * vs::kDim * sizeof(uint16_t)));
+            HIPCHK(vs::launch_row_filter_image(h->d_vecs, rows, st, have_img ? h->d_img.get() : nullptr, nullptr));
             unsigned long long v[4];
             HIPCHK(hipMemcpy(v, st, sizeof(v), hipMemcpyDeviceToHost));
             double m[3];
@@ -449,7 +462,8 @@ int upload_vectors(vs_index* h, const float* host, int64_t rows) {
             h->fstats.bmax = sqrt(m[0]);
             h->fstats.emax = sqrt(m[1]);
             h->fstats.bpmax = sqrt(m[2]);
-            h->filter_ok = v[3] == 0 && std::isfinite(m[0]) && std::isfinite(m[2]);
+            h->filter_ok = have_img && v[3] == 0 && std::isfinite(m[0]) && std::isfinite(m[2]);
+            if (!h->filter_ok) h->d_img.reset();  // (the copy above has waited for the kernel)
         }
         HIPCHK(hipDeviceSynchronize());
     }
@@ -596,6 +610,7 @@ int g_f32_filter = [] {
     const char* e = getenv("VSEARCH_F32_FILTER");
     return e ? atoi(e) : 1;
 }();
+bool f32_filter_enabled() { return g_f32_filter != 0; }
 
 // tuning knob (VSEARCH_STREAM=0): seeded launches use the per-batch scan kernels (lane lists + workgroup merge) instead of
 // the streaming scans
@@ -871,6 +886,7 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
             if (f32_filter) {  // one sweep over the rows serves all nb batches (batches_per_pass does not apply)
                 sp.qbf = L.qbf;
                 sp.qbound = L.qbound;
+                sp.img = h->d_img;
             }
             HIPCHK(vs::launch_scan_f32_stream(sp, sgrid, s));
             prof_end(h, 0, s);
@@ -1801,6 +1817,16 @@ int64_t vs_index_rows(const vs_index* h) { return h ? h->n_total : 0; }
 int vs_index_dim(const vs_index* h) { return h ? h->dim : 0; }
 float vs_f32_filter_bound(double eq, double nq, double nqp, double bmax, double emax, double bpmax) {
     return vs::filter_bound(eq, nq, nqp, vs::FilterStats{bmax, emax, bpmax});
+}
+int vs_bf_filter_image_read(const vs_index* h, int64_t row0, int64_t n, uint16_t* dst) {
+    if (!h || !dst || !h->filter_ok || !h->d_img || row0 < 0 || n < 0 || row0 + n > h->n_rows + vs::kScanPadRows) {
+        set_error("vs_bf_filter_image_read: no image or rows out of range");
+        return VS_ERR_INVALID;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(dst, h->d_img + (size_t)row0 * vs::kDim, (size_t)n * vs::kDim * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return VS_OK;
 }
 int vs_index_nlist(const vs_index* h) { return h ? h->nlist : 0; }
 void vs_destroy(vs_index* h) {

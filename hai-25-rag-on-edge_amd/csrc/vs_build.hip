@@ -45,20 +45,35 @@ hipError_t launch_row_sqnorm_ld(const float* v, int64_t rows, int dim, int64_t l
     return hipGetLastError();
 }
 
-// Shard constants of the bf16 prefilter (FilterStats): 8 threads per row as above, in double (exact squares of the
-// rounding residuals, which in float could fall below the normal range), maxima by integer atomics on the bits of
-// non-negative doubles (their order is the integers' order).
+// Shard constants of the bf16 prefilter (FilterStats) and the rows' bf16 image for scan_f32f_kernel, in one pass over the
+// rows.  A workgroup takes 32 rows through LDS (whole 512-byte rows per load instruction; rows 136 floats apart, so that
+// the strided reads below spread over the banks).  The statistics keep the arithmetic they always had: 8 threads per
+// row, thread j over v[8 i + j] in double (exact squares of the rounding residuals, which in float could fall below the
+// normal range), a butterfly over the 8, maxima by integer atomics on the bits of non-negative doubles (their order is
+// the integers' order).  The image is written from the same tile, a 16-byte chunk per thread and store: chunk 4 s + g of
+// a row = bf16 of floats 32 s + 4 g .. + 3 and 32 s + 16 + 4 g .. + 3 (vs_kernels.h), rounded as the statistics assume.
 __device__ __forceinline__ bool filter_scaled(float x) {
     const float a = fabsf(x);
     return a == 0.f || (a >= (float)kFiltLo && a <= (float)kFiltHi);  // (false for inf and NaN)
 }
-__global__ __launch_bounds__(256) void row_filter_stats_kernel(const float* __restrict__ v, int64_t rows,
-                                                               unsigned long long* __restrict__ out) {
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t row = gid >> 3;
-    const int j = (int)(gid & 7);
-    const bool ok = row < rows;
-    const float* src = v + (ok ? row : 0) * kDim;
+constexpr int kImgBlockRows = 32;
+constexpr int kImgLd = kDim + 8;  // 8 lanes per row x 8 banks: the 8 rows of a wave's strided read meet 64 different banks
+__global__ __launch_bounds__(256) void row_filter_image_kernel(const float* __restrict__ v, int64_t rows,
+                                                               unsigned long long* __restrict__ out, uint16_t* __restrict__ img) {
+    __shared__ __attribute__((aligned(16))) float tile[kImgBlockRows * kImgLd];
+    const int tid = threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * kImgBlockRows;
+#pragma unroll
+    for (int m = 0; m < kImgBlockRows * (kDim / 4) / 256; ++m) {
+        const int idx = tid + 256 * m, rr = idx >> 5, c4 = idx & 31;
+        float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row0 + rr < rows) x = *reinterpret_cast<const float4*>(v + (row0 + rr) * kDim + 4 * c4);
+        *reinterpret_cast<float4*>(tile + rr * kImgLd + 4 * c4) = x;
+    }
+    __syncthreads();
+    const int j = tid & 7;
+    const bool ok = row0 + (tid >> 3) < rows;
+    const float* src = tile + (tid >> 3) * kImgLd;
     double n2 = 0.0, e2 = 0.0, p2 = 0.0;
     bool bad = false;
     for (int i = 0; i < kDim; i += 8) {
@@ -83,13 +98,26 @@ __global__ __launch_bounds__(256) void row_filter_stats_kernel(const float* __re
         atomicMax(out + 2, (unsigned long long)__double_as_longlong(p2));
     }
     if (any_bad && (threadIdx.x & 63) == 0) atomicMax(out + 3, 1ull);
+    if (!img) return;
+#pragma unroll
+    for (int m = 0; m < kImgBlockRows * 16 / 256; ++m) {
+        const int c = tid + 256 * m, rr = c >> 4, ch = c & 15;
+        if (row0 + rr >= rows) continue;
+        const float* lo = tile + rr * kImgLd + 32 * (ch >> 2) + 4 * (ch & 3);
+        unsigned w[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float x0 = lo[16 * (e >> 1) + 2 * (e & 1)], x1 = lo[16 * (e >> 1) + 2 * (e & 1) + 1];
+            w[e] = (unsigned)__builtin_bit_cast(uint16_t, (__bf16)x0) | ((unsigned)__builtin_bit_cast(uint16_t, (__bf16)x1) << 16);
+        }
+        *reinterpret_cast<uint4*>(img + (row0 + rr) * kDim + 8 * ch) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
 }
 
-hipError_t launch_row_filter_stats(const float* v, int64_t rows, unsigned long long* out, hipStream_t s) {
+hipError_t launch_row_filter_image(const float* v, int64_t rows, unsigned long long* out, uint16_t* img, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
-    const int64_t threads = rows * 8;
-    const int grid = (int)((threads + 255) / 256);
-    hipLaunchKernelGGL(row_filter_stats_kernel, dim3(grid), dim3(256), 0, s, v, rows, out);
+    const int grid = (int)((rows + kImgBlockRows - 1) / kImgBlockRows);
+    hipLaunchKernelGGL(row_filter_image_kernel, dim3(grid), dim3(256), 0, s, v, rows, out, img);
     return hipGetLastError();
 }
 

@@ -100,7 +100,7 @@ constexpr double kFiltG32 = 128.0 / 16777216.0 / (1.0 - 128.0 / 16777216.0);
 constexpr double kFiltG16 = 128.0 / 4194304.0 / (1.0 - 128.0 / 4194304.0);
 constexpr double kFiltLo = 8.673617379884035e-19;  // 2^-60
 constexpr double kFiltHi = 1152921504606846976.0;  // 2^60
-struct FilterStats {     // per shard, from launch_row_filter_stats (index creation)
+struct FilterStats {     // per shard, from launch_row_filter_image (index creation)
     double bmax;         // max ||b||
     double emax;         // max ||b - bf16(b)||
     double bpmax;        // max ||bf16(b)||
@@ -228,9 +228,10 @@ struct StreamParams {
     CandSink sink;
     int batches_per_pass;    // scan_f32s_kernel: 1 (HBM bound) or 2 (two batches share a pass over the rows: MFMA bound)
     // the bf16 prefilter (scan_f32f_kernel: one sweep over the rows for all n_batches <= 32) instead, when set:
-    // SeedParams::qbf / qbound
+    // SeedParams::qbf / qbound, and the rows' bf16 image (launch_row_filter_image)
     const uint16_t* qbf;
     const float* qbound;
+    const uint16_t* img;     // [n_rows + 64][128] bf16
 };
 hipError_t launch_scan_f32_stream(const StreamParams& p, int grid, hipStream_t s);
 
@@ -335,8 +336,11 @@ constexpr int kKppBlockRows = 1024;
 hipError_t launch_row_sqnorm(const float* v, int64_t rows, int dim, float* out, hipStream_t s);
 hipError_t launch_row_sqnorm_ld(const float* v, int64_t rows, int dim, int64_t ld, float* out, hipStream_t s);  // rows ld floats apart
 // shard constants of the bf16 prefilter: out[0..2] = max of ||b||^2, ||b - bf16(b)||^2, ||bf16(b)||^2 as double bits,
-// out[3] = 1 when a row is not well scaled (FilterStats); out must be zeroed before
-hipError_t launch_row_filter_stats(const float* v, int64_t rows, unsigned long long* out, hipStream_t s);
+// out[3] = 1 when a row is not well scaled (FilterStats); out must be zeroed before.  The same pass writes the rows'
+// bf16 image for scan_f32f_kernel when img is given: img[row][8 (4 s + g) + 4 u + i] = bf16(v[row][32 s + 16 u + 4 g + i])
+// (round to nearest even, the rounding the statistics are taken from), s, g < 4, u < 2, i < 4: 16-byte chunk 4 s + g of
+// a row is lane (row & 15, g)'s A fragment of k-step s.  Rows [rows, rows + kScanPadRows) of img are the caller's to zero.
+hipError_t launch_row_filter_image(const float* v, int64_t rows, unsigned long long* out, uint16_t* img, hipStream_t s);
 
 // ---- IVF ----
 // Per query: the nprobe nearest centroids (ascending (dist, id)) out of a [B][ld] score matrix.

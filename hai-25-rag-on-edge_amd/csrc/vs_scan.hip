@@ -4,9 +4,9 @@
 //                          v_mfma_f32_16x16x4_f32 with the L2 epilogue (cpu_baseline.cpp:229-242), NB batches per pass
 //                          over the rows, candidates under seeded bounds to per-wave buffers; scan_i8w_kernel: the same
 //                          on exact u8 rows (v_mfma_i32_16x16x64_i8), four batches per pass.
-//   scan_f32f_kernel<CBW, D> : the same fp32 scan with the bulk test on v_mfma_f32_16x16x32_bf16 under a rigorous error
-//                          bound, one sweep over the rows for all batches of a launch through a ring shared by the
-//                          workgroup, survivors recomputed with scan_f32s_kernel's exact fp32 chain (default).
+//   scan_f32f_kernel<CBW, D, IP> : the same fp32 scan with the bulk test on v_mfma_f32_16x16x32_bf16 under a rigorous error
+//                          bound, one sweep over the index's bf16 row image for all batches of a launch through a ring
+//                          shared by the workgroup, survivors recomputed with scan_f32s_kernel's exact fp32 chain (default).
 //   scan_kernel          : per-batch scan with the top-k (cpu_baseline.cpp:127-153) fused in (short calls, fallback);
 //                          kModeStore = the B x N score matrix of QnnRunner::executeBatchRaw, kModeAssign = k-means
 //                          assignment for the index builder, kModeFilter = tie-resolver candidates.
@@ -1190,16 +1190,18 @@ __global__ __launch_bounds__(kScanThreads, NB == 1 ? 2 : 1) void scan_f32s_kerne
 // is recomputed with scan_f32s_kernel's exact fmaf chain when the wave bins its buffer (RecheckF32).  The candidate
 // lists then hold exactly the entries of scan_f32s_kernel, with the same bits.
 //
-// Organisation: ONE sweep of the workgroup's tiles (blockIdx.x + n G) serves every batch of the launch.  The launch's
-// 2 n_batches 16-query column blocks are dealt to the 8 waves (wave w: column blocks w + 8 h, h < CBW), whose bf16 B
-// operands stay in registers for the whole launch, and the 8 waves share one ring of D tile slots in LDS: every tile is
-// staged once per workgroup (wave w moves its w-th 1 KB piece), not once per wave.  One raw barrier per tile publishes
-// the slot (the handshake is described at the tile loop below).
+// The rows are not converted here: the sweep reads the bf16 image that index creation wrote beside the fp32 rows
+// (row_filter_image_kernel, vs_build.hip; StreamParams::img), already rounded and already in A-fragment order.  Row b of
+// the image is 256 bytes = 16 chunks of 16 bytes; chunk 4 s + g holds k = 32 s + 4 g + i (elements 0..3) and
+// 32 s + 16 + 4 g + i (4..7), i.e. what lane (r = b & 15, g) feeds k-step s of the MFMA -- the order of the query
+// fragments of launch_seed (SeedParams::qbf).  The fp32 rows are read by the exact recheck only.
 //
-// The A side keeps scan_f32s_kernel's slot image and fa[] addressing: k-step s of the bf16 MFMA pairs chunks a[2 s] and
-// a[2 s + 1], so lane (r, g) supplies row r, k = 32 s + 4 g + i (elements 0..3) and 32 s + 16 + 4 g + i (4..7); the
-// query fragments of launch_seed (SeedParams::qbf) use the same order.  At CBW = 8 (17..32 batches) the bf16 B operands
-// are 128 registers, at two waves per SIMD.
+// Organisation: ONE sweep of the workgroup's 64-row units (blockIdx.x + n G) serves every batch of the launch.  The
+// launch's 2 n_batches 16-query column blocks are dealt to the 8 waves (wave w: column blocks w + 8 h, h < CBW), whose
+// bf16 B operands stay in registers for the whole launch, and the 8 waves share one ring of D unit slots in LDS: a
+// unit (16 KB of rows + its 64 norms) is staged once per workgroup, wave w moving rows 4 w .. 4 w + 3 of each half.  One
+// raw barrier per unit publishes the slot (the handshake is described at the loop below).  At CBW = 8 (17..32 batches)
+// the bf16 B operands are 128 registers, at two waves per SIMD.
 // ------------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -1249,10 +1251,10 @@ struct RecheckF32 {
     }
 };
 
-// Ring depth (tile slots) of scan_f32f_kernel, and the cache policy of its row pieces (2 = nt: a launch reads every row
-// once, and the 512 MB of a SIFT-1M shard never fit a cache from one launch to the next).
+// Ring depth (64-row unit slots) of scan_f32f_kernel, and the cache policy of its row pieces (2 = nt: a launch reads
+// every row once, and the 256 MB image of a SIFT-1M shard never fits a cache from one launch to the next).
 #ifndef VS_F32F_DEPTH
-#define VS_F32F_DEPTH 8
+#define VS_F32F_DEPTH 4
 #endif
 #ifndef VS_F32F_CPOL
 #define VS_F32F_CPOL 2
@@ -1265,52 +1267,65 @@ struct RecheckF32 {
 #error "VS_F32F_CPOL: 0 (default policy) or 2 (nt)"
 #endif
 constexpr int kFilterDepth = VS_F32F_DEPTH;
+constexpr int kUnitRows = 64;                         // rows per ring slot: four 16-row tiles
+constexpr int kUnitTiles = kUnitRows / kTileRows;
+constexpr int kUnitRowBytes = kUnitRows * kDim * 2;   // 16 KB of bf16 rows
+constexpr int kUnitBytes = kUnitRowBytes + kUnitRows * 4;  // + the unit's 64 norms
+static_assert(kUnitRows <= kScanPadRows, "units are fetched unclamped: the image and the norms have kScanPadRows spare rows");
 
-// CBW = column blocks per wave (1, 2, 4 or 8: up to 4, 8, 16 or 32 batches), D = tile slots of the shared ring.
-template <int CBW, int D>
+// CBW = column blocks per wave (1, 2, 4 or 8: up to 4, 8, 16 or 32 batches), D = unit slots of the shared ring, IP = the
+// metric (the hot test differs: one kernel per metric keeps the loop free of branches on it).
+template <int CBW, int D, bool IP>
 __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const StreamParams p) {
     constexpr int TR = kTileRows;
-    constexpr int kTileVmem = 2;  // vector-memory instructions per wave and tile: its row piece + the norm piece
-    static_assert(TR * kDim * 4 == kScanWaves * 1024, "a tile is one 1 KB row piece per wave");
-    static_assert(D >= 3 && D * kSlotBytes <= kWideLds, "the ring: one slot being read, one being filled, >= 1 in flight");
-    static_assert((D - 2) * kTileVmem <= 63, "vmcnt is a 6-bit count");
+    constexpr int kUnitVmem = 3;  // vector-memory instructions per wave and unit: two row pieces + the norm piece
+    static_assert(kUnitRowBytes == 2 * kScanWaves * 1024, "a unit is two 1 KB row pieces per wave");
+    static_assert(D >= 3 && D * kUnitBytes <= 160 * 1024, "the ring: one slot being read, one being filled, >= 1 in flight");
+    static_assert((D - 2) * kUnitVmem <= 63, "vmcnt is a 6-bit count");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, g = lane >> 4;
-    const int tiles_total = (int)((p.n_rows + TR - 1) / TR);
+    const int units_total = (int)((p.n_rows + kUnitRows - 1) / kUnitRows);
     const int G = (int)gridDim.x;
-    const int T = (tiles_total - (int)blockIdx.x + G - 1) / G;  // tiles of this workgroup (grid <= tiles_total: T >= 1)
+    const int T = (units_total - (int)blockIdx.x + G - 1) / G;  // units of this workgroup (grid <= units_total: T >= 1)
     const int n_cb = 2 * p.n_batches;                           // column blocks of the launch (<= 8 CBW)
 
-    // LDS-DMA written as instructions (see scan_f32s_kernel): "scalar tile base + this lane's 32-bit offset".  Wave w
-    // moves rows 2 w, 2 w + 1 of a tile: lane l lands at row 2 w + (l >> 5), stored chunk l & 31 <- source chunk
-    // (l & 31) ^ row.  Every wave also moves the tile's 16 norms (lane l <- norm of row l & 15, one 64-byte line), so
-    // that all waves issue the same kTileVmem instructions per tile and one constant vmcnt serves them all; the eight
-    // copies write the same bytes, and fa_n reads the first 16 of them.  M0 is written in the statement that reads it,
-    // and restored there: the compiler neither knows nor preserves it around an asm statement.
-    const int row_in = 2 * wave + (lane >> 5);
-    const unsigned voff = (unsigned)(row_in * 512 + 16 * ((lane & 31) ^ row_in));
-    const unsigned voff_n = (unsigned)r * 4u;
+    // LDS-DMA written as instructions (see scan_f32s_kernel): "scalar unit base + this lane's 32-bit offset".  Wave w
+    // moves rows 4 w .. 4 w + 3 of each 32-row half of a unit: lane l lands at row b = 4 w + (l >> 4) (+ 32), stored
+    // chunk l & 15 <- source chunk (l & 15) ^ (b & 15); the second half is the same lane offsets 8 KB further on both
+    // sides.  Every wave also moves the unit's 64 norms (lane l <- norm of row l, one 256-byte piece), so that all waves
+    // issue the same kUnitVmem instructions per unit and one constant vmcnt serves them all; the eight copies write the
+    // same bytes.  M0 is written in the statement that reads it, and restored there: the compiler neither knows nor
+    // preserves it around an asm statement.
+    const int row_in = 4 * wave + (lane >> 4);
+    const unsigned voff = (unsigned)(row_in * 256 + 16 * ((lane & 15) ^ (row_in & 15)));
+    const unsigned voff_n = (unsigned)lane * 4u;
     const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
-    auto issue_tile = [&](int n, int slot) __attribute__((always_inline)) {  // tile n of the workgroup, kTileVmem instructions
-        // past the end (the last D - 1 prefetches): the workgroup's last tile once more, into a slot nobody reads -- in
+    auto issue_unit = [&](int n, int slot) __attribute__((always_inline)) {  // unit n of the workgroup, kUnitVmem instructions
+        // past the end (the last D - 1 prefetches): the workgroup's last unit once more, into a slot nobody reads -- in
         // bounds, and the count of the queue stays what the waits assume
-        const int64_t row0 = ((int64_t)blockIdx.x + (int64_t)min(n, T - 1) * G) * TR;
-        const char* tb = reinterpret_cast<const char*>(p.base) + row0 * (kDim * 4);
+        const int64_t row0 = ((int64_t)blockIdx.x + (int64_t)min(n, T - 1) * G) * kUnitRows;
+        const char* ub0 = reinterpret_cast<const char*>(p.img) + row0 * (kDim * 2);
+        const char* ub1 = ub0 + kUnitRowBytes / 2;
         const char* nb = reinterpret_cast<const char*>(p.bnorm + row0);
-        const unsigned dst = ring_lds + (unsigned)(slot * kSlotBytes) + (unsigned)wave * 1024u;
-        const unsigned dst_n = ring_lds + (unsigned)(slot * kSlotBytes + 8192);
+        const unsigned dst0 = ring_lds + (unsigned)(slot * kUnitBytes) + (unsigned)wave * 1024u;
+        const unsigned dst1 = dst0 + (unsigned)(kUnitRowBytes / 2);
+        const unsigned dst_n = ring_lds + (unsigned)(slot * kUnitBytes + kUnitRowBytes);
         unsigned keep;
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" VS_F32F_CPOL_ASM "\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(tb), "s"(dst) : "memory");
+                     : "=&s"(keep) : "v"(voff), "s"(ub0), "s"(dst0) : "memory");
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" VS_F32F_CPOL_ASM "\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(voff), "s"(ub1), "s"(dst1) : "memory");
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
                      : "=&s"(keep) : "v"(voff_n), "s"(nb), "s"(dst_n) : "memory");
     };
-    unsigned fa[8];
+    // this lane's fragment of k-step s of tile 0 of a slot (tile i: + 4096 i): row r, chunk (4 s + g) ^ r.  Rows are 256
+    // bytes = one bank row apart, and the 16 lanes of every ds_read_b128 lane group hit 16 different 16-byte slots
+    unsigned fa[4];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) fa[c] = (unsigned)(r * 512 + (((4 * c + g) ^ r) << 4));
-    const unsigned fa_n = (unsigned)(8192 + 16 * g);
+    for (int s = 0; s < 4; ++s) fa[s] = (unsigned)(r * 256 + (((4 * s + g) ^ r) << 4));
+    const unsigned fa_n = (unsigned)(kUnitRowBytes + 16 * g);  // norms of rows 4 g .. 4 g + 3 of tile 0 (tile i: + 64 i)
 
     // The wave's column blocks as bf16 B operands (qb[h][s], SeedParams::qbf), loaded once for the launch, and their
     // widened bounds.  The loads are inline asm so that the compiler puts no wait of its own in front of the operands'
@@ -1337,10 +1352,10 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
         asm volatile("global_load_dword %0, %1, off" : "=v"(tau[h]) : "v"(pt) : "memory");
         asm volatile("global_load_dword %0, %1, off" : "=v"(eb[h]) : "v"(pe) : "memory");
     }
-    // prologue: tiles 0 .. D - 2 into slots 0 .. D - 2
+    // prologue: units 0 .. D - 2 into slots 0 .. D - 2
 #pragma unroll
-    for (int s = 0; s < D - 1; ++s) issue_tile(s, s);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 2) * kTileVmem) : "memory");  // the operands (older than every DMA) are here
+    for (int s = 0; s < D - 1; ++s) issue_unit(s, s);
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 2) * kUnitVmem) : "memory");  // the operands (older than every DMA) and unit 0 are here
 #pragma unroll
     for (int h = 0; h < CBW; ++h) {
         asm volatile("" : "+v"(qb[h][0]), "+v"(qb[h][1]), "+v"(qb[h][2]), "+v"(qb[h][3]), "+v"(qn[h]), "+v"(tau[h]), "+v"(eb[h]) :: "memory");
@@ -1350,7 +1365,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
         // <= t (a float: RN, then one step up) and RN(bn - 2 S') <= t < next_up(t) =: thr'.  IP: S_fl > thr gives
         // S' > thr - E >= thr' := next_down(RN(thr - E)).  E = +inf (a query outside the well-scaled range) admits every row.
         const float inf = __builtin_inff();
-        if (!p.metric) {
+        if constexpr (!IP) {
             const float t = nextafterf(stream_l2_thr(tau[h], qn[h]) + 2.0f * eb[h], inf);
             thr[h] = live ? nextafterf(t, inf) : -inf;
         } else {
@@ -1361,76 +1376,62 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
     int4* wbuf = p.sink.wbuf + ((int64_t)blockIdx.x * kScanWaves + wave) * p.sink.wcap;
     int wbase = 0;  // wave-uniform fill of the private candidate buffer
 
-    // Step t (tile t in slot t % D, its fragments already in registers; tiles t + 1 .. t + D - 2 in flight on entry):
-    //   1. s_waitcnt vmcnt((D - 3) kTileVmem): this wave's pieces of tile t + 1 have landed; those of t + 2 .. t + D - 2
+    // Step t (unit t in slot t % D; the fragments of its tiles 0 and 1 already in registers; units t + 1 .. t + D - 2 in
+    // flight on entry):
+    //   1. s_waitcnt vmcnt((D - 3) kUnitVmem): this wave's pieces of unit t + 1 have landed; those of t + 2 .. t + D - 2
     //      stay in flight.  Candidate stores to wbuf count on vmcnt as well, but every one of them is younger than the
-    //      DMAs of the tile it follows: they can only make this wait retire more, never less, than tile t + 1.
-    //   2. raw s_barrier: every wave has passed step 1, so all 8 pieces and the norms of tile t + 1 are in LDS; and
-    //      every wave has finished step t - 1, whose fragment reads (of tile t) it waited for before its conversions,
-    //      so slot (t - 1) % D is free.  (__syncthreads() would add vmcnt(0) -- a drain of the ring -- through its fence.)
-    //   3. issue tile t + D - 1 into slot (t + D - 1) % D = (t - 1) % D;
-    //   4. convert tile t to bf16, read tile t + 1's fragments (their latency hides behind the MFMAs), then the MFMAs
-    //      and the test of tile t.
-    // The waves leave the barrier together, so a wave must not wait for LDS between it and its MFMAs: the fragments
-    // of a tile are read one step ahead, and the test of a column block runs beside the MFMAs of the next one.
-    // The slot index is a constant in the unrolled body, so the slot offset folds into the ds_read offsets.
-    f32x4 a[8], bn;
-    auto read_frags = [&](const int sl) __attribute__((always_inline)) {
-        const char* src = smem + sl * kSlotBytes;
+    //      DMAs of the unit it follows: they can only make this wait retire more, never less, than unit t + 1.
+    //   2. raw s_barrier: every wave has passed step 1, so all 16 row pieces and the norms of unit t + 1 are in LDS; and
+    //      every wave has finished step t - 1, whose last MFMAs consumed the last fragments read from unit t - 1 (an
+    //      MFMA issues only once its operands have arrived, and score_tile pins its last chain in front of the barrier;
+    //      the reads at the end of step t - 1 are of unit t), so slot (t - 1) % D is free.  (__syncthreads() would add
+    //      vmcnt(0) -- a drain of the ring -- through its fence.)
+    //   3. issue unit t + D - 1 into slot (t + D - 1) % D = (t - 1) % D;
+    //   4. the four tiles of unit t, alternating between two fragment sets: MFMAs and test of tile i, then the read of
+    //      the tile two ahead into the set just consumed -- tiles 2 and 3 of unit t, then tiles 0 and 1 of unit t + 1
+    //      (published by the barrier of this step).
+    // The waves leave the barrier together, so a wave must not wait for LDS between it and its MFMAs: every tile's
+    // fragments are read at least one tile (32 CBW / 8 MFMAs) ahead, and the test of a column block runs beside the MFMAs
+    // of the next one.  The slot index is a constant in the unrolled body, so slot and tile offsets fold into the
+    // ds_read offsets.
+    u32x4 a[2][4];
+    f32x4 bn[2];
+    auto read_frags = [&](const int set, const int sl, const int i) __attribute__((always_inline)) {
+        const char* src = smem + sl * kUnitBytes + i * (TR * kDim * 2);
 #pragma unroll
-        for (int c = 0; c < 8; ++c) a[c] = *reinterpret_cast<const f32x4*>(src + fa[c]);
-        bn = *reinterpret_cast<const f32x4*>(src + fa_n);
+        for (int s = 0; s < 4; ++s) a[set][s] = *reinterpret_cast<const u32x4*>(src + fa[s]);
+        bn[set] = *reinterpret_cast<const f32x4*>(smem + sl * kUnitBytes + fa_n + 64 * i);
     };
-    // tile 0 landed with the operands (the wait above): publish it, read it
+    // unit 0 landed with the operands (the wait above): publish it, read its first two tiles
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    read_frags(0);
-    auto step = [&](const int t, const int sl) __attribute__((always_inline)) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 3) * kTileVmem) : "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        issue_tile(t + D - 1, (sl + D - 1) % D);
-        bf16x8 ab[4];  // k-step s = chunks 2 s, 2 s + 1, rounded to nearest even (v_cvt_pk_bf16_f32)
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                ab[s][i] = (__bf16)a[2 * s][i];
-                ab[s][4 + i] = (__bf16)a[2 * s + 1][i];
-            }
-        const f32x4 bt = bn;
-        read_frags((sl + 1) % D);  // tile t + 1 (past the end: the re-read last tile, unused)
+    read_frags(0, 0, 0);
+    read_frags(1, 0, 1);
+    auto score_tile = [&](const int set, const int row_t) __attribute__((always_inline)) {  // row_t: this lane's first row, 16 tile + 4 g
+        const f32x4 bt = bn[set];
         auto mfma_cb = [&](const int h) __attribute__((always_inline)) -> f32x4 {
             f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < 4; ++s)
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[s], __builtin_bit_cast(bf16x8, qb[h][s]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a[set][s]), __builtin_bit_cast(bf16x8, qb[h][s]), acc, 0, 0, 0);
             return acc;
         };
-        // one fma and one compare per value, as in scan_f32s_kernel (a dead column block has thr = -inf / +inf); the
-        // verdicts as wave masks in scalar registers
+        // L2: one fma and one compare per value, as in scan_f32s_kernel; IP: one compare (a dead column block has
+        // thr = -inf / +inf); the verdicts as wave masks in scalar registers
         auto test_cb = [&](const int h, const f32x4 acc) __attribute__((always_inline)) {
             unsigned long long hit[4], hits = 0;
-            if (!p.metric) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    hit[j] = __ballot(fmaf(-2.0f, acc[j], bt[j]) < thr[h]);
-                    hits |= hit[j];
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    hit[j] = __ballot(acc[j] > thr[h]);  // -acc < tau, widened
-                    hits |= hit[j];
-                }
+            for (int j = 0; j < 4; ++j) {
+                if constexpr (!IP) hit[j] = __ballot(fmaf(-2.0f, acc[j], bt[j]) < thr[h]);
+                else hit[j] = __ballot(acc[j] > thr[h]);  // -acc < tau, widened
+                hits |= hit[j];
             }
             if (__builtin_expect(hits != 0, 0)) {  // rare: a few hundred rows per query per million
-                const int row_t = ((int)blockIdx.x + t * G) * TR + 4 * g;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (!hit[j]) continue;  // wave-uniform
                     const int row = row_t + j;
-                    const bool pass = ((hit[j] >> lane) & 1) && row < (int)p.n_rows;
+                    const bool pass = ((hit[j] >> lane) & 1) && row < (int)p.n_rows;  // (spare rows of the image score as zeros)
                     const unsigned long long mask = __ballot(pass);
                     if (mask) {
                         const int pos = wbase + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
@@ -1454,13 +1455,37 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
             acc = nxt;
         }
         test_cb(CBW - 1, acc);
+        // the tile's last chain has issued, so every fragment of this set has arrived: what follows this statement (the
+        // barrier behind which the set's slot is refilled) follows the set's LDS reads
+        asm volatile("" ::"v"(acc));
     };
-    for (int t0 = 0; t0 < T; t0 += D) {  // T is workgroup-uniform: every wave passes the same barriers
+    auto step = [&](const int t, const int sl) __attribute__((always_inline)) {
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 3) * kUnitVmem) : "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        issue_unit(t + D - 1, (sl + D - 1) % D);
+        const int row_u = ((int)blockIdx.x + t * G) * kUnitRows + 4 * g;
 #pragma unroll
-        for (int sl = 0; sl < D; ++sl) {
-            if (t0 + sl >= T) break;
-            step(t0 + sl, sl);
+        for (int i = 0; i < kUnitTiles; ++i) {
+            score_tile(i & 1, row_u + TR * i);
+            // two tiles ahead, into the set just consumed (past the end: the re-read last unit, unused)
+            if (i + 2 < kUnitTiles) read_frags(i & 1, sl, i + 2);
+            else read_frags(i & 1, (sl + 1) % D, i + 2 - kUnitTiles);
         }
+    };
+    // one turn of the ring per iteration, every slot a constant; T is workgroup-uniform: every wave passes the same barriers
+    static_assert(D <= 8, "the turn below is written out for up to 8 slots");
+    for (int t0 = 0; t0 < T; t0 += D) {
+        step(t0, 0);
+        if (t0 + 1 >= T) break;
+        step(t0 + 1, 1);
+        if (t0 + 2 >= T) break;
+        step(t0 + 2, 2);
+        if constexpr (D > 3) { if (t0 + 3 >= T) break; step(t0 + 3, 3); }
+        if constexpr (D > 4) { if (t0 + 4 >= T) break; step(t0 + 4, 4); }
+        if constexpr (D > 5) { if (t0 + 5 >= T) break; step(t0 + 5, 5); }
+        if constexpr (D > 6) { if (t0 + 6 >= T) break; step(t0 + 6, 6); }
+        if constexpr (D > 7) { if (t0 + 7 >= T) break; step(t0 + 7, 7); }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // retire the tail prefetches before the wave ends
     const RecheckF32 fix{p.base, p.bnorm, p.q, p.q_batch_stride, p.qnorm, p.tau0, p.metric, p.id_offset};
@@ -1469,15 +1494,16 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
 
 template <int CBW>
 static hipError_t launch_scan_f32f(const StreamParams& p, int grid, hipStream_t s) {
-    constexpr int kLds = kFilterDepth * kSlotBytes;
-    auto kfn = scan_f32f_kernel<CBW, kFilterDepth>;
-    static bool attr_set[64] = {};
+    constexpr int kLds = kFilterDepth * kUnitBytes;
+    auto kfn = p.metric ? scan_f32f_kernel<CBW, kFilterDepth, true> : scan_f32f_kernel<CBW, kFilterDepth, false>;
+    grid = (int)std::max<int64_t>(1, std::min<int64_t>(grid, (p.n_rows + kUnitRows - 1) / kUnitRows));  // every workgroup owns a unit
+    static bool attr_set[64][2] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
+    if (!attr_set[dev][p.metric ? 1 : 0]) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
         if (e != hipSuccess) return e;
-        attr_set[dev] = true;
+        attr_set[dev][p.metric ? 1 : 0] = true;
     }
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(kScanThreads), kLds, s, p);
     return hipGetLastError();
@@ -1489,7 +1515,7 @@ hipError_t launch_scan_f32_stream(const StreamParams& p, int grid, hipStream_t s
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     if (p.qbf) {  // the bf16 prefilter: column blocks per wave for the launch's 2 n_batches column blocks
         const int cbw = (2 * p.n_batches + kScanWaves - 1) / kScanWaves;
-        if (p.n_batches < 1 || cbw > 8) return hipErrorInvalidValue;
+        if (p.n_batches < 1 || cbw > 8 || !p.img) return hipErrorInvalidValue;
         return cbw == 1 ? launch_scan_f32f<1>(p, grid, s) : cbw == 2 ? launch_scan_f32f<2>(p, grid, s)
              : cbw <= 4 ? launch_scan_f32f<4>(p, grid, s) : launch_scan_f32f<8>(p, grid, s);
     }

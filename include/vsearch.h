@@ -506,6 +506,11 @@ VS_API int vs_index_nlist(const vs_index* h);     /* 0 for brute force */
  * query with ||q|| = nq, ||bf16(q)|| = nqp, ||q - bf16(q)|| = eq against a shard with max ||b|| = bmax, max ||b - bf16(b)||
  * = emax, max ||bf16(b)|| = bpmax, as the library computes it (rounded up to float).  Pure host arithmetic. */
 VS_API float vs_f32_filter_bound(double eq, double nq, double nqp, double bmax, double emax, double bpmax);
+/* Diagnostic read-back of the bf16 row image of the prefilter: rows [row0, row0 + n) of the image, 128
+ * uint16 each, to dst (host memory); the 64 zero spare rows behind the index's last row can be read as well.
+ * VS_ERR_INVALID when the index has no image (not a 128-d brute-force index, too small for the prefilter, ill-scaled
+ * rows, VSEARCH_F32_FILTER=0) or the range leaves it. */
+VS_API int vs_bf_filter_image_read(const vs_index* h, int64_t row0, int64_t n, uint16_t* dst);
 VS_API void vs_destroy(vs_index* h);
 
 #ifdef __cplusplus
