@@ -141,6 +141,9 @@ def lib():
         "vs_ivf_load": (i32, [C.c_char_p, i32, i32, i32, C.POINTER(vp)]),
         "vs_ivf_create": (i32, [vp, i64, i32, vp, i32, vp, vp, i32, i32, i32, C.POINTER(vp)]),
         "vs_ivf_build": (i32, [vp, i64, i32, i32, i32, C.c_double, C.c_uint64, i32, vp, vp, C.POINTER(i32)]),
+        "vs_ivf_build_nd": (i32, [vp, i64, i32, i32, i32, C.c_double, C.c_uint64, i32, vp, vp, C.POINTER(i32)]),
+        "vs_ivf_build_index_nd": (i32, [vp, i64, i32, i32, i32, C.c_double, C.c_uint64, i32, C.POINTER(vp), C.POINTER(i32)]),
+        "vs_ivf_build_last_assign_ms": (C.c_double, []),
         "vs_ivf_clamp_nlist": (i32, [i64, i32]),
         "vs_ivf_layout": (i32, [vp, i64, i32, vp, vp]),
         "vs_ivf_build_index": (i32, [vp, i64, i32, i32, i32, C.c_double, C.c_uint64, i32, C.POINTER(vp), C.POINTER(i32)]),
@@ -556,13 +559,13 @@ class IVFIndex(_Index):
     @classmethod
     def build(cls, base, n_clusters: int, max_iter: int = 100, tol: float = 1e-4, seed: int = 42, device: int = 0):
         """build_ivf_index_reordered (create_ivf_model_reordered.py:82-177) entirely inside the library
-        (vs_ivf_build_index); returns (index, n_iter).  `index.save(dir)` writes the reference's directory."""
+        (vs_ivf_build_index; vs_ivf_build_index_nd at a dimension other than 128); returns (index, n_iter).  `index.save(dir)` writes the reference's directory."""
         base = _f32c(base)
         self = cls.__new__(cls)
         _Index.__init__(self)
         it = C.c_int(0)
-        _check(lib().vs_ivf_build_index(_p(base), base.shape[0], base.shape[1], n_clusters, max_iter, tol, seed, device,
-                                        C.byref(self._h), C.byref(it)))
+        build = lib().vs_ivf_build_index if base.shape[1] == 128 else lib().vs_ivf_build_index_nd
+        _check(build(_p(base), base.shape[0], base.shape[1], n_clusters, max_iter, tol, seed, device, C.byref(self._h), C.byref(it)))
         self.d = self.getDim()
         return self, int(it.value)
 
@@ -688,6 +691,11 @@ def ivf_layout_from_assignment(vectors: np.ndarray, cluster_ids: np.ndarray, n_c
     return np.ascontiguousarray(vectors[order], dtype=np.float32), offsets, order
 
 
+def _kmeans_fn(dim: int):
+    """vs_ivf_build at 128-d, vs_ivf_build_nd (the builder at any dimension from 1 to 2048) otherwise."""
+    return lib().vs_ivf_build if dim == 128 else lib().vs_ivf_build_nd
+
+
 def ivf_build(base, n_clusters: int, max_iter: int = 100, tol: float = 1e-4, seed: int = 42, device: int = 0):
     """build_ivf_index_reordered (create_ivf_model_reordered.py:82-177) on the GPU: k-means (vs_ivf_build),
     then the reordered layout.  Returns (vectors_reordered, cluster_offsets, reorder_to_original, centroids, n_iter)."""
@@ -697,19 +705,19 @@ def ivf_build(base, n_clusters: int, max_iter: int = 100, tol: float = 1e-4, see
     cents = np.empty((n_clusters, d), dtype=np.float32)
     assign = np.empty(n, dtype=np.int32)
     it = C.c_int(0)
-    _check(lib().vs_ivf_build(_p(base), n, d, n_clusters, max_iter, tol, seed, device, _p(cents), _p(assign), C.byref(it)))
+    _check(_kmeans_fn(d)(_p(base), n, d, n_clusters, max_iter, tol, seed, device, _p(cents), _p(assign), C.byref(it)))
     vr, off, r2o = ivf_layout_from_assignment(base, assign, n_clusters)
     return vr, off, r2o, cents, int(it.value)
 
 
 def ivf_kmeans(base, nlist: int, max_iter: int, tol: float, seed: int, device: int = 0):
-    """vs_ivf_build as it is: no nlist clamp, no layout.  Returns (centroids [nlist x dim], assign [n_rows], n_iter)."""
+    """vs_ivf_build (vs_ivf_build_nd at dim != 128) as it is: no nlist clamp, no layout.  Returns (centroids [nlist x dim], assign [n_rows], n_iter)."""
     base = _f32c(base)
     n, d = base.shape
     cents = np.empty((nlist, d), dtype=np.float32)
     assign = np.empty(n, dtype=np.int32)
     it = C.c_int(0)
-    _check(lib().vs_ivf_build(_p(base), n, d, nlist, max_iter, tol, seed, device, _p(cents), _p(assign), C.byref(it)))
+    _check(_kmeans_fn(d)(_p(base), n, d, nlist, max_iter, tol, seed, device, _p(cents), _p(assign), C.byref(it)))
     return cents, assign, int(it.value)
 
 

@@ -2417,80 +2417,74 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
 
 // GPU index builder: Lloyd k-means on the scan kernel (assignment = the brute-force MFMA scan with the
 // centroids as "queries", 32 per pass) + deterministic fixed-point update.
-static int ivf_build_impl(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol, uint64_t seed,
-                          int device, float* centroids_out, int32_t* assign_out, int* iters_done);
-int vs_ivf_build(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol, uint64_t seed,
-                 int device, float* centroids_out, int32_t* assign_out, int* iters_done) {
-    return guarded([&]() -> int {
-        return ivf_build_impl(base_host, n_rows, dim, nlist, max_iter, tol, seed, device, centroids_out, assign_out, iters_done);
-    });
-}
-static int ivf_build_impl(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol, uint64_t seed,
-                          int device, float* centroids_out, int32_t* assign_out, int* iters_done) {
+//
+// The argument checks and the one host pass of both builders, before any device work: every value finite, max |x| inside
+// the range of the fixed-point cluster sums (kmeans_accum_kernel: 64-bit sums of rint(x * 2^20) wrap once a sum leaves
+// +-2^63), and the per-feature variance of sklearn's stopping rule: sum of squared centre shifts <= tol * mean
+// per-feature variance.  dim_lo .. dim_hi: what the entry point compiles (below dim_lo, for the general builder: invalid).
+static int ivf_build_checks(const char* who, const float* base_host, int64_t n_rows, int dim, int dim_lo, int dim_hi, int nlist,
+                            int max_iter, double tol, const float* centroids_out, const int32_t* assign_out, double& tol_abs) {
     if (!base_host || !centroids_out || !assign_out || n_rows <= 0 || nlist <= 0 || nlist > n_rows || max_iter < 0) {
-        set_error("vs_ivf_build: bad arguments");
+        set_error(std::string(who) + ": bad arguments");
         return VS_ERR_INVALID;
     }
-    if (dim != vs::kDim) {
-        set_error("only dim == 128 is compiled in");
+    if (dim_lo != dim_hi && dim < dim_lo) {
+        set_error(std::string(who) + ": dim must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (dim < dim_lo || dim > dim_hi) {
+        set_error(dim_lo == dim_hi ? std::string("only dim == 128 is compiled in")
+                                   : std::string(who) + ": dim " + std::to_string(dim) + " is above the largest supported, 2048");
         return VS_ERR_UNSUPPORTED;
     }
-    // One host pass before any device work: every value finite, max |x| inside the range of the fixed-point cluster
-    // sums (kmeans_accum_kernel: 64-bit sums of rint(x * 2^20) wrap once a sum leaves +-2^63), and the per-feature
-    // variance of sklearn's stopping rule: sum of squared centre shifts <= tol * mean per-feature variance.
-    double tol_abs = 0.0;
-    {
-        std::vector<double> sum(dim, 0.0), sq(dim, 0.0);
-        double amax = 0.0;
-        bool finite = true;
-        for (int64_t i = 0; i < n_rows; ++i)
-            for (int t = 0; t < dim; ++t) {
-                const double v = base_host[i * dim + t];
-                const double a = std::fabs(v);
-                if (!(a <= 3.4028234663852886e38)) finite = false;  // inf or NaN
-                else if (a > amax) amax = a;
-                sum[t] += v;
-                sq[t] += v * v;
-            }
-        if (!finite) {
-            set_error("vs_ivf_build: the base holds a NaN or an infinity");
-            return VS_ERR_INVALID;
+    tol_abs = 0.0;
+    std::vector<double> sum(dim, 0.0), sq(dim, 0.0);
+    double amax = 0.0;
+    bool finite = true;
+    for (int64_t i = 0; i < n_rows; ++i)
+        for (int t = 0; t < dim; ++t) {
+            const double v = base_host[i * dim + t];
+            const double a = std::fabs(v);
+            if (!(a <= 3.4028234663852886e38)) finite = false;  // inf or NaN
+            else if (a > amax) amax = a;
+            sum[t] += v;
+            sq[t] += v * v;
         }
-        // |sum of n quantised values| <= n * (max|x| * 2^20 + 1/2) must stay below 2^63
-        if ((double)n_rows * (amax + 0x1p-21) >= 0x1p43) {
-            set_error("vs_ivf_build: n_rows * max|x| = " + std::to_string((double)n_rows * amax) +
-                      " is outside the fixed-point range of the k-means update (must be < 2^43)");
-            return VS_ERR_INVALID;
-        }
-        if (tol > 0) {
-            double mv = 0;
-            for (int t = 0; t < dim; ++t) {
-                const double m = sum[t] / n_rows;
-                mv += sq[t] / n_rows - m * m;
-            }
-            tol_abs = tol * mv / dim;
-        }
+    if (!finite) {
+        set_error(std::string(who) + ": the base holds a NaN or an infinity");
+        return VS_ERR_INVALID;
     }
-    int rc = check_device(device);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device));
-    const int num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    vs::DevBuf<float> d_x, d_norm, d_cents, d_best_d;
-    vs::DevBuf<int32_t> d_best_i, d_counts;
-    vs::DevBuf<unsigned long long> d_acc;
-    vs::DevBuf<double> d_shift;
-    const int nlist_pad = (nlist + 31) & ~31;
-    if ((rc = d_x.alloc(((size_t)n_rows + vs::kScanPadRows) * dim))) return rc;
-    HIPCHK(hipMemset(d_x + (size_t)n_rows * dim, 0, (size_t)vs::kScanPadRows * dim * sizeof(float)));
-    if ((rc = d_norm.alloc((size_t)n_rows + 64)) || (rc = d_cents.alloc((size_t)nlist_pad * dim)) || (rc = d_best_d.alloc((size_t)n_rows)) ||
-        (rc = d_best_i.alloc((size_t)n_rows)) || (rc = d_counts.alloc((size_t)nlist)) || (rc = d_acc.alloc((size_t)nlist * dim)) ||
-        (rc = d_shift.alloc((size_t)nlist)))
-        return rc;
-    HIPCHK(hipMemcpy(d_x, base_host, (size_t)n_rows * dim * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(d_norm, 0, ((size_t)n_rows + 64) * sizeof(float)));
-    HIPCHK(vs::launch_row_sqnorm(d_x, n_rows, dim, d_norm, nullptr));
+    // |sum of n quantised values| <= n * (max|x| * 2^20 + 1/2) must stay below 2^63
+    if ((double)n_rows * (amax + 0x1p-21) >= 0x1p43) {
+        set_error(std::string(who) + ": n_rows * max|x| = " + std::to_string((double)n_rows * amax) +
+                  " is outside the fixed-point range of the k-means update (must be < 2^43)");
+        return VS_ERR_INVALID;
+    }
+    if (tol > 0) {
+        double mv = 0;
+        for (int t = 0; t < dim; ++t) {
+            const double m = sum[t] / n_rows;
+            mv += sq[t] / n_rows - m * m;
+        }
+        tol_abs = tol * mv / dim;
+    }
+    return VS_OK;
+}
+
+// What both builders do once the rows [n_rows][ld], their norms and the zeroed centroids [nlist_pad][dim] are on the device:
+// the seeding stream and the initial centres, the Lloyd loop with its stopping rule, the final assignment, the outputs.
+// The launches are the caller's: kpp_step(c, u, n_blocks, d_bsum) = one D^2 step, assign_pass() = best_d / best_i of every
+// row against the current centroids, update() = one fixed-point update with the shifts in d_shift.
+static thread_local double g_build_assign_ms = 0.0;  // device time of the calling thread's last assignment pass
+double vs_ivf_build_last_assign_ms(void) { return g_build_assign_ms; }
+
+extern "C++" {
+template <class KppStep, class AssignPass, class Update>
+static int ivf_build_run(const float* base_host, int64_t n_rows, int dim, int64_t ld, int nlist, int nlist_pad, int max_iter,
+                         double tol_abs, uint64_t seed, const float* d_x, float* d_cents, float* d_best_d, const int32_t* d_best_i,
+                         const double* d_shift, KppStep kpp_step, AssignPass assign_pass, Update update, float* centroids_out,
+                         int32_t* assign_out, int* iters_done) {
+    int rc;
     // initial centroids: k-means++ (D^2 sampling), sklearn's default for the reference's KMeans(random_state=42, n_init=1),
     // create_ivf_model_reordered.py:97-103.  sklearn's RNG stream and its greedy multi-trial variant are not
     // reproduced (VSEARCH_KMEANS_INIT=random: nlist distinct random rows instead).
@@ -2520,57 +2514,22 @@ static int ivf_build_impl(const float* base_host, int64_t n_rows, int dim, int n
             vs::DevBuf<double> d_bsum;
             if ((rc = d_bsum.alloc((size_t)n_blocks))) return rc;
             const int64_t first = (int64_t)(next() % (uint64_t)n_rows);
-            hipError_t e = hipMemcpy(d_cents, d_x + first * dim, (size_t)dim * sizeof(float), hipMemcpyDeviceToDevice);
+            hipError_t e = hipMemcpy(d_cents, d_x + first * ld, (size_t)dim * sizeof(float), hipMemcpyDeviceToDevice);
             // d_best_d doubles as the running min squared distance (+inf to start with)
-            if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_best_d.get()), 0x7f800000, (size_t)n_rows, nullptr);
+            if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_best_d), 0x7f800000, (size_t)n_rows, nullptr);
             for (int c = 1; c < nlist && e == hipSuccess; ++c) {
                 const double u = (double)(next() >> 11) * (1.0 / 9007199254740992.0);  // [0, 1)
-                e = vs::launch_kpp_step(d_x, d_norm, n_rows, d_cents, c, d_best_d, d_bsum, n_blocks, u, nullptr);
+                e = kpp_step(c, u, n_blocks, d_bsum.get());
             }
             if (e == hipSuccess) e = hipDeviceSynchronize();
             HIPCHK(e);
         }
     }
-    int grid, tp;
-    scan_geometry(n_rows, num_cus, grid, tp);
-    auto assign_pass = [&]() -> hipError_t {
-        hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_best_d.get()), 0x7f800000, (size_t)n_rows, nullptr);
-        if (e != hipSuccess) return e;
-        e = hipMemsetAsync(d_best_i, 0xff, (size_t)n_rows * sizeof(int32_t), nullptr);
-        if (e != hipSuccess) return e;
-        vs::ScanParams p{};
-        p.base = d_x;
-        p.bnorm = d_norm;
-        p.metric = 0;
-        p.row_begin = 0;
-        p.row_end = n_rows;
-        p.tiles_per_wg = tp;
-        p.best_d = d_best_d;
-        p.best_i = d_best_i;
-        p.q_batch_stride = (int64_t)32 * dim;
-        const int full = nlist / 32, rem = nlist % 32;
-        if (full) {
-            p.q = d_cents;
-            p.n_batches = full;
-            p.nq_valid = 32;
-            p.assign_base = 0;
-            e = vs::launch_scan(p, grid, 8, 2, vs::kModeAssign, nullptr);
-            if (e != hipSuccess) return e;
-        }
-        if (rem) {
-            p.q = d_cents + (size_t)full * 32 * dim;
-            p.n_batches = 1;
-            p.nq_valid = rem;
-            p.assign_base = full * 32;
-            e = vs::launch_scan(p, grid, 8, 2, vs::kModeAssign, nullptr);
-        }
-        return e;
-    };
     int it = 0;
     std::vector<double> shift((size_t)nlist);
     for (; it < max_iter; ++it) {
         HIPCHK(assign_pass());
-        HIPCHK(vs::launch_kmeans_update(d_x, d_best_i, n_rows, nlist, d_cents, d_acc, d_counts, d_shift, nullptr));
+        HIPCHK(update());
         HIPCHK(hipMemcpy(shift.data(), d_shift, (size_t)nlist * sizeof(double), hipMemcpyDeviceToHost));
         double total = 0;
         for (double v : shift) total += v;
@@ -2579,14 +2538,201 @@ static int ivf_build_impl(const float* base_host, int64_t n_rows, int dim, int n
             break;
         }
     }
+    vs::Event ev0, ev1;  // the last pass is timed for vs_ivf_build_last_assign_ms
+    if ((rc = ev0.create(true)) || (rc = ev1.create(true))) return rc;
+    HIPCHK(hipEventRecord(ev0, nullptr));
     HIPCHK(assign_pass());  // labels consistent with the final centroids
+    HIPCHK(hipEventRecord(ev1, nullptr));
     HIPCHK(hipMemcpy(assign_out, d_best_i, (size_t)n_rows * sizeof(int32_t), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(centroids_out, d_cents, (size_t)nlist * dim * sizeof(float), hipMemcpyDeviceToHost));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
+    g_build_assign_ms = (double)ms;
     if (iters_done) *iters_done = it;
     return VS_OK;
 }
 
+// best_d / best_i of one assignment pass: +inf / -1, then the launch for the nlist / 32 full batches of centroids and the
+// launch for the remainder (scan(p, grid) = the kModeAssign launch of the builder's scan kernel)
+template <class Scan>
+static hipError_t ivf_assign_launches(vs::ScanParams p, const float* d_cents, int dim, int nlist, int64_t n_rows, int grid, Scan scan) {
+    hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.best_d), 0x7f800000, (size_t)n_rows, nullptr);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(p.best_i, 0xff, (size_t)n_rows * sizeof(int32_t), nullptr);
+    if (e != hipSuccess) return e;
+    p.metric = 0;
+    p.row_begin = 0;
+    p.row_end = n_rows;
+    p.q_batch_stride = (int64_t)32 * dim;
+    const int full = nlist / 32, rem = nlist % 32;
+    if (full) {
+        p.q = d_cents;
+        p.n_batches = full;
+        p.nq_valid = 32;
+        p.assign_base = 0;
+        e = scan(p, grid, 0);
+        if (e != hipSuccess) return e;
+    }
+    if (rem) {
+        p.q = d_cents + (size_t)full * 32 * dim;
+        p.n_batches = 1;
+        p.nq_valid = rem;
+        p.assign_base = full * 32;
+        e = scan(p, grid, full);
+    }
+    return e;
+}
+}  // extern "C++"
+
+static int ivf_build_impl(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol, uint64_t seed,
+                          int device, float* centroids_out, int32_t* assign_out, int* iters_done);
+int vs_ivf_build(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol, uint64_t seed,
+                 int device, float* centroids_out, int32_t* assign_out, int* iters_done) {
+    return guarded([&]() -> int {
+        return ivf_build_impl(base_host, n_rows, dim, nlist, max_iter, tol, seed, device, centroids_out, assign_out, iters_done);
+    });
+}
+static int ivf_build_impl(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol, uint64_t seed,
+                          int device, float* centroids_out, int32_t* assign_out, int* iters_done) {
+    double tol_abs = 0.0;
+    int rc = ivf_build_checks("vs_ivf_build", base_host, n_rows, dim, vs::kDim, vs::kDim, nlist, max_iter, tol, centroids_out, assign_out,
+                              tol_abs);
+    if (rc) return rc;
+    if ((rc = check_device(device))) return rc;
+    HIPCHK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    const int num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    vs::DevBuf<float> d_x, d_norm, d_cents, d_best_d;
+    vs::DevBuf<int32_t> d_best_i, d_counts;
+    vs::DevBuf<unsigned long long> d_acc;
+    vs::DevBuf<double> d_shift;
+    const int nlist_pad = (nlist + 31) & ~31;
+    if ((rc = d_x.alloc(((size_t)n_rows + vs::kScanPadRows) * dim))) return rc;
+    HIPCHK(hipMemset(d_x + (size_t)n_rows * dim, 0, (size_t)vs::kScanPadRows * dim * sizeof(float)));
+    if ((rc = d_norm.alloc((size_t)n_rows + 64)) || (rc = d_cents.alloc((size_t)nlist_pad * dim)) || (rc = d_best_d.alloc((size_t)n_rows)) ||
+        (rc = d_best_i.alloc((size_t)n_rows)) || (rc = d_counts.alloc((size_t)nlist)) || (rc = d_acc.alloc((size_t)nlist * dim)) ||
+        (rc = d_shift.alloc((size_t)nlist)))
+        return rc;
+    HIPCHK(hipMemcpy(d_x, base_host, (size_t)n_rows * dim * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_norm, 0, ((size_t)n_rows + 64) * sizeof(float)));
+    HIPCHK(vs::launch_row_sqnorm(d_x, n_rows, dim, d_norm, nullptr));
+    int grid, tp;
+    scan_geometry(n_rows, num_cus, grid, tp);
+    vs::ScanParams p{};
+    p.base = d_x;
+    p.bnorm = d_norm;
+    p.tiles_per_wg = tp;
+    p.best_d = d_best_d;
+    p.best_i = d_best_i;
+    return ivf_build_run(
+        base_host, n_rows, dim, dim, nlist, nlist_pad, max_iter, tol_abs, seed, d_x, d_cents, d_best_d, d_best_i, d_shift,
+        [&](int c, double u, int n_blocks, double* d_bsum) {
+            return vs::launch_kpp_step(d_x, d_norm, n_rows, d_cents, c, d_best_d, d_bsum, n_blocks, u, nullptr);
+        },
+        [&]() {
+            return ivf_assign_launches(p, d_cents, dim, nlist, n_rows, grid, [](const vs::ScanParams& sp, int g, int) {
+                return vs::launch_scan(sp, g, 8, 2, vs::kModeAssign, nullptr);
+            });
+        },
+        [&]() { return vs::launch_kmeans_update(d_x, d_best_i, n_rows, nlist, d_cents, d_acc, d_counts, d_shift, nullptr); },
+        centroids_out, assign_out, iters_done);
+}
+
+// comparison toggle (VSEARCH_BUILD_ND_FORCE=1, read at every call of the _nd builders): the general builder at dim 128 too
+static bool build_nd_forced() {
+    const char* e = getenv("VSEARCH_BUILD_ND_FORCE");
+    return e && atoi(e) != 0;
+}
+
+// The builder at any dimension 1 <= dim <= 2048 (vsearch.h at vs_ivf_build_nd): the same contract on the layout of a general
+// index -- rows [n_rows + kScanPadRows][dim_p] zero padded, centroids [nlist_pad][dim] unpadded (what nd_prep_kernel reads),
+// assignment on scan_nd_kernel's kModeAssign, so that a distance is the brute-force general scan's to the bit.
+static int ivf_build_nd_impl(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol, uint64_t seed,
+                             int device, float* centroids_out, int32_t* assign_out, int* iters_done) {
+    // dim 128 is vs_ivf_build's, checks included (the same ones in the same order)
+    if (dim == vs::kDim && !build_nd_forced())
+        return ivf_build_impl(base_host, n_rows, dim, nlist, max_iter, tol, seed, device, centroids_out, assign_out, iters_done);
+    double tol_abs = 0.0;
+    int rc = ivf_build_checks("vs_ivf_build_nd", base_host, n_rows, dim, 1, vs::kNdMaxDim, nlist, max_iter, tol, centroids_out,
+                              assign_out, tol_abs);
+    if (rc) return rc;
+    if ((rc = check_device(device))) return rc;
+    HIPCHK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    const int num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    vs::DevBuf<float> d_x, d_norm, d_cents, d_best_d, d_qfrag, d_qnorm;
+    vs::DevBuf<int32_t> d_best_i, d_counts;
+    vs::DevBuf<unsigned long long> d_acc;
+    vs::DevBuf<double> d_shift;
+    const int nlist_pad = (nlist + 31) & ~31, n_batches = nlist_pad / 32;
+    const int dim_p = vs::nd_dim_p(dim);
+    const int64_t ld = dim_p;
+    const size_t x_floats = ((size_t)n_rows + vs::kScanPadRows) * (size_t)ld;
+    if ((rc = d_x.alloc(x_floats)) || (rc = d_norm.alloc((size_t)n_rows + 64)) || (rc = d_cents.alloc((size_t)nlist_pad * dim)) ||
+        (rc = d_best_d.alloc((size_t)n_rows)) || (rc = d_best_i.alloc((size_t)n_rows)) || (rc = d_counts.alloc((size_t)nlist)) ||
+        (rc = d_acc.alloc((size_t)nlist * dim)) || (rc = d_shift.alloc((size_t)nlist)) ||
+        (rc = d_qfrag.alloc((size_t)n_batches * dim_p * 32)) || (rc = d_qnorm.alloc((size_t)n_batches * vs::kMaxBatch)))
+        return rc;
+    // zero filled: the padding of a row and the spare rows add exact zeros to every chain (scan blocks are read unclamped)
+    HIPCHK(hipMemset(d_x, 0, x_floats * sizeof(float)));
+    HIPCHK(hipMemcpy2D(d_x, (size_t)ld * sizeof(float), base_host, (size_t)dim * sizeof(float), (size_t)dim * sizeof(float), (size_t)n_rows,
+                       hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_norm, 0, ((size_t)n_rows + 64) * sizeof(float)));
+    HIPCHK(vs::launch_row_sqnorm_ld(d_x, n_rows, dim, ld, d_norm, nullptr));
+    int grid, tp;
+    scan_geometry(n_rows, num_cus, grid, tp);
+    vs::ScanParams p{};
+    p.base = d_x;
+    p.bnorm = d_norm;
+    p.tiles_per_wg = tp;
+    p.best_d = d_best_d;
+    p.best_i = d_best_i;
+    return ivf_build_run(
+        base_host, n_rows, dim, ld, nlist, nlist_pad, max_iter, tol_abs, seed, d_x, d_cents, d_best_d, d_best_i, d_shift,
+        [&](int c, double u, int n_blocks, double* d_bsum) {
+            return vs::launch_kpp_step_nd(d_x, ld, d_norm, n_rows, dim, d_cents, c, d_best_d, d_bsum, n_blocks, u, nullptr);
+        },
+        [&]() {
+            return ivf_assign_launches(p, d_cents, dim, nlist, n_rows, grid, [&](const vs::ScanParams& sp, int g, int batch0) {
+                vs::ScanNdParams np{};
+                np.s = sp;
+                np.dim = dim;
+                np.dim_p = dim_p;
+                np.qfrag = d_qfrag + (size_t)batch0 * dim_p * 32;  // the remainder's batch has its own fragments and norms
+                np.qnorm = d_qnorm + (size_t)batch0 * vs::kMaxBatch;
+                return vs::launch_scan_nd(np, g, 8, 2, vs::kModeAssign, nullptr);
+            });
+        },
+        [&]() {
+            return vs::launch_kmeans_update_nd(d_x, ld, dim, d_best_i, n_rows, nlist, d_cents, d_acc, d_counts, d_shift, nullptr);
+        },
+        centroids_out, assign_out, iters_done);
+}
+int vs_ivf_build_nd(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol, uint64_t seed, int device,
+                    float* centroids_out, int32_t* assign_out, int* iters_done) {
+    return guarded([&]() -> int {
+        return ivf_build_nd_impl(base_host, n_rows, dim, nlist, max_iter, tol, seed, device, centroids_out, assign_out, iters_done);
+    });
+}
+
 // build_ivf_index_reordered (create_ivf_model_reordered.py:82-177) end to end: k-means, reordered layout, resident index.
+// build = vs_ivf_build or vs_ivf_build_nd.
+extern "C++" template <class Build>
+static int ivf_build_index_with(Build build, const float* base_host, int64_t n_rows, int dim, int nl, int max_iter, double tol,
+                                uint64_t seed, int device, vs_index** out, int* iters_done) {
+    std::vector<float> cents((size_t)nl * dim);
+    std::vector<int32_t> assign((size_t)n_rows), off((size_t)nl + 1), r2o((size_t)n_rows);
+    int rc = build(base_host, n_rows, dim, nl, max_iter, tol, seed, device, cents.data(), assign.data(), iters_done);
+    if (rc) return rc;
+    if ((rc = vs_ivf_layout(assign.data(), n_rows, nl, off.data(), r2o.data()))) return rc;
+    std::vector<float> vr((size_t)n_rows * dim);
+    for (int64_t i = 0; i < n_rows; ++i)
+        std::memcpy(&vr[(size_t)i * dim], base_host + (size_t)r2o[(size_t)i] * dim, (size_t)dim * sizeof(float));
+    return ivf_create_impl(vr.data(), n_rows, dim, cents.data(), nl, off.data(), r2o.data(), device, 0, 1, out);
+}
+
 int vs_ivf_build_index(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol, uint64_t seed,
                        int device, vs_index** out, int* iters_done) {
     if (!out || !base_host || n_rows <= 0 || nlist <= 0) {
@@ -2594,16 +2740,29 @@ int vs_ivf_build_index(const float* base_host, int64_t n_rows, int dim, int nlis
         return VS_ERR_INVALID;
     }
     return guarded([&]() -> int {
+        return ivf_build_index_with(vs_ivf_build, base_host, n_rows, dim, vs_ivf_clamp_nlist(n_rows, nlist), max_iter, tol, seed, device,
+                                    out, iters_done);
+    });
+}
+
+int vs_ivf_build_index_nd(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol, uint64_t seed,
+                          int device, vs_index** out, int* iters_done) {
+    if (!out || !base_host || n_rows <= 0 || nlist <= 0) {
+        set_error("vs_ivf_build_index_nd: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    return guarded([&]() -> int {
         const int nl = vs_ivf_clamp_nlist(n_rows, nlist);
-        std::vector<float> cents((size_t)nl * dim);
-        std::vector<int32_t> assign((size_t)n_rows), off((size_t)nl + 1), r2o((size_t)n_rows);
-        int rc = vs_ivf_build(base_host, n_rows, dim, nl, max_iter, tol, seed, device, cents.data(), assign.data(), iters_done);
-        if (rc) return rc;
-        if ((rc = vs_ivf_layout(assign.data(), n_rows, nl, off.data(), r2o.data()))) return rc;
-        std::vector<float> vr((size_t)n_rows * dim);
-        for (int64_t i = 0; i < n_rows; ++i)
-            std::memcpy(&vr[(size_t)i * dim], base_host + (size_t)r2o[(size_t)i] * dim, (size_t)dim * sizeof(float));
-        return ivf_create_impl(vr.data(), n_rows, dim, cents.data(), nl, off.data(), r2o.data(), device, 0, 1, out);
+        // vs_ivf_build_nd's argument checks that decide the size of the arrays below, in its order
+        if (nl > n_rows || max_iter < 0 || dim < 1) {
+            set_error("vs_ivf_build_index_nd: bad arguments");
+            return VS_ERR_INVALID;
+        }
+        if (dim > vs::kNdMaxDim) {
+            set_error("vs_ivf_build_index_nd: dim " + std::to_string(dim) + " is above the largest supported, 2048");
+            return VS_ERR_UNSUPPORTED;
+        }
+        return ivf_build_index_with(vs_ivf_build_nd, base_host, n_rows, dim, nl, max_iter, tol, seed, device, out, iters_done);
     });
 }
 

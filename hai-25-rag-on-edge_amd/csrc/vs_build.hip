@@ -175,6 +175,74 @@ hipError_t launch_kmeans_update(const float* x, const int32_t* assign, int64_t r
     return hipGetLastError();
 }
 
+// The same update at any dimension: rows ld floats apart, accumulators and centroids [nlist][dim].  One thread per
+// (row, column) element; the integer sums do not depend on how the elements are dealt out.
+__global__ __launch_bounds__(256) void kmeans_accum_nd_kernel(const float* __restrict__ x, int64_t ld, int dim,
+                                                              const int32_t* __restrict__ assign, int64_t rows,
+                                                              unsigned long long* __restrict__ acc, int32_t* __restrict__ counts) {
+    if (dim <= 256) {  // whole rows per workgroup pass: 256 / dim of them (a row is never split between passes)
+        const int rpp = 256 / dim;
+        const int rr = threadIdx.x / dim, t = threadIdx.x - rr * dim;
+        if (rr >= rpp) return;
+        for (int64_t row = (int64_t)blockIdx.x * rpp + rr; row < rows; row += (int64_t)gridDim.x * rpp) {
+            const int c = assign[row];
+            if (c < 0) continue;
+            const long long v = __double2ll_rn((double)x[row * ld + t] * kFix);
+            atomicAdd(acc + (int64_t)c * dim + t, (unsigned long long)v);
+            if (t == 0) atomicAdd(counts + c, 1);
+        }
+        return;
+    }
+    for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const int c = assign[row];
+        if (c < 0) continue;
+        for (int t = threadIdx.x; t < dim; t += 256) {
+            const long long v = __double2ll_rn((double)x[row * ld + t] * kFix);
+            atomicAdd(acc + (int64_t)c * dim + t, (unsigned long long)v);
+        }
+        if (threadIdx.x == 0) atomicAdd(counts + c, 1);
+    }
+}
+
+// One workgroup per centroid.  shift[c]: thread t adds the squared shifts of columns t, t + 128, ... in that order, then
+// kmeans_finalize_kernel's tree over the 128 threads (at dim 128 that is its sum).
+__global__ __launch_bounds__(128) void kmeans_finalize_nd_kernel(float* __restrict__ cents, int dim,
+                                                                 const unsigned long long* __restrict__ acc,
+                                                                 const int32_t* __restrict__ counts, double* __restrict__ shift) {
+    const int c = blockIdx.x, t = threadIdx.x;
+    const int n = counts[c];
+    float delta2 = 0.f;
+    if (n > 0) {
+        for (int col = t; col < dim; col += 128) {
+            const double mean = (double)(long long)acc[(int64_t)c * dim + col] / kFix / (double)n;
+            const float nv = (float)mean;
+            const float ov = cents[(int64_t)c * dim + col];
+            cents[(int64_t)c * dim + col] = nv;
+            delta2 += (nv - ov) * (nv - ov);
+        }
+    }  // an empty cluster keeps its centroid
+    __shared__ float red[128];
+    red[t] = delta2;
+    __syncthreads();
+    for (int sft = 64; sft > 0; sft >>= 1) {
+        if (t < sft) red[t] += red[t + sft];
+        __syncthreads();
+    }
+    if (t == 0) shift[c] = (double)red[0];
+}
+
+hipError_t launch_kmeans_update_nd(const float* x, int64_t ld, int dim, const int32_t* assign, int64_t rows, int nlist, float* cents,
+                                   unsigned long long* acc, int32_t* counts, double* shift, hipStream_t s) {
+    if (dim < 1 || dim > kNdMaxDim || ld < dim) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(acc, 0, (size_t)nlist * dim * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(counts, 0, (size_t)nlist * sizeof(int32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kmeans_accum_nd_kernel, dim3(4096), dim3(256), 0, s, x, ld, dim, assign, rows, acc, counts);
+    hipLaunchKernelGGL(kmeans_finalize_nd_kernel, dim3(nlist), dim3(128), 0, s, cents, dim, acc, counts, shift);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // k-means++ seeding.  kpp_update_kernel: one workgroup per kKppBlockRows rows, 8 lanes per row (as in the IVF
 // scans); kpp_pick_kernel: one workgroup finds the block, then the row, where the running sum passes u * total.
@@ -228,7 +296,7 @@ __global__ __launch_bounds__(256) void kpp_update_kernel(const float* __restrict
 
 __global__ __launch_bounds__(1024) void kpp_pick_kernel(const float* __restrict__ x, int64_t rows, const float* __restrict__ d2,
                                                         const double* __restrict__ block_sums, int n_blocks, double u,
-                                                        float* __restrict__ out_centre) {
+                                                        float* __restrict__ out_centre, int dim, int64_t ld) {
     __shared__ double s_part[1024];
     __shared__ double s_target, s_before;
     __shared__ int s_block;
@@ -295,13 +363,79 @@ __global__ __launch_bounds__(1024) void kpp_pick_kernel(const float* __restrict_
         s_row = pick;
     }
     __syncthreads();
-    if (tid < kDim) out_centre[tid] = x[s_row * kDim + tid];
+    for (int t = tid; t < dim; t += 1024) out_centre[t] = x[s_row * ld + t];  // rows ld floats apart, centres dim apart
 }
 
 hipError_t launch_kpp_step(const float* x, const float* xnorm, int64_t rows, float* cents, int c, float* d2, double* block_sums,
                            int n_blocks, double u, hipStream_t s) {
     hipLaunchKernelGGL(kpp_update_kernel, dim3(n_blocks), dim3(256), 0, s, x, xnorm, rows, cents + (size_t)(c - 1) * kDim, d2, block_sums);
-    hipLaunchKernelGGL(kpp_pick_kernel, dim3(1), dim3(1024), 0, s, x, rows, d2, block_sums, n_blocks, u, cents + (size_t)c * kDim);
+    hipLaunchKernelGGL(kpp_pick_kernel, dim3(1), dim3(1024), 0, s, x, rows, d2, block_sums, n_blocks, u, cents + (size_t)c * kDim,
+                       kDim, (int64_t)kDim);
+    return hipGetLastError();
+}
+
+// The same step at any dimension (index builder of a general IVF index): rows [rows][ld] with ld = nd_dim_p(dim), zero
+// padded; centres [nlist][dim], unpadded.  The centre goes through LDS (at 2048-d its 8 lanes x 64 f32x4 would not fit in
+// registers), zero padded to ld.  Summation order of D^2, stated in vsearch.h at vs_ivf_build_nd: 8 lanes per row, lane s
+// chains fmaf over the 16-byte chunks s, s + 8, s + 16, ... of the padded row (four elements each, in order), then the 8
+// partial sums are added as (((p0+p1)+(p2+p3)) + ((p7+p6)+(p5+p4))) -- dpp_add_xor1 / xor2 / half_mirror, which at dim
+// 128 is kpp_update_kernel's order.  ||c||^2 takes the same order; ||x||^2 is row_sqnorm_kernel's.  Everything else
+// (d2 = min(d2, max(fma(-2, x.c, xn + cn), 0)), the double sums per kKppBlockRows rows) is kpp_update_kernel's.
+__global__ __launch_bounds__(256) void kpp_update_nd_kernel(const float* __restrict__ x, int64_t ld, const float* __restrict__ xnorm,
+                                                            int64_t rows, const float* __restrict__ centre, int dim,
+                                                            float* __restrict__ d2, double* __restrict__ block_sums) {
+    __shared__ __attribute__((aligned(16))) float cs[kNdMaxDim];
+    __shared__ double wsum[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int rr = lane >> 3, s8 = lane & 7;
+    const int n_chunks = (int)(ld >> 2);
+    for (int t = tid; t < (int)ld; t += 256) cs[t] = t < dim ? centre[t] : 0.f;
+    __syncthreads();
+    float cn = 0.f;
+    for (int ch = s8; ch < n_chunks; ch += 8) {
+        const f32x4 c4 = *reinterpret_cast<const f32x4*>(cs + 4 * ch);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cn = fmaf(c4[i], c4[i], cn);
+    }
+    cn = dpp_add_xor1(cn);
+    cn = dpp_add_xor2(cn);
+    cn = dpp_add_half_mirror(cn);
+    const int64_t row_begin = (int64_t)blockIdx.x * kKppBlockRows;
+    double acc = 0.0;
+    for (int r0 = wave * 8; r0 < kKppBlockRows; r0 += 32) {
+        const int64_t row = row_begin + r0 + rr;
+        const bool ok = row < rows;
+        const float* src = x + (ok ? row : 0) * ld;
+        float dot = 0.f;
+        for (int ch = s8; ch < n_chunks; ch += 8) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * ch);
+            const f32x4 c4 = *reinterpret_cast<const f32x4*>(cs + 4 * ch);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dot = fmaf(v[i], c4[i], dot);
+        }
+        dot = dpp_add_xor1(dot);
+        dot = dpp_add_xor2(dot);
+        dot = dpp_add_half_mirror(dot);
+        if (ok && s8 == 0) {
+            const float d = fmaxf(fmaf(-2.0f, dot, xnorm[row] + cn), 0.f);
+            const float nd = fminf(d2[row], d);
+            d2[row] = nd;
+            acc += (double)nd;
+        }
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) acc += __shfl_xor(acc, m);
+    if (lane == 0) wsum[wave] = acc;
+    __syncthreads();
+    if (tid == 0) block_sums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+hipError_t launch_kpp_step_nd(const float* x, int64_t ld, const float* xnorm, int64_t rows, int dim, float* cents, int c, float* d2,
+                              double* block_sums, int n_blocks, double u, hipStream_t s) {
+    if (dim < 1 || dim > kNdMaxDim || ld != nd_dim_p(dim)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kpp_update_nd_kernel, dim3(n_blocks), dim3(256), 0, s, x, ld, xnorm, rows, cents + (size_t)(c - 1) * dim, dim, d2,
+                       block_sums);
+    hipLaunchKernelGGL(kpp_pick_kernel, dim3(1), dim3(1024), 0, s, x, rows, d2, block_sums, n_blocks, u, cents + (size_t)c * dim, dim, ld);
     return hipGetLastError();
 }
 

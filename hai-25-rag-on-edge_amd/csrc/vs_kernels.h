@@ -56,8 +56,8 @@ struct ScanParams {
 // Brute-force / coarse scan.  kcap in {8, 16}; nqh = 1 (<=16 queries) or 2.
 hipError_t launch_scan(const ScanParams& p, int grid, int kcap, int nqh, int mode, hipStream_t s);
 
-// General-dimension scan (vs_scan_nd.hip): ScanParams as above for kModeTopK / kModeStore / kModeFilter, with
-// rows of dim_p = nd_dim_p(dim) floats ([n_rows + kScanPadRows][dim_p], zero padded) and queries of dim floats
+// General-dimension scan (vs_scan_nd.hip): ScanParams as above for kModeTopK / kModeStore / kModeFilter, and
+// for kModeAssign with nqh = 2 (any n_batches; the index builder at general dimensions), with rows of dim_p = nd_dim_p(dim) floats ([n_rows + kScanPadRows][dim_p], zero padded) and queries of dim floats
 // ([n_batches][nq_valid][dim], unpadded; q_batch_stride in floats).  A preparation launch writes the queries in MFMA
 // B-fragment order and their squared norms into the caller's scratch; the fp32 fields of ScanParams are the only ones read.
 constexpr int kNdMaxDim = 2048;
@@ -331,6 +331,12 @@ hipError_t launch_kmeans_update(const float* x, const int32_t* assign, int64_t r
 hipError_t launch_kpp_step(const float* x, const float* xnorm, int64_t rows, float* cents, int c, float* d2, double* block_sums,
                            int n_blocks, double u, hipStream_t s);
 constexpr int kKppBlockRows = 1024;
+// The builder's update and seeding step at any dimension 1 <= dim <= kNdMaxDim (vs_ivf_build_nd): rows [rows][ld], ld =
+// nd_dim_p(dim), zero padded; cents / acc [nlist][dim].  Same fixed-point sums, same D^2 rule and block sums.
+hipError_t launch_kmeans_update_nd(const float* x, int64_t ld, int dim, const int32_t* assign, int64_t rows, int nlist, float* cents,
+                                   unsigned long long* acc, int32_t* counts, double* shift, hipStream_t s);
+hipError_t launch_kpp_step_nd(const float* x, int64_t ld, const float* xnorm, int64_t rows, int dim, float* cents, int c, float* d2,
+                              double* block_sums, int n_blocks, double u, hipStream_t s);
 
 // ||v||^2 per row in the reference's AVX2 summation order (cpu_baseline.cpp:95-114).
 hipError_t launch_row_sqnorm(const float* v, int64_t rows, int dim, float* out, hipStream_t s);

@@ -2,9 +2,10 @@
 //
 //   scan_nd_kernel<NQH, KCAP, MODE> : the general-dimension sibling of scan_kernel (vs_scan.hip): the same ScanParams
 //                          contract (kModeTopK partial lists + threshold exchange, kModeStore score matrix, kModeFilter
-//                          candidate lists), the same arithmetic (v_mfma_f32_16x16x4_f32, base rows = A operand, one
-//                          accumulation chain per distance in the k order of scan_kernel, fma(-2, dot, qn + bn) epilogue),
-//                          so that at dim = 128 it gives scan_kernel's distances to the bit.
+//                          candidate lists, kModeAssign nearest centroid of every row for the index builder), the same
+//                          arithmetic (v_mfma_f32_16x16x4_f32, base rows = A operand, one accumulation chain per
+//                          distance in the k order of scan_kernel, fma(-2, dot, qn + bn) epilogue), so that at dim = 128
+//                          it gives scan_kernel's distances to the bit.
 //   nd_prep_kernel       : per batch, the queries zero-padded to dim_p and laid out in MFMA B-fragment order, and their
 //                          squared norms in the reference's summation order (cpu_baseline.cpp:95-114).
 //
@@ -211,6 +212,44 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_nd_kernel(const ScanNdPa
                                 }
                         }
                     }
+                } else if (MODE == kModeAssign) {
+                    // k-means assignment (scan_kernel's assign branch): the "queries" are a block of 32 centroids, and
+                    // every base row keeps its nearest centroid so far in best_d / best_i.  A lane holds rows rbase ..
+                    // rbase + 3 for columns r and 16 + r: fold its columns, then the 16 lanes of the DPP row (the same
+                    // rows, other columns).  No atomics: a wave owns the same row blocks in every batch (wb0 and wb_step
+                    // do not depend on the batch), and the launches of one pass are ordered by their stream.
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        float bd = VS_INF;
+                        int bi = 0x7fffffff;
+#pragma unroll
+                        for (int h = 0; h < NQH; ++h) {
+                            const int cid = p.assign_base + batch * kMaxBatch + h * 16 + r;
+                            if (h * 16 + r < p.nq_valid && lex_lt(d[h][j], cid, bd, bi)) {
+                                bd = d[h][j];
+                                bi = cid;
+                            }
+                        }
+                        float od;
+                        int oi;
+                        od = dpp_mov_f<0xB1>(bd); oi = dpp_mov_i<0xB1>(bi);
+                        if (lex_lt(od, oi, bd, bi)) { bd = od; bi = oi; }
+                        od = dpp_mov_f<0x4E>(bd); oi = dpp_mov_i<0x4E>(bi);
+                        if (lex_lt(od, oi, bd, bi)) { bd = od; bi = oi; }
+                        od = dpp_mov_f<0x141>(bd); oi = dpp_mov_i<0x141>(bi);
+                        if (lex_lt(od, oi, bd, bi)) { bd = od; bi = oi; }
+                        od = dpp_mov_f<0x140>(bd); oi = dpp_mov_i<0x140>(bi);
+                        if (lex_lt(od, oi, bd, bi)) { bd = od; bi = oi; }
+                        const int64_t row = rbase + j;
+                        if (r == 0 && row <= last_row && bi != 0x7fffffff) {
+                            const float cur_d = p.best_d[row];
+                            const int cur_i = p.best_i[row];
+                            if (lex_lt(bd, bi, cur_d, cur_i < 0 ? 0x7fffffff : cur_i)) {
+                                p.best_d[row] = bd;
+                                p.best_i[row] = bi;
+                            }
+                        }
+                    }
                 } else {  // kModeStore
 #pragma unroll
                     for (int h = 0; h < NQH; ++h) {
@@ -234,6 +273,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_nd_kernel(const ScanNdPa
             xchg_bound<NQH>(tail, slots, p.k1, tid, wave, wmin, tq, tau);  // (after the first block: vs_scan_tail.h)
         }
         }
+        if (MODE == kModeAssign) continue;  // the next 32 centroids: nothing is shared between waves, so no barrier
         if (MODE != kModeTopK) return;
         wg_merge_lists<NQH, KCAP>(tail, p, batch, tid, wave, ld, li, tq);  // (ends with a barrier)
     }
@@ -247,13 +287,14 @@ static hipError_t launch_scan_nd_t(const ScanNdParams& p, int grid, hipStream_t 
 
 hipError_t launch_scan_nd(const ScanNdParams& p, int grid, int kcap, int nqh, int mode, hipStream_t s) {
     if (p.dim < 1 || p.dim > kNdMaxDim || p.dim_p != nd_dim_p(p.dim) || !p.qfrag || !p.qnorm || grid < 1 || grid > kSlotStride ||
-        (p.s.row_begin & 15) || p.s.n_batches < 1)
+        (p.s.row_begin & 15) || p.s.n_batches < 1 || (mode == kModeAssign && (!p.s.best_d || !p.s.best_i || nqh != 2)))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(nd_prep_kernel, dim3(p.s.n_batches), dim3(256), 0, s, p.s.q, p.s.q_batch_stride, p.s.nq_valid, p.dim, p.dim_p,
                        p.qfrag, p.qnorm, p.s.run_if);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (mode == kModeStore) return nqh == 1 ? launch_scan_nd_t<1, 8, kModeStore>(p, grid, s) : launch_scan_nd_t<2, 8, kModeStore>(p, grid, s);
+    if (mode == kModeAssign) return launch_scan_nd_t<2, 8, kModeAssign>(p, grid, s);  // (the builder's batches are 32 centroids wide)
     if (mode == kModeFilter) return nqh == 1 ? launch_scan_nd_t<1, 8, kModeFilter>(p, grid, s) : launch_scan_nd_t<2, 8, kModeFilter>(p, grid, s);
     if (mode != kModeTopK) return hipErrorInvalidValue;
     if (kcap == 8) return nqh == 1 ? launch_scan_nd_t<1, 8, kModeTopK>(p, grid, s) : launch_scan_nd_t<2, 8, kModeTopK>(p, grid, s);

@@ -312,8 +312,8 @@ VS_API int vs_ivf_load(const char* index_dir, int device, int rank, int world, v
  *     fp32 rows), vs_ivf_set_metric(VS_METRIC_L2);
  *   VS_ERR_UNSUPPORTED, with the dimension in the message: 17 <= k <= 128, vs_set_precision 2,
  *     vs_ivf_set_metric(VS_METRIC_IP), vs_ivf_widek_stats, every sharded and virtual-shard call.
- * vs_ivf_build and vs_ivf_build_index stay 128-d only: arrays for other dimensions come from the
- * caller or from a directory. */
+ * vs_ivf_build and vs_ivf_build_index stay 128-d only; vs_ivf_build_nd and vs_ivf_build_index_nd
+ * build at every dimension this creator takes. */
 VS_API int vs_ivf_create(const float* vectors_reordered, int64_t n_rows, int dim,
                          const float* centroids, int nlist, const int32_t* cluster_offsets,
                          const int32_t* reorder_to_original, int device, int rank, int world,
@@ -370,6 +370,44 @@ VS_API int vs_ivf_layout(const int32_t* assign, int64_t n_rows, int nlist, int32
  * resulting index resident on `device`; vs_ivf_save then writes the reference's directory.  No Python involved. */
 VS_API int vs_ivf_build_index(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol,
                               uint64_t seed, int device, vs_index** out, int* iters_done);
+
+/* The builder at any dimension 1 <= dim <= 2048: vs_ivf_build's contract, word for word (seeding stream, k-means++ pick
+ * rule over blocks of 1024 rows with its all-zero fallback, VSEARCH_KMEANS_INIT=random, ties to the lower centroid id,
+ * 2^20 fixed-point update with (float)((double)A / 2^20 / count), empty clusters keep their centroid, max_iter = 0, the
+ * meaning of *iters_done, the stopping rule), with these additions.
+ *   - dim == 128 runs vs_ivf_build itself: the same launches, the same outputs.  VSEARCH_BUILD_ND_FORCE=1 (read at every
+ *     call of the two _nd entry points; off by default) runs the general builder at dim 128 too: the comparison toggle,
+ *     as VSEARCH_ND_FORCE and VSEARCH_IVF_ND_FORCE are for the searches.
+ *   - assignment: the distance of row x to centroid c is bit for bit the number the general brute-force scan
+ *     (vs_bf_create_nd's fp32 index) returns for that pair -- one fp32 accumulation chain in k order over the rows zero
+ *     padded to a multiple of 16 floats, then fma(-2, dot, ||c||^2 + ||x||^2) with both norms in the reference's order
+ *     (8 FMA lanes over v[8 i + j], r0 + ... + r7, then the tail).  It is also the coarse score of c for query x in a
+ *     general IVF index (vs_ivf_create).
+ *   - k-means++ D^2 = max(fma(-2, x.c, ||x||^2 + ||c||^2'), 0), summed in double per block of 1024 rows.  ||x||^2 is the
+ *     norm above.  x.c and ||c||^2' are summed in fp32 as follows, with the vectors zero padded to a multiple of 16
+ *     floats and cut into chunks of 4 floats: partial sum p_s, s = 0..7, is one fmaf chain from 0 over chunks s, s + 8,
+ *     s + 16, ... (the four elements of a chunk in order); the result is ((p0 + p1) + (p2 + p3)) + ((p7 + p6) + (p5 + p4)).
+ *     At dim 128 this is vs_ivf_build's order.  Deterministic from run to run.
+ *   - sum of squared shifts of an update, per centroid in fp32: partial sum q_t, t = 0..127, adds the squared shifts of
+ *     columns t, t + 128, ... in that order; the 128 partial sums are folded in halves (q_t += q_{t + 64}, then 32, ...,
+ *     1).  The per-centroid sums are added in double in centroid order.  At dim 128 this is vs_ivf_build's order.
+ * Checks, in this order (the first five need no device; nothing is written to the outputs on any failure): null
+ * pointers, n_rows <= 0, nlist <= 0, nlist > n_rows or max_iter < 0 -> VS_ERR_INVALID; dim < 1 -> VS_ERR_INVALID;
+ * dim > 2048 -> VS_ERR_UNSUPPORTED; a non-finite value -> VS_ERR_INVALID; n_rows * (max|x| + 2^-21) >= 2^43 ->
+ * VS_ERR_INVALID; then the device. */
+VS_API int vs_ivf_build_nd(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol,
+                           uint64_t seed, int device, float* centroids_out, int32_t* assign_out, int* iters_done);
+
+/* vs_ivf_build_index at any dimension: nlist clamp, vs_ivf_build_nd, vs_ivf_layout, and the index resident on `device`:
+ * a general IVF index at dim != 128, the specialised one at 128 (see vs_ivf_create).  vs_ivf_save / vs_ivf_load handle
+ * both. */
+VS_API int vs_ivf_build_index_nd(const float* base_host, int64_t n_rows, int dim, int nlist, int max_iter, double tol,
+                                 uint64_t seed, int device, vs_index** out, int* iters_done);
+
+/* Device time in ms of the assignment pass that closed the calling thread's last successful build (any of the four
+ * builders): the two scan launches and the resets before them, between two events.  0 before the first build.  For
+ * scripts/ivf_nd_bench.py --build. */
+VS_API double vs_ivf_build_last_assign_ms(void);
 
 /* Writes the index held by h in the reference's directory format: unpadded [n_rows][dim] and [nlist][dim] arrays at
  * any dimension; vs_ivf_load of that directory gives the same index. */

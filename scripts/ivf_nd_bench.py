@@ -1,6 +1,7 @@
 """List-major IVF at a general dimension against exact brute force on the same rows: device time per 1024 queries.
 
     python scripts/ivf_nd_bench.py [--dims 96,384,768] [--rows 1000000] [--nlist 1024] [--nprobe 8,32] [--groups 4] [--reps 5]
+                                   [--build ITERS]
 
 Data: synth_sift rows (integer valued) at every dimension, nlist sampled rows as centroids, every row assigned to its
 nearest centroid through the library's own brute force (a timing index, not a trained one).  Queries: `groups` groups of
@@ -10,12 +11,19 @@ groups of one path between two device events, reported per 1024 queries, every r
 that exact result.  bytes_ratio is the expectation to compare against: brute force reads N rows per 32 queries, the list
 scan group_q * nprobe / 16 blocks of N / nlist rows.  Each dimension runs in a process of its own; one JSON line per
 measurement.
+
+--build ITERS trains the index with the library's builder instead (ivf_kmeans: vs_ivf_build_nd, k-means++ seeds, ITERS Lloyd
+iterations at tol = 0, seed 42) and prints one more JSON line: the build's wall time, the device time of one assignment
+pass (vs_ivf_build_last_assign_ms) and the iterations done; after the brute-force timing, a line that sets the assignment
+pass against its yardstick, nlist / 32 x the per-batch time of the brute-force general scan on the same rows.  At dim 128
+it prints the wall time of the specialised builder and of the general one (VSEARCH_BUILD_ND_FORCE=1), alternated, and stops.
 """
 import argparse
 import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 
@@ -33,6 +41,62 @@ def one(a, dim):
     st = torch.cuda.current_stream().cuda_stream
     base = pkg.synth_sift(a.rows, seed=1, dim=dim)
     q = pkg.synth_sift(a.groups * GROUP_Q, seed=2, dim=dim)
+    if a.build and dim == 128:
+        build_128(a, pkg, base)
+        return
+    assign_pass_ms = None
+    if a.build:
+        assign, cents, assign_pass_ms = build(a, pkg, base, dim)
+    else:
+        assign, cents = sampled_rows(a, pkg, base, dev, st)
+    vr, off, r2o = pkg.ivf_layout_from_assignment(base, assign, a.nlist)
+    search(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st, assign_pass_ms)
+
+
+def build(a, pkg, base, dim):
+    """the trained index: k-means through the library's builder"""
+    t0 = time.perf_counter()
+    cents, assign, iters = pkg.ivf_kmeans(base, a.nlist, a.build, 0.0, 42)
+    wall = time.perf_counter() - t0
+    assign_pass_ms = round(float(pkg.lib().vs_ivf_build_last_assign_ms()), 3)
+    print(json.dumps({"what": "build", "dim": dim, "rows": a.rows, "nlist": a.nlist, "max_iter": a.build, "iters_done": iters,
+                      "build_wall_s": round(wall, 3), "assign_pass_ms": assign_pass_ms}), flush=True)
+    return assign, cents, assign_pass_ms
+
+
+def build_128(a, pkg, base):
+    """dim 128: the specialised builder (vs_ivf_build) and the general one (vs_ivf_build_nd under the toggle), alternated"""
+    import ctypes as C
+    n = base.shape[0]
+    cents = np.empty((a.nlist, 128), dtype=np.float32)
+    assign = np.empty(n, dtype=np.int32)
+    it = C.c_int(0)
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    out = {"specialised": [], "general": []}
+    keep = {}
+    for _ in range(2):
+        for name in ("specialised", "general"):
+            if name == "general":
+                os.environ["VSEARCH_BUILD_ND_FORCE"] = "1"
+            try:
+                t0 = time.perf_counter()
+                rc = pkg.lib().vs_ivf_build_nd(p(base), n, 128, a.nlist, a.build, 0.0, 42, 0, p(cents), p(assign), C.byref(it))
+                wall = time.perf_counter() - t0
+            finally:
+                os.environ.pop("VSEARCH_BUILD_ND_FORCE", None)
+            if rc:
+                raise RuntimeError(pkg.lib().vs_last_error().decode())
+            out[name].append({"build_wall_s": round(wall, 3), "assign_pass_ms": round(float(pkg.lib().vs_ivf_build_last_assign_ms()), 3),
+                              "iters_done": it.value})
+            keep.setdefault(name, (cents.copy(), assign.copy()))
+    same = bool(np.array_equal(keep["specialised"][0].view(np.uint32), keep["general"][0].view(np.uint32)) and
+                np.array_equal(keep["specialised"][1], keep["general"][1]))
+    print(json.dumps({"what": "build_128", "rows": n, "nlist": a.nlist, "max_iter": a.build, **out, "same_bits": same}), flush=True)
+
+
+def sampled_rows(a, pkg, base, dev, st):
+    """the timing index: nlist sampled rows as centroids, every row assigned to its nearest one"""
+    import torch
     rng = np.random.default_rng(3)
     cents = np.ascontiguousarray(base[np.sort(rng.choice(a.rows, a.nlist, replace=False))])
 
@@ -57,7 +121,11 @@ def one(a, dim):
             torch.cuda.synchronize()
             assign[r0:r0 + n] = oi[:n, 0].cpu().numpy()
             del chunk
-    vr, off, r2o = pkg.ivf_layout_from_assignment(base, assign, a.nlist)
+    return assign, cents
+
+
+def search(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st, assign_pass_ms):
+    import torch
     sizes = np.diff(off)
     print(json.dumps({"what": "index", "dim": dim, "rows": a.rows, "nlist": a.nlist, "list_min": int(sizes.min()),
                       "list_mean": float(sizes.mean()), "list_max": int(sizes.max())}), flush=True)
@@ -109,6 +177,11 @@ def one(a, dim):
             for name, f, args in paths:
                 us[name].append(timed(f, *args))
         med = {n: sorted(v)[len(v) // 2] for n, v in us.items()}
+        if assign_pass_ms is not None:  # the assignment pass against nlist / 32 passes of the brute-force scan over the same rows
+            yard = med["bf"] / (GROUP_Q // B) * (a.nlist / B) / 1e3
+            print(json.dumps({"what": "assign_vs_yardstick", "dim": dim, "rows": a.rows, "nlist": a.nlist, "assign_pass_ms": assign_pass_ms,
+                              "bf_us_per_batch": round(med["bf"] / (GROUP_Q // B), 2), "yardstick_ms": round(yard, 3),
+                              "ratio": round(assign_pass_ms / yard, 3)}), flush=True)
         for name, _, args in paths:
             rec = {"what": "us_per_1024_queries", "path": name, "dim": dim, "rows": a.rows, "nlist": a.nlist, "k": K,
                    "us": [round(u, 1) for u in us[name]], "median_us": round(med[name], 1)}
@@ -127,13 +200,14 @@ def main():
     ap.add_argument("--nprobe", default="8,32")
     ap.add_argument("--groups", type=int, default=4)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--build", type=int, default=0, metavar="ITERS", help="train the index with the library's builder")
     ap.add_argument("--one", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.one:
         one(a, a.one)
         return
     cmd = [sys.executable, os.path.abspath(__file__), "--rows", str(a.rows), "--nlist", str(a.nlist), "--nprobe", a.nprobe,
-           "--groups", str(a.groups), "--reps", str(a.reps)]
+           "--groups", str(a.groups), "--reps", str(a.reps), "--build", str(a.build)]
     for dim in [int(x) for x in a.dims.split(",")]:
         r = subprocess.run(cmd + ["--one", str(dim)], timeout=900)
         if r.returncode != 0:  # a failed or faulted step ends the run: nothing more is started on the GPU
