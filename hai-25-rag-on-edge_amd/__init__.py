@@ -140,6 +140,7 @@ def lib():
         "vs_bf_search_topk_dev_multi": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "vs_ivf_load": (i32, [C.c_char_p, i32, i32, i32, C.POINTER(vp)]),
         "vs_ivf_create": (i32, [vp, i64, i32, vp, i32, vp, vp, i32, i32, i32, C.POINTER(vp)]),
+        "vs_ivf_create_nd_u8": (i32, [vp, i64, i32, vp, i32, vp, vp, i32, C.POINTER(vp)]),
         "vs_ivf_build": (i32, [vp, i64, i32, i32, i32, C.c_double, C.c_uint64, i32, vp, vp, C.POINTER(i32)]),
         "vs_ivf_build_nd": (i32, [vp, i64, i32, i32, i32, C.c_double, C.c_uint64, i32, vp, vp, C.POINTER(i32)]),
         "vs_ivf_build_index_nd": (i32, [vp, i64, i32, i32, i32, C.c_double, C.c_uint64, i32, C.POINTER(vp), C.POINTER(i32)]),
@@ -181,6 +182,7 @@ def lib():
         "vs_prof_enable": (i32, [vp, i32]),
         "vs_prof_read": (i32, [vp, i32, C.POINTER(C.c_double), C.POINTER(i64)]),
         "vs_ivf_widek_stats": (i32, [vp, C.POINTER(i64), i32]),
+        "vs_ivf_nd_u8_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_prof_read_launches": (i32, [vp, i32, vp, i64, C.POINTER(i64)]),
         "vs_index_rows": (i64, [vp]),
         "vs_index_dim": (i32, [vp]),
@@ -540,7 +542,9 @@ class IVFIndex(_Index):
     """class IVFIndex (IVFIndex.h:14-97) on the GPU, reordered (contiguous list) layout, L2.
 
     Any vector length 1 <= d <= 2048: 128-d arrays or directories give the specialised index, any other dimension a
-    general IVF index (fp32 rows, squared L2, k <= 16, one GPU; vsearch.h at vs_ivf_create)."""
+    general IVF index (fp32 rows, squared L2, k <= 16, one GPU; vsearch.h at vs_ivf_create).  ``from_u8`` takes uint8
+    rows instead (vs_ivf_create_nd_u8): at dimensions other than 128 the general index keeps a byte copy of the rows
+    beside the fp32 ones and scans it with int8 MFMA for every query that is byte valued itself; same results."""
 
     def __init__(self, index_dir: str | None = None, device: int = 0, rank: int = 0, world: int = 1, *,
                  vectors_reordered=None, centroids=None, cluster_offsets=None, reorder_to_original=None):
@@ -568,6 +572,44 @@ class IVFIndex(_Index):
         _check(build(_p(base), base.shape[0], base.shape[1], n_clusters, max_iter, tol, seed, device, C.byref(self._h), C.byref(it)))
         self.d = self.getDim()
         return self, int(it.value)
+
+    @classmethod
+    def from_u8(cls, vectors_reordered, centroids, cluster_offsets, reorder_to_original, device: int = 0):
+        """An index over uint8 rows [N, d] in the reordered layout (vs_ivf_create_nd_u8); centroids stay float."""
+        v = np.asarray(vectors_reordered)
+        if v.dtype != np.uint8:
+            raise ValueError("vectors_reordered must have dtype uint8")
+        if v.ndim != 2:
+            raise ValueError("vectors_reordered must be [N, d]")
+        v = np.ascontiguousarray(v)
+        c = _f32c(centroids)
+        off = np.ascontiguousarray(cluster_offsets, dtype=np.int32)
+        r2o = None if reorder_to_original is None else np.ascontiguousarray(reorder_to_original, dtype=np.int32)
+        self = cls.__new__(cls)
+        _Index.__init__(self)
+        _check(lib().vs_ivf_create_nd_u8(_p(v), v.shape[0], v.shape[1], _p(c), c.shape[0], _p(off),
+                                         _p(r2o) if r2o is not None else None, device, C.byref(self._h)))
+        self.d = self.getDim()
+        return self
+
+    @classmethod
+    def build_u8(cls, base_u8, n_clusters: int, max_iter: int = 100, tol: float = 1e-4, seed: int = 42, device: int = 0):
+        """ivf_build on the uint8 rows as float, then from_u8 on the reordered rows cast back (exact: the reordered rows
+        are the input's rows); returns (index, n_iter)."""
+        base = np.asarray(base_u8)
+        if base.dtype != np.uint8:
+            raise ValueError("base_u8 must have dtype uint8")
+        if base.ndim != 2:
+            raise ValueError("base_u8 must be [N, d]")
+        vr, off, r2o, cents, it = ivf_build(base.astype(np.float32), n_clusters, max_iter, tol, seed, device)
+        return cls.from_u8(vr.astype(np.uint8), cents, off, r2o, device), it
+
+    def nd_u8_stats(self, reset: bool = False):
+        """(pairs planned on the byte rows, pairs planned on the fp32 rows) of a from_u8 general index since the last
+        reset (vs_ivf_nd_u8_stats); a pair is a (query, probed non-empty list)."""
+        out = (C.c_int64 * 2)()
+        _check(lib().vs_ivf_nd_u8_stats(self._h, out, 1 if reset else 0))
+        return int(out[0]), int(out[1])
 
     def getNumVectors(self) -> int:
         return self.getNumDocs()

@@ -83,8 +83,9 @@ struct vs_index {
     // general index (vs_bf_create_nd with dim != 128, or VSEARCH_ND_FORCE): rows of dim_p = nd_dim_p(dim) floats, zero padded,
     // scanned by scan_nd_kernel; no int8 copy, no seed sample, no bf16 filter statistics.  Otherwise dim_p == dim == 128.
     // General IVF index (kind 1; vs_ivf_create / vs_ivf_load with dim != 128, or VSEARCH_IVF_ND_FORCE): rows and centroids
-    // laid out the same way, searched by the list-major general scan (ivf_group_nd_dev); no int8 copy, no tiled copy, no
-    // head rows, no chunk table.
+    // laid out the same way, searched by the list-major general scan (ivf_group_nd_dev); no tiled copy, no head rows, no
+    // chunk table, and no int8 copy unless the rows came as uint8 (vs_ivf_create_nd_u8: the byte fields below, scanned by
+    // ivf_scan_nd_i8_kernel for the queries that qualify).
     bool general = false;
     int dim_p = 0;
     vs::DevBuf<float> d_nd_qfrag;  // [kMaxMulti][dim_p / 16][2][64][4] scratch of launch_scan_nd
@@ -98,6 +99,7 @@ struct vs_index {
     vs::DevBuf<int32_t> d_nd_rterm;  // [n_rows + 64] sum (b - 128)^2
     vs::DevBuf<int8_t> d_nd_q8frag;  // [kMaxMulti][dim_b / 64][2][64][16] scratch of launch_scan_nd_i8
     vs::DevBuf<int32_t> d_nd_qterm;  // [kMaxMulti][32]
+    vs::DevBuf<unsigned long long> d_nd_stats;  // general IVF index from uint8 rows: (query, probe) pairs planned on bytes | on fp32
     int metric = VS_METRIC_L2;
     int64_t n_rows = 0;   // rows resident on this GPU
     int64_t n_total = 0;  // rows of the whole (unsharded) index
@@ -253,6 +255,11 @@ struct vs_index {
         vs::DevBuf<int32_t> items;   // [ivf_nd_items_cap(nlist, np_max)][2]
         vs::DevBuf<float> part_d;    // [kIvfNdGroupQ][np_max][kKcapMax]
         vs::DevBuf<int32_t> part_i;
+        // an index with a byte copy (vs_ivf_create_nd_u8): the byte plan's tables and the byte queries
+        vs::DevBuf<int32_t> plan8, slots8, items8;  // as plan / slots / items
+        vs::DevBuf<int8_t> q8rows;   // [kIvfNdGroupQ][dim_b]
+        vs::DevBuf<int32_t> qterm;   // [kIvfNdGroupQ]
+        vs::DevBuf<int32_t> valid;   // [kIvfNdGroupQ] 1: the query runs on bytes
         bool ready = false;          // every buffer above allocated
     } ivfnd;
     vs::Stream wide_stream[kWideLanesMax];
@@ -672,8 +679,8 @@ int refuse_general_bf(const vs_index* h, const char* what) { return h && h->kind
 int refuse_general_ivf(const vs_index* h, const char* what) {
     if (!h || !h->general || h->kind != 1) return VS_OK;
     char msg[200];
-    snprintf(msg, sizeof(msg), "%s: not available on a general-dimension IVF index (dim = %d): fp32 rows, squared L2, k <= 16, one GPU", what,
-             h->dim);
+    snprintf(msg, sizeof(msg), "%s: not available on a general-dimension IVF index (dim = %d): %ssquared L2, k <= 16, one GPU", what,
+             h->dim, h->nd_from_u8 ? "" : "fp32 rows, ");
     set_error(msg);
     return VS_ERR_UNSUPPORTED;
 }
@@ -1218,6 +1225,10 @@ int ensure_ivf_nd(vs_index* h) {
         (rc = W.items.alloc((size_t)2 * vs::ivf_nd_items_cap(h->nlist, W.np_max))) || (rc = W.part_d.alloc(pairs * kKcapMax)) ||
         (rc = W.part_i.alloc(pairs * kKcapMax)))
         return rc;
+    if (h->d_nd_u8 && ((rc = W.plan8.alloc((size_t)3 * h->nlist + 2)) || (rc = W.slots8.alloc(pairs)) ||
+                       (rc = W.items8.alloc((size_t)2 * vs::ivf_nd_items_cap(h->nlist, W.np_max))) ||
+                       (rc = W.q8rows.alloc(gq * h->dim_b)) || (rc = W.qterm.alloc(gq)) || (rc = W.valid.alloc(gq))))
+        return rc;
     W.ready = true;
     h->ivfnd = std::move(W);
     return VS_OK;
@@ -1225,7 +1236,9 @@ int ensure_ivf_nd(vs_index* h) {
 
 // One launch group of a general IVF index: nb <= 32 batches of B queries ([nb][B][dim], back to back), everything on s.
 // Coarse scores per batch are the brute-force general scan's on the centroid table (equal scores: the lower list id,
-// launch_pick_probes); then the plan, the list-major scan and the ranking of the group's partial lists.
+// launch_pick_probes); then the plan, the list-major scan and the ranking of the group's partial lists.  An index with a
+// byte copy of its rows plans twice: the pairs of the queries that qualify for the byte rows (IvfNdI8Params::valid) go to
+// ivf_scan_nd_i8_kernel, the others to ivf_scan_nd_kernel, both into the same partial lists.
 int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int nprobe, float* out_d, int32_t* out_i, hipStream_t s) {
     const int kcap = pick_kcap(k);
     if (!kcap) return refuse_general_ivf(h, "k > 16");
@@ -1266,10 +1279,37 @@ int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int 
     ip.part_d = W.part_d;
     ip.part_i = W.part_i;
     ip.cand_count = h->d_cand;
+    if (h->d_nd_stats) ip.pair_count = h->d_nd_stats + 1;
+    vs::IvfNdI8Params bp{};
+    const bool two_plans = (bool)h->d_nd_u8;
+    if (two_plans) {
+        bp.s = ip;
+        bp.s.list_cnt = W.plan8;
+        bp.s.list_start = W.plan8 + (size_t)2 * h->nlist;
+        bp.s.n_items = W.plan8 + (size_t)3 * h->nlist + 1;
+        bp.s.slots = W.slots8;
+        bp.s.items = W.items8;
+        bp.s.route = W.valid;
+        bp.s.route_want = 1;
+        bp.s.pair_count = h->d_nd_stats;
+        bp.vecs_u8 = h->d_nd_u8;
+        bp.rterm = h->d_nd_rterm;
+        bp.dim_b = h->dim_b;
+        bp.bmax = h->nd_bmax;
+        bp.all_f32 = h->precision == 1;
+        bp.q8rows = W.q8rows;
+        bp.qterm = W.qterm;
+        bp.valid = W.valid;
+        ip.route = W.valid;
+        ip.route_want = 0;
+        HIPCHK(vs::launch_ivf_nd_i8_prep(bp, s));
+    }
     HIPCHK(vs::launch_ivf_nd_plan(ip, s));
+    if (two_plans) HIPCHK(vs::launch_ivf_nd_plan_second(bp.s, s));
     stage_mark(h, 2, s);
     prof_begin(h, 1, s);
     HIPCHK(vs::launch_ivf_nd_scan(ip, h->num_cus, s));
+    if (two_plans) HIPCHK(vs::launch_ivf_nd_i8_scan(bp, h->num_cus, s));
     prof_end(h, 1, s);
     vs::MergeParams m{};
     m.part_d = W.part_d;
@@ -1872,6 +1912,22 @@ int vs_ivf_widek_stats(vs_index* h, int64_t* out, int reset) {
     return VS_OK;
 }
 
+int vs_ivf_nd_u8_stats(vs_index* h, int64_t* out, int reset) {
+    if (!h || h->kind != 1 || !h->d_nd_stats || !out) {
+        set_error("vs_ivf_nd_u8_stats: a general IVF index made by vs_ivf_create_nd_u8 and an output of two words");
+        return VS_ERR_INVALID;
+    }
+    int rc = set_device(h);
+    if (rc) return rc;
+    unsigned long long v[2];
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(v, h->d_nd_stats, sizeof(v), hipMemcpyDeviceToHost));
+    out[0] = (int64_t)v[0];
+    out[1] = (int64_t)v[1];
+    if (reset) HIPCHK(hipMemset(h->d_nd_stats, 0, sizeof(v)));
+    return VS_OK;
+}
+
 int vs_prof_read(vs_index* h, int which, double* total_ms, int64_t* launches) {
     if (!h || which < 0 || which > 1) return VS_ERR_INVALID;
     int rc = set_device(h);
@@ -2207,19 +2263,22 @@ static int build_tau_heads(vs_index* h, const float* vectors, const int32_t* off
     return VS_OK;
 }
 
+// rows_u8: the rows as uint8 instead of `vectors` (vs_ivf_create_nd_u8; unsharded): converted to float once the
+// arguments are checked, and kept as bytes beside the fp32 rows when the index is a general one
 static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const float* centroids, int nlist,
                            const int32_t* offsets, const int32_t* r2o, int device, int rank, int world,
-                           vs_index** out) {
-    if (!out || !vectors || !centroids || !offsets || n_rows <= 0 || nlist <= 0 || world < 1 || rank < 0 || rank >= world) {
-        set_error("vs_ivf_create: bad arguments");
+                           vs_index** out, const uint8_t* rows_u8 = nullptr) {
+    const std::string who = rows_u8 ? "vs_ivf_create_nd_u8" : "vs_ivf_create";
+    if (!out || (!vectors && !rows_u8) || !centroids || !offsets || n_rows <= 0 || nlist <= 0 || world < 1 || rank < 0 || rank >= world) {
+        set_error(who + ": bad arguments");
         return VS_ERR_INVALID;
     }
     if (dim < 1) {
-        set_error("vs_ivf_create: dim must be at least 1");
+        set_error(who + ": dim must be at least 1");
         return VS_ERR_INVALID;
     }
     if (dim > vs::kNdMaxDim) {
-        set_error("vs_ivf_create: dim > 2048 is not compiled in");
+        set_error(who + ": dim > 2048 is not compiled in");
         return VS_ERR_UNSUPPORTED;
     }
     if (dim != vs::kDim && world > 1) {
@@ -2240,6 +2299,12 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
     int rc = check_device(device);
     if (rc) return rc;
     HIPCHK(hipSetDevice(device));
+    std::vector<float> rows_f32;
+    if (rows_u8) {  // (exact: every byte is a float)
+        rows_f32.resize((size_t)n_rows * dim);
+        for (size_t i = 0; i < rows_f32.size(); ++i) rows_f32[i] = (float)rows_u8[i];
+        vectors = rows_f32.data();
+    }
     vs_index* h = new (std::nothrow) vs_index();
     if (!h) {
         set_error("out of host memory");
@@ -2323,6 +2388,12 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
         h->ivf_lanes = 1;
         h->ivf_nsb = 1;
         for (int c = 0; c < nlist; ++c) h->max_list = std::max(h->max_list, loc_off[c + 1] - loc_off[c]);
+        if (rows_u8) {  // (unsharded: the local rows are the caller's) the byte copy, unless max ||b||^2 >= 2^24, and the pair counters
+            h->nd_from_u8 = true;
+            h->dim_b = vs::nd_dim_b(dim);
+            if ((rc = build_nd_u8_copy(h, rows_u8, n_local)) || (rc = h->d_nd_stats.alloc(2))) return fail(rc);
+            if (hipMemset(h->d_nd_stats, 0, 2 * sizeof(unsigned long long)) != hipSuccess) return fail(VS_ERR_DEVICE);
+        }
         if ((rc = alloc_scratch(h)) || (rc = ensure_ivf_nd(h)) || (rc = ensure_wide_streams(h)) || (rc = ensure_ivf_host(h))) return fail(rc);
         *out = h;
         return VS_OK;
@@ -2772,6 +2843,19 @@ int vs_ivf_create(const float* vectors_reordered, int64_t n_rows, int dim, const
     return guarded([&]() -> int {
         return ivf_create_impl(vectors_reordered, n_rows, dim, centroids, nlist, cluster_offsets, reorder_to_original, device, rank,
                                world, out);
+    });
+}
+
+// uint8 rows: vs_ivf_create's checks and index, unsharded, plus the byte copy on a general index
+int vs_ivf_create_nd_u8(const uint8_t* vectors_reordered, int64_t n_rows, int dim, const float* centroids, int nlist,
+                        const int32_t* cluster_offsets, const int32_t* reorder_to_original, int device, vs_index** out) {
+    return guarded([&]() -> int {
+        if (!vectors_reordered) {
+            set_error("vs_ivf_create_nd_u8: bad arguments");
+            return VS_ERR_INVALID;
+        }
+        return ivf_create_impl(nullptr, n_rows, dim, centroids, nlist, cluster_offsets, reorder_to_original, device, 0, 1, out,
+                               vectors_reordered);
     });
 }
 

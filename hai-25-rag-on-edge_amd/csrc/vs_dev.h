@@ -7,6 +7,7 @@
 namespace vs {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 #define VS_INF __builtin_huge_valf()
 
@@ -15,6 +16,20 @@ __device__ __forceinline__ float next_up(float x) {
     if (x == 0.f) return __builtin_bit_cast(float, 1);
     const int b = __builtin_bit_cast(int, x);
     return __builtin_bit_cast(float, b + (b >= 0 ? 1 : -1));
+}
+
+// The byte scans of a general index (vs_scan_nd_i8.hip, vs_ivf_nd_i8.hip) run a query only when the fp32 path is exact
+// for it: ||q||^2 + ||b||^2 at most this
+constexpr int kNd8NormLimit = 1 << 24;
+
+// x as an integer in [0, 255], or false (NaN and infinities included)
+__device__ __forceinline__ bool byte_value(float x, int& xi) {
+    xi = 128;
+    if (!(x >= 0.f && x <= 255.f)) return false;
+    const int v = (int)x;
+    if ((float)v != x) return false;
+    xi = v;
+    return true;
 }
 
 __device__ __forceinline__ bool lex_lt(float d0, int i0, float d1, int i1) {

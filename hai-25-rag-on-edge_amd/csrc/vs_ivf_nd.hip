@@ -4,7 +4,9 @@
 //   ivf_nd_prep     : the launch group's queries zero-padded row-major [group_q][dim_p] and their squared norms in
 //                     nd_prep_kernel's summation order; clears the plan's counters.
 //   ivf_nd_count    : one thread per (query, probe rank) pair: pairs per list, rows per pair (total_candidates), and the
-//                     pair's partial list preset to (+inf, -1).
+//                     pair's partial list preset to (+inf, -1).  An index with a byte copy of its rows
+//                     (vs_ivf_create_nd_u8) keeps two plans per group and routes every query to one of them
+//                     (IvfNdParams::route); its second plan's count leaves the preset and the candidates alone.
 //   ivf_nd_prefix   : one workgroup: prefix of the pair counts over the lists -> the first slot of every list's run, and
 //                     the item table -- (list, first slot) for every 16 slots of a probed list that holds rows.
 //   ivf_nd_fill     : one thread per pair: the pair's slot (query << 8 | rank) into its list's run.  The order inside a
@@ -65,30 +67,44 @@ __global__ __launch_bounds__(256) void ivf_nd_prep(const IvfNdParams p) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < 2 * p.nlist; i += gridDim.x * 256) p.list_cnt[i] = 0;
 }
 
-// the list a pair probes, or -1 when it yields no slot (no probe, or a list without rows)
+// the list a pair probes, or -1 when it yields no slot in this plan (no probe, a list without rows, or a query routed to
+// the group's other plan); rows = the probed list's length either way
 __device__ __forceinline__ int ivf_nd_pair_list(const IvfNdParams& p, int pair, int& rows) {
     const int c = p.probes[pair];
     rows = (c >= 0 && c < p.nlist) ? p.offsets[c + 1] - p.offsets[c] : 0;
-    return rows > 0 ? c : -1;
+    if (rows <= 0) return -1;
+    if (p.route && p.route[pair / p.nprobe] != p.route_want) return -1;
+    return c;
 }
 
-// grid = ceil(group_q * nprobe / 256), 256 threads
-__global__ __launch_bounds__(256) void ivf_nd_count(const IvfNdParams p) {
+// grid = ceil(group_q * nprobe / 256), 256 threads.  first: the group's first (or only) plan, which also presets the
+// partial lists and counts the candidates
+__global__ __launch_bounds__(256) void ivf_nd_count(const IvfNdParams p, const int first) {
     const int pair = blockIdx.x * 256 + threadIdx.x;
-    int rows = 0;
+    int rows = 0, got = 0;
     if (pair < p.group_q * p.nprobe) {
         const int c = ivf_nd_pair_list(p, pair, rows);
-        if (c >= 0) atomicAdd(p.list_cnt + c, 1);
-        for (int j = 0; j < p.kcap; ++j) {
-            p.part_d[(int64_t)pair * p.kcap + j] = VS_INF;
-            p.part_i[(int64_t)pair * p.kcap + j] = -1;
+        if (c >= 0) {
+            atomicAdd(p.list_cnt + c, 1);
+            got = 1;
         }
+        if (first)
+            for (int j = 0; j < p.kcap; ++j) {
+                p.part_d[(int64_t)pair * p.kcap + j] = VS_INF;
+                p.part_i[(int64_t)pair * p.kcap + j] = -1;
+            }
     }
-    if (p.cand_count) {
+    if (first && p.cand_count) {
         unsigned long long t = (unsigned long long)rows;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
         if ((threadIdx.x & 63) == 0 && t) atomicAdd(p.cand_count, t);
+    }
+    if (p.pair_count) {
+        int t = got;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+        if ((threadIdx.x & 63) == 0 && t) atomicAdd(p.pair_count, (unsigned long long)t);
     }
 }
 
@@ -256,7 +272,17 @@ hipError_t launch_ivf_nd_plan(const IvfNdParams& p, hipStream_t s) {
         return hipErrorInvalidValue;
     const int pairs = p.group_q * p.nprobe;
     hipLaunchKernelGGL(ivf_nd_prep, dim3((p.group_q + kMaxBatch - 1) / kMaxBatch), dim3(256), 0, s, p);
-    hipLaunchKernelGGL(ivf_nd_count, dim3((pairs + 255) / 256), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(ivf_nd_count, dim3((pairs + 255) / 256), dim3(256), 0, s, p, 1);
+    hipLaunchKernelGGL(ivf_nd_prefix, dim3(1), dim3(1024), 0, s, p);
+    hipLaunchKernelGGL(ivf_nd_fill, dim3((pairs + 255) / 256), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_ivf_nd_plan_second(const IvfNdParams& p, hipStream_t s) {
+    if (p.group_q < 1 || p.group_q > kIvfNdGroupQ || p.nprobe < 1 || p.nprobe > kIvfMaxProbe || p.nlist < 1 || !p.route)
+        return hipErrorInvalidValue;
+    const int pairs = p.group_q * p.nprobe;
+    hipLaunchKernelGGL(ivf_nd_count, dim3((pairs + 255) / 256), dim3(256), 0, s, p, 0);
     hipLaunchKernelGGL(ivf_nd_prefix, dim3(1), dim3(1024), 0, s, p);
     hipLaunchKernelGGL(ivf_nd_fill, dim3((pairs + 255) / 256), dim3(256), 0, s, p);
     return hipGetLastError();

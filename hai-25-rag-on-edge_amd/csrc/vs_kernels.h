@@ -530,8 +530,39 @@ struct IvfNdParams {
     float* part_d;            // [group_q][nprobe][kcap] (pairs without an item: (+inf, -1))
     int32_t* part_i;          // reordered row positions
     unsigned long long* cand_count;  // += rows of every probed list, per (query, probe) pair
+    // the per-query route of an index that keeps two plans per group (vs_ivf_create_nd_u8): a pair gets a slot in this
+    // plan only when route[query] == route_want.  Null: every pair, as on a vs_ivf_create index.
+    const int32_t* route;     // [group_q]
+    int route_want;
+    unsigned long long* pair_count;  // += pairs that got a slot in this plan (null: not counted)
 };
 hipError_t launch_ivf_nd_plan(const IvfNdParams& p, hipStream_t s);
+// a group's second plan: the pair counts, prefix and fill of launch_ivf_nd_plan on p's own plan tables -- no query
+// preparation, no preset of the partial lists, no candidate count (the first plan's launches did those), and p's
+// list_cnt cleared by the caller's earlier launch (launch_ivf_nd_i8_prep)
+hipError_t launch_ivf_nd_plan_second(const IvfNdParams& p, hipStream_t s);
 hipError_t launch_ivf_nd_scan(const IvfNdParams& p, int grid, hipStream_t s);
+
+// ---- the same on the byte copy of a general IVF index made from uint8 rows (vs_ivf_nd_i8.hip).
+// launch_ivf_nd_i8_prep writes the group's queries as int8 (x - 128), zero padded, row-major [group_q][dim_b], qterm =
+// sum (q - 128)^2 and valid[query]: 1 when the query runs on bytes -- every value an integer in [0, 255] and ||q||^2 +
+// bmax <= 2^24, checked in integers (nd_prep_i8_kernel's rules, per query) -- and 0 otherwise or when all_f32 is set; it
+// also clears s.list_cnt.  s is the byte plan (route = valid, route_want = 1); the caller's fp32 plan takes route_want =
+// 0 on the same words.  launch_ivf_nd_i8_scan scores the byte plan's items with v_mfma_i32_16x16x64_i8 and writes
+// (float)(qterm + rterm - 2 q'.b') -- the integer the fp32 scan computes exactly for such a query -- into the shared
+// partial lists; a pair has one writer.
+struct IvfNdI8Params {
+    IvfNdParams s;            // vecs / vnorm / qrows / qnorm are not read
+    const int8_t* vecs_u8;    // [n_rows + kScanPadRows][dim_b] bytes (x - 128), zero padded
+    const int32_t* rterm;     // [n_rows + 64] sum (b - 128)^2
+    int dim_b;                // nd_dim_b(dim)
+    int32_t bmax;             // max over the rows of ||b||^2, < 2^24
+    int all_f32;              // vs_set_precision(1): no query runs on bytes
+    int8_t* q8rows;           // scratch [kIvfNdGroupQ][dim_b]
+    int32_t* qterm;           // scratch [kIvfNdGroupQ]
+    int32_t* valid;           // scratch [kIvfNdGroupQ]
+};
+hipError_t launch_ivf_nd_i8_prep(const IvfNdI8Params& p, hipStream_t s);
+hipError_t launch_ivf_nd_i8_scan(const IvfNdI8Params& p, int grid, hipStream_t s);
 
 }  // namespace vs

@@ -33,22 +33,10 @@
 
 namespace vs {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kNd8Tiles = 4;                          // 16-row tiles per wave block
 constexpr int kNd8BlockRows = kNd8Tiles * kTileRows;  // 64 <= kScanPadRows: a block never reads past the spare rows
 static_assert(kNd8BlockRows <= kScanPadRows, "row blocks are loaded unclamped");
-constexpr int kNd8NormLimit = 1 << 24;                // ||q||^2 + ||b||^2 at most this: the fp32 path is exact
-
-// x as an integer in [0, 255], or false (NaN and infinities included)
-__device__ __forceinline__ bool byte_value(float x, int& xi) {
-    xi = 128;
-    if (!(x >= 0.f && x <= 255.f)) return false;
-    const int v = (int)x;
-    if ((float)v != x) return false;
-    xi = v;
-    return true;
-}
+// (byte_value and kNd8NormLimit, the exactness rule's pieces, are in vs_dev.h: the IVF byte scan shares them)
 
 // grid = n_batches, 256 threads
 __global__ __launch_bounds__(256) void nd_prep_i8_kernel(const float* __restrict__ q, int64_t q_batch_stride, int nq_valid, int dim,

@@ -313,11 +313,41 @@ VS_API int vs_ivf_load(const char* index_dir, int device, int rank, int world, v
  *   VS_ERR_UNSUPPORTED, with the dimension in the message: 17 <= k <= 128, vs_set_precision 2,
  *     vs_ivf_set_metric(VS_METRIC_IP), vs_ivf_widek_stats, every sharded and virtual-shard call.
  * vs_ivf_build and vs_ivf_build_index stay 128-d only; vs_ivf_build_nd and vs_ivf_build_index_nd
- * build at every dimension this creator takes. */
+ * build at every dimension this creator takes.  A general IVF index that also keeps its rows as
+ * bytes and scans them with int8 MFMA comes from vs_ivf_create_nd_u8 below, not from this creator. */
 VS_API int vs_ivf_create(const float* vectors_reordered, int64_t n_rows, int dim,
                          const float* centroids, int nlist, const int32_t* cluster_offsets,
                          const int32_t* reorder_to_original, int device, int rank, int world,
                          vs_index** out);
+
+/* Byte-valued rows at any vector length: vectors_reordered is uint8 [n_rows][dim], 1 <= dim <=
+ * 2048; the centroids stay float [nlist][dim]; the index is unsharded.  Checks in vs_ivf_create's
+ * order (the first four need no device): null pointers, n_rows / nlist <= 0 -> VS_ERR_INVALID;
+ * dim < 1 -> VS_ERR_INVALID; dim > 2048 -> VS_ERR_UNSUPPORTED; offsets that do not cover the rows
+ * or are not monotone -> VS_ERR_INVALID; then the device.
+ *
+ * dim == 128 gives the index vs_ivf_create gives for the same rows converted to float (same
+ * launches, same results; VSEARCH_IVF_ND_FORCE=1 builds the general form here too).  Any other
+ * dim gives the general IVF index of vs_ivf_create PLUS the reordered rows once more as int8
+ * (x - 128), padded to 64 bytes, with an int32 term per row: about 1.25 x the device memory (more
+ * below 64-d).  As for vs_bf_create_nd_u8 the byte copy is not kept when max ||b||^2 >= 2^24.
+ *
+ * Results: ids, distances and *total_candidates are what vs_ivf_create's index returns for the
+ * same rows converted to float, for every query and every call.  Coarse scores and probes are
+ * computed as there, on the fp32 centroids; the byte copy only changes which kernel scans a
+ * (query, list) pair.  The exactness rule of vs_bf_create_nd_u8 is applied PER QUERY: a query is
+ * scanned on the byte rows only when every value of it is an integer in [0, 255] and ||q||^2 +
+ * max ||b||^2 <= 2^24, both checked on the device in integers; every other query of the same
+ * launch group is scanned on the fp32 rows.  No host synchronisation, nothing is rerun,
+ * everything stays on the caller's stream.
+ *
+ * Accepted and refused calls: as vs_ivf_create's general index, except vs_set_precision: 0
+ * (default) and 2 use the byte rows for the queries that qualify, 1 scans every pair on the fp32
+ * rows, 2 returns VS_ERR_UNSUPPORTED when the byte copy was not kept.  vs_ivf_save writes float
+ * arrays: vs_ivf_load of them gives an fp32 general index. */
+VS_API int vs_ivf_create_nd_u8(const uint8_t* vectors_reordered, int64_t n_rows, int dim,
+                               const float* centroids, int nlist, const int32_t* cluster_offsets,
+                               const int32_t* reorder_to_original, int device, vs_index** out);
 
 /* GPU index builder, the device side of build_ivf_index_reordered (create_ivf_model_reordered.py:82-177):
  * Lloyd k-means under L2 with sklearn's stopping rule (sum of squared centre shifts <= tol * mean feature
@@ -532,6 +562,10 @@ VS_API int vs_prof_read(vs_index* h, int which, double* total_ms, int64_t* launc
  * of their probed lists (no bound, or a candidate list overflowed), out[3] = launch groups whose candidate buffers
  * overflowed (all their queries ranked exactly).  Synchronises the device; reset != 0 clears the counters. */
 VS_API int vs_ivf_widek_stats(vs_index* h, int64_t* out /* [4] */, int reset);
+/* Which rows the list scan of a vs_ivf_create_nd_u8 general index read: out[0] = (query, probe) pairs that got a slot in
+ * the byte plan since the last reset, out[1] = the same for the fp32 plan (pairs that probe an empty list get neither).
+ * Always counted.  Synchronises the device; reset != 0 clears the counters.  VS_ERR_INVALID on any other kind of index. */
+VS_API int vs_ivf_nd_u8_stats(vs_index* h, int64_t* out /* [2] */, int reset);
 /* per-launch durations (ms) of the same window, oldest first; *launches = how many there were (may exceed cap).
  * One brute-force launch serves up to 32 batches: the CLIs turn these into the per-batch statistics of
  * main.cpp:262-330 (avg / stddev / min / max / P50 / P95 / P99 "graph execute time"). */

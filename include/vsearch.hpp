@@ -214,6 +214,12 @@ public:
         (void)backendPath;
         check(vs_ivf_load(indexDir.c_str(), device, rank, world, &h_));
     }
+    // uint8 rows in the reordered layout (vs_ivf_create_nd_u8): at dimensions other than 128 the general IVF index plus
+    // a byte copy of the rows, scanned with int8 MFMA for the queries that are byte valued themselves; same results.
+    IVFIndex(const uint8_t* vectorsReordered, int64_t rows, int dim, const float* centroids, int nlist,
+             const int32_t* clusterOffsets, const int32_t* reorderToOriginal, int device = 0) {
+        check(vs_ivf_create_nd_u8(vectorsReordered, rows, dim, centroids, nlist, clusterOffsets, reorderToOriginal, device, &h_));
+    }
     ~IVFIndex() { vs_destroy(h_); }
     IVFIndex(const IVFIndex&) = delete;
     IVFIndex& operator=(const IVFIndex&) = delete;

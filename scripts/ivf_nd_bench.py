@@ -1,7 +1,7 @@
 """List-major IVF at a general dimension against exact brute force on the same rows: device time per 1024 queries.
 
     python scripts/ivf_nd_bench.py [--dims 96,384,768] [--rows 1000000] [--nlist 1024] [--nprobe 8,32] [--groups 4] [--reps 5]
-                                   [--build ITERS]
+                                   [--build ITERS] [--u8]
 
 Data: synth_sift rows (integer valued) at every dimension, nlist sampled rows as centroids, every row assigned to its
 nearest centroid through the library's own brute force (a timing index, not a trained one).  Queries: `groups` groups of
@@ -17,6 +17,13 @@ iterations at tol = 0, seed 42) and prints one more JSON line: the build's wall 
 pass (vs_ivf_build_last_assign_ms) and the iterations done; after the brute-force timing, a line that sets the assignment
 pass against its yardstick, nlist / 32 x the per-batch time of the brute-force general scan on the same rows.  At dim 128
 it prints the wall time of the specialised builder and of the general one (VSEARCH_BUILD_ND_FORCE=1), alternated, and stops.
+
+--u8 takes the rows as uint8 (synth_sift rows are byte valued) and alternates three paths on them in one process: the
+byte index (IVFIndex.from_u8: vs_ivf_create_nd_u8, paths ivf_u8_nprobeP), the vs_ivf_create index on the rows as float
+(ivf_nprobeP, the yardstick) and exact brute force.  Both indexes must return the same ids and distance bits.  After the
+end-to-end windows it times the list-scan launches alone (vs_prof_read(.., 1): the fp32 scan on one index, the fp32 scan
+on an empty plan plus the byte scan on the other), again alternated, and prints the byte index's pair counts
+(vs_ivf_nd_u8_stats: pairs planned on bytes, pairs planned on fp32).
 """
 import argparse
 import json
@@ -133,8 +140,16 @@ def search(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st, assign_pass_ms):
     qd = torch.from_numpy(q).to(dev)
     nbg = GROUP_Q // B
     nprobes = [int(x) for x in a.nprobe.split(",")]
-    with pkg.BruteForceIndex(base) as bf, pkg.IVFIndex(vectors_reordered=vr, centroids=cents, cluster_offsets=off,
-                                                       reorder_to_original=r2o) as ivf:
+    import contextlib
+    with contextlib.ExitStack() as stack:
+        bf = stack.enter_context(pkg.BruteForceIndex(base))
+        ivf = stack.enter_context(pkg.IVFIndex(vectors_reordered=vr, centroids=cents, cluster_offsets=off, reorder_to_original=r2o))
+        ivf8 = None
+        if a.u8:
+            rows_u8 = vr.astype(np.uint8)
+            assert np.array_equal(rows_u8.astype(np.float32), vr), "--u8 needs byte-valued rows"
+            ivf8 = stack.enter_context(pkg.IVFIndex.from_u8(rows_u8, cents, off, r2o))
+            del rows_u8
         del vr
         bf.set_precision(1)
         bi = torch.empty((a.groups * GROUP_Q, K + 1), dtype=torch.int32, device=dev)
@@ -148,10 +163,10 @@ def search(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st, assign_pass_ms):
                 o = g * GROUP_Q
                 bf.search_dev_multi(qd[o].data_ptr(), nbg, B, K, bi[o].data_ptr(), bd[o].data_ptr(), bfl[o].data_ptr(), st)
 
-        def run_ivf(nprobe):
+        def run_ivf(nprobe, index=ivf):
             for g in range(a.groups):
                 o = g * GROUP_Q
-                ivf.search_dev_multi(qd[o].data_ptr(), nbg, B, K, nprobe, ii[o].data_ptr(), idd[o].data_ptr(), st)
+                index.search_dev_multi(qd[o].data_ptr(), nbg, B, K, nprobe, ii[o].data_ptr(), idd[o].data_ptr(), st)
 
         def timed(f, *args):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -162,7 +177,9 @@ def search(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st, assign_pass_ms):
             return e0.elapsed_time(e1) * 1e3 / a.groups  # us per 1024 queries
 
         paths = [("bf", run_bf, ())] + [(f"ivf_nprobe{p}", run_ivf, (p,)) for p in nprobes]
-        recall = {}
+        if a.u8:
+            paths += [(f"ivf_u8_nprobe{p}", run_ivf, (p, ivf8)) for p in nprobes]
+        recall, results = {}, {}
         for name, f, args in paths:  # warm-up of every path, and the recall of the IVF ones
             f(*args)
             f(*args)
@@ -172,6 +189,11 @@ def search(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st, assign_pass_ms):
             else:
                 got = ii.cpu().numpy()
                 recall[name] = float(np.mean([len(set(got[i]) & set(exact[i])) / K for i in range(len(exact))]))
+                results[name] = (got, idd.cpu().numpy().view(np.int32).copy())
+        if a.u8:  # faster and different is not faster: the byte index returns the fp32 index's ids and distance bits
+            for p in nprobes:
+                x, y = results[f"ivf_nprobe{p}"], results[f"ivf_u8_nprobe{p}"]
+                assert np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1]), f"byte index differs at nprobe {p}"
         us = {name: [] for name, _, _ in paths}
         for _ in range(a.reps):
             for name, f, args in paths:
@@ -190,6 +212,27 @@ def search(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st, assign_pass_ms):
                 rec["speedup_vs_bf"] = round(med["bf"] / med[name], 2)
                 rec["bytes_ratio"] = round((GROUP_Q / B) / (GROUP_Q * args[0] / 16.0 / a.nlist), 2)
             print(json.dumps(rec), flush=True)
+        if a.u8:  # the list-scan launches alone (vs_prof_read window 1), the two indexes alternated
+            scan = {(name, p): [] for name in ("fp32", "u8") for p in nprobes}
+            for _ in range(a.reps):
+                for p in nprobes:
+                    for name, index in (("fp32", ivf), ("u8", ivf8)):
+                        index.prof_enable(True)
+                        run_ivf(p, index)
+                        torch.cuda.synchronize()
+                        ms, n = index.prof_read(1)
+                        index.prof_enable(False)
+                        assert n == a.groups
+                        scan[(name, p)].append(ms / n)
+            for p in nprobes:
+                ivf8.nd_u8_stats(reset=True)
+                run_ivf(p, ivf8)
+                on_bytes, on_fp32 = ivf8.nd_u8_stats()
+                f, b = sorted(scan[("fp32", p)]), sorted(scan[("u8", p)])
+                print(json.dumps({"what": "list_scan_ms_per_group", "dim": dim, "nprobe": p, "fp32_index": [round(x, 3) for x in scan[("fp32", p)]],
+                                  "u8_index": [round(x, 3) for x in scan[("u8", p)]], "fp32_median": round(f[len(f) // 2], 3),
+                                  "u8_median": round(b[len(b) // 2], 3), "ratio": round(f[len(f) // 2] / b[len(b) // 2], 2),
+                                  "pairs_on_bytes": on_bytes, "pairs_on_fp32": on_fp32}), flush=True)
 
 
 def main():
@@ -201,13 +244,14 @@ def main():
     ap.add_argument("--groups", type=int, default=4)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--build", type=int, default=0, metavar="ITERS", help="train the index with the library's builder")
+    ap.add_argument("--u8", action="store_true", help="rows as uint8: the byte index beside the vs_ivf_create index and brute force")
     ap.add_argument("--one", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.one:
         one(a, a.one)
         return
     cmd = [sys.executable, os.path.abspath(__file__), "--rows", str(a.rows), "--nlist", str(a.nlist), "--nprobe", a.nprobe,
-           "--groups", str(a.groups), "--reps", str(a.reps), "--build", str(a.build)]
+           "--groups", str(a.groups), "--reps", str(a.reps), "--build", str(a.build)] + (["--u8"] if a.u8 else [])
     for dim in [int(x) for x in a.dims.split(",")]:
         r = subprocess.run(cmd + ["--one", str(dim)], timeout=900)
         if r.returncode != 0:  # a failed or faulted step ends the run: nothing more is started on the GPU
