@@ -183,6 +183,9 @@ def lib():
         "vs_prof_read": (i32, [vp, i32, C.POINTER(C.c_double), C.POINTER(i64)]),
         "vs_ivf_widek_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_ivf_nd_u8_stats": (i32, [vp, C.POINTER(i64), i32]),
+        "vs_ivf_nd_widek_stats": (i32, [vp, C.POINTER(i64), i32]),
+        "vs_ivf_search_topk": (i32, [vp, vp, i64, i32, i32, vp, vp, C.POINTER(i64), C.POINTER(Timing)]),
+        "vs_ivf_search_topk_dev_multi": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "vs_prof_read_launches": (i32, [vp, i32, vp, i64, C.POINTER(i64)]),
         "vs_index_rows": (i64, [vp]),
         "vs_index_dim": (i32, [vp]),
@@ -655,6 +658,31 @@ class IVFIndex(_Index):
                          stream: int):
         """n_batches independent batches [n_batches][B][dim] -> [n_batches][B][k]; asynchronous on `stream`."""
         _check(lib().vs_ivf_search_dev_multi(self._h, q_ptr, n_batches, B, k, nprobe, ids_ptr, dists_ptr, stream))
+
+    def search_topk(self, queries, k: int, nprobe: int, timing: Timing | None = None):
+        """searchBatch for 1 <= k <= 128 on every IVF index (vs_ivf_search_topk): k <= 16, and every k on a 128-d index, is
+        searchBatch itself; 17 <= k <= 128 on a general index takes the wide-k pipeline on the fp32 rows.  Returns (ids,
+        dists, total_candidates)."""
+        q = _f32c(queries).reshape(-1, self.d)
+        nq = q.shape[0]
+        ids = np.empty((nq, max(k, 0)), dtype=np.int32)
+        dists = np.empty((nq, max(k, 0)), dtype=np.float32)
+        total = C.c_int64(0)
+        tm = timing if timing is not None else Timing()
+        _check(lib().vs_ivf_search_topk(self._h, _p(q), nq, k, nprobe, _p(ids), _p(dists), C.byref(total), C.byref(tm)))
+        return ids, dists, int(total.value)
+
+    def search_topk_dev_multi(self, q_ptr: int, n_batches: int, B: int, k: int, nprobe: int, ids_ptr: int, dists_ptr: int,
+                              stream: int):
+        """search_dev_multi for 1 <= k <= 128 on every IVF index (vs_ivf_search_topk_dev_multi); asynchronous on `stream`."""
+        _check(lib().vs_ivf_search_topk_dev_multi(self._h, q_ptr, n_batches, B, k, nprobe, ids_ptr, dists_ptr, stream))
+
+    def nd_widek_stats(self, reset: bool = False):
+        """(candidates ranked from candidate lists, most candidates of one query, queries ranked by the exact fallback) of
+        the wide-k calls on a general index since the last reset (vs_ivf_nd_widek_stats)."""
+        out = (C.c_int64 * 3)()
+        _check(lib().vs_ivf_nd_widek_stats(self._h, out, 1 if reset else 0))
+        return tuple(int(v) for v in out)
 
     def search_dev_sharded(self, comm: "Comm", q_ptr: int, n_batches: int, B: int, k: int, nprobe: int, ids_ptr: int,
                            dists_ptr: int, stream: int):

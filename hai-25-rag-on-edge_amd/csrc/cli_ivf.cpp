@@ -78,7 +78,7 @@ int main(int argc, char* argv[]) {
             vsearch::IVFIndex::SearchTiming wt;
             if (wn > 0) {
                 if (ranks.world > 1) ivf.searchBatchSharded(ranks.comm, wq, (int)wn, TOP_K, NPROBE, wi, ws, wt);
-                else ivf.searchBatch(wq, (int)wn, TOP_K, NPROBE, wi, ws, wt);
+                else ivf.searchBatchTopk(wq, (int)wn, TOP_K, NPROBE, wi, ws, wt);
             }
         }
         auto total_start = std::chrono::high_resolution_clock::now();
@@ -95,7 +95,7 @@ int main(int argc, char* argv[]) {
             vsearch::IVFIndex::SearchTiming timing;
             auto b0 = std::chrono::high_resolution_clock::now();
             if (ranks.world > 1) total_candidates += ivf.searchBatchSharded(ranks.comm, batch, (int)cur, TOP_K, NPROBE, bi, bs, timing);
-            else total_candidates += ivf.searchBatch(batch, (int)cur, TOP_K, NPROBE, bi, bs, timing);
+            else total_candidates += ivf.searchBatchTopk(batch, (int)cur, TOP_K, NPROBE, bi, bs, timing);  // (k up to 128 at every dimension)
             auto b1 = std::chrono::high_resolution_clock::now();
             const double call_ms = std::chrono::duration<double, std::milli>(b1 - b0).count();
             const size_t n_b = (cur + (size_t)std::max(BATCH_SIZE, 1) - 1) / (size_t)std::max(BATCH_SIZE, 1);

@@ -262,6 +262,16 @@ struct vs_index {
         vs::DevBuf<int32_t> valid;   // [kIvfNdGroupQ] 1: the query runs on bytes
         bool ready = false;          // every buffer above allocated
     } ivfnd;
+    // ... and what a wide-k group (17 <= k <= 128, ivf_group_nd_wide_dev) needs beside it, allocated on the first such call
+    struct IvfNdWide {
+        vs::DevBuf<int32_t> plan, slots, items;  // the rescan plan's tables, as IvfNd's
+        vs::DevBuf<float> tau;       // [kIvfNdGroupQ]
+        vs::DevBuf<int32_t> mask;    // [kIvfNdGroupQ * np_max] saturated pairs
+        vs::DevBuf<int32_t> cnt;     // [kIvfNdGroupQ] candidates per query (zero between groups)
+        vs::DevBuf<unsigned long long> cand;   // [kIvfNdGroupQ][kIvfNdWideCand] keys
+        vs::DevBuf<unsigned long long> stats;  // [3]: see vs_ivf_nd_widek_stats
+        bool ready = false;          // every buffer above allocated (ensure_ivf_nd_wide)
+    } ivfndw;
     vs::Stream wide_stream[kWideLanesMax];
     vs::Event wide_fork, wide_join[kWideLanesMax];
     bool wide_streams_ready = false;
@@ -1234,6 +1244,54 @@ int ensure_ivf_nd(vs_index* h) {
     return VS_OK;
 }
 
+// ... of its wide-k groups, the same way
+int ensure_ivf_nd_wide(vs_index* h) {
+    if (h->ivfndw.ready) return VS_OK;
+    int rc = ensure_ivf_nd(h);
+    if (rc) return rc;
+    vs_index::IvfNdWide W;
+    const size_t gq = vs::kIvfNdGroupQ, pairs = gq * h->ivfnd.np_max;
+    if ((rc = W.plan.alloc((size_t)3 * h->nlist + 2)) || (rc = W.slots.alloc(pairs)) ||
+        (rc = W.items.alloc((size_t)2 * vs::ivf_nd_items_cap(h->nlist, h->ivfnd.np_max))) || (rc = W.tau.alloc(gq)) ||
+        (rc = W.mask.alloc(pairs)) || (rc = W.cnt.alloc(gq)) || (rc = W.cand.alloc(gq * vs::kIvfNdWideCand)) || (rc = W.stats.alloc(3)))
+        return rc;
+    HIPCHK(hipMemset(W.cnt, 0, gq * sizeof(int32_t)));
+    HIPCHK(hipMemset(W.stats, 0, 3 * sizeof(unsigned long long)));
+    W.ready = true;
+    h->ivfndw = std::move(W);
+    return VS_OK;
+}
+
+// the fp32 plan of a launch group of a general IVF index on the index's own tables, every pair
+vs::IvfNdParams ivf_nd_params(vs_index* h, const float* q_dev, int group_q, int k, int kcap, int nprobe) {
+    vs_index::IvfNd& W = h->ivfnd;
+    vs::IvfNdParams ip{};
+    ip.vecs = h->d_vecs;
+    ip.vnorm = h->d_norm;
+    ip.offsets = h->d_offsets;
+    ip.nlist = h->nlist;
+    ip.dim = h->dim;
+    ip.dim_p = h->dim_p;
+    ip.q = q_dev;
+    ip.group_q = group_q;
+    ip.nprobe = nprobe;
+    ip.k = k;
+    ip.kcap = kcap;
+    ip.probes = W.probes;
+    ip.qrows = W.qrows;
+    ip.qnorm = W.qnorm;
+    ip.list_cnt = W.plan;
+    ip.list_start = W.plan + (size_t)2 * h->nlist;
+    ip.n_items = W.plan + (size_t)3 * h->nlist + 1;
+    ip.slots = W.slots;
+    ip.items = W.items;
+    ip.part_d = W.part_d;
+    ip.part_i = W.part_i;
+    ip.cand_count = h->d_cand;
+    if (h->d_nd_stats) ip.pair_count = h->d_nd_stats + 1;
+    return ip;
+}
+
 // One launch group of a general IVF index: nb <= 32 batches of B queries ([nb][B][dim], back to back), everything on s.
 // Coarse scores per batch are the brute-force general scan's on the centroid table (equal scores: the lower list id,
 // launch_pick_probes); then the plan, the list-major scan and the ranking of the group's partial lists.  An index with a
@@ -1256,30 +1314,7 @@ int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int 
         HIPCHK(vs::launch_pick_probes(h->d_scores, ld, B, h->nlist, nprobe, W.probes + (size_t)b * B * nprobe, s));
     }
     stage_mark(h, 1, s);
-    vs::IvfNdParams ip{};
-    ip.vecs = h->d_vecs;
-    ip.vnorm = h->d_norm;
-    ip.offsets = h->d_offsets;
-    ip.nlist = h->nlist;
-    ip.dim = h->dim;
-    ip.dim_p = h->dim_p;
-    ip.q = q_dev;
-    ip.group_q = nb * B;
-    ip.nprobe = nprobe;
-    ip.k = k;
-    ip.kcap = kcap;
-    ip.probes = W.probes;
-    ip.qrows = W.qrows;
-    ip.qnorm = W.qnorm;
-    ip.list_cnt = W.plan;
-    ip.list_start = W.plan + (size_t)2 * h->nlist;
-    ip.n_items = W.plan + (size_t)3 * h->nlist + 1;
-    ip.slots = W.slots;
-    ip.items = W.items;
-    ip.part_d = W.part_d;
-    ip.part_i = W.part_i;
-    ip.cand_count = h->d_cand;
-    if (h->d_nd_stats) ip.pair_count = h->d_nd_stats + 1;
+    vs::IvfNdParams ip = ivf_nd_params(h, q_dev, nb * B, k, kcap, nprobe);
     vs::IvfNdI8Params bp{};
     const bool two_plans = (bool)h->d_nd_u8;
     if (two_plans) {
@@ -1322,6 +1357,62 @@ int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int 
     m.out_i = out_i;
     m.id_map = h->d_r2o;
     HIPCHK(vs::launch_merge_layout(m, kcap, (int64_t)nprobe * kcap, s));
+    stage_mark(h, 3, s);
+    return VS_OK;
+}
+
+// The same launch group at 17 <= k <= 128: coarse, query rows, plan and scan exactly as above at KCAP 16 on
+// the fp32 rows with every pair (an index with a byte copy plans once: wide k scans the fp32 rows whatever
+// vs_set_precision says); then the bound, the rescan of the saturated pairs into per-query candidate lists, and the ranking.
+// Everything on s, no host synchronisation.
+int ivf_group_nd_wide_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int nprobe, float* out_d, int32_t* out_i, hipStream_t s) {
+    if (k <= 16 || k > vs::kIvfNdWideKMax) {
+        set_error("ivf_group_nd_wide_dev: 17 <= k <= 128");
+        return VS_ERR_INVALID;
+    }
+    int rc = ensure_ivf_nd_wide(h);
+    if (rc) return rc;
+    vs_index::IvfNdWide& X = h->ivfndw;
+    if (nb < 1 || nb * B > vs::kIvfNdGroupQ || nprobe > h->ivfnd.np_max) {
+        set_error("ivf_group_nd_wide_dev: launch group out of range");
+        return VS_ERR_INVALID;
+    }
+    const int64_t ld = (h->nlist + 63) & ~63;
+    stage_mark(h, 0, s);
+    for (int b = 0; b < nb; ++b) {
+        if ((rc = scores_dev(h, h->d_centroids, h->d_cnorm, h->nlist, q_dev + (size_t)b * B * h->dim, B, h->d_scores, ld, s))) return rc;
+        HIPCHK(vs::launch_pick_probes(h->d_scores, ld, B, h->nlist, nprobe, h->ivfnd.probes + (size_t)b * B * nprobe, s));
+    }
+    stage_mark(h, 1, s);
+    vs::IvfNdParams ip = ivf_nd_params(h, q_dev, nb * B, kKcapMax, kKcapMax, nprobe);
+    HIPCHK(vs::launch_ivf_nd_plan(ip, s));
+    stage_mark(h, 2, s);
+    prof_begin(h, 1, s);
+    HIPCHK(vs::launch_ivf_nd_scan(ip, h->num_cus, s));
+    vs::IvfNdWideParams wp{};
+    wp.r = ip;
+    wp.r.k = k;
+    wp.r.list_cnt = X.plan;
+    wp.r.list_start = X.plan + (size_t)2 * h->nlist;
+    wp.r.n_items = X.plan + (size_t)3 * h->nlist + 1;
+    wp.r.slots = X.slots;
+    wp.r.items = X.items;
+    wp.r.cand_count = nullptr;  // (counted once, by the first plan)
+    wp.r.pair_count = nullptr;
+    wp.r.pair_mask = X.mask;
+    wp.tau = X.tau;
+    wp.pair_mask = X.mask;
+    wp.cnt = X.cnt;
+    wp.cand = X.cand;
+    wp.id_map = h->d_r2o;
+    wp.out_d = out_d;
+    wp.out_i = out_i;
+    wp.stats = X.stats;
+    HIPCHK(vs::launch_ivf_nd_wide_bound(wp, s));
+    HIPCHK(vs::launch_ivf_nd_plan_second(wp.r, s));
+    HIPCHK(vs::launch_ivf_nd_wide_scan(wp, h->num_cus, s));
+    prof_end(h, 1, s);
+    HIPCHK(vs::launch_ivf_nd_wide_rank(wp, s));
     stage_mark(h, 3, s);
     return VS_OK;
 }
@@ -1729,15 +1820,15 @@ int ensure_ivf_host(vs_index* h, int k = 0) {
 // kernels fill the device beside the current group's scan and ranking)
 int ivf_multi_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int nprobe, float* out_d, int32_t* out_i, hipStream_t user) {
     int rc = VS_OK;
-    if (k > vs::kIvfWideKMax || (k > 16 && !ivf_wide_ok(h, k))) {
+    if (k > vs::kIvfWideKMax || (k > 16 && !h->general && !ivf_wide_ok(h, k))) {
         set_error(k > vs::kIvfWideKMax ? "k > 128 not supported"
                                        : "k > 16 needs the list-major IVF pipeline (nlist <= 4096, rows resident)");
         return VS_ERR_UNSUPPORTED;
     }
     if (h->general) {  // launch groups of up to 32 batches, all on the caller's stream
         for (int b0 = 0; b0 < nb && !rc; b0 += vs::kIvfWideBatches)
-            rc = ivf_group_nd_dev(h, q_dev + (size_t)b0 * B * h->dim, std::min(vs::kIvfWideBatches, nb - b0), B, k, nprobe,
-                                  out_d + (size_t)b0 * B * k, out_i + (size_t)b0 * B * k, user);
+            rc = (k > 16 ? ivf_group_nd_wide_dev : ivf_group_nd_dev)(h, q_dev + (size_t)b0 * B * h->dim, std::min(vs::kIvfWideBatches, nb - b0), B, k,
+                                                                     nprobe, out_d + (size_t)b0 * B * k, out_i + (size_t)b0 * B * k, user);
         return rc;
     }
     if (!ivf_wide_ok(h, k)) {
@@ -1909,6 +2000,23 @@ int vs_ivf_widek_stats(vs_index* h, int64_t* out, int reset) {
     HIPCHK(hipMemcpy(v, h->widek_stats, sizeof(v), hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; ++i) out[i] = (int64_t)v[i];
     if (reset) HIPCHK(hipMemset(h->widek_stats, 0, sizeof(v)));
+    return VS_OK;
+}
+
+int vs_ivf_nd_widek_stats(vs_index* h, int64_t* out, int reset) {
+    if (!h || h->kind != 1 || !h->general || !out) {
+        set_error("vs_ivf_nd_widek_stats: a general IVF index and an output of three words");
+        return VS_ERR_INVALID;
+    }
+    int rc = set_device(h);
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    unsigned long long v[3] = {0, 0, 0};  // (no wide-k call yet: nothing counted)
+    if (h->ivfndw.ready) {
+        HIPCHK(hipMemcpy(v, h->ivfndw.stats, sizeof(v), hipMemcpyDeviceToHost));
+        if (reset) HIPCHK(hipMemset(h->ivfndw.stats, 0, sizeof(v)));
+    }
+    for (int i = 0; i < 3; ++i) out[i] = (int64_t)v[i];
     return VS_OK;
 }
 
@@ -3010,6 +3118,34 @@ int vs_ivf_search_dev_multi(vs_index* h, const float* queries_dev, int n_batches
     return rc ? rc : order_end(h, user);
 }
 
+int vs_ivf_search_topk_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k, int nprobe, int32_t* ids_dev,
+                                 float* dists_dev, void* stream) {
+    if (h && h->kind == 0) {
+        set_error("vs_ivf_search_topk_dev_multi: not an IVF index");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (!h || !queries_dev || !ids_dev || !dists_dev || n_batches < 1 || B < 1 || B > vs::kMaxBatch || k < 1 || nprobe < 1) {
+        set_error("vs_ivf_search_topk_dev_multi: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    if (k > vs::kIvfNdWideKMax) {
+        set_error("vs_ivf_search_topk_dev_multi: k > 128");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (k <= 16 || !h->general) return vs_ivf_search_dev_multi(h, queries_dev, n_batches, B, k, nprobe, ids_dev, dists_dev, stream);
+    nprobe = std::min(nprobe, h->nlist);
+    if (nprobe > kMaxNprobe) {
+        set_error("nprobe > 256 not supported");
+        return VS_ERR_UNSUPPORTED;
+    }
+    int rc = set_device(h);
+    if (rc) return rc;
+    hipStream_t user = static_cast<hipStream_t>(stream);
+    if ((rc = order_begin(h, user))) return rc;
+    rc = ivf_multi_dev(h, queries_dev, n_batches, B, k, nprobe, dists_dev, ids_dev, user);
+    return rc ? rc : order_end(h, user);
+}
+
 #ifdef VS_STAMPS
 // diagnostic builds only (make EXTRA=-DVS_STAMPS; not part of the ABI): state of the wide IVF pipeline after the last launch group
 __attribute__((visibility("default"))) int vs_debug_ivf_wide_stats(vs_index* h, int64_t* out /*[8]*/) {
@@ -3961,7 +4097,7 @@ int ivf_search_host(vs_index* h, vs_comm* c, const float* queries_host, int64_t 
                 const float* q = S.d_q + o * h->dim;
                 if (c) return vs_ivf_search_dev_sharded(h, c, q, nb, B, k, nprobe, oi + o * k, od + o * k, cs);
                 if (wide) return ivf_group_wide_dev(h, lane, q, nb, B, k, nprobe, od + o * k, oi + o * k, cs);
-                if (h->general) return ivf_group_nd_dev(h, q, nb, B, k, nprobe, od + o * k, oi + o * k, cs);
+                if (h->general) return (k > 16 ? ivf_group_nd_wide_dev : ivf_group_nd_dev)(h, q, nb, B, k, nprobe, od + o * k, oi + o * k, cs);
                 int r3 = VS_OK;
                 for (int b = 0; b < nb && !r3; ++b)
                     r3 = ivf_fallback_batch_dev(h, q + (size_t)b * B * h->dim, B, k, nprobe, od + (o + (size_t)b * B) * k,
@@ -4155,6 +4291,29 @@ int vs_ivf_search(vs_index* h, const float* queries_host, int64_t nq, int k, int
     }
     if (k > vs::kIvfWideKMax) {
         set_error("k > 128 not supported");
+        return VS_ERR_UNSUPPORTED;
+    }
+    return guarded([&] { return ivf_search_host(h, nullptr, queries_host, nq, k, nprobe, ids, dists, total_candidates, timing); });
+}
+
+int vs_ivf_search_topk(vs_index* h, const float* queries_host, int64_t nq, int k, int nprobe, int32_t* ids, float* dists,
+                       int64_t* total_candidates, vs_timing* timing) {
+    if (h && h->kind == 0) {
+        set_error("vs_ivf_search_topk: not an IVF index");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (!h || !queries_host || !ids || !dists || nq < 0 || k < 1 || nprobe < 1) {
+        set_error("vs_ivf_search_topk: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    if (k > vs::kIvfNdWideKMax) {
+        set_error("vs_ivf_search_topk: k > 128");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (k <= 16 || !h->general) return vs_ivf_search(h, queries_host, nq, k, nprobe, ids, dists, total_candidates, timing);
+    nprobe = std::min(nprobe, h->nlist);
+    if (nprobe > kMaxNprobe) {
+        set_error("nprobe > 256 not supported");
         return VS_ERR_UNSUPPORTED;
     }
     return guarded([&] { return ivf_search_host(h, nullptr, queries_host, nq, k, nprobe, ids, dists, total_candidates, timing); });

@@ -67,13 +67,14 @@ __global__ __launch_bounds__(256) void ivf_nd_prep(const IvfNdParams p) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < 2 * p.nlist; i += gridDim.x * 256) p.list_cnt[i] = 0;
 }
 
-// the list a pair probes, or -1 when it yields no slot in this plan (no probe, a list without rows, or a query routed to
-// the group's other plan); rows = the probed list's length either way
+// the list a pair probes, or -1 when it yields no slot in this plan (no probe, a list without rows, a query routed to
+// the group's other plan, or a pair the rescan's mask leaves out); rows = the probed list's length either way
 __device__ __forceinline__ int ivf_nd_pair_list(const IvfNdParams& p, int pair, int& rows) {
     const int c = p.probes[pair];
     rows = (c >= 0 && c < p.nlist) ? p.offsets[c + 1] - p.offsets[c] : 0;
     if (rows <= 0) return -1;
     if (p.route && p.route[pair / p.nprobe] != p.route_want) return -1;
+    if (p.pair_mask && !p.pair_mask[pair]) return -1;
     return c;
 }
 
@@ -279,7 +280,7 @@ hipError_t launch_ivf_nd_plan(const IvfNdParams& p, hipStream_t s) {
 }
 
 hipError_t launch_ivf_nd_plan_second(const IvfNdParams& p, hipStream_t s) {
-    if (p.group_q < 1 || p.group_q > kIvfNdGroupQ || p.nprobe < 1 || p.nprobe > kIvfMaxProbe || p.nlist < 1 || !p.route)
+    if (p.group_q < 1 || p.group_q > kIvfNdGroupQ || p.nprobe < 1 || p.nprobe > kIvfMaxProbe || p.nlist < 1 || (!p.route && !p.pair_mask))
         return hipErrorInvalidValue;
     const int pairs = p.group_q * p.nprobe;
     hipLaunchKernelGGL(ivf_nd_count, dim3((pairs + 255) / 256), dim3(256), 0, s, p, 0);

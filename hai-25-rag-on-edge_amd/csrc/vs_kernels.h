@@ -535,11 +535,14 @@ struct IvfNdParams {
     const int32_t* route;     // [group_q]
     int route_want;
     unsigned long long* pair_count;  // += pairs that got a slot in this plan (null: not counted)
+    // the rescan plan of the wide-k pipeline (vs_ivf_nd_wide.hip): a pair gets a slot only when pair_mask[pair] != 0.
+    // Null: every pair, as everywhere else.
+    const int32_t* pair_mask; // [group_q * nprobe]
 };
 hipError_t launch_ivf_nd_plan(const IvfNdParams& p, hipStream_t s);
-// a group's second plan: the pair counts, prefix and fill of launch_ivf_nd_plan on p's own plan tables -- no query
-// preparation, no preset of the partial lists, no candidate count (the first plan's launches did those), and p's
-// list_cnt cleared by the caller's earlier launch (launch_ivf_nd_i8_prep)
+// a group's second plan (p.route or p.pair_mask set): the pair counts, prefix and fill of launch_ivf_nd_plan on p's own
+// plan tables -- no query preparation, no preset of the partial lists, no candidate count (the first plan's launches did
+// those), and p's list_cnt cleared by the caller's earlier launch (launch_ivf_nd_i8_prep, launch_ivf_nd_wide_bound)
 hipError_t launch_ivf_nd_plan_second(const IvfNdParams& p, hipStream_t s);
 hipError_t launch_ivf_nd_scan(const IvfNdParams& p, int grid, hipStream_t s);
 
@@ -564,5 +567,39 @@ struct IvfNdI8Params {
 };
 hipError_t launch_ivf_nd_i8_prep(const IvfNdI8Params& p, hipStream_t s);
 hipError_t launch_ivf_nd_i8_scan(const IvfNdI8Params& p, int grid, hipStream_t s);
+
+// ---- wide k (17 <= k <= kIvfNdWideKMax) on a general IVF index (vs_ivf_nd_wide.hip).  The group's first
+// plan and scan run as above at kcap 16 on the fp32 rows with every pair; part[(query * nprobe + rank) * 16] then holds
+// each probed list's 16 best by (distance, row).
+//   launch_ivf_nd_wide_bound : tau[query] = the k-th smallest finite distance among the query's partial lists (+inf when
+//       there are fewer than k).  A pair whose 16th entry is finite and <= tau is saturated: its list may hold more rows
+//       at or under tau, pair_mask = 1.  Every other pair has all its rows at or under tau in its partial list already;
+//       those entries go to the query's candidate list as keys (tw_key of vs_wide_select.h) and pair_mask = 0.  Also
+//       clears r.list_cnt, the rescan plan's counters.
+//   launch_ivf_nd_plan_second(r) with r.pair_mask : the rescan plan, over the saturated pairs only.
+//   launch_ivf_nd_wide_scan  : ivf_scan_nd_kernel's item loop and accumulation chain on the rescan plan; no lane lists,
+//       no merge: every real row of a real slot with d <= tau[query] and d < +inf is appended to the query's list (no
+//       slack: the same chain computed tau).  Entries past kIvfNdWideCand are dropped, cnt keeps counting.
+//   launch_ivf_nd_wide_rank  : per query, the k smallest keys of its list, ids through id_map; a query whose list
+//       overflowed is ranked over every row of its probed lists instead, each distance recomputed by one thread in the
+//       MFMA's order (segments of 16 floats ascending, i = 0..3, g = 0..3, element 16 c + 4 g + i, one fma each: bit-
+//       identical).  Leaves cnt[query] = 0 and adds to stats: candidates ranked from lists, the most of one query (max),
+//       queries ranked by the fallback.
+constexpr int kIvfNdWideKMax = 128;
+constexpr int kIvfNdWideCand = 8192;   // keys per query
+struct IvfNdWideParams {
+    IvfNdParams r;            // the rescan plan: the first plan's fields with tables of its own and pair_mask set
+    float* tau;               // [kIvfNdGroupQ]
+    int32_t* pair_mask;       // [group_q * nprobe] (= r.pair_mask)
+    int32_t* cnt;             // [kIvfNdGroupQ] (zero between groups)
+    unsigned long long* cand; // [kIvfNdGroupQ][kIvfNdWideCand]
+    const int32_t* id_map;    // reorder_to_original
+    float* out_d;             // [group_q][k]
+    int32_t* out_i;
+    unsigned long long* stats;  // [3]
+};
+hipError_t launch_ivf_nd_wide_bound(const IvfNdWideParams& p, hipStream_t s);
+hipError_t launch_ivf_nd_wide_scan(const IvfNdWideParams& p, int grid, hipStream_t s);
+hipError_t launch_ivf_nd_wide_rank(const IvfNdWideParams& p, hipStream_t s);
 
 }  // namespace vs

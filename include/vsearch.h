@@ -312,6 +312,7 @@ VS_API int vs_ivf_load(const char* index_dir, int device, int rank, int world, v
  *     fp32 rows), vs_ivf_set_metric(VS_METRIC_L2);
  *   VS_ERR_UNSUPPORTED, with the dimension in the message: 17 <= k <= 128, vs_set_precision 2,
  *     vs_ivf_set_metric(VS_METRIC_IP), vs_ivf_widek_stats, every sharded and virtual-shard call.
+ *   17 <= k <= 128 comes through vs_ivf_search_topk / vs_ivf_search_topk_dev_multi below.
  * vs_ivf_build and vs_ivf_build_index stay 128-d only; vs_ivf_build_nd and vs_ivf_build_index_nd
  * build at every dimension this creator takes.  A general IVF index that also keeps its rows as
  * bytes and scans them with int8 MFMA comes from vs_ivf_create_nd_u8 below, not from this creator. */
@@ -468,6 +469,25 @@ VS_API int vs_ivf_search_dev(vs_index* h, const float* queries_dev, int B, int k
 VS_API int vs_ivf_search_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k, int nprobe,
                                    int32_t* ids_dev, float* dists_dev, void* stream);
 
+/* IVF search for 1 <= k <= 128 on EVERY IVF index.  Signatures, output layouts ([nq][k], [n_batches][B][k]),
+ * *total_candidates and the timing fields are those of vs_ivf_search / vs_ivf_search_dev_multi; slots past the
+ * candidates of the probed lists are (-1, +inf).  k < 1 -> VS_ERR_INVALID, k > 128 -> VS_ERR_UNSUPPORTED, a brute-force
+ * index -> VS_ERR_UNSUPPORTED.
+ *   k <= 16 on any IVF index, and every k on the specialised 128-d index: the call IS vs_ivf_search /
+ *     vs_ivf_search_dev_multi (same launches, same results, same refusals).
+ *   17 <= k <= 128 on a general IVF index (dim != 128; vs_ivf_create, vs_ivf_load, vs_ivf_build_index_nd,
+ *     vs_ivf_create_nd_u8): the wide-k pipeline of DESIGN.md 4.6c, in launch groups of up to 32 batches on the caller's
+ *     stream, without a host synchronisation.  The result is the k best rows of the probed lists by (distance, position
+ *     in vectors_reordered), ids through reorder_to_original; every distance is bit-identical to what vs_bf_create_nd's
+ *     fp32 index returns for that row and query.  Wide k scans the fp32 rows whatever vs_set_precision says, also on a
+ *     vs_ivf_create_nd_u8 index (as vs_bf_search_topk does for brute force): on data that qualifies for the byte rows
+ *     the distances are the same numbers, so the result does not depend on it.  The first such call allocates about
+ *     66 MB of device scratch. */
+VS_API int vs_ivf_search_topk(vs_index* h, const float* queries_host, int64_t nq, int k, int nprobe,
+                              int32_t* ids, float* dists, int64_t* total_candidates, vs_timing* timing);
+VS_API int vs_ivf_search_topk_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k, int nprobe,
+                                        int32_t* ids_dev, float* dists_dev, void* stream);
+
 /* ---------------------------------------------------------------- multi-GPU */
 /* Which rank owns which inverted list in a cluster-sharded index (host only, no GPU needed):
  * lists sorted by length, longest first, dealt round-robin -> owner_out[nlist] in [0, world).
@@ -566,6 +586,11 @@ VS_API int vs_ivf_widek_stats(vs_index* h, int64_t* out /* [4] */, int reset);
  * the byte plan since the last reset, out[1] = the same for the fp32 plan (pairs that probe an empty list get neither).
  * Always counted.  Synchronises the device; reset != 0 clears the counters.  VS_ERR_INVALID on any other kind of index. */
 VS_API int vs_ivf_nd_u8_stats(vs_index* h, int64_t* out /* [2] */, int reset);
+/* The wide-k calls (17 <= k <= 128) on a general IVF index since the last reset: out[0] = candidates ranked from
+ * candidate lists, out[1] = the most candidates of one query, out[2] = queries ranked by the exact fallback (more than
+ * 8192 candidates: every row of their probed lists scored again).  Always counted; zeros before the first wide-k call.
+ * Synchronises the device; reset != 0 clears the counters.  VS_ERR_INVALID on any other kind of index. */
+VS_API int vs_ivf_nd_widek_stats(vs_index* h, int64_t* out /* [3] */, int reset);
 /* per-launch durations (ms) of the same window, oldest first; *launches = how many there were (may exceed cap).
  * One brute-force launch serves up to 32 batches: the CLIs turn these into the per-batch statistics of
  * main.cpp:262-330 (avg / stddev / min / max / P50 / P95 / P99 "graph execute time"). */

@@ -208,7 +208,8 @@ public:
     // backendPath is kept for signature compatibility (the reference passes libQnnHtp.so); the
     // backend here is always the HIP library this header links against.
     // The directory states the dimension (1 <= dim <= 2048, getDim()): 128-d indexes take the specialised pipeline,
-    // any other a general IVF index (fp32 rows, squared L2, k <= 16, one GPU; vsearch.h at vs_ivf_create).
+    // any other a general IVF index (fp32 rows, squared L2, one GPU; k <= 16 through searchBatch, k <= 128 through
+    // searchBatchTopk; vsearch.h at vs_ivf_create).
     explicit IVFIndex(const std::string& indexDir, const std::string& backendPath = "libvsearch_hip.so",
                       int device = 0, int rank = 0, int world = 1) {
         (void)backendPath;
@@ -242,11 +243,26 @@ public:
     size_t searchBatch(const std::vector<float>& queries, int batchSize, int k, int nprobe,
                        std::vector<std::vector<int>>& allIndices, std::vector<std::vector<float>>& allScores,
                        SearchTiming& timing) {
+        return searchBatchWith(vs_ivf_search, queries, batchSize, k, nprobe, allIndices, allScores, timing);
+    }
+    // the same for 1 <= k <= 128 at every dimension (vs_ivf_search_topk): k <= 16, and every k on a 128-d index, is
+    // searchBatch itself; 17 <= k <= 128 on a general index takes the wide-k pipeline
+    size_t searchBatchTopk(const std::vector<float>& queries, int batchSize, int k, int nprobe,
+                           std::vector<std::vector<int>>& allIndices, std::vector<std::vector<float>>& allScores,
+                           SearchTiming& timing) {
+        return searchBatchWith(vs_ivf_search_topk, queries, batchSize, k, nprobe, allIndices, allScores, timing);
+    }
+
+  private:
+    using HostSearch = int (*)(vs_index*, const float*, int64_t, int, int, int32_t*, float*, int64_t*, vs_timing*);
+    size_t searchBatchWith(HostSearch call, const std::vector<float>& queries, int batchSize, int k, int nprobe,
+                           std::vector<std::vector<int>>& allIndices, std::vector<std::vector<float>>& allScores,
+                           SearchTiming& timing) {
         std::vector<int32_t> ids((size_t)batchSize * k);
         std::vector<float> dists((size_t)batchSize * k);
         int64_t total = 0;
         vs_timing tm{};
-        check(vs_ivf_search(h_, queries.data(), batchSize, k, nprobe, ids.data(), dists.data(), &total, &tm));
+        check(call(h_, queries.data(), batchSize, k, nprobe, ids.data(), dists.data(), &total, &tm));
         allIndices.assign((size_t)batchSize, {});
         allScores.assign((size_t)batchSize, {});
         for (int b = 0; b < batchSize; ++b)
@@ -262,6 +278,7 @@ public:
         return (size_t)total;
     }
 
+  public:
     // collective over `comm`: this index holds rank's lists (constructed with the same rank / world); returns the rows
     // scanned by THIS rank
     size_t searchBatchSharded(vs_comm* comm, const std::vector<float>& queries, int batchSize, int k, int nprobe,

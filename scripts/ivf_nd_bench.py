@@ -1,7 +1,7 @@
 """List-major IVF at a general dimension against exact brute force on the same rows: device time per 1024 queries.
 
     python scripts/ivf_nd_bench.py [--dims 96,384,768] [--rows 1000000] [--nlist 1024] [--nprobe 8,32] [--groups 4] [--reps 5]
-                                   [--build ITERS] [--u8]
+                                   [--build ITERS] [--u8] [--widek K]
 
 Data: synth_sift rows (integer valued) at every dimension, nlist sampled rows as centroids, every row assigned to its
 nearest centroid through the library's own brute force (a timing index, not a trained one).  Queries: `groups` groups of
@@ -24,6 +24,13 @@ byte index (IVFIndex.from_u8: vs_ivf_create_nd_u8, paths ivf_u8_nprobeP), the vs
 end-to-end windows it times the list-scan launches alone (vs_prof_read(.., 1): the fp32 scan on one index, the fp32 scan
 on an empty plan plus the byte scan on the other), again alternated, and prints the byte index's pair counts
 (vs_ivf_nd_u8_stats: pairs planned on bytes, pairs planned on fp32).
+
+--widek K (17 <= K <= 128) times the wide-k call of the general index (IVFIndex.search_topk_dev_multi at k = K, paths
+ivf_kK_nprobeP) against two references alternated in the same process: the same index at k = 10 (ivf_k10_nprobeP) and exact
+wide-k brute force on the same rows (bf_kK: BruteForceIndex.search_topk_dev_multi at k = K).  It also prints recall@K
+against that exact result, the three counters of vs_ivf_nd_widek_stats for one pass over the queries, and the share of
+(query, probe) pairs the rescan takes -- recomputed on the host in float64 for the first 64 queries (a pair is rescanned
+when the 16th best distance of its list is at or under the K-th smallest of the query's per-list top-16s).
 """
 import argparse
 import json
@@ -57,6 +64,9 @@ def one(a, dim):
     else:
         assign, cents = sampled_rows(a, pkg, base, dev, st)
     vr, off, r2o = pkg.ivf_layout_from_assignment(base, assign, a.nlist)
+    if a.widek:
+        search_widek(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st)
+        return
     search(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st, assign_pass_ms)
 
 
@@ -235,6 +245,108 @@ def search(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st, assign_pass_ms):
                                   "pairs_on_bytes": on_bytes, "pairs_on_fp32": on_fp32}), flush=True)
 
 
+def rescan_share(vr, off, cents, q, k, nprobe):
+    """share of the (query, probe) pairs with rows that the wide-k rescan takes, recomputed in float64"""
+    c64 = cents.astype(np.float64)
+    cn = (c64 * c64).sum(1)
+    taken = pairs = 0
+    for x in q.astype(np.float64):
+        probes = np.argsort(cn - 2 * c64 @ x, kind="stable")[:nprobe]
+        tops = []
+        for c in probes:
+            rows = vr[off[c]:off[c + 1]].astype(np.float64)
+            if len(rows):
+                tops.append(np.sort(((rows - x) ** 2).sum(1))[:16])
+        if not tops:
+            continue
+        every = np.sort(np.concatenate(tops))
+        tau = every[k - 1] if len(every) >= k else np.inf
+        pairs += len(tops)
+        taken += sum(1 for t in tops if len(t) == 16 and t[15] <= tau)
+    return taken / max(pairs, 1)
+
+
+def search_widek(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st):
+    import torch
+    KW = a.widek
+    sizes = np.diff(off)
+    print(json.dumps({"what": "index", "dim": dim, "rows": a.rows, "nlist": a.nlist, "list_min": int(sizes.min()),
+                      "list_mean": float(sizes.mean()), "list_max": int(sizes.max())}), flush=True)
+    qd = torch.from_numpy(q).to(dev)
+    nq, nbg = a.groups * GROUP_Q, GROUP_Q // B
+    nprobes = [int(x) for x in a.nprobe.split(",")]
+    share = {p: rescan_share(vr, off, cents, q[:64], KW, p) for p in nprobes}
+    with pkg.BruteForceIndex(base) as bf, pkg.IVFIndex(vectors_reordered=vr, centroids=cents, cluster_offsets=off,
+                                                      reorder_to_original=r2o) as ivf:
+        bf.set_precision(1)
+        bi = torch.empty((nq, KW + 1), dtype=torch.int32, device=dev)
+        bd = torch.empty((nq, KW + 1), dtype=torch.float32, device=dev)
+        bfl = torch.empty((nq,), dtype=torch.int32, device=dev)
+        wi = torch.empty((nq, KW), dtype=torch.int32, device=dev)
+        wd = torch.empty((nq, KW), dtype=torch.float32, device=dev)
+        ii = torch.empty((nq, K), dtype=torch.int32, device=dev)
+        idd = torch.empty((nq, K), dtype=torch.float32, device=dev)
+
+        def run_bf():
+            for g in range(a.groups):
+                o = g * GROUP_Q
+                bf.search_topk_dev_multi(qd[o].data_ptr(), nbg, B, KW, bi[o].data_ptr(), bd[o].data_ptr(), bfl[o].data_ptr(), st)
+
+        def run_k10(nprobe):
+            for g in range(a.groups):
+                o = g * GROUP_Q
+                ivf.search_dev_multi(qd[o].data_ptr(), nbg, B, K, nprobe, ii[o].data_ptr(), idd[o].data_ptr(), st)
+
+        def run_wide(nprobe):
+            for g in range(a.groups):
+                o = g * GROUP_Q
+                ivf.search_topk_dev_multi(qd[o].data_ptr(), nbg, B, KW, nprobe, wi[o].data_ptr(), wd[o].data_ptr(), st)
+
+        def timed(f, *args):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f(*args)
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) * 1e3 / a.groups  # us per 1024 queries
+
+        paths = [(f"bf_k{KW}", run_bf, ())]
+        for p in nprobes:
+            paths += [(f"ivf_k{K}_nprobe{p}", run_k10, (p,)), (f"ivf_k{KW}_nprobe{p}", run_wide, (p,))]
+        recall, stats = {}, {}
+        for name, f, args in paths:  # warm-up of every path; recall and counters of the wide ones
+            f(*args)
+            torch.cuda.synchronize()
+            if f is run_wide:
+                ivf.nd_widek_stats(reset=True)
+            f(*args)
+            torch.cuda.synchronize()
+            if f is run_bf:
+                exact = bi[:, :KW].cpu().numpy()
+            elif f is run_wide:
+                stats[name] = ivf.nd_widek_stats(reset=True)
+                got = wi.cpu().numpy()
+                recall[name] = float(np.mean([len(set(got[i]) & set(exact[i])) / KW for i in range(nq)]))
+        us = {name: [] for name, _, _ in paths}
+        for _ in range(a.reps):
+            for name, f, args in paths:
+                us[name].append(timed(f, *args))
+        med = {n: sorted(v)[len(v) // 2] for n, v in us.items()}
+        for name, f, args in paths:
+            rec = {"what": "us_per_1024_queries", "path": name, "dim": dim, "rows": a.rows, "nlist": a.nlist,
+                   "k": K if f is run_k10 else KW, "us": [round(u, 1) for u in us[name]], "median_us": round(med[name], 1)}
+            if f is run_wide:
+                p = args[0]
+                rec[f"recall_at_{KW}"] = round(recall[name], 4)
+                rec["ratio_to_k10"] = round(med[name] / med[f"ivf_k{K}_nprobe{p}"], 2)
+                rec["speedup_vs_bf_wide"] = round(med[f"bf_k{KW}"] / med[name], 2)
+                rec["widek_stats"] = list(stats[name])
+                rec["candidates_per_query"] = round(stats[name][0] / max(nq - stats[name][2], 1), 1)
+                rec["rescan_share_first_64_queries"] = round(share[p], 4)
+                rec["rescan_share_expected"] = round(KW / (16.0 * p), 4)
+            print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dims", default="96,384,768")
@@ -245,13 +357,14 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--build", type=int, default=0, metavar="ITERS", help="train the index with the library's builder")
     ap.add_argument("--u8", action="store_true", help="rows as uint8: the byte index beside the vs_ivf_create index and brute force")
+    ap.add_argument("--widek", type=int, default=0, metavar="K", help="time the wide-k call (17 <= K <= 128) against k = 10 and exact wide-k brute force")
     ap.add_argument("--one", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.one:
         one(a, a.one)
         return
     cmd = [sys.executable, os.path.abspath(__file__), "--rows", str(a.rows), "--nlist", str(a.nlist), "--nprobe", a.nprobe,
-           "--groups", str(a.groups), "--reps", str(a.reps), "--build", str(a.build)] + (["--u8"] if a.u8 else [])
+           "--groups", str(a.groups), "--reps", str(a.reps), "--build", str(a.build)] + (["--u8"] if a.u8 else []) + ["--widek", str(a.widek)]
     for dim in [int(x) for x in a.dims.split(",")]:
         r = subprocess.run(cmd + ["--one", str(dim)], timeout=900)
         if r.returncode != 0:  # a failed or faulted step ends the run: nothing more is started on the GPU
