@@ -3690,7 +3690,9 @@ int sh_reserve(vs_index* o, int G, size_t lists_words, int64_t L0p, int64_t ldm,
 // arrive -- and that maximum never rises.  So: the first L0 rows of shard 0 are taken densely (their distance rows), the
 // k-th smallest of them bounds the buffer maximum for every later row of every shard, each shard emits its rows under that
 // bound in ONE filtered pass (about N * k / L0 of them), and the host replays "dense rows, then the shards' candidates in row
-// order".  Exact whenever the distances are (integer-valued SIFT: always).
+// order".  Exact whenever the distances are: the replay compares the scan kernels' own fp32 numbers, whatever their sign, so
+// it is as exact on real-valued rows as on integer-valued SIFT.  Both are tested: integer ties throughout the suite,
+// bit-equal noise distances (negative ones and +0 included) of duplicate real-valued rows by tests/test_gpu_cancel.py.
 int resolve_ties_shards(const Shards& S, const std::vector<int32_t>& meta /*[G][2] rows, id_offset*/, const float* queries_host,
                         const std::vector<int64_t>& flagged, int k, int32_t* ids, float* dists) {
     vs_index* o = S.owner();

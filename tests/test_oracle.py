@@ -275,3 +275,71 @@ def test_ivf_oracle_orders_agree_on_integer_centroids_and_name_the_scan_order():
     assert got[4].shape == (20, 4) and (np.diff(got[4], axis=1) >= 0).all()
     ex = oracle.exact_int_dists(q, cents).astype(np.float32)
     assert np.array_equal(np.take_along_axis(ex, got[3].astype(np.int64), 1), got[4])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# tests/cancel_data.py: self-queries on real-valued rows.  Asserted on the reference alone, for every data set that
+# test_gpu_cancel.py searches, that the expected results hold what that data is for.  These are conditions on the data,
+# not measurements of the product: a seed that misses one is replaced (cancel_data.SEED), no count is lowered.
+# ---------------------------------------------------------------------------------------------------------------------
+import cancel_data  # noqa: E402
+
+
+@pytest.mark.parametrize("n,nq,dim,offset", cancel_data.BF_SETS)
+def test_cancel_data_produces_negative_zero_and_tied_distances(n, nq, dim, offset):
+    base, q, src = cancel_data.case(n, nq, dim, offset)
+    m, mid = cancel_data.layout(n)
+    assert np.array_equal(q, base[src]) and np.array_equal(base[n - m:], base[:m]) and np.array_equal(base[mid:mid + 50], base[:50])
+    assert mid % 64 != 0 and (n - m) % 64 != 0  # a copy never sits at its original's place inside a 64-row block
+    bounds = [n // 3 // 16 * 16, 2 * n // 3 // 16 * 16]           # three contiguous shards: copies on both sides of each border
+    assert m < bounds[0] < mid and mid + 50 < bounds[1] < n - m
+    ids, d = cancel_data.sorted_scores(q[:64], base, 17)
+    # the self-query, its copies and the two planted neighbours are each query's five best and the rest is far away
+    i = np.arange(len(ids))
+    want = [{int(s), int(n - m + s), int(m + 3 * j + 1), int(n - m - 2 - 5 * j)} | ({int(mid + s)} if s < 50 else set()) for j, s in zip(i, src[:64])]
+    assert all(set(ids[j, :len(want[j])].tolist()) == want[j] for j in i)
+    assert (d[i, [len(w) for w in want]] > 1).all() and (d[i, [len(w) - 1 for w in want]] < 1e-4 * dim * (1 + offset) ** 2).all()
+    neg, zero, tie, _ = cancel_data.require(d, 5, f"n {n} dim {dim} offset {offset}", negative=8, zero=4, tie=32)
+    assert max(cancel_data.counts(d, k)[3] for k in (1, 5, 15)) >= 1  # some tested k has a negative k-th best: a bound below 0
+
+
+@pytest.mark.parametrize("n,nq,dim,offset,nlist", cancel_data.IVF_SETS)
+def test_cancel_ivf_layout_produces_negative_and_zero_coarse_scores(n, nq, dim, offset, nlist):
+    vr, off, r2o, cents, q = cancel_data.ivf_case(n, nq, dim, offset, nlist)
+    base = cancel_data.case(n, nq, dim, offset)[0]
+    assert np.array_equal(vr, base[r2o]) and off[0] == 0 and off[-1] == n and len(np.unique(cents, axis=0)) == nlist
+    assert len(q) == nq + nlist // 2 and np.array_equal(q[nq:], cents[::2])
+    lists = np.repeat(np.arange(nlist), np.diff(off))
+    assert (np.diff(lists) >= 0).all() and all((np.diff(r2o[off[c]:off[c + 1]]) > 0).all() for c in range(nlist))  # stable
+    score = oracle.l2_matrix(cents, base, "chain")
+    assert np.array_equal(lists, score.argmin(0)[r2o])
+    q = q[:256]
+    wide = nlist <= 64
+    cases = {64: ((1, 1), (10, 8), (16, 8), (2, 1), (3, 8), (17, 8), (100, 8)), 24: ((1, 1), (10, 4), (16, 8), (40, 8), (128, 24)),
+             5000: ((1, 24), (5, 24))}[nlist]
+    neg_kth = 0
+    for k, nprobe in cases:
+        scan = "fold8" if nlist > 4096 else None
+        _, od, _, _, coarse = oracle.ivf_search(vr, off, r2o, cents, q, k + 1, nprobe, dot_order="chain", scan_order=scan, return_coarse=True)
+        c = cancel_data.require(od[:64], k, f"ivf n {n} dim {dim} offset {offset} nlist {nlist} k {k} nprobe {nprobe}",
+                                negative=8, zero=4, tie=32 if (k > 1 or not wide) and nprobe > 1 else 1)
+        neg_kth += c[3]
+        assert int((coarse < 0).sum()) >= 4 and int(((coarse == 0) & ~np.signbit(coarse)).sum()) >= 4, (k, nprobe)
+    assert neg_kth >= 1
+
+
+def test_results_writer_on_cancelled_distances(pkg, tmp_path):
+    """a tiny negative, +0, a denormal and (-1, +inf) padding: the default form is "%g"'s, the fixed four-decimal form
+    prints the tiny negative as -0.0000, as std::fixed does in the reference's writer"""
+    d = np.array([[-7.6293945e-06, 0.0, 2.0 ** -140, np.inf], [0.0, 0.0, 0.00015, np.inf]], dtype=np.float32)
+    ids = np.array([[3, 19999, 7, -1], [0, 1, 2, -1]], dtype=np.int32)
+    assert d[0, 0] < 0 and 0 < d[0, 2] < np.finfo(np.float32).tiny
+    p, po = str(tmp_path / "p.txt"), str(tmp_path / "o.txt")
+    pkg.write_results(p, ids, d)
+    oracle.write_results(po, ids, d)
+    assert open(p).read() == open(po).read() == "Query 0: (3, -7.62939e-06) (19999, 0) (7, 7.17465e-43)\nQuery 1: (0, 0) (1, 0) (2, 0.00015)\n"
+    pkg.write_results(p, ids, d, style=1)
+    assert open(p).read() == "Query 0: (3, -0.0000) (19999, 0.0000) (7, 0.0000)\nQuery 1: (0, 0.0000) (1, 0.0000) (2, 0.0002)\n"
+    assert open(p).read().split()[3] == "%.4f)" % d[0, 0]
+    pkg.write_results(p, ids, d)  # the fixed form of one call does not leak into the next
+    assert open(p).read() == open(po).read()
