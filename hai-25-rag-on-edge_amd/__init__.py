@@ -192,6 +192,9 @@ def lib():
         "vs_index_nlist": (i32, [vp]),
         "vs_f32_filter_bound": (C.c_float, [C.c_double] * 6),
         "vs_bf_filter_image_read": (i32, [vp, i64, i64, vp]),
+        "vs_f32_filter_cnorm": (C.c_float, [C.c_double]),
+        "vs_f32_filter_th2": (C.c_float, [C.c_float] * 3),
+        "vs_bf_filter_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_destroy": (None, [vp]),
     }
     for name, (res, args) in sig.items():
@@ -399,6 +402,13 @@ class BruteForceIndex(_Index):
         out = np.empty((n, 128), dtype=np.uint16)
         _check(lib().vs_bf_filter_image_read(self._h, row0, n, _p(out)))
         return out
+
+    def filter_stats(self, reset: bool = False):
+        """(prefilter launches, launches that overflowed into the fallback scan, candidates written by the sweeps,
+        candidates that survived the exact recheck) since the last reset (vs_bf_filter_stats)."""
+        out = (C.c_int64 * 4)()
+        _check(lib().vs_bf_filter_stats(self._h, out, 1 if reset else 0))
+        return tuple(int(x) for x in out)
 
     def search(self, queries, k: int, timing: Timing | None = None):
         q = _f32c(queries).reshape(-1, self.d)

@@ -113,7 +113,12 @@ struct vs_index {
     // scaled (otherwise the index keeps scan_f32s_kernel), and the rows once more as bf16 in A-fragment order, which is
     // what that kernel sweeps (launch_row_filter_image; present exactly when filter_ok: +256 bytes per row)
     vs::FilterStats fstats{};
+    float filter_cnorm = 0.f;  // vs::filter_cnorm of the largest stored norm: the L2 test's shard constant (vs::filter_th2)
     bool filter_ok = false;
+    // vs_bf_filter_stats: [1] launches that overflowed, [2] candidates of the sweeps, [3] survivors of the recheck (device
+    // counters, allocated with the image), and the prefilter launches made (counted where they are enqueued)
+    vs::DevBuf<unsigned long long> filter_stats;
+    int64_t filter_launches = 0;
     vs::DevBuf<uint16_t> d_img;  // [n_rows + 64][128], spare rows zero
     // int8 data path: only when every base value is an integer in [0, 255]
     vs::DevBuf<int8_t> d_vecs_u8;   // [n_rows][128] bytes (x - 128)
@@ -460,8 +465,8 @@ int upload_vectors(vs_index* h, const float* host, int64_t rows) {
         HIPCHK(vs::launch_row_sqnorm(h->d_vecs, rows, vs::kDim, h->d_norm, nullptr));
         if (h->kind == 0) {  // brute force: the bf16 prefilter's shard constants and row image, in one pass
             vs::DevBuf<unsigned long long> st;
-            if ((rc = st.alloc(4))) return rc;
-            HIPCHK(hipMemset(st, 0, 4 * sizeof(unsigned long long)));
+            if ((rc = st.alloc(5))) return rc;
+            HIPCHK(hipMemset(st, 0, 5 * sizeof(unsigned long long)));
             // the image is an accelerator, not a requirement: without the memory for it the index keeps scan_f32s_kernel
             // (and only a shard that the seeded streaming launches take can use it: bf_launch's tiles_total test)
             const bool want_img = f32_filter_enabled() && (rows + vs::kTileRows - 1) / vs::kTileRows >= 2 * vs::kSeedWaves;
@@ -471,15 +476,24 @@ int upload_vectors(vs_index* h, const float* host, int64_t rows) {
                 vs::set_error("");
             }
             if (have_img) HIPCHK(hipMemset(h->d_img + (size_t)rows * vs::kDim, 0, (size_t)vs::kScanPadRows * vs::kDim * sizeof(uint16_t)));
-            HIPCHK(vs::launch_row_filter_image(h->d_vecs, rows, st, have_img ? h->d_img.get() : nullptr, nullptr));
-            unsigned long long v[4];
+            HIPCHK(vs::launch_row_filter_image(h->d_vecs, h->d_norm, rows, st, have_img ? h->d_img.get() : nullptr, nullptr));
+            unsigned long long v[5];
             HIPCHK(hipMemcpy(v, st, sizeof(v), hipMemcpyDeviceToHost));
             double m[3];
             for (int i = 0; i < 3; ++i) memcpy(&m[i], &v[i], sizeof(double));
             h->fstats.bmax = sqrt(m[0]);
             h->fstats.emax = sqrt(m[1]);
             h->fstats.bpmax = sqrt(m[2]);
-            h->filter_ok = have_img && v[3] == 0 && std::isfinite(m[0]) && std::isfinite(m[2]);
+            double bnmax;
+            memcpy(&bnmax, &v[4], sizeof(double));
+            h->filter_cnorm = vs::filter_cnorm(bnmax);
+            h->filter_ok = have_img && v[3] == 0 && std::isfinite(m[0]) && std::isfinite(m[2]) && std::isfinite(h->filter_cnorm);
+            if (h->filter_ok && h->filter_stats.alloc(4) != VS_OK) {  // (as the image: an accelerator, not a requirement)
+                (void)hipGetLastError();
+                vs::set_error("");
+                h->filter_ok = false;
+            }
+            if (h->filter_ok) HIPCHK(hipMemset(h->filter_stats, 0, 4 * sizeof(unsigned long long)));
             if (!h->filter_ok) h->d_img.reset();  // (the copy above has waited for the kernel)
         }
         HIPCHK(hipDeviceSynchronize());
@@ -904,6 +918,12 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
                 sp.qbf = L.qbf;
                 sp.qbound = L.qbound;
                 sp.img = h->d_img;
+#ifdef VS_STAMPS
+                sp.dbg = g_dbg ? g_dbg + 12288 * 16 : nullptr;  // (rows of its own: the kernels around it stamp rows [0, 256))
+#endif
+                sp.cnorm = h->filter_cnorm;
+                sp.sink.stats = h->filter_stats;
+                ++h->filter_launches;
             }
             HIPCHK(vs::launch_scan_f32_stream(sp, sgrid, s));
             prof_end(h, 0, s);
@@ -1957,6 +1977,25 @@ int vs_bf_filter_image_read(const vs_index* h, int64_t row0, int64_t n, uint16_t
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(dst, h->d_img + (size_t)row0 * vs::kDim, (size_t)n * vs::kDim * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return VS_OK;
+}
+float vs_f32_filter_cnorm(double bnmax) { return vs::filter_cnorm(bnmax); }
+float vs_f32_filter_th2(float thr, float e, float cnorm) { return vs::filter_th2(thr, e, cnorm); }
+int vs_bf_filter_stats(vs_index* h, int64_t* out, int reset) {
+    if (!h || !out || !h->filter_ok || !h->filter_stats) {
+        set_error("vs_bf_filter_stats: an index with the bf16 prefilter and an output of four words");
+        return VS_ERR_INVALID;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    unsigned long long v[4];
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(v, h->filter_stats, sizeof(v), hipMemcpyDeviceToHost));
+    out[0] = h->filter_launches;
+    for (int i = 1; i < 4; ++i) out[i] = (int64_t)v[i];
+    if (reset) {
+        HIPCHK(hipMemset(h->filter_stats, 0, sizeof(v)));
+        h->filter_launches = 0;
+    }
     return VS_OK;
 }
 int vs_index_nlist(const vs_index* h) { return h ? h->nlist : 0; }

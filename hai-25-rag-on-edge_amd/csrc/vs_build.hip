@@ -58,7 +58,7 @@ __device__ __forceinline__ bool filter_scaled(float x) {
 }
 constexpr int kImgBlockRows = 32;
 constexpr int kImgLd = kDim + 8;  // 8 lanes per row x 8 banks: the 8 rows of a wave's strided read meet 64 different banks
-__global__ __launch_bounds__(256) void row_filter_image_kernel(const float* __restrict__ v, int64_t rows,
+__global__ __launch_bounds__(256) void row_filter_image_kernel(const float* __restrict__ v, const float* __restrict__ bnorm, int64_t rows,
                                                                unsigned long long* __restrict__ out, uint16_t* __restrict__ img) {
     __shared__ __attribute__((aligned(16))) float tile[kImgBlockRows * kImgLd];
     const int tid = threadIdx.x;
@@ -96,6 +96,8 @@ __global__ __launch_bounds__(256) void row_filter_image_kernel(const float* __re
         atomicMax(out + 0, (unsigned long long)__double_as_longlong(n2));
         atomicMax(out + 1, (unsigned long long)__double_as_longlong(e2));
         atomicMax(out + 2, (unsigned long long)__double_as_longlong(p2));
+        // the largest STORED norm (what the scans read; a non-negative float, widened exactly): filter_cnorm
+        if (bnorm) atomicMax(out + 4, (unsigned long long)__double_as_longlong((double)bnorm[row0 + (tid >> 3)]));
     }
     if (any_bad && (threadIdx.x & 63) == 0) atomicMax(out + 3, 1ull);
     if (!img) return;
@@ -114,10 +116,10 @@ __global__ __launch_bounds__(256) void row_filter_image_kernel(const float* __re
     }
 }
 
-hipError_t launch_row_filter_image(const float* v, int64_t rows, unsigned long long* out, uint16_t* img, hipStream_t s) {
+hipError_t launch_row_filter_image(const float* v, const float* bnorm, int64_t rows, unsigned long long* out, uint16_t* img, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
     const int grid = (int)((rows + kImgBlockRows - 1) / kImgBlockRows);
-    hipLaunchKernelGGL(row_filter_image_kernel, dim3(grid), dim3(256), 0, s, v, rows, out, img);
+    hipLaunchKernelGGL(row_filter_image_kernel, dim3(grid), dim3(256), 0, s, v, bnorm, rows, out, img);
     return hipGetLastError();
 }
 

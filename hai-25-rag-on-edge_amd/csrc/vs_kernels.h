@@ -110,6 +110,38 @@ __host__ __device__ inline float filter_bound(double eq, double nq, double nqp, 
     const double e = eq * f.bmax + nqp * f.emax + (kFiltG32 + kFiltG16) * nqm * nb + 7.888609052210118e-31;  // + 2^-100
     return (float)(e * (1.0 + 1.0 / 1048576.0));  // (the 2^-20 covers the rounding of the norms and of this cast)
 }
+// The L2 hot test of scan_f32f_kernel carries the row norm through the C operand of the chain's first MFMA:
+// with c0 = -bn / 2 (bn the STORED fp32 norm, the one scan_f32s_kernel tests with; halving is exact on well-scaled rows)
+// the accumulator comes out as S'' ~ q'.b' - bn / 2, and the test is S'' > th2.  Claim: every (row, query) that
+// scan_f32s_kernel's hot test RN(bn - 2 S_fl) < thr admits is admitted.  Proof: thr is a float and RN is monotone, so the
+// old test gives bn - 2 S_fl < thr in the reals, i.e. A := S_fl - bn / 2 > -thr / 2.  The MFMA now sums 129 terms, c0 and the
+// 128 exact products, with sum of magnitudes <= ||q'|| ||b'|| + bn / 2 (Cauchy-Schwarz), so under the accumulation
+// assumption above, |S'' - (q'.b' - bn / 2)| <= g16c (||q'|| ||b'|| + bn / 2), g16c = 129 u / (1 - 129 u), u = 2^-22.  Hence
+//   A - S'' <= |S_fl - q'.b'| + g16c ||q'|| ||b'|| + g16c bn / 2
+//           <= E + (g16c - g16) ||q'|| ||b'|| + g16c bnmax / 2      (E = filter_bound: its g16 term is the 128-term one)
+//           <= E (1 + 2^-7) + C                                     =: Et
+// because E 2^-7 >= 2^-7 (g32 + g16) nqm nb >= 1.25 * 2^-22 nqm nb > (g16c - g16) nqm nb, and C = filter_cnorm(bnmax), a
+// constant of the shard: bnmax is its largest stored norm.  So S'' >= A - Et > -thr / 2 - Et >= th2, where filter_th2 forms
+// the right-hand side rounded DOWN: in double, -thr / 2 and e (1 + 2^-7) are exact and the two subtractions round by at
+// most 2^-53 of a partial sum <= |thr| / 2 + Et each, which the 2^-50 term covers; the cast rounds to nearest (at most
+// half an ulp up) and the step to the next float below takes at least that back.  e = +inf (a query outside the
+// well-scaled range) or thr = +inf gives -inf: every row passes.
+constexpr double kFiltG16C = 129.0 / 4194304.0 / (1.0 - 129.0 / 4194304.0);
+__host__ __device__ inline float filter_cnorm(double bnmax) {  // (+ 2^-100 and 2^-20 as in filter_bound: flushed subnormals, this cast)
+    return (float)((kFiltG16C * 0.5 * bnmax + 7.888609052210118e-31) * (1.0 + 1.0 / 1048576.0));
+}
+__host__ __device__ inline float filter_th2(float thr, float e, float cn) {  // thr = stream_l2_thr(tau, ||q||^2)
+    const float inf = __builtin_inff();
+    if (!(e < inf) || !(cn < inf) || thr == inf) return -inf;
+    if (!(thr > -inf)) return inf;  // (nothing is under such a bound; NaN: nothing passes the exact test either)
+    const double et = (double)e * (1.0 + 1.0 / 128.0) + (double)cn;
+    const double x = -0.5 * (double)thr - et;
+    const double y = x - 8.881784197001252e-16 * (0.5 * __builtin_fabs((double)thr) + et);  // 2^-50
+    const float f = (float)y;  // finite or -inf: |y| can exceed the float range only downwards (a huge e)
+    if (f == -inf) return f;
+    const unsigned b = __builtin_bit_cast(unsigned, f);
+    return (b << 1) == 0 ? -1.401298464324817e-45f : __builtin_bit_cast(float, f > 0.f ? b - 1 : b + 1);
+}
 
 // Bounds for a multi-batch scan, computed up front on a sample of the rows: kSeedWaves 16-row tiles spread evenly
 // over the shard, scored against every batch; tau0[batch][q] = next_up of the k1-th smallest of 64 group minima
@@ -187,6 +219,9 @@ struct CandSink {
     int cap;                 // per sub-list
     int nsub;
     int32_t* slow;           // optional [queries]: a query whose lists overflow is marked here instead of raising `overflow`
+    // optional (the bf16 prefilter, vs_bf_filter_stats): [1] += 1 by whoever raises `overflow` first in a launch,
+    // [2] += candidates the sweep wrote, [3] += candidates the recheck kept -- one atomic instruction per wave, at its end
+    unsigned long long* stats;
     // XCD-local sub-lists (0 = off): sub-list = xcd * xcd_subs + hash % xcd_subs (nsub = 8 * xcd_subs) and the counters
     // are sub-list major, cnt[sub * cnt_sub_stride + query]: every counter line and every list is then written by the
     // workgroups of ONE XCD and stays in that XCD's L2 (lines appended to from several XCDs travel between the L2s
@@ -232,6 +267,8 @@ struct StreamParams {
     const uint16_t* qbf;
     const float* qbound;
     const uint16_t* img;     // [n_rows + 64][128] bf16
+    int32_t* dbg;            // diagnostic builds (-DVS_STAMPS) only: scan_f32f_kernel's step split [grid][8 waves][16] (rows 12288.. of the debug buffer)
+    float cnorm;             // filter_cnorm of the shard's largest stored norm (the L2 test, filter_th2)
 };
 hipError_t launch_scan_f32_stream(const StreamParams& p, int grid, hipStream_t s);
 
@@ -342,11 +379,12 @@ hipError_t launch_kpp_step_nd(const float* x, int64_t ld, const float* xnorm, in
 hipError_t launch_row_sqnorm(const float* v, int64_t rows, int dim, float* out, hipStream_t s);
 hipError_t launch_row_sqnorm_ld(const float* v, int64_t rows, int dim, int64_t ld, float* out, hipStream_t s);  // rows ld floats apart
 // shard constants of the bf16 prefilter: out[0..2] = max of ||b||^2, ||b - bf16(b)||^2, ||bf16(b)||^2 as double bits,
-// out[3] = 1 when a row is not well scaled (FilterStats); out must be zeroed before.  The same pass writes the rows'
+// out[3] = 1 when a row is not well scaled (FilterStats), out[4] = max of bnorm[row] (the stored fp32 norms, optional) as
+// double bits; the five words of out must be zeroed before.  The same pass writes the rows'
 // bf16 image for scan_f32f_kernel when img is given: img[row][8 (4 s + g) + 4 u + i] = bf16(v[row][32 s + 16 u + 4 g + i])
 // (round to nearest even, the rounding the statistics are taken from), s, g < 4, u < 2, i < 4: 16-byte chunk 4 s + g of
 // a row is lane (row & 15, g)'s A fragment of k-step s.  Rows [rows, rows + kScanPadRows) of img are the caller's to zero.
-hipError_t launch_row_filter_image(const float* v, int64_t rows, unsigned long long* out, uint16_t* img, hipStream_t s);
+hipError_t launch_row_filter_image(const float* v, const float* bnorm, int64_t rows, unsigned long long* out, uint16_t* img, hipStream_t s);
 
 // ---- IVF ----
 // Per query: the nprobe nearest centroids (ascending (dist, id)) out of a [B][ld] score matrix.

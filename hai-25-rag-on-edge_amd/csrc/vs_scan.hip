@@ -1273,6 +1273,15 @@ constexpr int kUnitRowBytes = kUnitRows * kDim * 2;   // 16 KB of bf16 rows
 constexpr int kUnitBytes = kUnitRowBytes + kUnitRows * 4;  // + the unit's 64 norms
 static_assert(kUnitRows <= kScanPadRows, "units are fetched unclamped: the image and the norms have kScanPadRows spare rows");
 
+// The largest of a lane's four accumulators in two instructions.  Rows and queries are finite on this path.  A plain
+// fmaxf(v0, v1) on values that may be signalling NaNs is compiled to a canonicalising v_max_f32 x, x per operand in front
+// of the maximum; the median of (v0, v1, +inf) is the same number in one v_med3_f32, and the outer pair folds into one
+// v_max3_f32 (whose operands are not canonicalised).  `inf` is +inf in a register that the compiler cannot see through
+// (it would turn the median back into fmaxf).
+__device__ __forceinline__ float max4_finite(const f32x4 v, const float inf) {
+    return __builtin_fmaxf(__builtin_fmaxf(__builtin_amdgcn_fmed3f(v[0], v[1], inf), v[2]), v[3]);
+}
+
 // CBW = column blocks per wave (1, 2, 4 or 8: up to 4, 8, 16 or 32 batches), D = unit slots of the shared ring, IP = the
 // metric (the hot test differs: one kernel per metric keeps the loop free of branches on it).
 template <int CBW, int D, bool IP>
@@ -1330,7 +1339,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
     // The wave's column blocks as bf16 B operands (qb[h][s], SeedParams::qbf), loaded once for the launch, and their
     // widened bounds.  The loads are inline asm so that the compiler puts no wait of its own in front of the operands'
     // first use (it would be vmcnt(0), a drain of the ring); each loaded register is tied to the explicit wait of the
-    // prologue below.  A column block past the launch's (cb >= n_cb) loads the last one and gets thr = -inf / +inf.
+    // prologue below.  A column block past the launch's (cb >= n_cb) loads the last one and gets thr = +inf.
     u32x4 qb[CBW][4];
     float thr[CBW];
     float qn[CBW], tau[CBW], eb[CBW];
@@ -1361,13 +1370,13 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
         asm volatile("" : "+v"(qb[h][0]), "+v"(qb[h][1]), "+v"(qb[h][2]), "+v"(qb[h][3]), "+v"(qn[h]), "+v"(tau[h]), "+v"(eb[h]) :: "memory");
         const int cb = wave + kScanWaves * h;
         const bool live = cb < n_cb && 16 * (cb & 1) + r < p.nq_valid;
-        // |S_fl - S'| <= E.  L2: the exact hot test RN(bn - 2 S_fl) < thr means bn - 2 S_fl < thr, so bn - 2 S' < thr + 2E
-        // <= t (a float: RN, then one step up) and RN(bn - 2 S') <= t < next_up(t) =: thr'.  IP: S_fl > thr gives
-        // S' > thr - E >= thr' := next_down(RN(thr - E)).  E = +inf (a query outside the well-scaled range) admits every row.
+        // |S_fl - S'| <= E.  L2: the accumulators start from -bn / 2 (score_tile), and the exact hot test
+        // RN(bn - 2 S_fl) < thr implies S'' > th2 = filter_th2(thr, E, C) (vs_kernels.h).  IP: S_fl > thr gives
+        // S' > thr - E >= thr' := next_down(RN(thr - E)).  E = +inf (a query outside the well-scaled range) admits every
+        // row.  Either way a value passes when it is ABOVE thr[h]: a dead column block or a padding query gets +inf.
         const float inf = __builtin_inff();
         if constexpr (!IP) {
-            const float t = nextafterf(stream_l2_thr(tau[h], qn[h]) + 2.0f * eb[h], inf);
-            thr[h] = live ? nextafterf(t, inf) : -inf;
+            thr[h] = live ? filter_th2(stream_l2_thr(tau[h], qn[h]), eb[h], p.cnorm) : inf;
         } else {
             thr[h] = live ? nextafterf(-tau[h] - eb[h], -inf) : inf;
         }
@@ -1375,6 +1384,8 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
 
     int4* wbuf = p.sink.wbuf + ((int64_t)blockIdx.x * kScanWaves + wave) * p.sink.wcap;
     int wbase = 0;  // wave-uniform fill of the private candidate buffer
+    float opaque_inf = __builtin_inff();  // for max4_finite: a scalar register, opaque to the optimiser
+    asm volatile("" : "+s"(opaque_inf));
 
     // Step t (unit t in slot t % D; the fragments of its tiles 0 and 1 already in registers; units t + 1 .. t + D - 2 in
     // flight on entry):
@@ -1408,30 +1419,27 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
     read_frags(0, 0, 0);
     read_frags(1, 0, 1);
     auto score_tile = [&](const int set, const int row_t) __attribute__((always_inline)) {  // row_t: this lane's first row, 16 tile + 4 g
-        const f32x4 bt = bn[set];
+        // L2: the chain starts from c0 = -bn / 2, the tile's norms scaled once per tile (the same registers feed every
+        // column block: the MFMA writes its result elsewhere), so the accumulators are S'' = q'.b' - bn / 2; IP: from zero
+        f32x4 c0 = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if constexpr (!IP) c0 = -0.5f * bn[set];
         auto mfma_cb = [&](const int h) __attribute__((always_inline)) -> f32x4 {
-            f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = c0;
 #pragma unroll
             for (int s = 0; s < 4; ++s)
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a[set][s]), __builtin_bit_cast(bf16x8, qb[h][s]), acc, 0, 0, 0);
             return acc;
         };
-        // L2: one fma and one compare per value, as in scan_f32s_kernel; IP: one compare (a dead column block has
-        // thr = -inf / +inf); the verdicts as wave masks in scalar registers
+        // Both metrics: a value passes when it is above thr[h], so the largest of the lane's four decides for them --
+        // two maxima, one compare into vcc, one branch (a dead column block has thr = +inf)
         auto test_cb = [&](const int h, const f32x4 acc) __attribute__((always_inline)) {
-            unsigned long long hit[4], hits = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if constexpr (!IP) hit[j] = __ballot(fmaf(-2.0f, acc[j], bt[j]) < thr[h]);
-                else hit[j] = __ballot(acc[j] > thr[h]);  // -acc < tau, widened
-                hits |= hit[j];
-            }
-            if (__builtin_expect(hits != 0, 0)) {  // rare: a few hundred rows per query per million
+            if (__builtin_expect(__ballot(max4_finite(acc, opaque_inf) > thr[h]) != 0, 0)) {  // rare: a few hundred rows per query per million
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if (!hit[j]) continue;  // wave-uniform
+                    const unsigned long long hit = __ballot(acc[j] > thr[h]);
+                    if (!hit) continue;  // wave-uniform
                     const int row = row_t + j;
-                    const bool pass = ((hit[j] >> lane) & 1) && row < (int)p.n_rows;  // (spare rows of the image score as zeros)
+                    const bool pass = ((hit >> lane) & 1) && row < (int)p.n_rows;  // (spare rows of the image score as zeros)
                     const unsigned long long mask = __ballot(pass);
                     if (mask) {
                         const int pos = wbase + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
@@ -1459,11 +1467,32 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
         // barrier behind which the set's slot is refilled) follows the set's LDS reads
         asm volatile("" ::"v"(acc));
     };
+    // Diagnostic builds (-DVS_STAMPS, scripts/diag/f32fstamps.py): every wave splits its steps by the shader clock -- [0]
+    // between steps, [1] the vmcnt wait, [2] the barrier, [3] the unit's DMA issue, [4 + i] tile i -- summed over its steps
+    // in scalar registers and written once, by lane 0 at the wave's end, to dbg[workgroup][wave][16] ([8] = steps, [9] =
+    // candidates).  (Reading the clock waits for lgkmcnt(0), so a stamped tile also waits for the fragment reads issued
+    // in it: the stamped kernel is slower than the product, the shares are what it is for.)
+#ifdef VS_STAMPS
+    int st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned st_prev = (unsigned)__builtin_amdgcn_s_memtime();
+#define VS_F32F_STAMP(i)                                                \
+    do {                                                                \
+        const unsigned now_ = (unsigned)__builtin_amdgcn_s_memtime();   \
+        st_sum[i] += (int)(now_ - st_prev);                             \
+        st_prev = now_;                                                 \
+    } while (0)
+#else
+#define VS_F32F_STAMP(i)
+#endif
     auto step = [&](const int t, const int sl) __attribute__((always_inline)) {
+        VS_F32F_STAMP(0);
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 3) * kUnitVmem) : "memory");
+        VS_F32F_STAMP(1);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
+        VS_F32F_STAMP(2);
         issue_unit(t + D - 1, (sl + D - 1) % D);
+        VS_F32F_STAMP(3);
         const int row_u = ((int)blockIdx.x + t * G) * kUnitRows + 4 * g;
 #pragma unroll
         for (int i = 0; i < kUnitTiles; ++i) {
@@ -1471,6 +1500,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
             // two tiles ahead, into the set just consumed (past the end: the re-read last unit, unused)
             if (i + 2 < kUnitTiles) read_frags(i & 1, sl, i + 2);
             else read_frags(i & 1, (sl + 1) % D, i + 2 - kUnitTiles);
+            VS_F32F_STAMP(4 + i);
         }
     };
     // one turn of the ring per iteration, every slot a constant; T is workgroup-uniform: every wave passes the same barriers
@@ -1488,8 +1518,23 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
         if constexpr (D > 7) { if (t0 + 7 >= T) break; step(t0 + 7, 7); }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // retire the tail prefetches before the wave ends
+#ifdef VS_STAMPS
+    if (p.dbg && lane == 0) {
+        int32_t* o = p.dbg + ((int64_t)blockIdx.x * kScanWaves + wave) * 16;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = st_sum[i];
+        o[8] = T;
+        o[9] = wbase;
+    }
+#endif
+#undef VS_F32F_STAMP
     const RecheckF32 fix{p.base, p.bnorm, p.q, p.q_batch_stride, p.qnorm, p.tau0, p.metric, p.id_offset};
-    sink_bin_wave<RecheckF32, true>(p.sink, (int)blockIdx.x * kScanWaves + wave, wbase, lane, fix);
+    int kept = sink_bin_wave<RecheckF32, true>(p.sink, (int)blockIdx.x * kScanWaves + wave, wbase, lane, fix);
+    if (p.sink.stats && wbase > 0) {  // (wave-uniform) one atomic instruction: lane 0 adds the sweep's count, lane 1 the survivors
+#pragma unroll
+        for (int u = 32; u >= 1; u >>= 1) kept += __shfl_xor(kept, u);
+        if (lane < 2) atomicAdd(p.sink.stats + 2 + lane, (unsigned long long)(lane == 0 ? wbase : kept));
+    }
 }
 
 template <int CBW>

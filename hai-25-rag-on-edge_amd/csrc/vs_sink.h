@@ -11,14 +11,21 @@ namespace vs {
 struct SinkEntryAsIs {
     __device__ __forceinline__ int4 operator()(const int4& c) const { return c; }
 };
+// the launch's overflow word; where the sink counts (CandSink::stats), the first to raise it in a launch counts the launch
+__device__ __forceinline__ void sink_raise_overflow(const CandSink& p) {
+    if (!p.stats) p.overflow[0] = 1;
+    else if (atomicExch(p.overflow, 1) == 0) atomicAdd(p.stats + 1, 1ull);
+}
 // Drop = true: an entry that `fix` returns with a negative query is not binned (the bf16 prefilter's exact recheck).
+// Returns how many entries this lane binned (or tried to: a full list).
 template <typename Fix = SinkEntryAsIs, bool Drop = false>
-__device__ __forceinline__ void sink_bin_wave(const CandSink& p, int wb, int n, int lane, const Fix fix = Fix(), int diag = 0) {
+__device__ __forceinline__ int sink_bin_wave(const CandSink& p, int wb, int n, int lane, const Fix fix = Fix(), int diag = 0) {
+    int kept = 0;
     if (n > p.wcap) {
-        if (lane == 0) p.overflow[0] = 1;  // entries were dropped: the fallback kernels behind take over
-        return;
+        if (lane == 0) sink_raise_overflow(p);  // entries were dropped: the fallback kernels behind take over
+        return 0;
     }
-    if (n == 0) return;
+    if (n == 0) return 0;
     // The wave reads back what it stored itself.  Its stores are complete after the wait; the lines were never read in
     // this launch before (so no stale copy can sit in this CU's vector cache), and the loads below are agent-scope
     // atomic loads anyway, which do not hit that cache.  (An acquire fence here invalidates the whole vector cache
@@ -37,6 +44,7 @@ __device__ __forceinline__ void sink_bin_wave(const CandSink& p, int wb, int n, 
         if constexpr (Drop) {
             if (c.x < 0) continue;
         }
+        ++kept;
         const int64_t lst = (int64_t)c.x * p.nsub + sub;
 #ifdef VS_STAMPS
         if (diag & 32) {
@@ -52,9 +60,10 @@ __device__ __forceinline__ void sink_bin_wave(const CandSink& p, int wb, int n, 
         } else if (p.slow) {
             p.slow[c.x] = 1;    // more rows under this query's bound than its lists hold: the exact slow path takes it
         } else {
-            p.overflow[0] = 1;  // ... or, where there is no per-query slow path, the launch's fallback kernels
+            sink_raise_overflow(p);  // ... or, where there is no per-query slow path, the launch's fallback kernels
         }
     }
+    return kept;
 }
 
 }  // namespace vs

@@ -608,6 +608,18 @@ VS_API float vs_f32_filter_bound(double eq, double nq, double nqp, double bmax, 
  * VS_ERR_INVALID when the index has no image (not a 128-d brute-force index, too small for the prefilter, ill-scaled
  * rows, VSEARCH_F32_FILTER=0) or the range leaves it. */
 VS_API int vs_bf_filter_image_read(const vs_index* h, int64_t row0, int64_t n, uint16_t* dst);
+/* The L2 test of the prefilter carries the row norm through the MFMA's C operand: a value S'' = bf16 dot -
+ * norm / 2 passes when it is above th2.  vs_f32_filter_cnorm: the shard constant C of that test from the shard's largest
+ * stored fp32 norm.  vs_f32_filter_th2: the bound th2 from the exact scan's hot-test bound thr (a row passes the exact
+ * scan when RN(norm - 2 dot) < thr), the query's E (vs_f32_filter_bound) and C, as the library computes it (rounded
+ * down).  Pure host arithmetic. */
+VS_API float vs_f32_filter_cnorm(double bnmax);
+VS_API float vs_f32_filter_th2(float thr, float e, float cnorm);
+/* Counters of the prefilter since the index was created or last reset (waits for the device): out[0] = launches that took
+ * the prefilter, out[1] = of those, launches whose candidate buffers overflowed (the exact fallback scan behind produced
+ * their results), out[2] = candidates written by the sweeps, out[3] = candidates that survived the exact recheck.
+ * VS_ERR_INVALID when the index has no prefilter (see vs_bf_filter_image_read). */
+VS_API int vs_bf_filter_stats(vs_index* h, int64_t* out /* [4] */, int reset);
 VS_API void vs_destroy(vs_index* h);
 
 #ifdef __cplusplus
