@@ -186,6 +186,8 @@ def lib():
         "vs_ivf_nd_widek_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_ivf_search_topk": (i32, [vp, vp, i64, i32, i32, vp, vp, C.POINTER(i64), C.POINTER(Timing)]),
         "vs_ivf_search_topk_dev_multi": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "vs_ivf_search_metric": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, C.POINTER(i64), C.POINTER(Timing)]),
+        "vs_ivf_search_metric_dev_multi": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
         "vs_prof_read_launches": (i32, [vp, i32, vp, i64, C.POINTER(i64)]),
         "vs_index_rows": (i64, [vp]),
         "vs_index_dim": (i32, [vp]),
@@ -686,6 +688,25 @@ class IVFIndex(_Index):
                               stream: int):
         """search_dev_multi for 1 <= k <= 128 on every IVF index (vs_ivf_search_topk_dev_multi); asynchronous on `stream`."""
         _check(lib().vs_ivf_search_topk_dev_multi(self._h, q_ptr, n_batches, B, k, nprobe, ids_ptr, dists_ptr, stream))
+
+    def search_metric(self, queries, k: int, nprobe: int, metric: int, timing: Timing | None = None):
+        """search_topk under a metric given per call (vs_ivf_search_metric), on every IVF index and 1 <= k <= 128; the
+        index's own set_metric setting is neither used nor changed.  METRIC_IP: the scores q.v, descending, +inf in empty
+        slots.  Returns (ids, dists, total_candidates)."""
+        q = _f32c(queries).reshape(-1, self.d)
+        nq = q.shape[0]
+        ids = np.empty((nq, max(k, 0)), dtype=np.int32)
+        dists = np.empty((nq, max(k, 0)), dtype=np.float32)
+        total = C.c_int64(0)
+        tm = timing if timing is not None else Timing()
+        _check(lib().vs_ivf_search_metric(self._h, _p(q), nq, k, nprobe, metric, _p(ids), _p(dists), C.byref(total), C.byref(tm)))
+        return ids, dists, int(total.value)
+
+    def search_metric_dev_multi(self, q_ptr: int, n_batches: int, B: int, k: int, nprobe: int, metric: int, ids_ptr: int,
+                                dists_ptr: int, stream: int):
+        """search_topk_dev_multi under a metric given per call (vs_ivf_search_metric_dev_multi); asynchronous on `stream`.
+        METRIC_IP: dists are -(q.v), ascending."""
+        _check(lib().vs_ivf_search_metric_dev_multi(self._h, q_ptr, n_batches, B, k, nprobe, metric, ids_ptr, dists_ptr, stream))
 
     def nd_widek_stats(self, reset: bool = False):
         """(candidates ranked from candidate lists, most candidates of one query, queries ranked by the exact fallback) of

@@ -5,6 +5,9 @@
 //   ... --gpus N : one process per GPU (forked before HIP starts); every rank loads the lists it owns (longest-first
 //   round robin), runs the same coarse stage and scans its lists; per-shard top-k lists meet in one RCCL all-gather per
 //   32 batches (vs_ivf_search_sharded); rank 0 writes the files ("Avg candidates" is then rank 0's share).
+//   ... --metric ip|l2 : the search goes through vs_ivf_search_metric with that metric, at any dimension; under ip
+//   results.txt holds the scores q.v, descending, as the reference's own main_ivf prints them.  Without the flag the
+//   index's own metric (squared L2) is used, as before.  Not together with --gpus N > 1.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -18,10 +21,27 @@
 #include "../../include/vsearch.hpp"
 #include "cli_ranks.hpp"
 
+// takes "--metric ip|l2" out of argv like --gpus; -1 when the flag is not given
+static int take_metric_flag(int& argc, char** argv) {
+    for (int i = 1; i < argc; ++i)
+        if (std::string(argv[i]) == "--metric" && i + 1 < argc) {
+            const std::string v = argv[i + 1];
+            if (v != "ip" && v != "l2") throw std::runtime_error("--metric must be ip or l2");
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2;
+            return v == "ip" ? VS_METRIC_IP : VS_METRIC_L2;
+        }
+    return -1;
+}
+
 int main(int argc, char* argv[]) {
     vsearch::RankSet ranks;
+    int METRIC = -1;
     try {
-        ranks = vsearch::fork_ranks(vsearch::take_gpus_flag(argc, argv));  // before anything touches HIP
+        METRIC = take_metric_flag(argc, argv);
+        const int gpus = vsearch::take_gpus_flag(argc, argv);
+        if (METRIC >= 0 && gpus > 1) throw std::runtime_error("--metric is not available together with --gpus N > 1 (the sharded calls are squared L2)");
+        ranks = vsearch::fork_ranks(gpus);  // before anything touches HIP
     } catch (const std::exception& e) {
         std::cerr << "FATAL ERROR: " << e.what() << std::endl;
         return 1;
@@ -29,7 +49,7 @@ int main(int argc, char* argv[]) {
     if (argc < 6) {
         if (ranks.rank == 0)
             std::cerr << "Usage: " << argv[0]
-                      << " <index_dir> <queries.fvecs> <results_dir> <backend.so> <top_k> [nprobe] [groundtruth.ivecs] [batch] [--gpus N]"
+                      << " <index_dir> <queries.fvecs> <results_dir> <backend.so> <top_k> [nprobe] [groundtruth.ivecs] [batch] [--gpus N] [--metric ip|l2]"
                       << std::endl;
         return vsearch::join_ranks(ranks, 1);
     }
@@ -78,6 +98,7 @@ int main(int argc, char* argv[]) {
             vsearch::IVFIndex::SearchTiming wt;
             if (wn > 0) {
                 if (ranks.world > 1) ivf.searchBatchSharded(ranks.comm, wq, (int)wn, TOP_K, NPROBE, wi, ws, wt);
+                else if (METRIC >= 0) ivf.searchBatchMetric(wq, (int)wn, TOP_K, NPROBE, METRIC, wi, ws, wt);
                 else ivf.searchBatchTopk(wq, (int)wn, TOP_K, NPROBE, wi, ws, wt);
             }
         }
@@ -95,6 +116,7 @@ int main(int argc, char* argv[]) {
             vsearch::IVFIndex::SearchTiming timing;
             auto b0 = std::chrono::high_resolution_clock::now();
             if (ranks.world > 1) total_candidates += ivf.searchBatchSharded(ranks.comm, batch, (int)cur, TOP_K, NPROBE, bi, bs, timing);
+            else if (METRIC >= 0) total_candidates += ivf.searchBatchMetric(batch, (int)cur, TOP_K, NPROBE, METRIC, bi, bs, timing);
             else total_candidates += ivf.searchBatchTopk(batch, (int)cur, TOP_K, NPROBE, bi, bs, timing);  // (k up to 128 at every dimension)
             auto b1 = std::chrono::high_resolution_clock::now();
             const double call_ms = std::chrono::duration<double, std::milli>(b1 - b0).count();

@@ -277,6 +277,12 @@ struct vs_index {
         vs::DevBuf<unsigned long long> stats;  // [3]: see vs_ivf_nd_widek_stats
         bool ready = false;          // every buffer above allocated (ensure_ivf_nd_wide)
     } ivfndw;
+    // ... and what an inner-product group on the byte rows needs, built at the index's first such call (ensure_ivf_nd_ip)
+    struct IvfNdIp {
+        vs::DevBuf<int32_t> rsum;    // [n_rows + 64] sum (b - 128) per row of d_nd_u8
+        vs::DevBuf<int32_t> qsum;    // [kIvfNdGroupQ] sum (q - 128) per query of the group
+        bool ready = false;
+    } ivfndip;
     vs::Stream wide_stream[kWideLanesMax];
     vs::Event wide_fork, wide_join[kWideLanesMax];
     bool wide_streams_ready = false;
@@ -702,9 +708,11 @@ int refuse_general_bf(const vs_index* h, const char* what) { return h && h->kind
 // what a general IVF index leaves out
 int refuse_general_ivf(const vs_index* h, const char* what) {
     if (!h || !h->general || h->kind != 1) return VS_OK;
-    char msg[200];
-    snprintf(msg, sizeof(msg), "%s: not available on a general-dimension IVF index (dim = %d): %ssquared L2, k <= 16, one GPU", what,
-             h->dim, h->nd_from_u8 ? "" : "fp32 rows, ");
+    char msg[280];
+    snprintf(msg, sizeof(msg),
+             "%s: not available on a general-dimension IVF index (dim = %d): %ssquared L2, k <= 16, one GPU (inner product and k <= 128: "
+             "vs_ivf_search_metric)",
+             what, h->dim, h->nd_from_u8 ? "" : "fp32 rows, ");
     set_error(msg);
     return VS_ERR_UNSUPPORTED;
 }
@@ -1282,6 +1290,19 @@ int ensure_ivf_nd_wide(vs_index* h) {
     return VS_OK;
 }
 
+// ... and the row term of the inner-product byte scan, the same way: allocated and filled (one launch on s, ahead of
+// the scan that reads it) at the first inner-product group of an index with a byte copy
+int ensure_ivf_nd_ip(vs_index* h, hipStream_t s) {
+    if (h->ivfndip.ready) return VS_OK;
+    vs_index::IvfNdIp W;
+    int rc;
+    if ((rc = W.rsum.alloc((size_t)h->n_rows + 64)) || (rc = W.qsum.alloc((size_t)vs::kIvfNdGroupQ))) return rc;
+    HIPCHK(vs::launch_ivf_nd_i8_rowsum(h->d_nd_u8, h->dim_b, h->n_rows, W.rsum, s));
+    W.ready = true;
+    h->ivfndip = std::move(W);
+    return VS_OK;
+}
+
 // the fp32 plan of a launch group of a general IVF index on the index's own tables, every pair
 vs::IvfNdParams ivf_nd_params(vs_index* h, const float* q_dev, int group_q, int k, int kcap, int nprobe) {
     vs_index::IvfNd& W = h->ivfnd;
@@ -1309,6 +1330,7 @@ vs::IvfNdParams ivf_nd_params(vs_index* h, const float* q_dev, int group_q, int 
     ip.part_i = W.part_i;
     ip.cand_count = h->d_cand;
     if (h->d_nd_stats) ip.pair_count = h->d_nd_stats + 1;
+    ip.metric = h->metric;
     return ip;
 }
 
@@ -1316,7 +1338,9 @@ vs::IvfNdParams ivf_nd_params(vs_index* h, const float* q_dev, int group_q, int 
 // Coarse scores per batch are the brute-force general scan's on the centroid table (equal scores: the lower list id,
 // launch_pick_probes); then the plan, the list-major scan and the ranking of the group's partial lists.  An index with a
 // byte copy of its rows plans twice: the pairs of the queries that qualify for the byte rows (IvfNdI8Params::valid) go to
-// ivf_scan_nd_i8_kernel, the others to ivf_scan_nd_kernel, both into the same partial lists.
+// ivf_scan_nd_i8_kernel, the others to ivf_scan_nd_kernel, both into the same partial lists.  The metric is the handle's at the
+// time of the call (vs_ivf_search_metric* set it for the call's duration): under inner product the coarse scores are
+// -(q.c), the scans run their IP instantiations, and the byte scan needs the rows' byte sums (ensure_ivf_nd_ip).
 int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int nprobe, float* out_d, int32_t* out_i, hipStream_t s) {
     const int kcap = pick_kcap(k);
     if (!kcap) return refuse_general_ivf(h, "k > 16");
@@ -1337,6 +1361,7 @@ int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int 
     vs::IvfNdParams ip = ivf_nd_params(h, q_dev, nb * B, k, kcap, nprobe);
     vs::IvfNdI8Params bp{};
     const bool two_plans = (bool)h->d_nd_u8;
+    if (two_plans && h->metric == VS_METRIC_IP && (rc = ensure_ivf_nd_ip(h, s))) return rc;
     if (two_plans) {
         bp.s = ip;
         bp.s.list_cnt = W.plan8;
@@ -1355,6 +1380,10 @@ int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int 
         bp.q8rows = W.q8rows;
         bp.qterm = W.qterm;
         bp.valid = W.valid;
+        if (h->metric == VS_METRIC_IP) {
+            bp.rsum = h->ivfndip.rsum;
+            bp.qsum = h->ivfndip.qsum;
+        }
         ip.route = W.valid;
         ip.route_want = 0;
         HIPCHK(vs::launch_ivf_nd_i8_prep(bp, s));
@@ -3185,6 +3214,57 @@ int vs_ivf_search_topk_dev_multi(vs_index* h, const float* queries_dev, int n_ba
     return rc ? rc : order_end(h, user);
 }
 
+// The metric of one call: the kernels, the coarse scores and the host pipeline's sign all read h->metric, so the call runs
+// with it set to its own metric and puts the index's setting back on every way out.  (Calls on one index are not
+// concurrent: its scratch is one set.)
+struct CallMetric {
+    vs_index* h;
+    int saved;
+    CallMetric(vs_index* h_, int metric) : h(h_), saved(h_->metric) { h->metric = metric; }
+    ~CallMetric() { h->metric = saved; }
+    CallMetric(const CallMetric&) = delete;
+    CallMetric& operator=(const CallMetric&) = delete;
+};
+
+// the checks the two vs_ivf_search_metric* calls share, in the order vsearch.h states them
+static int search_metric_checks(const char* who, const vs_index* h, bool ptrs_ok, int k, int metric) {
+    char msg[160];
+    if (!h || !ptrs_ok) {
+        snprintf(msg, sizeof(msg), "%s: null argument", who);
+        set_error(msg);
+        return VS_ERR_INVALID;
+    }
+    if (h->kind == 0) {
+        snprintf(msg, sizeof(msg), "%s: not an IVF index", who);
+        set_error(msg);
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (metric != VS_METRIC_L2 && metric != VS_METRIC_IP) {
+        snprintf(msg, sizeof(msg), "%s: metric must be VS_METRIC_L2 or VS_METRIC_IP", who);
+        set_error(msg);
+        return VS_ERR_INVALID;
+    }
+    if (k < 1) {
+        snprintf(msg, sizeof(msg), "%s: k < 1", who);
+        set_error(msg);
+        return VS_ERR_INVALID;
+    }
+    if (k > vs::kIvfNdWideKMax) {
+        snprintf(msg, sizeof(msg), "%s: k > 128", who);
+        set_error(msg);
+        return VS_ERR_UNSUPPORTED;
+    }
+    return VS_OK;
+}
+
+int vs_ivf_search_metric_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k, int nprobe, int metric,
+                                   int32_t* ids_dev, float* dists_dev, void* stream) {
+    const int rc = search_metric_checks("vs_ivf_search_metric_dev_multi", h, queries_dev && ids_dev && dists_dev, k, metric);
+    if (rc) return rc;
+    CallMetric cm(h, metric);
+    return vs_ivf_search_topk_dev_multi(h, queries_dev, n_batches, B, k, nprobe, ids_dev, dists_dev, stream);
+}
+
 #ifdef VS_STAMPS
 // diagnostic builds only (make EXTRA=-DVS_STAMPS; not part of the ABI): state of the wide IVF pipeline after the last launch group
 __attribute__((visibility("default"))) int vs_debug_ivf_wide_stats(vs_index* h, int64_t* out /*[8]*/) {
@@ -4358,6 +4438,14 @@ int vs_ivf_search_topk(vs_index* h, const float* queries_host, int64_t nq, int k
         return VS_ERR_UNSUPPORTED;
     }
     return guarded([&] { return ivf_search_host(h, nullptr, queries_host, nq, k, nprobe, ids, dists, total_candidates, timing); });
+}
+
+int vs_ivf_search_metric(vs_index* h, const float* queries_host, int64_t nq, int k, int nprobe, int metric, int32_t* ids, float* dists,
+                         int64_t* total_candidates, vs_timing* timing) {
+    const int rc = search_metric_checks("vs_ivf_search_metric", h, queries_host && ids && dists, k, metric);
+    if (rc) return rc;
+    CallMetric cm(h, metric);
+    return vs_ivf_search_topk(h, queries_host, nq, k, nprobe, ids, dists, total_candidates, timing);
 }
 
 int vs_ivf_search_sharded(vs_index* h, vs_comm* c, const float* queries_host, int64_t nq, int k, int nprobe, int32_t* ids,

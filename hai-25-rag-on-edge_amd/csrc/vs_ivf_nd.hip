@@ -1,5 +1,5 @@
-// vs_ivf_nd.hip -- the list-major IVF scan of a general index, 1 <= dim <= 2048, fp32 rows, squared L2 (gfx950;
-// DESIGN 4.6c).
+// vs_ivf_nd.hip -- the list-major IVF scan of a general index, 1 <= dim <= 2048, fp32 rows, squared L2 or inner product
+// (gfx950).
 //
 //   ivf_nd_prep     : the launch group's queries zero-padded row-major [group_q][dim_p] and their squared norms in
 //                     nd_prep_kernel's summation order; clears the plan's counters.
@@ -21,8 +21,9 @@
 //
 // Kernel contract: the accumulation chain of a (row, query) distance is scan_nd_kernel's -- the same order of s, u and
 // i and the same lane-to-k mapping, then fma(-2, dot, qn + bn) -- so a distance is bit-identical to what the brute-force
-// general scan returns for the pair, whichever item, slot or wave computed it.  Slots past the run's end in a list's
-// last item repeat the item's first slot; their results are discarded.
+// general scan returns for the pair, whichever item, slot or wave computed it.  Under inner product (IvfNdParams::metric,
+// the IP instantiation) the score is the same chain negated, -(q.v), as the brute-force general scan returns it under
+// VS_METRIC_IP.  Slots past the run's end in a list's last item repeat the item's first slot; their results are discarded.
 //
 // All loads are ordinary global loads whose waits the compiler places.  The row loads carry no nontemporal
 // hint, unlike scan_nd_kernel's: a list is read again by every item that probes it, and with the hint the pipeline was
@@ -159,7 +160,8 @@ __global__ __launch_bounds__(256) void ivf_nd_fill(const IvfNdParams p) {
     p.slots[pos] = q << 8 | rank;
 }
 
-template <int KCAP>
+// IP: the inner-product instantiation -- the same loads and chain, the epilogue is d = -acc and no norm is loaded
+template <int KCAP, bool IP>
 __global__ __launch_bounds__(kScanThreads, 1) void ivf_scan_nd_kernel(const IvfNdParams p) {
     constexpr int T = kIvfNdTiles;
     __shared__ NdTailLds tail;
@@ -184,7 +186,8 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_scan_nd_kernel(const IvfN
         const int blocks_total = (int)((row_end - row_lo + kIvfNdBlockRows - 1) / kIvfNdBlockRows);
         const int sv = p.slots[slot0 + (r < n_slots ? r : 0)];  // (a slot past the run's end repeats the first: discarded below)
         const int qi = sv >> 8;
-        const float qn = p.qnorm[qi];
+        float qn = 0.f;
+        if constexpr (!IP) qn = p.qnorm[qi];
         // this lane's 16 bytes of a 64-byte segment of its slot's padded query row
         const char* qb = reinterpret_cast<const char*>(p.qrows + (int64_t)qi * dim_p + 4 * g);
         float wmin = VS_INF, tau = VS_INF;
@@ -249,8 +252,11 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_scan_nd_kernel(const IvfN
                 float d[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    d[j] = fmaf(-2.0f, acc[t][j], qn + p.vnorm[rbase + j]);  // (the norms have 64 spare entries)
-                    if (ragged && rbase + j > last_row) d[j] = VS_INF;
+                    if constexpr (IP)
+                        d[j] = -acc[t][j];  // (an exactly zero product is +0 out of the chain: -0.0)
+                    else
+                        d[j] = fmaf(-2.0f, acc[t][j], qn + p.vnorm[rbase + j]);  // (the norms have 64 spare entries)
+                    if (ragged && rbase + j > last_row) d[j] = VS_INF;  // (under IP a spare row's -0.0 must never compete)
                 }
                 nd_topk_step<KCAP>(d, rbase, 0, wmin, tau, ld[0], li[0]);
             }
@@ -291,10 +297,15 @@ hipError_t launch_ivf_nd_plan_second(const IvfNdParams& p, hipStream_t s) {
 
 hipError_t launch_ivf_nd_scan(const IvfNdParams& p, int grid, hipStream_t s) {
     if (grid < 1 || p.k < 1 || p.k > p.kcap) return hipErrorInvalidValue;
-    if (p.kcap == 8)
-        hipLaunchKernelGGL(ivf_scan_nd_kernel<8>, dim3(grid), dim3(kScanThreads), 0, s, p);
+    if (p.metric != 0 && p.metric != 1) return hipErrorInvalidValue;
+    if (p.kcap == 8 && !p.metric)
+        hipLaunchKernelGGL((ivf_scan_nd_kernel<8, false>), dim3(grid), dim3(kScanThreads), 0, s, p);
+    else if (p.kcap == 16 && !p.metric)
+        hipLaunchKernelGGL((ivf_scan_nd_kernel<16, false>), dim3(grid), dim3(kScanThreads), 0, s, p);
+    else if (p.kcap == 8)
+        hipLaunchKernelGGL((ivf_scan_nd_kernel<8, true>), dim3(grid), dim3(kScanThreads), 0, s, p);
     else if (p.kcap == 16)
-        hipLaunchKernelGGL(ivf_scan_nd_kernel<16>, dim3(grid), dim3(kScanThreads), 0, s, p);
+        hipLaunchKernelGGL((ivf_scan_nd_kernel<16, true>), dim3(grid), dim3(kScanThreads), 0, s, p);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();

@@ -18,6 +18,12 @@
 // fits).  The plan (vs_ivf_nd.hip) gives the pairs of valid queries slots in the byte plan and every other pair a slot
 // in the fp32 plan: a pair has exactly one writer, whichever it is it writes the same bits, and nothing is rerun.
 //
+// Inner product (IvfNdParams::metric == 1, the IP instantiation): under the same rule every partial sum of q.b is at most
+// (||q||^2 + ||b||^2) / 2 <= 2^23, so the fp32 chain is exact in any order and equals the int32 product.  The epilogue
+// rebuilds it from the stored bytes, q.b = q'.b' + 128 (sum q' + sum b') + 128^2 dim, with sum q' from ivf_nd_prep_i8
+// and sum b' from ivf_nd_i8_rowsum_kernel (built at the index's first inner-product call), and writes -(float)(q.b):
+// the fp32 scan's bits, -0.0 for a zero product included.
+//
 // All loads are ordinary global loads whose waits the compiler places.  The row loads carry no nontemporal hint, as in
 // ivf_scan_nd_kernel: a list is read again by every item that probes it.  Measured once with the hint on the byte rows
 // (1 M rows, profiles/ivf_nd_u8_bench.txt): the list scan was 3 % slower at 96-d and 9 % slower at 384-d.
@@ -57,12 +63,13 @@ __global__ __launch_bounds__(256) void ivf_nd_prep_i8(const IvfNdI8Params pb) {
     const int row = threadIdx.x >> 3, j = threadIdx.x & 7;
     const bool live = row < nq;
     const float* src = p.q + (int64_t)(q0 + (live ? row : 0)) * dim;
-    int t = 0, n2 = 0, bad = 0;
+    int t = 0, n2 = 0, bad = 0, s1 = 0;
     if (live) {
         for (int i = j; i < dim; i += 8) {
             int xi;
             if (byte_value(src[i], xi)) {
                 t += (xi - 128) * (xi - 128);
+                s1 += xi - 128;
                 n2 += xi * xi;
             } else {
                 bad = 1;
@@ -73,17 +80,20 @@ __global__ __launch_bounds__(256) void ivf_nd_prep_i8(const IvfNdI8Params pb) {
     for (int m = 1; m < 8; m <<= 1) {
         t += __shfl_xor(t, m);
         n2 += __shfl_xor(n2, m);
+        s1 += __shfl_xor(s1, m);
         bad |= __shfl_xor(bad, m);
     }
     if (j == 0 && live) {
         pb.qterm[q0 + row] = t;
+        if (pb.qsum) pb.qsum[q0 + row] = s1;  // (inner product only)
         // (n2 <= 2048 * 255^2, 0 <= bmax < 2^24: no overflow)
         pb.valid[q0 + row] = (!pb.all_f32 && !bad && n2 <= kNd8NormLimit - pb.bmax) ? 1 : 0;
     }
     for (int i = blockIdx.x * 256 + threadIdx.x; i < 2 * p.nlist; i += gridDim.x * 256) p.list_cnt[i] = 0;
 }
 
-template <int KCAP>
+// IP: the inner-product instantiation -- the same loads and MFMAs; the epilogue rebuilds q.b from the shifted bytes
+template <int KCAP, bool IP>
 __global__ __launch_bounds__(kScanThreads, 1) void ivf_scan_nd_i8_kernel(const IvfNdI8Params pb) {
     const IvfNdParams& p = pb.s;
     constexpr int T = kIvfNd8Tiles;
@@ -109,7 +119,11 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_scan_nd_i8_kernel(const I
         const int blocks_total = (int)((row_end - row_lo + kIvfNd8BlockRows - 1) / kIvfNd8BlockRows);
         const int sv = p.slots[slot0 + (r < n_slots ? r : 0)];  // (a slot past the run's end repeats the first: discarded below)
         const int qi = sv >> 8;
-        const int qt = pb.qterm[qi];
+        int qt;
+        if constexpr (IP)
+            qt = 128 * pb.qsum[qi] + 16384 * p.dim;  // q.b = q'.b' + 128 (sum q' + sum b') + 128^2 dim
+        else
+            qt = pb.qterm[qi];
         // this lane's 16 bytes of a 64-byte step of its slot's byte query row
         const char* qb = reinterpret_cast<const char*>(pb.q8rows) + (int64_t)qi * dim_b + 16 * g;
         float wmin = VS_INF, tau = VS_INF;
@@ -173,7 +187,10 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_scan_nd_i8_kernel(const I
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     // the integer the fp32 scan computes exactly: ||q||^2 + ||b||^2 - 2 q.b  (the terms have 64 spare entries)
-                    d[j] = (float)(qt + pb.rterm[rbase + j] - 2 * acc[t][j]);
+                    if constexpr (IP)  // (|q'.b'| <= 2^25, |128 (sum q' + sum b')| <= 2^26, 128^2 dim <= 2^25; zero gives -0.0)
+                        d[j] = -(float)(qt + 128 * pb.rsum[rbase + j] + acc[t][j]);
+                    else
+                        d[j] = (float)(qt + pb.rterm[rbase + j] - 2 * acc[t][j]);
                     if (ragged && rbase + j > last_row) d[j] = VS_INF;
                 }
                 nd_topk_step<KCAP>(d, rbase, 0, wmin, tau, ld[0], li[0]);
@@ -191,8 +208,29 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_scan_nd_i8_kernel(const I
     }
 }
 
+// grid = ceil((rows + 64) / 256), 256 threads: one thread per entry
+__global__ __launch_bounds__(256) void ivf_nd_i8_rowsum_kernel(const int8_t* __restrict__ vecs_u8, const int dim_b, const int64_t rows,
+                                                               int32_t* __restrict__ rsum) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= rows + 64) return;
+    int t = 0;
+    if (row < rows) {
+        const i32x4* src = reinterpret_cast<const i32x4*>(vecs_u8 + row * dim_b);  // (dim_b is a multiple of 64)
+        for (int c = 0; c < dim_b / 16; ++c) {
+            const i32x4 v = src[c];
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) t += (int)(int8_t)((unsigned)v[w] >> (8 * b));
+        }
+    }
+    rsum[row] = t;
+}
+
 static bool ivf_nd_i8_params_ok(const IvfNdI8Params& pb) {
     const IvfNdParams& p = pb.s;
+    if (p.metric != 0 && p.metric != 1) return false;
+    if (p.metric == 1 && (!pb.rsum || !pb.qsum)) return false;
     return p.dim >= 1 && p.dim <= kNdMaxDim && pb.dim_b == nd_dim_b(p.dim) && p.group_q >= 1 && p.group_q <= kIvfNdGroupQ &&
            p.nprobe >= 1 && p.nprobe <= kIvfMaxProbe && p.nlist >= 1 && (p.kcap == 8 || p.kcap == 16) && pb.vecs_u8 && pb.rterm &&
            pb.q8rows && pb.qterm && pb.valid && pb.bmax >= 0 && pb.bmax < kNd8NormLimit;
@@ -206,10 +244,20 @@ hipError_t launch_ivf_nd_i8_prep(const IvfNdI8Params& pb, hipStream_t s) {
 
 hipError_t launch_ivf_nd_i8_scan(const IvfNdI8Params& pb, int grid, hipStream_t s) {
     if (!ivf_nd_i8_params_ok(pb) || grid < 1 || pb.s.k < 1 || pb.s.k > pb.s.kcap) return hipErrorInvalidValue;
-    if (pb.s.kcap == 8)
-        hipLaunchKernelGGL(ivf_scan_nd_i8_kernel<8>, dim3(grid), dim3(kScanThreads), 0, s, pb);
+    if (pb.s.kcap == 8 && !pb.s.metric)
+        hipLaunchKernelGGL((ivf_scan_nd_i8_kernel<8, false>), dim3(grid), dim3(kScanThreads), 0, s, pb);
+    else if (!pb.s.metric)
+        hipLaunchKernelGGL((ivf_scan_nd_i8_kernel<16, false>), dim3(grid), dim3(kScanThreads), 0, s, pb);
+    else if (pb.s.kcap == 8)
+        hipLaunchKernelGGL((ivf_scan_nd_i8_kernel<8, true>), dim3(grid), dim3(kScanThreads), 0, s, pb);
     else
-        hipLaunchKernelGGL(ivf_scan_nd_i8_kernel<16>, dim3(grid), dim3(kScanThreads), 0, s, pb);
+        hipLaunchKernelGGL((ivf_scan_nd_i8_kernel<16, true>), dim3(grid), dim3(kScanThreads), 0, s, pb);
+    return hipGetLastError();
+}
+
+hipError_t launch_ivf_nd_i8_rowsum(const int8_t* vecs_u8, int dim_b, int64_t rows, int32_t* rsum, hipStream_t s) {
+    if (!vecs_u8 || !rsum || dim_b < 64 || dim_b % 64 || rows < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ivf_nd_i8_rowsum_kernel, dim3((unsigned)((rows + 64 + 255) / 256)), dim3(256), 0, s, vecs_u8, dim_b, rows, rsum);
     return hipGetLastError();
 }
 

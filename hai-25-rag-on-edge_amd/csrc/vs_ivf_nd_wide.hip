@@ -1,4 +1,5 @@
-// vs_ivf_nd_wide.hip -- wide k (17 <= k <= 128) on a general IVF index, fp32 rows, squared L2 (gfx950).
+// vs_ivf_nd_wide.hip -- wide k (17 <= k <= 128) on a general IVF index, fp32 rows, squared L2 or inner product (gfx950;
+// DESIGN 4.6c).  Under inner product (IvfNdParams::metric, the IP instantiations) a distance below is the score -(q.v).
 //
 // A launch group first runs the list-major pipeline of vs_ivf_nd.hip at KCAP 16: part[(query * nprobe + rank) * 16] holds
 // every probed list's 16 best by (distance, row).  Then
@@ -24,6 +25,28 @@
 
 namespace vs {
 
+// The key of a candidate.  Squared L2 (IP false): tw_key / tw_dist as they are.  Inner product: tw_key folds -0.0 into +0
+// -- the rank the float comparisons of the other merges give it -- and tw_dist would hand +0.0 back, but a zero product
+// is -0.0 in every other path and in the oracle.  The IP key keeps the folded distance word, so -0.0 still ranks above
+// every negative score, below every positive one and ties with +0.0 by row, and stores (row << 1 | was -0.0) in the low
+// word (rows are below 2^31; they are unique per query, so the last bit never decides an order).
+template <bool IP>
+__device__ __forceinline__ bool nd_wide_key(float d, int32_t row, uint64_t& key) {
+    if (!tw_key(d, row, key)) return false;
+    if constexpr (IP)
+        key = (key & 0xffffffff00000000ull) | ((uint32_t)row << 1) | (__builtin_bit_cast(uint32_t, d) == 0x80000000u ? 1u : 0u);
+    return true;
+}
+template <bool IP>
+__device__ __forceinline__ int32_t nd_wide_row(uint64_t key) {
+    return IP ? (int32_t)((uint32_t)key >> 1) : (int32_t)(uint32_t)key;
+}
+template <bool IP>
+__device__ __forceinline__ float nd_wide_dist(uint64_t key) {
+    const float d = tw_dist(key);
+    return IP && (key & 1u) ? -0.0f : d;
+}
+
 constexpr int kNdWideThreads = 256;
 constexpr int kNdWideSelCap = 2048;  // keys the final sort holds (16 KB of LDS)
 constexpr int kNdWideTiles = 4;      // as ivf_scan_nd_kernel: 16-row tiles per wave block
@@ -32,6 +55,7 @@ static_assert(kNdWideBlockRows <= kScanPadRows, "row blocks are loaded unclamped
 static_assert(kIvfMaxProbe * 16 <= kIvfNdWideCand, "the partial lists of a query fit its candidate list");
 
 // grid = group_q, 256 threads
+template <bool IP>
 __global__ __launch_bounds__(kNdWideThreads) void ivf_nd_wide_bound_kernel(const IvfNdWideParams p) {
     __shared__ WideSelLds<kNdWideSelCap> sel;
     __shared__ int s_n;
@@ -44,7 +68,7 @@ __global__ __launch_bounds__(kNdWideThreads) void ivf_nd_wide_bound_kernel(const
     const int M = wide_select<kNdWideThreads>(sel, n, k, [&](auto&& f) {
         for (int e = tid; e < n; e += kNdWideThreads) {
             uint64_t key;
-            if (tw_key(p.r.part_d[base + e], p.r.part_i[base + e], key)) f(key);
+            if (nd_wide_key<IP>(p.r.part_d[base + e], p.r.part_i[base + e], key)) f(key);
         }
     });  // (ends with a barrier)
     const float tau = M >= k ? tw_dist(sel.keys[k - 1]) : VS_INF;
@@ -58,7 +82,7 @@ __global__ __launch_bounds__(kNdWideThreads) void ivf_nd_wide_bound_kernel(const
         for (int j = 0; j < 16; ++j) {
             const float d = p.r.part_d[o + j];
             uint64_t key;
-            if (d <= tau && tw_key(d, p.r.part_i[o + j], key)) cand[atomicAdd(&s_n, 1)] = key;  // (at most 16 nprobe entries)
+            if (d <= tau && nd_wide_key<IP>(d, p.r.part_i[o + j], key)) cand[atomicAdd(&s_n, 1)] = key;  // (at most 16 nprobe entries)
         }
     }
     __syncthreads();
@@ -68,6 +92,7 @@ __global__ __launch_bounds__(kNdWideThreads) void ivf_nd_wide_bound_kernel(const
     }
 }
 
+template <bool IP>
 __global__ __launch_bounds__(kScanThreads, 1) void ivf_scan_nd_cand_kernel(const IvfNdWideParams w) {
     constexpr int T = kNdWideTiles;
     const IvfNdParams& p = w.r;
@@ -92,7 +117,8 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_scan_nd_cand_kernel(const
         const bool live = r < n_slots;  // (a slot past the run's end repeats the first and appends nothing)
         const int sv = p.slots[slot0 + (live ? r : 0)];
         const int qi = sv >> 8;
-        const float qn = p.qnorm[qi];
+        float qn = 0.f;
+        if constexpr (!IP) qn = p.qnorm[qi];
         const float tau = w.tau[qi];
         // this lane's 16 bytes of a 64-byte segment of its slot's padded query row
         const char* qb = reinterpret_cast<const char*>(p.qrows + (int64_t)qi * dim_p + 4 * g);
@@ -149,9 +175,14 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_scan_nd_cand_kernel(const
                 const int64_t rbase = row0 + 16 * t + 4 * g;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float d = fmaf(-2.0f, acc[t][j], qn + p.vnorm[rbase + j]);  // (the norms have 64 spare entries)
+                    float d;
+                    if constexpr (IP)
+                        d = -acc[t][j];
+                    else
+                        d = fmaf(-2.0f, acc[t][j], qn + p.vnorm[rbase + j]);  // (the norms have 64 spare entries)
                     uint64_t key;
-                    if (live && rbase + j <= last_row && d <= tau && tw_key(d, (int32_t)(rbase + j), key)) {
+                    // (rbase + j <= last_row: a row past the list's end never competes -- under IP it would score -0.0)
+                    if (live && rbase + j <= last_row && d <= tau && nd_wide_key<IP>(d, (int32_t)(rbase + j), key)) {
                         const int pos = atomicAdd(w.cnt + qi, 1);
                         if (pos < kIvfNdWideCand) cand[pos] = key;
                     }
@@ -181,6 +212,7 @@ __device__ __forceinline__ float nd_dot_chain(const float* __restrict__ b, const
 }
 
 // grid = group_q, 256 threads.  The group's last kernel.
+template <bool IP>
 __global__ __launch_bounds__(kNdWideThreads) void ivf_nd_wide_rank_kernel(const IvfNdWideParams w) {
     __shared__ WideSelLds<kNdWideSelCap> sel;
     __shared__ int s_upper;
@@ -198,7 +230,8 @@ __global__ __launch_bounds__(kNdWideThreads) void ivf_nd_wide_rank_kernel(const 
     } else {
         const int32_t* const pr = p.probes + (int64_t)q * p.nprobe;
         const float* const qv = p.qrows + (int64_t)q * p.dim_p;
-        const float qn = p.qnorm[q];
+        float qn = 0.f;
+        if constexpr (!IP) qn = p.qnorm[q];
         const int C = p.dim_p / 16;
         if (tid == 0) s_upper = 0;
         __syncthreads();
@@ -212,11 +245,15 @@ __global__ __launch_bounds__(kNdWideThreads) void ivf_nd_wide_rank_kernel(const 
                 const int c = pr[pp];
                 if (c < 0 || c >= p.nlist) continue;
                 const int s0 = p.offsets[c], s1 = p.offsets[c + 1];
-                for (int row = s0 + tid; row < s1; row += kNdWideThreads) {
+                for (int row = s0 + tid; row < s1; row += kNdWideThreads) {  // (the list's own rows only: none past s1)
                     const float dot = nd_dot_chain(p.vecs + (int64_t)row * p.dim_p, qv, C);
-                    const float d = fmaf(-2.0f, dot, qn + p.vnorm[row]);
+                    float d;
+                    if constexpr (IP)
+                        d = -dot;
+                    else
+                        d = fmaf(-2.0f, dot, qn + p.vnorm[row]);
                     uint64_t key;
-                    if (tw_key(d, row, key)) f(key);
+                    if (nd_wide_key<IP>(d, row, key)) f(key);
                 }
             }
         });
@@ -226,8 +263,8 @@ __global__ __launch_bounds__(kNdWideThreads) void ivf_nd_wide_rank_kernel(const 
         float d = VS_INF;
         int32_t id = -1;
         if (t < n_out) {
-            d = tw_dist(sel.keys[t]);
-            const int32_t row = (int32_t)(uint32_t)sel.keys[t];
+            d = nd_wide_dist<IP>(sel.keys[t]);
+            const int32_t row = nd_wide_row<IP>(sel.keys[t]);
             id = w.id_map ? w.id_map[row] : row;
         }
         w.out_d[(int64_t)q * k + t] = d;
@@ -247,25 +284,34 @@ __global__ __launch_bounds__(kNdWideThreads) void ivf_nd_wide_rank_kernel(const 
 static bool nd_wide_ok(const IvfNdWideParams& p) {
     const IvfNdParams& r = p.r;
     return r.dim >= 1 && r.dim <= kNdMaxDim && r.dim_p == nd_dim_p(r.dim) && r.group_q >= 1 && r.group_q <= kIvfNdGroupQ && r.nprobe >= 1 &&
-           r.nprobe <= kIvfMaxProbe && r.nlist >= 1 && r.kcap == 16 && r.k > 16 && r.k <= kIvfNdWideKMax && p.tau && p.pair_mask &&
+           r.nprobe <= kIvfMaxProbe && r.nlist >= 1 && (r.metric == 0 || r.metric == 1) && r.kcap == 16 && r.k > 16 && r.k <= kIvfNdWideKMax && p.tau && p.pair_mask &&
            r.pair_mask == p.pair_mask && p.cnt && p.cand && p.out_d && p.out_i && p.stats;
 }
 
 hipError_t launch_ivf_nd_wide_bound(const IvfNdWideParams& p, hipStream_t s) {
     if (!nd_wide_ok(p)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ivf_nd_wide_bound_kernel, dim3(p.r.group_q), dim3(kNdWideThreads), 0, s, p);
+    if (p.r.metric)
+        hipLaunchKernelGGL(ivf_nd_wide_bound_kernel<true>, dim3(p.r.group_q), dim3(kNdWideThreads), 0, s, p);
+    else
+        hipLaunchKernelGGL(ivf_nd_wide_bound_kernel<false>, dim3(p.r.group_q), dim3(kNdWideThreads), 0, s, p);
     return hipGetLastError();
 }
 
 hipError_t launch_ivf_nd_wide_scan(const IvfNdWideParams& p, int grid, hipStream_t s) {
     if (!nd_wide_ok(p) || grid < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ivf_scan_nd_cand_kernel, dim3(grid), dim3(kScanThreads), 0, s, p);
+    if (p.r.metric)
+        hipLaunchKernelGGL(ivf_scan_nd_cand_kernel<true>, dim3(grid), dim3(kScanThreads), 0, s, p);
+    else
+        hipLaunchKernelGGL(ivf_scan_nd_cand_kernel<false>, dim3(grid), dim3(kScanThreads), 0, s, p);
     return hipGetLastError();
 }
 
 hipError_t launch_ivf_nd_wide_rank(const IvfNdWideParams& p, hipStream_t s) {
     if (!nd_wide_ok(p)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ivf_nd_wide_rank_kernel, dim3(p.r.group_q), dim3(kNdWideThreads), 0, s, p);
+    if (p.r.metric)
+        hipLaunchKernelGGL(ivf_nd_wide_rank_kernel<true>, dim3(p.r.group_q), dim3(kNdWideThreads), 0, s, p);
+    else
+        hipLaunchKernelGGL(ivf_nd_wide_rank_kernel<false>, dim3(p.r.group_q), dim3(kNdWideThreads), 0, s, p);
     return hipGetLastError();
 }
 

@@ -545,6 +545,7 @@ hipError_t launch_ivf_scan(const IvfScanParams& p, hipStream_t s);
 // launch_ivf_nd_scan scores every item's list against its slots' queries (scan_nd_kernel's accumulation chain: a distance
 // is the number the brute-force general scan returns for that row and query) and writes the item's sorted top-kcap by
 // (distance, row) per slot to part[(query * nprobe + rank) * kcap] -- the layout ivf_fallback_batch_dev ranks.
+// IvfNdParams::metric == 1 (inner product): the "distance" everywhere below is the score -(q.v), the same chain negated.
 constexpr int kIvfNdGroupQ = 1024;     // 32 batches of 32 queries
 constexpr int kIvfNdSlotBlock = 16;    // slots per item: one MFMA column block
 constexpr long long ivf_nd_items_cap(int nlist, int nprobe) {  // every probed list ends in one ragged item at most
@@ -576,6 +577,10 @@ struct IvfNdParams {
     // the rescan plan of the wide-k pipeline (vs_ivf_nd_wide.hip): a pair gets a slot only when pair_mask[pair] != 0.
     // Null: every pair, as everywhere else.
     const int32_t* pair_mask; // [group_q * nprobe]
+    // 0: squared L2.  1: inner product -- a row's score is -(q.v), the accumulation chain negated, smallest first; vnorm
+    // and qnorm are not read, and a row past its list's end is left out by its row number in every epilogue (a spare
+    // row scores -0.0 and would beat every row with a negative product).
+    int metric;
 };
 hipError_t launch_ivf_nd_plan(const IvfNdParams& p, hipStream_t s);
 // a group's second plan (p.route or p.pair_mask set): the pair counts, prefix and fill of launch_ivf_nd_plan on p's own
@@ -602,9 +607,16 @@ struct IvfNdI8Params {
     int8_t* q8rows;           // scratch [kIvfNdGroupQ][dim_b]
     int32_t* qterm;           // scratch [kIvfNdGroupQ]
     int32_t* valid;           // scratch [kIvfNdGroupQ]
+    // inner product (s.metric == 1) only, null otherwise: q.b = q'.b' + 128 (qsum + rsum) + 128^2 dim in int32, exact
+    // and equal to the fp32 chain for a valid query (every partial sum of q.b is at most (||q||^2 + ||b||^2) / 2 <=
+    // 2^23); the scan writes -(float)(q.b)
+    const int32_t* rsum;      // [n_rows + 64] sum (b - 128) (launch_ivf_nd_i8_rowsum)
+    int32_t* qsum;            // scratch [kIvfNdGroupQ] sum (q - 128), written by launch_ivf_nd_i8_prep
 };
 hipError_t launch_ivf_nd_i8_prep(const IvfNdI8Params& p, hipStream_t s);
 hipError_t launch_ivf_nd_i8_scan(const IvfNdI8Params& p, int grid, hipStream_t s);
+// rsum[row] = the sum of the row's dim_b stored bytes (the padding is zero) for row < rows, 0 for the 64 spare entries
+hipError_t launch_ivf_nd_i8_rowsum(const int8_t* vecs_u8, int dim_b, int64_t rows, int32_t* rsum, hipStream_t s);
 
 // ---- wide k (17 <= k <= kIvfNdWideKMax) on a general IVF index (vs_ivf_nd_wide.hip).  The group's first
 // plan and scan run as above at kcap 16 on the fp32 rows with every pair; part[(query * nprobe + rank) * 16] then holds

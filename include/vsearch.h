@@ -313,6 +313,8 @@ VS_API int vs_ivf_load(const char* index_dir, int device, int rank, int world, v
  *   VS_ERR_UNSUPPORTED, with the dimension in the message: 17 <= k <= 128, vs_set_precision 2,
  *     vs_ivf_set_metric(VS_METRIC_IP), vs_ivf_widek_stats, every sharded and virtual-shard call.
  *   17 <= k <= 128 comes through vs_ivf_search_topk / vs_ivf_search_topk_dev_multi below.
+ *   Inner product comes through vs_ivf_search_metric / vs_ivf_search_metric_dev_multi below, which
+ *     take the metric per call; the index's own setting stays squared L2.
  * vs_ivf_build and vs_ivf_build_index stay 128-d only; vs_ivf_build_nd and vs_ivf_build_index_nd
  * build at every dimension this creator takes.  A general IVF index that also keeps its rows as
  * bytes and scans them with int8 MFMA comes from vs_ivf_create_nd_u8 below, not from this creator. */
@@ -487,6 +489,39 @@ VS_API int vs_ivf_search_topk(vs_index* h, const float* queries_host, int64_t nq
                               int32_t* ids, float* dists, int64_t* total_candidates, vs_timing* timing);
 VS_API int vs_ivf_search_topk_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k, int nprobe,
                                         int32_t* ids_dev, float* dists_dev, void* stream);
+
+/* IVF search under a metric given per call, for 1 <= k <= 128 on EVERY IVF index.  Signatures, output layouts,
+ * *total_candidates (the rows of the probed lists: it does not depend on the metric) and the timing fields are those of
+ * vs_ivf_search_topk / vs_ivf_search_topk_dev_multi, with `metric` added.
+ * Checks, in this order: null pointers -> VS_ERR_INVALID; a brute-force index -> VS_ERR_UNSUPPORTED; a metric other than
+ * VS_METRIC_L2 / VS_METRIC_IP -> VS_ERR_INVALID; k < 1 -> VS_ERR_INVALID; k > 128 -> VS_ERR_UNSUPPORTED; then those of
+ * vs_ivf_search_topk*.
+ * The call's metric decides.  What vs_ivf_set_metric left on the index does not enter the result and is the same after
+ * the call as before it, also when the call fails (the call is not reentrant on one index, like every other call).
+ *   VS_METRIC_L2 on any IVF index: the call IS vs_ivf_search_topk / vs_ivf_search_topk_dev_multi on an index whose
+ *     metric is L2 (same launches, same results, same refusals).
+ *   VS_METRIC_IP on the specialised 128-d index: exactly what vs_ivf_set_metric(h, VS_METRIC_IP) followed by
+ *     vs_ivf_search_topk* returns.
+ *   VS_METRIC_IP on a general IVF index (dim != 128; vs_ivf_create, vs_ivf_load, vs_ivf_build_index_nd,
+ *     vs_ivf_create_nd_u8, and the VSEARCH_IVF_ND_FORCE=1 form): the reference's own IVF ranking (IVFIndex.cpp:449-496,
+ *     :697-723, :738-771) at any dimension, in launch groups of up to 32 batches on the caller's stream, without a host
+ *     synchronisation.  The score of list c is -(q.c), the number the brute-force general scan returns
+ *     under VS_METRIC_IP for the centroid as a row; the nprobe smallest are taken by (score, list id).  A row scores
+ *     s = -(q.v), bit-identical to what the device calls of vs_bf_create_nd(..., VS_METRIC_IP, ...) return for that row
+ *     and query.  The result is the k best rows of the probed lists by (s, position in vectors_reordered), ids through
+ *     reorder_to_original; slots past the candidates are (-1, +inf).  The device call returns s ascending; the host call
+ *     returns q.v = -s descending and +inf in empty slots, as the 128-d index does.  A product that is exactly zero
+ *     gives s = -0.0 (sign bit set) on the device.
+ *     On a vs_ivf_create_nd_u8 index and k <= 16, the pairs of the queries that qualify (the L2 rule, unchanged: every
+ *     value an integer in [0, 255] and ||q||^2 + max ||b||^2 <= 2^24) are scanned on the byte rows with int8 MFMA and
+ *     every other pair on the fp32 rows, with the same bits either way; vs_set_precision 0 and 2 do so, 1 puts every pair
+ *     on the fp32 rows; 17 <= k <= 128 reads the fp32 rows.  The first inner-product call on such an index builds one
+ *     int32 per row on the device (the sum of the row's stored bytes).  vs_ivf_nd_u8_stats and vs_ivf_nd_widek_stats
+ *     count these calls like the L2 ones. */
+VS_API int vs_ivf_search_metric(vs_index* h, const float* queries_host, int64_t nq, int k, int nprobe, int metric,
+                                int32_t* ids, float* dists, int64_t* total_candidates, vs_timing* timing);
+VS_API int vs_ivf_search_metric_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k, int nprobe,
+                                          int metric, int32_t* ids_dev, float* dists_dev, void* stream);
 
 /* ---------------------------------------------------------------- multi-GPU */
 /* Which rank owns which inverted list in a cluster-sharded index (host only, no GPU needed):

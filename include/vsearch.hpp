@@ -209,7 +209,7 @@ public:
     // backend here is always the HIP library this header links against.
     // The directory states the dimension (1 <= dim <= 2048, getDim()): 128-d indexes take the specialised pipeline,
     // any other a general IVF index (fp32 rows, squared L2, one GPU; k <= 16 through searchBatch, k <= 128 through
-    // searchBatchTopk; vsearch.h at vs_ivf_create).
+    // searchBatchTopk, inner product through searchBatchMetric; vsearch.h at vs_ivf_create).
     explicit IVFIndex(const std::string& indexDir, const std::string& backendPath = "libvsearch_hip.so",
                       int device = 0, int rank = 0, int world = 1) {
         (void)backendPath;
@@ -252,9 +252,20 @@ public:
                            SearchTiming& timing) {
         return searchBatchWith(vs_ivf_search_topk, queries, batchSize, k, nprobe, allIndices, allScores, timing);
     }
+    // the same under a metric given per call (vs_ivf_search_metric; VS_METRIC_L2 or VS_METRIC_IP) on every IVF index:
+    // inner product returns the scores q.v, descending, as the reference's IVFIndex does.  The index's own metric is
+    // neither used nor changed.
+    size_t searchBatchMetric(const std::vector<float>& queries, int batchSize, int k, int nprobe, int metric,
+                             std::vector<std::vector<int>>& allIndices, std::vector<std::vector<float>>& allScores,
+                             SearchTiming& timing) {
+        auto call = [metric](vs_index* h, const float* q, int64_t nq, int k_, int np, int32_t* ids, float* dists, int64_t* total,
+                             vs_timing* tm) { return vs_ivf_search_metric(h, q, nq, k_, np, metric, ids, dists, total, tm); };
+        return searchBatchWith(call, queries, batchSize, k, nprobe, allIndices, allScores, timing);
+    }
 
   private:
-    using HostSearch = int (*)(vs_index*, const float*, int64_t, int, int, int32_t*, float*, int64_t*, vs_timing*);
+    // call: int(vs_index*, const float*, int64_t, int, int, int32_t*, float*, int64_t*, vs_timing*)
+    template <class HostSearch>
     size_t searchBatchWith(HostSearch call, const std::vector<float>& queries, int batchSize, int k, int nprobe,
                            std::vector<std::vector<int>>& allIndices, std::vector<std::vector<float>>& allScores,
                            SearchTiming& timing) {

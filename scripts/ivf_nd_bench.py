@@ -1,7 +1,7 @@
 """List-major IVF at a general dimension against exact brute force on the same rows: device time per 1024 queries.
 
     python scripts/ivf_nd_bench.py [--dims 96,384,768] [--rows 1000000] [--nlist 1024] [--nprobe 8,32] [--groups 4] [--reps 5]
-                                   [--build ITERS] [--u8] [--widek K]
+                                   [--build ITERS] [--u8] [--widek K] [--metric ip [--k 10,100]]
 
 Data: synth_sift rows (integer valued) at every dimension, nlist sampled rows as centroids, every row assigned to its
 nearest centroid through the library's own brute force (a timing index, not a trained one).  Queries: `groups` groups of
@@ -31,6 +31,15 @@ wide-k brute force on the same rows (bf_kK: BruteForceIndex.search_topk_dev_mult
 against that exact result, the three counters of vs_ivf_nd_widek_stats for one pass over the queries, and the share of
 (query, probe) pairs the rescan takes -- recomputed on the host in float64 for the first 64 queries (a pair is rescanned
 when the 16th best distance of its list is at or under the K-th smallest of the query's per-list top-16s).
+
+--metric ip times inner-product search through the per-call metric (IVFIndex.search_metric_dev_multi) against squared L2
+through the same call on the same index in the same process, the L2 leg twice (paths l2_a and l2_b: their spread is the
+noise an inner-product difference has to exceed), for every k of --k and every nprobe; with --u8 also the byte index
+under inner product (ip_u8: the pairs on the byte rows for k <= 16) beside the fp32 index (ip).  Per path: us per 1024
+queries between two device events and the list-scan launches alone (vs_prof_read(.., 1)).  recall@10 is inner-product IVF
+against exact inner-product brute force on the same rows (BruteForceIndex(metric=METRIC_IP)).  A "probe_spread" line per
+metric and nprobe says how many distinct lists a group of 1024 queries probes and how many rows a query's lists hold
+(host, float64): on rows that are not normalised the inner-product probes of all queries fall on the same few lists.
 """
 import argparse
 import json
@@ -66,6 +75,9 @@ def one(a, dim):
     vr, off, r2o = pkg.ivf_layout_from_assignment(base, assign, a.nlist)
     if a.widek:
         search_widek(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st)
+        return
+    if a.metric == "ip":
+        search_ip(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st)
         return
     search(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st, assign_pass_ms)
 
@@ -347,6 +359,119 @@ def search_widek(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st):
             print(json.dumps(rec), flush=True)
 
 
+def search_ip(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st):
+    import contextlib
+    import torch
+    sizes = np.diff(off)
+    print(json.dumps({"what": "index", "dim": dim, "rows": a.rows, "nlist": a.nlist, "list_min": int(sizes.min()),
+                      "list_mean": float(sizes.mean()), "list_max": int(sizes.max())}), flush=True)
+    qd = torch.from_numpy(q).to(dev)
+    nq, nbg = a.groups * GROUP_Q, GROUP_Q // B
+    nprobes = [int(x) for x in a.nprobe.split(",")]
+    ks = [int(x) for x in a.k.split(",")]
+    # how the probes spread, recomputed on the host in float64: the list-major scan reads a probed list once per 16 of the
+    # group's queries that probe it, so the fewer distinct lists a group of 1024 queries probes, the more of its reads hit
+    c64, q64 = cents.astype(np.float64), q.astype(np.float64)
+    dots = q64 @ c64.T
+    for name, sc in (("l2", (c64 * c64).sum(1)[None, :] - 2 * dots), ("ip", -dots)):
+        for p in nprobes:
+            pr = np.argpartition(sc, p - 1, axis=1)[:, :p]
+            distinct = [len(np.unique(pr[g * GROUP_Q:(g + 1) * GROUP_Q])) for g in range(a.groups)]
+            print(json.dumps({"what": "probe_spread", "metric": name, "dim": dim, "nprobe": p, "distinct_lists_per_group": distinct,
+                              "rows_per_query": round(float(sizes[pr].sum()) / nq, 1)}), flush=True)
+    del c64, q64, dots
+    with contextlib.ExitStack() as stack:
+        bf = stack.enter_context(pkg.BruteForceIndex(base, metric=pkg.METRIC_IP))
+        bf.set_precision(1)
+        bi = torch.empty((nq, K + 1), dtype=torch.int32, device=dev)
+        bd = torch.empty((nq, K + 1), dtype=torch.float32, device=dev)
+        bfl = torch.empty((nq,), dtype=torch.int32, device=dev)
+        for g in range(a.groups):
+            o = g * GROUP_Q
+            bf.search_dev_multi(qd[o].data_ptr(), nbg, B, K, bi[o].data_ptr(), bd[o].data_ptr(), bfl[o].data_ptr(), st)
+        torch.cuda.synchronize()
+        exact = bi[:, :K].cpu().numpy()
+        bf.close()
+        del bi, bd, bfl
+        ivf = stack.enter_context(pkg.IVFIndex(vectors_reordered=vr, centroids=cents, cluster_offsets=off, reorder_to_original=r2o))
+        ivf8 = None
+        if a.u8:
+            rows_u8 = vr.astype(np.uint8)
+            assert np.array_equal(rows_u8.astype(np.float32), vr), "--u8 needs byte-valued rows"
+            ivf8 = stack.enter_context(pkg.IVFIndex.from_u8(rows_u8, cents, off, r2o))
+            del rows_u8
+        del vr
+        for k in ks:
+            oi = torch.empty((nq, k), dtype=torch.int32, device=dev)
+            od = torch.empty((nq, k), dtype=torch.float32, device=dev)
+
+            def run(index, metric, nprobe):
+                for g in range(a.groups):
+                    o = g * GROUP_Q
+                    index.search_metric_dev_multi(qd[o].data_ptr(), nbg, B, k, nprobe, metric, oi[o].data_ptr(), od[o].data_ptr(), st)
+
+            def timed(*args):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                run(*args)
+                e1.record()
+                e1.synchronize()
+                return e0.elapsed_time(e1) * 1e3 / a.groups  # us per 1024 queries
+
+            for p in nprobes:
+                paths = [("l2_a", ivf, pkg.METRIC_L2), ("ip", ivf, pkg.METRIC_IP), ("l2_b", ivf, pkg.METRIC_L2)]
+                if ivf8 is not None:
+                    paths.append(("ip_u8", ivf8, pkg.METRIC_IP))
+                recall, results, pairs = {}, {}, None
+                for name, index, metric in paths:  # warm-up of every path; recall of the inner-product ones
+                    run(index, metric, p)
+                    if name == "ip_u8":
+                        index.nd_u8_stats(reset=True)
+                    run(index, metric, p)
+                    torch.cuda.synchronize()
+                    if name == "ip_u8":
+                        pairs = index.nd_u8_stats()
+                    if metric == pkg.METRIC_IP:
+                        got = oi.cpu().numpy()
+                        recall[name] = float(np.mean([len(set(got[i, :K]) & set(exact[i])) / K for i in range(nq)]))
+                        results[name] = (got, od.cpu().numpy().view(np.int32).copy())
+                if ivf8 is not None:  # the byte index returns the fp32 index's ids and score bits
+                    x, y = results["ip"], results["ip_u8"]
+                    assert np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1]), f"byte index differs at k {k}, nprobe {p}"
+                us = {name: [] for name, _, _ in paths}
+                scan = {name: [] for name, _, _ in paths}
+                for _ in range(a.reps):
+                    for name, index, metric in paths:
+                        us[name].append(timed(index, metric, p))
+                for _ in range(a.reps):  # the list-scan launches alone
+                    for name, index, metric in paths:
+                        index.prof_enable(True)
+                        run(index, metric, p)
+                        torch.cuda.synchronize()
+                        ms, n = index.prof_read(1)
+                        index.prof_enable(False)
+                        scan[name].append(ms / max(n, 1) * 1e3)
+                med = lambda v: sorted(v)[len(v) // 2]
+                l2 = 0.5 * (med(us["l2_a"]) + med(us["l2_b"]))
+                l2s = 0.5 * (med(scan["l2_a"]) + med(scan["l2_b"]))
+                for name, _, metric in paths:
+                    rec = {"what": "ip_vs_l2", "path": name, "dim": dim, "rows": a.rows, "nlist": a.nlist, "k": k, "nprobe": p,
+                           "us_per_1024": [round(u, 1) for u in us[name]], "median_us": round(med(us[name]), 1),
+                           "scan_us_per_group": [round(u, 1) for u in scan[name]], "scan_median_us": round(med(scan[name]), 1)}
+                    if metric == pkg.METRIC_IP:
+                        rec["recall_at_10"] = round(recall[name], 4)
+                        rec["ratio_to_l2"] = round(med(us[name]) / l2, 3)
+                        rec["scan_ratio_to_l2"] = round(med(scan[name]) / l2s, 3)
+                    if name == "ip_u8":
+                        rec["pairs_on_bytes"], rec["pairs_on_fp32"] = pairs
+                        rec["scan_ratio_to_ip_fp32"] = round(med(scan[name]) / med(scan["ip"]), 3)
+                    if name == "l2_b":
+                        rec["l2_spread"] = round(abs(med(us["l2_a"]) - med(us["l2_b"])) / l2, 4)
+                        rec["l2_scan_spread"] = round(abs(med(scan["l2_a"]) - med(scan["l2_b"])) / l2s, 4)
+                    print(json.dumps(rec), flush=True)
+            del oi, od
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dims", default="96,384,768")
@@ -358,6 +483,8 @@ def main():
     ap.add_argument("--build", type=int, default=0, metavar="ITERS", help="train the index with the library's builder")
     ap.add_argument("--u8", action="store_true", help="rows as uint8: the byte index beside the vs_ivf_create index and brute force")
     ap.add_argument("--widek", type=int, default=0, metavar="K", help="time the wide-k call (17 <= K <= 128) against k = 10 and exact wide-k brute force")
+    ap.add_argument("--metric", default="l2", choices=["l2", "ip"], help="ip: inner product against L2 through the per-call metric")
+    ap.add_argument("--k", default="10,100", help="the k values of the --metric ip leg")
     ap.add_argument("--one", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.one:
@@ -365,6 +492,7 @@ def main():
         return
     cmd = [sys.executable, os.path.abspath(__file__), "--rows", str(a.rows), "--nlist", str(a.nlist), "--nprobe", a.nprobe,
            "--groups", str(a.groups), "--reps", str(a.reps), "--build", str(a.build)] + (["--u8"] if a.u8 else []) + ["--widek", str(a.widek)]
+    cmd += ["--metric", a.metric, "--k", a.k]
     for dim in [int(x) for x in a.dims.split(",")]:
         r = subprocess.run(cmd + ["--one", str(dim)], timeout=900)
         if r.returncode != 0:  # a failed or faulted step ends the run: nothing more is started on the GPU
