@@ -649,6 +649,14 @@ int g_f32_filter = [] {
 }();
 bool f32_filter_enabled() { return g_f32_filter != 0; }
 
+// comparison toggle (VSEARCH_F32F_WAVES=8 or 4): scan_f32f_kernel runs as one 8-wave workgroup per CU, or as two 4-wave
+// workgroups per CU, at every launch size (default unset: the measured choice per launch size, launch_scan_f32_stream)
+int g_f32f_waves = [] {
+    const char* e = getenv("VSEARCH_F32F_WAVES");
+    const int v = e ? atoi(e) : 0;
+    return v == 4 || v == 8 ? v : 0;
+}();
+
 // tuning knob (VSEARCH_STREAM=0): seeded launches use the per-batch scan kernels (lane lists + workgroup merge) instead of
 // the streaming scans
 int g_stream = [] {
@@ -930,27 +938,23 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
                 sp.dbg = g_dbg ? g_dbg + 12288 * 16 : nullptr;  // (rows of its own: the kernels around it stamp rows [0, 256))
 #endif
                 sp.cnorm = h->filter_cnorm;
+                sp.f32f_waves = g_f32f_waves;
                 sp.sink.stats = h->filter_stats;
                 ++h->filter_launches;
             }
             HIPCHK(vs::launch_scan_f32_stream(sp, sgrid, s));
             prof_end(h, 0, s);
         }
-        // every query's candidate list (unsorted, a few hundred entries) -> k1 best by (dist, id), tie flags
-        vs::MergeParams mf = m;
-        mf.part_d = L.wide8.wcand_d;
-        mf.part_i = L.wide8.wcand_i;
-        mf.G = kWideSub;
-        mf.kin = kWideCap;
-        mf.flat_len = L.wide8.wcnt + 64;
-        mf.run_if = overflow;
-        mf.run_mode = 2;
-        HIPCHK(vs::launch_merge_layout(mf, kWideCap, (int64_t)kWideSub * kWideCap, s));
+        // every query's candidate list (unsorted, a few hundred entries) -> k1 best by (dist, id), tie flags: the merge
+        // launch at the end, which ranks the lane lists of the fallback instead where the overflow word is raised
+        m.G = kWideSub;
+        m.kin = kWideCap;
+        m.flat_len = L.wide8.wcnt + 64;
+        m.run_if = overflow;
+        m.run_mode = 3;
         // Fallback, enqueued behind and idle unless a candidate buffer overflowed (thousands of rows under one query's
         // bound: masses of duplicates): the per-batch scan with lane lists, which copes with any data.
         p.run_if = overflow;
-        m.run_if = overflow;
-        m.run_mode = 1;
     }
     p.row_begin = 0;
     p.row_end = h->n_rows;
@@ -972,6 +976,18 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     HIPCHK(scan_any(h, p, grid, kcap, nqh, vs::kModeTopK, s));
     if (!stream) prof_end(h, 0, s);
     // one merge launch ranks every (batch, query): lists are [batch*32 + q][workgroup][kcap]
+    if (stream) {  // ... or, unless the streaming scan overflowed, its candidate lists [batch*32 + q][kWideSub][kWideCap]
+        m.part_d = L.wide8.wcand_d;
+        m.part_i = L.wide8.wcand_i;
+        m.alt_part_d = L.part_d;
+        m.alt_part_i = L.part_i;
+        m.alt_G = grid;
+        m.alt_kin = kcap;
+        m.alt_stride_g = kcap;
+        m.alt_stride_q = (int64_t)vs::kSlotStride * kcap;
+        HIPCHK(vs::launch_merge_layout(m, kWideCap, (int64_t)kWideSub * kWideCap, s));
+        return VS_OK;
+    }
     m.part_d = L.part_d;
     m.part_i = L.part_i;
     m.G = grid;

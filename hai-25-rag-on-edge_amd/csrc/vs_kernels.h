@@ -210,7 +210,8 @@ struct CandSink {
     int4* wbuf;              // [grid * 8][wcap] x (query = batch * 32 + q, dist bits, id, 0)
     int wcap;
     int32_t* overflow;       // [1] (pre-set to 0): a wave buffer or a query list overflowed -> the launch's fallback kernels
-                             //     (the per-batch scan + its merge, enqueued behind with run_if = overflow) produce the result
+                             //     (brute force: the per-batch scan enqueued behind with run_if = overflow, whose lists the merge
+                             //     launch then ranks, MergeParams::run_mode 3) produce the result
     // per-query lists, split into nsub sub-lists (wave buffer w appends to sub-list w % nsub) so that the appending
     // atomics of one query spread over nsub counters
     int32_t* cnt;            // [n_batches][32][nsub] entries per sub-list (pre-set to 0)
@@ -267,8 +268,9 @@ struct StreamParams {
     const uint16_t* qbf;
     const float* qbound;
     const uint16_t* img;     // [n_rows + 64][128] bf16
-    int32_t* dbg;            // diagnostic builds (-DVS_STAMPS) only: scan_f32f_kernel's step split [grid][8 waves][16] (rows 12288.. of the debug buffer)
+    int32_t* dbg;            // diagnostic builds (-DVS_STAMPS) only: scan_f32f_kernel's step split [sweeper][8 waves][16], under either organisation (rows 12288.. of the debug buffer)
     float cnorm;             // filter_cnorm of the shard's largest stored norm (the L2 test, filter_th2)
+    int f32f_waves;          // scan_f32f_kernel's waves per workgroup: 8, 4 (two workgroups per CU), 0 = the measured choice per launch size
 };
 hipError_t launch_scan_f32_stream(const StreamParams& p, int grid, hipStream_t s);
 
@@ -314,7 +316,12 @@ struct MergeParams {
     const int32_t* shard_flags;  // optional (cross-GPU merge): shard g's own flag of output query q at g * shard_flags_stride + q;
     int64_t shard_flags_stride;  //   a shard that skipped the query's batch (flag 2) makes the merged flag 2: its rows are missing
     const int32_t* run_if;   // optional [1] with run_mode: 1 = run only if *run_if != 0, 2 = only if *run_if == 0 (the other
-    int run_mode;            //   launch of the pair writes the outputs)
+    int run_mode;            //   launch of the pair writes the outputs); 3 (launch_merge_layout, compacting merge only) = one launch
+                             //   for both: *run_if == 0 ranks the lists above, *run_if != 0 the alternative lists below
+    const float* alt_part_d;     // run_mode 3: sorted lists, entry (g, q, j) at g * alt_stride_g + q * alt_stride_q + j, g < alt_G,
+    const int32_t* alt_part_i;   //   j < alt_kin (no flat_len); everything else -- outputs, grouping, invalid, flags -- is shared
+    int alt_G, alt_kin;
+    int64_t alt_stride_g, alt_stride_q;
     const int32_t* flat_len; // optional [queries][G]: list (q, g) holds flat_len[q * G + g] <= kin UNSORTED candidates
     int flat_len_sub_stride; // != 0: the lengths are list major instead, flat_len[g * flat_len_sub_stride + q]
     int32_t* dbg;            // diagnostic builds (-DVS_STAMPS) only

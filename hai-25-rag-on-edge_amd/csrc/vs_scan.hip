@@ -4,7 +4,7 @@
 //                          v_mfma_f32_16x16x4_f32 with the L2 epilogue (cpu_baseline.cpp:229-242), NB batches per pass
 //                          over the rows, candidates under seeded bounds to per-wave buffers; scan_i8w_kernel: the same
 //                          on exact u8 rows (v_mfma_i32_16x16x64_i8), four batches per pass.
-//   scan_f32f_kernel<CBW, D, IP> : the same fp32 scan with the bulk test on v_mfma_f32_16x16x32_bf16 under a rigorous error
+//   scan_f32f_kernel<CBW, D, IP, NW> : the same fp32 scan with the bulk test on v_mfma_f32_16x16x32_bf16 under a rigorous error
 //                          bound, one sweep over the index's bf16 row image for all batches of a launch through a ring
 //                          shared by the workgroup, survivors recomputed with scan_f32s_kernel's exact fp32 chain (default).
 //   scan_kernel          : per-batch scan with the top-k (cpu_baseline.cpp:127-153) fused in (short calls, fallback);
@@ -1202,6 +1202,11 @@ __global__ __launch_bounds__(kScanThreads, NB == 1 ? 2 : 1) void scan_f32s_kerne
 // unit (16 KB of rows + its 64 norms) is staged once per workgroup, wave w moving rows 4 w .. 4 w + 3 of each half.  One
 // raw barrier per unit publishes the slot (the handshake is described at the loop below).  At CBW = 8 (17..32 batches)
 // the bf16 B operands are 128 registers, at two waves per SIMD.
+//
+// NW = 4 splits that workgroup into two of 4 waves (waves 0..3 and 4..7 with their column blocks, candidate buffers and
+// list hashes), each sweeping the same units through a ring of its own: two workgroups per CU, whose waves -- one of
+// each per SIMD -- never wait for each other.  A wave then moves rows 8 w .. 8 w + 7 of each half, and every unit is
+// fetched twice.  Same MFMA chains on the same operands: the candidates are the same entries in the same buffers.
 // ------------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -1282,50 +1287,67 @@ __device__ __forceinline__ float max4_finite(const f32x4 v, const float inf) {
     return __builtin_fmaxf(__builtin_fmaxf(__builtin_amdgcn_fmed3f(v[0], v[1], inf), v[2]), v[3]);
 }
 
-// CBW = column blocks per wave (1, 2, 4 or 8: up to 4, 8, 16 or 32 batches), D = unit slots of the shared ring, IP = the
+// CBW = column blocks per (virtual) wave (1, 2, 4 or 8: up to 4, 8, 16 or 32 batches), D = unit slots of the shared ring, IP = the
 // metric (the hot test differs: one kernel per metric keeps the loop free of branches on it).
-template <int CBW, int D, bool IP>
-__global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const StreamParams p) {
+// NW = waves per workgroup: 8 (one workgroup per CU) or 4 (two per CU, each a half of the 8-wave organisation: below).
+template <int CBW, int D, bool IP, int NW>
+__global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_kernel(const StreamParams p) {
     constexpr int TR = kTileRows;
-    constexpr int kUnitVmem = 3;  // vector-memory instructions per wave and unit: two row pieces + the norm piece
-    static_assert(kUnitRowBytes == 2 * kScanWaves * 1024, "a unit is two 1 KB row pieces per wave");
-    static_assert(D >= 3 && D * kUnitBytes <= 160 * 1024, "the ring: one slot being read, one being filled, >= 1 in flight");
+    static_assert(NW == 8 || NW == 4, "one 8-wave workgroup per CU, or two 4-wave halves");
+    constexpr int kPieces = kScanWaves / NW;   // 1 KB row pieces per wave and 32-row half of a unit
+    constexpr int kUnitVmem = 2 * kPieces + 1;  // vector-memory instructions per wave and unit: the row pieces + the norm piece
+    static_assert(kUnitRowBytes == 2 * kPieces * NW * 1024, "a unit is 2 kPieces 1 KB row pieces per wave");
+    static_assert(D >= 3 && (kScanWaves / NW) * D * kUnitBytes <= 160 * 1024, "the ring: one slot being read, one being filled, >= 1 in flight");
     static_assert((D - 2) * kUnitVmem <= 63, "vmcnt is a 6-bit count");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, g = lane >> 4;
     const int units_total = (int)((p.n_rows + kUnitRows - 1) / kUnitRows);
-    const int G = (int)gridDim.x;
-    const int T = (units_total - (int)blockIdx.x + G - 1) / G;  // units of this workgroup (grid <= units_total: T >= 1)
-    const int n_cb = 2 * p.n_batches;                           // column blocks of the launch (<= 8 CBW)
+    // NW = 4: workgroup x + G z (z = 0, 1) is half z of what workgroup x of the G-workgroup 8-wave grid is -- the same
+    // units x + n G, its wave w standing for wave vw = w + 4 z of that workgroup: the column blocks, the candidate buffer
+    // and the list hash of wave vw.  The two halves share nothing and never wait for each other.
+    const int G = (int)gridDim.x / (kScanWaves / NW);
+    const int z = NW == 8 ? 0 : ((int)blockIdx.x >= G ? 1 : 0);
+    const int bx = (int)blockIdx.x - z * G;
+    const int vw = wave + NW * z;
+    const int T = (units_total - bx + G - 1) / G;  // units of this workgroup (G <= units_total: T >= 1)
+    const int n_cb = 2 * p.n_batches;              // column blocks of the launch (<= 8 CBW)
+    if (NW * z >= n_cb) return;  // (workgroup-uniform, NW = 4 only) a half none of whose waves has a column block
 
     // LDS-DMA written as instructions (see scan_f32s_kernel): "scalar unit base + this lane's 32-bit offset".  Wave w
-    // moves rows 4 w .. 4 w + 3 of each 32-row half of a unit: lane l lands at row b = 4 w + (l >> 4) (+ 32), stored
-    // chunk l & 15 <- source chunk (l & 15) ^ (b & 15); the second half is the same lane offsets 8 KB further on both
-    // sides.  Every wave also moves the unit's 64 norms (lane l <- norm of row l, one 256-byte piece), so that all waves
-    // issue the same kUnitVmem instructions per unit and one constant vmcnt serves them all; the eight copies write the
-    // same bytes.  M0 is written in the statement that reads it, and restored there: the compiler neither knows nor
-    // preserves it around an asm statement.
-    const int row_in = 4 * wave + (lane >> 4);
-    const unsigned voff = (unsigned)(row_in * 256 + 16 * ((lane & 15) ^ (row_in & 15)));
+    // moves rows 4 kPieces w .. 4 kPieces (w + 1) - 1 of each 32-row half of a unit, four rows per piece: lane l of piece
+    // j lands at row b = 4 (kPieces w + j) + (l >> 4) (+ 32), stored chunk l & 15 <- source chunk (l & 15) ^ (b & 15); the
+    // second half is the same lane offsets 8 KB further on both sides.  Every wave also moves the unit's 64 norms (lane
+    // l <- norm of row l, one 256-byte piece), so that all waves issue the same kUnitVmem instructions per unit and one
+    // constant vmcnt serves them all; the NW copies write the same bytes.  M0 is written in the statement that reads
+    // it, and restored there: the compiler neither knows nor preserves it around an asm statement.
+    unsigned voff[kPieces];
+#pragma unroll
+    for (int j = 0; j < kPieces; ++j) {
+        const int row_in = 4 * (kPieces * wave + j) + (lane >> 4);
+        voff[j] = (unsigned)(row_in * 256 + 16 * ((lane & 15) ^ (row_in & 15)));
+    }
     const unsigned voff_n = (unsigned)lane * 4u;
     const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
     auto issue_unit = [&](int n, int slot) __attribute__((always_inline)) {  // unit n of the workgroup, kUnitVmem instructions
         // past the end (the last D - 1 prefetches): the workgroup's last unit once more, into a slot nobody reads -- in
         // bounds, and the count of the queue stays what the waits assume
-        const int64_t row0 = ((int64_t)blockIdx.x + (int64_t)min(n, T - 1) * G) * kUnitRows;
+        const int64_t row0 = ((int64_t)bx + (int64_t)min(n, T - 1) * G) * kUnitRows;
         const char* ub0 = reinterpret_cast<const char*>(p.img) + row0 * (kDim * 2);
         const char* ub1 = ub0 + kUnitRowBytes / 2;
         const char* nb = reinterpret_cast<const char*>(p.bnorm + row0);
-        const unsigned dst0 = ring_lds + (unsigned)(slot * kUnitBytes) + (unsigned)wave * 1024u;
-        const unsigned dst1 = dst0 + (unsigned)(kUnitRowBytes / 2);
         const unsigned dst_n = ring_lds + (unsigned)(slot * kUnitBytes + kUnitRowBytes);
         unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" VS_F32F_CPOL_ASM "\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(ub0), "s"(dst0) : "memory");
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" VS_F32F_CPOL_ASM "\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(ub1), "s"(dst1) : "memory");
+#pragma unroll
+        for (int j = 0; j < kPieces; ++j) {
+            const unsigned dst0 = ring_lds + (unsigned)(slot * kUnitBytes) + (unsigned)(kPieces * wave + j) * 1024u;
+            const unsigned dst1 = dst0 + (unsigned)(kUnitRowBytes / 2);
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" VS_F32F_CPOL_ASM "\n\ts_mov_b32 m0, %0"
+                         : "=&s"(keep) : "v"(voff[j]), "s"(ub0), "s"(dst0) : "memory");
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" VS_F32F_CPOL_ASM "\n\ts_mov_b32 m0, %0"
+                         : "=&s"(keep) : "v"(voff[j]), "s"(ub1), "s"(dst1) : "memory");
+        }
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
                      : "=&s"(keep) : "v"(voff_n), "s"(nb), "s"(dst_n) : "memory");
     };
@@ -1345,7 +1367,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
     float qn[CBW], tau[CBW], eb[CBW];
 #pragma unroll
     for (int h = 0; h < CBW; ++h) {
-        const int cb = min(wave + kScanWaves * h, n_cb - 1);  // = 2 batch + half
+        const int cb = min(vw + kScanWaves * h, n_cb - 1);  // = 2 batch + half
         const int qrow = 16 * (cb & 1) + r;
         const int qglob = (cb >> 1) * kMaxBatch + (qrow < p.nq_valid ? qrow : 0);
         const uint16_t* src = p.qbf + ((int64_t)cb * 4 * 64 + lane) * 8;  // 1 KB per instruction
@@ -1368,7 +1390,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
 #pragma unroll
     for (int h = 0; h < CBW; ++h) {
         asm volatile("" : "+v"(qb[h][0]), "+v"(qb[h][1]), "+v"(qb[h][2]), "+v"(qb[h][3]), "+v"(qn[h]), "+v"(tau[h]), "+v"(eb[h]) :: "memory");
-        const int cb = wave + kScanWaves * h;
+        const int cb = vw + kScanWaves * h;
         const bool live = cb < n_cb && 16 * (cb & 1) + r < p.nq_valid;
         // |S_fl - S'| <= E.  L2: the accumulators start from -bn / 2 (score_tile), and the exact hot test
         // RN(bn - 2 S_fl) < thr implies S'' > th2 = filter_th2(thr, E, C) (vs_kernels.h).  IP: S_fl > thr gives
@@ -1382,7 +1404,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
         }
     }
 
-    int4* wbuf = p.sink.wbuf + ((int64_t)blockIdx.x * kScanWaves + wave) * p.sink.wcap;
+    int4* wbuf = p.sink.wbuf + ((int64_t)bx * kScanWaves + vw) * p.sink.wcap;
     int wbase = 0;  // wave-uniform fill of the private candidate buffer
     float opaque_inf = __builtin_inff();  // for max4_finite: a scalar register, opaque to the optimiser
     asm volatile("" : "+s"(opaque_inf));
@@ -1392,7 +1414,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
     //   1. s_waitcnt vmcnt((D - 3) kUnitVmem): this wave's pieces of unit t + 1 have landed; those of t + 2 .. t + D - 2
     //      stay in flight.  Candidate stores to wbuf count on vmcnt as well, but every one of them is younger than the
     //      DMAs of the unit it follows: they can only make this wait retire more, never less, than unit t + 1.
-    //   2. raw s_barrier: every wave has passed step 1, so all 16 row pieces and the norms of unit t + 1 are in LDS; and
+    //   2. raw s_barrier: every wave of the workgroup has passed step 1, so all 16 row pieces and the norms of unit t + 1 are in LDS; and
     //      every wave has finished step t - 1, whose last MFMAs consumed the last fragments read from unit t - 1 (an
     //      MFMA issues only once its operands have arrived, and score_tile pins its last chain in front of the barrier;
     //      the reads at the end of step t - 1 are of unit t), so slot (t - 1) % D is free.  (__syncthreads() would add
@@ -1445,7 +1467,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
                         const int pos = wbase + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
                         // (query, value, id): the value is the bf16 sum, replaced by the exact distance in RecheckF32;
                         // query = batch * 32 + 16 half + r = 16 cb + r
-                        const int qglob = 16 * (wave + kScanWaves * h) + r;
+                        const int qglob = 16 * (vw + kScanWaves * h) + r;
                         if (pass && pos < p.sink.wcap)
                             wbuf[pos] = make_int4(qglob, __builtin_bit_cast(int, acc[j]), row + p.id_offset, 0);
                         wbase += __popcll(mask);
@@ -1493,7 +1515,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
         VS_F32F_STAMP(2);
         issue_unit(t + D - 1, (sl + D - 1) % D);
         VS_F32F_STAMP(3);
-        const int row_u = ((int)blockIdx.x + t * G) * kUnitRows + 4 * g;
+        const int row_u = (bx + t * G) * kUnitRows + 4 * g;
 #pragma unroll
         for (int i = 0; i < kUnitTiles; ++i) {
             score_tile(i & 1, row_u + TR * i);
@@ -1520,7 +1542,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // retire the tail prefetches before the wave ends
 #ifdef VS_STAMPS
     if (p.dbg && lane == 0) {
-        int32_t* o = p.dbg + ((int64_t)blockIdx.x * kScanWaves + wave) * 16;
+        int32_t* o = p.dbg + ((int64_t)bx * kScanWaves + vw) * 16;
 #pragma unroll
         for (int i = 0; i < 8; ++i) o[i] = st_sum[i];
         o[8] = T;
@@ -1529,7 +1551,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
 #endif
 #undef VS_F32F_STAMP
     const RecheckF32 fix{p.base, p.bnorm, p.q, p.q_batch_stride, p.qnorm, p.tau0, p.metric, p.id_offset};
-    int kept = sink_bin_wave<RecheckF32, true>(p.sink, (int)blockIdx.x * kScanWaves + wave, wbase, lane, fix);
+    int kept = sink_bin_wave<RecheckF32, true>(p.sink, bx * kScanWaves + vw, wbase, lane, fix);
     if (p.sink.stats && wbase > 0) {  // (wave-uniform) one atomic instruction: lane 0 adds the sweep's count, lane 1 the survivors
 #pragma unroll
         for (int u = 32; u >= 1; u >>= 1) kept += __shfl_xor(kept, u);
@@ -1537,10 +1559,10 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_f32f_kernel(const Stream
     }
 }
 
-template <int CBW>
+template <int CBW, int NW>
 static hipError_t launch_scan_f32f(const StreamParams& p, int grid, hipStream_t s) {
-    constexpr int kLds = kFilterDepth * kUnitBytes;
-    auto kfn = p.metric ? scan_f32f_kernel<CBW, kFilterDepth, true> : scan_f32f_kernel<CBW, kFilterDepth, false>;
+    constexpr int kLds = kFilterDepth * kUnitBytes;  // per workgroup: at NW = 4 a CU holds two rings
+    auto kfn = p.metric ? scan_f32f_kernel<CBW, kFilterDepth, true, NW> : scan_f32f_kernel<CBW, kFilterDepth, false, NW>;
     grid = (int)std::max<int64_t>(1, std::min<int64_t>(grid, (p.n_rows + kUnitRows - 1) / kUnitRows));  // every workgroup owns a unit
     static bool attr_set[64][2] = {};
     int dev = 0;
@@ -1550,8 +1572,19 @@ static hipError_t launch_scan_f32f(const StreamParams& p, int grid, hipStream_t 
         if (e != hipSuccess) return e;
         attr_set[dev][p.metric ? 1 : 0] = true;
     }
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(kScanThreads), kLds, s, p);
+    // NW = 4: workgroups x and x + grid are the two halves of the 8-wave workgroup x (the same units, waves 0..3 and 4..7)
+    hipLaunchKernelGGL(kfn, dim3(grid * (kScanWaves / NW)), dim3(NW * 64), kLds, s, p);
     return hipGetLastError();
+}
+
+// Waves per workgroup of the prefilter sweep where the caller does not force one (StreamParams::f32f_waves), by column
+// blocks per wave: the choice measured per launch size.
+static int f32f_waves_default(int cbw) { return cbw >= 4 ? 4 : 8; }
+
+template <int CBW>
+static hipError_t launch_scan_f32f(const StreamParams& p, int grid, hipStream_t s) {
+    const int nw = p.f32f_waves ? p.f32f_waves : f32f_waves_default(CBW);
+    return nw == 4 ? launch_scan_f32f<CBW, 4>(p, grid, s) : launch_scan_f32f<CBW, 8>(p, grid, s);
 }
 
 hipError_t launch_scan_f32_stream(const StreamParams& p, int grid, hipStream_t s) {
@@ -1560,7 +1593,7 @@ hipError_t launch_scan_f32_stream(const StreamParams& p, int grid, hipStream_t s
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     if (p.qbf) {  // the bf16 prefilter: column blocks per wave for the launch's 2 n_batches column blocks
         const int cbw = (2 * p.n_batches + kScanWaves - 1) / kScanWaves;
-        if (p.n_batches < 1 || cbw > 8 || !p.img) return hipErrorInvalidValue;
+        if (p.n_batches < 1 || cbw > 8 || !p.img || (p.f32f_waves != 0 && p.f32f_waves != 4 && p.f32f_waves != 8)) return hipErrorInvalidValue;
         return cbw == 1 ? launch_scan_f32f<1>(p, grid, s) : cbw == 2 ? launch_scan_f32f<2>(p, grid, s)
              : cbw <= 4 ? launch_scan_f32f<4>(p, grid, s) : launch_scan_f32f<8>(p, grid, s);
     }

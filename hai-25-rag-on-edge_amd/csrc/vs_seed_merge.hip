@@ -468,12 +468,29 @@ static hipError_t launch_merge_heads(const MergeParams& p, const MergeLayout& L,
 __global__ __launch_bounds__(256) void merge_compact_kernel(const MergeParams p, const MergeLayout L) {
     __shared__ float cd[kCompactCap];
     __shared__ int ci[kCompactCap];
-    merge_compact_body(p, L, cd, ci, blockIdx.x);
+    // run_mode 3, one launch behind a streaming scan and its fallback scan: the overflow word says whose lists hold the result
+    MergeParams e = p;
+    MergeLayout Le = L;
+    if (p.run_mode == 3) {
+        if (p.run_if[0]) {  // (kernel-uniform)
+            e.part_d = p.alt_part_d;
+            e.part_i = p.alt_part_i;
+            e.G = p.alt_G;
+            e.kin = p.alt_kin;
+            e.flat_len = nullptr;
+            Le.stride_g = p.alt_stride_g;
+            Le.stride_q = p.alt_stride_q;
+        }
+        e.run_if = nullptr;
+    }
+    merge_compact_body(e, Le, cd, ci, blockIdx.x);
 }
 
 hipError_t launch_merge_layout(const MergeParams& p, int64_t stride_g, int64_t stride_q, hipStream_t s) {
     if (p.kout < 1 || p.G < 1 || p.nq < 1) return hipErrorInvalidValue;
     MergeLayout L{stride_g, stride_q};
+    if (p.run_mode == 3 && (!p.run_if || p.alt_G < 1 || (int64_t)p.alt_G * p.alt_kin > kCompactCap || (int64_t)p.G * p.kin > kCompactCap))
+        return hipErrorInvalidValue;  // both parameter sets have to fit the compacting merge
     if ((int64_t)p.G * p.kin <= kCompactCap) {
         hipLaunchKernelGGL(merge_compact_kernel, dim3(p.nq), dim3(256), 0, s, p, L);
         return hipGetLastError();

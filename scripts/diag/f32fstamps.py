@@ -2,7 +2,8 @@
 root).  Every wave sums, over its steps, the shader-clock time between its steps' stamps (vs_scan.hip, VS_F32F_STAMP);
 this prints, over the waves and steps of one SIFT-1M launch of 32 batches x 32 queries, the share of a step spent in the
 vmcnt wait, in the barrier, in the unit's DMA issue and in the four tiles, and how far the waves of a workgroup are apart
-in tile time."""
+in tile time.  The kernel stamps [sweeper][8 waves][16] under either organisation; with two 4-wave workgroups per CU (the
+default at 32 batches; VSEARCH_F32F_WAVES=8 forces the other) waves 0..3 and 4..7 of a sweeper are workgroups of their own."""
 import ctypes as C
 import os
 import sys
@@ -25,7 +26,7 @@ o_d = torch.zeros((NB * B, 6), dtype=torch.float32, device="cuda")
 o_i = torch.zeros((NB * B, 6), dtype=torch.int32, device="cuda")
 fl = torch.zeros((NB * B,), dtype=torch.int32, device="cuda")
 ROW0 = 12288  # the kernel's rows of the debug buffer (the launches around it stamp the first rows)
-dbg = torch.zeros((ROW0 + 256 * 8, 16), dtype=torch.int32, device="cuda")  # the grid is at most 256 workgroups of 8 waves
+dbg = torch.zeros((ROW0 + 256 * 8, 16), dtype=torch.int32, device="cuda")  # at most 256 sweepers of 8 waves (256 workgroups of 8, or 512 of 4)
 L.vs_debug_buffer(dbg.data_ptr())
 names = ["between steps", "vmcnt wait", "barrier", "DMA issue", "tile 0", "tile 1", "tile 2", "tile 3"]
 with pkg.BruteForceIndex(base) as idx:
@@ -34,12 +35,13 @@ with pkg.BruteForceIndex(base) as idx:
         dbg.zero_()
         idx.search_dev_multi(qd.data_ptr(), NB, B, 5, o_i.data_ptr(), o_d.data_ptr(), fl.data_ptr(), st)
         torch.cuda.synchronize()
-    t = dbg.cpu().numpy().astype(np.int64)[ROW0:].reshape(256, 8, 16)
+    NW = 8 if os.environ.get("VSEARCH_F32F_WAVES") == "8" else 4  # waves per workgroup
+    t = dbg.cpu().numpy().astype(np.int64)[ROW0:].reshape(256 * 8 // NW, NW, 16)
     t = t[t[:, 0, 8] != 0]  # workgroups that ran
     steps = t[:, :, 8]
     per_step = t[:, :, :8] / steps[:, :, None]  # clocks per step, by wave
     total = per_step.sum(2)
-    print(f"workgroups {t.shape[0]}, steps per wave {steps.mean():.1f}, clocks per step {total.mean():.0f} "
+    print(f"workgroups {t.shape[0]} of {NW} waves, steps per wave {steps.mean():.1f}, clocks per step {total.mean():.0f} "
           f"(min wave {total.min():.0f}, max wave {total.max():.0f}), candidates per wave {t[:, :, 9].mean():.1f}")
     for i, n in enumerate(names):
         print(f"  {n:14s} {per_step[:, :, i].mean():9.1f} clocks  {100.0 * per_step[:, :, i].mean() / total.mean():5.1f} %")
