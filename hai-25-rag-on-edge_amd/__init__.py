@@ -169,6 +169,7 @@ def lib():
         "vs_ivf_shard_block_words": (i64, [i32, i32]),
         "vs_ivf_search_dev_vshards": (i32, [C.POINTER(vp), i32, vp, i32, i32, i32, i32, vp, vp, C.POINTER(C.c_double), vp]),
         "vs_q8_create": (i32, [vp, i64, i32, C.POINTER(Q8Encodings), i32, i64, C.POINTER(vp)]),
+        "vs_q8_create_nd": (i32, [vp, i64, i32, C.POINTER(Q8Encodings), i32, i64, C.POINTER(vp)]),
         "vs_q8_destroy": (None, [vp]),
         "vs_q8_num_docs": (i64, [vp]),
         "vs_q8_dim": (i32, [vp]),
@@ -482,7 +483,10 @@ class BruteForceIndex(_Index):
 class Q8Runner:
     """The reference's device runner with its UFIXED_POINT_8 I/O (QnnRunner.h:18-55): the database is baked in at
     construction, ``executeBatchRaw`` returns the raw uint8 [B, N] inner-product scores, ``search`` adds
-    find_top_k_int8 (main.cpp:30-57).  Method names follow QnnRunner."""
+    find_top_k_int8 (main.cpp:30-57).  Method names follow QnnRunner.
+
+    Any vector length 1 <= d <= 2048: 128-d bases take vs_q8_create, the others vs_q8_create_nd (rows padded to 64
+    bytes, the general-dimension score kernel)."""
 
     def __init__(self, base, input_scale=None, weight_scale=None, weight_offset: int = 0, output_scale=None,
                  device: int = 0, id_offset: int = 0):
@@ -495,7 +499,8 @@ class Q8Runner:
             if input_scale is None or weight_scale is None or output_scale is None:
                 raise ValueError("give all three scales or none (None = the runner's hard-coded encodings)")
             enc = C.byref(Q8Encodings(input_scale, weight_scale, weight_offset, output_scale))
-        _check(lib().vs_q8_create(_p(base), base.shape[0], base.shape[1], enc, device, id_offset, C.byref(self._h)))
+        create = lib().vs_q8_create if base.shape[1] == 128 else lib().vs_q8_create_nd
+        _check(create(_p(base), base.shape[0], base.shape[1], enc, device, id_offset, C.byref(self._h)))
 
     def close(self):
         if self._h:

@@ -23,12 +23,16 @@
 //                               the few entries above it ranked in LDS; long runs of equal scores: bisection over the
 //                               byte value with SWAR compares, lowest-numbered entries at the cut first
 //   q8_topk_final_kernel        per query: k rounds of "largest key below the previous one" over the chunks' candidates
+// The first two are the 128-d kernels (vs_q8_create).  A runner made by vs_q8_create_nd at any other vector dimension
+// (1 to 2048) takes q8_quantize_queries_nd_kernel and q8_scores_nd_kernel of vs_q8_nd.hip in their place, on rows padded
+// to 64 bytes; the top-k kernels work on the score matrix and serve both.
 // Order of equal scores: ascending row number (the reference's order among equal uint8 scores is whatever its C++
 // library's heap leaves, main.cpp:36-57).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -37,8 +41,10 @@
 
 #include "../../include/vsearch.h"
 #include "vs_host.h"
+#include "vs_q8_nd.h"
 #include "vs_res.h"
 
+using vs::q8_sat;
 using vs::set_error;
 
 #define HIPCHK(expr)                                                                                   \
@@ -53,9 +59,9 @@ using vs::set_error;
 namespace {
 
 constexpr int kDim = 128;
-constexpr int kBatch = 32;
+constexpr int kBatch = vs::kQ8Batch;
 constexpr int kGroup = 32;          // batches whose queries one quantiser launch prepares
-constexpr int kGroupRows = 64;      // rows a wave scores per step
+constexpr int kGroupRows = vs::kQ8GroupRows;  // rows a wave scores per step
 constexpr int kChunkRows = 16384;   // rows per top-k chunk (256 threads x 64 bytes)
 constexpr int kCand = 16;           // candidate slots per (chunk, query); k <= 16
 constexpr int kIpBias = 128 * 128 * kDim;  // sum over t of 128 * 128
@@ -64,12 +70,7 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
-// sat_u8(trunc(v)) for a value that already carries its +0.5: NaN and negatives -> 0 (QnnRunner.cpp:52-53)
-__device__ __forceinline__ unsigned q8_sat(float v) {
-    v = fminf(fmaxf(v, 0.0f), 255.0f);
-    return (unsigned)(int)v;
-}
-
+// (q8_sat, the saturating conversion of both quantisers, is in vs_q8_nd.h: the general-dimension kernels share it)
 __global__ __launch_bounds__(64) void q8_quantize_queries_kernel(const float* __restrict__ q, int B, float inv_scale, int w_off,
                                                                  int8_t* __restrict__ q8, int32_t* __restrict__ cq) {
     const int nb = blockIdx.x >> 5, b = blockIdx.x & 31, l = threadIdx.x;  // batch, row of the batch
@@ -381,16 +382,18 @@ __global__ __launch_bounds__(256) void q8_topk_chunk_kernel(const uint8_t* __res
 
 struct vs_q8 {
     int device = 0;
+    int dim = kDim, dim_b = kDim;  // vector length; row bytes (dim rounded up to 64)
+    bool general = false;          // the general-dimension kernels (vs_q8_nd.hip): any dim but 128, or 128 forced
     int64_t n_rows = 0, n_pad = 0;
     int32_t id_offset = 0;
     vs_q8_encodings enc{};
     float inv_in = 0, mult = 0;
     int num_cus = 256;
-    vs::DevBuf<int8_t> d_wq;       // [n_pad][128]
+    vs::DevBuf<int8_t> d_wq;       // [n_pad][dim_b]
     vs::DevBuf<int32_t> d_wterm;   // [n_pad]
-    vs::DevBuf<int8_t> d_q8;       // [kGroup][32][128] quantised queries of up to kGroup batches
+    vs::DevBuf<int8_t> d_q8;       // [kGroup][32][dim_b] quantised queries of up to kGroup batches (general: as fragments)
     vs::DevBuf<int32_t> d_cq;      // [kGroup][32]
-    vs::DevBuf<float> d_q;         // [32][128] staging of host queries
+    vs::DevBuf<float> d_q;         // [32][dim] staging of host queries
     vs::DevBuf<uint8_t> d_scores;  // [32][n_pad]  the runner's output buffer (QnnRunner.cpp:322-323)
     vs::DevBuf<u64> d_cand;        // [32][n_chunks][kCand]
     vs::DevBuf<int32_t> d_ids;     // [32][16]
@@ -423,20 +426,45 @@ int guarded(F&& f) {
     }
 }
 
+bool encodings_valid(const vs_q8_encodings& enc) {
+    return enc.input_scale > 0.0f && enc.weight_scale > 0.0f && enc.output_scale > 0.0f && enc.weight_offset <= 0 && enc.weight_offset >= -255;
+}
+
+int bad_encodings() {
+    set_error("vs_q8_create: scales must be positive, weight_offset in [-255, 0] (real = scale * (q + offset))");
+    return VS_ERR_INVALID;
+}
+
+// nd: vs_q8_create_nd (any dim from 1 to 2048, every host check before the device), otherwise vs_q8_create (128 only)
 int q8_create_impl(const float* base_host, int64_t n_rows, int dim, const vs_q8_encodings* enc_in, int device, int64_t id_offset,
-                   vs_q8** out) {
+                   vs_q8** out, bool nd) {
     if (!out || !base_host || n_rows <= 0) {
         set_error("vs_q8_create: bad arguments");
         return VS_ERR_INVALID;
     }
-    if (dim != kDim) {
+    if (!nd && dim != kDim) {
         set_error("only dim == 128 is compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (dim < 1) {
+        set_error("vs_q8_create_nd: dim must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (dim > vs::kQ8MaxDim) {
+        set_error("vs_q8_create_nd: dim > 2048 is not supported");
         return VS_ERR_UNSUPPORTED;
     }
     if (n_rows + id_offset > 0x7fffffffLL || id_offset < 0) {
         set_error("ids must fit int32");
         return VS_ERR_UNSUPPORTED;
     }
+    if (nd && enc_in && !encodings_valid(*enc_in)) return bad_encodings();
+    bool general = dim != kDim;
+    if (nd && !general) {  // the comparison toggle: the general kernels at 128 as well
+        const char* f = std::getenv("VSEARCH_Q8_ND_FORCE");
+        general = f && !std::strcmp(f, "1");
+    }
+    const int dim_b = vs::q8_dim_b(dim);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         set_error("no HIP device available (this library has no CPU fallback)");
@@ -453,15 +481,11 @@ int q8_create_impl(const float* base_host, int64_t n_rows, int dim, const vs_q8_
         enc.input_scale = 0.6627451181411743f;
         enc.output_scale = 1013.4312133789062500f;
         float mx = 0.0f;
-        for (int64_t i = 0; i < n_rows * kDim; ++i) mx = std::fmax(mx, base_host[i]);
+        for (int64_t i = 0; i < n_rows * dim; ++i) mx = std::fmax(mx, base_host[i]);
         enc.weight_scale = mx > 0.0f ? mx / 255.0f : 1.0f;
         enc.weight_offset = 0;
     }
-    if (!(enc.input_scale > 0.0f) || !(enc.weight_scale > 0.0f) || !(enc.output_scale > 0.0f) || enc.weight_offset > 0 ||
-        enc.weight_offset < -255) {
-        set_error("vs_q8_create: scales must be positive, weight_offset in [-255, 0] (real = scale * (q + offset))");
-        return VS_ERR_INVALID;
-    }
+    if (!encodings_valid(enc)) return bad_encodings();
     HIPCHK(hipSetDevice(device));
     std::unique_ptr<vs_q8> h(new (std::nothrow) vs_q8());  // (released, with what it holds, on every early return)
     if (!h) {
@@ -469,6 +493,9 @@ int q8_create_impl(const float* base_host, int64_t n_rows, int dim, const vs_q8_
         return VS_ERR_NOMEM;
     }
     h->device = device;
+    h->dim = dim;
+    h->dim_b = dim_b;
+    h->general = general;
     h->n_rows = n_rows;
     h->n_pad = (n_rows + kGroupRows - 1) / kGroupRows * kGroupRows;
     h->id_offset = (int32_t)id_offset;
@@ -478,34 +505,44 @@ int q8_create_impl(const float* base_host, int64_t n_rows, int dim, const vs_q8_
     h->n_chunks = (int)((n_rows + kChunkRows - 1) / kChunkRows);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) h->num_cus = prop.multiProcessorCount;
-    // database -> uint8 (stored minus 128) + 128 * row sums, in slabs of 1 M rows
+    // database -> uint8 (stored minus 128) + 128 * row sums, in slabs of 128 MB of row bytes (1 M rows at 128-d)
     int rc;
-    if ((rc = h->d_wq.alloc((size_t)h->n_pad * kDim))) return rc;
+    if ((rc = h->d_wq.alloc((size_t)h->n_pad * dim_b))) return rc;
     if ((rc = h->d_wterm.alloc((size_t)h->n_pad))) return rc;
-    if ((rc = h->d_q8.alloc((size_t)kGroup * kBatch * kDim))) return rc;
+    if ((rc = h->d_q8.alloc((size_t)kGroup * kBatch * dim_b))) return rc;
     if ((rc = h->d_cq.alloc((size_t)kGroup * kBatch))) return rc;
-    if ((rc = h->d_q.alloc((size_t)kBatch * kDim))) return rc;
+    if ((rc = h->d_q.alloc((size_t)kBatch * dim))) return rc;
     if ((rc = h->d_scores.alloc((size_t)kBatch * h->n_pad))) return rc;
     if ((rc = h->d_cand.alloc((size_t)kBatch * h->n_chunks * kCand))) return rc;
     if ((rc = h->d_ids.alloc((size_t)kBatch * kCand))) return rc;
     if ((rc = h->d_top.alloc((size_t)kBatch * kCand))) return rc;
     if ((rc = h->stream.create())) return rc;
     const float inv_w = 1.0f / enc.weight_scale;
-    const int64_t slab = 1 << 20;
-    std::vector<int8_t> bytes((size_t)std::min(slab, h->n_pad) * kDim);
+    const int64_t slab = ((int64_t)128 << 20) / dim_b;  // a multiple of 64 rows: dim_b is a multiple of 64 and at most 2048
+    // the general kernels take the real dim in their constant, so their padding (bytes past dim, rows past n_rows) is 0
+    // and adds nothing to a dot product; the 128-d kernels' padding rows are the quantised zero row, -128
+    const int8_t pad_row = general ? 0 : -128;
+    std::vector<int8_t> bytes((size_t)std::min(slab, h->n_pad) * dim_b);
     std::vector<int32_t> term((size_t)std::min(slab, h->n_pad));
     for (int64_t r0 = 0; r0 < h->n_pad; r0 += slab) {
         const int64_t rows = std::min(slab, h->n_pad - r0);
         for (int64_t i = 0; i < rows; ++i) {
+            int8_t* dst = bytes.data() + (size_t)i * dim_b;
             int sum = 0;
-            for (int t = 0; t < kDim; ++t) {
-                const int q = r0 + i < n_rows ? (int)quant_host(base_host[(size_t)(r0 + i) * kDim + t], inv_w, enc.weight_offset) : 0;
-                bytes[(size_t)i * kDim + t] = (int8_t)(q - 128);
-                sum += q;
+            if (r0 + i < n_rows) {
+                const float* src = base_host + (size_t)(r0 + i) * dim;
+                for (int t = 0; t < dim; ++t) {
+                    const int q = (int)quant_host(src[t], inv_w, enc.weight_offset);
+                    dst[t] = (int8_t)(q - 128);
+                    sum += q;
+                }
+                std::fill(dst + dim, dst + dim_b, (int8_t)0);
+            } else {
+                std::fill(dst, dst + dim_b, pad_row);
             }
             term[(size_t)i] = 128 * sum;
         }
-        if (hipMemcpy(h->d_wq + (size_t)r0 * kDim, bytes.data(), (size_t)rows * kDim, hipMemcpyHostToDevice) != hipSuccess ||
+        if (hipMemcpy(h->d_wq + (size_t)r0 * dim_b, bytes.data(), (size_t)rows * dim_b, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(h->d_wterm + r0, term.data(), (size_t)rows * 4, hipMemcpyHostToDevice) != hipSuccess) {
             set_error("vs_q8_create: upload failed");
             return VS_ERR_DEVICE;
@@ -516,6 +553,10 @@ int q8_create_impl(const float* base_host, int64_t n_rows, int dim, const vs_q8_
 }
 
 int q8_quantize_enqueue(vs_q8* h, const float* q_dev, int n_batches, int B, hipStream_t s) {
+    if (h->general) {
+        HIPCHK(vs::launch_q8_quantize_nd(q_dev, n_batches, B, h->dim, h->inv_in, h->enc.weight_offset, h->d_q8, h->d_cq, s));
+        return VS_OK;
+    }
     hipLaunchKernelGGL(q8_quantize_queries_kernel, dim3(n_batches * kBatch), dim3(64), 0, s, q_dev, B, h->inv_in, h->enc.weight_offset, h->d_q8,
                        h->d_cq);
     HIPCHK(hipGetLastError());
@@ -524,6 +565,11 @@ int q8_quantize_enqueue(vs_q8* h, const float* q_dev, int n_batches, int B, hipS
 
 // scores of the slot-th quantised batch
 int q8_scores_enqueue(vs_q8* h, int slot, int B, uint8_t* scores_dev, int64_t ld, hipStream_t s) {
+    if (h->general) {
+        HIPCHK(vs::launch_q8_scores_nd(h->d_wq, h->d_wterm, h->d_q8 + (size_t)slot * kBatch * h->dim_b, h->d_cq + slot * kBatch, h->dim,
+                                       h->n_rows, h->n_pad, B, h->mult, scores_dev, ld, h->num_cus, s));
+        return VS_OK;
+    }
     const int64_t n_groups = h->n_pad / kGroupRows;
     // 4 workgroups = 16 waves per CU: what 120 registers allow
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_groups + 3) / 4, (int64_t)h->num_cus * 4));
@@ -558,7 +604,12 @@ extern "C" {
 
 int vs_q8_create(const float* base_host, int64_t n_rows, int dim, const vs_q8_encodings* enc, int device, int64_t id_offset,
                  vs_q8** out) {
-    return guarded([&]() -> int { return q8_create_impl(base_host, n_rows, dim, enc, device, id_offset, out); });
+    return guarded([&]() -> int { return q8_create_impl(base_host, n_rows, dim, enc, device, id_offset, out, false); });
+}
+
+int vs_q8_create_nd(const float* base_host, int64_t n_rows, int dim, const vs_q8_encodings* enc, int device, int64_t id_offset,
+                    vs_q8** out) {
+    return guarded([&]() -> int { return q8_create_impl(base_host, n_rows, dim, enc, device, id_offset, out, true); });
 }
 
 void vs_q8_destroy(vs_q8* h) {
@@ -569,7 +620,7 @@ void vs_q8_destroy(vs_q8* h) {
 }
 
 int64_t vs_q8_num_docs(const vs_q8* h) { return h ? h->n_rows : 0; }
-int vs_q8_dim(const vs_q8* h) { return h ? kDim : 0; }
+int vs_q8_dim(const vs_q8* h) { return h ? h->dim : 0; }
 int vs_q8_batch(const vs_q8* h) { return h ? kBatch : 0; }
 float vs_q8_output_scale(const vs_q8* h) { return h ? h->enc.output_scale : 0.0f; }
 int vs_q8_get_encodings(const vs_q8* h, vs_q8_encodings* out) {
@@ -596,7 +647,7 @@ int vs_q8_execute(vs_q8* h, const float* queries_host, int B, uint8_t* scores_ho
         return VS_ERR_INVALID;
     }
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(h->d_q, queries_host, (size_t)B * kDim * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_q, queries_host, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, h->stream));
     int rc = q8_execute_enqueue(h, h->d_q, B, h->d_scores, h->n_pad, h->stream);
     if (rc) return rc;
     HIPCHK(hipMemcpy2DAsync(scores_host, (size_t)h->n_rows, h->d_scores, (size_t)h->n_pad, (size_t)h->n_rows, (size_t)B, hipMemcpyDeviceToHost,
@@ -618,7 +669,7 @@ int vs_q8_search_dev(vs_q8* h, const float* queries_dev, int n_batches, int B, i
     hipStream_t s = static_cast<hipStream_t>(stream);
     for (int g0 = 0; g0 < n_batches; g0 += kGroup) {  // one quantiser launch per group of batches, three launches per batch
         const int gs = std::min(kGroup, n_batches - g0);
-        int rc = q8_quantize_enqueue(h, queries_dev + (size_t)g0 * B * kDim, gs, B, s);
+        int rc = q8_quantize_enqueue(h, queries_dev + (size_t)g0 * B * h->dim, gs, B, s);
         if (rc) return rc;
         for (int j = 0; j < gs; ++j) {
             const size_t o = (size_t)(g0 + j) * B * k;
@@ -640,7 +691,7 @@ int vs_q8_search(vs_q8* h, const float* queries_host, int64_t nq, int k, int32_t
     HIPCHK(hipSetDevice(h->device));
     for (int64_t q0 = 0; q0 < nq; q0 += kBatch) {  // the harness loop of main.cpp:201-251
         const int B = (int)std::min<int64_t>(kBatch, nq - q0);
-        HIPCHK(hipMemcpyAsync(h->d_q, queries_host + (size_t)q0 * kDim, (size_t)B * kDim * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->d_q, queries_host + (size_t)q0 * h->dim, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, h->stream));
         int rc = q8_execute_enqueue(h, h->d_q, B, h->d_scores, h->n_pad, h->stream);
         if (rc || (rc = q8_topk_enqueue(h, B, k, h->d_ids, h->d_top, h->stream))) return rc;
         HIPCHK(hipMemcpyAsync(ids + (size_t)q0 * k, h->d_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, h->stream));

@@ -129,7 +129,7 @@ VS_API int vs_bf_create(const float* base_host, int64_t n_rows, int dim, int met
  * vs_bf_create_nd_u8 below, not from this creator).  The
  * sharded calls (vs_bf_search_dev_sharded, vs_bf_search_sharded, vs_bf_search_vshards) and
  * every vs_ivf_* call return VS_ERR_UNSUPPORTED on a general index made by this creator (an IVF
- * index at other dimensions comes from vs_ivf_create / vs_ivf_load); q8 stays at 128. */
+ * index at other dimensions comes from vs_ivf_create / vs_ivf_load; a q8 runner from vs_q8_create_nd). */
 VS_API int vs_bf_create_nd(const float* base_host, int64_t n_rows, int dim, int metric,
                            int device, int64_t id_offset, vs_index** out);
 
@@ -252,9 +252,29 @@ typedef struct vs_q8_encodings {
 } vs_q8_encodings;
 
 /* enc == NULL: the runner's hard-coded input / output scales and weight_scale =
- * max(database) / 255, offset 0.  id_offset as in vs_bf_create. */
+ * max(database) / 255, offset 0.  id_offset as in vs_bf_create.  dim must be 128
+ * (VS_ERR_UNSUPPORTED otherwise); any other vector length: vs_q8_create_nd. */
 VS_API int vs_q8_create(const float* base_host, int64_t n_rows, int dim, const vs_q8_encodings* enc,
                         int device, int64_t id_offset, vs_q8** out);
+
+/* The same for any vector length, as create_model.py builds the [batch, dim] x [dim, N] graph for
+ * whatever dim the .fvecs header states and QnnRunner::getDim() reports it: 1 <= dim <= 2048.
+ * Checked in this order, the first five without a device: null pointers or n_rows <= 0:
+ * VS_ERR_INVALID; dim < 1: VS_ERR_INVALID; dim > 2048: VS_ERR_UNSUPPORTED; ids that do not fit
+ * int32 (n_rows + id_offset > 2^31 - 1, id_offset < 0): VS_ERR_UNSUPPORTED; enc given with a scale
+ * that is not > 0 or a weight_offset outside [-255, 0]: VS_ERR_INVALID; no device: VS_ERR_DEVICE.
+ * dim == 128 gives exactly vs_q8_create's runner: the same kernels, launches and bytes
+ * (VSEARCH_Q8_ND_FORCE=1 in the environment, read at creation by this function only, builds the
+ * general runner at 128 as well: the comparison toggle).  Any other dim gives a "general"
+ * runner: rows as int8 (w8 - 128) padded with zeros to a multiple of 64 bytes, scored by a kernel
+ * that walks the row in 128-byte steps.  Every vs_q8_* call below accepts it with the same
+ * signatures and output layouts; queries are [B][dim] floats, unpadded; k <= 16 stays;
+ * vs_q8_dim returns dim.  enc == NULL: as above, weight_scale over all n_rows * dim values.
+ * The arithmetic is the one stated above, with t < dim; ip is exact in int32 (|ip| <= 255 * 255 *
+ * 2048 < 2^27) and (float)ip is its one round-to-nearest conversion, inexact above 2^24 exactly
+ * as in oracle/. */
+VS_API int vs_q8_create_nd(const float* base_host, int64_t n_rows, int dim, const vs_q8_encodings* enc,
+                           int device, int64_t id_offset, vs_q8** out);
 VS_API void vs_q8_destroy(vs_q8* h);
 VS_API int64_t vs_q8_num_docs(const vs_q8* h);     /* QnnRunner::getNumDocs   (QnnRunner.h:52) */
 VS_API int vs_q8_dim(const vs_q8* h);              /* QnnRunner::getDim       (QnnRunner.h:50) */

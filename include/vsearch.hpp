@@ -154,9 +154,10 @@ struct ExecutionTiming {  // QnnRunner.h:12-17
 
 class QuantizedRunner {
 public:
-    // enc == nullptr: the runner's hard-coded input / output scales (QnnRunner.cpp:490-521), weights min-max
+    // enc == nullptr: the runner's hard-coded input / output scales (QnnRunner.cpp:490-521), weights min-max.
+    // Any vector length 1 <= dim <= 2048: 128-d documents take vs_q8_create, the others vs_q8_create_nd.
     QuantizedRunner(const std::vector<float>& docs, int64_t rows, int dim, const vs_q8_encodings* enc = nullptr, int device = 0) {
-        check(vs_q8_create(docs.data(), rows, dim, enc, device, 0, &h_));
+        check((dim == 128 ? vs_q8_create : vs_q8_create_nd)(docs.data(), rows, dim, enc, device, 0, &h_));
         out_.resize((size_t)vs_q8_batch(h_) * (size_t)rows);
     }
     ~QuantizedRunner() { vs_q8_destroy(h_); }
