@@ -129,6 +129,7 @@ def lib():
         "vs_bf_create": (i32, [vp, i64, i32, i32, i32, i64, C.POINTER(vp)]),
         "vs_bf_create_nd": (i32, [vp, i64, i32, i32, i32, i64, C.POINTER(vp)]),
         "vs_bf_create_nd_u8": (i32, [vp, i64, i32, i32, i64, C.POINTER(vp)]),
+        "vs_bf_create_nd_u8_metric": (i32, [vp, i64, i32, i32, i32, i64, C.POINTER(vp)]),
         "vs_set_batch": (i32, [vp, i32]),
         "vs_set_precision": (i32, [vp, i32]),
         "vs_ivf_set_metric": (i32, [vp, i32]),
@@ -371,8 +372,8 @@ class BruteForceIndex(_Index):
 
     Any vector length 1 <= d <= 2048: 128-d bases take vs_bf_create (every specialised path), the others
     vs_bf_create_nd (fp32 rows, the general-dimension scan; no sharded calls, no int8 precision).  ``from_u8`` takes
-    uint8 rows instead (vs_bf_create_nd_u8): squared L2, and at dimensions other than 128 a byte copy of the rows beside
-    the fp32 ones, scanned with int8 MFMA for k <= 15 (set_precision 0 / 2; 1 = fp32 rows)."""
+    uint8 rows instead (vs_bf_create_nd_u8_metric): at dimensions other than 128 a byte copy of the rows beside the fp32
+    ones, scanned with int8 MFMA for k <= 15 (set_precision 0 / 2; 1 = fp32 rows), under squared L2 or inner product."""
 
     def __init__(self, base, metric: int = METRIC_L2, device: int = 0, id_offset: int = 0):
         super().__init__()
@@ -385,8 +386,9 @@ class BruteForceIndex(_Index):
         self.d = self.getDim()  # (buffers of every call below are sized by the index's own dimension)
 
     @classmethod
-    def from_u8(cls, base_u8, device: int = 0, id_offset: int = 0):
-        """An index over uint8 rows [N, d] (vs_bf_create_nd_u8)."""
+    def from_u8(cls, base_u8, device: int = 0, id_offset: int = 0, metric: int = METRIC_L2):
+        """An index over uint8 rows [N, d] (vs_bf_create_nd_u8_metric; METRIC_L2 is vs_bf_create_nd_u8).  METRIC_IP: a
+        general index at every d, 128 included, whose byte copy is scanned under inner product for k <= 15."""
         base = np.asarray(base_u8)
         if base.dtype != np.uint8:
             raise ValueError("base_u8 must have dtype uint8")
@@ -396,7 +398,7 @@ class BruteForceIndex(_Index):
         self = cls.__new__(cls)
         _Index.__init__(self)
         self.n, self.d = base.shape
-        _check(lib().vs_bf_create_nd_u8(_p(base), self.n, self.d, device, id_offset, C.byref(self._h)))
+        _check(lib().vs_bf_create_nd_u8_metric(_p(base), self.n, self.d, metric, device, id_offset, C.byref(self._h)))
         self.d = self.getDim()
         return self
 

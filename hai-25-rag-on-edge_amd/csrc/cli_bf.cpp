@@ -14,6 +14,10 @@
 //                                                ids of vs_bf_search_topk, 1 <= k <= 128), for vsearch_ivf's recall; one GPU
 //   a <base> or <query> file whose name ends in .bvecs is read as TEXMEX byte vectors: a byte base becomes an index over
 //   uint8 rows (vs_bf_create_nd_u8), byte queries are converted to float; the output files are the same
+//   ... --metric ip|l2                         : the ranking (default l2), on one GPU: a .fvecs base goes through vs_bf_create /
+//                                                vs_bf_create_nd with the metric, a .bvecs base through
+//                                                vs_bf_create_nd_u8_metric; under ip the results hold the scores q.v,
+//                                                descending, in the same grammar.  Not together with --gpus N > 1
 //   ... --gpus N                               : any form on N GPUs, one process per GPU (forked before HIP starts): the base
 //                                                is row-sharded, per-shard top-(k+1) lists meet in one RCCL all-gather per
 //                                                32 batches (vs_bf_search_sharded); rank 0 writes the files
@@ -118,6 +122,21 @@ void write_metrics(const std::string& path, const RunStats& r) {
 }
 
 vsearch::RankSet g_ranks;
+int g_metric = VS_METRIC_L2;  // --metric
+
+// takes "--metric ip|l2" out of argv like --gpus; false when the flag is not given
+bool take_metric_flag(int& argc, char** argv, int& metric) {
+    for (int i = 1; i < argc; ++i)
+        if (std::string(argv[i]) == "--metric" && i + 1 < argc) {
+            const std::string v = argv[i + 1];
+            if (v != "ip" && v != "l2") throw std::runtime_error("--metric must be ip or l2");
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2;
+            metric = v == "ip" ? VS_METRIC_IP : VS_METRIC_L2;
+            return true;
+        }
+    return false;
+}
 
 bool is_bvecs(const std::string& f) { return f.size() >= 6 && f.compare(f.size() - 6, 6, ".bvecs") == 0; }
 
@@ -134,8 +153,8 @@ bool read_vectors(const std::string& f, std::vector<float>& data, std::vector<ui
 // the index over rows [r0, r1) of a base read by read_vectors
 std::unique_ptr<vsearch::ExactSearch> make_index(const std::vector<float>& f, const std::vector<uint8_t>& bytes, bool byte_base,
                                                  int64_t r0, int64_t r1, int dim, int device) {
-    if (byte_base) return std::make_unique<vsearch::ExactSearch>(bytes.data() + (size_t)r0 * dim, r1 - r0, dim, r0, device);
-    return std::make_unique<vsearch::ExactSearch>(f.data() + (size_t)r0 * dim, r1 - r0, dim, r0, device);
+    if (byte_base) return std::make_unique<vsearch::ExactSearch>(bytes.data() + (size_t)r0 * dim, r1 - r0, dim, r0, device, g_metric);
+    return std::make_unique<vsearch::ExactSearch>(f.data() + (size_t)r0 * dim, r1 - r0, dim, r0, device, g_metric);
 }
 
 bool run_benchmark(const std::string& dataset_name, const std::string& base_file, const std::string& query_file, int k,
@@ -354,7 +373,8 @@ const char* kUsage =
     "       vsearch_bf <base.fvecs> <query.fvecs> <k> <out> [batch]\n"
     "       vsearch_bf <context_binary> <queries.fvecs> <results_dir> <backend.so> <documents.fvecs> <top_k> [batch] [--q8[=...]]\n"
     "       vsearch_bf --groundtruth <base.fvecs> <query.fvecs> <out.ivecs> [k=100]\n"
-    "       (any form but --groundtruth: [--gpus N]; 1 <= k <= 128, on one GPU for k > 15)\n";
+    "       (any form but --groundtruth: [--gpus N]; 1 <= k <= 128, on one GPU for k > 15)\n"
+    "       (any form: [--metric ip|l2], default l2; ip on one GPU only: results hold the scores q.v, descending)\n";
 
 bool file_exists(const char* path) {
     struct stat st;
@@ -401,7 +421,10 @@ int main(int argc, char* argv[]) {
     }
     int world = 1;
     try {
+        take_metric_flag(argc, argv, g_metric);
         world = vsearch::take_gpus_flag(argc, argv);
+        if (g_metric == VS_METRIC_IP && world > 1)
+            throw std::runtime_error("--metric ip is not available together with --gpus N > 1 (the sharded calls refuse a general index)");
     } catch (const std::exception& e) {
         std::cerr << "FATAL ERROR: " << e.what() << "\n" << kUsage;
         return 1;

@@ -90,13 +90,14 @@ struct vs_index {
     int dim_p = 0;
     vs::DevBuf<float> d_nd_qfrag;  // [kMaxMulti][dim_p / 16][2][64][4] scratch of launch_scan_nd
     vs::DevBuf<float> d_nd_qnorm;  // [kMaxMulti][32]
-    // general index made from uint8 rows (vs_bf_create_nd_u8): the rows once more as int8 (x - 128), scanned by
-    // scan_nd_i8_kernel for k <= 15.  Absent when max ||b||^2 >= 2^24: no batch could ever run on it.
+    // general index made from uint8 rows (vs_bf_create_nd_u8, vs_bf_create_nd_u8_metric): the rows once more as int8
+    // (x - 128), scanned by scan_nd_i8_kernel for k <= 15 under the index's metric.  Absent when max ||b||^2 >= 2^24: no batch could ever run on it.
     bool nd_from_u8 = false;
     int dim_b = 0;                   // dim rounded up to 64 bytes
     int32_t nd_bmax = 0;             // max ||b||^2 over the base (< 2^24)
     vs::DevBuf<int8_t> d_nd_u8;      // [n_rows + 64][dim_b], zero padded
-    vs::DevBuf<int32_t> d_nd_rterm;  // [n_rows + 64] sum (b - 128)^2
+    vs::DevBuf<int32_t> d_nd_rterm;  // [n_rows + 64] sum (b - 128)^2 (squared L2 indexes)
+    vs::DevBuf<int32_t> d_nd_rsum;   // [n_rows + 64] sum (b - 128) (inner-product indexes, vs_bf_create_nd_u8_metric)
     vs::DevBuf<int8_t> d_nd_q8frag;  // [kMaxMulti][dim_b / 64][2][64][16] scratch of launch_scan_nd_i8
     vs::DevBuf<int32_t> d_nd_qterm;  // [kMaxMulti][32]
     vs::DevBuf<unsigned long long> d_nd_stats;  // general IVF index from uint8 rows: (query, probe) pairs planned on bytes | on fp32
@@ -536,7 +537,8 @@ int build_u8_copy(vs_index* h, const float* host, int64_t rows, std::vector<int8
 }
 
 // byte copy of a general index made from uint8 rows: int8 (x - 128) rows padded to dim_b bytes, rterm = sum (b - 128)^2
-// over the real dim (dist = qterm + rterm - 2 q'.b', see vs_scan_nd_i8.hip), and max ||b||^2 for the exactness rule
+// over the real dim (dist = qterm + rterm - 2 q'.b', see vs_scan_nd_i8.hip), and max ||b||^2 for the exactness rule.
+// An inner-product brute-force index keeps rsum = sum (b - 128) per row instead of rterm (launch_ivf_nd_i8_rowsum).
 int build_nd_u8_copy(vs_index* h, const uint8_t* rows_u8, int64_t rows) {
     const size_t ld = (size_t)h->dim_b;
     std::vector<int8_t> bytes(((size_t)rows + vs::kScanPadRows) * ld, 0);  // spare rows: block loads are not clamped
@@ -559,10 +561,18 @@ int build_nd_u8_copy(vs_index* h, const uint8_t* rows_u8, int64_t rows) {
     if (bmax >= (int64_t)1 << 24) return VS_OK;  // ||q||^2 + ||b||^2 <= 2^24 fails for every batch: fp32 rows only
     h->nd_bmax = (int32_t)bmax;
     int rc;
-    if ((rc = h->d_nd_u8.alloc(bytes.size())) || (rc = h->d_nd_rterm.alloc(rterm.size())) || (rc = h->d_invalid.alloc((size_t)kMaxMulti)) ||
+    if ((rc = h->d_nd_u8.alloc(bytes.size())) || (rc = h->d_invalid.alloc((size_t)kMaxMulti)) ||
         (rc = h->d_nd_q8frag.alloc((size_t)kMaxMulti * 32 * ld)) || (rc = h->d_nd_qterm.alloc((size_t)kMaxMulti * 32)))
         return rc;
     HIPCHK(hipMemcpy(h->d_nd_u8, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+    if (h->kind == 0 && h->metric == VS_METRIC_IP) {
+        // a brute-force index keeps its metric: the inner-product epilogue needs sum (b - 128) per row, not the L2 term
+        if ((rc = h->d_nd_rsum.alloc(rterm.size()))) return rc;
+        HIPCHK(vs::launch_ivf_nd_i8_rowsum(h->d_nd_u8, h->dim_b, rows, h->d_nd_rsum, nullptr));
+        HIPCHK(hipDeviceSynchronize());
+        return VS_OK;
+    }
+    if ((rc = h->d_nd_rterm.alloc(rterm.size()))) return rc;
     HIPCHK(hipMemcpy(h->d_nd_rterm, rterm.data(), rterm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     return VS_OK;
 }
@@ -674,9 +684,10 @@ int g_nd_force = [] {
 // floats between consecutive device rows of a brute-force index
 inline int64_t row_ld(const vs_index* h) { return h->general ? h->dim_p : vs::kDim; }
 
-// whether a top-k launch on this index takes the byte scan of a general index (scan_nd_i8_kernel)
+// whether a top-k launch on this index takes the byte scan of a general index (scan_nd_i8_kernel, under either metric:
+// the byte copy comes with the row term of the index's metric)
 inline bool nd_u8_path(const vs_index* h, bool force_f32) {
-    return h->general && h->d_nd_u8 && h->precision != 1 && h->metric == VS_METRIC_L2 && !force_f32;
+    return h->general && h->d_nd_u8 && h->precision != 1 && !force_f32 && (h->metric == VS_METRIC_IP ? (bool)h->d_nd_rsum : (bool)h->d_nd_rterm);
 }
 
 // the per-batch scan of an index: scan_kernel on 128-d rows, scan_nd_kernel on a general index -- or, for a top-k launch
@@ -691,6 +702,7 @@ hipError_t scan_any(vs_index* h, const vs::ScanParams& p, int grid, int kcap, in
         bp.bmax = h->nd_bmax;
         bp.q8frag = h->d_nd_q8frag;
         bp.qterm = h->d_nd_qterm;
+        bp.rsum = h->d_nd_rsum;  // (inner product; null on an L2 index)
         return vs::launch_scan_nd_i8(bp, grid, kcap, nqh, s);
     }
     vs::ScanNdParams np{};
@@ -2156,7 +2168,7 @@ int vs_prof_read_launches(vs_index* h, int which, double* ms_out, int64_t cap, i
 
 // ------------------------------------------------------------------------------------- brute force
 static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset, vs_index** out,
-                          bool any_dim, const uint8_t* rows_u8 = nullptr);
+                          bool any_dim, const uint8_t* rows_u8 = nullptr, bool force_general = false);
 int vs_bf_create(const float* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset,
                  vs_index** out) {
     return guarded([&]() -> int { return bf_create_impl(base_host, n_rows, dim, metric, device, id_offset, out, false); });
@@ -2184,8 +2196,42 @@ int vs_bf_create_nd_u8(const uint8_t* base_host, int64_t n_rows, int dim, int de
         return bf_create_impl(f.data(), n_rows, dim, VS_METRIC_L2, device, id_offset, out, true, base_host);
     });
 }
+// ... under a metric.  Squared L2 is vs_bf_create_nd_u8 itself; inner product builds the general index at every dimension,
+// 128 included (the specialised 128-d index has no inner-product byte kernel), with the byte copy and its row sums
+int vs_bf_create_nd_u8_metric(const uint8_t* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset,
+                              vs_index** out) {
+    if (out && base_host && n_rows > 0 && dim >= 1 && dim <= vs::kNdMaxDim && metric == VS_METRIC_L2)
+        return vs_bf_create_nd_u8(base_host, n_rows, dim, device, id_offset, out);
+    return guarded([&]() -> int {
+        if (!out || !base_host || n_rows <= 0) {
+            set_error("vs_bf_create_nd_u8_metric: bad arguments");
+            return VS_ERR_INVALID;
+        }
+        if (dim < 1) {
+            set_error("vs_bf_create_nd_u8_metric: dim must be at least 1");
+            return VS_ERR_INVALID;
+        }
+        if (dim > vs::kNdMaxDim) {
+            set_error("vs_bf_create_nd_u8_metric: dim > 2048 is not compiled in");
+            return VS_ERR_UNSUPPORTED;
+        }
+        if (metric != VS_METRIC_IP) {  // (VS_METRIC_L2 went above)
+            set_error("vs_bf_create_nd_u8_metric: metric must be VS_METRIC_L2 or VS_METRIC_IP");
+            return VS_ERR_INVALID;
+        }
+        if (n_rows + id_offset > std::numeric_limits<int32_t>::max()) {  // (before the float copy of the rows is made)
+            set_error("ids must fit int32");
+            return VS_ERR_UNSUPPORTED;
+        }
+        int rc = check_device(device);
+        if (rc) return rc;
+        std::vector<float> f((size_t)n_rows * dim);
+        for (size_t i = 0; i < f.size(); ++i) f[i] = (float)base_host[i];
+        return bf_create_impl(f.data(), n_rows, dim, VS_METRIC_IP, device, id_offset, out, true, base_host, true);
+    });
+}
 static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset,
-                          vs_index** out, bool any_dim, const uint8_t* rows_u8) {
+                          vs_index** out, bool any_dim, const uint8_t* rows_u8, bool force_general) {
     if (!out || !base_host || n_rows <= 0) {
         set_error(any_dim ? "vs_bf_create_nd: bad arguments" : "vs_bf_create: bad arguments");
         return VS_ERR_INVALID;
@@ -2221,7 +2267,7 @@ static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int m
     h->kind = 0;
     h->device = device;
     h->dim = dim;
-    h->general = dim != vs::kDim || g_nd_force != 0;
+    h->general = dim != vs::kDim || g_nd_force != 0 || force_general;
     h->dim_p = h->general ? vs::nd_dim_p(dim) : dim;
     h->metric = metric;
     h->n_rows = h->n_total = n_rows;

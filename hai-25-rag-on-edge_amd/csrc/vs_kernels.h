@@ -74,7 +74,9 @@ hipError_t launch_scan_nd(const ScanNdParams& p, int grid, int kcap, int nqh, in
 // on s.base_u8 = [n_rows + kScanPadRows][dim_b] bytes (x - 128), dim_b = nd_dim_b(dim), zero padded, with
 // s.rterm[n_rows + 64] = sum (b - 128)^2 per row.  The preparation launch writes the byte queries in MFMA B-fragment
 // order, qterm = sum (q - 128)^2 per query and s.invalid[batch] (0 or 1): 1 unless every query value of the batch is an
-// integer in [0, 255] and max ||q||^2 + bmax <= 2^24; the scan skips such a batch.  L2 only.
+// integer in [0, 255] and max ||q||^2 + bmax <= 2^24; the scan skips such a batch.  Inner product (s.metric == 1, -(q.b)
+// ascending like launch_scan_nd): rsum instead of s.rterm, and the per-query term is 128 sum (q - 128) + 128^2 dim, so
+// that q.b = q'.b' + 128 (sum q' + sum b') + 128^2 dim in int32; the rule and the verdict are the same.
 constexpr int nd_dim_b(int dim) { return (dim + 63) & ~63; }  // whole 64-byte MFMA steps
 struct ScanNdI8Params {
     ScanParams s;
@@ -82,6 +84,8 @@ struct ScanNdI8Params {
     int32_t bmax;            // max over the base of ||b||^2, < 2^24
     int8_t* q8frag;          // scratch [n_batches][dim_b / 64][2][64][16]: fragment (s, h, lane) = bytes Q'[16 h + (lane & 15)][64 s + 16 (lane >> 4) ..]
     int32_t* qterm;          // scratch [n_batches][32]
+    // inner product (s.metric == 1) only, null otherwise: [n_rows + 64] sum (b - 128) per row (launch_ivf_nd_i8_rowsum)
+    const int32_t* rsum;
 };
 hipError_t launch_scan_nd_i8(const ScanNdI8Params& p, int grid, int kcap, int nqh, hipStream_t s);
 
@@ -623,6 +627,7 @@ struct IvfNdI8Params {
 hipError_t launch_ivf_nd_i8_prep(const IvfNdI8Params& p, hipStream_t s);
 hipError_t launch_ivf_nd_i8_scan(const IvfNdI8Params& p, int grid, hipStream_t s);
 // rsum[row] = the sum of the row's dim_b stored bytes (the padding is zero) for row < rows, 0 for the 64 spare entries
+// (also ScanNdI8Params::rsum: the inner-product brute-force byte index builds it with this launch at creation)
 hipError_t launch_ivf_nd_i8_rowsum(const int8_t* vecs_u8, int dim_b, int64_t rows, int32_t* rsum, hipStream_t s);
 
 // ---- wide k (17 <= k <= kIvfNdWideKMax) on a general IVF index (vs_ivf_nd_wide.hip).  The group's first

@@ -1,6 +1,6 @@
 // vs_scan_nd_i8.hip -- the byte scan of a general-dimension index made from uint8 rows (vs_bf_create_nd_u8; gfx950).
 //
-//   scan_nd_i8_kernel<NQH, KCAP> : scan_nd_kernel's kModeTopK contract (vs_scan_nd.hip: partial lists
+//   scan_nd_i8_kernel<NQH, KCAP, IP> : scan_nd_kernel's kModeTopK contract (vs_scan_nd.hip: partial lists
 //                          [batch*32+q][workgroup][kcap], threshold exchange through slots_cur, tau0, run_if, id_offset) on
 //                          rows stored as int8 (x - 128), with v_mfma_i32_16x16x64_i8 (base rows = A operand).  A quarter
 //                          of scan_nd_kernel's row bytes, the same distances.
@@ -22,6 +22,13 @@
 // same integer (< 2^24, so the conversion to float is exact).  Any other batch gets invalid[batch] = 1 and is skipped:
 // the merge reports flags = 2 and the host calls rerun it on the fp32 rows.
 //
+// Inner product (ScanParams::metric == 1, the IP instantiations; vs_bf_create_nd_u8_metric).  The rule is the same: under
+// it every partial sum of q.b is at most (||q||^2 + ||b||^2) / 2 <= 2^23, so the fp32 chain is exact in any order (as in
+// vs_ivf_nd_i8.hip) and equals the int32 product rebuilt from the stored bytes,
+//     q.b = q'.b' + 128 (sum q' + sum b') + 128^2 dim,
+// with qt_ip = 128 sum q' + 128^2 dim per query from the preparation launch (in the qterm buffer) and rsum = sum b' per
+// row (launch_ivf_nd_i8_rowsum).  The scan writes -(float)(q.b): the fp32 scan's bits, -0.0 for a zero product included.
+//
 // Organisation: scan_nd_kernel's.  Nothing in a wave grows with dim: a wave owns a block of kNd8Tiles 16-row tiles and
 // keeps their kNd8Tiles x NQH int32 accumulators resident while it walks the rows in steps of 128 bytes (one line per
 // row, two 16x16x64 MFMAs per tile and query block), with a 64-byte tail step when dim_b / 64 is odd.  Rows and
@@ -38,7 +45,8 @@ constexpr int kNd8BlockRows = kNd8Tiles * kTileRows;  // 64 <= kScanPadRows: a b
 static_assert(kNd8BlockRows <= kScanPadRows, "row blocks are loaded unclamped");
 // (byte_value and kNd8NormLimit, the exactness rule's pieces, are in vs_dev.h: the IVF byte scan shares them)
 
-// grid = n_batches, 256 threads
+// grid = n_batches, 256 threads.  IP: the per-query term is qt_ip = 128 sum q' + 128^2 dim instead of sum q'^2 (same buffer)
+template <bool IP>
 __global__ __launch_bounds__(256) void nd_prep_i8_kernel(const float* __restrict__ q, int64_t q_batch_stride, int nq_valid, int dim,
                                                          int dim_b, int bmax, int8_t* __restrict__ q8frag,
                                                          int32_t* __restrict__ qterm, int32_t* __restrict__ invalid,
@@ -82,7 +90,7 @@ __global__ __launch_bounds__(256) void nd_prep_i8_kernel(const float* __restrict
         for (int i = j; i < dim; i += 8) {
             int xi;
             if (byte_value(src[i], xi)) {
-                t += (xi - 128) * (xi - 128);
+                t += IP ? xi - 128 : (xi - 128) * (xi - 128);
                 n2 += xi * xi;
             }
         }
@@ -92,13 +100,15 @@ __global__ __launch_bounds__(256) void nd_prep_i8_kernel(const float* __restrict
         t += __shfl_xor(t, m);
         n2 += __shfl_xor(n2, m);
     }
+    if (IP) t = 128 * t + 16384 * dim;  // (|128 sum q'| <= 2^25, 128^2 dim <= 2^25; an absent query's term is never ranked)
     if (j == 0) qterm[batch * kMaxBatch + row] = t;
     if (live && n2 > kNd8NormLimit - bmax) bad = true;  // (n2 <= 2048 * 255^2, 0 <= bmax < 2^24: no overflow)
     const int any = __syncthreads_or(bad ? 1 : 0);
     if (threadIdx.x == 0) invalid[batch] = any ? 1 : 0;  // written as 0 or 1: nobody has to clear it before
 }
 
-template <int NQH, int KCAP>
+// IP: the inner-product instantiation -- the same loads and MFMAs; the epilogue rebuilds q.b from the shifted bytes
+template <int NQH, int KCAP, bool IP>
 __global__ __launch_bounds__(kScanThreads, 1) void scan_nd_i8_kernel(const ScanNdI8Params pn) {
     const ScanParams& p = pn.s;
     constexpr int T = kNd8Tiles;
@@ -225,14 +235,19 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_nd_i8_kernel(const ScanN
                 const int64_t rbase = row0 + 16 * t + 4 * g;
                 int rt[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) rt[j] = p.rterm[rbase + j];  // (the terms have 64 spare entries)
+                for (int j = 0; j < 4; ++j) rt[j] = IP ? pn.rsum[rbase + j] : p.rterm[rbase + j];  // (the terms have 64 spare entries)
 #pragma unroll
                 for (int h = 0; h < NQH; ++h) {
                     float d[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        // the integer the fp32 path computes exactly: ||q||^2 + ||b||^2 - 2 q.b
-                        d[j] = (float)(qt[h] + rt[j] - 2 * acc[t][h][j]);
+                        // the integer the fp32 path computes exactly: ||q||^2 + ||b||^2 - 2 q.b, or -(q.b) with
+                        // q.b = q'.b' + 128 (sum q' + sum b') + 128^2 dim (|q'.b'| <= 2^25, |128 (...)| <= 2^26, 128^2 dim <= 2^25;
+                        // a zero product gives -0.0 like the fp32 scan's negation)
+                        if constexpr (IP)
+                            d[j] = -(float)(qt[h] + 128 * rt[j] + acc[t][h][j]);
+                        else
+                            d[j] = (float)(qt[h] + rt[j] - 2 * acc[t][h][j]);
                         if (ragged && rbase + j > last_row) d[j] = VS_INF;
                     }
                     nd_topk_step<KCAP>(d, rbase, p.id_offset, wmin[h], tau[h], ld[h], li[h]);
@@ -254,17 +269,25 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_nd_i8_kernel(const ScanN
 
 template <int NQH, int KCAP>
 static hipError_t launch_scan_nd_i8_t(const ScanNdI8Params& p, int grid, hipStream_t s) {
-    hipLaunchKernelGGL((scan_nd_i8_kernel<NQH, KCAP>), dim3(grid), dim3(kScanThreads), 0, s, p);
+    if (p.s.metric)
+        hipLaunchKernelGGL((scan_nd_i8_kernel<NQH, KCAP, true>), dim3(grid), dim3(kScanThreads), 0, s, p);
+    else
+        hipLaunchKernelGGL((scan_nd_i8_kernel<NQH, KCAP, false>), dim3(grid), dim3(kScanThreads), 0, s, p);
     return hipGetLastError();
 }
 
 hipError_t launch_scan_nd_i8(const ScanNdI8Params& p, int grid, int kcap, int nqh, hipStream_t s) {
-    if (p.dim < 1 || p.dim > kNdMaxDim || p.dim_b != nd_dim_b(p.dim) || !p.q8frag || !p.qterm || !p.s.base_u8 || !p.s.rterm ||
-        !p.s.invalid || p.bmax < 0 || p.bmax >= kNd8NormLimit || p.s.metric != 0 || grid < 1 || grid > kSlotStride ||
+    if (p.dim < 1 || p.dim > kNdMaxDim || p.dim_b != nd_dim_b(p.dim) || !p.q8frag || !p.qterm || !p.s.base_u8 ||
+        (p.s.metric != 0 && p.s.metric != 1) || !(p.s.metric ? p.rsum : p.s.rterm) ||
+        !p.s.invalid || p.bmax < 0 || p.bmax >= kNd8NormLimit || grid < 1 || grid > kSlotStride ||
         (p.s.row_begin & 15) || p.s.n_batches < 1 || p.s.nq_valid < 1 || p.s.nq_valid > kMaxBatch)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nd_prep_i8_kernel, dim3(p.s.n_batches), dim3(256), 0, s, p.s.q, p.s.q_batch_stride, p.s.nq_valid, p.dim, p.dim_b,
-                       p.bmax, p.q8frag, p.qterm, p.s.invalid, p.s.run_if);
+    if (p.s.metric)
+        hipLaunchKernelGGL(nd_prep_i8_kernel<true>, dim3(p.s.n_batches), dim3(256), 0, s, p.s.q, p.s.q_batch_stride, p.s.nq_valid, p.dim,
+                           p.dim_b, p.bmax, p.q8frag, p.qterm, p.s.invalid, p.s.run_if);
+    else
+        hipLaunchKernelGGL(nd_prep_i8_kernel<false>, dim3(p.s.n_batches), dim3(256), 0, s, p.s.q, p.s.q_batch_stride, p.s.nq_valid, p.dim,
+                           p.dim_b, p.bmax, p.q8frag, p.qterm, p.s.invalid, p.s.run_if);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (kcap == 8) return nqh == 1 ? launch_scan_nd_i8_t<1, 8>(p, grid, s) : launch_scan_nd_i8_t<2, 8>(p, grid, s);

@@ -159,6 +159,41 @@ VS_API int vs_bf_create_nd(const float* base_host, int64_t n_rows, int dim, int 
 VS_API int vs_bf_create_nd_u8(const uint8_t* base_host, int64_t n_rows, int dim,
                               int device, int64_t id_offset, vs_index** out);
 
+/* The same under a metric.  Checks, in this order (all but the last need no device; *out is
+ * written on success only): null pointers or n_rows <= 0: VS_ERR_INVALID; dim < 1:
+ * VS_ERR_INVALID; dim > 2048: VS_ERR_UNSUPPORTED; a metric other than VS_METRIC_L2 /
+ * VS_METRIC_IP: VS_ERR_INVALID; ids that do not fit int32: VS_ERR_UNSUPPORTED; no device:
+ * VS_ERR_DEVICE.
+ *
+ * VS_METRIC_L2: the call is vs_bf_create_nd_u8 -- same index, same launches, at dim 128 too.
+ *
+ * VS_METRIC_IP, dim != 128: the general index of vs_bf_create_nd(rows as float, VS_METRIC_IP)
+ * PLUS the byte rows vs_bf_create_nd_u8 stores (int8 (x - 128), padded to 64 bytes) and one
+ * int32 per row, the sum of its stored bytes; not kept when max ||b||^2 >= 2^24, as under L2.
+ * VS_METRIC_IP, dim == 128: the specialised 128-d index has no inner-product byte kernel, so the
+ * creator builds the GENERAL form here as well, with the byte copy, and the same kernels serve
+ * SIFT.  The sharded and virtual-shard calls and every vs_ivf_* call refuse this index like any
+ * general index; data that needs those calls under inner product goes through vs_bf_create on
+ * float rows.
+ *
+ * For k <= 15 under precision 0 or 2, vs_bf_search, vs_bf_search_dev, vs_bf_search_dev_multi,
+ * vs_bf_search_topk and vs_bf_search_topk_dev_multi run on the byte rows under inner product.
+ * The exactness rule above applies unchanged, per batch: every query value an integer in
+ * [0, 255] and max over the batch of ||q||^2 + max over the base of ||b||^2 <= 2^24, checked on
+ * the device in integers.  Every partial sum of q.b is then at most (||q||^2 + ||b||^2) / 2 <=
+ * 2^23, so the fp32 chain is exact in any order and equals the int32 product the byte scan
+ * rebuilds, q.b = q'.b' + 128 (sum q' + sum b') + 128^2 dim with x' = x - 128.  Any other batch
+ * is skipped: the *_dev calls report flags == 2, the host calls rerun it on the fp32 rows.
+ * Precision 1 forces the fp32 rows; precision 2 returns VS_ERR_UNSUPPORTED when the byte copy
+ * was not kept.  k >= 16 and vs_bf_scores_dev read the fp32 rows, as under L2.
+ *
+ * Outputs are the inner-product ones of vs_bf_create_nd: the *_dev calls return s = -(q.v)
+ * ascending by (s, id), an exactly zero product as -0.0; the host calls return q.v descending,
+ * equal scores in ascending id, no tie replay.  Nothing ever returns a number that differs from
+ * what vs_bf_create_nd(rows as float, VS_METRIC_IP) returns for the same call. */
+VS_API int vs_bf_create_nd_u8_metric(const uint8_t* base_host, int64_t n_rows, int dim, int metric,
+                                     int device, int64_t id_offset, vs_index** out);
+
 /* Fixed model batch, like QnnRunner::getBatchSize (QnnRunner.h:37); 1..32, default 32.
  * Larger query sets are processed in batches of this size, the last one
  * zero-padded (main.cpp:206-211). */

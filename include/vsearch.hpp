@@ -83,11 +83,12 @@ struct Result {  // cpu_baseline.cpp:13-19
 
 // Any vector length 1 <= dim <= 2048: 128-d bases take vs_bf_create, the others vs_bf_create_nd (a general index:
 // one GPU, fp32 rows; the sharded calls refuse it with the library's message).  uint8 rows take vs_bf_create_nd_u8:
-// squared L2, and at dimensions other than 128 a byte copy beside the fp32 rows, scanned with int8 MFMA for k <= 15.
+// at dimensions other than 128 a byte copy beside the fp32 rows, scanned with int8 MFMA for k <= 15; under VS_METRIC_IP
+// (vs_bf_create_nd_u8_metric) at 128 too, as a general index.
 class ExactSearch {
 public:
-    ExactSearch(const uint8_t* rows_u8, int64_t rows, int dim, int64_t id_offset = 0, int device = 0) {
-        check(vs_bf_create_nd_u8(rows_u8, rows, dim, device, id_offset, &h_));
+    ExactSearch(const uint8_t* rows_u8, int64_t rows, int dim, int64_t id_offset = 0, int device = 0, int metric = VS_METRIC_L2) {
+        check(vs_bf_create_nd_u8_metric(rows_u8, rows, dim, metric, device, id_offset, &h_));
     }
     ExactSearch(const std::vector<float>& base, int rows, int dim, int device = 0, int metric = VS_METRIC_L2) {
         check((dim == 128 ? vs_bf_create : vs_bf_create_nd)(base.data(), rows, dim, metric, device, 0, &h_));
