@@ -5,6 +5,7 @@
 #include "vs_sink.h"
 #include "vs_merge.h"
 #include "vs_wide_select.h"
+#include "vs_ring.h"
 #include <type_traits>
 #include <algorithm>
 
@@ -232,10 +233,10 @@ __global__ __launch_bounds__(256) void ivf_coarse_mfma_kernel(const float* __res
     auto dma_tile = [&](const int t, const int par) __attribute__((always_inline)) {
         const unsigned voff = voff0 + (unsigned)t * (64u * kDim * 4u);
         const unsigned dst = lds_w + (unsigned)par * 8192u;
-        // (no instruction offset: it would move the LDS address as well as the global one)
-#define VS_CDMA(c8) asm volatile("s_add_u32 m0, %0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dst), "v"(voff + 64u * (c8)), "s"(cbytes), "n"((c8) * 1024) : "memory", "scc")
-        VS_CDMA(0); VS_CDMA(1); VS_CDMA(2); VS_CDMA(3); VS_CDMA(4); VS_CDMA(5); VS_CDMA(6); VS_CDMA(7);
-#undef VS_CDMA
+        unsigned vo[8];
+#pragma unroll
+        for (int c8 = 0; c8 < 8; ++c8) vo[c8] = voff + 64u * c8;
+        ring_dma_rows<false>(dst, cbytes, vo);
     };
     f32x4 d_out[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};  // the wave's scores of a tile: 16 centroids x 2 x 16 queries
     auto store_scores = [&](int t) {
@@ -1429,6 +1430,15 @@ __global__ __launch_bounds__(kIvfWideF32Threads) void ivf_scan_wide_f32_kernel(c
     __shared__ float tau_s[kIvfWideSlots];
     __shared__ float qn_s[kIvfWideSlots];
     constexpr int WAVES = kIvfWideF32Threads / 64, NT = kIvfWideTiles, PF = 4;
+    // Hand-counted waits of the column-block loop (compute(), below).  A column block's query fragments are kQPieces
+    // LDS-DMA instructions.  A record's first block requests, after its wait, the next record's rows and the slot
+    // entries of the one after: NT * 9 + PF loads that the COMPILER emits (eight fragments and a norm vector per tile,
+    // PF entries).  The waits count kRecCounted of them, two fewer than the nominal figure: a lower bound only makes
+    // a wait retire two loads more than it must, while a count above what was emitted would let it pass before the
+    // block's own fragments have landed -- the MFMAs would read stale LDS.
+    constexpr int kQPieces = 8;
+    constexpr int kRecCounted = NT * 9 + PF - 2;
+    static_assert(NT * 9 + PF >= 20 && kRecCounted <= NT * 9 + PF, "the waits count on loads that issue_rows and issue_slots really emit");
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, g = lane >> 4;
@@ -1517,10 +1527,10 @@ __global__ __launch_bounds__(kIvfWideF32Threads) void ivf_scan_wide_f32_kernel(c
         const int qg = qbase + ql;
         const unsigned voff = (unsigned)((long long)(qg >> 5) * p.q_batch_bytes) + (unsigned)((qg & 31) * (kDim * 4) + 16 * g);
         const unsigned dst = lds_w + (unsigned)par * 8192u;
-        // (no instruction offset: it would move the LDS address as well as the global one)
-#define VS_QDMA(c8) asm volatile("s_add_u32 m0, %0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dst), "v"(voff + 64u * (c8)), "s"(qbytes), "n"((c8) * 1024) : "memory", "scc")
-        VS_QDMA(0); VS_QDMA(1); VS_QDMA(2); VS_QDMA(3); VS_QDMA(4); VS_QDMA(5); VS_QDMA(6); VS_QDMA(7);
-#undef VS_QDMA
+        unsigned vo[8];
+#pragma unroll
+        for (int c8 = 0; c8 < 8; ++c8) vo[c8] = voff + 64u * c8;
+        ring_dma_rows<false>(dst, qbytes, vo);
     };
     auto score = [&](const Rec& rc, const f32x4 (&a)[NT][8], const f32x4 (&bn)[NT], const int par, const int ql, const bool live) __attribute__((always_inline)) {
         const f32x4* qb = reinterpret_cast<const f32x4*>(f32_smem + wave * 16384 + par * 8192) + lane;
@@ -1581,15 +1591,15 @@ __global__ __launch_bounds__(kIvfWideF32Threads) void ivf_scan_wide_f32_kernel(c
             const bool in_rec = cb + 16 < rc.nq, any = in_rec || rn.nq > 0;  // wave-uniform
             if (in_rec) ql_next = slot_of(rc, sq, cb + 16);
             else if (rn.nq > 0) ql_next = slot_of(rn, sqn, 0);
-            // What is younger than this block's DMA: the eight loads of the next block's, and -- if the block before this one
-            // was a record's first -- the 22 row and slot loads it requested after its wait (20 counted: a margin of two).
+            // What is younger than this block's DMA: the kQPieces of the next block's, and -- if the block before this one
+            // was a record's first -- the row and slot loads it requested after its wait (kRecCounted of them counted).
             if (any) {
                 dma(ql_next, par ^ 1);
-                if (young) asm volatile("s_waitcnt vmcnt(28)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+                if (young) wait_vm<kRecCounted + kQPieces>();
+                else wait_vm<kQPieces>();
             } else {
-                if (young) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (young) wait_vm<kRecCounted>();
+                else wait_vm<0>();
             }
             young = false;
             if (cb == 0) {

@@ -31,6 +31,7 @@
 #include <type_traits>
 #include <algorithm>
 #include "vs_sink.h"
+#include "vs_ring.h"
 
 namespace vs {
 
@@ -43,14 +44,9 @@ namespace vs {
 // result a lane holds ONE query column (l & 15) and four base rows (4 g + reg): the top-k state of
 // a query is lane-private and needs no cross-lane traffic until the workgroup is done.
 //
-// Data path.  Every wave owns a private ring of DEPTH tile slots in LDS and fills them with
-// LDS-DMA (global_load_lds_dwordx4: one wave-instruction moves two whole 512-byte rows, fully
-// coalesced, no VGPR destination).  The only VMEM operations in the loop are those DMA pieces and
-// they are counted by hand (s_waitcnt vmcnt(9*(DEPTH-1))): nothing drains the queue, and no
-// barrier is needed because a wave reads only what it loaded itself.  LDS image of a slot:
-// 16 rows x 512 B with 16-byte chunk c of row r stored at chunk c ^ r (XOR applied to the DMA
-// *source* address, the LDS side stays lane-linear), which makes the ds_read_b128 of the A
-// fragments bank-conflict free; followed by the tile's squared norms.
+// Data path.  Every wave owns a private ring of tile slots in LDS and fills them with LDS-DMA
+// (one wave-instruction moves two whole 512-byte rows, fully coalesced, no VGPR destination),
+// counted by hand: vs_ring.h has the slot layout, the swizzle and the bookkeeping.
 //
 // Everything a batch needs is inside this one launch:
 //   * query zero-padding (main.cpp:206-211) and squared norms in the reference's summation order
@@ -66,9 +62,7 @@ namespace vs {
 //   * the workgroup merge: surviving candidates (d < tau0) are compacted into LDS and ranked with
 //     DPP reductions; the per-workgroup sorted lists go to the cross-workgroup merge kernel.
 // ------------------------------------------------------------------------------------------------
-constexpr int kSlotBytes = kTileRows * kDim * 4 + 256;  // 16 rows + 64 norms
-constexpr int kDepth = 2;
-constexpr int kRingBytes = kScanWaves * kDepth * kSlotBytes;  // 135168
+constexpr int kRingBytes = kScanWaves * kRingWaveBytes;  // 135168
 constexpr int kQStageBytes = 32 * kDim * 4;                  // 16384
 constexpr int kScratchBytes = 2048;
 constexpr int kMergeSmall = 32;     // entries per query of the small workgroup-merge buffer
@@ -129,31 +123,17 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
     const int g = lane >> 4;
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
-    char* ring = smem + wave * (kDepth * kSlotBytes);
-    // DMA source mapping: piece j (0..7) writes LDS chunks [64 j, 64 j + 64) of the slot.
-    //   fp32: lane l lands at row 2 j + (l >> 5), stored chunk (l & 31)  <-  source chunk (l & 31) ^ row
-    //   int8: 128-byte rows, piece j moves rows 8j..8j+7; lane l lands at row 8j + (l >> 3), stored chunk l & 7
-    //         <-  source chunk (l & 7) ^ ((row >> 1) & 7)
-    // (the XOR makes the ds_read_b128 of the A fragments conflict free).  The per-lane byte offsets inside a
-    // tile are fixed, so a DMA is "scalar tile base + 32-bit lane offset" with no address arithmetic in the
-    // loop: while the other wave of the SIMD streams MFMAs, every extra VALU instruction here costs about one
-    // MFMA slot.  Rows past row_end are fetched unclamped (every row array has kScanPadRows spare rows) and
-    // masked in the epilogue of the last tile.
+    char* ring = smem + wave * kRingWaveBytes;
+    // DMA source offsets (vs_ring.h).  The pieces go out through the builtin here, not as vs_ring.h's instructions:
+    // this kernel serves five modes and two row formats, and its query staging uses the builtin as well, so the
+    // compiler writes M0 itself.
     unsigned voff[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        if (PREC == 0) {
-            const int row_in = 2 * j + (lane >> 5);
-            voff[j] = (unsigned)(row_in * 512 + 16 * ((lane & 31) ^ row_in));
-        } else {
-            const int row_in = 8 * j + (lane >> 3);
-            voff[j] = (unsigned)(row_in * 128 + 16 * ((lane & 7) ^ ((row_in >> 1) & 7)));
-        }
-    }
+    if (PREC == 0) ring_src_offsets_f32(lane, voff);
+    else ring_src_offsets_i8(lane, voff);
     const unsigned voff_n = (unsigned)lane * 4u;
     auto issue_tile = [&](int tile, int slot) __attribute__((always_inline)) {
         const int64_t row0 = p.row_begin + (int64_t)tile * TR;
-        char* dst = ring + slot * kSlotBytes;
+        char* dst = ring + slot * kRingSlotBytes;
         const char* tb = PREC ? reinterpret_cast<const char*>(p.base_u8) + row0 * kDim
                               : reinterpret_cast<const char*>(p.base) + row0 * (kDim * 4);
 #pragma unroll
@@ -169,7 +149,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
         unsigned vn = voff_n;
         asm volatile("" : "+v"(vn));
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(nb + vn),
-                                         (__attribute__((address_space(3))) void*)(dst + 8192), 4, 0, 0);
+                                         (__attribute__((address_space(3))) void*)(dst + kRingTermOffset), 4, 0, 0);
     };
 
     // Tiles of the workgroup's chunk are handed out through an LDS ticket counter, so a wave that
@@ -216,7 +196,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
     };
     if (tid == 0) lds_ticket[0] = 2 * kScanWaves;
     if (tid < 32) lds_cnt[tid] = 0;
-    asm volatile("s_waitcnt vmcnt(18)" ::: "memory");  // the two query pieces have landed (two tiles follow)
+    wait_vm<2 * kRingPieces>();  // the two query pieces have landed (two tiles follow)
     lds_barrier();
     // squared norms in the reference's AVX2 order (8 FMA lanes, then r0+...+r7): threads 0..255
     if (tid < 256) {
@@ -326,26 +306,15 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
             li[h][j] = -1;
         }
 
-    // distances of one tile: d[rg][h][j] for query column 16 h + r, base rows 16 rg + 4 g + j
-    // LDS byte offsets of this lane's A fragments inside slot 0 of its wave's ring (slot 1: + kSlotBytes, an
-    // immediate once the slot is a compile-time constant): no address arithmetic in the loop
-    unsigned fa[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        if (PREC == 0) {
-            fa[c] = (unsigned)(wave * (kDepth * kSlotBytes) + r * 512 + (((4 * c + g) ^ r) << 4));
-        } else {
-            // c = 2 rg + half: row 16 rg + r, chunk (4 half + g) ^ ((row >> 1) & 7)
-            const int row_in = 16 * (c >> 1) + r;
-            fa[c] = (unsigned)(wave * (kDepth * kSlotBytes) + row_in * 128 + ((((c & 1) * 4 + g) ^ ((row_in >> 1) & 7)) << 4));
-        }
-    }
-    const unsigned fa_n = (unsigned)(wave * (kDepth * kSlotBytes) + 8192 + 16 * g);  // norms / row terms of rows 4g..4g+3 (+16 rg)
+    // LDS byte offsets of this lane's A fragments and row terms in slot 0 of its wave's ring: no address arithmetic in the loop
+    unsigned fa[8], fa_n;
+    if (PREC == 0) ring_frag_offsets_f32(wave * kRingWaveBytes, r, g, fa, fa_n);
+    else ring_frag_offsets_i8(wave * kRingWaveBytes, r, g, fa, fa_n);
     // distances of one tile: d[rg][h][j] for query column 16 h + r, base rows 16 rg + 4 g + j
     // after_frags(): called once the tile's fragments have been requested from LDS (the caller waits for them and may
     // then refill the slot while the MFMAs run)
     auto tile_distances = [&](int tt, int slot, float (&d)[NRG][NQH][4], auto after_frags) __attribute__((always_inline)) {
-        const char* src = smem + slot * kSlotBytes;
+        const char* src = smem + slot * kRingSlotBytes;
         if (PREC == 0) {
             f32x4 a[8];
 #pragma unroll
@@ -536,7 +505,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
                         for (int j = 0; j < 4; ++j) w[rg][h][j] = VS_INF;
             }
         };
-        asm volatile("s_waitcnt vmcnt(9)" ::: "memory");  // A landed (B follows)
+        wait_vm<kRingPieces>();  // A landed (B follows)
         VS_STAMP(11);
         tile_distances(min(t_a, tlast), 0, wk[0], [] {});
         VS_STAMP(12);
@@ -563,7 +532,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
             __hip_atomic_store(slots + qx * kSlotStride + blockIdx.x, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         VS_STAMP(2);
-        asm volatile("s_waitcnt vmcnt(9)" ::: "memory");  // B landed (C, and on wave 1 the store, follow)
+        wait_vm<kRingPieces>();  // B landed (C, and on wave 1 the store, follow)
         tile_distances(min(t_b, tlast), 1, wk[1], [] {});
         kill(t_b >= tile1, wk[1]);
         VS_STAMP(7);
@@ -586,17 +555,18 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
         issue_or_stage(t_d, 1);  // queue: C loads(4) D
         int t_e = t_d;
         if (NKEEP == 3) {
-            asm volatile("s_waitcnt vmcnt(13)" ::: "memory");  // C landed
+            wait_vm<kRingPieces + 4>();  // C landed (the four loads and D follow)
             VS_STAMP(9);
             tile_distances(min(t_c, tlast), 0, wk[NKEEP - 1], [] {});
             kill(t_c >= tile1, wk[NKEEP - 1]);
             VS_STAMP(8);
             t_e = next_ticket();
             issue_or_stage(t_e, 0);  // queue: loads(4) D E
-            asm volatile("s_waitcnt vmcnt(18)" : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3)::"memory");  // the minima are here
+            wait_vm<2 * kRingPieces>();  // the minima are here
         } else {
-            asm volatile("s_waitcnt vmcnt(9)" : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3)::"memory");  // minima (and C) are here
+            wait_vm<kRingPieces>();  // minima (and C) are here
         }
+        tie_loaded(v0), tie_loaded(v1), tie_loaded(v2), tie_loaded(v3);
         VS_STAMP(10);
         // A workgroup that runs ahead of the others would find most slots still unpublished (+inf), i.e. a loose or
         // infinite bound, and then insert a large part of what it scans.  It re-reads its rows of minima until at
@@ -662,7 +632,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
     // (written per slot so that the slot is a compile-time constant: LDS offsets become immediates)
     auto step = [&](const int sl) __attribute__((always_inline)) {
         const int t_new = next_ticket();
-        asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
+        wait_vm<kRingPieces>();
         float d[NRG][NQH][4];
         // the slot is refilled as soon as its fragments sit in registers, before the MFMAs: two tiles in flight
         tile_distances(t_cur, sl, d, [&] {
@@ -755,12 +725,11 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
 
 
 // ------------------------------------------------------------------------------------------------
-// Wide exact-int8 scan (see WideParams).  The data path is the PREC = 1 path of scan_kernel: per-wave ring of two
-// 64-row tile slots filled by LDS-DMA, XOR-swizzled so that the A fragments read conflict free, hand-counted vmcnt.
-// What differs: NQH query column blocks per pass (the B operands come straight from global memory, prepared by
-// seed_qnorm_kernel), the bound is fixed (launch_seed), survivors go to global candidate lists, and the tile ticket
-// runs over all passes of the launch (ticket = pass * T + n), so a wave slides from one pass into the next without
-// meeting anybody: the kernel has one barrier (ticket initialisation).
+// Wide exact-int8 scan (see WideParams).  The data path is the PREC = 1 path of scan_kernel: the per-wave ring of
+// vs_ring.h with 64-row byte tiles.  What differs: NQH query column blocks per pass (the B operands come straight from
+// global memory, prepared by seed_qnorm_kernel), the bound is fixed (launch_seed), survivors go to global candidate
+// lists, and a wave walks the passes of the launch on its own (next_tile): it slides from one pass into the next without
+// meeting anybody, and the kernel has no barrier.
 // ------------------------------------------------------------------------------------------------
 constexpr int kWideLds = kRingBytes + 64;
 
@@ -769,7 +738,6 @@ __global__ __launch_bounds__(kScanThreads, NQH <= 8 ? 2 : 1) void scan_i8w_kerne
     typedef int i32x4 __attribute__((ext_vector_type(4)));
     constexpr int TR = 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int* lds_ticket = reinterpret_cast<int*>(smem + kRingBytes);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, g = lane >> 4;
@@ -778,37 +746,9 @@ __global__ __launch_bounds__(kScanThreads, NQH <= 8 ? 2 : 1) void scan_i8w_kerne
     const int T = (tiles_total - (int)blockIdx.x + G - 1) / G;  // tiles of this workgroup per pass (grid <= tiles_total)
     const int NB = NQH / p.bpb;                                  // batches per pass
     const int n_pass = (p.n_batches + NB - 1) / NB;
-    (void)lds_ticket;
     // a wave takes whole passes, and a contiguous range of the tiles of the passes that do not deal evenly to the 8 waves:
     // see scan_f32s_kernel.  No shared ticket, no barrier.
     const int n_whole = n_pass & ~(kScanWaves - 1), n_rest = n_pass - n_whole;
-    char* ring = smem + wave * (kDepth * kSlotBytes);
-    unsigned voff[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int row_in = 8 * j + (lane >> 3);
-        voff[j] = (unsigned)(row_in * 128 + 16 * ((lane & 7) ^ ((row_in >> 1) & 7)));
-    }
-    const unsigned voff_n = (unsigned)lane * 4u;
-    // LDS-DMA written as instructions (see scan_f32s_kernel): no vector instruction per piece
-    const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)ring);
-    auto issue_tile = [&](int tile, int slot) __attribute__((always_inline)) {
-        const int64_t row0 = (int64_t)tile * TR;
-        const unsigned dst = ring_lds + (unsigned)(slot * kSlotBytes);
-        const char* tb = reinterpret_cast<const char*>(p.base_u8) + row0 * kDim;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            asm volatile("s_add_u32 m0, %0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dst), "v"(voff[j]), "s"(tb), "n"(j * 1024) : "memory", "scc");
-        const char* nb = reinterpret_cast<const char*>(p.rterm + row0);
-        asm volatile("s_add_u32 m0, %0, 8192\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" ::"s"(dst), "v"(voff_n), "s"(nb) : "memory", "scc");
-    };
-    unsigned fa[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const int row_in = 16 * (c >> 1) + r;
-        fa[c] = (unsigned)(wave * (kDepth * kSlotBytes) + row_in * 128 + ((((c & 1) * 4 + g) ^ ((row_in >> 1) & 7)) << 4));
-    }
-    const unsigned fa_n = (unsigned)(wave * (kDepth * kSlotBytes) + 8192 + 16 * g);
     int it_u = wave - kScanWaves, it_n = 0, it_end = 0, it_pass = 0;
     int rem_pos = (int)((long long)wave * n_rest * T / kScanWaves), rem_end = (int)((long long)(wave + 1) * n_rest * T / kScanWaves);
     auto next_tile = [&](int& pass_out) __attribute__((always_inline)) -> int {
@@ -830,6 +770,18 @@ __global__ __launch_bounds__(kScanThreads, NQH <= 8 ? 2 : 1) void scan_i8w_kerne
         pass_out = it_pass;
         return (int)blockIdx.x + (it_n++) * G;
     };
+    char* ring = smem + wave * kRingWaveBytes;
+    unsigned voff[8];
+    ring_src_offsets_i8(lane, voff);
+    const unsigned voff_n = (unsigned)lane * 4u;
+    const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)ring);
+    auto issue_tile = [&](int tile, int slot) __attribute__((always_inline)) {
+        const int64_t row0 = (int64_t)tile * TR;
+        ring_issue_tile<false>(ring_lds + (unsigned)(slot * kRingSlotBytes), reinterpret_cast<const char*>(p.base_u8) + row0 * kDim,
+                               reinterpret_cast<const char*>(p.rterm + row0), voff, voff_n);
+    };
+    unsigned fa[8], fa_n;
+    ring_frag_offsets_i8(wave * kRingWaveBytes, r, g, fa, fa_n);
 
     // per-pass state: B operands of the NQH column blocks, the queries' constant terms and integer bounds.
     // d = qt + rt - 2 acc < tau  <=>  2 acc - rt > qt - tau =: thr  (the hot loop never forms d)
@@ -869,12 +821,12 @@ __global__ __launch_bounds__(kScanThreads, NQH <= 8 ? 2 : 1) void scan_i8w_kerne
         if (pass_cur != have_pass) {  // wave-uniform: this wave enters a new pass (four batches: the drain is amortised)
             load_pass(pass_cur);
             have_pass = pass_cur;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // operands are here (and so are both staged tiles)
+            wait_vm<0>();  // operands are here (and so are both staged tiles)
         }
         int pass_new;
         const int tile_new = next_tile(pass_new);
-        asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-        const char* src = smem + sl * kSlotBytes;
+        wait_vm<kRingPieces>();
+        const char* src = smem + sl * kRingSlotBytes;
         i32x4 a0[4], a1[4], rtv[4];
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg) {
@@ -954,7 +906,7 @@ __global__ __launch_bounds__(kScanThreads, NQH <= 8 ? 2 : 1) void scan_i8w_kerne
         if (pass_cur >= n_pass) break;
         step(1);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // retire the tail prefetches before the wave ends
+    wait_vm<0>();  // retire the tail prefetches before the wave ends
     sink_bin_wave(p.sink, (int)blockIdx.x * kScanWaves + wave, wbase, lane);  // no separate binning launch
 }
 
@@ -978,7 +930,6 @@ __global__ __launch_bounds__(kScanThreads, NB == 1 ? 2 : 1) void scan_f32s_kerne
     constexpr int NH = 2 * NB;  // 16-query column blocks per pass
     constexpr int TR = kTileRows;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int* lds_ticket = reinterpret_cast<int*>(smem + kRingBytes);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, g = lane >> 4;
@@ -986,7 +937,6 @@ __global__ __launch_bounds__(kScanThreads, NB == 1 ? 2 : 1) void scan_f32s_kerne
     const int G = (int)gridDim.x;
     const int T = (tiles_total - (int)blockIdx.x + G - 1) / G;  // tiles of this workgroup per batch (grid <= tiles_total)
     const int n_pass = (p.n_batches + NB - 1) / NB;
-    (void)lds_ticket;
     // Work of a wave = whole passes, not tiles dealt one by one: a pass costs its operand fetch and a drain on entry (1.3 us
     // with one batch per pass, 6.6 us with two), so a wave should enter as few passes as possible.  The workgroup's passes
     // are dealt whole as far as they deal evenly to the 8 waves (the first n_pass & ~7); the tiles of the n_rest others,
@@ -994,34 +944,10 @@ __global__ __launch_bounds__(kScanThreads, NB == 1 ? 2 : 1) void scan_f32s_kerne
     // two passes): 16 passes -> a wave takes 2 whole passes instead of entering all 16; 10 passes -> one whole pass and a
     // quarter of another; 5 passes -> 5/8 of a pass in at most two entries instead of an eighth of each of the five.
     // No shared ticket, no barrier: waves never meet.
+    // (This walk is written out in scan_i8w_kernel as well, on purpose.  As a struct in vs_ring.h -- the compiler then
+    // optimises the walk on its own before it inlines it -- both kernels came out with four more VGPRs and about twenty more
+    // vector instructions, and the byte scan measured 0.35 % slower: profiles/ring_refactor_ab.txt.)
     const int n_whole = n_pass & ~(kScanWaves - 1), n_rest = n_pass - n_whole;  // passes taken whole / shared out by range
-    char* ring = smem + wave * (kDepth * kSlotBytes);
-    unsigned voff[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int row_in = 2 * j + (lane >> 5);
-        voff[j] = (unsigned)(row_in * 512 + 16 * ((lane & 31) ^ row_in));
-    }
-    const unsigned voff_n = (unsigned)lane * 4u;
-    // LDS-DMA written as instructions: "scalar tile base + this lane's 32-bit offset", M0 = the slot's LDS address + the
-    // piece (one wait state between the scalar write of M0 and the instruction that reads it).  (Through the builtin every piece cost two vector instructions -- a register copy and the M0 value read
-    // back from a spilled scalar -- and a vector instruction costs this kernel about 8 cycles of MFMA pipe.)
-    const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)ring);
-    auto issue_tile = [&](int tile, int slot) __attribute__((always_inline)) {
-        const int64_t row0 = (int64_t)tile * TR;
-        const unsigned dst = ring_lds + (unsigned)(slot * kSlotBytes);
-        const char* tb = reinterpret_cast<const char*>(p.base) + row0 * (kDim * 4);
-        static_assert(VS_ROW_CPOL == 2, "the row pieces are issued with the nt policy");
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            asm volatile("s_add_u32 m0, %0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt" ::"s"(dst), "v"(voff[j]), "s"(tb), "n"(j * 1024) : "memory", "scc");
-        const char* nb = reinterpret_cast<const char*>(p.bnorm + row0);
-        asm volatile("s_add_u32 m0, %0, 8192\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" ::"s"(dst), "v"(voff_n), "s"(nb) : "memory", "scc");
-    };
-    unsigned fa[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) fa[c] = (unsigned)(wave * (kDepth * kSlotBytes) + r * 512 + (((4 * c + g) ^ r) << 4));
-    const unsigned fa_n = (unsigned)(wave * (kDepth * kSlotBytes) + 8192 + 16 * g);
     // this wave's position: whole pass it_u, then [rem_pos, rem_end) of the remaining passes' tiles; inside a pass tile
     // index it_n of the workgroup's T, up to it_end
     int it_u = wave - kScanWaves, it_n = 0, it_end = 0, it_pass = 0;
@@ -1045,11 +971,24 @@ __global__ __launch_bounds__(kScanThreads, NB == 1 ? 2 : 1) void scan_f32s_kerne
         pass_out = it_pass;
         return (int)blockIdx.x + (it_n++) * G;
     };
+    char* ring = smem + wave * kRingWaveBytes;
+    unsigned voff[8];
+    ring_src_offsets_f32(lane, voff);
+    const unsigned voff_n = (unsigned)lane * 4u;
+    const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)ring);
+    auto issue_tile = [&](int tile, int slot) __attribute__((always_inline)) {
+        const int64_t row0 = (int64_t)tile * TR;
+        static_assert(VS_ROW_CPOL == 2, "the row pieces are issued with the nt policy");
+        ring_issue_tile<true>(ring_lds + (unsigned)(slot * kRingSlotBytes), reinterpret_cast<const char*>(p.base) + row0 * (kDim * 4),
+                              reinterpret_cast<const char*>(p.bnorm + row0), voff, voff_n);
+    };
+    unsigned fa[8], fa_n;
+    ring_frag_offsets_f32(wave * kRingWaveBytes, r, g, fa, fa_n);
 
     // per-batch state: the 32 queries as B operands (qf[h][c][i] = Q[16 h + r][16 c + 4 g + i]), their norms and bounds.
     // The loads are inline asm on purpose: the compiler does not know them as memory operations, so it puts no
     // s_waitcnt of its own in front of their first use (it would be vmcnt(0): a drain of the tile queue in every
-    // step); the hand-counted waits of the tile loop cover them.  A padding query (main.cpp:206-211) reads row 0 and
+    // step); the wait at pass entry covers them, and every loaded register is tied behind it (vs_ring.h).  A padding query (main.cpp:206-211) reads row 0 and
     // is masked where candidates are taken: its MFMA column influences nothing else.
     f32x4 qf[NH][8];
     float qn[NH], tau[NH], thr[NH];
@@ -1065,14 +1004,9 @@ __global__ __launch_bounds__(kScanThreads, NB == 1 ? 2 : 1) void scan_f32s_kerne
             // fragment order (launch_seed): 1 KB per instruction in one piece
             const float* src = p.qfrag + (((int64_t)batch * 2 + (h & 1)) * 8 * 64 + lane) * 4;
 #pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const float* pc = src + c * 64 * 4;
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qf[h][c]) : "v"(pc) : "memory");
-            }
-            const float* pn = p.qnorm + qglob[h];
-            const float* pt = p.tau0 + qglob[h];
-            asm volatile("global_load_dword %0, %1, off" : "=v"(qn[h]) : "v"(pn) : "memory");
-            asm volatile("global_load_dword %0, %1, off" : "=v"(tau[h]) : "v"(pt) : "memory");
+            for (int c = 0; c < 8; ++c) asm_load_b128(qf[h][c], src + c * 64 * 4);
+            asm_load_b32(qn[h], p.qnorm + qglob[h]);
+            asm_load_b32(tau[h], p.tau0 + qglob[h]);
         }
     };
 
@@ -1091,9 +1025,10 @@ __global__ __launch_bounds__(kScanThreads, NB == 1 ? 2 : 1) void scan_f32s_kerne
             //  but delays that refill by the tile's arithmetic: measured slower, 12.3 vs 11.6 us per batch on a 125 K-row shard)
             load_pass(pass_cur);
             have_pass = pass_cur;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // operands are here (and so are both staged tiles)
+            wait_vm<0>();  // operands are here (and so are both staged tiles)
 #pragma unroll
             for (int h = 0; h < NH; ++h) {
+                tie_loaded(qf[h]), tie_loaded(qn[h]), tie_loaded(tau[h]);
                 // bound of the hot test (stream_l2_thr).  IP: -dot < tau <=> dot > -tau, exactly.
                 const float l2thr = stream_l2_thr(tau[h], qn[h]);
                 thr[h] = p.metric ? (live[h] ? -tau[h] : __builtin_inff()) : (live[h] ? l2thr : -__builtin_inff());
@@ -1101,8 +1036,8 @@ __global__ __launch_bounds__(kScanThreads, NB == 1 ? 2 : 1) void scan_f32s_kerne
         }
         int pass_new;
         const int tile_new = next_tile(pass_new);
-        asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-        const char* src = smem + sl * kSlotBytes;
+        wait_vm<kRingPieces>();
+        const char* src = smem + sl * kRingSlotBytes;
         f32x4 a[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) a[c] = *reinterpret_cast<const f32x4*>(src + fa[c]);
@@ -1179,7 +1114,7 @@ __global__ __launch_bounds__(kScanThreads, NB == 1 ? 2 : 1) void scan_f32s_kerne
         if (pass_cur >= n_pass) break;
         step(1);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // retire the tail prefetches before the wave ends
+    wait_vm<0>();  // retire the tail prefetches before the wave ends
     sink_bin_wave(p.sink, (int)blockIdx.x * kScanWaves + wave, wbase, lane);  // no separate binning launch
 }
 
@@ -1298,7 +1233,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_kernel(con
     constexpr int kUnitVmem = 2 * kPieces + 1;  // vector-memory instructions per wave and unit: the row pieces + the norm piece
     static_assert(kUnitRowBytes == 2 * kPieces * NW * 1024, "a unit is 2 kPieces 1 KB row pieces per wave");
     static_assert(D >= 3 && (kScanWaves / NW) * D * kUnitBytes <= 160 * 1024, "the ring: one slot being read, one being filled, >= 1 in flight");
-    static_assert((D - 2) * kUnitVmem <= 63, "vmcnt is a 6-bit count");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1315,7 +1249,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_kernel(con
     const int n_cb = 2 * p.n_batches;              // column blocks of the launch (<= 8 CBW)
     if (NW * z >= n_cb) return;  // (workgroup-uniform, NW = 4 only) a half none of whose waves has a column block
 
-    // LDS-DMA written as instructions (see scan_f32s_kernel): "scalar unit base + this lane's 32-bit offset".  Wave w
+    // LDS-DMA written as instructions (see vs_ring.h): "scalar unit base + this lane's 32-bit offset".  Wave w
     // moves rows 4 kPieces w .. 4 kPieces (w + 1) - 1 of each 32-row half of a unit, four rows per piece: lane l of piece
     // j lands at row b = 4 (kPieces w + j) + (l >> 4) (+ 32), stored chunk l & 15 <- source chunk (l & 15) ^ (b & 15); the
     // second half is the same lane offsets 8 KB further on both sides.  Every wave also moves the unit's 64 norms (lane
@@ -1360,8 +1294,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_kernel(con
 
     // The wave's column blocks as bf16 B operands (qb[h][s], SeedParams::qbf), loaded once for the launch, and their
     // widened bounds.  The loads are inline asm so that the compiler puts no wait of its own in front of the operands'
-    // first use (it would be vmcnt(0), a drain of the ring); each loaded register is tied to the explicit wait of the
-    // prologue below.  A column block past the launch's (cb >= n_cb) loads the last one and gets thr = +inf.
+    // first use (it would be vmcnt(0), a drain of the ring); each loaded register is tied behind the explicit wait of the
+    // prologue below (vs_ring.h).  A column block past the launch's (cb >= n_cb) loads the last one and gets thr = +inf.
     u32x4 qb[CBW][4];
     float thr[CBW];
     float qn[CBW], tau[CBW], eb[CBW];
@@ -1372,24 +1306,18 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_kernel(con
         const int qglob = (cb >> 1) * kMaxBatch + (qrow < p.nq_valid ? qrow : 0);
         const uint16_t* src = p.qbf + ((int64_t)cb * 4 * 64 + lane) * 8;  // 1 KB per instruction
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const uint16_t* ps = src + s * 64 * 8;
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qb[h][s]) : "v"(ps) : "memory");
-        }
-        const float* pn = p.qnorm + qglob;
-        const float* pt = p.tau0 + qglob;
-        const float* pe = p.qbound + qglob;
-        asm volatile("global_load_dword %0, %1, off" : "=v"(qn[h]) : "v"(pn) : "memory");
-        asm volatile("global_load_dword %0, %1, off" : "=v"(tau[h]) : "v"(pt) : "memory");
-        asm volatile("global_load_dword %0, %1, off" : "=v"(eb[h]) : "v"(pe) : "memory");
+        for (int s = 0; s < 4; ++s) asm_load_b128(qb[h][s], src + s * 64 * 8);
+        asm_load_b32(qn[h], p.qnorm + qglob);
+        asm_load_b32(tau[h], p.tau0 + qglob);
+        asm_load_b32(eb[h], p.qbound + qglob);
     }
     // prologue: units 0 .. D - 2 into slots 0 .. D - 2
 #pragma unroll
     for (int s = 0; s < D - 1; ++s) issue_unit(s, s);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 2) * kUnitVmem) : "memory");  // the operands (older than every DMA) and unit 0 are here
+    wait_vm<(D - 2) * kUnitVmem>();  // the operands (older than every DMA) and unit 0 are here
 #pragma unroll
     for (int h = 0; h < CBW; ++h) {
-        asm volatile("" : "+v"(qb[h][0]), "+v"(qb[h][1]), "+v"(qb[h][2]), "+v"(qb[h][3]), "+v"(qn[h]), "+v"(tau[h]), "+v"(eb[h]) :: "memory");
+        tie_loaded(qb[h]), tie_loaded(qn[h]), tie_loaded(tau[h]), tie_loaded(eb[h]);
         const int cb = vw + kScanWaves * h;
         const bool live = cb < n_cb && 16 * (cb & 1) + r < p.nq_valid;
         // |S_fl - S'| <= E.  L2: the accumulators start from -bn / 2 (score_tile), and the exact hot test
@@ -1508,7 +1436,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_kernel(con
 #endif
     auto step = [&](const int t, const int sl) __attribute__((always_inline)) {
         VS_F32F_STAMP(0);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 3) * kUnitVmem) : "memory");
+        wait_vm<(D - 3) * kUnitVmem>();
         VS_F32F_STAMP(1);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");

@@ -9,20 +9,19 @@
 //       settle after a few tiles (a lane inserts about k ln(n / k) of its n = N / 8192 rows);
 //     * no second launch: every workgroup ranks its lanes' lists into one sorted partial list per query, and the
 //       workgroup that arrives last (one atomic per workgroup) merges the partial lists into the result.
-//   Data path = the streaming scans': per-wave ring of two 16-row tile slots in LDS filled by LDS-DMA (`nt`), XOR
-//   swizzle on the source side, hand-counted vmcnt; tiles dealt statically (wave w of workgroup b takes tiles
+//   Data path = the streaming scans': the per-wave ring of two 16-row tile slots of vs_ring.h (`nt`); tiles dealt statically (wave w of workgroup b takes tiles
 //   b + (w + 8 n) G: at step n the 2048 waves of the grid read 2048 consecutive tiles) and no tile is fetched that is
 //   not used -- with one pass over the rows per launch two discarded tail prefetches per wave would be 6 % of the bytes.
 //   Bound: HBM (516 MB per call at SIFT-1M whatever the batch size).
 #include "vs_kernels.h"
 #include "vs_dev.h"
+#include "vs_ring.h"
 
 namespace vs {
 
 namespace {
 
-constexpr int kOneSlotBytes = kTileRows * kDim * 4 + 256;         // 16 rows + their norms
-constexpr int kOneRing = kScanWaves * 2 * kOneSlotBytes;          // 135168
+constexpr int kOneRing = kScanWaves * kRingWaveBytes;          // 135168
 constexpr int kOneScratch = 8192;                                 // per-wave query norms [8][32] | counters [32] | bounds [32] | flag | lane minima [32][32]
 constexpr int kOneLds = kOneRing + kOneScratch;
 
@@ -104,51 +103,38 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_one_kernel(const OnePara
     auto tile_of = [&](int n) { return ((p.reverse && n < n_full) ? n_full - 1 - n : n) * G + (int)blockIdx.x; };
     const int t_first = tile_of(wave), t_second = tile_of(wave + kScanWaves);
 
-    // ---- data path (see scan_f32s_kernel): LDS-DMA pieces as instructions, scalar tile base + the lane's 32-bit offset
-    char* ring = smem + wave * (2 * kOneSlotBytes);
+    // ---- data path (vs_ring.h): LDS-DMA pieces as instructions, scalar tile base + the lane's 32-bit offset
+    char* ring = smem + wave * kRingWaveBytes;
     unsigned voff[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int row_in = 2 * j + (lane >> 5);
-        voff[j] = (unsigned)(row_in * 512 + 16 * ((lane & 31) ^ row_in));
-    }
+    ring_src_offsets_f32(lane, voff);
     const unsigned voff_n = (unsigned)lane * 4u;
     const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)ring);
     auto issue_tile = [&](int tile, int slot) __attribute__((always_inline)) {
         const int64_t row0 = (int64_t)tile * TR;
-        const unsigned dst = ring_lds + (unsigned)(slot * kOneSlotBytes);
-        const char* tb = reinterpret_cast<const char*>(p.base) + row0 * (kDim * 4);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            asm volatile("s_add_u32 m0, %0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt" ::"s"(dst), "v"(voff[j]), "s"(tb), "n"(j * 1024) : "memory", "scc");
-        const char* nb = reinterpret_cast<const char*>(p.bnorm + row0);  // (the norm array is padded by 64)
-        asm volatile("s_add_u32 m0, %0, 8192\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" ::"s"(dst), "v"(voff_n), "s"(nb) : "memory", "scc");
+        ring_issue_tile<true>(ring_lds + (unsigned)(slot * kRingSlotBytes), reinterpret_cast<const char*>(p.base) + row0 * (kDim * 4),
+                              reinterpret_cast<const char*>(p.bnorm + row0), voff, voff_n);  // (the norm array is padded by 64)
     };
     // ---- the queries as MFMA B operands: qf[h][c][i] = Q[16 h + r][16 c + 4 g + i]; padding queries (main.cpp:206-211)
     // are zero columns that nothing looks at.  Every wave for itself.  The loads go out FIRST and as instructions the
     // compiler does not see as memory operations (it would wait for them with vmcnt(0), i.e. for the two tiles requested
-    // right behind them as well: the tile loop then started 3 us later).  ONE statement waits for them -- always exactly
-    // 18 younger pieces: a wave without a first or second tile fetches tile 0 into the slot -- and has every loaded
-    // register as an in/out operand: nothing that reads them can be placed above it (copies of a loaded register that
-    // the compiler made ahead of a separate wait statement were seen to break a test at random).
+    // right behind them as well: the tile loop then started 3 us later).  One wait covers them -- always exactly two
+    // tiles' younger pieces: a wave without a first or second tile fetches tile 0 into the slot -- and every loaded
+    // register is tied behind it: nothing that reads them can be placed above it (copies of a loaded register that
+    // the compiler made ahead of an untied wait statement were seen to break a test at random).
     f32x4 qf[NQH][8];
 #pragma unroll
     for (int h = 0; h < NQH; ++h) {
         const int qsafe = min(16 * h + r, p.nq_valid - 1);
 #pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const float* pc = p.q + (int64_t)qsafe * kDim + 16 * c + 4 * g;
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qf[h][c]) : "v"(pc) : "memory");
-        }
+        for (int c = 0; c < 8; ++c) asm_load_b128(qf[h][c], p.q + (int64_t)qsafe * kDim + 16 * c + 4 * g);
     }
     ONE_STAMP(0);
     const bool have0 = t_first < tiles_total, have1 = t_second < tiles_total;  // (wave-uniform)
     issue_tile(have0 ? t_first : 0, 0);
     issue_tile(have1 ? t_second : 0, 1);
-#define VS_TIE8(a) "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7])
-    if constexpr (NQH == 1) asm volatile("s_waitcnt vmcnt(18)" : VS_TIE8(qf[0]) : : "memory");
-    else asm volatile("s_waitcnt vmcnt(18)" : VS_TIE8(qf[0]), VS_TIE8(qf[NQH - 1]) : : "memory");
-#undef VS_TIE8
+    wait_vm<2 * kRingPieces>();
+#pragma unroll
+    for (int h = 0; h < NQH; ++h) tie_loaded(qf[h]);
 #pragma unroll
     for (int h = 0; h < NQH; ++h)
 #pragma unroll
@@ -199,10 +185,8 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_one_kernel(const OnePara
             li[h][j] = -1;
         }
 
-    unsigned fa[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) fa[c] = (unsigned)(wave * (2 * kOneSlotBytes) + r * 512 + (((4 * c + g) ^ r) << 4));
-    const unsigned fa_n = (unsigned)(wave * (2 * kOneSlotBytes) + 8192 + 16 * g);
+    unsigned fa[8], fa_n;
+    ring_frag_offsets_f32(wave * kRingWaveBytes, r, g, fa, fa_n);
     const int last_row = (int)p.n_rows - 1;
 
     // t_cur sits in slot `sl` (landed or landing), t_nxt in the other slot: nine DMA pieces behind it if it is a tile at all
@@ -212,9 +196,9 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_one_kernel(const OnePara
         int tk = 0;
         if (lane == 0) tk = atomicAdd(lds_ticket, 1);
         const int t_new = tile_of(__builtin_amdgcn_readfirstlane(tk));
-        if (t_nxt < tiles_total) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const char* src = smem + sl * kOneSlotBytes;
+        if (t_nxt < tiles_total) wait_vm<kRingPieces>();
+        else wait_vm<0>();
+        const char* src = smem + sl * kRingSlotBytes;
         f32x4 a[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) a[c] = *reinterpret_cast<const f32x4*>(src + fa[c]);

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle
+from dev_multi_check import check_dev_multi
 
 pytestmark = pytest.mark.gpu
 
@@ -539,15 +540,7 @@ def test_sift1m_streaming_scan_pairs_batches_exact(gpu_pkg, nb, B):
             idx.search_dev_multi(qd.data_ptr(), nb, B, 5, o_i.data_ptr(), o_d.data_ptr(), fl.data_ptr(),
                                  torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
-            f = fl.cpu().numpy()
-            assert set(np.unique(f)) <= {0, 1}
-            keep = f == 0
-            assert keep.mean() > 0.9
-            gi, gd = o_i.cpu().numpy(), o_d.cpu().numpy()
-            assert np.array_equal(gi[keep, :5], oi[keep]) and np.array_equal(gd[keep, :5], od[keep])
-            # flagged queries (equal distances among the k + 1 best): distances still exact, ids a valid tie order
-            assert np.array_equal(gd[:, :5], od)
-            assert (np.diff(gd, axis=1) >= 0).all() and (gi >= 0).all()
+            check_dev_multi(o_i.cpu().numpy(), o_d.cpu().numpy(), fl.cpu().numpy(), oi, od)
 
 
 @pytest.mark.parametrize("world", [2, 4, 8])
