@@ -283,6 +283,13 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const ScanParams 
         lds_barrier();
         if (!lds_flag[0]) {  // workgroup-uniform
             if (blockIdx.x == 0 && tid == 0 && p.invalid) p.invalid[batch] = 1;
+            // The next batch starts with this wave's two tiles in the ring and issues none, so nothing would follow
+            // its query pieces in the queue and its counted wait would hold for nothing: stage its queries here (every
+            // wave has passed the barriers behind the reads of the query stage) and land them with the tiles below.
+            if (batch + 1 < p.n_batches) {
+                issue_queries(qb + p.q_batch_stride);
+                q_staged = true;
+            }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             continue;

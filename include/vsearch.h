@@ -226,7 +226,8 @@ VS_API int vs_bf_search(vs_index* h, const float* queries_host, int64_t nq, int 
  * already in HBM -> the k+1 best (dist, id) per query by (dist, id) ascending,
  * [B x (k+1)], plus flags[B]: 1 where two of those distances are equal (the
  * caller must then use vs_bf_search for reference tie order), 2 where the int8
- * path had to skip the batch (rerun with vs_set_precision(h, 1)).  This is the
+ * path had to skip the batch (rerun with vs_set_precision(h, 1)).  A query with
+ * flags == 2 has all its k+1 ids -1 and all its k+1 distances +inf.  This is the
  * analogue of QnnRunner::executeBatchRaw + getRawOutputBuffer (QnnRunner.h:28-30)
  * with the top-k fused in, so the B x N score matrix never exists. */
 VS_API int vs_bf_search_dev(vs_index* h, const float* queries_dev, int B, int k,
@@ -237,7 +238,11 @@ VS_API int vs_bf_search_dev(vs_index* h, const float* queries_dev, int B, int k,
  * the harness loop of main.cpp:201-251 in one call.  Every batch still streams the
  * base once; groups of up to 32 batches share ONE persistent scan launch (preceded by
  * three small bound-seeding launches, followed by one merge launch), all on `stream`,
- * so no launch gap, grid fill or drain separates consecutive batches. */
+ * so no launch gap, grid fill or drain separates consecutive batches.
+ * flags == 2 is a verdict per batch: all B queries of a skipped batch carry it (ids -1,
+ * distances +inf), and every other batch of the same call is unaffected -- its lists and
+ * flags are what a call without the skipped batches returns, so only the flagged batches
+ * need the rerun under vs_set_precision(h, 1). */
 VS_API int vs_bf_search_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k,
                                   int32_t* ids_dev, float* dists_dev, int32_t* flags_dev, void* stream);
 

@@ -268,17 +268,15 @@ def test_base_norm_too_large_for_the_byte_scan(gpu_pkg):
 @pytest.mark.parametrize("dim,n", [(128, 40000), (320, 20000)])
 def test_l2_through_the_new_creator_is_vs_bf_create_nd_u8(gpu_pkg, dim, n):
     """Two indexes compared: vs_bf_create_nd_u8_metric(VS_METRIC_L2) against vs_bf_create_nd_u8 on the same rows -- ids,
-    distances, flags, the number of scan launches and the precision semantics.  The last batch of the device call holds a
-    value 7.5 (flags == 2 under precision 2 and 0).  It is the last one on purpose: at dim 128 both creators give the
-    specialised index, whose own byte scan (scan_kernel, not touched here) returned wrong, run-to-run different lists for
-    the batch that FOLLOWS a skipped batch of the same launch when this test had the value in batch 1 -- with either
-    creator, so it is no difference between them, and it is left to a change of its own (after a skipped batch the
-    kernel stages the next batch's queries with no tile loads behind them, and its counted wait assumes two)."""
+    distances, flags, the number of scan launches and the precision semantics.  The middle batch of the device call holds a
+    value 7.5 (flags == 2 under precision 2 and 0), so that a live batch follows the skipped one in the same launch: at
+    dim 128 both creators give the specialised index, whose scan_kernel stages the next batch's queries itself when it
+    skips a batch (test_gpu_mixed_batches.py checks those launches against exact lists), at dim 320 the general one."""
     L = gpu_pkg.lib()
     rng = np.random.default_rng(14000 + dim)
     base, q = u8_data(rng, n, 96, dim)
     qf = _f32(q)
-    qf[70, 3] = 7.5  # (batch 2 of the device call is no byte batch)
+    qf[40, 3] = 7.5  # (batch 1 of the device call is no byte batch)
     res = []
     for metric_form in (False, True):
         h = C.c_void_p(None)
@@ -310,7 +308,7 @@ def test_l2_through_the_new_creator_is_vs_bf_create_nd_u8(gpu_pkg, dim, n):
         else:
             assert a == b and a > 0
     flags2 = res[1][0][2]
-    assert (flags2[64:] == 2).all() and not (flags2[:64] == 2).any()
+    assert (flags2[32:64] == 2).all() and not (flags2[:32] == 2).any() and not (flags2[64:] == 2).any()
     assert not (res[1][6][2] == 2).any()  # (precision 1)
 
 
