@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "../../include/vsearch.h"
+#include "vs_i16_quant.h"
 
 namespace vs {
 
@@ -519,6 +520,72 @@ int vs_synth_mixture(float* dst, int64_t row_begin, int64_t rows, int dim, uint6
 int vs_select_topk_slots(const int32_t* rows, const float* dists, int64_t m, int k, int32_t* out_ids, float* out_dists) {
     if (!rows || !dists || !out_ids || !out_dists || k <= 0) { vs::set_error("bad arguments"); return VS_ERR_INVALID; }
     vs::select_topk_slots_sparse(rows, dists, m, k, out_ids, out_dists);
+    return VS_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ int16 cosine quantiser
+// AMD_npu/Codes/preprocess.py:24-42 restated from the contract in vsearch.h (vs_i16_quant.h holds the arithmetic)
+namespace vs {
+static float i16_pairwise(const float* x, int n) {
+    if (n <= kI16Leaf) return i16_leaf(x, n);
+    const int n2 = i16_split(n);
+    return i16_add(i16_pairwise(x, n2), i16_pairwise(x + n2, n - n2));
+}
+static bool i16_args_ok(const void* src, const void* dst, int64_t rows, int dim, float scale, const char* who) {
+    if (!src || !dst || rows < 0 || dim < 1 || dim > kI16MaxDim || !(scale >= 1.0f && scale <= 2047.0f)) {
+        set_error(std::string(who) + ": bad arguments (1 <= dim <= 2048, scale finite and in [1, 2047])");
+        return false;
+    }
+    return true;
+}
+static void i16_quantize_row(const float* x, int dim, float scale, int16_t* dst) {
+    const float den = i16_den(i16_pairwise(x, dim));
+    for (int t = 0; t < dim; ++t) dst[t] = (int16_t)i16_quant1(x[t], den, scale);
+}
+}  // namespace vs
+
+extern "C" {
+
+int vs_i16_quantize(const float* src, int64_t rows, int dim, float scale, int16_t* dst) {
+    if (!vs::i16_args_ok(src, dst, rows, dim, scale, "vs_i16_quantize")) return VS_ERR_INVALID;
+    for (int64_t r = 0; r < rows; ++r) vs::i16_quantize_row(src + (size_t)r * dim, dim, scale, dst + (size_t)r * dim);
+    return VS_OK;
+}
+
+int vs_i16_write_bin(const char* path, const float* src, int64_t rows, int dim, float scale, int64_t row_multiple) {
+    if (!vs::i16_args_ok(src, path, rows, dim, scale, "vs_i16_write_bin")) return VS_ERR_INVALID;
+    if (row_multiple < 1) {
+        vs::set_error("vs_i16_write_bin: row_multiple must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    FILE* f = std::fopen(path, "wb");
+    if (!f) {
+        vs::set_error(std::string("Cannot open output file ") + path);
+        return VS_ERR_IO;
+    }
+    // (int16 in memory order: the library is built for little-endian hosts only, like its other file formats)
+    bool ok = true;
+    try {
+        std::vector<int16_t> row((size_t)dim);
+        for (int64_t r = 0; r < rows && ok; ++r) {
+            vs::i16_quantize_row(src + (size_t)r * dim, dim, scale, row.data());
+            ok = std::fwrite(row.data(), 2, (size_t)dim, f) == (size_t)dim;
+        }
+        std::fill(row.begin(), row.end(), (int16_t)0);
+        const int64_t padded = (rows + row_multiple - 1) / row_multiple * row_multiple;
+        for (int64_t r = rows; r < padded && ok; ++r) ok = std::fwrite(row.data(), 2, (size_t)dim, f) == (size_t)dim;
+    } catch (const std::bad_alloc&) {
+        std::fclose(f);
+        vs::set_error("out of host memory");
+        return VS_ERR_NOMEM;
+    }
+    if (std::fclose(f) != 0) ok = false;
+    if (!ok) {
+        vs::set_error(std::string("write failed: ") + path);
+        return VS_ERR_IO;
+    }
     return VS_OK;
 }
 

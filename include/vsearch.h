@@ -339,6 +339,77 @@ VS_API int vs_q8_search_dev(vs_q8* h, const float* queries_dev, int n_batches, i
 VS_API int vs_q8_search(vs_q8* h, const float* queries_host, int64_t nq, int k, int32_t* ids,
                         uint8_t* scores);
 
+/* ------------------------------------------- int16 cosine score path */
+/* The reference's third score path (AMD_npu/): Codes/preprocess.py:24-42 L2-normalises every
+ * base row and every query, multiplies by 1000 and truncates to int16; Codes/test.cpp:32-43,
+ * 285-311 produces the int16 x int16 -> int32 matrix C = A B^T in row-major order.  A score is a
+ * cosine similarity in fixed point, scale^2 cos(theta).  XRT, the xclbin and the AIE tile-major
+ * output layout are not restated; the quantiser and the integer score matrix are, exactly.
+ *
+ * The quantiser.  For a row x[0..n) and a scale:
+ *  1. Squares: s_i = RN(x_i * x_i).  Every product and sum is rounded separately in fp32, with no
+ *     FMA.
+ *  2. Sum of squares: S = P(s, n), which is numpy's pairwise order.
+ *     - For n < 8: a running sum from 0, in order.
+ *     - For 8 <= n <= 128: start eight partial sums as r_j = s_j; for i = 8, 16, ... while
+ *       i + 8 <= n: r_j = RN(r_j + s_{i+j}); res = ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)); add the
+ *       last n mod 8 elements to res in order.
+ *     - For n > 128: n2 = floor(n / 2) rounded down to a multiple of 8;
+ *       S = RN(P(s[0..n2)) + P(s[n2..n))).
+ *  3. Quantise: den = RN(sqrt_rn(S) + (float)1e-8); v_i = RN(RN(x_i / den) * scale);
+ *     q_i = (int16) trunc(v_i).  A NaN gives 0.  Division and square root are correctly rounded.
+ * This equals ((x / (np.linalg.norm(x, axis=1, keepdims=True) + 1e-8)) * scale).astype(np.int16)
+ * on finite float32 rows.  Every finite |q_i| <= scale; a row with an infinity, or whose squares
+ * overflow, quantises to all zeros; a zero row stays zero.  scale must be finite and in
+ * [1, 2047]; the reference's value is 1000. */
+typedef struct vs_i16 vs_i16; /* opaque: quantised database, scratch, stream */
+
+/* Host only, no GPU: dst[rows x dim] = the quantised rows.  VS_ERR_INVALID for null pointers,
+ * rows < 0, dim outside [1, 2048] or a bad scale. */
+VS_API int vs_i16_quantize(const float* src, int64_t rows, int dim, float scale, int16_t* dst);
+/* Host only: the quantised rows as raw little-endian int16, the row count padded with zero rows
+ * to a multiple of row_multiple >= 1 (preprocess.py: 32 for A.bin, 256 for B.bin). */
+VS_API int vs_i16_write_bin(const char* path, const float* src, int64_t rows, int dim, float scale,
+                            int64_t row_multiple);
+
+/* The runner.  Checked in this order, all but the last without a device, *out written on success
+ * only: null pointers or n_rows <= 0: VS_ERR_INVALID; dim < 1: VS_ERR_INVALID; dim > 2048:
+ * VS_ERR_UNSUPPORTED; ids that do not fit int32 (n_rows + id_offset > 2^31 - 1, id_offset < 0):
+ * VS_ERR_UNSUPPORTED; a scale that is not finite or is outside [1, 2047]: VS_ERR_INVALID; no
+ * device: VS_ERR_DEVICE.  The float rows are uploaded in bounded chunks and quantised on the
+ * device by the kernel that quantises the queries of every call.  The device image holds 2 bytes
+ * per element (each int16 value as the float16 of the same integer), rows padded with zeros to 64
+ * bytes, 64 spare zero rows behind the last one. */
+VS_API int vs_i16_create(const float* base_host, int64_t n_rows, int dim, float scale, int device,
+                         int64_t id_offset, vs_i16** out);
+VS_API void vs_i16_destroy(vs_i16* h);
+VS_API int64_t vs_i16_num_docs(const vs_i16* h);
+VS_API int vs_i16_dim(const vs_i16* h);
+VS_API int vs_i16_batch(const vs_i16* h); /* 32 = the largest B */
+VS_API float vs_i16_scale(const vs_i16* h);
+/* Diagnostic: stored rows [row0, row0 + n) back as int16 [n x dim] in host memory.  Blocking.
+ * VS_ERR_INVALID when the range leaves the index. */
+VS_API int vs_i16_rows_read(vs_i16* h, int64_t row0, int64_t n, int16_t* dst);
+
+/* scores_dev[b*ld + j] = sum_t q'[b][t] * b'[j][t] with q', b' the quantised query b and row j:
+ * the row-major matrix test.cpp reconstructs, exact in int32.  queries_dev is [B x dim] floats,
+ * 1 <= B <= 32, ld >= rows.  Asynchronous on the caller's stream. */
+VS_API int vs_i16_execute_dev(vs_i16* h, const float* queries_dev, int B, int32_t* scores_dev,
+                              int64_t ld, void* stream);
+/* The same through host buffers: scores_host is [B x rows], dense.  Blocking. */
+VS_API int vs_i16_execute(vs_i16* h, const float* queries_host, int B, int32_t* scores_host);
+
+/* The k largest scores per query for n_batches batches of B queries ([n_batches*B x dim] floats):
+ * ids_dev and scores_dev are [n_batches*B x k], largest score first, equal scores in ascending
+ * id; slots past the rows are (-1, INT32_MIN).  1 <= B <= 32; k < 1: VS_ERR_INVALID; k > 16:
+ * VS_ERR_UNSUPPORTED.  The top-k is fused into the scan: the score matrix is never written.
+ * Asynchronous on the caller's stream, no host synchronisation. */
+VS_API int vs_i16_search_dev(vs_i16* h, const float* queries_dev, int n_batches, int B, int k,
+                             int32_t* ids_dev, int32_t* scores_dev, void* stream);
+/* Host-buffer form: batches of 32, the last one short.  Blocking. */
+VS_API int vs_i16_search(vs_i16* h, const float* queries_host, int64_t nq, int k, int32_t* ids,
+                         int32_t* scores);
+
 /* ---------------------------------------------------------------------- IVF */
 /* IVFIndex ctor (IVFIndex.cpp:154-177): reads ivf_config.json, cluster_offsets.npy,
  * vectors_reordered.npy, reorder_to_original.npy (reordered mode) and

@@ -198,6 +198,47 @@ private:
     int rows_valid_ = 0;
 };
 
+// The reference's int16 cosine score path (AMD_npu/Codes/preprocess.py:24-42, test.cpp:32-43, 285-311): rows and queries
+// L2-normalised, scaled and truncated to int16, scores = the exact int32 matrix C = A B^T (scale^2 cos).
+class I16Runner {
+public:
+    // Any vector length 1 <= dim <= 2048; scale finite and in [1, 2047] (the reference: 1000)
+    I16Runner(const std::vector<float>& docs, int64_t rows, int dim, float scale = 1000.0f, int device = 0, int64_t id_offset = 0) {
+        check(vs_i16_create(docs.data(), rows, dim, scale, device, id_offset, &h_));
+    }
+    ~I16Runner() { vs_i16_destroy(h_); }
+    I16Runner(const I16Runner&) = delete;
+    I16Runner& operator=(const I16Runner&) = delete;
+
+    size_t getBatchSize() const { return (size_t)vs_i16_batch(h_); }
+    size_t getDim() const { return (size_t)vs_i16_dim(h_); }
+    size_t getNumDocs() const { return (size_t)vs_i16_num_docs(h_); }
+    float getScale() const { return vs_i16_scale(h_); }
+
+    // the quantiser alone, on the host: [rows * dim] int16
+    static std::vector<int16_t> quantize(const std::vector<float>& x, int64_t rows, int dim, float scale = 1000.0f) {
+        std::vector<int16_t> q((size_t)rows * dim);
+        check(vs_i16_quantize(x.data(), rows, dim, scale, q.data()));
+        return q;
+    }
+    // batch_queries: [B * dim], B <= getBatchSize(); scores: [B x getNumDocs()] int32, row-major
+    void execute(const std::vector<float>& batch_queries, std::vector<int32_t>& scores) {
+        const int B = (int)(batch_queries.size() / getDim());
+        scores.resize((size_t)B * getNumDocs());
+        check(vs_i16_execute(h_, batch_queries.data(), B, scores.data()));
+    }
+    // the k <= 16 largest scores per query, equal scores in ascending id: ids / scores [nq x k], (-1, INT32_MIN) past the rows
+    void search(const std::vector<float>& queries, int64_t nq, int k, std::vector<int32_t>& ids, std::vector<int32_t>& scores) {
+        ids.assign((size_t)nq * k, -1);
+        scores.assign((size_t)nq * k, INT32_MIN);
+        check(vs_i16_search(h_, queries.data(), nq, k, ids.data(), scores.data()));
+    }
+    vs_i16* handle() { return h_; }
+
+private:
+    vs_i16* h_ = nullptr;
+};
+
 class IVFIndex {
 public:
     struct SearchTiming {  // IVFIndex.h:31-36
