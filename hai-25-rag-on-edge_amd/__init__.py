@@ -194,6 +194,10 @@ def lib():
         "vs_i16_execute": (i32, [vp, vp, i32, vp]),
         "vs_i16_search_dev": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
         "vs_i16_search": (i32, [vp, vp, i64, i32, vp, vp]),
+        "vs_i16_search_topk_dev": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+        "vs_i16_search_topk": (i32, [vp, vp, i64, i32, vp, vp]),
+        "vs_i16_wide_plan": (i32, [i64, i32, vp]),
+        "vs_i16_wide_stats": (i32, [vp, vp, i32]),
         "vs_prof_enable": (i32, [vp, i32]),
         "vs_prof_read": (i32, [vp, i32, C.POINTER(C.c_double), C.POINTER(i64)]),
         "vs_ivf_widek_stats": (i32, [vp, C.POINTER(i64), i32]),
@@ -595,7 +599,7 @@ class I16Runner:
     """The reference's int16 cosine score path (AMD_npu/: preprocess.py:24-42, test.cpp:32-43, 285-311): base rows and
     queries are L2-normalised, scaled and truncated to int16; ``execute`` returns the exact int32 matrix C = A B^T
     ([B, N], scale^2 cos), ``search`` the k largest scores per query, equal scores in ascending id.
-    Any vector length 1 <= d <= 2048; k <= 16; batches of at most 32 queries."""
+    Any vector length 1 <= d <= 2048; k <= 16 (``search_topk``: k <= 128); batches of at most 32 queries."""
 
     def __init__(self, base, scale: float = 1000.0, device: int = 0, id_offset: int = 0):
         self._h = C.c_void_p()
@@ -660,6 +664,33 @@ class I16Runner:
 
     def search_dev(self, q_ptr: int, n_batches: int, B: int, k: int, ids_ptr: int, scores_ptr: int, stream: int):
         _check(lib().vs_i16_search_dev(self._h, q_ptr, n_batches, B, k, ids_ptr, scores_ptr, stream))
+
+    def search_topk(self, queries, k: int):
+        """``search`` for k up to 128 (k <= 16 is ``search`` itself): ids [nq, k] and exact int32 scores [nq, k]."""
+        q = _f32c(queries).reshape(-1, self.getDim())
+        ids = np.empty((q.shape[0], max(k, 0)), dtype=np.int32)
+        top = np.empty((q.shape[0], max(k, 0)), dtype=np.int32)
+        _check(lib().vs_i16_search_topk(self._h, _p(q), q.shape[0], k, _p(ids), _p(top)))
+        return ids, top
+
+    def search_topk_dev(self, q_ptr: int, n_batches: int, B: int, k: int, ids_ptr: int, scores_ptr: int, stream: int):
+        """``search_dev`` for k up to 128: asynchronous on ``stream``, no host synchronisation."""
+        _check(lib().vs_i16_search_topk_dev(self._h, q_ptr, n_batches, B, k, ids_ptr, scores_ptr, stream))
+
+    def wide_stats(self, reset: bool = False):
+        """Counters of the k >= 17 pipeline since the last reset (synchronises the device): (queries ranked from their
+        candidate lists, most candidates of any query, queries answered by the dense fallback, queries whose sample was
+        the whole base)."""
+        out = (C.c_int64 * 4)()
+        _check(lib().vs_i16_wide_stats(self._h, out, 1 if reset else 0))
+        return tuple(int(v) for v in out)
+
+
+def i16_wide_plan(n_rows: int, k: int):
+    """(sample groups, stride, candidate cap) of ``I16Runner.search_topk`` for 17 <= k <= 128 (vsearch.h: the rule)."""
+    out = (C.c_int64 * 3)()
+    _check(lib().vs_i16_wide_plan(n_rows, k, out))
+    return tuple(int(v) for v in out)
 
 
 class IVFIndex(_Index):

@@ -28,6 +28,10 @@
 //                               under key -acc, threshold exchange, workgroup merge); merge_compact_kernel ranks the
 //                               partial lists and i16_finish_kernel turns the keys into int32 scores.  The score matrix is
 //                               never written.
+//   i16_keys_kernel<NQH>        the walk of i16_scores_kernel (both are i16_walk_kernel) over chosen 64-row groups, float
+//                               keys out: the sample and the fallback chunks of the wide-k pipeline
+//   i16_filter_kernel<NQH>      i16_topk_kernel's scan without lists: rows under a per-query bound go to candidate lists
+//                               (17 <= k <= 128: wide_enqueue, ranked by topk_wide_kernel)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +39,7 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/vsearch.h"
@@ -66,6 +71,9 @@ constexpr int kBatch = 32;
 constexpr int kGroup = 16;       // batches one quantiser launch and one fused scan launch serve
 constexpr int kGroupRows = 64;   // rows a wave scores per step
 constexpr int kMaxK = 16;
+constexpr int kWideMaxK = 128;             // vs_i16_search_topk*
+constexpr int kWideCap = 8192;             // candidates kept per query
+constexpr int64_t kWideChunk = 1 << 20;    // rows per chunk of the dense fallback
 constexpr int kPadRows = vs::kScanPadRows;
 static_assert(kGroupRows <= kPadRows, "row groups are loaded unclamped");
 
@@ -172,12 +180,31 @@ __global__ __launch_bounds__(256) void i16_quantize_kernel(const float* __restri
     }
 }
 
-// rows: [n_pad][dim_b] bytes, n_pad a multiple of 64 inside the image; out: [B][ld] int32
-template <int NQH>
-__global__ __launch_bounds__(256) void i16_scores_kernel(const char* __restrict__ rows, const i32x4* __restrict__ qf, int dim_b,
-                                                         int64_t n_rows, int64_t n_groups, int B, int32_t* __restrict__ out,
-                                                         int64_t ld, int aligned) {
+// Which 64-row groups a score walk visits: all of them (the score matrix: column = row) ...
+struct AllGroups {
+    __device__ __forceinline__ bool idle() const { return false; }
+    __device__ __forceinline__ int64_t group(int64_t j) const { return j; }
+    __device__ __forceinline__ int64_t column(int64_t, int64_t row) const { return row; }
+};
+// ... or the groups first + j stride (a sample, a chunk), and nothing at all unless *run_if != 0 when run_if is given
+struct SomeGroups {
+    int64_t first, stride;
+    const int32_t* run_if;
+    __device__ __forceinline__ bool idle() const { return run_if && !run_if[0]; }
+    __device__ __forceinline__ int64_t group(int64_t j) const { return first + j * stride; }
+    __device__ __forceinline__ int64_t column(int64_t j, int64_t row) const { return row - (group(j) - j) * kGroupRows; }
+};
+
+// rows: [n_pad][dim_b] bytes, n_pad a multiple of 64 inside the image.  The j-th group visited, j < n_groups, goes to
+// columns 64 j .. of out ([B][ld]): Out = int32_t the scores (i16_scores_kernel), Out = float the top-k keys -(q'.b')
+// (i16_keys_kernel)
+template <int NQH, class Out, class Groups>
+__global__ __launch_bounds__(256) void i16_walk_kernel(const char* __restrict__ rows, const i32x4* __restrict__ qf, int dim_b,
+                                                       int64_t n_rows, int64_t n_groups, int B, Out* __restrict__ out, int64_t ld,
+                                                       int aligned, const Groups groups) {
     constexpr int T = 4;  // 16-row tiles of a wave's 64 rows
+    constexpr bool KEYS = std::is_floating_point<Out>::value;
+    if (groups.idle()) return;
     const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), waves = (int64_t)gridDim.x * 4;
     const int S = dim_b / 64;    // 64-byte steps per row
@@ -187,7 +214,7 @@ __global__ __launch_bounds__(256) void i16_scores_kernel(const char* __restrict_
     const unsigned voff = (unsigned)((16 * (c >> 2) + (c & 3)) * dim_b + 16 * g);
     const unsigned tile_bytes = 4u * (unsigned)dim_b;
     for (int64_t grp = wave0; grp < n_groups; grp += waves) {
-        const int64_t row0 = grp * kGroupRows;
+        const int64_t row0 = groups.group(grp) * kGroupRows;
         const char* sb = rows + row0 * (int64_t)dim_b;  // uniform base + 32-bit lane offset
         f32x4 acc[T][NQH];
 #pragma unroll
@@ -256,10 +283,13 @@ __global__ __launch_bounds__(256) void i16_scores_kernel(const char* __restrict_
             for (int t = 0; t < T; ++t) {
                 const int64_t r = row0 + 16 * g + 4 * t;  // accumulator i of tile t: row r + i
                 if (r >= n_rows) continue;
-                int32_t* dst = out + (size_t)qi * ld + r;
-                const i32x4 word = {(int)acc[t][h][0], (int)acc[t][h][1], (int)acc[t][h][2], (int)acc[t][h][3]};  // exact: see above
+                Out* dst = out + (size_t)qi * ld + groups.column(grp, r);
+                typedef Out Out4 __attribute__((ext_vector_type(4)));
+                Out4 word;  // exact: see above
+                if constexpr (KEYS) word = -acc[t][h];
+                else word = (Out4){(int)acc[t][h][0], (int)acc[t][h][1], (int)acc[t][h][2], (int)acc[t][h][3]};
                 if (aligned && r + 4 <= n_rows) {
-                    *reinterpret_cast<i32x4*>(dst) = word;
+                    *reinterpret_cast<Out4*>(dst) = word;
                 } else {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
@@ -269,6 +299,11 @@ __global__ __launch_bounds__(256) void i16_scores_kernel(const char* __restrict_
         }
     }
 }
+
+template <int NQH>
+constexpr auto i16_scores_kernel = i16_walk_kernel<NQH, int32_t, AllGroups>;
+template <int NQH>
+constexpr auto i16_keys_kernel = i16_walk_kernel<NQH, float, SomeGroups>;
 
 struct TopkParams {
     const char* rows;      // [n_rows + 64][dim_b] bytes
@@ -434,6 +469,178 @@ __global__ __launch_bounds__(256) void i16_finish_kernel(int32_t* __restrict__ s
     scores[i] = d < VS_INF ? (int)(-d) : (int)0x80000000;
 }
 
+// ---- wide k (17 <= k <= 128): the filter scan of wide_enqueue below
+struct FilterParams {
+    const char* rows;      // [n_rows + 64][dim_b] bytes
+    const i32x4* qfrag;    // [n_batches][dim_b / 64][2][64]
+    int dim_b;
+    int64_t n_rows;
+    int n_batches;
+    const float* tau;      // [n_batches][32]: a row is a candidate of the query when its key is below this bound
+    int32_t* cnt;          // [n_batches][32] candidates counted (zero on entry; keeps counting past cap)
+    float* cand_d;         // [n_batches][32][cap] keys
+    int32_t* cand_i;       //                      rows
+    int cap;
+};
+
+// i16_topk_kernel's scan (512 threads, 64-row blocks dealt round-robin, non-temporal row loads and the query fragments one
+// step ahead, the batch loop inside) without its lists: a block's epilogue compares the 16 x NQH keys of a lane with the
+// bound of the lane's query, leaves when no lane of the wave has a key under its bound, and otherwise reserves the
+// lane's places in the query's candidate list with one atomicAdd per query block.  No LDS, no exchange, no merge.
+template <int NQH>
+__global__ __launch_bounds__(vs::kScanThreads, 1) void i16_filter_kernel(const FilterParams p) {
+    using namespace vs;
+    constexpr int T = 4;
+    constexpr int kBlockRows = T * kTileRows;  // 64
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, g = lane >> 4;
+    const int dim_b = p.dim_b;
+    const unsigned voff = (unsigned)(r * dim_b + 16 * g);  // this lane's 16 bytes inside a 16-row tile's 64-byte step
+    const int S = dim_b / 64;
+    const int n_pairs = S >> 1;
+    const int64_t last_row = p.n_rows - 1;
+    const int blocks_total = (int)((p.n_rows + kBlockRows - 1) / kBlockRows);
+    const int wb0 = blockIdx.x * kScanWaves + wave;
+    const int wb_step = gridDim.x * kScanWaves;
+
+#pragma clang loop unroll(disable)
+    for (int batch = 0; batch < p.n_batches; ++batch) {
+        const i32x4* qf_b = p.qfrag + (int64_t)batch * S * 128;
+        // Keys are integers: key < tau <=> key < ceil(tau).  tau is next_up of an integer-valued key (+0 for a zero
+        // product, whose next_up is the smallest denormal: named by its bits, so that no denormal is ever compared) or
+        // an infinity (-inf: a padding query, nothing passes).
+        float thr[NQH];
+#pragma unroll
+        for (int h = 0; h < NQH; ++h) {
+            const float t = p.tau[batch * kMaxBatch + 16 * h + r];
+            thr[h] = __builtin_bit_cast(int, t) == 1 ? 1.0f : ceilf(t);
+        }
+        for (int wb = wb0; wb < blocks_total; wb += wb_step) {
+            const int64_t row0 = (int64_t)wb * kBlockRows;
+            const char* sb = p.rows + row0 * (int64_t)dim_b;
+            const unsigned tile_bytes = 16u * (unsigned)dim_b;
+            f32x4 acc[T][NQH];
+#pragma unroll
+            for (int t = 0; t < T; ++t)
+#pragma unroll
+                for (int h = 0; h < NQH; ++h) acc[t][h] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            i32x4 a[T][2], b[NQH][2];
+            auto load_a = [&](int s, i32x4 (&av)[T][2]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    av[t][0] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(sb + (t * tile_bytes + 128u * s) + voff));
+                    av[t][1] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(sb + (t * tile_bytes + 128u * s + 64u) + voff));
+                }
+            };
+            auto load_b = [&](int s, i32x4 (&bv)[NQH][2]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int h = 0; h < NQH; ++h) {
+                    bv[h][0] = qf_b[((2 * s) * 2 + h) * 64 + lane];
+                    bv[h][1] = qf_b[((2 * s + 1) * 2 + h) * 64 + lane];
+                }
+            };
+            auto mfma_half = [&](const i32x4 (&av)[T][2], const i32x4 (&bv)[NQH][2], int u) __attribute__((always_inline)) {
+#pragma unroll
+                for (int t = 0; t < T; ++t)
+#pragma unroll
+                    for (int h = 0; h < NQH; ++h) acc[t][h] = mfma_f16(av[t][u], bv[h][u], acc[t][h]);
+            };
+            if (n_pairs > 0) {
+                load_a(0, a);
+                load_b(0, b);
+            }
+            for (int s = 0; s < n_pairs; ++s) {
+                i32x4 an[T][2], bn2[NQH][2];
+                const bool more = s + 1 < n_pairs;
+                if (more) {
+                    load_a(s + 1, an);
+                    load_b(s + 1, bn2);
+                }
+                mfma_half(a, b, 0);
+                mfma_half(a, b, 1);
+                if (more) {
+#pragma unroll
+                    for (int t = 0; t < T; ++t) {
+                        a[t][0] = an[t][0];
+                        a[t][1] = an[t][1];
+                    }
+#pragma unroll
+                    for (int h = 0; h < NQH; ++h) {
+                        b[h][0] = bn2[h][0];
+                        b[h][1] = bn2[h][1];
+                    }
+                }
+            }
+            if (S & 1) {
+#pragma unroll
+                for (int t = 0; t < T; ++t)
+                    a[t][0] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(sb + (t * tile_bytes + 128u * n_pairs) + voff));
+#pragma unroll
+                for (int h = 0; h < NQH; ++h) b[h][0] = qf_b[((2 * n_pairs) * 2 + h) * 64 + lane];
+                mfma_half(a, b, 0);
+            }
+            // accumulator j of tile t: row row0 + 16 t + 4 g + j, query 16 h + r; bit 4 t + j of mask[h] = a candidate
+            const bool ragged = row0 + kBlockRows - 1 > last_row;  // wave-uniform
+            unsigned mask[NQH], hit = 0;
+#pragma unroll
+            for (int h = 0; h < NQH; ++h) {
+                mask[h] = 0;
+#pragma unroll
+                for (int t = 0; t < T; ++t)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        bool ok = -acc[t][h][j] < thr[h];  // exact (a zero product gives -0.0, which compares equal to 0.0)
+                        if (ragged && row0 + 16 * t + 4 * g + j > last_row) ok = false;
+                        mask[h] |= (unsigned)ok << (4 * t + j);
+                    }
+                hit |= mask[h];
+            }
+            if (__builtin_amdgcn_ballot_w64(hit != 0) == 0) continue;  // wave-uniform: the common case
+#pragma unroll
+            for (int h = 0; h < NQH; ++h) {
+                if (!mask[h]) continue;
+                const int q = batch * kMaxBatch + 16 * h + r;
+                int pos = atomicAdd(p.cnt + q, __builtin_popcount(mask[h]));
+                float* cd = p.cand_d + (int64_t)q * p.cap;
+                int32_t* ci = p.cand_i + (int64_t)q * p.cap;
+#pragma unroll
+                for (int t = 0; t < T; ++t)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if ((mask[h] >> (4 * t + j)) & 1) {
+                            if (pos < p.cap) {
+                                cd[pos] = -acc[t][h][j];
+                                ci[pos] = (int32_t)(row0 + 16 * t + 4 * g + j);
+                            }
+                            ++pos;
+                        }
+            }
+        }
+    }
+}
+
+// One workgroup after a group's ranking launch.  st[0] += queries ranked from their lists, st[1] = max(st[1], candidates
+// of any query), st[2] += queries of the batches whose overflow word is set (the dense fallback answers those).
+__global__ __launch_bounds__(512) void i16_wide_stats_kernel(const int32_t* __restrict__ cnt, const int32_t* __restrict__ ovf, int nb, int B,
+                                                             unsigned long long* __restrict__ st) {
+    __shared__ int s_max, s_list, s_dense;
+    const int tid = threadIdx.x, batch = tid >> 5, qi = tid & 31;
+    if (tid == 0) s_max = s_list = s_dense = 0;
+    __syncthreads();
+    if (batch < nb && qi < B) {
+        atomicMax(&s_max, cnt[tid]);
+        atomicAdd(ovf[batch] ? &s_dense : &s_list, 1);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        st[0] += (unsigned long long)s_list;
+        st[1] = st[1] > (unsigned long long)s_max ? st[1] : (unsigned long long)s_max;
+        st[2] += (unsigned long long)s_dense;
+    }
+}
+
 }  // namespace
 
 struct vs_i16 {
@@ -452,6 +659,25 @@ struct vs_i16 {
     vs::DevBuf<int32_t> d_part_i;
     vs::DevBuf<int32_t> d_ids;      // [kGroup * 32][16]
     vs::DevBuf<int32_t> d_top;      // [kGroup * 32][16]
+    // wide k (17..128, wide_enqueue), allocated by the first such call
+    struct Wide {
+        bool ready = false;
+        int64_t ld = 0;                  // columns of keys: the largest sample (k = 128) or a fallback chunk, whichever is longer
+        int64_t chunk = 0;               // rows per fallback chunk (a multiple of 64)
+        int n_chunks = 0;
+        int64_t whole = 0;               // queries whose sample was the whole base (counted on the host)
+        vs::DevBuf<float> keys;          // [32][ld] keys of one batch's sample, later of a fallback chunk
+        vs::DevBuf<float> tau;           // [kGroup][32]
+        vs::DevBuf<float> pre_d;         // [32][128] the sample's best (only its bound is used)
+        vs::DevBuf<int32_t> pre_i;
+        vs::DevBuf<int32_t> cz;          // [kGroup * 32] candidate counts, [kGroup] overflow words: cleared by the bound launch
+        vs::DevBuf<float> cand_d;        // [kGroup][32][kWideCap]
+        vs::DevBuf<int32_t> cand_i;
+        vs::DevBuf<float> ch_d;          // [32][n_chunks][128] the fallback's chunk lists
+        vs::DevBuf<int32_t> ch_i;
+        vs::DevBuf<unsigned long long> stats;  // [3] (i16_wide_stats_kernel)
+        vs::DevBuf<int32_t> ids, top;    // [kGroup * 32][128] the host call's outputs
+    } wide;
     vs::Stream stream;
 };
 
@@ -558,10 +784,10 @@ int execute_enqueue(vs_i16* h, const float* q_dev, int B, int32_t* scores_dev, i
     const int aligned = (ld % 4 == 0) && (reinterpret_cast<uintptr_t>(scores_dev) % 16 == 0);
     if (B <= 16)
         hipLaunchKernelGGL(i16_scores_kernel<1>, dim3(grid), dim3(256), 0, s, h->d_rows.get(), h->d_qfrag.get(), h->dim_b, h->n_rows, n_groups, B,
-                           scores_dev, ld, aligned);
+                           scores_dev, ld, aligned, AllGroups{});
     else
         hipLaunchKernelGGL(i16_scores_kernel<2>, dim3(grid), dim3(256), 0, s, h->d_rows.get(), h->d_qfrag.get(), h->dim_b, h->n_rows, n_groups, B,
-                           scores_dev, ld, aligned);
+                           scores_dev, ld, aligned, AllGroups{});
     HIPCHK(hipGetLastError());
     return VS_OK;
 }
@@ -620,6 +846,187 @@ int search_enqueue(vs_i16* h, const float* q_dev, int nb, int B, int k, int32_t*
 int check_k(int k) {
     if (k > kMaxK) {
         set_error("k too large for the compiled top-k kernels (k <= 16)");
+        return VS_ERR_UNSUPPORTED;
+    }
+    return VS_OK;
+}
+
+// ---- wide k (17 <= k <= 128), per launch group of nb <= kGroup batches, every step stream-ordered:
+//   quantiser; per batch the keys of the strided sample (i16_keys_kernel) and its k best (topk_wide_kernel, dense form):
+//   bound tau = next_up(k-th smallest sample key); one filter scan over ALL rows for the whole group (i16_filter_kernel:
+//   every key under its query's bound goes to the query's candidate list, counted past the cap); one ranking launch over
+//   the lists (topk_wide_kernel, list form, grp_out = B); i16_finish_kernel.  Exact: a row that is not listed has a key
+//   >= tau, and the k sample rows under tau are listed and are ahead of it.  A list that overflows raises its batch's
+//   overflow word, and the dense fallback enqueued behind the ranking under that word (keys of row chunks, a selection
+//   per chunk, a selection over the chunk lists) rewrites the batch.  When the sample is the whole base the bound launch
+//   writes the final lists (column = row) and nothing else runs.
+// The sampling rule is the header's (vs_i16_wide_plan).
+void wide_plan(int64_t n_rows, int k, int64_t& sample_groups, int64_t& stride) {
+    const int64_t n_groups = (n_rows + kGroupRows - 1) / kGroupRows;
+    const int64_t share = (n_rows / 2048) * k + ((n_rows % 2048) * k + 2047) / 2048;  // ceil(n_rows k / 2048)
+    const int64_t l0 = std::max<int64_t>((int64_t)kGroupRows * k, share);
+    sample_groups = std::min(n_groups, (l0 + kGroupRows - 1) / kGroupRows);
+    stride = n_groups / sample_groups;
+}
+
+int ensure_wide(vs_i16* h, hipStream_t s) {
+    if (h->wide.ready) return VS_OK;
+    vs_i16::Wide w;
+    int64_t sg, stride;
+    wide_plan(h->n_rows, kWideMaxK, sg, stride);
+    w.chunk = std::min(h->n_pad, kWideChunk);
+    w.n_chunks = (int)((h->n_pad + w.chunk - 1) / w.chunk);
+    w.ld = std::max(sg * kGroupRows, w.chunk);
+    const size_t q = (size_t)kGroup * kBatch;
+    int rc;
+    if ((rc = w.keys.alloc((size_t)kBatch * w.ld)) || (rc = w.tau.alloc(q)) || (rc = w.pre_d.alloc((size_t)kBatch * kWideMaxK)) ||
+        (rc = w.pre_i.alloc((size_t)kBatch * kWideMaxK)) || (rc = w.cz.alloc(q + kGroup)) || (rc = w.cand_d.alloc(q * kWideCap)) ||
+        (rc = w.cand_i.alloc(q * kWideCap)) || (rc = w.ch_d.alloc((size_t)kBatch * w.n_chunks * kWideMaxK)) ||
+        (rc = w.ch_i.alloc((size_t)kBatch * w.n_chunks * kWideMaxK)) || (rc = w.stats.alloc(3)) || (rc = w.ids.alloc(q * kWideMaxK)) ||
+        (rc = w.top.alloc(q * kWideMaxK)))
+        return rc;
+    HIPCHK(hipMemsetAsync(w.stats, 0, 3 * sizeof(unsigned long long), s));
+    w.ready = true;
+    h->wide = std::move(w);
+    return VS_OK;
+}
+
+// keys of the groups first + j stride, j < count, of one batch (fragments qf) -> W.keys
+int keys_enqueue(vs_i16* h, const i32x4* qf, int64_t first, int64_t stride, int64_t count, int B, const int32_t* run_if, hipStream_t s) {
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((count + 3) / 4, (int64_t)h->num_cus * 3));
+    const SomeGroups groups{first, stride, run_if};
+    if (B <= 16)
+        hipLaunchKernelGGL(i16_keys_kernel<1>, dim3(grid), dim3(256), 0, s, h->d_rows.get(), qf, h->dim_b, h->n_rows, count, B, h->wide.keys.get(),
+                           h->wide.ld, 1, groups);
+    else
+        hipLaunchKernelGGL(i16_keys_kernel<2>, dim3(grid), dim3(256), 0, s, h->d_rows.get(), qf, h->dim_b, h->n_rows, count, B, h->wide.keys.get(),
+                           h->wide.ld, 1, groups);
+    HIPCHK(hipGetLastError());
+    return VS_OK;
+}
+
+int wide_enqueue(vs_i16* h, const float* q_dev, int nb, int B, int k, int32_t* ids_dev, int32_t* scores_dev, hipStream_t s) {
+    vs_i16::Wide& W = h->wide;
+    int rc = quantize_enqueue(q_dev, (int64_t)nb * kBatch, B, h->dim, h->dim_b, h->scale, h->d_qfrag, s);
+    if (rc) return rc;
+    int64_t sg, stride;
+    wide_plan(h->n_rows, k, sg, stride);
+    const int64_t n = h->n_rows, n_groups = h->n_pad / kGroupRows;
+    const bool whole = sg == n_groups;
+    const size_t frag_b = (size_t)(h->dim_b / 64) * 128;  // fragments of a batch
+    float* const keys_out = reinterpret_cast<float*>(scores_dev);  // keys first; i16_finish_kernel turns them into scores in place
+    int32_t* const cnt = W.cz;
+    int32_t* const ovf = W.cz + kGroup * kBatch;
+    for (int b = 0; b < nb; ++b) {
+        if ((rc = keys_enqueue(h, h->d_qfrag + b * frag_b, 0, stride, sg, B, nullptr, s))) return rc;
+        vs::TopkWideParams t{};
+        t.dense = W.keys;
+        t.dense_ld = W.ld;
+        t.nq = B;
+        t.k1 = k;
+        if (whole) {  // column = row: the final lists
+            t.n_dense = n;
+            t.dense_id0 = h->id_offset;
+            t.out_d = keys_out + (size_t)b * B * k;
+            t.out_i = ids_dev + (size_t)b * B * k;
+            t.out_ld = k;
+            HIPCHK(vs::launch_topk_wide(t, B, s));
+            continue;
+        }
+        t.n_dense = sg * kGroupRows;  // full groups (vsearch.h); the ids of this selection are sample columns and unused
+        t.out_d = W.pre_d;
+        t.out_i = W.pre_i;
+        t.out_ld = kWideMaxK;
+        t.tau_out = W.tau + b * kBatch;  // padding queries: -inf
+        if (b == 0) {  // counts and overflow words of the group, cleared in stream order behind the previous call's use
+            t.zero = W.cz;
+            t.zero_words = kGroup * kBatch + kGroup;
+        }
+        HIPCHK(vs::launch_topk_wide(t, kBatch, s));
+    }
+    if (whole) {
+        W.whole += (int64_t)nb * B;
+    } else {
+        FilterParams f{};
+        f.rows = h->d_rows;
+        f.qfrag = h->d_qfrag;
+        f.dim_b = h->dim_b;
+        f.n_rows = n;
+        f.n_batches = nb;
+        f.tau = W.tau;
+        f.cnt = cnt;
+        f.cand_d = W.cand_d;
+        f.cand_i = W.cand_i;
+        f.cap = kWideCap;
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_groups + vs::kScanWaves - 1) / vs::kScanWaves, h->num_cus));
+        if (B <= 16) hipLaunchKernelGGL(i16_filter_kernel<1>, dim3(grid), dim3(vs::kScanThreads), 0, s, f);
+        else hipLaunchKernelGGL(i16_filter_kernel<2>, dim3(grid), dim3(vs::kScanThreads), 0, s, f);
+        HIPCHK(hipGetLastError());
+        vs::TopkWideParams r{};
+        r.list[0] = {W.cand_d, W.cand_i, kWideCap, cnt, kWideCap, h->id_offset};
+        r.n_list = 1;
+        r.nq = nb * B;
+        r.k1 = k;
+        r.out_d = keys_out;
+        r.out_i = ids_dev;
+        r.out_ld = k;
+        r.overflow = ovf;
+        r.grp_out = B;
+        r.grp_in = kBatch;
+        HIPCHK(vs::launch_topk_wide(r, nb * B, s));
+        hipLaunchKernelGGL(i16_wide_stats_kernel, dim3(1), dim3(512), 0, s, cnt, ovf, nb, B, W.stats.get());
+        HIPCHK(hipGetLastError());
+        // dense fallback of a batch, idle unless one of its lists overflowed
+        for (int b = 0; b < nb; ++b) {
+            float* const od = keys_out + (size_t)b * B * k;
+            int32_t* const oi = ids_dev + (size_t)b * B * k;
+            const int nc = W.n_chunks;
+            for (int c = 0; c < nc; ++c) {
+                const int64_t r0 = (int64_t)c * W.chunk, rows = std::min(W.chunk, n - r0);
+                if ((rc = keys_enqueue(h, h->d_qfrag + b * frag_b, r0 / kGroupRows, 1, (rows + kGroupRows - 1) / kGroupRows, B, ovf + b, s)))
+                    return rc;
+                vs::TopkWideParams d{};
+                d.dense = W.keys;
+                d.dense_ld = W.ld;
+                d.n_dense = rows;
+                d.dense_id0 = (int32_t)(h->id_offset + r0);
+                d.nq = B;
+                d.k1 = k;
+                d.run_if = ovf + b;
+                if (nc == 1) {
+                    d.out_d = od;
+                    d.out_i = oi;
+                    d.out_ld = k;
+                } else {
+                    d.out_d = W.ch_d + (size_t)c * k;
+                    d.out_i = W.ch_i + (size_t)c * k;
+                    d.out_ld = (int64_t)nc * k;
+                }
+                HIPCHK(vs::launch_topk_wide(d, B, s));
+            }
+            if (nc > 1) {
+                vs::TopkWideParams m{};
+                m.list[0] = {W.ch_d, W.ch_i, (int64_t)nc * k, nullptr, nc * k, 0};
+                m.n_list = 1;
+                m.nq = B;
+                m.k1 = k;
+                m.out_d = od;
+                m.out_i = oi;
+                m.out_ld = k;
+                m.run_if = ovf + b;
+                HIPCHK(vs::launch_topk_wide(m, B, s));
+            }
+        }
+    }
+    const int n_out = nb * B * k;
+    hipLaunchKernelGGL(i16_finish_kernel, dim3((n_out + 255) / 256), dim3(256), 0, s, scores_dev, n_out);
+    HIPCHK(hipGetLastError());
+    return VS_OK;
+}
+
+int check_wide_k(int k) {
+    if (k > kWideMaxK) {
+        set_error("k too large for the wide top-k pipeline (k <= 128)");
         return VS_ERR_UNSUPPORTED;
     }
     return VS_OK;
@@ -726,6 +1133,82 @@ int vs_i16_search(vs_i16* h, const float* queries_host, int64_t nq, int k, int32
         HIPCHK(hipMemcpyAsync(scores + (size_t)q0 * k, h->d_top, n * k * 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         q0 += (int64_t)n;
+    }
+    return VS_OK;
+}
+
+int vs_i16_search_topk_dev(vs_i16* h, const float* queries_dev, int n_batches, int B, int k, int32_t* ids_dev, int32_t* scores_dev,
+                           void* stream) {
+    if (!h || !queries_dev || !ids_dev || !scores_dev || n_batches < 1 || B < 1 || B > kBatch || k < 1) {
+        set_error("vs_i16_search_topk_dev: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    int rc = check_wide_k(k);
+    if (rc) return rc;
+    if (k <= kMaxK) return vs_i16_search_dev(h, queries_dev, n_batches, B, k, ids_dev, scores_dev, stream);
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if ((rc = ensure_wide(h, s))) return rc;
+    for (int g0 = 0; g0 < n_batches; g0 += kGroup) {
+        const int gs = std::min(kGroup, n_batches - g0);
+        const size_t o = (size_t)g0 * B * k;
+        if ((rc = wide_enqueue(h, queries_dev + (size_t)g0 * B * h->dim, gs, B, k, ids_dev + o, scores_dev + o, s))) return rc;
+    }
+    return VS_OK;
+}
+
+int vs_i16_search_topk(vs_i16* h, const float* queries_host, int64_t nq, int k, int32_t* ids, int32_t* scores) {
+    if (!h || !queries_host || !ids || !scores || nq < 0 || k < 1) {
+        set_error("vs_i16_search_topk: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    int rc = check_wide_k(k);
+    if (rc) return rc;
+    if (k <= kMaxK) return vs_i16_search(h, queries_host, nq, k, ids, scores);
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = ensure_wide(h, h->stream))) return rc;
+    for (int64_t q0 = 0; q0 < nq;) {  // groups of full batches of 32, then the short last batch
+        const int64_t left = nq - q0;
+        const int nb = left >= kBatch ? (int)std::min<int64_t>(kGroup, left / kBatch) : 1;
+        const int B = left >= kBatch ? kBatch : (int)left;
+        const size_t n = (size_t)nb * B;
+        HIPCHK(hipMemcpyAsync(h->d_q, queries_host + (size_t)q0 * h->dim, n * h->dim * 4, hipMemcpyHostToDevice, h->stream));
+        if ((rc = wide_enqueue(h, h->d_q, nb, B, k, h->wide.ids, h->wide.top, h->stream))) return rc;
+        HIPCHK(hipMemcpyAsync(ids + (size_t)q0 * k, h->wide.ids, n * k * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(scores + (size_t)q0 * k, h->wide.top, n * k * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        q0 += (int64_t)n;
+    }
+    return VS_OK;
+}
+
+int vs_i16_wide_plan(int64_t n_rows, int k, int64_t* out) {
+    if (!out || n_rows < 1 || k <= kMaxK || k > kWideMaxK) {
+        set_error("vs_i16_wide_plan: bad arguments (n_rows >= 1, 17 <= k <= 128)");
+        return VS_ERR_INVALID;
+    }
+    wide_plan(n_rows, k, out[0], out[1]);
+    out[2] = kWideCap;
+    return VS_OK;
+}
+
+int vs_i16_wide_stats(vs_i16* h, int64_t* out, int reset) {
+    if (!h || !out) {
+        set_error("vs_i16_wide_stats: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!h->wide.ready) return VS_OK;  // no wide call yet
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    unsigned long long st[3];
+    HIPCHK(hipMemcpy(st, h->wide.stats, sizeof(st), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3; ++i) out[i] = (int64_t)st[i];
+    out[3] = h->wide.whole;
+    if (reset) {
+        HIPCHK(hipMemset(h->wide.stats, 0, sizeof(st)));
+        HIPCHK(hipDeviceSynchronize());
+        h->wide.whole = 0;
     }
     return VS_OK;
 }

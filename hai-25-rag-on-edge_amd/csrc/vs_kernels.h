@@ -366,6 +366,9 @@ struct TopkWideParams {
     int zero_words;
     int32_t* overflow;       // optional [1]: set to 1 when a list count exceeds its cap
     const int32_t* run_if;   // optional [1]: the launch does nothing unless *run_if != 0
+    int grp_out, grp_in;     // grp_out > 0: several batches in one launch.  Block q writes output q as before and reads
+                             //   the dense row, the lists and cnt of query (q / grp_out) * grp_in + q % grp_out; overflow
+                             //   is then [ceil(nq / grp_out)], one word per batch.  0: every index is q, one overflow word
 };
 hipError_t launch_topk_wide(const TopkWideParams& p, int grid, hipStream_t s);
 

@@ -49,14 +49,15 @@ __global__ __launch_bounds__(kTwThreads) void topk_wide_kernel(const TopkWidePar
         if (tid == 0 && p.tau_out) p.tau_out[q] = -VS_INF;  // padding query: a filter pass under this bound emits nothing
         return;
     }
+    const int qin = p.grp_out > 0 ? (q / p.grp_out) * p.grp_in + q % p.grp_out : q;  // (see TopkWideParams)
     int len[2] = {0, 0};
     int64_t upper = p.dense ? p.n_dense : 0;  // entries at most
     for (int l = 0; l < p.n_list; ++l) {
         int c = p.list[l].cap;
         if (p.list[l].cnt) {
-            const int n = p.list[l].cnt[q];
+            const int n = p.list[l].cnt[qin];
             if (n > c) {
-                if (tid == 0 && p.overflow) p.overflow[0] = 1;
+                if (tid == 0 && p.overflow) p.overflow[p.grp_out > 0 ? q / p.grp_out : 0] = 1;
             } else {
                 c = n > 0 ? n : 0;
             }
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(kTwThreads) void topk_wide_kernel(const TopkWidePar
         len[l] = c;
         upper += c;
     }
-    const int M = wide_select<kTwThreads>(sel, upper, p.k1, [&](auto&& f) { tw_for_each(p, q, len, f); });
+    const int M = wide_select<kTwThreads>(sel, upper, p.k1, [&](auto&& f) { tw_for_each(p, qin, len, f); });
     const uint64_t* keys = sel.keys;
 
     const int n_out = min(M, p.k1);
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(kTwThreads) void topk_wide_kernel(const TopkWidePar
 }
 
 hipError_t launch_topk_wide(const TopkWideParams& p, int grid, hipStream_t s) {
-    if (p.k1 < 1 || p.k1 > kTopkWideMax || p.nq < 0 || grid < p.nq || grid < 1 || p.n_list < 0 || p.n_list > 2 ||
+    if (p.k1 < 1 || p.k1 > kTopkWideMax || p.nq < 0 || grid < p.nq || grid < 1 || p.n_list < 0 || p.n_list > 2 || p.grp_out < 0 ||
         (p.dense && (p.dense_ld & 3)))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(topk_wide_kernel, dim3(grid), dim3(kTwThreads), 0, s, p);

@@ -410,6 +410,51 @@ VS_API int vs_i16_search_dev(vs_i16* h, const float* queries_dev, int n_batches,
 VS_API int vs_i16_search(vs_i16* h, const float* queries_host, int64_t nq, int k, int32_t* ids,
                          int32_t* scores);
 
+/* The same for k up to 128.  Layouts and meaning are those of vs_i16_search_dev / vs_i16_search:
+ * [n_batches*B x k], largest score first, equal scores in ascending id, ids include id_offset,
+ * slots past the rows are (-1, INT32_MIN), scores are the exact int32 products of the quantised
+ * vectors, 1 <= B <= 32.  Checked in this order: null pointers, n_batches < 1, B out of range or
+ * nq < 0: VS_ERR_INVALID; k < 1: VS_ERR_INVALID; k > 128: VS_ERR_UNSUPPORTED.
+ *  - k <= 16: the call IS vs_i16_search_dev / vs_i16_search (same launches, same results).
+ *  - 17 <= k <= 128: the wide pipeline.  Per launch group of up to 16 batches, all stream-ordered:
+ *    the keys -(q'.b') of a strided sample of the rows and their k-th smallest give a bound per
+ *    query; one filter scan over all rows lists every row whose key is at or under the bound
+ *    (at most 8192 stored per query, all counted); the k best of each list are the answer.  A
+ *    query with more than 8192 candidates (masses of equal scores) has its batch answered by a
+ *    dense fallback enqueued behind under a device-side flag: keys of row chunks, a selection per
+ *    chunk, a selection over the chunk lists.  When the sample is the whole base its selection is
+ *    the answer.  Exact on every path.
+ * The device call is asynchronous on the caller's stream: no host synchronisation, nothing is
+ * rerun from the host.  Scratch is allocated by the first call with k >= 17 (callers with k <= 16
+ * pay nothing) and does not depend on n_batches: with P = rows rounded up to 64,
+ * 128 max(min(P, 2^20), 64 sample_groups(rows, 128)) bytes of keys, 2 x 16 MiB of candidate
+ * lists, 32 KiB ceil(P / 2^20) of chunk lists and under 1 MiB of outputs, bounds and counters. */
+VS_API int vs_i16_search_topk_dev(vs_i16* h, const float* queries_dev, int n_batches, int B, int k,
+                                  int32_t* ids_dev, int32_t* scores_dev, void* stream);
+/* Host-buffer form: batches of 32, the last one short.  Blocking. */
+VS_API int vs_i16_search_topk(vs_i16* h, const float* queries_host, int64_t nq, int k,
+                              int32_t* ids, int32_t* scores);
+/* Host only, no GPU: the sample of the wide pipeline for a base of n_rows rows at 17 <= k <= 128
+ * (VS_ERR_INVALID for a null out, n_rows < 1 or any other k).  out[0] = sample groups,
+ * out[1] = stride, out[2] = candidates stored per query (8192).  The rule:
+ *  - rows come in groups of 64: n_groups = ceil(n_rows / 64);
+ *  - L0 = max(64 k, ceil(n_rows k / 2048));
+ *  - sample_groups = min(n_groups, ceil(L0 / 64)); stride = n_groups / sample_groups (integer
+ *    division); the sample is the groups j stride for j < sample_groups.
+ * When sample_groups < n_groups every sample group is a full group (the last one sampled is at
+ * most n_groups - 2), so the sample holds at least 64 k rows; when sample_groups == n_groups the
+ * sample is the whole base.  The stride is deliberate: a prefix gives a useless bound on a base
+ * whose similar rows sit together, as the chunks of one document do.  A query's candidates are
+ * the rows whose score is at least the k-th best score of the sample. */
+VS_API int vs_i16_wide_plan(int64_t n_rows, int k, int64_t* out /* [3] */);
+/* Counters of the wide pipeline since the last reset, always kept; synchronises the device;
+ * reset != 0 clears them afterwards.  out[0] = queries ranked from their candidate lists,
+ * out[1] = the most candidates any one query had (the count, not the number stored: it may exceed
+ * 8192), out[2] = queries answered by the dense fallback (every query of a batch in which a list
+ * overflowed), out[3] = queries whose sample was the whole base.  All zeros before the first call
+ * with k >= 17.  VS_ERR_INVALID for null pointers. */
+VS_API int vs_i16_wide_stats(vs_i16* h, int64_t* out /* [4] */, int reset);
+
 /* ---------------------------------------------------------------------- IVF */
 /* IVFIndex ctor (IVFIndex.cpp:154-177): reads ivf_config.json, cluster_offsets.npy,
  * vectors_reordered.npy, reorder_to_original.npy (reordered mode) and

@@ -11,6 +11,8 @@
 // Errors: the IVF side throws std::runtime_error like the reference (IVFIndex.cpp:184-198,
 // main_ivf.cpp:287-290); the exact-search side returns bool like cpu_baseline.cpp:194-207.
 #pragma once
+#include <algorithm>
+#include <array>
 #include <cstdint>
 #include <stdexcept>
 #include <chrono>
@@ -232,6 +234,24 @@ public:
         ids.assign((size_t)nq * k, -1);
         scores.assign((size_t)nq * k, INT32_MIN);
         check(vs_i16_search(h_, queries.data(), nq, k, ids.data(), scores.data()));
+    }
+    // the same for k <= 128 (k <= 16 is search itself; vsearch.h at vs_i16_search_topk_dev)
+    void searchTopk(const std::vector<float>& queries, int64_t nq, int k, std::vector<int32_t>& ids, std::vector<int32_t>& scores) {
+        ids.assign((size_t)nq * std::max(k, 0), -1);
+        scores.assign((size_t)nq * std::max(k, 0), INT32_MIN);
+        check(vs_i16_search_topk(h_, queries.data(), nq, k, ids.data(), scores.data()));
+    }
+    // (sample groups, stride, candidate cap) of searchTopk at 17 <= k <= 128, on the host
+    static std::array<int64_t, 3> widePlan(int64_t rows, int k) {
+        std::array<int64_t, 3> out{};
+        check(vs_i16_wide_plan(rows, k, out.data()));
+        return out;
+    }
+    // (queries ranked from lists, most candidates of a query, queries of the dense fallback, queries with a whole-base sample)
+    std::array<int64_t, 4> wideStats(bool reset = false) {
+        std::array<int64_t, 4> out{};
+        check(vs_i16_wide_stats(h_, out.data(), reset ? 1 : 0));
+        return out;
     }
     vs_i16* handle() { return h_; }
 
