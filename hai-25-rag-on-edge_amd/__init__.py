@@ -155,6 +155,7 @@ def lib():
         "vs_ivf_search_dev_multi": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "vs_ivf_list_owners": (i32, [vp, i32, i32, vp]),
         "vs_topk_merge_dev": (i32, [vp, vp, i32, i32, i32, i64, i32, vp, vp, vp, vp]),
+        "vs_topk_merge_plan": (i32, [i32, i32, i32, vp]),
         "vs_comm_unique_id": (i32, [vp]),
         "vs_comm_create": (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
         "vs_comm_rank": (i32, [vp]),
@@ -919,6 +920,14 @@ def topk_merge_dev(dists_ptr: int, ids_ptr: int, G: int, B: int, kin: int, kout:
     """Merge G per-shard sorted lists (e.g. an RCCL all-gather receive buffer) on the device."""
     _check(lib().vs_topk_merge_dev(dists_ptr, ids_ptr, G, B, kin, stride_g, kout, out_d_ptr, out_i_ptr,
                                    flags_ptr, stream))
+
+
+def topk_merge_plan(G: int, kin: int, kout: int):
+    """(kernel, compacting capacity, flag window) of ``topk_merge_dev`` for a shape, without a GPU: kernel 0 is the
+    compacting merge, otherwise the lists per thread of the list-head merge (vsearch.h, vs_topk_merge_plan)."""
+    out = (C.c_int64 * 3)()
+    _check(lib().vs_topk_merge_plan(G, kin, kout, out))
+    return tuple(int(v) for v in out)
 
 
 # ------------------------------------------------------------------ IVF index building (host logic)

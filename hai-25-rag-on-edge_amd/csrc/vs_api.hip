@@ -3372,12 +3372,43 @@ __attribute__((visibility("default"))) int vs_debug_buffer(int* dev_ptr) {
 #endif
 
 // --------------------------------------------------------------------------------------- multi-GPU
+// vs::merge_plan for the ABI: the kernel of (G, kin) and the two constants into out[3] (may be null), or VS_ERR_UNSUPPORTED where there is none
+static int merge_plan_checked(const char* who, int G, int kin, int64_t* out) {
+    int cap = 0, track = 0;
+    const int lpt = vs::merge_plan(G, kin, &cap, &track);
+    if (lpt < 0) {
+        set_error(std::string(who) + ": G*kin = " + std::to_string((int64_t)G * kin) + " is above " + std::to_string(cap) +
+                  " and G = " + std::to_string(G) + " is above the largest supported there, " + std::to_string(vs::kMergeMaxLists));
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (out) {
+        out[0] = lpt;
+        out[1] = cap;
+        out[2] = track;
+    }
+    return VS_OK;
+}
+
+int vs_topk_merge_plan(int G, int kin, int kout, int64_t* out) {
+    if (!out || G < 1 || kin < 1 || kout < 1) {
+        set_error("vs_topk_merge_plan: bad arguments (out != NULL, G, kin, kout >= 1)");
+        return VS_ERR_INVALID;
+    }
+    return merge_plan_checked("vs_topk_merge_plan", G, kin, out);
+}
+
 int vs_topk_merge_dev(const float* dists_dev, const int32_t* ids_dev, int G, int B, int kin, int64_t stride_g,
                       int kout, float* out_dists_dev, int32_t* out_ids_dev, int32_t* flags_dev, void* stream) {
     if (!dists_dev || !ids_dev || !out_dists_dev || !out_ids_dev || G < 1 || B < 1 || kin < 1 || kout < 1) {
         set_error("vs_topk_merge_dev: bad arguments");
         return VS_ERR_INVALID;
     }
+    if (stride_g < 0 || (stride_g > 0 && stride_g < (int64_t)B * kin)) {
+        set_error("vs_topk_merge_dev: stride_g must be 0 (dense) or at least B*kin = " + std::to_string((int64_t)B * kin) +
+                  " (got " + std::to_string(stride_g) + ")");
+        return VS_ERR_INVALID;
+    }
+    if (int rc = merge_plan_checked("vs_topk_merge_dev", G, kin, nullptr)) return rc;
     vs::MergeParams m{};
     m.part_d = dists_dev;
     m.part_i = ids_dev;

@@ -154,6 +154,10 @@ __device__ __forceinline__ void wave_select_rounds(const float* cd, const int* c
         float bd;
         int bi;
         wave_lexmin(md, mi, bd, bi);
+        if (bd == 0.f) {  // (wave-uniform) -0.0 == +0.0: the minimum may carry the other zero's sign; the winner keeps its own bits
+            const unsigned long long own = __ballot(mi == bi && md == bd);
+            if (own != 0ull) bd = rdlane_f(md, __builtin_ctzll(own));
+        }
         emit(round, bd, bi);
 #pragma unroll
         for (int e = 0; e < EPL; ++e)

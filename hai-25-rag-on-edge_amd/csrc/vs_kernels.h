@@ -333,6 +333,11 @@ struct MergeParams {
 hipError_t launch_merge(const MergeParams& p, hipStream_t s);  // scan-partial layout [G][nq_stride][kin]
 // general layout: entry (g, q, j) at g*stride_g + q*stride_q + j
 hipError_t launch_merge_layout(const MergeParams& p, int64_t stride_g, int64_t stride_q, hipStream_t s);
+// Which kernel launch_merge_layout runs for G lists of kin entries (host only; the launch itself goes through this):
+// 0 = the compacting merge (G*kin <= cap), else the LPT of the merge_kernel instantiation (1, 2, 4 .. 64: lists per
+// thread), -1 = no kernel (G*kin > cap and G > kMergeMaxLists).  cap / track: kCompactCap / kMergeTrack (vs_merge.h).
+constexpr int kMergeMaxLists = 16384;
+int merge_plan(int G, int kin, int* cap, int* track);
 
 // Wide top-k (vs_topk_wide.hip): per query, the k1 <= kTopkWideMax smallest 64-bit keys (order-preserving bits of the
 // distance) << 32 | id out of a dense score block and / or up to two candidate lists -- i.e. the k1 best by (dist, id).

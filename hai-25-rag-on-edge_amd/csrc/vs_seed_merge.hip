@@ -369,7 +369,9 @@ __global__ __launch_bounds__(256) void merge_kernel(const MergeParams p, const M
             const int64_t off = (int64_t)g * L.stride_g + (int64_t)q * L.stride_q + j;
             d = p.part_d[off];
             id = p.part_i ? p.part_i[off] : (g * p.kin + j);
-            if (d != d) { d = VS_INF; id = -1; }  // NaN never wins
+            // a sorted list ends at its first entry that is not below +inf or has a negative id, as in the compacting
+            // merge: the head stays (+inf, -1) and never advances into what follows.  Without ids: NaN never wins.
+            if (p.part_i ? (!(d < VS_INF) || id < 0) : d != d) { d = VS_INF; id = -1; }
         } else {
             d = VS_INF;
             id = -1;
@@ -446,16 +448,27 @@ __global__ __launch_bounds__(256) void merge_kernel(const MergeParams p, const M
     }
 }
 
-static hipError_t launch_merge_heads(const MergeParams& p, const MergeLayout& L, hipStream_t s) {
-    const int lpt = (p.G + 255) / 256;
-    if (lpt <= 1) hipLaunchKernelGGL(merge_kernel<1>, dim3(p.nq), dim3(256), 0, s, p, L);
-    else if (lpt <= 2) hipLaunchKernelGGL(merge_kernel<2>, dim3(p.nq), dim3(256), 0, s, p, L);
-    else if (lpt <= 4) hipLaunchKernelGGL(merge_kernel<4>, dim3(p.nq), dim3(256), 0, s, p, L);
-    else if (lpt <= 8) hipLaunchKernelGGL(merge_kernel<8>, dim3(p.nq), dim3(256), 0, s, p, L);
-    else if (lpt <= 16) hipLaunchKernelGGL(merge_kernel<16>, dim3(p.nq), dim3(256), 0, s, p, L);
-    else if (lpt <= 32) hipLaunchKernelGGL(merge_kernel<32>, dim3(p.nq), dim3(256), 0, s, p, L);
-    else if (lpt <= 64) hipLaunchKernelGGL(merge_kernel<64>, dim3(p.nq), dim3(256), 0, s, p, L);  // (G <= 16384: the probe pick of the nlist > 4096 fallback)
-    else return hipErrorInvalidValue;
+int merge_plan(int G, int kin, int* cap, int* track) {
+    if (cap) *cap = kCompactCap;
+    if (track) *track = kMergeTrack;
+    if ((int64_t)G * kin <= kCompactCap) return 0;
+    if (G > kMergeMaxLists) return -1;
+    int lpt = 1;
+    while (256 * lpt < G) lpt *= 2;  // (G <= 16384 = 256 * 64: the probe pick of the nlist > 4096 fallback)
+    return lpt;
+}
+
+static hipError_t launch_merge_heads(const MergeParams& p, const MergeLayout& L, int lpt, hipStream_t s) {
+    switch (lpt) {
+    case 1: hipLaunchKernelGGL(merge_kernel<1>, dim3(p.nq), dim3(256), 0, s, p, L); break;
+    case 2: hipLaunchKernelGGL(merge_kernel<2>, dim3(p.nq), dim3(256), 0, s, p, L); break;
+    case 4: hipLaunchKernelGGL(merge_kernel<4>, dim3(p.nq), dim3(256), 0, s, p, L); break;
+    case 8: hipLaunchKernelGGL(merge_kernel<8>, dim3(p.nq), dim3(256), 0, s, p, L); break;
+    case 16: hipLaunchKernelGGL(merge_kernel<16>, dim3(p.nq), dim3(256), 0, s, p, L); break;
+    case 32: hipLaunchKernelGGL(merge_kernel<32>, dim3(p.nq), dim3(256), 0, s, p, L); break;
+    case 64: hipLaunchKernelGGL(merge_kernel<64>, dim3(p.nq), dim3(256), 0, s, p, L); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 
@@ -491,11 +504,12 @@ hipError_t launch_merge_layout(const MergeParams& p, int64_t stride_g, int64_t s
     MergeLayout L{stride_g, stride_q};
     if (p.run_mode == 3 && (!p.run_if || p.alt_G < 1 || (int64_t)p.alt_G * p.alt_kin > kCompactCap || (int64_t)p.G * p.kin > kCompactCap))
         return hipErrorInvalidValue;  // both parameter sets have to fit the compacting merge
-    if ((int64_t)p.G * p.kin <= kCompactCap) {
+    const int lpt = merge_plan(p.G, p.kin, nullptr, nullptr);
+    if (lpt == 0) {
         hipLaunchKernelGGL(merge_compact_kernel, dim3(p.nq), dim3(256), 0, s, p, L);
         return hipGetLastError();
     }
-    return launch_merge_heads(p, L, s);
+    return launch_merge_heads(p, L, lpt, s);
 }
 
 hipError_t launch_merge(const MergeParams& p, hipStream_t s) {

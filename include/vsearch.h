@@ -706,13 +706,33 @@ VS_API int vs_ivf_search_metric_dev_multi(vs_index* h, const float* queries_dev,
 VS_API int vs_ivf_list_owners(const int32_t* cluster_offsets, int nlist, int world, int32_t* owner_out);
 
 /* Merge G per-shard sorted lists (e.g. the receive buffer of an RCCL
- * all-gather) into [B x kout] by (dist, id) ascending; flags as above when
- * flags_dev != NULL.  Entry (g, b, j) lives at g*stride_g + b*kin + j in both
- * arrays; stride_g = 0 means the dense layout B*kin.  Runs on the current
- * device, asynchronously on `stream`. */
+ * all-gather) into [B x kout] by (dist, id) ascending.  Entry (g, b, j) lives
+ * at g*stride_g + b*kin + j in both arrays; stride_g = 0 means the dense
+ * layout B*kin.  Runs on the current device, asynchronously on `stream`.
+ *   Input.  Each list (g, b) is ascending by (dist, id).  A list ends at its first entry whose distance is not
+ *     < +inf (+inf or NaN) or whose id is negative; whatever follows in that list is ignored (it is read, never used).
+ *     The ids of one query are distinct across its G lists and lie in [0, 2^31 - 2]; the result is unspecified
+ *     otherwise (2^31 - 1 is taken as "none", and the kernels disagree on repeated ids).  The inputs are not written.
+ *   Output.  Row b holds the kout smallest of the pooled entries of query b by (dist, id): equal distances
+ *     (-0.0 == +0.0) are ordered by ascending id, and each output distance carries the bits of the entry it came from
+ *     (zero signs, subnormals and -inf included).  Slots past the pooled entries are (+inf, -1); kout may exceed kin
+ *     and G*kin.
+ *   flags_dev (may be NULL): flags[b] = 1 iff two adjacent outputs among the first min(kout, 256) have equal
+ *     distances below +inf (the +inf tail is no tie; two -inf are one), else 0.  A tie further down a longer output
+ *     is not looked for.
+ *   Limits.  G, B, kin, kout >= 1.  stride_g is 0 or >= B*kin: VS_ERR_INVALID otherwise (a smaller stride would alias
+ *     the groups).  G*kin <= 4096 takes any G; above that G <= 16384, else VS_ERR_UNSUPPORTED.  All of these are
+ *     refused before any device work.
+ * vs_topk_merge_plan (host only, no GPU needed) tells which kernel a shape runs on, so that a test can assert the
+ * precondition of the path it is about: out[0] = 0 for the compacting kernel (G*kin <= out[1]; it pools a query's
+ * entries on chip and ranks them by their number), else the lists per thread of the list-head kernel (1, 2, 4, 8, 16,
+ * 32 or 64: the smallest power of two with 256*out[0] >= G); out[1] = 4096, the compacting kernel's capacity; out[2] =
+ * 256, the outputs among which flags looks for a tie.  It refuses what vs_topk_merge_dev refuses for (G, kin, kout),
+ * with the same codes; the launch goes through the same rule. */
 VS_API int vs_topk_merge_dev(const float* dists_dev, const int32_t* ids_dev, int G, int B, int kin,
                              int64_t stride_g, int kout, float* out_dists_dev, int32_t* out_ids_dev,
                              int32_t* flags_dev, void* stream);
+VS_API int vs_topk_merge_plan(int G, int kin, int kout, int64_t* out /* [3] */);
 
 /* One process per GPU.  A vs_comm owns an RCCL communicator over the ranks of the job, a stream for
  * the collective and the exchange buffers.  Bootstrap like any NCCL program: rank 0 calls vs_comm_unique_id and
