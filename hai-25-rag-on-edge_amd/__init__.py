@@ -182,6 +182,10 @@ def lib():
         "vs_q8_execute": (i32, [vp, vp, i32, vp]),
         "vs_q8_search_dev": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
         "vs_q8_search": (i32, [vp, vp, i64, i32, vp, vp]),
+        "vs_q8_search_topk_dev": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+        "vs_q8_search_topk": (i32, [vp, vp, i64, i32, vp, vp]),
+        "vs_q8_topk_scores_dev": (i32, [vp, vp, i64, i32, i32, vp, vp, vp]),
+        "vs_q8_wide_plan": (i32, [i64, i32, vp]),
         "vs_i16_quantize": (i32, [vp, i64, i32, C.c_float, vp]),
         "vs_i16_write_bin": (i32, [C.c_char_p, vp, i64, i32, C.c_float, i64]),
         "vs_i16_create": (i32, [vp, i64, i32, C.c_float, i32, i64, C.POINTER(vp)]),
@@ -576,6 +580,31 @@ class Q8Runner:
 
     def search_dev(self, q_ptr: int, n_batches: int, B: int, k: int, ids_ptr: int, scores_ptr: int, stream: int):
         _check(lib().vs_q8_search_dev(self._h, q_ptr, n_batches, B, k, ids_ptr, scores_ptr, stream))
+
+    def search_topk(self, queries, k: int):
+        """``search`` for k up to 128 (k <= 16 is ``search`` itself): ids [nq, k] and uint8 scores [nq, k], largest first,
+        equal scores in ascending id; slots past the rows are (-1, 0)."""
+        q = _f32c(queries).reshape(-1, self.getDim())
+        ids = np.empty((q.shape[0], max(k, 0)), dtype=np.int32)
+        top = np.empty((q.shape[0], max(k, 0)), dtype=np.uint8)
+        _check(lib().vs_q8_search_topk(self._h, _p(q), q.shape[0], k, _p(ids), _p(top)))
+        return ids, top
+
+    def search_topk_dev(self, q_ptr: int, n_batches: int, B: int, k: int, ids_ptr: int, scores_ptr: int, stream: int):
+        """``search_dev`` for k up to 128: asynchronous on ``stream``, no host synchronisation."""
+        _check(lib().vs_q8_search_topk_dev(self._h, q_ptr, n_batches, B, k, ids_ptr, scores_ptr, stream))
+
+    def topk_scores_dev(self, scores_ptr: int, ld: int, B: int, k: int, ids_ptr: int, top_ptr: int, stream: int):
+        """The top-k stage alone (find_top_k_batch_parallel, main.cpp:59-71) on a caller-owned uint8 buffer of B rows of ld
+        bytes, the first getNumDocs() of each the scores; ld a multiple of 64, the pointer 16-byte aligned; k <= 128."""
+        _check(lib().vs_q8_topk_scores_dev(self._h, scores_ptr, ld, B, k, ids_ptr, top_ptr, stream))
+
+
+def q8_wide_plan(n_rows: int, k: int):
+    """(chunks per query, rows per chunk, device scratch bytes) of ``Q8Runner.search_topk`` for 17 <= k <= 128."""
+    out = (C.c_int64 * 3)()
+    _check(lib().vs_q8_wide_plan(n_rows, k, out))
+    return tuple(int(v) for v in out)
 
 
 def i16_quantize(x, scale: float = 1000.0) -> np.ndarray:

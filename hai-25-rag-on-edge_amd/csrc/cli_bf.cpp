@@ -8,7 +8,8 @@
 //                                                slots are accepted and ignored, results_dir gets results.txt + metrics.txt
 //   ... --q8[=in_scale,w_scale,w_offset,out_scale]: the qidk form through the runner's UFIXED_POINT_8 path (QnnRunner.cpp:
 //                                                13-55, 608-645; main.cpp:30-57): uint8 scores, results.txt holds
-//                                                (id, score8 * output_scale) with 4 decimals (main.cpp:244-246)
+//                                                (id, score8 * output_scale) with 4 decimals (main.cpp:244-246);
+//                                                1 <= top_k <= 128 (vs_q8_search_topk)
 //   vsearch_bf --groundtruth <base.fvecs> <query.fvecs> <out.ivecs> [k=100]
 //                                              : exact k-NN ground truth (TEXMEX .ivecs: one row of k ids per query, the
 //                                                ids of vs_bf_search_topk, 1 <= k <= 128), for vsearch_ivf's recall; one GPU
@@ -301,9 +302,9 @@ bool run_q8(const std::string& docs_file, const std::string& query_file, int k, 
                   << e.weight_offset << ", output scale " << e.output_scale << std::endl;
         std::vector<int32_t> ids;
         std::vector<uint8_t> top;
-        runner.search(Q_data, std::min(Q_rows, 32), k, ids, top);  // untimed warm-up (kernel code loads)
+        runner.searchTopk(Q_data, std::min(Q_rows, 32), k, ids, top);  // untimed warm-up (kernel code loads)
         const auto t0 = high_resolution_clock::now();
-        runner.search(Q_data, Q_rows, k, ids, top);
+        runner.searchTopk(Q_data, Q_rows, k, ids, top);
         const double total_s = duration_cast<duration<double>>(high_resolution_clock::now() - t0).count();
         std::vector<float> scores((size_t)Q_rows * k);
         for (size_t i = 0; i < scores.size(); ++i) scores[i] = static_cast<float>(top[i]) * e.output_scale;  // main.cpp:244
@@ -444,6 +445,13 @@ int main(int argc, char* argv[]) {
             return 1;
         }
         return run_groundtruth(argv[1], argv[2], argv[3], k) ? 0 : 1;
+    }
+    if (q8 && (argc == 7 || argc == 8)) {  // the quantised runner: k in 1..128 (vs_q8_search_topk)
+        int k = 0;
+        if (vsearch::arg_int(argv[6], k) && (k < 1 || k > 128)) {
+            std::cerr << "FATAL ERROR: --q8: top_k must be in 1..128\n" << kUsage;
+            return 1;
+        }
     }
     if (!q8 && argc >= 5 && argc <= 8) {  // the positional and qidk forms: k in 1..128, and k > 15 on one GPU only
         int k = 0;

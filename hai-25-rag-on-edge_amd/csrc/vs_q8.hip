@@ -26,6 +26,8 @@
 // The first two are the 128-d kernels (vs_q8_create).  A runner made by vs_q8_create_nd at any other vector dimension
 // (1 to 2048) takes q8_quantize_queries_nd_kernel and q8_scores_nd_kernel of vs_q8_nd.hip in their place, on rows padded
 // to 64 bytes; the top-k kernels work on the score matrix and serve both.
+// k up to 128 (vs_q8_search_topk*, vs_q8_topk_scores_dev): 17 <= k <= 128 is the counting select of vs_q8_wide.hip on the
+// same matrix -- histogram per chunk, cut value per query, scatter into sorted place -- launched from here.
 // Order of equal scores: ascending row number (the reference's order among equal uint8 scores is whatever its C++
 // library's heap leaves, main.cpp:36-57).
 #include <hip/hip_runtime.h>
@@ -44,6 +46,7 @@
 #include "vs_q8_nd.h"
 #include "vs_res.h"
 
+using vs::count_ge;
 using vs::q8_sat;
 using vs::set_error;
 
@@ -62,8 +65,9 @@ constexpr int kDim = 128;
 constexpr int kBatch = vs::kQ8Batch;
 constexpr int kGroup = 32;          // batches whose queries one quantiser launch prepares
 constexpr int kGroupRows = vs::kQ8GroupRows;  // rows a wave scores per step
-constexpr int kChunkRows = 16384;   // rows per top-k chunk (256 threads x 64 bytes)
+constexpr int kChunkRows = vs::kQ8ChunkRows;  // rows per top-k chunk (256 threads x 64 bytes)
 constexpr int kCand = 16;           // candidate slots per (chunk, query); k <= 16
+constexpr int kWideK = vs::kQ8WideK;  // the largest k of the counting select (vs_q8_wide.hip)
 constexpr int kIpBias = 128 * 128 * kDim;  // sum over t of 128 * 128
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -154,23 +158,7 @@ __global__ __launch_bounds__(256) void q8_scores_kernel(const int8_t* __restrict
     }
 }
 
-// 128 * (number of bytes of x that are >= the byte replicated in m4), added to acc.  m7 = m4 & 0x7f7f7f7f, nm = ~m4.
-__device__ __forceinline__ unsigned ge_bytes_acc(unsigned x, unsigned m4, unsigned m7, unsigned nm, unsigned acc) {
-    const unsigned H = 0x80808080u;
-    const unsigned t = (x | H) - m7;                    // per byte (x | 0x80) - (m & 0x7f): no borrow crosses bytes
-    const unsigned ge = ((x & nm) | (~(x ^ m4) & t)) & H;  // bit 7 of a byte: x >= m (unsigned)
-    return __builtin_amdgcn_udot4(ge, 0x01010101u, acc, false);
-}
-
-// bytes of the thread's 16 words that are >= mid (mid in 1..255)
-__device__ __forceinline__ int count_ge(const unsigned (&w)[16], int mid) {
-    const unsigned m4 = 0x01010101u * (unsigned)mid, m7 = m4 & 0x7f7f7f7fu, nm = ~m4;
-    unsigned a = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) a = ge_bytes_acc(w[j], m4, m7, nm, a);
-    return (int)(a >> 7);
-}
-
+// (count_ge, the SWAR count of a thread's bytes at or above a value, is in vs_q8_nd.h: the counting select shares it)
 __device__ __forceinline__ int block_sum_256(int v, int* sh) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -380,6 +368,16 @@ __global__ __launch_bounds__(256) void q8_topk_chunk_kernel(const uint8_t* __res
 
 }  // namespace
 
+// scratch of the counting select (17 <= k <= 128), made by the first call that needs it (ensure_wide)
+struct vs_q8_wide_scratch {
+    vs::DevBuf<uint32_t> hist;  // [32][n_chunks][256] counts, then output positions (vs_q8_wide.hip)
+    vs::DevBuf<int32_t> cut;    // [32]
+    vs::DevBuf<uint32_t> flag;  // [32][n_chunks]
+    vs::DevBuf<int32_t> ids;    // [32][128] results of the host form
+    vs::DevBuf<uint8_t> top;    // [32][128]
+    bool ready = false;
+};
+
 struct vs_q8 {
     int device = 0;
     int dim = kDim, dim_b = kDim;  // vector length; row bytes (dim rounded up to 64)
@@ -398,6 +396,7 @@ struct vs_q8 {
     vs::DevBuf<u64> d_cand;        // [32][n_chunks][kCand]
     vs::DevBuf<int32_t> d_ids;     // [32][16]
     vs::DevBuf<uint8_t> d_top;     // [32][16]
+    vs_q8_wide_scratch wide;
     int n_chunks = 0;
     vs::Stream stream;
 };
@@ -591,10 +590,58 @@ int q8_execute_enqueue(vs_q8* h, const float* q_dev, int B, uint8_t* scores_dev,
     return rc ? rc : q8_scores_enqueue(h, 0, B, scores_dev, ld, s);
 }
 
-int q8_topk_enqueue(vs_q8* h, int B, int k, int32_t* ids_dev, uint8_t* top_dev, hipStream_t s) {
-    hipLaunchKernelGGL(q8_topk_chunk_kernel, dim3(h->n_chunks, B), dim3(256), 0, s, h->d_scores, h->n_pad, h->n_rows, k, h->n_chunks, h->d_cand);
+// k <= 16 over scores [B][ld] (the runner's own matrix: h->d_scores, h->n_pad)
+int q8_topk_enqueue(vs_q8* h, const uint8_t* scores, int64_t ld, int B, int k, int32_t* ids_dev, uint8_t* top_dev, hipStream_t s) {
+    hipLaunchKernelGGL(q8_topk_chunk_kernel, dim3(h->n_chunks, B), dim3(256), 0, s, scores, ld, h->n_rows, k, h->n_chunks, h->d_cand);
     hipLaunchKernelGGL(q8_topk_final_kernel, dim3(B), dim3(256), 0, s, h->d_cand, h->n_chunks, k, h->id_offset, ids_dev, top_dev);
     HIPCHK(hipGetLastError());
+    return VS_OK;
+}
+
+// Element counts of the wide scratch for n_chunks chunks: hist, cut, flag, host-form ids, host-form scores.  The one place
+// that sizes it: vs_q8_wide_plan reports the bytes, ensure_wide allocates them.
+struct WideSizes {
+    size_t hist, cut, flag, ids, top;
+    size_t bytes() const { return 4 * hist + 4 * cut + 4 * flag + 4 * ids + top; }
+};
+WideSizes wide_sizes(int64_t n_chunks) {
+    return {(size_t)kBatch * (size_t)n_chunks * 256, (size_t)kBatch, (size_t)kBatch * (size_t)n_chunks, (size_t)kBatch * kWideK,
+            (size_t)kBatch * kWideK};
+}
+
+// all or nothing: a failed allocation frees what was made and leaves the runner as it was
+int ensure_wide(vs_q8* h) {
+    if (h->wide.ready) return VS_OK;
+    const WideSizes z = wide_sizes(h->n_chunks);
+    vs_q8_wide_scratch w;
+    int rc;
+    if ((rc = w.hist.alloc(z.hist)) || (rc = w.cut.alloc(z.cut)) || (rc = w.flag.alloc(z.flag)) || (rc = w.ids.alloc(z.ids)) ||
+        (rc = w.top.alloc(z.top)))
+        return rc;
+    w.ready = true;
+    h->wide = std::move(w);
+    return VS_OK;
+}
+
+// 17 <= k <= 128 over scores [B][ld]: the counting select, three launches
+int q8_wide_enqueue(vs_q8* h, const uint8_t* scores, int64_t ld, int B, int k, int32_t* ids_dev, uint8_t* top_dev, hipStream_t s) {
+    vs_q8_wide_scratch& w = h->wide;
+    HIPCHK(vs::launch_q8_hist(scores, ld, h->n_rows, h->n_chunks, B, w.hist, s));
+    HIPCHK(vs::launch_q8_cut(w.hist, h->n_rows, h->n_chunks, B, k, w.cut, w.flag, ids_dev, top_dev, s));
+    HIPCHK(vs::launch_q8_scatter(scores, ld, h->n_rows, h->n_chunks, B, k, h->id_offset, w.hist, w.cut, w.flag, ids_dev, top_dev, s));
+    return VS_OK;
+}
+
+// the checks the three _topk calls share behind their pointers: k < 1 invalid, k > 128 unsupported
+int wide_k_check(const char* who, int k) {
+    if (k < 1) {
+        set_error(std::string(who) + ": k must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (k > kWideK) {
+        set_error(std::string(who) + ": k > 128 is not supported");
+        return VS_ERR_UNSUPPORTED;
+    }
     return VS_OK;
 }
 
@@ -673,7 +720,9 @@ int vs_q8_search_dev(vs_q8* h, const float* queries_dev, int n_batches, int B, i
         if (rc) return rc;
         for (int j = 0; j < gs; ++j) {
             const size_t o = (size_t)(g0 + j) * B * k;
-            if ((rc = q8_scores_enqueue(h, j, B, h->d_scores, h->n_pad, s)) || (rc = q8_topk_enqueue(h, B, k, ids_dev + o, scores_dev + o, s))) return rc;
+            if ((rc = q8_scores_enqueue(h, j, B, h->d_scores, h->n_pad, s)) ||
+                (rc = q8_topk_enqueue(h, h->d_scores, h->n_pad, B, k, ids_dev + o, scores_dev + o, s)))
+                return rc;
         }
     }
     return VS_OK;
@@ -693,11 +742,89 @@ int vs_q8_search(vs_q8* h, const float* queries_host, int64_t nq, int k, int32_t
         const int B = (int)std::min<int64_t>(kBatch, nq - q0);
         HIPCHK(hipMemcpyAsync(h->d_q, queries_host + (size_t)q0 * h->dim, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, h->stream));
         int rc = q8_execute_enqueue(h, h->d_q, B, h->d_scores, h->n_pad, h->stream);
-        if (rc || (rc = q8_topk_enqueue(h, B, k, h->d_ids, h->d_top, h->stream))) return rc;
+        if (rc || (rc = q8_topk_enqueue(h, h->d_scores, h->n_pad, B, k, h->d_ids, h->d_top, h->stream))) return rc;
         HIPCHK(hipMemcpyAsync(ids + (size_t)q0 * k, h->d_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(scores + (size_t)q0 * k, h->d_top, (size_t)B * k, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
+    return VS_OK;
+}
+
+int vs_q8_search_topk_dev(vs_q8* h, const float* queries_dev, int n_batches, int B, int k, int32_t* ids_dev, uint8_t* scores_dev,
+                          void* stream) {
+    if (!h || !queries_dev || !ids_dev || !scores_dev || n_batches < 1 || B < 1 || B > kBatch) {
+        set_error("vs_q8_search_topk_dev: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    int rc = wide_k_check("vs_q8_search_topk_dev", k);
+    if (rc) return rc;
+    if (k <= kCand) return vs_q8_search_dev(h, queries_dev, n_batches, B, k, ids_dev, scores_dev, stream);
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = ensure_wide(h))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int g0 = 0; g0 < n_batches; g0 += kGroup) {  // as vs_q8_search_dev: one quantiser launch per group, then per batch
+        const int gs = std::min(kGroup, n_batches - g0);  // the score kernel and the three launches of the counting select
+        if ((rc = q8_quantize_enqueue(h, queries_dev + (size_t)g0 * B * h->dim, gs, B, s))) return rc;
+        for (int j = 0; j < gs; ++j) {
+            const size_t o = (size_t)(g0 + j) * B * k;
+            if ((rc = q8_scores_enqueue(h, j, B, h->d_scores, h->n_pad, s)) ||
+                (rc = q8_wide_enqueue(h, h->d_scores, h->n_pad, B, k, ids_dev + o, scores_dev + o, s)))
+                return rc;
+        }
+    }
+    return VS_OK;
+}
+
+int vs_q8_search_topk(vs_q8* h, const float* queries_host, int64_t nq, int k, int32_t* ids, uint8_t* scores) {
+    if (!h || !queries_host || !ids || !scores || nq < 0) {
+        set_error("vs_q8_search_topk: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    int rc = wide_k_check("vs_q8_search_topk", k);
+    if (rc) return rc;
+    if (k <= kCand) return vs_q8_search(h, queries_host, nq, k, ids, scores);
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = ensure_wide(h))) return rc;
+    for (int64_t q0 = 0; q0 < nq; q0 += kBatch) {  // the loop of vs_q8_search
+        const int B = (int)std::min<int64_t>(kBatch, nq - q0);
+        HIPCHK(hipMemcpyAsync(h->d_q, queries_host + (size_t)q0 * h->dim, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, h->stream));
+        rc = q8_execute_enqueue(h, h->d_q, B, h->d_scores, h->n_pad, h->stream);
+        if (rc || (rc = q8_wide_enqueue(h, h->d_scores, h->n_pad, B, k, h->wide.ids, h->wide.top, h->stream))) return rc;
+        HIPCHK(hipMemcpyAsync(ids + (size_t)q0 * k, h->wide.ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(scores + (size_t)q0 * k, h->wide.top, (size_t)B * k, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return VS_OK;
+}
+
+int vs_q8_topk_scores_dev(vs_q8* h, const uint8_t* scores_dev, int64_t ld, int B, int k, int32_t* ids_dev, uint8_t* top_dev,
+                          void* stream) {
+    if (!h || !scores_dev || !ids_dev || !top_dev || B < 1 || B > kBatch) {
+        set_error("vs_q8_topk_scores_dev: bad arguments");
+        return VS_ERR_INVALID;
+    }
+    if (ld < h->n_rows || ld % 64 != 0 || reinterpret_cast<uintptr_t>(scores_dev) % 16 != 0) {
+        set_error("vs_q8_topk_scores_dev: ld must be a multiple of 64 and at least the rows, scores_dev 16-byte aligned");
+        return VS_ERR_INVALID;
+    }
+    int rc = wide_k_check("vs_q8_topk_scores_dev", k);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (k <= kCand) return q8_topk_enqueue(h, scores_dev, ld, B, k, ids_dev, top_dev, s);
+    if ((rc = ensure_wide(h))) return rc;
+    return q8_wide_enqueue(h, scores_dev, ld, B, k, ids_dev, top_dev, s);
+}
+
+int vs_q8_wide_plan(int64_t n_rows, int k, int64_t* out) {
+    if (!out || n_rows < 1 || k <= kCand || k > kWideK) {
+        set_error("vs_q8_wide_plan: bad arguments (n_rows >= 1, 17 <= k <= 128)");
+        return VS_ERR_INVALID;
+    }
+    const int64_t n_chunks = (n_rows + kChunkRows - 1) / kChunkRows;
+    out[0] = n_chunks;
+    out[1] = kChunkRows;
+    out[2] = (int64_t)wide_sizes(n_chunks).bytes();
     return VS_OK;
 }
 

@@ -308,7 +308,7 @@ VS_API int vs_q8_create(const float* base_host, int64_t n_rows, int dim, const v
  * general runner at 128 as well: the comparison toggle).  Any other dim gives a "general"
  * runner: rows as int8 (w8 - 128) padded with zeros to a multiple of 64 bytes, scored by a kernel
  * that walks the row in 128-byte steps.  Every vs_q8_* call below accepts it with the same
- * signatures and output layouts; queries are [B][dim] floats, unpadded; k <= 16 stays;
+ * signatures and output layouts; queries are [B][dim] floats, unpadded; k <= 16 stays (k <= 128: the _topk calls);
  * vs_q8_dim returns dim.  enc == NULL: as above, weight_scale over all n_rows * dim values.
  * The arithmetic is the one stated above, with t < dim; ip is exact in int32 (|ip| <= 255 * 255 *
  * 2048 < 2^27) and (float)ip is its one round-to-nearest conversion, inexact above 2^24 exactly
@@ -338,6 +338,48 @@ VS_API int vs_q8_search_dev(vs_q8* h, const float* queries_dev, int n_batches, i
  * short). Blocking. */
 VS_API int vs_q8_search(vs_q8* h, const float* queries_host, int64_t nq, int k, int32_t* ids,
                         uint8_t* scores);
+
+/* The same for k up to 128 (find_top_k_int8 takes any top_k, main.cpp:36-57, 85).  Layouts and
+ * meaning are those of vs_q8_search_dev / vs_q8_search: [n_batches*B x k] ([nq x k] for the host
+ * form), largest score first, equal scores in ascending id, ids include id_offset, slots past the
+ * rows are (-1, 0), 1 <= B <= 32.  Checked in this order: null pointers (a NULL handle is refused
+ * without touching a device), n_batches < 1, B out of range or nq < 0: VS_ERR_INVALID; k < 1:
+ * VS_ERR_INVALID; k > 128: VS_ERR_UNSUPPORTED.
+ *  - k <= 16: the call IS vs_q8_search_dev / vs_q8_search (same launches, same results).
+ *  - 17 <= k <= 128: per batch the quantiser and score kernel as above (one quantiser launch per
+ *    group of 32 batches), then a counting select over the score matrix in three launches: the
+ *    256-bin histogram of every 16384-row chunk; per query the cut value t = the largest score
+ *    with at least min(k, rows) rows at or above it, from a suffix sum, and for every value at or
+ *    above t the output position of each chunk's first row of that value; then every chunk that
+ *    holds a row to be returned writes its rows straight into their sorted places (of the rows
+ *    equal to t, the lowest-numbered ones).  No sort, no candidate cap, no fallback, no atomics on
+ *    global memory: exact by construction, the same bits on every run, at a cost that does not
+ *    depend on the score distribution.  Bytes of the matrix past the last row are never counted.
+ * The device call is asynchronous on the caller's stream: no host synchronisation, nothing is
+ * rerun from the host.  Scratch is allocated by the first call with k >= 17, all or nothing
+ * (callers with k <= 16 pay nothing), and does not depend on n_batches: vs_q8_wide_plan. */
+VS_API int vs_q8_search_topk_dev(vs_q8* h, const float* queries_dev, int n_batches, int B, int k,
+                                 int32_t* ids_dev, uint8_t* scores_dev, void* stream);
+/* Host-buffer form: batches of 32, the last one short.  Blocking. */
+VS_API int vs_q8_search_topk(vs_q8* h, const float* queries_host, int64_t nq, int k,
+                             int32_t* ids, uint8_t* scores);
+/* find_top_k_batch_parallel (main.cpp:59-71) on a raw score buffer the caller owns, as the harness
+ * ranks the buffer of getRawOutputBuffer: B rows of ld bytes, of which the first
+ * vs_q8_num_docs(h) are the scores of the runner's rows (ids include id_offset); the bytes from
+ * there to ld may hold anything and are ignored.  ids_dev / top_dev are [B x k] as above.
+ * ld >= rows, ld % 64 == 0 and a 16-byte aligned scores_dev, otherwise VS_ERR_INVALID before any
+ * device work; then k < 1: VS_ERR_INVALID, k > 128: VS_ERR_UNSUPPORTED.  k <= 16 runs the chunk
+ * and final kernels of vs_q8_search_dev on that buffer, 17 <= k <= 128 the counting select.
+ * Asynchronous on the caller's stream. */
+VS_API int vs_q8_topk_scores_dev(vs_q8* h, const uint8_t* scores_dev, int64_t ld, int B, int k,
+                                 int32_t* ids_dev, uint8_t* top_dev, void* stream);
+/* Host only, no GPU: the counting select for a runner of n_rows rows at 17 <= k <= 128
+ * (VS_ERR_INVALID for a null out, n_rows < 1 or any other k).  out[0] = chunks per query =
+ * ceil(n_rows / 16384), out[1] = 16384, out[2] = the device scratch bytes the first wide call
+ * allocates (the launch code sizes its allocation through the same function): with C = out[0],
+ * 32 C 1024 of histograms / positions, 32 * 4 of cut values, 32 C 4 of chunk flags and
+ * 32 * 128 * (4 + 1) of host-form results. */
+VS_API int vs_q8_wide_plan(int64_t n_rows, int k, int64_t* out /* [3] */);
 
 /* ------------------------------------------- int16 cosine score path */
 /* The reference's third score path (AMD_npu/): Codes/preprocess.py:24-42 L2-normalises every

@@ -192,6 +192,12 @@ public:
         scores.assign((size_t)nq * k, 0);
         check(vs_q8_search(h_, queries.data(), nq, k, ids.data(), scores.data()));
     }
+    // the same for k <= 128 (k <= 16 is search itself; vsearch.h at vs_q8_search_topk_dev)
+    void searchTopk(const std::vector<float>& queries, int64_t nq, int k, std::vector<int32_t>& ids, std::vector<uint8_t>& scores) {
+        ids.assign((size_t)nq * std::max(k, 0), -1);
+        scores.assign((size_t)nq * std::max(k, 0), 0);
+        check(vs_q8_search_topk(h_, queries.data(), nq, k, ids.data(), scores.data()));
+    }
     vs_q8* handle() { return h_; }
 
 private:
