@@ -156,6 +156,7 @@ def lib():
         "vs_ivf_list_owners": (i32, [vp, i32, i32, vp]),
         "vs_topk_merge_dev": (i32, [vp, vp, i32, i32, i32, i64, i32, vp, vp, vp, vp]),
         "vs_topk_merge_plan": (i32, [i32, i32, i32, vp]),
+        "vs_bf_one_plan": (i32, [i64, i32, i32, i32, i32, i32, vp]),
         "vs_comm_unique_id": (i32, [vp]),
         "vs_comm_create": (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
         "vs_comm_rank": (i32, [vp]),
@@ -480,6 +481,15 @@ class BruteForceIndex(_Index):
                               flags_ptr: int, stream: int):
         """``search_dev_multi`` for 1 <= k <= 128 (vs_bf_search_topk_dev_multi): outputs are [n_batches*B, k+1]."""
         _check(lib().vs_bf_search_topk_dev_multi(self._h, q_ptr, n_batches, B, k, ids_ptr, dists_ptr, flags_ptr, stream))
+
+    @staticmethod
+    def one_plan(n_rows: int, dim: int, num_cus: int, n_batches: int, B: int, k: int):
+        """(route, workgroups, rows per unit of work, most units of any one wave) of the single-call scan for a call of
+        n_batches batches of B queries on the fp32 rows of an [n_rows, dim] index (vs_bf_one_plan; host only): route 0 =
+        no single-call launch, 1 = the 128-d kernel, 2 = the general-dimension kernel."""
+        out = (C.c_int64 * 4)()
+        _check(lib().vs_bf_one_plan(n_rows, dim, num_cus, n_batches, B, k, out))
+        return tuple(int(x) for x in out)
 
     @staticmethod
     def search_vshards(shards, queries: np.ndarray, k: int, timing: "Timing | None" = None):

@@ -88,6 +88,7 @@ struct vs_index {
     // ivf_scan_nd_i8_kernel for the queries that qualify).
     bool general = false;
     int dim_p = 0;
+    bool nd_one = true;  // general brute-force index: short calls on the fp32 rows take scan_one_nd_kernel (VSEARCH_ND_ONE=0 at creation: off)
     vs::DevBuf<float> d_nd_qfrag;  // [kMaxMulti][dim_p / 16][2][64][4] scratch of launch_scan_nd
     vs::DevBuf<float> d_nd_qnorm;  // [kMaxMulti][32]
     // general index made from uint8 rows (vs_bf_create_nd_u8, vs_bf_create_nd_u8_metric): the rows once more as int8
@@ -754,6 +755,40 @@ int ensure_wide(vs_index::Lane& L) {
 
 int pick_kcap(int need) { return need <= 8 ? 8 : (need <= 16 ? 16 : 0); }
 
+// whether a call of nb batches on the specialised 128-d index takes its bounds from the seed launches (bf_launch)
+bool bf_seeded(int64_t n_rows, int nb, int k1) {
+    const int64_t tiles_total = (n_rows + vs::kTileRows - 1) / vs::kTileRows;
+    // The streaming scans' candidate buffers are sized for what survives the seeded bounds: about n_rows * k1 / 32768 rows per
+    // query (the sample is 32 768 rows), in kWideSub sub-lists of kWideCap entries.  A shard on which that expectation passes
+    // half the capacity (5.6 M rows at k = 5) would overflow on nearly every launch and run the fallback scan as well:
+    // it takes the per-batch scan directly.
+    const bool cap_ok = (double)n_rows * k1 <= 0.5 * 32768.0 * kWideSub * kWideCap;
+    return nb >= g_seed_min_batches && tiles_total >= 2 * vs::kSeedWaves && g_xchg_first_it >= 0 && cap_ok;
+}
+
+// The single-call route of a call that reads the fp32 rows (vs_bf_one_plan's rule; bf_launch goes through it): 0 = none,
+// 1 = scan_one_kernel (the specialised 128-d index), 2 = scan_one_nd_kernel (a general index), with the
+// launch's workgroups, the rows of a wave's unit of work and the most units any one wave gets in out[1..3] (route 1
+// hands its units out through a ticket: the even share).
+int one_route(int64_t n_rows, bool general, int num_cus, int nb, int B, int k1, int64_t* out) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (nb >= kOneMaxBatches || B > kOneMaxQueries || k1 > 16) return 0;
+    if (general) {
+        if (n_rows > 0x7fffffff - 2 * vs::kOneNdUnit) return 0;  // (the kernel counts rows in 32 bits)
+        out[0] = 2;
+        out[2] = vs::kOneNdUnit;
+        vs::scan_one_nd_geometry(n_rows, num_cus, &out[1], &out[3]);
+        return 2;
+    }
+    if (bf_seeded(n_rows, nb, k1)) return 0;
+    const int64_t tiles = (n_rows + vs::kTileRows - 1) / vs::kTileRows;
+    out[0] = 1;
+    out[1] = vs::scan_one_grid(n_rows, num_cus);
+    out[2] = vs::kTileRows;
+    out[3] = (tiles + out[1] * vs::kScanWaves - 1) / (out[1] * vs::kScanWaves);
+    return 1;
+}
+
 // nb <= kMaxMulti batches of B queries in ONE persistent launch on stream s (preceded by the seed launches or the
 // slot reset, followed by one merge launch), outputs [nb][B][k1].  Consecutive calls on one lane must be stream-ordered.
 int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B, int k1, float* out_d, int32_t* out_i,
@@ -782,13 +817,8 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     // sample tiles are a minority of it); a short call keeps the in-kernel exchange, which needs a few tiles per
     // wave after its warm-up tiles (int8 tiles hold 64 rows)
     const int64_t tiles_total = (h->n_rows + vs::kTileRows - 1) / vs::kTileRows;
-    // The streaming scans' candidate buffers are sized for what survives the seeded bounds: about n_rows * k1 / 32768 rows per
-    // query (the sample is 32 768 rows), in kWideSub sub-lists of kWideCap entries.  A shard on which that expectation passes
-    // half the capacity (5.6 M rows at k = 5) would overflow on nearly every launch and run the fallback scan as well:
-    // it takes the per-batch scan directly.
-    const bool cap_ok = (double)h->n_rows * k1 <= 0.5 * 32768.0 * kWideSub * kWideCap;
     // (a general index has no seed sample and no streaming scan: per-batch scan_nd_kernel + merge, with the threshold exchange)
-    const bool seeded = !h->general && nb >= g_seed_min_batches && tiles_total >= 2 * vs::kSeedWaves && g_xchg_first_it >= 0 && cap_ok;
+    const bool seeded = !h->general && bf_seeded(h->n_rows, nb, k1);
     int grid, tp;
     scan_geometry(h->n_rows, h->num_cus, grid, tp, seeded ? 0 : (u8_path ? 16 : 6) * vs::kScanWaves);
     const bool exchange = !seeded && grid >= 16 && tp >= (u8_path ? 16 : 6) * vs::kScanWaves && g_xchg_first_it >= 0;
@@ -799,17 +829,21 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     const bool i8_seed = h->d_vecs_u8 && h->metric == VS_METRIC_L2 && g_seed_i8;
     const bool stream = seeded && g_stream && (use_u8 ? (g_i8_wide > 0 && i8_seed) : true);
     const bool f32_filter = stream && !use_u8 && g_f32_filter && h->filter_ok;
-    if (!h->general && !seeded && !use_u8 && nb < kOneMaxBatches && B <= kOneMaxQueries) {
-        // a short call on the fp32 rows: one launch per batch (lane lists, workgroup ranking, the last workgroup merges).
-        // Batches of more than 16 queries stay with the per-batch scan below: with two column blocks per tile the
-        // single-call kernel's lane lists cost more than that kernel's threshold exchange (measured at 1 M rows, B = 32:
-        // 154 us against 102 us; B <= 16: 88 - 97 us against 102 - 114 us)
+    // a short call on the fp32 rows: one launch per batch (lane lists, workgroup ranking, the last workgroup merges).
+    // Batches of more than 16 queries stay with the per-batch scan below: with two column blocks per tile the
+    // single-call kernel's lane lists cost more than that kernel's threshold exchange (measured at 1 M rows, B = 32:
+    // 154 us against 102 us; B <= 16: 88 - 97 us against 102 - 114 us).  On a general index the same rule sends the
+    // call to scan_one_nd_kernel, unless the index was created under VSEARCH_ND_ONE=0.
+    int64_t one_plan[4] = {0, 0, 0, 0};
+    const bool reads_f32 = h->general ? !nd_u8_path(h, force_f32) : !use_u8;
+    if (reads_f32 && (!h->general || h->nd_one)) one_route(h->n_rows, h->general, h->num_cus, nb, B, k1, one_plan);
+    if (one_plan[0]) {
         for (int b = 0; b < nb; ++b) {
             vs::OneParams op{};
             op.base = h->d_vecs;
             op.bnorm = h->d_norm;
             op.n_rows = h->n_rows;
-            op.q = q_dev + (size_t)b * B * vs::kDim;
+            op.q = q_dev + (size_t)b * B * h->dim;
             op.nq_valid = B;
             op.k1 = k1;
             op.metric = h->metric;
@@ -823,7 +857,15 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
             op.flags = flags ? flags + (size_t)b * B : nullptr;
             op.dbg = g_dbg;
             if (b == 0) prof_begin(h, 0, s);
-            HIPCHK(vs::launch_scan_one(op, vs::scan_one_grid(h->n_rows, h->num_cus), s));
+            if (one_plan[0] == 2) {
+                vs::OneNdParams np{};
+                np.o = op;
+                np.dim = h->dim;
+                np.dim_p = h->dim_p;
+                HIPCHK(vs::launch_scan_one_nd(np, (int)one_plan[1], s));
+            } else {
+                HIPCHK(vs::launch_scan_one(op, (int)one_plan[1], s));
+            }
             if (b == nb - 1) prof_end(h, 0, s);
         }
         return VS_OK;
@@ -2269,6 +2311,9 @@ static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int m
     h->dim = dim;
     h->general = dim != vs::kDim || g_nd_force != 0 || force_general;
     h->dim_p = h->general ? vs::nd_dim_p(dim) : dim;
+    // comparison toggle (VSEARCH_ND_ONE=0, read here): short calls on this general index keep the per-batch scan_nd_kernel
+    // route instead of scan_one_nd_kernel
+    if (const char* e = getenv("VSEARCH_ND_ONE")) h->nd_one = atoi(e) != 0;
     h->metric = metric;
     h->n_rows = h->n_total = n_rows;
     h->id_offset = id_offset;
@@ -3395,6 +3440,29 @@ int vs_topk_merge_plan(int G, int kin, int kout, int64_t* out) {
         return VS_ERR_INVALID;
     }
     return merge_plan_checked("vs_topk_merge_plan", G, kin, out);
+}
+
+// one_route for the ABI (host only): the index shape comes as arguments; dim == 128 stands for the specialised index
+// unless VSEARCH_ND_FORCE makes vs_bf_create build the general one there too
+int vs_bf_one_plan(int64_t n_rows, int dim, int num_cus, int n_batches, int B, int k, int64_t* out) {
+    if (!out || n_rows < 1 || num_cus < 1 || n_batches < 1 || B < 1 || B > vs::kMaxBatch || k < 1) {
+        set_error("vs_bf_one_plan: bad arguments (out != NULL, n_rows, num_cus, n_batches, k >= 1, 1 <= B <= 32)");
+        return VS_ERR_INVALID;
+    }
+    if (dim < 1) {
+        set_error("vs_bf_one_plan: dim must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (dim > vs::kNdMaxDim) {
+        set_error("vs_bf_one_plan: dim > 2048 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (k > vs::kTopkWideMax - 1) {
+        set_error("vs_bf_one_plan: k > 128 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    one_route(n_rows, dim != vs::kDim || g_nd_force != 0, num_cus, n_batches, B, k + 1, out);
+    return VS_OK;
 }
 
 int vs_topk_merge_dev(const float* dists_dev, const int32_t* ids_dev, int G, int B, int kin, int64_t stride_g,

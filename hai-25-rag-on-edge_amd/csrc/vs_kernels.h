@@ -300,6 +300,19 @@ struct OneParams {
 int scan_one_grid(int64_t n_rows, int num_cus);
 hipError_t launch_scan_one(const OneParams& p, int grid, hipStream_t s);
 
+// The same at any vector length (vs_scan_one_nd.hip): one launch per batch of <= 16 queries on the fp32 rows
+// of a general index -- OneParams with base = [n_rows + kScanPadRows][dim_p] (zero padded), q = [nq_valid][dim] unpadded
+// (the kernel pads them and works out their norms itself: no preparation launch), nq_valid <= 16, k1 <= 16.  Distances
+// are launch_scan_nd's to the bit.  A wave's unit of work is kOneNdUnit rows; scan_one_nd_geometry gives the launch's
+// workgroups and the most units any one wave gets (units are dealt statically).
+constexpr int kOneNdUnit = 64;
+struct OneNdParams {
+    OneParams o;
+    int dim, dim_p;
+};
+void scan_one_nd_geometry(int64_t n_rows, int num_cus, int64_t* grid, int64_t* units_per_wave);
+hipError_t launch_scan_one_nd(const OneNdParams& p, int grid, hipStream_t s);
+
 // Cross-workgroup merge of sorted partial lists -> [nq][kout] + tie flags (+ seed thresholds).
 struct MergeParams {
     const float* part_d;     // [G][nq_stride][kin]

@@ -120,7 +120,8 @@ VS_API int vs_bf_create(const float* base_host, int64_t n_rows, int dim, int met
 /* The same for any vector length, as cpu_baseline.cpp reads whatever dimension the .fvecs
  * header states: 1 <= dim <= 2048 (dim < 1: VS_ERR_INVALID, dim > 2048: VS_ERR_UNSUPPORTED).
  * dim == 128 gives exactly vs_bf_create's index.  Any other dim gives a "general" index: fp32
- * rows padded to a multiple of 16 floats, scanned by the general-dimension kernel.  It is
+ * rows padded to a multiple of 16 floats, scanned by the general-dimension kernels (short
+ * calls by one launch per batch: vs_bf_one_plan below; same results either way).  It is
  * accepted by vs_bf_search, vs_bf_search_topk, vs_bf_search_dev, vs_bf_search_dev_multi,
  * vs_bf_search_topk_dev_multi, vs_bf_scores_dev, vs_set_batch, vs_index_rows, vs_index_dim,
  * vs_prof_* and vs_destroy, with the same signatures and output layouts (queries are
@@ -132,6 +133,33 @@ VS_API int vs_bf_create(const float* base_host, int64_t n_rows, int dim, int met
  * index at other dimensions comes from vs_ivf_create / vs_ivf_load; a q8 runner from vs_q8_create_nd). */
 VS_API int vs_bf_create_nd(const float* base_host, int64_t n_rows, int dim, int metric,
                            int device, int64_t id_offset, vs_index** out);
+
+/* The single-call scan (host only, no GPU needed).  A short call that reads the fp32 rows --
+ * fewer than 4 batches of at most 16 queries, k <= 15 -- is answered by ONE launch per batch,
+ * without preparation, threshold exchange or merge launches: on the specialised 128-d index
+ * by the 128-d single-call kernel, on a general index (vs_bf_create_nd with dim != 128, the
+ * fp32 rows of a vs_bf_create_nd_u8* index under vs_set_precision(1) or in a rerun, and the
+ * VSEARCH_ND_FORCE=1 form at dim 128) by its sibling for any 1 <= dim <= 2048 (DESIGN.md
+ * 4.4d).  The result of a call does not depend on the route: ids, distance bits and flags are
+ * those of the per-batch scan.  VSEARCH_ND_ONE=0, read when a general index is created, keeps
+ * the per-batch scan for short calls on that index: the comparison toggle.
+ *
+ * vs_bf_one_plan states the rule for a call of n_batches batches of B queries for k neighbours
+ * on the fp32 rows of an index of n_rows rows of dim floats on a device of num_cus compute
+ * units; the launch code takes its decision and geometry through the same function.
+ *   out[0] = 0: no single-call launch; 1: the 128-d kernel (dim == 128, unless VSEARCH_ND_FORCE
+ *            makes vs_bf_create build general indexes there); 2: the general-dimension kernel
+ *   out[1] = workgroups of the launch
+ *   out[2] = rows in one unit of work handed to a wave (16 / 64)
+ *   out[3] = the largest number of such units any one wave gets (route 2 deals them
+ *            statically; route 1 hands them out on demand and reports the even share)
+ * out[1..3] are 0 with out[0] = 0.  It describes the default rule: the toggle above and a byte
+ * scan in force on the index are not its business.
+ * Checks, in this order: null out, n_rows < 1, num_cus < 1, n_batches < 1, B outside [1, 32],
+ * k < 1 -> VS_ERR_INVALID; dim < 1 -> VS_ERR_INVALID; dim > 2048 -> VS_ERR_UNSUPPORTED;
+ * k > 128 -> VS_ERR_UNSUPPORTED. */
+VS_API int vs_bf_one_plan(int64_t n_rows, int dim, int num_cus, int n_batches, int B, int k,
+                          int64_t* out /* [4] */);
 
 /* Byte-valued rows at any vector length: base_host is uint8 [n_rows][dim], 1 <= dim <= 2048
  * (dim < 1: VS_ERR_INVALID, dim > 2048: VS_ERR_UNSUPPORTED), squared L2 only.  dim == 128 gives
