@@ -3,9 +3,9 @@
 //
 //   scan_one_nd_kernel<KCAP>: scan_nd_kernel's arithmetic (v_mfma_f32_16x16x4_f32, base rows = A operand, one accumulation
 //   chain per distance in the (c, i) order of DESIGN 4.4c, the half step when dim_p / 16 is odd, fma(-2, dot, qn + bn) or
-//   -dot) with scan_one_kernel's top-k (vs_scan_one.hip: per-lane sorted lists, a bound from the workgroup's lane minima
-//   at a few checkpoints, one partial list per workgroup and query, the workgroup that arrives last merges them).  No
-//   preparation launch, no memset, no merge launch, and nothing anywhere waits for another workgroup.
+//   -dot) with scan_one_kernel's top-k (per-lane sorted lists, a bound from the workgroup's lane minima at a few
+//   checkpoints, one partial list per workgroup and query, the workgroup that arrives last merges them: the bound and
+//   everything after the scan loop are vs_one_tail.h, shared with vs_scan_one.hip).  No preparation launch, no memset, no merge launch, and nothing anywhere waits for another workgroup.
 //
 //   Queries.  Every workgroup reads the caller's unpadded [B][dim] queries itself, once: it writes them zero-padded in
 //   MFMA B-fragment order into LDS (dim_p / 16 segments of 1 KB: 128 KB at dim 2048) and works out ||q||^2 in the
@@ -22,6 +22,7 @@
 //   exact.  All loads are ordinary global loads whose waits the compiler places.
 #include "vs_kernels.h"
 #include "vs_dev.h"
+#include "vs_one_tail.h"
 
 namespace vs {
 
@@ -36,47 +37,11 @@ constexpr int kOneNdDepth = 4;                              // K steps in flight
 constexpr int kOneNdQ = 16;                                 // query columns
 constexpr int kOneNdScratch = 8192;                         // norms [16] | counters [32] | flag | lane minima [16][33]
 constexpr int one_nd_region(int dim_p, int kcap) {          // query fragments, later the merge buffers
-    const int frag = dim_p * 64, merge = kOneNdQ * 32 * kcap * 8;
+    const int frag = dim_p * 64, merge = one_tail_bytes(1, kcap);
     return frag > merge ? frag : merge;
 }
 constexpr int kOneNdMaxLds = one_nd_region(kNdMaxDim, 16) + kOneNdScratch;
 static_assert(kOneNdMaxLds <= 160 * 1024, "LDS of a CU");
-
-// (vs_scan_one.hip's) k smallest of M (dist, id) pairs by ascending (dist, id), read through `get(e, d, id)`; ids are
-// unique.  One wave, nothing is modified: round r takes the smallest pair above round r - 1's.  emit(round, d, id, none).
-template <class Get, class Emit>
-__device__ __forceinline__ void nd_rank_rounds(int M, int rounds, int lane, Get get, Emit emit) {
-    float last_d = -VS_INF;
-    int last_i = -1;
-    bool first = true;
-    for (int round = 0; round < rounds; ++round) {
-        float md = VS_INF;
-        int mi = 0x7fffffff;
-        for (int e = lane; e < M; e += 64) {
-            float d;
-            int id;
-            get(e, d, id);
-            if (id < 0) continue;
-            if (!first && (d < last_d || (d == last_d && id <= last_i))) continue;  // emitted already
-            if (lex_lt(d, id, md, mi)) {
-                md = d;
-                mi = id;
-            }
-        }
-        float bd;
-        int bi;
-        wave_lexmin(md, mi, bd, bi);
-        const bool none = bi == 0x7fffffff;
-        emit(round, bd, bi, none);
-        if (none) {
-            for (int r2 = round + 1; r2 < rounds; ++r2) emit(r2, VS_INF, 0x7fffffff, true);
-            return;
-        }
-        last_d = bd;
-        last_i = bi;
-        first = false;
-    }
-}
 
 }  // namespace
 
@@ -140,12 +105,12 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_one_nd_kernel(const OneN
     const float qn = lds_qn[r];
     const bool live = r < p.nq_valid;
     float tau = live ? VS_INF : -VS_INF;  // a padding column never takes a candidate
-    float ld[KCAP];
-    int li[KCAP];
+    float ld[1][KCAP];  // (one column block: the shared tail's shape)
+    int li[1][KCAP];
 #pragma unroll
     for (int j = 0; j < KCAP; ++j) {
-        ld[j] = VS_INF;
-        li[j] = -1;
+        ld[0][j] = VS_INF;
+        li[0][j] = -1;
     }
 
     // ---- the wave's units.  Run n of the base = units [n 8 G, (n + 1) 8 G): the grid reads one run at about the same
@@ -185,30 +150,6 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_one_nd_kernel(const OneN
             l_s = 0;
             ++l_n;
         }
-    };
-
-    // The bound that makes insertions rare (scan_one_kernel's): each of the column's 4 lanes takes the t-th smallest of 8
-    // of the column's 32 lane minima, t = ceil(k1 / 4); the largest of the four has 4 t >= k1 minima at or below it, and k1
-    // distinct rows are at least that close.  A missing or stale minimum only loosens it.
-    auto shared_bound = [&]() __attribute__((always_inline)) {
-        const int t = (p.k1 + 3) >> 2;
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = lds_lmin[r * 33 + 8 * g + i];
-        float m = VS_INF;
-        for (int round = 0; round < t; ++round) {
-            m = fminf(fminf(fminf(v[0], v[1]), fminf(v[2], v[3])), fminf(fminf(v[4], v[5]), fminf(v[6], v[7])));
-            bool done = false;
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (!done && v[i] == m) {
-                    v[i] = VS_INF;
-                    done = true;
-                }
-        }
-        float x = fmaxf(m, __shfl_xor(m, 16));
-        x = fmaxf(x, __shfl_xor(x, 32));
-        return x;  // (+inf while a lane holds fewer than t minima)
     };
 
     f32x4 acc[T];
@@ -256,15 +197,15 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_one_nd_kernel(const OneN
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     if (d[j] < tau) {
-                        list_insert<KCAP>(ld, li, d[j], rbase + j + p.id_offset);
-                        tau = fminf(tau, ld[KCAP - 1]);
+                        list_insert<KCAP>(ld[0], li[0], d[j], rbase + j + p.id_offset);
+                        tau = fminf(tau, ld[0][KCAP - 1]);
                     }
                 touched = true;
             }
         }
-        if (touched) lds_lmin[r * 33 + 4 * wave + g] = ld[0];  // this lane's best so far, for the shared bound
+        if (touched) lds_lmin[r * 33 + 4 * wave + g] = ld[0][0];  // this lane's best so far, for the shared bound
         if (c_n == 1 || c_n == 2 || c_n == 4 || c_n == 8) {    // wave-uniform checkpoints
-            const float sb = shared_bound();
+            const float sb = one_shared_bound(lds_lmin, r, g, p.k1);
             if (live && sb < VS_INF) tau = fminf(tau, next_up(sb));
         }
     };
@@ -289,170 +230,8 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_one_nd_kernel(const OneN
     }
 #undef VS_ONE_ND_STEP
 
-    // ---- workgroup merge (scan_one_kernel's).  A query's 32 lane lists (4 lane groups x 8 waves): the bound from the
-    // lane minima bounds the workgroup's k1-th best (+inf with fewer than k1 rows); entries not above it are compacted into
-    // LDS (the query fragments are done with: room for every entry, so nothing can overflow) and ranked by one wave per
-    // query.
-    __syncthreads();  // (every wave is done with the fragments; the lane minima are final)
-    if (tid < 32) lds_cnt[tid] = 0;
-    constexpr int CAP = 32 * KCAP;
-    float* cand_d = reinterpret_cast<float*>(smem);
-    int* cand_i = reinterpret_cast<int*>(smem + (size_t)NQ * CAP * sizeof(float));
-    const float wg_bound = shared_bound();
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < KCAP; ++j)
-        if (li[j] >= 0 && ld[j] <= wg_bound) {
-            const int pos = atomicAdd(&lds_cnt[r], 1);
-            cand_d[r * CAP + pos] = ld[j];
-            cand_i[r * CAP + pos] = li[j];
-        }
-    __syncthreads();
-    // partial lists: part[query][workgroup][k1], sorted by (dist, id), padded with (+inf, -1); written with agent-scope
-    // (write-through) stores, one per lane
-    for (int qq = wave; qq < p.nq_valid; qq += kScanWaves) {
-        float* od = p.part_d + ((int64_t)qq * G + blockIdx.x) * p.k1;
-        int32_t* oi = p.part_i + ((int64_t)qq * G + blockIdx.x) * p.k1;
-        auto put = [&](int slot, float d, int id) {
-            __hip_atomic_store(od + slot, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(oi + slot, id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        };
-        const int M = lds_cnt[qq];
-        if (M <= 64) {
-            const float d = lane < M ? cand_d[qq * CAP + lane] : VS_INF;
-            const int id = lane < M ? cand_i[qq * CAP + lane] : 0x7fffffff;
-            const int rank = wave_rank_count(d, id, M);
-            if (lane < M && rank < p.k1) put(rank, d, id);
-            if (lane >= M && lane < p.k1) put(lane, VS_INF, -1);
-        } else {
-            nd_rank_rounds(
-                M, p.k1, lane,
-                [&](int e, float& d, int& id) {
-                    d = cand_d[qq * CAP + e];
-                    id = cand_i[qq * CAP + e];
-                },
-                [&](int round, float d, int id, bool none) {
-                    if (lane == 0) put(round, none ? VS_INF : d, none ? -1 : id);
-                });
-        }
-    }
-    // ---- the workgroup that arrives last merges the partial lists (scan_one_kernel's: no fences while others stream --
-    // the partial lists are written with agent-scope stores that have completed before the arrival is counted).  Nobody
-    // waits for anybody: a workgroup that is not the last one is done.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) lds_flag[0] = (__hip_atomic_fetch_add(p.done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1) ? 1 : 0;
-    __syncthreads();
-    if (!lds_flag[0]) return;  // workgroup-uniform
-    if (tid == 0) __hip_atomic_store(p.done, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch (stream ordered)
-    // ONE acquire fence in ONE workgroup (every other workgroup has arrived): lines of the partial lists this XCD's L2 may
-    // still hold from an earlier launch are dropped, plain cached loads below.
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    // Per query two memory round trips: (1) the FIRST entry of each of its G partial lists; their k1-th smallest bounds
-    // the k1-th best.  (2) the lists whose first entry is not above the bound are read whole, one (list, entry) pair per
-    // lane; what is not above the bound is ranked by counting.  One wave per query.
-    constexpr int QPW = kOneNdQ / kScanWaves;         // queries per wave at most: 2
-    constexpr int SPL = kSlotStride / 64;             // lists per lane and query at most: 4
-    constexpr int FCAP = 256;                         // candidates per query kept in LDS
-    float* fin_d = reinterpret_cast<float*>(smem) + wave * FCAP;
-    int* fin_i = reinterpret_cast<int*>(smem + kScanWaves * FCAP * sizeof(float)) + wave * FCAP;
-    int* pl = reinterpret_cast<int*>(smem + 2 * kScanWaves * FCAP * sizeof(float)) + wave * kSlotStride;  // passing lists of the current query
-    static_assert(2 * kScanWaves * FCAP * 4 + kScanWaves * kSlotStride * 4 <= kOneNdQ * 32 * 8 * 8, "the final merge's buffers fit the region");
-    float fd[QPW][SPL];
-#pragma unroll
-    for (int qi = 0; qi < QPW; ++qi) {
-        const int qq = wave + kScanWaves * qi;
-#pragma unroll
-        for (int u = 0; u < SPL; ++u) {
-            const int w = lane + 64 * u;
-            fd[qi][u] = VS_INF;
-            if (qq < p.nq_valid && 64 * u < G) fd[qi][u] = p.part_d[((int64_t)qq * G + min(w, G - 1)) * p.k1];
-            if (w >= G) fd[qi][u] = VS_INF;
-        }
-    }
-#pragma unroll
-    for (int qi = 0; qi < QPW; ++qi) {
-        const int qq = wave + kScanWaves * qi;
-        if (qq >= p.nq_valid) break;  // wave-uniform
-        const float* pd = p.part_d + (int64_t)qq * G * p.k1;
-        const int32_t* pi = p.part_i + (int64_t)qq * G * p.k1;
-        float* od = p.out_d + (int64_t)qq * p.k1;
-        int32_t* oi = p.out_i + (int64_t)qq * p.k1;
-        const float b = wave_kth_smallest(fd[qi][0], fd[qi][1], fd[qi][2], fd[qi][3], p.k1, lane);  // (+inf with fewer than k1 rows in all)
-        // the passing lists, compacted (ballot prefix), then one (list, entry) pair per lane
-        int P = 0;
-#pragma unroll
-        for (int u = 0; u < SPL; ++u) {
-            const bool pass = fd[qi][u] < VS_INF && fd[qi][u] <= b;
-            const unsigned long long mask = __ballot(pass);
-            if (pass) pl[P + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0))] = lane + 64 * u;
-            P += __popcll(mask);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const int pairs = P * p.k1;
-        int M = 0;
-        for (int e0 = 0; e0 < pairs; e0 += 64) {
-            const int e = e0 + lane;
-            float d = VS_INF;
-            int id = -1;
-            if (e < pairs) {
-                const int off = pl[e / p.k1] * p.k1 + e % p.k1;
-                d = pd[off];
-                id = pi[off];
-            }
-            const bool pass = id >= 0 && d <= b;
-            const unsigned long long mask = __ballot(pass);
-            const int pos = M + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-            if (pass && pos < FCAP) {
-                fin_d[pos] = d;
-                fin_i[pos] = id;
-            }
-            M += __popcll(mask);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (M <= 64) {
-            const float d = lane < M ? fin_d[lane] : VS_INF;
-            const int id = lane < M ? fin_i[lane] : 0x7fffffff;
-            const int rank = wave_rank_count(d, id, M);
-            if (lane < M && rank < p.k1) {
-                od[rank] = d;
-                oi[rank] = id;
-            }
-            if (lane >= M && lane < p.k1) {
-                od[lane] = VS_INF;
-                oi[lane] = -1;
-            }
-            // two of the k1 outputs at one distance (select_topk's order among them is history dependent: the caller's flag)
-            bool tie = false;
-            for (int j = 0; j < M; ++j) {
-                const float dj = rdlane_f(d, j);
-                const int rj = __builtin_amdgcn_readlane(rank, j);
-                tie = tie || (j != lane && dj == d && rj < p.k1);
-            }
-            const bool any_tie = __any(lane < M && rank < p.k1 && tie);
-            if (lane == 0 && p.flags) p.flags[qq] = any_tie ? 1 : 0;
-        } else {
-            float prev = VS_INF;
-            int tie = 0;
-            auto emit = [&](int round, float d, int id, bool none) {
-                if (!none && round > 0 && d == prev) tie = 1;
-                prev = none ? VS_INF : d;
-                if (lane == 0) {
-                    od[round] = none ? VS_INF : d;
-                    oi[round] = none ? -1 : id;
-                }
-            };
-            if (M <= FCAP) {
-                nd_rank_rounds(M, p.k1, lane, [&](int e, float& d, int& id) { d = fin_d[e]; id = fin_i[e]; }, emit);
-            } else {  // masses of equal distances at the bound: rank straight from the partial lists
-                nd_rank_rounds(G * p.k1, p.k1, lane, [&](int e, float& d, int& id) { d = pd[e]; id = pi[e]; }, emit);
-            }
-            if (lane == 0 && p.flags) p.flags[qq] = tie;
-        }
-        __builtin_amdgcn_wave_barrier();  // (fin / pl are reused by the wave's next query)
-    }
+    // (the query fragments are done with: the merges overlay them)
+    one_tail<1, KCAP, one_nd_region(16, KCAP)>(p, OneTailLds{smem, lds_cnt, lds_flag, lds_lmin}, ld, li);
 }
 
 void scan_one_nd_geometry(int64_t n_rows, int num_cus, int64_t* grid, int64_t* units_per_wave) {
