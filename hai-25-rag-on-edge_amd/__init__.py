@@ -208,6 +208,8 @@ def lib():
         "vs_prof_read": (i32, [vp, i32, C.POINTER(C.c_double), C.POINTER(i64)]),
         "vs_ivf_widek_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_ivf_nd_u8_stats": (i32, [vp, C.POINTER(i64), i32]),
+        "vs_ivf_one_plan": (i32, [i64, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "vs_ivf_one_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_ivf_nd_widek_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_ivf_search_topk": (i32, [vp, vp, i64, i32, i32, vp, vp, C.POINTER(i64), C.POINTER(Timing)]),
         "vs_ivf_search_topk_dev_multi": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
@@ -733,6 +735,15 @@ def i16_wide_plan(n_rows: int, k: int):
     return tuple(int(v) for v in out)
 
 
+def ivf_one_plan(n_rows: int, dim: int, nlist: int, num_cus: int, n_batches: int, B: int, k: int, nprobe: int):
+    """(route, workgroups of the coarse launch, rows per unit of the scan, workgroups of the scan launch) of a launch group
+    of n_batches batches of B queries on a general IVF index (vs_ivf_one_plan; host only): route 0 = the group route,
+    1 = two launches per batch."""
+    out = (C.c_int64 * 4)()
+    _check(lib().vs_ivf_one_plan(n_rows, dim, nlist, num_cus, n_batches, B, k, nprobe, out))
+    return tuple(int(x) for x in out)
+
+
 class IVFIndex(_Index):
     """class IVFIndex (IVFIndex.h:14-97) on the GPU, reordered (contiguous list) layout, L2.
 
@@ -804,6 +815,13 @@ class IVFIndex(_Index):
         reset (vs_ivf_nd_u8_stats); a pair is a (query, probed non-empty list)."""
         out = (C.c_int64 * 2)()
         _check(lib().vs_ivf_nd_u8_stats(self._h, out, 1 if reset else 0))
+        return int(out[0]), int(out[1])
+
+    def one_stats(self, reset: bool = False):
+        """(batches answered by the two-launch route of short calls, most units of any one of them) of a general IVF
+        index since the last reset (vs_ivf_one_stats; synchronises the device)."""
+        out = (C.c_int64 * 2)()
+        _check(lib().vs_ivf_one_stats(self._h, out, 1 if reset else 0))
         return int(out[0]), int(out[1])
 
     def getNumVectors(self) -> int:

@@ -269,6 +269,20 @@ struct vs_index {
         vs::DevBuf<int32_t> valid;   // [kIvfNdGroupQ] 1: the query runs on bytes
         bool ready = false;          // every buffer above allocated
     } ivfnd;
+    // ... and what a short call (ivf_one_route) needs instead of the plan tables, allocated by the index's
+    // first such call (ensure_ivf_one)
+    struct IvfOne {
+        vs::DevBuf<float> scores;    // [16][nlist padded to 64] the coarse launch's scores
+        vs::DevBuf<int32_t> probes;  // [16][min(kMaxNprobe, nlist)] the batch's probes (pick_probes' table)
+        vs::DevBuf<int32_t> units;   // [units_cap][4] first row, end row, column mask, list
+        int units_cap = 0;
+        vs::DevBuf<float> part_d;    // [16][kSlotStride][kKcapMax] one partial list per workgroup and query
+        vs::DevBuf<int32_t> part_i;
+        vs::DevBuf<int32_t> words;   // [0] the coarse launch's ticket | [1] the scan launch's | [2] units of the batch in flight
+        vs::DevBuf<unsigned long long> counters;  // [2]: see vs_ivf_one_stats
+        bool ready = false;          // every buffer above allocated
+    } ivfone;
+    bool ivf_one = true;  // general IVF index: short calls take the two-launch route (VSEARCH_IVF_ONE=0 at creation: off)
     // ... and what a wide-k group (17 <= k <= 128, ivf_group_nd_wide_dev) needs beside it, allocated on the first such call
     struct IvfNdWide {
         vs::DevBuf<int32_t> plan, slots, items;  // the rescan plan's tables, as IvfNd's
@@ -1342,6 +1356,101 @@ int ensure_ivf_nd(vs_index* h) {
     return VS_OK;
 }
 
+// The two-launch route of a short call on a general IVF index (vs_ivf_one_plan's rule; ivf_group_nd_dev goes through it):
+// 0 = the group route, 1 = ivf_one_coarse_kernel + ivf_one_scan_kernel per batch, with the coarse launch's
+// workgroups, the rows of one unit of the scan and the scan launch's workgroups in out[1..3].  nprobe is the call's,
+// clamped to nlist here.
+//   Measured over the whole rule (profiles/ivf_one_bench.txt: 1 M synth_sift rows, trained index, nlist 1024, k = 10,
+//   us per call back to back, two launches against the group route, spread between repeats under 0.3 %):
+//     B = 1 : 96-d 86 / 92 / 139 / 191 against 170 / 187 / 221 / 257 at nprobe 8 / 32 / 128 / 256; 768-d 162 / 322 / 539 / 635
+//             against 1873 / 1964 / 2015 / 2072
+//     B = 16: 96-d 173 / 247 / 371 / 477 against 202 / 304 / 380 / 523; 128-d 195 / 268 / 383 / 490 against 267 / 327 / 498 /
+//             558; 768-d 449 / 556 / 699 / 859 against 2258 / 2397 / 2433 / 2641
+//   The closest point is 96-d, B = 16, nprobe 128 (2.4 % faster): the coarse launch's selection costs about 0.4 us per round
+//   and query, two queries per wave at B = 16.  Nothing measured is slower, so no shape is taken out; B > 16 is not built.
+int ivf_one_route(int64_t n_rows, int nlist, int num_cus, int nb, int B, int k, int nprobe, int64_t* out) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (nb >= kOneMaxBatches || B > kOneMaxQueries || k > 16 || std::min(nprobe, nlist) > kMaxNprobe) return 0;
+    if (n_rows >= (1ll << 31) - 128) return 0;  // (the kernels count rows in 32 bits)
+    if (nlist > vs::kIvfOneMaxNlist) return 0;   // (the coarse launch's last workgroup selects from [16][1024] scores in LDS)
+    out[0] = 1;
+    out[1] = vs::ivf_one_coarse_grid(nlist, num_cus);
+    out[2] = vs::kIvfOneUnitRows;
+    out[3] = vs::ivf_one_scan_grid(num_cus);
+    return 1;
+}
+
+// scratch of the two-launch route, all or nothing (vs_res.h handles); the tickets and counters start at zero
+int ensure_ivf_one(vs_index* h) {
+    if (h->ivfone.ready) return VS_OK;
+    vs_index::IvfOne W;
+    int rc;
+    const size_t ld = ((size_t)h->nlist + 63) & ~(size_t)63;
+    const int np_max = std::min(kMaxNprobe, h->nlist);
+    W.units_cap = (int)(std::min<int64_t>((int64_t)kOneMaxQueries * np_max, h->nlist) + h->n_rows / vs::kIvfOneUnitRows);
+    const size_t part = (size_t)kOneMaxQueries * vs::kSlotStride * kKcapMax;
+    if ((rc = W.scores.alloc(kOneMaxQueries * ld)) || (rc = W.probes.alloc((size_t)kOneMaxQueries * np_max)) || (rc = W.units.alloc((size_t)4 * W.units_cap)) || (rc = W.part_d.alloc(part)) ||
+        (rc = W.part_i.alloc(part)) || (rc = W.words.alloc(4)) || (rc = W.counters.alloc(2)))
+        return rc;
+    HIPCHK(hipMemset(W.words, 0, 4 * sizeof(int32_t)));
+    HIPCHK(hipMemset(W.counters, 0, 2 * sizeof(unsigned long long)));
+    HIPCHK(hipDeviceSynchronize());  // (the first launches go to the caller's stream, which nothing orders behind the memsets)
+    W.ready = true;
+    h->ivfone = std::move(W);
+    return VS_OK;
+}
+
+// nb < kOneMaxBatches batches of B <= 16 queries, two launches each, everything on s
+int ivf_one_nd_dev(vs_index* h, const int64_t* plan, const float* q_dev, int nb, int B, int k, int nprobe, float* out_d, int32_t* out_i,
+                   hipStream_t s) {
+    int rc = ensure_ivf_one(h);
+    if (rc) return rc;
+    vs_index::IvfOne& W = h->ivfone;
+    vs::IvfOneParams p{};
+    p.vecs = h->d_vecs;
+    p.vnorm = h->d_norm;
+    p.offsets = h->d_offsets;
+    p.cents = h->d_centroids;
+    p.cnorm = h->d_cnorm;
+    p.id_map = h->d_r2o;
+    p.nlist = h->nlist;
+    p.dim = h->dim;
+    p.dim_p = h->dim_p;
+    p.nprobe = nprobe;
+    p.metric = h->metric;
+    p.unit_rows = (int)plan[2];
+    p.scores = W.scores;
+    p.ld = (h->nlist + 63) & ~63;
+    p.units = W.units;
+    p.units_cap = W.units_cap;
+    p.ticket = W.words;
+    p.n_units = W.words + 2;
+    p.counters = W.counters;
+    p.cand_count = h->d_cand;
+    if (h->d_nd_stats) p.pair_count = h->d_nd_stats + 1;  // (an index with a byte copy, under vs_set_precision(h, 1): fp32 pairs)
+    p.o.nq_valid = B;
+    p.o.k1 = k;
+    p.o.metric = h->metric;
+    p.o.part_d = W.part_d;
+    p.o.part_i = W.part_i;
+    p.o.done = W.words + 1;
+    for (int b = 0; b < nb; ++b) {
+        p.o.q = q_dev + (size_t)b * B * h->dim;
+        p.o.out_d = out_d + (size_t)b * B * k;
+        p.o.out_i = out_i + (size_t)b * B * k;
+        p.probes = W.probes;
+        stage_mark(h, 0, s);  // (a set of marks per batch: centroid_search_ms = the coarse launches, fine_search_ms = the scan launches)
+        HIPCHK(vs::launch_ivf_one_coarse(p, (int)plan[1], s));
+        stage_mark(h, 1, s);
+        stage_mark(h, 2, s);
+        prof_begin(h, 1, s);
+        HIPCHK(vs::launch_ivf_one_scan(p, (int)plan[3], s));
+        prof_end(h, 1, s);
+        stage_mark(h, 3, s);
+    }
+    return VS_OK;
+}
+
 // ... of its wide-k groups, the same way
 int ensure_ivf_nd_wide(vs_index* h) {
     if (h->ivfndw.ready) return VS_OK;
@@ -1414,6 +1523,13 @@ vs::IvfNdParams ivf_nd_params(vs_index* h, const float* q_dev, int group_q, int 
 int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int nprobe, float* out_d, int32_t* out_i, hipStream_t s) {
     const int kcap = pick_kcap(k);
     if (!kcap) return refuse_general_ivf(h, "k > 16");
+    // a short call: two launches per batch, unless the index was created under VSEARCH_IVF_ONE=0.  An index
+    // with a byte copy of its rows takes the route only when no query can run on bytes (vs_set_precision(h, 1)).  The
+    // route has scratch of its own: an index that only ever serves short calls allocates none of the group route's.
+    int64_t one_plan[4] = {0, 0, 0, 0};
+    if (h->ivf_one && nb >= 1 && B >= 1 && nprobe >= 1 && nprobe <= std::min(kMaxNprobe, h->nlist) && (!h->d_nd_u8 || h->precision == 1))
+        ivf_one_route(h->n_rows, h->nlist, h->num_cus, nb, B, k, nprobe, one_plan);
+    if (one_plan[0]) return ivf_one_nd_dev(h, one_plan, q_dev, nb, B, k, nprobe, out_d, out_i, s);
     int rc = ensure_ivf_nd(h);
     if (rc) return rc;
     vs_index::IvfNd& W = h->ivfnd;
@@ -2174,6 +2290,24 @@ int vs_ivf_nd_u8_stats(vs_index* h, int64_t* out, int reset) {
     return VS_OK;
 }
 
+int vs_ivf_one_stats(vs_index* h, int64_t* out, int reset) {
+    if (!h || h->kind != 1 || !h->general || !out) {
+        set_error("vs_ivf_one_stats: a general IVF index and an output of two words");
+        return VS_ERR_INVALID;
+    }
+    int rc = set_device(h);
+    if (rc) return rc;
+    unsigned long long v[2] = {0, 0};
+    HIPCHK(hipDeviceSynchronize());
+    if (h->ivfone.ready) {  // (zero before the index's first short call)
+        HIPCHK(hipMemcpy(v, h->ivfone.counters, sizeof(v), hipMemcpyDeviceToHost));
+        if (reset) HIPCHK(hipMemset(h->ivfone.counters, 0, sizeof(v)));
+    }
+    out[0] = (int64_t)v[0];
+    out[1] = (int64_t)v[1];
+    return VS_OK;
+}
+
 int vs_prof_read(vs_index* h, int which, double* total_ms, int64_t* launches) {
     if (!h || which < 0 || which > 1) return VS_ERR_INVALID;
     int rc = set_device(h);
@@ -2601,6 +2735,8 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
     const char* nd_force = getenv("VSEARCH_IVF_ND_FORCE");
     h->general = dim != vs::kDim || (world == 1 && nd_force && atoi(nd_force) != 0);
     h->dim_p = h->general ? vs::nd_dim_p(dim) : dim;
+    // comparison toggle (VSEARCH_IVF_ONE=0, read here): short calls on this general index keep the group route
+    if (const char* e = getenv("VSEARCH_IVF_ONE")) h->ivf_one = atoi(e) != 0;
     h->metric = VS_METRIC_L2;
     h->n_total = n_rows;
     h->nlist = nlist;
@@ -3462,6 +3598,29 @@ int vs_bf_one_plan(int64_t n_rows, int dim, int num_cus, int n_batches, int B, i
         return VS_ERR_UNSUPPORTED;
     }
     one_route(n_rows, dim != vs::kDim || g_nd_force != 0, num_cus, n_batches, B, k + 1, out);
+    return VS_OK;
+}
+
+// ivf_one_route for the ABI (host only): the index shape comes as arguments.  VSEARCH_IVF_ONE and the byte copy of a
+// vs_ivf_create_nd_u8 index are not its business.
+int vs_ivf_one_plan(int64_t n_rows, int dim, int nlist, int num_cus, int n_batches, int B, int k, int nprobe, int64_t* out) {
+    if (!out || n_rows < 1 || nlist < 1 || num_cus < 1 || n_batches < 1 || B < 1 || B > vs::kMaxBatch || k < 1 || nprobe < 1) {
+        set_error("vs_ivf_one_plan: bad arguments (out != NULL, n_rows, nlist, num_cus, n_batches, k, nprobe >= 1, 1 <= B <= 32)");
+        return VS_ERR_INVALID;
+    }
+    if (dim < 1) {
+        set_error("vs_ivf_one_plan: dim must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (dim > vs::kNdMaxDim) {
+        set_error("vs_ivf_one_plan: dim > 2048 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (k > vs::kIvfWideKMax) {
+        set_error("vs_ivf_one_plan: k > 128 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    ivf_one_route(n_rows, nlist, num_cus, n_batches, B, k, nprobe, out);
     return VS_OK;
 }
 

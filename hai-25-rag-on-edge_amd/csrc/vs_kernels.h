@@ -621,6 +621,43 @@ hipError_t launch_ivf_nd_plan(const IvfNdParams& p, hipStream_t s);
 hipError_t launch_ivf_nd_plan_second(const IvfNdParams& p, hipStream_t s);
 hipError_t launch_ivf_nd_scan(const IvfNdParams& p, int grid, hipStream_t s);
 
+// ---- the single-call IVF search of a general index (vs_ivf_one_nd.hip): one batch of o.nq_valid <= 16
+// queries, o.k1 = k <= 16 results each (k entries, not k + 1), nlist <= kIvfOneMaxNlist, in TWO launches on one stream.
+// launch_ivf_one_coarse scores the centroid table (launch_scan_nd's kModeStore numbers, to the bit) and its last
+// workgroup writes the probes (launch_pick_probes' table), the unit table -- every probed list that holds rows cut into
+// units of unit_rows rows with the 16-bit mask of the query columns that probe it -- and the counts;
+// launch_ivf_one_scan scores the units (ivf_scan_nd_kernel's distances, to the bit) and its last workgroup writes
+// out_d / out_i [nq_valid][k] by (distance, position), ids through id_map, (+inf, -1) in empty slots.  No memset, no
+// preparation launch, no merge launch; both tickets are zero between launches.
+constexpr int kIvfOneMaxNlist = 1024;  // lists the coarse launch's selection is built for: a wave keeps a query's scores in registers, 16 per lane
+constexpr int kIvfOneUnitRows = 512;   // rows per unit of the scan: one 64-row block for each of a workgroup's 8 waves
+struct IvfOneParams {
+    OneParams o;              // q = [nq_valid][dim] raw queries, nq_valid, k1 = k, part_d / part_i = [16][grid][k] scratch of the
+                              // scan launch, done = the scan launch's ticket, out_d / out_i; base, bnorm, n_rows, reverse, id_offset, flags unused
+    const float* vecs;        // [n_rows + kScanPadRows][dim_p] cluster-reordered, zero padded
+    const float* vnorm;       // [n_rows + 64]
+    const int32_t* offsets;   // [nlist + 1]
+    const float* cents;       // [nlist + kScanPadRows][dim_p]
+    const float* cnorm;       // [nlist + 64]
+    const int32_t* id_map;    // [n_rows] position -> output id (null: the position)
+    int nlist, dim, dim_p, nprobe, metric;
+    int unit_rows;            // a multiple of 64
+    float* scores;            // scratch [16][ld]
+    int64_t ld;
+    int32_t* probes;          // [nq_valid][nprobe] (-1: fewer valid scores than nprobe)
+    int32_t* units;           // scratch [units_cap][4]: first row, end row, column mask, list
+    int units_cap;
+    int32_t* n_units;         // scratch [1]
+    int32_t* ticket;          // [1] the coarse launch's arrival counter: 0 at launch, left 0
+    unsigned long long* counters;    // [2] batches answered | the most units of any one of them
+    unsigned long long* cand_count;  // += rows of every probed list, per (query, probe) pair
+    unsigned long long* pair_count;  // optional: += pairs whose list holds rows (what ivf_nd_count adds for an fp32 plan)
+};
+int ivf_one_coarse_grid(int nlist, int num_cus);
+int ivf_one_scan_grid(int num_cus);
+hipError_t launch_ivf_one_coarse(const IvfOneParams& p, int grid, hipStream_t s);
+hipError_t launch_ivf_one_scan(const IvfOneParams& p, int grid, hipStream_t s);
+
 // ---- the same on the byte copy of a general IVF index made from uint8 rows (vs_ivf_nd_i8.hip).
 // launch_ivf_nd_i8_prep writes the group's queries as int8 (x - 128), zero padded, row-major [group_q][dim_b], qterm =
 // sum (q - 128)^2 and valid[query]: 1 when the query runs on bytes -- every value an integer in [0, 255] and ||q||^2 +

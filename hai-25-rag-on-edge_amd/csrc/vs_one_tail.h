@@ -100,10 +100,18 @@ __device__ __forceinline__ float one_shared_bound(const float* lds_lmin, int col
     return x;  // (+inf while a lane holds fewer than t minima)
 }
 
+// the ids of the lane lists are the ids of the outputs (the brute-force scans add id_offset when they insert)
+struct OneTailSameId {
+    __device__ __forceinline__ int operator()(int id) const { return id; }
+};
+
 // Everything after the scan loop; every thread of the workgroup calls it, with nothing of its own outstanding on
-// L.region.  REGION is the least size in bytes L.region can have in this instantiation of the kernel.
-template <int NQH, int KCAP, int REGION>
-__device__ __forceinline__ void one_tail(const OneParams& p, const OneTailLds& L, const float (&ld)[NQH][KCAP], const int (&li)[NQH][KCAP]) {
+// L.region.  REGION is the least size in bytes L.region can have in this instantiation of the kernel.  The lists are
+// merged and ranked by (dist, id) on the ids the kernel inserted; an output id is id_map(that id) (the IVF single-call
+// scan ranks positions in the reordered rows and writes original ids).
+template <int NQH, int KCAP, int REGION, class IdMap = OneTailSameId>
+__device__ __forceinline__ void one_tail(const OneParams& p, const OneTailLds& L, const float (&ld)[NQH][KCAP], const int (&li)[NQH][KCAP],
+                                         const IdMap id_map = IdMap{}) {
     static_assert(one_tail_bytes(NQH, KCAP) <= REGION, "the merge buffers overlay the kernel's region");
     constexpr int NQ = NQH * 16;
     char* const smem = L.region;
@@ -264,7 +272,7 @@ __device__ __forceinline__ void one_tail(const OneParams& p, const OneTailLds& L
             const int rank = wave_rank_count(d, id, M);
             if (lane < M && rank < p.k1) {
                 od[rank] = d;
-                oi[rank] = id;
+                oi[rank] = id_map(id);
             }
             if (lane >= M && lane < p.k1) {
                 od[lane] = VS_INF;
@@ -287,7 +295,7 @@ __device__ __forceinline__ void one_tail(const OneParams& p, const OneTailLds& L
                 prev = none ? VS_INF : d;
                 if (lane == 0) {
                     od[round] = none ? VS_INF : d;
-                    oi[round] = none ? -1 : id;
+                    oi[round] = none ? -1 : id_map(id);
                 }
             };
             if (M <= FCAP) {

@@ -23,6 +23,7 @@
 #include "vs_kernels.h"
 #include "vs_dev.h"
 #include "vs_one_tail.h"
+#include "vs_one_nd_queries.h"
 
 namespace vs {
 
@@ -68,37 +69,8 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_one_nd_kernel(const OneN
     const int S = (C + 1) >> 1;          // K steps per unit; the last one is a half step when C is odd
     const bool odd = (C & 1) != 0;
 
-    // ---- the queries: B fragments into LDS, fragment (c, lane) = Q[lane & 15][16 c + 4 (lane >> 4) ..], zeros past dim
-    // and past nq_valid (padding columns that nothing looks at)
-    for (int e = tid; e < C * 64; e += kScanThreads) {
-        const int ql = e & 63, c = e >> 6;
-        const int qi = ql & 15, k0 = 16 * c + 4 * (ql >> 4);
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (qi < p.nq_valid) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (k0 + i < dim) v[i] = p.q[(int64_t)qi * dim + k0 + i];
-        }
-        qfrag[e] = v;
-    }
-    // ||q||^2: 8 FMA lanes over v[8 i + j], r0 + ... + r7, then the tail (nd_prep_kernel's order); waves 0 and 1
-    if (wave < 2) {
-        const int row = tid >> 3, j = tid & 7;
-        const bool live = row < p.nq_valid;
-        const float* src = p.q + (int64_t)(live ? row : 0) * dim;
-        float acc = 0.f;
-        const int d8 = dim & ~7;
-        for (int i = 0; i < d8; i += 8) {
-            const float x = src[i + j];
-            acc = fmaf(x, x, acc);
-        }
-        const int b8 = lane & ~7;
-        float sum = __shfl(acc, b8);
-#pragma unroll
-        for (int u = 1; u < 8; ++u) sum = sum + __shfl(acc, b8 + u);
-        for (int i = d8; i < dim; ++i) sum = fmaf(src[i], src[i], sum);
-        if (j == 0) lds_qn[row] = live ? sum : 0.f;
-    }
+    // ---- the queries: B fragments into LDS and their squared norms (vs_one_nd_queries.h)
+    one_nd_stage_queries(p.q, p.nq_valid, dim, dim_p, qfrag, lds_qn);
     // the lanes' current minima, shared by the workgroup (see the checkpoints)
     for (int i = tid; i < NQ * 33; i += kScanThreads) lds_lmin[i] = VS_INF;  // (rows 33 apart: bank spread)
     __syncthreads();

@@ -561,6 +561,19 @@ VS_API int vs_ivf_load(const char* index_dir, int device, int rank, int world, v
  *   17 <= k <= 128 comes through vs_ivf_search_topk / vs_ivf_search_topk_dev_multi below.
  *   Inner product comes through vs_ivf_search_metric / vs_ivf_search_metric_dev_multi below, which
  *     take the metric per call; the index's own setting stays squared L2.
+ * Short calls.  A launch group of fewer than 4 batches of at most 16 queries with k <= 16 on a
+ * general IVF index (any creator, VSEARCH_IVF_ND_FORCE=1 at 128-d included, either metric) is
+ * answered by TWO launches per batch on the caller's stream -- centroid scores, probe selection
+ * and the work table; then the probed lists in row chunks over the whole grid, top-k, ranking and
+ * id mapping (vs_ivf_one_plan below states the rule).  The result of a call does
+ * not depend on the route: ids, distance bits, empty slots and *total_candidates are those of the
+ * launch group's ordinary route.  VSEARCH_IVF_ONE=0, read when the index is created, keeps that
+ * route for short calls on that index: the comparison toggle.  An index with a byte copy of its
+ * rows (vs_ivf_create_nd_u8) takes the two launches only under vs_set_precision(h, 1).
+ * The route's scratch (scores, unit table, tickets, counters) exists once per index, like the
+ * group route's: calls on ONE index must be ordered by their streams.  Short calls on one index
+ * from two streams at once corrupt each other silently; concurrent front ends need an index each
+ * or a stream in common.
  * vs_ivf_build and vs_ivf_build_index stay 128-d only; vs_ivf_build_nd and vs_ivf_build_index_nd
  * build at every dimension this creator takes.  A general IVF index that also keeps its rows as
  * bytes and scans them with int8 MFMA comes from vs_ivf_create_nd_u8 below, not from this creator. */
@@ -887,6 +900,27 @@ VS_API int vs_ivf_widek_stats(vs_index* h, int64_t* out /* [4] */, int reset);
  * the byte plan since the last reset, out[1] = the same for the fp32 plan (pairs that probe an empty list get neither).
  * Always counted.  Synchronises the device; reset != 0 clears the counters.  VS_ERR_INVALID on any other kind of index. */
 VS_API int vs_ivf_nd_u8_stats(vs_index* h, int64_t* out /* [2] */, int reset);
+/* The two-launch route of short calls on a general IVF index (host only, no GPU needed): the rule for a launch
+ * group of n_batches batches of B queries for k neighbours in nprobe lists (clamped to nlist) on an index of n_rows rows
+ * of dim floats in nlist lists on a device of num_cus compute units; the launch code takes its decision and geometry
+ * through the same function.
+ *   out[0] = 0: the group route; 1: the two-launch route -- all of n_batches < 4, B <= 16, k <= 16,
+ *            min(nprobe, nlist) <= 256, n_rows < 2^31 - 128 and nlist <= 1024 (the coarse launch's last workgroup selects
+ *            the probes from [16][1024] scores in its LDS; above that the call keeps the group route)
+ *   out[1] = workgroups of the coarse launch
+ *   out[2] = rows in one unit of the scan: a probed list is cut into units of at most this many rows, a multiple of 64
+ *            counted from the list's first row
+ *   out[3] = workgroups of the scan launch
+ * out[1..3] are 0 with out[0] = 0.  It describes the default rule: VSEARCH_IVF_ONE=0 and the byte copy of a
+ * vs_ivf_create_nd_u8 index are not its business.
+ * Checks, in this order: null out, n_rows < 1, nlist < 1, num_cus < 1, n_batches < 1, B outside [1, 32], k < 1,
+ * nprobe < 1 -> VS_ERR_INVALID; dim < 1 -> VS_ERR_INVALID; dim > 2048 -> VS_ERR_UNSUPPORTED; k > 128 -> VS_ERR_UNSUPPORTED. */
+VS_API int vs_ivf_one_plan(int64_t n_rows, int dim, int nlist, int num_cus, int n_batches, int B, int k, int nprobe,
+                           int64_t* out /* [4] */);
+/* What that route did on a general IVF index since the last reset: out[0] = batches answered by the two launches,
+ * out[1] = the most units any one of those batches had (written by the coarse launch).  Always counted; zeros before the
+ * first short call.  Synchronises the device; reset != 0 clears the counters.  VS_ERR_INVALID on any other kind of index. */
+VS_API int vs_ivf_one_stats(vs_index* h, int64_t* out /* [2] */, int reset);
 /* The wide-k calls (17 <= k <= 128) on a general IVF index since the last reset: out[0] = candidates ranked from
  * candidate lists, out[1] = the most candidates of one query, out[2] = queries ranked by the exact fallback (more than
  * 8192 candidates: every row of their probed lists scored again).  Always counted; zeros before the first wide-k call.

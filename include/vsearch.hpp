@@ -294,6 +294,8 @@ public:
     IVFIndex(const IVFIndex&) = delete;
     IVFIndex& operator=(const IVFIndex&) = delete;
 
+    // One query, one answer.  On a general index (dim != 128) with k <= 16 and nlist <= 1024 this is the two-launch route
+    // of short calls (vsearch.h at vs_ivf_create, vs_ivf_one_plan); same result as through searchBatch.
     size_t search(const std::vector<float>& query, int k, int nprobe, std::vector<int>& indices,
                   std::vector<float>& scores) {
         SearchTiming t;
