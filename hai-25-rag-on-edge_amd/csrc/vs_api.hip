@@ -682,6 +682,15 @@ int g_f32f_waves = [] {
     return v == 4 || v == 8 ? v : 0;
 }();
 
+// comparison toggle (VSEARCH_F32F_PRIO=0..8): the second 4-wave workgroup of a CU raises its wave priority in
+// scan_f32f_kernel on that many steps of every eight, at every shard size; 0 = never (default unset: the measured choice
+// per shard size, launch_scan_f32_stream)
+int g_f32f_prio = [] {
+    const char* e = getenv("VSEARCH_F32F_PRIO");
+    const int v = e ? atoi(e) : -1;
+    return v >= 0 && v <= 8 ? v : -1;
+}();
+
 // tuning knob (VSEARCH_STREAM=0): seeded launches use the per-batch scan kernels (lane lists + workgroup merge) instead of
 // the streaming scans
 int g_stream = [] {
@@ -1002,11 +1011,12 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
                 sp.qbf = L.qbf;
                 sp.qbound = L.qbound;
                 sp.img = h->d_img;
-#ifdef VS_STAMPS
+#if defined(VS_STAMPS) || defined(VS_F32F_ENDS)
                 sp.dbg = g_dbg ? g_dbg + 12288 * 16 : nullptr;  // (rows of its own: the kernels around it stamp rows [0, 256))
 #endif
                 sp.cnorm = h->filter_cnorm;
                 sp.f32f_waves = g_f32f_waves;
+                sp.f32f_prio = g_f32f_prio;
                 sp.sink.stats = h->filter_stats;
                 ++h->filter_launches;
             }
@@ -3545,7 +3555,10 @@ __attribute__((visibility("default"))) int vs_debug_ivf_wide_stats(vs_index* h, 
     out[7] = big * 100000 + maxq;
     return VS_OK;
 }
+#endif
 
+#if defined(VS_STAMPS) || defined(VS_F32F_ENDS)
+// diagnostic builds only: where the stamping kernels write
 __attribute__((visibility("default"))) int vs_debug_buffer(int* dev_ptr) {
     g_dbg = dev_ptr;
     return VS_OK;

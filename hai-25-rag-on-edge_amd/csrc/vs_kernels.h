@@ -272,9 +272,10 @@ struct StreamParams {
     const uint16_t* qbf;
     const float* qbound;
     const uint16_t* img;     // [n_rows + 64][128] bf16
-    int32_t* dbg;            // diagnostic builds (-DVS_STAMPS) only: scan_f32f_kernel's step split [sweeper][8 waves][16], under either organisation (rows 12288.. of the debug buffer)
+    int32_t* dbg;            // diagnostic builds only: scan_f32f_kernel's [sweeper][8 waves][16], under either organisation (rows 12288.. of the debug buffer) -- the step split (-DVS_STAMPS) or the waves' start, loop end and end (-DVS_F32F_ENDS)
     float cnorm;             // filter_cnorm of the shard's largest stored norm (the L2 test, filter_th2)
     int f32f_waves;          // scan_f32f_kernel's waves per workgroup: 8, 4 (two workgroups per CU), 0 = the measured choice per launch size
+    int f32f_prio;           // 4-wave organisation: steps of every eight (0..8) on which half 1 raises its wave priority, so that the two workgroups of a CU end together; < 0 = the measured choice per shard size
 };
 hipError_t launch_scan_f32_stream(const StreamParams& p, int grid, hipStream_t s);
 

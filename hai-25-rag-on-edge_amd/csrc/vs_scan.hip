@@ -1241,6 +1241,12 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_kernel(con
     static_assert(kUnitRowBytes == 2 * kPieces * NW * 1024, "a unit is 2 kPieces 1 KB row pieces per wave");
     static_assert(D >= 3 && (kScanWaves / NW) * D * kUnitBytes <= 160 * 1024, "the ring: one slot being read, one being filled, >= 1 in flight");
     extern __shared__ __attribute__((aligned(16))) char smem[];
+#ifdef VS_F32F_ENDS
+    // Diagnostic builds (-DVS_F32F_ENDS, scripts/diag/f32fstamps.py --ends): when every wave of the launch starts, leaves
+    // its loop and ends, by the constant 100 MHz clock that all XCDs share -- three reads per wave, none inside the loop,
+    // so the kernel runs at the product's speed.
+    const unsigned long long en_start = __builtin_amdgcn_s_memrealtime();
+#endif
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, g = lane >> 4;
@@ -1448,6 +1454,18 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_kernel(con
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         VS_F32F_STAMP(2);
+        // NW = 4: a CU holds a workgroup of each half, a wave of each per SIMD, and between equals the SIMD issues the
+        // older wave's instruction first.  Left alone, half 0 (dispatched first) ends its loop some 48 us of 210 ahead
+        // of half 1, which then runs on without a second wave whose MFMAs would cover its tests (measured: DESIGN 4.2b,
+        // profiles/r09a_wg_ends_parent.txt).  Half 1 therefore raises its waves' priority on f32f_prio steps of every
+        // eight (four: every other turn of the ring), so that each half wins the SIMD about half of the time and both end
+        // together.  The launcher asks for it on long sweeps only (f32f_prio_default).
+        if constexpr (NW == 4) {
+            if (z == 1 && p.f32f_prio) {  // (workgroup-uniform)
+                if ((t & 7) < p.f32f_prio) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
+            }
+        }
         issue_unit(t + D - 1, (sl + D - 1) % D);
         VS_F32F_STAMP(3);
         const int row_u = (bx + t * G) * kUnitRows + 4 * g;
@@ -1485,6 +1503,12 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_kernel(con
     }
 #endif
 #undef VS_F32F_STAMP
+    if constexpr (NW == 4) {
+        if (z == 1 && p.f32f_prio) __builtin_amdgcn_s_setprio(0);
+    }
+#ifdef VS_F32F_ENDS
+    const unsigned long long en_loop = __builtin_amdgcn_s_memrealtime();
+#endif
     const RecheckF32 fix{p.base, p.bnorm, p.q, p.q_batch_stride, p.qnorm, p.tau0, p.metric, p.id_offset};
     int kept = sink_bin_wave<RecheckF32, true>(p.sink, bx * kScanWaves + vw, wbase, lane, fix);
     if (p.sink.stats && wbase > 0) {  // (wave-uniform) one atomic instruction: lane 0 adds the sweep's count, lane 1 the survivors
@@ -1492,13 +1516,37 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_kernel(con
         for (int u = 32; u >= 1; u >>= 1) kept += __shfl_xor(kept, u);
         if (lane < 2) atomicAdd(p.sink.stats + 2 + lane, (unsigned long long)(lane == 0 ? wbase : kept));
     }
+#ifdef VS_F32F_ENDS
+    // dbg[workgroup][wave][16]: [0..1] start, [2..3] loop end, [4..5] end (100 MHz ticks, low word first), [6] units swept,
+    // [7] XCC_ID, [8] candidates
+    const unsigned long long en_end = __builtin_amdgcn_s_memrealtime();
+    if (p.dbg && lane == 0) {
+        int32_t* o = p.dbg + ((int64_t)bx * kScanWaves + vw) * 16;
+        o[0] = (int)en_start, o[1] = (int)(en_start >> 32);
+        o[2] = (int)en_loop, o[3] = (int)(en_loop >> 32);
+        o[4] = (int)en_end, o[5] = (int)(en_end >> 32);
+        o[6] = T;
+        o[7] = (int)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7);
+        o[8] = wbase;
+    }
+#endif
 }
 
+// Steps of every eight on which the second 4-wave workgroup of a CU raises its priority, where the caller does not
+// force a count (StreamParams::f32f_prio < 0), by units per workgroup: the choice measured per shard size (DESIGN 4.2b,
+// profiles/r09a_sizes_ab.txt).  Four of eight pay from about 60 units per workgroup on (1 M rows: - 4 % at 32 batches,
+// - 1 % at 16); at 30 units and fewer (500 K rows and below) a block of four steps is too large a part of the sweep, and
+// the launch group measured 3 - 5 % longer with it.
+static int f32f_prio_default(int64_t units_per_wg) { return units_per_wg >= 48 ? 4 : 0; }
+
 template <int CBW, int NW>
-static hipError_t launch_scan_f32f(const StreamParams& p, int grid, hipStream_t s) {
+static hipError_t launch_scan_f32f(const StreamParams& p0, int grid, hipStream_t s) {
     constexpr int kLds = kFilterDepth * kUnitBytes;  // per workgroup: at NW = 4 a CU holds two rings
-    auto kfn = p.metric ? scan_f32f_kernel<CBW, kFilterDepth, true, NW> : scan_f32f_kernel<CBW, kFilterDepth, false, NW>;
-    grid = (int)std::max<int64_t>(1, std::min<int64_t>(grid, (p.n_rows + kUnitRows - 1) / kUnitRows));  // every workgroup owns a unit
+    auto kfn = p0.metric ? scan_f32f_kernel<CBW, kFilterDepth, true, NW> : scan_f32f_kernel<CBW, kFilterDepth, false, NW>;
+    const int64_t units = (p0.n_rows + kUnitRows - 1) / kUnitRows;
+    grid = (int)std::max<int64_t>(1, std::min<int64_t>(grid, units));  // every workgroup owns a unit
+    StreamParams p = p0;
+    if (p.f32f_prio < 0) p.f32f_prio = f32f_prio_default(units / grid);
     static bool attr_set[64][2] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
