@@ -157,6 +157,8 @@ def lib():
         "vs_topk_merge_dev": (i32, [vp, vp, i32, i32, i32, i64, i32, vp, vp, vp, vp]),
         "vs_topk_merge_plan": (i32, [i32, i32, i32, vp]),
         "vs_bf_one_plan": (i32, [i64, i32, i32, i32, i32, i32, vp]),
+        "vs_bf_one_plan_u8": (i32, [i64, i32, i32, i32, i32, i32, vp]),
+        "vs_bf_one_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_comm_unique_id": (i32, [vp]),
         "vs_comm_create": (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
         "vs_comm_rank": (i32, [vp]),
@@ -492,6 +494,21 @@ class BruteForceIndex(_Index):
         out = (C.c_int64 * 4)()
         _check(lib().vs_bf_one_plan(n_rows, dim, num_cus, n_batches, B, k, out))
         return tuple(int(x) for x in out)
+
+    @staticmethod
+    def one_plan_u8(n_rows: int, dim: int, num_cus: int, n_batches: int, B: int, k: int):
+        """``one_plan`` for a call that reads the byte rows of a general ``from_u8`` index (vs_bf_one_plan_u8; host only):
+        route 0 = no single-call launch, 3 = the single-call byte kernel, with route 2's geometry."""
+        out = (C.c_int64 * 4)()
+        _check(lib().vs_bf_one_plan_u8(n_rows, dim, num_cus, n_batches, B, k, out))
+        return tuple(int(x) for x in out)
+
+    def one_stats(self, reset: bool = False):
+        """(single-call launches enqueued on the fp32 rows, on the byte rows) of this index since the last reset
+        (vs_bf_one_stats; counted on the host, no synchronisation)."""
+        out = (C.c_int64 * 2)()
+        _check(lib().vs_bf_one_stats(self._h, out, 1 if reset else 0))
+        return int(out[0]), int(out[1])
 
     @staticmethod
     def search_vshards(shards, queries: np.ndarray, k: int, timing: "Timing | None" = None):

@@ -89,6 +89,8 @@ struct vs_index {
     bool general = false;
     int dim_p = 0;
     bool nd_one = true;  // general brute-force index: short calls on the fp32 rows take scan_one_nd_kernel (VSEARCH_ND_ONE=0 at creation: off)
+    bool nd_one_u8 = true;  // ... and short calls on its byte rows scan_one_nd_i8_kernel (VSEARCH_ND_ONE_U8=0 at creation: off)
+    int64_t one_stat[2] = {0, 0};  // single-call launches enqueued on the fp32 rows | on the byte rows (vs_bf_one_stats; host side)
     vs::DevBuf<float> d_nd_qfrag;  // [kMaxMulti][dim_p / 16][2][64][4] scratch of launch_scan_nd
     vs::DevBuf<float> d_nd_qnorm;  // [kMaxMulti][32]
     // general index made from uint8 rows (vs_bf_create_nd_u8, vs_bf_create_nd_u8_metric): the rows once more as int8
@@ -812,6 +814,25 @@ int one_route(int64_t n_rows, bool general, int num_cus, int nb, int B, int k1, 
     return 1;
 }
 
+// The single-call route of a short call that reads the byte rows of a general index (vs_bf_one_plan_u8's rule; bf_launch
+// goes through it): 0 = none, 3 = scan_one_nd_i8_kernel, with the geometry of route 2 in out[1..3].
+// The measured exception: rows of at most 128 bytes (dim <= 128: a unit is a single K step and the distance epilogue runs
+// every step) with more than 12 queries in the batch keep the per-batch route -- at 64-d and 96-d under squared L2 the
+// single-call kernel took 63.7 and 69.2 us against 62.8 and 67.6 us at B = 16 (1 M rows; the same 2 - 3 % at 400 K and
+// 700 K rows), and was 2 - 4 % faster at B = 12.
+constexpr int kOneU8ShortRowBytes = 128;
+constexpr int kOneU8ShortRowQueries = 12;
+int one_route_u8(int64_t n_rows, int dim, int num_cus, int nb, int B, int k1, int64_t* out) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (nb >= kOneMaxBatches || B > kOneMaxQueries || k1 > 16) return 0;
+    if (n_rows > 0x7fffffff - 2 * vs::kOneNdUnit) return 0;  // (the kernel counts rows in 32 bits)
+    if (vs::nd_dim_b(dim) <= kOneU8ShortRowBytes && B > kOneU8ShortRowQueries) return 0;
+    out[0] = 3;
+    out[2] = vs::kOneNdUnit;
+    vs::scan_one_nd_geometry(n_rows, num_cus, &out[1], &out[3]);
+    return 3;
+}
+
 // nb <= kMaxMulti batches of B queries in ONE persistent launch on stream s (preceded by the seed launches or the
 // slot reset, followed by one merge launch), outputs [nb][B][k1].  Consecutive calls on one lane must be stream-ordered.
 int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B, int k1, float* out_d, int32_t* out_i,
@@ -860,6 +881,9 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     int64_t one_plan[4] = {0, 0, 0, 0};
     const bool reads_f32 = h->general ? !nd_u8_path(h, force_f32) : !use_u8;
     if (reads_f32 && (!h->general || h->nd_one)) one_route(h->n_rows, h->general, h->num_cus, nb, B, k1, one_plan);
+    // ... and a short call on the byte rows of a general index goes to scan_one_nd_i8_kernel, unless the
+    // index was created under VSEARCH_ND_ONE_U8=0
+    if (!reads_f32 && h->general && h->nd_one_u8) one_route_u8(h->n_rows, h->dim, h->num_cus, nb, B, k1, one_plan);
     if (one_plan[0]) {
         for (int b = 0; b < nb; ++b) {
             vs::OneParams op{};
@@ -880,7 +904,18 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
             op.flags = flags ? flags + (size_t)b * B : nullptr;
             op.dbg = g_dbg;
             if (b == 0) prof_begin(h, 0, s);
-            if (one_plan[0] == 2) {
+            ++h->one_stat[one_plan[0] == 3 ? 1 : 0];
+            if (one_plan[0] == 3) {
+                vs::OneNdI8Params bp{};
+                bp.o = op;
+                bp.dim = h->dim;
+                bp.dim_b = h->dim_b;
+                bp.bmax = h->nd_bmax;
+                bp.base_u8 = h->d_nd_u8;
+                bp.rterm = h->d_nd_rterm;  // (squared L2; null on an inner-product index)
+                bp.rsum = h->d_nd_rsum;    // (inner product; null on an L2 index)
+                HIPCHK(vs::launch_scan_one_nd_i8(bp, (int)one_plan[1], s));
+            } else if (one_plan[0] == 2) {
                 vs::OneNdParams np{};
                 np.o = op;
                 np.dim = h->dim;
@@ -2458,6 +2493,8 @@ static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int m
     // comparison toggle (VSEARCH_ND_ONE=0, read here): short calls on this general index keep the per-batch scan_nd_kernel
     // route instead of scan_one_nd_kernel
     if (const char* e = getenv("VSEARCH_ND_ONE")) h->nd_one = atoi(e) != 0;
+    // ... and VSEARCH_ND_ONE_U8=0 the per-batch scan_nd_i8_kernel route for short calls on its byte rows
+    if (const char* e = getenv("VSEARCH_ND_ONE_U8")) h->nd_one_u8 = atoi(e) != 0;
     h->metric = metric;
     h->n_rows = h->n_total = n_rows;
     h->id_offset = id_offset;
@@ -3611,6 +3648,40 @@ int vs_bf_one_plan(int64_t n_rows, int dim, int num_cus, int n_batches, int B, i
         return VS_ERR_UNSUPPORTED;
     }
     one_route(n_rows, dim != vs::kDim || g_nd_force != 0, num_cus, n_batches, B, k + 1, out);
+    return VS_OK;
+}
+
+// one_route_u8 for the ABI (host only): vs_bf_one_plan's checks in its order; whether an index keeps a byte copy, its
+// precision setting and VSEARCH_ND_ONE_U8 are not its business
+int vs_bf_one_plan_u8(int64_t n_rows, int dim, int num_cus, int n_batches, int B, int k, int64_t* out) {
+    if (!out || n_rows < 1 || num_cus < 1 || n_batches < 1 || B < 1 || B > vs::kMaxBatch || k < 1) {
+        set_error("vs_bf_one_plan_u8: bad arguments (out != NULL, n_rows, num_cus, n_batches, k >= 1, 1 <= B <= 32)");
+        return VS_ERR_INVALID;
+    }
+    if (dim < 1) {
+        set_error("vs_bf_one_plan_u8: dim must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (dim > vs::kNdMaxDim) {
+        set_error("vs_bf_one_plan_u8: dim > 2048 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (k > vs::kTopkWideMax - 1) {
+        set_error("vs_bf_one_plan_u8: k > 128 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    one_route_u8(n_rows, dim, num_cus, n_batches, B, k + 1, out);
+    return VS_OK;
+}
+
+int vs_bf_one_stats(vs_index* h, int64_t* out, int reset) {
+    if (!h || h->kind != 0 || !out) {
+        set_error("vs_bf_one_stats: a brute-force index and an output of two words");
+        return VS_ERR_INVALID;
+    }
+    out[0] = h->one_stat[0];
+    out[1] = h->one_stat[1];
+    if (reset) h->one_stat[0] = h->one_stat[1] = 0;
     return VS_OK;
 }
 

@@ -314,6 +314,21 @@ struct OneNdParams {
 void scan_one_nd_geometry(int64_t n_rows, int num_cus, int64_t* grid, int64_t* units_per_wave);
 hipError_t launch_scan_one_nd(const OneNdParams& p, int grid, hipStream_t s);
 
+// ... and on the byte rows of a general index made from uint8 rows (vs_scan_one_nd_i8.hip): one launch per
+// batch of <= 16 queries, k1 <= 16, under either metric.  o.base / o.bnorm are not read; o.q = [nq_valid][dim] unpadded
+// floats: every workgroup turns them into bytes, works out the per-query term and reaches nd_prep_i8_kernel's verdict
+// itself.  Distances, ids and flags are launch_scan_nd_i8's to the bit; a batch the verdict refuses comes back with ids
+// -1, distances +inf and flags = 2 for all nq_valid queries.  Units and geometry: scan_one_nd_geometry.
+struct OneNdI8Params {
+    OneParams o;
+    int dim, dim_b;
+    int32_t bmax;            // max over the base of ||b||^2, < 2^24
+    const int8_t* base_u8;   // [n_rows + kScanPadRows][dim_b] bytes (x - 128), zero padded
+    const int32_t* rterm;    // [n_rows + 64] sum (b - 128)^2 per row (o.metric == 0)
+    const int32_t* rsum;     // [n_rows + 64] sum (b - 128) per row (o.metric == 1)
+};
+hipError_t launch_scan_one_nd_i8(const OneNdI8Params& p, int grid, hipStream_t s);
+
 // Cross-workgroup merge of sorted partial lists -> [nq][kout] + tie flags (+ seed thresholds).
 struct MergeParams {
     const float* part_d;     // [G][nq_stride][kin]

@@ -154,12 +154,40 @@ VS_API int vs_bf_create_nd(const float* base_host, int64_t n_rows, int dim, int 
  *   out[3] = the largest number of such units any one wave gets (route 2 deals them
  *            statically; route 1 hands them out on demand and reports the even share)
  * out[1..3] are 0 with out[0] = 0.  It describes the default rule: the toggle above and a byte
- * scan in force on the index are not its business.
+ * scan in force on the index are not its business (a short call that reads the BYTE rows of a
+ * general index has a single-call route of its own: vs_bf_one_plan_u8 below).
  * Checks, in this order: null out, n_rows < 1, num_cus < 1, n_batches < 1, B outside [1, 32],
  * k < 1 -> VS_ERR_INVALID; dim < 1 -> VS_ERR_INVALID; dim > 2048 -> VS_ERR_UNSUPPORTED;
  * k > 128 -> VS_ERR_UNSUPPORTED. */
 VS_API int vs_bf_one_plan(int64_t n_rows, int dim, int num_cus, int n_batches, int B, int k,
                           int64_t* out /* [4] */);
+
+/* The same for a call that reads the byte rows of a general index made from uint8 rows
+ * (vs_bf_create_nd_u8, vs_bf_create_nd_u8_metric; precision 0 / 2, k <= 15): fewer than 4
+ * batches of at most 16 queries on at most 2^31 - 1 - 128 rows are ONE launch per batch of the
+ * single-call byte kernel, under either metric, instead of a reset, a
+ * preparation launch, the per-batch byte scan and a merge launch.  One measured exception: at
+ * dim <= 128 (rows of at most 128 bytes) a batch of more than 12 queries keeps the per-batch
+ * route, which was 2 - 3 % faster there.  Results do not depend on the
+ * route: ids, distance bits and flags (flags == 2 for a batch the exactness rule refuses
+ * included) are those of the per-batch byte scan.  VSEARCH_ND_ONE_U8=0, read when the index is
+ * created, keeps the per-batch route for short byte calls on that index (VSEARCH_ND_ONE is the
+ * toggle of the fp32 rows only).
+ *   out[0] = 0: no single-call launch; 3: the single-call byte kernel
+ *   out[1..3] as for vs_bf_one_plan's route 2 (workgroups, 64 rows per unit, the most units of
+ *            any one wave); 0 with out[0] = 0
+ * Host only; the launch code takes its decision and geometry through the same function.  Whether
+ * a given index keeps a byte copy, its precision setting and the toggle are not its business.
+ * Checks and codes: vs_bf_one_plan's, in the same order. */
+VS_API int vs_bf_one_plan_u8(int64_t n_rows, int dim, int num_cus, int n_batches, int B, int k,
+                             int64_t* out /* [4] */);
+
+/* Single-call launches enqueued on a brute-force index since the last reset: out[0] = on the
+ * fp32 rows (routes 1 and 2 of vs_bf_one_plan), out[1] = on the byte rows (route 3 of
+ * vs_bf_one_plan_u8).  Counted on the host when a launch is enqueued, always; no device
+ * synchronisation.  reset != 0 clears both after reading.  Null pointers or an IVF index:
+ * VS_ERR_INVALID. */
+VS_API int vs_bf_one_stats(vs_index* h, int64_t* out /* [2] */, int reset);
 
 /* Byte-valued rows at any vector length: base_host is uint8 [n_rows][dim], 1 <= dim <= 2048
  * (dim < 1: VS_ERR_INVALID, dim > 2048: VS_ERR_UNSUPPORTED), squared L2 only.  dim == 128 gives
@@ -183,7 +211,11 @@ VS_API int vs_bf_one_plan(int64_t n_rows, int dim, int num_cus, int n_batches, i
  *
  * vs_set_precision on such an index: 0 (default) and 2 use the byte scan for k <= 15, 1 forces
  * the fp32 rows; 2 returns VS_ERR_UNSUPPORTED when max ||b||^2 >= 2^24 (the byte rows are then
- * not kept: no batch could run on them).  Calls accepted and refused: as vs_bf_create_nd. */
+ * not kept: no batch could run on them).  Calls accepted and refused: as vs_bf_create_nd.
+ *
+ * A short call on the byte rows -- fewer than 4 batches of at most 16 queries, k <= 15 -- is one
+ * launch per batch (vs_bf_one_plan_u8 above; VSEARCH_ND_ONE_U8=0 at creation keeps the
+ * per-batch byte scan); same results and flags either way. */
 VS_API int vs_bf_create_nd_u8(const uint8_t* base_host, int64_t n_rows, int dim,
                               int device, int64_t id_offset, vs_index** out);
 
@@ -213,7 +245,8 @@ VS_API int vs_bf_create_nd_u8(const uint8_t* base_host, int64_t n_rows, int dim,
  * rebuilds, q.b = q'.b' + 128 (sum q' + sum b') + 128^2 dim with x' = x - 128.  Any other batch
  * is skipped: the *_dev calls report flags == 2, the host calls rerun it on the fp32 rows.
  * Precision 1 forces the fp32 rows; precision 2 returns VS_ERR_UNSUPPORTED when the byte copy
- * was not kept.  k >= 16 and vs_bf_scores_dev read the fp32 rows, as under L2.
+ * was not kept.  k >= 16 and vs_bf_scores_dev read the fp32 rows, as under L2.  Short calls on
+ * the byte rows take the single-call byte kernel as under L2 (vs_bf_one_plan_u8).
  *
  * Outputs are the inner-product ones of vs_bf_create_nd: the *_dev calls return s = -(q.v)
  * ascending by (s, id), an exactly zero product as -0.0; the host calls return q.v descending,

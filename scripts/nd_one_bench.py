@@ -15,7 +15,16 @@ specialised scan_one_kernel (this library, no force) is measured beside them as 
 
     python scripts/nd_one_bench.py [--dims 96,128,384,768,1024,2048] [--rows 1000000] [--reps 5] [--parent-root DIR]
 
-One JSON line per (dimension, B, leg) with every repeat and min / max."""
+One JSON line per (dimension, B, leg) with every repeat and min / max.
+
+--u8: the single-call BYTE scan (scan_one_nd_i8_kernel) instead: N = 1 M synth_sift rows as uint8 in a from_u8
+index, byte-valued synth_sift queries, the same three legs with VSEARCH_ND_ONE_U8=0 as the toggle (per-batch route: reset,
+nd_prep_i8_kernel, scan_nd_i8_kernel, merge), and a fourth, `f32`: the default index under precision 1 (the fp32 rows on
+scan_one_nd_kernel), for scale.  --dims takes dim[:metric] there (default 96,128:ip,384,384:ip,768,1024,2048; dim 128 is a
+general byte index under inner product only).  The check before timing also ends the run if a byte leg refuses a batch
+(flags == 2: it would time an empty scan).  Row bytes are N dim_b for the byte legs and 4 N dim_p for `f32`.
+
+    python scripts/nd_one_bench.py --u8 [--parent-root DIR] > profiles/nd_one_u8_bench.txt"""
 import argparse
 import hashlib
 import json
@@ -49,26 +58,38 @@ def worker(a):
 
     pkg = ge.load_package()
     dev = torch.device("cuda:0")
-    base = _data(a.rows, a.dim, 1)
+    base = pkg.synth_sift(a.rows, 1, a.dim).astype(np.uint8) if a.u8 else _data(a.rows, a.dim, 1)
     idx = {}
     for leg in a.legs.split(","):
         name, _, env = leg.partition("=")
         var, _, val = env.partition("=")
+        if name == "f32":  # (--u8) the default index once more: measured under precision 1
+            idx[name] = idx["one"]
+            continue
         if var:
             os.environ[var] = val
         try:
-            idx[name] = pkg.BruteForceIndex(base)
-            idx[name].set_precision(1)
+            if a.u8:
+                idx[name] = pkg.BruteForceIndex.from_u8(base, metric=a.metric)
+                idx[name].set_precision(2)  # (refused if the byte copy was not kept)
+            else:
+                idx[name] = pkg.BruteForceIndex(base)
+                idx[name].set_precision(1)
         finally:
             if var:
                 del os.environ[var]
     del base
-    qd = torch.from_numpy(_data(64 * 16, a.dim, 2)).to(dev)
+    qd = torch.from_numpy(pkg.synth_sift(64 * 16, 2, a.dim) if a.u8 else _data(64 * 16, a.dim, 2)).to(dev)
     oi = torch.zeros((16, K + 1), dtype=torch.int32, device=dev)
     od = torch.zeros((16, K + 1), dtype=torch.float32, device=dev)
     fl = torch.zeros((16,), dtype=torch.int32, device=dev)
     st = torch.cuda.current_stream().cuda_stream
     print(json.dumps({"ready": sorted(idx)}), flush=True)
+
+    def select(name):
+        if a.u8:
+            idx[name].set_precision(1 if name == "f32" else 2)
+        return idx[name]
 
     def call(ix, B, i):
         ix.search_dev(qd.data_ptr() + (i % 64) * B * a.dim * 4, B, K, oi.data_ptr(), od.data_ptr(), fl.data_ptr(), st)
@@ -79,19 +100,22 @@ def worker(a):
             break
         if cmd[0] == "check":  # a digest of the outputs of calls 0..3 of every index, forwards and backwards walks included
             B = int(cmd[1])
-            out = {}
-            for name, ix in idx.items():
+            out, refused = {}, []
+            for name in idx:
+                ix = select(name)
                 h = hashlib.sha256()
                 for i in range(4):
                     call(ix, B, i)
                     torch.cuda.synchronize()
                     for t in (oi, od, fl):
                         h.update(t[:B].cpu().numpy().tobytes())
+                    if (fl[:B] == 2).any().item():
+                        refused.append(name)
                 out[name] = h.hexdigest()[:16]
-            print(json.dumps({"check": out}), flush=True)
+            print(json.dumps({"check": out, "refused": refused}), flush=True)
             continue
         name, B = cmd[1], int(cmd[2])
-        ix = idx[name]
+        ix = select(name)
         for i in range(8):
             call(ix, B, i)
         torch.cuda.synchronize()
@@ -126,7 +150,7 @@ class Worker:
         e.update(env)
         self.legs = [x.partition("=")[0] for x in legs.split(",")]
         self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", "--root", root, "--dim", str(dim), "--rows", str(a.rows),
-                                   "--legs", legs], env=e, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+                                   "--legs", legs] + (["--u8", "--metric", str(a.metric)] if a.u8 else []), env=e, stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
 
     def read(self):
         line = self.p.stdout.readline()
@@ -150,7 +174,9 @@ class Worker:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--dims", default="96,128,384,768,1024,2048")
+    ap.add_argument("--dims", default="")
+    ap.add_argument("--u8", action="store_true", help="the byte scan of a from_u8 index (scan_one_nd_i8_kernel) instead")
+    ap.add_argument("--metric", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--batches", default="1,16")
@@ -162,6 +188,9 @@ def main():
     a = ap.parse_args()
     if a.worker:
         return worker(a)
+    if a.u8:
+        return main_u8(a)
+    a.dims = a.dims or "96,128,384,768,1024,2048"
     for dim in [int(x) for x in a.dims.split(",")]:
         force = {"VSEARCH_ND_FORCE": "1"} if dim == 128 else {}
         workers = [Worker(a, ROOT, dim, "one,off=VSEARCH_ND_ONE=0", force)]
@@ -193,6 +222,47 @@ def main():
                                       "us_per_call": [round(x, 2) for x in us], "us_min": round(min(us), 2), "us_max": round(max(us), 2),
                                       "sync_call_us": [round(x, 1) for x in sy], "sync_min": round(min(sy), 1), "sync_max": round(max(sy), 1),
                                       "hbm_frac_best": round(4.0 * a.rows * row_floats / (min(us) * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+                                      "same_outputs": True}), flush=True)
+        finally:
+            for w in workers:
+                w.close()
+
+
+def main_u8(a):
+    for spec in (a.dims or "96,128:ip,384,384:ip,768,1024,2048").split(","):
+        d, _, mname = spec.partition(":")
+        dim, a.metric = int(d), 1 if mname == "ip" else 0
+        workers = [Worker(a, ROOT, dim, "one,off=VSEARCH_ND_ONE_U8=0,f32", {})]
+        if a.parent_root:
+            workers.append(Worker(a, os.path.abspath(a.parent_root), dim, "parent", {}))
+        try:
+            for w in workers:
+                w.read()  # ready
+            order = [(w, leg) for w in workers for leg in w.legs]
+            dim_p, dim_b = (dim + 15) // 16 * 16, (dim + 63) // 64 * 64
+            for B in [int(x) for x in a.batches.split(",")]:
+                digests = {}
+                for w in workers:
+                    c = w.ask(f"check {B}")
+                    if c["refused"]:
+                        raise SystemExit(f"dim {dim} B {B}: a batch was refused (flags == 2) on {c['refused']}")
+                    digests.update(c["check"])
+                if len(set(digests.values())) != 1:
+                    raise SystemExit(f"dim {dim} B {B}: the legs answer differently: {digests}")
+                res = {leg: {"us": [], "sync_us": []} for _, leg in order}
+                for _ in range(a.reps):
+                    for w, leg in order:
+                        m = w.ask(f"measure {leg} {B}")
+                        res[leg]["us"].append(m["us"])
+                        res[leg]["sync_us"].append(m["sync_us"])
+                for _, leg in order:
+                    us, sy = res[leg]["us"], res[leg]["sync_us"]
+                    row_bytes = 4 * dim_p if leg == "f32" else dim_b
+                    print(json.dumps({"dim": dim, "dim_b": dim_b, "metric": "ip" if a.metric else "l2", "rows": a.rows, "B": B, "k": K, "leg": leg,
+                                      "us_per_call": [round(x, 2) for x in us], "us_min": round(min(us), 2), "us_max": round(max(us), 2),
+                                      "sync_call_us": [round(x, 1) for x in sy], "sync_min": round(min(sy), 1), "sync_max": round(max(sy), 1),
+                                      "row_bytes": row_bytes,
+                                      "hbm_frac_best": round(1.0 * a.rows * row_bytes / (min(us) * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
                                       "same_outputs": True}), flush=True)
         finally:
             for w in workers:
