@@ -791,20 +791,24 @@ bool bf_seeded(int64_t n_rows, int nb, int k1) {
     return nb >= g_seed_min_batches && tiles_total >= 2 * vs::kSeedWaves && g_xchg_first_it >= 0 && cap_ok;
 }
 
+// What every single-call route refuses, and the plan of routes 2 and 3, which share their body and its geometry.
+bool one_call_is_short(int nb, int B, int k1) { return nb < kOneMaxBatches && B <= kOneMaxQueries && k1 <= 16; }
+int one_route_nd(int route, int64_t n_rows, int num_cus, int64_t* out) {
+    if (n_rows > 0x7fffffff - 2 * vs::kOneNdUnit) return 0;  // (the kernel counts rows in 32 bits)
+    out[0] = route;
+    out[2] = vs::kOneNdUnit;
+    vs::scan_one_nd_geometry(n_rows, num_cus, &out[1], &out[3]);
+    return route;
+}
+
 // The single-call route of a call that reads the fp32 rows (vs_bf_one_plan's rule; bf_launch goes through it): 0 = none,
 // 1 = scan_one_kernel (the specialised 128-d index), 2 = scan_one_nd_kernel (a general index), with the
 // launch's workgroups, the rows of a wave's unit of work and the most units any one wave gets in out[1..3] (route 1
 // hands its units out through a ticket: the even share).
 int one_route(int64_t n_rows, bool general, int num_cus, int nb, int B, int k1, int64_t* out) {
     out[0] = out[1] = out[2] = out[3] = 0;
-    if (nb >= kOneMaxBatches || B > kOneMaxQueries || k1 > 16) return 0;
-    if (general) {
-        if (n_rows > 0x7fffffff - 2 * vs::kOneNdUnit) return 0;  // (the kernel counts rows in 32 bits)
-        out[0] = 2;
-        out[2] = vs::kOneNdUnit;
-        vs::scan_one_nd_geometry(n_rows, num_cus, &out[1], &out[3]);
-        return 2;
-    }
+    if (!one_call_is_short(nb, B, k1)) return 0;
+    if (general) return one_route_nd(2, n_rows, num_cus, out);
     if (bf_seeded(n_rows, nb, k1)) return 0;
     const int64_t tiles = (n_rows + vs::kTileRows - 1) / vs::kTileRows;
     out[0] = 1;
@@ -824,13 +828,9 @@ constexpr int kOneU8ShortRowBytes = 128;
 constexpr int kOneU8ShortRowQueries = 12;
 int one_route_u8(int64_t n_rows, int dim, int num_cus, int nb, int B, int k1, int64_t* out) {
     out[0] = out[1] = out[2] = out[3] = 0;
-    if (nb >= kOneMaxBatches || B > kOneMaxQueries || k1 > 16) return 0;
-    if (n_rows > 0x7fffffff - 2 * vs::kOneNdUnit) return 0;  // (the kernel counts rows in 32 bits)
+    if (!one_call_is_short(nb, B, k1)) return 0;
     if (vs::nd_dim_b(dim) <= kOneU8ShortRowBytes && B > kOneU8ShortRowQueries) return 0;
-    out[0] = 3;
-    out[2] = vs::kOneNdUnit;
-    vs::scan_one_nd_geometry(n_rows, num_cus, &out[1], &out[3]);
-    return 3;
+    return one_route_nd(3, n_rows, num_cus, out);
 }
 
 // nb <= kMaxMulti batches of B queries in ONE persistent launch on stream s (preceded by the seed launches or the

@@ -38,12 +38,7 @@ static_assert(kIvfOneUnitRows % kIvfOneBlockRows == 0, "a unit is whole blocks, 
 constexpr int kIvfOneQ = 16;                                   // query columns
 constexpr int kIvfOnePickVPL = 16;                             // scores per lane of the selection
 static_assert(64 * kIvfOnePickVPL == kIvfOneMaxNlist, "the selection keeps a query's scores in one wave's registers");
-// scan: norms [16] | counters [32] | flag | lane minima [16][33]  (scan_one_nd_kernel's layout)
-constexpr int kIvfOneScanScratch = 8192;
-constexpr int ivf_one_scan_region(int dim_p, int kcap) {       // query fragments, later the merge buffers
-    const int frag = dim_p * 64, merge = one_tail_bytes(1, kcap);
-    return frag > merge ? frag : merge;
-}
+// (the scan's LDS is OneNdLds of vs_one_tail.h over rows of 4 dim_p bytes)
 // coarse: query fragments, later the last arriver's winners [8 waves][kIvfMaxProbe]; behind them norms [32] | flag [32] |
 // masks [kIvfOneMaxNlist] | prefix scan [kScanThreads]
 constexpr int kIvfOneCoarseScratch = (32 + 32 + kIvfOneMaxNlist + kScanThreads) * 4;
@@ -51,10 +46,8 @@ constexpr int ivf_one_coarse_region(int dim_p) {
     const int frag = dim_p * 64, sel = kScanWaves * kIvfMaxProbe * 4;
     return frag > sel ? frag : sel;
 }
-constexpr int kIvfOneMaxLds =
-    (ivf_one_coarse_region(kNdMaxDim) + kIvfOneCoarseScratch > ivf_one_scan_region(kNdMaxDim, 16) + kIvfOneScanScratch)
-        ? ivf_one_coarse_region(kNdMaxDim) + kIvfOneCoarseScratch
-        : ivf_one_scan_region(kNdMaxDim, 16) + kIvfOneScanScratch;
+constexpr int kIvfOneCoarseMaxLds = ivf_one_coarse_region(kNdMaxDim) + kIvfOneCoarseScratch;
+constexpr int kIvfOneMaxLds = kIvfOneCoarseMaxLds > one_nd_lds_bytes(4 * kNdMaxDim, 16) ? kIvfOneCoarseMaxLds : one_nd_lds_bytes(4 * kNdMaxDim, 16);
 static_assert(kIvfOneMaxLds <= 160 * 1024, "LDS of a CU");
 
 // The dot products of one 64-row block (four 16-row tiles at sb) with the 16 staged query columns: scan_nd_kernel's chain,
@@ -283,15 +276,11 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_one_coarse_kernel(const I
 template <int KCAP, bool IP>
 __global__ __launch_bounds__(kScanThreads, 1) void ivf_one_scan_kernel(const IvfOneParams p) {
     constexpr int T = kIvfOneTiles;
-    constexpr int NQ = kIvfOneQ;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int dim_p = p.dim_p, B = p.o.nq_valid;
-    const int region = ivf_one_scan_region(dim_p, KCAP);
-    f32x4* qfrag = reinterpret_cast<f32x4*>(smem);                   // [dim_p / 16][64]
-    float* lds_qn = reinterpret_cast<float*>(smem + region);         // [16]
-    int* lds_cnt = reinterpret_cast<int*>(lds_qn + 32);              // [32]
-    int* lds_flag = lds_cnt + 32;                                    // [1]
-    float* lds_lmin = reinterpret_cast<float*>(lds_flag + 32);       // [16 queries][32 lanes of the workgroup holding that column]
+    const auto L = one_nd_lds<float>(smem, 4 * dim_p, KCAP);
+    f32x4* qfrag = reinterpret_cast<f32x4*>(L.tail.region);  // [dim_p / 16][64]
+    float* lds_qn = L.term;        // [16]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -301,7 +290,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_one_scan_kernel(const Ivf
     const bool has_units = (int)blockIdx.x < n_units;  // a workgroup without units goes straight to the ticket
 
     if (has_units) one_nd_stage_queries(p.o.q, B, p.dim, dim_p, qfrag, lds_qn);
-    for (int i = tid; i < NQ * 33; i += kScanThreads) lds_lmin[i] = VS_INF;  // (rows 33 apart: bank spread)
+    one_nd_reset_lmin(L.tail.lmin);
     __syncthreads();
     float qn = 0.f;
     if constexpr (!IP) qn = has_units ? lds_qn[r] : 0.f;
@@ -356,19 +345,19 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_one_scan_kernel(const Ivf
                     touched = true;
                 }
             }
-            if (touched) lds_lmin[r * 33 + 4 * wave + g] = ld[0][0];  // this lane's best so far, for the shared bound
+            if (touched) L.tail.lmin[r * 33 + 4 * wave + g] = ld[0][0];  // this lane's best so far, for the shared bound
             ++c_n;
             if (c_n == 1 || c_n == 2 || c_n == 4 || c_n == 8 || c_n == 16) {  // wave-uniform checkpoints
                 // the k-th smallest of the column's lane minima: k distinct rows of the column's probed lists are at
                 // least that close (vs_one_tail.h); whatever the other waves have published by now, stale only loosens it
-                const float sbound = one_shared_bound(lds_lmin, r, g, p.o.k1);
+                const float sbound = one_shared_bound(L.tail.lmin, r, g, p.o.k1);
                 if (live && sbound < VS_INF) tau = fminf(tau, next_up(sbound));
             }
         }
     }
 
     // (the query fragments are done with: the merges overlay them)
-    one_tail<1, KCAP, ivf_one_scan_region(16, KCAP)>(p.o, OneTailLds{smem, lds_cnt, lds_flag, lds_lmin}, ld, li, IvfOneIdMap{p.id_map});
+    one_tail<1, KCAP, one_nd_region(64, KCAP)>(p.o, L.tail, ld, li, IvfOneIdMap{p.id_map});  // (64: the shortest row, dim_p = 16)
 }
 
 int ivf_one_coarse_grid(int nlist, int num_cus) {
@@ -377,20 +366,6 @@ int ivf_one_coarse_grid(int nlist, int num_cus) {
 }
 
 int ivf_one_scan_grid(int num_cus) { return std::max(1, std::min(num_cus, kSlotStride)); }
-
-template <void (*kfn)(const IvfOneParams)>
-static hipError_t ivf_one_launch_t(const IvfOneParams& p, int grid, int lds, hipStream_t s) {
-    static bool attr_set[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, kIvfOneMaxLds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(kScanThreads), lds, s, p);
-    return hipGetLastError();
-}
 
 static bool ivf_one_params_ok(const IvfOneParams& p) {
     return p.dim >= 1 && p.dim <= kNdMaxDim && p.dim_p == nd_dim_p(p.dim) && p.nlist >= 1 && p.nlist <= kIvfOneMaxNlist && p.o.nq_valid >= 1 &&
@@ -402,16 +377,16 @@ static bool ivf_one_params_ok(const IvfOneParams& p) {
 hipError_t launch_ivf_one_coarse(const IvfOneParams& p, int grid, hipStream_t s) {
     if (!ivf_one_params_ok(p) || grid < 1 || grid > kSlotStride) return hipErrorInvalidValue;
     const int lds = ivf_one_coarse_region(p.dim_p) + kIvfOneCoarseScratch;
-    return p.metric ? ivf_one_launch_t<ivf_one_coarse_kernel<true>>(p, grid, lds, s) : ivf_one_launch_t<ivf_one_coarse_kernel<false>>(p, grid, lds, s);
+    return p.metric ? launch_big_lds<ivf_one_coarse_kernel<true>, kIvfOneMaxLds>(p, grid, lds, s) : launch_big_lds<ivf_one_coarse_kernel<false>, kIvfOneMaxLds>(p, grid, lds, s);
 }
 
 hipError_t launch_ivf_one_scan(const IvfOneParams& p, int grid, hipStream_t s) {
     if (!ivf_one_params_ok(p) || grid < 1 || grid > kSlotStride) return hipErrorInvalidValue;
     const int kcap = p.o.k1 <= 8 ? 8 : 16;
-    const int lds = ivf_one_scan_region(p.dim_p, kcap) + kIvfOneScanScratch;
+    const int lds = one_nd_lds_bytes(4 * p.dim_p, kcap);
     if (kcap == 8)
-        return p.metric ? ivf_one_launch_t<ivf_one_scan_kernel<8, true>>(p, grid, lds, s) : ivf_one_launch_t<ivf_one_scan_kernel<8, false>>(p, grid, lds, s);
-    return p.metric ? ivf_one_launch_t<ivf_one_scan_kernel<16, true>>(p, grid, lds, s) : ivf_one_launch_t<ivf_one_scan_kernel<16, false>>(p, grid, lds, s);
+        return p.metric ? launch_big_lds<ivf_one_scan_kernel<8, true>, kIvfOneMaxLds>(p, grid, lds, s) : launch_big_lds<ivf_one_scan_kernel<8, false>, kIvfOneMaxLds>(p, grid, lds, s);
+    return p.metric ? launch_big_lds<ivf_one_scan_kernel<16, true>, kIvfOneMaxLds>(p, grid, lds, s) : launch_big_lds<ivf_one_scan_kernel<16, false>, kIvfOneMaxLds>(p, grid, lds, s);
 }
 
 }  // namespace vs

@@ -13,6 +13,23 @@ constexpr int kMaxBatch = 32;      // queries per scan pass (two 16-query MFMA c
 constexpr int kScanPadRows = 64;  // every row array handed to the scan is allocated with this many spare rows (tile DMAs are not clamped)
 constexpr int kSlotStride = 256;   // threshold-exchange slots: [32 queries][256 workgroups]
 
+// Launch of a kernel of kScanThreads threads that takes its parameter block P by value and `lds` <= MAX_LDS bytes of
+// dynamic LDS, more than the default limit allows: the kernel's limit is raised once per device (the attribute belongs
+// to the device's copy of the code object).
+template <auto kfn, int MAX_LDS, class P>
+hipError_t launch_big_lds(const P& p, int grid, int lds, hipStream_t s) {
+    static bool attr_set[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (!attr_set[dev]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS);
+        if (e != hipSuccess) return e;
+        attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(kScanThreads), lds, s, p);
+    return hipGetLastError();
+}
+
 enum ScanMode { kModeTopK = 0, kModeStore = 1, kModeAssign = 2, kModeFilter = 3 };
 
 struct ScanParams {

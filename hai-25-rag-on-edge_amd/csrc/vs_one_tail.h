@@ -1,9 +1,11 @@
-// vs_one_tail.h -- what the two single-call scans, scan_one_kernel (vs_scan_one.hip) and scan_one_nd_kernel
-// (vs_scan_one_nd.hip), do with their lane lists without a second launch: the bound from the workgroup's lane minima that
-// the scan loops take at their checkpoints, the workgroup merge into one partial list per query, and the merge of the
-// partial lists by the workgroup that arrives last.  Device functions only; the kernel keeps its prologue, data path,
-// distance epilogue and checkpoint schedule and hands over its lane lists and its LDS (OneTailLds).  lane = tid & 63,
-// wave = tid >> 6, r = lane & 15 and g = lane >> 4 as in the kernels: lane (r, g) holds queries 16 h + r, h < NQH.
+// vs_one_tail.h -- what the single-call scans, scan_one_kernel (vs_scan_one.hip), scan_one_nd_kernel (vs_scan_one_nd.hip),
+// scan_one_nd_i8_kernel (vs_scan_one_nd_i8.hip) and ivf_one_scan_kernel (vs_ivf_one_nd.hip), do with their lane lists without
+// a second launch: the bound from the workgroup's lane minima that the scan loops take at their checkpoints, the
+// workgroup merge into one partial list per query, and the merge of the partial lists by the workgroup that arrives
+// last; and the LDS layout of the three of them on a general index (OneNdLds).
+// Device functions only; the kernel keeps its prologue, data path and distance arithmetic and hands over its lane lists
+// and its LDS (OneTailLds).  lane = tid & 63, wave = tid >> 6, r = lane & 15 and g = lane >> 4 as in the kernels: lane
+// (r, g) holds queries 16 h + r, h < NQH.
 #pragma once
 #include "vs_kernels.h"
 #include "vs_dev.h"
@@ -98,6 +100,38 @@ __device__ __forceinline__ float one_shared_bound(const float* lds_lmin, int col
     float x = fmaxf(m, __shfl_xor(m, 16));
     x = fmaxf(x, __shfl_xor(x, 32));
     return x;  // (+inf while a lane holds fewer than t minima)
+}
+
+// The LDS of a single-call kernel on a general index: region | term [32] | counters [32] | flag [32] | lane minima
+// [16][33].  The region holds the 16 query columns in MFMA B-fragment order (16 x the bytes of a padded row) while the
+// rows are scanned and the merge buffers afterwards; `term` is the per-query term of the kernel's arithmetic (a float
+// norm, an int32 term).
+constexpr int kOneNdScratch = 8192;  // everything behind the region
+constexpr int one_nd_region(int row_bytes, int kcap) {
+    const int frag = 16 * row_bytes, merge = one_tail_bytes(1, kcap);
+    return frag > merge ? frag : merge;
+}
+constexpr int one_nd_lds_bytes(int row_bytes, int kcap) { return one_nd_region(row_bytes, kcap) + kOneNdScratch; }
+static_assert(one_nd_lds_bytes(4 * kNdMaxDim, 16) <= 160 * 1024, "LDS of a CU");
+template <class Term>  // float or int
+struct OneNdLds {
+    OneTailLds tail;  // region | counters | flag | lane minima: what one_tail takes
+    Term* term;       // [16]
+};
+template <class Term>
+__device__ __forceinline__ OneNdLds<Term> one_nd_lds(char* smem, int row_bytes, int kcap) {
+    static_assert(sizeof(Term) == 4, "32 words of terms");
+    OneNdLds<Term> L;
+    L.tail.region = smem;
+    L.term = reinterpret_cast<Term*>(smem + one_nd_region(row_bytes, kcap));
+    L.tail.cnt = reinterpret_cast<int*>(L.term + 32);
+    L.tail.flag = L.tail.cnt + 32;
+    L.tail.lmin = reinterpret_cast<float*>(L.tail.flag + 32);
+    return L;
+}
+// no lane of the workgroup has a minimum yet; every thread calls it, the caller's next barrier publishes it
+__device__ __forceinline__ void one_nd_reset_lmin(float* lds_lmin) {
+    for (int i = threadIdx.x; i < 16 * 33; i += kScanThreads) lds_lmin[i] = VS_INF;  // (rows 33 apart: bank spread)
 }
 
 // the ids of the lane lists are the ids of the outputs (the brute-force scans add id_offset when they insert)

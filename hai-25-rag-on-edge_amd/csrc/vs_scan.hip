@@ -1615,18 +1615,7 @@ hipError_t launch_scan_i8_wide(const WideParams& p, int grid, int nqh, hipStream
 
 template <int NQH, int KCAP, int MODE, int PREC = 0>
 static hipError_t launch_scan_t(const ScanParams& p, int grid, hipStream_t s) {
-    auto kfn = scan_kernel<NQH, KCAP, MODE, PREC>;
-    static bool attr_set[64] = {};  // per device: the attribute belongs to the device's copy of the code object
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kScanLds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(kScanThreads), kScanLds, s, p);
-    return hipGetLastError();
+    return launch_big_lds<scan_kernel<NQH, KCAP, MODE, PREC>, kScanLds>(p, grid, kScanLds, s);
 }
 
 

@@ -224,17 +224,7 @@ int scan_one_grid(int64_t n_rows, int num_cus) {
 
 template <int NQH, int KCAP>
 static hipError_t launch_one_t(const OneParams& p, int grid, hipStream_t s) {
-    auto kfn = scan_one_kernel<NQH, KCAP>;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, kOneLds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(kScanThreads), kOneLds, s, p);
-    return hipGetLastError();
+    return launch_big_lds<scan_one_kernel<NQH, KCAP>, kOneLds>(p, grid, kOneLds, s);
 }
 
 hipError_t launch_scan_one(const OneParams& p, int grid, hipStream_t s) {

@@ -36,13 +36,7 @@ static_assert(kOneNdUnitRows <= kScanPadRows, "units are loaded unclamped");
 static_assert(kOneNdUnitRows == 64, "one row norm per lane");
 constexpr int kOneNdDepth = 4;                              // K steps in flight per wave
 constexpr int kOneNdQ = 16;                                 // query columns
-constexpr int kOneNdScratch = 8192;                         // norms [16] | counters [32] | flag | lane minima [16][33]
-constexpr int one_nd_region(int dim_p, int kcap) {          // query fragments, later the merge buffers
-    const int frag = dim_p * 64, merge = one_tail_bytes(1, kcap);
-    return frag > merge ? frag : merge;
-}
-constexpr int kOneNdMaxLds = one_nd_region(kNdMaxDim, 16) + kOneNdScratch;
-static_assert(kOneNdMaxLds <= 160 * 1024, "LDS of a CU");
+constexpr int kOneNdMaxLds = one_nd_lds_bytes(4 * kNdMaxDim, 16);  // (OneNdLds of vs_one_tail.h over rows of 4 dim_p bytes)
 
 }  // namespace
 
@@ -51,15 +45,12 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_one_nd_kernel(const OneN
     const OneParams& p = pn.o;
     constexpr int T = kOneNdTiles;
     constexpr int D = kOneNdDepth;
-    constexpr int NQ = kOneNdQ;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int dim = pn.dim, dim_p = pn.dim_p;
-    const int region = one_nd_region(dim_p, KCAP);
-    f32x4* qfrag = reinterpret_cast<f32x4*>(smem);                   // [dim_p / 16][64]
-    float* lds_qn = reinterpret_cast<float*>(smem + region);         // [16]
-    int* lds_cnt = reinterpret_cast<int*>(lds_qn + 32);              // [32]
-    int* lds_flag = lds_cnt + 32;                                    // [1]
-    float* lds_lmin = reinterpret_cast<float*>(lds_flag + 32);       // [16 queries][32 lanes of the workgroup holding that column]
+    const auto L = one_nd_lds<float>(smem, 4 * dim_p, KCAP);
+    f32x4* qfrag = reinterpret_cast<f32x4*>(L.tail.region);  // [dim_p / 16][64]
+    float* lds_qn = L.term;                                  // [16]
+    float* lds_lmin = L.tail.lmin;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -72,7 +63,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_one_nd_kernel(const OneN
     // ---- the queries: B fragments into LDS and their squared norms (vs_one_nd_queries.h)
     one_nd_stage_queries(p.q, p.nq_valid, dim, dim_p, qfrag, lds_qn);
     // the lanes' current minima, shared by the workgroup (see the checkpoints)
-    for (int i = tid; i < NQ * 33; i += kScanThreads) lds_lmin[i] = VS_INF;  // (rows 33 apart: bank spread)
+    one_nd_reset_lmin(lds_lmin);
     __syncthreads();
     const float qn = lds_qn[r];
     const bool live = r < p.nq_valid;
@@ -203,7 +194,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_one_nd_kernel(const OneN
 #undef VS_ONE_ND_STEP
 
     // (the query fragments are done with: the merges overlay them)
-    one_tail<1, KCAP, one_nd_region(16, KCAP)>(p, OneTailLds{smem, lds_cnt, lds_flag, lds_lmin}, ld, li);
+    one_tail<1, KCAP, one_nd_region(64, KCAP)>(p, L.tail, ld, li);  // (64: the shortest padded row, dim_p = 16)
 }
 
 void scan_one_nd_geometry(int64_t n_rows, int num_cus, int64_t* grid, int64_t* units_per_wave) {
@@ -215,17 +206,7 @@ void scan_one_nd_geometry(int64_t n_rows, int num_cus, int64_t* grid, int64_t* u
 
 template <int KCAP>
 static hipError_t launch_one_nd_t(const OneNdParams& p, int grid, hipStream_t s) {
-    auto kfn = scan_one_nd_kernel<KCAP>;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, kOneNdMaxLds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(kScanThreads), one_nd_region(p.dim_p, KCAP) + kOneNdScratch, s, p);
-    return hipGetLastError();
+    return launch_big_lds<scan_one_nd_kernel<KCAP>, kOneNdMaxLds>(p, grid, one_nd_lds_bytes(4 * p.dim_p, KCAP), s);
 }
 
 hipError_t launch_scan_one_nd(const OneNdParams& p, int grid, hipStream_t s) {

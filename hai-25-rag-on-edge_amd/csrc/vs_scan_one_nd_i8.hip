@@ -38,13 +38,7 @@ static_assert(kOneNd8UnitRows <= kScanPadRows, "units are loaded unclamped");
 static_assert(kOneNd8UnitRows == 64, "one row term per lane");
 constexpr int kOneNd8Depth = 4;                               // K steps in flight per wave
 constexpr int kOneNd8Q = 16;                                  // query columns
-constexpr int kOneNd8Scratch = 8192;                          // query terms [16] | counters [32] | flag | lane minima [16][33]
-constexpr int one_nd_i8_region(int dim_b, int kcap) {         // query fragments, later the merge buffers
-    const int frag = dim_b * 16, merge = one_tail_bytes(1, kcap);
-    return frag > merge ? frag : merge;
-}
-constexpr int kOneNd8MaxLds = one_nd_i8_region(kNdMaxDim, 16) + kOneNd8Scratch;
-static_assert(kOneNd8MaxLds <= 160 * 1024, "LDS of a CU");
+constexpr int kOneNd8MaxLds = one_nd_lds_bytes(kNdMaxDim, 16);  // (OneNdLds of vs_one_tail.h over rows of dim_b bytes)
 
 }  // namespace
 
@@ -53,15 +47,13 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_one_nd_i8_kernel(const O
     const OneParams& p = pn.o;
     constexpr int T = kOneNd8Tiles;
     constexpr int D = kOneNd8Depth;
-    constexpr int NQ = kOneNd8Q;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int dim_b = pn.dim_b;
-    const int region = one_nd_i8_region(dim_b, KCAP);
-    i32x4* qfrag = reinterpret_cast<i32x4*>(smem);                   // [dim_b / 64][64]
-    int* lds_qt = reinterpret_cast<int*>(smem + region);             // [16]
-    int* lds_cnt = lds_qt + 32;                                      // [32]
-    int* lds_flag = lds_cnt + 32;                                    // [1]
-    float* lds_lmin = reinterpret_cast<float*>(lds_flag + 32);       // [16 queries][32 lanes of the workgroup holding that column]
+    const auto L = one_nd_lds<int>(smem, dim_b, KCAP);
+    i32x4* qfrag = reinterpret_cast<i32x4*>(L.tail.region);  // [dim_b / 64][64]
+    int* lds_qt = L.term;                                    // [16]
+    int* lds_flag = L.tail.flag;
+    float* lds_lmin = L.tail.lmin;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -72,7 +64,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_one_nd_i8_kernel(const O
     const bool odd = (C & 1) != 0;
 
     // the lanes' current minima, shared by the workgroup (see the checkpoints)
-    for (int i = tid; i < NQ * 33; i += kScanThreads) lds_lmin[i] = VS_INF;  // (rows 33 apart: bank spread)
+    one_nd_reset_lmin(lds_lmin);
     // ---- the queries: byte B fragments into LDS, their terms, and the batch verdict (vs_one_nd_queries.h; ends with a barrier)
     const bool run = one_nd_stage_queries_i8<IP>(p.q, p.nq_valid, pn.dim, dim_b, pn.bmax, qfrag, lds_qt);  // workgroup-uniform
     const int qt = lds_qt[r];
@@ -203,7 +195,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_one_nd_i8_kernel(const O
 #undef VS_ONE_ND8_STEP
 
     // (the query fragments are done with: the merges overlay them)
-    one_tail<1, KCAP, one_nd_i8_region(64, KCAP)>(p, OneTailLds{smem, lds_cnt, lds_flag, lds_lmin}, ld, li);
+    one_tail<1, KCAP, one_nd_region(64, KCAP)>(p, L.tail, ld, li);  // (64: the shortest padded row)
     // a refused batch: the workgroup that arrived last (the only one whose flag word is set) overwrites the tail's
     // flags with the verdict -- the lanes that wrote them there (lane 0 of wave q & 7), after a barrier
     if (!run) {  // workgroup-uniform
@@ -215,17 +207,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void scan_one_nd_i8_kernel(const O
 
 template <int KCAP, bool IP>
 static hipError_t launch_one_nd_i8_t(const OneNdI8Params& p, int grid, hipStream_t s) {
-    auto kfn = scan_one_nd_i8_kernel<KCAP, IP>;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, kOneNd8MaxLds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(kScanThreads), one_nd_i8_region(p.dim_b, KCAP) + kOneNd8Scratch, s, p);
-    return hipGetLastError();
+    return launch_big_lds<scan_one_nd_i8_kernel<KCAP, IP>, kOneNd8MaxLds>(p, grid, one_nd_lds_bytes(p.dim_b, KCAP), s);
 }
 
 hipError_t launch_scan_one_nd_i8(const OneNdI8Params& p, int grid, hipStream_t s) {
