@@ -212,6 +212,8 @@ def lib():
         "vs_ivf_nd_u8_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_ivf_one_plan": (i32, [i64, i32, i32, i32, i32, i32, i32, i32, vp]),
         "vs_ivf_one_stats": (i32, [vp, C.POINTER(i64), i32]),
+        "vs_ivf_one_plan_u8": (i32, [i64, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "vs_ivf_one_u8_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_ivf_nd_widek_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_ivf_search_topk": (i32, [vp, vp, i64, i32, i32, vp, vp, C.POINTER(i64), C.POINTER(Timing)]),
         "vs_ivf_search_topk_dev_multi": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
@@ -761,6 +763,15 @@ def ivf_one_plan(n_rows: int, dim: int, nlist: int, num_cus: int, n_batches: int
     return tuple(int(x) for x in out)
 
 
+def ivf_one_plan_u8(n_rows: int, dim: int, nlist: int, num_cus: int, n_batches: int, B: int, k: int, nprobe: int):
+    """The same for a general IVF index that keeps a byte copy of its rows (IVFIndex.from_u8 / build_u8 at precision 0
+    or 2; vs_ivf_one_plan_u8; host only): route 0 = the group route, 2 = the two-launch byte route; the rows per unit
+    are those of a byte unit."""
+    out = (C.c_int64 * 4)()
+    _check(lib().vs_ivf_one_plan_u8(n_rows, dim, nlist, num_cus, n_batches, B, k, nprobe, out))
+    return tuple(int(x) for x in out)
+
+
 class IVFIndex(_Index):
     """class IVFIndex (IVFIndex.h:14-97) on the GPU, reordered (contiguous list) layout, L2.
 
@@ -840,6 +851,14 @@ class IVFIndex(_Index):
         out = (C.c_int64 * 2)()
         _check(lib().vs_ivf_one_stats(self._h, out, 1 if reset else 0))
         return int(out[0]), int(out[1])
+
+    def one_u8_stats(self, reset: bool = False):
+        """(batches answered by the two-launch byte route of short calls, of those the batches with both byte and fp32
+        units, most units of any one of them) of a from_u8 general index since the last reset (vs_ivf_one_u8_stats;
+        synchronises the device)."""
+        out = (C.c_int64 * 3)()
+        _check(lib().vs_ivf_one_u8_stats(self._h, out, 1 if reset else 0))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def getNumVectors(self) -> int:
         return self.getNumDocs()

@@ -280,11 +280,15 @@ struct vs_index {
         int units_cap = 0;
         vs::DevBuf<float> part_d;    // [16][kSlotStride][kKcapMax] one partial list per workgroup and query
         vs::DevBuf<int32_t> part_i;
-        vs::DevBuf<int32_t> words;   // [0] the coarse launch's ticket | [1] the scan launch's | [2] units of the batch in flight
-        vs::DevBuf<unsigned long long> counters;  // [2]: see vs_ivf_one_stats
+        vs::DevBuf<int32_t> words;   // [0] the coarse launch's ticket | [1] the scan launch's | [2] units of the batch in flight |
+                                     // [3] of those, byte units (the byte route)
+        vs::DevBuf<unsigned long long> counters;  // [2]: see vs_ivf_one_stats | [3]: see vs_ivf_one_u8_stats
         bool ready = false;          // every buffer above allocated
     } ivfone;
     bool ivf_one = true;  // general IVF index: short calls take the two-launch route (VSEARCH_IVF_ONE=0 at creation: off)
+    // ... and on an index with a byte copy the byte route.  VSEARCH_IVF_ONE_U8 at creation: 0 = off, 2 = the
+    // byte route at every shape of ivf_one_route, the shapes ivf_one_route_u8 takes out included (the measurement's leg)
+    int ivf_one_u8 = 1;
     // ... and what a wide-k group (17 <= k <= 128, ivf_group_nd_wide_dev) needs beside it, allocated on the first such call
     struct IvfNdWide {
         vs::DevBuf<int32_t> plan, slots, items;  // the rescan plan's tables, as IvfNd's
@@ -1425,6 +1429,34 @@ int ivf_one_route(int64_t n_rows, int nlist, int num_cus, int nb, int B, int k, 
     return 1;
 }
 
+// The same for a short call on a general IVF index that keeps a byte copy of its rows, at precision 0 or 2
+// (vs_ivf_one_plan_u8's rule; ivf_group_nd_dev goes through it): 0 = the group route, 2 = ivf_one_coarse_kernel in its
+// byte-index mode + ivf_one_scan_u8_kernel per batch; out[2] = the rows of one BYTE unit (an fp32 unit of
+// the same batch has kIvfOneUnitRows).  The default rule is ivf_one_route's own; a shape leaves it only because it
+// measured slower than the route it would replace (include/vsearch.h, vs_ivf_one_plan_u8, lists them with their numbers).
+//   Measured (profiles/ivf_one_u8_bench.txt: 1 M synth_sift rows as uint8, trained index, nlist 1024, k = 10, B = 1 / 8 / 16,
+//   nprobe 8 / 32 / 128 / 256, 96, 128, 384 and 768-d, us per call back to back; the byte route | the group route on the byte
+//   rows | the fp32 two launches on the same index (precision 1)).  Two of the 48 shapes were slower than the group route
+//   they would replace, and keep it: B = 16 at nprobe 128 on 96-d rows, 345 | 330 | 369, and B = 16 at nprobe 256 on 128-d
+//   rows, 446 | 441 | 488.  Their measured neighbours were faster than both alternatives (96-d B = 16: nprobe 32 234 | 267 |
+//   247, nprobe 256 456 | 456 | 474; 128-d B = 16 nprobe 128: 340 | 392 | 380; B = 8 at every nprobe by 2.0 - 16 %), so the
+//   exception is those two shapes and nothing around them: what was not measured stays on the rule.
+//   One shape is 1.6 % behind the fp32 two launches and stays IN, because the rule could only send it to the group route
+//   instead: 96-d, B = 1, nprobe 8: 87.7 | 157.0 | 86.2.
+static bool ivf_one_u8_measured_slower(int dim, int B, int probes) {
+    return B == 16 && ((dim == 96 && probes == 128) || (dim == 128 && probes == 256));
+}
+int ivf_one_route_u8(int64_t n_rows, int dim, int nlist, int num_cus, int nb, int B, int k, int nprobe, int64_t* out) {
+    if (!ivf_one_route(n_rows, nlist, num_cus, nb, B, k, nprobe, out)) return 0;
+    if (ivf_one_u8_measured_slower(dim, B, std::min(nprobe, nlist))) {
+        out[0] = out[1] = out[2] = out[3] = 0;
+        return 0;
+    }
+    out[0] = 2;
+    out[2] = vs::kIvfOneU8UnitRows;
+    return 2;
+}
+
 // scratch of the two-launch route, all or nothing (vs_res.h handles); the tickets and counters start at zero
 int ensure_ivf_one(vs_index* h) {
     if (h->ivfone.ready) return VS_OK;
@@ -1433,25 +1465,35 @@ int ensure_ivf_one(vs_index* h) {
     const size_t ld = ((size_t)h->nlist + 63) & ~(size_t)63;
     const int np_max = std::min(kMaxNprobe, h->nlist);
     W.units_cap = (int)(std::min<int64_t>((int64_t)kOneMaxQueries * np_max, h->nlist) + h->n_rows / vs::kIvfOneUnitRows);
+    // (an index with a byte copy: a list probed by both kinds of query of a batch appears once as byte units and once as
+    // fp32 units)
+    if (h->d_nd_u8) W.units_cap += (int)(std::min<int64_t>((int64_t)kOneMaxQueries * np_max, h->nlist) + h->n_rows / vs::kIvfOneU8UnitRows);
     const size_t part = (size_t)kOneMaxQueries * vs::kSlotStride * kKcapMax;
     if ((rc = W.scores.alloc(kOneMaxQueries * ld)) || (rc = W.probes.alloc((size_t)kOneMaxQueries * np_max)) || (rc = W.units.alloc((size_t)4 * W.units_cap)) || (rc = W.part_d.alloc(part)) ||
-        (rc = W.part_i.alloc(part)) || (rc = W.words.alloc(4)) || (rc = W.counters.alloc(2)))
+        (rc = W.part_i.alloc(part)) || (rc = W.words.alloc(4)) || (rc = W.counters.alloc(5)))
         return rc;
     HIPCHK(hipMemset(W.words, 0, 4 * sizeof(int32_t)));
-    HIPCHK(hipMemset(W.counters, 0, 2 * sizeof(unsigned long long)));
+    HIPCHK(hipMemset(W.counters, 0, 5 * sizeof(unsigned long long)));
     HIPCHK(hipDeviceSynchronize());  // (the first launches go to the caller's stream, which nothing orders behind the memsets)
     W.ready = true;
     h->ivfone = std::move(W);
     return VS_OK;
 }
 
-// nb < kOneMaxBatches batches of B <= 16 queries, two launches each, everything on s
+int ensure_ivf_nd_ip(vs_index* h, hipStream_t s);
+
+// nb < kOneMaxBatches batches of B <= 16 queries, two launches each, everything on s.  plan[0] == 2: the byte route of an
+// index with a byte copy of its rows -- the coarse launch in its byte-index mode and ivf_one_scan_u8_kernel, the same
+// scratch, tickets and stage marks, counters of its own (vs_ivf_one_u8_stats); under inner product the rows' byte sums
+// first (ensure_ivf_nd_ip: one build launch on s at the index's first inner-product call, as on the group route).
 int ivf_one_nd_dev(vs_index* h, const int64_t* plan, const float* q_dev, int nb, int B, int k, int nprobe, float* out_d, int32_t* out_i,
                    hipStream_t s) {
     int rc = ensure_ivf_one(h);
     if (rc) return rc;
+    const bool bytes = plan[0] == 2;
+    if (bytes && h->metric == VS_METRIC_IP && (rc = ensure_ivf_nd_ip(h, s))) return rc;
     vs_index::IvfOne& W = h->ivfone;
-    vs::IvfOneParams p{};
+    vs::IvfOneU8Params p{};  // (the fp32 route launches its base)
     p.vecs = h->d_vecs;
     p.vnorm = h->d_norm;
     p.offsets = h->d_offsets;
@@ -1479,17 +1521,30 @@ int ivf_one_nd_dev(vs_index* h, const int64_t* plan, const float* q_dev, int nb,
     p.o.part_d = W.part_d;
     p.o.part_i = W.part_i;
     p.o.done = W.words + 1;
+    if (bytes) {
+        p.unit_rows = vs::kIvfOneUnitRows;  // (plan[2] is the byte unit's)
+        p.unit_rows8 = vs::kIvfOneU8UnitRows;
+        p.counters = W.counters + 2;
+        p.pair_count8 = h->d_nd_stats;
+        p.vecs_u8 = h->d_nd_u8;
+        p.rterm = h->d_nd_rterm;
+        if (h->metric == VS_METRIC_IP) p.rsum = h->ivfndip.rsum;
+        p.dim_b = h->dim_b;
+        p.bmax = h->nd_bmax;
+        p.n_units8 = W.words + 3;
+    }
+    const vs::IvfOneParams& pf = p;
     for (int b = 0; b < nb; ++b) {
         p.o.q = q_dev + (size_t)b * B * h->dim;
         p.o.out_d = out_d + (size_t)b * B * k;
         p.o.out_i = out_i + (size_t)b * B * k;
         p.probes = W.probes;
         stage_mark(h, 0, s);  // (a set of marks per batch: centroid_search_ms = the coarse launches, fine_search_ms = the scan launches)
-        HIPCHK(vs::launch_ivf_one_coarse(p, (int)plan[1], s));
+        HIPCHK(bytes ? vs::launch_ivf_one_coarse_u8(p, (int)plan[1], s) : vs::launch_ivf_one_coarse(pf, (int)plan[1], s));
         stage_mark(h, 1, s);
         stage_mark(h, 2, s);
         prof_begin(h, 1, s);
-        HIPCHK(vs::launch_ivf_one_scan(p, (int)plan[3], s));
+        HIPCHK(bytes ? vs::launch_ivf_one_scan_u8(p, (int)plan[3], s) : vs::launch_ivf_one_scan(pf, (int)plan[3], s));
         prof_end(h, 1, s);
         stage_mark(h, 3, s);
     }
@@ -1569,11 +1624,18 @@ int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int 
     const int kcap = pick_kcap(k);
     if (!kcap) return refuse_general_ivf(h, "k > 16");
     // a short call: two launches per batch, unless the index was created under VSEARCH_IVF_ONE=0.  An index
-    // with a byte copy of its rows takes the route only when no query can run on bytes (vs_set_precision(h, 1)).  The
-    // route has scratch of its own: an index that only ever serves short calls allocates none of the group route's.
+    // with a byte copy of its rows takes the fp32 route when no query can run on bytes (vs_set_precision(h, 1)) and the
+    // byte route otherwise, unless it was created under VSEARCH_IVF_ONE_U8=0.  The routes share scratch of
+    // their own: an index that only ever serves short calls allocates none of the group route's.
     int64_t one_plan[4] = {0, 0, 0, 0};
-    if (h->ivf_one && nb >= 1 && B >= 1 && nprobe >= 1 && nprobe <= std::min(kMaxNprobe, h->nlist) && (!h->d_nd_u8 || h->precision == 1))
-        ivf_one_route(h->n_rows, h->nlist, h->num_cus, nb, B, k, nprobe, one_plan);
+    if (h->ivf_one && nb >= 1 && B >= 1 && nprobe >= 1 && nprobe <= std::min(kMaxNprobe, h->nlist)) {
+        if (!h->d_nd_u8 || h->precision == 1)
+            ivf_one_route(h->n_rows, h->nlist, h->num_cus, nb, B, k, nprobe, one_plan);
+        else if (h->ivf_one_u8 == 2 && ivf_one_route(h->n_rows, h->nlist, h->num_cus, nb, B, k, nprobe, one_plan))
+            one_plan[0] = 2, one_plan[2] = vs::kIvfOneU8UnitRows;
+        else if (h->ivf_one_u8 == 1)
+            ivf_one_route_u8(h->n_rows, h->dim, h->nlist, h->num_cus, nb, B, k, nprobe, one_plan);
+    }
     if (one_plan[0]) return ivf_one_nd_dev(h, one_plan, q_dev, nb, B, k, nprobe, out_d, out_i, s);
     int rc = ensure_ivf_nd(h);
     if (rc) return rc;
@@ -2353,6 +2415,23 @@ int vs_ivf_one_stats(vs_index* h, int64_t* out, int reset) {
     return VS_OK;
 }
 
+int vs_ivf_one_u8_stats(vs_index* h, int64_t* out, int reset) {
+    if (!h || h->kind != 1 || !h->general || !h->d_nd_u8 || !out) {
+        set_error("vs_ivf_one_u8_stats: a general IVF index that keeps a byte copy of its rows and an output of three words");
+        return VS_ERR_INVALID;
+    }
+    int rc = set_device(h);
+    if (rc) return rc;
+    unsigned long long v[3] = {0, 0, 0};
+    HIPCHK(hipDeviceSynchronize());
+    if (h->ivfone.ready) {  // (zero before the index's first short call)
+        HIPCHK(hipMemcpy(v, h->ivfone.counters + 2, sizeof(v), hipMemcpyDeviceToHost));
+        if (reset) HIPCHK(hipMemset(h->ivfone.counters + 2, 0, sizeof(v)));
+    }
+    for (int i = 0; i < 3; ++i) out[i] = (int64_t)v[i];
+    return VS_OK;
+}
+
 int vs_prof_read(vs_index* h, int which, double* total_ms, int64_t* launches) {
     if (!h || which < 0 || which > 1) return VS_ERR_INVALID;
     int rc = set_device(h);
@@ -2784,6 +2863,7 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
     h->dim_p = h->general ? vs::nd_dim_p(dim) : dim;
     // comparison toggle (VSEARCH_IVF_ONE=0, read here): short calls on this general index keep the group route
     if (const char* e = getenv("VSEARCH_IVF_ONE")) h->ivf_one = atoi(e) != 0;
+    if (const char* e = getenv("VSEARCH_IVF_ONE_U8")) h->ivf_one_u8 = atoi(e) == 2 ? 2 : atoi(e) != 0;
     h->metric = VS_METRIC_L2;
     h->n_total = n_rows;
     h->nlist = nlist;
@@ -3705,6 +3785,29 @@ int vs_ivf_one_plan(int64_t n_rows, int dim, int nlist, int num_cus, int n_batch
         return VS_ERR_UNSUPPORTED;
     }
     ivf_one_route(n_rows, nlist, num_cus, n_batches, B, k, nprobe, out);
+    return VS_OK;
+}
+
+// ivf_one_route_u8 for the ABI (host only), vs_ivf_one_plan's checks in its order.  The toggles, the precision and
+// whether the byte copy was kept are not its business.
+int vs_ivf_one_plan_u8(int64_t n_rows, int dim, int nlist, int num_cus, int n_batches, int B, int k, int nprobe, int64_t* out) {
+    if (!out || n_rows < 1 || nlist < 1 || num_cus < 1 || n_batches < 1 || B < 1 || B > vs::kMaxBatch || k < 1 || nprobe < 1) {
+        set_error("vs_ivf_one_plan_u8: bad arguments (out != NULL, n_rows, nlist, num_cus, n_batches, k, nprobe >= 1, 1 <= B <= 32)");
+        return VS_ERR_INVALID;
+    }
+    if (dim < 1) {
+        set_error("vs_ivf_one_plan_u8: dim must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (dim > vs::kNdMaxDim) {
+        set_error("vs_ivf_one_plan_u8: dim > 2048 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (k > vs::kIvfWideKMax) {
+        set_error("vs_ivf_one_plan_u8: k > 128 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    ivf_one_route_u8(n_rows, dim, nlist, num_cus, n_batches, B, k, nprobe, out);
     return VS_OK;
 }
 

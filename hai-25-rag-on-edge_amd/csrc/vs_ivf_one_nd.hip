@@ -6,6 +6,10 @@
 //                     scan_nd_kernel's chain into a [16][ld] scratch; release fence, ticket; the workgroup that arrives
 //                     last picks every query's nprobe smallest by (score, list id) (pick_probes_kernel's method), builds the per-list column masks and
 //                     the unit table, counts the candidates, and resets the ticket.
+//   ivf_one_coarse_kernel<IP, IvfOneU8Params> : its byte-index mode, for an index that keeps a byte copy of its rows (DESIGN
+//                     4.6e): the same scores and probes; the last workgroup also applies the exactness rule to every
+//                     query and cuts the probed lists into byte units and fp32 units for ivf_one_scan_u8_kernel
+//                     (vs_ivf_one_nd_i8.hip).  The fp32 instantiations compile to the code they had without it.
 //   ivf_one_scan_kernel<KCAP, IP>  : a fixed grid loops over the unit table.  A unit is at most kIvfOneUnitRows rows of
 //                     one probed list, counted in 64-row blocks from the list's first row as ivf_scan_nd_kernel counts
 //                     them; the 8 waves take its blocks round-robin, four 16-row tiles against the 16 query columns,
@@ -22,89 +26,74 @@
 // query, and a row's distance is ivf_scan_nd_kernel's -- the same accumulation chain (the (c, i) order of DESIGN 4.4c,
 // the half step when dim_p / 16 is odd), then fma(-2, dot, qn + norm) or -dot.  The probes are pick_probes_kernel's, so
 // ids, distance bits, empty slots and the candidate count of a call are those of ivf_group_nd_dev's launches.
-#include "vs_kernels.h"
-#include "vs_dev.h"
-#include "vs_one_tail.h"
-#include "vs_one_nd_queries.h"
+#include "vs_ivf_one_scan.h"
 
 namespace vs {
 
 namespace {
 
-constexpr int kIvfOneTiles = 4;                                // 16-row tiles per wave block
-constexpr int kIvfOneBlockRows = kIvfOneTiles * kTileRows;     // 64 <= kScanPadRows: a block never reads past the spare rows
-static_assert(kIvfOneBlockRows <= kScanPadRows, "row blocks are loaded unclamped");
-static_assert(kIvfOneUnitRows % kIvfOneBlockRows == 0, "a unit is whole blocks, counted from the list's first row");
-constexpr int kIvfOneQ = 16;                                   // query columns
 constexpr int kIvfOnePickVPL = 16;                             // scores per lane of the selection
 static_assert(64 * kIvfOnePickVPL == kIvfOneMaxNlist, "the selection keeps a query's scores in one wave's registers");
-// (the scan's LDS is OneNdLds of vs_one_tail.h over rows of 4 dim_p bytes)
-// coarse: query fragments, later the last arriver's winners [8 waves][kIvfMaxProbe]; behind them norms [32] | flag [32] |
-// masks [kIvfOneMaxNlist] | prefix scan [kScanThreads]
-constexpr int kIvfOneCoarseScratch = (32 + 32 + kIvfOneMaxNlist + kScanThreads) * 4;
-constexpr int ivf_one_coarse_region(int dim_p) {
-    const int frag = dim_p * 64, sel = kScanWaves * kIvfMaxProbe * 4;
-    return frag > sel ? frag : sel;
-}
-constexpr int kIvfOneCoarseMaxLds = ivf_one_coarse_region(kNdMaxDim) + kIvfOneCoarseScratch;
-constexpr int kIvfOneMaxLds = kIvfOneCoarseMaxLds > one_nd_lds_bytes(4 * kNdMaxDim, 16) ? kIvfOneCoarseMaxLds : one_nd_lds_bytes(4 * kNdMaxDim, 16);
-static_assert(kIvfOneMaxLds <= 160 * 1024, "LDS of a CU");
 
-// The dot products of one 64-row block (four 16-row tiles at sb) with the 16 staged query columns: scan_nd_kernel's chain,
-// the B fragments from LDS.  Row loads run one K step ahead of the MFMAs.
-__device__ __forceinline__ void ivf_one_block_dots(const char* sb, unsigned voff, unsigned tile_bytes, int C, const f32x4* qfrag, int lane,
-                                                   f32x4 (&acc)[kIvfOneTiles]) {
-    constexpr int T = kIvfOneTiles;
-    const int n_pairs = C >> 1;  // full 32-float steps
-#pragma unroll
-    for (int t = 0; t < T; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    f32x4 a[T][2];
-    auto load_pair = [&](int s, f32x4 (&av)[T][2]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            av[t][0] = *(reinterpret_cast<const f32x4*>(sb + (t * tile_bytes + 128u * s) + voff));
-            av[t][1] = *(reinterpret_cast<const f32x4*>(sb + (t * tile_bytes + 128u * s + 64u) + voff));
-        }
-    };
-    auto mfma_half = [&](const f32x4 (&av)[T][2], const f32x4 bv, int u) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int t = 0; t < T; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t][u][i], bv[i], acc[t], 0, 0, 0);
-    };
-    if (n_pairs > 0) load_pair(0, a);
-    for (int s = 0; s < n_pairs; ++s) {
-        f32x4 an[T][2];
-        const bool more = s + 1 < n_pairs;
-        if (more) load_pair(s + 1, an);
-        const f32x4 b0 = qfrag[(2 * s) * 64 + lane], b1 = qfrag[(2 * s + 1) * 64 + lane];
-        mfma_half(a, b0, 0);
-        mfma_half(a, b1, 1);
-        if (more) {
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                a[t][0] = an[t][0];
-                a[t][1] = an[t][1];
-            }
-        }
+// The unit table of the byte-index mode, by the last workgroup: a probed list with column mask m gives byte units
+// (unit_rows8 rows, mask m & V) and fp32 units (unit_rows rows, mask m & ~V), each kind only when its mask is non-zero;
+// all byte units first.  Thread t owns lists [lo, hi).  Two prefix scans side by side: lds_scan8 [kScanThreads] overlays
+// the winners, which every wave is done with (the caller's barrier).
+__device__ __forceinline__ void ivf_one_unit_table_u8(const IvfOneU8Params& p, const int V, const int lo, const int hi, const int* lds_mask,
+                                                      int* lds_scan, int* lds_scan8) {
+    const int tid = threadIdx.x;
+    const int U = p.unit_rows, U8R = p.unit_rows8;
+    int nu = 0, nu8 = 0;
+    for (int c = lo; c < hi; ++c) {
+        const int m = lds_mask[c], rows = p.offsets[c + 1] - p.offsets[c];
+        if (m & V) nu8 += (rows + U8R - 1) / U8R;
+        if (m & ~V) nu += (rows + U - 1) / U;
     }
-    if (C & 1) {  // the last 16 floats of a row whose dim_p is an odd number of segments
-#pragma unroll
-        for (int t = 0; t < T; ++t) a[t][0] = *(reinterpret_cast<const f32x4*>(sb + (t * tile_bytes + 128u * n_pairs) + voff));
-        mfma_half(a, qfrag[(2 * n_pairs) * 64 + lane], 0);
+    lds_scan[tid] = nu;
+    lds_scan8[tid] = nu8;
+    __syncthreads();
+    for (int o = 1; o < kScanThreads; o <<= 1) {  // inclusive scans
+        const int a = tid >= o ? lds_scan[tid - o] : 0;
+        const int a8 = tid >= o ? lds_scan8[tid - o] : 0;
+        __syncthreads();
+        lds_scan[tid] += a;
+        lds_scan8[tid] += a8;
+        __syncthreads();
+    }
+    const int total8 = lds_scan8[kScanThreads - 1];
+    int unit8 = lds_scan8[tid] - nu8;
+    int unit = total8 + lds_scan[tid] - nu;
+    for (int c = lo; c < hi; ++c) {
+        const int m = lds_mask[c];
+        if (!m) continue;
+        const int row_lo = p.offsets[c], row_end = p.offsets[c + 1];
+        if (m & V)
+            for (int r0 = row_lo; r0 < row_end; r0 += U8R, ++unit8)
+                if (unit8 < p.units_cap) reinterpret_cast<i32x4*>(p.units)[unit8] = (i32x4){r0, min(r0 + U8R, row_end), m & V, c};
+        if (m & ~V)
+            for (int r0 = row_lo; r0 < row_end; r0 += U, ++unit)
+                if (unit < p.units_cap) reinterpret_cast<i32x4*>(p.units)[unit] = (i32x4){r0, min(r0 + U, row_end), m & ~V, c};
+    }
+    if (tid == kScanThreads - 1) {
+        const int n8 = min(total8, p.units_cap), n = min(total8 + lds_scan[tid], p.units_cap);
+        p.n_units8[0] = n8;
+        p.n_units[0] = n;
+        p.counters[0] += 1ull;  // (one writer at a time: the launches of an index are stream ordered)
+        if (n8 > 0 && n > n8) p.counters[1] += 1ull;
+        if ((unsigned long long)n > p.counters[2]) p.counters[2] = (unsigned long long)n;
     }
 }
-
-// position in the reordered rows -> the caller's id
-struct IvfOneIdMap {
-    const int32_t* map;  // null: identity
-    __device__ __forceinline__ int operator()(int id) const { return map ? map[id] : id; }
-};
 
 }  // namespace
 
-template <bool IP>
-__global__ __launch_bounds__(kScanThreads, 1) void ivf_one_coarse_kernel(const IvfOneParams p) {
+// The coarse launch.  U8 (P is IvfOneU8Params): the byte-index mode -- the last workgroup also reaches the exactness
+// rule's verdict per query (ivf_nd_prep_i8's, in integers: the 16-bit mask V) from the staged queries, counts a pair on
+// the byte rows or on the fp32 rows by its query's bit in V, and cuts every probed list that holds rows into byte units
+// (column mask m & V) and fp32 units (m & ~V), the byte units first.  Without U8 none of that is compiled.
+
+template <bool IP, class P = IvfOneParams>
+__global__ __launch_bounds__(kScanThreads, 1) void ivf_one_coarse_kernel(const P p) {
+    constexpr bool U8 = std::is_same_v<P, IvfOneU8Params>;
     constexpr int T = kIvfOneTiles;
     constexpr int NL = kIvfOneMaxNlist;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -152,6 +141,9 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_one_coarse_kernel(const I
     }
 
     // ---- the workgroup that arrives last selects.  Nobody waits for anybody: every other workgroup is done here.
+    if constexpr (U8) {
+        if (tid < 17) lds_scan[tid] = 0;  // (the last arriver's per-query sums, below)
+    }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     __syncthreads();
     if (tid == 0) lds_flag[0] = (__hip_atomic_fetch_add(p.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1) ? 1 : 0;
@@ -161,7 +153,42 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_one_coarse_kernel(const I
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 
     for (int c = tid; c < NL; c += kScanThreads) lds_mask[c] = 0;
+    if constexpr (U8) {
+        // ivf_nd_prep_i8's verdict per query, in integers (n2 <= 2048 * 255^2, 0 <= bmax < 2^24), from the query fragments
+        // in LDS before the winners overlay them: floats in MFMA order, and the zeros past dim and past B are bytes.
+        // Fragment e belongs to query e & 15 = tid & 15 in every round of a thread; lanes r, r + 16, r + 32, r + 48 of a wave
+        // add up by shuffle, the 8 waves in LDS (lds_scan [0, 16): ||q||^2, [16]: the queries with a value that is no
+        // byte; cleared ahead of the ticket's barrier, used again by the unit table behind the next barrier but one).
+        // No global memory is read for it: a dependent round trip in the one workgroup everybody waits for is a
+        // microsecond or two of every call.
+        int n2 = 0, bad = 0;
+        for (int e = tid; e < C * 64; e += kScanThreads) {
+            const f32x4 v = qfrag[e];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                int xi;
+                if (byte_value(v[i], xi))
+                    n2 += xi * xi;
+                else
+                    bad = 1;
+            }
+        }
+        n2 += __shfl_xor(n2, 16);
+        bad |= __shfl_xor(bad, 16);
+        n2 += __shfl_xor(n2, 32);
+        bad |= __shfl_xor(bad, 32);
+        if (lane < 16) {
+            atomicAdd(&lds_scan[lane], n2);
+            if (bad) atomicOr(&lds_scan[16], 1 << lane);
+        }
+    }
     __syncthreads();
+    int V = 0;  // byte-index mode: bit q set when query q runs on the byte rows
+    if constexpr (U8) {
+        const int not_bytes = lds_scan[16];
+        for (int qq = 0; qq < B; ++qq)
+            if (!((not_bytes >> qq) & 1) && lds_scan[qq] <= kNd8NormLimit - p.bmax) V |= 1 << qq;
+    }
 
     // per query, one wave: the nprobe smallest by (score, list id); a NaN never competes.  pick_probes_kernel's method:
     // every lane sorts its 16 strided scores once in registers (bitonic network, static indices); a round is then one
@@ -173,6 +200,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_one_coarse_kernel(const I
     //   at B = 16, nprobe 32, 96-d, and that shape was slower than the group route, 325 against 293 us)
     int* won = reinterpret_cast<int*>(smem) + wave * kIvfMaxProbe;  // [8 waves][256]
     unsigned long long rows_sum = 0, pairs_sum = 0;
+    unsigned long long pairs8_sum = 0;  // byte-index mode: the pairs of the queries in V (pairs_sum: the others')
     for (int qq = wave; qq < B; qq += kScanWaves) {
         float v[kIvfOnePickVPL];
         int id[kIvfOnePickVPL];
@@ -227,7 +255,10 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_one_coarse_kernel(const I
             if (rows > 0) {
                 atomicOr(&lds_mask[c], 1 << qq);
                 rows_sum += (unsigned long long)rows;
-                ++pairs_sum;
+                if (U8 && ((V >> qq) & 1))
+                    ++pairs8_sum;
+                else
+                    ++pairs_sum;
             }
         }
         __builtin_amdgcn_wave_barrier();  // (won is reused by the wave's next query)
@@ -236,9 +267,13 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_one_coarse_kernel(const I
     for (int o = 32; o > 0; o >>= 1) {
         rows_sum += __shfl_xor(rows_sum, o);
         pairs_sum += __shfl_xor(pairs_sum, o);
+        if constexpr (U8) pairs8_sum += __shfl_xor(pairs8_sum, o);
     }
     if (lane == 0 && rows_sum && p.cand_count) atomicAdd(p.cand_count, rows_sum);
     if (lane == 0 && pairs_sum && p.pair_count) atomicAdd(p.pair_count, pairs_sum);
+    if constexpr (U8) {
+        if (lane == 0 && pairs8_sum && p.pair_count8) atomicAdd(p.pair_count8, pairs8_sum);
+    }
     __syncthreads();
 
     // the unit table: every probed list that holds rows, cut into units of unit_rows rows.  Thread t owns lists
@@ -246,6 +281,10 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_one_coarse_kernel(const I
     const int U = p.unit_rows;
     const int per = (nlist + kScanThreads - 1) / kScanThreads;
     const int lo = min(tid * per, nlist), hi = min(lo + per, nlist);
+    if constexpr (U8) {
+        ivf_one_unit_table_u8(p, V, lo, hi, lds_mask, lds_scan, reinterpret_cast<int*>(smem));
+        return;
+    }
     int nu = 0;
     for (int c = lo; c < hi; ++c)
         if (lds_mask[c]) nu += (p.offsets[c + 1] - p.offsets[c] + U - 1) / U;
@@ -307,54 +346,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_one_scan_kernel(const Ivf
     const unsigned tile_bytes = 64u * (unsigned)dim_p;         // 16 rows
     int c_n = 0;  // blocks this wave has done (wave-uniform): the checkpoints of the shared bound
 
-#pragma clang loop unroll(disable)
-    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
-        const i32x4 u = reinterpret_cast<const i32x4*>(p.units)[unit];
-        const int row_lo = u[0], row_end = u[1];  // (a unit that is not its list's last ends on a block boundary)
-        const int last_row = row_end - 1;
-        const bool mine = live && ((u[2] >> r) & 1);
-        const int blocks_total = (row_end - row_lo + kIvfOneBlockRows - 1) / kIvfOneBlockRows;
-#pragma clang loop unroll(disable)
-        for (int wb = wave; wb < blocks_total; wb += kScanWaves) {
-            const int row0 = row_lo + wb * kIvfOneBlockRows;
-            const char* sb = reinterpret_cast<const char*>(p.vecs + (int64_t)row0 * dim_p);
-            f32x4 acc[T];
-            ivf_one_block_dots(sb, voff, tile_bytes, C, qfrag, lane, acc);
-            const bool ragged = row0 + kIvfOneBlockRows - 1 > last_row;  // wave-uniform
-            bool touched = false;
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                const int rbase = row0 + 16 * t + 4 * g;
-                float d[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if constexpr (IP)
-                        d[j] = -acc[t][j];  // (an exactly zero product is +0 out of the chain: -0.0)
-                    else
-                        d[j] = fmaf(-2.0f, acc[t][j], qn + p.vnorm[rbase + j]);  // (the norms have 64 spare entries)
-                    if (ragged && rbase + j > last_row) d[j] = VS_INF;  // (under IP a spare row's -0.0 must never compete)
-                }
-                const float dmin = fminf(fminf(d[0], d[1]), fminf(d[2], d[3]));
-                if (dmin < (mine ? tau : -VS_INF)) {  // (a column outside the mask: its bound is -inf)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (d[j] < tau) {
-                            list_insert<KCAP>(ld[0], li[0], d[j], rbase + j);
-                            tau = fminf(tau, ld[0][KCAP - 1]);
-                        }
-                    touched = true;
-                }
-            }
-            if (touched) L.tail.lmin[r * 33 + 4 * wave + g] = ld[0][0];  // this lane's best so far, for the shared bound
-            ++c_n;
-            if (c_n == 1 || c_n == 2 || c_n == 4 || c_n == 8 || c_n == 16) {  // wave-uniform checkpoints
-                // the k-th smallest of the column's lane minima: k distinct rows of the column's probed lists are at
-                // least that close (vs_one_tail.h); whatever the other waves have published by now, stale only loosens it
-                const float sbound = one_shared_bound(L.tail.lmin, r, g, p.o.k1);
-                if (live && sbound < VS_INF) tau = fminf(tau, next_up(sbound));
-            }
-        }
-    }
+    VS_IVF_ONE_UNITS_F32(blockIdx.x)
 
     // (the query fragments are done with: the merges overlay them)
     one_tail<1, KCAP, one_nd_region(64, KCAP)>(p.o, L.tail, ld, li, IvfOneIdMap{p.id_map});  // (64: the shortest row, dim_p = 16)
@@ -367,7 +359,7 @@ int ivf_one_coarse_grid(int nlist, int num_cus) {
 
 int ivf_one_scan_grid(int num_cus) { return std::max(1, std::min(num_cus, kSlotStride)); }
 
-static bool ivf_one_params_ok(const IvfOneParams& p) {
+bool ivf_one_params_ok(const IvfOneParams& p) {
     return p.dim >= 1 && p.dim <= kNdMaxDim && p.dim_p == nd_dim_p(p.dim) && p.nlist >= 1 && p.nlist <= kIvfOneMaxNlist && p.o.nq_valid >= 1 &&
            p.o.nq_valid <= kIvfOneQ && p.o.k1 >= 1 && p.o.k1 <= 16 && p.nprobe >= 1 && p.nprobe <= kIvfMaxProbe && p.nprobe <= p.nlist &&
            p.unit_rows >= kIvfOneBlockRows && p.unit_rows % kIvfOneBlockRows == 0 && p.units_cap >= 1 && p.ld >= p.nlist &&
@@ -378,6 +370,15 @@ hipError_t launch_ivf_one_coarse(const IvfOneParams& p, int grid, hipStream_t s)
     if (!ivf_one_params_ok(p) || grid < 1 || grid > kSlotStride) return hipErrorInvalidValue;
     const int lds = ivf_one_coarse_region(p.dim_p) + kIvfOneCoarseScratch;
     return p.metric ? launch_big_lds<ivf_one_coarse_kernel<true>, kIvfOneMaxLds>(p, grid, lds, s) : launch_big_lds<ivf_one_coarse_kernel<false>, kIvfOneMaxLds>(p, grid, lds, s);
+}
+
+hipError_t launch_ivf_one_coarse_u8(const IvfOneU8Params& p, int grid, hipStream_t s) {
+    if (!ivf_one_params_ok(p) || grid < 1 || grid > kSlotStride || p.dim_b != nd_dim_b(p.dim) || p.bmax < 0 || p.bmax >= kNd8NormLimit ||
+        p.unit_rows8 < kIvfOneBlockRows || p.unit_rows8 % kIvfOneBlockRows || !p.n_units8)
+        return hipErrorInvalidValue;
+    const int lds = ivf_one_coarse_region(p.dim_p) + kIvfOneCoarseScratch;
+    return p.metric ? launch_big_lds<ivf_one_coarse_kernel<true, IvfOneU8Params>, kIvfOneMaxLds>(p, grid, lds, s)
+                      : launch_big_lds<ivf_one_coarse_kernel<false, IvfOneU8Params>, kIvfOneMaxLds>(p, grid, lds, s);
 }
 
 hipError_t launch_ivf_one_scan(const IvfOneParams& p, int grid, hipStream_t s) {

@@ -691,6 +691,34 @@ int ivf_one_scan_grid(int num_cus);
 hipError_t launch_ivf_one_coarse(const IvfOneParams& p, int grid, hipStream_t s);
 hipError_t launch_ivf_one_scan(const IvfOneParams& p, int grid, hipStream_t s);
 
+// ---- the same two launches on a general IVF index that keeps a byte copy of its rows (vs_ivf_create_nd_u8).
+// The coarse launch (vs_ivf_one_nd.hip, its byte-index mode) scores and selects as above; its last workgroup also reaches
+// launch_ivf_nd_i8_prep's verdict for every query of the batch (every value an integer in [0, 255] and ||q||^2 + bmax <=
+// 2^24, in integers) and cuts every probed list that holds rows into BYTE units (unit_rows8 rows, column mask = the
+// probing queries that qualify) and FP32 units (s.unit_rows rows, column mask = the others), each kind only when its
+// mask is non-zero: units [0, n_units8) are byte units, [n_units8, n_units) fp32 units.  The scan launch
+// (vs_ivf_one_nd_i8.hip) scores the byte units with v_mfma_i32_16x16x64_i8 -- (float)(qterm + rterm - 2 q'.b'), or
+// -(float)(q.b) under inner product: the fp32 scan's bits for such a query -- and then the fp32 units as
+// launch_ivf_one_scan does, into the same lane lists; one tail.
+#ifndef VS_IVF_ONE_U8_UNIT_ROWS  // (a build with EXTRA=-DVS_IVF_ONE_U8_UNIT_ROWS=2048 is the other side of the unit-size measurement)
+#define VS_IVF_ONE_U8_UNIT_ROWS 512
+#endif
+constexpr int kIvfOneU8UnitRows = VS_IVF_ONE_U8_UNIT_ROWS;  // rows per byte unit (measured against 2048: DESIGN 4.6e)
+struct IvfOneU8Params : IvfOneParams {  // counters = [3] batches answered | of those with both kinds of unit | the most units of
+                                        // any one; pair_count = the pairs of the queries that do not qualify (fp32 rows)
+    const int8_t* vecs_u8;    // [n_rows + kScanPadRows][dim_b] bytes (x - 128), zero padded
+    const int32_t* rterm;     // [n_rows + 64] sum (b - 128)^2 (squared L2)
+    const int32_t* rsum;      // [n_rows + 64] sum (b - 128) (inner product; launch_ivf_nd_i8_rowsum)
+    int dim_b;                // nd_dim_b(dim)
+    int32_t bmax;             // max over the rows of ||b||^2, < 2^24
+    int unit_rows8;           // a multiple of 64
+    int32_t* n_units8;        // scratch [1]
+    unsigned long long* pair_count8;  // optional: += pairs of the qualifying queries whose list holds rows
+};
+hipError_t launch_ivf_one_coarse_u8(const IvfOneU8Params& p, int grid, hipStream_t s);
+hipError_t launch_ivf_one_scan_u8(const IvfOneU8Params& p, int grid, hipStream_t s);
+bool ivf_one_params_ok(const IvfOneParams& p);
+
 // ---- the same on the byte copy of a general IVF index made from uint8 rows (vs_ivf_nd_i8.hip).
 // launch_ivf_nd_i8_prep writes the group's queries as int8 (x - 128), zero padded, row-major [group_q][dim_b], qterm =
 // sum (q - 128)^2 and valid[query]: 1 when the query runs on bytes -- every value an integer in [0, 255] and ||q||^2 +

@@ -602,7 +602,12 @@ VS_API int vs_ivf_load(const char* index_dir, int device, int rank, int world, v
  * not depend on the route: ids, distance bits, empty slots and *total_candidates are those of the
  * launch group's ordinary route.  VSEARCH_IVF_ONE=0, read when the index is created, keeps that
  * route for short calls on that index: the comparison toggle.  An index with a byte copy of its
- * rows (vs_ivf_create_nd_u8) takes the two launches only under vs_set_precision(h, 1).
+ * rows (vs_ivf_create_nd_u8) takes two launches too: under vs_set_precision(h, 1) the ones above,
+ * on the fp32 rows; at precision 0 or 2 the byte route (vs_ivf_one_plan_u8 below
+ * states the rule) -- the same coarse launch, which also decides per query whether it runs on
+ * bytes, and ONE scan launch that reads the byte rows with int8 MFMA for the queries that qualify
+ * and the fp32 rows for every other query of the same batch.  VSEARCH_IVF_ONE_U8=0, read when
+ * the index is created, keeps the group route for such calls on that index.
  * The route's scratch (scores, unit table, tickets, counters) exists once per index, like the
  * group route's: calls on ONE index must be ordered by their streams.  Short calls on one index
  * from two streams at once corrupt each other silently; concurrent front ends need an index each
@@ -635,6 +640,22 @@ VS_API int vs_ivf_create(const float* vectors_reordered, int64_t n_rows, int dim
  * max ||b||^2 <= 2^24, both checked on the device in integers; every other query of the same
  * launch group is scanned on the fp32 rows.  No host synchronisation, nothing is rerun,
  * everything stays on the caller's stream.
+ *
+ * Short calls (fewer than 4 batches of at most 16 queries, k <= 16; vs_ivf_one_plan_u8) at
+ * precision 0 or 2 take TWO launches per batch on the caller's stream, under either metric: the
+ * coarse launch of vs_ivf_create's short calls, whose last workgroup also applies the rule above
+ * to every query of the batch, and one scan launch that reads the byte rows for the queries that
+ * qualify and the fp32 rows for the others.  Results, *total_candidates, the timing fields and
+ * vs_ivf_nd_u8_stats are those of the group route; vs_ivf_one_u8_stats counts the route's
+ * batches, vs_ivf_one_stats keeps counting the fp32 route only (precision 1).  The first
+ * inner-product call of an index builds the rows' byte sums with one more launch, as on the
+ * group route.  An index whose byte copy was not kept behaves as vs_ivf_create's.
+ * VSEARCH_IVF_ONE_U8=0 at creation keeps the group route for short calls (the comparison
+ * toggle); VSEARCH_IVF_ONE=0 turns both short routes off.  (One more value exists for the
+ * benchmark only: VSEARCH_IVF_ONE_U8=2 sends every shape of vs_ivf_one_plan's rule to the byte
+ * route, the shapes vs_ivf_one_plan_u8 takes out included, so that they can be timed on it; an
+ * index created under it does not decide through vs_ivf_one_plan_u8.)  The scratch is the short
+ * calls' own, once per index: calls on ONE index must be ordered by their streams.
  *
  * Accepted and refused calls: as vs_ivf_create's general index, except vs_set_precision: 0
  * (default) and 2 use the byte rows for the queries that qualify, 1 scans every pair on the fp32
@@ -954,6 +975,33 @@ VS_API int vs_ivf_one_plan(int64_t n_rows, int dim, int nlist, int num_cus, int 
  * out[1] = the most units any one of those batches had (written by the coarse launch).  Always counted; zeros before the
  * first short call.  Synchronises the device; reset != 0 clears the counters.  VS_ERR_INVALID on any other kind of index. */
 VS_API int vs_ivf_one_stats(vs_index* h, int64_t* out /* [2] */, int reset);
+/* The byte route of short calls on a general IVF index that keeps a byte copy of its rows (vs_ivf_create_nd_u8 at
+ * precision 0 or 2; host only, no GPU needed): the rule for the same launch group as vs_ivf_one_plan, and the launch
+ * code takes its decision and geometry through the same function.
+ *   out[0] = 0: the group route; 2: the two-launch byte route.  The default rule is vs_ivf_one_plan's own conditions:
+ *            n_batches < 4, B <= 16, k <= 16, min(nprobe, nlist) <= 256, nlist <= 1024, n_rows < 2^31 - 128.  A shape
+ *            leaves the rule only because it MEASURED slower than the route it would replace.  Two have, at 1 M rows,
+ *            nlist 1024, k = 10 (byte route | group route | fp32 two launches, us per call): dim 96, B = 16, nprobe 128:
+ *            345 | 330 | 369; dim 128, B = 16, nprobe 256: 446 | 441 | 488.  Exactly these two shapes (nprobe after the
+ *            clamp to nlist) keep the group route; every measured neighbour was faster than both alternatives.  One shape
+ *            stays in although the fp32 two launches were 1.6 % faster, because the group route is what it would get
+ *            instead: dim 96, B = 1, nprobe 8: 87.7 | 157.0 | 86.2 (profiles/ivf_one_u8_bench.txt)
+ *   out[1] = workgroups of the coarse launch
+ *   out[2] = rows in one BYTE unit of the scan (a multiple of 64 counted from the list's first row); the fp32 units of
+ *            the same batch have vs_ivf_one_plan's out[2] rows
+ *   out[3] = workgroups of the scan launch
+ * out[1..3] are 0 with out[0] = 0; out[1] and out[3] equal vs_ivf_one_plan's wherever both say "short".  VSEARCH_IVF_ONE=0,
+ * VSEARCH_IVF_ONE_U8=0 (and its benchmark-only value 2, see vs_ivf_create_nd_u8), the precision and whether the byte
+ * copy was kept are not its business.
+ * Checks, codes and their order: vs_ivf_one_plan's. */
+VS_API int vs_ivf_one_plan_u8(int64_t n_rows, int dim, int nlist, int num_cus, int n_batches, int B, int k, int nprobe,
+                              int64_t* out /* [4] */);
+/* What the byte route did on such an index since the last reset: out[0] = batches answered by it, out[1] = of those,
+ * batches that held both byte units and fp32 units (queries of both kinds that probe lists with rows), out[2] = the most
+ * units, both kinds together, any one of those batches had (all three written by the coarse launch).  Always counted;
+ * zeros before the first such call.  Synchronises the device; reset != 0 clears the counters.  VS_ERR_INVALID for null
+ * pointers and on any index that is not a general IVF index with a byte copy of its rows. */
+VS_API int vs_ivf_one_u8_stats(vs_index* h, int64_t* out /* [3] */, int reset);
 /* The wide-k calls (17 <= k <= 128) on a general IVF index since the last reset: out[0] = candidates ranked from
  * candidate lists, out[1] = the most candidates of one query, out[2] = queries ranked by the exact fallback (more than
  * 8192 candidates: every row of their probed lists scored again).  Always counted; zeros before the first wide-k call.

@@ -18,7 +18,22 @@ exact one is reported per nprobe over 256 queries.
 
     python scripts/ivf_one_bench.py [--dims 96,128,384,768] [--rows 1000000] [--nlist 1024] [--reps 5] [--parent-root DIR]
                                     [--out profiles/ivf_one_bench.txt]
+    python scripts/ivf_one_bench.py --u8 [--u8-unit-root DIR] [--batches 1,8,16] [--out profiles/ivf_one_u8_bench.txt]
     rocprofv3 --kernel-trace --stats -d DIR --output-format csv -- python scripts/ivf_one_bench.py --one DIM,B,NPROBE
+
+--u8: the byte route (ivf_one_coarse_kernel in its byte-index mode + ivf_one_scan_u8_kernel) on the same index
+built from the same rows as uint8 (IVFIndex.from_u8; synth_sift rows are byte valued), against its two alternatives:
+
+    u8      the byte route at every shape of vs_ivf_one_plan's rule (VSEARCH_IVF_ONE_U8=2: the shapes vs_ivf_one_plan_u8 takes
+            out included -- the column `rule` says what vs_ivf_one_plan_u8 makes of the shape)
+    u8f32   the SAME index in the same process under set_precision(1): the fp32 two-launch route
+    u8off   the same index created under VSEARCH_IVF_ONE_U8=0 in a process of its own: the group route on the byte rows
+    u8unit  with --u8-unit-root DIR: the same leg on another build of this tree (EXTRA=-DVS_IVF_ONE_U8_UNIT_ROWS=2048: byte
+            units of 2048 rows), a process of its own
+    parent  with --parent-root: the parent commit's library on the same index (its group route on the byte rows)
+
+and, for B = 1, the probed rows' bytes over the WHOLE call's time: total_candidates x dim_b bytes (dim_p x 4 for u8f32).  (With
+more queries total_candidates counts a list once per query that probes it, not once per read: no such figure is printed.)
 
 One JSON line per (dimension, nprobe, B, leg) with every repeat, min and median; --out writes the same as a table.  --one
 runs 320 calls of one shape in one process: the run to profile for the per-launch split (coarse, scan)."""
@@ -67,6 +82,13 @@ def worker(a):
         ix = pkg.BruteForceIndex(base)
         ix.set_precision(1)
         kk = K + 1
+    elif a.kind == "ivfu8":
+        vr, off, r2o, cents, _ = pkg.ivf_build(base, a.nlist, 4, 1e-4, 42, 0)
+        u8 = vr.astype(np.uint8)
+        assert np.array_equal(u8.astype(np.float32), vr), "--u8 needs byte-valued rows"
+        ix = pkg.IVFIndex.from_u8(u8, cents, off, r2o)
+        kk = K
+        del vr, u8
     else:
         vr, off, r2o, cents, _ = pkg.ivf_build(base, a.nlist, 4, 1e-4, 42, 0)
         ix = pkg.IVFIndex(vectors_reordered=vr, centroids=cents, cluster_offsets=off, reorder_to_original=r2o)
@@ -101,6 +123,22 @@ def worker(a):
                 for t in (oi, od):
                     h.update(t[:B].cpu().numpy().tobytes())
             print(json.dumps({"check": h.hexdigest()[:16]}), flush=True)
+            continue
+        if cmd[0] == "precision":  # (--u8: the same index on the fp32 two-launch route and back)
+            ix.set_precision(int(cmd[1]))
+            print(json.dumps({"precision": int(cmd[1])}), flush=True)
+            continue
+        if cmd[0] == "route":  # (--u8) what the counters say the last calls took, cleared; candidate rows of one call of the shape
+            B, nprobe = int(cmd[1]), int(cmd[2])
+            one = list(ix.one_stats(reset=True))
+            one8 = list(ix.one_u8_stats(reset=True)) if hasattr(ix, "one_u8_stats") else None
+            nd = list(ix.nd_u8_stats(reset=True))
+            rows = ix.searchBatch(qd[:B].cpu().numpy(), B, K, nprobe)[2]
+            ix.one_stats(reset=True)  # (that call is not one of the measured ones)
+            if one8 is not None:
+                ix.one_u8_stats(reset=True)
+            ix.nd_u8_stats(reset=True)
+            print(json.dumps({"one": one, "one_u8": one8, "nd_u8": nd, "rows": int(rows)}), flush=True)
             continue
         if cmd[0] == "answers":  # the ids of the first 256 queries, one query per call
             nprobe = int(cmd[1])
@@ -161,7 +199,7 @@ def one_shape(a):
 class Worker:
     def __init__(self, a, name, root, dim, kind, env, general):
         e = dict(os.environ)
-        for v in ("VSEARCH_IVF_ONE", "VSEARCH_IVF_ND_FORCE"):
+        for v in ("VSEARCH_IVF_ONE", "VSEARCH_IVF_ONE_U8", "VSEARCH_IVF_ND_FORCE"):
             e.pop(v, None)
         e.update(env)
         self.name, self.kind = name, kind
@@ -189,6 +227,79 @@ class Worker:
         self.p.wait(timeout=120)
 
 
+def main_u8(a):
+    """--u8: see the module's text"""
+    table = [f"# python3 scripts/ivf_one_bench.py --u8 --dims {a.dims} --rows {a.rows} --nlist {a.nlist} --reps {a.reps} --nprobes {a.nprobes} --data {a.data}"
+             + (" --u8-unit-root <this tree built with EXTRA=-DVS_IVF_ONE_U8_UNIT_ROWS=2048>" if a.u8_unit_root else "") + (" --parent-root <a checkout of the parent commit, library built>" if a.parent_root else ""),
+             "# us per call back to back by HIP events (min, median over the alternations) | synchronised single call, host clock (median) |",
+             "# GB/s (B = 1 only) = probed rows x bytes per padded row of the kind the leg reads / us min, the whole call | route: batches the",
+             "# counters saw (byte route, fp32 route) | rule: vs_ivf_one_plan_u8's route for the shape (2 = the byte route, 0 = the group route)",
+             f"{'dim':>4} {'nprobe':>6} {'B':>3} {'leg':>7} {'us min':>8} {'us med':>8} {'sync med':>9} {'GB/s':>7} {'route':>9} {'rule':>4}  us per repeat"]
+    sys.path.insert(0, ROOT)
+    import __graft_entry__ as ge
+    plan_u8 = ge.load_package().ivf_one_plan_u8
+    for dim in [int(x) for x in a.dims.split(",")]:
+        force = {"VSEARCH_IVF_ND_FORCE": "1"} if dim == 128 else {}
+        workers = [Worker(a, "u8", ROOT, dim, "ivfu8", dict(force, VSEARCH_IVF_ONE_U8="2"), True),
+                   Worker(a, "u8off", ROOT, dim, "ivfu8", dict(force, VSEARCH_IVF_ONE_U8="0"), True)]
+        if a.u8_unit_root:
+            workers.append(Worker(a, "u8unit", os.path.abspath(a.u8_unit_root), dim, "ivfu8", dict(force, VSEARCH_IVF_ONE_U8="2"), True))
+        if a.parent_root:
+            workers.append(Worker(a, "parent", os.path.abspath(a.parent_root), dim, "ivfu8", force, False))
+        legs = [(w.name, w, None) for w in workers]
+        legs.insert(1, ("u8f32", workers[0], 1))
+        dim_b, dim_p = (dim + 63) // 64 * 64, (dim + 15) // 16 * 16
+        try:
+            for w in workers:
+                w.read()  # ready
+            for nprobe in [int(x) for x in a.nprobes.split(",")]:
+                for B in [int(x) for x in a.batches.split(",")]:
+                    digests = {}
+                    for name, w, prec in legs:
+                        if prec is not None:
+                            w.ask(f"precision {prec}")
+                        digests[name] = w.ask(f"check {B} {nprobe}")["check"]
+                        if prec is not None:
+                            w.ask("precision 0")
+                    if len(set(digests.values())) != 1:
+                        raise SystemExit(f"dim {dim} nprobe {nprobe} B {B}: the legs answer differently: {digests}")
+                    res = {name: {"us": [], "sync_us": []} for name, _, _ in legs}
+                    route = {}
+                    for w in workers:
+                        if w.name != "parent":
+                            w.ask(f"route {B} {nprobe}")  # (clears the counters)
+                    for _ in range(a.reps):
+                        for name, w, prec in legs:
+                            if prec is not None:
+                                w.ask(f"precision {prec}")
+                            m = w.ask(f"measure {B} {nprobe}")
+                            res[name]["us"].append(m["us"])
+                            res[name]["sync_us"].append(m["sync_us"])
+                            if name != "parent":
+                                route[name] = w.ask(f"route {B} {nprobe}")
+                            if prec is not None:
+                                w.ask("precision 0")
+                    for name, w, prec in legs:
+                        us, sy = res[name]["us"], res[name]["sync_us"]
+                        r = route.get(name)
+                        rows = route["u8"]["rows"]
+                        gbs = rows * (4 * dim_p if name == "u8f32" else dim_b) / min(us) / 1e3 if B == 1 else 0.0
+                        rule = plan_u8(a.rows, dim, a.nlist, 256, 1, B, K, nprobe)[0]
+                        rt = f"{r['one_u8'][0] if r['one_u8'] else 0},{r['one'][0]}" if r else "-"
+                        print(json.dumps({"dim": dim, "rows": a.rows, "nlist": a.nlist, "nprobe": nprobe, "B": B, "k": K, "leg": name,
+                                          "us_per_call": [round(x, 2) for x in us], "us_min": round(min(us), 2), "us_median": round(statistics.median(us), 2),
+                                          "sync_median": round(statistics.median(sy), 1), "probed_rows": rows, "gb_per_s": round(gbs, 1), "route": r, "rule": rule,
+                                          "same_outputs": True}), flush=True)
+                        table.append(f"{dim:>4} {nprobe:>6} {B:>3} {name:>7} {min(us):>8.2f} {statistics.median(us):>8.2f} {statistics.median(sy):>9.1f} "
+                                     f"{(f'{gbs:.1f}' if B == 1 else '-'):>7} {rt:>9} {rule:>4}  {[round(x, 1) for x in us]}")
+                        if a.out:
+                            with open(a.out, "w") as f:
+                                f.write("\n".join(table) + "\n")
+        finally:
+            for w in workers:
+                w.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dims", default="96,128,384,768")
@@ -202,6 +313,8 @@ def main():
     ap.add_argument("--one", default="", metavar="DIM,B,NPROBE", help="one process, 300 calls of one shape on the default route: "
                     "the run to put under rocprofv3 --kernel-trace --stats for the per-launch split")
     ap.add_argument("--parent-root", default="", help="a checkout of the parent commit with its library built")
+    ap.add_argument("--u8", action="store_true", help="the byte route's leg: the index from the same rows as uint8 (DESIGN 4.6e)")
+    ap.add_argument("--u8-unit-root", default="", metavar="DIR", help="--u8: one more leg on this tree built with another byte unit size")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--root", default=ROOT, help=argparse.SUPPRESS)
     ap.add_argument("--dim", type=int, default=0, help=argparse.SUPPRESS)
@@ -212,6 +325,8 @@ def main():
         return worker(a)
     if a.one:
         return one_shape(a)
+    if a.u8:
+        return main_u8(a)
     table = [f"# python3 scripts/ivf_one_bench.py --dims {a.dims} --rows {a.rows} --nlist {a.nlist} --reps {a.reps} --nprobes {a.nprobes} --data {a.data}"
              + (" --parent-root <a checkout of the parent commit, library built>" if a.parent_root else ""),
              "# us per call back to back by HIP events (min, median over the alternations) | synchronised single call, host clock (median)",
