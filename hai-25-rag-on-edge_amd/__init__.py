@@ -159,6 +159,8 @@ def lib():
         "vs_bf_one_plan": (i32, [i64, i32, i32, i32, i32, i32, vp]),
         "vs_bf_one_plan_u8": (i32, [i64, i32, i32, i32, i32, i32, vp]),
         "vs_bf_one_stats": (i32, [vp, C.POINTER(i64), i32]),
+        "vs_bf_wide_plan": (i32, [i64, i32, i32, vp]),
+        "vs_bf_wide_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_comm_unique_id": (i32, [vp]),
         "vs_comm_create": (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
         "vs_comm_rank": (i32, [vp]),
@@ -511,6 +513,21 @@ class BruteForceIndex(_Index):
         out = (C.c_int64 * 2)()
         _check(lib().vs_bf_one_stats(self._h, out, 1 if reset else 0))
         return int(out[0]), int(out[1])
+
+    @staticmethod
+    def wide_plan(n_rows: int, dim: int, k: int):
+        """(1 when a wide call reads the byte rows, prefix rows, candidates stored per query) of a call for 16 <= k <= 128
+        on the byte copy of a general ``from_u8`` index of [n_rows, dim] (vs_bf_wide_plan; host only); zeros for k <= 15."""
+        out = (C.c_int64 * 3)()
+        _check(lib().vs_bf_wide_plan(n_rows, dim, k, out))
+        return tuple(int(x) for x in out)
+
+    def wide_stats(self, reset: bool = False):
+        """(wide batches whose bulk passes ran on the byte rows, batches of the byte route their verdict sent to the fp32
+        rows, every wide batch enqueued) on this index since the last reset (vs_bf_wide_stats; synchronises the device)."""
+        out = (C.c_int64 * 3)()
+        _check(lib().vs_bf_wide_stats(self._h, out, 1 if reset else 0))
+        return int(out[0]), int(out[1]), int(out[2])
 
     @staticmethod
     def search_vshards(shards, queries: np.ndarray, k: int, timing: "Timing | None" = None):

@@ -91,6 +91,8 @@ struct vs_index {
     bool nd_one = true;  // general brute-force index: short calls on the fp32 rows take scan_one_nd_kernel (VSEARCH_ND_ONE=0 at creation: off)
     bool nd_one_u8 = true;  // ... and short calls on its byte rows scan_one_nd_i8_kernel (VSEARCH_ND_ONE_U8=0 at creation: off)
     int64_t one_stat[2] = {0, 0};  // single-call launches enqueued on the fp32 rows | on the byte rows (vs_bf_one_stats; host side)
+    bool nd_wide_u8 = true;  // ... and wide k (k >= 16) runs its bulk passes on the byte rows (VSEARCH_ND_WIDE_U8=0 at creation: off)
+    int64_t wide_batches = 0;  // wide batches enqueued on this index, on any route (vs_bf_wide_stats; host side)
     vs::DevBuf<float> d_nd_qfrag;  // [kMaxMulti][dim_p / 16][2][64][4] scratch of launch_scan_nd
     vs::DevBuf<float> d_nd_qnorm;  // [kMaxMulti][32]
     // general index made from uint8 rows (vs_bf_create_nd_u8, vs_bf_create_nd_u8_metric): the rows once more as int8
@@ -103,6 +105,7 @@ struct vs_index {
     vs::DevBuf<int32_t> d_nd_rsum;   // [n_rows + 64] sum (b - 128) (inner-product indexes, vs_bf_create_nd_u8_metric)
     vs::DevBuf<int8_t> d_nd_q8frag;  // [kMaxMulti][dim_b / 64][2][64][16] scratch of launch_scan_nd_i8
     vs::DevBuf<int32_t> d_nd_qterm;  // [kMaxMulti][32]
+    vs::DevBuf<unsigned long long> d_wide_cnt;  // brute force: [2] wide batches scanned on the byte rows | sent to the fp32 rows by their verdict
     vs::DevBuf<unsigned long long> d_nd_stats;  // general IVF index from uint8 rows: (query, probe) pairs planned on bytes | on fp32
     int metric = VS_METRIC_L2;
     int64_t n_rows = 0;   // rows resident on this GPU
@@ -586,6 +589,10 @@ int build_nd_u8_copy(vs_index* h, const uint8_t* rows_u8, int64_t rows) {
         (rc = h->d_nd_q8frag.alloc((size_t)kMaxMulti * 32 * ld)) || (rc = h->d_nd_qterm.alloc((size_t)kMaxMulti * 32)))
         return rc;
     HIPCHK(hipMemcpy(h->d_nd_u8, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+    if (h->kind == 0) {
+        if ((rc = h->d_wide_cnt.alloc(2))) return rc;
+        HIPCHK(hipMemset(h->d_wide_cnt, 0, 2 * sizeof(unsigned long long)));
+    }
     if (h->kind == 0 && h->metric == VS_METRIC_IP) {
         // a brute-force index keeps its metric: the inner-product epilogue needs sum (b - 128) per row, not the L2 term
         if ((rc = h->d_nd_rsum.alloc(rterm.size()))) return rc;
@@ -1164,6 +1171,15 @@ int64_t topw_prefix(int64_t n_rows, int k1) {
     return std::min(l, n_rows);
 }
 
+// Whether a wide call (k1 = k + 1 > 16) on the byte copy of a general index of this shape runs its two bulk passes on the
+// byte rows (vs_bf_wide_plan's rule; topw_launch goes through it).  Every shape does: none measured slower -- 1.07 x at
+// 96-d to 3.8 x at 2048-d on 1 M rows; a shape that does would leave here, with its numbers.
+bool wide_route_u8(int64_t n_rows, int dim, int k1) {
+    (void)n_rows;
+    (void)dim;
+    return k1 > kKcapMax;
+}
+
 int ensure_topw(vs_index* h) {
     if (h->topw.ready) return VS_OK;
     vs_index::TopW w;
@@ -1201,13 +1217,55 @@ int topw_launch(vs_index* h, const float* q_dev, int nb, int B, int k1, float* o
     const int64_t l0 = topw_prefix(n, k1), l0p = (l0 + 15) & ~int64_t(15);
     int32_t* const overflow = W.fz + 32;
     int rc;
+    // On an index with byte rows the two bulk passes (prefix scores, filter) run on them: one preparation
+    // launch per kMaxMulti batches (what the scratch holds) gives each its byte fragments and its verdict word; per batch the byte launch of a pass
+    // returns at once where the word is set, and the fp32 launch behind it runs only there (run_if).  Either writes the
+    // same scratch with the same bits, so the selections between the passes and the fallback stay as they are.
+    const bool u8 = nd_u8_path(h, false) && h->nd_wide_u8 && wide_route_u8(n, h->dim, k1);
+    vs::ScanNdI8Params bp{};
+    if (u8) {
+        bp.dim = h->dim;
+        bp.dim_b = h->dim_b;
+        bp.bmax = h->nd_bmax;
+        bp.q8frag = h->d_nd_q8frag;
+        bp.qterm = h->d_nd_qterm;
+        bp.rsum = h->d_nd_rsum;  // (inner product; null on an L2 index)
+        bp.wide_cnt = h->d_wide_cnt;
+        bp.s.base_u8 = h->d_nd_u8;
+        bp.s.rterm = h->d_nd_rterm;
+        bp.s.invalid = h->d_invalid;
+        bp.s.q_batch_stride = (int64_t)B * h->dim;
+        bp.s.metric = h->metric;
+        bp.s.nq_valid = B;
+        bp.s.k1 = k1;
+    }
+    const int nqh8 = B <= 16 ? 1 : 2;
+    h->wide_batches += nb;
     prof_begin(h, 0, s);
     for (int b = 0; b < nb; ++b) {
         const float* qb = q_dev + (size_t)b * B * h->dim;
         float* const od = out_d + (size_t)b * B * k1;
         int32_t* const oi = out_i + (size_t)b * B * k1;
         int32_t* const fl = flags ? flags + (size_t)b * B : nullptr;
-        if ((rc = scores_dev(h, h->d_vecs, h->d_norm, l0, qb, B, W.pre, l0p, s))) return rc;
+        const int slot = b % kMaxMulti;  // this batch's place in the byte scratch
+        const int32_t* const not_bytes = u8 ? h->d_invalid + slot : nullptr;  // the fp32 passes' run_if
+        if (u8) {
+            bp.wide_batch = slot;
+            if (slot == 0) {
+                bp.s.q = qb;
+                bp.s.n_batches = std::min(kMaxMulti, nb - b);
+            }
+            vs::ScanNdI8Params sp = bp;
+            sp.wide_prepared = slot > 0;
+            sp.s.row_begin = 0;
+            sp.s.row_end = l0;
+            sp.s.store = W.pre;
+            sp.s.store_ld = l0p;
+            int sgrid, stp;
+            scan_geometry(l0, h->num_cus, sgrid, stp);
+            HIPCHK(vs::launch_scan_nd_i8_wide(sp, sgrid, nqh8, vs::kModeStore, s));
+        }
+        if ((rc = scores_dev(h, h->d_vecs, h->d_norm, l0, qb, B, W.pre, l0p, s, not_bytes))) return rc;
         vs::TopkWideParams t{};
         t.dense = W.pre;
         t.dense_ld = l0p;
@@ -1248,6 +1306,19 @@ int topw_launch(vs_index* h, const float* q_dev, int nb, int B, int k1, float* o
         int grid, tp;
         scan_geometry(n - l0, h->num_cus, grid, tp);
         p.tiles_per_wg = tp;
+        if (u8) {
+            vs::ScanNdI8Params fp = bp;
+            fp.wide_prepared = 1;
+            fp.s.row_begin = l0;
+            fp.s.row_end = n;
+            fp.s.tau0 = W.tau;
+            fp.s.f_cnt = W.fz;
+            fp.s.f_row = W.f_row;
+            fp.s.f_d = W.f_d;
+            fp.s.f_cap = kTopwFilterCap;
+            HIPCHK(vs::launch_scan_nd_i8_wide(fp, grid, nqh8, vs::kModeFilter, s));
+            p.run_if = not_bytes;
+        }
         HIPCHK(scan_any(h, p, grid, 8, 2, vs::kModeFilter, s));
         vs::TopkWideParams f{};
         f.list[0] = {W.pre_d, W.pre_i, vs::kTopkWideMax, nullptr, k1, 0};
@@ -2574,6 +2645,8 @@ static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int m
     if (const char* e = getenv("VSEARCH_ND_ONE")) h->nd_one = atoi(e) != 0;
     // ... and VSEARCH_ND_ONE_U8=0 the per-batch scan_nd_i8_kernel route for short calls on its byte rows
     if (const char* e = getenv("VSEARCH_ND_ONE_U8")) h->nd_one_u8 = atoi(e) != 0;
+    // ... and VSEARCH_ND_WIDE_U8=0 the fp32 launches for wide k on an index with byte rows (topw_launch)
+    if (const char* e = getenv("VSEARCH_ND_WIDE_U8")) h->nd_wide_u8 = atoi(e) != 0;
     h->metric = metric;
     h->n_rows = h->n_total = n_rows;
     h->id_offset = id_offset;
@@ -3751,6 +3824,53 @@ int vs_bf_one_plan_u8(int64_t n_rows, int dim, int num_cus, int n_batches, int B
         return VS_ERR_UNSUPPORTED;
     }
     one_route_u8(n_rows, dim, num_cus, n_batches, B, k + 1, out);
+    return VS_OK;
+}
+
+// wide_route_u8 and topw_prefix for the ABI (host only); whether an index keeps a byte copy, its precision setting and
+// VSEARCH_ND_WIDE_U8 are not its business
+int vs_bf_wide_plan(int64_t n_rows, int dim, int k, int64_t* out) {
+    if (!out || n_rows < 1 || k < 1) {
+        set_error("vs_bf_wide_plan: bad arguments (out != NULL, n_rows, k >= 1)");
+        return VS_ERR_INVALID;
+    }
+    if (dim < 1) {
+        set_error("vs_bf_wide_plan: dim must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (dim > vs::kNdMaxDim) {
+        set_error("vs_bf_wide_plan: dim > 2048 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (k > vs::kTopkWideMax - 1) {
+        set_error("vs_bf_wide_plan: k > 128 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    out[0] = out[1] = out[2] = 0;
+    if (k + 1 <= kKcapMax) return VS_OK;  // not a wide call
+    out[0] = wide_route_u8(n_rows, dim, k + 1) ? 1 : 0;
+    out[1] = topw_prefix(n_rows, k + 1);
+    out[2] = kTopwFilterCap;
+    return VS_OK;
+}
+
+int vs_bf_wide_stats(vs_index* h, int64_t* out, int reset) {
+    if (!h || h->kind != 0 || !out) {
+        set_error("vs_bf_wide_stats: a brute-force index and an output of three words");
+        return VS_ERR_INVALID;
+    }
+    int rc = set_device(h);
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    unsigned long long c[2] = {0, 0};
+    if (h->d_wide_cnt) HIPCHK(hipMemcpy(c, h->d_wide_cnt, sizeof(c), hipMemcpyDeviceToHost));
+    out[0] = (int64_t)c[0];
+    out[1] = (int64_t)c[1];
+    out[2] = h->wide_batches;
+    if (reset) {
+        if (h->d_wide_cnt) HIPCHK(hipMemset(h->d_wide_cnt, 0, sizeof(c)));
+        h->wide_batches = 0;
+    }
     return VS_OK;
 }
 

@@ -103,8 +103,28 @@ struct ScanNdI8Params {
     int32_t* qterm;          // scratch [n_batches][32]
     // inner product (s.metric == 1) only, null otherwise: [n_rows + 64] sum (b - 128) per row (launch_ivf_nd_i8_rowsum)
     const int32_t* rsum;
+    // launch_scan_nd_i8_wide only (zero otherwise).  wide_batch: the batch of the prepared scratch (fragments, terms,
+    // verdict) that the launch scans.  wide_prepared != 0: an earlier launch on the stream prepared that scratch for
+    // these queries, so the preparation launch is left out.  wide_cnt, kModeStore, optional: [2] batches scanned on the
+    // byte rows | batches the verdict sent away, counted once per launch.
+    int wide_batch, wide_prepared;
+    unsigned long long* wide_cnt;
 };
+constexpr int kNd8Tiles = 4;                          // 16-row tiles per wave block of the byte scans
+constexpr int kNd8BlockRows = kNd8Tiles * kTileRows;  // 64 <= kScanPadRows: a block never reads past the spare rows
+static_assert(kNd8BlockRows <= kScanPadRows, "row blocks are loaded unclamped");
 hipError_t launch_scan_nd_i8(const ScanNdI8Params& p, int grid, int kcap, int nqh, hipStream_t s);
+// What launch_scan_nd_i8 refuses; and that check (hipErrorInvalidValue), then its preparation launch for all s.n_batches batches.
+bool scan_nd_i8_params_ok(const ScanNdI8Params& p, int grid);
+hipError_t launch_nd_prep_i8(const ScanNdI8Params& p, int grid, hipStream_t s);
+
+// Wide-k passes on the byte rows (vs_scan_nd_i8_wide.hip): launch_scan_nd's kModeStore and kModeFilter
+// contracts (store / store_ld, or tau0 / f_cnt / f_row / f_d / f_cap; s.run_if is not read) on the byte copy, for one
+// batch: batch wide_batch of the prepared scratch.  The launch does nothing when s.invalid[wide_batch] is set -- the
+// caller enqueues the fp32 launch behind it with run_if on that word.  Under the exactness rule the distances are
+// launch_scan_nd's bits.  kModeStore: store_ld a multiple of 16.  Unless wide_prepared, the preparation launch comes
+// first (launch_nd_prep_i8: s.q, s.n_batches, s.q_batch_stride).
+hipError_t launch_scan_nd_i8_wide(const ScanNdI8Params& p, int grid, int nqh, int mode, hipStream_t s);
 
 // bf16 prefilter of the fp32 streaming scan (scan_f32f_kernel).  With S = q.b exact, S_fl the fp32 chain of
 // scan_f32s_kernel and S' the v_mfma_f32_16x16x32_bf16 sum of q' = bf16(q), b' = bf16(b):

@@ -40,10 +40,8 @@
 
 namespace vs {
 
-constexpr int kNd8Tiles = 4;                          // 16-row tiles per wave block
-constexpr int kNd8BlockRows = kNd8Tiles * kTileRows;  // 64 <= kScanPadRows: a block never reads past the spare rows
-static_assert(kNd8BlockRows <= kScanPadRows, "row blocks are loaded unclamped");
-// (byte_value and kNd8NormLimit, the exactness rule's pieces, are in vs_dev.h: the IVF byte scan shares them)
+// (kNd8Tiles and kNd8BlockRows are in vs_kernels.h: the wide-k passes, vs_scan_nd_i8_wide.hip, share them; byte_value and
+// kNd8NormLimit, the exactness rule's pieces, are in vs_dev.h: the IVF byte scan shares them)
 
 // grid = n_batches, 256 threads.  IP: the per-query term is qt_ip = 128 sum q' + 128^2 dim instead of sum q'^2 (same buffer)
 template <bool IP>
@@ -276,19 +274,28 @@ static hipError_t launch_scan_nd_i8_t(const ScanNdI8Params& p, int grid, hipStre
     return hipGetLastError();
 }
 
-hipError_t launch_scan_nd_i8(const ScanNdI8Params& p, int grid, int kcap, int nqh, hipStream_t s) {
+bool scan_nd_i8_params_ok(const ScanNdI8Params& p, int grid) {
     if (p.dim < 1 || p.dim > kNdMaxDim || p.dim_b != nd_dim_b(p.dim) || !p.q8frag || !p.qterm || !p.s.base_u8 ||
         (p.s.metric != 0 && p.s.metric != 1) || !(p.s.metric ? p.rsum : p.s.rterm) ||
         !p.s.invalid || p.bmax < 0 || p.bmax >= kNd8NormLimit || grid < 1 || grid > kSlotStride ||
         (p.s.row_begin & 15) || p.s.n_batches < 1 || p.s.nq_valid < 1 || p.s.nq_valid > kMaxBatch)
-        return hipErrorInvalidValue;
+        return false;
+    return true;
+}
+
+hipError_t launch_nd_prep_i8(const ScanNdI8Params& p, int grid, hipStream_t s) {
+    if (!scan_nd_i8_params_ok(p, grid)) return hipErrorInvalidValue;
     if (p.s.metric)
         hipLaunchKernelGGL(nd_prep_i8_kernel<true>, dim3(p.s.n_batches), dim3(256), 0, s, p.s.q, p.s.q_batch_stride, p.s.nq_valid, p.dim,
                            p.dim_b, p.bmax, p.q8frag, p.qterm, p.s.invalid, p.s.run_if);
     else
         hipLaunchKernelGGL(nd_prep_i8_kernel<false>, dim3(p.s.n_batches), dim3(256), 0, s, p.s.q, p.s.q_batch_stride, p.s.nq_valid, p.dim,
                            p.dim_b, p.bmax, p.q8frag, p.qterm, p.s.invalid, p.s.run_if);
-    hipError_t e = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t launch_scan_nd_i8(const ScanNdI8Params& p, int grid, int kcap, int nqh, hipStream_t s) {
+    hipError_t e = launch_nd_prep_i8(p, grid, s);
     if (e != hipSuccess) return e;
     if (kcap == 8) return nqh == 1 ? launch_scan_nd_i8_t<1, 8>(p, grid, s) : launch_scan_nd_i8_t<2, 8>(p, grid, s);
     if (kcap == 16) return nqh == 1 ? launch_scan_nd_i8_t<1, 16>(p, grid, s) : launch_scan_nd_i8_t<2, 16>(p, grid, s);

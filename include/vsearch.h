@@ -189,14 +189,54 @@ VS_API int vs_bf_one_plan_u8(int64_t n_rows, int dim, int num_cus, int n_batches
  * VS_ERR_INVALID. */
 VS_API int vs_bf_one_stats(vs_index* h, int64_t* out /* [2] */, int reset);
 
+/* Wide k on the byte rows (host only, no GPU needed).  A wide call (16 <= k <= 128) spends most
+ * of its time in two bulk passes per batch: the distances to a prefix of the rows, and a
+ * filtered pass over the rest that keeps what falls under the prefix's bound.  On a general
+ * index that keeps a byte copy of its rows (vs_bf_create_nd_u8, vs_bf_create_nd_u8_metric) both
+ * passes read the byte rows with int8 MFMA for every batch the exactness rule
+ * admits -- decided per batch on the device, without a host synchronisation; any other batch is
+ * answered on the fp32 rows inside the same call.  Results do not depend on the route: ids,
+ * distance bits and flags are those of the same index under vs_set_precision(h, 1).
+ * VSEARCH_ND_WIDE_U8=0, read when the index is created, keeps the fp32 launches for wide k on
+ * that index: the comparison toggle.
+ *
+ * vs_bf_wide_plan states the rule for a call for k neighbours on an index of n_rows rows of dim
+ * values; the launch code takes its decision and geometry through the same function.
+ *   out[0] = 1: a wide call on the byte copy of a general index of this shape reads the byte
+ *            rows; 0: it reads the fp32 rows
+ *   out[1] = rows of the prefix: min(n_rows, max(512 (k + 1), n_rows (k + 1) / 2048) rounded up
+ *            to a multiple of 4096)
+ *   out[2] = 8192, the candidates stored per query behind the prefix (more: the dense fallback)
+ * For k <= 15 (not a wide call) all three are 0.  out[0] = 1 for every 16 <= k <= 128 and every
+ * dim: no shape left the rule, because none measured slower on the byte rows than under the
+ * toggle (1 M rows, batches of 32, k = 16 / 100 / 128, us per batch): 96-d 339 / 457 / 461
+ * against 374 / 491 / 498, the smallest gain; 128-d inner product 253 / 338 / 350 against 304 /
+ * 390 / 402; 384-d 366 / 464 / 471 against 612 / 680 / 693; 768-d 366 / 485 / 495 against 1049 /
+ * 1110 / 1128; 2048-d 578 / 664 / 680 against 2199 / 2265 / 2281 -- every margin many times the
+ * spread of either leg (DESIGN.md 4.5c has the table).  Whether a given index keeps a byte copy, its precision setting
+ * and the toggle are not its business.
+ * Checks, in this order: null out, n_rows < 1, k < 1 -> VS_ERR_INVALID; dim < 1 ->
+ * VS_ERR_INVALID; dim > 2048 -> VS_ERR_UNSUPPORTED; k > 128 -> VS_ERR_UNSUPPORTED. */
+VS_API int vs_bf_wide_plan(int64_t n_rows, int dim, int k, int64_t* out /* [3] */);
+
+/* Wide batches (k >= 16) on a brute-force index since the last reset: out[0] = batches whose
+ * bulk passes ran on the byte rows, out[1] = batches enqueued on the byte route whose verdict
+ * sent them to the fp32 rows (both counted on the device, by the first launch of the batch),
+ * out[2] = every wide batch enqueued on the index, on any route (counted on the host).  The call
+ * synchronises the device; reset != 0 clears all three after reading.  All zeros before the
+ * first wide call.  Null pointers or an IVF index: VS_ERR_INVALID (a null handle is refused
+ * before any device is touched). */
+VS_API int vs_bf_wide_stats(vs_index* h, int64_t* out /* [3] */, int reset);
+
 /* Byte-valued rows at any vector length: base_host is uint8 [n_rows][dim], 1 <= dim <= 2048
  * (dim < 1: VS_ERR_INVALID, dim > 2048: VS_ERR_UNSUPPORTED), squared L2 only.  dim == 128 gives
  * the index vs_bf_create gives for the same rows converted to float: same results, same
  * launches.  Any other dim gives a general index exactly as vs_bf_create_nd builds it (fp32
  * rows padded to 16 floats, norms) PLUS the rows once more as int8 (x - 128), padded to 64
- * bytes, with an int32 term per row, scanned with int8 MFMA for k <= 15 at a quarter of the
- * row traffic.  The fp32 rows stay -- they serve k >= 16, vs_bf_scores_dev, the tie replay and
- * reruns -- so the index takes 1.25 x the device memory of a vs_bf_create_nd index (more below
+ * bytes, with an int32 term per row, scanned with int8 MFMA at a quarter of the row traffic:
+ * for k <= 15 by the byte scan, for 16 <= k <= 128 by the two bulk passes of the wide call
+ * (vs_bf_wide_plan above).  The fp32 rows stay -- they serve vs_bf_scores_dev, the tie replay,
+ * the dense fallback of a wide call, reruns and every batch the rule below refuses -- so the index takes 1.25 x the device memory of a vs_bf_create_nd index (more below
  * 64-d, where the byte rows are padded to 64).
  *
  * Exactness rule.  The byte scan returns the fp32 scan's distances to the bit when every fp32
@@ -205,11 +245,12 @@ VS_API int vs_bf_one_stats(vs_index* h, int64_t* out /* [2] */, int reset);
  * and fma(-2, dot, qn + bn) are exact in any summation order.  A batch therefore runs on the
  * byte rows only when (1) every query value of the batch is an integer in [0, 255] and (2) max
  * over the batch of ||q||^2 + max over the base of ||b||^2 <= 2^24; both are checked on the
- * device, in integers.  Any other batch is skipped: the *_dev calls report flags == 2 for its
- * queries, vs_bf_search / vs_bf_search_topk rerun it on the fp32 rows themselves.  Nothing ever
- * returns a distance that differs from the fp32 path's.
+ * device, in integers.  Any other batch is skipped at k <= 15: the *_dev calls report flags == 2
+ * for its queries, vs_bf_search / vs_bf_search_topk rerun it on the fp32 rows themselves.  At
+ * k >= 16 such a batch is answered on the fp32 rows inside the same call (flags == 2 does not
+ * occur).  Nothing ever returns a distance that differs from the fp32 path's.
  *
- * vs_set_precision on such an index: 0 (default) and 2 use the byte scan for k <= 15, 1 forces
+ * vs_set_precision on such an index: 0 (default) and 2 use the byte rows for every k, 1 forces
  * the fp32 rows; 2 returns VS_ERR_UNSUPPORTED when max ||b||^2 >= 2^24 (the byte rows are then
  * not kept: no batch could run on them).  Calls accepted and refused: as vs_bf_create_nd.
  *
@@ -245,7 +286,9 @@ VS_API int vs_bf_create_nd_u8(const uint8_t* base_host, int64_t n_rows, int dim,
  * rebuilds, q.b = q'.b' + 128 (sum q' + sum b') + 128^2 dim with x' = x - 128.  Any other batch
  * is skipped: the *_dev calls report flags == 2, the host calls rerun it on the fp32 rows.
  * Precision 1 forces the fp32 rows; precision 2 returns VS_ERR_UNSUPPORTED when the byte copy
- * was not kept.  k >= 16 and vs_bf_scores_dev read the fp32 rows, as under L2.  Short calls on
+ * was not kept.  k >= 16 runs its bulk passes on the byte rows as under L2 (vs_bf_wide_plan; a
+ * batch the rule refuses: on the fp32 rows, in the same call); vs_bf_scores_dev reads the fp32
+ * rows.  Short calls on
  * the byte rows take the single-call byte kernel as under L2 (vs_bf_one_plan_u8).
  *
  * Outputs are the inner-product ones of vs_bf_create_nd: the *_dev calls return s = -(q.v)
@@ -266,7 +309,9 @@ VS_API int vs_set_batch(vs_index* h, int batch);
  * traffic.  A batch containing a non-integer query is detected on the device, skipped and rerun in fp32
  * (vs_bf_search does that itself; the *_dev calls report it as flags == 2).  1 = force fp32 (the reference
  * arithmetic, cblas_sgemm + epilogue); 2 = require int8 (VS_ERR_UNSUPPORTED when the base does not allow it).
- * IVF indexes alike: 1 = the list scan reads the fp32 rows (IVFIndex.cpp:270-358's arithmetic). */
+ * IVF indexes alike: 1 = the list scan reads the fp32 rows (IVFIndex.cpp:270-358's arithmetic).
+ * Wide k (k >= 16): the specialised 128-d index and vs_bf_create_nd indexes read the fp32 rows whatever the setting; a
+ * general index with a byte copy (vs_bf_create_nd_u8*) reads the byte rows at 0 and 2 and the fp32 rows at 1. */
 VS_API int vs_set_precision(vs_index* h, int precision);
 /* IVF indexes are created with the north-star's squared L2; VS_METRIC_IP selects the reference's own ranking (IVFIndex.cpp:
  * 449-496, :697-723): nprobe lists of LARGEST q.c, k candidates of largest q.v (fp32 rows; the int8 copies are an L2 device).
@@ -309,14 +354,17 @@ VS_API int vs_bf_search_dev_multi(vs_index* h, const float* queries_dev, int n_b
 
 /* Wide k: 1 <= k <= 128.  For k <= 15 the result is exactly vs_bf_search's (same code path).  For k >= 16: the k best by
  * select_topk's slot semantics; order among equal distances = slot order, stably sorted.  k > 128 returns
- * VS_ERR_UNSUPPORTED.  The k >= 16 path scans the fp32 rows whatever vs_set_precision says (the distances are the same).
+ * VS_ERR_UNSUPPORTED.  The k >= 16 path scans the fp32 rows whatever vs_set_precision says -- except on a general index
+ * with a byte copy (vs_bf_create_nd_u8*), where its two bulk passes read the byte rows at precision 0 or 2 (vs_bf_wide_plan);
+ * the tie replay reads the fp32 rows; the distances are the same either way.
  * VS_METRIC_IP, for every k: the scores q.v, descending (vs_bf_search_topk_dev_multi returns -q.v, ascending); equal scores
  * in ascending id, with no tie replay. */
 VS_API int vs_bf_search_topk(vs_index* h, const float* queries_host, int64_t nq, int k,
                              int32_t* ids, float* dists, vs_timing* timing);
 /* Device form of vs_bf_search_dev_multi for 1 <= k <= 128: outputs [n_batches*B x (k+1)] by (dist, id) ascending,
  * flags[n_batches*B] as vs_bf_search_dev_multi (1 = equal distances among the k+1, 2 = int8 batch skipped; for k >= 16
- * the fp32 rows are scanned and 2 does not occur). */
+ * 2 does not occur: the fp32 rows are scanned, or, on a general index with a byte copy, the byte rows for the batches the
+ * exactness rule admits and the fp32 rows for the others, in the same call -- vs_bf_wide_plan). */
 VS_API int vs_bf_search_topk_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k,
                                        int32_t* ids_dev, float* dists_dev, int32_t* flags_dev, void* stream);
 
