@@ -230,6 +230,9 @@ def lib():
         "vs_f32_filter_cnorm": (C.c_float, [C.c_double]),
         "vs_f32_filter_th2": (C.c_float, [C.c_float] * 3),
         "vs_bf_filter_stats": (i32, [vp, C.POINTER(i64), i32]),
+        "vs_bf_filter_i8_stats": (i32, [vp, C.POINTER(i64), i32]),
+        "vs_bf_filter_i8_plan": (i32, [vp, i32, i32]),
+        "vs_f32_filter_i8_test": (None, [C.c_float, i32, i32, i32, C.POINTER(i32)]),
         "vs_destroy": (None, [vp]),
     }
     for name, (res, args) in sig.items():
@@ -445,6 +448,18 @@ class BruteForceIndex(_Index):
         out = (C.c_int64 * 4)()
         _check(lib().vs_bf_filter_stats(self._h, out, 1 if reset else 0))
         return tuple(int(x) for x in out)
+
+    def filter_i8_stats(self, reset: bool = False):
+        """(launch groups enqueued on the int8 prefilter route, groups the device handed to the bf16 sweep, candidates the
+        int8 sweep wrote, candidates that survived the exact recheck) since the last reset (vs_bf_filter_i8_stats)."""
+        out = (C.c_int64 * 4)()
+        _check(lib().vs_bf_filter_i8_stats(self._h, out, 1 if reset else 0))
+        return tuple(int(x) for x in out)
+
+    def filter_i8_plan(self, n_batches: int, k: int) -> bool:
+        """Whether a search_dev_multi launch group of n_batches batches is enqueued on the int8 prefilter route
+        (vs_bf_filter_i8_plan)."""
+        return bool(lib().vs_bf_filter_i8_plan(self._h, n_batches, k))
 
     def search(self, queries, k: int, timing: Timing | None = None):
         q = _f32c(queries).reshape(-1, self.d)

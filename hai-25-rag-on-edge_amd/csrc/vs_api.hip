@@ -124,8 +124,10 @@ struct vs_index {
     bool filter_ok = false;
     // vs_bf_filter_stats: [1] launches that overflowed, [2] candidates of the sweeps, [3] survivors of the recheck (device
     // counters, allocated with the image), and the prefilter launches made (counted where they are enqueued)
+    // ... and behind them vs_bf_filter_i8_stats' words of the int8 sweep: [5] groups handed to the bf16 sweep, [6], [7] as [2], [3]
     vs::DevBuf<unsigned long long> filter_stats;
     int64_t filter_launches = 0;
+    int64_t filter_i8_groups = 0;  // launch groups enqueued on the int8 route
     vs::DevBuf<uint16_t> d_img;  // [n_rows + 64][128], spare rows zero
     // int8 data path: only when every base value is an integer in [0, 255]
     vs::DevBuf<int8_t> d_vecs_u8;   // [n_rows][128] bytes (x - 128)
@@ -519,12 +521,12 @@ int upload_vectors(vs_index* h, const float* host, int64_t rows) {
             memcpy(&bnmax, &v[4], sizeof(double));
             h->filter_cnorm = vs::filter_cnorm(bnmax);
             h->filter_ok = have_img && v[3] == 0 && std::isfinite(m[0]) && std::isfinite(m[2]) && std::isfinite(h->filter_cnorm);
-            if (h->filter_ok && h->filter_stats.alloc(4) != VS_OK) {  // (as the image: an accelerator, not a requirement)
+            if (h->filter_ok && h->filter_stats.alloc(8) != VS_OK) {  // (as the image: an accelerator, not a requirement)
                 (void)hipGetLastError();
                 vs::set_error("");
                 h->filter_ok = false;
             }
-            if (h->filter_ok) HIPCHK(hipMemset(h->filter_stats, 0, 4 * sizeof(unsigned long long)));
+            if (h->filter_ok) HIPCHK(hipMemset(h->filter_stats, 0, 8 * sizeof(unsigned long long)));
             if (!h->filter_ok) h->d_img.reset();  // (the copy above has waited for the kernel)
         }
         HIPCHK(hipDeviceSynchronize());
@@ -536,7 +538,7 @@ int upload_vectors(vs_index* h, const float* host, int64_t rows) {
 // ||b||^2 - 256 * sum(b - 128); dist = [||q||^2 - 256 sum(q-128) - 2*128^3] + rterm - 2 * sum((q-128)(b-128)).
 int build_u8_copy(vs_index* h, const float* host, int64_t rows, std::vector<int8_t>* bytes_out = nullptr, std::vector<int32_t>* rterm_out = nullptr) {
     std::vector<int8_t> bytes(((size_t)rows + vs::kScanPadRows) * vs::kDim, 0);  // spare rows: tile DMAs are not clamped
-    std::vector<int32_t> rterm((size_t)rows + 64, 0);
+    std::vector<int32_t> rterm((size_t)rows + vs::kScanPadRows, 0);
     for (int64_t i = 0; i < rows; ++i) {
         int32_t n2 = 0, sb = 0;
         for (int t = 0; t < vs::kDim; ++t) {
@@ -686,6 +688,14 @@ int g_f32_filter = [] {
     return e ? atoi(e) : 1;
 }();
 bool f32_filter_enabled() { return g_f32_filter != 0; }
+
+// comparison toggle (VSEARCH_F32_FILTER_I8=0): a byte-valued L2 shard's prefilter launches run the bf16 sweep alone, without
+// the int8 sweep on the byte copy in front of it (scan_f32f_i8_kernel); 2 = the int8 sweep at every launch size (default 1:
+// where it was measured faster, vs::filter_i8_pays)
+int g_f32_filter_i8 = [] {
+    const char* e = getenv("VSEARCH_F32_FILTER_I8");
+    return e ? atoi(e) : 1;
+}();
 
 // comparison toggle (VSEARCH_F32F_WAVES=8 or 4): scan_f32f_kernel runs as one 8-wave workgroup per CU, or as two 4-wave
 // workgroups per CU, at every launch size (default unset: the measured choice per launch size, launch_scan_f32_stream)
@@ -1065,6 +1075,15 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
                 sp.f32f_prio = g_f32f_prio;
                 sp.sink.stats = h->filter_stats;
                 ++h->filter_launches;
+                if (i8_seed && (g_f32_filter_i8 > 1 || (g_f32_filter_i8 == 1 && vs::filter_i8_pays(h->n_rows, nb, sgrid)))) {  // byte-valued shard, L2: the int8 sweep in front, the verdict words choose on the device
+                    sp.base_u8 = h->d_vecs_u8;
+                    sp.rterm = h->d_rterm;
+                    sp.q8frag = L.q8frag;
+                    sp.qterm = L.wide8.qterm;
+                    sp.invalid = invalid;
+                    sp.i8_stats = h->filter_stats + 4;
+                    ++h->filter_i8_groups;
+                }
             }
             HIPCHK(vs::launch_scan_f32_stream(sp, sgrid, s));
             prof_end(h, 0, s);
@@ -2380,16 +2399,52 @@ int vs_bf_filter_stats(vs_index* h, int64_t* out, int reset) {
         return VS_ERR_INVALID;
     }
     HIPCHK(hipSetDevice(h->device));
-    unsigned long long v[4];
+    unsigned long long v[8];  // [4..7]: the int8 sweep's words (vs_bf_filter_i8_stats)
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(v, h->filter_stats, sizeof(v), hipMemcpyDeviceToHost));
     out[0] = h->filter_launches;
-    for (int i = 1; i < 4; ++i) out[i] = (int64_t)v[i];
+    out[1] = (int64_t)v[1];  // (either sweep raises the one overflow word of its group)
+    for (int i = 2; i < 4; ++i) out[i] = (int64_t)(v[i] + v[4 + i]);  // whichever sweep answered the group
     if (reset) {
         HIPCHK(hipMemset(h->filter_stats, 0, sizeof(v)));
         h->filter_launches = 0;
+        h->filter_i8_groups = 0;
     }
     return VS_OK;
+}
+int vs_bf_filter_i8_stats(vs_index* h, int64_t* out, int reset) {
+    if (!h || !out) {
+        set_error("vs_bf_filter_i8_stats: an index and an output of four words");
+        return VS_ERR_INVALID;
+    }
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!h->filter_ok || !h->filter_stats) return VS_OK;  // an index that never takes the route
+    HIPCHK(hipSetDevice(h->device));
+    unsigned long long v[4];
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(v, h->filter_stats + 4, sizeof(v), hipMemcpyDeviceToHost));
+    out[0] = h->filter_i8_groups;
+    for (int i = 1; i < 4; ++i) out[i] = (int64_t)v[i];
+    if (reset) {
+        HIPCHK(hipMemset(h->filter_stats + 4, 0, sizeof(v)));
+        h->filter_i8_groups = 0;
+    }
+    return VS_OK;
+}
+int vs_bf_filter_i8_plan(const vs_index* h, int n_batches, int k) {
+    if (!h || h->kind != 0 || h->general || n_batches < 1 || n_batches > kMaxMulti || k < 1 || !pick_kcap(k + 1)) return 0;
+    const bool stream = bf_seeded(h->n_rows, n_batches, k + 1) && g_stream;
+    const bool f32_filter = stream && !(h->d_vecs_u8 && h->precision != 1) && g_f32_filter && h->filter_ok;
+    const bool i8_seed = h->d_vecs_u8 && h->metric == VS_METRIC_L2 && g_seed_i8;
+    const int64_t tiles_total = (h->n_rows + vs::kTileRows - 1) / vs::kTileRows;
+    const int sgrid = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(h->num_cus, vs::kSlotStride), tiles_total));
+    return f32_filter && i8_seed && (g_f32_filter_i8 > 1 || (g_f32_filter_i8 == 1 && vs::filter_i8_pays(h->n_rows, n_batches, sgrid))) ? 1 : 0;
+}
+void vs_f32_filter_i8_test(float tau0, int32_t qterm, int32_t rterm, int32_t dot, int32_t* out) {
+    const int32_t thr = vs::filter_i8_thr(tau0, qterm), a = dot + vs::filter_i8_c0(rterm);
+    out[0] = thr;
+    out[1] = vs::filter_i8_hot(a, thr) ? 1 : 0;
+    out[2] = vs::filter_i8_exact(a, rterm, thr) ? 1 : 0;
 }
 int vs_index_nlist(const vs_index* h) { return h ? h->nlist : 0; }
 void vs_destroy(vs_index* h) {

@@ -313,7 +313,42 @@ struct StreamParams {
     float cnorm;             // filter_cnorm of the shard's largest stored norm (the L2 test, filter_th2)
     int f32f_waves;          // scan_f32f_kernel's waves per workgroup: 8, 4 (two workgroups per CU), 0 = the measured choice per launch size
     int f32f_prio;           // 4-wave organisation: steps of every eight (0..8) on which half 1 raises its wave priority, so that the two workgroups of a CU end together; < 0 = the measured choice per shard size
+    // the int8 prefilter on the rows' exact byte copy (scan_f32f_i8_kernel, L2 only), when base_u8 is set: launched in
+    // front of the bf16 sweep.  `invalid` ([n_batches], written 0 / 1 by the seed's query preparation earlier in the
+    // stream) decides on the device which of the two answers the group: the byte sweep returns at once when a batch is
+    // not byte valued, the bf16 sweep when every batch is.
+    const int8_t* base_u8;   // [n_rows + 64][128] bytes (x - 128)
+    const int32_t* rterm;    // [n_rows + 64]
+    const int8_t* q8frag;    // SeedParams::q8frag
+    const int32_t* qterm;    // [n_batches][32]
+    const int32_t* invalid;  // [n_batches]
+    unsigned long long* i8_stats;  // optional (vs_bf_filter_i8_stats): [1] += 1 per group handed to the bf16 sweep, [2] += candidates written, [3] += candidates kept
 };
+
+// The integer test of scan_f32f_i8_kernel, with acc = sum (q - 128)(b - 128), qt = SeedParams::qterm and
+// rt = the row term: d = qt + rt - 2 acc, exactly the fp32 distance of a byte-valued pair (every partial sum an integer
+// below 2^24).  d < tau0  <=>  d < ceil(tau0) =: ti for an integer d  <=>  2 acc - rt > qt - ti =: thr.  With rt = 2 rh + ro
+// (ro = 0 / 1) that is 2 (acc - rh) - ro > thr.  The hot test compares A = acc - rh (-rh rides in the MFMA's C operand) with
+// thr >> 1 = floor(thr / 2):  2 A - ro > thr gives 2 A > thr, so A > thr / 2 >= floor(thr / 2) -- it admits every pair under
+// the bound, and for an odd thr and ro = 1 also the pairs with 2 A - 1 = thr, which the exact test (rare path) drops.
+// tau0 is clamped to +-2^26 first: distances are below 2^24, so +inf admits every row and -inf (or NaN) none.
+__host__ __device__ inline int32_t filter_i8_thr(float tau0, int32_t qt) {
+    const float t = tau0 > -67108864.f ? (tau0 < 67108864.f ? tau0 : 67108864.f) : -67108864.f;  // (NaN -> -2^26)
+    return qt - (int32_t)__builtin_ceilf(t);
+}
+constexpr int32_t kFilterI8Dead = 0x7fffffff;  // thr of a dead column block or a padding query: nothing is above 2^30
+// Which launch groups take the byte sweep (profiles/r10a_sizes_ab.txt): it saves arithmetic in proportion to column blocks
+// per wave x units per workgroup and costs one idle launch of the bf16 sweep behind it (about 4 us).  Measured faster
+// beyond the spread at 4 and 8 column blocks per wave (9 batches and more) on every shard from 125 K rows, and at 1 and 2
+// from 30 units per workgroup (500 K rows on 256 CUs); slower by 0.5 - 3 % at 1 and 2 with 15 units and fewer.
+inline bool filter_i8_pays(int64_t n_rows, int n_batches, int grid) {
+    const int64_t units = (n_rows + 63) / 64;
+    const int cbw = (2 * n_batches + kScanWaves - 1) / kScanWaves;
+    return cbw > 2 || units / (grid > 0 ? grid : 1) >= 24;
+}
+__host__ __device__ inline int32_t filter_i8_c0(int32_t rt) { return -(rt >> 1); }
+__host__ __device__ inline bool filter_i8_hot(int32_t a, int32_t thr) { return a > (thr >> 1); }
+__host__ __device__ inline bool filter_i8_exact(int32_t a, int32_t rt, int32_t thr) { return 2 * a - (rt & 1) > thr; }
 hipError_t launch_scan_f32_stream(const StreamParams& p, int grid, hipStream_t s);
 
 // Single-call scan (vs_scan_one.hip): one launch per batch of <= 32 queries, no seed launches, no merge launch -- a lane

@@ -32,6 +32,7 @@
 #include <algorithm>
 #include "vs_sink.h"
 #include "vs_ring.h"
+#include "vs_f32f.h"
 
 namespace vs {
 
@@ -917,14 +918,6 @@ __global__ __launch_bounds__(kScanThreads, NQH <= 8 ? 2 : 1) void scan_i8w_kerne
     sink_bin_wave(p.sink, (int)blockIdx.x * kScanWaves + wave, wbase, lane);  // no separate binning launch
 }
 
-// L2 bound of the streaming fp32 scan's hot test fma(-2, dot, bn) < thr: d = RN(RN(qn + bn) - 2 dot) < tau implies
-// RN(bn - 2 dot) < tau - qn + slack: the three roundings together move the comparison by less than 2^-24 * 8 (qn + |tau|)
-// (a row under the bound has bn < 2 (qn + tau)); the slack is 16 times that.  (One function: the exact recheck of the bf16
-// prefilter must form the same bits.)
-__device__ __forceinline__ float stream_l2_thr(float tau, float qn) {
-    return (tau - qn) + 9.5367431640625e-7f * (qn + fabsf(tau));
-}
-
 // ------------------------------------------------------------------------------------------------
 // Streaming fp32 scan (see StreamParams): scan_kernel's fp32 data path and arithmetic, the wide int8 scan's organisation.
 // ------------------------------------------------------------------------------------------------
@@ -1153,51 +1146,6 @@ __global__ __launch_bounds__(kScanThreads, NB == 1 ? 2 : 1) void scan_f32s_kerne
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// the exact recheck: scan_f32s_kernel's dot of (row, query), its distance and both of its tests, or a dropped entry
-struct RecheckF32 {
-    const float* base;
-    const float* bnorm;
-    const float* q;
-    int64_t q_batch_stride;
-    const float* qnorm;
-    const float* tau0;
-    int metric;
-    int32_t id_offset;
-    __device__ __forceinline__ int4 operator()(const int4& c) const {
-        const int qg = c.x;
-        const int64_t row = (int64_t)c.z - id_offset;
-        const float* b = base + row * kDim;
-        const float* qq = q + (int64_t)(qg / kMaxBatch) * q_batch_stride + (int64_t)(qg % kMaxBatch) * kDim;
-        // the MFMA chain of scan_f32s_kernel: step (c, i) of v_mfma_f32_16x16x4_f32 adds the four products of k = 16 c +
-        // 4 g + i, g = 0..3 in order, each rounded like an fmaf
-        float dot = 0.f;
-#pragma unroll
-        for (int cc = 0; cc < 8; ++cc) {
-            f32x4 bv[4], qv[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                bv[g] = *reinterpret_cast<const f32x4*>(b + 16 * cc + 4 * g);
-                qv[g] = *reinterpret_cast<const f32x4*>(qq + 16 * cc + 4 * g);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) dot = fmaf(bv[g][i], qv[g][i], dot);
-        }
-        const float qn = qnorm[qg], tau = tau0[qg], bn = bnorm[row];
-        bool keep;
-        float d;
-        if (!metric) {
-            d = fmaf(-2.0f, dot, qn + bn);
-            keep = fmaf(-2.0f, dot, bn) < stream_l2_thr(tau, qn) && d < tau;
-        } else {
-            d = -dot;
-            keep = dot > -tau && d < tau;
-        }
-        return keep ? make_int4(qg, __builtin_bit_cast(int, d), c.z, 0) : make_int4(-1, 0, 0, 0);
-    }
-};
-
 // Ring depth (64-row unit slots) of scan_f32f_kernel, and the cache policy of its row pieces (2 = nt: a launch reads
 // every row once, and the 256 MB image of a SIFT-1M shard never fits a cache from one launch to the next).
 #ifndef VS_F32F_DEPTH
@@ -1214,8 +1162,6 @@ struct RecheckF32 {
 #error "VS_F32F_CPOL: 0 (default policy) or 2 (nt)"
 #endif
 constexpr int kFilterDepth = VS_F32F_DEPTH;
-constexpr int kUnitRows = 64;                         // rows per ring slot: four 16-row tiles
-constexpr int kUnitTiles = kUnitRows / kTileRows;
 constexpr int kUnitRowBytes = kUnitRows * kDim * 2;   // 16 KB of bf16 rows
 constexpr int kUnitBytes = kUnitRowBytes + kUnitRows * 4;  // + the unit's 64 norms
 static_assert(kUnitRows <= kScanPadRows, "units are fetched unclamped: the image and the norms have kScanPadRows spare rows");
@@ -1261,6 +1207,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_kernel(con
     const int T = (units_total - bx + G - 1) / G;  // units of this workgroup (G <= units_total: T >= 1)
     const int n_cb = 2 * p.n_batches;              // column blocks of the launch (<= 8 CBW)
     if (NW * z >= n_cb) return;  // (workgroup-uniform, NW = 4 only) a half none of whose waves has a column block
+    // behind the byte sweep (StreamParams::invalid): that one has answered a group whose batches are all byte valued
+    if (p.invalid && !f32f_some_batch_not_bytes(p.invalid, p.n_batches, lane)) return;  // (kernel-uniform)
 
     // LDS-DMA written as instructions (see vs_ring.h): "scalar unit base + this lane's 32-bit offset".  Wave w
     // moves rows 4 kPieces w .. 4 kPieces (w + 1) - 1 of each 32-row half of a unit, four rows per piece: lane l of piece
@@ -1532,13 +1480,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_kernel(con
 #endif
 }
 
-// Steps of every eight on which the second 4-wave workgroup of a CU raises its priority, where the caller does not
-// force a count (StreamParams::f32f_prio < 0), by units per workgroup: the choice measured per shard size (DESIGN 4.2b,
-// profiles/r09a_sizes_ab.txt).  Four of eight pay from about 60 units per workgroup on (1 M rows: - 4 % at 32 batches,
-// - 1 % at 16); at 30 units and fewer (500 K rows and below) a block of four steps is too large a part of the sweep, and
-// the launch group measured 3 - 5 % longer with it.
-static int f32f_prio_default(int64_t units_per_wg) { return units_per_wg >= 48 ? 4 : 0; }
-
 template <int CBW, int NW>
 static hipError_t launch_scan_f32f(const StreamParams& p0, int grid, hipStream_t s) {
     constexpr int kLds = kFilterDepth * kUnitBytes;  // per workgroup: at NW = 4 a CU holds two rings
@@ -1560,10 +1501,6 @@ static hipError_t launch_scan_f32f(const StreamParams& p0, int grid, hipStream_t
     return hipGetLastError();
 }
 
-// Waves per workgroup of the prefilter sweep where the caller does not force one (StreamParams::f32f_waves), by column
-// blocks per wave: the choice measured per launch size.
-static int f32f_waves_default(int cbw) { return cbw >= 4 ? 4 : 8; }
-
 template <int CBW>
 static hipError_t launch_scan_f32f(const StreamParams& p, int grid, hipStream_t s) {
     const int nw = p.f32f_waves ? p.f32f_waves : f32f_waves_default(CBW);
@@ -1577,6 +1514,11 @@ hipError_t launch_scan_f32_stream(const StreamParams& p, int grid, hipStream_t s
     if (p.qbf) {  // the bf16 prefilter: column blocks per wave for the launch's 2 n_batches column blocks
         const int cbw = (2 * p.n_batches + kScanWaves - 1) / kScanWaves;
         if (p.n_batches < 1 || cbw > 8 || !p.img || (p.f32f_waves != 0 && p.f32f_waves != 4 && p.f32f_waves != 8)) return hipErrorInvalidValue;
+        if (p.base_u8) {  // the byte sweep in front; the bf16 sweep below then runs only where the device hands the group over
+            if (p.metric || !p.rterm || !p.q8frag || !p.qterm || !p.invalid) return hipErrorInvalidValue;
+            const hipError_t e = launch_scan_f32f_i8(p, cbw <= 2 ? cbw : cbw <= 4 ? 4 : 8, grid, s);
+            if (e != hipSuccess) return e;
+        }
         return cbw == 1 ? launch_scan_f32f<1>(p, grid, s) : cbw == 2 ? launch_scan_f32f<2>(p, grid, s)
              : cbw <= 4 ? launch_scan_f32f<4>(p, grid, s) : launch_scan_f32f<8>(p, grid, s);
     }

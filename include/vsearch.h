@@ -309,6 +309,9 @@ VS_API int vs_set_batch(vs_index* h, int batch);
  * traffic.  A batch containing a non-integer query is detected on the device, skipped and rerun in fp32
  * (vs_bf_search does that itself; the *_dev calls report it as flags == 2).  1 = force fp32 (the reference
  * arithmetic, cblas_sgemm + epilogue); 2 = require int8 (VS_ERR_UNSUPPORTED when the base does not allow it).
+ * Under 1 a long call (4 batches and more) on a byte-valued squared-L2 index may still PREFILTER on the byte copy (int8 MFMA,
+ * vs_bf_filter_i8_stats below): what passes is recomputed from the fp32 rows, which decide every returned id, distance bit
+ * and flag; a launch group with a batch that is not byte valued is prefiltered on the bf16 image instead.
  * IVF indexes alike: 1 = the list scan reads the fp32 rows (IVFIndex.cpp:270-358's arithmetic).
  * Wide k (k >= 16): the specialised 128-d index and vs_bf_create_nd indexes read the fp32 rows whatever the setting; a
  * general index with a byte copy (vs_bf_create_nd_u8*) reads the byte rows at 0 and 2 and the fp32 rows at 1. */
@@ -1084,6 +1087,24 @@ VS_API float vs_f32_filter_th2(float thr, float e, float cnorm);
  * their results), out[2] = candidates written by the sweeps, out[3] = candidates that survived the exact recheck.
  * VS_ERR_INVALID when the index has no prefilter (see vs_bf_filter_image_read). */
 VS_API int vs_bf_filter_stats(vs_index* h, int64_t* out /* [4] */, int reset);
+/* On an index that also keeps a byte copy (every value an integer in [0, 255]), squared L2, a prefilter launch group is
+ * swept on the byte copy with int8 MFMA first (VSEARCH_F32_FILTER_I8=0: never), and the bf16 sweep, enqueued
+ * behind it, runs only when the device finds a batch of the group that is not byte valued.  vs_bf_filter_stats counts the
+ * prefilter whichever sweep answered (out[0]: one per launch group; out[1]: an overflow of either sweep; out[2], out[3]: the
+ * candidates of both, and its reset clears the counters of this call too); this call counts the int8 sweep's share: out[0] = launch groups enqueued on the int8 route, out[1] = of those, groups the device handed to
+ * the bf16 sweep, out[2] = candidates the int8 sweep wrote, out[3] = candidates that survived the exact recheck.  All zero
+ * on an index that never takes the route. */
+VS_API int vs_bf_filter_i8_stats(vs_index* h, int64_t* out /* [4] */, int reset);
+/* Whether a vs_bf_search_dev_multi launch group of n_batches batches (at most 32) at this k is enqueued on that route
+ * (host only): 1 on a byte-valued squared-L2 128-d index under vs_set_precision(h, 1) whose group takes the prefilter, at
+ * the launch sizes where the int8 sweep was measured faster than the bf16 sweep plus the idle launch behind it -- more than
+ * 8 batches, or at least 24 units of 64 rows per workgroup; VSEARCH_F32_FILTER_I8=2: at every size. */
+VS_API int vs_bf_filter_i8_plan(const vs_index* h, int n_batches, int k);
+/* The integer test of that sweep as the library computes it (vs_kernels.h, filter_i8_thr; pure host arithmetic): for a
+ * query with bound tau0 and term qterm = ||q||^2 - 256 sum(q - 128) - 2 * 128^3, a row with term rterm = ||b||^2 - 256 sum(b -
+ * 128) and dot = sum (q - 128)(b - 128):  out[0] = thr = qterm - ceil(tau0), out[1] = the hot test dot - (rterm >> 1) >
+ * floor(thr / 2), out[2] = the exact test 2 (dot - (rterm >> 1)) - (rterm & 1) > thr, i.e. d = qterm + rterm - 2 dot < tau0. */
+VS_API void vs_f32_filter_i8_test(float tau0, int32_t qterm, int32_t rterm, int32_t dot, int32_t* out /* [3] */);
 VS_API void vs_destroy(vs_index* h);
 
 #ifdef __cplusplus

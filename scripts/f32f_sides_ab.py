@@ -7,7 +7,8 @@ shard with HIP events.  Prints every repeat: the figures DESIGN 4.2b chooses the
     python3 scripts/f32f_sides_ab.py --sides "off:VSEARCH_F32F_PRIO=0 rule: on:VSEARCH_F32F_PRIO=4" \\
         [--repeats 3] [--rows 125000,250000,500000,1000000] [--batches 4,8,16,32]
 
-A side is name:KEY=VALUE[,KEY=VALUE...]; the key LIB names another build of the library.
+A side is name:KEY=VALUE[,KEY=VALUE...]; the key LIB names another build of the library.  The int8 sweep of a byte-valued
+shard (scan_f32f_i8_kernel) against the bf16 sweep alone: --sides "bf16:VSEARCH_F32_FILTER_I8=0 i8:VSEARCH_F32_FILTER_I8=2".
 """
 import argparse
 import json
