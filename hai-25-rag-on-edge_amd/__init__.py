@@ -227,6 +227,9 @@ def lib():
         "vs_index_nlist": (i32, [vp]),
         "vs_f32_filter_bound": (C.c_float, [C.c_double] * 6),
         "vs_bf_filter_image_read": (i32, [vp, i64, i64, vp]),
+        "vs_f32_filter_bound_nd": (C.c_float, [i32] + [C.c_double] * 6),
+        "vs_f32_filter_nd_th": (C.c_float, [i32] + [C.c_float] * 4 + [C.c_double] * 2),
+        "vs_bf_filter_nd_plan": (i32, [i64, i32, i32, i32, i32, vp]),
         "vs_f32_filter_cnorm": (C.c_float, [C.c_double]),
         "vs_f32_filter_th2": (C.c_float, [C.c_float] * 3),
         "vs_bf_filter_stats": (i32, [vp, C.POINTER(i64), i32]),
@@ -437,8 +440,9 @@ class BruteForceIndex(_Index):
         return self
 
     def filter_image(self, row0: int, n: int) -> np.ndarray:
-        """Rows [row0, row0 + n) of the prefilter's bf16 row image as uint16 [n, 128] (vs_bf_filter_image_read)."""
-        out = np.empty((n, 128), dtype=np.uint16)
+        """Rows [row0, row0 + n) of the prefilter's bf16 row image as uint16 [n, d rounded up to 32], in row order
+        (vs_bf_filter_image_read)."""
+        out = np.empty((n, (self.d + 31) // 32 * 32), dtype=np.uint16)
         _check(lib().vs_bf_filter_image_read(self._h, row0, n, _p(out)))
         return out
 
@@ -784,6 +788,19 @@ def i16_wide_plan(n_rows: int, k: int):
     out = (C.c_int64 * 3)()
     _check(lib().vs_i16_wide_plan(n_rows, k, out))
     return tuple(int(v) for v in out)
+
+
+def f32_filter_bound_nd(dim: int, eq: float, nq: float, nqp: float, bmax: float, emax: float, bpmax: float) -> float:
+    """The bf16 prefilter's error bound at any dimension (vs_f32_filter_bound_nd; host only)."""
+    return float(lib().vs_f32_filter_bound_nd(dim, eq, nq, nqp, bmax, emax, bpmax))
+
+
+def bf_filter_nd_plan(n_rows: int, dim: int, num_cus: int, n_batches: int, k: int):
+    """(takes the bf16 prefilter, workgroups per pass, passes, column blocks per wave, sample rows, sample stride) of a
+    launch group on a general fp32 index (vs_bf_filter_nd_plan; host only)."""
+    out = (C.c_int64 * 6)()
+    _check(lib().vs_bf_filter_nd_plan(n_rows, dim, num_cus, n_batches, k, out))
+    return tuple(int(x) for x in out)
 
 
 def ivf_one_plan(n_rows: int, dim: int, nlist: int, num_cus: int, n_batches: int, B: int, k: int, nprobe: int):

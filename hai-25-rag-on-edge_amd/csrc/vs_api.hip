@@ -129,6 +129,18 @@ struct vs_index {
     int64_t filter_launches = 0;
     int64_t filter_i8_groups = 0;  // launch groups enqueued on the int8 route
     vs::DevBuf<uint16_t> d_img;  // [n_rows + 64][128], spare rows zero
+    // ... and of a general index made by vs_bf_create_nd (build_nd_filter): the image in the unit / slab order of
+    // scan_nd_f32f_kernel in d_img (+ 2 dim32 bytes per row), fstats and filter_stats as above, the compact copy of the
+    // sample rows the bounds come from, and the prepared queries.  nd_filter: 0 = no image (VSEARCH_ND_FILTER=0, an ill-scaled
+    // shard, no memory), 1 = the launch groups of vs_bf_filter_nd_plan's rule, 2 = every group of >= 4 batches with k <= 15
+    int nd_filter = 0;
+    double nd_bnmax = 0.0;                 // the largest stored norm
+    int64_t nd_sample_rows = 0;
+    vs::DevBuf<float> d_nd_sample;         // [nd_sample_rows + 64][dim_p]
+    vs::DevBuf<float> d_nd_sample_norm;    // [nd_sample_rows + 64]
+    // (scratch of the index, like d_nd_qfrag: consecutive calls on one index must be stream-ordered)
+    vs::DevBuf<uint16_t> d_nd_qbf;         // [2 kMaxMulti][slabs][64][8]
+    vs::DevBuf<float> d_nd_qbound, d_nd_qnp;  // [kMaxMulti][32]
     // int8 data path: only when every base value is an integer in [0, 255]
     vs::DevBuf<int8_t> d_vecs_u8;   // [n_rows][128] bytes (x - 128)
     vs::DevBuf<int32_t> d_rterm;    // [n_rows + 64] ||b||^2 - 256 * sum(b - 128)
@@ -562,6 +574,73 @@ int build_u8_copy(vs_index* h, const float* host, int64_t rows, std::vector<int8
     return VS_OK;
 }
 
+// The bf16 prefilter of a general index made from fp32 rows: the row image, the shard constants and the
+// compact sample copy, in one pass at creation.  An accelerator, not a requirement: an ill-scaled shard, memory that
+// cannot be had or VSEARCH_ND_FILTER=0 (the comparison toggle) leave the index as it was.
+int build_nd_filter(vs_index* h) {
+    const char* env = getenv("VSEARCH_ND_FILTER");
+    const int mode = env ? atoi(env) : 1;
+    if (mode <= 0 || h->n_rows > 0x7fffffff - 2 * vs::kNdfUnitRows) return VS_OK;
+    auto give_up = [&]() {
+        (void)hipGetLastError();
+        vs::set_error("");
+        h->d_img.reset();
+        h->d_nd_sample.reset();
+        h->d_nd_sample_norm.reset();
+        h->d_nd_qbf.reset();
+        h->d_nd_qbound.reset();
+        h->d_nd_qnp.reset();
+        h->filter_stats.reset();
+        return VS_OK;
+    };
+    const size_t words = (size_t)vs::ndf_image_words(h->n_rows, h->dim_p);
+    int64_t srows, stride;
+    vs::ndf_sample(h->n_rows, &srows, &stride);
+    vs::DevBuf<unsigned long long> st;
+    if (st.alloc(5) != VS_OK || h->d_img.alloc(words) != VS_OK || h->filter_stats.alloc(8) != VS_OK ||
+        h->d_nd_sample.alloc(((size_t)srows + vs::kScanPadRows) * h->dim_p) != VS_OK || h->d_nd_sample_norm.alloc((size_t)srows + 64) != VS_OK ||
+        h->d_nd_qbf.alloc((size_t)kMaxMulti * 2 * vs::ndf_slabs(h->dim_p) * 512) != VS_OK || h->d_nd_qbound.alloc((size_t)kMaxMulti * 32) != VS_OK ||
+        h->d_nd_qnp.alloc((size_t)kMaxMulti * 32) != VS_OK)
+        return give_up();
+    HIPCHK(hipMemset(st, 0, 5 * sizeof(unsigned long long)));
+    HIPCHK(hipMemset(h->d_img, 0, words * sizeof(uint16_t)));
+    HIPCHK(hipMemset(h->filter_stats, 0, 8 * sizeof(unsigned long long)));
+    HIPCHK(hipMemset(h->d_nd_sample, 0, ((size_t)srows + vs::kScanPadRows) * h->dim_p * sizeof(float)));
+    HIPCHK(hipMemset(h->d_nd_sample_norm, 0, ((size_t)srows + 64) * sizeof(float)));
+    HIPCHK(vs::launch_nd_filter_image(h->d_vecs, h->d_norm, h->n_rows, h->dim_p, st, h->d_img, nullptr));
+    HIPCHK(vs::launch_nd_filter_sample(h->d_vecs, h->d_norm, srows, stride, h->dim_p, h->d_nd_sample, h->d_nd_sample_norm, nullptr));
+    unsigned long long v[5];
+    HIPCHK(hipMemcpy(v, st, sizeof(v), hipMemcpyDeviceToHost));
+    double m[3];
+    for (int i = 0; i < 3; ++i) memcpy(&m[i], &v[i], sizeof(double));
+    h->fstats.bmax = sqrt(m[0]);
+    h->fstats.emax = sqrt(m[1]);
+    h->fstats.bpmax = sqrt(m[2]);
+    memcpy(&h->nd_bnmax, &v[4], sizeof(double));
+    if (v[3] != 0 || !std::isfinite(m[0]) || !std::isfinite(m[2]) || !std::isfinite((float)h->nd_bnmax)) return give_up();
+    h->nd_sample_rows = srows;
+    h->nd_filter = mode >= 2 ? 2 : 1;
+    return VS_OK;
+}
+
+// Which launch groups of a general index take the bf16 prefilter (vs_bf_filter_nd_plan's rule; bf_launch goes through it):
+// 4 to kMaxMulti batches and k <= 15, at the dimensions and shard sizes where the route was MEASURED faster than the same
+// library under VSEARCH_ND_FILTER=0 by more than the spread of either leg (profiles/nd_filter_bench.txt).
+// Everything else is reachable only under VSEARCH_ND_FILTER=2 (`always`).  The route enqueues more launches than the
+// per-batch route at every nb (sample preparation and scan, bound merge, query preparation, sweep, then the idle fallback
+// preparation and scan, and the merge; against reset, preparation, scan and merge), so a small shard can only lose.
+// Measured slower, and so left out (384-d, 4 / 8 / 16 / 32 batches, us per call, route against toggle): 65 536 rows 665 / 1215 /
+// 2272 / 4550 against 592 / 1147 / 2253 / 4456; 262 144 rows 732 / 1303 / 2472 / 4857 against 636 / 1207 / 2385 / 4756; and at
+// 96-d on 262 144 rows 516 / 945 / 1796 / 3539 against 325 / 615 / 1212 / 2416.  The route carries about 0.5 ms per group that
+// does not depend on the shard (the sample's scan_nd_kernel: DESIGN 4.4f).
+constexpr int64_t kNdFilterMinRows = 1000000;  // measured faster from here (1.15 x at 96-d, 4 batches, the smallest gain) ...
+constexpr int64_t kNdFilterMaxRows = 3000000;  // ... to here (3.3 - 4.7 x at 384-d)
+constexpr int kNdFilterMinDim = 96, kNdFilterMaxDim = 1024;  // measured at 96, 128, 384, 768 and 1024
+bool nd_filter_route(int64_t n_rows, int dim, int nb, int k1, bool always) {
+    if (nb < 4 || nb > kMaxMulti || k1 < 2 || k1 > 16 || n_rows > 0x7fffffff - 2 * vs::kNdfUnitRows) return false;
+    return always || (n_rows >= kNdFilterMinRows && n_rows <= kNdFilterMaxRows && dim >= kNdFilterMinDim && dim <= kNdFilterMaxDim);
+}
+
 // byte copy of a general index made from uint8 rows: int8 (x - 128) rows padded to dim_b bytes, rterm = sum (b - 128)^2
 // over the real dim (dist = qterm + rterm - 2 q'.b', see vs_scan_nd_i8.hip), and max ||b||^2 for the exactness rule.
 // An inner-product brute-force index keeps rsum = sum (b - 128) per row instead of rterm (launch_ivf_nd_i8_rowsum).
@@ -884,9 +963,12 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     const int64_t tiles_total = (h->n_rows + vs::kTileRows - 1) / vs::kTileRows;
     // (a general index has no seed sample and no streaming scan: per-batch scan_nd_kernel + merge, with the threshold exchange)
     const bool seeded = !h->general && bf_seeded(h->n_rows, nb, k1);
+    // ... unless it has the bf16 image: a long call then takes its bounds from the sample rows, sweeps the
+    // image once for all batches and keeps the per-batch scan as the fallback behind the overflow word
+    const bool nd_filter = h->general && h->nd_filter && !nd_u8_path(h, force_f32) && nd_filter_route(h->n_rows, h->dim, nb, k1, h->nd_filter == 2);
     int grid, tp;
-    scan_geometry(h->n_rows, h->num_cus, grid, tp, seeded ? 0 : (u8_path ? 16 : 6) * vs::kScanWaves);
-    const bool exchange = !seeded && grid >= 16 && tp >= (u8_path ? 16 : 6) * vs::kScanWaves && g_xchg_first_it >= 0;
+    scan_geometry(h->n_rows, h->num_cus, grid, tp, seeded || nd_filter ? 0 : (u8_path ? 16 : 6) * vs::kScanWaves);
+    const bool exchange = !seeded && !nd_filter && grid >= 16 && tp >= (u8_path ? 16 : 6) * vs::kScanWaves && g_xchg_first_it >= 0;
     const bool use_u8 = u8_path;
     // With the bounds known up front the batches need nothing from each other: the streaming scans (fp32: one batch per
     // pass; exact int8 rows: several batches per pass over the rows) hand out the tiles of ALL batches through one
@@ -949,7 +1031,7 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
         }
         return VS_OK;
     }
-    if (seeded || use_u8) {
+    if (seeded || use_u8 || nd_filter) {
         int rc = ensure_wide(L);
         if (rc) return rc;
     }
@@ -957,8 +1039,8 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     int32_t* const overflow = L.wide8.wcnt;
     int32_t* const invalid = L.wide8.wcnt ? L.wide8.wcnt + 16 : nullptr;
     // (cleared by the seed's query-preparation launch where there is one and nobody else writes the batches' verdict words)
-    const size_t zero_words = 64 + (stream ? (size_t)nb * 32 * kWideSub : 0);
-    const bool zero_in_seed = seeded && (!use_u8 || i8_seed);
+    const size_t zero_words = 64 + (stream || nd_filter ? (size_t)nb * 32 * kWideSub : 0);
+    const bool zero_in_seed = (seeded && (!use_u8 || i8_seed)) || nd_filter;  // (nd_filter: its query preparation clears them)
     if (L.wide8.wcnt && !zero_in_seed) HIPCHK(hipMemsetAsync(L.wide8.wcnt, 0, zero_words * sizeof(int32_t), s));
     if (seeded) {
         vs::SeedParams sp{};
@@ -1014,6 +1096,85 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     m.q_group_out = B;
     m.q_group_in = vs::kMaxBatch;
     m.invalid = use_u8 ? invalid : nullptr;
+    if (nd_filter) {
+        const vs::NdFilterPlan g = vs::ndf_plan(h->n_rows, h->num_cus, nb);
+        // bounds: scan_nd_kernel's own top-k on the compact sample copy (exact distances of k1 distinct rows), ranked by
+        // one merge launch into tau0 = next_up(k1-th best) for all 32 query slots of every batch
+        vs::ScanNdParams sn{};
+        sn.s = p;
+        sn.s.base = h->d_nd_sample;
+        sn.s.bnorm = h->d_nd_sample_norm;
+        sn.s.row_begin = 0;
+        sn.s.row_end = h->nd_sample_rows;
+        sn.s.id_offset = 0;
+        sn.s.part_d = L.part_d;
+        sn.s.part_i = L.part_i;
+        sn.dim = h->dim;
+        sn.dim_p = h->dim_p;
+        sn.qfrag = h->d_nd_qfrag;
+        sn.qnorm = h->d_nd_qnorm;
+        int sgrid, stp;
+        scan_geometry(h->nd_sample_rows, h->num_cus, sgrid, stp);
+        sn.s.tiles_per_wg = stp;
+        prof_begin(h, 0, s);
+        HIPCHK(vs::launch_scan_nd(sn, sgrid, kcap, 2, vs::kModeTopK, s));
+        vs::MergeParams mt{};
+        mt.part_d = L.part_d;
+        mt.part_i = L.part_i;
+        mt.G = sgrid;
+        mt.kin = kcap;
+        mt.nq = nb * vs::kMaxBatch;
+        mt.kout = k1;
+        mt.tau_out = L.tau0;
+        HIPCHK(vs::launch_merge_layout(mt, kcap, (int64_t)vs::kSlotStride * kcap, s));
+        p.tau0 = L.tau0;
+        vs::NdFilterParams fp{};
+        fp.img = h->d_img;
+        fp.base = h->d_vecs;
+        fp.bnorm = h->d_norm;
+        fp.n_rows = h->n_rows;
+        fp.dim = h->dim;
+        fp.dim_p = h->dim_p;
+        fp.slabs = vs::ndf_slabs(h->dim_p);
+        fp.q = q_dev;
+        fp.q_batch_stride = (int64_t)B * h->dim;
+        fp.qfrag = h->d_nd_qfrag;
+        fp.qnorm = h->d_nd_qnorm;
+        fp.tau0 = L.tau0;
+        fp.qbf = h->d_nd_qbf;
+        fp.qbound = h->d_nd_qbound;
+        fp.qnp = h->d_nd_qnp;
+        fp.zero = L.wide8.wcnt;
+        fp.zero_words = (int)zero_words;
+        fp.n_batches = nb;
+        fp.nq_valid = B;
+        fp.metric = h->metric;
+        fp.id_offset = (int32_t)h->id_offset;
+        fp.fstats = h->fstats;
+        fp.bnmax = h->nd_bnmax;
+        fp.sink.wbuf = L.wide8.wbuf;
+        // (the buffers are allocated for 256 workgroups: a launch of fewer waves -- a small shard -- shares them out)
+        fp.sink.wcap = (int)((int64_t)kWideWaveCap * vs::kSlotStride / ((int64_t)g.grid * g.passes));
+        fp.sink.overflow = overflow;
+        fp.sink.cnt = L.wide8.wcnt + 64;
+        fp.sink.cand_d = L.wide8.wcand_d;
+        fp.sink.cand_i = L.wide8.wcand_i;
+        fp.sink.cap = kWideCap;
+        fp.sink.nsub = kWideSub;
+        fp.sink.stats = h->filter_stats;
+        ++h->filter_launches;
+        HIPCHK(vs::launch_scan_nd_f32f(fp, g, s));
+        prof_end(h, 0, s);
+    }
+    const bool lists = stream || nd_filter;  // the scan's candidate lists are ranked, the per-batch scan is the fallback
+    if (lists) {
+        m.G = kWideSub;
+        m.kin = kWideCap;
+        m.flat_len = L.wide8.wcnt + 64;
+        m.run_if = overflow;
+        m.run_mode = 3;
+        p.run_if = overflow;
+    }
     if (stream) {
         vs::CandSink sink{};
         sink.wbuf = L.wide8.wbuf;
@@ -1115,11 +1276,11 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
         p.invalid = h->d_invalid;
         m.invalid = h->d_invalid;
     }
-    if (!stream) prof_begin(h, 0, s);
+    if (!lists) prof_begin(h, 0, s);
     HIPCHK(scan_any(h, p, grid, kcap, nqh, vs::kModeTopK, s));
-    if (!stream) prof_end(h, 0, s);
+    if (!lists) prof_end(h, 0, s);
     // one merge launch ranks every (batch, query): lists are [batch*32 + q][workgroup][kcap]
-    if (stream) {  // ... or, unless the streaming scan overflowed, its candidate lists [batch*32 + q][kWideSub][kWideCap]
+    if (lists) {  // ... or, unless the streaming scan overflowed, its candidate lists [batch*32 + q][kWideSub][kWideCap]
         m.part_d = L.wide8.wcand_d;
         m.part_i = L.wide8.wcand_i;
         m.alt_part_d = L.part_d;
@@ -2381,7 +2542,62 @@ int vs_index_dim(const vs_index* h) { return h ? h->dim : 0; }
 float vs_f32_filter_bound(double eq, double nq, double nqp, double bmax, double emax, double bpmax) {
     return vs::filter_bound(eq, nq, nqp, vs::FilterStats{bmax, emax, bpmax});
 }
+float vs_f32_filter_bound_nd(int dim, double eq, double nq, double nqp, double bmax, double emax, double bpmax) {
+    return vs::filter_bound_nd(dim, eq, nq, nqp, vs::FilterStats{bmax, emax, bpmax});
+}
+float vs_f32_filter_nd_th(int metric, float tau, float qn, float e, float nqp, double bnmax, double bpmax) {
+    return vs::filter_nd_th(metric, tau, qn, e, nqp, bnmax, bpmax);
+}
+int vs_bf_filter_nd_plan(int64_t n_rows, int dim, int num_cus, int n_batches, int k, int64_t* out) {
+    if (!out) {
+        set_error("vs_bf_filter_nd_plan: no output");
+        return VS_ERR_INVALID;
+    }
+    for (int i = 0; i < 6; ++i) out[i] = 0;
+    if (n_rows < 1 || num_cus < 1 || n_batches < 1 || k < 1) {
+        set_error("vs_bf_filter_nd_plan: n_rows, num_cus, n_batches and k must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (dim < 1) {
+        set_error("vs_bf_filter_nd_plan: dim must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (dim > vs::kNdMaxDim) {
+        set_error("vs_bf_filter_nd_plan: dim > 2048 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (!nd_filter_route(n_rows, dim, n_batches, k + 1, false)) return VS_OK;
+    const vs::NdFilterPlan g = vs::ndf_plan(n_rows, num_cus, n_batches);
+    out[0] = 1;
+    out[1] = g.grid;
+    out[2] = g.passes;
+    out[3] = g.cbw;
+    out[4] = g.sample_rows;
+    out[5] = g.sample_stride;
+    return VS_OK;
+}
+// a general index: the image is kept in unit / slab / fragment order (vs_scan_nd_f32f.hip) and returned in row order
+static int nd_filter_image_read(const vs_index* h, int64_t row0, int64_t n, uint16_t* dst) {
+    const int S = vs::ndf_slabs(h->dim_p), d32 = 32 * S;
+    if (row0 < 0 || n < 0 || row0 + n > h->n_rows + vs::kScanPadRows || row0 + n > ((h->n_rows + 63) / 64 + 1) * 64) {
+        set_error("vs_bf_filter_image_read: rows out of range");
+        return VS_ERR_INVALID;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<uint16_t> unit((size_t)S * 2048);
+    for (int64_t u = row0 / 64; u * 64 < row0 + n; ++u) {
+        HIPCHK(hipMemcpy(unit.data(), h->d_img + (size_t)u * S * 2048, unit.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        for (int64_t row = std::max(row0, u * 64); row < std::min(row0 + n, (u + 1) * 64); ++row) {
+            const int rr = (int)(row - u * 64), t = rr >> 4, r = rr & 15;
+            for (int k = 0; k < d32; ++k)
+                dst[(size_t)(row - row0) * d32 + k] = unit[(((size_t)(k >> 5) * 4 + t) * 64 + 16 * ((k >> 3) & 3) + r) * 8 + (k & 7)];
+        }
+    }
+    return VS_OK;
+}
 int vs_bf_filter_image_read(const vs_index* h, int64_t row0, int64_t n, uint16_t* dst) {
+    if (h && dst && h->general && h->nd_filter && h->d_img) return nd_filter_image_read(h, row0, n, dst);
     if (!h || !dst || !h->filter_ok || !h->d_img || row0 < 0 || n < 0 || row0 + n > h->n_rows + vs::kScanPadRows) {
         set_error("vs_bf_filter_image_read: no image or rows out of range");
         return VS_ERR_INVALID;
@@ -2394,7 +2610,7 @@ int vs_bf_filter_image_read(const vs_index* h, int64_t row0, int64_t n, uint16_t
 float vs_f32_filter_cnorm(double bnmax) { return vs::filter_cnorm(bnmax); }
 float vs_f32_filter_th2(float thr, float e, float cnorm) { return vs::filter_th2(thr, e, cnorm); }
 int vs_bf_filter_stats(vs_index* h, int64_t* out, int reset) {
-    if (!h || !out || !h->filter_ok || !h->filter_stats) {
+    if (!h || !out || !(h->filter_ok || h->nd_filter) || !h->filter_stats) {
         set_error("vs_bf_filter_stats: an index with the bf16 prefilter and an output of four words");
         return VS_ERR_INVALID;
     }
@@ -2717,6 +2933,9 @@ static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int m
                 vs_destroy(h);
                 return rc;
             }
+        } else if ((rc = build_nd_filter(h))) {  // fp32 rows: the bf16 image for long calls
+            vs_destroy(h);
+            return rc;
         }
         *out = h;
         return VS_OK;

@@ -184,6 +184,104 @@ __host__ __device__ inline float filter_th2(float thr, float e, float cn) {  // 
     return (b << 1) == 0 ? -1.401298464324817e-45f : __builtin_bit_cast(float, f > 0.f ? b - 1 : b + 1);
 }
 
+// ---- the same prefilter on the fp32 rows of a general index (vs_scan_nd_f32f.hip) ----
+// filter_bound at any dimension: g32(n) = n u / (1 - n u), u = 2^-24, n = dim_p, the fp32 chain length of scan_nd_kernel (one
+// rounding per fmaf; the zero padding adds exact zeros but is counted); g16(m) the same form with u = 2^-22 under the
+// accumulation assumption above, m = dim rounded up to 32, the terms scan_nd_f32f_kernel's bf16 chain adds (the row norm
+// does not ride in the C operand there).  At dim = 128 both are filter_bound's constants and the value is filter_bound's.
+__host__ __device__ inline float filter_bound_nd(int dim, double eq, double nq, double nqp, const FilterStats& f) {
+    const double n32 = (double)((dim + 15) & ~15) / 16777216.0, n16 = (double)((dim + 31) & ~31) / 4194304.0;
+    const double g32 = n32 / (1.0 - n32), g16 = n16 / (1.0 - n16);
+    const double nb = f.bmax > f.bpmax ? f.bmax : f.bpmax, nqm = nq > nqp ? nq : nqp;
+    const double e = eq * f.bmax + nqp * f.emax + (g32 + g16) * nqm * nb + 7.888609052210118e-31;  // + 2^-100
+    return (float)(e * (1.0 + 1.0 / 1048576.0));
+}
+// The hot test of scan_nd_f32f_kernel is v > th with v = RN(2 S' - bn) (one fmaf; bn the STORED fp32 norm) under squared
+// L2 and v = S' under inner product, S' the bf16 MFMA sum.  Claim: every (row, query) whose exact distance -- scan_nd_kernel's
+// d = RN(c - 2 S_fl), c = RN(qn + bn), or d = -S_fl -- is < tau passes.  Proof (L2): tau is a float and RN is monotone,
+// so d < tau gives c - 2 S_fl < tau in the reals.  c >= (qn + bn)(1 - u), u = 2^-24 (both norms are non-negative), hence
+// 2 S_fl - bn > qn - tau - u (qn + bn).  |S_fl - S'| <= E = filter_bound_nd, so 2 S' - bn > qn - tau - u (qn + bnmax) - 2 E,
+// bnmax the shard's largest stored norm.  The fmaf rounds once: v >= (2 S' - bn) - u |2 S' - bn|, and |2 S' - bn| <= 2 |S'| +
+// bn <= 2.02 ||q'|| ||b'||max + bnmax (Cauchy-Schwarz on the exact bf16 products; the accumulation error is below 1 % of
+// that at m <= 2048).  So v > X := qn - tau - 2 E - u (qn + 2 bnmax + 2.02 ||q'|| bpmax).  th is X rounded DOWN: in double
+// every product is exact or rounds by 2^-53, the sum of five terms by at most 4 * 2^-53 of the sum of magnitudes, which
+// the 2^-50 term covers; the cast rounds to nearest (at most half an ulp up) and the step to the next float below takes
+// at least that back.  Inner product: d = -S_fl < tau gives S_fl > -tau and S' > -tau - E =: X.  E = +inf (a query outside
+// the well-scaled range), a non-finite norm or tau = +inf gives -inf: every row passes, the launch overflows and the
+// per-batch scan behind answers.  A NaN bound admits nothing under the exact test either, and nothing here.  The test is
+// the strict v > th: a v that the fmaf overflows to -inf, or a NaN v (inf - inf), does not pass even th = -inf.  That
+// needs |2 S'| or bn at the float range's end, where c - 2 S_fl is +inf or NaN as well, so the exact distance is not
+// < tau for any tau either (+inf included): nothing that the exact test admits is lost.
+__host__ __device__ inline float filter_nd_th(int metric, float tau, float qn, float e, float nqp, double bnmax, double bpmax) {
+    const float inf = __builtin_inff();
+    if (!(e < inf) || !(qn < inf) || !(nqp < inf) || tau == inf) return -inf;
+    if (!(tau > -inf)) return inf;
+    double x, mag;
+    if (metric) {
+        x = -(double)tau - (double)e;
+        mag = __builtin_fabs((double)tau) + (double)e;
+    } else {
+        const double r = (double)qn + 2.0 * bnmax + 2.02 * (double)nqp * bpmax;
+        x = (double)qn - (double)tau - 2.0 * (double)e - r / 16777216.0;
+        mag = (double)qn + __builtin_fabs((double)tau) + 2.0 * (double)e + r / 16777216.0;
+    }
+    const float f = (float)(x - 8.881784197001252e-16 * mag);  // 2^-50
+    if (!(f > -inf)) return -inf;                               // (overflow downwards, or NaN: let everything pass)
+    if (f == inf) return 3.4028234663852886e38f;
+    const unsigned b = __builtin_bit_cast(unsigned, f);
+    return (b << 1) == 0 ? -1.401298464324817e-45f : __builtin_bit_cast(float, f > 0.f ? b - 1 : b + 1);
+}
+constexpr int kNdfUnitRows = 64;  // rows per unit of the image: four 16-row tiles (<= kScanPadRows: one spare unit)
+constexpr int ndf_slabs(int dim_p) { return (dim_p + 31) / 32; }  // 32-element K slabs of a row
+// bf16 elements of the image of n_rows rows: whole units, one spare unit
+constexpr int64_t ndf_image_words(int64_t n_rows, int dim_p) { return ((n_rows + 63) / 64 + 1) * ndf_slabs(dim_p) * 2048; }
+// shard constants and the image (layout: vs_scan_nd_f32f.hip): out[0..4] as launch_row_filter_image, zeroed before; the
+// caller zeroes the image first (ragged last unit, spare unit)
+hipError_t launch_nd_filter_image(const float* v, const float* bnorm, int64_t rows, int dim_p, unsigned long long* out, uint16_t* img,
+                                  hipStream_t s);
+// rows i * stride, i < n, of v ([..][dim_p]) and their norms into the compact sample copy
+hipError_t launch_nd_filter_sample(const float* v, const float* bnorm, int64_t n, int64_t stride, int dim_p, float* out, float* out_norm,
+                                   hipStream_t s);
+// Geometry of a launch group (host): workgroups per pass, passes over the image, column blocks per wave, sample rows
+struct NdFilterPlan {
+    int grid, passes, cbw;
+    int64_t sample_rows, sample_stride;
+};
+// The sample the bounds come from: row i * stride, i < rows, strided so that bases whose similar rows sit together are
+// sampled evenly.  tau0 = next_up of the k1-th best distance of the sample (scan_nd_kernel's own top-k on the compact
+// copy: exact values of k1 distinct rows), so about k1 * stride rows per query are expected under it, and the sweep
+// writes about 1.4 times that (measured).  The stride, not the sample, is bounded: a sixteenth of the shard (at least 256
+// rows) up to 524 288 rows, 32 768 rows from there to 1 M, a thirty-second of the shard beyond -- stride <= kNdfMaxStride at
+// every size, so that the candidates do not grow with the shard.  Against the sinks' capacities at k1 = 16: kept <= 512
+// and written ~ 720 per query of 2048 (16 hashed sub-lists of 128: 45 expected in each); 1024 queries write ~ 740 K
+// entries of the wave buffers' 2 M (~ 360 of 1024 per wave).  (The sample scan reads a thirty-second of the rows at most,
+// but runs latency bound, one 64-row block per wave and batch after batch: measured 5.8 ms of a 32-batch group's 8.5 ms at
+// 768-d -- DESIGN 4.4f.)
+constexpr int kNdfMaxStride = 32;
+inline void ndf_sample(int64_t n_rows, int64_t* rows, int64_t* stride) {
+    int64_t s = n_rows / 16;
+    s = s < 256 ? 256 : s > 32768 ? 32768 : s;
+    if (n_rows / s > kNdfMaxStride) s = (n_rows + kNdfMaxStride - 1) / kNdfMaxStride;
+    if (s > n_rows) s = n_rows;
+    *rows = s;
+    *stride = s > 0 ? n_rows / s : 1;
+}
+inline NdFilterPlan ndf_plan(int64_t n_rows, int num_cus, int n_batches) {
+    NdFilterPlan g{};
+    const int n_cb = 2 * n_batches;
+    g.passes = (n_cb + 31) / 32;
+    const int per_pass = (n_cb + g.passes - 1) / g.passes;
+    g.cbw = (per_pass + 7) / 8;
+    g.passes = (n_cb + 8 * g.cbw - 1) / (8 * g.cbw);
+    const int64_t units = (n_rows + kNdfUnitRows - 1) / kNdfUnitRows;
+    int64_t wg = num_cus < kSlotStride ? num_cus : kSlotStride;
+    wg = wg / g.passes;
+    g.grid = (int)(wg < 1 ? 1 : wg > units ? units : wg);
+    ndf_sample(n_rows, &g.sample_rows, &g.sample_stride);
+    return g;
+}
+// (NdFilterParams and launch_scan_nd_f32f: behind CandSink, below)
+
 // Bounds for a multi-batch scan, computed up front on a sample of the rows: kSeedWaves 16-row tiles spread evenly
 // over the shard, scored against every batch; tau0[batch][q] = next_up of the k1-th smallest of 64 group minima
 // (groups of 32 tiles) -- an upper bound of the k1-th best distance, because k1 distinct rows are at least that
@@ -271,6 +369,32 @@ struct CandSink {
     int xcd_subs;
     int cnt_sub_stride;
 };
+
+// the bf16 prefilter of a general index (above)
+struct NdFilterParams {
+    const uint16_t* img;     // the rows' bf16 image
+    const float* base;       // [n_rows + 64][dim_p] fp32 rows (the recheck only)
+    const float* bnorm;      // [n_rows + 64]
+    int64_t n_rows;
+    int dim, dim_p, slabs;
+    const float* q;          // [n_batches][nq_valid][dim] raw queries
+    int64_t q_batch_stride;
+    const float* qfrag;      // ScanNdParams::qfrag / qnorm of these queries, written earlier in the stream (nd_prep_kernel)
+    const float* qnorm;
+    const float* tau0;       // [n_batches][32]
+    uint16_t* qbf;           // scratch [2 n_batches][slabs][64][8] bf16 B fragments
+    float* qbound;           // scratch [n_batches][32] E per query (+inf: not well scaled, 0: padding)
+    float* qnp;              // scratch [n_batches][32] ||q'||, rounded up
+    int32_t* zero;           // zero_words words cleared by the preparation launch (overflow word, list counters)
+    int zero_words;
+    int n_batches, nq_valid, metric;
+    int32_t id_offset;
+    FilterStats fstats;
+    double bnmax;            // the shard's largest stored norm
+    CandSink sink;
+};
+// the preparation launch and the sweep
+hipError_t launch_scan_nd_f32f(const NdFilterParams& p, const NdFilterPlan& g, hipStream_t s);
 
 struct WideParams {
     const int8_t* base_u8;   // [n_rows (+64)][128] bytes (x - 128)

@@ -131,6 +131,10 @@ VS_API int vs_bf_create(const float* base_host, int64_t n_rows, int dim, int met
  * sharded calls (vs_bf_search_dev_sharded, vs_bf_search_sharded, vs_bf_search_vshards) and
  * every vs_ivf_* call return VS_ERR_UNSUPPORTED on a general index made by this creator (an IVF
  * index at other dimensions comes from vs_ivf_create / vs_ivf_load; a q8 runner from vs_q8_create_nd). */
+/* Such an index also keeps its rows as bf16, once more, for long calls: device memory is about 1.5 x that
+ * of the fp32 rows alone (2 bytes per element of the row padded to 32, on top of 4).  No image is kept for rows outside
+ * the well-scaled range (a non-finite value, or a non-zero magnitude outside [2^-60, 2^60]), when the memory cannot be had,
+ * or under VSEARCH_ND_FILTER=0 in the environment at creation; the index then answers every call as it did without it. */
 VS_API int vs_bf_create_nd(const float* base_host, int64_t n_rows, int dim, int metric,
                            int device, int64_t id_offset, vs_index** out);
 
@@ -352,6 +356,8 @@ VS_API int vs_bf_search_dev(vs_index* h, const float* queries_dev, int B, int k,
  * distances +inf), and every other batch of the same call is unaffected -- its lists and
  * flags are what a call without the skipped batches returns, so only the flagged batches
  * need the rerun under vs_set_precision(h, 1). */
+/* On a general index made by vs_bf_create_nd, a launch group of 4 to 32 batches with k <= 15 takes the bf16 prefilter
+ * (vs_bf_filter_nd_plan): same ids, distance bits and flags, less time. */
 VS_API int vs_bf_search_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k,
                                   int32_t* ids_dev, float* dists_dev, int32_t* flags_dev, void* stream);
 
@@ -1075,6 +1081,29 @@ VS_API float vs_f32_filter_bound(double eq, double nq, double nqp, double bmax, 
  * VS_ERR_INVALID when the index has no image (not a 128-d brute-force index, too small for the prefilter, ill-scaled
  * rows, VSEARCH_F32_FILTER=0) or the range leaves it. */
 VS_API int vs_bf_filter_image_read(const vs_index* h, int64_t row0, int64_t n, uint16_t* dst);
+/* ... and at any dimension.  vs_f32_filter_bound_nd: E for the prefilter of a general index of dimension dim
+ * (fp32 chain of dim rounded up to 16 steps, bf16 chain of dim rounded up to 32 terms); at dim = 128 exactly
+ * vs_f32_filter_bound's value.  vs_f32_filter_nd_th: the bound th of that sweep's hot test v > th (v = RN(2 bf16 dot - norm)
+ * under squared L2, the bf16 dot under inner product) for a query with bound tau, stored squared norm qn, E = e and
+ * ||bf16(q)|| = nqp on a shard whose largest stored squared norm is bnmax and max ||bf16(b)|| = bpmax, rounded down.
+ * On such an index vs_bf_filter_image_read returns rows of dim rounded up to 32 uint16 in row order (padding zero),
+ * whatever the device layout, and vs_bf_filter_stats counts its launch groups with the same four meanings.
+ * Pure host arithmetic. */
+VS_API float vs_f32_filter_bound_nd(int dim, double eq, double nq, double nqp, double bmax, double emax, double bpmax);
+VS_API float vs_f32_filter_nd_th(int metric, float tau, float qn, float e, float nqp, double bnmax, double bpmax);
+/* Whether a vs_bf_search_dev_multi launch group of n_batches batches at this k on a vs_bf_create_nd index of n_rows rows
+ * takes the bf16 prefilter, and its geometry (host only; the launch code decides through it): out[0] = 1 or 0, out[1] =
+ * workgroups per pass, out[2] = passes over the image (1 up to 16 batches, 2 above), out[3] = column blocks per wave
+ * (8 waves x out[3] x out[2] >= 2 n_batches), out[4] = sample rows the bounds come from, out[5] = their stride (<= 32 at
+ * every size, so the candidates per query, about (k + 1) x stride, do not grow with the shard).  The rule holds the shapes
+ * that were measured faster than the same library under VSEARCH_ND_FILTER=0 by more than the spread of either leg
+ * (profiles/nd_filter_bench.txt): 4 <= n_batches <= 32, k <= 15, 96 <= dim <= 1024, 1 000 000 <= n_rows <= 3 000 000.  Left
+ * out as measured slower: n_rows = 65 536 and 262 144 (384-d, 4 batches: 665 and 732 us against 592 and 636 us; every
+ * number in DESIGN 4.4f); left out as not measured: every other dimension and larger shards.  The route enqueues eight launches against the per-batch route's
+ * four, so small shards can only lose.  VSEARCH_ND_FILTER=2 at creation sends every group of 4 to 32 batches with k <= 15
+ * there whatever dim and n_rows (tests, benchmark); 0 builds no image.  num_cus takes the place vs_bf_one_plan gives it.
+ * Argument checks and their order: vs_bf_one_plan's. */
+VS_API int vs_bf_filter_nd_plan(int64_t n_rows, int dim, int num_cus, int n_batches, int k, int64_t* out /* [6] */);
 /* The L2 test of the prefilter carries the row norm through the MFMA's C operand: a value S'' = bf16 dot -
  * norm / 2 passes when it is above th2.  vs_f32_filter_cnorm: the shard constant C of that test from the shard's largest
  * stored fp32 norm.  vs_f32_filter_th2: the bound th2 from the exact scan's hot-test bound thr (a row passes the exact
