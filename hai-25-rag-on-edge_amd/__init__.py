@@ -236,6 +236,7 @@ def lib():
         "vs_bf_filter_i8_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_bf_filter_i8_plan": (i32, [vp, i32, i32]),
         "vs_f32_filter_i8_test": (None, [C.c_float, i32, i32, i32, C.POINTER(i32)]),
+        "vs_f32_filter_i8_dist": (C.c_float, [i32, i32, i32]),
         "vs_destroy": (None, [vp]),
     }
     for name, (res, args) in sig.items():
@@ -455,7 +456,8 @@ class BruteForceIndex(_Index):
 
     def filter_i8_stats(self, reset: bool = False):
         """(launch groups enqueued on the int8 prefilter route, groups the device handed to the bf16 sweep, candidates the
-        int8 sweep wrote, candidates that survived the exact recheck) since the last reset (vs_bf_filter_i8_stats)."""
+        int8 sweep wrote, candidates it binned: the same number, its entries are final) since the last reset
+        (vs_bf_filter_i8_stats)."""
         out = (C.c_int64 * 4)()
         _check(lib().vs_bf_filter_i8_stats(self._h, out, 1 if reset else 0))
         return tuple(int(x) for x in out)
@@ -793,6 +795,11 @@ def i16_wide_plan(n_rows: int, k: int):
 def f32_filter_bound_nd(dim: int, eq: float, nq: float, nqp: float, bmax: float, emax: float, bpmax: float) -> float:
     """The bf16 prefilter's error bound at any dimension (vs_f32_filter_bound_nd; host only)."""
     return float(lib().vs_f32_filter_bound_nd(dim, eq, nq, nqp, bmax, emax, bpmax))
+
+
+def f32_filter_i8_dist(qterm: int, rterm: int, dot: int) -> float:
+    """The distance the int8 prefilter sweep writes for a pair (vs_f32_filter_i8_dist; host only)."""
+    return float(lib().vs_f32_filter_i8_dist(int(qterm), int(rterm), int(dot)))
 
 
 def bf_filter_nd_plan(n_rows: int, dim: int, num_cus: int, n_batches: int, k: int):

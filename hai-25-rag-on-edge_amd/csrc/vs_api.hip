@@ -776,6 +776,13 @@ int g_f32_filter_i8 = [] {
     return e ? atoi(e) : 1;
 }();
 
+// comparison toggle (VSEARCH_F32_FILTER_I8_RECHECK=1): the int8 sweep recomputes every entry from the fp32 rows before it
+// bins it, as the bf16 sweep must (default 0: the integer distance is the fp32 distance and is binned as it stands)
+int g_f32_filter_i8_recheck = [] {
+    const char* e = getenv("VSEARCH_F32_FILTER_I8_RECHECK");
+    return e && atoi(e) ? 1 : 0;
+}();
+
 // comparison toggle (VSEARCH_F32F_WAVES=8 or 4): scan_f32f_kernel runs as one 8-wave workgroup per CU, or as two 4-wave
 // workgroups per CU, at every launch size (default unset: the measured choice per launch size, launch_scan_f32_stream)
 int g_f32f_waves = [] {
@@ -1243,6 +1250,7 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
                     sp.qterm = L.wide8.qterm;
                     sp.invalid = invalid;
                     sp.i8_stats = h->filter_stats + 4;
+                    sp.i8_recheck = g_f32_filter_i8_recheck;
                     ++h->filter_i8_groups;
                 }
             }
@@ -2662,6 +2670,7 @@ void vs_f32_filter_i8_test(float tau0, int32_t qterm, int32_t rterm, int32_t dot
     out[1] = vs::filter_i8_hot(a, thr) ? 1 : 0;
     out[2] = vs::filter_i8_exact(a, rterm, thr) ? 1 : 0;
 }
+float vs_f32_filter_i8_dist(int32_t qterm, int32_t rterm, int32_t dot) { return vs::filter_i8_dist(qterm, rterm, dot); }
 int vs_index_nlist(const vs_index* h) { return h ? h->nlist : 0; }
 void vs_destroy(vs_index* h) {
     if (!h) return;

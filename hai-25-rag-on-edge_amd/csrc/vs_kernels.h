@@ -446,7 +446,8 @@ struct StreamParams {
     const int8_t* q8frag;    // SeedParams::q8frag
     const int32_t* qterm;    // [n_batches][32]
     const int32_t* invalid;  // [n_batches]
-    unsigned long long* i8_stats;  // optional (vs_bf_filter_i8_stats): [1] += 1 per group handed to the bf16 sweep, [2] += candidates written, [3] += candidates kept
+    unsigned long long* i8_stats;  // optional (vs_bf_filter_i8_stats): [1] += 1 per group handed to the bf16 sweep, [2] += candidates written, [3] += candidates binned (the same number: the sweep's entries are final)
+    int i8_recheck;          // comparison toggle (VSEARCH_F32_FILTER_I8_RECHECK=1): the byte sweep recomputes its entries from the fp32 rows (RecheckF32) before it bins them
 };
 
 // The integer test of scan_f32f_i8_kernel, with acc = sum (q - 128)(b - 128), qt = SeedParams::qterm and
@@ -456,6 +457,13 @@ struct StreamParams {
 // thr >> 1 = floor(thr / 2):  2 A - ro > thr gives 2 A > thr, so A > thr / 2 >= floor(thr / 2) -- it admits every pair under
 // the bound, and for an odd thr and ro = 1 also the pairs with 2 A - 1 = thr, which the exact test (rare path) drops.
 // tau0 is clamped to +-2^26 first: distances are below 2^24, so +inf admits every row and -inf (or NaN) none.
+// The sweep's entry is final (no fp32 recheck behind it).  For a byte-valued pair scan_f32s_kernel computes dot = sum q b
+// <= 128 * 255^2 = 8 323 200 < 2^24 by fmaf over integers (exact in any order), qn and bn as sums of integer squares
+// <= 8 323 200 (exact), qn + bn <= 16 646 400 < 2^24 = 16 777 216 (exact) and d = fmaf(-2, dot, qn + bn), one rounding of
+// an exact integer below 2^24: the integer d above, as a float (filter_i8_dist; +0.0 for d = 0 on both sides).  It keeps
+// the row iff fmaf(-2, dot, bn) < stream_l2_thr(tau0, qn) && d < tau0, where d < tau0 implies the first test
+// (stream_l2_thr, vs_f32f.h): keep <=> d < tau0 <=> filter_i8_exact.  A NaN bound keeps nothing and +-inf everything /
+// nothing on both sides (the clamp).
 __host__ __device__ inline int32_t filter_i8_thr(float tau0, int32_t qt) {
     const float t = tau0 > -67108864.f ? (tau0 < 67108864.f ? tau0 : 67108864.f) : -67108864.f;  // (NaN -> -2^26)
     return qt - (int32_t)__builtin_ceilf(t);
@@ -473,6 +481,8 @@ inline bool filter_i8_pays(int64_t n_rows, int n_batches, int grid) {
 __host__ __device__ inline int32_t filter_i8_c0(int32_t rt) { return -(rt >> 1); }
 __host__ __device__ inline bool filter_i8_hot(int32_t a, int32_t thr) { return a > (thr >> 1); }
 __host__ __device__ inline bool filter_i8_exact(int32_t a, int32_t rt, int32_t thr) { return 2 * a - (rt & 1) > thr; }
+// the distance the sweep writes for a pair: the integer d (below 2^24: the conversion is exact), the fp32 scan's bits
+__host__ __device__ inline float filter_i8_dist(int32_t qt, int32_t rt, int32_t dot) { return (float)(qt + rt - 2 * dot); }
 hipError_t launch_scan_f32_stream(const StreamParams& p, int grid, hipStream_t s);
 
 // Single-call scan (vs_scan_one.hip): one launch per batch of <= 32 queries, no seed launches, no merge launch -- a lane

@@ -5,8 +5,20 @@
 // the byte forms that the seed's query preparation writes (SeedParams::q8frag / qterm) -- two MFMAs per 16-row tile and
 // column block instead of four, and ring units of 8 KB + 256 B instead of 16 KB + 256 B.  The test is exact in integers
 // (filter_i8_thr, vs_kernels.h): there is no error bound, the candidates are the rows under tau0 (plus, for an odd bound,
-// nothing: the rare path tests exactly).  What passes is recomputed from the fp32 rows by RecheckF32 when the wave bins
-// its buffer, so every id, distance bit and flag is decided as scan_f32s_kernel decides it.  L2 only.
+// nothing: the rare path tests exactly).  L2 only.
+//
+// The sweep's entry is final: (query, (float)d, row + id_offset) is binned as it stands, and the kernel reads neither the
+// fp32 rows nor their norms nor the raw queries.  The kernel runs only on a group whose batches are all byte valued
+// (f32f_some_batch_not_bytes) against a byte-valued shard, and for such a pair scan_f32s_kernel's arithmetic gives the
+// sweep's integer (filter_i8_dist, vs_kernels.h): dot = sum q b <= 128 * 255^2 < 2^24 with every product and partial
+// sum an integer, so its fmaf chain is exact in any order; qn and bn are sums of integer squares <= 8 323 200 and
+// qn + bn <= 16 646 400 < 2^24 is exact; d = fmaf(-2, dot, qn + bn) is one rounding of an exact integer below 2^24 --
+// the integer d of the sweep, which it stores as (float)d (+0.0 for a zero distance on both sides).  scan_f32s_kernel
+// keeps a row iff fmaf(-2, dot, bn) < stream_l2_thr(tau, qn) && d < tau, and stream_l2_thr is built so that d < tau
+// implies the first test (vs_f32f.h): keep <=> d < tau0, which filter_i8_exact decided before the entry was written
+// (NaN and infinite bounds alike: filter_i8_thr's clamp).  So every id, distance bit and flag is what scan_f32s_kernel
+// decides.  Comparison toggle VSEARCH_F32_FILTER_I8_RECHECK=1 (StreamParams::i8_recheck): the wave recomputes every
+// entry from the fp32 rows by RecheckF32 when it bins its buffer, as the bf16 sweep must -- the same bytes, later.
 //
 // Kept from scan_f32f_kernel: the grid and both organisations (NW = 8: one workgroup per CU; NW = 4: two halves, waves vw =
 // w + 4 z), one sweep of the workgroup's 64-row units (bx + n G) for all batches, column blocks vw + 8 h, one shared ring
@@ -51,6 +63,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_i8_kernel(
     static_assert(D >= 3 && D <= 8 && (kScanWaves / NW) * D * kI8UnitBytes <= 160 * 1024, "the ring: one slot being read, one being filled, >= 1 in flight");
     static_assert((D - 2) * kUnitVmem <= 63, "vmcnt is a 6-bit count");
     extern __shared__ __attribute__((aligned(16))) char smem[];
+#ifdef VS_F32F_ENDS
+    // Diagnostic builds (-DVS_F32F_ENDS, scripts/diag/f32fstamps.py --ends): scan_f32f_kernel's three clock reads per wave,
+    // none inside the loop, and two words from inside the tail (sink_bin_wave)
+    const unsigned long long en_start = __builtin_amdgcn_s_memrealtime();
+#endif
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, g = lane >> 4;
@@ -165,11 +182,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_i8_kernel(
                     const unsigned long long mask = __ballot(pass);
                     if (mask) {  // wave-uniform
                         const int pos = wbase + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-                        // (query, value, id): the value is the integer distance, replaced by RecheckF32's; query = 16 cb + r
+                        // (query, value, id): the value is the distance, final (the kernel's head); query = 16 cb + r
                         const int qglob = 16 * (vw + kScanWaves * h) + r;
-                        const int d = qt[h] + rt[set][j] - 2 * (acc[j] + (rt[set][j] >> 1));
+                        const float d = filter_i8_dist(qt[h], rt[set][j], acc[j] + (rt[set][j] >> 1));  // acc = dot - (rt >> 1)
                         if (pass && pos < p.sink.wcap)
-                            wbuf[pos] = make_int4(qglob, __builtin_bit_cast(int, (float)d), row + p.id_offset, 0);
+                            wbuf[pos] = make_int4(qglob, __builtin_bit_cast(int, d), row + p.id_offset, 0);
                         wbase += __popcll(mask);
                     }
                 }
@@ -187,10 +204,28 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_i8_kernel(
         // set's slot is refilled follows the set's LDS reads
         asm volatile("" ::"v"(acc));
     };
+    // Diagnostic builds (-DVS_STAMPS, scripts/diag/f32fstamps.py): the step split of scan_f32f_kernel -- [0] between
+    // steps, [1] the vmcnt wait, [2] the barrier, [3] the unit's DMA issue, [4 + i] tile i, summed over the wave's steps in
+    // shader clocks and written by lane 0 at the wave's end to dbg[workgroup][wave][16] ([8] = steps, [9] = candidates).
+#ifdef VS_STAMPS
+    int st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned st_prev = (unsigned)__builtin_amdgcn_s_memtime();
+#define VS_F32F_STAMP(i)                                                \
+    do {                                                                \
+        const unsigned now_ = (unsigned)__builtin_amdgcn_s_memtime();   \
+        st_sum[i] += (int)(now_ - st_prev);                             \
+        st_prev = now_;                                                 \
+    } while (0)
+#else
+#define VS_F32F_STAMP(i)
+#endif
     auto step = [&](const int t, const int sl) __attribute__((always_inline)) {
+        VS_F32F_STAMP(0);
         wait_vm<(D - 3) * kUnitVmem>();
+        VS_F32F_STAMP(1);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
+        VS_F32F_STAMP(2);
         if constexpr (NW == 4) {  // half 1 wins the SIMD on f32f_prio steps of every eight (scan_f32f_kernel)
             if (z == 1 && p.f32f_prio) {
                 if ((t & 7) < p.f32f_prio) __builtin_amdgcn_s_setprio(1);
@@ -198,12 +233,14 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_i8_kernel(
             }
         }
         issue_unit(t + D - 1, (sl + D - 1) % D);
+        VS_F32F_STAMP(3);
         const int row_u = (bx + t * G) * kUnitRows + 4 * g;
 #pragma unroll
         for (int i = 0; i < kUnitTiles; ++i) {
             score_tile(i & 1, row_u + TR * i);
             if (i + 2 < kUnitTiles) read_frags(i & 1, sl, i + 2);
             else read_frags(i & 1, (sl + 1) % D, i + 2 - kUnitTiles);
+            VS_F32F_STAMP(4 + i);
         }
     };
     // one turn of the ring per iteration, every slot a constant; T is workgroup-uniform: every wave passes the same barriers
@@ -220,16 +257,57 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void scan_f32f_i8_kernel(
         if constexpr (D > 7) { if (t0 + 7 >= T) break; step(t0 + 7, 7); }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // retire the tail prefetches before the wave ends
+#ifdef VS_STAMPS
+    if (p.dbg && lane == 0) {
+        int32_t* o = p.dbg + ((int64_t)bx * kScanWaves + vw) * 16;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = st_sum[i];
+        o[8] = T;
+        o[9] = wbase;
+    }
+#endif
+#undef VS_F32F_STAMP
     if constexpr (NW == 4) {
         if (z == 1 && p.f32f_prio) __builtin_amdgcn_s_setprio(0);
     }
-    const RecheckF32 fix{p.base, p.bnorm, p.q, p.q_batch_stride, p.qnorm, p.tau0, 0, p.id_offset};
-    int kept = sink_bin_wave<RecheckF32, true>(p.sink, bx * kScanWaves + vw, wbase, lane, fix);
-    if (p.i8_stats && wbase > 0) {  // (wave-uniform) one atomic instruction: lane 0 adds the sweep's count, lane 1 the survivors
+#ifdef VS_F32F_ENDS
+    const unsigned long long en_loop = __builtin_amdgcn_s_memrealtime();
+    unsigned long long en_tail[2] = {0ull, 0ull};
+#define VS_F32F_TAIL , 0, en_tail
+#else
+#define VS_F32F_TAIL
+#endif
+    // the entries are final and binned as they are; the toggle (kernel-uniform) recomputes them from the fp32 rows first
+    int kept;
+    if (__builtin_expect(p.i8_recheck, 0)) {
+        const RecheckF32 fix{p.base, p.bnorm, p.q, p.q_batch_stride, p.qnorm, p.tau0, 0, p.id_offset};
+        kept = sink_bin_wave<RecheckF32, true>(p.sink, bx * kScanWaves + vw, wbase, lane, fix VS_F32F_TAIL);
+    } else {
+        kept = sink_bin_wave(p.sink, bx * kScanWaves + vw, wbase, lane, SinkEntryAsIs() VS_F32F_TAIL);
+    }
+#undef VS_F32F_TAIL
+    if (p.i8_stats && wbase > 0) {  // (wave-uniform) one atomic instruction: lane 0 adds the sweep's count, lane 1 the entries binned
 #pragma unroll
         for (int u = 32; u >= 1; u >>= 1) kept += __shfl_xor(kept, u);
         if (lane < 2) atomicAdd(p.i8_stats + 2 + lane, (unsigned long long)(lane == 0 ? wbase : kept));
     }
+#ifdef VS_F32F_ENDS
+    // scan_f32f_kernel's dbg[workgroup][wave][16]: [0..1] start, [2..3] loop end, [4..5] end (100 MHz ticks, low word first),
+    // [6] units swept, [7] XCC_ID, [8] candidates; and of the tail: [9..10] the first round read back (and rechecked, under
+    // the toggle), just before the first binning atomic, [11] ticks of read-back (and recheck) summed over the rounds
+    const unsigned long long en_end = __builtin_amdgcn_s_memrealtime();
+    if (p.dbg && lane == 0) {
+        int32_t* o = p.dbg + ((int64_t)bx * kScanWaves + vw) * 16;
+        o[0] = (int)en_start, o[1] = (int)(en_start >> 32);
+        o[2] = (int)en_loop, o[3] = (int)(en_loop >> 32);
+        o[4] = (int)en_end, o[5] = (int)(en_end >> 32);
+        o[6] = T;
+        o[7] = (int)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7);
+        o[8] = wbase;
+        o[9] = (int)en_tail[0], o[10] = (int)(en_tail[0] >> 32);
+        o[11] = (int)en_tail[1];
+    }
+#endif
 }
 
 template <int CBW, int NW>

@@ -18,8 +18,15 @@ __device__ __forceinline__ void sink_raise_overflow(const CandSink& p) {
 }
 // Drop = true: an entry that `fix` returns with a negative query is not binned (the bf16 prefilter's exact recheck).
 // Returns how many entries this lane binned (or tried to: a full list).
+// Diagnostic builds (-DVS_F32F_ENDS) only: `tail`, where given, receives in tail[0] the 100 MHz clock when the first
+// round's entries have been read back and fixed, just before the first binning atomic, and in tail[1] the ticks that the
+// read-back and `fix` took summed over the rounds (lane 0 takes part in every round: its copy is the wave's).
 template <typename Fix = SinkEntryAsIs, bool Drop = false>
-__device__ __forceinline__ int sink_bin_wave(const CandSink& p, int wb, int n, int lane, const Fix fix = Fix(), int diag = 0) {
+__device__ __forceinline__ int sink_bin_wave(const CandSink& p, int wb, int n, int lane, const Fix fix = Fix(), int diag = 0
+#ifdef VS_F32F_ENDS
+                                             , unsigned long long* tail = nullptr
+#endif
+) {
     int kept = 0;
     if (n > p.wcap) {
         if (lane == 0) sink_raise_overflow(p);  // entries were dropped: the fallback kernels behind take over
@@ -37,10 +44,21 @@ __device__ __forceinline__ int sink_bin_wave(const CandSink& p, int wb, int n, i
     int sub = (int)(hash % (unsigned)p.nsub);
     if (p.xcd_subs) sub = (int)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7) * p.xcd_subs + (int)(hash % (unsigned)p.xcd_subs);  // XCC_ID
     for (int e = lane; e < n; e += 64) {
+#ifdef VS_F32F_ENDS
+        const unsigned long long t_round = tail ? __builtin_amdgcn_s_memrealtime() : 0ull;
+#endif
         const unsigned long long* s64 = reinterpret_cast<const unsigned long long*>(src + e);
         const unsigned long long lo = __hip_atomic_load(s64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned long long hi = __hip_atomic_load(s64 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int4 c = fix(make_int4((int)lo, (int)(lo >> 32), (int)hi, (int)(hi >> 32)));  // (query, distance bits, id, -)
+#ifdef VS_F32F_ENDS
+        if (tail) {
+            asm volatile("s_waitcnt vmcnt(0)" ::"v"(c.x), "v"(c.y), "v"(c.z) : "memory");  // the entry is complete: loads and fix
+            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+            if (!tail[0]) tail[0] = now;
+            tail[1] += now - t_round;
+        }
+#endif
         if constexpr (Drop) {
             if (c.x < 0) continue;
         }

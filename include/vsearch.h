@@ -314,8 +314,10 @@ VS_API int vs_set_batch(vs_index* h, int batch);
  * (vs_bf_search does that itself; the *_dev calls report it as flags == 2).  1 = force fp32 (the reference
  * arithmetic, cblas_sgemm + epilogue); 2 = require int8 (VS_ERR_UNSUPPORTED when the base does not allow it).
  * Under 1 a long call (4 batches and more) on a byte-valued squared-L2 index may still PREFILTER on the byte copy (int8 MFMA,
- * vs_bf_filter_i8_stats below): what passes is recomputed from the fp32 rows, which decide every returned id, distance bit
- * and flag; a launch group with a batch that is not byte valued is prefiltered on the bf16 image instead.
+ * vs_bf_filter_i8_stats below): for a byte-valued pair the integer distance is the fp32 distance, bit for bit (every
+ * partial sum of the fp32 chain is an integer below 2^24), and is returned as it stands; a launch group with a batch that
+ * is not byte valued is prefiltered on the bf16 image instead, where what passes is recomputed from the fp32 rows -- they
+ * decide every returned id, distance bit and flag on that route and in the fallback scan.
  * IVF indexes alike: 1 = the list scan reads the fp32 rows (IVFIndex.cpp:270-358's arithmetic).
  * Wide k (k >= 16): the specialised 128-d index and vs_bf_create_nd indexes read the fp32 rows whatever the setting; a
  * general index with a byte copy (vs_bf_create_nd_u8*) reads the byte rows at 0 and 2 and the fp32 rows at 1. */
@@ -1113,7 +1115,9 @@ VS_API float vs_f32_filter_cnorm(double bnmax);
 VS_API float vs_f32_filter_th2(float thr, float e, float cnorm);
 /* Counters of the prefilter since the index was created or last reset (waits for the device): out[0] = launches that took
  * the prefilter, out[1] = of those, launches whose candidate buffers overflowed (the exact fallback scan behind produced
- * their results), out[2] = candidates written by the sweeps, out[3] = candidates that survived the exact recheck.
+ * their results), out[2] = candidates written by the sweeps, out[3] = candidates that survived the exact recheck
+ * on the fp32 rows (the bf16 sweep; the int8 sweep's integer distance is the fp32 distance and is returned as it stands, so
+ * every candidate it writes counts as kept).
  * VS_ERR_INVALID when the index has no prefilter (see vs_bf_filter_image_read). */
 VS_API int vs_bf_filter_stats(vs_index* h, int64_t* out /* [4] */, int reset);
 /* On an index that also keeps a byte copy (every value an integer in [0, 255]), squared L2, a prefilter launch group is
@@ -1121,8 +1125,11 @@ VS_API int vs_bf_filter_stats(vs_index* h, int64_t* out /* [4] */, int reset);
  * behind it, runs only when the device finds a batch of the group that is not byte valued.  vs_bf_filter_stats counts the
  * prefilter whichever sweep answered (out[0]: one per launch group; out[1]: an overflow of either sweep; out[2], out[3]: the
  * candidates of both, and its reset clears the counters of this call too); this call counts the int8 sweep's share: out[0] = launch groups enqueued on the int8 route, out[1] = of those, groups the device handed to
- * the bf16 sweep, out[2] = candidates the int8 sweep wrote, out[3] = candidates that survived the exact recheck.  All zero
- * on an index that never takes the route. */
+ * the bf16 sweep, out[2] = candidates the int8 sweep wrote, out[3] = candidates it binned: the same number, because
+ * the sweep's integer distance d = qterm + rterm - 2 dot is the fp32 distance of a byte-valued pair and its test d < tau0 the
+ * fp32 scan's, so the entry is returned as it stands and the fp32 rows are not read (they decide on the bf16 route and in
+ * the fallback; VSEARCH_F32_FILTER_I8_RECHECK=1 recomputes every entry from them for comparison: the same results, and
+ * out[3] then counts what that recheck kept).  All zero on an index that never takes the route. */
 VS_API int vs_bf_filter_i8_stats(vs_index* h, int64_t* out /* [4] */, int reset);
 /* Whether a vs_bf_search_dev_multi launch group of n_batches batches (at most 32) at this k is enqueued on that route
  * (host only): 1 on a byte-valued squared-L2 128-d index under vs_set_precision(h, 1) whose group takes the prefilter, at
@@ -1134,6 +1141,9 @@ VS_API int vs_bf_filter_i8_plan(const vs_index* h, int n_batches, int k);
  * 128) and dot = sum (q - 128)(b - 128):  out[0] = thr = qterm - ceil(tau0), out[1] = the hot test dot - (rterm >> 1) >
  * floor(thr / 2), out[2] = the exact test 2 (dot - (rterm >> 1)) - (rterm & 1) > thr, i.e. d = qterm + rterm - 2 dot < tau0. */
 VS_API void vs_f32_filter_i8_test(float tau0, int32_t qterm, int32_t rterm, int32_t dot, int32_t* out /* [3] */);
+/* The distance that sweep writes for such a pair (vs_kernels.h, filter_i8_dist, the function the kernel calls; pure host
+ * arithmetic): d = qterm + rterm - 2 dot as a float, for byte-valued q and b the bits of the fp32 scan's distance. */
+VS_API float vs_f32_filter_i8_dist(int32_t qterm, int32_t rterm, int32_t dot);
 VS_API void vs_destroy(vs_index* h);
 
 #ifdef __cplusplus

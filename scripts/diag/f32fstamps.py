@@ -12,7 +12,12 @@ and none inside the loop, so the kernel runs at the product's speed): when every
 its loop and ends, over the grid, per XCD and per half, and the share of the launch that a perfect balance could remove
 -- (last end - mean end) / (last end - first start).  The two halves of the 4-wave organisation share a CU, so read the
 share per half as well: what lies between the halves' ends is no imbalance between CUs.  VSEARCH_F32F_PRIO
-sets the priority duty of half 1."""
+sets the priority duty of half 1.
+
+The synthetic SIFT shard is byte valued, so by default the launch is answered by scan_f32f_i8_kernel, which stamps the
+same layout in both builds (VSEARCH_F32_FILTER_I8=0: the bf16 sweep).  Its ends build also splits the tail: when the
+first round of the wave's buffer has been read back (and rechecked, under VSEARCH_F32_FILTER_I8_RECHECK=1), and the
+time of read-back and recheck over all rounds."""
 import ctypes as C
 import os
 import sys
@@ -77,6 +82,23 @@ with pkg.BruteForceIndex(base) as idx:
         print(f"launch {last - first:.2f} us; last end - mean end = {last - wg[:, 2].mean():.2f} us = "
               f"{100.0 * (last - wg[:, 2].mean()) / (last - first):.2f} % of the launch (what a perfect balance could remove); "
               f"last loop end - mean loop end = {wg[:, 1].max() - wg[:, 1].mean():.2f} us")
+        has_tail = (raw[:, :, 9] != 0) | (raw[:, :, 10] != 0)  # scan_f32f_i8_kernel's words from inside sink_bin_wave
+        if has_tail.any():
+            w32 = raw.astype(np.int64) & 0xFFFFFFFF
+            first_bin = (w32[:, :, 9] | (w32[:, :, 10] << 32)) * 0.01
+            a = (first_bin - tick[:, :, 1])[has_tail]        # loop end -> first round read back (and rechecked)
+            b = (tick[:, :, 2] - first_bin)[has_tail]        # -> end: the binning, and the later rounds whole
+            c = (tick[:, :, 2] - tick[:, :, 1])[has_tail]
+            rb = (raw[:, :, 11] * 0.01)[has_tail]            # read-back (and recheck), all rounds
+            cand = raw[:, :, 8][has_tail]
+            print(f"tail per wave ({has_tail.sum()} waves with candidates, {cand.mean():.1f} each, {np.ceil(cand / 64).mean():.2f} rounds), "
+                  f"VSEARCH_F32_FILTER_I8_RECHECK={os.environ.get('VSEARCH_F32_FILTER_I8_RECHECK', 'unset')}: "
+                  f"end - loop end {c.mean():.2f} us [{c.min():.2f}, {c.max():.2f}] = "
+                  f"read-back and recheck of round 1 {a.mean():.2f} [{a.min():.2f}, {a.max():.2f}] + the rest {b.mean():.2f} [{b.min():.2f}, {b.max():.2f}]; "
+                  f"read-back and recheck of all rounds {rb.mean():.2f} [{rb.min():.2f}, {rb.max():.2f}], "
+                  f"so binning {(c - rb).mean():.2f} us")
+        tl = wg[:, 2] - wg[:, 1]
+        print(f"per workgroup, end - loop end: mean {tl.mean():.2f} us, last {tl.max():.2f} us")
         print("per workgroup: sweeper half XCD units start loop_end end")
         for i in range(raw.shape[0]):
             print(f"{ran[i] // (8 // NW):4d} {half[i]} {xcd[i]} {units[i]:3d} {wg[i, 0]:7.2f} {wg[i, 1]:7.2f} {wg[i, 2]:7.2f}")
