@@ -217,6 +217,7 @@ def lib():
         "vs_ivf_one_plan_u8": (i32, [i64, i32, i32, i32, i32, i32, i32, i32, vp]),
         "vs_ivf_one_u8_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_ivf_nd_widek_stats": (i32, [vp, C.POINTER(i64), i32]),
+        "vs_ivf_nd_widek_u8_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_ivf_search_topk": (i32, [vp, vp, i64, i32, i32, vp, vp, C.POINTER(i64), C.POINTER(Timing)]),
         "vs_ivf_search_topk_dev_multi": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "vs_ivf_search_metric": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, C.POINTER(i64), C.POINTER(Timing)]),
@@ -1003,6 +1004,14 @@ class IVFIndex(_Index):
         the wide-k calls on a general index since the last reset (vs_ivf_nd_widek_stats)."""
         out = (C.c_int64 * 3)()
         _check(lib().vs_ivf_nd_widek_stats(self._h, out, 1 if reset else 0))
+        return tuple(int(v) for v in out)
+
+    def nd_widek_u8_stats(self, reset: bool = False):
+        """(pairs on the byte plan, pairs on the fp32 plan of the first scan; saturated pairs on the byte plan, on the fp32
+        plan of the rescan) of the wide-k calls on a from_u8 general index that keeps its byte copy, since the last reset
+        (vs_ivf_nd_widek_u8_stats); a pair is a (query, probed non-empty list)."""
+        out = (C.c_int64 * 4)()
+        _check(lib().vs_ivf_nd_widek_u8_stats(self._h, out, 1 if reset else 0))
         return tuple(int(v) for v in out)
 
     def search_dev_sharded(self, comm: "Comm", q_ptr: int, n_batches: int, B: int, k: int, nprobe: int, ids_ptr: int,

@@ -106,7 +106,9 @@ struct vs_index {
     vs::DevBuf<int8_t> d_nd_q8frag;  // [kMaxMulti][dim_b / 64][2][64][16] scratch of launch_scan_nd_i8
     vs::DevBuf<int32_t> d_nd_qterm;  // [kMaxMulti][32]
     vs::DevBuf<unsigned long long> d_wide_cnt;  // brute force: [2] wide batches scanned on the byte rows | sent to the fp32 rows by their verdict
-    vs::DevBuf<unsigned long long> d_nd_stats;  // general IVF index from uint8 rows: (query, probe) pairs planned on bytes | on fp32
+    // general IVF index from uint8 rows: [0..1] (query, probe) pairs of k <= 16 groups planned on bytes | on fp32
+    // (vs_ivf_nd_u8_stats); [2..5] the four counters of vs_ivf_nd_widek_u8_stats
+    vs::DevBuf<unsigned long long> d_nd_stats;
     int metric = VS_METRIC_L2;
     int64_t n_rows = 0;   // rows resident on this GPU
     int64_t n_total = 0;  // rows of the whole (unsharded) index
@@ -306,10 +308,14 @@ struct vs_index {
     // ... and on an index with a byte copy the byte route.  VSEARCH_IVF_ONE_U8 at creation: 0 = off, 2 = the
     // byte route at every shape of ivf_one_route, the shapes ivf_one_route_u8 takes out included (the measurement's leg)
     int ivf_one_u8 = 1;
+    // ... and wide k (17 <= k <= 128) scans the byte rows for the queries that qualify (DESIGN 4.6c;
+    // VSEARCH_IVF_ND_WIDE_U8=0 at creation: the fp32 launches for every pair)
+    bool ivf_nd_wide_u8 = true;
     // ... and what a wide-k group (17 <= k <= 128, ivf_group_nd_wide_dev) needs beside it, allocated on the first such call
     struct IvfNdWide {
         vs::DevBuf<int32_t> plan, slots, items;  // the rescan plan's tables, as IvfNd's
-        vs::DevBuf<float> tau;       // [kIvfNdGroupQ]
+        vs::DevBuf<int32_t> plan8, slots8, items8;  // ... and the byte rescan plan's (an index that scans wide k on bytes)
+        vs::DevBuf<float> tau;      // [kIvfNdGroupQ]
         vs::DevBuf<int32_t> mask;    // [kIvfNdGroupQ * np_max] saturated pairs
         vs::DevBuf<int32_t> cnt;     // [kIvfNdGroupQ] candidates per query (zero between groups)
         vs::DevBuf<unsigned long long> cand;   // [kIvfNdGroupQ][kIvfNdWideCand] keys
@@ -1817,8 +1823,11 @@ int ensure_ivf_nd_wide(vs_index* h) {
     if (rc) return rc;
     vs_index::IvfNdWide W;
     const size_t gq = vs::kIvfNdGroupQ, pairs = gq * h->ivfnd.np_max;
-    if ((rc = W.plan.alloc((size_t)3 * h->nlist + 2)) || (rc = W.slots.alloc(pairs)) ||
-        (rc = W.items.alloc((size_t)2 * vs::ivf_nd_items_cap(h->nlist, h->ivfnd.np_max))) || (rc = W.tau.alloc(gq)) ||
+    const size_t n_items2 = (size_t)2 * vs::ivf_nd_items_cap(h->nlist, h->ivfnd.np_max);
+    const bool bytes = h->d_nd_u8 && h->ivf_nd_wide_u8;  // a second rescan plan, on the byte rows
+    if ((rc = W.plan.alloc((size_t)3 * h->nlist + 2)) || (rc = W.slots.alloc(pairs)) || (rc = W.items.alloc(n_items2)) ||
+        (bytes && ((rc = W.plan8.alloc((size_t)3 * h->nlist + 2)) || (rc = W.slots8.alloc(pairs)) || (rc = W.items8.alloc(n_items2)))) ||
+        (rc = W.tau.alloc(gq)) ||
         (rc = W.mask.alloc(pairs)) || (rc = W.cnt.alloc(gq)) || (rc = W.cand.alloc(gq * vs::kIvfNdWideCand)) || (rc = W.stats.alloc(3)))
         return rc;
     HIPCHK(hipMemset(W.cnt, 0, gq * sizeof(int32_t)));
@@ -1872,6 +1881,37 @@ vs::IvfNdParams ivf_nd_params(vs_index* h, const float* q_dev, int group_q, int 
     return ip;
 }
 
+// the byte plan of the same group on an index with a byte copy of its rows: ip's fields on the byte plan's tables with
+// route_want = 1; ip itself becomes the fp32 plan of the two (route_want = 0 on the same verdicts)
+vs::IvfNdI8Params ivf_nd_i8_params(vs_index* h, vs::IvfNdParams& ip) {
+    vs_index::IvfNd& W = h->ivfnd;
+    vs::IvfNdI8Params bp{};
+    bp.s = ip;
+    bp.s.list_cnt = W.plan8;
+    bp.s.list_start = W.plan8 + (size_t)2 * h->nlist;
+    bp.s.n_items = W.plan8 + (size_t)3 * h->nlist + 1;
+    bp.s.slots = W.slots8;
+    bp.s.items = W.items8;
+    bp.s.route = W.valid;
+    bp.s.route_want = 1;
+    bp.s.pair_count = h->d_nd_stats;
+    bp.vecs_u8 = h->d_nd_u8;
+    bp.rterm = h->d_nd_rterm;
+    bp.dim_b = h->dim_b;
+    bp.bmax = h->nd_bmax;
+    bp.all_f32 = h->precision == 1;
+    bp.q8rows = W.q8rows;
+    bp.qterm = W.qterm;
+    bp.valid = W.valid;
+    if (h->metric == VS_METRIC_IP) {
+        bp.rsum = h->ivfndip.rsum;
+        bp.qsum = h->ivfndip.qsum;
+    }
+    ip.route = W.valid;
+    ip.route_want = 0;
+    return bp;
+}
+
 // One launch group of a general IVF index: nb <= 32 batches of B queries ([nb][B][dim], back to back), everything on s.
 // Coarse scores per batch are the brute-force general scan's on the centroid table (equal scores: the lower list id,
 // launch_pick_probes); then the plan, the list-major scan and the ranking of the group's partial lists.  An index with a
@@ -1915,29 +1955,7 @@ int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int 
     const bool two_plans = (bool)h->d_nd_u8;
     if (two_plans && h->metric == VS_METRIC_IP && (rc = ensure_ivf_nd_ip(h, s))) return rc;
     if (two_plans) {
-        bp.s = ip;
-        bp.s.list_cnt = W.plan8;
-        bp.s.list_start = W.plan8 + (size_t)2 * h->nlist;
-        bp.s.n_items = W.plan8 + (size_t)3 * h->nlist + 1;
-        bp.s.slots = W.slots8;
-        bp.s.items = W.items8;
-        bp.s.route = W.valid;
-        bp.s.route_want = 1;
-        bp.s.pair_count = h->d_nd_stats;
-        bp.vecs_u8 = h->d_nd_u8;
-        bp.rterm = h->d_nd_rterm;
-        bp.dim_b = h->dim_b;
-        bp.bmax = h->nd_bmax;
-        bp.all_f32 = h->precision == 1;
-        bp.q8rows = W.q8rows;
-        bp.qterm = W.qterm;
-        bp.valid = W.valid;
-        if (h->metric == VS_METRIC_IP) {
-            bp.rsum = h->ivfndip.rsum;
-            bp.qsum = h->ivfndip.qsum;
-        }
-        ip.route = W.valid;
-        ip.route_want = 0;
+        bp = ivf_nd_i8_params(h, ip);
         HIPCHK(vs::launch_ivf_nd_i8_prep(bp, s));
     }
     HIPCHK(vs::launch_ivf_nd_plan(ip, s));
@@ -1962,9 +1980,12 @@ int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int 
     return VS_OK;
 }
 
-// The same launch group at 17 <= k <= 128: coarse, query rows, plan and scan exactly as above at KCAP 16 on
-// the fp32 rows with every pair (an index with a byte copy plans once: wide k scans the fp32 rows whatever
-// vs_set_precision says); then the bound, the rescan of the saturated pairs into per-query candidate lists, and the ranking.
+// The same launch group at 17 <= k <= 128: coarse, query rows, plans and scans exactly as above at KCAP 16;
+// then the bound, the rescan of the saturated pairs into per-query candidate lists, and the ranking.  An index with a byte
+// copy plans the rescan twice as well: the saturated pairs of the queries that run on bytes go to
+// ivf_scan_nd_cand_i8_kernel, the others to ivf_scan_nd_cand_kernel, both into the same candidate lists.  Under
+// vs_set_precision(h, 1), or on an index created under VSEARCH_IVF_ND_WIDE_U8=0, every pair is on the fp32 plans.  The
+// plans count their pairs into the words of vs_ivf_nd_widek_u8_stats, never into vs_ivf_nd_u8_stats' byte word.
 // Everything on s, no host synchronisation.
 int ivf_group_nd_wide_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int nprobe, float* out_d, int32_t* out_i, hipStream_t s) {
     if (k <= 16 || k > vs::kIvfNdWideKMax) {
@@ -1986,10 +2007,23 @@ int ivf_group_nd_wide_dev(vs_index* h, const float* q_dev, int nb, int B, int k,
     }
     stage_mark(h, 1, s);
     vs::IvfNdParams ip = ivf_nd_params(h, q_dev, nb * B, kKcapMax, kKcapMax, nprobe);
+    vs::IvfNdI8Params bp{};
+    unsigned long long* const wide8 = h->d_nd_u8 && h->ivf_nd_wide_u8 ? h->d_nd_stats + 2 : nullptr;
+    const bool two_plans = wide8 && h->precision != 1;
+    if (two_plans && h->metric == VS_METRIC_IP && (rc = ensure_ivf_nd_ip(h, s))) return rc;
+    if (wide8) ip.pair_count2 = wide8 + 1;
+    if (two_plans) {
+        bp = ivf_nd_i8_params(h, ip);
+        bp.s.pair_count = wide8;
+        bp.s.pair_count2 = nullptr;
+        HIPCHK(vs::launch_ivf_nd_i8_prep(bp, s));
+    }
     HIPCHK(vs::launch_ivf_nd_plan(ip, s));
+    if (two_plans) HIPCHK(vs::launch_ivf_nd_plan_second(bp.s, s));
     stage_mark(h, 2, s);
     prof_begin(h, 1, s);
     HIPCHK(vs::launch_ivf_nd_scan(ip, h->num_cus, s));
+    if (two_plans) HIPCHK(vs::launch_ivf_nd_i8_scan(bp, h->num_cus, s));
     vs::IvfNdWideParams wp{};
     wp.r = ip;
     wp.r.k = k;
@@ -1999,8 +2033,9 @@ int ivf_group_nd_wide_dev(vs_index* h, const float* q_dev, int nb, int B, int k,
     wp.r.slots = X.slots;
     wp.r.items = X.items;
     wp.r.cand_count = nullptr;  // (counted once, by the first plan)
-    wp.r.pair_count = nullptr;
-    wp.r.pair_mask = X.mask;
+    wp.r.pair_count = wide8 ? wide8 + 3 : nullptr;
+    wp.r.pair_count2 = nullptr;
+    wp.r.pair_mask = X.mask;  // (and ip's route: the fp32 rescan plan of the two)
     wp.tau = X.tau;
     wp.pair_mask = X.mask;
     wp.cnt = X.cnt;
@@ -2009,8 +2044,29 @@ int ivf_group_nd_wide_dev(vs_index* h, const float* q_dev, int nb, int B, int k,
     wp.out_d = out_d;
     wp.out_i = out_i;
     wp.stats = X.stats;
+    if (two_plans) wp.list_cnt8 = X.plan8;
     HIPCHK(vs::launch_ivf_nd_wide_bound(wp, s));
     HIPCHK(vs::launch_ivf_nd_plan_second(wp.r, s));
+    if (two_plans) {
+        vs::IvfNdWideI8Params wb{};
+        wb.w = wp;
+        wb.w.r.list_cnt = X.plan8;
+        wb.w.r.list_start = X.plan8 + (size_t)2 * h->nlist;
+        wb.w.r.n_items = X.plan8 + (size_t)3 * h->nlist + 1;
+        wb.w.r.slots = X.slots8;
+        wb.w.r.items = X.items8;
+        wb.w.r.route_want = 1;
+        wb.w.r.pair_count = wide8 + 2;
+        wb.vecs_u8 = bp.vecs_u8;
+        wb.rterm = bp.rterm;
+        wb.rsum = bp.rsum;
+        wb.dim_b = bp.dim_b;
+        wb.q8rows = bp.q8rows;
+        wb.qterm = bp.qterm;
+        wb.qsum = bp.qsum;
+        HIPCHK(vs::launch_ivf_nd_plan_second(wb.w.r, s));
+        HIPCHK(vs::launch_ivf_nd_wide_i8_scan(wb, h->num_cus, s));
+    }
     HIPCHK(vs::launch_ivf_nd_wide_scan(wp, h->num_cus, s));
     prof_end(h, 1, s);
     HIPCHK(vs::launch_ivf_nd_wide_rank(wp, s));
@@ -2732,6 +2788,21 @@ int vs_ivf_nd_widek_stats(vs_index* h, int64_t* out, int reset) {
     return VS_OK;
 }
 
+int vs_ivf_nd_widek_u8_stats(vs_index* h, int64_t* out, int reset) {
+    if (!h || h->kind != 1 || !h->general || !h->d_nd_u8 || !h->d_nd_stats || !out) {
+        set_error("vs_ivf_nd_widek_u8_stats: a general IVF index that keeps a byte copy of its rows and an output of four words");
+        return VS_ERR_INVALID;
+    }
+    int rc = set_device(h);
+    if (rc) return rc;
+    unsigned long long v[4];
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(v, h->d_nd_stats + 2, sizeof(v), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; ++i) out[i] = (int64_t)v[i];
+    if (reset) HIPCHK(hipMemset(h->d_nd_stats + 2, 0, sizeof(v)));
+    return VS_OK;
+}
+
 int vs_ivf_nd_u8_stats(vs_index* h, int64_t* out, int reset) {
     if (!h || h->kind != 1 || !h->d_nd_stats || !out) {
         set_error("vs_ivf_nd_u8_stats: a general IVF index made by vs_ivf_create_nd_u8 and an output of two words");
@@ -3220,6 +3291,8 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
     // comparison toggle (VSEARCH_IVF_ONE=0, read here): short calls on this general index keep the group route
     if (const char* e = getenv("VSEARCH_IVF_ONE")) h->ivf_one = atoi(e) != 0;
     if (const char* e = getenv("VSEARCH_IVF_ONE_U8")) h->ivf_one_u8 = atoi(e) == 2 ? 2 : atoi(e) != 0;
+    // ... and VSEARCH_IVF_ND_WIDE_U8=0 the fp32 launches for wide k on an index with a byte copy (ivf_group_nd_wide_dev)
+    if (const char* e = getenv("VSEARCH_IVF_ND_WIDE_U8")) h->ivf_nd_wide_u8 = atoi(e) != 0;
     h->metric = VS_METRIC_L2;
     h->n_total = n_rows;
     h->nlist = nlist;
@@ -3293,8 +3366,8 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
         if (rows_u8) {  // (unsharded: the local rows are the caller's) the byte copy, unless max ||b||^2 >= 2^24, and the pair counters
             h->nd_from_u8 = true;
             h->dim_b = vs::nd_dim_b(dim);
-            if ((rc = build_nd_u8_copy(h, rows_u8, n_local)) || (rc = h->d_nd_stats.alloc(2))) return fail(rc);
-            if (hipMemset(h->d_nd_stats, 0, 2 * sizeof(unsigned long long)) != hipSuccess) return fail(VS_ERR_DEVICE);
+            if ((rc = build_nd_u8_copy(h, rows_u8, n_local)) || (rc = h->d_nd_stats.alloc(6))) return fail(rc);
+            if (hipMemset(h->d_nd_stats, 0, 6 * sizeof(unsigned long long)) != hipSuccess) return fail(VS_ERR_DEVICE);
         }
         if ((rc = alloc_scratch(h)) || (rc = ensure_ivf_nd(h)) || (rc = ensure_wide_streams(h)) || (rc = ensure_ivf_host(h))) return fail(rc);
         *out = h;

@@ -102,11 +102,14 @@ __global__ __launch_bounds__(256) void ivf_nd_count(const IvfNdParams p, const i
         for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
         if ((threadIdx.x & 63) == 0 && t) atomicAdd(p.cand_count, t);
     }
-    if (p.pair_count) {
+    if (p.pair_count || p.pair_count2) {
         int t = got;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-        if ((threadIdx.x & 63) == 0 && t) atomicAdd(p.pair_count, (unsigned long long)t);
+        if ((threadIdx.x & 63) == 0 && t) {
+            if (p.pair_count) atomicAdd(p.pair_count, (unsigned long long)t);
+            if (p.pair_count2) atomicAdd(p.pair_count2, (unsigned long long)t);
+        }
     }
 }
 

@@ -17,6 +17,11 @@
 //                     candidates (a long list under an infinite bound, masses of equal rows) is ranked over every row of
 //                     its probed lists, each distance recomputed by one thread in the MFMA's order.
 //
+// An index with a byte copy of its rows runs the first scan on two plans, as at k <= 16, and plans the rescan twice as
+// well: the saturated pairs of the queries that run on bytes go to ivf_scan_nd_cand_i8_kernel (vs_ivf_nd_wide_i8.hip), the
+// others to ivf_scan_nd_cand_kernel, into the same candidate lists.  A query sits on one route, so its partial lists and
+// its tau carry the same bits either way; the bound kernel also clears the counters of the second rescan plan.
+//
 // A candidate is the 64-bit key of vs_wide_select.h: (ordered distance bits) << 32 | reordered row -- the order the
 // result is ranked by.  The lists of a query's pairs are disjoint, so its keys are unique.
 #include "vs_kernels.h"
@@ -24,28 +29,6 @@
 #include "vs_wide_select.h"
 
 namespace vs {
-
-// The key of a candidate.  Squared L2 (IP false): tw_key / tw_dist as they are.  Inner product: tw_key folds -0.0 into +0
-// -- the rank the float comparisons of the other merges give it -- and tw_dist would hand +0.0 back, but a zero product
-// is -0.0 in every other path and in the oracle.  The IP key keeps the folded distance word, so -0.0 still ranks above
-// every negative score, below every positive one and ties with +0.0 by row, and stores (row << 1 | was -0.0) in the low
-// word (rows are below 2^31; they are unique per query, so the last bit never decides an order).
-template <bool IP>
-__device__ __forceinline__ bool nd_wide_key(float d, int32_t row, uint64_t& key) {
-    if (!tw_key(d, row, key)) return false;
-    if constexpr (IP)
-        key = (key & 0xffffffff00000000ull) | ((uint32_t)row << 1) | (__builtin_bit_cast(uint32_t, d) == 0x80000000u ? 1u : 0u);
-    return true;
-}
-template <bool IP>
-__device__ __forceinline__ int32_t nd_wide_row(uint64_t key) {
-    return IP ? (int32_t)((uint32_t)key >> 1) : (int32_t)(uint32_t)key;
-}
-template <bool IP>
-__device__ __forceinline__ float nd_wide_dist(uint64_t key) {
-    const float d = tw_dist(key);
-    return IP && (key & 1u) ? -0.0f : d;
-}
 
 constexpr int kNdWideThreads = 256;
 constexpr int kNdWideSelCap = 2048;  // keys the final sort holds (16 KB of LDS)
@@ -61,7 +44,10 @@ __global__ __launch_bounds__(kNdWideThreads) void ivf_nd_wide_bound_kernel(const
     __shared__ int s_n;
     const int q = blockIdx.x, tid = threadIdx.x;
     const int nprobe = p.r.nprobe, k = p.r.k;
-    for (int i = blockIdx.x * kNdWideThreads + tid; i < 2 * p.r.nlist; i += gridDim.x * kNdWideThreads) p.r.list_cnt[i] = 0;
+    for (int i = blockIdx.x * kNdWideThreads + tid; i < 2 * p.r.nlist; i += gridDim.x * kNdWideThreads) {
+        p.r.list_cnt[i] = 0;
+        if (p.list_cnt8) p.list_cnt8[i] = 0;
+    }
     const int64_t base = (int64_t)q * nprobe * 16;
     const int n = nprobe * 16;
     if (tid == 0) s_n = 0;

@@ -828,6 +828,7 @@ struct IvfNdParams {
     const int32_t* route;     // [group_q]
     int route_want;
     unsigned long long* pair_count;  // += pairs that got a slot in this plan (null: not counted)
+    unsigned long long* pair_count2; // += the same number once more (null: not counted): a wide-k group's own counter
     // the rescan plan of the wide-k pipeline (vs_ivf_nd_wide.hip): a pair gets a slot only when pair_mask[pair] != 0.
     // Null: every pair, as everywhere else.
     const int32_t* pair_mask; // [group_q * nprobe]
@@ -939,13 +940,13 @@ hipError_t launch_ivf_nd_i8_scan(const IvfNdI8Params& p, int grid, hipStream_t s
 hipError_t launch_ivf_nd_i8_rowsum(const int8_t* vecs_u8, int dim_b, int64_t rows, int32_t* rsum, hipStream_t s);
 
 // ---- wide k (17 <= k <= kIvfNdWideKMax) on a general IVF index (vs_ivf_nd_wide.hip).  The group's first
-// plan and scan run as above at kcap 16 on the fp32 rows with every pair; part[(query * nprobe + rank) * 16] then holds
-// each probed list's 16 best by (distance, row).
+// plan and scan run as above at kcap 16 -- on the fp32 rows with every pair, or on an index with a byte copy on two plans
+// as at k <= 16; part[(query * nprobe + rank) * 16] then holds each probed list's 16 best by (distance, row).
 //   launch_ivf_nd_wide_bound : tau[query] = the k-th smallest finite distance among the query's partial lists (+inf when
 //       there are fewer than k).  A pair whose 16th entry is finite and <= tau is saturated: its list may hold more rows
 //       at or under tau, pair_mask = 1.  Every other pair has all its rows at or under tau in its partial list already;
 //       those entries go to the query's candidate list as keys (tw_key of vs_wide_select.h) and pair_mask = 0.  Also
-//       clears r.list_cnt, the rescan plan's counters.
+//       clears r.list_cnt, the rescan plan's counters, and list_cnt8, those of a second rescan plan.
 //   launch_ivf_nd_plan_second(r) with r.pair_mask : the rescan plan, over the saturated pairs only.
 //   launch_ivf_nd_wide_scan  : ivf_scan_nd_kernel's item loop and accumulation chain on the rescan plan; no lane lists,
 //       no merge: every real row of a real slot with d <= tau[query] and d < +inf is appended to the query's list (no
@@ -967,9 +968,29 @@ struct IvfNdWideParams {
     float* out_d;             // [group_q][k]
     int32_t* out_i;
     unsigned long long* stats;  // [3]
+    int32_t* list_cnt8;       // [2][nlist] the byte rescan plan's counters, for the bound to clear (null: one rescan plan)
 };
 hipError_t launch_ivf_nd_wide_bound(const IvfNdWideParams& p, hipStream_t s);
 hipError_t launch_ivf_nd_wide_scan(const IvfNdWideParams& p, int grid, hipStream_t s);
 hipError_t launch_ivf_nd_wide_rank(const IvfNdWideParams& p, hipStream_t s);
+
+// ---- the rescan of a wide-k group on the byte copy of the rows (vs_ivf_nd_wide_i8.hip).  An index with a
+// byte copy plans the saturated pairs twice: w.r with route_want = 1 holds the pairs of the queries that run on bytes
+// (IvfNdI8Params::valid), the fp32 rescan plan the others.  launch_ivf_nd_wide_i8_scan scores w.r's items with
+// v_mfma_i32_16x16x64_i8 and tests every real row of a real slot in integers against w.tau[query], which for such a
+// query is +inf or an exact integer (its partial lists came out of launch_ivf_nd_i8_scan); a passing row is appended to
+// the query's candidate list with the key of (float)(qterm + rterm - 2 q'.b'), or of -(float)(q.b) under inner product:
+// the bits launch_ivf_nd_wide_scan appends for that row and query.
+struct IvfNdWideI8Params {
+    IvfNdWideParams w;        // w.r: the byte rescan plan (vecs / vnorm / qrows / qnorm are not read)
+    const int8_t* vecs_u8;    // [n_rows + kScanPadRows][dim_b] bytes (x - 128), zero padded
+    const int32_t* rterm;     // [n_rows + 64] sum (b - 128)^2
+    const int32_t* rsum;      // [n_rows + 64] sum (b - 128) (inner product only)
+    int dim_b;                // nd_dim_b(dim)
+    const int8_t* q8rows;     // [kIvfNdGroupQ][dim_b], qterm, qsum: as launch_ivf_nd_i8_prep left them for this group
+    const int32_t* qterm;
+    const int32_t* qsum;      // (inner product only)
+};
+hipError_t launch_ivf_nd_wide_i8_scan(const IvfNdWideI8Params& p, int grid, hipStream_t s);
 
 }  // namespace vs

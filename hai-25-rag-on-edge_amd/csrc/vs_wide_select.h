@@ -22,6 +22,28 @@ __device__ __forceinline__ float tw_dist(uint64_t key) {
     return __builtin_bit_cast(float, (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
+// The key of a candidate of the general IVF index's wide-k lists (vs_ivf_nd_wide.hip, vs_ivf_nd_wide_i8.hip).  Squared
+// L2 (IP false): tw_key / tw_dist as they are.  Inner product: tw_key folds -0.0 into +0 -- the rank the float comparisons of the other merges give it -- and tw_dist would hand +0.0 back, but a zero product
+// is -0.0 in every other path and in the oracle.  The IP key keeps the folded distance word, so -0.0 still ranks above
+// every negative score, below every positive one and ties with +0.0 by row, and stores (row << 1 | was -0.0) in the low
+// word (rows are below 2^31; they are unique per query, so the last bit never decides an order).
+template <bool IP>
+__device__ __forceinline__ bool nd_wide_key(float d, int32_t row, uint64_t& key) {
+    if (!tw_key(d, row, key)) return false;
+    if constexpr (IP)
+        key = (key & 0xffffffff00000000ull) | ((uint32_t)row << 1) | (__builtin_bit_cast(uint32_t, d) == 0x80000000u ? 1u : 0u);
+    return true;
+}
+template <bool IP>
+__device__ __forceinline__ int32_t nd_wide_row(uint64_t key) {
+    return IP ? (int32_t)((uint32_t)key >> 1) : (int32_t)(uint32_t)key;
+}
+template <bool IP>
+__device__ __forceinline__ float nd_wide_dist(uint64_t key) {
+    const float d = tw_dist(key);
+    return IP && (key & 1u) ? -0.0f : d;
+}
+
 // LDS of one selection: CAP keys for the final sort
 template <int CAP>
 struct WideSelLds {

@@ -320,7 +320,8 @@ VS_API int vs_set_batch(vs_index* h, int batch);
  * decide every returned id, distance bit and flag on that route and in the fallback scan.
  * IVF indexes alike: 1 = the list scan reads the fp32 rows (IVFIndex.cpp:270-358's arithmetic).
  * Wide k (k >= 16): the specialised 128-d index and vs_bf_create_nd indexes read the fp32 rows whatever the setting; a
- * general index with a byte copy (vs_bf_create_nd_u8*) reads the byte rows at 0 and 2 and the fp32 rows at 1. */
+ * general index with a byte copy (vs_bf_create_nd_u8*) reads the byte rows at 0 and 2 and the fp32 rows at 1, and so
+ * does a general IVF index with a byte copy (vs_ivf_create_nd_u8) at 17 <= k <= 128, per query as at k <= 16. */
 VS_API int vs_set_precision(vs_index* h, int precision);
 /* IVF indexes are created with the north-star's squared L2; VS_METRIC_IP selects the reference's own ranking (IVFIndex.cpp:
  * 449-496, :697-723): nprobe lists of LARGEST q.c, k candidates of largest q.v (fp32 rows; the int8 copies are an L2 device).
@@ -853,10 +854,15 @@ VS_API int vs_ivf_search_dev_multi(vs_index* h, const float* queries_dev, int n_
  *     vs_ivf_create_nd_u8): the wide-k pipeline of DESIGN.md 4.6c, in launch groups of up to 32 batches on the caller's
  *     stream, without a host synchronisation.  The result is the k best rows of the probed lists by (distance, position
  *     in vectors_reordered), ids through reorder_to_original; every distance is bit-identical to what vs_bf_create_nd's
- *     fp32 index returns for that row and query.  Wide k scans the fp32 rows whatever vs_set_precision says, also on a
- *     vs_ivf_create_nd_u8 index (as vs_bf_search_topk does for brute force): on data that qualifies for the byte rows
- *     the distances are the same numbers, so the result does not depend on it.  The first such call allocates about
- *     66 MB of device scratch. */
+ *     fp32 index returns for that row and query.  On a vs_ivf_create_nd_u8 index that keeps its byte copy, both scans of a
+ *     wide group -- the first scan of every probed list and the rescan of the saturated pairs -- read the byte rows
+ *     with int8 MFMA for the pairs of the queries that qualify (the rule of k <= 16, per query: every value an integer
+ *     in [0, 255] and ||q||^2 + max ||b||^2 <= 2^24) and the fp32 rows for every other pair of the same group, in the
+ *     same call, with no host synchronisation and nothing rerun: ids, distance bits and *total_candidates are those of
+ *     the fp32 rows.  vs_set_precision 0 and 2 do so, 1 puts every pair on the fp32 rows; VSEARCH_IVF_ND_WIDE_U8=0, read
+ *     when the index is created, keeps the fp32 launches for wide k on that index (the comparison toggle).
+ *     vs_ivf_nd_widek_u8_stats counts the pairs of either kind.  The first such call allocates about 66 MB of device
+ *     scratch. */
 VS_API int vs_ivf_search_topk(vs_index* h, const float* queries_host, int64_t nq, int k, int nprobe,
                               int32_t* ids, float* dists, int64_t* total_candidates, vs_timing* timing);
 VS_API int vs_ivf_search_topk_dev_multi(vs_index* h, const float* queries_dev, int n_batches, int B, int k, int nprobe,
@@ -887,7 +893,7 @@ VS_API int vs_ivf_search_topk_dev_multi(vs_index* h, const float* queries_dev, i
  *     On a vs_ivf_create_nd_u8 index and k <= 16, the pairs of the queries that qualify (the L2 rule, unchanged: every
  *     value an integer in [0, 255] and ||q||^2 + max ||b||^2 <= 2^24) are scanned on the byte rows with int8 MFMA and
  *     every other pair on the fp32 rows, with the same bits either way; vs_set_precision 0 and 2 do so, 1 puts every pair
- *     on the fp32 rows; 17 <= k <= 128 reads the fp32 rows.  The first inner-product call on such an index builds one
+ *     on the fp32 rows; 17 <= k <= 128 does the same in both of its scans (vs_ivf_search_topk above).  The first inner-product call on such an index builds one
  *     int32 per row on the device (the sum of the row's stored bytes).  vs_ivf_nd_u8_stats and vs_ivf_nd_widek_stats
  *     count these calls like the L2 ones. */
 VS_API int vs_ivf_search_metric(vs_index* h, const float* queries_host, int64_t nq, int k, int nprobe, int metric,
@@ -1066,6 +1072,13 @@ VS_API int vs_ivf_one_u8_stats(vs_index* h, int64_t* out /* [3] */, int reset);
  * 8192 candidates: every row of their probed lists scored again).  Always counted; zeros before the first wide-k call.
  * Synchronises the device; reset != 0 clears the counters.  VS_ERR_INVALID on any other kind of index. */
 VS_API int vs_ivf_nd_widek_stats(vs_index* h, int64_t* out /* [3] */, int reset);
+/* Which rows those calls read on a general IVF index that keeps a byte copy of its rows (vs_ivf_create_nd_u8), since the
+ * last reset: out[0] / out[1] = (query, probe) pairs that got a slot in the byte / fp32 plan of a wide group's first scan,
+ * out[2] / out[3] = saturated pairs that got a slot in the byte / fp32 plan of its rescan.  Always counted, on the device;
+ * all zero on an index created under VSEARCH_IVF_ND_WIDE_U8=0.  vs_ivf_nd_u8_stats' byte word is not moved by wide groups.
+ * Synchronises the device; reset != 0 clears the counters.  VS_ERR_INVALID for null pointers and on any index that is
+ * not a general IVF index with a byte copy of its rows. */
+VS_API int vs_ivf_nd_widek_u8_stats(vs_index* h, int64_t* out /* [4] */, int reset);
 /* per-launch durations (ms) of the same window, oldest first; *launches = how many there were (may exceed cap).
  * One brute-force launch serves up to 32 batches: the CLIs turn these into the per-batch statistics of
  * main.cpp:262-330 (avg / stddev / min / max / P50 / P95 / P99 "graph execute time"). */

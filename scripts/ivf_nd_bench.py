@@ -32,6 +32,12 @@ against that exact result, the three counters of vs_ivf_nd_widek_stats for one p
 (query, probe) pairs the rescan takes -- recomputed on the host in float64 for the first 64 queries (a pair is rescanned
 when the 16th best distance of its list is at or under the K-th smallest of the query's per-list top-16s).
 
+--u8 --widek K times the wide-k call on the byte index (both scans on the byte rows, leg "bytes") against the same call on
+a byte index created under VSEARCH_IVF_ND_WIDE_U8=0 (the fp32 launches; legs toggle_a and toggle_b, whose difference is
+the spread) and against the k = 10 call (k10), alternated in one process; with --metric ip under both metrics.  Per leg:
+us per 1024 queries and the group's four list scans alone (vs_prof_read(.., 1)); the four counters of
+vs_ivf_nd_widek_u8_stats for one pass.  The legs must return the same ids and bits.
+
 --metric ip times inner-product search through the per-call metric (IVFIndex.search_metric_dev_multi) against squared L2
 through the same call on the same index in the same process, the L2 leg twice (paths l2_a and l2_b: their spread is the
 noise an inner-product difference has to exceed), for every k of --k and every nprobe; with --u8 also the byte index
@@ -73,6 +79,9 @@ def one(a, dim):
     else:
         assign, cents = sampled_rows(a, pkg, base, dev, st)
     vr, off, r2o = pkg.ivf_layout_from_assignment(base, assign, a.nlist)
+    if a.widek and a.u8:
+        search_widek_u8(a, pkg, dim, q, vr, off, r2o, cents, dev, st)
+        return
     if a.widek:
         search_widek(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st)
         return
@@ -357,6 +366,86 @@ def search_widek(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st):
                 rec["rescan_share_first_64_queries"] = round(share[p], 4)
                 rec["rescan_share_expected"] = round(KW / (16.0 * p), 4)
             print(json.dumps(rec), flush=True)
+
+
+def search_widek_u8(a, pkg, dim, q, vr, off, r2o, cents, dev, st):
+    """--u8 --widek K: the wide-k call on a from_u8 index (both scans on the byte rows), the same call on an index created
+    under VSEARCH_IVF_ND_WIDE_U8=0 (the fp32 launches: the yardstick, twice -- toggle_a and toggle_b, whose difference is the
+    spread a gain has to exceed) and the k = 10 call, alternated in one process, for every nprobe under the metrics of
+    --metric (l2, or l2 and ip).  Per leg: us per 1024 queries between two device events and the four list scans of a
+    group alone (vs_prof_read(.., 1): first scan and rescan, byte and fp32 parts together).  The legs' ids and bits are
+    asserted equal."""
+    import torch
+    rows_u8 = vr.astype(np.uint8)
+    assert np.array_equal(rows_u8.astype(np.float32), vr), "--u8 needs byte-valued rows"
+    KW = a.widek
+    qd = torch.from_numpy(q).to(dev)
+    nq, nbg = a.groups * GROUP_Q, GROUP_Q // B
+    ivf8 = pkg.IVFIndex.from_u8(rows_u8, cents, off, r2o)
+    os.environ["VSEARCH_IVF_ND_WIDE_U8"] = "0"
+    try:
+        tog = pkg.IVFIndex.from_u8(rows_u8, cents, off, r2o)
+    finally:
+        os.environ.pop("VSEARCH_IVF_ND_WIDE_U8", None)
+    del rows_u8
+    with ivf8, tog:
+        for metric in ([pkg.METRIC_L2] if a.metric == "l2" else [pkg.METRIC_L2, pkg.METRIC_IP]):
+            for p in [int(x) for x in a.nprobe.split(",")]:
+                legs = [("bytes", ivf8, KW), ("toggle_a", tog, KW), ("k10", ivf8, K), ("toggle_b", tog, KW)]
+                out = {n: (torch.empty((nq, k), dtype=torch.int32, device=dev), torch.empty((nq, k), dtype=torch.float32, device=dev))
+                       for n, _, k in legs}
+
+                def run(name, index, k):
+                    for g in range(a.groups):
+                        o = g * GROUP_Q
+                        index.search_metric_dev_multi(qd[o].data_ptr(), nbg, B, k, p, metric, out[name][0][o].data_ptr(),
+                                                      out[name][1][o].data_ptr(), st)
+
+                for leg in legs:  # warm-up; the counters of one pass
+                    run(*leg)
+                ivf8.nd_widek_u8_stats(reset=True)
+                tog.nd_widek_u8_stats(reset=True)
+                for leg in legs:
+                    run(*leg)
+                torch.cuda.synchronize()
+                counters = ivf8.nd_widek_u8_stats()
+                assert tog.nd_widek_u8_stats() == (0, 0, 0, 0)
+                for n in ("toggle_a", "toggle_b"):
+                    assert torch.equal(out[n][0], out["bytes"][0]) and torch.equal(out[n][1].view(torch.int32), out["bytes"][1].view(torch.int32)), \
+                        f"the byte route differs from the fp32 launches at nprobe {p}, metric {metric}"
+                us, scan = {n: [] for n, _, _ in legs}, {n: [] for n, _, _ in legs}
+                for _ in range(a.reps):
+                    for leg in legs:
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        run(*leg)
+                        e1.record()
+                        e1.synchronize()
+                        us[leg[0]].append(e0.elapsed_time(e1) * 1e3 / a.groups)
+                for _ in range(a.reps):
+                    for leg in legs:
+                        leg[1].prof_enable(True)
+                        run(*leg)
+                        torch.cuda.synchronize()
+                        ms, n = leg[1].prof_read(1)
+                        leg[1].prof_enable(False)
+                        scan[leg[0]].append(ms / max(n, 1) * 1e3)
+                med = lambda v: sorted(v)[len(v) // 2]
+                t = 0.5 * (med(us["toggle_a"]) + med(us["toggle_b"]))
+                ts = 0.5 * (med(scan["toggle_a"]) + med(scan["toggle_b"]))
+                for name, _, k in legs:
+                    rec = {"what": "widek_u8", "leg": name, "dim": dim, "rows": a.rows, "nlist": a.nlist, "k": k, "nprobe": p,
+                           "metric": "ip" if metric == pkg.METRIC_IP else "l2", "us_per_1024": [round(u, 1) for u in us[name]],
+                           "median_us": round(med(us[name]), 1), "scans_us_per_group": [round(u, 1) for u in scan[name]],
+                           "scans_median_us": round(med(scan[name]), 1)}
+                    if name == "bytes":
+                        rec["speedup_vs_toggle"] = round(t / med(us[name]), 3)
+                        rec["scans_speedup_vs_toggle"] = round(ts / med(scan[name]), 3)
+                        rec["first_pairs_bytes_fp32_rescan_pairs_bytes_fp32"] = list(counters)
+                    if name == "toggle_b":
+                        rec["toggle_spread"] = round(abs(med(us["toggle_a"]) - med(us["toggle_b"])) / t, 4)
+                        rec["toggle_scans_spread"] = round(abs(med(scan["toggle_a"]) - med(scan["toggle_b"])) / ts, 4)
+                    print(json.dumps(rec), flush=True)
 
 
 def search_ip(a, pkg, dim, base, q, vr, off, r2o, cents, dev, st):
