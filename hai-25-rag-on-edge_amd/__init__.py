@@ -130,6 +130,8 @@ def lib():
         "vs_bf_create_nd": (i32, [vp, i64, i32, i32, i32, i64, C.POINTER(vp)]),
         "vs_bf_create_nd_u8": (i32, [vp, i64, i32, i32, i64, C.POINTER(vp)]),
         "vs_bf_create_nd_u8_metric": (i32, [vp, i64, i32, i32, i32, i64, C.POINTER(vp)]),
+        "vs_bf_create_nd_f16": (i32, [vp, i64, i32, i32, i32, i64, C.POINTER(vp)]),
+        "vs_bf_f16_rows_read": (i32, [vp, i64, i64, vp]),
         "vs_set_batch": (i32, [vp, i32]),
         "vs_set_precision": (i32, [vp, i32]),
         "vs_ivf_set_metric": (i32, [vp, i32]),
@@ -440,6 +442,29 @@ class BruteForceIndex(_Index):
         _check(lib().vs_bf_create_nd_u8_metric(_p(base), self.n, self.d, metric, device, id_offset, C.byref(self._h)))
         self.d = self.getDim()
         return self
+
+    @classmethod
+    def from_f16(cls, base_f16, metric: int = METRIC_L2, device: int = 0, id_offset: int = 0):
+        """An index over float16 rows [N, d] (vs_bf_create_nd_f16): the half rows are its only row storage, and every
+        call returns what it returns on ``BruteForceIndex(base_f16.astype(np.float32), metric)``, bit for bit."""
+        base = np.asarray(base_f16)
+        if base.dtype != np.float16:
+            raise ValueError("base_f16 must have dtype float16")
+        if base.ndim != 2:
+            raise ValueError("base must be [N, d]")
+        base = np.ascontiguousarray(base)
+        self = cls.__new__(cls)
+        _Index.__init__(self)
+        self.n, self.d = base.shape
+        _check(lib().vs_bf_create_nd_f16(_p(base), self.n, self.d, metric, device, id_offset, C.byref(self._h)))
+        self.d = self.getDim()
+        return self
+
+    def f16_rows(self, row0: int, n: int) -> np.ndarray:
+        """Stored rows [row0, row0 + n) of a ``from_f16`` index as float16 [n, d], in row order (vs_bf_f16_rows_read)."""
+        out = np.empty((n, self.d), dtype=np.float16)
+        _check(lib().vs_bf_f16_rows_read(self._h, row0, n, _p(out)))
+        return out
 
     def filter_image(self, row0: int, n: int) -> np.ndarray:
         """Rows [row0, row0 + n) of the prefilter's bf16 row image as uint16 [n, d rounded up to 32], in row order

@@ -105,6 +105,11 @@ struct vs_index {
     vs::DevBuf<int32_t> d_nd_rsum;   // [n_rows + 64] sum (b - 128) (inner-product indexes, vs_bf_create_nd_u8_metric)
     vs::DevBuf<int8_t> d_nd_q8frag;  // [kMaxMulti][dim_b / 64][2][64][16] scratch of launch_scan_nd_i8
     vs::DevBuf<int32_t> d_nd_qterm;  // [kMaxMulti][32]
+    // general index made from float16 rows (vs_bf_create_nd_f16): the half rows are its ONLY row storage --
+    // d_vecs, d_img and the byte fields stay empty, nd_one and nd_filter are off -- scanned by scan_nd_f16_kernel in
+    // every mode (scan_any); d_norm holds the squared norms of the widened rows
+    int dim_h = 0;                   // dim rounded up to 32 halves
+    vs::DevBuf<uint16_t> d_nd_f16;   // [n_rows + 64][dim_h] in launch_scan_nd_f16's layout, zero padded
     vs::DevBuf<unsigned long long> d_wide_cnt;  // brute force: [2] wide batches scanned on the byte rows | sent to the fp32 rows by their verdict
     // general IVF index from uint8 rows: [0..1] (query, probe) pairs of k <= 16 groups planned on bytes | on fp32
     // (vs_ivf_nd_u8_stats); [2..5] the four counters of vs_ivf_nd_widek_u8_stats
@@ -453,7 +458,7 @@ int alloc_scratch(vs_index* h) {
     scan_geometry(std::max<int64_t>(h->n_rows, 1), h->num_cus, h->max_grid, tp);
     h->max_grid = std::max(h->max_grid, h->num_cus);
     if ((rc = h->d_q.alloc((size_t)kMaxMulti * 32 * h->dim))) return rc;
-    if (h->general && ((rc = h->d_nd_qfrag.alloc((size_t)kMaxMulti * 32 * h->dim_p)) || (rc = h->d_nd_qnorm.alloc((size_t)kMaxMulti * 32))))
+    if (h->general && ((rc = h->d_nd_qfrag.alloc((size_t)kMaxMulti * 32 * std::max(h->dim_p, h->dim_h))) || (rc = h->d_nd_qnorm.alloc((size_t)kMaxMulti * 32))))
         return rc;
     {
         const char* e = getenv("VSEARCH_LANES");
@@ -829,10 +834,23 @@ inline bool nd_u8_path(const vs_index* h, bool force_f32) {
     return h->general && h->d_nd_u8 && h->precision != 1 && !force_f32 && (h->metric == VS_METRIC_IP ? (bool)h->d_nd_rsum : (bool)h->d_nd_rterm);
 }
 
+// the half rows of an index made by vs_bf_create_nd_f16 from row r0 on (null on any other index): ScanParams::base_f16
+inline const uint16_t* f16_rows_at(const vs_index* h, int64_t r0) { return h->d_nd_f16 ? h->d_nd_f16 + (size_t)r0 * h->dim_h : nullptr; }
+
 // the per-batch scan of an index: scan_kernel on 128-d rows, scan_nd_kernel on a general index -- or, for a top-k launch
-// whose caller set the byte fields of p (bf_launch, under nd_u8_path), scan_nd_i8_kernel on its byte copy
+// whose caller set the byte fields of p (bf_launch, under nd_u8_path), scan_nd_i8_kernel on its byte copy; an index with
+// half rows has no other rows: scan_nd_f16_kernel in every mode, on p.base_f16
 hipError_t scan_any(vs_index* h, const vs::ScanParams& p, int grid, int kcap, int nqh, int mode, hipStream_t s) {
     if (!h->general) return vs::launch_scan(p, grid, kcap, nqh, mode, s);
+    if (h->d_nd_f16) {
+        vs::ScanNdF16Params hp{};
+        hp.s = p;
+        hp.dim = h->dim;
+        hp.dim_h = h->dim_h;
+        hp.qfrag = h->d_nd_qfrag;
+        hp.qnorm = h->d_nd_qnorm;
+        return vs::launch_scan_nd_f16(hp, grid, kcap, nqh, mode, s);
+    }
     if (p.base_u8 && mode == vs::kModeTopK) {
         vs::ScanNdI8Params bp{};
         bp.s = p;
@@ -958,6 +976,7 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     const int nqh = B <= 16 ? 1 : 2;
     vs::ScanParams p{};
     p.base = h->d_vecs;
+    p.base_f16 = f16_rows_at(h, 0);
     p.bnorm = h->d_norm;
     p.q = q_dev;
     p.n_batches = nb;
@@ -1331,11 +1350,13 @@ int bf_multi_dev(vs_index* h, const float* q_dev, int nb, int B, int k1, float* 
     return VS_OK;
 }
 
+// (vecs_f16: the same rows of an index with half rows, f16_rows_at; vecs is then not read)
 int scores_dev(vs_index* h, const float* vecs, const float* norms, int64_t rows, const float* q_dev, int B,
-               float* scores, int64_t ld, hipStream_t s, const int32_t* run_if = nullptr) {
+               float* scores, int64_t ld, hipStream_t s, const int32_t* run_if = nullptr, const uint16_t* vecs_f16 = nullptr) {
     vs::ScanParams p{};
     p.run_if = run_if;
     p.base = vecs;
+    p.base_f16 = vecs_f16;
     p.bnorm = norms;
     p.q = q_dev;
     p.metric = h->metric;
@@ -1459,7 +1480,7 @@ int topw_launch(vs_index* h, const float* q_dev, int nb, int B, int k1, float* o
             scan_geometry(l0, h->num_cus, sgrid, stp);
             HIPCHK(vs::launch_scan_nd_i8_wide(sp, sgrid, nqh8, vs::kModeStore, s));
         }
-        if ((rc = scores_dev(h, h->d_vecs, h->d_norm, l0, qb, B, W.pre, l0p, s, not_bytes))) return rc;
+        if ((rc = scores_dev(h, h->d_vecs, h->d_norm, l0, qb, B, W.pre, l0p, s, not_bytes, f16_rows_at(h, 0)))) return rc;
         vs::TopkWideParams t{};
         t.dense = W.pre;
         t.dense_ld = l0p;
@@ -1484,6 +1505,7 @@ int topw_launch(vs_index* h, const float* q_dev, int nb, int B, int k1, float* o
         HIPCHK(vs::launch_topk_wide(t, 32, s));
         vs::ScanParams p{};
         p.base = h->d_vecs;
+        p.base_f16 = f16_rows_at(h, 0);
         p.bnorm = h->d_norm;
         p.q = qb;
         p.n_batches = 1;
@@ -1542,7 +1564,8 @@ int topw_launch(vs_index* h, const float* q_dev, int nb, int B, int k1, float* o
         const int nc = W.n_chunks;
         for (int c = 0; c < nc; ++c) {
             const int64_t r0 = (int64_t)c * W.chunk, rows = std::min(W.chunk, n - r0);
-            if ((rc = scores_dev(h, h->d_vecs + (size_t)r0 * row_ld(h), h->d_norm + r0, rows, qb, B, W.full, W.chunk, s, overflow)))
+            if ((rc = scores_dev(h, h->d_nd_f16 ? nullptr : h->d_vecs + (size_t)r0 * row_ld(h), h->d_norm + r0, rows, qb, B, W.full, W.chunk, s, overflow,
+                                 f16_rows_at(h, r0))))
                 return rc;
             vs::TopkWideParams d{};
             d.dense = W.full;
@@ -2674,6 +2697,10 @@ int vs_bf_filter_image_read(const vs_index* h, int64_t row0, int64_t n, uint16_t
 float vs_f32_filter_cnorm(double bnmax) { return vs::filter_cnorm(bnmax); }
 float vs_f32_filter_th2(float thr, float e, float cnorm) { return vs::filter_th2(thr, e, cnorm); }
 int vs_bf_filter_stats(vs_index* h, int64_t* out, int reset) {
+    if (h && out && h->d_nd_f16) {  // half rows: no image is kept, the route is never taken
+        out[0] = out[1] = out[2] = out[3] = 0;
+        return VS_OK;
+    }
     if (!h || !out || !(h->filter_ok || h->nd_filter) || !h->filter_stats) {
         set_error("vs_bf_filter_stats: an index with the bf16 prefilter and an output of four words");
         return VS_ERR_INVALID;
@@ -2952,6 +2979,102 @@ int vs_bf_create_nd_u8_metric(const uint8_t* base_host, int64_t n_rows, int dim,
         return bf_create_impl(f.data(), n_rows, dim, VS_METRIC_IP, device, id_offset, out, true, base_host, true);
     });
 }
+// float16 rows: always the general form, and the half rows are all it stores.  The rows go up in chunks of
+// at most kF16ChunkBytes in row order, and nd_f16_layout_kernel writes each chunk's stored layout and norms: the base is
+// never widened on the host.
+constexpr size_t kF16ChunkBytes = (size_t)64 << 20;
+int vs_bf_create_nd_f16(const uint16_t* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset, vs_index** out) {
+    return guarded([&]() -> int {
+        if (!out || !base_host || n_rows <= 0) {
+            set_error("vs_bf_create_nd_f16: bad arguments");
+            return VS_ERR_INVALID;
+        }
+        if (dim < 1) {
+            set_error("vs_bf_create_nd_f16: dim must be at least 1");
+            return VS_ERR_INVALID;
+        }
+        if (dim > vs::kNdMaxDim) {
+            set_error("vs_bf_create_nd_f16: dim > 2048 is not compiled in");
+            return VS_ERR_UNSUPPORTED;
+        }
+        if (metric != VS_METRIC_L2 && metric != VS_METRIC_IP) {
+            set_error("vs_bf_create_nd_f16: metric must be VS_METRIC_L2 or VS_METRIC_IP");
+            return VS_ERR_INVALID;
+        }
+        if (n_rows + id_offset > std::numeric_limits<int32_t>::max()) {
+            set_error("ids must fit int32");
+            return VS_ERR_UNSUPPORTED;
+        }
+        int rc = check_device(device);
+        if (rc) return rc;
+        HIPCHK(hipSetDevice(device));
+        vs_index* h = new (std::nothrow) vs_index();
+        if (!h) {
+            set_error("out of host memory");
+            return VS_ERR_NOMEM;
+        }
+        h->kind = 0;
+        h->device = device;
+        h->dim = dim;
+        h->general = true;
+        h->dim_p = vs::nd_dim_p(dim);
+        h->dim_h = vs::nd_dim_h(dim);
+        h->nd_one = h->nd_one_u8 = h->nd_wide_u8 = false;  // no route but scan_any's: nothing else could read these rows
+        h->metric = metric;
+        h->n_rows = h->n_total = n_rows;
+        h->id_offset = id_offset;
+        auto upload = [&]() -> int {
+            int r2;
+            const size_t total = ((size_t)n_rows + vs::kScanPadRows) * h->dim_h;
+            const int64_t chunk_rows = std::max<int64_t>(1, std::min<int64_t>(n_rows, (int64_t)(kF16ChunkBytes / ((size_t)dim * sizeof(uint16_t)))));
+            vs::DevBuf<uint16_t> stage;
+            if ((r2 = h->d_nd_f16.alloc(total)) || (r2 = h->d_norm.alloc((size_t)n_rows + 64)) || (r2 = stage.alloc((size_t)chunk_rows * dim)))
+                return r2;
+            // the spare rows and the norms behind the last row stay zero: block loads are not clamped
+            HIPCHK(hipMemset(h->d_nd_f16 + (size_t)n_rows * h->dim_h, 0, (size_t)vs::kScanPadRows * h->dim_h * sizeof(uint16_t)));
+            HIPCHK(hipMemset(h->d_norm + (size_t)n_rows, 0, 64 * sizeof(float)));
+            for (int64_t r0 = 0; r0 < n_rows; r0 += chunk_rows) {
+                const int64_t rows = std::min(chunk_rows, n_rows - r0);
+                HIPCHK(hipMemcpy(stage, base_host + (size_t)r0 * dim, (size_t)rows * dim * sizeof(uint16_t), hipMemcpyHostToDevice));
+                HIPCHK(vs::launch_nd_f16_layout(stage, rows, dim, h->d_nd_f16 + (size_t)r0 * h->dim_h, h->d_norm + r0, nullptr));
+            }
+            HIPCHK(hipDeviceSynchronize());  // (before the staging buffer goes)
+            return VS_OK;
+        };
+        if ((rc = upload()) || (rc = alloc_scratch(h))) {
+            vs_destroy(h);
+            return rc;
+        }
+        *out = h;
+        return VS_OK;
+    });
+}
+
+// The stored half rows [row0, row0 + n) in row order: the inverse of the creator's permutation, on the host.  Blocking.
+int vs_bf_f16_rows_read(vs_index* h, int64_t row0, int64_t n, uint16_t* dst) {
+    if (!h || !dst || h->kind != 0 || !h->d_nd_f16 || row0 < 0 || n < 0 || row0 + n > h->n_rows) {
+        set_error("vs_bf_f16_rows_read: an index made by vs_bf_create_nd_f16 and a range inside it");
+        return VS_ERR_INVALID;
+    }
+    return guarded([&]() -> int {
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipDeviceSynchronize());
+        const size_t ld = (size_t)h->dim_h;
+        const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(kF16ChunkBytes / (ld * sizeof(uint16_t))));
+        std::vector<uint16_t> buf((size_t)std::min(chunk_rows, std::max<int64_t>(n, 1)) * ld);
+        for (int64_t r0 = 0; r0 < n; r0 += chunk_rows) {
+            const int64_t rows = std::min(chunk_rows, n - r0);
+            HIPCHK(hipMemcpy(buf.data(), h->d_nd_f16 + (size_t)(row0 + r0) * ld, (size_t)rows * ld * sizeof(uint16_t), hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < rows; ++i)
+                for (int pos = 0; pos < (int)ld; ++pos) {
+                    const int k = (pos & ~31) + vs::nd_f16_elem_at(pos & 31);
+                    if (k < h->dim) dst[(size_t)(r0 + i) * h->dim + k] = buf[(size_t)i * ld + pos];
+                }
+        }
+        return VS_OK;
+    });
+}
+
 static int bf_create_impl(const float* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset,
                           vs_index** out, bool any_dim, const uint8_t* rows_u8, bool force_general) {
     if (!out || !base_host || n_rows <= 0) {
@@ -3060,7 +3183,7 @@ int vs_set_precision(vs_index* h, int precision) {
         set_error("vs_set_precision: 0 = auto, 1 = fp32, 2 = int8");
         return VS_ERR_INVALID;
     }
-    if (precision == 2 && h->general && !h->nd_from_u8) return refuse_general(h, "vs_set_precision(2)");
+    if (precision == 2 && h->general && !h->nd_from_u8) return refuse_general(h, "vs_set_precision(2)");  // (half rows too: 0 and 1 both mean them)
     if (precision == 2 && h->general && !h->d_nd_u8) {
         set_error("vs_set_precision(2): max ||b||^2 >= 2^24 on this index: no batch could run on the byte rows");
         return VS_ERR_UNSUPPORTED;
@@ -3114,7 +3237,7 @@ int vs_bf_scores_dev(vs_index* h, const float* queries_dev, int B, float* scores
     if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((rc = order_begin(h, st))) return rc;
-    rc = scores_dev(h, h->d_vecs, h->d_norm, h->n_rows, queries_dev, B, scores_dev_, ld, st);
+    rc = scores_dev(h, h->d_vecs, h->d_norm, h->n_rows, queries_dev, B, scores_dev_, ld, st, nullptr, f16_rows_at(h, 0));
     return rc ? rc : order_end(h, st);
 }
 
@@ -4836,7 +4959,7 @@ int resolve_ties_shards(const Shards& S, const std::vector<int32_t>& meta /*[G][
         HIPCHK(hipMemcpyAsync(o->d_q, qbuf.data(), (size_t)B * qd * sizeof(float), hipMemcpyHostToDevice, st));
         if (S.first == 0) {
             vs_index* h0 = S.hs[0];
-            if ((rc = scores_dev(h0, h0->d_vecs, h0->d_norm, L0, o->d_q, B, dense0, L0p, st))) return rc;
+            if ((rc = scores_dev(h0, h0->d_vecs, h0->d_norm, L0, o->d_q, B, dense0, L0p, st, nullptr, f16_rows_at(h0, 0)))) return rc;
             if (total > L0) {  // rows follow the prefix: bound = next_up(k-th smallest of the dense rows)
                 HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(tau0), 0xff800000u, 32, st));  // -inf: padding queries emit nothing
                 if (k <= 15) {  // merge kernel over G = L0 one-entry lists
@@ -4873,6 +4996,7 @@ int resolve_ties_shards(const Shards& S, const std::vector<int32_t>& meta /*[G][
             if (h->n_rows <= rb) continue;
             vs::ScanParams p{};
             p.base = h->d_vecs;
+            p.base_f16 = f16_rows_at(h, 0);
             p.bnorm = h->d_norm;
             p.q = o->d_q;
             p.n_batches = 1;
@@ -4973,7 +5097,7 @@ int resolve_ties_shards(const Shards& S, const std::vector<int32_t>& meta /*[G][
                 vs_index* h = S.hs[i];
                 const int g = S.first + (int)i;
                 if ((rc = scores_dev(h, h->d_vecs, h->d_norm, h->n_rows, o->d_q + (size_t)b * qd, 1,
-                                     reinterpret_cast<float*>(Bf.row + (size_t)g * ldm), ldm, st)))
+                                     reinterpret_cast<float*>(Bf.row + (size_t)g * ldm), ldm, st, nullptr, f16_rows_at(h, 0))))
                     return rc;
             }
             if ((rc = S.exchange(Bf.row, (size_t)ldm, st))) return rc;

@@ -37,6 +37,7 @@ struct ScanParams {
     const float* bnorm;      // [n_rows (+64 pad)] squared norms (cpu_baseline.cpp:116-125)
     const int8_t* base_u8;   // int8 path: [n_rows][128] bytes (x - 128), or nullptr = fp32 path
     const int32_t* rterm;    // int8 path: [n_rows (+64 pad)] ||b||^2 - 256 * sum(b - 128)
+    const uint16_t* base_f16;  // launch_scan_nd_f16 only: the half rows, [n_rows + kScanPadRows][dim_h] in its stored layout (base is not read)
     int32_t* invalid;        // int8 path: [n_batches], set to 1 for a batch whose queries are not integers in [0, 255]
     const float* q;          // [n_batches][nq_valid][128] raw queries; rows up to 32 are zero-padded in-kernel (main.cpp:206-211)
     int n_batches;           // query batches served by this one persistent launch (1 for kModeStore)
@@ -86,6 +87,28 @@ struct ScanNdParams {
     float* qnorm;            // scratch [n_batches][32]
 };
 hipError_t launch_scan_nd(const ScanNdParams& p, int grid, int kcap, int nqh, int mode, hipStream_t s);
+// Its preparation launch alone (nd_prep_kernel), for n_batches batches: qfrag [n_batches][dim_p / 16][2][64][4] and qnorm
+// [n_batches][32] of queries q [n_batches][nq_valid][dim]; dim_p any multiple of 16 >= dim (zero padded).
+hipError_t launch_nd_prep(const float* q, int64_t q_batch_stride, int nq_valid, int dim, int dim_p, float* qfrag, float* qnorm,
+                          const int32_t* run_if, int n_batches, hipStream_t s);
+
+// Scan of a general index whose rows are IEEE binary16 (vs_scan_nd_f16.hip): launch_scan_nd's contract in
+// kModeTopK / kModeStore / kModeFilter on s.base_f16 = [n_rows + kScanPadRows][dim_h] halves, dim_h = nd_dim_h(dim), zero
+// padded, every 32-half block permuted (stored position w holds element nd_f16_elem_at(w) of the block), with s.bnorm the
+// squared norms of the widened rows.  The halves are widened in registers and go through launch_scan_nd's chains: ids,
+// distance bits and flags are those of launch_scan_nd on the rows widened to float.  qfrag: scratch [n_batches][dim_h / 16][2][64][4].
+constexpr int nd_dim_h(int dim) { return (dim + 31) & ~31; }  // whole 64-byte segments of halves: one K step of 32 elements
+constexpr int nd_f16_elem_at(int w) { return (w & 4) ? 16 + 4 * (w >> 3) + (w & 3) : 4 * (w >> 3) + (w & 3); }
+struct ScanNdF16Params {
+    ScanParams s;
+    int dim, dim_h;
+    float* qfrag;
+    float* qnorm;            // scratch [n_batches][32]
+};
+hipError_t launch_scan_nd_f16(const ScanNdF16Params& p, int grid, int kcap, int nqh, int mode, hipStream_t s);
+// The creator's layout pass: `rows` half rows in row order [rows][dim] -> dst [rows][dim_h] in the stored layout, and
+// norm[rows] = their squared norms from the widened values in launch_row_sqnorm's summation order.
+hipError_t launch_nd_f16_layout(const uint16_t* src, int64_t rows, int dim, uint16_t* dst, float* norm, hipStream_t s);
 
 // Byte scan of a general index made from uint8 rows (vs_scan_nd_i8.hip): launch_scan_nd's kModeTopK contract
 // on s.base_u8 = [n_rows + kScanPadRows][dim_b] bytes (x - 128), dim_b = nd_dim_b(dim), zero padded, with

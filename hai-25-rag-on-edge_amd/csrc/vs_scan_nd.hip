@@ -285,13 +285,17 @@ static hipError_t launch_scan_nd_t(const ScanNdParams& p, int grid, hipStream_t 
     return hipGetLastError();
 }
 
+hipError_t launch_nd_prep(const float* q, int64_t q_batch_stride, int nq_valid, int dim, int dim_p, float* qfrag, float* qnorm,
+                          const int32_t* run_if, int n_batches, hipStream_t s) {
+    hipLaunchKernelGGL(nd_prep_kernel, dim3(n_batches), dim3(256), 0, s, q, q_batch_stride, nq_valid, dim, dim_p, qfrag, qnorm, run_if);
+    return hipGetLastError();
+}
+
 hipError_t launch_scan_nd(const ScanNdParams& p, int grid, int kcap, int nqh, int mode, hipStream_t s) {
     if (p.dim < 1 || p.dim > kNdMaxDim || p.dim_p != nd_dim_p(p.dim) || !p.qfrag || !p.qnorm || grid < 1 || grid > kSlotStride ||
         (p.s.row_begin & 15) || p.s.n_batches < 1 || (mode == kModeAssign && (!p.s.best_d || !p.s.best_i || nqh != 2)))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nd_prep_kernel, dim3(p.s.n_batches), dim3(256), 0, s, p.s.q, p.s.q_batch_stride, p.s.nq_valid, p.dim, p.dim_p,
-                       p.qfrag, p.qnorm, p.s.run_if);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_nd_prep(p.s.q, p.s.q_batch_stride, p.s.nq_valid, p.dim, p.dim_p, p.qfrag, p.qnorm, p.s.run_if, p.s.n_batches, s);
     if (e != hipSuccess) return e;
     if (mode == kModeStore) return nqh == 1 ? launch_scan_nd_t<1, 8, kModeStore>(p, grid, s) : launch_scan_nd_t<2, 8, kModeStore>(p, grid, s);
     if (mode == kModeAssign) return launch_scan_nd_t<2, 8, kModeAssign>(p, grid, s);  // (the builder's batches are 32 centroids wide)

@@ -302,6 +302,39 @@ VS_API int vs_bf_create_nd_u8(const uint8_t* base_host, int64_t n_rows, int dim,
 VS_API int vs_bf_create_nd_u8_metric(const uint8_t* base_host, int64_t n_rows, int dim, int metric,
                                      int device, int64_t id_offset, vs_index** out);
 
+/* A brute-force index over float16 rows, at any dimension 1 <= dim <= 2048, under squared L2 or
+ * inner product.  base_host is [n_rows][dim] IEEE binary16 bit patterns.  Checks, in this order
+ * (all but the last need no device; *out is written on success only): null pointers or
+ * n_rows <= 0: VS_ERR_INVALID; dim < 1: VS_ERR_INVALID; dim > 2048: VS_ERR_UNSUPPORTED; a metric
+ * other than VS_METRIC_L2 / VS_METRIC_IP: VS_ERR_INVALID; ids that do not fit int32:
+ * VS_ERR_UNSUPPORTED; no device: VS_ERR_DEVICE.
+ *
+ * The index is always the general form, at dim 128 too, and the half rows are its ONLY row
+ * storage: no fp32 rows, no bf16 image, no byte copy.  Device memory: 2 bytes per padded element
+ * (dim rounded up to 32) plus one float per row, the squared norm of the widened row.  The rows
+ * are uploaded and laid out in bounded chunks; the base is never widened on the host.
+ *
+ * A float16 value widens to fp32 exactly, subnormals included, and the scan widens in registers
+ * and runs the chains of the fp32 general scan in the same order.  CONTRACT: every call returns
+ * what the same call returns on vs_bf_create_nd(the rows widened to float, metric), bit for bit
+ * -- ids, distance bits, flags, the reference tie order of the host calls and the -0.0 of an
+ * exactly zero inner product.
+ *
+ * Calls accepted, with unchanged signatures and output layouts: vs_bf_search, vs_bf_search_topk,
+ * vs_bf_search_dev, vs_bf_search_dev_multi, vs_bf_search_topk_dev_multi, vs_bf_scores_dev,
+ * vs_set_batch, vs_index_rows, vs_index_dim, vs_prof_*, vs_destroy.  Every call runs the
+ * per-batch half-row kernel: there is no single-call route and no prefilter on this index
+ * (vs_bf_one_stats and vs_bf_filter_stats read zero).  vs_set_precision: 0 and 1 both mean the
+ * half rows, 2 returns VS_ERR_UNSUPPORTED.  The sharded calls, the virtual-shard calls and every
+ * vs_ivf_* call refuse it, like any general index. */
+VS_API int vs_bf_create_nd_f16(const uint16_t* base_host, int64_t n_rows, int dim, int metric,
+                               int device, int64_t id_offset, vs_index** out);
+
+/* Diagnostic, like vs_i16_rows_read: the stored rows [row0, row0 + n) of an index made by
+ * vs_bf_create_nd_f16 as [n][dim] half bit patterns in row order, whatever the device layout is.
+ * Blocking.  VS_ERR_INVALID for a range that leaves the index, or an index without half rows. */
+VS_API int vs_bf_f16_rows_read(vs_index* h, int64_t row0, int64_t n, uint16_t* dst);
+
 /* Fixed model batch, like QnnRunner::getBatchSize (QnnRunner.h:37); 1..32, default 32.
  * Larger query sets are processed in batches of this size, the last one
  * zero-padded (main.cpp:206-211). */

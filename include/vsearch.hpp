@@ -99,6 +99,15 @@ public:
     ExactSearch(const float* shard, int64_t rows, int dim, int64_t id_offset, int device, int metric = VS_METRIC_L2) {
         check((dim == 128 ? vs_bf_create : vs_bf_create_nd)(shard, rows, dim, metric, device, id_offset, &h_));
     }
+    // float16 rows (IEEE binary16 bit patterns): vs_bf_create_nd_f16 -- the half rows are the index's only storage, and
+    // every call returns what it returns on the rows widened to float
+    static ExactSearch fromF16(const uint16_t* rows_f16, int64_t rows, int dim, int metric = VS_METRIC_L2, int device = 0,
+                               int64_t id_offset = 0) {
+        vs_index* h = nullptr;
+        check(vs_bf_create_nd_f16(rows_f16, rows, dim, metric, device, id_offset, &h));
+        return ExactSearch(h);
+    }
+    ExactSearch(ExactSearch&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
     ~ExactSearch() { vs_destroy(h_); }
     ExactSearch(const ExactSearch&) = delete;
     ExactSearch& operator=(const ExactSearch&) = delete;
@@ -143,6 +152,7 @@ public:
     vs_index* handle() { return h_; }
 
 private:
+    explicit ExactSearch(vs_index* h) : h_(h) {}  // (fromF16)
     vs_index* h_ = nullptr;
 };
 
