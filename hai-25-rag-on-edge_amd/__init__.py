@@ -233,6 +233,7 @@ def lib():
         "vs_f32_filter_bound_nd": (C.c_float, [i32] + [C.c_double] * 6),
         "vs_f32_filter_nd_th": (C.c_float, [i32] + [C.c_float] * 4 + [C.c_double] * 2),
         "vs_bf_filter_nd_plan": (i32, [i64, i32, i32, i32, i32, vp]),
+        "vs_bf_filter_f16_plan": (i32, [i64, i32, i32, i32, i32, vp]),
         "vs_f32_filter_cnorm": (C.c_float, [C.c_double]),
         "vs_f32_filter_th2": (C.c_float, [C.c_float] * 3),
         "vs_bf_filter_stats": (i32, [vp, C.POINTER(i64), i32]),
@@ -446,7 +447,9 @@ class BruteForceIndex(_Index):
     @classmethod
     def from_f16(cls, base_f16, metric: int = METRIC_L2, device: int = 0, id_offset: int = 0):
         """An index over float16 rows [N, d] (vs_bf_create_nd_f16): the half rows are its only row storage, and every
-        call returns what it returns on ``BruteForceIndex(base_f16.astype(np.float32), metric)``, bit for bit."""
+        call returns what it returns on ``BruteForceIndex(base_f16.astype(np.float32), metric)``, bit for bit.  Long
+        ``search_dev_multi`` calls (4 to 32 batches, k <= 15) may take the f16 MFMA prefilter (``filter_f16_plan``;
+        ``VSEARCH_ND_F16_FILTER`` at creation: 0 = never, 2 = always), counted by ``filter_stats``."""
         base = np.asarray(base_f16)
         if base.dtype != np.float16:
             raise ValueError("base_f16 must have dtype float16")
@@ -833,6 +836,14 @@ def bf_filter_nd_plan(n_rows: int, dim: int, num_cus: int, n_batches: int, k: in
     launch group on a general fp32 index (vs_bf_filter_nd_plan; host only)."""
     out = (C.c_int64 * 6)()
     _check(lib().vs_bf_filter_nd_plan(n_rows, dim, num_cus, n_batches, k, out))
+    return tuple(int(x) for x in out)
+
+
+def filter_f16_plan(n_rows: int, dim: int, num_cus: int, n_batches: int, k: int):
+    """(takes the f16 prefilter, workgroups per pass, passes, column blocks per wave, sample rows, sample stride) of a
+    launch group on a ``BruteForceIndex.from_f16`` index (vs_bf_filter_f16_plan; host only)."""
+    out = (C.c_int64 * 6)()
+    _check(lib().vs_bf_filter_f16_plan(n_rows, dim, num_cus, n_batches, k, out))
     return tuple(int(x) for x in out)
 
 

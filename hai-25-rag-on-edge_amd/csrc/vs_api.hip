@@ -110,6 +110,14 @@ struct vs_index {
     // every mode (scan_any); d_norm holds the squared norms of the widened rows
     int dim_h = 0;                   // dim rounded up to 32 halves
     vs::DevBuf<uint16_t> d_nd_f16;   // [n_rows + 64][dim_h] in launch_scan_nd_f16's layout, zero padded
+    // ... and its f16 MFMA prefilter (build_nd_f16_filter): no image -- the stored rows are the sweep's operand --
+    // only the shard constants, the compact copy of the sample rows (as stored) and the prepared queries, in d_nd_qbf,
+    // d_nd_qbound, d_nd_qnp, d_nd_sample_norm, nd_sample_rows, nd_bnmax and filter_stats below.  nd_f16_filter: 0 = no route
+    // (VSEARCH_ND_F16_FILTER=0, a non-finite half, no memory), 1 = the launch groups of vs_bf_filter_f16_plan's rule, 2 =
+    // every group of >= 4 batches with k <= 15
+    int nd_f16_filter = 0;
+    vs::F16FilterStats f16_fstats{};
+    vs::DevBuf<uint16_t> d_nd_f16_sample;  // [nd_sample_rows + 64][dim_h]
     vs::DevBuf<unsigned long long> d_wide_cnt;  // brute force: [2] wide batches scanned on the byte rows | sent to the fp32 rows by their verdict
     // general IVF index from uint8 rows: [0..1] (query, probe) pairs of k <= 16 groups planned on bytes | on fp32
     // (vs_ivf_nd_u8_stats); [2..5] the four counters of vs_ivf_nd_widek_u8_stats
@@ -652,6 +660,68 @@ bool nd_filter_route(int64_t n_rows, int dim, int nb, int k1, bool always) {
     return always || (n_rows >= kNdFilterMinRows && n_rows <= kNdFilterMaxRows && dim >= kNdFilterMinDim && dim <= kNdFilterMaxDim);
 }
 
+// The f16 MFMA prefilter of an index made from float16 rows: the shard constants, the compact sample copy and
+// the prepared-query scratch -- no other device memory.  An accelerator, not a requirement: a shard with a half that is inf
+// or NaN (or non-finite maxima), memory that cannot be had or VSEARCH_ND_F16_FILTER=0 (the comparison toggle) leave the
+// index on the per-batch kernel.  VSEARCH_ND_FILTER is not read here.
+int build_nd_f16_filter(vs_index* h) {
+    const char* env = getenv("VSEARCH_ND_F16_FILTER");
+    const int mode = env ? atoi(env) : 1;
+    if (mode <= 0 || h->n_rows > 0x7fffffff - 2 * vs::kNdfUnitRows) return VS_OK;
+    auto give_up = [&]() {
+        (void)hipGetLastError();
+        vs::set_error("");
+        h->d_nd_f16_sample.reset();
+        h->d_nd_sample_norm.reset();
+        h->d_nd_qbf.reset();
+        h->d_nd_qbound.reset();
+        h->d_nd_qnp.reset();
+        h->filter_stats.reset();
+        return VS_OK;
+    };
+    int64_t srows, stride;
+    vs::ndf_sample(h->n_rows, &srows, &stride);
+    const size_t swords = ((size_t)srows + vs::kScanPadRows) * h->dim_h;
+    vs::DevBuf<unsigned long long> st;
+    if (st.alloc(4) != VS_OK || h->filter_stats.alloc(8) != VS_OK || h->d_nd_f16_sample.alloc(swords) != VS_OK ||
+        h->d_nd_sample_norm.alloc((size_t)srows + 64) != VS_OK || h->d_nd_qbf.alloc((size_t)kMaxMulti * 2 * (h->dim_h / 32) * 512) != VS_OK ||
+        h->d_nd_qbound.alloc((size_t)kMaxMulti * 32) != VS_OK || h->d_nd_qnp.alloc((size_t)kMaxMulti * 32) != VS_OK)
+        return give_up();
+    HIPCHK(hipMemset(st, 0, 4 * sizeof(unsigned long long)));
+    HIPCHK(hipMemset(h->filter_stats, 0, 8 * sizeof(unsigned long long)));
+    HIPCHK(hipMemset(h->d_nd_f16_sample, 0, swords * sizeof(uint16_t)));
+    HIPCHK(hipMemset(h->d_nd_sample_norm, 0, ((size_t)srows + 64) * sizeof(float)));
+    HIPCHK(vs::launch_nd_f16_stats(h->d_nd_f16, h->d_norm, h->n_rows, h->dim_h, st, nullptr));
+    HIPCHK(vs::launch_nd_f16_sample(h->d_nd_f16, h->d_norm, srows, stride, h->dim_h, h->d_nd_f16_sample, h->d_nd_sample_norm, nullptr));
+    unsigned long long v[4];
+    HIPCHK(hipMemcpy(v, st, sizeof(v), hipMemcpyDeviceToHost));
+    double b2;
+    memcpy(&b2, &v[0], sizeof(double));
+    memcpy(&h->nd_bnmax, &v[1], sizeof(double));
+    if (v[3] != 0 || !std::isfinite(b2) || !std::isfinite((float)h->nd_bnmax)) return give_up();
+    h->f16_fstats.bmax = sqrt(b2) * (1.0 + 1.0 / 4503599627370496.0);  // (rounded up: the square root rounds to nearest)
+    h->f16_fstats.has_sub = v[2] != 0 ? 1 : 0;
+    h->nd_sample_rows = srows;
+    h->nd_f16_filter = mode >= 2 ? 2 : 1;
+    return VS_OK;
+}
+
+// Which launch groups of an index with half rows take the f16 prefilter (vs_bf_filter_f16_plan's rule; bf_launch goes through
+// it): 4 to kMaxMulti batches and k <= 15, at the dimensions and shard sizes where the route was MEASURED faster than the
+// same library under VSEARCH_ND_F16_FILTER=0 by more than the spread of either leg (profiles/nd_f16_filter_bench.txt, DESIGN
+// 4.4h).  Everything else is reachable only under VSEARCH_ND_F16_FILTER=2 (`always`).  The route enqueues eight launches
+// against the per-batch route's four, as nd_filter_route's does, so a small shard can only lose.
+// Measured slower, and so left out (us per call at 4 / 8 / 16 / 32 batches, route against toggle): 262 144 rows at 384-d, 641 /
+// 1142 / 2151 / 4203 against 489 / 909 / 1782 / 3550; and 96-d at 1 M rows, where the legs cross (559 / 984 / 1848 / 3647 against
+// 523 / 996 / 1963 / 3885: slower at 4 batches, 1 - 7 % faster above).
+constexpr int64_t kNdF16FilterMinRows = 1000000;  // measured faster from here (1.49 x at 384-d, 4 batches, the smallest gain) ...
+constexpr int64_t kNdF16FilterMaxRows = 3000000;  // ... to here (2.25 - 3.22 x at 384-d)
+constexpr int kNdF16FilterMinDim = 384, kNdF16FilterMaxDim = 2048;  // measured at 384, 768, 1024 and 2048
+bool nd_f16_filter_route(int64_t n_rows, int dim, int nb, int k1, bool always) {
+    if (nb < 4 || nb > kMaxMulti || k1 < 2 || k1 > 16 || n_rows > 0x7fffffff - 2 * vs::kNdfUnitRows) return false;
+    return always || (n_rows >= kNdF16FilterMinRows && n_rows <= kNdF16FilterMaxRows && dim >= kNdF16FilterMinDim && dim <= kNdF16FilterMaxDim);
+}
+
 // byte copy of a general index made from uint8 rows: int8 (x - 128) rows padded to dim_b bytes, rterm = sum (b - 128)^2
 // over the real dim (dist = qterm + rterm - 2 q'.b', see vs_scan_nd_i8.hip), and max ||b||^2 for the exactness rule.
 // An inner-product brute-force index keeps rsum = sum (b - 128) per row instead of rterm (launch_ivf_nd_i8_rowsum).
@@ -998,9 +1068,12 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     // ... unless it has the bf16 image: a long call then takes its bounds from the sample rows, sweeps the
     // image once for all batches and keeps the per-batch scan as the fallback behind the overflow word
     const bool nd_filter = h->general && h->nd_filter && !nd_u8_path(h, force_f32) && nd_filter_route(h->n_rows, h->dim, nb, k1, h->nd_filter == 2);
+    // ... or, with half rows, their f16 prefilter: the same eight launches on the stored rows
+    const bool f16_filter = h->d_nd_f16 && h->nd_f16_filter && nd_f16_filter_route(h->n_rows, h->dim, nb, k1, h->nd_f16_filter == 2);
+    const bool nd_sweep = nd_filter || f16_filter;
     int grid, tp;
-    scan_geometry(h->n_rows, h->num_cus, grid, tp, seeded || nd_filter ? 0 : (u8_path ? 16 : 6) * vs::kScanWaves);
-    const bool exchange = !seeded && !nd_filter && grid >= 16 && tp >= (u8_path ? 16 : 6) * vs::kScanWaves && g_xchg_first_it >= 0;
+    scan_geometry(h->n_rows, h->num_cus, grid, tp, seeded || nd_sweep ? 0 : (u8_path ? 16 : 6) * vs::kScanWaves);
+    const bool exchange = !seeded && !nd_sweep && grid >= 16 && tp >= (u8_path ? 16 : 6) * vs::kScanWaves && g_xchg_first_it >= 0;
     const bool use_u8 = u8_path;
     // With the bounds known up front the batches need nothing from each other: the streaming scans (fp32: one batch per
     // pass; exact int8 rows: several batches per pass over the rows) hand out the tiles of ALL batches through one
@@ -1063,7 +1136,7 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
         }
         return VS_OK;
     }
-    if (seeded || use_u8 || nd_filter) {
+    if (seeded || use_u8 || nd_sweep) {
         int rc = ensure_wide(L);
         if (rc) return rc;
     }
@@ -1071,8 +1144,8 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     int32_t* const overflow = L.wide8.wcnt;
     int32_t* const invalid = L.wide8.wcnt ? L.wide8.wcnt + 16 : nullptr;
     // (cleared by the seed's query-preparation launch where there is one and nobody else writes the batches' verdict words)
-    const size_t zero_words = 64 + (stream || nd_filter ? (size_t)nb * 32 * kWideSub : 0);
-    const bool zero_in_seed = (seeded && (!use_u8 || i8_seed)) || nd_filter;  // (nd_filter: its query preparation clears them)
+    const size_t zero_words = 64 + (stream || nd_sweep ? (size_t)nb * 32 * kWideSub : 0);
+    const bool zero_in_seed = (seeded && (!use_u8 || i8_seed)) || nd_sweep;  // (nd_sweep: its query preparation clears them)
     if (L.wide8.wcnt && !zero_in_seed) HIPCHK(hipMemsetAsync(L.wide8.wcnt, 0, zero_words * sizeof(int32_t), s));
     if (seeded) {
         vs::SeedParams sp{};
@@ -1198,7 +1271,77 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
         HIPCHK(vs::launch_scan_nd_f32f(fp, g, s));
         prof_end(h, 0, s);
     }
-    const bool lists = stream || nd_filter;  // the scan's candidate lists are ranked, the per-batch scan is the fallback
+    if (f16_filter) {
+        const vs::NdFilterPlan g = vs::ndf_plan(h->n_rows, h->num_cus, nb);
+        // bounds: scan_nd_f16_kernel's own top-k on the compact sample copy, ranked by one merge launch into tau0 =
+        // next_up(k1-th best) for all 32 query slots of every batch; its preparation launch writes the fp32 fragments and
+        // norms of all nb batches (dim_p = dim_h), which the recheck reads
+        vs::ScanNdF16Params sn{};
+        sn.s = p;
+        sn.s.base_f16 = h->d_nd_f16_sample;
+        sn.s.bnorm = h->d_nd_sample_norm;
+        sn.s.row_begin = 0;
+        sn.s.row_end = h->nd_sample_rows;
+        sn.s.id_offset = 0;
+        sn.s.part_d = L.part_d;
+        sn.s.part_i = L.part_i;
+        sn.dim = h->dim;
+        sn.dim_h = h->dim_h;
+        sn.qfrag = h->d_nd_qfrag;
+        sn.qnorm = h->d_nd_qnorm;
+        int sgrid, stp;
+        scan_geometry(h->nd_sample_rows, h->num_cus, sgrid, stp);
+        sn.s.tiles_per_wg = stp;
+        prof_begin(h, 0, s);
+        HIPCHK(vs::launch_scan_nd_f16(sn, sgrid, kcap, 2, vs::kModeTopK, s));
+        vs::MergeParams mt{};
+        mt.part_d = L.part_d;
+        mt.part_i = L.part_i;
+        mt.G = sgrid;
+        mt.kin = kcap;
+        mt.nq = nb * vs::kMaxBatch;
+        mt.kout = k1;
+        mt.tau_out = L.tau0;
+        HIPCHK(vs::launch_merge_layout(mt, kcap, (int64_t)vs::kSlotStride * kcap, s));
+        p.tau0 = L.tau0;
+        vs::NdF16FilterParams fp{};
+        fp.rows = h->d_nd_f16;
+        fp.bnorm = h->d_norm;
+        fp.n_rows = h->n_rows;
+        fp.dim = h->dim;
+        fp.dim_h = h->dim_h;
+        fp.slabs = h->dim_h / 32;
+        fp.q = q_dev;
+        fp.q_batch_stride = (int64_t)B * h->dim;
+        fp.qfrag = h->d_nd_qfrag;
+        fp.qnorm = h->d_nd_qnorm;
+        fp.tau0 = L.tau0;
+        fp.qh = h->d_nd_qbf;
+        fp.qbound = h->d_nd_qbound;
+        fp.qnp = h->d_nd_qnp;
+        fp.zero = L.wide8.wcnt;
+        fp.zero_words = (int)zero_words;
+        fp.n_batches = nb;
+        fp.nq_valid = B;
+        fp.metric = h->metric;
+        fp.id_offset = (int32_t)h->id_offset;
+        fp.fstats = h->f16_fstats;
+        fp.bnmax = h->nd_bnmax;
+        fp.sink.wbuf = L.wide8.wbuf;
+        // (the buffers are allocated for 256 workgroups: a launch of fewer waves -- a small shard -- shares them out)
+        fp.sink.wcap = (int)((int64_t)kWideWaveCap * vs::kSlotStride / ((int64_t)g.grid * g.passes));
+        fp.sink.overflow = overflow;
+        fp.sink.cnt = L.wide8.wcnt + 64;
+        fp.sink.cand_d = L.wide8.wcand_d;
+        fp.sink.cand_i = L.wide8.wcand_i;
+        fp.sink.cap = kWideCap;
+        fp.sink.nsub = kWideSub;
+        fp.sink.stats = h->filter_stats;
+        ++h->filter_launches;
+        HIPCHK(vs::launch_scan_nd_f16f(fp, g, s));
+        prof_end(h, 0, s);
+    }
+    const bool lists = stream || nd_sweep;  // the scan's candidate lists are ranked, the per-batch scan is the fallback
     if (lists) {
         m.G = kWideSub;
         m.kin = kWideCap;
@@ -2663,6 +2806,34 @@ int vs_bf_filter_nd_plan(int64_t n_rows, int dim, int num_cus, int n_batches, in
     out[5] = g.sample_stride;
     return VS_OK;
 }
+int vs_bf_filter_f16_plan(int64_t n_rows, int dim, int num_cus, int n_batches, int k, int64_t* out) {
+    if (!out) {
+        set_error("vs_bf_filter_f16_plan: no output");
+        return VS_ERR_INVALID;
+    }
+    for (int i = 0; i < 6; ++i) out[i] = 0;
+    if (n_rows < 1 || num_cus < 1 || n_batches < 1 || k < 1) {
+        set_error("vs_bf_filter_f16_plan: n_rows, num_cus, n_batches and k must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (dim < 1) {
+        set_error("vs_bf_filter_f16_plan: dim must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (dim > vs::kNdMaxDim) {
+        set_error("vs_bf_filter_f16_plan: dim > 2048 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (!nd_f16_filter_route(n_rows, dim, n_batches, k + 1, false)) return VS_OK;
+    const vs::NdFilterPlan g = vs::ndf_plan(n_rows, num_cus, n_batches);
+    out[0] = 1;
+    out[1] = g.grid;
+    out[2] = g.passes;
+    out[3] = g.cbw;
+    out[4] = g.sample_rows;
+    out[5] = g.sample_stride;
+    return VS_OK;
+}
 // a general index: the image is kept in unit / slab / fragment order (vs_scan_nd_f32f.hip) and returned in row order
 static int nd_filter_image_read(const vs_index* h, int64_t row0, int64_t n, uint16_t* dst) {
     const int S = vs::ndf_slabs(h->dim_p), d32 = 32 * S;
@@ -2697,11 +2868,11 @@ int vs_bf_filter_image_read(const vs_index* h, int64_t row0, int64_t n, uint16_t
 float vs_f32_filter_cnorm(double bnmax) { return vs::filter_cnorm(bnmax); }
 float vs_f32_filter_th2(float thr, float e, float cnorm) { return vs::filter_th2(thr, e, cnorm); }
 int vs_bf_filter_stats(vs_index* h, int64_t* out, int reset) {
-    if (h && out && h->d_nd_f16) {  // half rows: no image is kept, the route is never taken
+    if (h && out && h->d_nd_f16 && !h->nd_f16_filter) {  // half rows without their prefilter: the route is never taken
         out[0] = out[1] = out[2] = out[3] = 0;
         return VS_OK;
     }
-    if (!h || !out || !(h->filter_ok || h->nd_filter) || !h->filter_stats) {
+    if (!h || !out || !(h->filter_ok || h->nd_filter || h->nd_f16_filter) || !h->filter_stats) {
         set_error("vs_bf_filter_stats: an index with the bf16 prefilter and an output of four words");
         return VS_ERR_INVALID;
     }
@@ -3041,7 +3212,7 @@ int vs_bf_create_nd_f16(const uint16_t* base_host, int64_t n_rows, int dim, int 
             HIPCHK(hipDeviceSynchronize());  // (before the staging buffer goes)
             return VS_OK;
         };
-        if ((rc = upload()) || (rc = alloc_scratch(h))) {
+        if ((rc = upload()) || (rc = alloc_scratch(h)) || (rc = build_nd_f16_filter(h))) {  // (the f16 prefilter for long calls: DESIGN 4.4h)
             vs_destroy(h);
             return rc;
         }

@@ -305,6 +305,46 @@ inline NdFilterPlan ndf_plan(int64_t n_rows, int num_cus, int n_batches) {
 }
 // (NdFilterParams and launch_scan_nd_f32f: behind CandSink, below)
 
+// ---- the prefilter on the half rows of a vs_bf_create_nd_f16 index (vs_scan_nd_f16f.hip) ----
+// The rows are NOT rounded: the stored halves are the MFMA's A operand.  With S = q.b exact, S_fl the fp32 chain of
+// scan_nd_f16_kernel (scan_nd_kernel's at dim_p = dim_h = dim rounded up to 32: launch_scan_nd_f16 pads to 32, so the
+// chain has dim_h steps, the padding adding exact zeros but counted), q' what ndf16_prep_kernel writes -- f16(q) by RNE,
+// f16 subnormals written as zero -- and S' the v_mfma_f32_16x16x32_f16 sum of q' and b:
+//   |S_fl - S'| <= |S_fl - S| + |S - q'.b| + |q'.b - S'|
+//               <= g32 ||q|| ||b||  +  e_q ||b||  +  (g16 ||q'|| ||b|| + sub)
+// with e_q = ||q - q'|| and S - q'.b = (q - q').b (Cauchy-Schwarz); filter_bound_nd's middle term ||q'|| e_b is zero
+// (emax = 0, bpmax = bmax).  g32(n) = n u / (1 - n u), u = 2^-24, n = dim_h (one rounding per fmaf).  f16 x f16 products
+// are exact in fp32 (11 + 11 = 22 significant bits).  B never holds a subnormal or a non-finite value (ndf16_round) and
+// the route exists only on shards of finite halves, so a product of two NORMAL halves has magnitude in [2^-28, 2^32):
+// normal in fp32, never flushed, never overflowing.  How the MFMA accumulates the products is not documented, so g16(m),
+// m = dim_h terms, keeps the worst-case assumption of filter_bound: a unit roundoff of 2^-22 per addition.  What is
+// not known either is whether the f16 MFMA honours or flushes SUBNORMAL A inputs; the proof rests on neither.  If it
+// honours them the products are exact as above (a subnormal half times a normal one is a normal or exactly
+// representable float).  If it flushes them, it drops the products a_k q'_k of the subnormal a_k: |a_k| < 2^-14, so what is
+// dropped is below sub = 2^-14 ||q'||_1 in magnitude.  sub is charged whenever the shard holds any subnormal half, and is
+// zero otherwise.  The 2^-100 absolute term covers partial sums that cancel into the fp32 subnormal range, as in
+// filter_bound.  Shard constant: ||b|| <= bmax, in double from the widened halves.  The result is rounded up to float.
+struct F16FilterStats {  // per shard, from launch_nd_f16_stats (index creation)
+    double bmax;         // max ||b||
+    int has_sub;         // 1 when any stored half is subnormal
+};
+__host__ __device__ inline float filter_bound_nd_f16(int dim, double eq, double nq, double nqp, double nqp1, const F16FilterStats& f) {
+    const double m = (double)((dim + 31) & ~31), n32 = m / 16777216.0, n16 = m / 4194304.0;
+    const double g32 = n32 / (1.0 - n32), g16 = n16 / (1.0 - n16);
+    const double sub = f.has_sub ? nqp1 / 16384.0 : 0.0;  // 2^-14 ||q'||_1
+    const double e = g32 * nq * f.bmax + eq * f.bmax + g16 * nqp * f.bmax + sub + 7.888609052210118e-31;  // + 2^-100
+    return (float)(e * (1.0 + 1.0 / 1048576.0));  // (the 2^-20 covers the rounding of the norms and of this cast)
+}
+// The hot test is filter_nd_th's with bpmax = bmax: its proof uses |S'| <= 1.01 ||q'|| ||b'||max, and b' = b here (a flush
+// of subnormal inputs only removes terms).
+// shard constants: out[0] = max ||b||^2 and out[1] = the largest stored norm as double bits, out[2] = 1 when a half is
+// subnormal, out[3] = 1 when a half or a stored norm is not finite; zeroed before
+hipError_t launch_nd_f16_stats(const uint16_t* rows, const float* bnorm, int64_t n_rows, int dim_h, unsigned long long* out, hipStream_t s);
+// stored rows i * stride, i < n, and their norms into the compact sample copy (whole rows, unchanged)
+hipError_t launch_nd_f16_sample(const uint16_t* rows, const float* bnorm, int64_t n, int64_t stride, int dim_h, uint16_t* out, float* out_norm,
+                                hipStream_t s);
+// (NdF16FilterParams and launch_scan_nd_f16f: behind CandSink, below)
+
 // Bounds for a multi-batch scan, computed up front on a sample of the rows: kSeedWaves 16-row tiles spread evenly
 // over the shard, scored against every batch; tau0[batch][q] = next_up of the k1-th smallest of 64 group minima
 // (groups of 32 tiles) -- an upper bound of the k1-th best distance, because k1 distinct rows are at least that
@@ -418,6 +458,31 @@ struct NdFilterParams {
 };
 // the preparation launch and the sweep
 hipError_t launch_scan_nd_f32f(const NdFilterParams& p, const NdFilterPlan& g, hipStream_t s);
+
+// the f16 prefilter of an index with half rows (above)
+struct NdF16FilterParams {
+    const uint16_t* rows;    // [n_rows + 64][dim_h] the stored half rows: the sweep's A operand and the recheck's rows
+    const float* bnorm;      // [n_rows + 64]
+    int64_t n_rows;
+    int dim, dim_h, slabs;   // slabs = dim_h / 32
+    const float* q;          // [n_batches][nq_valid][dim] raw queries
+    int64_t q_batch_stride;
+    const float* qfrag;      // ScanNdF16Params::qfrag / qnorm of these queries, written earlier in the stream (nd_prep_kernel at dim_p = dim_h)
+    const float* qnorm;
+    const float* tau0;       // [n_batches][32]
+    uint16_t* qh;            // scratch [2 n_batches][slabs][64][8] f16 B fragments in the stored k order
+    float* qbound;           // scratch [n_batches][32] E per query (+inf: a value f16 cannot hold, 0: padding)
+    float* qnp;              // scratch [n_batches][32] ||q'||, rounded up
+    int32_t* zero;           // zero_words words cleared by the preparation launch (overflow word, list counters)
+    int zero_words;
+    int n_batches, nq_valid, metric;
+    int32_t id_offset;
+    F16FilterStats fstats;
+    double bnmax;            // the shard's largest stored norm
+    CandSink sink;
+};
+// the preparation launch and the sweep; the geometry is ndf_plan's
+hipError_t launch_scan_nd_f16f(const NdF16FilterParams& p, const NdFilterPlan& g, hipStream_t s);
 
 struct WideParams {
     const int8_t* base_u8;   // [n_rows (+64)][128] bytes (x - 128)

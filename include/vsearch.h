@@ -322,9 +322,11 @@ VS_API int vs_bf_create_nd_u8_metric(const uint8_t* base_host, int64_t n_rows, i
  *
  * Calls accepted, with unchanged signatures and output layouts: vs_bf_search, vs_bf_search_topk,
  * vs_bf_search_dev, vs_bf_search_dev_multi, vs_bf_search_topk_dev_multi, vs_bf_scores_dev,
- * vs_set_batch, vs_index_rows, vs_index_dim, vs_prof_*, vs_destroy.  Every call runs the
- * per-batch half-row kernel: there is no single-call route and no prefilter on this index
- * (vs_bf_one_stats and vs_bf_filter_stats read zero).  vs_set_precision: 0 and 1 both mean the
+ * vs_set_batch, vs_index_rows, vs_index_dim, vs_prof_*, vs_destroy.  There is no single-call
+ * route on this index (vs_bf_one_stats reads zero).  A vs_bf_search_dev_multi launch group of
+ * 4 to 32 batches with k <= 15 may take the f16 MFMA prefilter on the half rows
+ * (vs_bf_filter_f16_plan; counted by vs_bf_filter_stats); every other call runs the per-batch
+ * half-row kernel, and the results are the same bits on either route.  vs_set_precision: 0 and 1 both mean the
  * half rows, 2 returns VS_ERR_UNSUPPORTED.  The sharded calls, the virtual-shard calls and every
  * vs_ivf_* call refuse it, like any general index. */
 VS_API int vs_bf_create_nd_f16(const uint16_t* base_host, int64_t n_rows, int dim, int metric,
@@ -1152,6 +1154,17 @@ VS_API float vs_f32_filter_nd_th(int metric, float tau, float qn, float e, float
  * there whatever dim and n_rows (tests, benchmark); 0 builds no image.  num_cus takes the place vs_bf_one_plan gives it.
  * Argument checks and their order: vs_bf_one_plan's. */
 VS_API int vs_bf_filter_nd_plan(int64_t n_rows, int dim, int num_cus, int n_batches, int k, int64_t* out /* [6] */);
+/* The same question for an index made by vs_bf_create_nd_f16: whether a vs_bf_search_dev_multi launch group
+ * takes the f16 MFMA prefilter on the stored half rows, and its geometry, out[0..5] as above (the sweep reads the stored
+ * rows: there is no image).  The route needs 4 <= n_batches <= 32 and k <= 15, a shard whose halves are all finite, and memory
+ * for the compact sample copy; it returns the ids, distance bits and flags of the per-batch half-row kernel, and
+ * vs_bf_filter_stats counts it with its four meanings.  The rule holds only the shapes that were measured faster than the
+ * same library under VSEARCH_ND_F16_FILTER=0 by more than the spread of either leg (profiles/nd_f16_filter_bench.txt):
+ * 384 <= dim <= 2048 and 1 000 000 <= n_rows <= 3 000 000.  Left out as measured slower: 262 144 rows (384-d) and 96-d at
+ * 4 batches (1 M rows); left out as not measured: everything else.  VSEARCH_ND_F16_FILTER, read at creation: 0 = no route (the comparison
+ * toggle), unset or 1 = the rule, 2 = every group of 4 to 32 batches with k <= 15 (tests, benchmark).  VSEARCH_ND_FILTER
+ * does not touch this index.  Argument checks and their order: vs_bf_filter_nd_plan's. */
+VS_API int vs_bf_filter_f16_plan(int64_t n_rows, int dim, int num_cus, int n_batches, int k, int64_t* out /* [6] */);
 /* The L2 test of the prefilter carries the row norm through the MFMA's C operand: a value S'' = bf16 dot -
  * norm / 2 passes when it is above th2.  vs_f32_filter_cnorm: the shard constant C of that test from the shard's largest
  * stored fp32 norm.  vs_f32_filter_th2: the bound th2 from the exact scan's hot-test bound thr (a row passes the exact
