@@ -161,6 +161,8 @@ def lib():
         "vs_bf_one_plan": (i32, [i64, i32, i32, i32, i32, i32, vp]),
         "vs_bf_one_plan_u8": (i32, [i64, i32, i32, i32, i32, i32, vp]),
         "vs_bf_one_stats": (i32, [vp, C.POINTER(i64), i32]),
+        "vs_bf_one_plan_f16": (i32, [i64, i32, i32, i32, i32, i32, vp]),
+        "vs_bf_one_f16_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_bf_wide_plan": (i32, [i64, i32, i32, vp]),
         "vs_bf_wide_stats": (i32, [vp, C.POINTER(i64), i32]),
         "vs_comm_unique_id": (i32, [vp]),
@@ -449,7 +451,9 @@ class BruteForceIndex(_Index):
         """An index over float16 rows [N, d] (vs_bf_create_nd_f16): the half rows are its only row storage, and every
         call returns what it returns on ``BruteForceIndex(base_f16.astype(np.float32), metric)``, bit for bit.  Long
         ``search_dev_multi`` calls (4 to 32 batches, k <= 15) may take the f16 MFMA prefilter (``filter_f16_plan``;
-        ``VSEARCH_ND_F16_FILTER`` at creation: 0 = never, 2 = always), counted by ``filter_stats``."""
+        ``VSEARCH_ND_F16_FILTER`` at creation: 0 = never, 2 = always), counted by ``filter_stats``.  Short calls (fewer
+        than 4 batches of at most 16 queries, k <= 15) are one launch per batch (``one_plan_f16``, counted by
+        ``one_f16_stats``; ``VSEARCH_ND_ONE_F16=0`` at creation keeps the per-batch route)."""
         base = np.asarray(base_f16)
         if base.dtype != np.float16:
             raise ValueError("base_f16 must have dtype float16")
@@ -563,6 +567,21 @@ class BruteForceIndex(_Index):
         out = (C.c_int64 * 2)()
         _check(lib().vs_bf_one_stats(self._h, out, 1 if reset else 0))
         return int(out[0]), int(out[1])
+
+    @staticmethod
+    def one_plan_f16(n_rows: int, dim: int, num_cus: int, n_batches: int, B: int, k: int):
+        """``one_plan`` for a call on the half rows of a ``from_f16`` index (vs_bf_one_plan_f16; host only): route 0 = no
+        single-call launch, 4 = the single-call half-row kernel, with route 2's geometry."""
+        out = (C.c_int64 * 4)()
+        _check(lib().vs_bf_one_plan_f16(n_rows, dim, num_cus, n_batches, B, k, out))
+        return tuple(int(x) for x in out)
+
+    def one_f16_stats(self, reset: bool = False) -> int:
+        """Single-call launches enqueued on the half rows of this ``from_f16`` index since the last reset
+        (vs_bf_one_f16_stats; counted on the host, no synchronisation)."""
+        out = (C.c_int64 * 1)()
+        _check(lib().vs_bf_one_f16_stats(self._h, out, 1 if reset else 0))
+        return int(out[0])
 
     @staticmethod
     def wide_plan(n_rows: int, dim: int, k: int):

@@ -107,8 +107,10 @@ struct vs_index {
     vs::DevBuf<int32_t> d_nd_qterm;  // [kMaxMulti][32]
     // general index made from float16 rows (vs_bf_create_nd_f16): the half rows are its ONLY row storage --
     // d_vecs, d_img and the byte fields stay empty, nd_one and nd_filter are off -- scanned by scan_nd_f16_kernel in
-    // every mode (scan_any); d_norm holds the squared norms of the widened rows
+    // every mode (scan_any) and by scan_one_nd_f16_kernel in short calls; d_norm holds the squared norms of the widened rows
     int dim_h = 0;                   // dim rounded up to 32 halves
+    bool nd_one_f16 = false;  // short calls on the half rows take scan_one_nd_f16_kernel (VSEARCH_ND_ONE_F16=0 at creation: off)
+    int64_t one_f16_stat = 0;  // single-call launches enqueued on the half rows (vs_bf_one_f16_stats; host side)
     vs::DevBuf<uint16_t> d_nd_f16;   // [n_rows + 64][dim_h] in launch_scan_nd_f16's layout, zero padded
     // ... and its f16 MFMA prefilter (build_nd_f16_filter): no image -- the stored rows are the sweep's operand --
     // only the shard constants, the compact copy of the sample rows (as stored) and the prepared queries, in d_nd_qbf,
@@ -1034,6 +1036,18 @@ int one_route_u8(int64_t n_rows, int dim, int num_cus, int nb, int B, int k1, in
     return one_route_nd(3, n_rows, num_cus, out);
 }
 
+// The single-call route of a short call that reads the half rows of a vs_bf_create_nd_f16 index (vs_bf_one_plan_f16's rule;
+// bf_launch goes through it): 0 = none, 4 = scan_one_nd_f16_kernel, with the geometry of route 2 in out[1..3].
+// No measured exception: at 1 M rows, k = 5, the route was faster than the per-batch route by more than either leg's
+// spread (< 0.5 %) at every shape timed -- 96- to 2048-d, 1.06 - 1.28 x at B = 1 and 1.016 - 1.082 x at B = 16, the
+// narrowest 96-d at B = 16 (98.1 against 99.6 us; profiles/nd_one_f16_bench.txt).  dim is here for the day one appears.
+int one_route_f16(int64_t n_rows, int dim, int num_cus, int nb, int B, int k1, int64_t* out) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    (void)dim;
+    if (!one_call_is_short(nb, B, k1)) return 0;
+    return one_route_nd(4, n_rows, num_cus, out);
+}
+
 // nb <= kMaxMulti batches of B queries in ONE persistent launch on stream s (preceded by the seed launches or the
 // slot reset, followed by one merge launch), outputs [nb][B][k1].  Consecutive calls on one lane must be stream-ordered.
 int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B, int k1, float* out_d, int32_t* out_i,
@@ -1092,6 +1106,9 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     // ... and a short call on the byte rows of a general index goes to scan_one_nd_i8_kernel, unless the
     // index was created under VSEARCH_ND_ONE_U8=0
     if (!reads_f32 && h->general && h->nd_one_u8) one_route_u8(h->n_rows, h->dim, h->num_cus, nb, B, k1, one_plan);
+    // ... and a short call on the half rows to scan_one_nd_f16_kernel, unless the index was created under
+    // VSEARCH_ND_ONE_F16=0 (nd_one and nd_one_u8 are off on such an index: nothing above has answered)
+    if (h->d_nd_f16 && h->nd_one_f16) one_route_f16(h->n_rows, h->dim, h->num_cus, nb, B, k1, one_plan);
     if (one_plan[0]) {
         for (int b = 0; b < nb; ++b) {
             vs::OneParams op{};
@@ -1112,8 +1129,19 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
             op.flags = flags ? flags + (size_t)b * B : nullptr;
             op.dbg = g_dbg;
             if (b == 0) prof_begin(h, 0, s);
-            ++h->one_stat[one_plan[0] == 3 ? 1 : 0];
-            if (one_plan[0] == 3) {
+            if (one_plan[0] == 4)
+                ++h->one_f16_stat;  // (vs_bf_one_stats keeps counting the fp32 and the byte rows only)
+            else
+                ++h->one_stat[one_plan[0] == 3 ? 1 : 0];
+            if (one_plan[0] == 4) {
+                vs::OneNdF16Params fp{};
+                fp.o = op;
+                fp.o.base = nullptr;  // (the index has no fp32 rows)
+                fp.dim = h->dim;
+                fp.dim_h = h->dim_h;
+                fp.base_f16 = f16_rows_at(h, 0);
+                HIPCHK(vs::launch_scan_one_nd_f16(fp, (int)one_plan[1], s));
+            } else if (one_plan[0] == 3) {
                 vs::OneNdI8Params bp{};
                 bp.o = op;
                 bp.dim = h->dim;
@@ -3190,7 +3218,9 @@ int vs_bf_create_nd_f16(const uint16_t* base_host, int64_t n_rows, int dim, int 
         h->general = true;
         h->dim_p = vs::nd_dim_p(dim);
         h->dim_h = vs::nd_dim_h(dim);
-        h->nd_one = h->nd_one_u8 = h->nd_wide_u8 = false;  // no route but scan_any's: nothing else could read these rows
+        h->nd_one = h->nd_one_u8 = h->nd_wide_u8 = false;  // no route of the fp32 or the byte rows could read these
+        h->nd_one_f16 = true;                               // short calls: one launch per batch on the half rows
+        if (const char* e = getenv("VSEARCH_ND_ONE_F16")) h->nd_one_f16 = atoi(e) != 0;  // (the measurement's other leg)
         h->metric = metric;
         h->n_rows = h->n_total = n_rows;
         h->id_offset = id_offset;
@@ -4477,6 +4507,28 @@ int vs_bf_one_plan_u8(int64_t n_rows, int dim, int num_cus, int n_batches, int B
     return VS_OK;
 }
 
+// one_route_f16 for the ABI (host only): vs_bf_one_plan's checks in its order; VSEARCH_ND_ONE_F16 is not its business
+int vs_bf_one_plan_f16(int64_t n_rows, int dim, int num_cus, int n_batches, int B, int k, int64_t* out) {
+    if (!out || n_rows < 1 || num_cus < 1 || n_batches < 1 || B < 1 || B > vs::kMaxBatch || k < 1) {
+        set_error("vs_bf_one_plan_f16: bad arguments (out != NULL, n_rows, num_cus, n_batches, k >= 1, 1 <= B <= 32)");
+        return VS_ERR_INVALID;
+    }
+    if (dim < 1) {
+        set_error("vs_bf_one_plan_f16: dim must be at least 1");
+        return VS_ERR_INVALID;
+    }
+    if (dim > vs::kNdMaxDim) {
+        set_error("vs_bf_one_plan_f16: dim > 2048 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    if (k > vs::kTopkWideMax - 1) {
+        set_error("vs_bf_one_plan_f16: k > 128 is not compiled in");
+        return VS_ERR_UNSUPPORTED;
+    }
+    one_route_f16(n_rows, dim, num_cus, n_batches, B, k + 1, out);
+    return VS_OK;
+}
+
 // wide_route_u8 and topw_prefix for the ABI (host only); whether an index keeps a byte copy, its precision setting and
 // VSEARCH_ND_WIDE_U8 are not its business
 int vs_bf_wide_plan(int64_t n_rows, int dim, int k, int64_t* out) {
@@ -4532,6 +4584,16 @@ int vs_bf_one_stats(vs_index* h, int64_t* out, int reset) {
     out[0] = h->one_stat[0];
     out[1] = h->one_stat[1];
     if (reset) h->one_stat[0] = h->one_stat[1] = 0;
+    return VS_OK;
+}
+
+int vs_bf_one_f16_stats(vs_index* h, int64_t* out, int reset) {
+    if (!h || h->kind != 0 || !h->d_nd_f16 || !out) {
+        set_error("vs_bf_one_f16_stats: an index made by vs_bf_create_nd_f16 and an output of one word");
+        return VS_ERR_INVALID;
+    }
+    out[0] = h->one_f16_stat;
+    if (reset) h->one_f16_stat = 0;
     return VS_OK;
 }
 

@@ -623,6 +623,17 @@ struct OneNdI8Params {
 };
 hipError_t launch_scan_one_nd_i8(const OneNdI8Params& p, int grid, hipStream_t s);
 
+// ... and on the half rows of a vs_bf_create_nd_f16 index (vs_scan_one_nd_f16.hip): one launch per batch of
+// <= 16 queries, k1 <= 16, under either metric.  o.base is not read; o.bnorm = the squared norms of the widened rows;
+// o.q = [nq_valid][dim] unpadded floats (the kernel pads them to dim_h and works out their norms itself).  Distances, ids
+// and flags are launch_scan_nd_f16's to the bit.  Units and geometry: scan_one_nd_geometry.
+struct OneNdF16Params {
+    OneParams o;
+    int dim, dim_h;
+    const uint16_t* base_f16;  // [n_rows + kScanPadRows][dim_h] halves in launch_scan_nd_f16's stored layout
+};
+hipError_t launch_scan_one_nd_f16(const OneNdF16Params& p, int grid, hipStream_t s);
+
 // Cross-workgroup merge of sorted partial lists -> [nq][kout] + tie flags (+ seed thresholds).
 struct MergeParams {
     const float* part_d;     // [G][nq_stride][kin]

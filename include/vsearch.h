@@ -193,6 +193,28 @@ VS_API int vs_bf_one_plan_u8(int64_t n_rows, int dim, int num_cus, int n_batches
  * VS_ERR_INVALID. */
 VS_API int vs_bf_one_stats(vs_index* h, int64_t* out /* [2] */, int reset);
 
+/* The same for a call on the half rows of an index made by vs_bf_create_nd_f16 (k <= 15): fewer
+ * than 4 batches of at most 16 queries on at most 2^31 - 1 - 128 rows are ONE launch per batch
+ * of the single-call half-row kernel, under either metric, instead of a
+ * preparation launch, a reset, the per-batch half-row scan and a merge launch.  Results do not
+ * depend on the route: ids, distance bits and flags are those of the per-batch half-row scan.
+ * VSEARCH_ND_ONE_F16=0, read when the index is created, keeps the per-batch route for short
+ * calls on that index: the comparison toggle.
+ *   out[0] = 0: no single-call launch; 4: the single-call half-row kernel
+ *   out[1..3] as for vs_bf_one_plan's route 2 (workgroups, 64 rows per unit, the most units of
+ *            any one wave); 0 with out[0] = 0
+ * Host only; the launch code takes its decision and geometry through the same function.  The
+ * toggle is not its business.  Checks and codes: vs_bf_one_plan's, in the same order. */
+VS_API int vs_bf_one_plan_f16(int64_t n_rows, int dim, int num_cus, int n_batches, int B, int k,
+                              int64_t* out /* [4] */);
+
+/* Single-call launches enqueued on the half rows of an index made by vs_bf_create_nd_f16 since
+ * the last reset (route 4 of vs_bf_one_plan_f16; vs_bf_one_stats counts the fp32 and the byte
+ * rows only and keeps reading zero on such an index).  Counted on the host when a launch is
+ * enqueued; no device synchronisation.  reset != 0 clears it after reading.  Null pointers or
+ * an index without half rows: VS_ERR_INVALID. */
+VS_API int vs_bf_one_f16_stats(vs_index* h, int64_t* out /* [1] */, int reset);
+
 /* Wide k on the byte rows (host only, no GPU needed).  A wide call (16 <= k <= 128) spends most
  * of its time in two bulk passes per batch: the distances to a prefix of the rows, and a
  * filtered pass over the rest that keeps what falls under the prefix's bound.  On a general
@@ -322,11 +344,14 @@ VS_API int vs_bf_create_nd_u8_metric(const uint8_t* base_host, int64_t n_rows, i
  *
  * Calls accepted, with unchanged signatures and output layouts: vs_bf_search, vs_bf_search_topk,
  * vs_bf_search_dev, vs_bf_search_dev_multi, vs_bf_search_topk_dev_multi, vs_bf_scores_dev,
- * vs_set_batch, vs_index_rows, vs_index_dim, vs_prof_*, vs_destroy.  There is no single-call
- * route on this index (vs_bf_one_stats reads zero).  A vs_bf_search_dev_multi launch group of
- * 4 to 32 batches with k <= 15 may take the f16 MFMA prefilter on the half rows
- * (vs_bf_filter_f16_plan; counted by vs_bf_filter_stats); every other call runs the per-batch
- * half-row kernel, and the results are the same bits on either route.  vs_set_precision: 0 and 1 both mean the
+ * vs_set_batch, vs_index_rows, vs_index_dim, vs_prof_*, vs_destroy.  A short call (fewer than 4
+ * batches of at most 16 queries, k <= 15) is ONE launch per batch of the single-call half-row
+ * kernel (vs_bf_one_plan_f16; counted by vs_bf_one_f16_stats, while vs_bf_one_stats keeps
+ * reading zero here; VSEARCH_ND_ONE_F16=0 at creation keeps the per-batch route).  A
+ * vs_bf_search_dev_multi launch group of 4 to 32 batches with k <= 15 may take the f16 MFMA
+ * prefilter on the half rows (vs_bf_filter_f16_plan; counted by vs_bf_filter_stats); every other
+ * call runs the per-batch half-row kernel.  Results do not depend on the route: the same bits
+ * on all three.  vs_set_precision: 0 and 1 both mean the
  * half rows, 2 returns VS_ERR_UNSUPPORTED.  The sharded calls, the virtual-shard calls and every
  * vs_ivf_* call refuse it, like any general index. */
 VS_API int vs_bf_create_nd_f16(const uint16_t* base_host, int64_t n_rows, int dim, int metric,
