@@ -822,10 +822,29 @@ int g_seed_min_batches = [] {
     return v > 0 ? v : 1 << 30;
 }();
 
+// tuning knob (VSEARCH_SEED_I8): 0 = the seed always runs on the fp32 rows (also turns the wide int8 scan off), 1 = on the
+// exact int8 copy with one batch per workgroup (seed_kernel), 2 (default) = on the int8 copy with a block of consecutive
+// batches per workgroup (seed_block_kernel)
 int g_seed_i8 = [] {
     const char* e = getenv("VSEARCH_SEED_I8");
-    return e ? atoi(e) : 1;
+    return e ? atoi(e) : 2;
 }();
+// tuning knob (VSEARCH_SEED_NB): batches per block of seed_block_kernel at every launch size, 2 or 4 (anything else: the
+// rule of seed_block)
+int g_seed_nb = [] {
+    const char* e = getenv("VSEARCH_SEED_NB");
+    const int v = e ? atoi(e) : 0;
+    return v == 2 || v == 4 ? v : 0;
+}();
+// Batches per block of the int8 seed for a launch of nb batches (0 = one batch per workgroup).  A block of NB batches
+// fetches a sample tile once per NB batches but leaves 64 ceil(nb / NB) workgroups with NB times the serial work each:
+// measured per launch group at 1 M rows, blocks of 4 win at 32 batches (-3.5 %) and lose at 4 and 8 (+3.6 %,
+// +1.7 %), blocks of 2 win at 8 to 20 (-0.4 % to -1.9 %) and lose at 4 (+1 %).
+static int seed_block(int nb) {
+    if (g_seed_i8 < 2) return 0;
+    if (g_seed_nb) return g_seed_nb;
+    return nb >= 24 ? 4 : (nb >= 8 ? 2 : 0);
+}
 
 // tuning knob (VSEARCH_I8_WIDE): query column blocks per pass of the wide int8 scan (8 = four 32-query batches share one
 // pass over the rows, 4 = two, 0 = off: the per-batch int8 scan)
@@ -1186,6 +1205,7 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
             sp.rterm = h->d_rterm;
             sp.sample_u8 = h->d_seed_u8;
             sp.sample_rterm = h->d_seed_rterm;
+            sp.seed_block = seed_block(nb);
         }
         sp.n_rows = h->n_rows;
         sp.q = q_dev;

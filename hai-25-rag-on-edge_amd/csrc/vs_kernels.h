@@ -362,6 +362,10 @@ struct SeedParams {
     const int32_t* sample_rterm; // [kSeedWaves][16]
     const int8_t* base_u8;   // optional exact int8 copy (x - 128) + row terms: the seed then runs on v_mfma_i32_16x16x64_i8
     const int32_t* rterm;    //   (16x fewer MFMA cycles) for batches whose queries are byte valued too (q8 / qterm / invalid below are then required)
+    // with base_u8: consecutive batches whose byte queries one wave of the seed keeps resident and scores every loaded sample
+    // tile against (2 or 4: seed_block_kernel), or 0 = one batch per workgroup (seed_kernel).  The minima are exact integers
+    // either way: same wmin, same tau0.
+    int seed_block;
     int64_t n_rows;
     const float* q;          // [n_batches][nq_valid][128]
     int n_batches;

@@ -10,8 +10,8 @@ namespace vs {
 
 // ------------------------------------------------------------------------------------------------
 // Seed bounds (see SeedParams).  seed_qnorm_kernel: ||q||^2 in the reference's order (+ the queries as bytes for the
-// int8 paths); seed_kernel: minima of 64 groups of 32 sample tiles per (batch, query); seed_tau_kernel: k1-th smallest
-// of a query's 64 group minima.
+// int8 paths); seed_kernel / seed_block_kernel: minima of 64 groups of 32 sample tiles per (batch, query), one batch or a
+// block of batches per workgroup; seed_tau_kernel: k1-th smallest of a query's 64 group minima.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void seed_qnorm_kernel(const SeedParams p) {
     // blockIdx.y = which of the batch's outputs: 0 norms (+ bytes, terms, verdict), 1 the fp32 fragments, 2 the byte fragments
@@ -248,6 +248,85 @@ __device__ __forceinline__ void seed_body_i8(const SeedParams& p, int batch, int
     }
 }
 
+// The same for NB consecutive batches at once (seed_block_kernel): the byte queries of the block's batches (bit b of `live`
+// set: byte valued and inside the launch) stay resident as B operands, 16 registers per batch, and every loaded sample tile
+// is scored against all of them -- a tile is fetched once per block instead of once per batch, a batch's queries once per
+// (block, group) instead of once per (batch, group) with NB times the loads in front of them.  Batches not in `live` load
+// nothing and give +inf.  m[b][h] is seed_body_i8's m[h] of batch batch0 + b bit for bit: the distance of (row j, query r)
+// is qterm[r] + rt[j] - 2 acc[j] as an exact integer, qterm is constant in a lane, int -> float is monotone, so
+// min_j (float)(qterm + rt[j] - 2 acc[j]) = (float)(qterm - max_j (2 acc[j] - rt[j])): one shift-add and one max per value
+// instead of two adds, a conversion and a masked min.  A row past the end of the shard (or a tile past its last one) takes
+// part with -rt = kSeedMasked, below every real 2 acc - rt (|2 acc| <= 2^22, |rt| < 2^25), and is recognised at the end.
+constexpr int kSeedMasked = -(1 << 30);
+template <int NB, int U>
+__device__ __forceinline__ void seed_body_i8_block(const SeedParams& p, int batch0, unsigned live, int chunk, int wv, int r, int g,
+                                                   float (&m)[NB][2]) {
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    const int64_t tiles_total = (p.n_rows + kTileRows - 1) / kTileRows;
+    i32x4 qi[NB][2][2];
+    int qterm[NB][2], mx[NB][2];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            mx[b][h] = -2147483647 - 1;
+            qterm[b][h] = 0;
+            qi[b][h][0] = qi[b][h][1] = (i32x4){0, 0, 0, 0};
+            if ((live >> b) & 1u) {  // (workgroup-uniform)
+                const int qrow = h * 16 + r;
+                const int8_t* src = p.q8 + ((int64_t)(batch0 + b) * kMaxBatch + qrow) * kDim;  // padding queries are all-zero rows
+                qi[b][h][0] = *reinterpret_cast<const i32x4*>(src + 16 * g);
+                qi[b][h][1] = *reinterpret_cast<const i32x4*>(src + 64 + 16 * g);
+                qterm[b][h] = p.qterm[(batch0 + b) * kMaxBatch + qrow];
+            }
+        }
+    }
+    for (int t0 = wv * (kSeedTilesPerWave / 4); t0 < (wv + 1) * (kSeedTilesPerWave / 4); t0 += U) {
+        i32x4 a0[U], a1[U], nrt[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int smp = chunk * kSeedTilesPerWave + t0 + u;
+            const int64_t tile = seed_tile(tiles_total, smp);
+            const bool ok = tile < tiles_total;  // wave-uniform
+            const int64_t row0 = (ok ? tile : 0) * kTileRows;
+            // rows of this lane's four (4 g ..) inside the shard: row0 + 4 g + j < n_rows as a 32-bit compare per value
+            const int left = ok ? (int)min((int64_t)kTileRows, p.n_rows - row0) - 4 * g : 0;
+            i32x4 rt;
+            if (p.sample_u8) {  // compact copy in fragment order (1 KB per instruction)
+                const int8_t* sp = p.sample_u8 + ((int64_t)smp * 2 * 64 + (16 * g + r)) * 16;
+                a0[u] = *reinterpret_cast<const i32x4*>(sp);
+                a1[u] = *reinterpret_cast<const i32x4*>(sp + 64 * 16);
+                rt = *reinterpret_cast<const i32x4*>(p.sample_rterm + smp * 16 + 4 * g);
+            } else {
+                a0[u] = *reinterpret_cast<const i32x4*>(p.base_u8 + (row0 + r) * kDim + 16 * g);
+                a1[u] = *reinterpret_cast<const i32x4*>(p.base_u8 + (row0 + r) * kDim + 64 + 16 * g);
+                rt = *reinterpret_cast<const i32x4*>(p.rterm + row0 + 4 * g);  // padded by 64
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) nrt[u][j] = j < left ? -rt[j] : kSeedMasked;
+        }
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            if (!((live >> b) & 1u)) continue;  // (workgroup-uniform)
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    i32x4 acc = {0, 0, 0, 0};
+                    acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0[u], qi[b][h][0], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1[u], qi[b][h][1], acc, 0, 0, 0);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) mx[b][h] = max(mx[b][h], 2 * acc[j] + nrt[u][j]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) m[b][h] = mx[b][h] < kSeedMasked / 2 ? VS_INF : (float)(qterm[b][h] - mx[b][h]);
+}
+
 // A batch's bounds from its 64 group minima per query: a wave per query (n_waves waves share the 32 queries), lane l holds
 // group minimum l, k1 rounds of a wave minimum.
 __device__ __forceinline__ void seed_tau_body(const SeedParams& p, const int batch, const int lane, const int wave, const int n_waves) {
@@ -299,6 +378,68 @@ __global__ __launch_bounds__(256) void seed_kernel(const SeedParams p) {
     // the wait for them and 64 atomics per batch made this kernel take 28 instead of 14 us per 20 batches.)
 }
 
+// The seed on the exact int8 copy with one workgroup per (block of NB consecutive batches, group of 32 sample tiles): the
+// four waves take 8 tiles each as in seed_kernel, U of them in flight per step, and score them against every byte-valued
+// batch of the block (seed_body_i8_block).  A batch of the block that is not byte valued (block-uniform, rare) is scored on
+// the fp32 rows afterwards, one batch at a time, by the same workgroup; the last block of a launch may be short.  wmin has
+// seed_kernel's layout and values.
+// (Two waves per SIMD as the minimum: within 256 registers the MFMAs write plain vector registers; allowed 512, the compiler
+// put the accumulators into AGPRs and paid a v_accvgpr_read per value.  The wave index as a scalar keeps the tile
+// addresses and the row mask in scalar registers.)
+template <int NB, int U>
+__global__ __launch_bounds__(256, 2) void seed_block_kernel(const SeedParams p) {
+    __shared__ float wm[NB][4][kMaxBatch];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int batch0 = ((int)blockIdx.x / kSeedChunks) * NB, chunk = (int)blockIdx.x % kSeedChunks;
+    const int nbv = min(NB, p.n_batches - batch0);  // batches of this block
+    const int r = lane & 15, g = lane >> 4;
+    unsigned live = 0, other = 0;
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+        if (b < nbv) {
+            if (p.invalid[batch0 + b] == 0) live |= 1u << b;
+            else other |= 1u << b;
+        }
+    float m[NB][2];
+    seed_body_i8_block<NB, U>(p, batch0, live, chunk, wv, r, g, m);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            m[b][h] = fminf(m[b][h], __shfl_xor(m[b][h], 16));
+            m[b][h] = fminf(m[b][h], __shfl_xor(m[b][h], 32));
+        }
+        if (g == 0) {
+            wm[b][wv][r] = m[b][0];
+            wm[b][wv][16 + r] = m[b][1];
+        }
+    }
+    if (other) {  // (block-uniform)
+#pragma unroll 1
+        for (int b = 0; b < nbv; ++b) {
+            if (!((other >> b) & 1u)) continue;
+            float mf[2] = {VS_INF, VS_INF};
+            seed_body_f32(p, batch0 + b, chunk, wv, r, g, mf);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                mf[h] = fminf(mf[h], __shfl_xor(mf[h], 16));
+                mf[h] = fminf(mf[h], __shfl_xor(mf[h], 32));
+            }
+            if (g == 0) {
+                wm[b][wv][r] = mf[0];
+                wm[b][wv][16 + r] = mf[1];
+            }
+        }
+    }
+    __syncthreads();
+    const int b = (int)threadIdx.x / kMaxBatch, qq = (int)threadIdx.x % kMaxBatch;  // (256 threads = 8 batches of 32 queries)
+    if (b < nbv) {
+        float* dst = p.wmin + ((int64_t)(batch0 + b) * kSeedChunks + chunk) * kMaxBatch;  // 128 contiguous bytes per (batch, group)
+        dst[qq] = fminf(fminf(wm[b][0][qq], wm[b][1][qq]), fminf(wm[b][2][qq], wm[b][3][qq]));
+    }
+}
+
 __global__ __launch_bounds__(1024) void seed_tau_kernel(const SeedParams p) {
     seed_tau_body(p, blockIdx.x, threadIdx.x & 63, threadIdx.x >> 6, 16);
 }
@@ -340,8 +481,17 @@ hipError_t launch_seed_sample(const float* base, const float* bnorm, const int8_
 
 hipError_t launch_seed(const SeedParams& p, hipStream_t s) {
     hipLaunchKernelGGL(seed_qnorm_kernel, dim3(p.n_batches, p.zero ? 4 : 3), dim3(256), 0, s, p);
-    const int wgs = p.n_batches * kSeedChunks;  // one workgroup per (batch, group of sample tiles)
-    hipLaunchKernelGGL(seed_kernel, dim3(wgs), dim3(256), 0, s, p);
+    if (p.base_u8 && p.seed_block) {  // one workgroup per (block of batches, group of sample tiles)
+        const int nb = p.seed_block, wgs = (p.n_batches + nb - 1) / nb * kSeedChunks;
+        switch (nb) {  // (blocks of 8 batches, and 8 tiles per step, were measured slower at every launch size: DESIGN 4.1)
+        case 2: hipLaunchKernelGGL((seed_block_kernel<2, 4>), dim3(wgs), dim3(256), 0, s, p); break;
+        case 4: hipLaunchKernelGGL((seed_block_kernel<4, 4>), dim3(wgs), dim3(256), 0, s, p); break;
+        default: return hipErrorInvalidValue;
+        }
+    } else {
+        const int wgs = p.n_batches * kSeedChunks;  // one workgroup per (batch, group of sample tiles)
+        hipLaunchKernelGGL(seed_kernel, dim3(wgs), dim3(256), 0, s, p);
+    }
     hipLaunchKernelGGL(seed_tau_kernel, dim3(p.n_batches), dim3(1024), 0, s, p);
     return hipGetLastError();
 }
