@@ -144,6 +144,7 @@ def lib():
         "vs_ivf_load": (i32, [C.c_char_p, i32, i32, i32, C.POINTER(vp)]),
         "vs_ivf_create": (i32, [vp, i64, i32, vp, i32, vp, vp, i32, i32, i32, C.POINTER(vp)]),
         "vs_ivf_create_nd_u8": (i32, [vp, i64, i32, vp, i32, vp, vp, i32, C.POINTER(vp)]),
+        "vs_ivf_create_nd_f16": (i32, [vp, i64, i32, vp, i32, vp, vp, i32, C.POINTER(vp)]),
         "vs_ivf_build": (i32, [vp, i64, i32, i32, i32, C.c_double, C.c_uint64, i32, vp, vp, C.POINTER(i32)]),
         "vs_ivf_build_nd": (i32, [vp, i64, i32, i32, i32, C.c_double, C.c_uint64, i32, vp, vp, C.POINTER(i32)]),
         "vs_ivf_build_index_nd": (i32, [vp, i64, i32, i32, i32, C.c_double, C.c_uint64, i32, C.POINTER(vp), C.POINTER(i32)]),
@@ -890,7 +891,10 @@ class IVFIndex(_Index):
     Any vector length 1 <= d <= 2048: 128-d arrays or directories give the specialised index, any other dimension a
     general IVF index (fp32 rows, squared L2, k <= 16, one GPU; vsearch.h at vs_ivf_create).  ``from_u8`` takes uint8
     rows instead (vs_ivf_create_nd_u8): at dimensions other than 128 the general index keeps a byte copy of the rows
-    beside the fp32 ones and scans it with int8 MFMA for every query that is byte valued itself; same results."""
+    beside the fp32 ones and scans it with int8 MFMA for every query that is byte valued itself; same results.
+    ``from_f16`` takes float16 rows (vs_ivf_create_nd_f16): always the general index, the half rows are its only row
+    storage (half the memory and list-scan traffic), k <= 16, and every result equals the fp32 index's on the rows
+    widened to float."""
 
     def __init__(self, index_dir: str | None = None, device: int = 0, rank: int = 0, world: int = 1, *,
                  vectors_reordered=None, centroids=None, cluster_offsets=None, reorder_to_original=None):
@@ -949,6 +953,37 @@ class IVFIndex(_Index):
             raise ValueError("base_u8 must be [N, d]")
         vr, off, r2o, cents, it = ivf_build(base.astype(np.float32), n_clusters, max_iter, tol, seed, device)
         return cls.from_u8(vr.astype(np.uint8), cents, off, r2o, device), it
+
+    @classmethod
+    def from_f16(cls, vectors_reordered_f16, centroids, cluster_offsets, reorder_to_original, device: int = 0):
+        """An index over float16 rows [N, d] in the reordered layout (vs_ivf_create_nd_f16); centroids stay float."""
+        v = np.asarray(vectors_reordered_f16)
+        if v.dtype != np.float16:
+            raise ValueError("vectors_reordered_f16 must have dtype float16")
+        if v.ndim != 2:
+            raise ValueError("vectors_reordered_f16 must be [N, d]")
+        v = np.ascontiguousarray(v)
+        c = _f32c(centroids)
+        off = np.ascontiguousarray(cluster_offsets, dtype=np.int32)
+        r2o = None if reorder_to_original is None else np.ascontiguousarray(reorder_to_original, dtype=np.int32)
+        self = cls.__new__(cls)
+        _Index.__init__(self)
+        _check(lib().vs_ivf_create_nd_f16(_p(v), v.shape[0], v.shape[1], _p(c), c.shape[0], _p(off),
+                                          _p(r2o) if r2o is not None else None, device, C.byref(self._h)))
+        self.d = self.getDim()
+        return self
+
+    @classmethod
+    def build_f16(cls, base_f16, n_clusters: int, max_iter: int = 100, tol: float = 1e-4, seed: int = 42, device: int = 0):
+        """ivf_build on the float16 rows widened to float, then from_f16 on the reordered rows cast back (exact: the
+        reordered rows are the input's rows); returns (index, n_iter)."""
+        base = np.asarray(base_f16)
+        if base.dtype != np.float16:
+            raise ValueError("base_f16 must have dtype float16")
+        if base.ndim != 2:
+            raise ValueError("base_f16 must be [N, d]")
+        vr, off, r2o, cents, it = ivf_build(base.astype(np.float32), n_clusters, max_iter, tol, seed, device)
+        return cls.from_f16(vr.astype(np.float16), cents, off, r2o, device), it
 
     def nd_u8_stats(self, reset: bool = False):
         """(pairs planned on the byte rows, pairs planned on the fp32 rows) of a from_u8 general index since the last

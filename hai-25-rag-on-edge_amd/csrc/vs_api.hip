@@ -112,6 +112,10 @@ struct vs_index {
     bool nd_one_f16 = false;  // short calls on the half rows take scan_one_nd_f16_kernel (VSEARCH_ND_ONE_F16=0 at creation: off)
     int64_t one_f16_stat = 0;  // single-call launches enqueued on the half rows (vs_bf_one_f16_stats; host side)
     vs::DevBuf<uint16_t> d_nd_f16;   // [n_rows + 64][dim_h] in launch_scan_nd_f16's layout, zero padded
+    // (kind 1, vs_ivf_create_nd_f16, DESIGN 4.6f: the same field holds the cluster-reordered half rows of a general IVF
+    // index, again its only row storage -- d_vecs and the byte fields stay empty, ivf_one is off -- scanned by
+    // ivf_scan_nd_f16_kernel; centroids stay fp32 rows of dim_p floats.  Every brute-force path that tests this field
+    // is behind a kind == 0 check.)
     // ... and its f16 MFMA prefilter (build_nd_f16_filter): no image -- the stored rows are the sweep's operand --
     // only the shard constants, the compact copy of the sample rows (as stored) and the prepared queries, in d_nd_qbf,
     // d_nd_qbound, d_nd_qnp, d_nd_sample_norm, nd_sample_rows, nd_bnmax and filter_stats below.  nd_f16_filter: 0 = no route
@@ -291,7 +295,7 @@ struct vs_index {
     struct IvfNd {
         int np_max = 0;              // probes per query the buffers hold: min(kMaxNprobe, nlist)
         vs::DevBuf<int32_t> probes;  // [kIvfNdGroupQ][np_max]
-        vs::DevBuf<float> qrows;     // [kIvfNdGroupQ][dim_p]
+        vs::DevBuf<float> qrows;     // [kIvfNdGroupQ][dim_p] (an index with half rows: [kIvfNdGroupQ][dim_h])
         vs::DevBuf<float> qnorm;     // [kIvfNdGroupQ]
         vs::DevBuf<int32_t> plan;    // list_cnt [2][nlist] | list_start [nlist + 1] | n_items [1]
         vs::DevBuf<int32_t> slots;   // [kIvfNdGroupQ * np_max]
@@ -933,7 +937,7 @@ inline const uint16_t* f16_rows_at(const vs_index* h, int64_t r0) { return h->d_
 // half rows has no other rows: scan_nd_f16_kernel in every mode, on p.base_f16
 hipError_t scan_any(vs_index* h, const vs::ScanParams& p, int grid, int kcap, int nqh, int mode, hipStream_t s) {
     if (!h->general) return vs::launch_scan(p, grid, kcap, nqh, mode, s);
-    if (h->d_nd_f16) {
+    if (h->kind == 0 && h->d_nd_f16) {  // (an IVF index with half rows scans its fp32 centroid table here)
         vs::ScanNdF16Params hp{};
         hp.s = p;
         hp.dim = h->dim;
@@ -981,6 +985,15 @@ int refuse_general_ivf(const vs_index* h, const char* what) {
              "%s: not available on a general-dimension IVF index (dim = %d): %ssquared L2, k <= 16, one GPU (inner product and k <= 128: "
              "vs_ivf_search_metric)",
              what, h->dim, h->nd_from_u8 ? "" : "fp32 rows, ");
+    set_error(msg);
+    return VS_ERR_UNSUPPORTED;
+}
+
+// ... and what an IVF index with half rows leaves out beside that (vs_ivf_create_nd_f16): the wide-k kernels read fp32 rows
+int refuse_wide_k_f16(const vs_index* h, const char* what) {
+    if (!h || h->kind != 1 || !h->d_nd_f16) return VS_OK;
+    char msg[200];
+    snprintf(msg, sizeof(msg), "%s: 17 <= k <= 128 is not available on an IVF index with float16 half rows (dim = %d): k <= 16", what, h->dim);
     set_error(msg);
     return VS_ERR_UNSUPPORTED;
 }
@@ -1870,7 +1883,7 @@ int ensure_ivf_nd(vs_index* h) {
     int rc;
     W.np_max = std::min(kMaxNprobe, h->nlist);
     const size_t gq = vs::kIvfNdGroupQ, pairs = gq * W.np_max;
-    if ((rc = W.probes.alloc(pairs)) || (rc = W.qrows.alloc(gq * h->dim_p)) || (rc = W.qnorm.alloc(gq)) ||
+    if ((rc = W.probes.alloc(pairs)) || (rc = W.qrows.alloc(gq * std::max(h->dim_p, h->dim_h))) || (rc = W.qnorm.alloc(gq)) ||
         (rc = W.plan.alloc((size_t)3 * h->nlist + 2)) || (rc = W.slots.alloc(pairs)) ||
         (rc = W.items.alloc((size_t)2 * vs::ivf_nd_items_cap(h->nlist, W.np_max))) || (rc = W.part_d.alloc(pairs * kKcapMax)) ||
         (rc = W.part_i.alloc(pairs * kKcapMax)))
@@ -2133,6 +2146,8 @@ vs::IvfNdI8Params ivf_nd_i8_params(vs_index* h, vs::IvfNdParams& ip) {
 // ivf_scan_nd_i8_kernel, the others to ivf_scan_nd_kernel, both into the same partial lists.  The metric is the handle's at the
 // time of the call (vs_ivf_search_metric* set it for the call's duration): under inner product the coarse scores are
 // -(q.c), the scans run their IP instantiations, and the byte scan needs the rows' byte sums (ensure_ivf_nd_ip).
+// An index with half rows (vs_ivf_create_nd_f16) has one plan, on query rows of dim_h floats, and ivf_scan_nd_f16_kernel
+// in place of ivf_scan_nd_kernel; coarse stage, plan and ranking are the same launches.
 int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int nprobe, float* out_d, int32_t* out_i, hipStream_t s) {
     const int kcap = pick_kcap(k);
     if (!kcap) return refuse_general_ivf(h, "k > 16");
@@ -2165,6 +2180,12 @@ int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int 
     }
     stage_mark(h, 1, s);
     vs::IvfNdParams ip = ivf_nd_params(h, q_dev, nb * B, k, kcap, nprobe);
+    vs::IvfNdF16Params hp{};
+    if (h->d_nd_f16) {  // half rows: the query rows padded to whole K steps of 32, the list scan on the halves
+        ip.dim_p = h->dim_h;
+        hp.vecs_f16 = h->d_nd_f16;
+        hp.dim_h = h->dim_h;
+    }
     vs::IvfNdI8Params bp{};
     const bool two_plans = (bool)h->d_nd_u8;
     if (two_plans && h->metric == VS_METRIC_IP && (rc = ensure_ivf_nd_ip(h, s))) return rc;
@@ -2176,7 +2197,12 @@ int ivf_group_nd_dev(vs_index* h, const float* q_dev, int nb, int B, int k, int 
     if (two_plans) HIPCHK(vs::launch_ivf_nd_plan_second(bp.s, s));
     stage_mark(h, 2, s);
     prof_begin(h, 1, s);
-    HIPCHK(vs::launch_ivf_nd_scan(ip, h->num_cus, s));
+    if (h->d_nd_f16) {
+        hp.s = ip;
+        HIPCHK(vs::launch_ivf_nd_f16_scan(hp, h->num_cus, s));
+    } else {
+        HIPCHK(vs::launch_ivf_nd_scan(ip, h->num_cus, s));
+    }
     if (two_plans) HIPCHK(vs::launch_ivf_nd_i8_scan(bp, h->num_cus, s));
     prof_end(h, 1, s);
     vs::MergeParams m{};
@@ -2916,7 +2942,7 @@ int vs_bf_filter_image_read(const vs_index* h, int64_t row0, int64_t n, uint16_t
 float vs_f32_filter_cnorm(double bnmax) { return vs::filter_cnorm(bnmax); }
 float vs_f32_filter_th2(float thr, float e, float cnorm) { return vs::filter_th2(thr, e, cnorm); }
 int vs_bf_filter_stats(vs_index* h, int64_t* out, int reset) {
-    if (h && out && h->d_nd_f16 && !h->nd_f16_filter) {  // half rows without their prefilter: the route is never taken
+    if (h && out && h->kind == 0 && h->d_nd_f16 && !h->nd_f16_filter) {  // half rows without their prefilter: the route is never taken
         out[0] = out[1] = out[2] = out[3] = 0;
         return VS_OK;
     }
@@ -3202,6 +3228,25 @@ int vs_bf_create_nd_u8_metric(const uint8_t* base_host, int64_t n_rows, int dim,
 // at most kF16ChunkBytes in row order, and nd_f16_layout_kernel writes each chunk's stored layout and norms: the base is
 // never widened on the host.
 constexpr size_t kF16ChunkBytes = (size_t)64 << 20;
+// h->d_nd_f16 and h->d_norm of n_rows rows of h->dim halves (h->dim_h set): the upload both float16 creators share
+static int upload_f16_rows(vs_index* h, const uint16_t* base_host, int64_t n_rows) {
+    int rc;
+    const int dim = h->dim;
+    const size_t total = ((size_t)n_rows + vs::kScanPadRows) * h->dim_h;
+    const int64_t chunk_rows = std::max<int64_t>(1, std::min<int64_t>(n_rows, (int64_t)(kF16ChunkBytes / ((size_t)dim * sizeof(uint16_t)))));
+    vs::DevBuf<uint16_t> stage;
+    if ((rc = h->d_nd_f16.alloc(total)) || (rc = h->d_norm.alloc((size_t)n_rows + 64)) || (rc = stage.alloc((size_t)chunk_rows * dim))) return rc;
+    // the spare rows and the norms behind the last row stay zero: block loads are not clamped
+    HIPCHK(hipMemset(h->d_nd_f16 + (size_t)n_rows * h->dim_h, 0, (size_t)vs::kScanPadRows * h->dim_h * sizeof(uint16_t)));
+    HIPCHK(hipMemset(h->d_norm + (size_t)n_rows, 0, 64 * sizeof(float)));
+    for (int64_t r0 = 0; r0 < n_rows; r0 += chunk_rows) {
+        const int64_t rows = std::min(chunk_rows, n_rows - r0);
+        HIPCHK(hipMemcpy(stage, base_host + (size_t)r0 * dim, (size_t)rows * dim * sizeof(uint16_t), hipMemcpyHostToDevice));
+        HIPCHK(vs::launch_nd_f16_layout(stage, rows, dim, h->d_nd_f16 + (size_t)r0 * h->dim_h, h->d_norm + r0, nullptr));
+    }
+    HIPCHK(hipDeviceSynchronize());  // (before the staging buffer goes)
+    return VS_OK;
+}
 int vs_bf_create_nd_f16(const uint16_t* base_host, int64_t n_rows, int dim, int metric, int device, int64_t id_offset, vs_index** out) {
     return guarded([&]() -> int {
         if (!out || !base_host || n_rows <= 0) {
@@ -3244,25 +3289,7 @@ int vs_bf_create_nd_f16(const uint16_t* base_host, int64_t n_rows, int dim, int 
         h->metric = metric;
         h->n_rows = h->n_total = n_rows;
         h->id_offset = id_offset;
-        auto upload = [&]() -> int {
-            int r2;
-            const size_t total = ((size_t)n_rows + vs::kScanPadRows) * h->dim_h;
-            const int64_t chunk_rows = std::max<int64_t>(1, std::min<int64_t>(n_rows, (int64_t)(kF16ChunkBytes / ((size_t)dim * sizeof(uint16_t)))));
-            vs::DevBuf<uint16_t> stage;
-            if ((r2 = h->d_nd_f16.alloc(total)) || (r2 = h->d_norm.alloc((size_t)n_rows + 64)) || (r2 = stage.alloc((size_t)chunk_rows * dim)))
-                return r2;
-            // the spare rows and the norms behind the last row stay zero: block loads are not clamped
-            HIPCHK(hipMemset(h->d_nd_f16 + (size_t)n_rows * h->dim_h, 0, (size_t)vs::kScanPadRows * h->dim_h * sizeof(uint16_t)));
-            HIPCHK(hipMemset(h->d_norm + (size_t)n_rows, 0, 64 * sizeof(float)));
-            for (int64_t r0 = 0; r0 < n_rows; r0 += chunk_rows) {
-                const int64_t rows = std::min(chunk_rows, n_rows - r0);
-                HIPCHK(hipMemcpy(stage, base_host + (size_t)r0 * dim, (size_t)rows * dim * sizeof(uint16_t), hipMemcpyHostToDevice));
-                HIPCHK(vs::launch_nd_f16_layout(stage, rows, dim, h->d_nd_f16 + (size_t)r0 * h->dim_h, h->d_norm + r0, nullptr));
-            }
-            HIPCHK(hipDeviceSynchronize());  // (before the staging buffer goes)
-            return VS_OK;
-        };
-        if ((rc = upload()) || (rc = alloc_scratch(h)) || (rc = build_nd_f16_filter(h))) {  // (the f16 prefilter for long calls: DESIGN 4.4h)
+        if ((rc = upload_f16_rows(h, base_host, n_rows)) || (rc = alloc_scratch(h)) || (rc = build_nd_f16_filter(h))) {  // (the f16 prefilter for long calls: DESIGN 4.4h)
             vs_destroy(h);
             return rc;
         }
@@ -3272,11 +3299,16 @@ int vs_bf_create_nd_f16(const uint16_t* base_host, int64_t n_rows, int dim, int 
 }
 
 // The stored half rows [row0, row0 + n) in row order: the inverse of the creator's permutation, on the host.  Blocking.
+static int f16_rows_read(const vs_index* h, int64_t row0, int64_t n, uint16_t* dst);
 int vs_bf_f16_rows_read(vs_index* h, int64_t row0, int64_t n, uint16_t* dst) {
     if (!h || !dst || h->kind != 0 || !h->d_nd_f16 || row0 < 0 || n < 0 || row0 + n > h->n_rows) {
         set_error("vs_bf_f16_rows_read: an index made by vs_bf_create_nd_f16 and a range inside it");
         return VS_ERR_INVALID;
     }
+    return f16_rows_read(h, row0, n, dst);
+}
+// (any index with half rows, checked by the caller: vs_ivf_save reads an IVF index's through it)
+static int f16_rows_read(const vs_index* h, int64_t row0, int64_t n, uint16_t* dst) {
     return guarded([&]() -> int {
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipDeviceSynchronize());
@@ -3577,6 +3609,32 @@ static int build_tau_heads(vs_index* h, const float* vectors, const int32_t* off
     return VS_OK;
 }
 
+// The tables of an IVF index beside its rows (h->nlist, dim, dim_p set): centroids [nlist + 64][dim_p], zero padded like
+// the rows on a general index (the coarse scores are a brute-force scan of this table), their norms, the local list
+// offsets and the local position -> original id map.  Blocking.
+static int ivf_upload_tables(vs_index* h, const float* centroids, const int32_t* loc_off, const int32_t* loc_r2o, int64_t n_local) {
+    int rc;
+    const int nlist = h->nlist, dim = h->dim;
+    const size_t cld = (size_t)h->dim_p, cents_total = ((size_t)nlist + vs::kScanPadRows) * cld;
+    if ((rc = h->d_centroids.alloc(cents_total))) return rc;
+    if (hipMemset(h->d_centroids, 0, cents_total * sizeof(float)) != hipSuccess) return VS_ERR_DEVICE;
+    if ((rc = h->d_cnorm.alloc((size_t)nlist + 64))) return rc;
+    if ((rc = h->d_offsets.alloc((size_t)nlist + 1))) return rc;
+    if ((rc = h->d_r2o.alloc((size_t)std::max<int64_t>(n_local, 1)))) return rc;
+    hipError_t e;
+    if ((e = hipMemset(h->d_cnorm, 0, ((size_t)nlist + 64) * sizeof(float))) != hipSuccess ||
+        (e = hipMemcpy2D(h->d_centroids, cld * sizeof(float), centroids, (size_t)dim * sizeof(float), (size_t)dim * sizeof(float), (size_t)nlist,
+                         hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(h->d_offsets, loc_off, ((size_t)nlist + 1) * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(h->d_r2o, loc_r2o, (size_t)std::max<int64_t>(n_local, 1) * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = vs::launch_row_sqnorm_ld(h->d_centroids, nlist, dim, (int64_t)cld, h->d_cnorm, nullptr)) != hipSuccess ||
+        (e = hipDeviceSynchronize()) != hipSuccess) {
+        set_error(std::string("ivf upload: ") + hipGetErrorString(e));
+        return VS_ERR_DEVICE;
+    }
+    return VS_OK;
+}
+
 // rows_u8: the rows as uint8 instead of `vectors` (vs_ivf_create_nd_u8; unsharded): converted to float once the
 // arguments are checked, and kept as bytes beside the fp32 rows when the index is a general one
 static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const float* centroids, int nlist,
@@ -3681,25 +3739,8 @@ static int ivf_create_impl(const float* vectors, int64_t n_rows, int dim, const 
     std::vector<int32_t> host_rterm;
     if (!h->general && h->metric == VS_METRIC_L2 && n_local > 0 && (rc = build_u8_copy(h, up, n_local, &host_bytes, &host_rterm)))
         return fail(rc);
-    // centroids [nlist + 64][dim_p]: zero padded like the rows on a general index (the coarse scores are a brute-force scan
-    // of this table)
-    const size_t cld = (size_t)h->dim_p, cents_total = ((size_t)nlist + vs::kScanPadRows) * cld;
-    if ((rc = h->d_centroids.alloc(cents_total))) return fail(rc);
-    if (hipMemset(h->d_centroids, 0, cents_total * sizeof(float)) != hipSuccess) return fail(VS_ERR_DEVICE);
-    if ((rc = h->d_cnorm.alloc((size_t)nlist + 64))) return fail(rc);
-    if ((rc = h->d_offsets.alloc((size_t)nlist + 1))) return fail(rc);
-    if ((rc = h->d_r2o.alloc((size_t)std::max<int64_t>(n_local, 1)))) return fail(rc);
+    if ((rc = ivf_upload_tables(h, centroids, loc_off.data(), loc_r2o.data(), n_local))) return fail(rc);
     hipError_t e;
-    if ((e = hipMemset(h->d_cnorm, 0, ((size_t)nlist + 64) * sizeof(float))) != hipSuccess ||
-        (e = hipMemcpy2D(h->d_centroids, cld * sizeof(float), centroids, (size_t)dim * sizeof(float), (size_t)dim * sizeof(float), (size_t)nlist,
-                         hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(h->d_offsets, loc_off.data(), ((size_t)nlist + 1) * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(h->d_r2o, loc_r2o.data(), (size_t)std::max<int64_t>(n_local, 1) * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = vs::launch_row_sqnorm_ld(h->d_centroids, nlist, dim, (int64_t)cld, h->d_cnorm, nullptr)) != hipSuccess ||
-        (e = hipDeviceSynchronize()) != hipSuccess) {
-        set_error(std::string("ivf upload: ") + hipGetErrorString(e));
-        return fail(VS_ERR_DEVICE);
-    }
     if (h->general) {
         // no chunk table, no tiled copy, no heads: launch groups of 32 batches on the caller's stream (ivf_group_nd_dev),
         // their scratch and the host staging now rather than inside the first search
@@ -4178,6 +4219,70 @@ int vs_ivf_create_nd_u8(const uint8_t* vectors_reordered, int64_t n_rows, int di
     });
 }
 
+// float16 rows: always the general IVF index, unsharded, and the half rows are all the rows it stores --
+// uploaded in bounded chunks and laid out by nd_f16_layout_kernel, which also yields the norms of the widened rows; never
+// widened on the host.  Centroids, their norms and the tables are vs_ivf_create's.  Short calls keep the group route:
+// the two-launch kernels read fp32 rows.
+int vs_ivf_create_nd_f16(const uint16_t* vectors_reordered, int64_t n_rows, int dim, const float* centroids, int nlist,
+                         const int32_t* cluster_offsets, const int32_t* reorder_to_original, int device, vs_index** out) {
+    return guarded([&]() -> int {
+        if (!out || !vectors_reordered || !centroids || !cluster_offsets || n_rows <= 0 || nlist <= 0) {
+            set_error("vs_ivf_create_nd_f16: bad arguments");
+            return VS_ERR_INVALID;
+        }
+        if (dim < 1) {
+            set_error("vs_ivf_create_nd_f16: dim must be at least 1");
+            return VS_ERR_INVALID;
+        }
+        if (dim > vs::kNdMaxDim) {
+            set_error("vs_ivf_create_nd_f16: dim > 2048 is not compiled in");
+            return VS_ERR_UNSUPPORTED;
+        }
+        if (cluster_offsets[0] != 0 || cluster_offsets[nlist] != n_rows) {
+            set_error("cluster_offsets do not cover the vectors");
+            return VS_ERR_INVALID;
+        }
+        for (int c = 0; c < nlist; ++c)
+            if (cluster_offsets[c + 1] < cluster_offsets[c]) {
+                set_error("cluster_offsets not monotone");
+                return VS_ERR_INVALID;
+            }
+        int rc = check_device(device);
+        if (rc) return rc;
+        HIPCHK(hipSetDevice(device));
+        vs_index* h = new (std::nothrow) vs_index();
+        if (!h) {
+            set_error("out of host memory");
+            return VS_ERR_NOMEM;
+        }
+        h->kind = 1;
+        h->device = device;
+        h->dim = dim;
+        h->general = true;
+        h->dim_p = vs::nd_dim_p(dim);
+        h->dim_h = vs::nd_dim_h(dim);
+        h->ivf_one = false;  // (no short-call scan on half rows yet)
+        h->metric = VS_METRIC_L2;
+        h->n_rows = h->n_total = n_rows;
+        h->nlist = nlist;
+        h->h_offsets_global.assign(cluster_offsets, cluster_offsets + nlist + 1);
+        h->avg_cluster_size = (double)n_rows / nlist;
+        h->ivf_gb = vs::kIvfWideBatches;  // launch groups of 32 batches on the caller's stream (ivf_group_nd_dev)
+        h->ivf_lanes = 1;
+        h->ivf_nsb = 1;
+        for (int c = 0; c < nlist; ++c) h->max_list = std::max(h->max_list, cluster_offsets[c + 1] - cluster_offsets[c]);
+        std::vector<int32_t> r2o((size_t)n_rows);
+        for (int64_t r = 0; r < n_rows; ++r) r2o[(size_t)r] = reorder_to_original ? reorder_to_original[r] : (int32_t)r;
+        if ((rc = upload_f16_rows(h, vectors_reordered, n_rows)) || (rc = ivf_upload_tables(h, centroids, cluster_offsets, r2o.data(), n_rows)) ||
+            (rc = alloc_scratch(h)) || (rc = ensure_ivf_nd(h)) || (rc = ensure_wide_streams(h)) || (rc = ensure_ivf_host(h))) {
+            vs_destroy(h);
+            return rc;
+        }
+        *out = h;
+        return VS_OK;
+    });
+}
+
 int vs_ivf_load(const char* index_dir, int device, int rank, int world, vs_index** out) {
     if (!index_dir || !out) {
         set_error("vs_ivf_load: bad arguments");
@@ -4258,7 +4363,17 @@ int vs_ivf_save(vs_index* h, const char* index_dir) {
     std::vector<int32_t> r2o((size_t)h->n_rows);
     // unpadded [n_rows][dim] arrays (a general index keeps rows of dim_p floats on the device)
     const size_t row_b = (size_t)h->dim * sizeof(float), ld_b = (size_t)h->dim_p * sizeof(float);
-    HIPCHK(hipMemcpy2D(vecs.data(), row_b, h->d_vecs, ld_b, row_b, (size_t)h->n_rows, hipMemcpyDeviceToHost));
+    if (h->d_nd_f16) {  // half rows: read back in row order and widened here (exact)
+        std::vector<uint16_t> halves(vecs.size());
+        if ((rc = f16_rows_read(h, 0, h->n_rows, halves.data()))) return rc;
+        for (size_t i = 0; i < vecs.size(); ++i) {
+            _Float16 x;
+            std::memcpy(&x, &halves[i], sizeof(x));
+            vecs[i] = (float)x;
+        }
+    } else {
+        HIPCHK(hipMemcpy2D(vecs.data(), row_b, h->d_vecs, ld_b, row_b, (size_t)h->n_rows, hipMemcpyDeviceToHost));
+    }
     HIPCHK(hipMemcpy2D(cents.data(), row_b, h->d_centroids, ld_b, row_b, (size_t)h->nlist, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(r2o.data(), h->d_r2o, r2o.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     std::vector<int32_t> sizes(h->nlist);
@@ -4344,6 +4459,7 @@ int vs_ivf_search_topk_dev_multi(vs_index* h, const float* queries_dev, int n_ba
         return VS_ERR_UNSUPPORTED;
     }
     if (k <= 16 || !h->general) return vs_ivf_search_dev_multi(h, queries_dev, n_batches, B, k, nprobe, ids_dev, dists_dev, stream);
+    if (refuse_wide_k_f16(h, "vs_ivf_search_topk_dev_multi")) return VS_ERR_UNSUPPORTED;
     nprobe = std::min(nprobe, h->nlist);
     if (nprobe > kMaxNprobe) {
         set_error("nprobe > 256 not supported");
@@ -5792,6 +5908,7 @@ int vs_ivf_search_topk(vs_index* h, const float* queries_host, int64_t nq, int k
         return VS_ERR_UNSUPPORTED;
     }
     if (k <= 16 || !h->general) return vs_ivf_search(h, queries_host, nq, k, nprobe, ids, dists, total_candidates, timing);
+    if (refuse_wide_k_f16(h, "vs_ivf_search_topk")) return VS_ERR_UNSUPPORTED;
     nprobe = std::min(nprobe, h->nlist);
     if (nprobe > kMaxNprobe) {
         set_error("nprobe > 256 not supported");

@@ -277,7 +277,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void ivf_scan_nd_kernel(const IvfN
 }
 
 hipError_t launch_ivf_nd_plan(const IvfNdParams& p, hipStream_t s) {
-    if (p.dim < 1 || p.dim > kNdMaxDim || p.dim_p != nd_dim_p(p.dim) || p.group_q < 1 || p.group_q > kIvfNdGroupQ || p.nprobe < 1 ||
+    if (p.dim < 1 || p.dim > kNdMaxDim || (p.dim_p != nd_dim_p(p.dim) && p.dim_p != nd_dim_h(p.dim)) || p.group_q < 1 || p.group_q > kIvfNdGroupQ || p.nprobe < 1 ||
         p.nprobe > kIvfMaxProbe || p.nlist < 1 || (p.kcap != 8 && p.kcap != 16))
         return hipErrorInvalidValue;
     const int pairs = p.group_q * p.nprobe;

@@ -947,6 +947,17 @@ hipError_t launch_ivf_nd_plan(const IvfNdParams& p, hipStream_t s);
 hipError_t launch_ivf_nd_plan_second(const IvfNdParams& p, hipStream_t s);
 hipError_t launch_ivf_nd_scan(const IvfNdParams& p, int grid, hipStream_t s);
 
+// ---- the same scan on an index whose rows are float16 (vs_ivf_nd_f16.hip; vs_ivf_create_nd_f16): s is
+// launch_ivf_nd_plan's group with s.dim_p == dim_h = nd_dim_h(s.dim) (the query rows padded to whole K steps of 32) and
+// s.vecs unused; the rows are vecs_f16 in launch_scan_nd_f16's stored layout, s.vnorm the squared norms of the widened
+// rows.  Writes what launch_ivf_nd_scan writes on the rows widened to float, to the bit.
+struct IvfNdF16Params {
+    IvfNdParams s;
+    const uint16_t* vecs_f16;  // [n_rows + kScanPadRows][dim_h] halves, every 32-half block permuted (nd_f16_elem_at)
+    int dim_h;
+};
+hipError_t launch_ivf_nd_f16_scan(const IvfNdF16Params& p, int grid, hipStream_t s);
+
 // ---- the single-call IVF search of a general index (vs_ivf_one_nd.hip): one batch of o.nq_valid <= 16
 // queries, o.k1 = k <= 16 results each (k entries, not k + 1), nlist <= kIvfOneMaxNlist, in TWO launches on one stream.
 // launch_ivf_one_coarse scores the centroid table (launch_scan_nd's kModeStore numbers, to the bit) and its last

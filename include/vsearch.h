@@ -785,6 +785,36 @@ VS_API int vs_ivf_create_nd_u8(const uint8_t* vectors_reordered, int64_t n_rows,
                                const float* centroids, int nlist, const int32_t* cluster_offsets,
                                const int32_t* reorder_to_original, int device, vs_index** out);
 
+/* An IVF index over float16 rows (IEEE binary16 bit patterns; any 1 <= dim <= 2048, unsharded):
+ * vs_ivf_create's arguments with the reordered rows as halves.  Always the general IVF index, at
+ * dim 128 too.  The half rows are the index's ONLY row storage -- no fp32 rows, no byte copy:
+ * about 2 * dim_h + 4 bytes per row (dim_h = dim rounded up to 32) against the fp32 index's
+ * 4 * dim_p + 4 -- uploaded in bounded chunks and never widened on the host; centroids and their
+ * norms stay float.  Probed lists are scanned by ivf_scan_nd_f16_kernel.
+ *
+ * Argument checks, in this order, the first four without a device: a null pointer (vectors,
+ * centroids, offsets, out), n_rows <= 0 or nlist <= 0 -> VS_ERR_INVALID; dim < 1 ->
+ * VS_ERR_INVALID; dim > 2048 -> VS_ERR_UNSUPPORTED; offsets that do not cover the rows or are
+ * not monotone -> VS_ERR_INVALID; then the device.
+ *
+ * Results: a half widens to float exactly, and every accepted call returns what it returns on
+ * vs_ivf_create(the rows widened to float, ...): ids, distance bits, empty slots and
+ * *total_candidates.
+ *
+ * Accepted: vs_ivf_search, vs_ivf_search_dev, vs_ivf_search_dev_multi at 1 <= k <= 16;
+ * vs_ivf_search_metric and vs_ivf_search_metric_dev_multi at k <= 16 under both metrics;
+ * vs_ivf_save, which writes the rows widened to float (vs_ivf_load of that directory gives an
+ * fp32 general index); vs_index_rows / _dim / _nlist, vs_prof_*, vs_set_batch, vs_destroy;
+ * vs_set_precision 0 or 1, which both mean the half rows.
+ * Refused: vs_ivf_search_topk* (and the metric calls) at 17 <= k <= 128 -> VS_ERR_UNSUPPORTED
+ * with a message that names the half rows; vs_set_precision 2; the sharded and virtual-shard
+ * calls; vs_ivf_set_metric(VS_METRIC_IP), as on every general index; every vs_bf_* call.
+ * Short calls take the group route (the two-launch kernels read fp32 rows); results do not depend
+ * on the route. */
+VS_API int vs_ivf_create_nd_f16(const uint16_t* vectors_reordered, int64_t n_rows, int dim,
+                                const float* centroids, int nlist, const int32_t* cluster_offsets,
+                                const int32_t* reorder_to_original, int device, vs_index** out);
+
 /* GPU index builder, the device side of build_ivf_index_reordered (create_ivf_model_reordered.py:82-177):
  * Lloyd k-means under L2 with sklearn's stopping rule (sum of squared centre shifts <= tol * mean feature
  * variance, default tol 1e-4, max_iter 100 in the reference, :97-103).  Assignment runs on the MFMA scan

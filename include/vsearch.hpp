@@ -300,6 +300,16 @@ public:
              const int32_t* clusterOffsets, const int32_t* reorderToOriginal, int device = 0) {
         check(vs_ivf_create_nd_u8(vectorsReordered, rows, dim, centroids, nlist, clusterOffsets, reorderToOriginal, device, &h_));
     }
+    // float16 rows (IEEE binary16 bit patterns) in the reordered layout: vs_ivf_create_nd_f16 -- always the general IVF
+    // index, the half rows are its only row storage, k <= 16, and every call returns what it returns on the rows widened
+    // to float
+    static IVFIndex fromF16(const uint16_t* vectorsReorderedF16, int64_t rows, int dim, const float* centroids, int nlist,
+                            const int32_t* clusterOffsets, const int32_t* reorderToOriginal, int device = 0) {
+        vs_index* h = nullptr;
+        check(vs_ivf_create_nd_f16(vectorsReorderedF16, rows, dim, centroids, nlist, clusterOffsets, reorderToOriginal, device, &h));
+        return IVFIndex(h);
+    }
+    IVFIndex(IVFIndex&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
     ~IVFIndex() { vs_destroy(h_); }
     IVFIndex(const IVFIndex&) = delete;
     IVFIndex& operator=(const IVFIndex&) = delete;
@@ -401,6 +411,7 @@ public:
     vs_index* handle() { return h_; }
 
 private:
+    explicit IVFIndex(vs_index* h) : h_(h) {}  // (fromF16)
     vs_index* h_ = nullptr;
 };
 
