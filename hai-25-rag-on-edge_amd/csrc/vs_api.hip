@@ -1262,28 +1262,30 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
     m.q_group_out = B;
     m.q_group_in = vs::kMaxBatch;
     m.invalid = use_u8 ? invalid : nullptr;
-    if (nd_filter) {
+    if (nd_sweep) {  // the bf16 prefilter on the image (nd_filter) or the f16 prefilter on the half rows (f16_filter)
         const vs::NdFilterPlan g = vs::ndf_plan(h->n_rows, h->num_cus, nb);
-        // bounds: scan_nd_kernel's own top-k on the compact sample copy (exact distances of k1 distinct rows), ranked by
-        // one merge launch into tau0 = next_up(k1-th best) for all 32 query slots of every batch
-        vs::ScanNdParams sn{};
-        sn.s = p;
-        sn.s.base = h->d_nd_sample;
-        sn.s.bnorm = h->d_nd_sample_norm;
-        sn.s.row_begin = 0;
-        sn.s.row_end = h->nd_sample_rows;
-        sn.s.id_offset = 0;
-        sn.s.part_d = L.part_d;
-        sn.s.part_i = L.part_i;
-        sn.dim = h->dim;
-        sn.dim_p = h->dim_p;
-        sn.qfrag = h->d_nd_qfrag;
-        sn.qnorm = h->d_nd_qnorm;
+        // bounds: the per-batch scan's own top-k on the compact sample copy -- scan_nd_kernel's, on half rows
+        // scan_nd_f16_kernel's: exact distances of k1 distinct rows -- ranked by one merge launch into tau0 = next_up(k1-th
+        // best) for all 32 query slots of every batch; its preparation launch writes the fp32 fragments and norms of all nb
+        // batches (on half rows at dim_p = dim_h), which the recheck reads
+        vs::ScanParams ss = p;
+        ss.bnorm = h->d_nd_sample_norm;
+        ss.row_begin = 0;
+        ss.row_end = h->nd_sample_rows;
+        ss.id_offset = 0;
+        ss.part_d = L.part_d;
+        ss.part_i = L.part_i;
         int sgrid, stp;
         scan_geometry(h->nd_sample_rows, h->num_cus, sgrid, stp);
-        sn.s.tiles_per_wg = stp;
+        ss.tiles_per_wg = stp;
         prof_begin(h, 0, s);
-        HIPCHK(vs::launch_scan_nd(sn, sgrid, kcap, 2, vs::kModeTopK, s));
+        if (nd_filter) {
+            ss.base = h->d_nd_sample;
+            HIPCHK(vs::launch_scan_nd(vs::ScanNdParams{ss, h->dim, h->dim_p, h->d_nd_qfrag, h->d_nd_qnorm}, sgrid, kcap, 2, vs::kModeTopK, s));
+        } else {
+            ss.base_f16 = h->d_nd_f16_sample;
+            HIPCHK(vs::launch_scan_nd_f16(vs::ScanNdF16Params{ss, h->dim, h->dim_h, h->d_nd_qfrag, h->d_nd_qnorm}, sgrid, kcap, 2, vs::kModeTopK, s));
+        }
         vs::MergeParams mt{};
         mt.part_d = L.part_d;
         mt.part_i = L.part_i;
@@ -1294,20 +1296,17 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
         mt.tau_out = L.tau0;
         HIPCHK(vs::launch_merge_layout(mt, kcap, (int64_t)vs::kSlotStride * kcap, s));
         p.tau0 = L.tau0;
-        vs::NdFilterParams fp{};
-        fp.img = h->d_img;
-        fp.base = h->d_vecs;
+        vs::NdfSweepParams fp{};
         fp.bnorm = h->d_norm;
         fp.n_rows = h->n_rows;
         fp.dim = h->dim;
-        fp.dim_p = h->dim_p;
-        fp.slabs = vs::ndf_slabs(h->dim_p);
+        fp.slabs = nd_filter ? vs::ndf_slabs(h->dim_p) : h->dim_h / 32;
         fp.q = q_dev;
         fp.q_batch_stride = (int64_t)B * h->dim;
         fp.qfrag = h->d_nd_qfrag;
         fp.qnorm = h->d_nd_qnorm;
         fp.tau0 = L.tau0;
-        fp.qbf = h->d_nd_qbf;
+        fp.qb16 = h->d_nd_qbf;
         fp.qbound = h->d_nd_qbound;
         fp.qnp = h->d_nd_qnp;
         fp.zero = L.wide8.wcnt;
@@ -1316,7 +1315,6 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
         fp.nq_valid = B;
         fp.metric = h->metric;
         fp.id_offset = (int32_t)h->id_offset;
-        fp.fstats = h->fstats;
         fp.bnmax = h->nd_bnmax;
         fp.sink.wbuf = L.wide8.wbuf;
         // (the buffers are allocated for 256 workgroups: a launch of fewer waves -- a small shard -- shares them out)
@@ -1329,77 +1327,8 @@ int bf_launch(vs_index* h, vs_index::Lane& L, const float* q_dev, int nb, int B,
         fp.sink.nsub = kWideSub;
         fp.sink.stats = h->filter_stats;
         ++h->filter_launches;
-        HIPCHK(vs::launch_scan_nd_f32f(fp, g, s));
-        prof_end(h, 0, s);
-    }
-    if (f16_filter) {
-        const vs::NdFilterPlan g = vs::ndf_plan(h->n_rows, h->num_cus, nb);
-        // bounds: scan_nd_f16_kernel's own top-k on the compact sample copy, ranked by one merge launch into tau0 =
-        // next_up(k1-th best) for all 32 query slots of every batch; its preparation launch writes the fp32 fragments and
-        // norms of all nb batches (dim_p = dim_h), which the recheck reads
-        vs::ScanNdF16Params sn{};
-        sn.s = p;
-        sn.s.base_f16 = h->d_nd_f16_sample;
-        sn.s.bnorm = h->d_nd_sample_norm;
-        sn.s.row_begin = 0;
-        sn.s.row_end = h->nd_sample_rows;
-        sn.s.id_offset = 0;
-        sn.s.part_d = L.part_d;
-        sn.s.part_i = L.part_i;
-        sn.dim = h->dim;
-        sn.dim_h = h->dim_h;
-        sn.qfrag = h->d_nd_qfrag;
-        sn.qnorm = h->d_nd_qnorm;
-        int sgrid, stp;
-        scan_geometry(h->nd_sample_rows, h->num_cus, sgrid, stp);
-        sn.s.tiles_per_wg = stp;
-        prof_begin(h, 0, s);
-        HIPCHK(vs::launch_scan_nd_f16(sn, sgrid, kcap, 2, vs::kModeTopK, s));
-        vs::MergeParams mt{};
-        mt.part_d = L.part_d;
-        mt.part_i = L.part_i;
-        mt.G = sgrid;
-        mt.kin = kcap;
-        mt.nq = nb * vs::kMaxBatch;
-        mt.kout = k1;
-        mt.tau_out = L.tau0;
-        HIPCHK(vs::launch_merge_layout(mt, kcap, (int64_t)vs::kSlotStride * kcap, s));
-        p.tau0 = L.tau0;
-        vs::NdF16FilterParams fp{};
-        fp.rows = h->d_nd_f16;
-        fp.bnorm = h->d_norm;
-        fp.n_rows = h->n_rows;
-        fp.dim = h->dim;
-        fp.dim_h = h->dim_h;
-        fp.slabs = h->dim_h / 32;
-        fp.q = q_dev;
-        fp.q_batch_stride = (int64_t)B * h->dim;
-        fp.qfrag = h->d_nd_qfrag;
-        fp.qnorm = h->d_nd_qnorm;
-        fp.tau0 = L.tau0;
-        fp.qh = h->d_nd_qbf;
-        fp.qbound = h->d_nd_qbound;
-        fp.qnp = h->d_nd_qnp;
-        fp.zero = L.wide8.wcnt;
-        fp.zero_words = (int)zero_words;
-        fp.n_batches = nb;
-        fp.nq_valid = B;
-        fp.metric = h->metric;
-        fp.id_offset = (int32_t)h->id_offset;
-        fp.fstats = h->f16_fstats;
-        fp.bnmax = h->nd_bnmax;
-        fp.sink.wbuf = L.wide8.wbuf;
-        // (the buffers are allocated for 256 workgroups: a launch of fewer waves -- a small shard -- shares them out)
-        fp.sink.wcap = (int)((int64_t)kWideWaveCap * vs::kSlotStride / ((int64_t)g.grid * g.passes));
-        fp.sink.overflow = overflow;
-        fp.sink.cnt = L.wide8.wcnt + 64;
-        fp.sink.cand_d = L.wide8.wcand_d;
-        fp.sink.cand_i = L.wide8.wcand_i;
-        fp.sink.cap = kWideCap;
-        fp.sink.nsub = kWideSub;
-        fp.sink.stats = h->filter_stats;
-        ++h->filter_launches;
-        HIPCHK(vs::launch_scan_nd_f16f(fp, g, s));
+        if (nd_filter) HIPCHK(vs::launch_scan_nd_f32f(vs::NdFilterParams{fp, h->d_img, h->d_vecs, h->dim_p, h->fstats}, g, s));
+        else HIPCHK(vs::launch_scan_nd_f16f(vs::NdF16FilterParams{fp, h->d_nd_f16, h->dim_h, h->f16_fstats}, g, s));
         prof_end(h, 0, s);
     }
     const bool lists = stream || nd_sweep;  // the scan's candidate lists are ranked, the per-batch scan is the fallback

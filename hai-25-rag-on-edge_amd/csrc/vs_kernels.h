@@ -437,53 +437,42 @@ struct CandSink {
     int cnt_sub_stride;
 };
 
-// the bf16 prefilter of a general index (above)
-struct NdFilterParams {
-    const uint16_t* img;     // the rows' bf16 image
-    const float* base;       // [n_rows + 64][dim_p] fp32 rows (the recheck only)
+// what the prefilter sweep of a general index reads whichever rows it sweeps (vs_ndf_sweep.h)
+struct NdfSweepParams {
     const float* bnorm;      // [n_rows + 64]
     int64_t n_rows;
-    int dim, dim_p, slabs;
+    int dim, slabs;          // slabs: 32-element K slabs of a row as the sweep reads it
     const float* q;          // [n_batches][nq_valid][dim] raw queries
     int64_t q_batch_stride;
-    const float* qfrag;      // ScanNdParams::qfrag / qnorm of these queries, written earlier in the stream (nd_prep_kernel)
-    const float* qnorm;
+    const float* qfrag;      // ScanNdParams / ScanNdF16Params::qfrag and qnorm of these queries, written earlier in the stream
+    const float* qnorm;      //   (nd_prep_kernel; on half rows at dim_p = dim_h)
     const float* tau0;       // [n_batches][32]
-    uint16_t* qbf;           // scratch [2 n_batches][slabs][64][8] bf16 B fragments
-    float* qbound;           // scratch [n_batches][32] E per query (+inf: not well scaled, 0: padding)
+    uint16_t* qb16;          // scratch [2 n_batches][slabs][64][8] B fragments: bf16, or f16 in the stored k order of the half rows
+    float* qbound;           // scratch [n_batches][32] E per query (+inf: not well scaled / a value f16 cannot hold, 0: padding)
     float* qnp;              // scratch [n_batches][32] ||q'||, rounded up
     int32_t* zero;           // zero_words words cleared by the preparation launch (overflow word, list counters)
     int zero_words;
     int n_batches, nq_valid, metric;
     int32_t id_offset;
-    FilterStats fstats;
     double bnmax;            // the shard's largest stored norm
     CandSink sink;
+};
+
+// the bf16 prefilter of a general index (above)
+struct NdFilterParams : NdfSweepParams {
+    const uint16_t* img;     // the rows' bf16 image
+    const float* base;       // [n_rows + 64][dim_p] fp32 rows (the recheck only)
+    int dim_p;               // (slabs = ndf_slabs(dim_p))
+    FilterStats fstats;
 };
 // the preparation launch and the sweep
 hipError_t launch_scan_nd_f32f(const NdFilterParams& p, const NdFilterPlan& g, hipStream_t s);
 
 // the f16 prefilter of an index with half rows (above)
-struct NdF16FilterParams {
+struct NdF16FilterParams : NdfSweepParams {
     const uint16_t* rows;    // [n_rows + 64][dim_h] the stored half rows: the sweep's A operand and the recheck's rows
-    const float* bnorm;      // [n_rows + 64]
-    int64_t n_rows;
-    int dim, dim_h, slabs;   // slabs = dim_h / 32
-    const float* q;          // [n_batches][nq_valid][dim] raw queries
-    int64_t q_batch_stride;
-    const float* qfrag;      // ScanNdF16Params::qfrag / qnorm of these queries, written earlier in the stream (nd_prep_kernel at dim_p = dim_h)
-    const float* qnorm;
-    const float* tau0;       // [n_batches][32]
-    uint16_t* qh;            // scratch [2 n_batches][slabs][64][8] f16 B fragments in the stored k order
-    float* qbound;           // scratch [n_batches][32] E per query (+inf: a value f16 cannot hold, 0: padding)
-    float* qnp;              // scratch [n_batches][32] ||q'||, rounded up
-    int32_t* zero;           // zero_words words cleared by the preparation launch (overflow word, list counters)
-    int zero_words;
-    int n_batches, nq_valid, metric;
-    int32_t id_offset;
+    int dim_h;               // (slabs = dim_h / 32)
     F16FilterStats fstats;
-    double bnmax;            // the shard's largest stored norm
-    CandSink sink;
 };
 // the preparation launch and the sweep; the geometry is ndf_plan's
 hipError_t launch_scan_nd_f16f(const NdF16FilterParams& p, const NdFilterPlan& g, hipStream_t s);

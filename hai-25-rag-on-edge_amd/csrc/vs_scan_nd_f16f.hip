@@ -6,31 +6,23 @@
 //                                 STORED k order of the rows, and per query ||q'|| and the error bound E (filter_bound_nd_f16);
 //                                 clears the group's counters.
 //   scan_nd_f16f_kernel<CBW, IP>: ONE sweep over the stored half rows for up to 8 * CBW 16-query column blocks with
-//                                 v_mfma_f32_16x16x32_f16: a tiled product with a threshold epilogue.  What passes is recomputed
-//                                 from the half rows by RecheckNdF16 (scan_nd_f16_kernel's chain, bit for bit) when the wave
-//                                 bins its buffer, so every id, distance bit and flag is decided as scan_nd_f16_kernel decides it.
+//                                 v_mfma_f32_16x16x32_f16: ndf_sweep (vs_ndf_sweep.h, where the organisation is described) on
+//                                 NdfHalfRowsSrc.  What passes is recomputed from the half rows by RecheckNdF16
+//                                 (scan_nd_f16_kernel's chain, bit for bit) when the wave bins its buffer, so every id,
+//                                 distance bit and flag is decided as scan_nd_f16_kernel decides it.
 //
 // No image.  The stored rows are [n_rows + 64][dim_h] halves, every 32-half block permuted: stored position w holds element
 // nd_f16_elem_at(w) of the block (vs_scan_nd_f16.hip).  The 16 bytes at stored positions 8 g .. 8 g + 7 of block s of row r
 // -- what lane (r, g) of scan_nd_f16_kernel loads -- are eight elements of K slab s, each element of the slab in exactly one
 // lane group: a valid A operand of one 32-element MFMA step.  The permutation is only an order of the k index, and a dot
-// product does not depend on it as long as B uses the same one: qh[(cb * S + s) * 64 + lane][j] =
+// product does not depend on it as long as B uses the same one: qb16[(cb * S + s) * 64 + lane][j] =
 // f16(Q[16 cb + r][32 s + nd_f16_elem_at(8 g + j)]), S = dim_h / 32.
 //
-// Organisation: scan_nd_f32f_kernel's.  A unit is 64 rows (four 16-row tiles; the 64 spare rows behind the
-// base serve as the spare unit).  Workgroup x of gridDim.x sweeps units x + n G; gridDim.y = passes; wave w owns column
-// blocks cb0 + w + 8 h, h < CBW, and keeps their 4 CBW f32x4 accumulators resident while K walks in 32-element slabs.  A
-// step is one (unit, slab): waves 0..3 issue the slab's piece of row tile `wave` -- LDS-DMA with per-lane addresses, scalar
-// base rows + ((64 unit + 16 t) dim_h + 32 s) 2 bytes, lane offset (r dim_h + 8 g) 2 bytes, so one instruction covers 16 rows
-// x one 64-byte segment and lands lane-linear (1 KB per tile and slab, read back with one ds_read_b128 at 16 lane, no
-// swizzle) -- waves 4..7 the unit's 64 stored norms, and every wave the CBW 1 KB B pieces of its own column blocks.  Waits
-// use one constant vmcnt, one raw s_barrier per step; the loop holds no other vector-memory instruction than these pieces
-// and the (rare) candidate stores.
+// The sweep's piece of row tile t of (unit, slab s) is therefore read in place: scalar base rows + ((64 unit + 16 t) dim_h +
+// 32 s) 2 bytes, lane offset (r dim_h + 8 g) 2 bytes, so one LDS-DMA instruction covers 16 rows x one 64-byte segment.
 #include "vs_kernels.h"
 #include "vs_dev.h"
-#include "vs_sink.h"
-#include "vs_ring.h"
-#include <algorithm>
+#include "vs_ndf_sweep.h"
 
 namespace vs {
 
@@ -102,7 +94,7 @@ __global__ __launch_bounds__(256) void ndf16_prep_kernel(const NdF16FilterParams
     for (int i = batch * 256 + tid; i < p.zero_words; i += gridDim.x * 256) p.zero[i] = 0;
     const float* qb = p.q + (int64_t)batch * p.q_batch_stride;
     const int S = p.slabs, dim = p.dim;
-    uint4* out = reinterpret_cast<uint4*>(p.qh) + (int64_t)batch * 2 * S * 64;
+    uint4* out = reinterpret_cast<uint4*>(p.qb16) + (int64_t)batch * 2 * S * 64;
     for (int e = tid; e < 2 * S * 64; e += 256) {
         const int lane = e & 63, s = (e >> 6) % S, h = (e >> 6) / S;
         const int qi = 16 * h + (lane & 15), g = lane >> 4;
@@ -189,216 +181,54 @@ struct RecheckNdF16 {
     }
 };
 
-constexpr int kNdhfWaves = 8;
-constexpr int kNdhfSlabBytes = kNdfUnitRows * 64;              // 4 KB: 64 rows x 32 halves
-constexpr int kNdhfNormOff = kNdhfSlabBytes;                   // the unit's 64 stored norms behind the rows
-constexpr int kNdhfBOff = kNdhfSlabBytes + kNdfUnitRows * 4;   // the waves' B pieces behind those
-constexpr int ndhf_slot_bytes(int cbw) { return kNdhfBOff + kNdhfWaves * cbw * 1024; }
-constexpr int ndhf_depth(int cbw) { return std::min(8, (160 * 1024) / ndhf_slot_bytes(cbw)); }  // slots of the ring
+template <int CBW, bool IP>
+__global__ __launch_bounds__(kNdfWaves * 64, 1) void scan_nd_f16f_kernel(const NdF16FilterParams p);
+
+// the stored half rows as the sweep's source of rows (vs_ndf_sweep.h): no image.  The 64 spare rows behind the base serve
+// as the spare unit.
+struct NdfHalfRowsSrc {
+    using Params = NdF16FilterParams;
+    const char* rows;
+    int64_t unit_bytes, tile_bytes;
+    unsigned voff;  // scan_nd_f16_kernel's voff: this lane's 16 bytes of a tile's segment
+    __device__ __forceinline__ NdfHalfRowsSrc(const Params& p, int lane)
+        : rows(reinterpret_cast<const char*>(p.rows)), unit_bytes((int64_t)kNdfUnitRows * p.dim_h * 2), tile_bytes((int64_t)16 * p.dim_h * 2),
+          voff((unsigned)((lane & 15) * p.dim_h + 8 * (lane >> 4)) * 2u) {}
+    // row tile `wave` of the unit, slab s: 16 rows x one 64-byte segment, straight from the stored rows (LDS-DMA with
+    // per-lane addresses: one instruction covers the tile's piece and lands lane-linear)
+    __device__ __forceinline__ const char* row_piece(int64_t unit, int s, int wave) const {
+        return rows + unit * unit_bytes + wave * tile_bytes + s * 64;
+    }
+    static __device__ __forceinline__ f32x4 mfma(const i32x4& a, const i32x4& b, const f32x4& c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    }
+    // filter_nd_th with ||b'||max = ||b||max: the rows are not rounded.  A query without a bound (E = +inf: a value that f16
+    // cannot hold) sends the group to the per-batch scan behind at once: the overflow word is raised here, by the first
+    // workgroup of the pass, and nothing of that query is written (what the sweep finds is not ranked once the word is set)
+    static __device__ __forceinline__ float threshold(const Params& p, int ip, int qg, bool herald) {
+        const float e = p.qbound[qg];
+        if (e < VS_INF) return filter_nd_th(ip, p.tau0[qg], p.qnorm[qg], e, p.qnp[qg], p.bnmax, p.fstats.bmax);
+        if (herald) sink_raise_overflow(p.sink);
+        return VS_INF;
+    }
+    static __device__ __forceinline__ RecheckNdF16 recheck(const Params& p, int ip) {
+        return RecheckNdF16{p.rows, p.bnorm, p.qfrag, p.qnorm, p.tau0, p.dim_h, ip, p.id_offset};
+    }
+    template <int CBW, bool IP>
+    static auto kernel() { return scan_nd_f16f_kernel<CBW, IP>; }
+};
 
 template <int CBW, bool IP>
-__global__ __launch_bounds__(kNdhfWaves * 64, 1) void scan_nd_f16f_kernel(const NdF16FilterParams p) {
-    constexpr int NW = kNdhfWaves;
-    constexpr int D = ndhf_depth(CBW);
-    constexpr int kSlot = ndhf_slot_bytes(CBW);
-    constexpr int kStepVmem = 1 + CBW;  // vector-memory instructions per wave and step
-    static_assert(D >= 3 && D * kSlot <= 160 * 1024, "the ring: one slot being read, one being filled, >= 1 in flight");
-    static_assert((D - 2) * kStepVmem <= 63, "vmcnt is a 6-bit count");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r = lane & 15, g = lane >> 4;
-    const int G = (int)gridDim.x, bx = (int)blockIdx.x;
-    const int units_total = (int)((p.n_rows + kNdfUnitRows - 1) / kNdfUnitRows);
-    const int T = (units_total - bx + G - 1) / G;  // units of this workgroup (G <= units_total: T >= 1)
-    const int S = p.slabs;
-    const int steps = T * S;
-    const int n_cb = 2 * p.n_batches;
-    const int cb0 = (int)blockIdx.y * NW * CBW;  // (cb0 < n_cb: the launcher's passes)
-
-    // per (h, lane): the hot test's threshold of query 16 cb + r (filter_nd_th with ||b'||max = ||b||max: the rows are not
-    // rounded); +inf for a dead block or a padding query.  A query without a bound (E = +inf: a value that f16 cannot
-    // hold) sends the group to the per-batch scan behind at once: the overflow word is raised here, by the first workgroup
-    // of the pass, and nothing of that query is written (what the sweep finds is not ranked once the word is set)
-    float th[CBW];
-#pragma unroll
-    for (int h = 0; h < CBW; ++h) {
-        const int cb = cb0 + wave + NW * h;
-        const int qrow = 16 * (cb & 1) + r;
-        th[h] = VS_INF;
-        if (cb < n_cb && qrow < p.nq_valid) {
-            const int qg = (cb >> 1) * kMaxBatch + qrow;
-            const float e = p.qbound[qg];
-            if (e < VS_INF) th[h] = filter_nd_th(IP ? 1 : 0, p.tau0[qg], p.qnorm[qg], e, p.qnp[qg], p.bnmax, p.fstats.bmax);
-            else if (bx == 0 && g == 0) sink_raise_overflow(p.sink);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the accesses above are the compiler's; the counted queue starts empty)
-
-    const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
-    const unsigned voff16 = (unsigned)lane * 16u, voff4 = (unsigned)lane * 4u;
-    const unsigned voff_row = (unsigned)(r * p.dim_h + 8 * g) * 2u;  // scan_nd_f16_kernel's voff: this lane's 16 bytes of a tile's segment
-    const int64_t unit_bytes = (int64_t)kNdfUnitRows * p.dim_h * 2, tile_bytes = (int64_t)16 * p.dim_h * 2;
-    const char* const rows = reinterpret_cast<const char*>(p.rows);
-    const char* qsrc[CBW];  // this wave's column blocks in the prepared queries (a block past the launch's: the last one)
-#pragma unroll
-    for (int h = 0; h < CBW; ++h) qsrc[h] = reinterpret_cast<const char*>(p.qh) + (int64_t)min(cb0 + wave + NW * h, n_cb - 1) * S * 1024;
-    // (an "s" operand must be in scalar registers whatever the compiler thinks of its divergence: every value here is wave-uniform)
-    auto uni = [](const char* ptr) __attribute__((always_inline)) -> const char* {
-        const unsigned long long v = (unsigned long long)ptr;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return reinterpret_cast<const char*>(((unsigned long long)hi << 32) | lo);
-    };
-    // step (n, s) of the workgroup into ring slot `slot`: kStepVmem instructions; M0 saved and restored in the statement
-    auto issue = [&](const int n, const int s, const int slot) __attribute__((always_inline)) {
-        const int64_t unit = (int64_t)bx + (int64_t)n * G;
-        const unsigned sbase = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(slot * kSlot));
-        unsigned keep;
-        if (wave < 4) {  // row tile `wave` of the unit, slab s: 16 rows x one 64-byte segment, straight from the stored rows
-            const char* src = uni(rows + unit * unit_bytes + wave * tile_bytes + s * 64);
-            const unsigned dst = sbase + (unsigned)wave * 1024u;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(voff_row), "s"(src), "s"(dst) : "memory");
-        } else {
-            const char* src = uni(reinterpret_cast<const char*>(p.bnorm + unit * kNdfUnitRows));
-            const unsigned dst = sbase + (unsigned)kNdhfNormOff;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(voff4), "s"(src), "s"(dst) : "memory");
-        }
-#pragma unroll
-        for (int h = 0; h < CBW; ++h) {
-            const char* src = uni(qsrc[h] + s * 1024);
-            const unsigned dst = sbase + (unsigned)(kNdhfBOff + (wave * CBW + h) * 1024);
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(voff16), "s"(src), "s"(dst) : "memory");
-        }
-    };
-
-    int4* wbuf = p.sink.wbuf + ((int64_t)((int)blockIdx.y * G + bx) * NW + wave) * p.sink.wcap;
-    int wbase = 0;  // wave-uniform fill of the private candidate buffer
-
-    // the issue cursor runs D - 1 steps ahead of the read cursor; past the end it stays on the last step (a slot nobody reads)
-    int ni = 0, si = 0;
-    auto advance_issue = [&]() __attribute__((always_inline)) {
-        if (ni * S + si + 1 < steps) {
-            if (++si == S) si = 0, ++ni;
-        }
-    };
-#pragma unroll
-    for (int j = 0; j < D - 1; ++j) {
-        issue(ni, si, j);
-        advance_issue();
-    }
-
-    f32x4 acc[4][CBW];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int h = 0; h < CBW; ++h) acc[t][h] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    int sl = 0, nc = 0, sc = 0;
-#pragma clang loop unroll(disable)
-    for (int j = 0; j < steps; ++j) {
-        // this wave's pieces of step j have landed; behind the barrier so have everyone's, and step j - 1's slot is free
-        wait_vm<(D - 2) * kStepVmem>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        issue(ni, si, sl == 0 ? D - 1 : sl - 1);
-        advance_issue();
-        const char* slot = smem + sl * kSlot;
-        i32x4 a[4], b[CBW];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) a[t] = *reinterpret_cast<const i32x4*>(slot + t * 1024 + lane * 16);
-#pragma unroll
-        for (int h = 0; h < CBW; ++h) b[h] = *reinterpret_cast<const i32x4*>(slot + kNdhfBOff + (wave * CBW + h) * 1024 + lane * 16);
-#pragma unroll
-        for (int h = 0; h < CBW; ++h)
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-                acc[t][h] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a[t]), __builtin_bit_cast(f16x8, b[h]), acc[t][h], 0, 0, 0);
-        if (sc == S - 1) {  // (workgroup-uniform) the unit's last slab: the threshold epilogue
-            const int row_u = (bx + nc * G) * kNdfUnitRows + 4 * g;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const f32x4 bn = *reinterpret_cast<const f32x4*>(slot + kNdhfNormOff + (16 * t + 4 * g) * 4);
-#pragma unroll
-                for (int h = 0; h < CBW; ++h) {
-                    f32x4 v;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] = IP ? acc[t][h][i] : fmaf(2.0f, acc[t][h][i], -bn[i]);
-                    const float vmax = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-                    if (__builtin_expect(__ballot(vmax > th[h]) != 0, 0)) {  // rare
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const int row = row_u + 16 * t + i;
-                            const bool pass = v[i] > th[h] && row < (int)p.n_rows;
-                            const unsigned long long mask = __ballot(pass);
-                            if (mask) {  // wave-uniform
-                                const int pos = wbase + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-                                // (query, value, id): the value is replaced by RecheckNdF16's
-                                if (pass && pos < p.sink.wcap)
-                                    wbuf[pos] = make_int4(16 * (cb0 + wave + NW * h) + r, __builtin_bit_cast(int, v[i]), row + p.id_offset, 0);
-                                wbase += __popcll(mask);
-                            }
-                        }
-                    }
-                    acc[t][h] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                }
-            }
-            sc = 0, ++nc;
-        } else {
-            ++sc;
-            // the step's chains have issued, so its fragments have arrived: the barrier behind which the slot is refilled
-            // follows the LDS reads
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int h = 0; h < CBW; ++h) asm volatile("" : "+v"(acc[t][h]));
-        }
-        sl = sl + 1 == D ? 0 : sl + 1;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // retire the tail prefetches before the wave ends
-    const RecheckNdF16 fix{p.rows, p.bnorm, p.qfrag, p.qnorm, p.tau0, p.dim_h, IP ? 1 : 0, p.id_offset};
-    int kept = sink_bin_wave<RecheckNdF16, true>(p.sink, ((int)blockIdx.y * G + bx) * NW + wave, wbase, lane, fix);
-    if (p.sink.stats && wbase > 0) {  // (wave-uniform) one atomic instruction: lane 0 adds the sweep's count, lane 1 the survivors
-#pragma unroll
-        for (int u = 32; u >= 1; u >>= 1) kept += __shfl_xor(kept, u);
-        if (lane < 2) atomicAdd(p.sink.stats + 2 + lane, (unsigned long long)(lane == 0 ? wbase : kept));
-    }
-}
-
-template <int CBW, bool IP>
-static hipError_t launch_ndhf_t(const NdF16FilterParams& p, int grid, int passes, hipStream_t s) {
-    constexpr int kLds = ndhf_depth(CBW) * ndhf_slot_bytes(CBW);
-    auto kfn = scan_nd_f16f_kernel<CBW, IP>;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3(grid, passes), dim3(kNdhfWaves * 64), kLds, s, p);
-    return hipGetLastError();
-}
+__global__ __launch_bounds__(kNdfWaves * 64, 1) void scan_nd_f16f_kernel(const NdF16FilterParams p) { ndf_sweep<NdfHalfRowsSrc, CBW, IP>(p); }
 
 hipError_t launch_scan_nd_f16f(const NdF16FilterParams& p, const NdFilterPlan& g, hipStream_t s) {
-    const int64_t units = (p.n_rows + kNdfUnitRows - 1) / kNdfUnitRows;
-    if (p.n_batches < 1 || p.n_batches > 32 || p.dim < 1 || p.dim > kNdMaxDim || p.dim_h != nd_dim_h(p.dim) || p.slabs != p.dim_h / 32 ||
-        g.grid < 1 || g.grid > units || g.passes < 1 || g.cbw < 1 || g.cbw > 4 || g.passes * kNdhfWaves * g.cbw < 2 * p.n_batches ||
-        (g.passes - 1) * kNdhfWaves * g.cbw >= 2 * p.n_batches || (int64_t)g.grid * g.passes > kSlotStride || p.n_rows > 0x7fffffff - 2 * kNdfUnitRows ||
-        p.nq_valid < 1 || p.nq_valid > kMaxBatch || !p.rows || !p.bnorm || !p.qh || !p.qfrag || !p.zero || p.sink.wcap < 1)
+    if (!ndf_sweep_args_ok(p, g) || p.dim_h != nd_dim_h(p.dim) || p.slabs != p.dim_h / 32 || p.nq_valid < 1 || p.nq_valid > kMaxBatch || !p.rows ||
+        !p.bnorm || p.sink.wcap < 1)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(ndf16_prep_kernel, dim3(p.n_batches), dim3(256), 0, s, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const bool ip = p.metric != 0;
-    switch (g.cbw) {
-    case 1: return ip ? launch_ndhf_t<1, true>(p, g.grid, g.passes, s) : launch_ndhf_t<1, false>(p, g.grid, g.passes, s);
-    case 2: return ip ? launch_ndhf_t<2, true>(p, g.grid, g.passes, s) : launch_ndhf_t<2, false>(p, g.grid, g.passes, s);
-    case 3: return ip ? launch_ndhf_t<3, true>(p, g.grid, g.passes, s) : launch_ndhf_t<3, false>(p, g.grid, g.passes, s);
-    default: return ip ? launch_ndhf_t<4, true>(p, g.grid, g.passes, s) : launch_ndhf_t<4, false>(p, g.grid, g.passes, s);
-    }
+    return launch_ndf_sweep<NdfHalfRowsSrc>(p, g, s);
 }
 
 }  // namespace vs

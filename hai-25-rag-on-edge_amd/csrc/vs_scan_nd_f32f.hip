@@ -4,33 +4,20 @@
 //                                 v_mfma_f32_16x16x32_bf16, and the shard constants of FilterStats.
 //   ndf_prep_kernel             : per launch group, the queries as bf16 B fragments in the matching k order, and per query
 //                                 ||q'|| and the error bound E (filter_bound_nd); clears the group's counters.
-//   scan_nd_f32f_kernel<CBW, IP>: ONE sweep over the image for up to 8 * CBW 16-query column blocks: a tiled product with a
-//                                 threshold epilogue.  What passes is recomputed from the fp32 rows by RecheckNd (scan_nd_kernel's
-//                                 chain, bit for bit) when the wave bins its buffer, so every id, distance bit and flag is
-//                                 decided as scan_nd_kernel decides it.
+//   scan_nd_f32f_kernel<CBW, IP>: ONE sweep over the image for up to 8 * CBW 16-query column blocks: ndf_sweep (vs_ndf_sweep.h,
+//                                 where the organisation is described) on NdfImageSrc.  What passes is recomputed from the
+//                                 fp32 rows by RecheckNd (scan_nd_kernel's chain, bit for bit) when the wave bins its buffer,
+//                                 so every id, distance bit and flag is decided as scan_nd_kernel decides it.
 //
 // Image layout.  dim32 = dim rounded up to 32 elements, S = dim32 / 32 slabs.  A unit is 64 rows (four 16-row tiles); its
 // image is S slabs of 4 KB, unit major:  img[((unit * S + s) * 4 + t) * 64 + lane][j], j < 8, lane = 16 g + r, holds
 // bf16(row 64 unit + 16 t + r, element 32 s + 8 g + j): the 16 bytes of lane (r, g) are its A operand of tile t for
 // K-slab s, so a slab is moved by four 1 KB LDS-DMA pieces and read back lane-linear (ds_read_b128 at 16 lane: no bank
 // conflict, no swizzle).  Rows past n_rows and elements past dim are zero; there is one spare unit of zero rows.
-// The prepared queries use the same k order: qbf[(cb * S + s) * 64 + lane][j] = bf16(Q[16 cb + r][32 s + 8 g + j]).
-//
-// Organisation.  Workgroup x of gridDim.x sweeps units x + n G; gridDim.y = passes, pass y serves column blocks
-// [64 y CBW / 8 ...): wave w owns column blocks cb0 + w + 8 h, h < CBW, and keeps their accumulators for the unit's four
-// row tiles (4 CBW f32x4) resident while K walks in slabs.  A step is one (unit, slab): every wave issues 1 + CBW LDS-DMA
-// pieces for step j + D - 1 -- waves 0..3 one of the slab's four row pieces, waves 4..7 the unit's 64 stored norms (256
-// bytes, the same piece four times), and every wave the CBW 1 KB B pieces of its own column blocks, which only it reads --
-// waits for its own pieces of step j by a constant vmcnt, passes one raw s_barrier (which publishes the row pieces of
-// step j and frees the slot of step j - 1), and feeds 4 CBW MFMAs from LDS.  The loop contains no other vector-memory
-// instruction than these pieces and the (rare) candidate stores, which only make the counted wait stricter.
-// Each unit of the image leaves HBM once per pass: ceil(n_cb / (8 CBW)) times per launch group, i.e. once up to 16
-// batches and twice from 17 to 32 (CBW <= 4: the accumulators, not LDS, set that limit).
+// The prepared queries use the same k order: qb16[(cb * S + s) * 64 + lane][j] = bf16(Q[16 cb + r][32 s + 8 g + j]).
 #include "vs_kernels.h"
 #include "vs_dev.h"
-#include "vs_sink.h"
-#include "vs_ring.h"
-#include <algorithm>
+#include "vs_ndf_sweep.h"
 
 namespace vs {
 
@@ -123,7 +110,7 @@ __global__ __launch_bounds__(256) void ndf_prep_kernel(const NdFilterParams p) {
     for (int i = batch * 256 + tid; i < p.zero_words; i += gridDim.x * 256) p.zero[i] = 0;
     const float* qb = p.q + (int64_t)batch * p.q_batch_stride;
     const int S = p.slabs, dim = p.dim;
-    uint4* out = reinterpret_cast<uint4*>(p.qbf) + (int64_t)batch * 2 * S * 64;
+    uint4* out = reinterpret_cast<uint4*>(p.qb16) + (int64_t)batch * 2 * S * 64;
     for (int e = tid; e < 2 * S * 64; e += 256) {
         const int lane = e & 63, s = (e >> 6) % S, h = (e >> 6) / S;
         const int qi = 16 * h + (lane & 15), k0 = 32 * s + 8 * (lane >> 4);
@@ -196,209 +183,43 @@ struct RecheckNd {
     }
 };
 
-constexpr int kNdfWaves = 8;
-constexpr int kNdfSlabBytes = kNdfUnitRows * 64;             // 4 KB: 64 rows x 32 bf16
-constexpr int kNdfNormOff = kNdfSlabBytes;                   // the unit's 64 stored norms behind the rows
-constexpr int kNdfBOff = kNdfSlabBytes + kNdfUnitRows * 4;   // the waves' B pieces behind those
-constexpr int ndf_slot_bytes(int cbw) { return kNdfBOff + kNdfWaves * cbw * 1024; }
-constexpr int ndf_depth(int cbw) { return std::min(8, (160 * 1024) / ndf_slot_bytes(cbw)); }  // slots of the ring
+template <int CBW, bool IP>
+__global__ __launch_bounds__(kNdfWaves * 64, 1) void scan_nd_f32f_kernel(const NdFilterParams p);
+
+// the image as the sweep's source of rows (vs_ndf_sweep.h)
+struct NdfImageSrc {
+    using Params = NdFilterParams;
+    const char* img;
+    int S;
+    unsigned voff;  // a slab's piece of a tile is lane-linear in the image
+    __device__ __forceinline__ NdfImageSrc(const Params& p, int lane)
+        : img(reinterpret_cast<const char*>(p.img)), S(p.slabs), voff((unsigned)lane * 16u) {}
+    __device__ __forceinline__ const char* row_piece(int64_t unit, int s, int wave) const {
+        return img + (unit * S + s) * kNdfSlabBytes + wave * 1024;
+    }
+    static __device__ __forceinline__ f32x4 mfma(const i32x4& a, const i32x4& b, const f32x4& c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    }
+    // filter_nd_th; a query outside the well-scaled range has E = +inf, which leaves the threshold at -inf: everything passes
+    static __device__ __forceinline__ float threshold(const Params& p, int ip, int qg, bool) {
+        return filter_nd_th(ip, p.tau0[qg], p.qnorm[qg], p.qbound[qg], p.qnp[qg], p.bnmax, p.fstats.bpmax);
+    }
+    static __device__ __forceinline__ RecheckNd recheck(const Params& p, int ip) {
+        return RecheckNd{p.base, p.bnorm, p.qfrag, p.qnorm, p.tau0, p.dim_p, ip, p.id_offset};
+    }
+    template <int CBW, bool IP>
+    static auto kernel() { return scan_nd_f32f_kernel<CBW, IP>; }
+};
 
 template <int CBW, bool IP>
-__global__ __launch_bounds__(kNdfWaves * 64, 1) void scan_nd_f32f_kernel(const NdFilterParams p) {
-    constexpr int NW = kNdfWaves;
-    constexpr int D = ndf_depth(CBW);
-    constexpr int kSlot = ndf_slot_bytes(CBW);
-    constexpr int kStepVmem = 1 + CBW;  // vector-memory instructions per wave and step
-    static_assert(D >= 3 && D * kSlot <= 160 * 1024, "the ring: one slot being read, one being filled, >= 1 in flight");
-    static_assert((D - 2) * kStepVmem <= 63, "vmcnt is a 6-bit count");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r = lane & 15, g = lane >> 4;
-    const int G = (int)gridDim.x, bx = (int)blockIdx.x;
-    const int units_total = (int)((p.n_rows + kNdfUnitRows - 1) / kNdfUnitRows);
-    const int T = (units_total - bx + G - 1) / G;  // units of this workgroup (G <= units_total: T >= 1)
-    const int S = p.slabs;
-    const int steps = T * S;
-    const int n_cb = 2 * p.n_batches;
-    const int cb0 = (int)blockIdx.y * NW * CBW;  // (cb0 < n_cb: the launcher's passes)
-
-    // per (h, lane): the hot test's threshold of query 16 cb + r (filter_nd_th); +inf for a dead block or a padding query
-    float th[CBW];
-#pragma unroll
-    for (int h = 0; h < CBW; ++h) {
-        const int cb = cb0 + wave + NW * h;
-        const int qrow = 16 * (cb & 1) + r;
-        th[h] = VS_INF;
-        if (cb < n_cb && qrow < p.nq_valid) {
-            const int qg = (cb >> 1) * kMaxBatch + qrow;
-            th[h] = filter_nd_th(IP ? 1 : 0, p.tau0[qg], p.qnorm[qg], p.qbound[qg], p.qnp[qg], p.bnmax, p.fstats.bpmax);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the loads above are the compiler's; the counted queue starts empty)
-
-    const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem);
-    const unsigned voff16 = (unsigned)lane * 16u, voff4 = (unsigned)lane * 4u;
-    const char* const img = reinterpret_cast<const char*>(p.img);
-    const char* qsrc[CBW];  // this wave's column blocks in the prepared queries (a block past the launch's: the last one)
-#pragma unroll
-    for (int h = 0; h < CBW; ++h) qsrc[h] = reinterpret_cast<const char*>(p.qbf) + (int64_t)min(cb0 + wave + NW * h, n_cb - 1) * S * 1024;
-    // (an "s" operand must be in scalar registers whatever the compiler thinks of its divergence: every value here is wave-uniform)
-    auto uni = [](const char* ptr) __attribute__((always_inline)) -> const char* {
-        const unsigned long long v = (unsigned long long)ptr;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return reinterpret_cast<const char*>(((unsigned long long)hi << 32) | lo);
-    };
-    // step (n, s) of the workgroup into ring slot `slot`: kStepVmem instructions; M0 saved and restored in the statement
-    auto issue = [&](const int n, const int s, const int slot) __attribute__((always_inline)) {
-        const int64_t unit = (int64_t)bx + (int64_t)n * G;
-        const unsigned sbase = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(slot * kSlot));
-        unsigned keep;
-        if (wave < 4) {
-            const char* src = uni(img + (unit * S + s) * kNdfSlabBytes + wave * 1024);
-            const unsigned dst = sbase + (unsigned)wave * 1024u;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(voff16), "s"(src), "s"(dst) : "memory");
-        } else {
-            const char* src = uni(reinterpret_cast<const char*>(p.bnorm + unit * kNdfUnitRows));
-            const unsigned dst = sbase + (unsigned)kNdfNormOff;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(voff4), "s"(src), "s"(dst) : "memory");
-        }
-#pragma unroll
-        for (int h = 0; h < CBW; ++h) {
-            const char* src = uni(qsrc[h] + s * 1024);
-            const unsigned dst = sbase + (unsigned)(kNdfBOff + (wave * CBW + h) * 1024);
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(voff16), "s"(src), "s"(dst) : "memory");
-        }
-    };
-
-    int4* wbuf = p.sink.wbuf + ((int64_t)((int)blockIdx.y * G + bx) * NW + wave) * p.sink.wcap;
-    int wbase = 0;  // wave-uniform fill of the private candidate buffer
-
-    // the issue cursor runs D - 1 steps ahead of the read cursor; past the end it stays on the last step (a slot nobody reads)
-    int ni = 0, si = 0;
-    auto advance_issue = [&]() __attribute__((always_inline)) {
-        if (ni * S + si + 1 < steps) {
-            if (++si == S) si = 0, ++ni;
-        }
-    };
-#pragma unroll
-    for (int j = 0; j < D - 1; ++j) {
-        issue(ni, si, j);
-        advance_issue();
-    }
-
-    f32x4 acc[4][CBW];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int h = 0; h < CBW; ++h) acc[t][h] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    int sl = 0, nc = 0, sc = 0;
-#pragma clang loop unroll(disable)
-    for (int j = 0; j < steps; ++j) {
-        // this wave's pieces of step j have landed; behind the barrier so have everyone's, and step j - 1's slot is free
-        wait_vm<(D - 2) * kStepVmem>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        issue(ni, si, sl == 0 ? D - 1 : sl - 1);
-        advance_issue();
-        const char* slot = smem + sl * kSlot;
-        i32x4 a[4], b[CBW];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) a[t] = *reinterpret_cast<const i32x4*>(slot + t * 1024 + lane * 16);
-#pragma unroll
-        for (int h = 0; h < CBW; ++h) b[h] = *reinterpret_cast<const i32x4*>(slot + kNdfBOff + (wave * CBW + h) * 1024 + lane * 16);
-#pragma unroll
-        for (int h = 0; h < CBW; ++h)
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-                acc[t][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a[t]), __builtin_bit_cast(bf16x8, b[h]), acc[t][h], 0, 0, 0);
-        if (sc == S - 1) {  // (workgroup-uniform) the unit's last slab: the threshold epilogue
-            const int row_u = (bx + nc * G) * kNdfUnitRows + 4 * g;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const f32x4 bn = *reinterpret_cast<const f32x4*>(slot + kNdfNormOff + (16 * t + 4 * g) * 4);
-#pragma unroll
-                for (int h = 0; h < CBW; ++h) {
-                    f32x4 v;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] = IP ? acc[t][h][i] : fmaf(2.0f, acc[t][h][i], -bn[i]);
-                    const float vmax = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-                    if (__builtin_expect(__ballot(vmax > th[h]) != 0, 0)) {  // rare: a few hundred rows per query per million
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const int row = row_u + 16 * t + i;
-                            const bool pass = v[i] > th[h] && row < (int)p.n_rows;
-                            const unsigned long long mask = __ballot(pass);
-                            if (mask) {  // wave-uniform
-                                const int pos = wbase + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-                                // (query, value, id): the value is replaced by RecheckNd's
-                                if (pass && pos < p.sink.wcap)
-                                    wbuf[pos] = make_int4(16 * (cb0 + wave + NW * h) + r, __builtin_bit_cast(int, v[i]), row + p.id_offset, 0);
-                                wbase += __popcll(mask);
-                            }
-                        }
-                    }
-                    acc[t][h] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                }
-            }
-            sc = 0, ++nc;
-        } else {
-            ++sc;
-            // the step's chains have issued, so its fragments have arrived: the barrier behind which the slot is refilled
-            // follows the LDS reads
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int h = 0; h < CBW; ++h) asm volatile("" : "+v"(acc[t][h]));
-        }
-        sl = sl + 1 == D ? 0 : sl + 1;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // retire the tail prefetches before the wave ends
-    const RecheckNd fix{p.base, p.bnorm, p.qfrag, p.qnorm, p.tau0, p.dim_p, IP ? 1 : 0, p.id_offset};
-    int kept = sink_bin_wave<RecheckNd, true>(p.sink, ((int)blockIdx.y * G + bx) * NW + wave, wbase, lane, fix);
-    if (p.sink.stats && wbase > 0) {  // (wave-uniform) one atomic instruction: lane 0 adds the sweep's count, lane 1 the survivors
-#pragma unroll
-        for (int u = 32; u >= 1; u >>= 1) kept += __shfl_xor(kept, u);
-        if (lane < 2) atomicAdd(p.sink.stats + 2 + lane, (unsigned long long)(lane == 0 ? wbase : kept));
-    }
-}
-
-template <int CBW, bool IP>
-static hipError_t launch_ndf_t(const NdFilterParams& p, int grid, int passes, hipStream_t s) {
-    constexpr int kLds = ndf_depth(CBW) * ndf_slot_bytes(CBW);
-    auto kfn = scan_nd_f32f_kernel<CBW, IP>;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3(grid, passes), dim3(kNdfWaves * 64), kLds, s, p);
-    return hipGetLastError();
-}
+__global__ __launch_bounds__(kNdfWaves * 64, 1) void scan_nd_f32f_kernel(const NdFilterParams p) { ndf_sweep<NdfImageSrc, CBW, IP>(p); }
 
 hipError_t launch_scan_nd_f32f(const NdFilterParams& p, const NdFilterPlan& g, hipStream_t s) {
-    const int64_t units = (p.n_rows + kNdfUnitRows - 1) / kNdfUnitRows;
-    if (p.n_batches < 1 || p.n_batches > 32 || p.dim < 1 || p.dim > kNdMaxDim || p.dim_p != nd_dim_p(p.dim) || p.slabs != ndf_slabs(p.dim_p) ||
-        g.grid < 1 || g.grid > units || g.passes < 1 || g.cbw < 1 || g.cbw > 4 || g.passes * kNdfWaves * g.cbw < 2 * p.n_batches ||
-        (g.passes - 1) * kNdfWaves * g.cbw >= 2 * p.n_batches || (int64_t)g.grid * g.passes > kSlotStride || p.n_rows > 0x7fffffff - 2 * kNdfUnitRows ||
-        !p.img || !p.qbf || !p.qfrag || !p.zero)
-        return hipErrorInvalidValue;
+    if (!ndf_sweep_args_ok(p, g) || p.dim_p != nd_dim_p(p.dim) || p.slabs != ndf_slabs(p.dim_p) || !p.img) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ndf_prep_kernel, dim3(p.n_batches), dim3(256), 0, s, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const bool ip = p.metric != 0;
-    switch (g.cbw) {
-    case 1: return ip ? launch_ndf_t<1, true>(p, g.grid, g.passes, s) : launch_ndf_t<1, false>(p, g.grid, g.passes, s);
-    case 2: return ip ? launch_ndf_t<2, true>(p, g.grid, g.passes, s) : launch_ndf_t<2, false>(p, g.grid, g.passes, s);
-    case 3: return ip ? launch_ndf_t<3, true>(p, g.grid, g.passes, s) : launch_ndf_t<3, false>(p, g.grid, g.passes, s);
-    default: return ip ? launch_ndf_t<4, true>(p, g.grid, g.passes, s) : launch_ndf_t<4, false>(p, g.grid, g.passes, s);
-    }
+    return launch_ndf_sweep<NdfImageSrc>(p, g, s);
 }
 
 }  // namespace vs

@@ -102,6 +102,28 @@ def test_inner_product(gpu_pkg, monkeypatch):
         assert idx.filter_stats()[0] == 1
 
 
+@functools.lru_cache(maxsize=None)
+def _width_lists(metric):
+    """_data("gauss", 48) with, under inner product, the lists of the 85 queries that 17 batches of 5 use"""
+    base, q, ri, rd = _data("gauss", 48)
+    if metric == "ip":
+        ri, rd = _ip_lists(q[:85], base.astype(np.float32), 16)
+        ri.setflags(write=False), rd.setflags(write=False)
+    return base, q, ri, rd
+
+
+@pytest.mark.parametrize("nb", [6, 16, 17])
+@pytest.mark.parametrize("metric", ["l2", "ip"])
+def test_every_sweep_width_and_two_passes(gpu_pkg, monkeypatch, metric, nb):
+    """the sweep at 2 and 4 column blocks per wave (6 and 16 batches), and at 3 over two passes whose last block is partly
+    dead (17 batches: 34 column blocks on 2 x 24); SHAPES runs 1 and 3 in one pass only"""
+    monkeypatch.setenv("VSEARCH_ND_F16_FILTER", "2")
+    base, q, ri, rd = _width_lists(metric)
+    with gpu_pkg.BruteForceIndex.from_f16(base, metric=gpu_pkg.METRIC_IP if metric == "ip" else gpu_pkg.METRIC_L2) as idx:
+        _check(idx, q, ri, rd, nb, 5, 15, (metric, nb))
+        assert idx.filter_stats()[:2] == (1, 0)  # the sweep, not the fallback, produced the result
+
+
 @pytest.mark.parametrize("how", ["all rows equal", "a query value above 65504"])
 def test_overflow_takes_the_fallback(gpu_pkg, monkeypatch, how):
     monkeypatch.setenv("VSEARCH_ND_F16_FILTER", "2")
